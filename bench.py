@@ -6,14 +6,28 @@ points / scalars, inputs resident in HBM. One "step" = one complete MSM over the
 slice (weak scaling: with N ranks the job is one N*2^20-point MSM whose per-rank partial points are
 all-gathered over RCCL and summed on every rank -- SURVEY.md 8e).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload msm_g1_2p20|msm_g1_2pXX|prove_2pXX|merkle_<leaves>] [--no-also]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload msm_g1_2p20|msm_g1_2pXX|prove_2pXX|merkle_<leaves>]
+                  [--full [--no-also] [--no-cpu-baseline]] [--dump-outputs DIR]
 
-Prints ONE JSON line on rank 0. BASELINE.json's metric is "Groth16 proofs/sec + G1-MSM pts/s at 2^20 / 2^26", so
-with N = 1 and the default workload the same line carries, under "also", the other shapes of that metric measured
-in the same process: the 2^26 MSM, the 2^20 MSM in fixed-base form, and full proves at the layer_one(2 sigs)
-2^21 shape, the layer_two(2, 12) 2^25 shape, the synthetic layer_one(128 sigs) 2^26 shape and the layer_three(2)
-2^26 / 13-public shape (prove_2p26_l3) -- each with its own step count, roofline object and correctness check (pi_c
-included). With --gpus N > 1 the default workload is ONE 2^26 proof over the N GPUs (strong scaling). `value` is always the headline workload alone.
+Prints ONE JSON line on rank 0. A plain run does only what the headline needs: set up, warm up, time the K steps
+(`ms_per_step` = wall milliseconds of one timed step), write the outputs if asked, print the line.
+
+--full adds everything else, in the same process: the correctness check of what was timed (known discrete log; pi_c
+by the quotient identity), the per-kernel / roofline figures that take runs of their own (solo MSMs, serialised
+proofs), the CPU baselines and, with the default workload, the rest of BASELINE.json's metric ("Groth16 proofs/sec +
+G1-MSM pts/s at 2^20 / 2^26"): with N = 1 the line carries, under "also", the 2^26 MSM, the 2^20 MSM in fixed-base
+form, and full proves at the layer_one(2 sigs) 2^21 shape, the layer_two(2, 12) 2^25 shape, the synthetic
+layer_one(128 sigs) 2^26 shape and the layer_three(2) 2^26 / 13-public shape (prove_2p26_l3) -- each with its own
+step count, roofline object and correctness check (pi_c included) -- and the `curve` / `curve_weak` objects. With
+--gpus N > 1 the default workload is ONE 2^26 proof over the N GPUs (strong scaling). `value` is always the headline
+workload alone.
+
+--dump-outputs DIR writes (rank 0) what the headline's last timed step returned, as DIR/<name>.npy in float64: every
+256-bit field element (a coordinate in the wire format -- affine, Montgomery form -- or a hash) is one row of sixteen
+16-bit limbs, least significant first, so the values are exact. The inputs are seeded: the same arguments give the
+same inputs in every run. msm_*: msm_g1_point (2 x 16: x, y); prove_*: proof_points (8 x 16: pi_a x, y; pi_b x.c0,
+x.c1, y.c0, y.c1; pi_c x, y); merkle_*: merkle_root (1 x 16) and merkle_leaves_sample (the first min(n, 2^16)
+leaf hashes).
 """
 import argparse
 import json
@@ -61,6 +75,26 @@ def oracle_g2(k):
 
 class BenchError(Exception):
     """A correctness check of something that was timed failed."""
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def field_rows(raw):
+    """Concatenated 32-byte little-endian field elements -> float64 [n, 16] of 16-bit limbs (exact)."""
+    import numpy as np
+    return np.frombuffer(bytes(raw), dtype="<u2").astype(np.float64).reshape(-1, 16)
+
+
+def write_outputs(directory, outputs):
+    """--dump-outputs: one DIR/<name>.npy per array, at most DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    total = sum(a.nbytes for a in outputs.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: outputs of %d bytes exceed the %d-byte dump limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(directory, name + ".npy"), arr)
 
 
 def pmc_traffic(workload, kernel_substr):
@@ -180,8 +214,10 @@ class Env:
 
 
 # ---------------------------------------------------------------------------------------------------------------
-def msm_leg(env, logn, steps, warmup, inflight, fixed_base=False, cpu_baseline=False):
-    """G1 MSM over 2^logn points per rank, `inflight` MSMs kept in flight on separate lanes. -> line dict."""
+def msm_leg(env, logn, steps, warmup, inflight, fixed_base=False, cpu_baseline=False, full=True, outputs=None):
+    """G1 MSM over 2^logn points per rank, `inflight` MSMs kept in flight on separate lanes. -> line dict.
+    full=False: the timed steps alone (no solo MSMs, no check, no roofline, no CPU baseline). outputs: dict to receive
+    the last result."""
     import numpy as np
     import torch
     from collections import deque
@@ -247,23 +283,26 @@ def msm_leg(env, logn, steps, warmup, inflight, fixed_base=False, cpu_baseline=F
         # the dominant kernel ALONE (nothing else in flight on the chip): three more MSMs, one at a time, after the
         # timed region; the roofline fractions below use this duration, never an overlapped one
         solo_k, solo_d = 0.0, 0.0
-        for _ in range(3):
+        for _ in range(3 if full else 0):
             _, k1, k0 = msm_on(0)
             solo_k += k1 / 3
             solo_d += k0 / 3
     finally:
         pool.shutdown()
+    if outputs is not None:
+        outputs["msm_g1_point"] = field_rows(result)
 
     # ---- correctness of what was timed (outside the timed region): known-dlog check
-    s0, s1 = dlog_sums(limbs, i0)
-    d_loc = (a * s0 + b * s1) % R_MOD
-    if env.multi:
-        parts = [None] * env.world
-        dist.all_gather_object(parts, d_loc)
-        d_all = sum(parts) % R_MOD
-    else:
-        d_all = d_loc
-    env.agree(result == oracle_g1(d_all), "MSM result failed the known-dlog check")
+    if full:
+        s0, s1 = dlog_sums(limbs, i0)
+        d_loc = (a * s0 + b * s1) % R_MOD
+        if env.multi:
+            parts = [None] * env.world
+            dist.all_gather_object(parts, d_loc)
+            d_all = sum(parts) % R_MOD
+        else:
+            d_all = d_loc
+        env.agree(result == oracle_g1(d_all), "MSM result failed the known-dlog check")
 
     line = None
     if env.rank == 0:
@@ -272,11 +311,6 @@ def msm_leg(env, logn, steps, warmup, inflight, fixed_base=False, cpu_baseline=F
         else:
             c_win = int(os.environ.get("ZKPOA_MSM_C") or classic_window(n_local))
             windows, table_bytes = (254 + c_win - 1) // c_win, 0
-        adds = n_local * windows
-        achieved = G1_MSM_BYTES_PER_POINT * n_local / (solo_k * 1e-3) / 1e9
-        gadds = adds / (solo_k * 1e-3) / 1e9
-        wl = "msm_g1_2p%d" % logn
-        traffic, tsrc = pmc_traffic(wl + ("_fixed_base" if fixed_base else ""), "msm_accum0_kernel")
         line = {
             "metric": "G1-MSM throughput", "value": n_local * env.world * steps / elapsed, "unit": "pts/s",
             "n_gpus": env.world, "steps": steps, "warmup": warmup,
@@ -293,21 +327,29 @@ def msm_leg(env, logn, steps, warmup, inflight, fixed_base=False, cpu_baseline=F
                                 "in one bucket set" % (table_bytes / 1e9)) if fixed_base else
                                "classic: arbitrary bases, nothing precomputed",
                        "checked": "known discrete log of the result (O(n) field arithmetic; the expected point from the "
-                                  "oracle's scalar multiplication)"},
-            "roofline": {"bound": "hbm", "kernel": "msm_accum0_kernel<Fq> (bucket accumulation)",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": tsrc,
-                         "kernel_ms": solo_k, "kernel_ms_overlapped": kernel_ms / steps,
-                         "msm_device_ms_solo": solo_d, "msm_device_ms_overlapped": msm_dev_ms / steps,
-                         "valu": {"unit": "G mixed additions/s", "achieved": gadds, "peak": VALU_PEAK_GADDS,
-                                  "frac": gadds / VALU_PEAK_GADDS, "additions_per_launch": adds, "window_bits": c_win,
-                                  "windows": windows},
-                         "note": "achieved = 96 B/point x points per launch / kernel_ms, kernel_ms = the accumulation "
-                                 "kernel alone on the chip (HIP events on its stream, 3 launches after the timed "
-                                 "region; kernel_ms <= ms_per_step). The kernel is integer-VALU-bound (v_mad_u64_u32), "
-                                 "not HBM-bound: `valu` is the bound that binds (DESIGN.md section 4)"},
+                                  "oracle's scalar multiplication)" if full else
+                                  "not in a plain run (--full checks the known discrete log)"},
         }
-        if cpu_baseline:
+        if full:
+            adds = n_local * windows
+            achieved = G1_MSM_BYTES_PER_POINT * n_local / (solo_k * 1e-3) / 1e9
+            gadds = adds / (solo_k * 1e-3) / 1e9
+            wl = "msm_g1_2p%d" % logn
+            traffic, tsrc = pmc_traffic(wl + ("_fixed_base" if fixed_base else ""), "msm_accum0_kernel")
+            line["roofline"] = {
+                "bound": "hbm", "kernel": "msm_accum0_kernel<Fq> (bucket accumulation)",
+                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": tsrc,
+                "kernel_ms": solo_k, "kernel_ms_overlapped": kernel_ms / steps,
+                "msm_device_ms_solo": solo_d, "msm_device_ms_overlapped": msm_dev_ms / steps,
+                "valu": {"unit": "G mixed additions/s", "achieved": gadds, "peak": VALU_PEAK_GADDS,
+                         "frac": gadds / VALU_PEAK_GADDS, "additions_per_launch": adds, "window_bits": c_win,
+                         "windows": windows},
+                "note": "achieved = 96 B/point x points per launch / kernel_ms, kernel_ms = the accumulation "
+                        "kernel alone on the chip (HIP events on its stream, 3 launches after the timed "
+                        "region; kernel_ms <= ms_per_step). The kernel is integer-VALU-bound (v_mad_u64_u32), "
+                        "not HBM-bound: `valu` is the bound that binds (DESIGN.md section 4)"}
+        if cpu_baseline and full:
             line["cpu_baseline"] = cpu_msm_baseline(env, d_bases, limbs, logn)
     if table is not None:
         table.close()
@@ -448,9 +490,10 @@ def cpu_prove_baseline(env, circ, gpu_points):
             "seconds": tcpu}
 
 
-def prove_leg(env, k, steps, warmup, precompute=True, cpu_baseline=False, serial=False):
+def prove_leg(env, k, steps, warmup, precompute=True, cpu_baseline=False, serial=False, full=True, outputs=None):
     """Full Groth16 prove against a key + witness resident in HBM. N>1: the proof's five MSMs are sharded
-    over the ranks (BASELINE.json configs[3..4]); the H-scalar chain is split or replicated."""
+    over the ranks (BASELINE.json configs[3..4]); the H-scalar chain is split or replicated.
+    full=False: the timed proofs alone (no serialised proofs, no checks). outputs: dict to receive the last proof."""
     import torch
     from zkpoa_amd import sharding
     from zkpoa_amd.synthetic import SyntheticCircuit
@@ -516,7 +559,9 @@ def prove_leg(env, k, steps, warmup, precompute=True, cpu_baseline=False, serial
         # ---- every stage ALONE (nothing else on the chip): two proofs with the stages serialised. Their sum against
         # the overlapped wall time says how much of a proof is arithmetic and how much is scheduling.
         solo = None
-        if world == 1:
+        if outputs is not None:
+            outputs["proof_points"] = field_rows(pts)
+        if world == 1 and full:
             ctx.set_option("prove_serial", 1)
             proofs_run += 2
             try:
@@ -540,21 +585,23 @@ def prove_leg(env, k, steps, warmup, precompute=True, cpu_baseline=False, serial
         # N > 1: every rank's H scalars (its cyclic shard after the split chain, its index range of the replicated
         # chain -- what its H MSM actually consumed) are gathered and checked on rank 0, so pi_c is covered on the
         # real multi-process path too.
-        from oracle import c_oracle as co
-        P = gather_h_scalars(env, circ, split)
-        ok, tq, threads = True, 0.0, min(32, host_cores())
-        if rank == 0:
-            zpt = random.Random(0xC0FFEE + k).randrange(R_MOD)
-            tq = time.perf_counter()
-            ok = co.quotient_check(circ.coeff_section(), circ.w_limbs, m, k, P, zpt, threads)
-            tq = time.perf_counter() - tq
-            ea, eb, ec = circ.expected_dlogs(0, 0, P)      # exponents in Fr; the group elements come from the oracle
-            ok = ok and pts[0:64] == oracle_g1(ea) and pts[64:192] == oracle_g2(eb) and pts[192:256] == oracle_g1(ec)
-        checked = ("pi_a, pi_b, pi_c by known discrete log (expected points from the oracle's scalar multiplication); the 2^%d H scalars%s by the oracle's quotient identity at a "
-                   "random point (%.1f s on %d host threads)"
-                   % (k, " (gathered from the %d ranks)" % world if world > 1 else "", tq, threads))
-        env.agree(ok, "proof failed the known-dlog / quotient-identity check")
-        cpu = cpu_prove_baseline(env, circ, pts) if (cpu_baseline and world == 1) else None
+        checked, cpu = "not in a plain run (--full checks pi_a, pi_b, pi_c and the H scalars)", None
+        if full:
+            from oracle import c_oracle as co
+            P = gather_h_scalars(env, circ, split)
+            ok, tq, threads = True, 0.0, min(32, host_cores())
+            if rank == 0:
+                zpt = random.Random(0xC0FFEE + k).randrange(R_MOD)
+                tq = time.perf_counter()
+                ok = co.quotient_check(circ.coeff_section(), circ.w_limbs, m, k, P, zpt, threads)
+                tq = time.perf_counter() - tq
+                ea, eb, ec = circ.expected_dlogs(0, 0, P)      # exponents in Fr; the group elements come from the oracle
+                ok = ok and pts[0:64] == oracle_g1(ea) and pts[64:192] == oracle_g2(eb) and pts[192:256] == oracle_g1(ec)
+            checked = ("pi_a, pi_b, pi_c by known discrete log (expected points from the oracle's scalar multiplication); the 2^%d H scalars%s by the oracle's quotient identity at a "
+                       "random point (%.1f s on %d host threads)"
+                       % (k, " (gathered from the %d ranks)" % world if world > 1 else "", tq, threads))
+            env.agree(ok, "proof failed the known-dlog / quotient-identity check")
+            cpu = cpu_prove_baseline(env, circ, pts) if (cpu_baseline and world == 1) else None
     except BaseException:
         circ.close()
         raise
@@ -629,9 +676,11 @@ POSEIDON_MAC_PAIRS = 8 * (3 * (2 * 108 + 136) + 3 * 264) + 2 * 200 + 57 * ((2 * 
 POSEIDON_MODMULS = POSEIDON_MAC_PAIRS / 136.0   # 486.8 (r03: 607 products, every one with its own reduction)
 
 
-def merkle_leg(env, n_leaves, steps, warmup, cpu_baseline=True):
+def merkle_leg(env, n_leaves, steps, warmup, cpu_baseline=True, full=True, outputs=None):
     """The anonymity-set Poseidon Merkle tree (scripts/merkle_tree.rs): n (address, balance) pairs
-    resident in HBM -> all levels of the tree. One step = one complete tree."""
+    resident in HBM -> all levels of the tree. One step = one complete tree.
+    full=False: the timed trees alone (no check, no CPU baseline). outputs: dict to receive the last tree's root and
+    first leaf hashes."""
     import numpy as np
     import torch
     ctx = env.ctx
@@ -666,18 +715,22 @@ def merkle_leg(env, n_leaves, steps, warmup, cpu_baseline=True):
         dev_ms += ms
     env.sync()
     elapsed = time.perf_counter() - t0
+    if outputs is not None:
+        outputs["merkle_root"] = field_rows(tree.root().to_bytes(32, "little"))
+        outputs["merkle_leaves_sample"] = field_rows(tree.leaves(0, min(n_leaves, 1 << 16)))
     # correctness of what was timed: the root folds from a sampled leaf through its path with the CPU oracle's hash,
     # and a 2^12-leaf prefix tree equals the oracle's tree
-    from oracle import c_oracle as co
-    root = tree.root()
     ok = True
-    for idx in (0, n_leaves - 1, n_leaves // 3):
-        elems, bits = tree.path(idx)
-        node = co.poseidon2(a[idx].tobytes(), b[idx].tobytes(), 1)
-        for e, bit in zip(elems, bits):
-            eb = int(e).to_bytes(32, "little")
-            node = co.poseidon2(eb, node, 1) if bit else co.poseidon2(node, eb, 1)
-        ok = ok and int.from_bytes(node, "little") == root
+    if full:
+        from oracle import c_oracle as co
+        root = tree.root()
+        for idx in (0, n_leaves - 1, n_leaves // 3):
+            elems, bits = tree.path(idx)
+            node = co.poseidon2(a[idx].tobytes(), b[idx].tobytes(), 1)
+            for e, bit in zip(elems, bits):
+                eb = int(e).to_bytes(32, "little")
+                node = co.poseidon2(eb, node, 1) if bit else co.poseidon2(node, eb, 1)
+            ok = ok and int.from_bytes(node, "little") == root
     tree.close()
     env.agree(ok, "Merkle root does not fold from sampled leaves with the oracle's Poseidon")
     sec = elapsed / steps
@@ -689,7 +742,8 @@ def merkle_leg(env, n_leaves, steps, warmup, cpu_baseline=True):
         "config": {"workload": "Poseidon(2) Merkle tree of %d (address, balance) leaves padded to 2^%d (scripts/merkle_tree.rs; "
                                "its header quotes 2.5 hours for a 10 M set on the CPU), inputs resident in HBM" % (n_leaves, k),
                    "hashes_per_tree": hashes,
-                   "checked": "root folded from 3 sampled leaves through their paths with the CPU oracle's Poseidon"},
+                   "checked": "root folded from 3 sampled leaves through their paths with the CPU oracle's Poseidon"
+                              if full else "not in a plain run (--full folds the root from sampled leaves)"},
         "roofline": {"bound": "hbm", "kernel": "poseidon2_kernel (all levels of one tree)",
                      "achieved": 96.0 * hashes / kernel_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": 96.0 * hashes / kernel_s / 1e9 / HBM_PEAK_GBS, "traffic": None, "kernel_ms": kernel_s * 1e3,
@@ -700,7 +754,7 @@ def merkle_leg(env, n_leaves, steps, warmup, cpu_baseline=True):
                              "Montgomery products' worth (sums of products share one reduction): integer-VALU-bound"
                              % (POSEIDON_MAC_PAIRS, POSEIDON_MODMULS)},
     }
-    if cpu_baseline:
+    if cpu_baseline and full:
         cores = host_cores()
         ns = 1 << 16
         tc = time.perf_counter()
@@ -723,8 +777,13 @@ def main():
     ap.add_argument("--workload", default=None,
                     help="default: msm_g1_2p20 with --gpus 1 (BASELINE.json configs[1]); prove_2p26 with --gpus N > 1 "
                          "(configs[4]: ONE synthetic layer_one 2^26 proof sharded over the N GPUs, strong scaling)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="headline workload only (no 'also' legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also check what was timed and add the roofline figures, the CPU baselines and, with the "
+                         "default workload, the 'also' legs and curves (a plain run times the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="--full: headline workload only (no 'also' legs)")
     ap.add_argument("--fixed-base", action="store_true", help="msm workloads: fixed-base form (precomputed table)")
     ap.add_argument("--no-precompute", action="store_true", help="prove workloads: no fixed-base tables")
     ap.add_argument("--replicated-chain", action="store_true",
@@ -784,26 +843,32 @@ def main():
             env.ctx.set_option("msm_c", int(os.environ["ZKPOA_MSM_C"]))
         if os.environ.get("ZKPOA_MSM_K0"):       # experiments only: force the level-0 piece length
             env.ctx.set_option("msm_k0", int(os.environ["ZKPOA_MSM_K0"]))
+        full = args.full
+        outputs = {} if (args.dump_outputs and rank == 0) else None
         if args.workload.startswith("prove_2p"):
             line = prove_leg(env, args.workload[len("prove_2p"):], args.steps, args.warmup,
-                             precompute=not args.no_precompute, serial=args.serial,
+                             precompute=not args.no_precompute, serial=args.serial, full=full, outputs=outputs,
                              cpu_baseline=(world == 1 and not args.no_cpu_baseline and args.workload == "prove_2p21"))
         elif args.workload.startswith("merkle_"):
             spec = args.workload[len("merkle_"):]            # merkle_10000000, merkle_1e7, merkle_10M, merkle_64k
             mult = {"k": 10**3, "K": 10**3, "M": 10**6}.get(spec[-1:], 1)
-            line = merkle_leg(env, int(float(spec[:-1] if mult > 1 else spec) * mult), args.steps, args.warmup)
+            line = merkle_leg(env, int(float(spec[:-1] if mult > 1 else spec) * mult), args.steps, args.warmup,
+                              full=full, outputs=outputs)
         elif args.workload.startswith("msm_g1_2p"):
             line = msm_leg(env, int(args.workload[len("msm_g1_2p"):]), args.steps, args.warmup, args.inflight,
-                           fixed_base=args.fixed_base, cpu_baseline=(world == 1 and not args.no_cpu_baseline))
+                           fixed_base=args.fixed_base, cpu_baseline=(world == 1 and not args.no_cpu_baseline),
+                           full=full, outputs=outputs)
         else:
             raise SystemExit("unknown workload " + args.workload)
+        if outputs is not None:
+            write_outputs(args.dump_outputs, outputs)
         # ---- the rest of BASELINE.json's metric, same process, N = 1 only (bounded: about two minutes in total)
-        if world == 1 and not force_dist and not args.no_also and default_workload and small:
+        if full and world == 1 and not force_dist and not args.no_also and default_workload and small:
             leg = prove_leg(env, strong_wl[len("prove_2p"):], args.steps, args.warmup)
             entry = {"workload": strong_wl}
             entry.update({kk: leg[kk] for kk in ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "config", "roofline")})
             line["also"] = [entry]
-        elif world == 1 and not force_dist and not args.no_also and args.workload == "msm_g1_2p20" and not args.fixed_base:
+        elif full and world == 1 and not force_dist and not args.no_also and args.workload == "msm_g1_2p20" and not args.fixed_base:
             also = []
             for name, fn in (
                     ("msm_g1_2p20_fixed_base", lambda: msm_leg(env, 20, args.steps, args.warmup, args.inflight, fixed_base=True)),
@@ -824,7 +889,7 @@ def main():
             line["also"] = also
         # N > 1 with the driver's command line: the headline is the north-star's strong-scaling proof; the weak-scaling
         # MSM of BASELINE.json configs[1] (2^20 points per GPU, all-gather of the partial points) rides along
-        if world > 1 and default_workload and not args.no_also:
+        if full and world > 1 and default_workload and not args.no_also:
             t0 = time.perf_counter()
             leg = msm_leg(env, weak_log, args.steps, args.warmup, args.inflight)
             if rank == 0:
@@ -833,7 +898,7 @@ def main():
                                                       "config", "roofline") if kk in leg})
                 entry["leg_seconds"] = time.perf_counter() - t0
                 line["also"] = [entry]
-        if rank == 0 and default_workload:
+        if full and rank == 0 and default_workload:
             # The two curves of BASELINE.json's metric under the SAME keys at every N, so that a plot of `curve.value`
             # (or `curve_weak.value`) over N never mixes metrics: `value` is the headline of this N (N = 1: configs[1],
             # the 2^20 MSM; N > 1: the north-star's one 2^26 proof over N GPUs), the curves are N-independent.

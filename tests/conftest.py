@@ -34,6 +34,23 @@ def ctx(zk):
     c.close()
 
 
+@pytest.fixture
+def sock_dir(tmp_path):
+    """A directory for the resident prover's Unix socket (ZKPOA_SERVER=<path>). A socket path must fit sun_path (108
+    bytes with its NUL): tmp_path when it leaves room for the name, else a short private directory under /tmp."""
+    if len(str(tmp_path)) <= 80:
+        yield tmp_path
+        return
+    import pathlib
+    import shutil
+    import tempfile
+    d = tempfile.mkdtemp(prefix="zkpoa-test-", dir="/tmp")
+    try:
+        yield pathlib.Path(d)
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
 @pytest.fixture(scope="session")
 def vectors():
     with open(os.path.join(GOLDEN, "gen", "vectors.json")) as f:

@@ -125,7 +125,7 @@ def test_product_does_not_reference_oracle():
     assert bad == []
 
 
-def test_prover_server_lifecycle_without_gpu(zk, tmp_path):
+def test_prover_server_lifecycle_without_gpu(zk, tmp_path, sock_dir):
     """Server mode of the CLI on a box without a GPU: the resident process starts, answers with the library's
     loud "no HIP device" failure (exit 1, no outputs), and stops on request. On a GPU box the same sequence
     is the parity test tests/test_gpu_prove.py::test_prover_cli_server_mode."""
@@ -137,7 +137,7 @@ def test_prover_server_lifecycle_without_gpu(zk, tmp_path):
     g = golden_case("n8")
     (tmp_path / "c.zkey").write_bytes(g["circuit.zkey"])
     (tmp_path / "w.wtns").write_bytes(g["witness.wtns"])
-    sock = str(tmp_path / "p.sock")
+    sock = str(sock_dir / "p.sock")
     env = dict(os.environ, ZKPOA_SERVER=sock, ZKPOA_SERVER_IDLE_S="30")
     try:
         rc = subprocess.run([zk.PROVER_BIN, "c.zkey", "w.wtns", "proof.json", "public.json"], env=env, cwd=tmp_path,
@@ -161,7 +161,7 @@ def test_prover_server_lifecycle_without_gpu(zk, tmp_path):
     assert not os.path.exists(sock)
 
 
-def test_prover_server_failure_paths_without_gpu(zk, tmp_path):
+def test_prover_server_failure_paths_without_gpu(zk, tmp_path, sock_dir):
     """(1) a server that dies with a request in hand does not fail the call -- the client proves in its own
     process (here: reaches the library, which has no GPU on this box); (2) a client that connects and says nothing
     does not hold the single-threaded server. On a GPU box tests/test_gpu_prove.py checks that (1) yields a proof."""
@@ -176,13 +176,13 @@ def test_prover_server_failure_paths_without_gpu(zk, tmp_path):
     (tmp_path / "w.wtns").write_bytes(g["witness.wtns"])
     argv = [zk.PROVER_BIN, "c.zkey", "w.wtns", "proof.json", "public.json"]
     # (1) the server exits on receipt of the request
-    sock = str(tmp_path / "crash.sock")
+    sock = str(sock_dir / "crash.sock")
     env = dict(os.environ, ZKPOA_SERVER=sock, ZKPOA_SERVER_IDLE_S="30", ZKPOA_SERVER_TEST_CRASH="1")
     rc = subprocess.run(argv, env=env, cwd=tmp_path, capture_output=True, text=True, timeout=120)
     assert "went away without answering; proving in-process" in rc.stderr
     assert rc.returncode == 1 and "no HIP device" in rc.stderr       # the in-process attempt ran (and has no GPU here)
     # (2) a silent connection is dropped after the receive timeout and the next request is served
-    sock = str(tmp_path / "quiet.sock")
+    sock = str(sock_dir / "quiet.sock")
     env = dict(os.environ, ZKPOA_SERVER=sock, ZKPOA_SERVER_IDLE_S="30", ZKPOA_SERVER_RCV_TIMEOUT_S="1")
     # (requests that fail on their INPUT -- a missing witness -- so that the server stays up on this GPU-less box: a HIP
     # runtime that cannot start makes it leave, see test_prover_server_lifecycle_without_gpu)
@@ -272,7 +272,7 @@ def test_malformed_device_environment_is_an_input_error(zk, tmp_path):
             assert "no HIP device" in rc.stderr or var in rc.stderr
 
 
-def test_server_pool_answers_concurrent_requests_without_gpu(zk, tmp_path):
+def test_server_pool_answers_concurrent_requests_without_gpu(zk, tmp_path, sock_dir):
     """The resident prover serves from a pool of threads (r04). Sixteen clients at once, each with its own missing witness
     (an INPUT error, answered before any GPU work, so the server stays up on this box): every client gets its own message
     and exit code 1, nothing is written, and the server still stops on request. (The same sixteen under ThreadSanitizer
@@ -283,7 +283,7 @@ def test_server_pool_answers_concurrent_requests_without_gpu(zk, tmp_path):
         pytest.skip("GPU present: covered by tests/test_gpu_prove.py::test_server_overlaps_requests_without_mixing_them_up")
     g = golden_case("n8")
     (tmp_path / "c.zkey").write_bytes(g["circuit.zkey"])
-    env = dict(os.environ, ZKPOA_SERVER=str(tmp_path / "p.sock"), ZKPOA_SERVER_IDLE_S="30", ZKPOA_SERVER_WORKERS="4")
+    env = dict(os.environ, ZKPOA_SERVER=str(sock_dir / "p.sock"), ZKPOA_SERVER_IDLE_S="30", ZKPOA_SERVER_WORKERS="4")
     try:
         procs = [subprocess.Popen([zk.PROVER_BIN, "c.zkey", "missing%d.wtns" % i, "p%d.json" % i, "u%d.json" % i], env=env,
                                   cwd=tmp_path, stderr=subprocess.PIPE, text=True) for i in range(16)]
@@ -291,7 +291,7 @@ def test_server_pool_answers_concurrent_requests_without_gpu(zk, tmp_path):
             _, err = pr.communicate(timeout=120)
             assert pr.returncode == 1 and ("missing%d.wtns" % i) in err and "cannot read witness file" in err, err
             assert not (tmp_path / ("p%d.json" % i)).exists()
-        assert os.path.exists(tmp_path / "p.sock")
+        assert os.path.exists(sock_dir / "p.sock")
     finally:
         rc = subprocess.run([zk.PROVER_BIN, "--stop-server"], env=env, cwd=tmp_path, timeout=60)
     assert rc.returncode == 0

@@ -402,7 +402,7 @@ def test_prover_cli_one_proof_over_several_ranks(zk, tmp_path, devices, tag):
     assert (tmp_path / "public.json").read_text() == g["public_rapidsnark.json"]
 
 
-def test_prover_cli_several_ranks_mid_size_server_and_errors(zk, tmp_path, mid_circuit):
+def test_prover_cli_several_ranks_mid_size_server_and_errors(zk, tmp_path, mid_circuit, sock_dir):
     """The same path at 2^13 with real block-cyclic shards (4 ranks, blocks of 2^7 wires), through the resident server:
     first call loads the shards, the second builds every shard's fixed-base tables, the third is served from the cache
     -- all three byte-identical to the single-device proof; then the error conventions (bad device list, short witness)."""
@@ -416,7 +416,7 @@ def test_prover_cli_several_ranks_mid_size_server_and_errors(zk, tmp_path, mid_c
     rc = subprocess.run(argv("single"), env=dict(base, ZKPOA_DEVICE="0"), capture_output=True, text=True, cwd=tmp_path, timeout=300)
     assert rc.returncode == 0, rc.stderr
     want = (tmp_path / "single.json").read_text()
-    sock = str(tmp_path / "prover.sock")
+    sock = str(sock_dir / "prover.sock")
     # (ZKPOA_PRECOMP=eager: the tables on the key's second use, inside the request -- the r03 policy; the default builds
     # them from the server's idle time, test_server_builds_tables_in_its_idle_time_not_in_a_request)
     env = dict(base, ZKPOA_DEVICES="0,0,0,0", ZKPOA_SERVER=sock, ZKPOA_SERVER_IDLE_S="60", ZKPOA_PRECOMP="eager")
@@ -426,7 +426,7 @@ def test_prover_cli_several_ranks_mid_size_server_and_errors(zk, tmp_path, mid_c
             assert rc.returncode == 0, rc.stderr
             assert (tmp_path / ("multi%d.json" % i)).read_text() == want
             assert (tmp_path / ("multi%d_public.json" % i)).read_text() == (tmp_path / "single_public.json").read_text()
-        log = (tmp_path / "prover.sock.log").read_text()
+        log = (sock_dir / "prover.sock.log").read_text()
         assert log.count("| zkey sharded load ") == 1 and log.count("| zkey cached,") == 2
         assert "fixed-base tables for the cached key on 4 ranks" in log and "sections 5-8 block-cyclic" in log
         rc = subprocess.run([zk.PROVER_BIN, "circuit_final.zkey", "short.wtns", "bad.json", "bad_public.json"], env=env,
@@ -526,7 +526,7 @@ def test_prover_cli_over_distinct_gpus(zk, tmp_path):
         assert (tmp_path / "mid.json").read_text() == zk.proof_to_json(want_pts, "rapidsnark")
 
 
-def test_a_stale_exchange_is_caught_by_the_self_check_and_repeated_with_copies(zk, tmp_path):
+def test_a_stale_exchange_is_caught_by_the_self_check_and_repeated_with_copies(zk, tmp_path, sock_dir):
     """The peer-store exchanges of the multi-GPU drop-in rest on a memory-visibility rule no multi-GPU node has confirmed
     yet. Safety net: the first three proofs of a key are verified against the zkey's own verification key, and a proof
     that fails is repeated with hipMemcpyPeerAsync exchanges, which then stay on. Here rank 0 withholds its first push
@@ -536,7 +536,7 @@ def test_a_stale_exchange_is_caught_by_the_self_check_and_repeated_with_copies(z
     rs = json.loads(g["rs.json"])
     (tmp_path / "circuit_final.zkey").write_bytes(g["circuit.zkey"])
     (tmp_path / "witness.wtns").write_bytes(g["witness.wtns"])
-    sock = str(tmp_path / "prover.sock")
+    sock = str(sock_dir / "prover.sock")
     env = dict(os.environ, ZKPOA_R=rs["r"], ZKPOA_S=rs["s"], ZKPOA_SERVER=sock, ZKPOA_SERVER_IDLE_S="60",
                ZKPOA_DEVICES="0,0,0,0", ZKPOA_TEST_STALE_EXCHANGE="1", ZKPOA_VERBOSE="1")
     argv = [zk.PROVER_BIN, "circuit_final.zkey", "witness.wtns", "proof.json", "public.json"]
@@ -547,7 +547,7 @@ def test_a_stale_exchange_is_caught_by_the_self_check_and_repeated_with_copies(z
             rc = subprocess.run(argv, env=env, capture_output=True, text=True, cwd=tmp_path, timeout=300)
             assert rc.returncode == 0, rc.stderr
             assert (tmp_path / "proof.json").read_text() == g["proof_rapidsnark.json"], i
-        log = (tmp_path / "prover.sock.log").read_text()
+        log = (sock_dir / "prover.sock.log").read_text()
         assert log.count("failed its self-check with the peer-store exchanges") == 1
     finally:
         subprocess.run([zk.PROVER_BIN, "--stop-server"], env=env, cwd=tmp_path, timeout=60)
@@ -572,7 +572,7 @@ def test_a_failing_rank_ends_the_multi_rank_proof_with_an_error_not_a_hang(zk, t
     assert rc.returncode == 0 and (tmp_path / "proof.json").read_text() == g["proof_rapidsnark.json"]
 
 
-def test_prover_cli_server_mode(zk, tmp_path):
+def test_prover_cli_server_mode(zk, tmp_path, sock_dir):
     """ZKPOA_SERVER: same argv, exit codes and output bytes, but the proofs come from a resident prover
     process that keeps the key in HBM between calls (second call = cache hit)."""
     g, g8 = golden_case("n128"), golden_case("n8")
@@ -580,7 +580,7 @@ def test_prover_cli_server_mode(zk, tmp_path):
     (tmp_path / "circuit_final.zkey").write_bytes(g["circuit.zkey"])
     (tmp_path / "witness.wtns").write_bytes(g["witness.wtns"])
     (tmp_path / "short.wtns").write_bytes(g8["witness.wtns"])
-    sock = str(tmp_path / "prover.sock")
+    sock = str(sock_dir / "prover.sock")
     env = dict(os.environ, ZKPOA_R=rs["r"], ZKPOA_S=rs["s"], ZKPOA_SERVER=sock, ZKPOA_VERBOSE="1",
                ZKPOA_SERVER_IDLE_S="60")
 
@@ -597,7 +597,7 @@ def test_prover_cli_server_mode(zk, tmp_path):
         assert rc.returncode == 0, rc.stderr
         assert (tmp_path / "proof_s.json").read_text() == g["proof_snarkjs.json"]
         assert (tmp_path / "public_s.json").read_text() == g["public_snarkjs.json"]
-        log = (tmp_path / "prover.sock.log").read_text()
+        log = (sock_dir / "prover.sock.log").read_text()
         assert log.count("| zkey load ") == 1 and log.count("| zkey cached,") == 1   # uploaded once, reused once
         # a failing request: rapidsnark's message, exit code 1, no output files, and the server stays up
         rc = run("short.wtns", "bad.json", "bad_public.json")
@@ -616,7 +616,7 @@ def test_prover_cli_server_mode(zk, tmp_path):
         os.utime(tmp_path / "circuit_final.zkey", ns=(1, 1))
         rc = run("witness.wtns", "proof3.json", "public3.json")
         assert rc.returncode == 0 and (tmp_path / "proof3.json").read_text() == g["proof_rapidsnark.json"]
-        assert (tmp_path / "prover.sock.log").read_text().count("| zkey load ") == 2
+        assert (sock_dir / "prover.sock.log").read_text().count("| zkey load ") == 2
     finally:
         subprocess.run([zk.PROVER_BIN, "--stop-server"], env=env, cwd=tmp_path, timeout=60)
     for _ in range(100):
@@ -627,7 +627,7 @@ def test_prover_cli_server_mode(zk, tmp_path):
 
 
 @pytest.mark.parametrize("devices", [None, "0,0"])
-def test_server_builds_tables_in_its_idle_time_not_in_a_request(zk, tmp_path, mid_circuit, devices):
+def test_server_builds_tables_in_its_idle_time_not_in_a_request(zk, tmp_path, mid_circuit, devices, sock_dir):
     """Default policy (ZKPOA_PRECOMP unset): a resident key's fixed-base tables are never built inside a request -- a whole
     set is seconds at the layer-two / -three sizes, which a two-batch workflow never earns back -- but one table per step
     from the server's idle time (zkpoa_idle_work, after ZKPOA_SERVER_IDLE_WORK_MS without a request). First call: load;
@@ -636,7 +636,7 @@ def test_server_builds_tables_in_its_idle_time_not_in_a_request(zk, tmp_path, mi
     zkey, vk, wt, n_pub = mid_circuit
     (tmp_path / "circuit_final.zkey").write_bytes(zkey)
     (tmp_path / "witness.wtns").write_bytes(wt)
-    sock = str(tmp_path / "prover.sock")
+    sock = str(sock_dir / "prover.sock")
     env = dict(os.environ, ZKPOA_R="12345678901234567890", ZKPOA_S="98765432109876543210", ZKPOA_VERBOSE="1",
                ZKPOA_SERVER=sock, ZKPOA_SERVER_IDLE_S="60", ZKPOA_SERVER_IDLE_WORK_MS="100")
     env.pop("ZKPOA_PRECOMP", None)
@@ -649,7 +649,7 @@ def test_server_builds_tables_in_its_idle_time_not_in_a_request(zk, tmp_path, mi
         log = ""
         for _ in range(100):                                   # the idle work starts by itself
             time.sleep(0.1)
-            log = (tmp_path / "prover.sock.log").read_text()
+            log = (sock_dir / "prover.sock.log").read_text()
             if ("complete)" in log) if not devices else ("idle: fixed-base tables for the cached key on 2 ranks" in log):
                 break
         assert "zkpoa: idle: fixed-base table" in log, log
@@ -657,14 +657,14 @@ def test_server_builds_tables_in_its_idle_time_not_in_a_request(zk, tmp_path, mi
             rc = subprocess.run(argv("p%d" % i), env=env, capture_output=True, text=True, cwd=tmp_path, timeout=300)
             assert rc.returncode == 0, rc.stderr
             assert (tmp_path / ("p%d.json" % i)).read_text() == (tmp_path / "p0.json").read_text()
-        log = (tmp_path / "prover.sock.log").read_text()
+        log = (sock_dir / "prover.sock.log").read_text()
         assert log.count("| zkey cached,") == 2
         assert "fixed-base tables for the cached key:" not in log and "fixed-base tables for the cached key on" not in log.replace("idle: fixed-base tables for the cached key on", "")
     finally:
         subprocess.run([zk.PROVER_BIN, "--stop-server"], env=env, cwd=tmp_path, timeout=60)
 
 
-def test_server_overlaps_requests_without_mixing_them_up(zk, tmp_path):
+def test_server_overlaps_requests_without_mixing_them_up(zk, tmp_path, sock_dir):
     """The resident prover serves requests from a pool of threads: the witness of one request is staged into the key's
     second buffer while another request proves (two locks inside zkpoa_groth16_prover_files), and r, s and the JSON style
     travel per request and per thread, never through the server's environment. Twelve clients at once -- two witnesses,
@@ -676,7 +676,7 @@ def test_server_overlaps_requests_without_mixing_them_up(zk, tmp_path):
     (tmp_path / "circuit_final.zkey").write_bytes(zkey)
     (tmp_path / "wa.wtns").write_bytes(g["witness.wtns"])
     (tmp_path / "wb.wtns").write_bytes(g16.write_wtns(w0))
-    sock = str(tmp_path / "prover.sock")
+    sock = str(sock_dir / "prover.sock")
     env = dict(os.environ, ZKPOA_SERVER=sock, ZKPOA_SERVER_IDLE_S="60", ZKPOA_SERVER_WORKERS="3")
     for k in ("ZKPOA_R", "ZKPOA_S", "ZKPOA_JSON", "ZKPOA_VERBOSE"):
         env.pop(k, None)
@@ -1097,7 +1097,7 @@ def test_multi_process_sharded_prove_rehearsal(nproc, extra):
     env = dict(os.environ, ZKPOA_BENCH_REHEARSE="1")
     rc = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc),
                          "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                         "--gpus", str(nproc), "--steps", "2", "--warmup", "1", "--workload", "prove_2p16"] + extra,
+                         "--gpus", str(nproc), "--steps", "2", "--warmup", "1", "--workload", "prove_2p16", "--full"] + extra,
                         env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert rc.returncode == 0, rc.stderr[-2000:]
     line = json.loads([l for l in rc.stdout.splitlines() if l.startswith("{")][-1])
@@ -1125,7 +1125,8 @@ def test_bench_lines_carry_the_same_curves_at_every_n():
         port = s.getsockname()[1]
         s.close()
         env = dict(os.environ, ZKPOA_BENCH_SMALL="1")
-        tail = [os.path.join(root, "bench.py"), "--gpus", str(nproc), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+        tail = [os.path.join(root, "bench.py"), "--gpus", str(nproc), "--steps", "2", "--warmup", "1", "--full",
+                "--no-cpu-baseline"]
         if nproc == 1:
             argv = [sys.executable] + tail
         else:
@@ -1160,7 +1161,7 @@ def test_bench_collectives_over_rccl_with_one_rank():
         env = dict(os.environ, ZKPOA_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0",
                    WORLD_SIZE="1", LOCAL_RANK="0")
         rc = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                             "--workload", workload, "--no-cpu-baseline"], env=env, capture_output=True, text=True,
+                             "--workload", workload, "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
                             timeout=600, cwd=root)
         assert rc.returncode == 0, rc.stderr[-2000:]
         line = json.loads([l for l in rc.stdout.splitlines() if l.startswith("{")][-1])
@@ -1170,14 +1171,14 @@ def test_bench_collectives_over_rccl_with_one_rank():
 
 
 # ---- failure paths that used to be silent or sticky ---------------------------------------------------
-def test_server_death_mid_request_still_yields_the_proof(zk, tmp_path):
+def test_server_death_mid_request_still_yields_the_proof(zk, tmp_path, sock_dir):
     """The resident server dies with a request in hand (ZKPOA_SERVER_TEST_CRASH): the client proves in its own
     process, exit 0, same bytes; the next call starts a fresh server and is served by it."""
     g = golden_case("n128")
     rs = json.loads(g["rs.json"])
     (tmp_path / "circuit_final.zkey").write_bytes(g["circuit.zkey"])
     (tmp_path / "witness.wtns").write_bytes(g["witness.wtns"])
-    sock = str(tmp_path / "prover.sock")
+    sock = str(sock_dir / "prover.sock")
     env = dict(os.environ, ZKPOA_R=rs["r"], ZKPOA_S=rs["s"], ZKPOA_SERVER=sock, ZKPOA_VERBOSE="1",
                ZKPOA_SERVER_IDLE_S="60")
     argv = [zk.PROVER_BIN, "circuit_final.zkey", "witness.wtns", "proof.json", "public.json"]
@@ -1195,7 +1196,7 @@ def test_server_death_mid_request_still_yields_the_proof(zk, tmp_path):
         subprocess.run([zk.PROVER_BIN, "--stop-server"], env=env, cwd=tmp_path, timeout=60)
 
 
-def test_server_failure_is_logged_and_strict_mode_refuses_the_fallback(zk, tmp_path):
+def test_server_failure_is_logged_and_strict_mode_refuses_the_fallback(zk, tmp_path, sock_dir):
     """the in-process fallback must never hide a GPU-side failure. When the server dies with a
     request in hand the client still proves (exit 0) but leaves a line in the persistent fault log and names it on
     stderr; with ZKPOA_STRICT=1 the same event is exit != 0 and no proof is written."""
@@ -1203,7 +1204,7 @@ def test_server_failure_is_logged_and_strict_mode_refuses_the_fallback(zk, tmp_p
     rs = json.loads(g["rs.json"])
     (tmp_path / "circuit_final.zkey").write_bytes(g["circuit.zkey"])
     (tmp_path / "witness.wtns").write_bytes(g["witness.wtns"])
-    sock = str(tmp_path / "prover.sock")
+    sock = str(sock_dir / "prover.sock")
     log = "/tmp/zkpoa-%d/faults.log" % os.getuid()
     before = os.path.getsize(log) if os.path.exists(log) else 0
     env = dict(os.environ, ZKPOA_R=rs["r"], ZKPOA_S=rs["s"], ZKPOA_SERVER=sock, ZKPOA_SERVER_IDLE_S="60",
@@ -1258,7 +1259,7 @@ def test_out_of_range_field_elements_are_rejected(ctx, zk):
             ctx.load_zkey(bytes(bad))
 
 
-def test_witness_generation_of_one_batch_overlaps_proving_of_another(zk, tmp_path):
+def test_witness_generation_of_one_batch_overlaps_proving_of_another(zk, tmp_path, sock_dir):
     """witness generation stays on the CPU (circom C++, 18 s - 2 min per proof in the reference's
     logs, longer than the proving it feeds). The reference already runs its batches as parallel jobs
     (scripts/full_workflow.sh:552: `parallel prove_layers_one_two`), each job = witness generator, then prover
@@ -1274,7 +1275,7 @@ def test_witness_generation_of_one_batch_overlaps_proving_of_another(zk, tmp_pat
     gen = tmp_path / "witness_gen"
     gen.write_text('#!/bin/bash\nsleep 1\ncp "%s" "$2"\n' % (tmp_path / "ready.wtns"))
     gen.chmod(gen.stat().st_mode | stat.S_IXUSR)
-    env = dict(os.environ, ZKPOA_R=rs["r"], ZKPOA_S=rs["s"], ZKPOA_SERVER=str(tmp_path / "p.sock"),
+    env = dict(os.environ, ZKPOA_R=rs["r"], ZKPOA_S=rs["s"], ZKPOA_SERVER=str(sock_dir / "p.sock"),
                ZKPOA_SERVER_IDLE_S="60")
     try:
         # warm the server (its start-up and key upload are not what is measured)

@@ -22,7 +22,7 @@ from oracle.py import groth16 as g16
 pytestmark = pytest.mark.gpu
 
 
-def test_server_soak_every_proof_verified_no_memory_growth(zk, tmp_path):
+def test_server_soak_every_proof_verified_no_memory_growth(zk, tmp_path, sock_dir):
     import torch
     total = int(os.environ.get("ZKPOA_SOAK_PROOFS", "90"))
     clients = 3
@@ -36,7 +36,7 @@ def test_server_soak_every_proof_verified_no_memory_growth(zk, tmp_path):
     (tmp_path / "c.zkey").write_bytes(zkey)
     (tmp_path / "w.wtns").write_bytes(g16.write_wtns(w))
     (tmp_path / "vkey.json").write_text(json.dumps(vk))
-    sock = str(tmp_path / "prover.sock")
+    sock = str(sock_dir / "prover.sock")
     env = dict(os.environ, ZKPOA_SERVER=sock, ZKPOA_SERVER_IDLE_S="120", ZKPOA_SERVER_WORKERS="3")
     for k in ("ZKPOA_R", "ZKPOA_S", "ZKPOA_JSON", "ZKPOA_VERBOSE"):
         env.pop(k, None)

@@ -4,7 +4,7 @@
 set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out
-B="python3 $R/bench.py --no-cpu-baseline"
+B="python3 $R/bench.py --full --no-cpu-baseline"
 run() { name=$1; shift; timeout -k 10 300 env "$@" > $O/r03_ab_$name.json 2> $O/r03_ab_$name.err || echo "FAILED $name"; python3 $R/tools/show_bench.py $O/r03_ab_$name.json 2>/dev/null | head -8; }
 echo "== ntt radix 4 (default)"; timeout -k 10 120 python3 $R/tools/ntt_time.py
 echo "== ntt radix 2"; ZKPOA_NTT_RADIX=2 timeout -k 10 120 python3 $R/tools/ntt_time.py

@@ -9,7 +9,7 @@ PART=${PART:-all}      # 1 = bench lines + kernel stats, 2 = PMC passes (a gpuru
 [ "$PART" != 2 ] && rm -rf $O
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 if [ "$PART" != 2 ]; then
 $B > $O/bench_default.json.log 2>$O/bench_default.err; echo "bench default (headline + also legs) rc=$?"
 $B --no-also --no-cpu-baseline --inflight 1 > $O/bench_msm_g1_2p20_inflight1.json.log 2>/dev/null
