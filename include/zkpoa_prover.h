@@ -325,6 +325,33 @@ int zkpoa_zkey_contribute(zkpoa_context* ctx, const char* zkey_in_path, const ch
  * *first_violated (optional) <- the smallest failing constraint index. PROVER_ERROR for malformed files. */
 int zkpoa_wtns_check(zkpoa_context* ctx, const char* r1cs_path, const char* wtns_path, uint64_t* violated,
                      uint64_t* first_violated);
+/* `snarkjs zkey verify <circuit.r1cs> <pot.ptau> <circuit.zkey>` (scripts/g16_verify.sh -z): does the key belong to this
+ * circuit and this ceremony? Restates the formulas of zkpoa_zkey_new / zkpoa_zkey_contribute and checks them with
+ * random weights (rho over the wires, sigma over the domain, 253 bits each from /dev/urandom: a wrong key passes a check
+ * with probability about 2^-128 or less): random combinations of the point sections (MSMs on the device) against the
+ * same combinations of the ptau's Lagrange-form points, weighted by the r1cs' folds a = A rho, b = B rho, c = C rho.
+ * PROVER_OK: both files were read and every check ran; *failed_checks <- a bitmask of ZKPOA_ZKEY_* (0 = the key is good).
+ *   HEADER  protocol groth16 and BN254 moduli; alpha1, beta1, beta2 equal the ptau's; gamma2 is the G2 generator
+ *   POINTS  every key point on its curve or the all-zero infinity; B2, beta2, gamma2, delta2 in G2 ([r]Q = O); delta1 != O
+ *   DELTA   e(delta1, G2) = e(G1, delta2)
+ *   COEFFS  section 4's records in range, and its folds equal the r1cs' (A with the nPublic + 1 public rows, B)
+ *   A, B1, B2  sum rho_i X_i = sum_j (a or b)_j L_j over the matching ptau range
+ *   ICCH    e(sum_{i<=l} rho_i IC_i - Q, G2) e(sum_{i>l} rho_i C_i + sum_j sigma_j H_j, delta2) = 1,
+ *           Q = sum_j a_j beta*L_j + b_j alpha*L_j + c_j L_j + sigma_j (odd point j of the 2n basis)
+ * PROVER_ERROR (zkpoa_last_error) for a malformed file: bad magic, a missing section, a length that contradicts the
+ * header, a key whose nVars / nPublic / domain differ from the circuit's, a field element >= its modulus, a ptau too
+ * small for the domain or with a point off its curve. Section 10 (circuit hash, contribution records) is not read.
+ * These are this project's formulas: a key made by snarkjs passes as far as snarkjs computes the same sections. */
+#define ZKPOA_ZKEY_HEADER 0x01u
+#define ZKPOA_ZKEY_POINTS 0x02u
+#define ZKPOA_ZKEY_DELTA 0x04u
+#define ZKPOA_ZKEY_COEFFS 0x08u
+#define ZKPOA_ZKEY_A 0x10u
+#define ZKPOA_ZKEY_B1 0x20u
+#define ZKPOA_ZKEY_B2 0x40u
+#define ZKPOA_ZKEY_ICCH 0x80u
+int zkpoa_zkey_verify(zkpoa_context* ctx, const char* r1cs_path, const char* ptau_path, const char* zkey_path,
+                      uint32_t* failed_checks);
 
 /* ---- the step after the path; host only, no GPU ----------------------------------------
  * zkpoa_groth16_verify: `npx snarkjs groth16 verify <vkey> <public> <proof>` (scripts/g16_verify.sh:213-216)

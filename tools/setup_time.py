@@ -112,6 +112,11 @@ if "--files" in sys.argv:
     t0 = time.perf_counter()
     rc = subprocess.run([z.SETUP_BIN, "zkey", "contribute", d + "/c_0.zkey", d + "/c_final.zkey", "--name=First contributor", "-e=random text for entropy"], capture_output=True, text=True, env=dict(os.environ, ZKPOA_VERBOSE="1"))
     print("zkpoa-setup zkey contribute: %.2f s wall, rc=%d  %s" % (time.perf_counter() - t0, rc.returncode, rc.stderr.strip().splitlines()[-1] if rc.stderr.strip() else ""))
+    # zkey verify on the same files (the contributed key), beside zkey new
+    t0 = time.perf_counter()
+    rc = subprocess.run([z.SETUP_BIN, "zkey", "verify", d + "/c.r1cs", d + "/pot.ptau", d + "/c_final.zkey"], capture_output=True, text=True, env=dict(os.environ, ZKPOA_VERBOSE="1"))
+    print("zkpoa-setup zkey verify: %.2f s wall, rc=%d  %s" % (time.perf_counter() - t0, rc.returncode, rc.stdout.strip()))
+    print("\n".join("    " + l for l in rc.stderr.splitlines() if "zkey verify:" in l))
     # the key it wrote must load (section sizes, coordinate and coefficient range checks of the prover's loader)
     key = ctx.load_zkey(open(d + "/c_0.zkey", "rb").read()); key.close()
     print("the prover loads the key")

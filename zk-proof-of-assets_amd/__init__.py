@@ -25,12 +25,16 @@ PROVER_ERROR_SHORT_BUFFER = 2
 PROVER_INVALID_WITNESS_LENGTH = 3
 PROVER_ERROR_RUNTIME = 4
 
+# the bits of zkpoa_zkey_verify's result (include/zkpoa_prover.h ZKPOA_ZKEY_*)
+ZKEY_CHECKS = {"HEADER": 0x01, "POINTS": 0x02, "DELTA": 0x04, "COEFFS": 0x08, "A": 0x10, "B1": 0x20, "B2": 0x40,
+               "ICCH": 0x80}
+
 # every symbol include/zkpoa_prover.h declares
 EXPORTS = [
     "groth16_prover", "groth16_prover_zkey_file",
     "zkpoa_context_create", "zkpoa_context_destroy", "zkpoa_last_error",
     "zkpoa_zkey_load", "zkpoa_zkey_free", "zkpoa_zkey_info", "zkpoa_prove",
-    "zkpoa_zkey_load_device", "zkpoa_zkey_load_device_shard", "zkpoa_prove_device", "zkpoa_setup_accumulate", "zkpoa_zkey_new", "zkpoa_zkey_contribute", "zkpoa_wtns_check",
+    "zkpoa_zkey_load_device", "zkpoa_zkey_load_device_shard", "zkpoa_prove_device", "zkpoa_setup_accumulate", "zkpoa_zkey_new", "zkpoa_zkey_contribute", "zkpoa_wtns_check", "zkpoa_zkey_verify",
     "zkpoa_groth16_prover_files", "zkpoa_set_thread_options", "zkpoa_clear_thread_options", "zkpoa_idle_work", "zkpoa_zkey_load_shard", "zkpoa_zkey_load_shard_ex", "zkpoa_zkey_set_shard", "zkpoa_zkey_header",
     "zkpoa_prove_partials", "zkpoa_prove_partials_device", "zkpoa_prove_assemble",
     "zkpoa_zkey_load_shard_split", "zkpoa_zkey_set_shard_split", "zkpoa_witness_load",
@@ -140,6 +144,8 @@ def lib():
         L.zkpoa_wtns_check.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p,
                                        ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         L.zkpoa_zkey_contribute.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
+        L.zkpoa_zkey_verify.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
+                                        ctypes.POINTER(ctypes.c_uint32)]
         L.zkpoa_zkey_load_device_shard.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint,
                                                    ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int] + \
             [ctypes.c_void_p] * 6 + [ctypes.c_uint64, ctypes.c_char_p, c_void_pp]
@@ -399,6 +405,14 @@ class Context:
         self._check(lib().zkpoa_wtns_check(self._h, os.fsencode(r1cs_path), os.fsencode(wtns_path), ctypes.byref(bad),
                                            ctypes.byref(first)), "zkpoa_wtns_check")
         return int(bad.value), (int(first.value) if bad.value else None)
+
+    def zkey_verify(self, r1cs_path, ptau_path, zkey_path):
+        """`snarkjs zkey verify` on files: -> the bitmask of failed checks (ZKEY_CHECKS), 0 = the key belongs to this
+        circuit and this ceremony. A malformed file raises ZkpoaError (include/zkpoa_prover.h: zkpoa_zkey_verify)."""
+        failed = ctypes.c_uint32(0)
+        self._check(lib().zkpoa_zkey_verify(self._h, os.fsencode(r1cs_path), os.fsencode(ptau_path),
+                                            os.fsencode(zkey_path), ctypes.byref(failed)), "zkpoa_zkey_verify")
+        return int(failed.value)
 
     def zkey_contribute(self, zkey_in_path, zkey_out_path, delta=None):
         """The arithmetic of `snarkjs zkey contribute` (delta: int in [1, r), None = random)."""

@@ -3,6 +3,7 @@
 //     snarkjs groth16 setup <circuit.r1cs> <pot.ptau> <circuit_0.zkey>
 //     snarkjs zkey contribute <circuit_0.zkey> <circuit_final.zkey> --name="..." -e="..."     (:262-266; arithmetic only)
 //     snarkjs wtns check <circuit.r1cs> <witness.wtns>                                      (scripts/g16_verify.sh:205-210)
+//     snarkjs zkey verify <circuit.r1cs> <pot.ptau> <circuit_final.zkey>                    (scripts/g16_verify.sh -z)
 // Same three file arguments (the words `zkey new` / `groth16 setup` are accepted and ignored, so the command line
 // can be kept as it is with the executable swapped). The .ptau must be prepared for phase 2 (`snarkjs powersoftau
 // prepare phase2`), as snarkjs requires too. Exit status 0 / non-zero + message on stderr.
@@ -36,11 +37,43 @@ static bool parse_decimal_or_hex(const char* s, uint8_t out[32]) {   // ZKPOA_DE
   return true;
 }
 
+// `zkey verify`: true when the key's delta2 equals its gamma2 (the generator, which the HEADER check holds it to): no
+// contribution has been made, and whoever has the key can forge proofs with it
+static bool delta2_is_gamma2(const char* zkey_path) {
+  FILE* f = fopen(zkey_path, "rb");
+  if (!f) return false;
+  bool same = false;
+  unsigned char hd[12];
+  if (fread(hd, 1, 12, f) == 12) {
+    uint32_t ns;
+    memcpy(&ns, hd + 8, 4);
+    for (uint32_t i = 0; i < ns; i++) {
+      unsigned char sh[12];
+      if (fread(sh, 1, 12, f) != 12) break;
+      uint32_t type;
+      uint64_t len;
+      memcpy(&type, sh, 4);
+      memcpy(&len, sh + 4, 8);
+      if (type == 2) {
+        unsigned char h[660];
+        same = len == sizeof h && fread(h, 1, sizeof h, f) == sizeof h && !memcmp(h + 340, h + 532, 128);
+        break;
+      }
+      if (fseeko(f, (off_t)len, SEEK_CUR) != 0) break;
+    }
+  }
+  fclose(f);
+  return same;
+}
+
 int main(int argc, char** argv) {
   int a = 1;
-  bool contribute = false, check = false;
+  bool contribute = false, check = false, verify = false;
   if (argc - a >= 2 && !strcmp(argv[a], "zkey") && !strcmp(argv[a + 1], "contribute")) {
     contribute = true;
+    a += 2;
+  } else if (argc - a >= 2 && !strcmp(argv[a], "zkey") && !strcmp(argv[a + 1], "verify")) {
+    verify = true;
     a += 2;
   } else if (argc - a >= 2 && !strcmp(argv[a], "wtns") && !strcmp(argv[a + 1], "check")) {
     check = true;
@@ -61,7 +94,8 @@ int main(int argc, char** argv) {
   if (npos != (contribute || check ? 2 : 3)) {
     fprintf(stderr, "usage: zkpoa-setup [zkey new | groth16 setup] <circuit.r1cs> <pot.ptau> <circuit_0.zkey>\n"
                     "       zkpoa-setup zkey contribute <in.zkey> <out.zkey> [--name=...] [-e=...]\n"
-                    "       zkpoa-setup wtns check <circuit.r1cs> <witness.wtns>\n");
+                    "       zkpoa-setup wtns check <circuit.r1cs> <witness.wtns>\n"
+                    "       zkpoa-setup zkey verify <circuit.r1cs> <pot.ptau> <circuit.zkey>\n");
     return 2;
   }
   uint8_t delta[32];
@@ -76,7 +110,8 @@ int main(int argc, char** argv) {
   }
   // `zkey new` / `zkey contribute` run in a worker process and this one leaves as soon as the key is renamed into place
   // (csrc/worker_exit.hpp: a worker that has held ~100 GB of host arrays takes seconds to be dismantled).
-  zkpoa::WorkerExit we = zkpoa::WorkerExit::start(!check, "zkpoa-setup");
+  // (`wtns check` and `zkey verify` write nothing and use no worker)
+  zkpoa::WorkerExit we = zkpoa::WorkerExit::start(!check && !verify, "zkpoa-setup");
   if (we.is_worker()) zkpoa_setup_defer_host_frees(1);
   auto leave = [&](int code) -> int {
     if (we.is_worker()) we.leave(code);
@@ -101,13 +136,37 @@ int main(int argc, char** argv) {
       zkpoa_context_destroy(ctx);
       return 1;
     }
+  } else if (verify) {   // snarkjs prints "ZKey Ok!" and exits 0, or names what does not match and exits 1
+    uint32_t failed = 0;
+    rc = zkpoa_zkey_verify(ctx, pos[0], pos[1], pos[2], &failed);
+    if (rc == PROVER_OK) {
+      static const char* const kWhat[8] = {
+          "HEADER: protocol, moduli, alpha1 / beta1 / beta2 (against the ptau) or gamma2 (the G2 generator) do not match",
+          "POINTS: a point is off its curve, a G2 point (B2, beta2, gamma2, delta2) is outside G2, or delta1 is zero",
+          "DELTA: e(delta1, G2) != e(G1, delta2)",
+          "COEFFS: section 4 (coefficients) does not match the r1cs",
+          "A: section 5 (A) does not match the r1cs and the ptau",
+          "B1: section 6 (B in G1) does not match the r1cs and the ptau",
+          "B2: section 7 (B in G2) does not match the r1cs and the ptau",
+          "ICCH: sections 3, 8 or 9 (IC, C, H) do not match the r1cs, the ptau and delta"};
+      fprintf(stderr, "[WARN]  zkpoa: section 10 (circuit hash, contribution records) is not checked\n");
+      for (int b = 0; b < 8; b++)
+        if (failed & (1u << b)) fprintf(stderr, "[ERROR] zkpoa: %s\n", kWhat[b]);
+      if (failed) {
+        zkpoa_context_destroy(ctx);
+        return 1;
+      }
+      if (delta2_is_gamma2(pos[2]))
+        fprintf(stderr, "[WARN]  zkpoa: delta2 is the generator: the key has had no contribution, anyone can forge proofs with it\n");
+      printf("[INFO]  zkpoa: ZKey Ok!\n");
+    }
   } else {
     rc = contribute ? zkpoa_zkey_contribute(ctx, pos[0], pos[1], delta_p) : zkpoa_zkey_new(ctx, pos[0], pos[1], pos[2]);
   }
   if (rc != PROVER_OK) fprintf(stderr, "zkpoa-setup: %s\n", zkpoa_last_error(ctx));
   if (!we.is_worker()) zkpoa_context_destroy(ctx);
   clock_gettime(CLOCK_MONOTONIC, &t1);
-  if (rc == PROVER_OK && getenv("ZKPOA_VERBOSE") && !check)
+  if (rc == PROVER_OK && getenv("ZKPOA_VERBOSE") && !check && !verify)
     fprintf(stderr, "zkpoa-setup: %s written in %.2f s\n", pos[contribute ? 1 : 2],
             (t1.tv_sec - t0.tv_sec) + (t1.tv_nsec - t0.tv_nsec) / 1e9);
   return leave(rc == PROVER_OK ? 0 : 1);
