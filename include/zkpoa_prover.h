@@ -431,6 +431,23 @@ uint64_t zkpoa_msm_points_limit(const zkpoa_context* ctx);
 int zkpoa_field_op(zkpoa_context* ctx, int field, int op, const void* a, const void* b, void* out, uint64_t n);
 /* group: 1 = G1, 2 = G2. out[i] = a[i] + b[i] (affine in, affine out, all exceptional cases). */
 int zkpoa_group_add(zkpoa_context* ctx, int group, const void* a, const void* b, void* out, uint64_t n);
+/* The field layer's own primitives on raw lazy values (Montgomery form, each in [0, 2p) unless the op says more).
+ * field: 0 = Fq, 1 = Fr (32-byte elements), 2 = Fq2 (64 bytes: c0, c1). in: the op's operand arrays of n elements
+ * back to back; out: its result arrays likewise. raw != 0 stores results exactly as computed (lazy form), else
+ * canonical. Fq / Fr op (operands -> results): 0 = mul (a, b), 1 = sqr (a), 2 = add (a, b), 3 = sub (a, b),
+ * 4 = neg (a), 5 = neg_2p (a), 6 = dbl (a), 7 = canon (a), 8 = reduce_2p (a < 4p), 9 = inv (a),
+ * 10 = dot2 (a0, b0, a1, b1; b1 may be 2p), 11 = dot3 (a0, b0, a1, b1, a2, b2; every b < p),
+ * 12 = mul_pair (a, b, c, d -> ab, cd), 13 = sqr_pair (a, b -> a^2, b^2),
+ * 14 = dot2_pair (a0, b0, a1, b1, c0, d0, c1, d1 -> two dot2), 15 = is_zero (a), 16 = a == b;
+ * is_zero and == store 0 / 1 in limb 0. Fq2 op: 0 = mul, 1 = sqr, 2 = add, 3 = sub, 4 = neg, 5 = inv. */
+int zkpoa_field_prim(zkpoa_context* ctx, int field, int op, const void* in, void* out, uint64_t n, int raw);
+/* The group layer's own XYZZ primitives. group: 1 = G1, 2 = G2. a: n XYZZ points (x, y, zz, zzz; Montgomery;
+ * coordinates in [0, 2p); infinity = zz equal to 0 mod p); b: n affine points (zkey wire form) or, for op 0, n XYZZ
+ * points; k: n u32 negate flags (op 1) or multipliers (op 4). out: n XYZZ, stored as computed.
+ * op: 0 = a + b (xyzz_add), 1 = a + (k ? -b : b) (xyzz_add_affine), 2 = 2a (xyzz_dbl), 3 = 2b for b not infinity
+ * (xyzz_dbl_affine), 4 = k a (xyzz_mul_small). Arguments an op does not use may be NULL. */
+int zkpoa_curve_prim(zkpoa_context* ctx, int group, int op, const void* a, const void* b, const uint32_t* k,
+                     void* out, uint64_t n);
 
 #ifdef __cplusplus
 }

@@ -46,6 +46,7 @@ EXPORTS = [
     "zkpoa_gen_bases_g1_device", "zkpoa_gen_bases_g2_device",
     "zkpoa_g1_sum", "zkpoa_g2_sum", "zkpoa_g1_mul", "zkpoa_g2_mul",
     "zkpoa_setup_defer_host_frees", "zkpoa_last_ms", "zkpoa_set_option", "zkpoa_msm_points_limit", "zkpoa_field_op", "zkpoa_group_add",
+    "zkpoa_field_prim", "zkpoa_curve_prim",
     "zkpoa_groth16_verify", "zkpoa_sanitize_proof", "zkpoa_groth16_verify_points", "zkpoa_zkey_vkey", "zkpoa_zkey_export_vkey",
     "zkpoa_zkey_read_h_scalars", "zkpoa_zkey_precompute",
     "zkpoa_context_stream", "zkpoa_context_synchronize",
@@ -129,6 +130,10 @@ def lib():
                                      ctypes.c_void_p, ctypes.c_uint64]
         L.zkpoa_group_add.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.c_uint64]
+        L.zkpoa_field_prim.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_uint64, ctypes.c_int]
+        L.zkpoa_curve_prim.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
         L.zkpoa_zkey_load.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong, c_void_pp]
         L.zkpoa_zkey_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.zkpoa_zkey_free.restype = None
@@ -372,6 +377,29 @@ class Context:
         out = ctypes.create_string_buffer(max(1, size * n))
         self._check(lib().zkpoa_group_add(self._h, group, pa, pb, out, n), "zkpoa_group_add")
         return out.raw[:size * n]
+
+    def field_prim(self, field, op, operands, n_out=1, raw=True):
+        """zkpoa_field_prim: `operands` is the list of the op's operand arrays (n elements each, 32 B or 64 B for
+        Fq2); returns the list of its `n_out` result arrays."""
+        size = 64 if field == 2 else 32
+        n = len(operands[0]) // size if operands else 0
+        assert all(len(x) == n * size for x in operands)
+        pin, kin = _buf(b"".join(operands))
+        out = ctypes.create_string_buffer(max(1, size * n * n_out))
+        self._check(lib().zkpoa_field_prim(self._h, field, op, pin, out, n, 1 if raw else 0), "zkpoa_field_prim")
+        return [out.raw[size * n * j:size * n * (j + 1)] for j in range(n_out)]
+
+    def curve_prim(self, group, op, a=None, b=None, k=None, n=None):
+        """zkpoa_curve_prim: a, b as the op takes them (XYZZ / affine bytes), k a sequence of u32; returns n XYZZ."""
+        fb = 32 if group == 1 else 64
+        if n is None:
+            n = len(a) // (4 * fb) if a is not None else len(b) // (2 * fb)
+        pa, ka = _buf(a) if a is not None else (None, None)
+        pb, kb = _buf(b) if b is not None else (None, None)
+        pk, kk = _buf(b"".join(int(v).to_bytes(4, "little") for v in k)) if k is not None else (None, None)
+        out = ctypes.create_string_buffer(max(1, 4 * fb * n))
+        self._check(lib().zkpoa_curve_prim(self._h, group, op, pa, pb, pk, out, n), "zkpoa_curve_prim")
+        return out.raw[:4 * fb * n]
 
     # ---- proving key + prove -----------------------------------------------------------------
     def load_zkey(self, zkey_bytes):

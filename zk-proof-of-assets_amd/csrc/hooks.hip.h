@@ -141,5 +141,168 @@ inline void group_add_run(zkpoa_context* ctx, const void* a, const void* b, void
   ZK_HIP(hipMemcpy(out, dout.p, n * A, hipMemcpyDeviceToHost));
 }
 
+// ---------------------------------------------------------------------------------------------
+// primitive-level test kernels (zkpoa_field_prim / zkpoa_curve_prim): the field and curve layer's own functions on
+// raw lazy values, results stored as computed (or canonical) so the tests can assert each function's output range
+// ---------------------------------------------------------------------------------------------
+// operand / result counts per op (include/zkpoa_prover.h); {0, 0} = no such op
+struct PrimArity {
+  int in, out;
+};
+inline PrimArity field_prim_arity(int field, int op) {
+  static constexpr PrimArity kFp[] = {{2, 1}, {1, 1}, {2, 1}, {2, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 1},
+                                      {1, 1}, {4, 1}, {6, 1}, {4, 2}, {2, 2}, {8, 2}, {1, 1}, {2, 1}};
+  static constexpr PrimArity kFq2[] = {{2, 1}, {1, 1}, {2, 1}, {2, 1}, {1, 1}, {1, 1}};
+  if ((field == 0 || field == 1) && op >= 0 && op < (int)(sizeof(kFp) / sizeof(kFp[0]))) return kFp[op];
+  if (field == 2 && op >= 0 && op < (int)(sizeof(kFq2) / sizeof(kFq2[0]))) return kFq2[op];
+  return {0, 0};
+}
+
+template <class PRM>
+ZK_DEV void store_prim(void* p, const Fp<PRM>& v, int raw) {
+  if (!raw) {
+    store_fp<PRM>(p, v);
+    return;
+  }
+  uint4* q = reinterpret_cast<uint4*>(p);
+  q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
+  q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
+}
+ZK_DEV void store_prim(void* p, const Fq2& v, int raw) {
+  store_prim(p, v.c0, raw);
+  store_prim(reinterpret_cast<char*>(p) + 32, v.c1, raw);
+}
+
+// in: the op's operand arrays (n elements each) back to back; out: its result arrays, likewise. F = Fq, Fr or Fq2.
+template <class F>
+__global__ __launch_bounds__(256) void field_prim_kernel(int op, const void* in, void* out, uint64_t n, int raw) {
+  uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  constexpr int B = FieldBytes<F>::N;
+  const char* src = reinterpret_cast<const char*>(in);
+  char* dst = reinterpret_cast<char*>(out);
+  auto arg = [&](int j) { return load_field<F>(src + (j * n + i) * B); };
+  auto put = [&](int j, const F& v) { store_prim(dst + (j * n + i) * B, v, raw); };
+  if constexpr (std::is_same<F, Fq2>::value) {   // Fq2: mul, sqr, add, sub, neg, inv
+    F r;
+    switch (op) {
+      case 0: r = arg(0) * arg(1); break;
+      case 1: r = arg(0).sqr(); break;
+      case 2: r = arg(0) + arg(1); break;
+      case 3: r = arg(0) - arg(1); break;
+      case 4: r = arg(0).neg(); break;
+      default: r = arg(0).inv(); break;
+    }
+    put(0, r);
+    return;
+  } else {
+    auto flag = [&](bool b) {
+      F r = F::zero();
+      r.l[0] = b ? 1u : 0u;
+      put(0, r);
+    };
+    F r0, r1;
+    switch (op) {
+      case 0: put(0, arg(0) * arg(1)); break;
+      case 1: put(0, arg(0).sqr()); break;
+      case 2: put(0, arg(0) + arg(1)); break;
+      case 3: put(0, arg(0) - arg(1)); break;
+      case 4: put(0, arg(0).neg()); break;
+      case 5: put(0, arg(0).neg_2p()); break;
+      case 6: put(0, arg(0).dbl()); break;
+      case 7: put(0, arg(0).canon()); break;
+      case 8: put(0, F::reduce_2p(arg(0))); break;
+      case 9: put(0, arg(0).inv()); break;
+      case 10: put(0, F::dot2(arg(0), arg(1), arg(2), arg(3))); break;
+      case 11: put(0, F::dot3(arg(0), arg(1), arg(2), arg(3), arg(4), arg(5))); break;
+      case 12:
+        F::mul_pair(arg(0), arg(1), arg(2), arg(3), r0, r1);
+        put(0, r0);
+        put(1, r1);
+        break;
+      case 13:
+        F::sqr_pair(arg(0), arg(1), r0, r1);
+        put(0, r0);
+        put(1, r1);
+        break;
+      case 14:
+        F::dot2_pair(arg(0), arg(1), arg(2), arg(3), arg(4), arg(5), arg(6), arg(7), r0, r1);
+        put(0, r0);
+        put(1, r1);
+        break;
+      case 15: flag(arg(0).is_zero()); break;
+      default: flag(arg(0) == arg(1)); break;
+    }
+  }
+}
+
+// F = Fq, Fr or Fq2
+template <class F>
+inline void field_prim_run(zkpoa_context* ctx, int field, int op, const void* in, void* out, uint64_t n, int raw) {
+  const PrimArity ar = field_prim_arity(field, op);
+  if (ar.in == 0) throw HipError("field_prim: bad field/op");
+  if (n == 0) return;
+  constexpr size_t B = FieldBytes<F>::N;
+  DevBuf din(n * ar.in * B), dout(n * ar.out * B);
+  ZK_HIP(hipMemcpy(din.p, in, n * ar.in * B, hipMemcpyHostToDevice));
+  hipStream_t st = ctx->dev.lanes[0].stream;
+  dim3 grid((uint32_t)((n + 255) / 256));
+  hipLaunchKernelGGL((field_prim_kernel<F>), grid, dim3(256), 0, st, op, (const void*)din.p, dout.p, n, raw);
+  ZK_HIP(hipStreamSynchronize(st));
+  ZK_HIP(hipGetLastError());
+  ZK_HIP(hipMemcpy(out, dout.p, n * ar.out * B, hipMemcpyDeviceToHost));
+}
+
+// curve op: 0 = xyzz_add(a, b XYZZ), 1 = xyzz_add_affine(a, b affine, negate k != 0), 2 = xyzz_dbl(a),
+// 3 = xyzz_dbl_affine(b affine), 4 = xyzz_mul_small(a, k). Results stored as computed (coordinates in [0, 2p)).
+constexpr int kCurvePrimOps = 5;
+
+template <class F>
+__global__ __launch_bounds__(256) void curve_prim_kernel(int op, const void* a, const void* b, const uint32_t* k,
+                                                         void* out, uint64_t n) {
+  uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  XYZZ<F> r;
+  switch (op) {
+    case 0:
+      r = load_xyzz<F>(a, i);
+      xyzz_add(r, load_xyzz<F>(b, i));
+      break;
+    case 1:
+      r = load_xyzz<F>(a, i);
+      xyzz_add_affine(r, load_affine<F>(b, i), k[i] != 0);
+      break;
+    case 2: r = xyzz_dbl(load_xyzz<F>(a, i)); break;
+    case 3: r = xyzz_dbl_affine(load_affine<F>(b, i)); break;
+    default: r = xyzz_mul_small(load_xyzz<F>(a, i), k[i]); break;
+  }
+  constexpr int FB = FieldBytes<F>::N;
+  char* o = reinterpret_cast<char*>(out) + i * (4 * FB);
+  store_prim(o, r.x, 1);
+  store_prim(o + FB, r.y, 1);
+  store_prim(o + 2 * FB, r.zz, 1);
+  store_prim(o + 3 * FB, r.zzz, 1);
+}
+
+template <class F>
+inline void curve_prim_run(zkpoa_context* ctx, int op, const void* a, const void* b, const uint32_t* k, void* out,
+                           uint64_t n) {
+  if (op < 0 || op >= kCurvePrimOps) throw HipError("curve_prim: bad op");
+  if (n == 0) return;
+  constexpr size_t X = MsmSizes<F>::kXyzz;
+  const bool use_a = op != 3, use_b = op <= 1 || op == 3, use_k = op == 1 || op == 4;
+  const size_t bsz = op == 0 ? X : MsmSizes<F>::kAffine;
+  DevBuf da(use_a ? n * X : 0), db(use_b ? n * bsz : 0), dk(use_k ? n * 4 : 0), dout(n * X);
+  if (use_a) ZK_HIP(hipMemcpy(da.p, a, n * X, hipMemcpyHostToDevice));
+  if (use_b) ZK_HIP(hipMemcpy(db.p, b, n * bsz, hipMemcpyHostToDevice));
+  if (use_k) ZK_HIP(hipMemcpy(dk.p, k, n * 4, hipMemcpyHostToDevice));
+  hipStream_t st = ctx->dev.lanes[0].stream;
+  dim3 grid((uint32_t)((n + 255) / 256));
+  hipLaunchKernelGGL((curve_prim_kernel<F>), grid, dim3(256), 0, st, op, (const void*)da.p, (const void*)db.p,
+                     (const uint32_t*)dk.p, dout.p, n);
+  ZK_HIP(hipStreamSynchronize(st));
+  ZK_HIP(hipGetLastError());
+  ZK_HIP(hipMemcpy(out, dout.p, n * X, hipMemcpyDeviceToHost));
+}
 
 }  // namespace zkpoa

@@ -9,6 +9,14 @@ Affine<HFq> host_generator<HFq>() {
 void group_add_run_g1(zkpoa_context* ctx, const void* a, const void* b, void* out, uint64_t n) {
   group_add_run<Fq>(ctx, a, b, out, n);
 }
+void field_prim_run_g1(zkpoa_context* ctx, int field, int op, const void* in, void* out, uint64_t n, int raw) {
+  if (field == 0) field_prim_run<Fq>(ctx, field, op, in, out, n, raw);
+  else field_prim_run<Fr>(ctx, field, op, in, out, n, raw);
+}
+void curve_prim_run_g1(zkpoa_context* ctx, int op, const void* a, const void* b, const uint32_t* k, void* out,
+                       uint64_t n) {
+  curve_prim_run<Fq>(ctx, op, a, b, k, out, n);
+}
 void gen_bases_g1(zkpoa_context* ctx, const uint8_t a_le[32], const uint8_t b_le[32], uint64_t i0, uint64_t n, void* d_out) {
   gen_bases<Fq, HFq>(ctx, a_le, b_le, i0, n, d_out);
 }

@@ -271,6 +271,22 @@ extern "C" int zkpoa_group_add(zkpoa_context* ctx, int group, const void* a, con
   else throw HipError("group_add: group must be 1 or 2");
   ZK_API_END(ctx)
 }
+extern "C" int zkpoa_field_prim(zkpoa_context* ctx, int field, int op, const void* in, void* out, uint64_t n,
+                                int raw) {
+  ZK_API_BEGIN(ctx)
+  if (field == 0 || field == 1) field_prim_run_g1(ctx, field, op, in, out, n, raw);
+  else if (field == 2) field_prim_run_g2(ctx, op, in, out, n, raw);
+  else throw HipError("field_prim: field must be 0, 1 or 2");
+  ZK_API_END(ctx)
+}
+extern "C" int zkpoa_curve_prim(zkpoa_context* ctx, int group, int op, const void* a, const void* b, const uint32_t* k,
+                                void* out, uint64_t n) {
+  ZK_API_BEGIN(ctx)
+  if (group == 1) curve_prim_run_g1(ctx, op, a, b, k, out, n);
+  else if (group == 2) curve_prim_run_g2(ctx, op, a, b, k, out, n);
+  else throw HipError("curve_prim: group must be 1 or 2");
+  ZK_API_END(ctx)
+}
 
 // ---- host-only group helpers ---------------------------------------------------------------------
 template <class HF>

@@ -123,6 +123,13 @@ void msm_density(hipStream_t st, const void* d_scalars, uint64_t n, double out[3
 void msm_set_density_hint(const double* density);   // for the calling thread; nullptr = uniform scalars
 void group_add_run_g1(zkpoa_context* ctx, const void* a, const void* b, void* out, uint64_t n);
 void group_add_run_g2(zkpoa_context* ctx, const void* a, const void* b, void* out, uint64_t n);
+// zkpoa_field_prim / zkpoa_curve_prim (hooks.hip.h): an unknown op throws, also for n == 0
+void field_prim_run_g1(zkpoa_context* ctx, int field, int op, const void* in, void* out, uint64_t n, int raw);
+void field_prim_run_g2(zkpoa_context* ctx, int op, const void* in, void* out, uint64_t n, int raw);
+void curve_prim_run_g1(zkpoa_context* ctx, int op, const void* a, const void* b, const uint32_t* k, void* out,
+                       uint64_t n);
+void curve_prim_run_g2(zkpoa_context* ctx, int op, const void* a, const void* b, const uint32_t* k, void* out,
+                       uint64_t n);
 void gen_bases_g1(zkpoa_context* ctx, const uint8_t a_le[32], const uint8_t b_le[32], uint64_t i0, uint64_t n, void* d_out);
 void gen_bases_g2(zkpoa_context* ctx, const uint8_t a_le[32], const uint8_t b_le[32], uint64_t i0, uint64_t n, void* d_out);
 // shared-sort form (prover: the A, B1 and B2 queries use the same witness scalars): sort once on `lane`
