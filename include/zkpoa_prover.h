@@ -332,7 +332,7 @@ int zkpoa_wtns_check(zkpoa_context* ctx, const char* r1cs_path, const char* wtns
  * same combinations of the ptau's Lagrange-form points, weighted by the r1cs' folds a = A rho, b = B rho, c = C rho.
  * PROVER_OK: both files were read and every check ran; *failed_checks <- a bitmask of ZKPOA_ZKEY_* (0 = the key is good).
  *   HEADER  protocol groth16 and BN254 moduli; alpha1, beta1, beta2 equal the ptau's; gamma2 is the G2 generator
- *   POINTS  every key point on its curve or the all-zero infinity; B2, beta2, gamma2, delta2 in G2 ([r]Q = O); delta1 != O
+ *   POINTS  every key point on its curve or the all-zero infinity; B2, beta2, gamma2, delta2 in G2; delta1 != O
  *   DELTA   e(delta1, G2) = e(G1, delta2)
  *   COEFFS  section 4's records in range, and its folds equal the r1cs' (A with the nPublic + 1 public rows, B)
  *   A, B1, B2  sum rho_i X_i = sum_j (a or b)_j L_j over the matching ptau range
@@ -352,6 +352,37 @@ int zkpoa_wtns_check(zkpoa_context* ctx, const char* r1cs_path, const char* wtns
 #define ZKPOA_ZKEY_ICCH 0x80u
 int zkpoa_zkey_verify(zkpoa_context* ctx, const char* r1cs_path, const char* ptau_path, const char* zkey_path,
                       uint32_t* failed_checks);
+/* `snarkjs powersoftau verify <pot.ptau>` (the reference's TODO at scripts/g16_setup.sh:201, g16_verify.sh:164): do the
+ * powers of a ceremony file belong to one tau, alpha, beta, and does its Lagrange form (sections 12-15, what
+ * zkpoa_zkey_new reads) agree with them? Power p, N = 2^p; T = section 2 (2N - 1 G1 points), U = section 3 (N G2), A, B
+ * = sections 4, 5 (N G1), beta2 = section 6. Random weights (from /dev/urandom, drawn after the file is read): one rho
+ * per power section, one rho_l per Lagrange level; a wrong file passes a check with probability about 2^-220 or less.
+ * PROVER_OK: the file was read and every check ran; *failed_checks <- a bitmask of ZKPOA_PTAU_* (0 = the file is good):
+ *   POINTS   every point on its curve or the all-zero infinity; U, beta2 and section 13 in G2; T_0 and U_0 the
+ *            generators; T_1, A_0, B_0, beta2 != O
+ *   TAU_G1   e(sum_{i<2N-2} rho^i T_i, U_1) = e(sum_{i<2N-2} rho^i T_{i+1}, G2) and e(T_1, G2) = e(G1, U_1)
+ *   TAU_G2   e(T_1, sum_{i<N-1} rho^i U_i) = e(G1, sum_{i<N-1} rho^i U_{i+1})
+ *   ALPHA, BETA  the ratio check of TAU_G1 on A, on B against U_1; BETA also e(B_0, G2) = e(G1, beta2)
+ *   LAGRANGE_TAU_G1 / _TAU_G2 / _ALPHA / _BETA  section 12 / 13 / 14 / 15 agrees with section 2 / 3 / 4 / 5: per level
+ *            of n points, sum_j P(w_n^j) L_j = sum_{i<n} rho_l^i X_i for P(x) = sum_{i<n} (rho_l x)^i (the top level
+ *            p+1 of section 12 on the 2N - 1 powers that exist: P of degree 2N - 2)
+ * info[4] <- power, ceremony power, prepared (sections 12-15 present; 0 = only the powers were checked), the number of
+ * contributions in section 7 (which is not checked otherwise: no transcript hash, no proof of knowledge).
+ * piece_points: points per upload as the sections stream through HBM (0 = derived from free HBM).
+ * PROVER_ERROR (zkpoa_last_error) for a malformed file: bad magic or version, a non-BN254 header, a missing section 1-7,
+ * a power outside [1, 28] (27 when prepared), a section whose length does not fit the power, only some of 12-15, a
+ * coordinate >= q. */
+#define ZKPOA_PTAU_POINTS 0x001u
+#define ZKPOA_PTAU_TAU_G1 0x002u
+#define ZKPOA_PTAU_TAU_G2 0x004u
+#define ZKPOA_PTAU_ALPHA 0x008u
+#define ZKPOA_PTAU_BETA 0x010u
+#define ZKPOA_PTAU_LAGRANGE_TAU_G1 0x020u
+#define ZKPOA_PTAU_LAGRANGE_TAU_G2 0x040u
+#define ZKPOA_PTAU_LAGRANGE_ALPHA 0x080u
+#define ZKPOA_PTAU_LAGRANGE_BETA 0x100u
+int zkpoa_ptau_verify(zkpoa_context* ctx, const char* ptau_path, uint64_t piece_points, uint32_t* failed_checks,
+                      uint32_t info[4]);
 
 /* ---- the step after the path; host only, no GPU ----------------------------------------
  * zkpoa_groth16_verify: `npx snarkjs groth16 verify <vkey> <public> <proof>` (scripts/g16_verify.sh:213-216)

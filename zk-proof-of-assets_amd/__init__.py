@@ -28,13 +28,16 @@ PROVER_ERROR_RUNTIME = 4
 # the bits of zkpoa_zkey_verify's result (include/zkpoa_prover.h ZKPOA_ZKEY_*)
 ZKEY_CHECKS = {"HEADER": 0x01, "POINTS": 0x02, "DELTA": 0x04, "COEFFS": 0x08, "A": 0x10, "B1": 0x20, "B2": 0x40,
                "ICCH": 0x80}
+# the bits of zkpoa_ptau_verify's result (include/zkpoa_prover.h ZKPOA_PTAU_*)
+PTAU_CHECKS = {"POINTS": 0x001, "TAU_G1": 0x002, "TAU_G2": 0x004, "ALPHA": 0x008, "BETA": 0x010,
+               "LAGRANGE_TAU_G1": 0x020, "LAGRANGE_TAU_G2": 0x040, "LAGRANGE_ALPHA": 0x080, "LAGRANGE_BETA": 0x100}
 
 # every symbol include/zkpoa_prover.h declares
 EXPORTS = [
     "groth16_prover", "groth16_prover_zkey_file",
     "zkpoa_context_create", "zkpoa_context_destroy", "zkpoa_last_error",
     "zkpoa_zkey_load", "zkpoa_zkey_free", "zkpoa_zkey_info", "zkpoa_prove",
-    "zkpoa_zkey_load_device", "zkpoa_zkey_load_device_shard", "zkpoa_prove_device", "zkpoa_setup_accumulate", "zkpoa_zkey_new", "zkpoa_zkey_contribute", "zkpoa_wtns_check", "zkpoa_zkey_verify",
+    "zkpoa_zkey_load_device", "zkpoa_zkey_load_device_shard", "zkpoa_prove_device", "zkpoa_setup_accumulate", "zkpoa_zkey_new", "zkpoa_zkey_contribute", "zkpoa_wtns_check", "zkpoa_zkey_verify", "zkpoa_ptau_verify",
     "zkpoa_groth16_prover_files", "zkpoa_set_thread_options", "zkpoa_clear_thread_options", "zkpoa_idle_work", "zkpoa_zkey_load_shard", "zkpoa_zkey_load_shard_ex", "zkpoa_zkey_set_shard", "zkpoa_zkey_header",
     "zkpoa_prove_partials", "zkpoa_prove_partials_device", "zkpoa_prove_assemble",
     "zkpoa_zkey_load_shard_split", "zkpoa_zkey_set_shard_split", "zkpoa_witness_load",
@@ -150,6 +153,8 @@ def lib():
                                        ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         L.zkpoa_zkey_contribute.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
         L.zkpoa_zkey_verify.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
+                                        ctypes.POINTER(ctypes.c_uint32)]
+        L.zkpoa_ptau_verify.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32),
                                         ctypes.POINTER(ctypes.c_uint32)]
         L.zkpoa_zkey_load_device_shard.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint,
                                                    ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int] + \
@@ -441,6 +446,15 @@ class Context:
         self._check(lib().zkpoa_zkey_verify(self._h, os.fsencode(r1cs_path), os.fsencode(ptau_path),
                                             os.fsencode(zkey_path), ctypes.byref(failed)), "zkpoa_zkey_verify")
         return int(failed.value)
+
+    def ptau_verify(self, path, piece_points=0):
+        """`snarkjs powersoftau verify` on a .ptau: -> (bitmask of failed checks (PTAU_CHECKS), 0 = good;
+        (power, ceremony power, prepared, contributions)). piece_points: points per upload (0 = derived from free HBM).
+        A malformed file raises ZkpoaError (include/zkpoa_prover.h: zkpoa_ptau_verify)."""
+        failed, info = ctypes.c_uint32(0), (ctypes.c_uint32 * 4)()
+        self._check(lib().zkpoa_ptau_verify(self._h, os.fsencode(path), int(piece_points), ctypes.byref(failed), info),
+                    "zkpoa_ptau_verify")
+        return int(failed.value), tuple(int(v) for v in info)
 
     def zkey_contribute(self, zkey_in_path, zkey_out_path, delta=None):
         """The arithmetic of `snarkjs zkey contribute` (delta: int in [1, r), None = random)."""

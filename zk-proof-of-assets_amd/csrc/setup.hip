@@ -22,6 +22,7 @@
 #include "msm.hip.h"
 #include "hooks.hip.h"
 #include "pairing.hpp"
+#include "setup_common.hip.h"
 #include "zkpoa_internal.hpp"
 
 #include <fcntl.h>
@@ -42,11 +43,6 @@
 #include <vector>
 
 using namespace zkpoa;
-
-namespace zkpoa {
-template <> Affine<HFq> host_generator<HFq>();     // hooks_g1.hip
-template <> Affine<HFq2> host_generator<HFq2>();   // hooks_g2.hip
-}
 
 namespace {
 
@@ -265,58 +261,6 @@ void setup_scale(zkpoa_context* ctx, const void* d_in, uint64_t n, const uint8_t
 }
 
 // ---- `snarkjs zkey verify` (g16_verify.sh -z): the passes over a key's points and folds -----------------------------------
-// The curve's b in the wire encoding (G1: 3, first 32 B; G2: 3 / (9 + u), 64 B), made on the host.
-struct CurveB {
-  uint4 q[4];
-};
-// One streaming pass over n affine points (wire format): flags |= 1 for a coordinate >= q (the range check of
-// range_check_kernel), |= 2 for a point that is neither on the curve nor the all-zero point at infinity.
-template <class F>
-static __global__ __launch_bounds__(256) void point_check_kernel(const void* __restrict__ pts, uint64_t n, CurveB b,
-                                                                 uint32_t* __restrict__ flags) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  constexpr int kWords = FieldBytes<F>::N / 16;   // 32-byte coordinate words per point: 2 (G1), 4 (G2)
-  const uint4* q = reinterpret_cast<const uint4*>(pts) + (size_t)2 * kWords * i;
-  uint32_t over = 0, nz = 0;
-#pragma unroll
-  for (int w = 0; w < kWords; w++) {
-    const uint4 a = q[2 * w], c = q[2 * w + 1];
-    const uint32_t l[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
-    uint32_t bw = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      (void)subb(l[k], FqParams::P[k], bw);
-      nz |= l[k];
-    }
-    over |= bw ^ 1u;   // no borrow: value >= q
-  }
-  if (over) {
-    atomicOr(flags, 1u);
-    return;
-  }
-  if (!nz) return;
-  const Affine<F> p = load_affine<F>(pts, i);
-  if (p.y.sqr() != p.x.sqr() * p.x + load_field<F>(b.q)) atomicOr(flags, 2u);
-}
-
-// G2 subgroup membership over a whole section: flags |= 4 unless [r]Q = O (the all-zero infinity passes). A fixed
-// double-and-add over the bits of r in XYZZ (r: ScalarArg, top bit 253): every lane follows the same bit pattern, as in
-// setup_scale_kernel, and the additions handle the exceptional cases (P + P, P - P) that points outside G2 can meet.
-static __global__ __launch_bounds__(256) void g2_subgroup_kernel(const void* __restrict__ pts, uint64_t n, ScalarArg r,
-                                                                 uint32_t* __restrict__ flags) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  const Affine<Fq2> p = load_affine<Fq2>(pts, i);
-  if (p.is_inf()) return;
-  XYZZ<Fq2> acc = XYZZ<Fq2>::inf();
-  for (int bit = 253; bit >= 0; bit--) {
-    acc = xyzz_dbl(acc);
-    if ((r.l[bit >> 5] >> (bit & 31)) & 1u) xyzz_add_affine(acc, p, false);
-  }
-  if (!acc.is_inf()) atomicOr(flags, 4u);
-}
-
 // Row j < n of the folds (Montgomery form): rs = [a | b | c] from the r1cs (wtns_check_kernel), ks = [a' | b'] from the
 // key's section 4 (abc_rows_kernel). flags |= 1 where a' != a or b' != b; rs[0, 3n) is then rewritten in place as the
 // standard-form scalars of the MSMs.
@@ -415,41 +359,6 @@ extern "C" int zkpoa_setup_accumulate(zkpoa_context* ctx, int group, const void*
 
 // ---- `snarkjs zkey new <circuit.r1cs> <pot.ptau> <circuit_0.zkey>` (g16_setup.sh:243-246) on files -----------------------
 namespace {
-
-struct SetupError : std::runtime_error {
-  explicit SetupError(const std::string& m) : std::runtime_error(m) {}
-};
-
-uint32_t rd32(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }
-uint64_t rd64(const uint8_t* p) { uint64_t v; memcpy(&v, p, 8); return v; }
-
-struct MappedFile {
-  const uint8_t* p = nullptr;
-  uint64_t size = 0;
-  int fd = -1;
-  explicit MappedFile(const char* path) {
-    fd = open(path, O_RDONLY);
-    if (fd < 0) throw SetupError(std::string("cannot open ") + path);
-    struct stat sb;
-    if (fstat(fd, &sb) != 0 || sb.st_size <= 0) {
-      close(fd);
-      throw SetupError(std::string("cannot stat ") + path);
-    }
-    size = (uint64_t)sb.st_size;
-    void* m = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
-    if (m == MAP_FAILED) {
-      close(fd);
-      throw SetupError(std::string("cannot map ") + path);
-    }
-    p = static_cast<const uint8_t*>(m);
-  }
-  ~MappedFile() {
-    if (p) munmap(const_cast<uint8_t*>(p), size);
-    if (fd >= 0) close(fd);
-  }
-  MappedFile(const MappedFile&) = delete;
-  MappedFile& operator=(const MappedFile&) = delete;
-};
 
 // Output files are written under a temporary name and renamed into place (as prover_main's write_atomic): a failure
 // part-way (ENOSPC, HIP error, kill) never leaves a truncated .zkey under the final name for a later "skip if the zkey
@@ -643,30 +552,6 @@ void dev_check_coords(zkpoa_context* ctx, const void* d, uint64_t count32, const
   if (bad) throw SetupError(std::string(what) + ": a coordinate is not a field element (>= q)");
 }
 
-struct Sec {
-  uint64_t off = 0, len = 0;
-  bool present = false;
-};
-
-// iden3 binary container: magic(4) version(u32) nSections(u32) then { type(u32) size(u64) payload }
-std::map<uint32_t, Sec> bin_sections(const MappedFile& f, const char* magic, uint32_t max_version, const char* what) {
-  if (f.size < 12 || memcmp(f.p, magic, 4) != 0) throw SetupError(std::string(what) + ": bad magic");
-  if (rd32(f.p + 4) > max_version) throw SetupError(std::string(what) + ": unsupported version");
-  const uint32_t n = rd32(f.p + 8);
-  std::map<uint32_t, Sec> out;
-  uint64_t pos = 12;
-  for (uint32_t i = 0; i < n; i++) {
-    if (pos + 12 > f.size) throw SetupError(std::string(what) + ": truncated section table");
-    const uint32_t type = rd32(f.p + pos);
-    const uint64_t len = rd64(f.p + pos + 4);
-    pos += 12;
-    if (len > f.size - pos) throw SetupError(std::string(what) + ": section runs past the end of the file");
-    if (!out.count(type)) out[type] = Sec{pos, len, true};   // the first section of a type (as snarkjs' readers)
-    pos += len;
-  }
-  return out;
-}
-
 struct Term {
   uint32_t c, s;
   uint8_t coef[32];
@@ -760,17 +645,6 @@ void pread_all(int fd, void* dst, uint64_t len, uint64_t off, const char* what) 
     }
   });
 }
-
-struct DevArr {
-  void* p = nullptr;
-  explicit DevArr(size_t bytes) { ZK_HIP(hipMalloc(&p, bytes ? bytes : 1)); }
-  ~DevArr() { if (p) (void)hipFree(p); }
-  DevArr(const DevArr&) = delete;
-  DevArr& operator=(const DevArr&) = delete;
-  void up(const void* src, size_t bytes, size_t at = 0) {
-    if (bytes) ZK_HIP(hipMemcpy(static_cast<char*>(p) + at, src, bytes, hipMemcpyHostToDevice));
-  }
-};
 
 struct Entries {   // one zkpoa_setup_accumulate call; filled in place by several threads (set)
   UVec<uint8_t> coef;
@@ -1333,15 +1207,14 @@ uint32_t zkey_verify(zkpoa_context* ctx, const char* r1cs_path, const char* ptau
   CurveB b1{}, b2{};
   HFq::from_u64(3).to_bytes(&b1.q[0]);
   pairing::twist_b().to_bytes(&b2.q[0]);
-  ScalarArg r_arg;
-  memcpy(r_arg.l, HFrParams::P, 32);
+  const FrobArg frob = frob_arg();
   // flags of point_check_kernel (+ the subgroup pass for G2) over count points at d: range failures throw
   auto check_points = [&](const void* d, uint64_t count, int group, bool subgroup, const char* what) {
     if (!count) return 0u;
     const dim3 grid((uint32_t)((count + 255) / 256));
     if (group == 1) hipLaunchKernelGGL((point_check_kernel<Fq>), grid, dim3(256), 0, st, d, count, b1, fl);
     else hipLaunchKernelGGL((point_check_kernel<Fq2>), grid, dim3(256), 0, st, d, count, b2, fl);
-    if (subgroup) hipLaunchKernelGGL(g2_subgroup_kernel, grid, dim3(256), 0, st, d, count, r_arg, fl);
+    if (subgroup) hipLaunchKernelGGL(g2_subgroup_kernel, grid, dim3(256), 0, st, d, count, frob, fl);
     const uint32_t f = read_flags();
     if (f & 1u) throw SetupError(std::string(what) + ": a coordinate is not a field element (>= q)");
     return f;

@@ -4,6 +4,7 @@
 //     snarkjs zkey contribute <circuit_0.zkey> <circuit_final.zkey> --name="..." -e="..."     (:262-266; arithmetic only)
 //     snarkjs wtns check <circuit.r1cs> <witness.wtns>                                      (scripts/g16_verify.sh:205-210)
 //     snarkjs zkey verify <circuit.r1cs> <pot.ptau> <circuit_final.zkey>                    (scripts/g16_verify.sh -z)
+//     snarkjs powersoftau verify <pot.ptau>              (the TODO at g16_setup.sh:201 and g16_verify.sh:164)
 // Same three file arguments (the words `zkey new` / `groth16 setup` are accepted and ignored, so the command line
 // can be kept as it is with the executable swapped). The .ptau must be prepared for phase 2 (`snarkjs powersoftau
 // prepare phase2`), as snarkjs requires too. Exit status 0 / non-zero + message on stderr.
@@ -68,12 +69,15 @@ static bool delta2_is_gamma2(const char* zkey_path) {
 
 int main(int argc, char** argv) {
   int a = 1;
-  bool contribute = false, check = false, verify = false;
+  bool contribute = false, check = false, verify = false, pverify = false;
   if (argc - a >= 2 && !strcmp(argv[a], "zkey") && !strcmp(argv[a + 1], "contribute")) {
     contribute = true;
     a += 2;
   } else if (argc - a >= 2 && !strcmp(argv[a], "zkey") && !strcmp(argv[a + 1], "verify")) {
     verify = true;
+    a += 2;
+  } else if (argc - a >= 2 && !strcmp(argv[a], "powersoftau") && !strcmp(argv[a + 1], "verify")) {
+    pverify = true;
     a += 2;
   } else if (argc - a >= 2 && !strcmp(argv[a], "wtns") && !strcmp(argv[a + 1], "check")) {
     check = true;
@@ -91,11 +95,12 @@ int main(int argc, char** argv) {
     if (npos < 3) pos[npos] = argv[i];
     npos++;
   }
-  if (npos != (contribute || check ? 2 : 3)) {
+  if (npos != (pverify ? 1 : (contribute || check ? 2 : 3))) {
     fprintf(stderr, "usage: zkpoa-setup [zkey new | groth16 setup] <circuit.r1cs> <pot.ptau> <circuit_0.zkey>\n"
                     "       zkpoa-setup zkey contribute <in.zkey> <out.zkey> [--name=...] [-e=...]\n"
                     "       zkpoa-setup wtns check <circuit.r1cs> <witness.wtns>\n"
-                    "       zkpoa-setup zkey verify <circuit.r1cs> <pot.ptau> <circuit.zkey>\n");
+                    "       zkpoa-setup zkey verify <circuit.r1cs> <pot.ptau> <circuit.zkey>\n"
+                    "       zkpoa-setup powersoftau verify <pot.ptau>\n");
     return 2;
   }
   uint8_t delta[32];
@@ -110,8 +115,8 @@ int main(int argc, char** argv) {
   }
   // `zkey new` / `zkey contribute` run in a worker process and this one leaves as soon as the key is renamed into place
   // (csrc/worker_exit.hpp: a worker that has held ~100 GB of host arrays takes seconds to be dismantled).
-  // (`wtns check` and `zkey verify` write nothing and use no worker)
-  zkpoa::WorkerExit we = zkpoa::WorkerExit::start(!check && !verify, "zkpoa-setup");
+  // (`wtns check`, `zkey verify` and `powersoftau verify` write nothing and use no worker)
+  zkpoa::WorkerExit we = zkpoa::WorkerExit::start(!check && !verify && !pverify, "zkpoa-setup");
   if (we.is_worker()) zkpoa_setup_defer_host_frees(1);
   auto leave = [&](int code) -> int {
     if (we.is_worker()) we.leave(code);
@@ -160,13 +165,40 @@ int main(int argc, char** argv) {
         fprintf(stderr, "[WARN]  zkpoa: delta2 is the generator: the key has had no contribution, anyone can forge proofs with it\n");
       printf("[INFO]  zkpoa: ZKey Ok!\n");
     }
+  } else if (pverify) {   // snarkjs prints "Powers of Tau Ok!" and exits 0, or names what does not hold and exits 1
+    uint32_t failed = 0, info[4] = {0, 0, 0, 0};
+    rc = zkpoa_ptau_verify(ctx, pos[0], 0, &failed, info);
+    if (rc == PROVER_OK) {
+      static const char* const kWhat[9] = {
+          "POINTS: a point is off its curve, a G2 point (section 3, beta2, section 13) is outside G2, T_0 or U_0 is not "
+          "the generator, or T_1, A_0, B_0 or beta2 is zero",
+          "TAU_G1: section 2 (tau^i G1) is not one chain of powers of the tau of U_1",
+          "TAU_G2: section 3 (tau^i G2) is not one chain of powers of the tau of T_1",
+          "ALPHA: section 4 (alpha tau^i G1) is not one chain of powers of tau",
+          "BETA: section 5 (beta tau^i G1) is not one chain of powers of tau, or beta2 does not match it",
+          "LAGRANGE_TAU_G1: section 12 (Lagrange form of tau G1) does not agree with section 2",
+          "LAGRANGE_TAU_G2: section 13 (Lagrange form of tau G2) does not agree with section 3",
+          "LAGRANGE_ALPHA: section 14 (Lagrange form of alpha tau G1) does not agree with section 4",
+          "LAGRANGE_BETA: section 15 (Lagrange form of beta tau G1) does not agree with section 5"};
+      fprintf(stderr, "[WARN]  zkpoa: section 7 (%u contribution(s): transcript hashes, proofs of knowledge) is not checked\n",
+              info[3]);
+      if (!info[2])
+        fprintf(stderr, "[WARN]  zkpoa: the file is not prepared for phase 2 (no sections 12-15): only the powers were checked\n");
+      for (int b = 0; b < 9; b++)
+        if (failed & (1u << b)) fprintf(stderr, "[ERROR] zkpoa: %s\n", kWhat[b]);
+      if (failed) {
+        zkpoa_context_destroy(ctx);
+        return 1;
+      }
+      printf("[INFO]  zkpoa: Powers of Tau Ok!\n");
+    }
   } else {
     rc = contribute ? zkpoa_zkey_contribute(ctx, pos[0], pos[1], delta_p) : zkpoa_zkey_new(ctx, pos[0], pos[1], pos[2]);
   }
   if (rc != PROVER_OK) fprintf(stderr, "zkpoa-setup: %s\n", zkpoa_last_error(ctx));
   if (!we.is_worker()) zkpoa_context_destroy(ctx);
   clock_gettime(CLOCK_MONOTONIC, &t1);
-  if (rc == PROVER_OK && getenv("ZKPOA_VERBOSE") && !check && !verify)
+  if (rc == PROVER_OK && getenv("ZKPOA_VERBOSE") && !check && !verify && !pverify)
     fprintf(stderr, "zkpoa-setup: %s written in %.2f s\n", pos[contribute ? 1 : 2],
             (t1.tv_sec - t0.tv_sec) + (t1.tv_nsec - t0.tv_nsec) / 1e9);
   return leave(rc == PROVER_OK ? 0 : 1);
