@@ -243,5 +243,12 @@ inline Fq12 final_exponentiation(const Fq12& f) {
 
 inline Fq12 pairing(const G2& Q, const G1& P) { return final_exponentiation(miller_loop(Q, P)); }
 
+// e(a, b) == e(c, d), as one product of two pairings
+inline bool pair_eq(const G1& a, const G2& b, const G1& c, const G2& d) {
+  const G2 qs[2] = {b, d};
+  const G1 ps[2] = {a, {c.x, c.y.neg()}};
+  return final_exponentiation(multi_miller_loop(qs, ps, 2)).is_one();
+}
+
 }  // namespace pairing
 }  // namespace zkpoa

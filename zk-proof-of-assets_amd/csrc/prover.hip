@@ -5,6 +5,7 @@
 // (`prover <zkey> <wtns> <proof.json> <public.json>`); algorithm per snarkjs 0.7.2
 // groth16_prove.js as restated in SURVEY.md 3.2 / 8c (the reference vendors no prover source).
 #include "abc.hip.h"
+#include "binfile.hpp"
 #include "msm.hip.h"
 #include "ntt.hip.h"
 #include "zkpoa_internal.hpp"
@@ -62,40 +63,24 @@ const char* req_getenv(const char* name) {
   return getenv(name);
 }
 
-// ---- binfile container: magic[4] u32 version u32 nSections {u32 id u64 len payload}*
+// ---- binfile container (the scan itself: binfile.hpp) with the prover's error texts
 struct Section {
   const uint8_t* p = nullptr;
   uint64_t len = 0;
 };
 typedef std::map<uint32_t, Section> Sections;
 
-uint32_t rd_u32(const uint8_t* p) {
-  uint32_t v;
-  memcpy(&v, p, 4);
-  return v;
-}
-uint64_t rd_u64(const uint8_t* p) {
-  uint64_t v;
-  memcpy(&v, p, 8);
-  return v;
+void check_scan(BinScan r, const char* magic) {
+  static const char* const why[] = {"", "invalid file format (bad magic)", "version not supported",
+                                    "truncated section table", "truncated section"};
+  if (r != kBinOk) throw ProverError(PROVER_ERROR, std::string(magic) + " file: " + why[r]);
 }
 
 Sections parse_binfile(const uint8_t* buf, uint64_t size, const char* magic, uint32_t max_version) {
-  if (size < 12 || memcmp(buf, magic, 4) != 0)
-    throw ProverError(PROVER_ERROR, std::string(magic) + " file: invalid file format (bad magic)");
-  uint32_t version = rd_u32(buf + 4), nsec = rd_u32(buf + 8);
-  if (version > max_version) throw ProverError(PROVER_ERROR, std::string(magic) + " file: version not supported");
+  std::map<uint32_t, Sec> secs;
+  check_scan(bin_scan(buf, size, magic, max_version, secs), magic);
   Sections out;
-  uint64_t pos = 12;
-  for (uint32_t i = 0; i < nsec; i++) {
-    if (pos + 12 > size) throw ProverError(PROVER_ERROR, std::string(magic) + " file: truncated section table");
-    uint32_t id = rd_u32(buf + pos);
-    uint64_t len = rd_u64(buf + pos + 4);
-    pos += 12;
-    if (len > size - pos) throw ProverError(PROVER_ERROR, std::string(magic) + " file: truncated section");
-    if (!out.count(id)) out[id] = Section{buf + pos, len};
-    pos += len;
-  }
+  for (const auto& kv : secs) out[kv.first] = Section{buf + kv.second.off, kv.second.len};
   return out;
 }
 
@@ -105,8 +90,6 @@ const Section& need(const Sections& s, uint32_t id, const char* what) {
   return it->second;
 }
 
-const uint8_t kQ[32] = {0x47, 0xfd, 0x7c, 0xd8, 0x16, 0x8c, 0x20, 0x3c, 0x8d, 0xca, 0x71, 0x68, 0x91, 0x6a, 0x81, 0x97,
-                        0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
 const uint8_t kR[32] = {0x01, 0x00, 0x00, 0xf0, 0x93, 0xf5, 0xe1, 0x43, 0x91, 0x70, 0xb9, 0x79, 0x48, 0xe8, 0x33, 0x28,
                         0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
 
@@ -275,71 +258,30 @@ void range_check(hipStream_t st, const void* d, uint64_t count, uint32_t* d_flag
     hipLaunchKernelGGL((range_check_kernel<PRM>), dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, st, d, count, d_flag);
 }
 
-// list of the constraints too long for one lane (key-dependent only); returns the count, *list owned by the caller
-uint32_t build_long_list(hipStream_t st, const uint32_t* d_row_ptr, uint32_t rows, uint32_t** list) {
-  DevBuf cnt(64);
-  *list = nullptr;
-  uint32_t n_long = 0;
-  const uint32_t grid = (rows / 2 + 255) / 256;
-  ZK_HIP(hipMemsetAsync(cnt.p, 0, 64, st));
-  hipLaunchKernelGGL(abc_long_list_kernel, dim3(grid), dim3(256), 0, st, d_row_ptr, rows, (uint32_t*)cnt.p,
-                     (uint32_t*)nullptr);
-  ZK_HIP(hipMemcpyAsync(&n_long, cnt.p, 4, hipMemcpyDeviceToHost, st));
-  ZK_HIP(hipStreamSynchronize(st));
-  ZK_HIP(hipMalloc(reinterpret_cast<void**>(list), (size_t)(n_long ? n_long : 1) * 4));
-  if (n_long) {
-    ZK_HIP(hipMemsetAsync(cnt.p, 0, 64, st));
-    hipLaunchKernelGGL(abc_long_list_kernel, dim3(grid), dim3(256), 0, st, d_row_ptr, rows, (uint32_t*)cnt.p, *list);
-    ZK_HIP(hipStreamSynchronize(st));
-  }
-  ZK_HIP(hipGetLastError());
-  return n_long;
-}
-
-// CSR of the coefficient list by output row (2*c + m); d_recs = device copy of the 44-byte records.
+// CSR of the coefficient list by output row (2*c + m), into the handle; d_recs = device copy of the 44-byte records.
 // Also allocates the A/B/C work area and the witness buffer. With split_log > 0 (split chain loaded from a
 // file) only the records of this rank's constraints are kept, rows renumbered c >> split_log.
 void build_csr(zkpoa_context* ctx, zkpoa_zkey* zk, const void* d_recs, bool local_rows = false, hipStream_t st_in = nullptr) {
   hipStream_t st = st_in ? st_in : ctx->dev.lanes[0].stream;
   const uint32_t lp = local_rows ? zk->split_log : 0u, part = local_rows ? zk->split_rank : 0u;
-  const uint32_t rows = 2 * (zk->domain >> lp);
   const uint64_t n = zk->domain, m = zk->nVars;
   // work area: the chain transforms A_T, B_T, C_T in place (a split shard: its n / G rows of each)
   if (!zk->d_abc) ZK_HIP(hipMalloc(&zk->d_abc, (size_t)3 * (n >> lp) * 32));
   if (!zk->d_witness) ZK_HIP(hipMalloc(&zk->d_witness, (size_t)m * 32));
   if (!zk->d_flag) ZK_HIP(hipMalloc(reinterpret_cast<void**>(&zk->d_flag), 1024));   // + scratch of msm_density at +256
-  DevBuf d_cnt((size_t)rows * 4), d_rank((size_t)(zk->nCoefs ? zk->nCoefs : 1) * 4),
-      d_bs(((size_t)rows / kScanTile + 2) * 4), d_misc(64);
-  ZK_HIP(hipMalloc(&zk->d_row_ptr, ((size_t)rows + 1) * 4));
-  ZK_HIP(hipMemsetAsync(d_cnt.p, 0, (size_t)rows * 4, st));
-  ZK_HIP(hipMemsetAsync(d_misc.p, 0, 64, st));
-  uint32_t* misc = (uint32_t*)d_misc.p;
-  uint32_t grid = (uint32_t)((zk->nCoefs + 255) / 256);
-  uint32_t herr = 0, total = 0;
-  if (zk->nCoefs) {
-    hipLaunchKernelGGL(abc_count_kernel, dim3(grid), dim3(256), 0, st, (const CoefRec*)d_recs, zk->nCoefs, zk->domain,
-                       zk->nVars, lp, part, (uint32_t*)d_cnt.p, (uint32_t*)d_rank.p, misc + 4);
-    scan_u32(st, (const uint32_t*)d_cnt.p, rows, 0, 0, zk->d_row_ptr, (uint32_t*)d_bs.p, misc, nullptr);
-    ZK_HIP(hipMemcpyAsync(&total, zk->d_row_ptr + rows, 4, hipMemcpyDeviceToHost, st));
-  } else {
-    ZK_HIP(hipMemsetAsync(zk->d_row_ptr, 0, ((size_t)rows + 1) * 4, st));
-  }
-  ZK_HIP(hipMemcpyAsync(&herr, misc + 4, 4, hipMemcpyDeviceToHost, st));
-  ZK_HIP(hipStreamSynchronize(st));
-  ZK_HIP(hipGetLastError());
-  if (herr & 2u) throw ProverError(PROVER_ERROR, "zkey coefficient value is not a field element (>= r)");
-  if (herr) throw ProverError(PROVER_ERROR, "zkey coefficient record out of range (matrix/constraint/signal)");
-  zk->nCoefsLocal = total;
+  AbcCsr csr;
+  abc_build_csr(st, d_recs, zk->nCoefs, zk->domain, zk->nVars, lp, part, csr);
+  if (csr.err & 2u) throw ProverError(PROVER_ERROR, "zkey coefficient value is not a field element (>= r)");
+  if (csr.err) throw ProverError(PROVER_ERROR, "zkey coefficient record out of range (matrix/constraint/signal)");
+  zk->nCoefsLocal = csr.total;
   zk->csr_local = local_rows;
-  ZK_HIP(hipMalloc(&zk->d_sig, (size_t)(total ? total : 1) * 4));
-  ZK_HIP(hipMalloc(&zk->d_vals, (size_t)(total ? total : 1) * 32));
-  if (zk->nCoefs) {
-    hipLaunchKernelGGL(abc_scatter_kernel, dim3(grid), dim3(256), 0, st, (const CoefRec*)d_recs, zk->nCoefs, lp,
-                       (const uint32_t*)zk->d_row_ptr, (const uint32_t*)d_rank.p, zk->d_sig, zk->d_vals);
-    ZK_HIP(hipStreamSynchronize(st));
-    ZK_HIP(hipGetLastError());
-  }
-  zk->n_long = build_long_list(st, zk->d_row_ptr, rows, &zk->d_long);
+  zk->d_row_ptr = csr.row_ptr;   // the handle owns the arrays from here (zkpoa_zkey::release)
+  zk->d_sig = csr.sig;
+  zk->d_vals = csr.vals;
+  zk->d_long = csr.long_list;
+  zk->n_long = csr.n_long;
+  csr.row_ptr = csr.sig = csr.long_list = nullptr;
+  csr.vals = nullptr;
 }
 
 // split chain: world must be a power of two <= 8 with world^2 <= domain (every rank owns whole slots of
@@ -428,51 +370,42 @@ struct ZkeySections {
 std::unique_ptr<zkpoa_zkey> zkey_parse(const uint8_t* buf, uint64_t size, ZkeySections& out) {
   Sections secs = parse_binfile(buf, size, "zkey", 2);
   const Section& s1 = need(secs, 1, "1 (protocol)");
-  if (s1.len < 4 || rd_u32(s1.p) != 1) throw ProverError(PROVER_ERROR, "zkey file is not groth16");
+  if (s1.len < 4 || rd32(s1.p) != 1) throw ProverError(PROVER_ERROR, "zkey file is not groth16");
   const Section& s2 = need(secs, 2, "2 (groth16 header)");
-  const uint64_t hdr = 4 + 32 + 4 + 32 + 12 + 64 + 64 + 128 + 128 + 64 + 128;
-  if (s2.len < hdr) throw ProverError(PROVER_ERROR, "zkey header too short");
-  const uint8_t* p = s2.p;
-  if (rd_u32(p) != 32 || memcmp(p + 4, kQ, 32) != 0) throw ProverError(PROVER_ERROR, "zkey curve not supported (q is not BN254)");
-  p += 36;
-  if (rd_u32(p) != 32 || memcmp(p + 4, kR, 32) != 0) throw ProverError(PROVER_ERROR, "zkey curve not supported (r is not BN254)");
-  p += 36;
+  if (s2.len < kHdrLen) throw ProverError(PROVER_ERROR, "zkey header too short");
+  const ZkeyHeader h = read_zkey_header(s2.p);
+  if (h.n8q != 32 || !h.q_ok) throw ProverError(PROVER_ERROR, "zkey curve not supported (q is not BN254)");
+  if (h.n8r != 32 || !h.r_ok) throw ProverError(PROVER_ERROR, "zkey curve not supported (r is not BN254)");
   std::unique_ptr<zkpoa_zkey> zk(new zkpoa_zkey());
-  zk->nVars = rd_u32(p);
-  zk->nPublic = rd_u32(p + 4);
-  zk->domain = rd_u32(p + 8);
-  p += 12;
+  zk->nVars = h.nVars;
+  zk->nPublic = h.nPublic;
+  zk->domain = h.domain;
   if (zk->domain == 0 || (zk->domain & (zk->domain - 1))) throw ProverError(PROVER_ERROR, "zkey domainSize is not a power of two");
   zk->power = 0;
   while ((1u << zk->power) < zk->domain) zk->power++;
   if (zk->power > 28) throw ProverError(PROVER_ERROR, "zkey domainSize exceeds 2^28");
   if (zk->nPublic + 1 > zk->nVars) throw ProverError(PROVER_ERROR, "zkey nPublic >= nVars");
-  zk->alpha1 = h_affine_from_bytes<HFq>(p); p += 64;
-  zk->beta1 = h_affine_from_bytes<HFq>(p); p += 64;
-  const uint8_t* p_alpha1 = p - 128;
-  const uint8_t* p_beta2 = p;
-  zk->beta2 = h_affine_from_bytes<HFq2>(p); p += 128;
-  const uint8_t* p_gamma2 = p;
-  p += 128;  // gamma2: verifier only (kept for the self-check)
-  zk->delta1 = h_affine_from_bytes<HFq>(p); p += 64;
-  const uint8_t* p_delta2 = p;
-  zk->delta2 = h_affine_from_bytes<HFq2>(p);
+  zk->alpha1 = h_affine_from_bytes<HFq>(h.alpha1);
+  zk->beta1 = h_affine_from_bytes<HFq>(h.beta1);
+  zk->beta2 = h_affine_from_bytes<HFq2>(h.beta2);
+  zk->delta1 = h_affine_from_bytes<HFq>(h.delta1);
+  zk->delta2 = h_affine_from_bytes<HFq2>(h.delta2);
   // section 3 (IC) is optional for proving; with it the handle can verify its own proofs
   {
     auto it3 = secs.find(3);
     if (it3 != secs.end() && it3->second.len == ((uint64_t)zk->nPublic + 1) * 64) {
       zk->vkey_points.resize(448 + it3->second.len);
       uint8_t* v = zk->vkey_points.data();
-      memcpy(v, p_alpha1, 64);
-      memcpy(v + 64, p_beta2, 128);
-      memcpy(v + 192, p_gamma2, 128);
-      memcpy(v + 320, p_delta2, 128);
+      memcpy(v, h.alpha1, 64);
+      memcpy(v + 64, h.beta2, 128);
+      memcpy(v + 192, h.gamma2, 128);   // verifier only: kept for the self-check
+      memcpy(v + 320, h.delta2, 128);
       memcpy(v + 448, it3->second.p, it3->second.len);
     }
   }
   out.s4 = need(secs, 4, "4 (coefficients)");
   if (out.s4.len < 4) throw ProverError(PROVER_ERROR, "zkey coefficient section too short");
-  zk->nCoefs = rd_u32(out.s4.p);
+  zk->nCoefs = rd32(out.s4.p);
   if (out.s4.len != 4 + zk->nCoefs * 44) throw ProverError(PROVER_ERROR, "zkey coefficient section has the wrong size");
   out.s5 = need(secs, 5, "5 (A points)");
   out.s6 = need(secs, 6, "6 (B1 points)");
@@ -688,14 +621,8 @@ HFr hfr_from_le(const uint8_t* le) { return HFr::from_bytes(le); }
 // uniform on [0, r): 254 random bits, rejected while >= r (about one draw in four is), as Groth16's zero-knowledge
 // argument assumes and as snarkjs' Fr.random() samples
 void random_scalar(uint8_t out[32]) {
-  int fd = open("/dev/urandom", O_RDONLY);
-  if (fd < 0) throw ProverError(PROVER_ERROR, "cannot open /dev/urandom");
   for (;;) {
-    ssize_t got = read(fd, out, 32);
-    if (got != 32) {
-      close(fd);
-      throw ProverError(PROVER_ERROR, "short read from /dev/urandom");
-    }
+    if (const char* err = read_urandom(out, 32)) throw ProverError(PROVER_ERROR, err);
     out[31] &= 0x3f;   // 254 bits
     bool below = false;
     for (int i = 31; i >= 0; i--) {
@@ -704,7 +631,6 @@ void random_scalar(uint8_t out[32]) {
     }
     if (below) break;
   }
-  close(fd);
 }
 
 bool parse_decimal_mod_r(const char* s, uint8_t out[32]) {
@@ -763,18 +689,18 @@ struct WtnsView {
 WtnsView parse_wtns(const uint8_t* buf, uint64_t size) {
   Sections secs = parse_binfile(buf, size, "wtns", 2);
   const Section& s1 = need(secs, 1, "1 (wtns header)");
-  if (s1.len < 40 || rd_u32(s1.p) != 32) throw ProverError(PROVER_ERROR, "wtns header: unsupported field size");
+  if (s1.len < 40 || rd32(s1.p) != 32) throw ProverError(PROVER_ERROR, "wtns header: unsupported field size");
   if (memcmp(s1.p + 4, kR, 32) != 0)
     throw ProverError(PROVER_ERROR, "Curve of the witness does not match the curve of the proving key");
   WtnsView w;
-  w.n = rd_u32(s1.p + 36);
+  w.n = rd32(s1.p + 36);
   const Section& s2 = need(secs, 2, "2 (wtns values)");
   if (s2.len != (uint64_t)w.n * 32) throw ProverError(PROVER_ERROR, "wtns value section has the wrong size");
   w.values = s2.p;
   return w;
 }
 
-// the same container walk on an open file: 12 bytes per section header are read, payloads are skipped
+// the same on an open file: 12 bytes per section header are read, payloads are skipped
 WtnsView parse_wtns_fd(int fd, uint64_t size) {
   auto rd = [&](uint64_t pos, void* out, size_t len) {
     size_t got = 0;
@@ -784,35 +710,19 @@ WtnsView parse_wtns_fd(int fd, uint64_t size) {
       got += (size_t)r;
     }
   };
-  uint8_t head[12];
-  if (size < 12) throw ProverError(PROVER_ERROR, "wtns file: invalid file format (bad magic)");
-  rd(0, head, 12);
-  if (memcmp(head, "wtns", 4) != 0) throw ProverError(PROVER_ERROR, "wtns file: invalid file format (bad magic)");
-  if (rd_u32(head + 4) > 2) throw ProverError(PROVER_ERROR, "wtns file: version not supported");
-  const uint32_t nsec = rd_u32(head + 8);
-  uint64_t pos = 12, off1 = 0, len1 = 0, off2 = 0, len2 = 0;
-  bool have1 = false, have2 = false;
-  for (uint32_t i = 0; i < nsec; i++) {
-    if (pos + 12 > size) throw ProverError(PROVER_ERROR, "wtns file: truncated section table");
-    uint8_t sh[12];
-    rd(pos, sh, 12);
-    const uint32_t id = rd_u32(sh);
-    const uint64_t len = rd_u64(sh + 4);
-    pos += 12;
-    if (len > size - pos) throw ProverError(PROVER_ERROR, "wtns file: truncated section");
-    if (id == 1 && !have1) { have1 = true; off1 = pos; len1 = len; }
-    if (id == 2 && !have2) { have2 = true; off2 = pos; len2 = len; }
-    pos += len;
-  }
+  std::map<uint32_t, Sec> secs;
+  check_scan(bin_scan(rd, size, "wtns", 2, secs), "wtns");
+  const bool have1 = secs.count(1), have2 = secs.count(2);
+  const uint64_t off1 = secs[1].off, len1 = secs[1].len, off2 = secs[2].off, len2 = secs[2].len;
   if (!have1) throw ProverError(PROVER_ERROR, "missing section 1 (wtns header)");
   uint8_t h1[40];
   if (len1 < 40) throw ProverError(PROVER_ERROR, "wtns header: unsupported field size");
   rd(off1, h1, 40);
-  if (rd_u32(h1) != 32) throw ProverError(PROVER_ERROR, "wtns header: unsupported field size");
+  if (rd32(h1) != 32) throw ProverError(PROVER_ERROR, "wtns header: unsupported field size");
   if (memcmp(h1 + 4, kR, 32) != 0)
     throw ProverError(PROVER_ERROR, "Curve of the witness does not match the curve of the proving key");
   WtnsView w;
-  w.n = rd_u32(h1 + 36);
+  w.n = rd32(h1 + 36);
   if (!have2) throw ProverError(PROVER_ERROR, "missing section 2 (wtns values)");
   if (len2 != (uint64_t)w.n * 32) throw ProverError(PROVER_ERROR, "wtns value section has the wrong size");
   w.fd = fd;
@@ -2713,47 +2623,23 @@ extern "C" int zkpoa_h_scalars(zkpoa_context* ctx, const void* coeffs, unsigned 
     if (log_domain > 28) throw ProverError(PROVER_ERROR, "h_scalars: log_domain > 28");
     const uint8_t* cb = reinterpret_cast<const uint8_t*>(coeffs);
     if (coeffs_size < 4) throw ProverError(PROVER_ERROR, "h_scalars: coefficient payload too short");
-    uint64_t ncoef = rd_u32(cb);
+    uint64_t ncoef = rd32(cb);
     if (coeffs_size != 4 + ncoef * 44) throw ProverError(PROVER_ERROR, "h_scalars: coefficient payload has the wrong size");
-    const uint32_t domain = 1u << log_domain, rows = 2 * domain;
+    const uint32_t domain = 1u << log_domain;
     hipStream_t st = ctx->dev.lanes[0].stream;
-    DevBuf recs(ncoef * 44), cnt((size_t)rows * 4), rank((ncoef ? ncoef : 1) * 4), bs(((size_t)rows / kScanTile + 2) * 4),
-        misc(64), row_ptr(((size_t)rows + 1) * 4), sig((ncoef ? ncoef : 1) * 4), vals((ncoef ? ncoef : 1) * 32),
-        abc((size_t)3 * domain * 32), wit(n_vars * 32);
+    DevBuf recs(ncoef * 44), abc((size_t)3 * domain * 32), wit(n_vars * 32);
     ZK_HIP(hipMemcpy(recs.p, cb + 4, ncoef * 44, hipMemcpyHostToDevice));
     ZK_HIP(hipMemcpy(wit.p, witness, n_vars * 32, hipMemcpyHostToDevice));
-    ZK_HIP(hipMemsetAsync(cnt.p, 0, (size_t)rows * 4, st));
-    ZK_HIP(hipMemsetAsync(misc.p, 0, 64, st));
-    ZK_HIP(hipMemsetAsync(row_ptr.p, 0, ((size_t)rows + 1) * 4, st));
-    if (ncoef) {
-      uint32_t grid = (uint32_t)((ncoef + 255) / 256);
-      hipLaunchKernelGGL(abc_count_kernel, dim3(grid), dim3(256), 0, st, (const CoefRec*)recs.p, ncoef, domain,
-                         (uint32_t)n_vars, 0u, 0u, (uint32_t*)cnt.p, (uint32_t*)rank.p, (uint32_t*)misc.p + 4);
-      scan_u32(st, (const uint32_t*)cnt.p, rows, 0, 0, (uint32_t*)row_ptr.p, (uint32_t*)bs.p, (uint32_t*)misc.p,
-               nullptr);
-      hipLaunchKernelGGL(abc_scatter_kernel, dim3(grid), dim3(256), 0, st, (const CoefRec*)recs.p, ncoef, 0u,
-                         (const uint32_t*)row_ptr.p, (const uint32_t*)rank.p, (uint32_t*)sig.p, vals.p);
-    }
-    uint32_t herr = 0;
-    ZK_HIP(hipMemcpyAsync(&herr, (uint32_t*)misc.p + 4, 4, hipMemcpyDeviceToHost, st));
-    ZK_HIP(hipStreamSynchronize(st));
-    if (herr) throw ProverError(PROVER_ERROR, "h_scalars: coefficient record out of range or value >= r");
+    AbcCsr csr;
+    abc_build_csr(st, recs.p, ncoef, domain, (uint32_t)n_vars, 0u, 0u, csr);
+    if (csr.err) throw ProverError(PROVER_ERROR, "h_scalars: coefficient record out of range or value >= r");
     ntt_prepare(ctx, st, log_domain);
-    uint32_t* long_list = nullptr;
-    uint32_t n_long = build_long_list(st, (const uint32_t*)row_ptr.p, rows, &long_list);
     ZK_HIP(hipEventRecord(ctx->ev_a[5], st));
-    try {
-      h_chain(ctx, st, (const uint32_t*)row_ptr.p, (const uint32_t*)sig.p, vals.p, long_list, n_long, wit.p, domain,
-              log_domain, abc.p);
-    } catch (...) {
-      (void)hipFree(long_list);
-      throw;
-    }
+    h_chain(ctx, st, csr.row_ptr, csr.sig, csr.vals, csr.long_list, csr.n_long, wit.p, domain, log_domain, abc.p);
     ZK_HIP(hipEventRecord(ctx->ev_b[5], st));
     ZK_HIP(hipStreamSynchronize(st));
     ZK_HIP(hipGetLastError());
     ZK_HIP(hipEventElapsedTime(&ctx->ms[3], ctx->ev_a[5], ctx->ev_b[5]));
-    (void)hipFree(long_list);
     ZK_HIP(hipMemcpy(out, abc.p, (size_t)domain * 32, hipMemcpyDeviceToHost));
   }
   ZK_PROVER_CATCH(ctx)

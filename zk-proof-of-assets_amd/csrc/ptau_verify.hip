@@ -21,7 +21,6 @@
 #include "setup_common.hip.h"
 #include "zkpoa_internal.hpp"
 
-#include <time.h>
 #include <type_traits>
 #include <vector>
 
@@ -168,17 +167,12 @@ struct Streamer {
   int fd;
   uint64_t piece;
   hipStream_t st;
-  DevArr pts, w1, w2, flags;
+  DevBuf pts, w1, w2;
   const PtauLevel* d_lv;
-  CurveB b1{}, b2{};
-  FrobArg frob;
+  PointChecker points;
   bool bad_points = false;   // a point off its curve or (subgroup) outside G2
   Streamer(zkpoa_context* c, int f, uint64_t pc, const PtauLevel* lv)
-      : ctx(c), fd(f), piece(pc), st(c->dev.lanes[0].stream), pts(pc * 128), w1(pc * 32), w2(pc * 32), flags(64),
-        d_lv(lv), frob(frob_arg()) {
-    HFq::from_u64(3).to_bytes(&b1.q[0]);
-    pairing::twist_b().to_bytes(&b2.q[0]);
-  }
+      : ctx(c), fd(f), piece(pc), st(c->dev.lanes[0].stream), pts(pc * 128), w1(pc * 32), w2(pc * 32), d_lv(lv), points(c) {}
   enum Mode { kCheck, kPower, kLagrange };
   // kPower: *ratio += sum rho^i X_i and, with n_levels, *lag += sum s_i X_i; kLagrange: *lag += sum P_l(w^j) X_{l,j}
   template <class HF>
@@ -189,17 +183,7 @@ struct Streamer {
     for (uint64_t i0 = 0; i0 < K; i0 += piece) {
       const uint64_t cnt = K - i0 < piece ? K - i0 : piece;
       ctx->uploader.upload(pts.p, nullptr, cnt * unit, ctx->dev.device, st, fd, sc.off + i0 * unit);
-      const dim3 grid((uint32_t)((cnt + 255) / 256));
-      ZK_HIP(hipMemsetAsync(flags.p, 0, 4, st));
-      if (kG2) hipLaunchKernelGGL((point_check_kernel<Fq2>), grid, dim3(256), 0, st, pts.p, cnt, b2, (uint32_t*)flags.p);
-      else hipLaunchKernelGGL((point_check_kernel<Fq>), grid, dim3(256), 0, st, pts.p, cnt, b1, (uint32_t*)flags.p);
-      if (subgroup) hipLaunchKernelGGL(g2_subgroup_kernel, grid, dim3(256), 0, st, pts.p, cnt, frob, (uint32_t*)flags.p);
-      uint32_t f = 0;
-      ZK_HIP(hipMemcpyAsync(&f, flags.p, 4, hipMemcpyDeviceToHost, st));
-      ZK_HIP(hipStreamSynchronize(st));
-      ZK_HIP(hipGetLastError());
-      if (f & 1u) throw SetupError(std::string(what) + ": a coordinate is not a field element (>= q)");
-      if (f & 6u) bad_points = true;
+      if (points.check(pts.p, cnt, kG2 ? 2 : 1, subgroup, what) & 6u) bad_points = true;
       if (mode == kCheck) continue;
       const dim3 wgrid((uint32_t)((cnt + 256 * kRun - 1) / (256 * kRun)));
       if (mode == kPower)
@@ -223,22 +207,12 @@ struct Streamer {
   }
 };
 
-// e(a, b) == e(c, d)
-bool pair_eq(const pairing::G1& a, const pairing::G2& b, const pairing::G1& c, const pairing::G2& d) {
-  const pairing::G2 qs[2] = {b, d};
-  const pairing::G1 ps[2] = {a, {c.x, c.y.neg()}};
-  return pairing::final_exponentiation(pairing::multi_miller_loop(qs, ps, 2)).is_one();
-}
+using pairing::pair_eq;
 
-HFr draw_nonzero(int fd) {   // 253 random bits from /dev/urandom (below r), Montgomery form; 0 is drawn again
+HFr draw_nonzero() {   // 253 random bits from /dev/urandom (below r), Montgomery form; 0 is drawn again
   for (;;) {
     uint8_t b[32];
-    uint64_t got = 0;
-    while (got < 32) {
-      const ssize_t k = read(fd, b + got, 32 - got);
-      if (k <= 0) throw SetupError("short read from /dev/urandom");
-      got += (uint64_t)k;
-    }
+    urandom(b, 32);
     b[31] &= 0x1f;
     const HFr v = HFr::from_bytes(b);
     if (v.l[0] | v.l[1] | v.l[2] | v.l[3]) return v.to_mont();
@@ -246,27 +220,14 @@ HFr draw_nonzero(int fd) {   // 253 random bits from /dev/urandom (below r), Mon
 }
 
 uint32_t ptau_verify(zkpoa_context* ctx, const char* path, uint64_t piece_points, uint32_t info[4]) {
-  const bool verbose = getenv("ZKPOA_VERBOSE") != nullptr;
-  struct timespec tp0;
-  clock_gettime(CLOCK_MONOTONIC, &tp0);
-  auto phase = [&](const char* what) {
-    if (!verbose) return;
-    struct timespec t;
-    clock_gettime(CLOCK_MONOTONIC, &t);
-    fprintf(stderr, "zkpoa: powersoftau verify: %-34s %8.1f ms\n", what,
-            (t.tv_sec - tp0.tv_sec) * 1e3 + (t.tv_nsec - tp0.tv_nsec) / 1e6);
-    tp0 = t;
-  };
+  PhaseTimer phase("powersoftau verify", 34);
   // ---- the file's shape: anything that contradicts the header is a malformed file
   MappedFile fp(path);   // mapped for the section table and a few single points; the sections stream with pread
   auto ps = bin_sections(fp, "ptau", 1, "ptau");
   for (uint32_t t = 1; t <= 7; t++)
     if (!ps.count(t)) throw SetupError("ptau: section " + std::to_string(t) + " missing");
-  const Sec h = ps[1];
-  if (h.len < 4 + 32 + 8 || rd32(fp.p + h.off) != 32) throw SetupError("ptau: header too short or field size != 32");
-  for (int i = 0; i < 4; i++)
-    if (rd64(fp.p + h.off + 4 + 8 * i) != HFqParams::P[i]) throw SetupError("ptau: not a BN254 ceremony");
-  const uint32_t power = rd32(fp.p + h.off + 36), ceremony = rd32(fp.p + h.off + 40);
+  uint32_t ceremony = 0;
+  const uint32_t power = ptau_header(fp, ps[1], &ceremony);
   if (power < 1 || power > 28) throw SetupError("ptau: power " + std::to_string(power) + " is outside [1, 28]");
   const uint64_t N = 1ull << power;
   const uint64_t want[8] = {0, 0, (2 * N - 1) * 64, N * 128, N * 64, N * 64, 128, 0};
@@ -293,16 +254,10 @@ uint32_t ptau_verify(zkpoa_context* ctx, const char* path, uint64_t piece_points
   HFr rho_T, rho_U, rho_A, rho_B;
   std::vector<PtauLevel> lv(n_levels ? n_levels : 1);
   {
-    const int rfd = open("/dev/urandom", O_RDONLY);
-    if (rfd < 0) throw SetupError("cannot open /dev/urandom");
-    struct Closer {
-      int fd;
-      ~Closer() { close(fd); }
-    } closer{rfd};
-    rho_T = draw_nonzero(rfd);
-    rho_U = draw_nonzero(rfd);
-    rho_A = draw_nonzero(rfd);
-    rho_B = draw_nonzero(rfd);
+    rho_T = draw_nonzero();
+    rho_U = draw_nonzero();
+    rho_A = draw_nonzero();
+    rho_B = draw_nonzero();
     // w_{2^28} = 5^((r - 1) / 2^28); w_{2^l} = w_{2^28}^(2^(28 - l))
     uint64_t e[4];
     for (int i = 0; i < 4; i++) e[i] = (HFrParams::P[i] >> 28) | (i < 3 ? HFrParams::P[i + 1] << 36 : 0);
@@ -312,7 +267,7 @@ uint32_t ptau_verify(zkpoa_context* ctx, const char* path, uint64_t piece_points
       for (uint32_t s = l; s < 28; s++) w = w.sqr();
       HFr rho, rho_n;
       do {   // rho^n = 1 would make a denominator 1 - rho w^j zero
-        rho = draw_nonzero(rfd);
+        rho = draw_nonzero();
         rho_n = rho;
         for (uint32_t s = 0; s < l; s++) rho_n = rho_n.sqr();
       } while (rho_n == HFr::one());
@@ -325,7 +280,7 @@ uint32_t ptau_verify(zkpoa_context* ctx, const char* path, uint64_t piece_points
       L.c = fr_dev(L.top ? rho_n * rho.inv() : HFr::one() - rho_n);
     }
   }
-  DevArr d_lv(lv.size() * sizeof(PtauLevel));
+  DevBuf d_lv(lv.size() * sizeof(PtauLevel));
   d_lv.up(lv.data(), lv.size() * sizeof(PtauLevel));
   phase("random weights");
 

@@ -1,10 +1,15 @@
-// What the file commands of csrc/setup.hip (`zkey new`, `zkey verify`, ...) and csrc/ptau_verify.hip
-// (`powersoftau verify`) share: the iden3 binary container, and the device passes that check the points of a section
-// (curve, range, G2 subgroup). Internal linkage: each translation unit has its own copy.
+// What the file commands of csrc/setup.hip (`zkey new`, `zkey contribute`, `wtns check`), csrc/zkey_verify.hip
+// (`zkey verify`) and csrc/ptau_verify.hip (`powersoftau verify`) share: mapped files and their section tables
+// (the scan itself: binfile.hpp), the ptau header, the ZKPOA_VERBOSE phase timer, host threads and arrays, the r1cs
+// parser and its CSR, the ptau ranges a key is made from, the constraint-fold kernels, and the device passes that
+// check the points of a section (curve, range, G2 subgroup). Internal linkage: each translation unit has its own copy.
 #pragma once
+#include "binfile.hpp"
 #include "bn254_ec.hip.h"
 #include "device_ctx.hpp"
+#include "msm.hip.h"
 #include "pairing.hpp"
+#include "zkpoa_internal.hpp"
 
 #include <fcntl.h>
 #include <string.h>
@@ -12,9 +17,17 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <time.h>
+
+#include <algorithm>
+#include <atomic>
+#include <exception>
 #include <map>
+#include <memory>
 #include <stdexcept>
 #include <string>
+#include <thread>
+#include <vector>
 
 using namespace zkpoa;
 
@@ -23,6 +36,12 @@ template <class HF>
 Affine<HF> host_generator();
 template <> Affine<HFq> host_generator<HFq>();     // hooks_g1.hip
 template <> Affine<HFq2> host_generator<HFq2>();   // hooks_g2.hip
+// One-shot commands (zkpoa-setup) leave the tens of GB of host arrays of a `zkey new` to the process's exit: giving
+// 100 GB back page by page takes seconds that nobody is waiting for any more (zkpoa_setup_defer_host_frees).
+inline std::atomic<bool>& defer_host_frees() {   // one flag for all the units
+  static std::atomic<bool> on{false};
+  return on;
+}
 }
 
 namespace {
@@ -31,8 +50,21 @@ struct SetupError : std::runtime_error {
   explicit SetupError(const std::string& m) : std::runtime_error(m) {}
 };
 
-uint32_t rd32(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }
-uint64_t rd64(const uint8_t* p) { uint64_t v; memcpy(&v, p, 8); return v; }
+// ZKPOA_VERBOSE: where a command spends its time. One line per phase: "zkpoa: <command>: <what>  <ms since the last>"
+struct PhaseTimer {
+  const char* command;
+  int width;   // of the <what> column (each command keeps its own: logs of different dates compare)
+  const bool verbose = getenv("ZKPOA_VERBOSE") != nullptr;
+  struct timespec t0;
+  PhaseTimer(const char* cmd, int w) : command(cmd), width(w) { clock_gettime(CLOCK_MONOTONIC, &t0); }
+  void operator()(const char* what) {
+    if (!verbose) return;
+    struct timespec t;
+    clock_gettime(CLOCK_MONOTONIC, &t);
+    fprintf(stderr, "zkpoa: %s: %-*s %8.1f ms\n", command, width, what, (t.tv_sec - t0.tv_sec) * 1e3 + (t.tv_nsec - t0.tv_nsec) / 1e6);
+    t0 = t;
+  }
+};
 
 struct MappedFile {
   const uint8_t* p = nullptr;
@@ -62,40 +94,27 @@ struct MappedFile {
   MappedFile& operator=(const MappedFile&) = delete;
 };
 
-struct Sec {
-  uint64_t off = 0, len = 0;
-  bool present = false;
-};
-
-// iden3 binary container: magic(4) version(u32) nSections(u32) then { type(u32) size(u64) payload }
+// the section table of an iden3 binary file (binfile.hpp), with the setup commands' error texts
 std::map<uint32_t, Sec> bin_sections(const MappedFile& f, const char* magic, uint32_t max_version, const char* what) {
-  if (f.size < 12 || memcmp(f.p, magic, 4) != 0) throw SetupError(std::string(what) + ": bad magic");
-  if (rd32(f.p + 4) > max_version) throw SetupError(std::string(what) + ": unsupported version");
-  const uint32_t n = rd32(f.p + 8);
+  static const char* const why[] = {"", "bad magic", "unsupported version", "truncated section table",
+                                    "section runs past the end of the file"};
   std::map<uint32_t, Sec> out;
-  uint64_t pos = 12;
-  for (uint32_t i = 0; i < n; i++) {
-    if (pos + 12 > f.size) throw SetupError(std::string(what) + ": truncated section table");
-    const uint32_t type = rd32(f.p + pos);
-    const uint64_t len = rd64(f.p + pos + 4);
-    pos += 12;
-    if (len > f.size - pos) throw SetupError(std::string(what) + ": section runs past the end of the file");
-    if (!out.count(type)) out[type] = Sec{pos, len, true};   // the first section of a type (as snarkjs' readers)
-    pos += len;
-  }
+  const BinScan r = bin_scan(f.p, f.size, magic, max_version, out);
+  if (r != kBinOk) throw SetupError(std::string(what) + ": " + why[r]);
   return out;
 }
 
-struct DevArr {
-  void* p = nullptr;
-  explicit DevArr(size_t bytes) { ZK_HIP(hipMalloc(&p, bytes ? bytes : 1)); }
-  ~DevArr() { if (p) (void)hipFree(p); }
-  DevArr(const DevArr&) = delete;
-  DevArr& operator=(const DevArr&) = delete;
-  void up(const void* src, size_t bytes, size_t at = 0) {
-    if (bytes) ZK_HIP(hipMemcpy(static_cast<char*>(p) + at, src, bytes, hipMemcpyHostToDevice));
-  }
-};
+// header of a .ptau (section 1): n8(u32) q(32) power(u32) ceremony power(u32); returns the power
+uint32_t ptau_header(const MappedFile& f, const Sec& h, uint32_t* ceremony = nullptr) {
+  if (h.len < 4 + 32 + 8 || rd32(f.p + h.off) != 32) throw SetupError("ptau: header too short or field size != 32");
+  if (memcmp(f.p + h.off + 4, HFqParams::P, 32) != 0) throw SetupError("ptau: not a BN254 ceremony");
+  if (ceremony) *ceremony = rd32(f.p + h.off + 40);
+  return rd32(f.p + h.off + 36);
+}
+
+void urandom(void* dst, size_t len) {
+  if (const char* err = read_urandom(dst, len)) throw SetupError(err);
+}
 
 // The curve's b in the wire encoding (G1: 3, first 32 B; G2: 3 / (9 + u), 64 B), made on the host.
 struct CurveB {
@@ -174,6 +193,333 @@ static __global__ __launch_bounds__(256) void g2_subgroup_kernel(const void* __r
   const XYZZ<Fq2> rhs = g2_psi(g2_psi(g2_psi(xyzz_dbl(xq), cx, cy), cx, cy), cx, cy);
   xyzz_add(lhs, xyzz_neg(rhs));
   if (!lhs.is_inf()) atomicOr(flags, 4u);
+}
+
+
+// The point checks of a section on lane 0: point_check_kernel, for G2 optionally g2_subgroup_kernel.
+struct PointChecker {
+  Lane& lane;
+  DevBuf flags{64};   // word 0: the checks' bits; words 1-15 are free for the caller's kernels. Zero between read()s.
+  CurveB b1{}, b2{};
+  const FrobArg frob = frob_arg();
+  explicit PointChecker(zkpoa_context* ctx) : lane(ctx->dev.lanes[0]) {
+    HFq::from_u64(3).to_bytes(&b1.q[0]);
+    pairing::twist_b().to_bytes(&b2.q[0]);
+    ZK_HIP(hipMemsetAsync(flags.p, 0, 64, lane.stream));
+  }
+  uint32_t* fl() { return reinterpret_cast<uint32_t*>(flags.p); }
+  uint32_t read() {   // word 0 (the stream is synchronised), then every flag word zeroed
+    msm_read_back(lane, flags.p, 4);
+    uint32_t f;
+    memcpy(&f, lane.pinned, 4);
+    ZK_HIP(hipMemsetAsync(flags.p, 0, 64, lane.stream));
+    return f;
+  }
+  // over count points of group 1 / 2 at d: bit 1 = a point off its curve, bit 2 (subgroup) = a G2 point outside G2;
+  // a coordinate that is no field element throws
+  uint32_t check(const void* d, uint64_t count, int group, bool subgroup, const char* what) {
+    if (!count) return 0u;
+    const dim3 grid((uint32_t)((count + 255) / 256));
+    if (group == 1) hipLaunchKernelGGL((point_check_kernel<Fq>), grid, dim3(256), 0, lane.stream, d, count, b1, fl());
+    else hipLaunchKernelGGL((point_check_kernel<Fq2>), grid, dim3(256), 0, lane.stream, d, count, b2, fl());
+    if (subgroup) hipLaunchKernelGGL(g2_subgroup_kernel, grid, dim3(256), 0, lane.stream, d, count, frob, fl());
+    const uint32_t f = read();
+    if (f & 1u) throw SetupError(std::string(what) + ": a coordinate is not a field element (>= q)");
+    return f;
+  }
+};
+
+// ---- `snarkjs wtns check`: constraint c holds iff <A_c, w> * <B_c, w> == <C_c, w> ------------------------------------
+// row_ptr[3 * c + m .. +1): the terms of matrix m of constraint c; coefficients and witness in Montgomery form.
+// flags[0] = number of violated constraints, flags[1] = the smallest violated index (atomicMin, starts at ~0).
+// folds (optional, `zkey verify`): the three products are also stored, Montgomery form, at folds[m * fold_stride + c].
+static __global__ __launch_bounds__(256) void wtns_check_kernel(const uint32_t* __restrict__ row_ptr,
+                                                                const uint32_t* __restrict__ sig,
+                                                                const void* __restrict__ coef_m,
+                                                                const void* __restrict__ w_m, uint32_t n_cons,
+                                                                uint32_t* __restrict__ flags, void* __restrict__ folds,
+                                                                uint32_t fold_stride) {
+  uint32_t c = blockIdx.x * 256u + threadIdx.x;
+  if (c >= n_cons) return;
+  Fr v[3];
+#pragma unroll
+  for (int m = 0; m < 3; m++) {
+    Fr acc = Fr::zero();
+    for (uint32_t t = row_ptr[3 * c + m]; t < row_ptr[3 * c + m + 1]; t++)
+      acc = acc + load_field<Fr>(reinterpret_cast<const char*>(coef_m) + 32 * (size_t)t) *
+                      load_field<Fr>(reinterpret_cast<const char*>(w_m) + 32 * (size_t)sig[t]);
+    v[m] = acc;
+    if (folds) store_field(reinterpret_cast<char*>(folds) + 32 * ((size_t)m * fold_stride + c), acc);
+  }
+  if (!(v[0] * v[1] - v[2]).is_zero()) {
+    atomicAdd(&flags[0], 1u);
+    atomicMin(&flags[1], c);
+  }
+}
+// in place: standard form (canonical, < r checked by the caller's flag) -> Montgomery
+static __global__ __launch_bounds__(256) void fr_to_mont_kernel(void* __restrict__ data, uint64_t n, uint32_t* __restrict__ bad) {
+  uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  char* p = reinterpret_cast<char*>(data) + 32 * i;
+  Fr v = load_field<Fr>(p);
+  uint32_t bw = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) (void)subb(v.l[k], FrParams::P[k], bw);
+  if (!bw) atomicOr(bad, 1u);
+  store_field(p, v.to_mont());
+}
+
+// ---- host-side parallelism (r04) ---------------------------------------------------------------------------------------
+// At the layer-three shape `zkey new` reads 62 GB and writes 35 GB, and the device's share of the command is 3.5 s: what
+// was left was one host thread parsing, copying and converting (54 s in all). Every host stage below is split over
+// the host's threads; the arrays they fill are not zero-filled first (UVec), the threads are the first to touch them.
+unsigned host_threads() {
+  unsigned t = std::thread::hardware_concurrency();
+  if (const char* e = getenv("ZKPOA_SETUP_THREADS")) {
+    char* end = nullptr;
+    const long v = strtol(e, &end, 10);
+    if (end != e && !*end && v >= 1 && v <= 256) t = (unsigned)v;
+  }
+  return t < 1 ? 1 : (t > 32 ? 32 : t);
+}
+// fn(t, lo, hi) over [0, count) cut into host_threads() ranges; the first exception (in range order) is rethrown
+template <class Fn>
+void parallel_ranges(uint64_t count, uint64_t min_per_thread, Fn fn) {
+  unsigned T = host_threads();
+  if (count / (min_per_thread ? min_per_thread : 1) < T) T = (unsigned)(count / (min_per_thread ? min_per_thread : 1));
+  if (T <= 1) {
+    fn(0u, (uint64_t)0, count);
+    return;
+  }
+  std::vector<std::exception_ptr> errs(T);
+  std::vector<std::thread> th;
+  for (unsigned t = 0; t < T; t++)
+    th.emplace_back([&, t] {
+      try {
+        fn(t, count * t / T, count * (t + 1) / T);
+      } catch (...) {
+        errs[t] = std::current_exception();
+      }
+    });
+  for (auto& x : th) x.join();
+  for (auto& e : errs)
+    if (e) std::rethrow_exception(e);
+}
+template <class T>
+struct UVec {   // a sized array of trivially copyable elements whose storage is NOT value-initialised
+  std::unique_ptr<T[]> p;
+  size_t n = 0;
+  UVec() = default;
+  UVec(UVec&&) = default;
+  UVec& operator=(UVec&&) = default;
+  ~UVec() {
+    if (defer_host_frees().load()) (void)p.release();
+  }
+  explicit UVec(size_t count) { alloc(count); }
+  void alloc(size_t count) {
+    p.reset(new T[count ? count : 1]);
+    n = count;
+  }
+  size_t size() const { return n; }
+  bool empty() const { return n == 0; }
+  T* data() { return p.get(); }
+  const T* data() const { return p.get(); }
+  T& operator[](size_t i) { return p[i]; }
+  const T& operator[](size_t i) const { return p[i]; }
+  const T* begin() const { return p.get(); }
+  const T* end() const { return p.get() + n; }
+};
+
+// Untrusted inputs: the device keeps Fq elements lazily in [0, 2q) and takes file bytes raw, so every
+// coordinate that reaches a kernel or is copied into the key must be a canonical field element (< q).
+void host_check_coords(const uint8_t* p, uint64_t count32, const char* what) {
+  parallel_ranges(count32, 1u << 20, [&](unsigned, uint64_t lo, uint64_t hi) {
+    for (uint64_t i = lo; i < hi; i++) {
+      uint64_t v[4];
+      memcpy(v, p + 32 * i, 32);
+      if (v[3] >= HFqParams::P[3] && HFq::geq_p(v)) throw SetupError(std::string(what) + ": a coordinate is not a field element (>= q)");
+    }
+  });
+}
+struct Term {
+  uint32_t c, s;
+  uint8_t coef[32];
+};
+
+struct R1cs {
+  uint32_t nWires = 0, nPublic = 0, nConstraints = 0;
+  UVec<Term> A, B, C;   // per constraint in file order, terms of one linear combination ascending by signal
+};
+
+// Two passes: the first walks the term counts only (three words per constraint) and notes, every 2^14 constraints, where
+// the constraint starts in the file and how many A / B / C terms precede it; the second parses those blocks in parallel
+// straight into their places.
+R1cs parse_r1cs(const MappedFile& f) {
+  auto secs = bin_sections(f, "r1cs", 1, "r1cs");
+  if (!secs.count(1) || !secs.count(2)) throw SetupError("r1cs: header or constraint section missing");
+  const Sec h = secs[1], cs = secs[2];
+  if (h.len < 4 + 32 + 4 * 4 + 8 + 4 || rd32(f.p + h.off) != 32) throw SetupError("r1cs: header too short or field size != 32");
+  for (int i = 0; i < 4; i++)
+    if (rd64(f.p + h.off + 4 + 8 * i) != HFrParams::P[i]) throw SetupError("r1cs: not over the BN254 scalar field");
+  const uint8_t* q = f.p + h.off + 36;
+  R1cs r;
+  r.nWires = rd32(q);
+  const uint64_t n_public = (uint64_t)rd32(q + 4) + rd32(q + 8);   // outputs + public inputs (no 32-bit wrap)
+  r.nConstraints = rd32(q + 24);
+  if (r.nWires == 0 || n_public + 1 > r.nWires) throw SetupError("r1cs: inconsistent wire counts");
+  r.nPublic = (uint32_t)n_public;
+  const uint64_t end = cs.off + cs.len;
+  constexpr uint32_t kBlock = 1u << 14;
+  struct Mark { uint64_t pos, cnt[3]; };
+  std::vector<Mark> marks;
+  marks.reserve(r.nConstraints / kBlock + 2);
+  {
+    uint64_t pos = cs.off, cnt[3] = {0, 0, 0};
+    for (uint32_t c = 0; c < r.nConstraints; c++) {
+      if ((c & (kBlock - 1)) == 0) marks.push_back(Mark{pos, {cnt[0], cnt[1], cnt[2]}});
+      for (int m = 0; m < 3; m++) {
+        if (pos + 4 > end) throw SetupError("r1cs: constraint section truncated");
+        const uint32_t nt = rd32(f.p + pos);
+        pos += 4;
+        if ((uint64_t)nt * 36 > end - pos) throw SetupError("r1cs: constraint section truncated");
+        pos += (uint64_t)nt * 36;
+        cnt[m] += nt;
+      }
+    }
+    marks.push_back(Mark{pos, {cnt[0], cnt[1], cnt[2]}});
+  }
+  const Mark& tot = marks.back();
+  r.A.alloc(tot.cnt[0]);
+  r.B.alloc(tot.cnt[1]);
+  r.C.alloc(tot.cnt[2]);
+  const uint64_t blocks = marks.size() - 1;
+  parallel_ranges(blocks, 1, [&](unsigned, uint64_t b0, uint64_t b1) {
+    for (uint64_t b = b0; b < b1; b++) {
+      uint64_t pos = marks[b].pos, at[3] = {marks[b].cnt[0], marks[b].cnt[1], marks[b].cnt[2]};
+      const uint32_t c1 = (uint32_t)std::min<uint64_t>((b + 1) * kBlock, r.nConstraints);
+      for (uint32_t c = (uint32_t)(b * kBlock); c < c1; c++) {
+        for (int m = 0; m < 3; m++) {
+          const uint32_t nt = rd32(f.p + pos);
+          pos += 4;
+          Term* dst = (m == 0 ? r.A.data() : (m == 1 ? r.B.data() : r.C.data())) + at[m];
+          for (uint32_t t = 0; t < nt; t++, pos += 36) {
+            Term& x = dst[t];
+            x.c = c;
+            x.s = rd32(f.p + pos);
+            memcpy(x.coef, f.p + pos + 4, 32);
+            if (x.s >= r.nWires) throw SetupError("r1cs: wire index out of range");
+            uint64_t v[4];
+            memcpy(v, x.coef, 32);
+            if (HFr::geq_p(v)) throw SetupError("r1cs: coefficient is not a field element (>= r)");
+          }
+          // snarkjs holds a linear combination as an object keyed by the signal: iteration is ascending by signal
+          std::stable_sort(dst, dst + nt, [](const Term& a, const Term& b) { return a.s < b.s; });
+          for (uint32_t t = 1; t < nt; t++)
+            if (dst[t].s == dst[t - 1].s) throw SetupError("r1cs: a signal occurs twice in one linear combination");
+          at[m] += nt;
+        }
+      }
+    }
+  });
+  return r;
+}
+
+void pread_all(int fd, void* dst, uint64_t len, uint64_t off, const char* what) {
+  parallel_ranges(len, 32ull << 20, [&](unsigned, uint64_t lo, uint64_t hi) {
+    uint64_t got = lo;
+    while (got < hi) {
+      ssize_t n = pread(fd, static_cast<char*>(dst) + got, hi - got, (off_t)(off + got));
+      if (n <= 0) throw SetupError(std::string("ptau: short read of ") + what);
+      got += (uint64_t)n;
+    }
+  });
+}
+
+// the domain of `zkey new`: the smallest power of two that holds the constraints and the nPublic + 1 extra rows (zkey_new.js)
+uint32_t domain_log2(const R1cs& r) {
+  uint32_t cp = 0;
+  while ((1ull << cp) < (uint64_t)r.nConstraints + r.nPublic + 1) cp++;
+  if (cp > 27) throw SetupError("circuit too large (domain above 2^27)");
+  return cp;
+}
+
+// what `zkey new` (and `zkey verify`) read of a phase-2 .ptau for a domain of 2^cp: level cp of sections 12-15, level
+// cp + 1 of section 12 (the 2n basis, whose odd points are H), and alpha*G1, beta*G1, beta*G2 (sections 4-6)
+struct PtauRanges {
+  UVec<uint8_t> L1, L2, aL, bL, Hs;
+  uint8_t alpha1[64], beta1[64], beta2[128];
+};
+PtauRanges read_ptau_ranges(const char* ptau_path, uint32_t cp) {
+  const uint64_t n = 1ull << cp;
+  MappedFile fp(ptau_path);   // mapped for the section table only; the point ranges are read with pread
+  auto ps = bin_sections(fp, "ptau", 1, "ptau");
+  for (uint32_t t : {1u, 4u, 5u, 6u, 12u, 13u, 14u, 15u})
+    if (!ps.count(t)) throw SetupError("ptau: section " + std::to_string(t) + " missing (the file must be prepared for phase 2)");
+  const uint32_t power = ptau_header(fp, ps[1]);
+  if (cp > power) throw SetupError("ptau: ceremony of 2^" + std::to_string(power) + " is too small for a 2^" + std::to_string(cp) + " domain");
+  auto level = [&](uint32_t sec, uint32_t lvl, uint64_t unit, uint64_t count, const char* what) {
+    const uint64_t off = ((1ull << lvl) - 1) * unit;
+    if (off + count * unit > ps[sec].len) throw SetupError(std::string("ptau: section too short for ") + what);
+    return ps[sec].off + off;
+  };
+  PtauRanges pt;
+  UVec<uint8_t>&L1 = pt.L1, &L2 = pt.L2, &aL = pt.aL, &bL = pt.bL, &Hs = pt.Hs;
+  L1.alloc(n * 64);
+  L2.alloc(n * 128);
+  aL.alloc(n * 64);
+  bL.alloc(n * 64);
+  Hs.alloc(2 * n * 64);
+  pread_all(fp.fd, L1.data(), L1.size(), level(12, cp, 64, n, "tau*G1 (Lagrange)"), "tau*G1 (Lagrange)");
+  pread_all(fp.fd, L2.data(), L2.size(), level(13, cp, 128, n, "tau*G2 (Lagrange)"), "tau*G2 (Lagrange)");
+  pread_all(fp.fd, aL.data(), aL.size(), level(14, cp, 64, n, "alpha*tau*G1 (Lagrange)"), "alpha*tau*G1 (Lagrange)");
+  pread_all(fp.fd, bL.data(), bL.size(), level(15, cp, 64, n, "beta*tau*G1 (Lagrange)"), "beta*tau*G1 (Lagrange)");
+  pread_all(fp.fd, Hs.data(), Hs.size(), level(12, cp + 1, 64, 2 * n, "tau*G1 (Lagrange, 2n)"), "tau*G1 (Lagrange, 2n)");
+  uint8_t *alpha1 = pt.alpha1, *beta1 = pt.beta1, *beta2 = pt.beta2;
+  if (ps[4].len < 64 || ps[5].len < 64 || ps[6].len < 128) throw SetupError("ptau: alpha / beta sections too short");
+  pread_all(fp.fd, alpha1, 64, ps[4].off, "alpha*G1");
+  pread_all(fp.fd, beta1, 64, ps[5].off, "beta*G1");
+  pread_all(fp.fd, beta2, 128, ps[6].off, "beta*G2");
+  host_check_coords(alpha1, 2, "ptau alpha*G1");
+  host_check_coords(beta1, 2, "ptau beta*G1");
+  host_check_coords(beta2, 4, "ptau beta*G2");
+  host_check_coords(Hs.data(), 4 * n, "ptau tau*G1 (Lagrange, 2n)");   // copied into section 9 without touching the device
+  return pt;
+}
+
+// CSR over (constraint, matrix) of an R1CS, as wtns_check_kernel walks it: row_ptr[3 c + m], signals, coefficients
+// (standard form). The three term lists are already grouped by constraint in file order.
+struct R1csRows {
+  std::vector<uint32_t> row_ptr, sig;
+  std::vector<uint8_t> coef;
+};
+R1csRows r1cs_rows(const R1cs& r) {
+  const uint64_t nnz = r.A.size() + r.B.size() + r.C.size();
+  if (nnz >= (1ull << 32)) throw SetupError("more than 2^32 coefficients");
+  R1csRows out;
+  std::vector<uint32_t>&row_ptr = out.row_ptr, &sig = out.sig;
+  std::vector<uint8_t>& coef = out.coef;
+  row_ptr.assign(3 * (size_t)r.nConstraints + 1, 0);
+  sig.resize(nnz);
+  coef.resize(nnz * 32);
+  {
+    size_t ia = 0, ib = 0, ic = 0, t = 0;
+    auto take = [&](const UVec<Term>& v, size_t& i, uint32_t c) {
+      for (; i < v.size() && v[i].c == c; i++, t++) {
+        sig[t] = v[i].s;
+        memcpy(&coef[t * 32], v[i].coef, 32);
+      }
+    };
+    for (uint32_t c = 0; c < r.nConstraints; c++) {
+      row_ptr[3 * (size_t)c] = (uint32_t)t;
+      take(r.A, ia, c);
+      row_ptr[3 * (size_t)c + 1] = (uint32_t)t;
+      take(r.B, ib, c);
+      row_ptr[3 * (size_t)c + 2] = (uint32_t)t;
+      take(r.C, ic, c);
+    }
+    row_ptr[3 * (size_t)r.nConstraints] = (uint32_t)t;
+  }
+  return out;
 }
 
 }  // namespace

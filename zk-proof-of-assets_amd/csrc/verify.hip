@@ -4,6 +4,7 @@
 // (scripts/sanitize_groth16_proof.py:39-124, 43-bit x 6 limbs per scripts/lib/field_helper.py) --
 // as two C-ABI entry points over pairing.hpp. No GPU is needed or used: a verification is three
 // Miller loops and one final exponentiation (~15 ms on one core).
+#include "binfile.hpp"
 #include "pairing.hpp"
 #include "../../include/zkpoa_prover.h"
 #include "host_curve.hpp"
@@ -280,31 +281,15 @@ struct JOut {   // JSON.stringify(., null, 1): one space per nesting level
   }
 };
 
-uint32_t le32(const uint8_t* p) {
-  uint32_t v;
-  memcpy(&v, p, 4);
-  return v;
-}
-
 std::string export_vkey_impl(const uint8_t* buf, uint64_t size) {
-  if (size < 12 || memcmp(buf, "zkey", 4) != 0) throw std::runtime_error("zkey file: invalid file format (bad magic)");
-  const uint32_t nsec = le32(buf + 8);
-  const uint8_t *s2 = nullptr, *s3 = nullptr;
-  uint64_t l2 = 0, l3 = 0, pos = 12;
-  for (uint32_t i = 0; i < nsec; i++) {
-    if (pos + 12 > size) throw std::runtime_error("zkey file: truncated section table");
-    uint32_t id = le32(buf + pos);
-    uint64_t len;
-    memcpy(&len, buf + pos + 4, 8);
-    pos += 12;
-    if (len > size - pos) throw std::runtime_error("zkey file: truncated section");
-    if (id == 2 && !s2) { s2 = buf + pos; l2 = len; }
-    if (id == 3 && !s3) { s3 = buf + pos; l3 = len; }
-    pos += len;
-  }
-  const uint64_t hdr = 4 + 32 + 4 + 32 + 12 + 64 + 64 + 128 + 128 + 64 + 128;
+  static const char* const why[] = {"", "invalid file format (bad magic)", "", "truncated section table", "truncated section"};
+  std::map<uint32_t, Sec> secs;
+  const BinScan r = bin_scan(buf, size, "zkey", 0xffffffffu, secs);   // any container version
+  if (r != kBinOk) throw std::runtime_error(std::string("zkey file: ") + why[r]);
+  const uint8_t *s2 = secs.count(2) ? buf + secs[2].off : nullptr, *s3 = secs.count(3) ? buf + secs[3].off : nullptr;
+  const uint64_t l2 = secs[2].len, l3 = secs[3].len, hdr = kHdrLen;
   if (!s2 || l2 < hdr || !s3) throw std::runtime_error("zkey file: missing groth16 header (section 2) or IC (section 3)");
-  const uint32_t n_public = le32(s2 + 76);
+  const uint32_t n_public = rd32(s2 + 76);
   if (l3 != ((uint64_t)n_public + 1) * 64) throw std::runtime_error("zkey file: section 3 (IC) has the wrong size");
   const uint8_t* p = s2 + 84;
   G1 alpha1 = h_affine_from_bytes<HFq>(p);

@@ -92,6 +92,9 @@ struct DevBuf {  // RAII device allocation for the host-buffer entry points
   }
   DevBuf(const DevBuf&) = delete;
   DevBuf& operator=(const DevBuf&) = delete;
+  void up(const void* src, size_t bytes, size_t at = 0) {   // blocking host -> device copy to byte `at`
+    if (bytes) ZK_HIP(hipMemcpy(static_cast<char*>(p) + at, src, bytes, hipMemcpyHostToDevice));
+  }
 };
 
 
