@@ -8,7 +8,7 @@
 // exchanges done as peer-to-peer writes over xGMI (one kernel per rank and exchange stores chunk h of its buffer straight
 // into rank h's receive buffer: a single hop, all links busy at once, no ring; hipMemcpyPeerAsync where a pair has no
 // direct path), and the five 64/128-byte partial results summed on the host.
-// Included by prover.hip inside its anonymous namespace.
+// Included by prover.hip inside its anonymous namespace; the requests that use it: prove_request.hip.h.
 //
 // Which devices (env, read once per process):
 //   ZKPOA_DEVICES=0,1,2,3   exactly these HIP devices, one rank each (a device may be listed more than once: ranks
@@ -245,7 +245,7 @@ DeviceSet* process_devices(uint32_t power, std::string& err, int* code) {
       for (size_t g = 0; g < G; g++) list += (g ? "," : "") + std::to_string(ds->ids[g]);
       fprintf(stderr, "zkpoa: %zu rank(s) on HIP device(s) %s%s, contexts ready in %.1f ms\n", G, list.c_str(),
               ds->automatic ? " (picked by lock file)" : "",
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+              ms_since(t0));
     }
   } catch (const ProverError& e) {
     err = e.what();
@@ -257,7 +257,6 @@ DeviceSet* process_devices(uint32_t power, std::string& err, int* code) {
     return nullptr;
   }
   g_devset = ds.release();
-  g_ctx = g_devset->ctx[0];
   return g_devset;
 }
 
@@ -365,7 +364,7 @@ MultiKey* multi_key_load(DeviceSet* ds, const uint8_t* buf, uint64_t size) {
     multi_key_release(ds, mk.release());
     throw;
   }
-  mk->load_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  mk->load_ms = ms_since(t0);
   return mk.release();
 }
 
@@ -573,51 +572,4 @@ void multi_precompute(DeviceSet* ds, MultiKey* mk) {
   });
   mk->table_bytes = 0;
   for (uint64_t u : used) mk->table_bytes += u;
-}
-
-// witness -> proof JSON on a loaded MultiKey (the multi-GPU twin of prove_to_json)
-int multi_prove_to_json(DeviceSet* ds, MultiKey* mk, const WtnsSrc& wsrc, char* proof_buffer,
-                        unsigned long* proof_size, char* public_buffer, unsigned long* public_size, char* error_msg,
-                        unsigned long error_msg_maxsize, uint64_t zkey_size, bool cache_hit) {
-  zkpoa_zkey* z0 = mk->shards[0];
-  zkpoa_context* c0 = ds->ctx[0];
-  WtnsView w = parse_wtns(wsrc);
-  if (w.n != z0->nVars)
-    throw ProverError(PROVER_INVALID_WITNESS_LENGTH, "Invalid witness length. Circuit: " + std::to_string(z0->nVars) +
-                                                         ", witness: " + std::to_string(w.n));
-  uint8_t rb[32], sb[32], parts[384], header[448], pts[256];
-  const uint8_t *rp = nullptr, *sp = nullptr;
-  env_blinding(rb, sb, rp, sp);
-  auto t0 = std::chrono::steady_clock::now();
-  multi_proof_counter()++;
-  const bool kernel_exchange = ds->ids.size() > 1 && ds->peer_ok && !multi_force_copies();
-  multi_prove_partials(ds, mk, w, parts);
-  zkey_header_bytes(z0, header);
-  prove_assemble(header, parts, rp, sp, pts);
-  c0->ms[5] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  std::vector<uint8_t> pub_store;
-  const uint8_t* pubs = w.publics(z0->nPublic, pub_store);
-  // The peer-store exchanges rest on a memory-visibility rule that no run on a multi-GPU node has confirmed yet (DESIGN
-  // section 6), so the pairing check that normally guards a key's first proof guards its first three here -- a stale
-  // receive buffer can only show from the second proof on -- and a proof that fails it is not an error yet: it is
-  // repeated with hipMemcpyPeerAsync exchanges (DMA, ordered by the runtime), which then stay on for this process.
-  try {
-    selfcheck(c0, z0, pts, pubs, kernel_exchange ? 3 : 1);
-  } catch (const SelfCheckFailed&) {
-    if (!kernel_exchange) throw;
-    multi_copies_state().store(1);
-    fprintf(stderr, "zkpoa: WARNING: a proof over %zu ranks failed its self-check with the peer-store exchanges; repeating it "
-                    "with hipMemcpyPeerAsync exchanges, which stay on for the rest of this process (ZKPOA_EXCHANGE=copy makes "
-                    "them the default; DESIGN.md section 6 names the suspects)\n", ds->ids.size());
-    multi_prove_partials(ds, mk, w, parts);
-    prove_assemble(header, parts, rp, sp, pts);
-    c0->ms[5] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    selfcheck(c0, z0, pts, pubs, ~0ull);   // this one must verify
-  }
-  if (req_getenv("ZKPOA_VERBOSE"))
-    fprintf(stderr, "zkpoa: one proof over %zu ranks: H-scalar chain %s, sections 5-8 %s, %.2f GB of fixed-base tables; "
-                    "prove %.2f ms\n", ds->ids.size(), mk->split ? "split (2 peer-to-peer exchanges)" : "replicated",
-            z0->bc_log ? "block-cyclic" : "contiguous ranges", mk->table_bytes / 1e9, c0->ms[5]);
-  return emit_outputs(c0, z0, pts, pubs, proof_buffer, proof_size, public_buffer, public_size, error_msg,
-                      error_msg_maxsize, mk->load_ms, zkey_size, cache_hit ? "cached," : "sharded load");
 }

@@ -102,8 +102,7 @@ void* dev_upload(zkpoa_context* ctx, const void* src, size_t bytes) {
     if (bytes) ctx->uploader.upload(d, src, bytes, ctx->dev.device, ctx->dev.lanes[0].stream);
     if (req_getenv("ZKPOA_VERBOSE") && bytes > (16u << 20))
       fprintf(stderr, "zkpoa:   upload %.0f MB: hipMalloc %.1f ms, copy %.1f ms\n", bytes / 1e6,
-              std::chrono::duration<double, std::milli>(t1 - t0).count(),
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count());
+              std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
   } catch (...) {
     (void)hipFree(d);
     throw;
@@ -734,6 +733,12 @@ WtnsView parse_wtns(const WtnsSrc& src) {
   return src.fd >= 0 ? parse_wtns_fd(src.fd, src.size) : parse_wtns(src.buf, src.size);
 }
 
+void check_witness_len(const WtnsView& w, const zkpoa_zkey* zk) {
+  if (w.n != zk->nVars)
+    throw ProverError(PROVER_INVALID_WITNESS_LENGTH, "Invalid witness length. Circuit: " + std::to_string(zk->nVars) +
+                                                         ", witness: " + std::to_string(w.n));
+}
+
 // a table covers the whole resident array: the handle's current range must be that array
 bool split_c_partial(const zkpoa_zkey* zk) {
   uint64_t info[4];
@@ -1081,7 +1086,7 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
         }
       }
       if (!share_b) ZK_HIP(hipStreamSynchronize(ctx->dev.lanes[2].stream));   // the gathered scalars are read on lane 3 too
-      sort_b_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - ts0).count();
+      sort_b_ms = (float)ms_since(ts0);
       sorted_promise.set_value(sr);
     } catch (...) {
       sorted_promise.set_exception(std::current_exception());
@@ -1239,17 +1244,24 @@ bool is_full_key(const zkpoa_zkey* zk) {
          zk->hlo == 0 && zk->hcnt == zk->domain;
 }
 
+// the partial sums of a whole key -> proof points; ctx->ms[5] <- the prove time, counted from t0
+void assemble_proof(zkpoa_context* ctx, const zkpoa_zkey* zk, const uint8_t parts[384], const uint8_t* r_le,
+                    const uint8_t* s_le, std::chrono::steady_clock::time_point t0, uint8_t proof_points[256]) {
+  uint8_t header[448];
+  zkey_header_bytes(zk, header);
+  prove_assemble(header, parts, r_le, s_le, proof_points);
+  ctx->ms[5] = (float)ms_since(t0);
+}
+
 // unsharded prove = partials of the whole key + assembly
 void prove_core(zkpoa_context* ctx, const zkpoa_zkey* zk, const uint8_t* r_le, const uint8_t* s_le,
                 uint8_t proof_points[256]) {
   auto t0 = std::chrono::steady_clock::now();
   if (!is_full_key(zk))
     throw ProverError(PROVER_ERROR, "this key handle is a shard: use zkpoa_prove_partials + zkpoa_prove_assemble");
-  uint8_t parts[384], header[448];
+  uint8_t parts[384];
   prove_partials(ctx, zk, parts);
-  zkey_header_bytes(zk, header);
-  prove_assemble(header, parts, r_le, s_le, proof_points);
-  ctx->ms[5] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  assemble_proof(ctx, zk, parts, r_le, s_le, t0, proof_points);
 }
 
 // Self-check (ZKPOA_SELFCHECK): the reference verifies every proof right after proving it
@@ -1280,7 +1292,7 @@ void selfcheck(zkpoa_context* ctx, const zkpoa_zkey* zk, const uint8_t proof_poi
   char msg[256] = {0};
   int rc = zkpoa_groth16_verify_points(zk->vkey_points.data(), (unsigned long)zk->vkey_points.size(), proof_points,
                                        public_le, zk->nPublic, msg, sizeof(msg));
-  ctx->ms[6] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  ctx->ms[6] = (float)ms_since(t0);
   if (rc == PROVER_OK) {
     zk->selfchecks_done++;
     if (req_getenv("ZKPOA_VERBOSE")) fprintf(stderr, "zkpoa: self-check: proof verifies against the zkey's own verification key (%.1f ms)\n", ctx->ms[6]);
@@ -1296,23 +1308,23 @@ void selfcheck(zkpoa_context* ctx, const zkpoa_zkey* zk, const uint8_t proof_poi
   throw ProverError(PROVER_ERROR, std::string("self-check could not run: ") + msg);
 }
 
+// witness (its length checked by the caller) -> the key's buffer on lane 0, then prove_core; io_ms <- the upload
+void upload_and_prove(zkpoa_context* ctx, const zkpoa_zkey* zk, const WtnsView& w, const uint8_t* r_le,
+                      const uint8_t* s_le, uint8_t proof_points[256]) {
+  const auto tu = std::chrono::steady_clock::now();
+  w.upload(ctx, zk->d_witness, 0, w.n, ctx->dev.lanes[0].stream);
+  ctx->io_ms[0] = (float)ms_since(tu);
+  ctx->io_ms[1] = (float)((double)w.n * 32 / 1e6);
+  prove_core(ctx, zk, r_le, s_le, proof_points);
+}
+
 void prove_impl(zkpoa_context* ctx, const zkpoa_zkey* zk, const WtnsSrc& wsrc,
                 const uint8_t* r_le, const uint8_t* s_le, uint8_t proof_points[256], uint8_t* public_le,
                 uint64_t public_cap) {
   WtnsView w = parse_wtns(wsrc);
-  if (w.n != zk->nVars)
-    throw ProverError(PROVER_INVALID_WITNESS_LENGTH, "Invalid witness length. Circuit: " + std::to_string(zk->nVars) +
-                                                         ", witness: " + std::to_string(w.n));
+  check_witness_len(w, zk);
   if (public_cap < (uint64_t)zk->nPublic * 32) throw ProverError(PROVER_ERROR_SHORT_BUFFER, "public buffer too small");
-  Lane& l0 = ctx->dev.lanes[0];
-  (void)l0;
-  {
-    const auto tu = std::chrono::steady_clock::now();
-    w.upload(ctx, zk->d_witness, 0, w.n, ctx->dev.lanes[0].stream);
-    ctx->io_ms[0] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - tu).count();
-    ctx->io_ms[1] = (float)((double)w.n * 32 / 1e6);
-  }
-  prove_core(ctx, zk, r_le, s_le, proof_points);
+  upload_and_prove(ctx, zk, w, r_le, s_le, proof_points);
   std::vector<uint8_t> pub_store;
   const uint8_t* pubs = w.publics(zk->nPublic, pub_store);
   memcpy(public_le, pubs, (size_t)zk->nPublic * 32);
@@ -1335,9 +1347,7 @@ zkpoa_zkey* load_prove_staged(zkpoa_context* ctx, const uint8_t* buf, uint64_t s
   if (!cs) return nullptr;
   ZkeySections zs;
   std::unique_ptr<zkpoa_zkey> zk = zkey_parse(buf, size, zs);
-  if (w.n != zk->nVars)
-    throw ProverError(PROVER_INVALID_WITNESS_LENGTH, "Invalid witness length. Circuit: " + std::to_string(zk->nVars) +
-                                                         ", witness: " + std::to_string(w.n));
+  check_witness_len(w, zk.get());
   zk->set_full();
   const uint64_t m = zk->nVars, n = zk->domain, nC = m - zk->nPublic - 1;
   {
@@ -1382,8 +1392,7 @@ zkpoa_zkey* load_prove_staged(zkpoa_context* ctx, const uint8_t* buf, uint64_t s
   const auto t_start = std::chrono::steady_clock::now();
   auto mark = [&, verbose](const char* what) {   // ZKPOA_VERBOSE: the timeline of an overlapped load + prove
     if (verbose)
-      fprintf(stderr, "zkpoa: staged %7.1f ms  %s\n",
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count(), what);
+      fprintf(stderr, "zkpoa: staged %7.1f ms  %s\n", ms_since(t_start), what);
   };
   auto cleanup_temps = [&] {
     (void)hipDeviceSynchronize();
@@ -1514,657 +1523,8 @@ zkpoa_zkey* load_prove_staged(zkpoa_context* ctx, const uint8_t* buf, uint64_t s
   return zk.release();
 }
 
-// ---- JSON (byte formats pinned by the reference's committed fixtures) --------
-std::string fq_dec(const uint8_t* le_mont) { return HFq::from_bytes(le_mont).to_dec(); }
-bool all_zero(const uint8_t* p, size_t n) {
-  for (size_t i = 0; i < n; i++)
-    if (p[i]) return false;
-  return true;
-}
-
-std::string proof_json(const uint8_t pts[256], int style) {
-  // coordinates as decimal strings
-  std::string a[3], b[3][2], c[3];
-  auto g1 = [&](const uint8_t* p, std::string out[3]) {
-    if (all_zero(p, 64)) { out[0] = "0"; out[1] = "1"; out[2] = "0"; return; }
-    out[0] = fq_dec(p); out[1] = fq_dec(p + 32); out[2] = "1";
-  };
-  g1(pts, a);
-  g1(pts + 192, c);
-  const uint8_t* pb = pts + 64;
-  if (all_zero(pb, 128)) {
-    b[0][0] = "0"; b[0][1] = "0"; b[1][0] = "1"; b[1][1] = "0"; b[2][0] = "0"; b[2][1] = "0";
-  } else {
-    b[0][0] = fq_dec(pb); b[0][1] = fq_dec(pb + 32); b[1][0] = fq_dec(pb + 64); b[1][1] = fq_dec(pb + 96);
-    b[2][0] = "1"; b[2][1] = "0";
-  }
-  std::string o;
-  auto q = [](const std::string& s) { return "\"" + s + "\""; };
-  if (style == 0) {  // rapidsnark / nlohmann dump(): one line, no spaces
-    o += "{\"pi_a\":[" + q(a[0]) + "," + q(a[1]) + "," + q(a[2]) + "],";
-    o += "\"pi_b\":[[" + q(b[0][0]) + "," + q(b[0][1]) + "],[" + q(b[1][0]) + "," + q(b[1][1]) + "],[" + q(b[2][0]) +
-         "," + q(b[2][1]) + "]],";
-    o += "\"pi_c\":[" + q(c[0]) + "," + q(c[1]) + "," + q(c[2]) + "],";
-    o += "\"protocol\":\"groth16\"}";
-  } else {  // snarkjs: JSON.stringify(obj, null, 1)
-    auto g1s = [&](const char* key, const std::string v[3]) {
-      return std::string(" \"") + key + "\": [\n  " + q(v[0]) + ",\n  " + q(v[1]) + ",\n  " + q(v[2]) + "\n ],\n";
-    };
-    o += "{\n";
-    o += g1s("pi_a", a);
-    o += " \"pi_b\": [\n";
-    for (int i = 0; i < 3; i++) {
-      o += "  [\n   " + q(b[i][0]) + ",\n   " + q(b[i][1]) + "\n  ]";
-      o += (i < 2) ? ",\n" : "\n";
-    }
-    o += " ],\n";
-    o += g1s("pi_c", c);
-    o += " \"protocol\": \"groth16\",\n \"curve\": \"bn128\"\n}";
-  }
-  return o;
-}
-
-std::string public_json(const uint8_t* pub, uint64_t n, int style) {
-  std::string o;
-  if (style == 0) {
-    o = "[";
-    for (uint64_t i = 0; i < n; i++) {
-      HFr v = HFr::from_bytes(pub + 32 * i).to_mont();
-      o += (i ? ",\"" : "\"") + v.to_dec() + "\"";
-    }
-    o += "]";
-  } else {
-    if (n == 0) return "[]";
-    o = "[\n";
-    for (uint64_t i = 0; i < n; i++) {
-      HFr v = HFr::from_bytes(pub + 32 * i).to_mont();
-      o += " \"" + v.to_dec() + "\"" + (i + 1 < n ? ",\n" : "\n");
-    }
-    o += "]";
-  }
-  return o;
-}
-
-int emit(const std::string& s, char* buffer, unsigned long* size) {
-  if (!size) return PROVER_ERROR;
-  unsigned long needed = (unsigned long)s.size() + 1;
-  if (!buffer || *size < needed) {
-    *size = needed;
-    return PROVER_ERROR_SHORT_BUFFER;
-  }
-  memcpy(buffer, s.c_str(), needed);
-  *size = needed;
-  return PROVER_OK;
-}
-
-zkpoa_context* g_ctx = nullptr;
-std::mutex g_prove_mutex;   // one-shot entry points share the process-wide context: one proof at a time
-// The file entry point is entered by several threads of a resident server. Two stages, two locks: g_stage_mutex covers
-// the key cache and the upload of a request's witness into a free staging buffer of its key; g_prove_mutex the proof
-// itself. A request whose key is resident and already has its tables stages its witness while the request before it
-// is still proving -- at the layer-three size that is 31 ms of PCIe time per proof taken off the proof-to-proof period.
-// Anything that changes the cache or a key (a load, the second-use table build, an eviction) waits until no staged
-// request is pending and then holds both locks.
-std::mutex g_stage_mutex;
-std::condition_variable g_stage_cv;
-int g_staged_users = 0;
-
-// the code of a failure for the two file entry points + its message; call inside a catch (...) block
-int classify_current_exception(char* error_msg, unsigned long error_msg_maxsize) {
-  try {
-    throw;
-  } catch (const ProverError& e) {
-    set_err(error_msg, error_msg_maxsize, e.what());
-    return e.code;
-  } catch (const HipError& e) {            // HIP runtime failure: the context and its cached keys are suspect
-    set_err(error_msg, error_msg_maxsize, e.what());
-    return PROVER_ERROR_RUNTIME;
-  } catch (const std::bad_alloc&) {
-    set_err(error_msg, error_msg_maxsize, "out of host memory");
-    return PROVER_ERROR_RUNTIME;
-  } catch (const std::system_error& e) {   // a stage thread could not be started
-    set_err(error_msg, error_msg_maxsize, e.what());
-    return PROVER_ERROR_RUNTIME;
-  } catch (const std::exception& e) {
-    set_err(error_msg, error_msg_maxsize, e.what());
-    return PROVER_ERROR;
-  }
-}
-
-struct DeviceSet;
-DeviceSet* process_devices(uint32_t power, std::string& err, int* code);   // multi_device.hip.h: the device list of this process
-
-// r, s from the environment (ZKPOA_R / ZKPOA_S, decimal; test use) -> pointers, or null for /dev/urandom
-void env_blinding(uint8_t rb[32], uint8_t sb[32], const uint8_t*& rp, const uint8_t*& sp) {
-  rp = sp = nullptr;
-  if (req_getenv("ZKPOA_R") || req_getenv("ZKPOA_S")) {
-    static bool warned = false;
-    if (!warned) {
-      warned = true;
-      fprintf(stderr, "zkpoa: WARNING: blinding scalars fixed by ZKPOA_R / ZKPOA_S (test use): proofs made this way are "
-                      "not zero-knowledge; unset them in production\n");
-    }
-  }
-  if (const char* e = req_getenv("ZKPOA_R")) {
-    if (!parse_decimal_mod_r(e, rb)) throw ProverError(PROVER_ERROR, "ZKPOA_R is not a decimal number");
-    rp = rb;
-  }
-  if (const char* e = req_getenv("ZKPOA_S")) {
-    if (!parse_decimal_mod_r(e, sb)) throw ProverError(PROVER_ERROR, "ZKPOA_S is not a decimal number");
-    sp = sb;
-  }
-}
-
-// proof points + public values -> the two JSON texts (ZKPOA_JSON style) + the ZKPOA_VERBOSE phase line
-int emit_outputs(zkpoa_context* ctx, const zkpoa_zkey* zk, const uint8_t pts[256], const uint8_t* pub, char* proof_buffer,
-                 unsigned long* proof_size, char* public_buffer, unsigned long* public_size, char* error_msg,
-                 unsigned long error_msg_maxsize, double load_ms, uint64_t zkey_size, const char* how) {
-  int rc = PROVER_OK;
-  int style = 0;
-  if (const char* e = req_getenv("ZKPOA_JSON")) style = (strcmp(e, "snarkjs") == 0) ? 1 : 0;
-  std::string pj = proof_json(pts, style), uj = public_json(pub, zk->nPublic, style);
-  int r1 = emit(pj, proof_buffer, proof_size);
-  int r2 = emit(uj, public_buffer, public_size);
-  if (r1 != PROVER_OK || r2 != PROVER_OK) {
-    rc = PROVER_ERROR_SHORT_BUFFER;
-    set_err(error_msg, error_msg_maxsize, "output buffer too small");
-  }
-  if (req_getenv("ZKPOA_VERBOSE")) {
-    fprintf(stderr,
-            "zkpoa: nVars=%u nPublic=%u domain=2^%u nCoefs=%llu | zkey %s %.1f ms (%.2f GB/s) | witness -> HBM %.2f ms "
-            "(%.0f MB, %.1f GB/s) | h-chain %.2f ms, msm phase %.2f ms, prove %.2f ms, self-check %.2f ms\n",
-            zk->nVars, zk->nPublic, zk->power, (unsigned long long)zk->nCoefs, how, load_ms,
-            load_ms > 0 ? (double)zkey_size / load_ms / 1e6 : 0.0, ctx->io_ms[0], ctx->io_ms[1],
-            ctx->io_ms[0] > 0 ? ctx->io_ms[1] / ctx->io_ms[0] : 0.0, ctx->ms[3], ctx->ms[4], ctx->ms[5], ctx->ms[6]);
-  }
-  return rc;
-}
-
-// prove with a resident key, JSON out; options from the environment (ZKPOA_R / ZKPOA_S / ZKPOA_JSON / ZKPOA_VERBOSE)
-int prove_to_json(zkpoa_context* ctx, const zkpoa_zkey* zk, const WtnsSrc& wsrc, char* proof_buffer,
-                  unsigned long* proof_size, char* public_buffer, unsigned long* public_size, char* error_msg,
-                  unsigned long error_msg_maxsize, double load_ms, uint64_t zkey_size, bool cache_hit) {
-  uint8_t rb[32], sb[32];
-  const uint8_t *rp = nullptr, *sp = nullptr;
-  env_blinding(rb, sb, rp, sp);
-  uint8_t pts[256];
-  std::vector<uint8_t> pub((size_t)zk->nPublic * 32 + 1);
-  prove_impl(ctx, zk, wsrc, rp, sp, pts, pub.data(), pub.size());
-  return emit_outputs(ctx, zk, pts, pub.data(), proof_buffer, proof_size, public_buffer, public_size, error_msg,
-                      error_msg_maxsize, load_ms, zkey_size, cache_hit ? "cached," : "load");
-}
-
-// One-shot: load the key and prove, with the upload overlapped unless ZKPOA_OVERLAP=0. *out_zk <- the loaded key
-// (the caller frees or caches it). load_ms <- time to the end of the proof (load and prove are one phase here).
-int load_and_prove_to_json(zkpoa_context* ctx, const uint8_t* zkey, uint64_t zkey_size, const WtnsSrc& wsrc,
-                           char* proof_buffer, unsigned long* proof_size, char* public_buffer,
-                           unsigned long* public_size, char* error_msg, unsigned long error_msg_maxsize,
-                           zkpoa_zkey** out_zk, int zkey_fd = -1) {
-  *out_zk = nullptr;
-  const char* ov = getenv("ZKPOA_OVERLAP");
-  auto tl0 = std::chrono::steady_clock::now();
-  if (!ov || strcmp(ov, "0") != 0) {
-    WtnsView w = parse_wtns(wsrc);
-    uint8_t rb[32], sb[32], parts[384], header[448], pts[256];
-    const uint8_t *rp = nullptr, *sp = nullptr;
-    env_blinding(rb, sb, rp, sp);
-    auto t0 = std::chrono::steady_clock::now();
-    zkpoa_zkey* zk = load_prove_staged(ctx, zkey, zkey_size, w, parts, zkey_fd);
-    if (zk) {
-      *out_zk = zk;
-      zkey_header_bytes(zk, header);
-      prove_assemble(header, parts, rp, sp, pts);
-      const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      ctx->ms[5] = (float)ms;
-      std::vector<uint8_t> pub_store;
-      const uint8_t* pubs = w.publics(zk->nPublic, pub_store);
-      selfcheck(ctx, zk, pts, pubs);
-      return emit_outputs(ctx, zk, pts, pubs, proof_buffer, proof_size, public_buffer, public_size, error_msg,
-                          error_msg_maxsize, ms, zkey_size, "load overlapped with the prove:");
-    }
-  }
-  zkpoa_zkey* zk = zkey_load_impl(ctx, zkey, zkey_size);
-  *out_zk = zk;
-  const double load_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count();
-  return prove_to_json(ctx, zk, wsrc, proof_buffer, proof_size, public_buffer, public_size, error_msg,
-                       error_msg_maxsize, load_ms, zkey_size, false);
-}
-
-#include "multi_device.hip.h"
-
-// log2(domain) of a zkey image, for the automatic device selection (throws what zkey_parse throws)
-uint32_t zkey_power(const uint8_t* buf, uint64_t size) {
-  ZkeySections zs;
-  return zkey_parse(buf, size, zs)->power;
-}
-
-int one_shot(const uint8_t* zkey, uint64_t zkey_size, const WtnsSrc& wsrc, char* proof_buffer,
-             unsigned long* proof_size, char* public_buffer, unsigned long* public_size, char* error_msg,
-             unsigned long error_msg_maxsize) {
-  std::string err;
-  DeviceSet* ds = nullptr;
-  int dcode = PROVER_ERROR;
-  try {
-    ds = process_devices(zkey_power(zkey, zkey_size), err, &dcode);
-  } catch (const std::exception& e) {   // malformed key: nothing touches a GPU
-    set_err(error_msg, error_msg_maxsize, e.what());
-    return PROVER_ERROR;
-  }
-  if (!ds) {
-    set_err(error_msg, error_msg_maxsize, err);
-    return dcode;
-  }
-  zkpoa_context* ctx = ds->ctx[0];
-  std::lock_guard<std::mutex> lk(g_prove_mutex);
-  zkpoa_zkey* zk = nullptr;
-  MultiKey* mk = nullptr;
-  int rc = PROVER_OK;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
-    if (ds->ids.size() > 1) {   // one proof over all ranks of the process
-      mk = multi_key_load(ds, zkey, zkey_size);
-      rc = multi_prove_to_json(ds, mk, wsrc, proof_buffer, proof_size, public_buffer, public_size, error_msg,
-                               error_msg_maxsize, zkey_size, false);
-    } else {
-      rc = load_and_prove_to_json(ctx, zkey, zkey_size, wsrc, proof_buffer, proof_size, public_buffer,
-                                  public_size, error_msg, error_msg_maxsize, &zk);
-    }
-  } catch (const ProverError& e) {
-    set_err(error_msg, error_msg_maxsize, e.what());
-    rc = e.code;
-  } catch (const HipError& e) {            // HIP runtime failure: the context is suspect (PROVER_ERROR_RUNTIME)
-    set_err(error_msg, error_msg_maxsize, e.what());
-    rc = PROVER_ERROR_RUNTIME;
-  } catch (const std::bad_alloc&) {
-    set_err(error_msg, error_msg_maxsize, "out of host memory");
-    rc = PROVER_ERROR_RUNTIME;
-  } catch (const std::system_error& e) {   // a stage thread could not be started
-    set_err(error_msg, error_msg_maxsize, e.what());
-    rc = PROVER_ERROR_RUNTIME;
-  } catch (const std::exception& e) {
-    set_err(error_msg, error_msg_maxsize, e.what());
-    rc = PROVER_ERROR;
-  }
-  if (zk) {
-    zk->release();
-    delete zk;
-  }
-  if (mk) multi_key_release(ds, mk);
-  return rc;
-}
-
-// ---- device-resident key cache of groth16_prover_zkey_file ("optional device-resident zkey
-// cache keyed by path+mtime") ----------------------------------------------------------------------------
-// A long-lived caller (the prover server behind the CLI, or an FFI host process) proves many witnesses against
-// the same few keys (full_workflow.sh: layer one and two once per batch); uploading 1-21 GB and rebuilding the
-// CSR each time is most of a call. Keyed by (device, inode, size, mtime): a rewritten file is a different key.
-// ZKPOA_KEY_CACHE = number of keys kept (default 2, 0 = off); least recently used goes first, and everything
-// goes when an upload runs out of HBM.
-// When a resident key gets its fixed-base tables (ZKPOA_PRECOMP). A whole set costs 0.25 s at the layer-one shape and
-// 3-7 s at layers two and three -- twenty to thirty proofs' worth -- and saves ~10 % per proof, so it pays after a few
-// hundred proofs. r02 / r03 built it on the request path at the key's SECOND use: a workflow of two batches
-// (tests/4_sigs_2_batches_12_height) then spent 3.4 s on a 0.12 s proof. r04 default ("idle"): never on the request path
-// -- zkpoa_idle_work builds one table per call when the library has nothing else to do (the `prover` server calls it
-// after 300 ms without a request) -- except for a key that has served ZKPOA_PRECOMP_AFTER proofs (default 64) in a host
-// that never calls it. "eager" = the r03 behaviour, "0" = never.
-enum PrecompPolicy { kPrecompOff, kPrecompEager, kPrecompIdle };
-PrecompPolicy precomp_policy() {
-  const char* e = getenv("ZKPOA_PRECOMP");
-  if (!e || !*e) return kPrecompIdle;
-  if (!strcmp(e, "0") || !strcmp(e, "off")) return kPrecompOff;
-  if (!strcmp(e, "eager")) return kPrecompEager;
-  return kPrecompIdle;
-}
-uint64_t precomp_after() {
-  const char* e = getenv("ZKPOA_PRECOMP_AFTER");
-  const long v = e && *e ? atol(e) : 64;
-  return v < 1 ? 1 : (uint64_t)v;
-}
-// must this request build the key's tables before it proves? (done = proofs the key has served, settled / bytes = its tables)
-bool tables_due_now(uint64_t done, bool settled, uint64_t bytes) {
-  switch (precomp_policy()) {
-    case kPrecompEager: return done == 1 && bytes == 0;
-    case kPrecompIdle: return done >= precomp_after() && !settled && bytes == 0;
-    default: return false;
-  }
-}
-
-struct CachedKey {
-  dev_t dev;
-  ino_t ino;
-  off_t size;
-  struct timespec mtime;
-  zkpoa_zkey* zk;
-  uint64_t last_use;
-};
-std::vector<CachedKey> g_key_cache;
-uint64_t g_key_clock = 0;
-
-size_t key_cache_capacity() {
-  const char* e = getenv("ZKPOA_KEY_CACHE");
-  if (!e || !*e) return 2;
-  long v = atol(e);
-  return v < 0 ? 0 : (size_t)v;
-}
-
-void key_cache_drop(size_t idx) {
-  (void)hipDeviceSynchronize();
-  g_key_cache[idx].zk->release();
-  delete g_key_cache[idx].zk;
-  g_key_cache.erase(g_key_cache.begin() + (long)idx);
-}
-
-void key_cache_clear() {
-  while (!g_key_cache.empty()) key_cache_drop(g_key_cache.size() - 1);
-}
-
-// The same cache for keys sharded over the ranks of a multi-GPU process (one entry = G shard handles + their exchange
-// buffers); the second use of a key builds every shard's fixed-base tables, in parallel on the G devices.
-struct CachedMultiKey {
-  dev_t dev;
-  ino_t ino;
-  off_t size;
-  struct timespec mtime;
-  MultiKey* mk;
-  uint64_t last_use;
-};
-std::vector<CachedMultiKey> g_multi_cache;
-
-int multi_file_prove(DeviceSet* ds, int fd, const struct stat& sb, const char* path, const WtnsSrc& wsrc,
-                     char* proof_buffer, unsigned long* proof_size, char* public_buffer, unsigned long* public_size,
-                     char* error_msg, unsigned long error_msg_maxsize) {
-  int rc = PROVER_OK;
-  MultiKey* mk = nullptr;
-  bool cached = false, hit = false;
-  try {
-    const size_t cap = key_cache_capacity();
-    for (auto& c : g_multi_cache)
-      if (c.dev == sb.st_dev && c.ino == sb.st_ino && c.size == sb.st_size && c.mtime.tv_sec == sb.st_mtim.tv_sec &&
-          c.mtime.tv_nsec == sb.st_mtim.tv_nsec) {
-        mk = c.mk;
-        c.last_use = ++g_key_clock;
-        hit = cached = true;
-      }
-    auto drop = [&](size_t idx) {
-      multi_key_release(ds, g_multi_cache[idx].mk);
-      g_multi_cache.erase(g_multi_cache.begin() + (long)idx);
-    };
-    if (!mk) {
-      void* map = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-      if (map == MAP_FAILED) throw ProverError(PROVER_ERROR, std::string("cannot mmap zkey file ") + path);
-      try {
-        while (cap && g_multi_cache.size() >= cap) {
-          size_t lru = 0;
-          for (size_t i = 1; i < g_multi_cache.size(); i++)
-            if (g_multi_cache[i].last_use < g_multi_cache[lru].last_use) lru = i;
-          drop(lru);
-        }
-        try {
-          mk = multi_key_load(ds, reinterpret_cast<const uint8_t*>(map), (uint64_t)sb.st_size);
-        } catch (const HipError&) {
-          if (g_multi_cache.empty()) throw;
-          while (!g_multi_cache.empty()) drop(g_multi_cache.size() - 1);   // probably out of HBM: retry alone
-          for (int d : ds->ids) {
-            (void)hipSetDevice(d);
-            (void)hipGetLastError();
-          }
-          mk = multi_key_load(ds, reinterpret_cast<const uint8_t*>(map), (uint64_t)sb.st_size);
-        }
-      } catch (...) {
-        munmap(map, (size_t)sb.st_size);
-        throw;
-      }
-      munmap(map, (size_t)sb.st_size);
-      if (cap) {
-        g_multi_cache.push_back({sb.st_dev, sb.st_ino, sb.st_size, sb.st_mtim, mk, ++g_key_clock});
-        cached = true;
-      }
-    }
-    if (hit && tables_due_now(mk->proofs_done, mk->tables_tried, mk->table_bytes)) {
-      {
-        auto tp0 = std::chrono::steady_clock::now();
-        multi_precompute(ds, mk);
-        mk->tables_tried = true;
-        if (req_getenv("ZKPOA_VERBOSE"))
-          fprintf(stderr, "zkpoa: fixed-base tables for the cached key on %zu ranks: %.2f GB in %.0f ms\n", ds->ids.size(),
-                  mk->table_bytes / 1e9,
-                  std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count());
-      }
-    }
-    rc = multi_prove_to_json(ds, mk, wsrc, proof_buffer, proof_size, public_buffer, public_size, error_msg,
-                             error_msg_maxsize, (uint64_t)sb.st_size, hit);
-    mk->proofs_done++;
-  } catch (const ProverError& e) {
-    set_err(error_msg, error_msg_maxsize, e.what());
-    rc = e.code;
-  } catch (const HipError& e) {
-    set_err(error_msg, error_msg_maxsize, e.what());
-    rc = PROVER_ERROR_RUNTIME;
-    // the shards of a key whose proof died in the HIP runtime are not kept for the next request
-    for (size_t i = 0; i < g_multi_cache.size(); i++)
-      if (g_multi_cache[i].mk == mk) {
-        g_multi_cache.erase(g_multi_cache.begin() + (long)i);
-        cached = false;
-        break;
-      }
-  } catch (const std::bad_alloc&) {
-    set_err(error_msg, error_msg_maxsize, "out of host memory");
-    rc = PROVER_ERROR_RUNTIME;
-  } catch (const std::system_error& e) {
-    set_err(error_msg, error_msg_maxsize, e.what());
-    rc = PROVER_ERROR_RUNTIME;
-  } catch (const std::exception& e) {
-    set_err(error_msg, error_msg_maxsize, e.what());
-    rc = PROVER_ERROR;
-  }
-  if (mk && !cached) multi_key_release(ds, mk);
-  return rc;
-}
-
-// A request on a resident key in steady state (cached, tables built or not wanted): the witness goes into a free
-// staging buffer under the stage lock -- which is then dropped -- and the proof runs under the prove lock. Enters with
-// stage_lk held, leaves with it released.
-int staged_prove(zkpoa_context* ctx, const zkpoa_zkey* zk, const WtnsSrc& wsrc, uint64_t zkey_size,
-                 std::unique_lock<std::mutex>& stage_lk, hipStream_t cs, char* proof_buffer, unsigned long* proof_size,
-                 char* public_buffer, unsigned long* public_size, char* error_msg, unsigned long error_msg_maxsize) {
-  int rc = PROVER_OK, slot = -1;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
-    WtnsView w = parse_wtns(wsrc);
-    if (w.n != zk->nVars)
-      throw ProverError(PROVER_INVALID_WITNESS_LENGTH, "Invalid witness length. Circuit: " + std::to_string(zk->nVars) +
-                                                           ", witness: " + std::to_string(w.n));
-    if (!zk->wbuf[0]) zk->wbuf[0] = zk->d_witness;   // adopt the buffer the key came with
-    g_stage_cv.wait(stage_lk, [&] { return !zk->wbusy[0] || !zk->wbusy[1]; });
-    slot = !zk->wbusy[0] ? 0 : 1;
-    if (!zk->wbuf[slot]) ZK_HIP(hipMalloc(&zk->wbuf[slot], (size_t)zk->nVars * 32));
-    zk->wbusy[slot] = true;
-    g_staged_users++;
-    const auto tu = std::chrono::steady_clock::now();
-    w.upload(ctx, zk->wbuf[slot], 0, w.n, cs);      // on the copy stream(s): lane 0 may be busy with another proof's chain
-    const float up_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - tu).count();
-    std::vector<uint8_t> pub_store;
-    const uint8_t* pubs = w.publics(zk->nPublic, pub_store);
-    stage_lk.unlock();
-    {
-      std::lock_guard<std::mutex> lk(g_prove_mutex);
-      zk->d_witness = zk->wbuf[slot];
-      uint8_t rb[32], sb[32], pts[256];
-      const uint8_t *rp = nullptr, *sp = nullptr;
-      env_blinding(rb, sb, rp, sp);
-      prove_core(ctx, zk, rp, sp, pts);
-      selfcheck(ctx, zk, pts, pubs);
-      ctx->io_ms[0] = up_ms;
-      ctx->io_ms[1] = (float)((double)w.n * 32 / 1e6);
-      rc = emit_outputs(ctx, zk, pts, pubs, proof_buffer, proof_size, public_buffer, public_size, error_msg,
-                        error_msg_maxsize, 0.0, zkey_size, "cached,");
-      const_cast<zkpoa_zkey*>(zk)->proofs_done++;
-    }
-  } catch (...) {
-    rc = classify_current_exception(error_msg, error_msg_maxsize);
-  }
-  if (!stage_lk.owns_lock()) stage_lk.lock();
-  if (slot >= 0) {
-    zk->wbusy[slot] = false;
-    g_staged_users--;
-  }
-  stage_lk.unlock();
-  g_stage_cv.notify_all();
-  return rc;
-}
-
-int zkey_file_prove(const char* path, const WtnsSrc& wsrc, char* proof_buffer,
-                    unsigned long* proof_size, char* public_buffer, unsigned long* public_size, char* error_msg,
-                    unsigned long error_msg_maxsize) {
-  int fd = open(path, O_RDONLY);
-  if (fd < 0) {
-    set_err(error_msg, error_msg_maxsize, std::string("cannot open zkey file ") + path);
-    return PROVER_ERROR;
-  }
-  struct stat sb;
-  if (fstat(fd, &sb) != 0 || sb.st_size == 0) {
-    close(fd);
-    set_err(error_msg, error_msg_maxsize, std::string("cannot stat zkey file ") + path);
-    return PROVER_ERROR;
-  }
-  std::string err;
-  DeviceSet* ds = nullptr;
-  int dcode = PROVER_ERROR;
-  try {
-    uint32_t power = 0;
-    if (!devices_ready()) {   // the first key of the process decides the device list: its domain size is in the header
-      void* map = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-      if (map == MAP_FAILED) throw ProverError(PROVER_ERROR, std::string("cannot mmap zkey file ") + path);
-      try {
-        power = zkey_power(reinterpret_cast<const uint8_t*>(map), (uint64_t)sb.st_size);
-      } catch (...) {
-        munmap(map, (size_t)sb.st_size);
-        throw;
-      }
-      munmap(map, (size_t)sb.st_size);
-    }
-    ds = process_devices(power, err, &dcode);
-  } catch (const std::exception& e) {   // malformed key: nothing touches a GPU
-    close(fd);
-    set_err(error_msg, error_msg_maxsize, e.what());
-    return PROVER_ERROR;
-  }
-  if (!ds) {
-    close(fd);
-    set_err(error_msg, error_msg_maxsize, err);
-    return dcode;
-  }
-  zkpoa_context* ctx = ds->ctx[0];
-  std::unique_lock<std::mutex> stage_lk(g_stage_mutex);
-  if (ds->ids.size() == 1) {   // steady state of a resident single-GPU key: stage the witness, then prove (two locks)
-    for (auto& c : g_key_cache)
-      if (c.dev == sb.st_dev && c.ino == sb.st_ino && c.size == sb.st_size && c.mtime.tv_sec == sb.st_mtim.tv_sec &&
-          c.mtime.tv_nsec == sb.st_mtim.tv_nsec) {
-        const uint64_t done = c.zk->proofs_done.load();
-        const bool tables_due = tables_due_now(done, c.zk->tables_settled, c.zk->table_bytes);
-        hipStream_t cs = ctx->dev.copy_stream_wait();
-        if (done >= 1 && !tables_due && cs) {
-          c.last_use = ++g_key_clock;
-          close(fd);
-          return staged_prove(ctx, c.zk, wsrc, (uint64_t)sb.st_size, stage_lk, cs, proof_buffer, proof_size, public_buffer,
-                              public_size, error_msg, error_msg_maxsize);
-        }
-      }
-  }
-  // everything else changes the cache or a key: alone, with both locks
-  g_stage_cv.wait(stage_lk, [] { return g_staged_users == 0; });
-  std::lock_guard<std::mutex> lk(g_prove_mutex);
-  if (ds->ids.size() > 1) {
-    int rc = multi_file_prove(ds, fd, sb, path, wsrc, proof_buffer, proof_size, public_buffer, public_size,
-                              error_msg, error_msg_maxsize);
-    close(fd);
-    return rc;
-  }
-  int rc = PROVER_OK;
-  zkpoa_zkey* zk = nullptr;
-  bool owned = false, hit = false, proved = false;
-  double load_ms = 0;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
-    const size_t cap = key_cache_capacity();
-    for (auto& c : g_key_cache)
-      if (c.dev == sb.st_dev && c.ino == sb.st_ino && c.size == sb.st_size && c.mtime.tv_sec == sb.st_mtim.tv_sec &&
-          c.mtime.tv_nsec == sb.st_mtim.tv_nsec) {
-        zk = c.zk;
-        c.last_use = ++g_key_clock;
-        hit = true;
-      }
-    if (zk && zk->wbuf[0]) zk->d_witness = zk->wbuf[0];   // nothing is staged now: back to the first buffer
-    if (!zk) {
-      void* map = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-      if (map == MAP_FAILED) throw ProverError(PROVER_ERROR, std::string("cannot mmap zkey file ") + path);
-      auto tl0 = std::chrono::steady_clock::now();
-      try {
-        while (cap && g_key_cache.size() >= cap) {   // make room first: least recently used
-          size_t lru = 0;
-          for (size_t i = 1; i < g_key_cache.size(); i++)
-            if (g_key_cache[i].last_use < g_key_cache[lru].last_use) lru = i;
-          key_cache_drop(lru);
-        }
-        // load and prove in one overlapped phase (the mapping must outlive it: the uploader streams from it)
-        try {
-          rc = load_and_prove_to_json(ctx, reinterpret_cast<const uint8_t*>(map), (uint64_t)sb.st_size, wsrc,
-                                      proof_buffer, proof_size, public_buffer, public_size, error_msg, error_msg_maxsize,
-                                      &zk, fd);
-        } catch (const HipError&) {
-          if (g_key_cache.empty()) throw;
-          key_cache_clear();                          // probably out of HBM: retry with nothing else resident
-          (void)hipGetLastError();
-          rc = load_and_prove_to_json(ctx, reinterpret_cast<const uint8_t*>(map), (uint64_t)sb.st_size, wsrc,
-                                      proof_buffer, proof_size, public_buffer, public_size, error_msg, error_msg_maxsize,
-                                      &zk, fd);
-        }
-        proved = true;
-      } catch (...) {
-        munmap(map, (size_t)sb.st_size);
-        if (zk) {   // loaded, but the proof failed afterwards (self-check, output): not cached, not leaked
-          (void)hipDeviceSynchronize();
-          zk->release();
-          delete zk;
-          zk = nullptr;
-        }
-        throw;
-      }
-      munmap(map, (size_t)sb.st_size);
-      load_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count();
-      if (cap) g_key_cache.push_back({sb.st_dev, sb.st_ino, sb.st_size, sb.st_mtim, zk, ++g_key_clock});
-      else owned = true;
-    }
-    // a key that comes out of the cache is being reused: build its fixed-base tables now, once (ZKPOA_PRECOMP=0 off)
-    if (hit && !owned && tables_due_now(zk->proofs_done, zk->tables_settled, zk->table_bytes)) {
-      {
-        auto tp0 = std::chrono::steady_clock::now();
-        try {
-          uint64_t used = zkey_precompute(ctx, zk, 0);
-          if (req_getenv("ZKPOA_VERBOSE"))
-            fprintf(stderr, "zkpoa: fixed-base tables for the cached key: %.2f GB in %.0f ms\n", used / 1e9,
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count());
-        } catch (const HipError&) {   // out of HBM: the classic form keeps working
-          zk->release_tables();
-          (void)hipGetLastError();
-        }
-        zk->tables_settled = true;
-      }
-    }
-    if (!proved)
-      rc = prove_to_json(ctx, zk, wsrc, proof_buffer, proof_size, public_buffer, public_size, error_msg,
-                         error_msg_maxsize, load_ms, (uint64_t)sb.st_size, hit);
-    zk->proofs_done++;
-  } catch (...) {
-    rc = classify_current_exception(error_msg, error_msg_maxsize);
-  }
-  close(fd);
-  if (owned && zk) {
-    zk->release();
-    delete zk;
-  }
-  return rc;
-}
+#include "multi_device.hip.h"   // several GPUs: the device set of the process, sharded keys and their proof
+#include "prove_request.hip.h"  // zkey + witness -> key cache -> proof -> self-check -> the two JSON texts
 
 }  // namespace
 
@@ -2179,27 +1539,37 @@ int zkey_file_prove(const char* path, const WtnsSrc& wsrc, char* proof_buffer,
     return PROVER_ERROR;              \
   }
 
-extern "C" int zkpoa_zkey_load(zkpoa_context* ctx, const void* zkey_buffer, unsigned long zkey_size, zkpoa_zkey** out) {
+// what the four loaders from a zkey image share; `shard` = the entry point's own arguments to zkey_load_impl
+template <class... Shard>
+static int zkey_load_abi(zkpoa_context* ctx, const void* zkey_buffer, unsigned long zkey_size, zkpoa_zkey** out, Shard... shard) {
   if (!ctx || !out || !zkey_buffer) return PROVER_ERROR;
   *out = nullptr;
   try {
     ZK_HIP(hipSetDevice(ctx->dev.device));
-    *out = zkey_load_impl(ctx, reinterpret_cast<const uint8_t*>(zkey_buffer), zkey_size);
+    *out = zkey_load_impl(ctx, reinterpret_cast<const uint8_t*>(zkey_buffer), zkey_size, shard...);
   }
   ZK_PROVER_CATCH(ctx)
   return PROVER_OK;
 }
 
+extern "C" int zkpoa_zkey_load(zkpoa_context* ctx, const void* zkey_buffer, unsigned long zkey_size, zkpoa_zkey** out) {
+  return zkey_load_abi(ctx, zkey_buffer, zkey_size, out);
+}
+
 extern "C" int zkpoa_zkey_load_shard(zkpoa_context* ctx, const void* zkey_buffer, unsigned long zkey_size,
                                      uint64_t rank, uint64_t world, zkpoa_zkey** out) {
-  if (!ctx || !out || !zkey_buffer) return PROVER_ERROR;
-  *out = nullptr;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
-    *out = zkey_load_impl(ctx, reinterpret_cast<const uint8_t*>(zkey_buffer), zkey_size, rank, world);
-  }
-  ZK_PROVER_CATCH(ctx)
-  return PROVER_OK;
+  return zkey_load_abi(ctx, zkey_buffer, zkey_size, out, rank, world);
+}
+
+extern "C" int zkpoa_zkey_load_shard_split(zkpoa_context* ctx, const void* zkey_buffer, unsigned long zkey_size,
+                                           uint64_t rank, uint64_t world, zkpoa_zkey** out) {
+  return zkey_load_abi(ctx, zkey_buffer, zkey_size, out, rank, world, true);
+}
+
+extern "C" int zkpoa_zkey_load_shard_ex(zkpoa_context* ctx, const void* zkey_buffer, unsigned long zkey_size,
+                                        uint64_t rank, uint64_t world, int flags, zkpoa_zkey** out) {
+  return zkey_load_abi(ctx, zkey_buffer, zkey_size, out, rank, world, (flags & ZKPOA_SHARD_SPLIT_CHAIN) != 0,
+                       ZKPOA_SHARD_BLOCK_LOG(flags));
 }
 
 extern "C" int zkpoa_zkey_set_shard(zkpoa_zkey* zkey, uint64_t rank, uint64_t world) {
@@ -2214,31 +1584,6 @@ extern "C" int zkpoa_zkey_set_shard(zkpoa_zkey* zkey, uint64_t rank, uint64_t wo
   } catch (const std::exception&) {
     return PROVER_ERROR;
   }
-  return PROVER_OK;
-}
-
-extern "C" int zkpoa_zkey_load_shard_split(zkpoa_context* ctx, const void* zkey_buffer, unsigned long zkey_size,
-                                           uint64_t rank, uint64_t world, zkpoa_zkey** out) {
-  if (!ctx || !out || !zkey_buffer) return PROVER_ERROR;
-  *out = nullptr;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
-    *out = zkey_load_impl(ctx, reinterpret_cast<const uint8_t*>(zkey_buffer), zkey_size, rank, world, true);
-  }
-  ZK_PROVER_CATCH(ctx)
-  return PROVER_OK;
-}
-
-extern "C" int zkpoa_zkey_load_shard_ex(zkpoa_context* ctx, const void* zkey_buffer, unsigned long zkey_size,
-                                        uint64_t rank, uint64_t world, int flags, zkpoa_zkey** out) {
-  if (!ctx || !out || !zkey_buffer) return PROVER_ERROR;
-  *out = nullptr;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
-    *out = zkey_load_impl(ctx, reinterpret_cast<const uint8_t*>(zkey_buffer), zkey_size, rank, world,
-                          (flags & ZKPOA_SHARD_SPLIT_CHAIN) != 0, ZKPOA_SHARD_BLOCK_LOG(flags));
-  }
-  ZK_PROVER_CATCH(ctx)
   return PROVER_OK;
 }
 
@@ -2283,9 +1628,7 @@ extern "C" int zkpoa_witness_load(zkpoa_context* ctx, const zkpoa_zkey* zkey, co
   try {
     ZK_HIP(hipSetDevice(ctx->dev.device));
     WtnsView w = parse_wtns(reinterpret_cast<const uint8_t*>(wtns_buffer), wtns_size);
-    if (w.n != zkey->nVars)
-      throw ProverError(PROVER_INVALID_WITNESS_LENGTH, "Invalid witness length. Circuit: " +
-                                                           std::to_string(zkey->nVars) + ", witness: " + std::to_string(w.n));
+    check_witness_len(w, zkey);
     if (public_le && public_capacity < (unsigned long)zkey->nPublic * 32)
       throw ProverError(PROVER_ERROR_SHORT_BUFFER, "public buffer too small");
     ctx->uploader.upload(zkey->d_witness, w.values, (size_t)w.n * 32, ctx->dev.device, ctx->dev.lanes[0].stream);
@@ -2371,9 +1714,7 @@ extern "C" int zkpoa_prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zkey, 
   try {
     ZK_HIP(hipSetDevice(ctx->dev.device));
     WtnsView w = parse_wtns(reinterpret_cast<const uint8_t*>(wtns_buffer), wtns_size);
-    if (w.n != zkey->nVars)
-      throw ProverError(PROVER_INVALID_WITNESS_LENGTH, "Invalid witness length. Circuit: " +
-                                                           std::to_string(zkey->nVars) + ", witness: " + std::to_string(w.n));
+    check_witness_len(w, zkey);
     if (public_le && public_capacity < (unsigned long)zkey->nPublic * 32)
       throw ProverError(PROVER_ERROR_SHORT_BUFFER, "public buffer too small");
     if (zkey->split_world > 1)
@@ -2506,21 +1847,6 @@ static zkpoa_zkey* zkey_load_device_impl(zkpoa_context* ctx, uint64_t n_vars, ui
   return zk.release();
 }
 
-extern "C" int zkpoa_zkey_load_device(zkpoa_context* ctx, uint64_t n_vars, uint64_t n_public, unsigned log_domain,
-                                      const void* d_A, const void* d_B1, const void* d_B2, const void* d_C,
-                                      const void* d_H, const void* d_coef_records, uint64_t n_coefs,
-                                      const uint8_t header_points[448], zkpoa_zkey** out) {
-  if (!ctx || !out || !header_points) return PROVER_ERROR;
-  *out = nullptr;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
-    *out = zkey_load_device_impl(ctx, n_vars, n_public, log_domain, 0, 1, false, 0, d_A, d_B1, d_B2, d_C, d_H,
-                                 d_coef_records, n_coefs, header_points);
-  }
-  ZK_PROVER_CATCH(ctx)
-  return PROVER_OK;
-}
-
 extern "C" int zkpoa_zkey_load_device_shard(zkpoa_context* ctx, uint64_t n_vars, uint64_t n_public, unsigned log_domain,
                                             uint64_t rank, uint64_t world, int split, const void* d_A,
                                             const void* d_B1, const void* d_B2, const void* d_C, const void* d_H,
@@ -2536,6 +1862,14 @@ extern "C" int zkpoa_zkey_load_device_shard(zkpoa_context* ctx, uint64_t n_vars,
   }
   ZK_PROVER_CATCH(ctx)
   return PROVER_OK;
+}
+
+extern "C" int zkpoa_zkey_load_device(zkpoa_context* ctx, uint64_t n_vars, uint64_t n_public, unsigned log_domain,
+                                      const void* d_A, const void* d_B1, const void* d_B2, const void* d_C,
+                                      const void* d_H, const void* d_coef_records, uint64_t n_coefs,
+                                      const uint8_t header_points[448], zkpoa_zkey** out) {
+  return zkpoa_zkey_load_device_shard(ctx, n_vars, n_public, log_domain, 0, 1, 0, d_A, d_B1, d_B2, d_C, d_H, d_coef_records,
+                                      n_coefs, header_points, out);
 }
 
 extern "C" int zkpoa_prove_device(zkpoa_context* ctx, const zkpoa_zkey* zkey, const void* d_witness,
@@ -2677,44 +2011,30 @@ extern "C" int groth16_prover(const void* zkey_buffer, unsigned long zkey_size, 
                               unsigned long wtns_size, char* proof_buffer, unsigned long* proof_size,
                               char* public_buffer, unsigned long* public_size, char* error_msg,
                               unsigned long error_msg_maxsize) {
-  if (!zkey_buffer || !wtns_buffer || !proof_size || !public_size) {
-    set_err(error_msg, error_msg_maxsize, "null argument");
-    return PROVER_ERROR;
-  }
+  const ProveOut out{proof_buffer, proof_size, public_buffer, public_size, error_msg, error_msg_maxsize};
+  if (!zkey_buffer || !wtns_buffer || !proof_size || !public_size) return out.fail(PROVER_ERROR, "null argument");
   return one_shot(reinterpret_cast<const uint8_t*>(zkey_buffer), zkey_size,
-                  WtnsSrc{reinterpret_cast<const uint8_t*>(wtns_buffer), wtns_size, -1}, proof_buffer, proof_size, public_buffer,
-                  public_size, error_msg, error_msg_maxsize);
+                  WtnsSrc{reinterpret_cast<const uint8_t*>(wtns_buffer), wtns_size, -1}, out);
 }
 
 extern "C" int groth16_prover_zkey_file(const char* zkey_file_path, const void* wtns_buffer, unsigned long wtns_size,
                                         char* proof_buffer, unsigned long* proof_size, char* public_buffer,
                                         unsigned long* public_size, char* error_msg, unsigned long error_msg_maxsize) {
-  if (!zkey_file_path || !wtns_buffer || !proof_size || !public_size) {
-    set_err(error_msg, error_msg_maxsize, "null argument");
-    return PROVER_ERROR;
-  }
-  return zkey_file_prove(zkey_file_path, WtnsSrc{reinterpret_cast<const uint8_t*>(wtns_buffer), wtns_size, -1}, proof_buffer,
-                         proof_size, public_buffer, public_size, error_msg, error_msg_maxsize);
+  const ProveOut out{proof_buffer, proof_size, public_buffer, public_size, error_msg, error_msg_maxsize};
+  if (!zkey_file_path || !wtns_buffer || !proof_size || !public_size) return out.fail(PROVER_ERROR, "null argument");
+  return zkey_file_prove(zkey_file_path, WtnsSrc{reinterpret_cast<const uint8_t*>(wtns_buffer), wtns_size, -1}, out);
 }
 
 extern "C" int zkpoa_groth16_prover_files(const char* zkey_file_path, const char* wtns_file_path, char* proof_buffer,
                                           unsigned long* proof_size, char* public_buffer, unsigned long* public_size,
                                           char* error_msg, unsigned long error_msg_maxsize) {
-  if (!zkey_file_path || !wtns_file_path || !proof_size || !public_size) {
-    set_err(error_msg, error_msg_maxsize, "null argument");
-    return PROVER_ERROR;
-  }
-  int wfd = open(wtns_file_path, O_RDONLY | O_CLOEXEC);
+  const ProveOut out{proof_buffer, proof_size, public_buffer, public_size, error_msg, error_msg_maxsize};
+  if (!zkey_file_path || !wtns_file_path || !proof_size || !public_size) return out.fail(PROVER_ERROR, "null argument");
+  const Fd wtns(open(wtns_file_path, O_RDONLY | O_CLOEXEC));
   struct stat wsb;
-  if (wfd < 0 || fstat(wfd, &wsb) != 0 || !S_ISREG(wsb.st_mode)) {
-    if (wfd >= 0) close(wfd);
-    set_err(error_msg, error_msg_maxsize, std::string("cannot read witness file ") + wtns_file_path);
-    return PROVER_ERROR;
-  }
-  int rc = zkey_file_prove(zkey_file_path, WtnsSrc{nullptr, (uint64_t)wsb.st_size, wfd}, proof_buffer, proof_size,
-                           public_buffer, public_size, error_msg, error_msg_maxsize);
-  close(wfd);
-  return rc;
+  if (wtns.fd < 0 || fstat(wtns.fd, &wsb) != 0 || !S_ISREG(wsb.st_mode))
+    return out.fail(PROVER_ERROR, std::string("cannot read witness file ") + wtns_file_path);
+  return zkey_file_prove(zkey_file_path, WtnsSrc{nullptr, (uint64_t)wsb.st_size, wtns.fd}, out);
 }
 
 extern "C" int zkpoa_set_thread_options(const char* r_dec, const char* s_dec, const char* json_style, int verbose) {
@@ -2736,70 +2056,4 @@ extern "C" int zkpoa_clear_thread_options(void) {
 // next fixed-base table of the most recently used resident key that has none yet (ZKPOA_PRECOMP policy "idle") -- so that
 // a request arriving meanwhile waits for one table at most. Returns 1 when a step was done (call again while idle), 0
 // when there is nothing to do, the policy says no, or a request is in flight (never blocks behind one).
-extern "C" int zkpoa_idle_work(void) {
-  if (precomp_policy() != kPrecompIdle) return 0;
-  std::unique_lock<std::mutex> stage_lk(g_stage_mutex, std::try_to_lock);
-  if (!stage_lk.owns_lock() || g_staged_users) return 0;
-  std::unique_lock<std::mutex> lk(g_prove_mutex, std::try_to_lock);
-  if (!lk.owns_lock()) return 0;
-  DeviceSet* ds = nullptr;
-  {
-    std::lock_guard<std::mutex> dl(g_devset_mutex);
-    ds = g_devset;
-  }
-  if (!ds) return 0;
-  const bool verbose = getenv("ZKPOA_VERBOSE") != nullptr;
-  try {
-    if (ds->ids.size() > 1) {
-      for (auto& c : g_multi_cache)
-        if (c.mk->proofs_done >= 1 && c.mk->table_bytes == 0 && !c.mk->tables_tried) {
-          auto t0 = std::chrono::steady_clock::now();
-          c.mk->tables_tried = true;
-          multi_precompute(ds, c.mk);
-          if (verbose)
-            fprintf(stderr, "zkpoa: idle: fixed-base tables for the cached key on %zu ranks: %.2f GB in %.0f ms\n", ds->ids.size(),
-                    c.mk->table_bytes / 1e9, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-          return 1;
-        }
-      return 0;
-    }
-    CachedKey* pick = nullptr;
-    for (auto& c : g_key_cache)
-      if (c.zk->proofs_done.load() >= 1 && !c.zk->tables_settled && (!pick || c.last_use > pick->last_use)) pick = &c;
-    zkpoa_context* ctx = ds->ctx[0];
-    ZK_HIP(hipSetDevice(ctx->dev.device));
-    if (!pick) {
-      // Tables complete: one throw-away proof on the witness the key still holds. Building the tables gave the lanes'
-      // workspaces back to the allocator, and the first proof through the tables would otherwise pay for regrowing them
-      // (0.5-0.6 s at the layer-two / -three shapes) inside a request.
-      for (auto& c : g_key_cache)
-        if (c.zk->tables_settled && c.zk->table_bytes && !c.zk->warmed && c.zk->d_witness && is_full_key(c.zk)) {
-          auto t0 = std::chrono::steady_clock::now();
-          c.zk->warmed = true;
-          uint8_t parts[384];
-          prove_partials(ctx, c.zk, parts);
-          if (verbose)
-            fprintf(stderr, "zkpoa: idle: warm-up proof through the new tables: %.0f ms\n",
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-          return 1;
-        }
-      return 0;
-    }
-    const uint64_t before = pick->zk->table_bytes;
-    auto t0 = std::chrono::steady_clock::now();
-    try {
-      (void)zkey_precompute(ctx, pick->zk, 0, 1);
-    } catch (const HipError&) {   // out of HBM: what exists stays, nothing more is tried
-      (void)hipGetLastError();
-      pick->zk->tables_settled = true;
-    }
-    if (verbose)
-      fprintf(stderr, "zkpoa: idle: fixed-base table step for the cached key: +%.2f GB in %.0f ms (%.2f GB so far%s)\n",
-              (pick->zk->table_bytes - before) / 1e9,
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(),
-              pick->zk->table_bytes / 1e9, pick->zk->tables_settled ? ", complete" : "");
-    return 1;
-  } catch (const std::exception&) {
-    return 0;
-  }
-}
+extern "C" int zkpoa_idle_work(void) { return idle_work(); }

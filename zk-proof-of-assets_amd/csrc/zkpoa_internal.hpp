@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <string>
 #include <vector>
 
@@ -74,6 +75,11 @@ struct zkpoa_msm_table {   // C-ABI handle of a fixed-base table (zkpoa_msm_tabl
 
 namespace zkpoa {
 void set_err(char* buf, unsigned long cap, const std::string& msg);
+
+// host-clock milliseconds since t0 (the phase times of ZKPOA_VERBOSE and of zkpoa_context::ms / io_ms)
+inline double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
 
 // hipFree waits for the whole device, copies in flight included. While a one-shot prove overlaps the key upload with
 // compute, temporaries are therefore parked in the calling thread's sink and freed after the proof.
