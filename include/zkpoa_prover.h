@@ -305,10 +305,63 @@ int zkpoa_setup_accumulate(zkpoa_context* ctx, int group, const void* d_points, 
  * ranges of the circuit's domain; computes sections 3 and 5-8 with zkpoa_setup_accumulate, section 9 (H) as the odd
  * points of the size-2n Lagrange basis, section 4 as snarkjs stores it (A and B terms per constraint ascending by
  * signal, then the nPublic + 1 public rows; values scaled by R^2), header with gamma2 = delta2 = the G2 generator
- * and delta1 = the G1 generator. Section 10 holds a zero circuit hash and no contributions: snarkjs' transcript hash
- * is not restated (nothing in the reference pins it), so the key proves and verifies but `snarkjs zkey verify` would
- * not accept its hash. The `zkpoa-setup` executable takes snarkjs' argument order. Errors: zkpoa_last_error. */
+ * and delta1 = the G1 generator. Section 10 holds a zero circuit hash and no contributions ("no transcript"); see
+ * zkpoa_zkey_new_ex for a key with one. The `zkpoa-setup` executable takes snarkjs' argument order.
+ * Errors: zkpoa_last_error. */
 int zkpoa_zkey_new(zkpoa_context* ctx, const char* r1cs_path, const char* ptau_path, const char* zkey_path);
+/* ---- the phase-2 transcript (section 10; DESIGN.md "Phase-2 transcript") ------------------------------------------------
+ * The publicly checkable trail of phase 2 as snarkjs lays it out: a circuit hash (Blake2b-512 over the initial key's
+ * points) and one record per contribution or beacon (public key of its secret, transcript hash). It is opt-in: the
+ * functions above keep writing and accepting keys without one.
+ * No file made by snarkjs exists on this machine or in the reference. Interoperability with `snarkjs zkey verify` is
+ * therefore NOT exercised. What is tested is self-consistency, plus every primitive against an independent
+ * implementation.
+ * zkpoa_zkey_new_ex with ZKPOA_SETUP_TRANSCRIPT writes the same key as zkpoa_zkey_new with the circuit hash filled in
+ * (the ptau must hold section 2, tau^i G1 for i < 2n - 1). flags = 0 is zkpoa_zkey_new. */
+#define ZKPOA_SETUP_TRANSCRIPT 0x1u
+int zkpoa_zkey_new_ex(zkpoa_context* ctx, const char* r1cs_path, const char* ptau_path, const char* zkey_path,
+                      uint32_t flags);
+/* zkpoa_zkey_contribute on a key that carries a transcript (an error otherwise): the same arithmetic, and a type-0 record
+ * appended: deltaAfter, g1_s = s * G1 (s from /dev/urandom), g1_sx = d * g1_s, g2_spx = d * hashToG2(transcript hash),
+ * the optional name (at most 255 bytes). ZKPOA_PHASE2_S in the environment fixes s (tests only; a warning is printed). */
+int zkpoa_zkey_contribute_ex(zkpoa_context* ctx, const char* zkey_in_path, const char* zkey_out_path,
+                             const uint8_t* delta_le, const char* name);
+/* `snarkjs zkey beacon <in> <out> <beaconHash> <numIterationsExp>` (g16_setup.sh:269-278): a contribution whose secret
+ * and g1_s come from a ChaCha generator keyed by SHA-256 iterated 2^num_iterations_exp times over the beacon bytes, so
+ * that any verifier recomputes them; a type-1 record. The input must carry a transcript. Exponents above 30 are refused
+ * (2^30 hashes take minutes; more would not finish); beacon_len at most 255. */
+int zkpoa_zkey_beacon(zkpoa_context* ctx, const char* zkey_in_path, const char* zkey_out_path, const uint8_t* beacon,
+                      unsigned long beacon_len, uint32_t num_iterations_exp, const char* name);
+/* Host only: *has_transcript <- the circuit hash is not zero, *count <- the records of section 10, text (optional) <- one
+ * line "contribution <name>" or "beacon <name>" per record. PROVER_ERROR for an unreadable file or section 10. */
+int zkpoa_zkey_contributions(const char* zkey_path, int* has_transcript, uint32_t* count, char* text, unsigned long cap);
+/* Test hooks of the transcript's device work. zkpoa_hash_form: n points of group 1 | 2 (host, wire form) -> their hash
+ * form (uncompressed big-endian standard form, Fq2 as c1 then c0, infinity = 0x40 then zeros), converted on the device
+ * in pieces of piece_points (0 = default) through double-buffered pinned staging; digest <- Blake2b-512 of the stream,
+ * out_bytes (optional) <- the stream itself. zkpoa_h_diff: out[i] = points[i + n] - points[i], i < n - 1, over 2n - 1
+ * G1 points (the H part of the circuit hash over ptau section 2). */
+int zkpoa_hash_form(zkpoa_context* ctx, int group, const void* points, uint64_t n, uint64_t piece_points, void* out_bytes,
+                    uint8_t digest[64]);
+int zkpoa_h_diff(zkpoa_context* ctx, const void* points, uint64_t n, void* out);
+/* Host-only primitives of the transcript (csrc/phase2.hpp), exported for the tests. Field elements and scalars are 32 B
+ * little-endian standard form unless a point's wire form (Montgomery) is named; ChaCha keys are eight u32 words. */
+int zkpoa_blake2b512(const void* data, unsigned long len, uint8_t out[64]);
+void* zkpoa_blake2b_new(void);
+int zkpoa_blake2b_update(void* state, const void* data, unsigned long len);
+int zkpoa_blake2b_final(void* state, uint8_t out[64]);          /* also frees the state */
+int zkpoa_sha256(const void* data, unsigned long len, uint8_t out[32]);
+void* zkpoa_chacha_new(const uint32_t key[8]);
+uint32_t zkpoa_chacha_next_u32(void* rng);
+uint64_t zkpoa_chacha_next_u64(void* rng);                       /* high word first */
+int zkpoa_chacha_next_bool(void* rng);
+void zkpoa_chacha_free(void* rng);
+int zkpoa_fq_sqrt(const uint8_t a[32], uint8_t root[32]);        /* 1 = a root was written, 0 = not a square */
+int zkpoa_fq2_sqrt(const uint8_t a[64], uint8_t root[64]);
+int zkpoa_fr_from_rng(const uint32_t key[8], uint8_t out[32]);
+int zkpoa_g1_from_rng(const uint32_t key[8], uint8_t out[64]);   /* wire form */
+int zkpoa_g2_from_rng(const uint32_t key[8], uint8_t out[128]);  /* wire form, cofactor cleared */
+int zkpoa_hash_to_g2(const uint8_t hash[64], uint8_t out[128]);
+int zkpoa_beacon_key(const uint8_t* beacon, unsigned long len, uint32_t num_iterations_exp, uint32_t key[8]);
 /* For a one-shot command only (zkpoa-setup): on != 0 leaves the large host arrays of zkpoa_zkey_new to the process's
  * exit instead of freeing them before the call returns (giving ~100 GB back page by page takes seconds at the
  * layer-three shape). A long-lived caller leaves this off. */
@@ -316,9 +369,8 @@ void zkpoa_setup_defer_host_frees(int on);
 /* The arithmetic of `snarkjs zkey contribute <in.zkey> <out.zkey>` (g16_setup.sh:262-266): with a secret d (delta_le:
  * 32 B little-endian in [1, r); NULL = drawn from /dev/urandom), delta1, delta2 <- d * delta1, d * delta2 and every
  * point of sections 8 (C) and 9 (H) <- (1/d) * point (device; one scalar for all points, so no lane diverges). All
- * other sections are copied. NOT produced: the contribution record of section 10 (public key of d, proof of
- * knowledge, transcript hash) -- snarkjs' transcript is not restated, so the result proves and verifies under its new
- * verification key but carries no publicly checkable trail; use snarkjs where that trail is the point. */
+ * other sections are copied, section 10 included: no contribution record is written (zkpoa_zkey_contribute_ex writes
+ * one). On a key that carries a transcript this leaves a stale trail, which zkpoa_zkey_verify reports as CONTRIBUTIONS. */
 int zkpoa_zkey_contribute(zkpoa_context* ctx, const char* zkey_in_path, const char* zkey_out_path, const uint8_t* delta_le);
 /* `snarkjs wtns check <circuit.r1cs> <witness.wtns>` (scripts/g16_verify.sh:205-210): every constraint's
  * <A, w> * <B, w> == <C, w> on the device. *violated <- how many constraints fail (0 = "WITNESS IS CORRECT"),
@@ -340,7 +392,12 @@ int zkpoa_wtns_check(zkpoa_context* ctx, const char* r1cs_path, const char* wtns
  *           Q = sum_j a_j beta*L_j + b_j alpha*L_j + c_j L_j + sigma_j (odd point j of the 2n basis)
  * PROVER_ERROR (zkpoa_last_error) for a malformed file: bad magic, a missing section, a length that contradicts the
  * header, a key whose nVars / nPublic / domain differ from the circuit's, a field element >= its modulus, a ptau too
- * small for the domain or with a point off its curve. Section 10 (circuit hash, contribution records) is not read.
+ * small for the domain or with a point off its curve, a truncated or over-long section 10.
+ * A key whose circuit hash is zero carries no transcript: section 10 is not looked at further. Otherwise two more checks:
+ *   CSHASH         the circuit hash, recomputed from the r1cs, the ptau and the key's A, B1, B2, IC
+ *   CONTRIBUTIONS  every record, against the recomputed circuit hash: its transcript hash; e(g1_s, g2_spx) =
+ *                  e(g1_sx, g2_sp); e(deltaAfter_k, g2_sp) = e(deltaAfter_{k-1}, g2_spx) with deltaAfter_0 = G1; the last
+ *                  deltaAfter equals delta1; a beacon's g1_s and g1_sx recomputed from its beacon bytes
  * These are this project's formulas: a key made by snarkjs passes as far as snarkjs computes the same sections. */
 #define ZKPOA_ZKEY_HEADER 0x01u
 #define ZKPOA_ZKEY_POINTS 0x02u
@@ -350,6 +407,8 @@ int zkpoa_wtns_check(zkpoa_context* ctx, const char* r1cs_path, const char* wtns
 #define ZKPOA_ZKEY_B1 0x20u
 #define ZKPOA_ZKEY_B2 0x40u
 #define ZKPOA_ZKEY_ICCH 0x80u
+#define ZKPOA_ZKEY_CSHASH 0x100u
+#define ZKPOA_ZKEY_CONTRIBUTIONS 0x200u
 int zkpoa_zkey_verify(zkpoa_context* ctx, const char* r1cs_path, const char* ptau_path, const char* zkey_path,
                       uint32_t* failed_checks);
 /* `snarkjs powersoftau verify <pot.ptau>` (the reference's TODO at scripts/g16_setup.sh:201, g16_verify.sh:164): do the

@@ -15,7 +15,45 @@
 #      ZKPOA_JSON=snarkjs our public.json must equal snarkjs' byte for byte. (proof.json differs: r, s are random
 #      on both sides; "bit-identical proofs" only exists for injected r, s -- BASELINE north_star)
 # Exit code 0 = every step agreed.
+#
+#   tools/crosscheck_snarkjs.sh --zkey-trail <circuit.r1cs> <pot.ptau> [workdir]
+#
+# The phase-2 transcript: is a key made HERE accepted by `snarkjs zkey verify`, and one made by
+# snarkjs by `zkpoa-setup zkey verify`? The .ptau must be prepared for phase 2 and carry section 2. Never run so far:
+#   a. `zkpoa-setup zkey new --transcript`, `zkey contribute --name=...`, `zkey beacon <hex> 10`
+#   b. `snarkjs zkey verify r1cs ptau <that key>`            -> must print "ZKey Ok!"
+#   c. `snarkjs zkey new`, `zkey contribute`, `zkey beacon` -> `zkpoa-setup zkey verify` on snarkjs' key must exit 0
+#   d. both initial keys must carry the same circuit hash (section 10's first 64 bytes: same r1cs, same ptau)
 set -euo pipefail
+
+if [ "${1:-}" = "--zkey-trail" ]; then
+  R1CS=${2:?usage: crosscheck_snarkjs.sh --zkey-trail <circuit.r1cs> <pot.ptau> [workdir]}
+  PTAU=${3:?usage: crosscheck_snarkjs.sh --zkey-trail <circuit.r1cs> <pot.ptau> [workdir]}
+  WORK=${4:-$(mktemp -d)}
+  HERE=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
+  SETUP="$HERE/zk-proof-of-assets_amd/zkpoa-setup"
+  SNARKJS=${SNARKJS:-npx snarkjs}
+  BEACON=0102030405060708090a0b0c0d0e0f101112131415161718191a1b1c1d1e1f
+  mkdir -p "$WORK"
+  echo "== a. a key with a transcript made here"
+  "$SETUP" zkey new "$R1CS" "$PTAU" "$WORK/ours_0.zkey" --transcript
+  "$SETUP" zkey contribute "$WORK/ours_0.zkey" "$WORK/ours_1.zkey" --name="First contributor"
+  "$SETUP" zkey beacon "$WORK/ours_1.zkey" "$WORK/ours_final.zkey" "$BEACON" 10 -n="Final Beacon"
+  "$SETUP" zkey verify "$R1CS" "$PTAU" "$WORK/ours_final.zkey"
+  echo "== b. snarkjs zkey verify on it"
+  $SNARKJS zkey verify "$R1CS" "$PTAU" "$WORK/ours_final.zkey" | tee "$WORK/snarkjs_verify.log"
+  grep -q "ZKey Ok!" "$WORK/snarkjs_verify.log"
+  echo "== c. a key made by snarkjs, verified here"
+  $SNARKJS zkey new "$R1CS" "$PTAU" "$WORK/sj_0.zkey"
+  $SNARKJS zkey contribute "$WORK/sj_0.zkey" "$WORK/sj_1.zkey" --name="First contributor" -e="random text"
+  $SNARKJS zkey beacon "$WORK/sj_1.zkey" "$WORK/sj_final.zkey" "$BEACON" 10 -n="Final Beacon"
+  "$SETUP" zkey verify "$R1CS" "$PTAU" "$WORK/sj_final.zkey"
+  echo "== d. the two initial keys must be the same file (same circuit hash in section 10)"
+  cmp "$WORK/ours_0.zkey" "$WORK/sj_0.zkey"
+  echo "crosscheck OK: snarkjs accepts our trail, we accept snarkjs' trail, the initial keys are identical"
+  echo "(files kept in $WORK)"
+  exit 0
+fi
 
 ZKEY=${1:?usage: crosscheck_snarkjs.sh <zkey> <wtns> [workdir]}
 WTNS=${2:?usage: crosscheck_snarkjs.sh <zkey> <wtns> [workdir]}

@@ -1,7 +1,10 @@
 """Timing of the phase-2 setup arithmetic (zkpoa_setup_accumulate) at the reference's layer-one shape: 2^21
 constraints, 2.08 M signals, 6.3 M coefficients (3 per constraint, as the synthetic prove workload has), with an R1CS-like
 coefficient mix (1, -1, small constants, a few powers of two and full-width values) and a hot signal (the constant one).
-Points are (a + i b) G from the device generator -- for timing only (parity: tests/test_gpu_setup.py)."""
+Points are (a + i b) G from the device generator -- for timing only (parity: tests/test_gpu_setup.py).
+--files: the whole commands on files. --transcript (with --files): the same with the phase-2 transcript (the ptau then
+carries section 2; `zkey new --transcript`, a recorded contribution, a beacon of 2^10 iterations, `zkey verify` of the
+trail), with the PhaseTimer lines of the H differences and the circuit hash (convert, hash)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -61,6 +64,7 @@ print("domain 2^%d: point sections of `snarkjs zkey new` in %.2f s on the device
 
 # ---- the whole command on files: zkpoa-setup <r1cs> <ptau> <zkey> at the same shape (format-valid inputs: the "ceremony"
 # points come from the device generator, the constraints are the synthetic prove workload's: 2 A terms, 1 B term, 1 C term)
+transcript = "--transcript" in sys.argv
 if "--files" in sys.argv:
     import struct, subprocess, tempfile
     d = tempfile.mkdtemp()
@@ -90,7 +94,8 @@ if "--files" in sys.argv:
         t = torch.empty(cnt * 64, dtype=torch.uint8, device="cuda"); ctx.gen_bases_g1_device(seed, seed + 7, 0, cnt, t.data_ptr()); return t.cpu().numpy().tobytes()
     def g2pts(cnt, seed):
         t = torch.empty(cnt * 128, dtype=torch.uint8, device="cuda"); ctx.gen_bases_g2_device(seed, seed + 7, 0, cnt, t.data_ptr()); return t.cpu().numpy().tobytes()
-    secs = [(1, struct.pack("<I", 32) + le32(Q) + struct.pack("<II", k, k)), (2, b""), (3, b""), (4, g1pts(1, 11)),
+    secs = [(1, struct.pack("<I", 32) + le32(Q) + struct.pack("<II", k, k)), (2, g1pts((2 << k) - 1, 18) if transcript else b""),
+            (3, b""), (4, g1pts(1, 11)),
             (5, g1pts(1, 12)), (6, g2pts(1, 13)), (7, struct.pack("<I", 0)), (12, g1pts((4 << k) - 1, 14)),
             (13, g2pts((2 << k) - 1, 15)), (14, g1pts((2 << k) - 1, 16)), (15, g1pts((2 << k) - 1, 17))]
     with open(d + "/pot.ptau", "wb") as f:
@@ -105,13 +110,17 @@ if "--files" in sys.argv:
     g1 = g2 = None; torch.cuda.empty_cache()
     for i in range(2):
         t0 = time.perf_counter()
-        rc = subprocess.run([z.SETUP_BIN, "zkey", "new", d + "/c.r1cs", d + "/pot.ptau", d + "/c_0.zkey"], capture_output=True, text=True, env=dict(os.environ, ZKPOA_VERBOSE="1"))
+        rc = subprocess.run([z.SETUP_BIN, "zkey", "new", d + "/c.r1cs", d + "/pot.ptau", d + "/c_0.zkey"] + (["--transcript"] if transcript else []), capture_output=True, text=True, env=dict(os.environ, ZKPOA_VERBOSE="1"))
         print("zkpoa-setup zkey new, run %d: %.2f s wall, rc=%d, zkey %.2f GB  %s" % (i, time.perf_counter() - t0, rc.returncode, os.path.getsize(d + "/c_0.zkey") / 1e9 if rc.returncode == 0 else 0, rc.stderr.strip().splitlines()[-1] if rc.stderr.strip() else ""))
         if i == 1:
             print("\n".join("    " + l for l in rc.stderr.splitlines() if "zkey new:" in l))
     t0 = time.perf_counter()
     rc = subprocess.run([z.SETUP_BIN, "zkey", "contribute", d + "/c_0.zkey", d + "/c_final.zkey", "--name=First contributor", "-e=random text for entropy"], capture_output=True, text=True, env=dict(os.environ, ZKPOA_VERBOSE="1"))
     print("zkpoa-setup zkey contribute: %.2f s wall, rc=%d  %s" % (time.perf_counter() - t0, rc.returncode, rc.stderr.strip().splitlines()[-1] if rc.stderr.strip() else ""))
+    if transcript:
+        t0 = time.perf_counter()
+        rc = subprocess.run([z.SETUP_BIN, "zkey", "beacon", d + "/c_final.zkey", d + "/c_final.zkey", "0102030405060708090a0b0c0d0e0f101112131415161718191a1b1c1d1e1f", "10", "-n=Final Beacon"], capture_output=True, text=True, env=dict(os.environ, ZKPOA_VERBOSE="1"))
+        print("zkpoa-setup zkey beacon: %.2f s wall, rc=%d  %s" % (time.perf_counter() - t0, rc.returncode, rc.stderr.strip().splitlines()[-1] if rc.stderr.strip() else ""))
     # zkey verify on the same files (the contributed key), beside zkey new
     t0 = time.perf_counter()
     rc = subprocess.run([z.SETUP_BIN, "zkey", "verify", d + "/c.r1cs", d + "/pot.ptau", d + "/c_final.zkey"], capture_output=True, text=True, env=dict(os.environ, ZKPOA_VERBOSE="1"))

@@ -27,7 +27,8 @@ PROVER_ERROR_RUNTIME = 4
 
 # the bits of zkpoa_zkey_verify's result (include/zkpoa_prover.h ZKPOA_ZKEY_*)
 ZKEY_CHECKS = {"HEADER": 0x01, "POINTS": 0x02, "DELTA": 0x04, "COEFFS": 0x08, "A": 0x10, "B1": 0x20, "B2": 0x40,
-               "ICCH": 0x80}
+               "ICCH": 0x80, "CSHASH": 0x100, "CONTRIBUTIONS": 0x200}
+SETUP_TRANSCRIPT = 0x1      # zkpoa_zkey_new_ex: fill in section 10's circuit hash (ZKPOA_SETUP_TRANSCRIPT)
 # the bits of zkpoa_ptau_verify's result (include/zkpoa_prover.h ZKPOA_PTAU_*)
 PTAU_CHECKS = {"POINTS": 0x001, "TAU_G1": 0x002, "TAU_G2": 0x004, "ALPHA": 0x008, "BETA": 0x010,
                "LAGRANGE_TAU_G1": 0x020, "LAGRANGE_TAU_G2": 0x040, "LAGRANGE_ALPHA": 0x080, "LAGRANGE_BETA": 0x100}
@@ -56,6 +57,12 @@ EXPORTS = [
     "zkpoa_poseidon_params", "zkpoa_poseidon2", "zkpoa_poseidon2_device", "zkpoa_merkle_build", "zkpoa_merkle_build_device", "zkpoa_merkle_free",
     "zkpoa_merkle_info", "zkpoa_merkle_root", "zkpoa_merkle_leaves", "zkpoa_merkle_path",
     "zkpoa_msm_table_build", "zkpoa_msm_table_free", "zkpoa_msm_table_info", "zkpoa_msm_table_run_lane",
+    "zkpoa_zkey_new_ex", "zkpoa_zkey_contribute_ex", "zkpoa_zkey_beacon", "zkpoa_zkey_contributions",
+    "zkpoa_hash_form", "zkpoa_h_diff",
+    "zkpoa_blake2b512", "zkpoa_blake2b_new", "zkpoa_blake2b_update", "zkpoa_blake2b_final", "zkpoa_sha256",
+    "zkpoa_chacha_new", "zkpoa_chacha_next_u32", "zkpoa_chacha_next_u64", "zkpoa_chacha_next_bool", "zkpoa_chacha_free",
+    "zkpoa_fq_sqrt", "zkpoa_fq2_sqrt", "zkpoa_fr_from_rng", "zkpoa_g1_from_rng", "zkpoa_g2_from_rng", "zkpoa_hash_to_g2",
+    "zkpoa_beacon_key",
 ]
 
 
@@ -149,6 +156,37 @@ def lib():
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                              ctypes.c_uint64, ctypes.c_void_p]
         L.zkpoa_zkey_new.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
+        L.zkpoa_zkey_new_ex.argtypes = L.zkpoa_zkey_new.argtypes + [ctypes.c_uint32]
+        L.zkpoa_zkey_contribute_ex.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
+                                               ctypes.c_char_p]
+        L.zkpoa_zkey_beacon.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_ulong,
+                                        ctypes.c_uint32, ctypes.c_char_p]
+        L.zkpoa_zkey_contributions.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int),
+                                               ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p, ctypes.c_ulong]
+        L.zkpoa_hash_form.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64,
+                                      ctypes.c_void_p, ctypes.c_char_p]
+        L.zkpoa_h_diff.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
+        L.zkpoa_blake2b512.argtypes = [ctypes.c_char_p, ctypes.c_ulong, ctypes.c_char_p]
+        L.zkpoa_blake2b_new.restype = ctypes.c_void_p
+        L.zkpoa_blake2b_update.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_ulong]
+        L.zkpoa_blake2b_final.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
+        L.zkpoa_sha256.argtypes = [ctypes.c_char_p, ctypes.c_ulong, ctypes.c_char_p]
+        key_t = ctypes.POINTER(ctypes.c_uint32)
+        L.zkpoa_chacha_new.argtypes = [key_t]
+        L.zkpoa_chacha_new.restype = ctypes.c_void_p
+        L.zkpoa_chacha_next_u32.argtypes = [ctypes.c_void_p]
+        L.zkpoa_chacha_next_u32.restype = ctypes.c_uint32
+        L.zkpoa_chacha_next_u64.argtypes = [ctypes.c_void_p]
+        L.zkpoa_chacha_next_u64.restype = ctypes.c_uint64
+        L.zkpoa_chacha_next_bool.argtypes = [ctypes.c_void_p]
+        L.zkpoa_chacha_free.argtypes = [ctypes.c_void_p]
+        L.zkpoa_chacha_free.restype = None
+        L.zkpoa_fq_sqrt.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
+        L.zkpoa_fq2_sqrt.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
+        for f in (L.zkpoa_fr_from_rng, L.zkpoa_g1_from_rng, L.zkpoa_g2_from_rng):
+            f.argtypes = [key_t, ctypes.c_char_p]
+        L.zkpoa_hash_to_g2.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
+        L.zkpoa_beacon_key.argtypes = [ctypes.c_char_p, ctypes.c_ulong, ctypes.c_uint32, key_t]
         L.zkpoa_wtns_check.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p,
                                        ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         L.zkpoa_zkey_contribute.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
@@ -461,6 +499,37 @@ class Context:
         d = None if delta is None else int(delta).to_bytes(32, "little")
         self._check(lib().zkpoa_zkey_contribute(self._h, os.fsencode(zkey_in_path), os.fsencode(zkey_out_path), d),
                     "zkpoa_zkey_contribute")
+
+    def zkey_new_ex(self, r1cs_path, ptau_path, zkey_path, flags=SETUP_TRANSCRIPT):
+        """`zkey new` with section 10's circuit hash filled in (include/zkpoa_prover.h: zkpoa_zkey_new_ex)."""
+        self._check(lib().zkpoa_zkey_new_ex(self._h, os.fsencode(r1cs_path), os.fsencode(ptau_path),
+                                            os.fsencode(zkey_path), flags), "zkpoa_zkey_new_ex")
+
+    def zkey_contribute_ex(self, zkey_in_path, zkey_out_path, delta=None, name=None):
+        """`zkey contribute` on a key with a transcript: the arithmetic and a contribution record."""
+        d = None if delta is None else int(delta).to_bytes(32, "little")
+        self._check(lib().zkpoa_zkey_contribute_ex(self._h, os.fsencode(zkey_in_path), os.fsencode(zkey_out_path), d,
+                                                   None if name is None else name.encode()), "zkpoa_zkey_contribute_ex")
+
+    def zkey_beacon(self, zkey_in_path, zkey_out_path, beacon, num_iterations_exp, name=None):
+        """`snarkjs zkey beacon`: beacon bytes, 2^num_iterations_exp SHA-256 iterations (at most 2^30)."""
+        self._check(lib().zkpoa_zkey_beacon(self._h, os.fsencode(zkey_in_path), os.fsencode(zkey_out_path), bytes(beacon),
+                                            len(beacon), num_iterations_exp, None if name is None else name.encode()),
+                    "zkpoa_zkey_beacon")
+
+    def hash_form(self, group, points, piece_points=0):
+        """Hash form of wire-form points, converted on the device in pieces: -> (bytes, Blake2b-512 digest)."""
+        unit = 64 if group == 1 else 128
+        n = len(points) // unit
+        out, dg = ctypes.create_string_buffer(max(1, n * unit)), ctypes.create_string_buffer(64)
+        self._check(lib().zkpoa_hash_form(self._h, group, bytes(points), n, piece_points, out, dg), "zkpoa_hash_form")
+        return out.raw[:n * unit], dg.raw
+
+    def h_diff(self, points, n):
+        """points[i + n] - points[i], i < n - 1, over 2n - 1 wire-form G1 points (device)."""
+        out = ctypes.create_string_buffer((n - 1) * 64)
+        self._check(lib().zkpoa_h_diff(self._h, bytes(points), n, out), "zkpoa_h_diff")
+        return out.raw
 
     def load_zkey_device_shard(self, n_vars, n_public, log_domain, rank, world, split, d_A, d_B1, d_B2, d_C, d_H,
                                d_coefs, n_coefs, header_points, block_log=0):
@@ -846,6 +915,104 @@ def g2_mul(point, k):
     out = ctypes.create_string_buffer(128)
     lib().zkpoa_g2_mul(point, int(k).to_bytes(32, "little"), out)
     return out.raw
+
+
+def zkey_contributions(zkey_path):
+    """(the key carries a transcript, [(type, name), ...]) of a .zkey's section 10 (host only)."""
+    has, cnt, text = ctypes.c_int(0), ctypes.c_uint32(0), ctypes.create_string_buffer(1 << 16)
+    if lib().zkpoa_zkey_contributions(os.fsencode(zkey_path), ctypes.byref(has), ctypes.byref(cnt), text, len(text)):
+        raise ZkpoaError("zkpoa_zkey_contributions failed")
+    lines = text.value.decode().split("\n")[:cnt.value]
+    return bool(has.value), [tuple(l.split(" ", 1)) for l in lines]
+
+
+# ---- host-only primitives of the phase-2 transcript (csrc/phase2.hpp), for the tests
+def blake2b512(data):
+    out = ctypes.create_string_buffer(64)
+    lib().zkpoa_blake2b512(bytes(data), len(data), out)
+    return out.raw
+
+
+def blake2b512_stream(pieces):
+    st, out = lib().zkpoa_blake2b_new(), ctypes.create_string_buffer(64)
+    for p in pieces:
+        lib().zkpoa_blake2b_update(st, bytes(p), len(p))
+    lib().zkpoa_blake2b_final(st, out)
+    return out.raw
+
+
+def sha256(data):
+    out = ctypes.create_string_buffer(32)
+    lib().zkpoa_sha256(bytes(data), len(data), out)
+    return out.raw
+
+
+def _key(words):
+    return (ctypes.c_uint32 * 8)(*words)
+
+
+class ChaCha:
+    """ffjavascript's ChaCha generator (key: eight u32 words)."""
+
+    def __init__(self, key):
+        self._h = lib().zkpoa_chacha_new(_key(key))
+
+    def next_u32(self):
+        return lib().zkpoa_chacha_next_u32(self._h)
+
+    def next_u64(self):
+        return lib().zkpoa_chacha_next_u64(self._h)
+
+    def next_bool(self):
+        return bool(lib().zkpoa_chacha_next_bool(self._h))
+
+    def __del__(self):
+        if self._h:
+            lib().zkpoa_chacha_free(self._h)
+            self._h = None
+
+
+def fq_sqrt(a):
+    out = ctypes.create_string_buffer(32)
+    return int.from_bytes(out.raw, "little") if lib().zkpoa_fq_sqrt(int(a).to_bytes(32, "little"), out) else None
+
+
+def fq2_sqrt(a):
+    out = ctypes.create_string_buffer(64)
+    if not lib().zkpoa_fq2_sqrt(int(a[0]).to_bytes(32, "little") + int(a[1]).to_bytes(32, "little"), out):
+        return None
+    return (int.from_bytes(out.raw[:32], "little"), int.from_bytes(out.raw[32:], "little"))
+
+
+def fr_from_rng(key):
+    out = ctypes.create_string_buffer(32)
+    lib().zkpoa_fr_from_rng(_key(key), out)
+    return int.from_bytes(out.raw, "little")
+
+
+def g1_from_rng(key):
+    out = ctypes.create_string_buffer(64)
+    lib().zkpoa_g1_from_rng(_key(key), out)
+    return out.raw
+
+
+def g2_from_rng(key):
+    out = ctypes.create_string_buffer(128)
+    lib().zkpoa_g2_from_rng(_key(key), out)
+    return out.raw
+
+
+def hash_to_g2(hash64):
+    out = ctypes.create_string_buffer(128)
+    lib().zkpoa_hash_to_g2(bytes(hash64), out)
+    return out.raw
+
+
+def beacon_key(beacon, num_iterations_exp):
+    key = (ctypes.c_uint32 * 8)()
+    if lib().zkpoa_beacon_key(bytes(beacon), len(beacon), num_iterations_exp, key):
+        raise ZkpoaError("zkpoa_beacon_key: numIterationsExp above 30")
+    return list(key)
 
 
 def groth16_prove(zkey_path, wtns_path, proof_path, public_path):

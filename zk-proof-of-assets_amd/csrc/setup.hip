@@ -22,6 +22,7 @@
 #include "msm.hip.h"
 #include "hooks.hip.h"
 #include "pairing.hpp"
+#include "phase2_dev.hip.h"
 #include "setup_common.hip.h"
 #include "zkpoa_internal.hpp"
 
@@ -422,19 +423,109 @@ struct Entries {   // one zkpoa_setup_accumulate call; filled in place by severa
   }
 };
 
+// keep: the device copy of the result outlives the call (the circuit hash reads it there)
 template <class F>
 UVec<uint8_t> run_accumulate(zkpoa_context* ctx, const DevBuf& points, uint64_t n_points, const Entries& e,
-                                    uint64_t n_signals) {
+                                    uint64_t n_signals, std::unique_ptr<DevBuf>* keep = nullptr) {
   constexpr size_t A = MsmSizes<F>::kAffine;
   const uint64_t nnz = e.sig.size();
-  DevBuf coef(nnz * 32), pidx(nnz * 4), sig(nnz * 4), out(n_signals * A);
+  DevBuf coef(nnz * 32), pidx(nnz * 4), sig(nnz * 4);
+  std::unique_ptr<DevBuf> out(new DevBuf(n_signals * A));
   coef.up(e.coef.data(), nnz * 32);
   pidx.up(e.pidx.data(), nnz * 4);
   sig.up(e.sig.data(), nnz * 4);
-  setup_accumulate<F>(ctx, points.p, n_points, coef.p, (const uint32_t*)pidx.p, (const uint32_t*)sig.p, nnz, n_signals, out.p);
+  setup_accumulate<F>(ctx, points.p, n_points, coef.p, (const uint32_t*)pidx.p, (const uint32_t*)sig.p, nnz, n_signals, out->p);
   UVec<uint8_t> host(n_signals * A);
-  if (!host.empty()) ZK_HIP(hipMemcpy(host.data(), out.p, host.size(), hipMemcpyDeviceToHost));
+  if (!host.empty()) ZK_HIP(hipMemcpy(host.data(), out->p, host.size(), hipMemcpyDeviceToHost));
+  if (keep) *keep = std::move(out);
   return host;
+}
+
+// entries of the three accumulations of `zkey new` (+ the nPublic + 1 rows `1 * signal_i` that bind the public inputs);
+// eA / eB may be null (`zkey verify` recomputes the initial IC / C only)
+void build_entries(const R1cs& r, uint64_t n, Entries* eA, Entries* eB, Entries& eK) {
+  const uint64_t nA = r.A.size(), nB = r.B.size(), nCt = r.C.size(), nPub1 = (uint64_t)r.nPublic + 1;
+  if (eA) eA->alloc(nA + nPub1);
+  if (eB) eB->alloc(nB);
+  eK.alloc(nA + nB + nCt + nPub1);
+  parallel_ranges(nA, 1u << 16, [&](unsigned, uint64_t lo, uint64_t hi) {
+    for (uint64_t i = lo; i < hi; i++) {
+      if (eA) eA->set(i, r.A[i], 0);
+      eK.set(i, r.A[i], 0);                                      // K: A over beta*L  (points [0, n))
+    }
+  });
+  parallel_ranges(nB, 1u << 16, [&](unsigned, uint64_t lo, uint64_t hi) {
+    for (uint64_t i = lo; i < hi; i++) {
+      if (eB) eB->set(i, r.B[i], 0);
+      eK.set(nA + i, r.B[i], (uint32_t)n);                       //    B over alpha*L ([n, 2n))
+    }
+  });
+  parallel_ranges(nCt, 1u << 16, [&](unsigned, uint64_t lo, uint64_t hi) {
+    for (uint64_t i = lo; i < hi; i++) eK.set(nA + nB + i, r.C[i], (uint32_t)(2 * n));   //    C over L       ([2n, 3n))
+  });
+  for (uint32_t i = 0; i <= r.nPublic; i++) {
+    if (eA) eA->set_one(nA + i, r.nConstraints + i, i);
+    eK.set_one(nA + nB + nCt + i, r.nConstraints + i, i);
+  }
+}
+
+// the initial IC | C of a key (m points: sections 3 and 8 before any contribution) on the device, and on the host
+UVec<uint8_t> accumulate_k(zkpoa_context* ctx, const PtauRanges& pt, uint64_t n, const Entries& eK, uint64_t m,
+                           std::unique_ptr<DevBuf>* keep) {
+  DevBuf dK(3 * n * 64);
+  dK.up(pt.bL.data(), n * 64, 0);
+  dK.up(pt.aL.data(), n * 64, n * 64);
+  dK.up(pt.L1.data(), n * 64, 2 * n * 64);
+  dev_check_coords(ctx, dK.p, 4 * n, "ptau alpha*tau*G1 / beta*tau*G1 (Lagrange)");
+  return run_accumulate<Fq>(ctx, dK, 3 * n, eK, m, keep);
+}
+
+// ---- the circuit hash (DESIGN.md "Phase-2 transcript"): Blake2b-512 over the initial key's points in hash form ----------
+struct CsHashPoints {   // device pointers, wire form
+  const void *IC, *C, *A, *B1, *B2;
+  uint64_t l, m, n;
+  const uint8_t *alpha1, *beta1, *beta2;   // host, wire form
+};
+void circuit_hash(zkpoa_context* ctx, const char* ptau_path, const CsHashPoints& k, PhaseTimer& phase, uint8_t out[64]) {
+  namespace p2 = zkpoa::phase2;
+  // ptau section 2: tau^i G1, i < 2n - 1 (the powers form; section 9 holds the Lagrange-odd points instead)
+  DevBuf dT(2 * k.n * 64), dH(k.n * 64);
+  {
+    MappedFile fp(ptau_path);
+    auto ps = bin_sections(fp, "ptau", 1, "ptau");
+    if (!ps.count(2) || ps[2].len < (2 * k.n - 1) * 64)
+      throw SetupError("ptau: section 2 (tau^i G1) is missing or too short for the transcript's H points");
+    UVec<uint8_t> T((2 * k.n - 1) * 64);
+    pread_all(fp.fd, T.data(), T.size(), ps[2].off, "tau^i G1");
+    dT.up(T.data(), T.size());
+    dev_check_coords(ctx, dT.p, 2 * (2 * k.n - 1), "ptau tau^i G1");
+  }
+  h_diff(ctx, dT.p, k.n, dH.p);
+  phase("H-diff (ptau section 2 read, device)");
+  p2::Blake2b h;
+  uint8_t g1[64], g2[128];
+  h_affine_to_bytes<HFq>(host_generator<HFq>(), g1);
+  h_affine_to_bytes<HFq2>(host_generator<HFq2>(), g2);
+  p2::hash_g1_wire(h, k.alpha1);
+  p2::hash_g1_wire(h, k.beta1);
+  p2::hash_g2_wire(h, k.beta2);
+  p2::hash_g2_wire(h, g2);   // gamma2, delta1, delta2 of the initial key: the generators
+  p2::hash_g1_wire(h, g1);
+  p2::hash_g2_wire(h, g2);
+  HashStream hs(ctx, h, 0);
+  hs.points(k.IC, k.l + 1, 1, true);
+  hs.points(dH.p, k.n - 1, 1, true);
+  hs.points(k.C, k.m - k.l - 1, 1, true);
+  hs.points(k.A, k.m, 1, true);
+  hs.points(k.B1, k.m, 1, true);
+  hs.points(k.B2, k.m, 2, true);
+  h.final(out);
+  if (phase.verbose) {
+    fprintf(stderr, "zkpoa: %s: %-*s %8.1f ms\n", phase.command, phase.width, "circuit hash: convert (host waits for the device)", hs.convert_ms);
+    fprintf(stderr, "zkpoa: %s: %-*s %8.1f ms  (%.3f GB, %.2f GB/s)\n", phase.command, phase.width, "circuit hash: hash (Blake2b, one host thread)",
+            hs.hash_ms, hs.bytes / 1e9, hs.hash_ms > 0 ? hs.bytes / 1e6 / hs.hash_ms : 0.0);
+  }
+  phase("circuit hash");
 }
 
 // A .zkey whose ten section lengths are known before their content: the file is sized, magic and section table are
@@ -467,7 +558,8 @@ struct ZkeyWriter {
 void put32(std::vector<uint8_t>& v, uint32_t x) { v.insert(v.end(), (uint8_t*)&x, (uint8_t*)&x + 4); }
 void put64(std::vector<uint8_t>& v, uint64_t x) { v.insert(v.end(), (uint8_t*)&x, (uint8_t*)&x + 8); }
 
-void zkey_new(zkpoa_context* ctx, const char* r1cs_path, const char* ptau_path, const char* zkey_path) {
+void zkey_new(zkpoa_context* ctx, const char* r1cs_path, const char* ptau_path, const char* zkey_path, uint32_t flags) {
+  const bool transcript = (flags & ZKPOA_SETUP_TRANSCRIPT) != 0;
   PhaseTimer phase("zkey new", 38);
   MappedFile fr(r1cs_path);
   const R1cs r = parse_r1cs(fr);
@@ -476,35 +568,12 @@ void zkey_new(zkpoa_context* ctx, const char* r1cs_path, const char* ptau_path, 
   const uint64_t n = 1ull << cp;
 
   const PtauRanges pt = read_ptau_ranges(ptau_path, cp);
-  const UVec<uint8_t>&L1 = pt.L1, &L2 = pt.L2, &aL = pt.aL, &bL = pt.bL, &Hs = pt.Hs;
+  const UVec<uint8_t>&L1 = pt.L1, &L2 = pt.L2, &Hs = pt.Hs;
   const uint8_t *alpha1 = pt.alpha1, *beta1 = pt.beta1, *beta2 = pt.beta2;
   phase("ptau ranges read");
 
-  // entries of the three accumulations (+ the nPublic + 1 rows `1 * signal_i` that bind the public inputs)
   Entries eA, eB, eK;
-  const uint64_t nA = r.A.size(), nB = r.B.size(), nCt = r.C.size(), nPub1 = (uint64_t)r.nPublic + 1;
-  eA.alloc(nA + nPub1);
-  eB.alloc(nB);
-  eK.alloc(nA + nB + nCt + nPub1);
-  parallel_ranges(nA, 1u << 16, [&](unsigned, uint64_t lo, uint64_t hi) {
-    for (uint64_t i = lo; i < hi; i++) {
-      eA.set(i, r.A[i], 0);
-      eK.set(i, r.A[i], 0);                                      // K: A over beta*L  (points [0, n))
-    }
-  });
-  parallel_ranges(nB, 1u << 16, [&](unsigned, uint64_t lo, uint64_t hi) {
-    for (uint64_t i = lo; i < hi; i++) {
-      eB.set(i, r.B[i], 0);
-      eK.set(nA + i, r.B[i], (uint32_t)n);                       //    B over alpha*L ([n, 2n))
-    }
-  });
-  parallel_ranges(nCt, 1u << 16, [&](unsigned, uint64_t lo, uint64_t hi) {
-    for (uint64_t i = lo; i < hi; i++) eK.set(nA + nB + i, r.C[i], (uint32_t)(2 * n));   //    C over L       ([2n, 3n))
-  });
-  for (uint32_t i = 0; i <= r.nPublic; i++) {
-    eA.set_one(nA + i, r.nConstraints + i, i);
-    eK.set_one(nA + nB + nCt + i, r.nConstraints + i, i);
-  }
+  build_entries(r, n, &eA, &eB, eK);
   phase("entry lists built");
   const uint64_t m = r.nWires;
   // ---- the file: sections 1-10 in the order snarkjs numbers them. Every length follows from the header and the term
@@ -542,7 +611,7 @@ void zkey_new(zkpoa_context* ctx, const char* r1cs_path, const char* ptau_path, 
       s2.insert(s2.end(), g1, g1 + 64);    // delta1
       s2.insert(s2.end(), g2, g2 + 128);   // delta2
       put_section(2, s2.data(), s2.size());
-      put_section(10, s10.data(), s10.size());
+      if (!transcript) put_section(10, s10.data(), s10.size());
       // coefficients: A and B terms per constraint, then the public rows; values scaled by R^2
       UVec<uint8_t> s4(4 + nCoefs * 44);
       {
@@ -612,33 +681,33 @@ void zkey_new(zkpoa_context* ctx, const char* r1cs_path, const char* ptau_path, 
     }
   } joiner{host_sections, writers};
   UVec<uint8_t> secA, secB1, secB2, secK;   // (alive until every writer has been joined)
+  std::unique_ptr<DevBuf> dA, dB1, dB2, dKout;   // transcript: the results stay on the device for the circuit hash
   {
     DevBuf dL1(n * 64);
     dL1.up(L1.data(), L1.size());
     dev_check_coords(ctx, dL1.p, 2 * n, "ptau tau*G1 (Lagrange)");
-    secA = run_accumulate<Fq>(ctx, dL1, n, eA, m);
+    secA = run_accumulate<Fq>(ctx, dL1, n, eA, m, transcript ? &dA : nullptr);
     write_async(5, secA.data(), secA.size());
-    secB1 = run_accumulate<Fq>(ctx, dL1, n, eB, m);
+    secB1 = run_accumulate<Fq>(ctx, dL1, n, eB, m, transcript ? &dB1 : nullptr);
     write_async(6, secB1.data(), secB1.size());
   }
   {
     DevBuf dL2(n * 128);
     dL2.up(L2.data(), L2.size());
     dev_check_coords(ctx, dL2.p, 4 * n, "ptau tau*G2 (Lagrange)");
-    secB2 = run_accumulate<Fq2>(ctx, dL2, n, eB, m);
+    secB2 = run_accumulate<Fq2>(ctx, dL2, n, eB, m, transcript ? &dB2 : nullptr);
     write_async(7, secB2.data(), secB2.size());
   }
-  {
-    DevBuf dK(3 * n * 64);
-    dK.up(bL.data(), n * 64, 0);
-    dK.up(aL.data(), n * 64, n * 64);
-    dK.up(L1.data(), n * 64, 2 * n * 64);
-    dev_check_coords(ctx, dK.p, 4 * n, "ptau alpha*tau*G1 / beta*tau*G1 (Lagrange)");
-    secK = run_accumulate<Fq>(ctx, dK, 3 * n, eK, m);
-  }
+  secK = accumulate_k(ctx, pt, n, eK, m, transcript ? &dKout : nullptr);
   phase("point sections (upload, device, download)");
   put_section(3, secK.data(), icb);
   put_section(8, secK.data() + icb, secK.size() - icb);
+  if (transcript) {
+    uint8_t s10[68] = {0};
+    const CsHashPoints k{dKout->p, (const char*)dKout->p + icb, dA->p, dB1->p, dB2->p, r.nPublic, m, n, alpha1, beta1, beta2};
+    circuit_hash(ctx, ptau_path, k, phase, s10);
+    put_section(10, s10, sizeof s10);
+  }
   host_sections.join();
   for (auto& x : writers) x.join();
   if (host_err) std::rethrow_exception(host_err);
@@ -692,7 +761,54 @@ uint64_t wtns_check(zkpoa_context* ctx, const char* r1cs_path, const char* wtns_
 }
 
 // ---- the arithmetic of `snarkjs zkey contribute` (g16_setup.sh:262-266): delta <- d * delta, C and H <- C, H / d ---------
-void zkey_contribute(zkpoa_context* ctx, const char* in_path, const char* out_path, const uint8_t* delta_le) {
+// what `zkey contribute` / `zkey beacon` add to section 10 when the input carries a transcript
+struct Phase2Append {
+  uint32_t type = 0;   // 0 contribution, 1 beacon
+  std::string name;
+  std::vector<uint8_t> beacon;
+  uint32_t num_iterations_exp = 0;
+};
+void random_scalar(uint8_t d[32]) {   // uniform on [1, r): 254 random bits, rejected while >= r or zero
+  for (;;) {
+    urandom(d, 32);
+    d[31] &= 0x3f;
+    uint64_t v[4];
+    memcpy(v, d, 32);
+    if (!HFr::geq_p(v) && (v[0] | v[1] | v[2] | v[3])) break;
+  }
+}
+// ZKPOA_PHASE2_S (tests / reproducible records only): the s of g1_s = s * G1, decimal or 0x... hex, in [1, r)
+bool env_scalar(const char* name, uint8_t out[32]) {
+  const char* e = getenv(name);
+  if (!e) return false;
+  memset(out, 0, 32);
+  const bool hex = e[0] == '0' && (e[1] == 'x' || e[1] == 'X');
+  bool ok = *(hex ? e + 2 : e) != 0;
+  for (const char* p = hex ? e + 2 : e; *p && ok; p++) {
+    unsigned d = 99;
+    if (*p >= '0' && *p <= '9') d = (unsigned)(*p - '0');
+    else if (hex && (*p | 32) >= 'a' && (*p | 32) <= 'f') d = (unsigned)((*p | 32) - 'a' + 10);
+    if (d == 99) ok = false;
+    unsigned carry = d;
+    for (int i = 0; i < 32; i++) {
+      const unsigned v = out[i] * (hex ? 16u : 10u) + carry;
+      out[i] = (uint8_t)v;
+      carry = v >> 8;
+    }
+    if (carry) ok = false;
+  }
+  uint64_t v[4];
+  memcpy(v, out, 32);
+  if (!ok || HFr::geq_p(v) || !(v[0] | v[1] | v[2] | v[3])) throw SetupError(std::string(name) + " is not a number in [1, r)");
+  fprintf(stderr, "zkpoa: WARNING: a secret of the contribution record taken from %s -- for tests only\n", name);
+  return true;
+}
+
+// rec: null = the arithmetic alone, section 10 copied as it is (zkpoa_zkey_contribute); else the input must carry a
+// transcript, and a record is appended. A beacon's delta comes from its generator (delta_le is not read).
+void zkey_contribute(zkpoa_context* ctx, const char* in_path, const char* out_path, const uint8_t* delta_le,
+                     const Phase2Append* rec) {
+  namespace p2 = zkpoa::phase2;
   MappedFile fi(in_path);
   auto secs = bin_sections(fi, "zkey", 1, "zkey");
   for (uint32_t t = 1; t <= 10; t++)
@@ -705,15 +821,28 @@ void zkey_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
   const uint64_t nVars = zh.nVars, nPublic = zh.nPublic, domain = zh.domain;
   if (nPublic + 1 > nVars || secs[8].len != (nVars - nPublic - 1) * 64 || secs[9].len != domain * 64)
     throw SetupError("zkey: C or H section has the wrong size");
-  uint8_t d[32];
-  if (delta_le) memcpy(d, delta_le, 32);
-  else {   // uniform on [1, r): 254 random bits, rejected while >= r or zero
-    for (;;) {
-      urandom(d, 32);
-      d[31] &= 0x3f;
-      uint64_t v[4];
-      memcpy(v, d, 32);
-      if (!HFr::geq_p(v) && (v[0] | v[1] | v[2] | v[3])) break;
+  p2::Transcript tr;
+  uint8_t d[32], g1_s[64];
+  if (rec) {
+    tr = p2::parse_section10(fi.p + secs[10].off, secs[10].len);
+    if (!tr.present()) throw SetupError("zkey: the key carries no transcript (circuit hash is zero): make it with `zkey new --transcript`");
+    if (rec->name.size() > 255 || rec->beacon.size() > 255) throw SetupError("contribution name or beacon longer than 255 bytes");
+  }
+  if (rec && rec->type == 1) {   // d, then g1_s, from the beacon's generator: any verifier recomputes both
+    uint32_t key[8];
+    p2::beacon_key(rec->beacon.data(), rec->beacon.size(), rec->num_iterations_exp, key);
+    p2::ChaCha rng(key);
+    p2::fr_from_rng(rng, d);
+    h_affine_to_bytes<HFq>(p2::g1_from_rng(rng), g1_s);
+  } else {
+    if (delta_le) memcpy(d, delta_le, 32);
+    else random_scalar(d);
+    if (rec) {
+      uint8_t sb[32];
+      if (!env_scalar("ZKPOA_PHASE2_S", sb)) random_scalar(sb);
+      uint64_t sv[4];
+      memcpy(sv, sb, 32);
+      h_affine_to_bytes<HFq>(h_to_affine(h_mul(XYZZ<HFq>::from_affine(host_generator<HFq>()), sv)), g1_s);
     }
   }
   uint64_t dv[4];
@@ -731,6 +860,21 @@ void zkey_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
     h_affine_to_bytes<HFq>(h_to_affine(h_mul(XYZZ<HFq>::from_affine(d1), dv)), &s2[kDelta1]);
     h_affine_to_bytes<HFq2>(h_to_affine(h_mul(XYZZ<HFq2>::from_affine(d2), dv)), &s2[kDelta2]);
   }
+  std::vector<uint8_t> s10(fi.p + secs[10].off, fi.p + secs[10].off + secs[10].len);
+  if (rec) {
+    p2::Record nr;
+    nr.type = rec->type;
+    nr.name = rec->name;
+    nr.beacon = rec->beacon;
+    nr.num_iterations_exp = rec->num_iterations_exp;
+    memcpy(nr.delta_after, &s2[kDelta1], 64);
+    memcpy(nr.g1_s, g1_s, 64);
+    h_affine_to_bytes<HFq>(h_to_affine(h_mul(XYZZ<HFq>::from_affine(h_affine_from_bytes<HFq>(g1_s)), dv)), nr.g1_sx);
+    p2::transcript_hash(tr, tr.records.size(), nr.g1_s, nr.g1_sx, nr.transcript);
+    h_affine_to_bytes<HFq2>(h_to_affine(h_mul(XYZZ<HFq2>::from_affine(p2::hash_to_g2(nr.transcript)), dv)), nr.g2_spx);
+    tr.records.push_back(nr);
+    s10 = p2::write_section10(tr);
+  }
   auto scaled = [&](const Sec& sc) {
     UVec<uint8_t> out(sc.len);
     if (sc.len) {
@@ -746,13 +890,15 @@ void zkey_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
   // it from a side thread while the device scales C and H
   uint64_t sec_len[11] = {0};
   for (uint32_t t = 1; t <= 10; t++) sec_len[t] = secs[t].len;
+  sec_len[10] = s10.size();
   ZkeyWriter out(out_path, sec_len);   // temporary name + rename: in_path == out_path is fine (the mapping keeps the old inode)
   auto put_section = [&](uint32_t t, const uint8_t* p) { out.put(t, p, sec_len[t]); };
   std::exception_ptr copy_err;
   std::thread copier([&] {
     try {
       put_section(2, s2.data());
-      for (uint32_t t : {1u, 3u, 4u, 5u, 6u, 7u, 10u}) put_section(t, fi.p + secs[t].off);
+      put_section(10, s10.data());
+      for (uint32_t t : {1u, 3u, 4u, 5u, 6u, 7u}) put_section(t, fi.p + secs[t].off);
     } catch (...) {
       copy_err = std::current_exception();
     }
@@ -778,6 +924,113 @@ void zkey_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
 
 }  // namespace
 
+// ---- `zkey verify` on a key that carries a transcript: the circuit hash and the contribution records ---------------------
+// CSHASH: section 10's circuit hash against the one recomputed from the r1cs and the ptau (the initial IC | C through the
+// accumulate path of `zkey new`; the key on disk holds C / delta) and the key's own A, B1, B2 (which `zkey verify` has
+// already held to the r1cs and the ptau). CONTRIBUTIONS: every record against the RECOMPUTED circuit hash, so a damaged
+// stored hash fails CSHASH alone. The caller has checked the key's shape and the range of its coordinates.
+uint32_t zkpoa::phase2_verify(zkpoa_context* ctx, const char* r1cs_path, const char* ptau_path, const char* zkey_path) {
+  namespace p2 = zkpoa::phase2;
+  PhaseTimer phase("zkey verify", 38);
+  MappedFile fk(zkey_path);
+  auto ks = bin_sections(fk, "zkey", 1, "zkey");
+  p2::Transcript tr;
+  try {
+    tr = p2::parse_section10(fk.p + ks[10].off, ks[10].len);
+  } catch (const std::runtime_error& e) {
+    throw SetupError(e.what());
+  }
+  uint32_t failed = 0;
+  const uint8_t* hp = fk.p + ks[2].off;
+  uint8_t cs[64];
+  {
+    MappedFile fr(r1cs_path);
+    const R1cs r = parse_r1cs(fr);
+    const uint32_t cp = domain_log2(r);
+    const uint64_t n = 1ull << cp, m = r.nWires, l = r.nPublic;
+    const PtauRanges pt = read_ptau_ranges(ptau_path, cp);
+    Entries eK;
+    build_entries(r, n, nullptr, nullptr, eK);
+    std::unique_ptr<DevBuf> dK;
+    (void)accumulate_k(ctx, pt, n, eK, m, &dK);
+    phase("initial IC | C recomputed");
+    DevBuf dIC((l + 1) * 64), dA(m * 64), dB1(m * 64), dB2(m * 128);
+    dIC.up(fk.p + ks[3].off, (l + 1) * 64);
+    dA.up(fk.p + ks[5].off, m * 64);
+    dB1.up(fk.p + ks[6].off, m * 64);
+    dB2.up(fk.p + ks[7].off, m * 128);
+    const CsHashPoints k{dIC.p, (const char*)dK->p + (l + 1) * 64, dA.p, dB1.p, dB2.p, l, m, n, hp + kAlpha1, hp + kBeta1, hp + kBeta2};
+    circuit_hash(ctx, ptau_path, k, phase, cs);
+  }
+  if (memcmp(cs, tr.cs_hash, 64)) failed |= ZKPOA_ZKEY_CSHASH;
+  memcpy(tr.cs_hash, cs, 64);
+  // the records: points of their groups, transcript hashes, the two pairing equations, the delta chain, beacons recomputed
+  bool ok = true;
+  pairing::G1 prev = host_generator<HFq>();
+  static const uint64_t kR[4] = {HFrParams::P[0], HFrParams::P[1], HFrParams::P[2], HFrParams::P[3]};
+  for (size_t k = 0; k < tr.records.size() && ok; k++) {
+    const p2::Record& rc = tr.records[k];
+    host_check_coords(rc.delta_after, 2 * 3 + 4, "zkey section 10 points");
+    const pairing::G1 da = h_affine_from_bytes<HFq>(rc.delta_after), s = h_affine_from_bytes<HFq>(rc.g1_s),
+                      sx = h_affine_from_bytes<HFq>(rc.g1_sx);
+    const pairing::G2 spx = h_affine_from_bytes<HFq2>(rc.g2_spx);
+    if (da.is_inf() || s.is_inf() || sx.is_inf() || spx.is_inf() || !pairing::g1_on_curve(da) || !pairing::g1_on_curve(s) ||
+        !pairing::g1_on_curve(sx) || !pairing::g2_on_curve(spx) || !h_mul(XYZZ<HFq2>::from_affine(spx), kR).is_inf()) {
+      ok = false;
+      break;
+    }
+    uint8_t th[64];
+    p2::transcript_hash(tr, k, rc.g1_s, rc.g1_sx, th);
+    if (memcmp(th, rc.transcript, 64)) ok = false;
+    const pairing::G2 sp = p2::hash_to_g2(th);
+    if (ok && !pairing::pair_eq(s, spx, sx, sp)) ok = false;      // the same d in g1_sx and g2_spx
+    if (ok && !pairing::pair_eq(da, sp, prev, spx)) ok = false;   // deltaAfter_k = d * deltaAfter_{k-1}
+    if (ok && rc.type == 1) {
+      if (rc.num_iterations_exp > p2::kMaxBeaconExp) ok = false;
+      else {
+        uint32_t key[8];
+        uint8_t d[32], want[64];
+        p2::beacon_key(rc.beacon.data(), rc.beacon.size(), rc.num_iterations_exp, key);
+        p2::ChaCha rng(key);
+        p2::fr_from_rng(rng, d);
+        const pairing::G1 ws = p2::g1_from_rng(rng);
+        h_affine_to_bytes<HFq>(ws, want);
+        if (memcmp(want, rc.g1_s, 64)) ok = false;
+        uint64_t dv[4];
+        memcpy(dv, d, 32);
+        h_affine_to_bytes<HFq>(h_to_affine(h_mul(XYZZ<HFq>::from_affine(ws), dv)), want);
+        if (memcmp(want, rc.g1_sx, 64)) ok = false;
+      }
+    }
+    prev = da;
+  }
+  uint8_t last[64];
+  h_affine_to_bytes<HFq>(prev, last);
+  if (!ok || memcmp(last, hp + kDelta1, 64)) failed |= ZKPOA_ZKEY_CONTRIBUTIONS;
+  phase("contribution records");
+  return failed;
+}
+
+// host only: does the key carry a transcript, how many records, and one line "<type> <name>" per record
+extern "C" int zkpoa_zkey_contributions(const char* zkey_path, int* has_transcript, uint32_t* count, char* text,
+                                        unsigned long cap) {
+  try {
+    if (!zkey_path || !has_transcript || !count) return PROVER_ERROR;
+    MappedFile fk(zkey_path);
+    auto ks = bin_sections(fk, "zkey", 1, "zkey");
+    if (!ks.count(10)) return PROVER_ERROR;
+    const zkpoa::phase2::Transcript tr = zkpoa::phase2::parse_section10(fk.p + ks[10].off, ks[10].len);
+    *has_transcript = tr.present() ? 1 : 0;
+    *count = (uint32_t)tr.records.size();
+    std::string out;
+    for (const auto& r : tr.records) out += std::string(r.type == 1 ? "beacon " : "contribution ") + r.name + "\n";
+    if (text && cap) zkpoa::set_err(text, cap, out);
+    return PROVER_OK;
+  } catch (const std::exception&) {
+    return PROVER_ERROR;
+  }
+}
+
 extern "C" int zkpoa_wtns_check(zkpoa_context* ctx, const char* r1cs_path, const char* wtns_path, uint64_t* violated,
                                 uint64_t* first_violated) {
   ZK_API_BEGIN(ctx)
@@ -790,7 +1043,63 @@ extern "C" int zkpoa_zkey_contribute(zkpoa_context* ctx, const char* zkey_in_pat
                                      const uint8_t* delta_le) {
   ZK_API_BEGIN(ctx)
   if (!zkey_in_path || !zkey_out_path) throw SetupError("zkey contribute: null path");
-  zkey_contribute(ctx, zkey_in_path, zkey_out_path, delta_le);
+  zkey_contribute(ctx, zkey_in_path, zkey_out_path, delta_le, nullptr);
+  ZK_API_END(ctx)
+}
+
+extern "C" int zkpoa_zkey_contribute_ex(zkpoa_context* ctx, const char* zkey_in_path, const char* zkey_out_path,
+                                        const uint8_t* delta_le, const char* name) {
+  ZK_API_BEGIN(ctx)
+  if (!zkey_in_path || !zkey_out_path) throw SetupError("zkey contribute: null path");
+  Phase2Append rec;
+  rec.name = name ? name : "";
+  zkey_contribute(ctx, zkey_in_path, zkey_out_path, delta_le, &rec);
+  ZK_API_END(ctx)
+}
+
+extern "C" int zkpoa_zkey_beacon(zkpoa_context* ctx, const char* zkey_in_path, const char* zkey_out_path,
+                                 const uint8_t* beacon, unsigned long beacon_len, uint32_t num_iterations_exp,
+                                 const char* name) {
+  ZK_API_BEGIN(ctx)
+  if (!zkey_in_path || !zkey_out_path || (!beacon && beacon_len)) throw SetupError("zkey beacon: null argument");
+  if (num_iterations_exp > zkpoa::phase2::kMaxBeaconExp) throw SetupError("zkey beacon: numIterationsExp above 30 is refused (2^30 hashes take minutes; more would not finish)");
+  Phase2Append rec;
+  rec.type = 1;
+  rec.name = name ? name : "";
+  rec.beacon.assign(beacon, beacon + beacon_len);
+  rec.num_iterations_exp = num_iterations_exp;
+  zkey_contribute(ctx, zkey_in_path, zkey_out_path, nullptr, &rec);
+  ZK_API_END(ctx)
+}
+
+// test hooks of the transcript's device work: the hash form of n points of group 1 / 2 (host wire form) streamed in
+// pieces of piece_points, its Blake2b-512 digest, and optionally the bytes; T[i + n] - T[i] over 2n - 1 points
+extern "C" int zkpoa_hash_form(zkpoa_context* ctx, int group, const void* points, uint64_t n, uint64_t piece_points,
+                               void* out_bytes, uint8_t digest[64]) {
+  ZK_API_BEGIN(ctx)
+  if ((group != 1 && group != 2) || (n && !points) || !digest) throw SetupError("hash form: bad argument");
+  const uint64_t unit = group == 1 ? 64 : 128;
+  DevBuf d(n * unit);
+  d.up(points, n * unit);
+  dev_check_coords(ctx, d.p, n * unit / 32, "hash form");
+  zkpoa::phase2::Blake2b h;
+  HashStream hs(ctx, h, piece_points);
+  std::vector<uint8_t> cap;
+  if (out_bytes) hs.capture = &cap;
+  hs.points(d.p, n, group, false);
+  h.final(digest);
+  if (out_bytes && n) memcpy(out_bytes, cap.data(), n * unit);
+  ZK_API_END(ctx)
+}
+
+extern "C" int zkpoa_h_diff(zkpoa_context* ctx, const void* points, uint64_t n, void* out) {
+  ZK_API_BEGIN(ctx)
+  if (n < 2 || !points || !out) throw SetupError("h diff: bad argument");
+  DevBuf dT((2 * n - 1) * 64), dH((n - 1) * 64);
+  dT.up(points, (2 * n - 1) * 64);
+  dev_check_coords(ctx, dT.p, 2 * (2 * n - 1), "h diff");
+  h_diff(ctx, dT.p, n, dH.p);
+  ZK_HIP(hipMemcpy(out, dH.p, (n - 1) * 64, hipMemcpyDeviceToHost));
   ZK_API_END(ctx)
 }
 
@@ -799,6 +1108,15 @@ extern "C" void zkpoa_setup_defer_host_frees(int on) { defer_host_frees() = on !
 extern "C" int zkpoa_zkey_new(zkpoa_context* ctx, const char* r1cs_path, const char* ptau_path, const char* zkey_path) {
   ZK_API_BEGIN(ctx)
   if (!r1cs_path || !ptau_path || !zkey_path) throw SetupError("zkey new: null path");
-  zkey_new(ctx, r1cs_path, ptau_path, zkey_path);
+  zkey_new(ctx, r1cs_path, ptau_path, zkey_path, 0);
+  ZK_API_END(ctx)
+}
+
+extern "C" int zkpoa_zkey_new_ex(zkpoa_context* ctx, const char* r1cs_path, const char* ptau_path, const char* zkey_path,
+                                 uint32_t flags) {
+  ZK_API_BEGIN(ctx)
+  if (!r1cs_path || !ptau_path || !zkey_path) throw SetupError("zkey new: null path");
+  if (flags & ~(uint32_t)ZKPOA_SETUP_TRANSCRIPT) throw SetupError("zkey new: unknown flag");
+  zkey_new(ctx, r1cs_path, ptau_path, zkey_path, flags);
   ZK_API_END(ctx)
 }

@@ -38,6 +38,9 @@ template <> Affine<HFq> host_generator<HFq>();     // hooks_g1.hip
 template <> Affine<HFq2> host_generator<HFq2>();   // hooks_g2.hip
 // One-shot commands (zkpoa-setup) leave the tens of GB of host arrays of a `zkey new` to the process's exit: giving
 // 100 GB back page by page takes seconds that nobody is waiting for any more (zkpoa_setup_defer_host_frees).
+// setup.hip: the transcript checks of `zkey verify` (ZKPOA_ZKEY_CSHASH | ZKPOA_ZKEY_CONTRIBUTIONS) on a key whose circuit
+// hash is not zero; a malformed section 10 throws
+uint32_t phase2_verify(zkpoa_context* ctx, const char* r1cs_path, const char* ptau_path, const char* zkey_path);
 inline std::atomic<bool>& defer_host_frees() {   // one flag for all the units
   static std::atomic<bool> on{false};
   return on;

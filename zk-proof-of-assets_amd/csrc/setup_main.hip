@@ -1,13 +1,18 @@
 // `zkpoa-setup` -- the GPU stand-in for the reference's key-generation command (scripts/g16_setup.sh:243-252):
 //     snarkjs zkey new      <circuit.r1cs> <pot.ptau> <circuit_0.zkey>
 //     snarkjs groth16 setup <circuit.r1cs> <pot.ptau> <circuit_0.zkey>
-//     snarkjs zkey contribute <circuit_0.zkey> <circuit_final.zkey> --name="..." -e="..."     (:262-266; arithmetic only)
+//     snarkjs zkey contribute <circuit_0.zkey> <circuit_final.zkey> --name="..." -e="..."     (:262-266)
+//     snarkjs zkey beacon <in.zkey> <out.zkey> <beaconHash(hex)> <numIterationsExp> -n="..."  (:269-278)
 //     snarkjs wtns check <circuit.r1cs> <witness.wtns>                                      (scripts/g16_verify.sh:205-210)
 //     snarkjs zkey verify <circuit.r1cs> <pot.ptau> <circuit_final.zkey>                    (scripts/g16_verify.sh -z)
 //     snarkjs powersoftau verify <pot.ptau>              (the TODO at g16_setup.sh:201 and g16_verify.sh:164)
 // Same three file arguments (the words `zkey new` / `groth16 setup` are accepted and ignored, so the command line
 // can be kept as it is with the executable swapped). The .ptau must be prepared for phase 2 (`snarkjs powersoftau
 // prepare phase2`), as snarkjs requires too. Exit status 0 / non-zero + message on stderr.
+// The phase-2 transcript (section 10: circuit hash, contribution records; DESIGN.md "Phase-2 transcript") is opt-in:
+// `zkey new ... --transcript` fills in the circuit hash; on such a key `zkey contribute` appends a record (--name= / -n=
+// is kept in it), `zkey beacon` works, and `zkey verify` checks the hash and every record. Without the option every
+// command writes and accepts what it did before. Acceptance of these keys by `snarkjs zkey verify` is not exercised.
 #include "../../include/zkpoa_prover.h"
 
 #include "worker_exit.hpp"
@@ -69,8 +74,11 @@ static bool delta2_is_gamma2(const char* zkey_path) {
 
 int main(int argc, char** argv) {
   int a = 1;
-  bool contribute = false, check = false, verify = false, pverify = false;
-  if (argc - a >= 2 && !strcmp(argv[a], "zkey") && !strcmp(argv[a + 1], "contribute")) {
+  bool contribute = false, check = false, verify = false, pverify = false, beacon = false;
+  if (argc - a >= 2 && !strcmp(argv[a], "zkey") && !strcmp(argv[a + 1], "beacon")) {
+    beacon = true;
+    a += 2;
+  } else if (argc - a >= 2 && !strcmp(argv[a], "zkey") && !strcmp(argv[a + 1], "contribute")) {
     contribute = true;
     a += 2;
   } else if (argc - a >= 2 && !strcmp(argv[a], "zkey") && !strcmp(argv[a + 1], "verify")) {
@@ -86,18 +94,28 @@ int main(int argc, char** argv) {
                                (!strcmp(argv[a], "groth16") && !strcmp(argv[a + 1], "setup")))) {
     a += 2;
   }
-  // snarkjs' options (--name=..., -e=..., -n=..., -v) are accepted and ignored: the name and the entropy text only feed
-  // the contribution record and snarkjs' own random generator; the secret here comes from /dev/urandom (or ZKPOA_DELTA)
-  const char* pos[3] = {nullptr, nullptr, nullptr};
+  // snarkjs' options: --name=... / -n=... goes into the contribution record when the key carries a transcript; the
+  // others (-e=..., -v) are accepted and ignored: the entropy text only feeds snarkjs' own random generator, the secret
+  // here comes from /dev/urandom (or ZKPOA_DELTA). --transcript (`zkey new`) is this tool's own.
+  const char* pos[4] = {nullptr, nullptr, nullptr, nullptr};
+  const char* name = nullptr;
+  bool transcript = false;
   int npos = 0;
   for (int i = a; i < argc; i++) {
-    if (argv[i][0] == '-' && argv[i][1]) continue;
-    if (npos < 3) pos[npos] = argv[i];
+    if (argv[i][0] == '-' && argv[i][1]) {
+      if (!strncmp(argv[i], "--name=", 7)) name = argv[i] + 7;
+      else if (!strncmp(argv[i], "-n=", 3)) name = argv[i] + 3;
+      else if (!strcmp(argv[i], "--transcript")) transcript = true;
+      continue;
+    }
+    if (npos < 4) pos[npos] = argv[i];
     npos++;
   }
-  if (npos != (pverify ? 1 : (contribute || check ? 2 : 3))) {
+  if (npos != (pverify ? 1 : (beacon ? 4 : (contribute || check ? 2 : 3)))) {
     fprintf(stderr, "usage: zkpoa-setup [zkey new | groth16 setup] <circuit.r1cs> <pot.ptau> <circuit_0.zkey>\n"
+                    "         [--transcript]   fill in section 10's circuit hash (needs the ptau's section 2)\n"
                     "       zkpoa-setup zkey contribute <in.zkey> <out.zkey> [--name=...] [-e=...]\n"
+                    "       zkpoa-setup zkey beacon <in.zkey> <out.zkey> <beaconHash(hex)> <numIterationsExp> [-n=...]\n"
                     "       zkpoa-setup wtns check <circuit.r1cs> <witness.wtns>\n"
                     "       zkpoa-setup zkey verify <circuit.r1cs> <pot.ptau> <circuit.zkey>\n"
                     "       zkpoa-setup powersoftau verify <pot.ptau>\n");
@@ -116,6 +134,37 @@ int main(int argc, char** argv) {
   // `zkey new` / `zkey contribute` run in a worker process and this one leaves as soon as the key is renamed into place
   // (csrc/worker_exit.hpp: a worker that has held ~100 GB of host arrays takes seconds to be dismantled).
   // (`wtns check`, `zkey verify` and `powersoftau verify` write nothing and use no worker)
+  // beacon: hex bytes and the exponent (at most 30: 2^30 hashes take minutes, more would not finish)
+  uint8_t beacon_bytes[255];
+  unsigned long beacon_len = 0;
+  unsigned beacon_exp = 0;
+  if (beacon) {
+    const char* h = pos[2];
+    if (h[0] == '0' && (h[1] == 'x' || h[1] == 'X')) h += 2;
+    const size_t hl = strlen(h);
+    bool ok = hl > 0 && hl % 2 == 0 && hl / 2 <= sizeof beacon_bytes;
+    for (size_t i = 0; ok && i < hl; i++) {
+      const char c = h[i];
+      const int v = c >= '0' && c <= '9' ? c - '0' : ((c | 32) >= 'a' && (c | 32) <= 'f' ? (c | 32) - 'a' + 10 : -1);
+      if (v < 0) ok = false;
+      else beacon_bytes[i / 2] = (uint8_t)(i % 2 ? (beacon_bytes[i / 2] | v) : v << 4);
+    }
+    char* end = nullptr;
+    const long e = strtol(pos[3], &end, 10);
+    if (!ok || end == pos[3] || *end || e < 0 || e > 30) {
+      fprintf(stderr, "zkpoa-setup: zkey beacon: the beacon must be 1-255 bytes of hex and numIterationsExp in [0, 30]\n");
+      return 2;
+    }
+    beacon_len = hl / 2;
+    beacon_exp = (unsigned)e;
+  }
+  // does the input of `zkey contribute` carry a transcript? (host only; an unreadable file is reported by the command)
+  bool in_transcript = false;
+  if (contribute) {
+    int has = 0;
+    uint32_t cnt = 0;
+    if (zkpoa_zkey_contributions(pos[0], &has, &cnt, nullptr, 0) == PROVER_OK) in_transcript = has != 0;
+  }
   zkpoa::WorkerExit we = zkpoa::WorkerExit::start(!check && !verify && !pverify, "zkpoa-setup");
   if (we.is_worker()) zkpoa_setup_defer_host_frees(1);
   auto leave = [&](int code) -> int {
@@ -145,7 +194,7 @@ int main(int argc, char** argv) {
     uint32_t failed = 0;
     rc = zkpoa_zkey_verify(ctx, pos[0], pos[1], pos[2], &failed);
     if (rc == PROVER_OK) {
-      static const char* const kWhat[8] = {
+      static const char* const kWhat[10] = {
           "HEADER: protocol, moduli, alpha1 / beta1 / beta2 (against the ptau) or gamma2 (the G2 generator) do not match",
           "POINTS: a point is off its curve, a G2 point (B2, beta2, gamma2, delta2) is outside G2, or delta1 is zero",
           "DELTA: e(delta1, G2) != e(G1, delta2)",
@@ -153,9 +202,17 @@ int main(int argc, char** argv) {
           "A: section 5 (A) does not match the r1cs and the ptau",
           "B1: section 6 (B in G1) does not match the r1cs and the ptau",
           "B2: section 7 (B in G2) does not match the r1cs and the ptau",
-          "ICCH: sections 3, 8 or 9 (IC, C, H) do not match the r1cs, the ptau and delta"};
-      fprintf(stderr, "[WARN]  zkpoa: section 10 (circuit hash, contribution records) is not checked\n");
-      for (int b = 0; b < 8; b++)
+          "ICCH: sections 3, 8 or 9 (IC, C, H) do not match the r1cs, the ptau and delta",
+          "CSHASH: section 10's circuit hash does not match the r1cs, the ptau and the key's A, B1, B2, IC",
+          "CONTRIBUTIONS: a contribution record does not verify (transcript hash, pairing checks, beacon) or the "
+          "records do not lead to delta1"};
+      int has_transcript = 0;
+      uint32_t n_records = 0;
+      static char records[1 << 16];
+      records[0] = 0;
+      (void)zkpoa_zkey_contributions(pos[2], &has_transcript, &n_records, records, sizeof records);
+      if (!has_transcript) fprintf(stderr, "[WARN]  zkpoa: section 10 (circuit hash, contribution records) is not checked: the key carries no transcript\n");
+      for (int b = 0; b < 10; b++)
         if (failed & (1u << b)) fprintf(stderr, "[ERROR] zkpoa: %s\n", kWhat[b]);
       if (failed) {
         zkpoa_context_destroy(ctx);
@@ -163,6 +220,12 @@ int main(int argc, char** argv) {
       }
       if (delta2_is_gamma2(pos[2]))
         fprintf(stderr, "[WARN]  zkpoa: delta2 is the generator: the key has had no contribution, anyone can forge proofs with it\n");
+      if (has_transcript) {
+        printf("[INFO]  zkpoa: circuit hash and %u contribution(s) verified\n", n_records);
+        unsigned k = 1;
+        for (char* line = strtok(records, "\n"); line; line = strtok(nullptr, "\n"), k++)
+          printf("[INFO]  zkpoa: contribution #%u: %s\n", k, line);
+      }
       printf("[INFO]  zkpoa: ZKey Ok!\n");
     }
   } else if (pverify) {   // snarkjs prints "Powers of Tau Ok!" and exits 0, or names what does not hold and exits 1
@@ -193,13 +256,16 @@ int main(int argc, char** argv) {
       printf("[INFO]  zkpoa: Powers of Tau Ok!\n");
     }
   } else {
-    rc = contribute ? zkpoa_zkey_contribute(ctx, pos[0], pos[1], delta_p) : zkpoa_zkey_new(ctx, pos[0], pos[1], pos[2]);
+    if (beacon) rc = zkpoa_zkey_beacon(ctx, pos[0], pos[1], beacon_bytes, beacon_len, beacon_exp, name);
+    else if (contribute && in_transcript) rc = zkpoa_zkey_contribute_ex(ctx, pos[0], pos[1], delta_p, name);
+    else if (contribute) rc = zkpoa_zkey_contribute(ctx, pos[0], pos[1], delta_p);
+    else rc = zkpoa_zkey_new_ex(ctx, pos[0], pos[1], pos[2], transcript ? ZKPOA_SETUP_TRANSCRIPT : 0u);
   }
   if (rc != PROVER_OK) fprintf(stderr, "zkpoa-setup: %s\n", zkpoa_last_error(ctx));
   if (!we.is_worker()) zkpoa_context_destroy(ctx);
   clock_gettime(CLOCK_MONOTONIC, &t1);
   if (rc == PROVER_OK && getenv("ZKPOA_VERBOSE") && !check && !verify && !pverify)
-    fprintf(stderr, "zkpoa-setup: %s written in %.2f s\n", pos[contribute ? 1 : 2],
+    fprintf(stderr, "zkpoa-setup: %s written in %.2f s\n", pos[contribute || beacon ? 1 : 2],
             (t1.tv_sec - t0.tv_sec) + (t1.tv_nsec - t0.tv_nsec) / 1e9);
   return leave(rc == PROVER_OK ? 0 : 1);
 }

@@ -31,8 +31,9 @@ static __global__ __launch_bounds__(256) void fold_compare_kernel(void* __restri
 //   A:  sum rho_i A_i  = sum a_j L1_j          B1 / B2: sum rho_i B_i = sum b_j L_j (G1 / G2)
 //   ICCH: e(sum_{i<=l} rho_i IC_i - Q, G2) e(sum_{i>l} rho_i C_i + sum sigma_j H_j, delta2) = 1,
 //         Q = sum a_j bL_j + b_j aL_j + c_j L1_j + sigma_j Hodd_j (one MSM over the four ptau ranges back to back)
-// Returns the bitmask of failed checks (include/zkpoa_prover.h ZKPOA_ZKEY_*); a malformed file throws. Section 10 is not
-// read. One key section at a time is on the device.
+// Returns the bitmask of failed checks (include/zkpoa_prover.h ZKPOA_ZKEY_*); a malformed file throws. One key section at a
+// time is on the device. Section 10: a zero circuit hash ("no transcript") is not looked at further; otherwise the circuit
+// hash and the contribution records are checked as well (setup.hip phase2_verify, DESIGN.md "Phase-2 transcript").
 uint32_t zkey_verify(zkpoa_context* ctx, const char* r1cs_path, const char* ptau_path, const char* zkey_path) {
   PhaseTimer phase("zkey verify", 38);
   MappedFile fr(r1cs_path);
@@ -46,6 +47,10 @@ uint32_t zkey_verify(zkpoa_context* ctx, const char* r1cs_path, const char* ptau
   auto ks = bin_sections(fk, "zkey", 1, "zkey");
   for (uint32_t t = 1; t <= 9; t++)
     if (!ks.count(t)) throw SetupError("zkey: section " + std::to_string(t) + " missing");
+  // a transcript: section 10 starts with a circuit hash that is not zero (a key without one is checked as before)
+  bool transcript = false;
+  if (ks.count(10) && ks[10].len >= 64)
+    for (int i = 0; i < 64; i++) transcript |= fk.p[ks[10].off + i] != 0;
   if (ks[1].len != 4) throw SetupError("zkey: section 1 has the wrong size");
   if (ks[2].len != kHdrLen) throw SetupError("zkey: groth16 header has the wrong size");
   const uint8_t* hp = fk.p + ks[2].off;
@@ -252,6 +257,7 @@ uint32_t zkey_verify(zkpoa_context* ctx, const char* r1cs_path, const char* ptau
     if (!pairing::pair_eq(h_to_affine(x), host_generator<HFq2>(), ch, delta2)) failed |= ZKPOA_ZKEY_ICCH;
   }
   phase("pairings");
+  if (transcript) failed |= phase2_verify(ctx, r1cs_path, ptau_path, zkey_path);
   return failed;
 }
 
