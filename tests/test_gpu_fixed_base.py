@@ -109,24 +109,34 @@ def test_prove_with_tables_is_bit_identical(ctx, zk, tag):
 
 def test_prove_with_partial_tables_and_shards(ctx, zk):
     """2^16 synthetic key: tables on every section, on a budget that only fits some, and with the handle re-pointed
-    to shards (tables are bypassed there) -- always the same proof, and it matches the known-dlog expectation."""
+    to shards (tables are bypassed there) -- always the same proof, and it matches the known-dlog expectation.
+    The proof is the same whichever form an MSM took, so which form it took is read off each lane's count of mixed
+    additions (deterministic for a witness, a form and a window width): a table that is built must also be used."""
     from zkpoa_amd.synthetic import SyntheticCircuit
     circ = SyntheticCircuit(zk, ctx, 16, 60000, n_public=2, seed=77, witness_like=True)
+
+    def lane_adds():                                      # H, A, B1, B2, C: millions of mixed additions of the last proof
+        return [ctx.last_ms_lane(lane, 2) for lane in range(5)]
     try:
         rng = random.Random(8)
         r_, s_ = rng.randrange(R), rng.randrange(R)
         want, _ = circ.prove(r_, s_)
+        classic = lane_adds()
         P = circ.h_scalars()
         assert P.tobytes() == co.h_scalars(circ.coeff_section_bytes(), circ.witness_bytes(), circ.m, 16)
         assert circ.check(want, r_, s_, P)
         full = circ.key.precompute()
         assert full > 0
         assert circ.prove(r_, s_)[0] == want
+        tabled = lane_adds()
+        print("mixed additions per lane (millions): classic %s, all tables %s" % (classic, tabled))
+        assert any(a != b for a, b in zip(classic, tabled))   # else the equalities below could not tell the forms apart
         some = circ.key.precompute(full // 3)             # only the first table(s) fit
         assert 0 < some <= full // 3
         assert circ.prove(r_, s_)[0] == want
         assert circ.key.precompute(1) == 0                # nothing fits: classic form everywhere
         assert circ.prove(r_, s_)[0] == want
+        assert lane_adds() == classic
         circ.key.precompute()
         header = circ.key.header()
         parts = []
@@ -136,6 +146,7 @@ def test_prove_with_partial_tables_and_shards(ctx, zk):
         circ.key.set_shard(0, 1)
         assert zk.prove_assemble(header, zk.sum_partials(parts), r_, s_) == want
         assert circ.prove(r_, s_)[0] == want              # whole key again: tables back in use
+        assert lane_adds() == tabled
     finally:
         circ.close()
 

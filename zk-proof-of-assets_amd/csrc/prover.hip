@@ -112,12 +112,28 @@ void* dev_upload(zkpoa_context* ctx, const void* src, size_t bytes) {
 
 }  // namespace
 
+// The five points of a zkey header the prover needs. Wire form (zkpoa_zkey_header, zkpoa_prove_assemble,
+// zkpoa_zkey_load_device): alpha1(64) beta1(64) beta2(128) delta1(64) delta2(128).
+struct HeaderPoints {   // (members in wire order)
+  Affine<HFq> alpha1, beta1;
+  Affine<HFq2> beta2;
+  Affine<HFq> delta1;
+  Affine<HFq2> delta2;
+};
+static HeaderPoints header_points(const uint8_t* alpha1, const uint8_t* beta1, const uint8_t* beta2, const uint8_t* delta1,
+                                  const uint8_t* delta2) {
+  return {h_affine_from_bytes<HFq>(alpha1), h_affine_from_bytes<HFq>(beta1), h_affine_from_bytes<HFq2>(beta2),
+          h_affine_from_bytes<HFq>(delta1), h_affine_from_bytes<HFq2>(delta2)};
+}
+static HeaderPoints header_points_from_bytes(const uint8_t in[448]) {   // the inverse of zkey_header_bytes
+  return header_points(in, in + 64, in + 128, in + 256, in + 320);
+}
+
 // ---- device-resident proving key -------------------------------------------------------------------
 struct zkpoa_zkey {
   uint32_t nVars = 0, nPublic = 0, domain = 0, power = 0;
   uint64_t nCoefs = 0;
-  Affine<HFq> alpha1, beta1, delta1;
-  Affine<HFq2> beta2, delta2;
+  HeaderPoints hdr;
   // Verification key carried by the zkey itself (section 2: alpha1, beta2, gamma2, delta2; section 3: IC), wire
   // format alpha1(64) beta2(128) gamma2(128) delta2(128) IC[(nPublic+1) x 64]. Empty for keys assembled from
   // device buffers (zkpoa_zkey_load_device has no gamma2 / IC). Used by the self-check of the first proof(s).
@@ -210,9 +226,18 @@ struct zkpoa_zkey {
     tables_settled = false;
     warmed = false;
   }
-  void set_full() {
-    wlo = 0; wcnt = nVars; clo = 0; ccnt = (uint64_t)nVars - nPublic - 1; hlo = 0; hcnt = domain;
+  void release_cyclic_h_table() {   // a new cyclic shard replaces dHs: the table built from the old one goes
+    if (!tH_cyclic) return;
+    uint64_t info[4];
+    msm_table_info(tH, info);
+    table_bytes -= std::min(info[3], table_bytes);
+    msm_table_release(tH);
+    tH = nullptr;
+    tH_cyclic = false;
   }
+  // H scalars one proof leaves in d_abc: a rank of a split chain computes its domain / G, anyone else all of them
+  static uint64_t split_h_count(uint64_t domain, uint64_t world) { return domain / world; }
+  uint64_t h_scalar_count() const { return split_world > 1 ? split_h_count(domain, split_world) : domain; }
   static void split(uint64_t n, uint64_t rank, uint64_t world, uint64_t& lo, uint64_t& cnt) {
     uint64_t base = n / world, rem = n % world;
     lo = rank * base + (rank < rem ? rank : rem);
@@ -384,11 +409,7 @@ std::unique_ptr<zkpoa_zkey> zkey_parse(const uint8_t* buf, uint64_t size, ZkeySe
   while ((1u << zk->power) < zk->domain) zk->power++;
   if (zk->power > 28) throw ProverError(PROVER_ERROR, "zkey domainSize exceeds 2^28");
   if (zk->nPublic + 1 > zk->nVars) throw ProverError(PROVER_ERROR, "zkey nPublic >= nVars");
-  zk->alpha1 = h_affine_from_bytes<HFq>(h.alpha1);
-  zk->beta1 = h_affine_from_bytes<HFq>(h.beta1);
-  zk->beta2 = h_affine_from_bytes<HFq2>(h.beta2);
-  zk->delta1 = h_affine_from_bytes<HFq>(h.delta1);
-  zk->delta2 = h_affine_from_bytes<HFq2>(h.delta2);
+  zk->hdr = header_points(h.alpha1, h.beta1, h.beta2, h.delta1, h.delta2);
   // section 3 (IC) is optional for proving; with it the handle can verify its own proofs
   {
     auto it3 = secs.find(3);
@@ -431,32 +452,61 @@ void set_block_cyclic(zkpoa_zkey* zk, uint64_t rank, uint64_t world, uint32_t bc
   zk->ccnt = zkpoa_zkey::bc_count((uint64_t)zk->nVars - zk->nPublic - 1, bc_log, rank, world);
 }
 
+// A new handle (its sizes set) becomes shard `rank` of `world`; world == 1: the whole key. Host state only: the
+// ranges, whose resident arrays start at the ranges themselves, then the split chain and the block-cyclic deal.
+void shard_init(zkpoa_zkey* zk, uint64_t rank, uint64_t world, bool split, uint32_t bc_log) {
+  if (world == 0 || rank >= world) throw ProverError(PROVER_ERROR, "zkey shard: rank/world out of range");
+  zk->set_shard(rank, world);
+  zk->wbase = zk->wlo; zk->cbase = zk->clo; zk->hbase = zk->hlo;
+  if (split) {
+    check_split(zk, rank, world);
+    set_split(zk, rank, world);
+    zk->hlo = zk->hbase = 0;
+    zk->hcnt = 0;   // no contiguous H range on this handle: its H points are the cyclic shard dHs
+  }
+  set_block_cyclic(zk, rank, world, bc_log);
+}
+
+struct LoadPhases {   // ZKPOA_VERBOSE: where a key load spends its time
+  bool verbose = req_getenv("ZKPOA_VERBOSE") != nullptr;
+  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+  void operator()(const char* what) {
+    if (verbose) fprintf(stderr, "zkpoa: zkey load: %-34s %7.1f ms\n", what, ms_since(t));
+    t = std::chrono::steady_clock::now();
+  }
+};
+
+// The rest of a key load, once the point sections are resident: compacted queries, CSR and per-proof buffers, NTT
+// tables; synchronised on return. recs: the 44-byte coefficient records, in device memory or (recs_on_host) still in
+// the file: those go up only after the queries' originals are freed, and their device copy goes once the CSR exists.
+void finish_load(zkpoa_context* ctx, zkpoa_zkey* zk, const void* recs, bool recs_on_host, bool split, LoadPhases phase) {
+  hipStream_t st = ctx->dev.lanes[0].stream;
+  if (zk->bc_log) ZK_HIP(hipMalloc(&zk->d_cscal, zk->ccnt ? zk->ccnt * 32 : 1));
+  queries_compact(ctx, zk, zk->wcnt);
+  phase("A / B queries without infinity");
+  std::unique_ptr<void, hipError_t (*)(void*)> uploaded(nullptr, hipFree);
+  if (recs_on_host) {
+    uploaded.reset(dev_upload(ctx, recs, zk->nCoefs * 44));
+    recs = uploaded.get();
+    phase("coefficient section -> HBM");
+  }
+  build_csr(ctx, zk, recs, split);
+  uploaded.reset();
+  phase("CSR of the coefficients");
+  ntt_prepare(ctx, st, zk->power);
+  if (split) ntt_prepare(ctx, st, zk->power - zk->split_log);
+  ZK_HIP(hipStreamSynchronize(st));
+  phase("NTT tables");
+}
+
 zkpoa_zkey* zkey_load_impl(zkpoa_context* ctx, const uint8_t* buf, uint64_t size, uint64_t rank = 0,
                            uint64_t world = 1, bool split = false, uint32_t bc_log = 0) {
   ZkeySections zs;
   std::unique_ptr<zkpoa_zkey> zk = zkey_parse(buf, size, zs);
   const Section &s4 = zs.s4, &s5 = zs.s5, &s6 = zs.s6, &s7 = zs.s7, &s8 = zs.s8, &s9 = zs.s9;
-  const uint64_t m = zk->nVars, n = zk->domain;
-
-  if (world == 0 || rank >= world) throw ProverError(PROVER_ERROR, "zkey shard: rank/world out of range");
-  zk->set_shard(rank, world);   // world == 1: the whole key
-  zk->wbase = zk->wlo;
-  zk->cbase = zk->clo;
-  zk->hbase = zk->hlo;
-  if (split) {
-    check_split(zk.get(), rank, world);
-    set_split(zk.get(), rank, world);
-  }
-  set_block_cyclic(zk.get(), rank, world, bc_log);
-  const bool verbose = req_getenv("ZKPOA_VERBOSE") != nullptr;
-  auto tph = std::chrono::steady_clock::now();
-  auto phase = [&](const char* what) {   // ZKPOA_VERBOSE: where a key load spends its time
-    if (!verbose) return;
-    auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "zkpoa: zkey load: %-34s %7.1f ms\n", what,
-            std::chrono::duration<double, std::milli>(now - tph).count());
-    tph = now;
-  };
+  const uint64_t m = zk->nVars;
+  shard_init(zk.get(), rank, world, split, bc_log);
+  LoadPhases phase;
   try {
     // each rank uploads only its byte range(s) of every point section: one contiguous range, or with block-cyclic
     // shards its blocks of 2^bc_log items one after the other (each still a contiguous byte range of the file)
@@ -483,10 +533,9 @@ zkpoa_zkey* zkey_load_impl(zkpoa_context* ctx, const uint8_t* buf, uint64_t size
     zk->dB1 = upload_items(s6.p, m, zk->wlo, zk->wcnt, 64);
     zk->dB2 = upload_items(s7.p, m, zk->wlo, zk->wcnt, 128);
     zk->dC = upload_items(s8.p, m - zk->nPublic - 1, zk->clo, zk->ccnt, 64);
-    if (zk->bc_log) ZK_HIP(hipMalloc(&zk->d_cscal, zk->ccnt ? zk->ccnt * 32 : 1));
     if (split) {
       // cyclic H shard: H[t * world + rank], gathered on the host (the section is walked once per rank)
-      const uint64_t cnt = n / world;
+      const uint64_t cnt = zk->h_scalar_count();
       std::vector<uint8_t> stage(cnt * 64);
       const unsigned nthreads = 6;
       std::vector<std::thread> th;
@@ -497,8 +546,6 @@ zkpoa_zkey* zkey_load_impl(zkpoa_context* ctx, const uint8_t* buf, uint64_t size
         });
       for (auto& t : th) t.join();
       zk->dHs = dev_upload(ctx, stage.data(), cnt * 64);
-      zk->hlo = zk->hbase = 0;
-      zk->hcnt = 0;   // no contiguous H range on this handle
     } else {
       zk->dH = dev_upload(ctx, s9.p + zk->hlo * 64, zk->hcnt * 64);
     }
@@ -511,30 +558,14 @@ zkpoa_zkey* zkey_load_impl(zkpoa_context* ctx, const uint8_t* buf, uint64_t size
       range_check<FqParams>(st0, zk->dB1, zk->wcnt * 2, (uint32_t*)flag.p);
       range_check<FqParams>(st0, zk->dB2, zk->wcnt * 4, (uint32_t*)flag.p);
       range_check<FqParams>(st0, zk->dC, zk->ccnt * 2, (uint32_t*)flag.p);
-      range_check<FqParams>(st0, split ? zk->dHs : zk->dH, (split ? n / world : zk->hcnt) * 2, (uint32_t*)flag.p);
+      range_check<FqParams>(st0, split ? zk->dHs : zk->dH, (split ? zk->h_scalar_count() : zk->hcnt) * 2, (uint32_t*)flag.p);
       uint32_t bad = 0;
       ZK_HIP(hipMemcpyAsync(&bad, flag.p, 4, hipMemcpyDeviceToHost, st0));
       ZK_HIP(hipStreamSynchronize(st0));
       if (bad) throw ProverError(PROVER_ERROR, "zkey point coordinate is not a field element (>= q)");
       phase("coordinate range check");
     }
-    queries_compact(ctx, zk.get(), zk->wcnt);
-    phase("A / B queries without infinity");
-    hipStream_t st = ctx->dev.lanes[0].stream;
-    void* d_recs = dev_upload(ctx, s4.p + 4, zk->nCoefs * 44);
-    phase("coefficient section -> HBM");
-    try {
-      build_csr(ctx, zk.get(), d_recs, split);
-    } catch (...) {
-      (void)hipFree(d_recs);
-      throw;
-    }
-    (void)hipFree(d_recs);
-    phase("CSR of the coefficients");
-    ntt_prepare(ctx, st, zk->power);
-    if (split) ntt_prepare(ctx, st, zk->power - zk->split_log);
-    ZK_HIP(hipStreamSynchronize(st));
-    phase("NTT tables");
+    finish_load(ctx, zk.get(), s4.p + 4, /*recs_on_host=*/true, split, phase);
   } catch (...) {
     zk->release();
     throw;
@@ -739,16 +770,62 @@ void check_witness_len(const WtnsView& w, const zkpoa_zkey* zk) {
                                                          ", witness: " + std::to_string(w.n));
 }
 
-// a table covers the whole resident array: the handle's current range must be that array
-bool split_c_partial(const zkpoa_zkey* zk) {
-  uint64_t info[4];
-  msm_table_info(zk->tC, info);
-  return info[0] != zk->ccnt;
-}
-bool split_h_partial(const zkpoa_zkey* zk) {
-  uint64_t info[4];
-  msm_table_info(zk->tH, info);
-  return info[0] != zk->hcnt;
+// ---- what each of the five MSMs of a proof covers, for the handle as it is right now (stage = lane id) -------------
+// The planner (lane_needs), the table builder (zkey_precompute) and the stages (prove_partials) all read this one view.
+enum { kStageH = 0, kStageA = 1, kStageB1 = 2, kStageB2 = 3, kStageC = 4 };
+struct StageView {
+  uint64_t n = 0;                    // points
+  const char* bases = nullptr;       // the first of them; null while a staged prove has not allocated the array
+  uint64_t scalar_off = 0;           // H, C: index of the first scalar in d_abc resp. in the witness from wire nPublic + 1
+  const MsmTable* table = nullptr;   // the fixed-base table whose array these n points cover exactly, else null (B1 and
+  int table_c = 0;                   // B2: only as a pair, they share one sort); table_c: its window width
+  // What a table for this stage is built from: the whole resident array, array_n points. The compacted queries record
+  // their length; of sections 8 and 9 the handle knows its current range only, which is the whole array when it starts
+  // at the array's first point. array_n == 0 means: no table can be built now (that, an absent or an empty array).
+  const void* array = nullptr;
+  uint64_t array_n = 0;
+};
+StageView stage_view(const zkpoa_zkey* zk, int stage) {
+  StageView v;
+  const MsmTable* t = nullptr;
+  uint64_t first = 0;   // of these points, in bytes from the start of the array
+  if (stage == kStageH && zk->split_world > 1) {   // the cyclic shard, all of it
+    v.array = zk->dHs;
+    v.n = v.array_n = zk->h_scalar_count();
+    t = zk->tH_cyclic ? zk->tH : nullptr;
+  } else if (stage == kStageH) {
+    v.array = zk->dH;
+    v.n = zk->hcnt;
+    first = (zk->hlo - zk->hbase) * 64;
+    v.array_n = first ? 0 : v.n;
+    v.scalar_off = zk->hlo;
+    t = zk->tH_cyclic ? nullptr : zk->tH;
+  } else if (stage == kStageC) {
+    v.array = zk->dC;
+    v.n = zk->ccnt;
+    first = (zk->clo - zk->cbase) * 64;
+    v.array_n = first ? 0 : v.n;
+    v.scalar_off = zk->clo;
+    t = zk->tC;
+  } else {
+    const zkpoa_zkey::CompactQuery& q = stage == kStageA ? zk->qA : zk->qB;
+    v.array = stage == kStageB2 ? q.g2 : q.g1;
+    v.n = q.cnt;
+    v.array_n = q.res;
+    first = q.lo * (stage == kStageB2 ? 128 : 64);
+    t = stage == kStageA ? zk->tA : !(zk->tB1 && zk->tB2) ? nullptr : stage == kStageB1 ? zk->tB1 : zk->tB2;
+  }
+  if (v.array) v.bases = reinterpret_cast<const char*>(v.array) + first;
+  else v.array_n = 0;
+  if (t && first == 0 && v.n == v.array_n) {
+    uint64_t info[4];
+    msm_table_info(t, info);
+    if (info[0] == v.n) {
+      v.table = t;
+      v.table_c = (int)info[1];
+    }
+  }
+  return v;
 }
 
 // Fixed-base tables for a resident key, most valuable first, while they fit the budget (bytes; 0 = half of the HBM
@@ -790,23 +867,31 @@ uint64_t zkey_precompute(zkpoa_context* ctx, zkpoa_zkey* zk, uint64_t budget, in
   if (step) zk->table_budget = budget;
   const int force_c = ctx->opt_msm_c;
   auto fits = [&](uint64_t bytes) { return zk->table_bytes + bytes <= budget; };
-  const uint64_t nH = split ? (zk->dHs ? (uint64_t)(zk->domain >> zk->split_log) : 0) : (zk->dH ? zk->hcnt : 0);
-  const uint64_t nC = zk->ccnt, nA = zk->qA.res, nB = zk->qB.res;
+  // One list of the tables this handle could have, most valuable first (B1 and B2 are one step). n = 0: nothing to
+  // build from -- an empty or absent array, or a range of section 8 / 9 that is not the whole resident array.
+  struct Candidate {
+    MsmTable** slot;
+    bool g2;
+    const void* bases;
+    uint64_t n;
+    int c;
+    size_t bytes() const { return g2 ? msm_table_bytes_g2(n, c) : msm_table_bytes_g1(n, c); }
+  };
   // a table that does not fit after all (allocation failure) ends the list; the ones built so far stay
-  auto build = [&](MsmTable** slot, bool g2, const void* bases, uint64_t n, int c) -> bool {
-    if (*slot) return true;                     // (step mode: built by an earlier step)
+  auto build = [&](const Candidate& t) -> bool {
+    if (*t.slot) return true;                   // (step mode: built by an earlier step)
     if (step && built >= max_new) {             // this step's share is done: the rest waits for the next step
       deferred = true;
       return false;
     }
     built++;
     try {
-      *slot = g2 ? msm_table_build_g2(ctx, bases, n, c) : msm_table_build_g1(ctx, bases, n, c);
-      zk->table_bytes += g2 ? msm_table_bytes_g2(n, c) : msm_table_bytes_g1(n, c);
+      *t.slot = t.g2 ? msm_table_build_g2(ctx, t.bases, t.n, t.c) : msm_table_build_g1(ctx, t.bases, t.n, t.c);
+      zk->table_bytes += t.bytes();
       return true;
     } catch (const HipError&) {
       (void)hipGetLastError();
-      *slot = nullptr;
+      *t.slot = nullptr;
       return false;
     }
   };
@@ -820,14 +905,21 @@ uint64_t zkey_precompute(zkpoa_context* ctx, zkpoa_zkey* zk, uint64_t budget, in
     return c;
   };
   msm_set_density_hint(nullptr);
-  const int cC = nC ? witness_c(nC, false) : 0, cA = nA ? witness_c(nA, false) : 0, cB = nB ? witness_c(nB, true) : 0;
+  // (one window width for both B tables: the G2 model's -- shorter pieces -- as the shared sort is planned for G2)
+  auto candidate = [&](MsmTable** slot, int stage) {
+    const StageView v = stage_view(zk, stage);
+    const int c = stage == kStageH ? force_c : v.array_n ? witness_c(v.array_n, stage == kStageB1 || stage == kStageB2) : 0;
+    return Candidate{slot, stage == kStageB2, v.array, v.array_n, c};
+  };
+  const Candidate tabs[5] = {candidate(&zk->tH, kStageH), candidate(&zk->tC, kStageC), candidate(&zk->tA, kStageA),
+                             candidate(&zk->tB1, kStageB1), candidate(&zk->tB2, kStageB2)};
+  const int kSingles = 3;   // H, C, A are one step each; the B pair behind them is one step
+  const Candidate &tB1 = tabs[kSingles], &tB2 = tabs[kSingles + 1];
   if (release_lanes) {
     // Nothing to build (a 2^27 key: the lanes' workspaces come first): keep the workspaces. Giving back 150 GB and
     // taking it again costs seconds -- the driver wipes released memory before it hands it out (measured: 5 s per lane).
-    const bool any = (!zk->tH && nH && (split || zk->hlo == zk->hbase) && fits(msm_table_bytes_g1(nH, force_c))) ||
-                     (!zk->tC && nC && zk->clo == zk->cbase && fits(msm_table_bytes_g1(nC, cC))) ||
-                     (!zk->tA && nA && fits(msm_table_bytes_g1(nA, cA))) ||
-                     (!(zk->tB1 && zk->tB2) && nB && fits(msm_table_bytes_g1(nB, cB) + msm_table_bytes_g2(nB, cB)));
+    bool any = !(zk->tB1 && zk->tB2) && tB1.n && fits(tB1.bytes() + tB2.bytes());
+    for (int i = 0; i < kSingles; i++) any = any || (!*tabs[i].slot && tabs[i].n && fits(tabs[i].bytes()));
     if (!any) {
       zk->tables_settled = true;
       return zk->table_bytes;
@@ -836,22 +928,20 @@ uint64_t zkey_precompute(zkpoa_context* ctx, zkpoa_zkey* zk, uint64_t budget, in
   }
   bool more = true;
   // (a table that exists already counts as fitting: its bytes are in table_bytes)
-  if (more && nH && (split || zk->hlo == zk->hbase) && (zk->tH || fits(msm_table_bytes_g1(nH, force_c)))) {
-    more = build(&zk->tH, false, split ? zk->dHs : zk->dH, nH, force_c);
-    zk->tH_cyclic = split && zk->tH;
+  for (int i = 0; i < kSingles && more; i++) {
+    if (!tabs[i].n || !(*tabs[i].slot || fits(tabs[i].bytes()))) continue;
+    more = build(tabs[i]);
+    if (tabs[i].slot == &zk->tH) zk->tH_cyclic = split && zk->tH;
   }
-  if (more && nC && zk->clo == zk->cbase && (zk->tC || fits(msm_table_bytes_g1(nC, cC)))) more = build(&zk->tC, false, zk->dC, nC, cC);
-  if (more && nA && (zk->tA || fits(msm_table_bytes_g1(nA, cA)))) more = build(&zk->tA, false, zk->qA.g1, nA, cA);
-  if (more && nB && !(zk->tB1 && zk->tB2)) {
-    // (one window width for both B tables: the G2 model's -- shorter pieces -- as the shared sort is planned for G2)
+  if (more && tB1.n && !(zk->tB1 && zk->tB2)) {
     if (step && built >= max_new) {   // the pair is one step's work
       more = false;
       deferred = true;
-    } else if (fits(msm_table_bytes_g1(nB, cB) + msm_table_bytes_g2(nB, cB))) {
+    } else if (fits(tB1.bytes() + tB2.bytes())) {
       if (step) max_new = built + 2;              // ... and both halves belong to it
-      more = build(&zk->tB1, false, zk->qB.g1, nB, cB) && build(&zk->tB2, true, zk->qB.g2, nB, cB);
+      more = build(tB1) && build(tB2);
       if (!more && zk->tB1) {   // the pair is only usable together
-        zk->table_bytes -= msm_table_bytes_g1(nB, cB);
+        zk->table_bytes -= tB1.bytes();
         msm_table_release(zk->tB1);
         zk->tB1 = nullptr;
       }
@@ -880,26 +970,21 @@ struct LaneNeeds {
 static LaneNeeds lane_needs(const zkpoa_context* ctx, const zkpoa_zkey* zk, const uint64_t lim[5], bool with_tables) {
   LaneNeeds w;
   const int fc = ctx->opt_msm_c;
-  const bool split = zk->split_world > 1;
-  auto table_c = [&](const MsmTable* t, uint64_t n, uint64_t limit) -> int {
-    if (!with_tables || !t || n > limit) return 0;
-    uint64_t info[4];
-    msm_table_info(t, info);
-    return info[0] == n ? (int)info[1] : 0;
-  };
+  const StageView v[5] = {stage_view(zk, 0), stage_view(zk, 1), stage_view(zk, 2), stage_view(zk, 3), stage_view(zk, 4)};
+  // a table is only of use to a whole MSM (msm_run)
+  auto table_c = [&](int l, uint64_t limit) { return with_tables && v[l].n <= limit ? v[l].table_c : 0; };
   const double* dens = zk->have_density ? zk->witness_density : nullptr;
   // H (lane 0): uniform scalars
   msm_set_density_hint(nullptr);
-  const uint64_t nH = split ? (uint64_t)(zk->domain >> zk->split_log) : zk->hcnt;
-  w.bytes[0] = msm_workspace_g1(std::min(nH, lim[0]), fc, false, table_c(zk->tH, nH, lim[0]), true);
+  w.bytes[0] = msm_workspace_g1(std::min(v[0].n, lim[0]), fc, false, table_c(0, lim[0]), true);
   // A (lane 1), C (lane 4): witness scalars
   msm_set_density_hint(dens);
-  w.bytes[1] = msm_workspace_g1(std::min(zk->qA.cnt, lim[1]), fc, false, table_c(zk->tA, zk->qA.cnt, lim[1]), true);
-  w.bytes[4] = msm_workspace_g1(std::min(zk->ccnt, lim[4]), fc, false, table_c(zk->tC, zk->ccnt, lim[4]), true);
+  w.bytes[1] = msm_workspace_g1(std::min(v[1].n, lim[1]), fc, false, table_c(1, lim[1]), true);
+  w.bytes[4] = msm_workspace_g1(std::min(v[4].n, lim[4]), fc, false, table_c(4, lim[4]), true);
   // B (lanes 2 and 3): one sort for both when the whole query fits one
-  const uint64_t nB = zk->qB.cnt, limB = std::min(lim[2], lim[3]);
+  const uint64_t nB = v[2].n, limB = std::min(lim[2], lim[3]);
   if (nB <= limB) {
-    const int tc = (zk->tB1 && zk->tB2) ? table_c(zk->tB1, nB, limB) : 0;
+    const int tc = table_c(2, limB);
     w.bytes[2] = msm_workspace_g1(nB, fc, true, tc, true);
     w.bytes[3] = msm_workspace_g2(nB, fc, tc, false);
   } else {
@@ -938,8 +1023,8 @@ static void budget_lane_workspaces(zkpoa_context* ctx, const zkpoa_zkey* zk) {
       if (ctx->dev.lanes[l].ws.limit && x.bytes[l] > ctx->dev.lanes[l].ws.limit) return false;
     return (double)x.total() <= avail;
   };
-  const uint64_t n_of[5] = {zk->split_world > 1 ? (uint64_t)(zk->domain >> zk->split_log) : zk->hcnt, zk->qA.cnt,
-                            zk->qB.cnt, zk->qB.cnt, zk->ccnt};
+  uint64_t n_of[5];
+  for (int l = 0; l < 5; l++) n_of[l] = stage_view(zk, l).n;
   while (!fits(w)) {
     // the lane that is over its cap first, else the one with the largest workspace; its MSM takes half as many points
     int pick = -1;
@@ -1042,15 +1127,13 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
   // opt_prove_serial (measurement only): every stage runs alone, one after the other, so the per-stage device times
   // are solo times and their sum / the overlapped wall time says how much the five lanes gain (bench.py).
   const bool serial = ctx->opt_prove_serial != 0;
-  // fixed-base tables apply when the MSM covers the whole array the table was built from
   std::thread tA = guarded(0, [&] {
     if (stg && stg->prep_A) stg->prep_A();
-    const MsmTable* useA = (zk->tA && zk->qA.lo == 0 && zk->qA.cnt == zk->qA.res) ? zk->tA : nullptr;
-    const char* pA = reinterpret_cast<const char*>(zk->qA.g1) + zk->qA.lo * 64;
+    const StageView vA = stage_view(zk, kStageA);
     if (!zk->d_witness || !zk->qA.g1 || !zk->qA.scalars) throw ProverError(PROVER_ERROR, "internal: A stage started before its inputs");
     msm_set_density_hint(with_density(1));
     gather(1, zk->qA);
-    msm_run_g1(ctx, 1, pA, zk->qA.scalars, zk->qA.cnt, outA, msm_ms[1], useA);
+    msm_run_g1(ctx, 1, vA.bases, zk->qA.scalars, vA.n, outA, msm_ms[1], vA.table);
   });
   if (serial) tA.join();
   // (a B query beyond the 32-bit entry index of one sort cannot share it: two chunked MSMs instead)
@@ -1061,15 +1144,12 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
   float sort_b_ms = 0;   // the shared sort of the B query (host clock: the call returns with its stream synchronised)
   std::thread tB1 = guarded(1, [&] {
     MsmSorted* sr = nullptr;
-    const char* pB1 = nullptr;
+    StageView vB1;
     try {
       if (stg && stg->prep_B) stg->prep_B();
-      const bool useB = zk->tB1 && zk->tB2 && zk->qB.lo == 0 && zk->qB.cnt == zk->qB.res;
-      share_b = zk->qB.cnt <= sort_limit;
-      uint64_t tb_info[4] = {0, 0, 0, 0};
-      if (useB) msm_table_info(zk->tB1, tb_info);
-      table_c_b = useB && share_b ? (int)tb_info[1] : 0;
-      pB1 = reinterpret_cast<const char*>(zk->qB.g1) + zk->qB.lo * 64;
+      vB1 = stage_view(zk, kStageB1);
+      share_b = vB1.n <= sort_limit;
+      table_c_b = share_b ? vB1.table_c : 0;
       if (!zk->d_witness || !zk->qB.g1 || !zk->qB.g2 || !zk->qB.scalars)
         throw ProverError(PROVER_ERROR, "internal: B stage started before its inputs");
       msm_set_density_hint(with_density(2));
@@ -1092,33 +1172,32 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
       sorted_promise.set_exception(std::current_exception());
       throw;
     }
-    if (share_b) msm_accum_g1(ctx, 2, sr, true, table_c_b ? msm_table_data(zk->tB1) : pB1, outB1, msm_ms[2]);
-    else msm_run_g1(ctx, 2, pB1, zk->qB.scalars, zk->qB.cnt, outB1, msm_ms[2]);
+    if (share_b) msm_accum_g1(ctx, 2, sr, true, table_c_b ? msm_table_data(vB1.table) : vB1.bases, outB1, msm_ms[2]);
+    else msm_run_g1(ctx, 2, vB1.bases, zk->qB.scalars, vB1.n, outB1, msm_ms[2]);
     if (share_b) msm_ms[2][0] += sort_b_ms;
   });
   if (serial) tB1.join();
   std::thread tB2 = guarded(2, [&] {
     const MsmSorted* sr = sorted_ready.get();
-    const char* pB2 = reinterpret_cast<const char*>(zk->qB.g2) + zk->qB.lo * 128;
+    const StageView vB2 = stage_view(zk, kStageB2);
     bool shared = share_b;
     if (shared) {
       try {
-        msm_accum_g2(ctx, 3, sr, false, table_c_b ? msm_table_data(zk->tB2) : pB2, outB2, msm_ms[3]);
+        msm_accum_g2(ctx, 3, sr, false, table_c_b ? msm_table_data(vB2.table) : vB2.bases, outB2, msm_ms[3]);
       } catch (const OomError& e) {   // the G2 buckets of the whole query did not fit beside the rest: own sort, in pieces
         if (!ctx->shrink_after_oom(3, zk->qB.cnt)) throw;
         if (getenv("ZKPOA_VERBOSE")) fprintf(stderr, "zkpoa:   B2: %s; sorting its own pieces\n", e.what());
         shared = false;
       }
     }
-    if (!shared) msm_run_g2(ctx, 3, pB2, zk->qB.scalars, zk->qB.cnt, outB2, msm_ms[3]);
+    if (!shared) msm_run_g2(ctx, 3, vB2.bases, zk->qB.scalars, vB2.n, outB2, msm_ms[3]);
   });
   if (serial) tB2.join();
   std::thread tC = guarded(3, [&] {
     if (stg && stg->prep_C) stg->prep_C();
-    const MsmTable* useC = (zk->tC && zk->clo == zk->cbase && !split_c_partial(zk)) ? zk->tC : nullptr;
-    const char* pC = reinterpret_cast<const char*>(zk->dC) + (zk->clo - zk->cbase) * 64;
-    const char* witC = reinterpret_cast<const char*>(zk->d_witness) + ((uint64_t)zk->nPublic + 1 + zk->clo) * 32;
-    if (!zk->d_witness || (zk->ccnt && !zk->dC)) throw ProverError(PROVER_ERROR, "internal: C stage started before its inputs");
+    const StageView vC = stage_view(zk, kStageC);
+    const char* witC = reinterpret_cast<const char*>(zk->d_witness) + ((uint64_t)zk->nPublic + 1 + vC.scalar_off) * 32;
+    if (!zk->d_witness || (vC.n && !vC.bases)) throw ProverError(PROVER_ERROR, "internal: C stage started before its inputs");
     if (zk->bc_log) {   // block-cyclic shard: the scalars of this rank's blocks, gathered in the order of its points
       if (zk->ccnt)
         hipLaunchKernelGGL(gather_bc32_kernel, dim3((uint32_t)((zk->ccnt * 2 + 255) / 256)), dim3(256), 0,
@@ -1128,7 +1207,7 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
       witC = reinterpret_cast<const char*>(zk->d_cscal);
     }
     msm_set_density_hint(with_density(4));
-    msm_run_g1(ctx, 4, pC, witC, zk->ccnt, outC, msm_ms[4], useC);
+    msm_run_g1(ctx, 4, vC.bases, witC, vC.n, outC, msm_ms[4], vC.table);
   });
   if (serial) tC.join();
 
@@ -1148,19 +1227,12 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
               zk->power, zk->d_abc);
     ZK_HIP(hipEventRecord(ctx->ev_b[5], l0.stream));
     if (stg && stg->prep_H) stg->prep_H();
-    const MsmTable* useH = split ? (zk->tH && zk->tH_cyclic ? zk->tH : nullptr)
-                                 : ((zk->tH && !zk->tH_cyclic && zk->hlo == zk->hbase && !split_h_partial(zk)) ? zk->tH : nullptr);
-    const char* pH = split ? reinterpret_cast<const char*>(zk->dHs)
-                           : reinterpret_cast<const char*>(zk->dH) + (zk->hlo - zk->hbase) * 64;
-    if ((split ? (zk->dHs == nullptr) : (zk->hcnt && zk->dH == nullptr)))
-      throw ProverError(PROVER_ERROR, "internal: H stage started before its inputs");
-    if (split) {
-      // the three stages left this rank's H scalars (odd-coset indices = rank mod G) in d_abc[0 .. n/G)
-      msm_run_g1(ctx, 0, pH, zk->d_abc, zk->domain >> zk->split_log, outH, msm_ms[0], useH);
-      zk->h_ready = false;
-    } else {
-      msm_run_g1(ctx, 0, pH, reinterpret_cast<const char*>(zk->d_abc) + zk->hlo * 32, zk->hcnt, outH, msm_ms[0], useH);
-    }
+    const StageView vH = stage_view(zk, kStageH);
+    if (vH.n && !vH.bases) throw ProverError(PROVER_ERROR, "internal: H stage started before its inputs");
+    // (a split handle: the three stages left this rank's H scalars, odd-coset indices = rank mod G, in d_abc[0 .. n/G))
+    msm_run_g1(ctx, 0, vH.bases, reinterpret_cast<const char*>(zk->d_abc) + vH.scalar_off * 32, vH.n, outH, msm_ms[0],
+               vH.table);
+    if (split) zk->h_ready = false;
     ZK_HIP(hipEventElapsedTime(&ctx->ms[3], ctx->ev_a[5], ctx->ev_b[5]));
     msm_read_back(l0, zk->d_flag, 4);   // lane 0 is idle (its MSM has returned): the flag through its pinned buffer
     witness_bad = *reinterpret_cast<const uint32_t*>(l0.pinned);
@@ -1194,31 +1266,27 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
 
 // header: alpha1(64) beta1(64) beta2(128) delta1(64) delta2(128); sums: A B1 B2 C H summed over all shards.
 // Randomised assembly (groth16_prove.js tail). Host only.
-void prove_assemble(const uint8_t header[448], const uint8_t sums[384], const uint8_t* r_le, const uint8_t* s_le,
+void prove_assemble(const HeaderPoints& h, const uint8_t sums[384], const uint8_t* r_le, const uint8_t* s_le,
                     uint8_t proof_points[256]) {
   uint8_t rb[32], sb[32];
   if (r_le) memcpy(rb, r_le, 32); else random_scalar(rb);
   if (s_le) memcpy(sb, s_le, 32); else random_scalar(sb);
-  Affine<HFq> alpha1 = h_affine_from_bytes<HFq>(header), beta1 = h_affine_from_bytes<HFq>(header + 64);
-  Affine<HFq2> beta2 = h_affine_from_bytes<HFq2>(header + 128);
-  Affine<HFq> delta1 = h_affine_from_bytes<HFq>(header + 256);
-  Affine<HFq2> delta2 = h_affine_from_bytes<HFq2>(header + 320);
   uint64_t rk[4], sk[4], nrs[4];
   memcpy(rk, rb, 32);
   memcpy(sk, sb, 32);
   HFr rs = hfr_from_le(rb).to_mont() * hfr_from_le(sb).to_mont();
   rs.neg().from_mont().to_bytes(nrs);
 
-  XYZZ<HFq> d1 = XYZZ<HFq>::from_affine(delta1);
-  XYZZ<HFq2> d2 = XYZZ<HFq2>::from_affine(delta2);
+  XYZZ<HFq> d1 = XYZZ<HFq>::from_affine(h.delta1);
+  XYZZ<HFq2> d2 = XYZZ<HFq2>::from_affine(h.delta2);
   XYZZ<HFq> pi_a = XYZZ<HFq>::from_affine(h_affine_from_bytes<HFq>(sums));
-  xyzz_add_affine(pi_a, alpha1, false);
+  xyzz_add_affine(pi_a, h.alpha1, false);
   xyzz_add(pi_a, h_mul(d1, rk));
   XYZZ<HFq2> pi_b = XYZZ<HFq2>::from_affine(h_affine_from_bytes<HFq2>(sums + 128));
-  xyzz_add_affine(pi_b, beta2, false);
+  xyzz_add_affine(pi_b, h.beta2, false);
   xyzz_add(pi_b, h_mul(d2, sk));
   XYZZ<HFq> pib1 = XYZZ<HFq>::from_affine(h_affine_from_bytes<HFq>(sums + 64));
-  xyzz_add_affine(pib1, beta1, false);
+  xyzz_add_affine(pib1, h.beta1, false);
   xyzz_add(pib1, h_mul(d1, sk));
   XYZZ<HFq> pi_c = XYZZ<HFq>::from_affine(h_affine_from_bytes<HFq>(sums + 256));
   xyzz_add_affine(pi_c, h_affine_from_bytes<HFq>(sums + 320), false);
@@ -1232,11 +1300,11 @@ void prove_assemble(const uint8_t header[448], const uint8_t sums[384], const ui
 }
 
 void zkey_header_bytes(const zkpoa_zkey* zk, uint8_t out[448]) {
-  h_affine_to_bytes<HFq>(zk->alpha1, out);
-  h_affine_to_bytes<HFq>(zk->beta1, out + 64);
-  h_affine_to_bytes<HFq2>(zk->beta2, out + 128);
-  h_affine_to_bytes<HFq>(zk->delta1, out + 256);
-  h_affine_to_bytes<HFq2>(zk->delta2, out + 320);
+  h_affine_to_bytes<HFq>(zk->hdr.alpha1, out);
+  h_affine_to_bytes<HFq>(zk->hdr.beta1, out + 64);
+  h_affine_to_bytes<HFq2>(zk->hdr.beta2, out + 128);
+  h_affine_to_bytes<HFq>(zk->hdr.delta1, out + 256);
+  h_affine_to_bytes<HFq2>(zk->hdr.delta2, out + 320);
 }
 
 bool is_full_key(const zkpoa_zkey* zk) {
@@ -1247,9 +1315,7 @@ bool is_full_key(const zkpoa_zkey* zk) {
 // the partial sums of a whole key -> proof points; ctx->ms[5] <- the prove time, counted from t0
 void assemble_proof(zkpoa_context* ctx, const zkpoa_zkey* zk, const uint8_t parts[384], const uint8_t* r_le,
                     const uint8_t* s_le, std::chrono::steady_clock::time_point t0, uint8_t proof_points[256]) {
-  uint8_t header[448];
-  zkey_header_bytes(zk, header);
-  prove_assemble(header, parts, r_le, s_le, proof_points);
+  prove_assemble(zk->hdr, parts, r_le, s_le, proof_points);
   ctx->ms[5] = (float)ms_since(t0);
 }
 
@@ -1348,7 +1414,7 @@ zkpoa_zkey* load_prove_staged(zkpoa_context* ctx, const uint8_t* buf, uint64_t s
   ZkeySections zs;
   std::unique_ptr<zkpoa_zkey> zk = zkey_parse(buf, size, zs);
   check_witness_len(w, zk.get());
-  zk->set_full();
+  shard_init(zk.get(), 0, 1, false, 0);   // the whole key
   const uint64_t m = zk->nVars, n = zk->domain, nC = m - zk->nPublic - 1;
   {
     // What the overlapped form holds at its peak: the sections AND the compacted copies of the A / B queries (a hipFree
@@ -1529,27 +1595,27 @@ zkpoa_zkey* load_prove_staged(zkpoa_context* ctx, const uint8_t* buf, uint64_t s
 }  // namespace
 
 // ---- C ABI -------------------------------------------------------------------------------------------
-#define ZK_PROVER_CATCH(ctx)          \
-  catch (const ProverError& e) {      \
-    (ctx)->last_error = e.what();     \
-    return e.code;                    \
-  }                                   \
-  catch (const std::exception& e) {   \
-    (ctx)->last_error = e.what();     \
-    return PROVER_ERROR;              \
+// The frame of an entry point that works on ctx's device: body() runs there; what it throws becomes the return code
+// and ctx's last_error. Null arguments are the entry point's own business, before the call.
+template <class Body>
+static int abi_call(zkpoa_context* ctx, Body&& body) {
+  try {
+    ZK_HIP(hipSetDevice(ctx->dev.device));
+    body();
+  } catch (const std::exception& e) {
+    ctx->last_error = e.what();
+    const ProverError* pe = dynamic_cast<const ProverError*>(&e);
+    return pe ? pe->code : PROVER_ERROR;
   }
+  return PROVER_OK;
+}
 
 // what the four loaders from a zkey image share; `shard` = the entry point's own arguments to zkey_load_impl
 template <class... Shard>
 static int zkey_load_abi(zkpoa_context* ctx, const void* zkey_buffer, unsigned long zkey_size, zkpoa_zkey** out, Shard... shard) {
   if (!ctx || !out || !zkey_buffer) return PROVER_ERROR;
   *out = nullptr;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
-    *out = zkey_load_impl(ctx, reinterpret_cast<const uint8_t*>(zkey_buffer), zkey_size, shard...);
-  }
-  ZK_PROVER_CATCH(ctx)
-  return PROVER_OK;
+  return abi_call(ctx, [&] { *out = zkey_load_impl(ctx, static_cast<const uint8_t*>(zkey_buffer), zkey_size, shard...); });
 }
 
 extern "C" int zkpoa_zkey_load(zkpoa_context* ctx, const void* zkey_buffer, unsigned long zkey_size, zkpoa_zkey** out) {
@@ -1572,10 +1638,15 @@ extern "C" int zkpoa_zkey_load_shard_ex(zkpoa_context* ctx, const void* zkey_buf
                        ZKPOA_SHARD_BLOCK_LOG(flags));
 }
 
+// Can the handle be re-pointed at another shard? Only when every section is resident from its first item in file
+// order (loaded whole, not block-cyclic) and the CSR holds every row.
+static bool resident_unsharded(const zkpoa_zkey* zk) {
+  return !(zk->wbase || zk->cbase || zk->hbase || zk->csr_local || !zk->dH || zk->bc_log);
+}
+
 extern "C" int zkpoa_zkey_set_shard(zkpoa_zkey* zkey, uint64_t rank, uint64_t world) {
   if (!zkey || world == 0 || rank >= world) return PROVER_ERROR;
-  if (zkey->wbase || zkey->cbase || zkey->hbase || zkey->csr_local || !zkey->dH || zkey->bc_log)
-    return PROVER_ERROR;  // only a fully resident key can be re-sharded
+  if (!resident_unsharded(zkey)) return PROVER_ERROR;
   zkey->set_shard(rank, world);
   zkey->split_world = zkey->split_rank = zkey->split_log = 0;
   zkey->h_ready = false;
@@ -1589,21 +1660,12 @@ extern "C" int zkpoa_zkey_set_shard(zkpoa_zkey* zkey, uint64_t rank, uint64_t wo
 
 extern "C" int zkpoa_zkey_set_shard_split(zkpoa_context* ctx, zkpoa_zkey* zkey, uint64_t rank, uint64_t world) {
   if (!ctx || !zkey) return PROVER_ERROR;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
-    if (zkey->wbase || zkey->cbase || zkey->hbase || zkey->csr_local || !zkey->dH || zkey->bc_log)
-      throw ProverError(PROVER_ERROR, "only a fully resident key can be re-sharded");
+  return abi_call(ctx, [&] {
+    if (!resident_unsharded(zkey)) throw ProverError(PROVER_ERROR, "only a fully resident key can be re-sharded");
     check_split(zkey, rank, world);
     hipStream_t st = ctx->dev.lanes[0].stream;
-    const uint64_t cnt = zkey->domain / world;
-    if (zkey->tH_cyclic) {   // built from the cyclic shard that is replaced now
-      uint64_t info[4];
-      msm_table_info(zkey->tH, info);
-      zkey->table_bytes -= info[3] < zkey->table_bytes ? info[3] : zkey->table_bytes;
-      msm_table_release(zkey->tH);
-      zkey->tH = nullptr;
-      zkey->tH_cyclic = false;
-    }
+    const uint64_t cnt = zkpoa_zkey::split_h_count(zkey->domain, world);
+    zkey->release_cyclic_h_table();
     if (zkey->dHs) {
       ZK_HIP(hipFree(zkey->dHs));
       zkey->dHs = nullptr;
@@ -1617,32 +1679,34 @@ extern "C" int zkpoa_zkey_set_shard_split(zkpoa_context* ctx, zkpoa_zkey* zkey, 
     ntt_prepare(ctx, st, zkey->power - zkey->split_log);
     ZK_HIP(hipStreamSynchronize(st));
     ZK_HIP(hipGetLastError());
-  }
-  ZK_PROVER_CATCH(ctx)
-  return PROVER_OK;
+  });
+}
+
+// A .wtns image in host memory, parsed and checked against the key and the caller's room for the public signals:
+// what zkpoa_witness_load and zkpoa_prove_partials do before anything moves.
+static WtnsView host_witness(const zkpoa_zkey* zk, const void* wtns_buffer, unsigned long wtns_size, const uint8_t* public_le,
+                             unsigned long public_capacity) {
+  WtnsView w = parse_wtns(reinterpret_cast<const uint8_t*>(wtns_buffer), wtns_size);
+  check_witness_len(w, zk);
+  if (public_le && public_capacity < (unsigned long)zk->nPublic * 32)
+    throw ProverError(PROVER_ERROR_SHORT_BUFFER, "public buffer too small");
+  return w;
 }
 
 extern "C" int zkpoa_witness_load(zkpoa_context* ctx, const zkpoa_zkey* zkey, const void* wtns_buffer,
                                   unsigned long wtns_size, uint8_t* public_le, unsigned long public_capacity) {
   if (!ctx || !zkey || !wtns_buffer) return PROVER_ERROR;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
-    WtnsView w = parse_wtns(reinterpret_cast<const uint8_t*>(wtns_buffer), wtns_size);
-    check_witness_len(w, zkey);
-    if (public_le && public_capacity < (unsigned long)zkey->nPublic * 32)
-      throw ProverError(PROVER_ERROR_SHORT_BUFFER, "public buffer too small");
-    ctx->uploader.upload(zkey->d_witness, w.values, (size_t)w.n * 32, ctx->dev.device, ctx->dev.lanes[0].stream);
+  return abi_call(ctx, [&] {
+    const WtnsView w = host_witness(zkey, wtns_buffer, wtns_size, public_le, public_capacity);
+    w.upload(ctx, zkey->d_witness, 0, w.n, ctx->dev.lanes[0].stream);
     zkey->h_ready = false;
     if (public_le) memcpy(public_le, w.values + 32, (size_t)zkey->nPublic * 32);
-  }
-  ZK_PROVER_CATCH(ctx)
-  return PROVER_OK;
+  });
 }
 
 extern "C" int zkpoa_split_stage1(zkpoa_context* ctx, const zkpoa_zkey* zkey, const void* d_witness, void* d_exchange) {
   if (!ctx || !zkey || !d_exchange) return PROVER_ERROR;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
+  return abi_call(ctx, [&] {
     if (zkey->split_world < 2) throw ProverError(PROVER_ERROR, "split chain: the key handle is not a split shard");
     hipStream_t st = ctx->dev.lanes[0].stream;
     if (d_witness && d_witness != zkey->d_witness) {
@@ -1652,31 +1716,23 @@ extern "C" int zkpoa_split_stage1(zkpoa_context* ctx, const zkpoa_zkey* zkey, co
       ctx->ev_witness_set = true;
     }
     split_stage1(ctx, zkey, d_exchange);
-  }
-  ZK_PROVER_CATCH(ctx)
-  return PROVER_OK;
+  });
 }
 
 extern "C" int zkpoa_split_stage2(zkpoa_context* ctx, const zkpoa_zkey* zkey, const void* d_received, void* d_exchange) {
   if (!ctx || !zkey || !d_received || !d_exchange || d_received == d_exchange) return PROVER_ERROR;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
+  return abi_call(ctx, [&] {
     if (zkey->split_world < 2) throw ProverError(PROVER_ERROR, "split chain: the key handle is not a split shard");
     split_stage2(ctx, zkey, d_received, d_exchange);
-  }
-  ZK_PROVER_CATCH(ctx)
-  return PROVER_OK;
+  });
 }
 
 extern "C" int zkpoa_split_stage3(zkpoa_context* ctx, const zkpoa_zkey* zkey, void* d_received) {
   if (!ctx || !zkey || !d_received) return PROVER_ERROR;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
+  return abi_call(ctx, [&] {
     if (zkey->split_world < 2) throw ProverError(PROVER_ERROR, "split chain: the key handle is not a split shard");
     split_stage3(ctx, zkey, d_received);
-  }
-  ZK_PROVER_CATCH(ctx)
-  return PROVER_OK;
+  });
 }
 
 extern "C" void* zkpoa_context_stream(zkpoa_context* ctx, int lane) {
@@ -1692,13 +1748,10 @@ extern "C" void* zkpoa_context_stream(zkpoa_context* ctx, int lane) {
 
 extern "C" int zkpoa_context_synchronize(zkpoa_context* ctx) {
   if (!ctx) return PROVER_ERROR;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
+  return abi_call(ctx, [&] {
     ZK_HIP(hipStreamSynchronize(ctx->dev.lanes[0].stream));
     ZK_HIP(hipGetLastError());
-  }
-  ZK_PROVER_CATCH(ctx)
-  return PROVER_OK;
+  });
 }
 
 extern "C" int zkpoa_zkey_header(const zkpoa_zkey* zkey, uint8_t header_points[448]) {
@@ -1711,44 +1764,35 @@ extern "C" int zkpoa_prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zkey, 
                                     unsigned long wtns_size, uint8_t partials[384], uint8_t* public_le,
                                     unsigned long public_capacity) {
   if (!ctx || !zkey || !wtns_buffer || !partials) return PROVER_ERROR;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
-    WtnsView w = parse_wtns(reinterpret_cast<const uint8_t*>(wtns_buffer), wtns_size);
-    check_witness_len(w, zkey);
-    if (public_le && public_capacity < (unsigned long)zkey->nPublic * 32)
-      throw ProverError(PROVER_ERROR_SHORT_BUFFER, "public buffer too small");
+  return abi_call(ctx, [&] {
+    const WtnsView w = host_witness(zkey, wtns_buffer, wtns_size, public_le, public_capacity);
     if (zkey->split_world > 1)
       throw ProverError(PROVER_ERROR, "split chain: use zkpoa_witness_load, zkpoa_split_stage1/2/3, then "
                                       "zkpoa_prove_partials_device with a NULL witness");
-    ctx->uploader.upload(zkey->d_witness, w.values, (size_t)w.n * 32, ctx->dev.device, ctx->dev.lanes[0].stream);
+    w.upload(ctx, zkey->d_witness, 0, w.n, ctx->dev.lanes[0].stream);
     prove_partials(ctx, zkey, partials);
     if (public_le) memcpy(public_le, w.values + 32, (size_t)zkey->nPublic * 32);
-  }
-  ZK_PROVER_CATCH(ctx)
-  return PROVER_OK;
+  });
 }
 
 extern "C" int zkpoa_prove_partials_device(zkpoa_context* ctx, const zkpoa_zkey* zkey, const void* d_witness,
                                            uint8_t partials[384]) {
   if (!ctx || !zkey || !partials) return PROVER_ERROR;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
+  return abi_call(ctx, [&] {
     hipStream_t st = ctx->dev.lanes[0].stream;
     if (d_witness && d_witness != zkey->d_witness) {
       ZK_HIP(hipMemcpyAsync(zkey->d_witness, d_witness, (size_t)zkey->nVars * 32, hipMemcpyDeviceToDevice, st));
       ZK_HIP(hipStreamSynchronize(st));
     }
     prove_partials(ctx, zkey, partials);
-  }
-  ZK_PROVER_CATCH(ctx)
-  return PROVER_OK;
+  });
 }
 
 extern "C" int zkpoa_prove_assemble(const uint8_t header_points[448], const uint8_t partial_sums[384],
                                     const uint8_t* r_le, const uint8_t* s_le, uint8_t proof_points[256]) {
   if (!header_points || !partial_sums || !proof_points) return PROVER_ERROR;
   try {
-    prove_assemble(header_points, partial_sums, r_le, s_le, proof_points);
+    prove_assemble(header_points_from_bytes(header_points), partial_sums, r_le, s_le, proof_points);
   } catch (const std::exception&) {
     return PROVER_ERROR;
   }
@@ -1778,90 +1822,57 @@ extern "C" int zkpoa_prove(zkpoa_context* ctx, const zkpoa_zkey* zkey, const voi
                            const uint8_t* r_le, const uint8_t* s_le, uint8_t proof_points[256], uint8_t* public_le,
                            unsigned long public_capacity) {
   if (!ctx || !zkey || !wtns_buffer || !proof_points) return PROVER_ERROR;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
+  return abi_call(ctx, [&] {
     uint8_t dummy[1];
     prove_impl(ctx, zkey, WtnsSrc{reinterpret_cast<const uint8_t*>(wtns_buffer), wtns_size, -1}, r_le, s_le, proof_points,
                public_le ? public_le : dummy, public_le ? public_capacity : (zkey->nPublic ? 0 : 1));
-  }
-  ZK_PROVER_CATCH(ctx)
-  return PROVER_OK;
+  });
 }
 
 // Key (or one rank's shard of it) from sections already in HBM. world == 1: the whole key. world > 1: the point
 // buffers hold only this rank's index ranges (zkpoa_zkey::split: the ranges zkpoa_zkey_load_shard uploads); with
 // `split`, d_H is the cyclic shard H[t * world + rank] and the records are those of the constraints
 // c = rank (mod world) (records of other constraints are ignored).
-static zkpoa_zkey* zkey_load_device_impl(zkpoa_context* ctx, uint64_t n_vars, uint64_t n_public, unsigned log_domain,
-                                         uint64_t rank, uint64_t world, bool split, uint32_t bc_log, const void* d_A, const void* d_B1,
-                                         const void* d_B2, const void* d_C, const void* d_H,
-                                         const void* d_coef_records, uint64_t n_coefs, const uint8_t header_points[448]) {
-  std::unique_ptr<zkpoa_zkey> zk(new zkpoa_zkey());
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
-    if (log_domain > 28 || n_vars == 0 || n_vars > (1ull << 28) || n_public + 1 > n_vars || n_coefs > 0xffffffffull)
-      throw ProverError(PROVER_ERROR, "zkey_load_device: size out of range");
-    if (world == 0 || rank >= world) throw ProverError(PROVER_ERROR, "zkey shard: rank/world out of range");
-    zk->nVars = (uint32_t)n_vars;
-    zk->nPublic = (uint32_t)n_public;
-    zk->power = log_domain;
-    zk->domain = 1u << log_domain;
-    zk->nCoefs = n_coefs;
-    zk->owns_points = false;
-    zk->dA = const_cast<void*>(d_A);
-    zk->dB1 = const_cast<void*>(d_B1);
-    zk->dB2 = const_cast<void*>(d_B2);
-    zk->dC = const_cast<void*>(d_C);
-    zk->alpha1 = h_affine_from_bytes<HFq>(header_points);
-    zk->beta1 = h_affine_from_bytes<HFq>(header_points + 64);
-    zk->beta2 = h_affine_from_bytes<HFq2>(header_points + 128);
-    zk->delta1 = h_affine_from_bytes<HFq>(header_points + 256);
-    zk->delta2 = h_affine_from_bytes<HFq2>(header_points + 320);
-    zk->set_shard(rank, world);   // world == 1: the whole key
-    zk->wbase = zk->wlo;
-    zk->cbase = zk->clo;
-    zk->hbase = zk->hlo;
-    if (split) {
-      check_split(zk.get(), rank, world);
-      set_split(zk.get(), rank, world);
-      // the handle owns its cyclic H shard (release() frees it): a copy of the caller's, device to device
-      const size_t bytes = (size_t)(zk->domain / world) * 64;
-      ZK_HIP(hipMalloc(&zk->dHs, bytes));
-      ZK_HIP(hipMemcpy(zk->dHs, d_H, bytes, hipMemcpyDeviceToDevice));
-      zk->hlo = zk->hbase = 0;
-      zk->hcnt = 0;   // no contiguous H range on this handle
-    } else {
-      zk->dH = const_cast<void*>(d_H);
-    }
-    set_block_cyclic(zk.get(), rank, world, bc_log);
-    if (zk->bc_log) ZK_HIP(hipMalloc(&zk->d_cscal, zk->ccnt ? zk->ccnt * 32 : 1));
-    queries_compact(ctx, zk.get(), zk->wcnt);
-    build_csr(ctx, zk.get(), d_coef_records, split);
-    ntt_prepare(ctx, ctx->dev.lanes[0].stream, zk->power);
-    if (split) ntt_prepare(ctx, ctx->dev.lanes[0].stream, zk->power - zk->split_log);
-    ZK_HIP(hipStreamSynchronize(ctx->dev.lanes[0].stream));
-  } catch (...) {
-    zk->release();
-    throw;
-  }
-  return zk.release();
-}
-
 extern "C" int zkpoa_zkey_load_device_shard(zkpoa_context* ctx, uint64_t n_vars, uint64_t n_public, unsigned log_domain,
-                                            uint64_t rank, uint64_t world, int split, const void* d_A,
+                                            uint64_t rank, uint64_t world, int flags, const void* d_A,
                                             const void* d_B1, const void* d_B2, const void* d_C, const void* d_H,
                                             const void* d_coef_records, uint64_t n_coefs,
                                             const uint8_t header_points[448], zkpoa_zkey** out) {
   if (!ctx || !out || !header_points) return PROVER_ERROR;
   *out = nullptr;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
-    *out = zkey_load_device_impl(ctx, n_vars, n_public, log_domain, rank, world, (split & ZKPOA_SHARD_SPLIT_CHAIN) != 0,
-                                 ZKPOA_SHARD_BLOCK_LOG(split), d_A, d_B1, d_B2, d_C, d_H,
-                                 d_coef_records, n_coefs, header_points);
-  }
-  ZK_PROVER_CATCH(ctx)
-  return PROVER_OK;
+  const bool split = (flags & ZKPOA_SHARD_SPLIT_CHAIN) != 0;
+  return abi_call(ctx, [&] {
+    std::unique_ptr<zkpoa_zkey> zk(new zkpoa_zkey());
+    try {
+      if (log_domain > 28 || n_vars == 0 || n_vars > (1ull << 28) || n_public + 1 > n_vars || n_coefs > 0xffffffffull)
+        throw ProverError(PROVER_ERROR, "zkey_load_device: size out of range");
+      zk->nVars = (uint32_t)n_vars;
+      zk->nPublic = (uint32_t)n_public;
+      zk->power = log_domain;
+      zk->domain = 1u << log_domain;
+      zk->nCoefs = n_coefs;
+      zk->owns_points = false;
+      zk->dA = const_cast<void*>(d_A);
+      zk->dB1 = const_cast<void*>(d_B1);
+      zk->dB2 = const_cast<void*>(d_B2);
+      zk->dC = const_cast<void*>(d_C);
+      zk->hdr = header_points_from_bytes(header_points);
+      shard_init(zk.get(), rank, world, split, ZKPOA_SHARD_BLOCK_LOG(flags));
+      if (split) {
+        // the handle owns its cyclic H shard (release() frees it): a copy of the caller's, device to device
+        const size_t bytes = (size_t)zk->h_scalar_count() * 64;
+        ZK_HIP(hipMalloc(&zk->dHs, bytes));
+        ZK_HIP(hipMemcpy(zk->dHs, d_H, bytes, hipMemcpyDeviceToDevice));
+      } else {
+        zk->dH = const_cast<void*>(d_H);
+      }
+      finish_load(ctx, zk.get(), d_coef_records, /*recs_on_host=*/false, split, LoadPhases{/*verbose=*/false});
+    } catch (...) {
+      zk->release();
+      throw;
+    }
+    *out = zk.release();
+  });
 }
 
 extern "C" int zkpoa_zkey_load_device(zkpoa_context* ctx, uint64_t n_vars, uint64_t n_public, unsigned log_domain,
@@ -1876,8 +1887,7 @@ extern "C" int zkpoa_prove_device(zkpoa_context* ctx, const zkpoa_zkey* zkey, co
                                   const uint8_t* r_le, const uint8_t* s_le, uint8_t proof_points[256],
                                   uint8_t* public_le, unsigned long public_capacity) {
   if (!ctx || !zkey || !d_witness || !proof_points) return PROVER_ERROR;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
+  return abi_call(ctx, [&] {
     if (public_le && public_capacity < (unsigned long)zkey->nPublic * 32)
       throw ProverError(PROVER_ERROR_SHORT_BUFFER, "public buffer too small");
     hipStream_t st = ctx->dev.lanes[0].stream;
@@ -1895,34 +1905,26 @@ extern "C" int zkpoa_prove_device(zkpoa_context* ctx, const zkpoa_zkey* zkey, co
                          hipMemcpyDeviceToHost));
       selfcheck(ctx, zkey, proof_points, pub.data());
     }
-  }
-  ZK_PROVER_CATCH(ctx)
-  return PROVER_OK;
+  });
 }
 
 extern "C" int zkpoa_zkey_precompute(zkpoa_context* ctx, zkpoa_zkey* zkey, uint64_t budget_bytes, uint64_t* used_bytes) {
   if (!ctx || !zkey) return PROVER_ERROR;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
+  return abi_call(ctx, [&] {
     uint64_t used = zkey_precompute(ctx, zkey, budget_bytes);
     if (used_bytes) *used_bytes = used;
-  }
-  ZK_PROVER_CATCH(ctx)
-  return PROVER_OK;
+  });
 }
 
 extern "C" int zkpoa_zkey_read_h_scalars(zkpoa_context* ctx, const zkpoa_zkey* zkey, void* out, unsigned long capacity) {
   if (!ctx || !zkey || !out) return PROVER_ERROR;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
-    const uint64_t cnt = zkey->split_world > 1 ? (uint64_t)zkey->domain >> zkey->split_log : zkey->domain;
+  return abi_call(ctx, [&] {
+    const uint64_t cnt = zkey->h_scalar_count();
     if (capacity < cnt * 32) throw ProverError(PROVER_ERROR_SHORT_BUFFER, "h-scalar buffer too small");
     if (!zkey->d_abc) throw ProverError(PROVER_ERROR, "no H scalars on this handle");
     ZK_HIP(hipDeviceSynchronize());
     ZK_HIP(hipMemcpy(out, zkey->d_abc, cnt * 32, hipMemcpyDeviceToHost));
-  }
-  ZK_PROVER_CATCH(ctx)
-  return PROVER_OK;
+  });
 }
 
 extern "C" int zkpoa_zkey_vkey(const zkpoa_zkey* zkey, uint8_t* buffer, unsigned long* size) {
@@ -1952,8 +1954,7 @@ extern "C" int zkpoa_public_to_json(const uint8_t* public_le, unsigned long n_pu
 extern "C" int zkpoa_h_scalars(zkpoa_context* ctx, const void* coeffs, unsigned long coeffs_size, const void* witness,
                                uint64_t n_vars, unsigned log_domain, void* out) {
   if (!ctx || !coeffs || !witness || !out) return PROVER_ERROR;
-  try {
-    ZK_HIP(hipSetDevice(ctx->dev.device));
+  return abi_call(ctx, [&] {
     if (log_domain > 28) throw ProverError(PROVER_ERROR, "h_scalars: log_domain > 28");
     const uint8_t* cb = reinterpret_cast<const uint8_t*>(coeffs);
     if (coeffs_size < 4) throw ProverError(PROVER_ERROR, "h_scalars: coefficient payload too short");
@@ -1975,9 +1976,7 @@ extern "C" int zkpoa_h_scalars(zkpoa_context* ctx, const void* coeffs, unsigned 
     ZK_HIP(hipGetLastError());
     ZK_HIP(hipEventElapsedTime(&ctx->ms[3], ctx->ev_a[5], ctx->ev_b[5]));
     ZK_HIP(hipMemcpy(out, abc.p, (size_t)domain * 32, hipMemcpyDeviceToHost));
-  }
-  ZK_PROVER_CATCH(ctx)
-  return PROVER_OK;
+  });
 }
 
 // Test hook (not in the header): the automatic GPU choice of the multi-GPU drop-in for a node of `count` GPUs of which
