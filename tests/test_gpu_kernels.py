@@ -2,12 +2,14 @@
 the oracle (golden vectors from the Python big-int oracle; the C restatement at sizes it finishes in
 seconds; size-independent properties at BASELINE.json's full size 2^20).
 Bar: bit-exact (integer arithmetic)."""
+import functools
+import os
 import random
 
 import numpy as np
 import pytest
 
-from conftest import le, rd
+from conftest import ROOT, le, rd
 from oracle import c_oracle as co
 from oracle.py import bn254 as bn
 from oracle.py import groth16 as g16
@@ -78,24 +80,67 @@ def _rand_scalars(rng, n, dist):
     return b"".join(le(k) for k in out)
 
 
-@pytest.mark.parametrize("n,dist", [(3000, "uniform"), (3000, "witness"), (500, "special"), (20000, "witness")])
-def test_msm_g1_vs_c_oracle(ctx, n, dist):
+@functools.lru_cache(maxsize=None)
+def _g1_oracle_case(n, dist):
+    """(bases, scalars, the C oracle's sum): computed once, shared by the tests that run this case."""
     rng = random.Random(n + len(dist))
     bases = bytearray(co.fixed_base_g1(b"".join(le(rng.randrange(R)) for _ in range(n)), 8))
     for i in range(0, n, 17):                      # infinity bases, as unused wires have in a zkey
         bases[64 * i:64 * i + 64] = bytes(64)
     sc = _rand_scalars(rng, n, dist)
-    assert ctx.msm_g1(bytes(bases), sc, n) == co.msm_g1(bytes(bases), sc, n, 8)
+    return bytes(bases), sc, co.msm_g1(bytes(bases), sc, n, 8)
 
 
-@pytest.mark.parametrize("n,dist", [(700, "uniform"), (2000, "witness")])
-def test_msm_g2_vs_c_oracle(ctx, n, dist):
+@functools.lru_cache(maxsize=None)
+def _g2_oracle_case(n, dist):
     rng = random.Random(n)
     bases = bytearray(co.fixed_base_g2(b"".join(le(rng.randrange(R)) for _ in range(n)), 8))
     for i in range(0, n, 13):
         bases[128 * i:128 * i + 128] = bytes(128)
     sc = _rand_scalars(rng, n, dist)
-    assert ctx.msm_g2(bytes(bases), sc, n) == co.msm_g2(bytes(bases), sc, n, 8)
+    return bytes(bases), sc, co.msm_g2(bytes(bases), sc, n, 8)
+
+
+@pytest.mark.parametrize("n,dist", [(3000, "uniform"), (3000, "witness"), (500, "special"), (20000, "witness")])
+def test_msm_g1_vs_c_oracle(ctx, n, dist):
+    bases, sc, want = _g1_oracle_case(n, dist)
+    assert ctx.msm_g1(bases, sc, n) == want
+
+
+@pytest.mark.parametrize("n,dist", [(700, "uniform"), (2000, "witness")])
+def test_msm_g2_vs_c_oracle(ctx, n, dist):
+    bases, sc, want = _g2_oracle_case(n, dist)
+    assert ctx.msm_g2(bases, sc, n) == want
+
+
+_SCAN3_CHILD = """
+import sys
+sys.path.insert(0, sys.argv[1])
+import __graft_entry__ as entry
+c = entry.load_package().Context(0)
+read = lambda name: open(sys.argv[2] + "/" + name, "rb").read()
+print(c.msm_g1(read("b1"), read("s1"), 3000).hex())
+print(c.msm_g2(read("b2"), read("s2"), 700).hex())
+c.close()
+"""
+
+
+def test_msm_three_launch_scans_vs_c_oracle(ctx, tmp_path):
+    """ZKPOA_SCAN=3 (the A/B switch back to three-launch scans, with the piece-length histogram in a launch of its own)
+    is read once per process: a fresh child, under a time limit of its own, runs the G1 n = 3000 "witness" and the G2
+    n = 700 case of the tests above. Its sums equal the C oracle's and, bit for bit, the default path's in this process."""
+    import subprocess
+    import sys
+    b1, s1, want1 = _g1_oracle_case(3000, "witness")
+    b2, s2, want2 = _g2_oracle_case(700, "uniform")
+    for name, data in (("b1", b1), ("s1", s1), ("b2", b2), ("s2", s2)):
+        (tmp_path / name).write_bytes(data)
+    rc = subprocess.run(["timeout", "-k", "10", "120", sys.executable, "-s", "-c", _SCAN3_CHILD, ROOT, str(tmp_path)],
+                        env=dict(os.environ, ZKPOA_SCAN="3"), capture_output=True, text=True)
+    assert rc.returncode == 0, rc.stderr
+    got1, got2 = (bytes.fromhex(h) for h in rc.stdout.split())
+    assert got1 == want1 and got2 == want2
+    assert got1 == ctx.msm_g1(b1, s1, 3000) and got2 == ctx.msm_g2(b2, s2, 700)
 
 
 def test_msm_repeated_and_opposite_bases(ctx):

@@ -560,6 +560,7 @@ namespace zkpoa {
 // global atomic per (workgroup, length)) gives every wave equal-length pieces and schedules the
 // longest first.
 constexpr uint32_t kMaxPieceLen = 512;
+static_assert(kMaxPieceLen == kMaxPieceLenPlan, "the plan, the scans' LDS histogram and the piece ordering share one bound");
 
 // order[pos] = t with the pieces sorted by descending length, pbkt[t] = the piece's bucket. The histogram of the
 // lengths comes from the scan that produced the piece offsets (ScanPair::hist). Every thread takes kPiecesPerThread
@@ -890,6 +891,145 @@ inline void msm_read_back(Lane& lane, const void* d_src, size_t bytes) {
   lane_check_fault(lane);
 }
 
+// The lane's scans: one launch (scan_pair), or under ZKPOA_SCAN=3 (A/B measurement) the same ScanPair as three-launch
+// scans, with the piece-length histogram -- which those do not carry -- in a launch of its own.
+inline void lane_scan(Lane& lane, const ScanPair& a, uint32_t* block_sums) {
+  if (!scan_three_kernel()) return scan_pair(lane, a);
+  scan_u32(lane.stream, a.in, a.n, a.mode_a, a.K_a, a.out_a, block_sums, a.total_a, a.max_out);
+  if (a.mode_b >= 0) scan_u32(lane.stream, a.in, a.n, a.mode_b, a.K_b, a.out_b, block_sums, a.total_b, nullptr);
+  if (a.hist)
+    hipLaunchKernelGGL(msm_piece_hist_kernel, dim3((a.n + 255) / 256), dim3(256), 0, lane.stream, a.in, a.n, a.hist_K, a.hist);
+}
+
+// ---- workspace layouts: a phase's share of the lane arena is described ONCE -------------------------------------
+// carve() names every region in arena order with its element count, against a taker: Arena (device_ctx.hpp) hands the
+// memory out, ArenaCount only adds up what it would hand out -- what reserve() and the prover's HBM budget are sized with.
+struct ArenaCount {
+  size_t off = 0;
+  template <class T> T* take(size_t count) { return off += (count * sizeof(T) + 255) & ~size_t(255), nullptr; }   // (Arena::take)
+};
+template <class Layout>
+inline size_t msm_layout_bytes(const MsmPlan& p) {
+  ArenaCount count;
+  Layout().carve(count, p);
+  return count.off;
+}
+template <class Layout>
+inline Layout msm_carve(Arena& ws, const MsmPlan& p) {
+  Layout m;
+  const size_t start = ws.off;
+  m.carve(ws, p);   // (one comparison per MSM keeps the two takers honest)
+  if (ws.off - start != msm_layout_bytes<Layout>(p)) throw HipError("msm: internal: workspace layout and its size disagree");
+  return m;
+}
+inline size_t msm_piece_cap(const MsmPlan& p) { return (size_t)p.n * p.W / p.K0 + p.TB + 1; }   // level-0 pieces at most
+
+struct MsmSortLayout {
+  // counts .. len_hist, zero_bytes in all: everything that must start at zero sits in ONE block at the head of the arena
+  // and is cleared by one memset (r03: four, each a launch of its own on a lane whose MSM is ~45 launches)
+  uint32_t* counts = nullptr;                // entries per bucket
+  uint32_t* seg_cnt[kSortMaxPasses] = {};    // per pass but the last: entries per output segment
+  uint32_t* misc = nullptr;   // [0]=T, [1]=max count, [2]=total pieces, [4 + 2l], [5 + 2l] totals of pass l, [8] entry counter
+  uint32_t* len_hist = nullptr;              // piece-length histogram, then its cursors
+  size_t zero_bytes = 0;
+  uint32_t *off0 = nullptr, *po_a = nullptr; // bucket offsets into `sorted`; level-0 piece offsets
+  uint2* elist = nullptr;                    // T pairs: the compact entry list (sparse form), or T words of digits (dense)
+  uint32_t* pre = nullptr;                   // sparse form: [0..1] offsets, [4..5] task offsets of pass 0's one segment
+  uint2* ebuf[2] = {};                       // entries between passes
+  // per pass: output segment offsets / task offsets (the last pass writes the bucket arrays) and bases
+  uint32_t *seg_off[kSortMaxPasses] = {}, *seg_tpo[kSortMaxPasses] = {}, *base[kSortMaxPasses] = {};
+  uint32_t* sorted = nullptr;                // point index | sign << 31, grouped by bucket
+  uint32_t* block_sums = nullptr;            // three-launch scans
+  uint32_t *pbkt = nullptr, *order = nullptr;   // piece -> bucket; piece ids, longest first
+  uint32_t* digits() const { return reinterpret_cast<uint32_t*>(elist); }
+  uint32_t* len_cursor() const { return len_hist + (kMaxPieceLen + 1); }
+  // Sparse or dense is decided per run from the density hint; the bytes must not depend on it, so the digit / entry
+  // region has the larger size and `pre` is always there.
+  template <class Taker>
+  void carve(Taker& ws, const MsmPlan& p) {
+    const SortPlan sp = make_sort_plan(p.ne, p.Wb, p.c);
+    const size_t T = (size_t)p.n * p.W, head = ws.off;
+    counts = ws.template take<uint32_t>(p.TB);
+    for (uint32_t l = 0; l + 1 < sp.npass; l++) seg_cnt[l] = ws.template take<uint32_t>(sp.segs[l + 1] + 1);
+    misc = ws.template take<uint32_t>(16);
+    len_hist = ws.template take<uint32_t>(2 * (kMaxPieceLen + 1));
+    zero_bytes = ws.off - head;
+    off0 = ws.template take<uint32_t>(p.TB + 1);
+    po_a = ws.template take<uint32_t>(p.TB + 1);
+    elist = ws.template take<uint2>(T);
+    pre = ws.template take<uint32_t>(8);
+    for (uint32_t k = 0; k < 2; k++) ebuf[k] = sp.npass > k + 1 ? ws.template take<uint2>(T) : nullptr;
+    for (uint32_t l = 0; l < sp.npass; l++) {
+      if (l + 1 < sp.npass) {
+        seg_off[l] = ws.template take<uint32_t>(sp.segs[l + 1] + 1);
+        seg_tpo[l] = ws.template take<uint32_t>(sp.segs[l + 1] + 1);
+      }
+      base[l] = ws.template take<uint32_t>((size_t)sp.tasks_max[l] << sp.bits[l]);
+    }
+    sorted = ws.template take<uint32_t>(T);
+    block_sums = ws.template take<uint32_t>(p.TB / kScanTile + 2);
+    pbkt = ws.template take<uint32_t>(msm_piece_cap(p));
+    order = ws.template take<uint32_t>(msm_piece_cap(p));
+  }
+};
+
+template <class F>
+struct MsmAccumLayout {
+  uint32_t *po_b = nullptr, *po_c = nullptr;   // piece offsets of the levels >= 1, ping-pong
+  uint32_t *block_sums = nullptr, *misc = nullptr;   // three-launch scans; [3] = pieces of the level
+  char* buckets = nullptr;                     // TB XYZZ
+  char *P1 = nullptr, *P2 = nullptr;           // partial sums of the levels, ping-pong: p1_cap and p2_cap XYZZ
+  size_t p1_cap = 0, p2_cap = 0;
+  char* X = nullptr;                           // row / column sums: 2 Wb groups of E = 2^logS (>= 2^logRows) XYZZ
+  char *Y1 = nullptr, *Y2 = nullptr;           // tree-sum levels over the per-bit totals of every group
+  template <class Taker>
+  void carve(Taker& ws, const MsmPlan& p) {
+    constexpr size_t kXyzz = MsmSizes<F>::kXyzz;
+    const size_t E = (size_t)1 << p.logS, sums = (size_t)2 * p.Wb * msm_reduce_bits(p.logS);
+    po_b = ws.template take<uint32_t>(p.TB + 1);
+    po_c = ws.template take<uint32_t>(p.TB + 1);
+    block_sums = ws.template take<uint32_t>(p.TB / kScanTile + 2);
+    misc = ws.template take<uint32_t>(16);
+    buckets = ws.template take<char>((size_t)p.TB * kXyzz);
+    p1_cap = msm_piece_cap(p);
+    p2_cap = p1_cap / 2 + 1;
+    P1 = ws.template take<char>(p1_cap * kXyzz);
+    P2 = ws.template take<char>(p2_cap * kXyzz);
+    X = ws.template take<char>(2 * p.Wb * E * kXyzz);
+    Y1 = ws.template take<char>((E + 255) / 256 * sums * kXyzz);
+    Y2 = ws.template take<char>((E + 255) / 256 * sums * kXyzz);
+  }
+};
+
+// Bytes of lane arena a phase takes for plan p: the counting run of its layout, plus slack.
+inline size_t msm_sort_workspace_bytes(const MsmPlan& p) { return msm_layout_bytes<MsmSortLayout>(p) + (1 << 12) - 256; }
+template <class F>
+inline size_t msm_accum_workspace_bytes(const MsmPlan& p) { return msm_layout_bytes<MsmAccumLayout<F>>(p) + (1 << 12); }
+
+// Partial-sum levels (after the MSM's level 0, and after the key set-up's multiplications): while some bucket still holds
+// more than one partial sum, one thread adds up to K of them. po_in: the TB + 1 offsets of the items entering the first
+// level (read-only); the levels' own offsets ping-pong between po_b / po_c, their sums between Pin / Pout (capacities in
+// XYZZ). max_items: most items in one bucket; total_in: at most this many enter the level. scan(in, out): its mode-3 scan.
+template <class F, class Scan>
+inline void msm_reduce_levels(hipStream_t st, uint32_t TB, uint32_t K, const uint32_t* po_in, uint32_t* po_b,
+                              uint32_t* po_c, char* Pin, size_t cap_in, char* Pout, size_t cap_out, uint64_t max_items,
+                              uint64_t total_in, void* buckets, Scan scan) {
+  uint32_t* po_out = po_b;
+  while (max_items > 1) {
+    uint64_t bound = total_in / 2 + 1;  // every unfinished bucket holds >= 2 items and emits <= items/2 + 1 pieces
+    if (bound > cap_out) throw HipError("msm: level buffer too small");
+    scan(po_in, po_out);
+    hipLaunchKernelGGL((msm_accumN_kernel<F>), dim3((uint32_t)((bound + 255) / 256)), dim3(256), 0, st, (const void*)Pin,
+                       po_in, (const uint32_t*)po_out, TB, K, buckets, (void*)Pout);
+    max_items = (max_items + K - 1) / K;
+    total_in = bound;
+    po_in = po_out;
+    po_out = (po_out == po_b) ? po_c : po_b;
+    std::swap(Pin, Pout);
+    std::swap(cap_in, cap_out);
+  }
+}
+
 // ---- host driver: two phases ---------------------------------------------------------------------
 // Phase A (scalars only): digits, bucket sort, scans, piece ordering. Its result can serve several
 // accumulations over DIFFERENT base arrays with the SAME scalars -- the prover's A, B1 and B2 queries all
@@ -897,57 +1037,11 @@ inline void msm_read_back(Lane& lane, const void* d_src, size_t bytes) {
 // Phase B (bases): bucket accumulation, further levels, bucket reduction, window sums to the host.
 struct MsmSorted {
   MsmPlan p;
-  uint32_t* counts = nullptr;   // entries per bucket
-  uint32_t* off0 = nullptr;     // bucket offsets into `sorted`
-  uint32_t* po_a = nullptr;     // level-0 piece offsets
-  uint32_t* sorted = nullptr;   // point index | sign << 31, grouped by bucket
-  uint32_t* order = nullptr;    // piece ids, longest first
-  uint32_t* pbkt = nullptr;     // piece -> bucket
+  MsmSortLayout m;              // phase B reads counts, off0, po_a, sorted, order, pbkt
   uint32_t total1 = 0;          // level-0 pieces
   uint32_t total_entries = 0;   // (point, window) entries with a non-zero digit = mixed additions of the level-0 kernel
   uint32_t max_count = 0;       // largest bucket
 };
-
-inline size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
-
-inline size_t msm_sort_workspace_bytes(const MsmPlan& p) {
-  size_t T = (size_t)p.n * p.W;
-  size_t p1 = T / p.K0 + p.TB + 1;
-  SortPlan sp = make_sort_plan(p.ne, p.Wb, p.c);
-  size_t bytes = 0;
-  bytes += al256((size_t)p.TB * 4);                  // counts
-  bytes += al256(((size_t)p.TB + 1) * 4) * 2;        // off0, po_a
-  bytes += al256(T * 4) + al256(T * 8);              // sorted; digits (T words) or the compact entry list (T pairs)
-  if (sp.npass > 1) bytes += al256(T * 8);           // entries between passes (ping)
-  if (sp.npass > 2) bytes += al256(T * 8);           // (pong)
-  for (uint32_t l = 0; l < sp.npass; l++) {
-    if (l + 1 < sp.npass) bytes += al256(((size_t)sp.segs[l + 1] + 1) * 4) * 3;   // seg_cnt, seg_off, tpo
-    bytes += al256((size_t)sp.tasks_max[l] * ((size_t)1 << sp.bits[l]) * 4);       // base
-  }
-  bytes += al256(((size_t)p.TB / kScanTile + 2) * 4);
-  bytes += al256(64);
-  bytes += al256(p1 * 4) * 2;                        // pbkt, order
-  bytes += al256((kMaxPieceLen + 1) * 4 * 2);        // len_hist, cursor
-  return bytes + (1 << 12);
-}
-
-template <class F>
-inline size_t msm_accum_workspace_bytes(const MsmPlan& p) {
-  size_t T = (size_t)p.n * p.W;
-  size_t p1 = T / p.K0 + p.TB + 1;
-  size_t p2 = p1 / 2 + 1;
-  size_t E = (size_t)1 << p.logS;   // logS >= logRows
-  size_t bytes = 0;
-  bytes += al256(((size_t)p.TB + 1) * 4) * 2;        // po_b, po_c
-  bytes += al256(((size_t)p.TB / kScanTile + 2) * 4);
-  bytes += al256(64);
-  bytes += al256((size_t)p.TB * MsmSizes<F>::kXyzz);  // buckets
-  bytes += al256(p1 * MsmSizes<F>::kXyzz);            // P1
-  bytes += al256(p2 * MsmSizes<F>::kXyzz);            // P2
-  bytes += al256(2 * p.Wb * E * MsmSizes<F>::kXyzz);                    // X: row / column sums
-  bytes += al256(2 * p.Wb * msm_reduce_bits(p.logS) * ((E + 255) / 256) * MsmSizes<F>::kXyzz) * 2;  // tree-sum levels
-  return bytes + (1 << 12);
-}
 
 inline void lane_reserve(Lane& lane, size_t need) {
   if (lane.ws.cap < need) {
@@ -975,23 +1069,10 @@ inline MsmSorted msm_sort_phase(Lane& lane, const void* d_scalars, size_t n, int
   if (merged && (uint64_t)p.n * p.W >= 0x80000000ull) throw HipError("msm: n * windows exceeds the fixed-base entry index");
   hipStream_t st = lane.stream;
   lane_reserve(lane, msm_sort_workspace_bytes(p) + (extra ? extra(p) : 0));
-  Arena& ws = lane.ws;
-  ws.reset();
-  const size_t T_max = (size_t)p.n * p.W;
+  lane.ws.reset();
   const SortPlan sp = make_sort_plan(p.ne, p.Wb, p.c);
-  // everything that must start at zero sits in ONE block at the head of the arena and is cleared by one memset (r03:
-  // four, each a launch of its own on a lane whose MSM is ~45 launches): bucket counts, the segment counts of the
-  // intermediate passes, the misc words, the piece-length histogram and its cursors
-  char* zero_lo = ws.base + ws.off;
-  sr.counts = ws.take<uint32_t>(p.TB);
-  uint32_t* seg_cnt[kSortMaxPasses] = {};
-  for (uint32_t l = 0; l + 1 < sp.npass; l++) seg_cnt[l] = ws.take<uint32_t>(sp.segs[l + 1] + 1);
-  uint32_t* misc = ws.take<uint32_t>(16);  // [0]=T, [1]=max count, [2]=total pieces, ...
-  uint32_t* len_hist = ws.take<uint32_t>(2 * (kMaxPieceLen + 1));
-  uint32_t* len_cursor = len_hist + (kMaxPieceLen + 1);
-  const size_t zero_bytes = (size_t)((ws.base + ws.off) - zero_lo);
-  sr.off0 = ws.take<uint32_t>(p.TB + 1);
-  sr.po_a = ws.take<uint32_t>(p.TB + 1);
+  const MsmSortLayout& m = sr.m = msm_carve<MsmSortLayout>(lane.ws, p);
+  ZK_HIP(hipMemsetAsync(m.counts, 0, m.zero_bytes, st));
   // sparse scalars in the fixed-base form (a witness through its tables): a compact entry list instead of the dense
   // digit array (msm_sort.hip.h msm_entries_kernel); ZKPOA_NO_SPARSE=1 keeps the dense form (measurement)
   static const bool no_sparse = [] {
@@ -1000,71 +1081,44 @@ inline MsmSorted msm_sort_phase(Lane& lane, const void* d_scalars, size_t n, int
   }();
   const double* dens = msm_density_hint();
   const bool sparse = merged && p.n && dens && dens[p.c] < 0.6 * (double)p.W && !no_sparse;
-  uint32_t* digits = sparse ? nullptr : ws.take<uint32_t>(T_max);
-  uint2* elist = sparse ? ws.take<uint2>(T_max) : nullptr;
-  uint32_t* pre = sparse ? ws.take<uint32_t>(8) : nullptr;   // [0..1] offsets, [4..5] task offsets of pass 0's one segment
-  uint2* ebuf[2] = {sp.npass > 1 ? ws.take<uint2>(T_max) : nullptr, sp.npass > 2 ? ws.take<uint2>(T_max) : nullptr};
-  // per pass: output segment counts / offsets / task offsets (the last pass writes the bucket arrays) and bases
-  uint32_t *seg_off[kSortMaxPasses] = {}, *seg_tpo[kSortMaxPasses] = {}, *base[kSortMaxPasses] = {};
-  for (uint32_t l = 0; l < sp.npass; l++) {
-    if (l + 1 < sp.npass) {
-      seg_off[l] = ws.take<uint32_t>(sp.segs[l + 1] + 1);
-      seg_tpo[l] = ws.take<uint32_t>(sp.segs[l + 1] + 1);
-    }
-    base[l] = ws.take<uint32_t>((size_t)sp.tasks_max[l] << sp.bits[l]);
-  }
-  sr.sorted = ws.take<uint32_t>(T_max);
-  uint32_t* block_sums = ws.take<uint32_t>(p.TB / kScanTile + 2);
-  size_t p1_cap = T_max / p.K0 + p.TB + 1;
-  sr.pbkt = ws.take<uint32_t>(p1_cap);
-  sr.order = ws.take<uint32_t>(p1_cap);
-
-  ZK_HIP(hipMemsetAsync(zero_lo, 0, zero_bytes, st));
+  uint32_t* digits = sparse ? nullptr : m.digits();   // one region, one view per form
+  uint2* elist = sparse ? m.elist : nullptr;
+  uint32_t* pre = sparse ? m.pre : nullptr;
   const uint32_t nblk = (p.n + 255) / 256;
   if (p.n && !sparse) hipLaunchKernelGGL(msm_digits_kernel, dim3(nblk), dim3(256), 0, st, d_scalars, p.n, p.c, p.W, digits);
   if (sparse) {
     const uint32_t per_wg = kEntriesThreads * kEntriesPerThread;
     hipLaunchKernelGGL(msm_entries_kernel, dim3((p.n + per_wg - 1) / per_wg), dim3(kEntriesThreads), 0, st, d_scalars, p.n,
-                       p.c, p.W, elist, misc + 8);
-    hipLaunchKernelGGL(msm_entries_finish_kernel, dim3(1), dim3(1), 0, st, (const uint32_t*)(misc + 8), sp.CH, pre, pre + 4);
+                       p.c, p.W, elist, m.misc + 8);
+    hipLaunchKernelGGL(msm_entries_finish_kernel, dim3(1), dim3(1), 0, st, (const uint32_t*)(m.misc + 8), sp.CH, pre, pre + 4);
   }
   for (uint32_t l = 0; l < sp.npass; l++) {
     const bool first = l == 0 && !sparse, last = l + 1 == sp.npass;
-    const uint2* in = l == 0 ? (const uint2*)elist : ebuf[(l - 1) & 1];
-    uint2* out = last ? nullptr : ebuf[l & 1];
-    const uint32_t* in_off = l == 0 ? (const uint32_t*)pre : seg_off[l - 1];
-    const uint32_t* tpo = l == 0 ? (const uint32_t*)(pre ? pre + 4 : nullptr) : seg_tpo[l - 1];
-    uint32_t* out_cnt = last ? sr.counts : seg_cnt[l];
-    uint32_t* out_off = last ? sr.off0 : seg_off[l];
+    const uint2* in = l == 0 ? (const uint2*)elist : m.ebuf[(l - 1) & 1];
+    uint2* out = last ? nullptr : m.ebuf[l & 1];
+    const uint32_t* in_off = l == 0 ? (const uint32_t*)pre : m.seg_off[l - 1];
+    const uint32_t* tpo = l == 0 ? (const uint32_t*)(pre ? pre + 4 : nullptr) : m.seg_tpo[l - 1];
+    uint32_t* out_cnt = last ? m.counts : m.seg_cnt[l];
+    uint32_t* out_off = last ? m.off0 : m.seg_off[l];
     const dim3 grid = first ? dim3(sp.chunks0, sp.W) : dim3((uint32_t)sp.tasks_max[l]);
     if (p.n) {
       if (first)
         hipLaunchKernelGGL((msm_sort_count_kernel<true>), grid, dim3(256), 0, st, sp, l, (const uint32_t*)digits, in,
-                           in_off, tpo, out_cnt, base[l]);
+                           in_off, tpo, out_cnt, m.base[l]);
       else
         hipLaunchKernelGGL((msm_sort_count_kernel<false>), grid, dim3(256), 0, st, sp, l, (const uint32_t*)digits, in,
-                           in_off, tpo, out_cnt, base[l]);
+                           in_off, tpo, out_cnt, m.base[l]);
     }
-    if (scan_three_kernel()) {   // ZKPOA_SCAN=3: the three-launch scans (A/B measurement)
-      if (last) {
-        scan_u32(st, sr.counts, p.TB, 0, 0, sr.off0, block_sums, misc + 0, misc + 1);
-        scan_u32(st, sr.counts, p.TB, 1, p.K0, sr.po_a, block_sums, misc + 2, nullptr);
-        hipLaunchKernelGGL(msm_piece_hist_kernel, dim3((p.TB + 255) / 256), dim3(256), 0, st, (const uint32_t*)sr.counts,
-                           p.TB, p.K0, len_hist);
-      } else {
-        scan_u32(st, seg_cnt[l], sp.segs[l + 1], 0, 0, seg_off[l], block_sums, misc + 4 + 2 * l, nullptr);
-        scan_u32(st, seg_cnt[l], sp.segs[l + 1], 1, sp.CH, seg_tpo[l], block_sums, misc + 5 + 2 * l, nullptr);
-      }
-    } else if (last) {   // bucket counts -> entry offsets + piece offsets (+ the largest bucket, the piece lengths), one launch
-      scan_pair(lane, ScanPair{sr.counts, p.TB, 0, 0, sr.off0, misc + 0, 1, p.K0, sr.po_a, misc + 2, misc + 1, len_hist, p.K0});
-    } else {             // segment counts -> entry offsets + task offsets
-      scan_pair(lane, ScanPair{seg_cnt[l], sp.segs[l + 1], 0, 0, seg_off[l], misc + 4 + 2 * l, 1, sp.CH, seg_tpo[l],
-                               misc + 5 + 2 * l, nullptr});
-    }
+    // bucket counts -> entry + piece offsets (+ the largest bucket, the piece lengths), or segment counts -> entry + task offsets
+    lane_scan(lane,
+              last ? ScanPair{m.counts, p.TB, 0, 0, m.off0, m.misc + 0, 1, p.K0, m.po_a, m.misc + 2, m.misc + 1, m.len_hist, p.K0}
+                   : ScanPair{m.seg_cnt[l], sp.segs[l + 1], 0, 0, m.seg_off[l], m.misc + 4 + 2 * l, 1, sp.CH, m.seg_tpo[l],
+                              m.misc + 5 + 2 * l, nullptr},
+              m.block_sums);
     if (p.n) {
 #define ZK_SORT_SCATTER(F_, L_)                                                                                       \
   hipLaunchKernelGGL((msm_sort_scatter_kernel<F_, L_>), grid, dim3(256), 0, st, sp, l, (const uint32_t*)digits, in,  \
-                     in_off, tpo, (const uint32_t*)out_off, (const uint32_t*)base[l], out, sr.sorted)
+                     in_off, tpo, (const uint32_t*)out_off, (const uint32_t*)m.base[l], out, m.sorted)
       if (first && last) ZK_SORT_SCATTER(true, true);
       else if (first) ZK_SORT_SCATTER(true, false);
       else if (last) ZK_SORT_SCATTER(false, true);
@@ -1073,15 +1127,15 @@ inline MsmSorted msm_sort_phase(Lane& lane, const void* d_scalars, size_t n, int
     }
   }
   uint32_t* hb = reinterpret_cast<uint32_t*>(lane.pinned);
-  msm_read_back(lane, misc, 16);
+  msm_read_back(lane, m.misc, 16);
   sr.total_entries = hb[0];
   sr.max_count = hb[1];
   sr.total1 = hb[2];
   if (sr.total1) {
     const uint32_t per_block = 256u * kPiecesPerThread;
     hipLaunchKernelGGL(msm_piece_order_kernel, dim3((sr.total1 + per_block - 1) / per_block), dim3(256), 0, st,
-                       (const uint32_t*)sr.counts, (const uint32_t*)sr.po_a, p.TB, p.K0, (const uint32_t*)len_hist,
-                       len_cursor, sr.pbkt, sr.order);
+                       (const uint32_t*)m.counts, (const uint32_t*)m.po_a, p.TB, p.K0, (const uint32_t*)m.len_hist,
+                       m.len_cursor(), m.pbkt, m.order);
   }
   if (sync_at_end) ZK_HIP(hipStreamSynchronize(st));  // other lanes are about to read the result
   return sr;
@@ -1098,83 +1152,41 @@ inline void msm_accum_phase(Lane& lane, const MsmSorted& sr, const void* d_bases
                             bool own_arena, float* accum_ms = nullptr) {
   const MsmPlan& p = sr.p;
   hipStream_t st = lane.stream;
-  Arena& ws = lane.ws;
   if (!own_arena) {
     lane_reserve(lane, msm_accum_workspace_bytes<F>(p));
-    ws.reset();
+    lane.ws.reset();
   }
-  const size_t T_max = (size_t)p.n * p.W;
-  uint32_t* po_b = ws.take<uint32_t>(p.TB + 1);
-  uint32_t* po_c = ws.take<uint32_t>(p.TB + 1);
-  uint32_t* block_sums = ws.take<uint32_t>(p.TB / kScanTile + 2);
-  uint32_t* misc = ws.take<uint32_t>(16);
-  char* buckets = ws.take<char>((size_t)p.TB * MsmSizes<F>::kXyzz);
-  size_t p1_cap = T_max / p.K0 + p.TB + 1;
-  size_t p2_cap = p1_cap / 2 + 1;
-  char* P1 = ws.take<char>(p1_cap * MsmSizes<F>::kXyzz);
-  char* P2 = ws.take<char>(p2_cap * MsmSizes<F>::kXyzz);
-  const uint32_t E = 1u << p.logS;            // entries per (window, row|column) group; logS >= logRows
-  const uint32_t groups = 2u * p.Wb;
-  char* X = ws.take<char>((size_t)groups * E * MsmSizes<F>::kXyzz);
-  const uint32_t S1 = (E + 255) / 256;
-  const uint32_t nbits = msm_reduce_bits(p.logS), sums = groups * nbits;   // per-bit totals of every group
-  char* Y1 = ws.take<char>((size_t)(S1 * sums) * MsmSizes<F>::kXyzz);
-  char* Y2 = ws.take<char>((size_t)(S1 * sums) * MsmSizes<F>::kXyzz);
+  const MsmAccumLayout<F> m = msm_carve<MsmAccumLayout<F>>(lane.ws, p);
+  const uint32_t E = 1u << p.logS, S1 = (E + 255) / 256;   // entries per (window, row|column) group; logS >= logRows
+  const uint32_t nbits = msm_reduce_bits(p.logS), sums = 2u * p.Wb * nbits;   // per-bit totals of every group
 
   if (accum_ms) ZK_HIP(hipEventRecord(lane.ev0, st));
   if (sr.total1) {
     const uint32_t pgrid = (sr.total1 + 255) / 256;
-    hipLaunchKernelGGL((msm_accum0_kernel<F>), dim3(pgrid), dim3(256), 0, st, d_bases, (const uint32_t*)sr.sorted,
-                       (const uint32_t*)sr.counts, (const uint32_t*)sr.off0, (const uint32_t*)sr.po_a,
-                       (const uint32_t*)sr.order, (const uint32_t*)sr.pbkt, p.TB, p.K0, (void*)buckets, (void*)P1);
+    hipLaunchKernelGGL((msm_accum0_kernel<F>), dim3(pgrid), dim3(256), 0, st, d_bases, (const uint32_t*)sr.m.sorted,
+                       (const uint32_t*)sr.m.counts, (const uint32_t*)sr.m.off0, (const uint32_t*)sr.m.po_a,
+                       (const uint32_t*)sr.m.order, (const uint32_t*)sr.m.pbkt, p.TB, p.K0, (void*)m.buckets, (void*)m.P1);
   }
   if (accum_ms) ZK_HIP(hipEventRecord(lane.ev1, st));
   // further levels while some bucket still has more than one partial sum; the shared po_a is read-only,
   // the level offsets ping-pong between this phase's own po_b / po_c
-  uint64_t max_items = ((uint64_t)sr.max_count + p.K0 - 1) / p.K0;  // max items per bucket entering level 1
-  uint64_t total_in = sr.total1;                                       // upper bound of items entering the level
-  const uint32_t* po_in = sr.po_a;
-  uint32_t* po_out = po_b;
-  char* Pin = P1;
-  char* Pout = P2;
-  size_t cap_out = p2_cap, cap_in = p1_cap;
-  while (max_items > 1) {
-    uint64_t bound = total_in / 2 + 1;  // every unfinished bucket holds >= 2 items and emits <= items/2 + 1 pieces
-    if (bound > cap_out) throw HipError("msm: level buffer too small");
-    if (scan_three_kernel()) scan_u32(st, po_in, p.TB, 3, p.K, po_out, block_sums, misc + 3, nullptr);
-    else scan_pair(lane, ScanPair{po_in, p.TB, 3, p.K, po_out, misc + 3, -1, 0, nullptr, nullptr, nullptr});
-    hipLaunchKernelGGL((msm_accumN_kernel<F>), dim3((uint32_t)((bound + 255) / 256)), dim3(256), 0, st, (const void*)Pin,
-                       po_in, (const uint32_t*)po_out, p.TB, p.K, (void*)buckets, (void*)Pout);
-    max_items = (max_items + p.K - 1) / p.K;
-    total_in = bound;
-    po_in = po_out;
-    po_out = (po_out == po_b) ? po_c : po_b;
-    std::swap(Pin, Pout);
-    std::swap(cap_in, cap_out);
-  }
+  auto scan = [&](auto* in, auto* out) { lane_scan(lane, ScanPair{in, p.TB, 3, p.K, out, m.misc + 3, -1}, m.block_sums); };
+  msm_reduce_levels<F>(st, p.TB, p.K, sr.m.po_a, m.po_b, m.po_c, m.P1, m.p1_cap, m.P2, m.p2_cap,
+                       ((uint64_t)sr.max_count + p.K0 - 1) / p.K0, sr.total1, m.buckets, scan);
   // bucket reduction: row / column sums, then per (window, group, weight bit) the total of the sums with that bit
   {
     uint32_t log_parts = msm_reduce_log_parts(p.logRows, p.logS, p.Wb);
     uint64_t threads = ((uint64_t)p.Wb << log_parts) * ((1u << p.logRows) + E);
     hipLaunchKernelGGL((msm_bucket_sums_kernel<F>), dim3((uint32_t)((threads + 255) / 256)), dim3(256),
-                       256 * MsmSizes<F>::kXyzz, st, (const void*)buckets, (const uint32_t*)sr.counts, p.Wb, p.Nb, p.logS,
-                       p.logRows, log_parts, E, (void*)X);
+                       256 * MsmSizes<F>::kXyzz, st, (const void*)m.buckets, (const uint32_t*)sr.m.counts, p.Wb, p.Nb, p.logS,
+                       p.logRows, log_parts, E, (void*)m.X);
   }
-  char* ybuf[2] = {Y1, Y2};
-  int yi = 0;
-  uint32_t S = S1;
+  char *cur = m.Y1, *next = m.Y2;
   hipLaunchKernelGGL((msm_bit_tree_sum_kernel<F>), dim3(S1, sums), dim3(64), 64 * MsmSizes<F>::kXyzz, st,
-                     (const void*)X, E, p.logS, p.logRows, nbits, S1, (void*)ybuf[yi]);
-  const char* cur = ybuf[yi];
-  yi ^= 1;
-  while (S > 1) {
-    uint32_t S_out = (S + 255) / 256;
-    hipLaunchKernelGGL((msm_tree_sum_kernel<F>), dim3(S_out, sums), dim3(64), 64 * MsmSizes<F>::kXyzz, st,
-                       (const void*)cur, S, S_out, (void*)ybuf[yi]);
-    cur = ybuf[yi];
-    yi ^= 1;
-    S = S_out;
-  }
+                     (const void*)m.X, E, p.logS, p.logRows, nbits, S1, (void*)cur);
+  for (uint32_t S = S1; S > 1; S = (S + 255) / 256, std::swap(cur, next))
+    hipLaunchKernelGGL((msm_tree_sum_kernel<F>), dim3((S + 255) / 256, sums), dim3(64), 64 * MsmSizes<F>::kXyzz, st,
+                       (const void*)cur, S, (S + 255) / 256, (void*)next);
   msm_read_back(lane, cur, (size_t)sums * MsmSizes<F>::kXyzz);
   ZK_HIP(hipGetLastError());
   memcpy(window_sums_host, lane.pinned, (size_t)sums * MsmSizes<F>::kXyzz);

@@ -248,23 +248,10 @@ void setup_accumulate(zkpoa_context* ctx, const void* d_points, uint64_t n_point
     hipLaunchKernelGGL((setup_mul_kernel<F>), dim3(grid), dim3(256), 0, st, d_points, d_coefs, d_pidx, d_sig,
                        (const uint32_t*)order.p, (const uint32_t*)by_len.p, (const uint32_t*)off.p, N, buckets.p, items.p);
   }
-  // partial-sum levels, as after the MSM's level 0 (msm_accum_phase): fan-in 4 until every segment is one point
-  const uint32_t K = 4;
-  uint64_t max_items = max_seg, total_in = N;
-  const uint32_t* po_in = (const uint32_t*)off.p;
-  uint32_t* po_out = (uint32_t*)po_b.p;
-  char *Pin = (char*)items.p, *Pout = (char*)items2.p;
-  while (max_items > 1) {
-    uint64_t bound = total_in / 2 + 1;
-    scan_u32(st, po_in, S, 3, K, po_out, (uint32_t*)block_sums.p, m + 3, nullptr);
-    hipLaunchKernelGGL((msm_accumN_kernel<F>), dim3((uint32_t)((bound + 255) / 256)), dim3(256), 0, st, (const void*)Pin,
-                       po_in, (const uint32_t*)po_out, S, K, buckets.p, (void*)Pout);
-    max_items = (max_items + K - 1) / K;
-    total_in = bound;
-    po_in = po_out;
-    po_out = (po_out == (uint32_t*)po_b.p) ? (uint32_t*)po_c.p : (uint32_t*)po_b.p;
-    std::swap(Pin, Pout);
-  }
+  const uint32_t K = 4;   // partial-sum levels, shared with the MSM (msm_reduce_levels): fan-in 4 until every segment is one point
+  auto scan = [&](const uint32_t* in, uint32_t* out) { scan_u32(st, in, S, 3, K, out, (uint32_t*)block_sums.p, m + 3, nullptr); };
+  msm_reduce_levels<F>(st, S, K, (const uint32_t*)off.p, (uint32_t*)po_b.p, (uint32_t*)po_c.p, (char*)items.p, N ? N : 1,
+                       (char*)items2.p, (size_t)N / 2 + 2, max_seg, N, buckets.p, scan);
   hipLaunchKernelGGL((xyzz_to_affine_kernel<F>), dim3((S + 255) / 256), dim3(256), 0, st, (const void*)buckets.p, d_out,
                      (uint64_t)S);
   ZK_HIP(hipStreamSynchronize(st));
