@@ -442,6 +442,25 @@ int zkpoa_zkey_verify(zkpoa_context* ctx, const char* r1cs_path, const char* pta
 #define ZKPOA_PTAU_LAGRANGE_BETA 0x100u
 int zkpoa_ptau_verify(zkpoa_context* ctx, const char* ptau_path, uint64_t piece_points, uint32_t* failed_checks,
                       uint32_t info[4]);
+/* The inverse NTT whose elements are curve points (ffjavascript's G.ifft), the arithmetic of `powersoftau prepare
+ * phase2`. Device pointers, wire format in and out (affine, Montgomery, G1 64 B / G2 128 B per point, infinity
+ * all-zero, coordinates < q on output); w_n is the 2^log_n-th root of unity of zkpoa_ntt. log_n <= 28. Complete for
+ * every input: equal points, opposite points, points at infinity. Every size takes the same kernels (one butterfly per
+ * thread, workgroups of 64): there is no size threshold to set. */
+/* d_out[j] = sum_i (w_n^(-ij) / n) * d_in[i], n = 2^log_n points in wire format (group = 1 | 2); d_out may equal d_in */
+int zkpoa_ec_intt_device(zkpoa_context* ctx, int group, const void* d_in, uint32_t log_n, void* d_out);
+/* `snarkjs powersoftau prepare phase2 <in.ptau> <out.ptau>`; info[4] as zkpoa_ptau_verify */
+/* Writes in.ptau's sections 1-7 byte for byte, then sections 12-15 made from sections 2-5: level l (2^l points from
+ * point 2^l - 1 on) is zkpoa_ec_intt_device of the section's first 2^l points; levels 0..power+1 for section 12 (the
+ * top level over the 2N - 1 powers and one point at infinity), 0..power for 13-15. Sections 12-15 already in the input
+ * are ignored (info[2] says whether it had them). The input is validated as zkpoa_ptau_verify validates it -- header,
+ * lengths, every point on its curve with coordinates < q, sections 3 and 6 in G2 -- but not checked with pairings: run
+ * zkpoa_ptau_verify on the result for that. PROVER_ERROR (zkpoa_last_error) for a malformed file (there a bad point is
+ * an error too), a power of 28 (no root of unity for the top level), an output path that names the input file, or a
+ * largest level whose buffers (about 700 B per point of 2^power) do not fit in free device memory. The output is
+ * written under a temporary name and renamed when complete: a failure leaves nothing behind and a file already at
+ * out_path untouched. */
+int zkpoa_ptau_prepare_phase2(zkpoa_context* ctx, const char* in_path, const char* out_path, uint32_t info[4]);
 
 /* ---- the step after the path; host only, no GPU ----------------------------------------
  * zkpoa_groth16_verify: `npx snarkjs groth16 verify <vkey> <public> <proof>` (scripts/g16_verify.sh:213-216)

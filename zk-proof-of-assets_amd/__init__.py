@@ -39,6 +39,7 @@ EXPORTS = [
     "zkpoa_context_create", "zkpoa_context_destroy", "zkpoa_last_error",
     "zkpoa_zkey_load", "zkpoa_zkey_free", "zkpoa_zkey_info", "zkpoa_prove",
     "zkpoa_zkey_load_device", "zkpoa_zkey_load_device_shard", "zkpoa_prove_device", "zkpoa_setup_accumulate", "zkpoa_zkey_new", "zkpoa_zkey_contribute", "zkpoa_wtns_check", "zkpoa_zkey_verify", "zkpoa_ptau_verify",
+    "zkpoa_ec_intt_device", "zkpoa_ptau_prepare_phase2",
     "zkpoa_groth16_prover_files", "zkpoa_set_thread_options", "zkpoa_clear_thread_options", "zkpoa_idle_work", "zkpoa_zkey_load_shard", "zkpoa_zkey_load_shard_ex", "zkpoa_zkey_set_shard", "zkpoa_zkey_header",
     "zkpoa_prove_partials", "zkpoa_prove_partials_device", "zkpoa_prove_assemble",
     "zkpoa_zkey_load_shard_split", "zkpoa_zkey_set_shard_split", "zkpoa_witness_load",
@@ -194,6 +195,9 @@ def lib():
                                         ctypes.POINTER(ctypes.c_uint32)]
         L.zkpoa_ptau_verify.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32),
                                         ctypes.POINTER(ctypes.c_uint32)]
+        L.zkpoa_ec_intt_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
+        L.zkpoa_ptau_prepare_phase2.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p,
+                                                ctypes.POINTER(ctypes.c_uint32)]
         L.zkpoa_zkey_load_device_shard.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint,
                                                    ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int] + \
             [ctypes.c_void_p] * 6 + [ctypes.c_uint64, ctypes.c_char_p, c_void_pp]
@@ -493,6 +497,20 @@ class Context:
         self._check(lib().zkpoa_ptau_verify(self._h, os.fsencode(path), int(piece_points), ctypes.byref(failed), info),
                     "zkpoa_ptau_verify")
         return int(failed.value), tuple(int(v) for v in info)
+
+    def ec_intt(self, group, d_in, log_n, d_out):
+        """Inverse NTT over 2^log_n curve points of G1 (group 1) or G2 (2), device pointers as ints, wire format:
+        out[j] = sum_i (w_n^(-ij) / n) * in[i]; d_out may equal d_in (include/zkpoa_prover.h: zkpoa_ec_intt_device)."""
+        self._check(lib().zkpoa_ec_intt_device(self._h, group, d_in, log_n, d_out), "zkpoa_ec_intt_device")
+
+    def ptau_prepare_phase2(self, in_path, out_path):
+        """`snarkjs powersoftau prepare phase2` on files: writes out_path with sections 12-15 made from sections 2-5
+        -> (power, ceremony power, the input was prepared already, contributions). A malformed file raises ZkpoaError
+        and leaves nothing at out_path (include/zkpoa_prover.h: zkpoa_ptau_prepare_phase2)."""
+        info = (ctypes.c_uint32 * 4)()
+        self._check(lib().zkpoa_ptau_prepare_phase2(self._h, os.fsencode(in_path), os.fsencode(out_path), info),
+                    "zkpoa_ptau_prepare_phase2")
+        return tuple(int(v) for v in info)
 
     def zkey_contribute(self, zkey_in_path, zkey_out_path, delta=None):
         """The arithmetic of `snarkjs zkey contribute` (delta: int in [1, r), None = random)."""

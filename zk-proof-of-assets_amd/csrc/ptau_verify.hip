@@ -224,29 +224,22 @@ uint32_t ptau_verify(zkpoa_context* ctx, const char* path, uint64_t piece_points
   // ---- the file's shape: anything that contradicts the header is a malformed file
   MappedFile fp(path);   // mapped for the section table and a few single points; the sections stream with pread
   auto ps = bin_sections(fp, "ptau", 1, "ptau");
-  for (uint32_t t = 1; t <= 7; t++)
-    if (!ps.count(t)) throw SetupError("ptau: section " + std::to_string(t) + " missing");
-  uint32_t ceremony = 0;
-  const uint32_t power = ptau_header(fp, ps[1], &ceremony);
-  if (power < 1 || power > 28) throw SetupError("ptau: power " + std::to_string(power) + " is outside [1, 28]");
+  const PtauShape shape = ptau_power_sections(fp, ps);
+  const uint32_t power = shape.power;
   const uint64_t N = 1ull << power;
-  const uint64_t want[8] = {0, 0, (2 * N - 1) * 64, N * 128, N * 64, N * 64, 128, 0};
-  for (uint32_t t = 2; t <= 6; t++)
-    if (ps[t].len != want[t]) throw SetupError("ptau: section " + std::to_string(t) + " has the wrong length for power " + std::to_string(power));
-  if (ps[7].len < 4) throw SetupError("ptau: section 7 has the wrong length");
   const int n_lag = (int)ps.count(12) + (int)ps.count(13) + (int)ps.count(14) + (int)ps.count(15);
   if (n_lag != 0 && n_lag != 4) throw SetupError("ptau: only some of sections 12-15 (Lagrange form) are present");
   const bool prepared = n_lag == 4;
   if (prepared) {
-    if (power > 27) throw SetupError("ptau: a prepared file of power above 27 has no root of unity for its top level");
+    ptau_check_preparable(power);
     const uint64_t wl[4] = {(4 * N - 1) * 64, (2 * N - 1) * 128, (2 * N - 1) * 64, (2 * N - 1) * 64};
     for (uint32_t t = 12; t <= 15; t++)
       if (ps[t].len != wl[t - 12]) throw SetupError("ptau: section " + std::to_string(t) + " has the wrong length for power " + std::to_string(power));
   }
   info[0] = power;
-  info[1] = ceremony;
+  info[1] = shape.ceremony;
   info[2] = prepared ? 1 : 0;
-  info[3] = rd32(fp.p + ps[7].off);
+  info[3] = shape.contributions;
   phase("sections");
 
   // ---- random weights: one rho per power section (ratio checks), one rho_l per level (Lagrange checks)

@@ -275,106 +275,6 @@ extern "C" int zkpoa_setup_accumulate(zkpoa_context* ctx, int group, const void*
 // ---- `snarkjs zkey new <circuit.r1cs> <pot.ptau> <circuit_0.zkey>` (g16_setup.sh:243-246) on files -----------------------
 namespace {
 
-// Output files are written under a temporary name and renamed into place (as prover_main's write_atomic): a failure
-// part-way (ENOSPC, HIP error, kill) never leaves a truncated .zkey under the final name for a later "skip if the zkey
-// exists" step to pick up, and writing over the input of `zkey contribute` is safe (the mapping keeps the old inode).
-struct AtomicFile {
-  std::string path, tmp;
-  FILE* f = nullptr;
-  bool ok = true;
-  explicit AtomicFile(const char* final_path) : path(final_path), tmp(path + ".tmp." + std::to_string((long)getpid())) {
-    f = fopen(tmp.c_str(), "wb");
-    if (!f) throw SetupError("cannot create " + tmp);
-  }
-  void write(const void* p, size_t len) {
-    if (ok && len) ok = fwrite(p, 1, len, f) == len;
-  }
-  // a payload of GBs: the stream is flushed, the file extended, and the bytes are copied by several threads through a
-  // shared mapping of their final place (buffered write() calls to one file queue up behind its inode lock -- measured on
-  // tmpfs: eight pwrite threads were no faster than one fwrite); the stream then continues behind them
-  void write_large(const void* p, size_t len) {
-    if (len < (64u << 20)) return write(p, len);
-    if (!ok) return;
-    if (fflush(f) != 0) {
-      ok = false;
-      return;
-    }
-    const off_t base = ftello(f);
-    const int fd = fileno(f);
-    if (base < 0 || ftruncate(fd, base + (off_t)len) != 0) {
-      ok = false;
-      return;
-    }
-    const off_t map_off = base & ~(off_t)4095;
-    const size_t lead = (size_t)(base - map_off);
-    void* m = mmap(nullptr, lead + len, PROT_READ | PROT_WRITE, MAP_SHARED, fd, map_off);
-    if (m == MAP_FAILED) {   // a file system without shared mappings: the plain way
-      ok = fseeko(f, base, SEEK_SET) == 0;
-      return write(p, len);
-    }
-    char* dst = static_cast<char*>(m) + lead;
-    parallel_ranges(len, 32ull << 20, [&](unsigned, uint64_t lo, uint64_t hi) { memcpy(dst + lo, static_cast<const char*>(p) + lo, hi - lo); });
-    ok = munmap(m, lead + len) == 0 && fseeko(f, base + (off_t)len, SEEK_SET) == 0;
-  }
-  // Absolute placement, for a file whose section offsets are known before their content: reserve() sizes it, put_at()
-  // may then be called from several threads for disjoint ranges in any order (small ranges: pwrite; large ones: the
-  // shared-mapping copy of write_large). The FILE stream is not used in this mode.
-  std::atomic<bool> placed_ok{true};
-  void reserve(uint64_t total) {
-    if (fflush(f) != 0 || ftruncate(fileno(f), (off_t)total) != 0) ok = false;
-  }
-  void put_at(uint64_t off, const void* p, uint64_t len) {
-    if (!len) return;
-    const int fd = fileno(f);
-    if (len < (64u << 20)) {
-      uint64_t done = 0;
-      while (done < len) {
-        const ssize_t w = pwrite(fd, static_cast<const char*>(p) + done, len - done, (off_t)(off + done));
-        if (w <= 0) {
-          placed_ok = false;
-          return;
-        }
-        done += (uint64_t)w;
-      }
-      return;
-    }
-    const uint64_t map_off = off & ~4095ull, lead = off - map_off;
-    void* m = mmap(nullptr, lead + len, PROT_READ | PROT_WRITE, MAP_SHARED, fd, (off_t)map_off);
-    if (m == MAP_FAILED) {
-      uint64_t done = 0;
-      while (done < len) {
-        const ssize_t w = pwrite(fd, static_cast<const char*>(p) + done, len - done, (off_t)(off + done));
-        if (w <= 0) {
-          placed_ok = false;
-          return;
-        }
-        done += (uint64_t)w;
-      }
-      return;
-    }
-    char* dst = static_cast<char*>(m) + lead;
-    parallel_ranges(len, 32ull << 20, [&](unsigned, uint64_t lo, uint64_t hi) { memcpy(dst + lo, static_cast<const char*>(p) + lo, hi - lo); });
-    if (munmap(m, lead + len) != 0) placed_ok = false;
-  }
-  void commit() {
-    ok = ok && placed_ok.load();
-    ok = (fclose(f) == 0) && ok;
-    f = nullptr;
-    if (!ok || rename(tmp.c_str(), path.c_str()) != 0) {
-      unlink(tmp.c_str());
-      throw SetupError("write to " + path + " failed");
-    }
-  }
-  ~AtomicFile() {
-    if (f) {
-      fclose(f);
-      unlink(tmp.c_str());
-    }
-  }
-  AtomicFile(const AtomicFile&) = delete;
-  AtomicFile& operator=(const AtomicFile&) = delete;
-};
-
 void dev_check_coords(zkpoa_context* ctx, const void* d, uint64_t count32, const char* what) {
   if (!count32) return;
   hipStream_t st = ctx->dev.lanes[0].stream;

@@ -1,8 +1,10 @@
 // What the file commands of csrc/setup.hip (`zkey new`, `zkey contribute`, `wtns check`), csrc/zkey_verify.hip
-// (`zkey verify`) and csrc/ptau_verify.hip (`powersoftau verify`) share: mapped files and their section tables
-// (the scan itself: binfile.hpp), the ptau header, the ZKPOA_VERBOSE phase timer, host threads and arrays, the r1cs
-// parser and its CSR, the ptau ranges a key is made from, the constraint-fold kernels, and the device passes that
-// check the points of a section (curve, range, G2 subgroup). Internal linkage: each translation unit has its own copy.
+// (`zkey verify`), csrc/ptau_verify.hip (`powersoftau verify`) and csrc/ptau_prepare.hip (`powersoftau prepare phase2`)
+// share: mapped files and their section tables (the scan itself: binfile.hpp), the ptau header and the shape of its power
+// sections, output files that appear only when complete (AtomicFile), the ZKPOA_VERBOSE phase timer, host threads and
+// arrays, the r1cs parser and its CSR, the ptau ranges a key is made from, the constraint-fold kernels, and the device
+// passes that check the points of a section (curve, range, G2 subgroup). Internal linkage: each translation unit has
+// its own copy.
 #pragma once
 #include "binfile.hpp"
 #include "bn254_ec.hip.h"
@@ -113,6 +115,31 @@ uint32_t ptau_header(const MappedFile& f, const Sec& h, uint32_t* ceremony = nul
   if (memcmp(f.p + h.off + 4, HFqParams::P, 32) != 0) throw SetupError("ptau: not a BN254 ceremony");
   if (ceremony) *ceremony = rd32(f.p + h.off + 40);
   return rd32(f.p + h.off + 36);
+}
+
+// The power sections of a ceremony file (`powersoftau verify`, `powersoftau prepare phase2`): sections 1-7 present, a
+// BN254 header, a power in [1, 28], and sections 2-6 of the lengths that power gives (N = 2^power: 2N - 1 G1, N G2, N G1,
+// N G1, one G2). Anything else is a malformed file.
+struct PtauShape {
+  uint32_t power, ceremony, contributions;
+};
+PtauShape ptau_power_sections(const MappedFile& fp, std::map<uint32_t, Sec>& ps) {
+  for (uint32_t t = 1; t <= 7; t++)
+    if (!ps.count(t)) throw SetupError("ptau: section " + std::to_string(t) + " missing");
+  PtauShape s{0, 0, 0};
+  s.power = ptau_header(fp, ps[1], &s.ceremony);
+  if (s.power < 1 || s.power > 28) throw SetupError("ptau: power " + std::to_string(s.power) + " is outside [1, 28]");
+  const uint64_t N = 1ull << s.power;
+  const uint64_t want[8] = {0, 0, (2 * N - 1) * 64, N * 128, N * 64, N * 64, 128, 0};
+  for (uint32_t t = 2; t <= 6; t++)
+    if (ps[t].len != want[t]) throw SetupError("ptau: section " + std::to_string(t) + " has the wrong length for power " + std::to_string(s.power));
+  if (ps[7].len < 4) throw SetupError("ptau: section 7 has the wrong length");
+  s.contributions = rd32(fp.p + ps[7].off);
+  return s;
+}
+// level power + 1 of section 12 is a transform of 2^(power + 1) points, and BN254's Fr has 2^28-th roots of unity at most
+void ptau_check_preparable(uint32_t power) {
+  if (power > 27) throw SetupError("ptau: a prepared file of power above 27 has no root of unity for its top level");
 }
 
 void urandom(void* dst, size_t len) {
@@ -331,6 +358,106 @@ struct UVec {   // a sized array of trivially copyable elements whose storage is
   const T& operator[](size_t i) const { return p[i]; }
   const T* begin() const { return p.get(); }
   const T* end() const { return p.get() + n; }
+};
+
+// Output files are written under a temporary name and renamed into place (as prover_main's write_atomic): a failure
+// part-way (ENOSPC, HIP error, kill) never leaves a truncated .zkey under the final name for a later "skip if the zkey
+// exists" step to pick up, and writing over the input of `zkey contribute` is safe (the mapping keeps the old inode).
+struct AtomicFile {
+  std::string path, tmp;
+  FILE* f = nullptr;
+  bool ok = true;
+  explicit AtomicFile(const char* final_path) : path(final_path), tmp(path + ".tmp." + std::to_string((long)getpid())) {
+    f = fopen(tmp.c_str(), "wb");
+    if (!f) throw SetupError("cannot create " + tmp);
+  }
+  void write(const void* p, size_t len) {
+    if (ok && len) ok = fwrite(p, 1, len, f) == len;
+  }
+  // a payload of GBs: the stream is flushed, the file extended, and the bytes are copied by several threads through a
+  // shared mapping of their final place (buffered write() calls to one file queue up behind its inode lock -- measured on
+  // tmpfs: eight pwrite threads were no faster than one fwrite); the stream then continues behind them
+  void write_large(const void* p, size_t len) {
+    if (len < (64u << 20)) return write(p, len);
+    if (!ok) return;
+    if (fflush(f) != 0) {
+      ok = false;
+      return;
+    }
+    const off_t base = ftello(f);
+    const int fd = fileno(f);
+    if (base < 0 || ftruncate(fd, base + (off_t)len) != 0) {
+      ok = false;
+      return;
+    }
+    const off_t map_off = base & ~(off_t)4095;
+    const size_t lead = (size_t)(base - map_off);
+    void* m = mmap(nullptr, lead + len, PROT_READ | PROT_WRITE, MAP_SHARED, fd, map_off);
+    if (m == MAP_FAILED) {   // a file system without shared mappings: the plain way
+      ok = fseeko(f, base, SEEK_SET) == 0;
+      return write(p, len);
+    }
+    char* dst = static_cast<char*>(m) + lead;
+    parallel_ranges(len, 32ull << 20, [&](unsigned, uint64_t lo, uint64_t hi) { memcpy(dst + lo, static_cast<const char*>(p) + lo, hi - lo); });
+    ok = munmap(m, lead + len) == 0 && fseeko(f, base + (off_t)len, SEEK_SET) == 0;
+  }
+  // Absolute placement, for a file whose section offsets are known before their content: reserve() sizes it, put_at()
+  // may then be called from several threads for disjoint ranges in any order (small ranges: pwrite; large ones: the
+  // shared-mapping copy of write_large). The FILE stream is not used in this mode.
+  std::atomic<bool> placed_ok{true};
+  void reserve(uint64_t total) {
+    if (fflush(f) != 0 || ftruncate(fileno(f), (off_t)total) != 0) ok = false;
+  }
+  void put_at(uint64_t off, const void* p, uint64_t len) {
+    if (!len) return;
+    const int fd = fileno(f);
+    if (len < (64u << 20)) {
+      uint64_t done = 0;
+      while (done < len) {
+        const ssize_t w = pwrite(fd, static_cast<const char*>(p) + done, len - done, (off_t)(off + done));
+        if (w <= 0) {
+          placed_ok = false;
+          return;
+        }
+        done += (uint64_t)w;
+      }
+      return;
+    }
+    const uint64_t map_off = off & ~4095ull, lead = off - map_off;
+    void* m = mmap(nullptr, lead + len, PROT_READ | PROT_WRITE, MAP_SHARED, fd, (off_t)map_off);
+    if (m == MAP_FAILED) {
+      uint64_t done = 0;
+      while (done < len) {
+        const ssize_t w = pwrite(fd, static_cast<const char*>(p) + done, len - done, (off_t)(off + done));
+        if (w <= 0) {
+          placed_ok = false;
+          return;
+        }
+        done += (uint64_t)w;
+      }
+      return;
+    }
+    char* dst = static_cast<char*>(m) + lead;
+    parallel_ranges(len, 32ull << 20, [&](unsigned, uint64_t lo, uint64_t hi) { memcpy(dst + lo, static_cast<const char*>(p) + lo, hi - lo); });
+    if (munmap(m, lead + len) != 0) placed_ok = false;
+  }
+  void commit() {
+    ok = ok && placed_ok.load();
+    ok = (fclose(f) == 0) && ok;
+    f = nullptr;
+    if (!ok || rename(tmp.c_str(), path.c_str()) != 0) {
+      unlink(tmp.c_str());
+      throw SetupError("write to " + path + " failed");
+    }
+  }
+  ~AtomicFile() {
+    if (f) {
+      fclose(f);
+      unlink(tmp.c_str());
+    }
+  }
+  AtomicFile(const AtomicFile&) = delete;
+  AtomicFile& operator=(const AtomicFile&) = delete;
 };
 
 // Untrusted inputs: the device keeps Fq elements lazily in [0, 2q) and takes file bytes raw, so every

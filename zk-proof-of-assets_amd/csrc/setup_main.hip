@@ -6,9 +6,10 @@
 //     snarkjs wtns check <circuit.r1cs> <witness.wtns>                                      (scripts/g16_verify.sh:205-210)
 //     snarkjs zkey verify <circuit.r1cs> <pot.ptau> <circuit_final.zkey>                    (scripts/g16_verify.sh -z)
 //     snarkjs powersoftau verify <pot.ptau>              (the TODO at g16_setup.sh:201 and g16_verify.sh:164)
+//     snarkjs powersoftau prepare phase2 <in.ptau> <out.ptau>     (what makes a ceremony file usable by the commands above)
 // Same three file arguments (the words `zkey new` / `groth16 setup` are accepted and ignored, so the command line
-// can be kept as it is with the executable swapped). The .ptau must be prepared for phase 2 (`snarkjs powersoftau
-// prepare phase2`), as snarkjs requires too. Exit status 0 / non-zero + message on stderr.
+// can be kept as it is with the executable swapped). The .ptau must be prepared for phase 2, as snarkjs requires too:
+// `zkpoa-setup powersoftau prepare phase2` does that here. Exit status 0 / non-zero + message on stderr.
 // The phase-2 transcript (section 10: circuit hash, contribution records; DESIGN.md "Phase-2 transcript") is opt-in:
 // `zkey new ... --transcript` fills in the circuit hash; on such a key `zkey contribute` appends a record (--name= / -n=
 // is kept in it), `zkey beacon` works, and `zkey verify` checks the hash and every record. Without the option every
@@ -74,7 +75,7 @@ static bool delta2_is_gamma2(const char* zkey_path) {
 
 int main(int argc, char** argv) {
   int a = 1;
-  bool contribute = false, check = false, verify = false, pverify = false, beacon = false;
+  bool contribute = false, check = false, verify = false, pverify = false, beacon = false, prepare = false;
   if (argc - a >= 2 && !strcmp(argv[a], "zkey") && !strcmp(argv[a + 1], "beacon")) {
     beacon = true;
     a += 2;
@@ -87,6 +88,9 @@ int main(int argc, char** argv) {
   } else if (argc - a >= 2 && !strcmp(argv[a], "powersoftau") && !strcmp(argv[a + 1], "verify")) {
     pverify = true;
     a += 2;
+  } else if (argc - a >= 3 && !strcmp(argv[a], "powersoftau") && !strcmp(argv[a + 1], "prepare") && !strcmp(argv[a + 2], "phase2")) {
+    prepare = true;
+    a += 3;
   } else if (argc - a >= 2 && !strcmp(argv[a], "wtns") && !strcmp(argv[a + 1], "check")) {
     check = true;
     a += 2;
@@ -111,14 +115,15 @@ int main(int argc, char** argv) {
     if (npos < 4) pos[npos] = argv[i];
     npos++;
   }
-  if (npos != (pverify ? 1 : (beacon ? 4 : (contribute || check ? 2 : 3)))) {
+  if (npos != (pverify ? 1 : (beacon ? 4 : (contribute || check || prepare ? 2 : 3)))) {
     fprintf(stderr, "usage: zkpoa-setup [zkey new | groth16 setup] <circuit.r1cs> <pot.ptau> <circuit_0.zkey>\n"
                     "         [--transcript]   fill in section 10's circuit hash (needs the ptau's section 2)\n"
                     "       zkpoa-setup zkey contribute <in.zkey> <out.zkey> [--name=...] [-e=...]\n"
                     "       zkpoa-setup zkey beacon <in.zkey> <out.zkey> <beaconHash(hex)> <numIterationsExp> [-n=...]\n"
                     "       zkpoa-setup wtns check <circuit.r1cs> <witness.wtns>\n"
                     "       zkpoa-setup zkey verify <circuit.r1cs> <pot.ptau> <circuit.zkey>\n"
-                    "       zkpoa-setup powersoftau verify <pot.ptau>\n");
+                    "       zkpoa-setup powersoftau verify <pot.ptau>\n"
+                    "       zkpoa-setup powersoftau prepare phase2 <in.ptau> <out.ptau>\n");
     return 2;
   }
   uint8_t delta[32];
@@ -133,7 +138,8 @@ int main(int argc, char** argv) {
   }
   // `zkey new` / `zkey contribute` run in a worker process and this one leaves as soon as the key is renamed into place
   // (csrc/worker_exit.hpp: a worker that has held ~100 GB of host arrays takes seconds to be dismantled).
-  // (`wtns check`, `zkey verify` and `powersoftau verify` write nothing and use no worker)
+  // (`wtns check`, `zkey verify` and `powersoftau verify` write nothing and use no worker; `powersoftau prepare phase2`
+  // runs in this process too)
   // beacon: hex bytes and the exponent (at most 30: 2^30 hashes take minutes, more would not finish)
   uint8_t beacon_bytes[255];
   unsigned long beacon_len = 0;
@@ -165,7 +171,7 @@ int main(int argc, char** argv) {
     uint32_t cnt = 0;
     if (zkpoa_zkey_contributions(pos[0], &has, &cnt, nullptr, 0) == PROVER_OK) in_transcript = has != 0;
   }
-  zkpoa::WorkerExit we = zkpoa::WorkerExit::start(!check && !verify && !pverify, "zkpoa-setup");
+  zkpoa::WorkerExit we = zkpoa::WorkerExit::start(!check && !verify && !pverify && !prepare, "zkpoa-setup");
   if (we.is_worker()) zkpoa_setup_defer_host_frees(1);
   auto leave = [&](int code) -> int {
     if (we.is_worker()) we.leave(code);
@@ -255,6 +261,10 @@ int main(int argc, char** argv) {
       }
       printf("[INFO]  zkpoa: Powers of Tau Ok!\n");
     }
+  } else if (prepare) {   // snarkjs logs its progress and exits 0, or names what is wrong with the file and exits 1
+    uint32_t info[4] = {0, 0, 0, 0};
+    rc = zkpoa_ptau_prepare_phase2(ctx, pos[0], pos[1], info);
+    if (rc == PROVER_OK) printf("[INFO]  zkpoa: Prepared phase 2\n");
   } else {
     if (beacon) rc = zkpoa_zkey_beacon(ctx, pos[0], pos[1], beacon_bytes, beacon_len, beacon_exp, name);
     else if (contribute && in_transcript) rc = zkpoa_zkey_contribute_ex(ctx, pos[0], pos[1], delta_p, name);
@@ -265,7 +275,7 @@ int main(int argc, char** argv) {
   if (!we.is_worker()) zkpoa_context_destroy(ctx);
   clock_gettime(CLOCK_MONOTONIC, &t1);
   if (rc == PROVER_OK && getenv("ZKPOA_VERBOSE") && !check && !verify && !pverify)
-    fprintf(stderr, "zkpoa-setup: %s written in %.2f s\n", pos[contribute || beacon ? 1 : 2],
+    fprintf(stderr, "zkpoa-setup: %s written in %.2f s\n", pos[contribute || beacon || prepare ? 1 : 2],
             (t1.tv_sec - t0.tv_sec) + (t1.tv_nsec - t0.tv_nsec) / 1e9);
   return leave(rc == PROVER_OK ? 0 : 1);
 }

@@ -153,6 +153,21 @@ void msm_accum_g1(zkpoa_context* ctx, int lane_id, const MsmSorted* sr, bool own
                   uint8_t* out, float* ms2);
 void msm_accum_g2(zkpoa_context* ctx, int lane_id, const MsmSorted* sr, bool own_arena, const void* d_bases,
                   uint8_t* out, float* ms2);
+// ec_ntt_g1.hip / ec_ntt_g2.hip (ec_ntt.hip.h): the inverse NTT over curve points. The work of transforms of up to
+// 2^log_max points: the XYZZ buffer and the twiddles; one transform at a time uses it.
+struct EcNttWork {
+  uint32_t log_max;
+  DevBuf work, tw;
+  EcNttWork(uint32_t lm, size_t work_bytes, size_t tw_bytes) : log_max(lm), work(work_bytes), tw(tw_bytes) {}
+};
+inline size_t ec_intt_work_bytes(int group, uint32_t log_max) {   // device memory of an EcNttWork
+  return ((size_t)(group == 2 ? 256 : 128) << log_max) + (log_max ? (size_t)32 << (log_max - 1) : 32);
+}
+EcNttWork* ec_intt_work_g1(zkpoa_context* ctx, uint32_t log_max);   // delete when done; twiddles built on lane 0's stream
+EcNttWork* ec_intt_work_g2(zkpoa_context* ctx, uint32_t log_max);
+// enqueued on lane 0's stream: d_out[j] = sum_i (w_n^(-ij) / n) d_in[i], n = 2^log_n <= 2^log_max; d_out may be d_in
+void ec_intt_g1(zkpoa_context* ctx, EcNttWork& wk, const void* d_in, uint32_t log_n, void* d_out);
+void ec_intt_g2(zkpoa_context* ctx, EcNttWork& wk, const void* d_in, uint32_t log_n, void* d_out);
 // ntt.hip
 void ntt_prepare(zkpoa_context* ctx, hipStream_t st, uint32_t k);  // builds twiddle tables (hipMalloc) once per k
 // batch > 1: that many vectors of 2^k elements, `stride` bytes apart, transformed together (one launch per pass)
