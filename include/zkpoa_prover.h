@@ -557,6 +557,11 @@ int zkpoa_field_prim(zkpoa_context* ctx, int field, int op, const void* in, void
  * (xyzz_dbl_affine), 4 = k a (xyzz_mul_small). Arguments an op does not use may be NULL. */
 int zkpoa_curve_prim(zkpoa_context* ctx, int group, int op, const void* a, const void* b, const uint32_t* k,
                      void* out, uint64_t n);
+/* The NTT's other forms on a host buffer, in place (parity tests). form: 0 = ntt_dif (natural in, bit-reversed out),
+ * 1 = ntt_dit (bit-reversed in, natural out), 2 = ntt_to_odd_coset (inverse ignored). No 1/n in forms 0 and 1.
+ * batch vectors of 2^log_n elements start stride elements apart (stride >= 2^log_n); elements between them are not
+ * touched. data holds ((batch - 1) * stride + 2^log_n) * 32 bytes. */
+int zkpoa_ntt_form(zkpoa_context* ctx, void* data, unsigned log_n, int form, int inverse, unsigned batch, uint64_t stride);
 
 #ifdef __cplusplus
 }

@@ -51,7 +51,7 @@ EXPORTS = [
     "zkpoa_gen_bases_g1_device", "zkpoa_gen_bases_g2_device",
     "zkpoa_g1_sum", "zkpoa_g2_sum", "zkpoa_g1_mul", "zkpoa_g2_mul",
     "zkpoa_setup_defer_host_frees", "zkpoa_last_ms", "zkpoa_set_option", "zkpoa_msm_points_limit", "zkpoa_field_op", "zkpoa_group_add",
-    "zkpoa_field_prim", "zkpoa_curve_prim",
+    "zkpoa_field_prim", "zkpoa_curve_prim", "zkpoa_ntt_form",
     "zkpoa_groth16_verify", "zkpoa_sanitize_proof", "zkpoa_groth16_verify_points", "zkpoa_zkey_vkey", "zkpoa_zkey_export_vkey",
     "zkpoa_zkey_read_h_scalars", "zkpoa_zkey_precompute",
     "zkpoa_context_stream", "zkpoa_context_synchronize",
@@ -145,6 +145,8 @@ def lib():
                                        ctypes.c_uint64, ctypes.c_int]
         L.zkpoa_curve_prim.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
+        L.zkpoa_ntt_form.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_uint, ctypes.c_uint64]
         L.zkpoa_zkey_load.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong, c_void_pp]
         L.zkpoa_zkey_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.zkpoa_zkey_free.restype = None
@@ -447,6 +449,18 @@ class Context:
         out = ctypes.create_string_buffer(max(1, 4 * fb * n))
         self._check(lib().zkpoa_curve_prim(self._h, group, op, pa, pb, pk, out, n), "zkpoa_curve_prim")
         return out.raw[:4 * fb * n]
+
+    def ntt_form(self, data, log_n, form, inverse=False, batch=1, stride=None):
+        """zkpoa_ntt_form: form 0 = DIF (natural in, bit-reversed out), 1 = DIT (bit-reversed in, natural out), 2 = to the
+        odd coset; `batch` vectors of 2^log_n elements, `stride` elements apart (default 2^log_n), transformed in a copy
+        of `data`, which is returned whole (the elements between the vectors included)."""
+        buf = bytearray(data)
+        p, k = _buf(buf)
+        stride = (1 << log_n) if stride is None else stride
+        if batch >= 1 and log_n <= 28 and len(buf) < ((batch - 1) * stride + (1 << log_n)) * 32:
+            raise ValueError("ntt_form: data is shorter than ((batch - 1) * stride + 2^log_n) * 32 bytes")
+        self._check(lib().zkpoa_ntt_form(self._h, p, log_n, form, 1 if inverse else 0, batch, stride), "zkpoa_ntt_form")
+        return bytes(buf)
 
     # ---- proving key + prove -----------------------------------------------------------------
     def load_zkey(self, zkey_bytes):

@@ -1,4 +1,4 @@
-// NTT translation unit: kernels from ntt.hip.h + the C-ABI entry points zkpoa_ntt / zkpoa_ntt_device.
+// NTT translation unit: kernels from ntt.hip.h + the C-ABI entry points zkpoa_ntt / zkpoa_ntt_device / zkpoa_ntt_form.
 #include "ntt.hip.h"
 #include "zkpoa_internal.hpp"
 
@@ -67,6 +67,29 @@ extern "C" int zkpoa_ntt(zkpoa_context* ctx, void* data, unsigned log_n, int inv
   ZK_HIP(hipMemcpy(d.p, data, bytes, hipMemcpyHostToDevice));
   int rc = zkpoa_ntt_device(ctx, d.p, log_n, inverse);
   if (rc != PROVER_OK) return rc;
+  ZK_HIP(hipMemcpy(data, d.p, bytes, hipMemcpyDeviceToHost));
+  ZK_API_END(ctx)
+}
+
+// The forms the prover and the split chain run (zkpoa_ntt reaches transform_natural only), on a host buffer.
+extern "C" int zkpoa_ntt_form(zkpoa_context* ctx, void* data, unsigned log_n, int form, int inverse, unsigned batch,
+                              uint64_t stride) {
+  ZK_API_BEGIN(ctx)
+  if (log_n > 28) throw HipError("ntt_form: log_n > 28 (two-adicity of Fr)");
+  if (form < 0 || form > 2) throw HipError("ntt_form: form is 0 (dif), 1 (dit) or 2 (to_odd_coset)");
+  if (batch == 0 || batch > 65535) throw HipError("ntt_form: batch is 1..65535 (grid.y)");
+  const uint64_t n = 1ull << log_n;
+  if (stride < n) throw HipError("ntt_form: stride < 2^log_n");
+  const size_t bytes = (size_t)((batch - 1) * stride + n) * 32;
+  DevBuf d(bytes);
+  d.up(data, bytes);
+  hipStream_t st = ctx->dev.lanes[0].stream;
+  ntt_prepare(ctx, st, log_n);
+  if (form == 0) ntt_dif(ctx, st, d.p, log_n, inverse != 0, batch, (size_t)stride * 32);
+  else if (form == 1) ntt_dit(ctx, st, d.p, log_n, inverse != 0, batch, (size_t)stride * 32);
+  else ntt_to_odd_coset(ctx, st, d.p, log_n, batch, (size_t)stride * 32);
+  ZK_HIP(hipStreamSynchronize(st));
+  ZK_HIP(hipGetLastError());
   ZK_HIP(hipMemcpy(data, d.p, bytes, hipMemcpyDeviceToHost));
   ZK_API_END(ctx)
 }
