@@ -425,12 +425,20 @@ int zkpoa_zkey_verify(zkpoa_context* ctx, const char* r1cs_path, const char* pta
  *   LAGRANGE_TAU_G1 / _TAU_G2 / _ALPHA / _BETA  section 12 / 13 / 14 / 15 agrees with section 2 / 3 / 4 / 5: per level
  *            of n points, sum_j P(w_n^j) L_j = sum_{i<n} rho_l^i X_i for P(x) = sum_{i<n} (rho_l x)^i (the top level
  *            p+1 of section 12 on the 2N - 1 powers that exist: P of degree 2N - 2)
+ *   CONTRIBUTIONS  section 7 (DESIGN.md "Phase-1 transcript") holds one or more records and they do not verify. With
+ *            prev = the generators and the challenge of a fresh file for record 0, for every record: a beacon's secrets
+ *            and g1_s recomputed from its bytes; e(g1_s, g2_spx) = e(g1_sx, g2_sp) for tau, alpha, beta (g2_sp from
+ *            the previous record's nextChallenge); tauG1, alphaG1, betaG1 against prev's with the key's ratio over
+ *            (g2_sp, g2_spx), tauG2 and betaG2 over (g1_s, g1_sx). For the last record: its five points are T_1, U_1,
+ *            A_0, B_0, beta2, and nextChallenge = Blake2b(response hash finished from partialHash and the key |
+ *            hash form of the file's sections 2-6, made on the device). A file with no record passes.
  * info[4] <- power, ceremony power, prepared (sections 12-15 present; 0 = only the powers were checked), the number of
- * contributions in section 7 (which is not checked otherwise: no transcript hash, no proof of knowledge).
+ * contribution records in section 7.
  * piece_points: points per upload as the sections stream through HBM (0 = derived from free HBM).
  * PROVER_ERROR (zkpoa_last_error) for a malformed file: bad magic or version, a non-BN254 header, a missing section 1-7,
  * a power outside [1, 28] (27 when prepared), a section whose length does not fit the power, only some of 12-15, a
- * coordinate >= q. */
+ * coordinate >= q, a section 7 that ends inside a record, has bytes left over, an unknown parameter tag or a type
+ * above 1. */
 #define ZKPOA_PTAU_POINTS 0x001u
 #define ZKPOA_PTAU_TAU_G1 0x002u
 #define ZKPOA_PTAU_TAU_G2 0x004u
@@ -440,6 +448,7 @@ int zkpoa_zkey_verify(zkpoa_context* ctx, const char* r1cs_path, const char* pta
 #define ZKPOA_PTAU_LAGRANGE_TAU_G2 0x040u
 #define ZKPOA_PTAU_LAGRANGE_ALPHA 0x080u
 #define ZKPOA_PTAU_LAGRANGE_BETA 0x100u
+#define ZKPOA_PTAU_CONTRIBUTIONS 0x200u
 int zkpoa_ptau_verify(zkpoa_context* ctx, const char* ptau_path, uint64_t piece_points, uint32_t* failed_checks,
                       uint32_t info[4]);
 /* The inverse NTT whose elements are curve points (ffjavascript's G.ifft), the arithmetic of `powersoftau prepare
@@ -461,6 +470,48 @@ int zkpoa_ec_intt_device(zkpoa_context* ctx, int group, const void* d_in, uint32
  * written under a temporary name and renamed when complete: a failure leaves nothing behind and a file already at
  * out_path untouched. */
 int zkpoa_ptau_prepare_phase2(zkpoa_context* ctx, const char* in_path, const char* out_path, uint32_t info[4]);
+/* ---- making and extending a ceremony file: `snarkjs powersoftau new / contribute / beacon` (DESIGN.md "Phase-1
+ * transcript"). The layout of section 7 follows snarkjs as far as it is known to this project; no file made by snarkjs
+ * has been read or written against, so interoperability is not exercised.
+ * zkpoa_scalar_mul_each_device: d_out[i] = k_i * P_i, i < n < 2^32. Device pointers; points in wire format (affine,
+ *   Montgomery, coordinates < q, infinity all-zero; group = 1 | 2), scalars 32 B little-endian standard form < r (a
+ *   larger one is PROVER_ERROR), output wire format with canonical coordinates; d_out may equal d_points. Complete for
+ *   P = O, k = 0 and every coincidence inside the walk. Every lane walks 64 signed 4-bit windows whatever its scalar.
+ * zkpoa_power_scalars_device: d_out[i] = first * ratio^(i0 + i), i < n, 32 B little-endian standard form (device).
+ * zkpoa_compressed_form: as zkpoa_hash_form, in the compressed form of a point: x alone (big-endian standard form, Fq2
+ *   as c1 then c0; 32 B for G1, 64 B for G2), bit 7 of byte 0 set when y is the negative root (above (q - 1) / 2; for
+ *   Fq2 by c1, by c0 when c1 = 0), infinity = 0x40 then zeros. */
+int zkpoa_scalar_mul_each_device(zkpoa_context* ctx, int group, const void* d_points, const void* d_scalars, uint64_t n,
+                                 void* d_out);
+int zkpoa_power_scalars_device(zkpoa_context* ctx, const uint8_t first_le[32], const uint8_t ratio_le[32], uint64_t i0,
+                               uint64_t n, void* d_out);
+int zkpoa_compressed_form(zkpoa_context* ctx, int group, const void* points, uint64_t n, uint64_t piece_points,
+                          void* out_bytes, uint8_t digest[64]);
+/* `powersoftau new bn128 <power> <out>`: sections 1-6 with every point the generator, section 7 with no record;
+ * power in [1, 28]. */
+int zkpoa_ptau_new(zkpoa_context* ctx, uint32_t power, const char* out_path);
+/* `powersoftau contribute <in> <out>`: point i of section 2 and 3 times tau^i, of section 4 times alpha tau^i, of
+ * section 5 times beta tau^i, section 6 times beta (zkpoa_power_scalars_device, zkpoa_scalar_mul_each_device), the
+ * sections streamed through device memory in pieces (option "ptau_piece_points"; 0 = from free memory), and one record
+ * appended to section 7. secrets_le: tau | alpha | beta, 3 x 32 B little-endian in [1, r), or NULL = /dev/urandom.
+ * ZKPOA_PHASE1_S in the environment ("s_tau,s_alpha,s_beta", decimal or 0x hex) fixes the s of the key's g1_s = s G1
+ * (tests only; a warning is printed). The input is validated as zkpoa_ptau_prepare_phase2 validates it; its sections
+ * 12-15 are dropped (a notice on stderr). The output appears under its name only when complete; an output path that
+ * names the input is refused. name: optional, at most 255 bytes. */
+int zkpoa_ptau_contribute(zkpoa_context* ctx, const char* in_path, const char* out_path, const uint8_t* secrets_le,
+                          const char* name);
+/* `powersoftau beacon <in> <out> <beaconHash> <numIterationsExp>`: a contribution whose secrets and g1_s come from the
+ * ChaCha generator of zkpoa_beacon_key (per key tau, alpha, beta: the secret, then g1_s); a type-1 record. Exponents
+ * above 30 and beacons above 255 bytes are refused. */
+int zkpoa_ptau_beacon(zkpoa_context* ctx, const char* in_path, const char* out_path, const uint8_t* beacon,
+                      unsigned long beacon_len, uint32_t num_iterations_exp, const char* name);
+/* Host only: *count <- the records of section 7, text (optional) <- one line "contribution <name> <response hash, hex>"
+ * or "beacon <name> <response hash, hex>" per record. PROVER_ERROR for an unreadable file or a malformed section 7. */
+int zkpoa_ptau_contributions(const char* ptau_path, uint32_t* count, char* text, unsigned long cap);
+/* The Blake2b state a record's partialHash holds (216 B: h[8], t[2], the 128-byte buffer, its fill; little-endian u64,
+ * buffer bytes past the fill zero). zkpoa_blake2b_restore: a new state to update / final, or NULL for a fill above 128. */
+int zkpoa_blake2b_state(void* state, uint8_t out[216]);
+void* zkpoa_blake2b_restore(const uint8_t saved[216]);
 
 /* ---- the step after the path; host only, no GPU ----------------------------------------
  * zkpoa_groth16_verify: `npx snarkjs groth16 verify <vkey> <public> <proof>` (scripts/g16_verify.sh:213-216)

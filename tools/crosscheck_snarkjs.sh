@@ -24,7 +24,46 @@
 #   b. `snarkjs zkey verify r1cs ptau <that key>`            -> must print "ZKey Ok!"
 #   c. `snarkjs zkey new`, `zkey contribute`, `zkey beacon` -> `zkpoa-setup zkey verify` on snarkjs' key must exit 0
 #   d. both initial keys must carry the same circuit hash (section 10's first 64 bytes: same r1cs, same ptau)
+#
+#   tools/crosscheck_snarkjs.sh --ptau-trail <power> [workdir]
+#
+# The phase-1 transcript: is a ceremony file made HERE accepted by `snarkjs powersoftau verify`,
+# and one made by snarkjs by `zkpoa-setup powersoftau verify`? Never run so far:
+#   a. `zkpoa-setup powersoftau new`, `contribute --name=...`, `beacon <hex> 10`, `prepare phase2`, `verify`
+#   b. `snarkjs powersoftau verify <that file>`             -> must print "Powers of Tau Ok!"
+#   c. `snarkjs powersoftau new`, `contribute`, `beacon`, `prepare phase2` -> `zkpoa-setup powersoftau verify` must exit 0
+#   d. the two fresh files must be the same file (every point the generator, no record)
 set -euo pipefail
+
+if [ "${1:-}" = "--ptau-trail" ]; then
+  POWER=${2:?usage: crosscheck_snarkjs.sh --ptau-trail <power> [workdir]}
+  WORK=${3:-$(mktemp -d)}
+  HERE=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
+  SETUP="$HERE/zk-proof-of-assets_amd/zkpoa-setup"
+  SNARKJS=${SNARKJS:-npx snarkjs}
+  BEACON=0102030405060708090a0b0c0d0e0f101112131415161718191a1b1c1d1e1f
+  mkdir -p "$WORK"
+  echo "== a. a ceremony file made here"
+  "$SETUP" powersoftau new bn128 "$POWER" "$WORK/ours_0.ptau"
+  "$SETUP" powersoftau contribute "$WORK/ours_0.ptau" "$WORK/ours_1.ptau" --name="First contributor"
+  "$SETUP" powersoftau beacon "$WORK/ours_1.ptau" "$WORK/ours_2.ptau" "$BEACON" 10 --name="Final Beacon"
+  "$SETUP" powersoftau prepare phase2 "$WORK/ours_2.ptau" "$WORK/ours_final.ptau"
+  "$SETUP" powersoftau verify "$WORK/ours_final.ptau"
+  echo "== b. snarkjs powersoftau verify on it"
+  $SNARKJS powersoftau verify "$WORK/ours_final.ptau" | tee "$WORK/snarkjs_ptau_verify.log"
+  grep -q "Powers of Tau Ok!" "$WORK/snarkjs_ptau_verify.log"
+  echo "== c. a ceremony file made by snarkjs, verified here"
+  $SNARKJS powersoftau new bn128 "$POWER" "$WORK/sj_0.ptau"
+  $SNARKJS powersoftau contribute "$WORK/sj_0.ptau" "$WORK/sj_1.ptau" --name="First contributor" -e="random text"
+  $SNARKJS powersoftau beacon "$WORK/sj_1.ptau" "$WORK/sj_2.ptau" "$BEACON" 10 -n="Final Beacon"
+  $SNARKJS powersoftau prepare phase2 "$WORK/sj_2.ptau" "$WORK/sj_final.ptau"
+  "$SETUP" powersoftau verify "$WORK/sj_final.ptau"
+  echo "== d. the two fresh files must be the same file"
+  cmp "$WORK/ours_0.ptau" "$WORK/sj_0.ptau"
+  echo "crosscheck OK: snarkjs accepts our trail, we accept snarkjs' trail, the fresh files are identical"
+  echo "(files kept in $WORK)"
+  exit 0
+fi
 
 if [ "${1:-}" = "--zkey-trail" ]; then
   R1CS=${2:?usage: crosscheck_snarkjs.sh --zkey-trail <circuit.r1cs> <pot.ptau> [workdir]}

@@ -31,7 +31,8 @@ ZKEY_CHECKS = {"HEADER": 0x01, "POINTS": 0x02, "DELTA": 0x04, "COEFFS": 0x08, "A
 SETUP_TRANSCRIPT = 0x1      # zkpoa_zkey_new_ex: fill in section 10's circuit hash (ZKPOA_SETUP_TRANSCRIPT)
 # the bits of zkpoa_ptau_verify's result (include/zkpoa_prover.h ZKPOA_PTAU_*)
 PTAU_CHECKS = {"POINTS": 0x001, "TAU_G1": 0x002, "TAU_G2": 0x004, "ALPHA": 0x008, "BETA": 0x010,
-               "LAGRANGE_TAU_G1": 0x020, "LAGRANGE_TAU_G2": 0x040, "LAGRANGE_ALPHA": 0x080, "LAGRANGE_BETA": 0x100}
+               "LAGRANGE_TAU_G1": 0x020, "LAGRANGE_TAU_G2": 0x040, "LAGRANGE_ALPHA": 0x080, "LAGRANGE_BETA": 0x100,
+               "CONTRIBUTIONS": 0x200}
 
 # every symbol include/zkpoa_prover.h declares
 EXPORTS = [
@@ -64,6 +65,9 @@ EXPORTS = [
     "zkpoa_chacha_new", "zkpoa_chacha_next_u32", "zkpoa_chacha_next_u64", "zkpoa_chacha_next_bool", "zkpoa_chacha_free",
     "zkpoa_fq_sqrt", "zkpoa_fq2_sqrt", "zkpoa_fr_from_rng", "zkpoa_g1_from_rng", "zkpoa_g2_from_rng", "zkpoa_hash_to_g2",
     "zkpoa_beacon_key",
+    "zkpoa_scalar_mul_each_device", "zkpoa_power_scalars_device", "zkpoa_compressed_form",
+    "zkpoa_ptau_new", "zkpoa_ptau_contribute", "zkpoa_ptau_beacon", "zkpoa_ptau_contributions",
+    "zkpoa_blake2b_state", "zkpoa_blake2b_restore",
 ]
 
 
@@ -168,6 +172,20 @@ def lib():
                                                ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p, ctypes.c_ulong]
         L.zkpoa_hash_form.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64,
                                       ctypes.c_void_p, ctypes.c_char_p]
+        L.zkpoa_compressed_form.argtypes = L.zkpoa_hash_form.argtypes
+        L.zkpoa_scalar_mul_each_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_uint64, ctypes.c_void_p]
+        L.zkpoa_power_scalars_device.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint64,
+                                                 ctypes.c_uint64, ctypes.c_void_p]
+        L.zkpoa_ptau_new.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_char_p]
+        L.zkpoa_ptau_contribute.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
+                                            ctypes.c_char_p]
+        L.zkpoa_ptau_beacon.argtypes = L.zkpoa_zkey_beacon.argtypes
+        L.zkpoa_ptau_contributions.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p,
+                                               ctypes.c_ulong]
+        L.zkpoa_blake2b_state.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
+        L.zkpoa_blake2b_restore.argtypes = [ctypes.c_char_p]
+        L.zkpoa_blake2b_restore.restype = ctypes.c_void_p
         L.zkpoa_h_diff.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
         L.zkpoa_blake2b512.argtypes = [ctypes.c_char_p, ctypes.c_ulong, ctypes.c_char_p]
         L.zkpoa_blake2b_new.restype = ctypes.c_void_p
@@ -556,6 +574,44 @@ class Context:
         out, dg = ctypes.create_string_buffer(max(1, n * unit)), ctypes.create_string_buffer(64)
         self._check(lib().zkpoa_hash_form(self._h, group, bytes(points), n, piece_points, out, dg), "zkpoa_hash_form")
         return out.raw[:n * unit], dg.raw
+
+    def compressed_form(self, group, points, piece_points=0):
+        """Compressed form of wire-form points, converted on the device in pieces: -> (bytes, Blake2b-512 digest)."""
+        unit = 64 if group == 1 else 128
+        n = len(points) // unit
+        out, dg = ctypes.create_string_buffer(max(1, n * unit // 2)), ctypes.create_string_buffer(64)
+        self._check(lib().zkpoa_compressed_form(self._h, group, bytes(points), n, piece_points, out, dg),
+                    "zkpoa_compressed_form")
+        return out.raw[:n * unit // 2], dg.raw
+
+    def scalar_mul_each(self, group, d_points, d_scalars, n, d_out):
+        """d_out[i] = k_i * P_i over n points of G1 (group 1) or G2 (2): device pointers as ints, points in wire format,
+        scalars 32 B little-endian below r (include/zkpoa_prover.h: zkpoa_scalar_mul_each_device)."""
+        self._check(lib().zkpoa_scalar_mul_each_device(self._h, group, d_points, d_scalars, n, d_out),
+                    "zkpoa_scalar_mul_each_device")
+
+    def power_scalars(self, first, ratio, i0, n, d_out):
+        """d_out[i] = first * ratio^(i0 + i), i < n, 32 B little-endian (device pointer as int)."""
+        self._check(lib().zkpoa_power_scalars_device(self._h, int(first).to_bytes(32, "little"),
+                                                     int(ratio).to_bytes(32, "little"), i0, n, d_out),
+                    "zkpoa_power_scalars_device")
+
+    def ptau_new(self, power, out_path):
+        """`snarkjs powersoftau new bn128 <power> <out>`: every point the generator, no contribution record."""
+        self._check(lib().zkpoa_ptau_new(self._h, power, os.fsencode(out_path)), "zkpoa_ptau_new")
+
+    def ptau_contribute(self, in_path, out_path, secrets=None, name=None):
+        """`snarkjs powersoftau contribute`: secrets = (tau, alpha, beta), ints in [1, r), None = random; appends a
+        record to section 7 (include/zkpoa_prover.h: zkpoa_ptau_contribute)."""
+        sec = None if secrets is None else b"".join(int(x).to_bytes(32, "little") for x in secrets)
+        self._check(lib().zkpoa_ptau_contribute(self._h, os.fsencode(in_path), os.fsencode(out_path), sec,
+                                                None if name is None else name.encode()), "zkpoa_ptau_contribute")
+
+    def ptau_beacon(self, in_path, out_path, beacon, num_iterations_exp, name=None):
+        """`snarkjs powersoftau beacon`: beacon bytes, 2^num_iterations_exp SHA-256 iterations (at most 2^30)."""
+        self._check(lib().zkpoa_ptau_beacon(self._h, os.fsencode(in_path), os.fsencode(out_path), bytes(beacon),
+                                            len(beacon), num_iterations_exp, None if name is None else name.encode()),
+                    "zkpoa_ptau_beacon")
 
     def h_diff(self, points, n):
         """points[i + n] - points[i], i < n - 1, over 2n - 1 wire-form G1 points (device)."""
@@ -946,6 +1002,39 @@ def g1_mul(point, k):
 def g2_mul(point, k):
     out = ctypes.create_string_buffer(128)
     lib().zkpoa_g2_mul(point, int(k).to_bytes(32, "little"), out)
+    return out.raw
+
+
+def ptau_contributions(ptau_path):
+    """Host only: -> (count, ["contribution <name> <response hash>" | "beacon <name> <response hash>", ...]) of a .ptau's
+    section 7; ZkpoaError for an unreadable file or a malformed section."""
+    cnt = ctypes.c_uint32(0)
+    if lib().zkpoa_ptau_contributions(os.fsencode(ptau_path), ctypes.byref(cnt), None, 0):
+        raise ZkpoaError("zkpoa_ptau_contributions failed")
+    text = ctypes.create_string_buffer(int(cnt.value) * 400 + 1)          # a line is at most 13 + 255 + 1 + 128 + 1 bytes
+    if lib().zkpoa_ptau_contributions(os.fsencode(ptau_path), ctypes.byref(cnt), text, len(text)):
+        raise ZkpoaError("zkpoa_ptau_contributions failed")
+    return int(cnt.value), text.value.decode().splitlines()
+
+
+def blake2b_state(data):
+    """The 216-byte Blake2b-512 state after `data` (a contribution record's partialHash form)."""
+    h = lib().zkpoa_blake2b_new()
+    lib().zkpoa_blake2b_update(h, bytes(data), len(data))
+    out = ctypes.create_string_buffer(216)
+    lib().zkpoa_blake2b_state(h, out)
+    lib().zkpoa_blake2b_final(h, ctypes.create_string_buffer(64))
+    return out.raw
+
+
+def blake2b_resume(state, data):
+    """The digest of a saved state continued with `data`; ZkpoaError for a state that cannot be one."""
+    h = lib().zkpoa_blake2b_restore(bytes(state))
+    if not h:
+        raise ZkpoaError("zkpoa_blake2b_restore: not a Blake2b state")
+    lib().zkpoa_blake2b_update(h, bytes(data), len(data))
+    out = ctypes.create_string_buffer(64)
+    lib().zkpoa_blake2b_final(h, out)
     return out.raw
 
 

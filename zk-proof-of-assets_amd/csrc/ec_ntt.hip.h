@@ -37,14 +37,10 @@ namespace zkpoa {
 constexpr uint32_t kEcNttThreads = 64;   // butterflies per workgroup
 constexpr uint32_t kEcNttRun = 16;       // points per inversion in the store pass
 
-// [t] q for t in Montgomery form (any element of Fr)
+// [k] q for k in standard form, canonical (below r); k is used up
 template <class F>
-ZK_DEV XYZZ<F> ec_ntt_mul(const XYZZ<F>& q, const Fr& t_mont) {
+ZK_DEV XYZZ<F> ec_mul_windowed(const XYZZ<F>& q, uint32_t (&k)[8]) {
   if (q.is_inf()) return q;
-  const Fr t = t_mont.from_mont().canon();
-  uint32_t k[8];
-#pragma unroll
-  for (int i = 0; i < 8; i++) k[i] = t.l[i];
   const bool neg = scalar_normalize(k);   // k <= (r - 1) / 2 < 2^253
   // signed digits d_i in [-7, 8], k = sum d_i 16^i: magnitudes packed as nibbles, signs as a bit mask
   uint32_t mag[8];
@@ -91,6 +87,16 @@ ZK_DEV XYZZ<F> ec_ntt_mul(const XYZZ<F>& q, const Fr& t_mont) {
     }
   }
   return acc;
+}
+
+// [t] q for t in Montgomery form (any element of Fr)
+template <class F>
+ZK_DEV XYZZ<F> ec_ntt_mul(const XYZZ<F>& q, const Fr& t_mont) {
+  const Fr t = t_mont.from_mont().canon();
+  uint32_t k[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) k[i] = t.l[i];
+  return ec_mul_windowed(q, k);
 }
 
 // W[p] = in[bitrev_k(p)] as XYZZ; W[0] and W[1] times 1 / n (k > 0)

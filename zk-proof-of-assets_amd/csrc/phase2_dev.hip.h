@@ -32,6 +32,48 @@ static __global__ __launch_bounds__(256) void hash_form_kernel(const uint4* __re
   out[2 * o + 1] = lo;
 }
 
+// Wire form -> compressed form (DESIGN.md "Phase-1 transcript": what a contribution's response hash covers). One lane
+// per point: x alone, big-endian standard form (G2: c1 then c0), bit 7 of the first byte set when y is the negative
+// root (standard form above (q - 1) / 2; for Fq2 the sign of c1, of c0 when c1 = 0 -- the sign rule of `fromRng`), a point
+// whose coordinates are all zero is infinity: 0x40 then zeros. q < 2^254 leaves both bits free.
+ZK_DEV bool fq_std_negative(const Fq& s) {   // s: standard form, canonical
+  constexpr uint32_t kHalfQ[8] = {0x6c3e7ea3u, 0x9e10460bu, 0xb438e546u, 0xcbc0b548u,
+                                  0x40c0ac2eu, 0xdc2822dbu, 0x7098d014u, 0x18322739u};
+  uint32_t bw = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) (void)subb(kHalfQ[k], s.l[k], bw);
+  return bw != 0;
+}
+ZK_DEV bool fq_std_zero(const Fq& s) {
+  uint32_t nz = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) nz |= s.l[k];
+  return nz == 0;
+}
+ZK_DEV void store_be(uint4* out, const Fq& s, uint32_t flag) {
+  out[0] = make_uint4(__builtin_bswap32(s.l[7]) | flag, __builtin_bswap32(s.l[6]), __builtin_bswap32(s.l[5]), __builtin_bswap32(s.l[4]));
+  out[1] = make_uint4(__builtin_bswap32(s.l[3]), __builtin_bswap32(s.l[2]), __builtin_bswap32(s.l[1]), __builtin_bswap32(s.l[0]));
+}
+template <class F>
+static __global__ __launch_bounds__(256) void compressed_form_kernel(const void* __restrict__ in, uint4* __restrict__ out,
+                                                                     uint64_t count) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= count) return;
+  const Affine<F> p = load_affine<F>(in, i);
+  if constexpr (std::is_same<F, Fq>::value) {
+    const Fq x = p.x.from_mont().canon(), y = p.y.from_mont().canon();
+    const bool inf = fq_std_zero(x) && fq_std_zero(y);
+    store_be(out + 2 * i, x, inf ? 0x40u : (fq_std_negative(y) ? 0x80u : 0u));
+  } else {
+    const Fq x0 = p.x.c0.from_mont().canon(), x1 = p.x.c1.from_mont().canon();
+    const Fq y0 = p.y.c0.from_mont().canon(), y1 = p.y.c1.from_mont().canon();
+    const bool inf = fq_std_zero(x0) && fq_std_zero(x1) && fq_std_zero(y0) && fq_std_zero(y1);
+    const bool neg = fq_std_zero(y1) ? fq_std_negative(y0) : fq_std_negative(y1);
+    store_be(out + 4 * i, x1, inf ? 0x40u : (neg ? 0x80u : 0u));
+    store_be(out + 4 * i + 2, x0, 0u);
+  }
+}
+
 // out[i] = T[i + n] - T[i], i < count (count = n - 1), affine wire form in and out. Thread t takes the points
 // t, t + threads, ... (kBatch of them, coalesced across the wave) and divides their slopes with ONE inversion
 // (Montgomery's trick over the lane's batch). Exceptional cases: either operand at infinity, T[i+n] = T[i] (result
@@ -127,16 +169,19 @@ struct HashStream {
   }
   HashStream(const HashStream&) = delete;
   HashStream& operator=(const HashStream&) = delete;
-  // `count` points of group 1 / 2 at d (wire form), preceded by their big-endian count when with_count
-  void points(const void* d, uint64_t count, int group, bool with_count) {
+  // `count` points of group 1 / 2 at d (wire form), preceded by their big-endian count when with_count; compressed: the
+  // compressed form (half the bytes) instead of the hash form
+  void points(const void* d, uint64_t count, int group, bool with_count, bool compressed = false) {
     if (with_count) hasher.update_u32_be((uint32_t)count);
-    const uint64_t unit = group == 1 ? 64 : 128, per_piece = piece_bytes / unit;
+    const uint64_t in_unit = group == 1 ? 64 : 128, unit = compressed ? in_unit / 2 : in_unit, per_piece = piece_bytes / in_unit;
     hipStream_t st = ctx->dev.lanes[0].stream;
     auto issue = [&](uint64_t first, int b) {
-      const uint64_t cnt = std::min(per_piece, count - first), coords = cnt * (unit / 32);
-      const uint4* src = reinterpret_cast<const uint4*>(static_cast<const char*>(d) + first * unit);
-      const dim3 grid((uint32_t)((coords + 255) / 256));
-      if (group == 1) hipLaunchKernelGGL((hash_form_kernel<2>), grid, dim3(256), 0, st, src, (uint4*)d_stage[b], coords);
+      const uint64_t cnt = std::min(per_piece, count - first), coords = cnt * (in_unit / 32);
+      const uint4* src = reinterpret_cast<const uint4*>(static_cast<const char*>(d) + first * in_unit);
+      const dim3 grid((uint32_t)((coords + 255) / 256)), pgrid((uint32_t)((cnt + 255) / 256));
+      if (compressed && group == 1) hipLaunchKernelGGL((compressed_form_kernel<Fq>), pgrid, dim3(256), 0, st, (const void*)src, (uint4*)d_stage[b], cnt);
+      else if (compressed) hipLaunchKernelGGL((compressed_form_kernel<Fq2>), pgrid, dim3(256), 0, st, (const void*)src, (uint4*)d_stage[b], cnt);
+      else if (group == 1) hipLaunchKernelGGL((hash_form_kernel<2>), grid, dim3(256), 0, st, src, (uint4*)d_stage[b], coords);
       else hipLaunchKernelGGL((hash_form_kernel<4>), grid, dim3(256), 0, st, src, (uint4*)d_stage[b], coords);
       ZK_HIP(hipMemcpyAsync(pinned[b], d_stage[b], cnt * unit, hipMemcpyDeviceToHost, st));
       ZK_HIP(hipEventRecord(ev[b], st));
@@ -158,6 +203,24 @@ struct HashStream {
     ZK_HIP(hipGetLastError());
   }
 };
+
+// The hash form of sections 2-6 of a ceremony file of 2^power (fd, its section table) into hs's hasher: what a
+// contribution's nextChallenge covers. The sections stream through d_piece (piece_points x 128 B of device memory).
+inline void hash_form_ptau_sections(zkpoa_context* ctx, HashStream& hs, int fd, std::map<uint32_t, Sec>& ps, uint32_t power,
+                                    void* d_piece, uint64_t piece_points) {
+  const uint64_t N = 1ull << power;
+  const uint64_t count[7] = {0, 0, 2 * N - 1, N, N, N, 1};
+  hipStream_t st = ctx->dev.lanes[0].stream;
+  for (uint32_t t = 2; t <= 6; t++) {
+    const int group = t == 3 || t == 6 ? 2 : 1;
+    const uint64_t unit = group == 2 ? 128 : 64;
+    for (uint64_t i0 = 0; i0 < count[t]; i0 += piece_points) {
+      const uint64_t cnt = std::min(piece_points, count[t] - i0);
+      ctx->uploader.upload(d_piece, nullptr, cnt * unit, ctx->dev.device, st, fd, ps[t].off + i0 * unit);
+      hs.points(d_piece, cnt, group, false);
+    }
+  }
+}
 
 // d_out[i] = T[i + n] - T[i] for i < n - 1 (T: the ptau's tau^i G1, at least 2n - 1 points on the device)
 inline void h_diff(zkpoa_context* ctx, const void* d_T, uint64_t n, void* d_out) {

@@ -17,7 +17,11 @@
 // The weights are made on the device per piece (power tables by thread runs; the Lagrange side's 1 / (1 - rho w^j) by a
 // batched inversion, Montgomery's trick per thread run). Each section streams through HBM in pieces: upload from the
 // file, point checks (curve, range, G2 subgroup), MSMs with the piece's weights; the partial sums are added on the host.
-// Section 7 (contribution transcript) is read for its count only.
+// Section 7 (DESIGN.md "Phase-1 transcript"): its records are checked on the host (csrc/phase1.hpp: keys, ratios, the
+// beacon, the last record against the file's points); the last nextChallenge needs the hash form of sections 2-6, which
+// streams from the file through the device conversion of csrc/phase2_dev.hip.h into Blake2b.
+#include "phase1.hpp"
+#include "phase2_dev.hip.h"
 #include "setup_common.hip.h"
 #include "zkpoa_internal.hpp"
 
@@ -240,6 +244,12 @@ uint32_t ptau_verify(zkpoa_context* ctx, const char* path, uint64_t piece_points
   info[1] = shape.ceremony;
   info[2] = prepared ? 1 : 0;
   info[3] = shape.contributions;
+  std::vector<zkpoa::phase1::Record> records;
+  try {
+    records = zkpoa::phase1::parse_section7(fp.p + ps[7].off, ps[7].len);
+  } catch (const std::runtime_error& e) {
+    throw SetupError(e.what());
+  }
   phase("sections");
 
   // ---- random weights: one rho per power section (ratio checks), one rho_l per level (Lagrange checks)
@@ -351,6 +361,22 @@ uint32_t ptau_verify(zkpoa_context* ctx, const char* path, uint64_t piece_points
     if (!xyzz_sub(lB, sB).is_inf()) failed |= ZKPOA_PTAU_LAGRANGE_BETA;
   }
   phase("pairings");
+  // ---- section 7: the records, then the last nextChallenge over the file's own sections 2-6
+  if (!records.empty()) {
+    uint8_t response[64], next[64];
+    bool ok = zkpoa::phase1::verify_records(records, power, pT + 64, pU + 128, pA, pB, pb2, response);
+    phase("contribution records (host)");
+    if (ok) {
+      zkpoa::phase2::Blake2b h;
+      h.update(response, 64);
+      HashStream hs(ctx, h, 0);
+      hash_form_ptau_sections(ctx, hs, fp.fd, ps, power, sm.pts.p, sm.piece);
+      h.final(next);
+      ok = !memcmp(next, records.back().next_challenge, 64);
+      phase("nextChallenge (device hash form, Blake2b)");
+    }
+    if (!ok) failed |= ZKPOA_PTAU_CONTRIBUTIONS;
+  }
   return failed;
 }
 

@@ -7,6 +7,9 @@
 //     snarkjs zkey verify <circuit.r1cs> <pot.ptau> <circuit_final.zkey>                    (scripts/g16_verify.sh -z)
 //     snarkjs powersoftau verify <pot.ptau>              (the TODO at g16_setup.sh:201 and g16_verify.sh:164)
 //     snarkjs powersoftau prepare phase2 <in.ptau> <out.ptau>     (what makes a ceremony file usable by the commands above)
+//     snarkjs powersoftau new bn128 <power> <out.ptau>            (snarkjs README steps 1-4 and 6: the ceremony file itself,
+//     snarkjs powersoftau contribute <in.ptau> <out.ptau>          which the reference downloads,
+//     snarkjs powersoftau beacon <in> <out> <beaconHash(hex)> <numIterationsExp>   scripts/machine_initialization.sh:377-385)
 // Same three file arguments (the words `zkey new` / `groth16 setup` are accepted and ignored, so the command line
 // can be kept as it is with the executable swapped). The .ptau must be prepared for phase 2, as snarkjs requires too:
 // `zkpoa-setup powersoftau prepare phase2` does that here. Exit status 0 / non-zero + message on stderr.
@@ -14,6 +17,9 @@
 // `zkey new ... --transcript` fills in the circuit hash; on such a key `zkey contribute` appends a record (--name= / -n=
 // is kept in it), `zkey beacon` works, and `zkey verify` checks the hash and every record. Without the option every
 // command writes and accepts what it did before. Acceptance of these keys by `snarkjs zkey verify` is not exercised.
+// The phase-1 transcript (a .ptau's section 7; DESIGN.md "Phase-1 transcript") is written by `powersoftau contribute` and
+// `powersoftau beacon` and checked by `powersoftau verify`. Acceptance of these files by `snarkjs powersoftau verify`
+// is not exercised.
 #include "../../include/zkpoa_prover.h"
 
 #include "worker_exit.hpp"
@@ -22,6 +28,18 @@
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
+
+// the record lines of a .ptau's section 7 ("<type> <name> <response hash>\n" each), sized from the record count: a
+// public ceremony's file holds scores of records with long names. Empty when the section cannot be read.
+#include <string>
+static std::string ptau_record_lines(const char* path, uint32_t* count) {
+  *count = 0;
+  if (zkpoa_ptau_contributions(path, count, nullptr, 0) != PROVER_OK || !*count) return std::string();
+  std::string text((size_t)*count * (13 + 255 + 1 + 128 + 1) + 1, '\0');
+  if (zkpoa_ptau_contributions(path, count, &text[0], (unsigned long)text.size()) != PROVER_OK) return std::string();
+  text.resize(strlen(text.c_str()));
+  return text;
+}
 
 static bool parse_decimal_or_hex(const char* s, uint8_t out[32]) {   // ZKPOA_DELTA: decimal, or 0x... hex; < 2^256
   memset(out, 0, 32);
@@ -76,6 +94,7 @@ static bool delta2_is_gamma2(const char* zkey_path) {
 int main(int argc, char** argv) {
   int a = 1;
   bool contribute = false, check = false, verify = false, pverify = false, beacon = false, prepare = false;
+  bool pnew = false, pcontribute = false, pbeacon = false;
   if (argc - a >= 2 && !strcmp(argv[a], "zkey") && !strcmp(argv[a + 1], "beacon")) {
     beacon = true;
     a += 2;
@@ -91,6 +110,15 @@ int main(int argc, char** argv) {
   } else if (argc - a >= 3 && !strcmp(argv[a], "powersoftau") && !strcmp(argv[a + 1], "prepare") && !strcmp(argv[a + 2], "phase2")) {
     prepare = true;
     a += 3;
+  } else if (argc - a >= 2 && !strcmp(argv[a], "powersoftau") && !strcmp(argv[a + 1], "new")) {
+    pnew = true;
+    a += 2;
+  } else if (argc - a >= 2 && !strcmp(argv[a], "powersoftau") && !strcmp(argv[a + 1], "contribute")) {
+    pcontribute = true;
+    a += 2;
+  } else if (argc - a >= 2 && !strcmp(argv[a], "powersoftau") && !strcmp(argv[a + 1], "beacon")) {
+    pbeacon = beacon = true;   // the same beacon arguments as `zkey beacon`
+    a += 2;
   } else if (argc - a >= 2 && !strcmp(argv[a], "wtns") && !strcmp(argv[a + 1], "check")) {
     check = true;
     a += 2;
@@ -115,7 +143,7 @@ int main(int argc, char** argv) {
     if (npos < 4) pos[npos] = argv[i];
     npos++;
   }
-  if (npos != (pverify ? 1 : (beacon ? 4 : (contribute || check || prepare ? 2 : 3)))) {
+  if (npos != (pverify ? 1 : (beacon ? 4 : (contribute || check || prepare || pcontribute ? 2 : 3)))) {
     fprintf(stderr, "usage: zkpoa-setup [zkey new | groth16 setup] <circuit.r1cs> <pot.ptau> <circuit_0.zkey>\n"
                     "         [--transcript]   fill in section 10's circuit hash (needs the ptau's section 2)\n"
                     "       zkpoa-setup zkey contribute <in.zkey> <out.zkey> [--name=...] [-e=...]\n"
@@ -123,8 +151,22 @@ int main(int argc, char** argv) {
                     "       zkpoa-setup wtns check <circuit.r1cs> <witness.wtns>\n"
                     "       zkpoa-setup zkey verify <circuit.r1cs> <pot.ptau> <circuit.zkey>\n"
                     "       zkpoa-setup powersoftau verify <pot.ptau>\n"
-                    "       zkpoa-setup powersoftau prepare phase2 <in.ptau> <out.ptau>\n");
+                    "       zkpoa-setup powersoftau prepare phase2 <in.ptau> <out.ptau>\n"
+                    "       zkpoa-setup powersoftau new bn128 <power> <out.ptau>\n"
+                    "       zkpoa-setup powersoftau contribute <in.ptau> <out.ptau> [--name=...]\n"
+                    "         (-e=<entropy> is accepted and ignored: the secrets come from /dev/urandom)\n"
+                    "       zkpoa-setup powersoftau beacon <in.ptau> <out.ptau> <beaconHash(hex)> <numIterationsExp> [--name=...]\n");
     return 2;
+  }
+  unsigned new_power = 0;
+  if (pnew) {
+    char* end = nullptr;
+    const long v = strtol(pos[1], &end, 10);
+    if ((strcmp(pos[0], "bn128") && strcmp(pos[0], "bn254")) || end == pos[1] || *end || v < 1 || v > 28) {
+      fprintf(stderr, "zkpoa-setup: powersoftau new: the curve must be bn128 and the power in [1, 28]\n");
+      return 2;
+    }
+    new_power = (unsigned)v;
   }
   uint8_t delta[32];
   const uint8_t* delta_p = nullptr;
@@ -158,7 +200,7 @@ int main(int argc, char** argv) {
     char* end = nullptr;
     const long e = strtol(pos[3], &end, 10);
     if (!ok || end == pos[3] || *end || e < 0 || e > 30) {
-      fprintf(stderr, "zkpoa-setup: zkey beacon: the beacon must be 1-255 bytes of hex and numIterationsExp in [0, 30]\n");
+      fprintf(stderr, "zkpoa-setup: %s beacon: the beacon must be 1-255 bytes of hex and numIterationsExp in [0, 30]\n", pbeacon ? "powersoftau" : "zkey");
       return 2;
     }
     beacon_len = hl / 2;
@@ -171,7 +213,8 @@ int main(int argc, char** argv) {
     uint32_t cnt = 0;
     if (zkpoa_zkey_contributions(pos[0], &has, &cnt, nullptr, 0) == PROVER_OK) in_transcript = has != 0;
   }
-  zkpoa::WorkerExit we = zkpoa::WorkerExit::start(!check && !verify && !pverify && !prepare, "zkpoa-setup");
+  const bool ptau_make = pnew || pcontribute || pbeacon;   // these run in this process, as `powersoftau prepare phase2`
+  zkpoa::WorkerExit we = zkpoa::WorkerExit::start(!check && !verify && !pverify && !prepare && !ptau_make, "zkpoa-setup");
   if (we.is_worker()) zkpoa_setup_defer_host_frees(1);
   auto leave = [&](int code) -> int {
     if (we.is_worker()) we.leave(code);
@@ -238,7 +281,7 @@ int main(int argc, char** argv) {
     uint32_t failed = 0, info[4] = {0, 0, 0, 0};
     rc = zkpoa_ptau_verify(ctx, pos[0], 0, &failed, info);
     if (rc == PROVER_OK) {
-      static const char* const kWhat[9] = {
+      static const char* const kWhat[10] = {
           "POINTS: a point is off its curve, a G2 point (section 3, beta2, section 13) is outside G2, T_0 or U_0 is not "
           "the generator, or T_1, A_0, B_0 or beta2 is zero",
           "TAU_G1: section 2 (tau^i G1) is not one chain of powers of the tau of U_1",
@@ -248,23 +291,43 @@ int main(int argc, char** argv) {
           "LAGRANGE_TAU_G1: section 12 (Lagrange form of tau G1) does not agree with section 2",
           "LAGRANGE_TAU_G2: section 13 (Lagrange form of tau G2) does not agree with section 3",
           "LAGRANGE_ALPHA: section 14 (Lagrange form of alpha tau G1) does not agree with section 4",
-          "LAGRANGE_BETA: section 15 (Lagrange form of beta tau G1) does not agree with section 5"};
-      fprintf(stderr, "[WARN]  zkpoa: section 7 (%u contribution(s): transcript hashes, proofs of knowledge) is not checked\n",
-              info[3]);
+          "LAGRANGE_BETA: section 15 (Lagrange form of beta tau G1) does not agree with section 5",
+          "CONTRIBUTIONS: a record of section 7 does not verify (key, ratios, beacon) or the records do not lead to this "
+          "file's points and challenge"};
+      uint32_t n_records = 0;
+      std::string records = ptau_record_lines(pos[0], &n_records);
+      if (!info[3])
+        fprintf(stderr, "[WARN]  zkpoa: section 7 holds no contribution record: the powers carry no trail of who made them\n");
       if (!info[2])
         fprintf(stderr, "[WARN]  zkpoa: the file is not prepared for phase 2 (no sections 12-15): only the powers were checked\n");
-      for (int b = 0; b < 9; b++)
+      for (int b = 0; b < 10; b++)
         if (failed & (1u << b)) fprintf(stderr, "[ERROR] zkpoa: %s\n", kWhat[b]);
       if (failed) {
         zkpoa_context_destroy(ctx);
         return 1;
       }
+      unsigned k = 1;   // one line per record: "contribution <name> <response hash>" or "beacon <name> <response hash>"
+      for (char* line = strtok(&records[0], "\n"); line; line = strtok(nullptr, "\n"), k++)
+        printf("[INFO]  zkpoa: contribution #%u: %s\n", k, line);
       printf("[INFO]  zkpoa: Powers of Tau Ok!\n");
     }
   } else if (prepare) {   // snarkjs logs its progress and exits 0, or names what is wrong with the file and exits 1
     uint32_t info[4] = {0, 0, 0, 0};
     rc = zkpoa_ptau_prepare_phase2(ctx, pos[0], pos[1], info);
     if (rc == PROVER_OK) printf("[INFO]  zkpoa: Prepared phase 2\n");
+  } else if (pnew) {
+    rc = zkpoa_ptau_new(ctx, new_power, pos[2]);
+    if (rc == PROVER_OK) printf("[INFO]  zkpoa: new ceremony file of power %u\n", new_power);
+  } else if (pcontribute || pbeacon) {
+    if (pbeacon) rc = zkpoa_ptau_beacon(ctx, pos[0], pos[1], beacon_bytes, beacon_len, beacon_exp, name);
+    else rc = zkpoa_ptau_contribute(ctx, pos[0], pos[1], nullptr, name);
+    if (rc == PROVER_OK) {
+      uint32_t n_records = 0;
+      const std::string records = ptau_record_lines(pos[1], &n_records);
+      size_t last = records.size() > 1 ? records.rfind('\n', records.size() - 2) : std::string::npos;   // the record just written
+      last = last == std::string::npos ? 0 : last + 1;
+      printf("[INFO]  zkpoa: contribution #%u: %s", n_records, records.empty() ? "\n" : records.c_str() + last);
+    }
   } else {
     if (beacon) rc = zkpoa_zkey_beacon(ctx, pos[0], pos[1], beacon_bytes, beacon_len, beacon_exp, name);
     else if (contribute && in_transcript) rc = zkpoa_zkey_contribute_ex(ctx, pos[0], pos[1], delta_p, name);
@@ -275,7 +338,7 @@ int main(int argc, char** argv) {
   if (!we.is_worker()) zkpoa_context_destroy(ctx);
   clock_gettime(CLOCK_MONOTONIC, &t1);
   if (rc == PROVER_OK && getenv("ZKPOA_VERBOSE") && !check && !verify && !pverify)
-    fprintf(stderr, "zkpoa-setup: %s written in %.2f s\n", pos[contribute || beacon || prepare ? 1 : 2],
+    fprintf(stderr, "zkpoa-setup: %s written in %.2f s\n", pos[contribute || beacon || prepare || pcontribute ? 1 : 2],
             (t1.tv_sec - t0.tv_sec) + (t1.tv_nsec - t0.tv_nsec) / 1e9);
   return leave(rc == PROVER_OK ? 0 : 1);
 }

@@ -93,6 +93,16 @@ extern "C" int zkpoa_set_option(zkpoa_context* ctx, const char* key, long value)
     ctx->opt_msm_max_points = value;
     return PROVER_OK;
   }
+  if (!strcmp(key, "ptau_piece_points")) {   // tests: stream the sections of a contribution in small pieces
+    if (value < 0) return PROVER_ERROR;
+    ctx->opt_ptau_piece_points = value;
+    return PROVER_OK;
+  }
+  if (!strcmp(key, "ptau_mul_slab")) {       // tests: several launches of scalar_mul_each at a small size
+    if (value < 0) return PROVER_ERROR;
+    ctx->opt_ptau_mul_slab = value;
+    return PROVER_OK;
+  }
   if (!strcmp(key, "msm_k0")) {           // experiments: level-0 piece length of the bucket accumulation (process-wide)
     msm_set_forced_k0((int)value);
     return PROVER_OK;

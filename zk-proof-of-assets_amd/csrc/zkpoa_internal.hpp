@@ -30,6 +30,8 @@ struct zkpoa_context {
   double lane_adds[zkpoa::DeviceCtx::kLanes] = {};   // per-lane mixed additions of that kernel (non-zero digits)
   int opt_msm_c = 0;
   long opt_msm_max_points = 0;   // 0 = default (2^27): larger MSMs run in chunks
+  long opt_ptau_piece_points = 0;   // powersoftau contribute / beacon: points per piece; 0 = derived from free HBM
+  long opt_ptau_mul_slab = 0;       // scalar_mul_each: points per launch; 0 = 2^20 (tests: cross a slab border at a small size)
   // Set when a lane's workspace for a whole MSM did not fit in HBM (found out by a failed reservation: msm_run, or
   // ahead of a proof: prover.hip budget_lane_workspaces): from then on the MSMs of that lane take at most this many
   // points at a time (never below 2^16); 0 = no limit of this kind.
@@ -168,6 +170,15 @@ EcNttWork* ec_intt_work_g2(zkpoa_context* ctx, uint32_t log_max);
 // enqueued on lane 0's stream: d_out[j] = sum_i (w_n^(-ij) / n) d_in[i], n = 2^log_n <= 2^log_max; d_out may be d_in
 void ec_intt_g1(zkpoa_context* ctx, EcNttWork& wk, const void* d_in, uint32_t log_n, void* d_out);
 void ec_intt_g2(zkpoa_context* ctx, EcNttWork& wk, const void* d_in, uint32_t log_n, void* d_out);
+// ptau_mul_g1.hip / ptau_mul_g2.hip (ptau_contribute.hip.h): d_out[i] = k_i * P_i enqueued on lane 0's stream (not
+// synchronised), wire form in and out, scalars standard form; flags: one zeroed device word, |= 1 for a scalar >= r.
+// n < 2^32. d_scratch: scalar_mul_each_scratch_gX(n, slab) bytes of the caller's; slab = points per launch, 0 = 2^20.
+size_t scalar_mul_each_scratch_g1(uint64_t n, uint64_t slab);
+size_t scalar_mul_each_scratch_g2(uint64_t n, uint64_t slab);
+void scalar_mul_each_g1(zkpoa_context* ctx, const void* d_points, const void* d_scalars, uint64_t n, void* d_out, uint32_t* d_flags,
+                        void* d_scratch, uint64_t slab);
+void scalar_mul_each_g2(zkpoa_context* ctx, const void* d_points, const void* d_scalars, uint64_t n, void* d_out, uint32_t* d_flags,
+                        void* d_scratch, uint64_t slab);
 // ntt.hip
 void ntt_prepare(zkpoa_context* ctx, hipStream_t st, uint32_t k);  // builds twiddle tables (hipMalloc) once per k
 // batch > 1: that many vectors of 2^k elements, `stride` bytes apart, transformed together (one launch per pass)
