@@ -393,6 +393,89 @@ def test_cli_refusals_leave_nothing_behind(zk, tmp_path):
     assert rc.returncode == 0 and "WARNING" in rc.stderr and "ZKPOA_PHASE1_S" in rc.stderr
 
 
+# ---- numbers from the environment: one parser behind ZKPOA_PHASE1_S, ZKPOA_PHASE2_S and ZKPOA_DELTA -------------------
+ENV_K = (0xabcdef0123456789abcdef, 0x1f2e3d4c5b6a, R - 0xbeef)   # every hex letter occurs
+ENV_FORMS = (str, hex, lambda k: "0X%X" % k)                   # decimal, 0x lower case, 0X upper case
+ENV_BAD = ("", "0x", "12,", "12a", "0x12g", "0", str(R), str(1 << 256), "0x1" + "0" * 64)
+
+
+def _zkey_contribute_cli(zk, key, out, delta):
+    return subprocess.run([zk.SETUP_BIN, "zkey", "contribute", str(key), str(out)], capture_output=True, text=True,
+                          timeout=300, env=dict(os.environ, ZKPOA_DELTA=delta))
+
+
+def test_env_numbers_parse_alike_for_all_three_variables(ctx, zk, tmp_path, monkeypatch):
+    """Power 1 and the committed n8 key (with a non-zero circuit hash patched into section 10 where a record is to be
+    appended: `zkey contribute` does not check the hash, `zkey verify` does). The same texts -- decimal, 0x lower case, 0X
+    upper case -- are taken by all three variables and give the same bytes, the ones the number itself gives; the same
+    refusals apply to all three and leave nothing behind. ZKPOA_DELTA is the command line's (a text that is no number
+    below 2^256 ends it with status 2, the library's range check with status 1), the other two are the library's."""
+    from conftest import GOLDEN
+    for name in ("ZKPOA_PHASE1_S", "ZKPOA_PHASE2_S", "ZKPOA_DELTA"):
+        monkeypatch.delenv(name, raising=False)
+    new, out = tmp_path / "new.ptau", tmp_path / "out"
+    ctx.ptau_new(1, new)
+    key = os.path.join(GOLDEN, "gen", "n8", "circuit.zkey")
+    kb = open(key, "rb").read()
+    off10 = {t: lst[0] for t, lst in g16.read_binfile(kb, "zkey", 1).items()}[10][0]
+    tkey = tmp_path / "t.zkey"
+    tkey.write_bytes(_patch(kb, off10, bytes(range(1, 65))))
+    k_g1 = [g16.g1_to_bytes(bn.g1_mul(bn.G1_GEN, k)) for k in ENV_K]
+
+    def made():
+        b = out.read_bytes()
+        out.unlink()
+        return b
+
+    # ---- accepted: three fixed secrets (PHASE1_S), the first of them (PHASE2_S, DELTA), in each form
+    ptaus, zkeys, deltas = [], [], []
+    for form in ENV_FORMS:
+        monkeypatch.setenv("ZKPOA_PHASE1_S", ",".join(form(k) for k in ENV_K))
+        ctx.ptau_contribute(new, out, (3, 5, 7), name="x")
+        monkeypatch.delenv("ZKPOA_PHASE1_S")
+        ptaus.append(made())
+        monkeypatch.setenv("ZKPOA_PHASE2_S", form(ENV_K[0]))
+        ctx.zkey_contribute_ex(tkey, out, 11, "x")
+        monkeypatch.delenv("ZKPOA_PHASE2_S")
+        zkeys.append(made())
+        rc = _zkey_contribute_cli(zk, key, out, form(ENV_K[0]))
+        assert rc.returncode == 0 and "WARNING" in rc.stderr and "delta" in rc.stderr, rc.stderr
+        deltas.append(made())
+    assert ptaus[0] == ptaus[1] == ptaus[2] and zkeys[0] == zkeys[1] == zkeys[2] and deltas[0] == deltas[1] == deltas[2]
+    (a0, _), = _records_at(ptaus[0])
+    assert [ptaus[0][a0 + 448 + 128 * i:a0 + 448 + 128 * i + 64] for i in range(3)] == k_g1      # the key's three g1_s
+    s10 = zkeys[0][{t: lst[0] for t, lst in g16.read_binfile(zkeys[0], "zkey", 1).items()}[10][0]:]
+    assert s10[64:68] == struct.pack("<I", 1) and s10[68 + 64:68 + 128] == k_g1[0]              # the record's g1_s
+    ctx.zkey_contribute(key, out, ENV_K[0])
+    assert made() == deltas[0]
+
+    # ---- refused, nothing written
+    def nothing_left():
+        return sorted(p.name for p in tmp_path.iterdir()) == ["new.ptau", "t.zkey"]
+
+    one, two = hex(ENV_K[0]), str(ENV_K[1])
+    for bad in ENV_BAD:
+        for text in (bad, ",".join((one, two, bad)), ",".join((bad, one, two)), ",".join((one, bad, two))):
+            monkeypatch.setenv("ZKPOA_PHASE1_S", text)
+            with pytest.raises(zk.ZkpoaError, match="ZKPOA_PHASE1_S"):
+                ctx.ptau_contribute(new, out, (3, 5, 7), name="x")
+        monkeypatch.delenv("ZKPOA_PHASE1_S")
+        monkeypatch.setenv("ZKPOA_PHASE2_S", bad)
+        with pytest.raises(zk.ZkpoaError, match="ZKPOA_PHASE2_S"):
+            ctx.zkey_contribute_ex(tkey, out, 11, "x")
+        monkeypatch.delenv("ZKPOA_PHASE2_S")
+        rc = _zkey_contribute_cli(zk, key, out, bad)
+        in_range_text = bad in ("0", str(R))                       # a number below 2^256: the library refuses it
+        assert rc.returncode == (1 if in_range_text else 2) and "delta" in rc.stderr.lower(), (bad, rc.stderr)
+        assert "ZKPOA_DELTA" in rc.stderr
+        assert nothing_left(), bad
+    for text in (",".join((one, two)), ",".join((one, two, one, two)), ",".join((one, two, one)) + ","):
+        monkeypatch.setenv("ZKPOA_PHASE1_S", text)
+        with pytest.raises(zk.ZkpoaError, match="ZKPOA_PHASE1_S"):
+            ctx.ptau_contribute(new, out, (3, 5, 7), name="x")
+    assert nothing_left()
+
+
 def test_cli_a_prepared_input_loses_its_lagrange_sections(ctx, zk, tmp_path_factory, tmp_path):
     c = _chain(ctx, tmp_path_factory, 3)
     out = tmp_path / "next.ptau"

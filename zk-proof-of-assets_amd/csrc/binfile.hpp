@@ -1,5 +1,5 @@
 // What the prover (prover.hip) and the setup commands (setup_common.hip.h) both read of iden3's binary files, host code
-// only: the container's section table, the Groth16 header of a .zkey, and random bytes. Nothing here throws a file
+// only: the container's section table, the Groth16 header of a .zkey, the point sections of a .ptau, and random bytes. Nothing here throws a file
 // error of its own: each caller turns a failure into its own exception type and text (include/zkpoa_prover.h lists
 // the prover's).
 #pragma once
@@ -10,6 +10,7 @@
 #include <string.h>
 #include <unistd.h>
 
+#include <array>
 #include <functional>
 #include <map>
 
@@ -65,6 +66,30 @@ inline ZkeyHeader read_zkey_header(const uint8_t* p) {
   return {rd32(p), rd32(p + 36), memcmp(p + 4, HFqParams::P, 32) == 0, memcmp(p + 40, HFrParams::P, 32) == 0,
           rd32(p + 72), rd32(p + 76), rd32(p + 80),
           p + kAlpha1, p + kBeta1, p + kBeta2, p + kGamma2, p + kDelta1, p + kDelta2};
+}
+
+// ---- ceremony file (.ptau) of power p, N = 2^p: its point sections, G1 points of 64 B and G2 points of 128 B ------------
+struct PowerSec {   // the powers: tau^i G1, tau^i G2, alpha tau^i G1, beta tau^i G1, beta G2
+  uint32_t id;
+  int group;
+  uint64_t count;
+  uint64_t unit() const { return group == 2 ? 128 : 64; }
+  uint64_t bytes() const { return count * unit(); }
+};
+inline std::array<PowerSec, 5> ptau_power_secs(uint32_t power) {
+  const uint64_t N = 1ull << power;
+  return {{{2, 1, 2 * N - 1}, {3, 2, N}, {4, 1, N}, {5, 1, N}, {6, 2, 1}}};
+}
+struct LagrangeSec {   // section dst: levels 0..top, level l = the 2^l Lagrange-form points of the first 2^l of section src
+  uint32_t src, dst;
+  int group;
+  uint32_t top;
+  uint64_t unit() const { return group == 2 ? 128 : 64; }
+  uint64_t count() const { return (2ull << top) - 1; }
+  uint64_t bytes() const { return count() * unit(); }
+};
+inline std::array<LagrangeSec, 4> ptau_lagrange_secs(uint32_t power) {
+  return {{{2, 12, 1, power + 1}, {3, 13, 2, power}, {4, 14, 1, power}, {5, 15, 1, power}}};
 }
 
 // len bytes of /dev/urandom (short reads are continued); returns null, or what went wrong

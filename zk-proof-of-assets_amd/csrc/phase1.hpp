@@ -1,8 +1,10 @@
 // The phase-1 transcript of a .ptau (section 7), host side, no GPU: what `snarkjs powersoftau new / contribute / beacon /
 // verify` hash, draw and check, written from DESIGN.md "Phase-1 transcript" on top of the primitives of csrc/phase2.hpp
-// (Blake2b-512, the ChaCha generator, `fromRng`, hash-to-G2, the beacon key, the hash form of a point). The saved Blake2b
+// (Blake2b-512, the ChaCha generator, `fromRng`, hash-to-G2, the beacon key and draw, the hash form of a point, mul_wire,
+// the type and params that end a record: RecordParams) and the section table of csrc/binfile.hpp. The saved Blake2b
 // state, the contribution key, the records of section 7 and the checks that need pairings only.
 #pragma once
+#include "binfile.hpp"
 #include "phase2.hpp"
 
 namespace zkpoa {
@@ -59,20 +61,14 @@ inline pairing::G2 g2_sp(int k, const uint8_t challenge[64], const uint8_t* g1_s
   h.final(d);
   return p2::hash_to_g2(d);
 }
-template <class HF>
-inline void mul_wire(const uint8_t* in, const uint8_t k_le[32], uint8_t* out) {
-  uint64_t kv[4];
-  memcpy(kv, k_le, 32);
-  h_affine_to_bytes<HF>(h_to_affine(h_mul(XYZZ<HF>::from_affine(h_affine_from_bytes<HF>(in)), kv)), out);
-}
 inline void make_key(const Secrets& s, const uint8_t challenge[64], uint8_t key[kKeyLen]) {
   for (int k = 0; k < 3; k++) {
     uint8_t* g1_s = key + 128 * k;
     memcpy(g1_s, s.g1_s[k], 64);
-    mul_wire<HFq>(g1_s, s.x[k], g1_s + 64);
+    p2::mul_wire<HFq>(g1_s, s.x[k], g1_s + 64);
     uint8_t sp[128];
     h_affine_to_bytes<HFq2>(g2_sp(k, challenge, g1_s, g1_s + 64), sp);
-    mul_wire<HFq2>(sp, s.x[k], key + 384 + 128 * k);
+    p2::mul_wire<HFq2>(sp, s.x[k], key + 384 + 128 * k);
   }
 }
 // a beacon: per key, in the order tau, alpha, beta: the secret (fromRng Fr), then g1_s (fromRng G1), one generator
@@ -80,10 +76,7 @@ inline void beacon_secrets(const uint8_t* beacon, size_t len, uint32_t exp, Secr
   uint32_t key[8];
   p2::beacon_key(beacon, len, exp, key);
   p2::ChaCha rng(key);
-  for (int k = 0; k < 3; k++) {
-    p2::fr_from_rng(rng, s->x[k]);
-    h_affine_to_bytes<HFq>(p2::g1_from_rng(rng), s->g1_s[k]);
-  }
+  for (int k = 0; k < 3; k++) p2::beacon_draw(rng, s->x[k], s->g1_s[k]);
 }
 inline void hash_key(p2::Blake2b& h, const uint8_t key[kKeyLen]) {
   for (int i = 0; i < 6; i++) p2::hash_g1_wire(h, key + 64 * i);
@@ -99,7 +92,6 @@ inline bool response_hash(const uint8_t partial[kStateLen], const uint8_t key[kK
 }
 // the challenge of a fresh file of 2^power: Blake2b-512(Blake2b-512("") | hash form of sections 2-6, all generators)
 inline void fresh_challenge(uint32_t power, uint8_t out[64]) {
-  const uint64_t N = 1ull << power;
   uint8_t g1[64], g2[128], e[64];
   p2::g1_hash_form(host_generator<HFq>(), g1);
   p2::g2_hash_form(host_generator<HFq2>(), g2);
@@ -111,41 +103,28 @@ inline void fresh_challenge(uint32_t power, uint8_t out[64]) {
     memcpy(&run1[64 * i], g1, 64);
     memcpy(&run2[128 * i], g2, 128);
   }
-  auto many = [&](const std::vector<uint8_t>& run, uint64_t unit, uint64_t count) {
-    for (uint64_t done = 0; done < count; done += 1024) h.update(run.data(), unit * std::min<uint64_t>(1024, count - done));
-  };
-  many(run1, 64, 2 * N - 1);
-  many(run2, 128, N);
-  many(run1, 64, N);
-  many(run1, 64, N);
-  many(run2, 128, 1);
+  for (const PowerSec& sc : ptau_power_secs(power))
+    for (uint64_t done = 0; done < sc.count; done += 1024)
+      h.update(sc.group == 2 ? run2.data() : run1.data(), sc.unit() * std::min<uint64_t>(1024, sc.count - done));
   h.final(out);
 }
 
 // ---- section 7: u32 count, then the records --------------------------------------------------------------------------
-struct Record {
+struct Record : p2::RecordParams {
   uint8_t tau_g1[64], tau_g2[128], alpha_g1[64], beta_g1[64], beta_g2[128];   // after the contribution, wire form
   uint8_t key[kKeyLen];
   uint8_t partial[kStateLen], next_challenge[64];
-  uint32_t type = 0;   // 0 contribution, 1 beacon
-  std::string name;
-  uint32_t num_iterations_exp = 0;
-  std::vector<uint8_t> beacon;
 };
-constexpr size_t kRecordFixed = 448 + kKeyLen + kStateLen + 64 + 8;
-inline size_t params_len(const Record& r) {
-  return (r.name.empty() ? 0 : 2 + r.name.size()) + (r.type == 1 ? 2 + 2 + r.beacon.size() : 0);
-}
-// params as DESIGN.md "Phase-2 transcript": tag 1 = name (u8 length, bytes); 2 = numIterationsExp (one byte); 3 = beacon
+constexpr size_t kRecordHead = 448 + kKeyLen + kStateLen + 64;   // what precedes the record's type and params
 inline std::vector<Record> parse_section7(const uint8_t* p, uint64_t len) {
-  auto fail = [] { throw std::runtime_error("ptau: section 7 is truncated, over-long or holds an unknown record"); };
-  if (len < 4) fail();
+  const char* const what = "ptau: section 7 is truncated, over-long or holds an unknown record";
+  if (len < 4) throw std::runtime_error(what);
   uint32_t count;
   memcpy(&count, p, 4);
   uint64_t at = 4;
   std::vector<Record> out;
   for (uint32_t k = 0; k < count; k++) {
-    if (len - at < kRecordFixed) fail();
+    if (len - at < kRecordHead) throw std::runtime_error(what);
     Record r;
     memcpy(r.tau_g1, p + at, 64);
     memcpy(r.tau_g2, p + at + 64, 128);
@@ -155,36 +134,18 @@ inline std::vector<Record> parse_section7(const uint8_t* p, uint64_t len) {
     memcpy(r.key, p + at + 448, kKeyLen);
     memcpy(r.partial, p + at + 448 + kKeyLen, kStateLen);
     memcpy(r.next_challenge, p + at + 448 + kKeyLen + kStateLen, 64);
-    uint32_t plen;
-    memcpy(&r.type, p + at + kRecordFixed - 8, 4);
-    memcpy(&plen, p + at + kRecordFixed - 4, 4);
-    at += kRecordFixed;
-    if (len - at < plen || r.type > 1) fail();
-    const uint8_t* q = p + at;
-    for (uint32_t i = 0; i < plen;) {
-      const uint8_t tag = q[i++];
-      if (tag == 2) {
-        if (i >= plen) fail();
-        r.num_iterations_exp = q[i++];
-      } else if (tag == 1 || tag == 3) {
-        if (i >= plen || plen - i - 1 < q[i]) fail();
-        const uint8_t l = q[i++];
-        if (tag == 1) r.name.assign((const char*)q + i, l);
-        else r.beacon.assign(q + i, q + i + l);
-        i += l;
-      } else fail();
-    }
-    at += plen;
+    at += kRecordHead;
+    at += r.parse(p + at, len - at, what);
     out.push_back(r);
   }
-  if (at != len) fail();
+  if (at != len) throw std::runtime_error(what);
   return out;
 }
 inline std::vector<uint8_t> write_section7(const std::vector<Record>& records) {
   std::vector<uint8_t> out;
-  auto u32 = [&](uint32_t v) { out.insert(out.end(), (uint8_t*)&v, (uint8_t*)&v + 4); };
   auto put = [&](const uint8_t* p, size_t n) { out.insert(out.end(), p, p + n); };
-  u32((uint32_t)records.size());
+  const uint32_t count = (uint32_t)records.size();
+  put((const uint8_t*)&count, 4);
   for (const Record& r : records) {
     put(r.tau_g1, 64);
     put(r.tau_g2, 128);
@@ -194,20 +155,7 @@ inline std::vector<uint8_t> write_section7(const std::vector<Record>& records) {
     put(r.key, kKeyLen);
     put(r.partial, kStateLen);
     put(r.next_challenge, 64);
-    u32(r.type);
-    u32((uint32_t)params_len(r));
-    if (!r.name.empty()) {
-      out.push_back(1);
-      out.push_back((uint8_t)r.name.size());
-      put((const uint8_t*)r.name.data(), r.name.size());
-    }
-    if (r.type == 1) {
-      out.push_back(2);
-      out.push_back((uint8_t)r.num_iterations_exp);
-      out.push_back(3);
-      out.push_back((uint8_t)r.beacon.size());
-      put(r.beacon.data(), r.beacon.size());
-    }
+    r.write(out);
   }
   return out;
 }
@@ -257,7 +205,7 @@ inline bool verify_records(const std::vector<Record>& records, uint32_t power, c
       beacon_secrets(r.beacon.data(), r.beacon.size(), r.num_iterations_exp, &bs);
       for (int k = 0; k < 3; k++) {
         uint8_t want[64];
-        mul_wire<HFq>(bs.g1_s[k], bs.x[k], want);
+        p2::mul_wire<HFq>(bs.g1_s[k], bs.x[k], want);
         if (memcmp(bs.g1_s[k], key_g1_s(r.key, k), 64) || memcmp(want, key_g1_sx(r.key, k), 64)) return false;
       }
     }

@@ -2,7 +2,8 @@
 // hash and draw, written from DESIGN.md "Phase-2 transcript" (snarkjs and ffjavascript are not vendored anywhere near
 // this project; the layout is restated from their published sources). Blake2b-512 (RFC 7693), SHA-256 (FIPS 180-4),
 // the ChaCha20 generator of ffjavascript, square roots in Fq and Fq2, `fromRng` for Fr, G1 and G2, hash-to-G2 of a
-// transcript hash, the beacon's key derivation, the hash form of a point and the records of section 10.
+// transcript hash, the beacon's key derivation, the hash form of a point, the type and params that end a record of either transcript
+// (RecordParams) and the records of section 10.
 #pragma once
 #include "host_curve.hpp"
 #include "pairing.hpp"
@@ -340,13 +341,82 @@ inline void hash_g2_wire(Blake2b& h, const uint8_t* wire) {
   h.update(b, 128);
 }
 
-// ---- section 10 --------------------------------------------------------------------------------------------------------
-struct Record {
-  uint8_t delta_after[64], g1_s[64], g1_sx[64], g2_spx[128], transcript[64];   // points in zkey wire form
-  uint32_t type = 0;                                                           // 0 contribution, 1 beacon
+// k * P on wire-form bytes (k: 32 B little-endian standard form); out may be in
+template <class HF>
+inline void mul_wire(const uint8_t* in, const uint8_t k_le[32], uint8_t* out) {
+  uint64_t kv[4];
+  memcpy(kv, k_le, 32);
+  h_affine_to_bytes<HF>(h_to_affine(h_mul(XYZZ<HF>::from_affine(h_affine_from_bytes<HF>(in)), kv)), out);
+}
+// what a beacon's generator yields per secret: the secret (fromRng Fr, standard form), then g1_s (fromRng G1, wire form)
+inline void beacon_draw(ChaCha& rng, uint8_t x[32], uint8_t g1_s[64]) {
+  fr_from_rng(rng, x);
+  h_affine_to_bytes<HFq>(g1_from_rng(rng), g1_s);
+}
+
+// ---- what a record of a .ptau's section 7 and of a .zkey's section 10 ends with: u32 type, u32 length of the params, the
+// params: tag 1 = name (u8 length, bytes); tag 2 = numIterationsExp (one byte, no length); tag 3 = beacon (u8 length, bytes)
+struct RecordParams {
+  uint32_t type = 0;   // 0 contribution, 1 beacon
   std::string name;
-  uint32_t num_iterations_exp = 0;
   std::vector<uint8_t> beacon;
+  uint32_t num_iterations_exp = 0;
+  // what a command may append: throws "<command>: ..." for a name or beacon that has no u8 length, or a beacon that
+  // would not finish
+  void check(const char* command) const {
+    if (num_iterations_exp > kMaxBeaconExp)
+      throw std::runtime_error(std::string(command) + ": numIterationsExp above 30 is refused (2^30 hashes take minutes; more would not finish)");
+    if (name.size() > 255 || beacon.size() > 255) throw std::runtime_error(std::string(command) + ": name or beacon longer than 255 bytes");
+  }
+  size_t len() const {   // of what write() appends
+    return 8 + (name.empty() ? 0 : 2 + name.size()) + (type == 1 ? 2 + 2 + beacon.size() : 0);
+  }
+  void write(std::vector<uint8_t>& out) const {
+    const uint32_t head[2] = {type, (uint32_t)(len() - 8)};
+    out.insert(out.end(), (const uint8_t*)head, (const uint8_t*)head + 8);
+    if (!name.empty()) {
+      out.push_back(1);
+      out.push_back((uint8_t)name.size());
+      out.insert(out.end(), name.begin(), name.end());
+    }
+    if (type == 1) {
+      out.push_back(2);
+      out.push_back((uint8_t)num_iterations_exp);
+      out.push_back(3);
+      out.push_back((uint8_t)beacon.size());
+      out.insert(out.end(), beacon.begin(), beacon.end());
+    }
+  }
+  // from the `avail` bytes at p; returns the bytes taken, throws `what` for a type above 1, an unknown tag or anything
+  // that runs past avail
+  uint64_t parse(const uint8_t* p, uint64_t avail, const char* what) {
+    auto fail = [&] { throw std::runtime_error(what); };
+    uint32_t plen;
+    if (avail < 8) fail();
+    memcpy(&type, p, 4);
+    memcpy(&plen, p + 4, 4);
+    if (avail - 8 < plen || type > 1) fail();
+    const uint8_t* q = p + 8;
+    for (uint32_t i = 0; i < plen;) {
+      const uint8_t tag = q[i++];
+      if (tag == 2) {
+        if (i >= plen) fail();
+        num_iterations_exp = q[i++];
+      } else if (tag == 1 || tag == 3) {
+        if (i >= plen || plen - i - 1 < q[i]) fail();
+        const uint8_t l = q[i++];
+        if (tag == 1) name.assign((const char*)q + i, l);
+        else beacon.assign(q + i, q + i + l);
+        i += l;
+      } else fail();
+    }
+    return 8 + (uint64_t)plen;
+  }
+};
+
+// ---- section 10 --------------------------------------------------------------------------------------------------------
+struct Record : RecordParams {
+  uint8_t delta_after[64], g1_s[64], g1_sx[64], g2_spx[128], transcript[64];   // points in zkey wire form
   void hash_pubkey(Blake2b& h) const {
     hash_g1_wire(h, delta_after);
     hash_g1_wire(h, g1_s);
@@ -364,74 +434,40 @@ struct Transcript {
     return false;
   }
 };
-// params: tag 1 = name (u8 length, bytes); tag 2 = numIterationsExp (one byte, no length); tag 3 = beacon (u8 length, bytes)
 inline Transcript parse_section10(const uint8_t* p, uint64_t len) {
-  auto fail = [] { throw std::runtime_error("zkey: section 10 is truncated or over-long"); };
-  if (len < 68) fail();
+  const char* const what = "zkey: section 10 is truncated or over-long";
+  if (len < 68) throw std::runtime_error(what);
   Transcript t;
   memcpy(t.cs_hash, p, 64);
   uint32_t count;
   memcpy(&count, p + 64, 4);
   uint64_t at = 68;
   for (uint32_t k = 0; k < count; k++) {
-    if (len - at < 384 + 8) fail();
+    if (len - at < 384) throw std::runtime_error(what);
     Record r;
     memcpy(r.delta_after, p + at, 64);
     memcpy(r.g1_s, p + at + 64, 64);
     memcpy(r.g1_sx, p + at + 128, 64);
     memcpy(r.g2_spx, p + at + 192, 128);
     memcpy(r.transcript, p + at + 320, 64);
-    uint32_t plen;
-    memcpy(&r.type, p + at + 384, 4);
-    memcpy(&plen, p + at + 388, 4);
-    at += 392;
-    if (len - at < plen || r.type > 1) fail();
-    const uint8_t* q = p + at;
-    for (uint32_t i = 0; i < plen;) {
-      const uint8_t tag = q[i++];
-      if (tag == 2) {
-        if (i >= plen) fail();
-        r.num_iterations_exp = q[i++];
-      } else if (tag == 1 || tag == 3) {
-        if (i >= plen || plen - i - 1 < q[i]) fail();
-        const uint8_t l = q[i++];
-        if (tag == 1) r.name.assign((const char*)q + i, l);
-        else r.beacon.assign(q + i, q + i + l);
-        i += l;
-      } else fail();
-    }
-    at += plen;
+    at += 384;
+    at += r.parse(p + at, len - at, what);
     t.records.push_back(r);
   }
-  if (at != len) fail();
+  if (at != len) throw std::runtime_error(what);
   return t;
 }
 inline std::vector<uint8_t> write_section10(const Transcript& t) {
   std::vector<uint8_t> out(t.cs_hash, t.cs_hash + 64);
-  auto u32 = [&](uint32_t v) { out.insert(out.end(), (uint8_t*)&v, (uint8_t*)&v + 4); };
-  u32((uint32_t)t.records.size());
+  const uint32_t count = (uint32_t)t.records.size();
+  out.insert(out.end(), (const uint8_t*)&count, (const uint8_t*)&count + 4);
   for (const Record& r : t.records) {
     out.insert(out.end(), r.delta_after, r.delta_after + 64);
     out.insert(out.end(), r.g1_s, r.g1_s + 64);
     out.insert(out.end(), r.g1_sx, r.g1_sx + 64);
     out.insert(out.end(), r.g2_spx, r.g2_spx + 128);
     out.insert(out.end(), r.transcript, r.transcript + 64);
-    u32(r.type);
-    std::vector<uint8_t> params;
-    if (!r.name.empty()) {
-      params.push_back(1);
-      params.push_back((uint8_t)r.name.size());
-      params.insert(params.end(), r.name.begin(), r.name.end());
-    }
-    if (r.type == 1) {
-      params.push_back(2);
-      params.push_back((uint8_t)r.num_iterations_exp);
-      params.push_back(3);
-      params.push_back((uint8_t)r.beacon.size());
-      params.insert(params.end(), r.beacon.begin(), r.beacon.end());
-    }
-    u32((uint32_t)params.size());
-    out.insert(out.end(), params.begin(), params.end());
+    r.write(out);
   }
   return out;
 }

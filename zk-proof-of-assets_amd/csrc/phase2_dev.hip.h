@@ -206,20 +206,11 @@ struct HashStream {
 
 // The hash form of sections 2-6 of a ceremony file of 2^power (fd, its section table) into hs's hasher: what a
 // contribution's nextChallenge covers. The sections stream through d_piece (piece_points x 128 B of device memory).
-inline void hash_form_ptau_sections(zkpoa_context* ctx, HashStream& hs, int fd, std::map<uint32_t, Sec>& ps, uint32_t power,
+inline void hash_form_ptau_sections(zkpoa_context* ctx, HashStream& hs, int fd, const std::map<uint32_t, Sec>& ps, uint32_t power,
                                     void* d_piece, uint64_t piece_points) {
-  const uint64_t N = 1ull << power;
-  const uint64_t count[7] = {0, 0, 2 * N - 1, N, N, N, 1};
-  hipStream_t st = ctx->dev.lanes[0].stream;
-  for (uint32_t t = 2; t <= 6; t++) {
-    const int group = t == 3 || t == 6 ? 2 : 1;
-    const uint64_t unit = group == 2 ? 128 : 64;
-    for (uint64_t i0 = 0; i0 < count[t]; i0 += piece_points) {
-      const uint64_t cnt = std::min(piece_points, count[t] - i0);
-      ctx->uploader.upload(d_piece, nullptr, cnt * unit, ctx->dev.device, st, fd, ps[t].off + i0 * unit);
-      hs.points(d_piece, cnt, group, false);
-    }
-  }
+  for (const PowerSec& sc : ptau_power_secs(power))
+    for_each_piece(ctx, fd, ps.at(sc.id).off, sc.count, sc.unit(), piece_points, d_piece,
+                   [&](uint64_t, uint64_t cnt) { hs.points(d_piece, cnt, sc.group, false); });
 }
 
 // d_out[i] = T[i + n] - T[i] for i < n - 1 (T: the ptau's tau^i G1, at least 2n - 1 points on the device)

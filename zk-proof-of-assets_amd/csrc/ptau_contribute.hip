@@ -7,8 +7,9 @@
 // Every point meets its own full-width scalar. The scalars are made on the device (power_scalars_kernel: first *
 // ratio^(i0 + i), one exponentiation per workgroup, a short one and a chain per thread), the products by
 // scalar_mul_each (csrc/ptau_contribute.hip.h: fixed signed 4-bit windows, every lane of a wave on the same path). The
-// sections stream through HBM in pieces: upload from the input file (the context's pinned uploader), point checks as
-// `powersoftau prepare phase2` makes them, scalars, products, the compressed form of the piece into the response hash
+// sections stream through HBM in pieces (csrc/setup_common.hip.h: for_each_piece over the rows of ptau_power_secs, the
+// upload through the context's pinned uploader), point checks as `powersoftau prepare phase2` makes them
+// (PointChecker::require), scalars, products, the compressed form of the piece into the response hash
 // (HashStream, double-buffered pinned staging into the one serial Blake2b), read-back into one of two pinned buffers
 // behind the stream's kernels and a writer thread that puts it at its place in the output while the device takes the
 // next piece. A second pass over the written sections makes their hash form for nextChallenge, which starts with the
@@ -28,16 +29,6 @@ namespace p2 = zkpoa::phase2;
 
 constexpr uint32_t kPowRun = 8;                 // consecutive scalars per thread
 constexpr uint32_t kPowBlock = 256 * kPowRun;   // scalars per workgroup
-
-ZK_DEV Fr fr_pow_u64(Fr b, uint64_t e) {
-  Fr r = Fr::one();
-  while (e) {
-    if (e & 1u) r = r * b;
-    b = b.sqr();
-    e >>= 1;
-  }
-  return r;
-}
 
 // out[i] = first * ratio^(i0 + i), i < n, standard form. Thread 0 of a workgroup raises ratio to the workgroup's first
 // exponent (64 bits: a streamed piece starts anywhere) and shares first * that through LDS; every thread then needs an
@@ -68,16 +59,6 @@ static __global__ __launch_bounds__(256) void power_scalars_kernel(Fr first, Fr 
   }
 }
 
-Fr fr_dev(const HFr& h) {
-  Fr f;
-  memcpy(&f, &h, 32);
-  return f;
-}
-bool scalar_in_range(const uint8_t le[32], bool nonzero) {
-  uint64_t v[4];
-  memcpy(v, le, 32);
-  return !HFr::geq_p(v) && (!nonzero || (v[0] | v[1] | v[2] | v[3]));
-}
 // enqueued on lane 0's stream; first, ratio: standard form, below r
 void power_scalars(zkpoa_context* ctx, const uint8_t first_le[32], const uint8_t ratio_le[32], uint64_t i0, uint64_t n, void* d_out) {
   if (!n) return;
@@ -90,48 +71,6 @@ void power_scalars(zkpoa_context* ctx, const uint8_t first_le[32], const uint8_t
   ZK_HIP(hipGetLastError());
 }
 
-void random_scalar(uint8_t d[32]) {   // uniform on [1, r): 254 random bits, rejected while >= r or zero
-  do {
-    urandom(d, 32);
-    d[31] &= 0x3f;
-  } while (!scalar_in_range(d, true));
-}
-// one number of ZKPOA_PHASE1_S: decimal or 0x... hex, in [1, r)
-bool parse_scalar(const char* b, const char* e, uint8_t out[32]) {
-  memset(out, 0, 32);
-  const bool hex = e - b > 2 && b[0] == '0' && (b[1] | 32) == 'x';
-  if (hex) b += 2;
-  if (b == e) return false;
-  for (const char* p = b; p < e; p++) {
-    unsigned d;
-    if (*p >= '0' && *p <= '9') d = (unsigned)(*p - '0');
-    else if (hex && (*p | 32) >= 'a' && (*p | 32) <= 'f') d = (unsigned)((*p | 32) - 'a' + 10);
-    else return false;
-    unsigned carry = d;
-    for (int i = 0; i < 32; i++) {
-      const unsigned v = out[i] * (hex ? 16u : 10u) + carry;
-      out[i] = (uint8_t)v;
-      carry = v >> 8;
-    }
-    if (carry) return false;
-  }
-  return scalar_in_range(out, true);
-}
-// ZKPOA_PHASE1_S (tests / reproducible records only): "s_tau,s_alpha,s_beta", the s of the key's g1_s = s * G1
-bool env_phase1_s(uint8_t s[3][32]) {
-  const char* e = getenv("ZKPOA_PHASE1_S");
-  if (!e) return false;
-  for (int k = 0; k < 3; k++) {
-    const char* end = strchr(e, ',');
-    if ((k < 2) != (end != nullptr)) throw SetupError("ZKPOA_PHASE1_S is not three numbers in [1, r) separated by commas");
-    if (!end) end = e + strlen(e);
-    if (!parse_scalar(e, end, s[k])) throw SetupError("ZKPOA_PHASE1_S is not three numbers in [1, r) separated by commas");
-    e = end + 1;
-  }
-  fprintf(stderr, "zkpoa: WARNING: the secrets of the contribution key's g1_s taken from ZKPOA_PHASE1_S -- for tests only\n");
-  return true;
-}
-
 // toxic waste does not outlive the command: host copies are overwritten (through a volatile pointer, so that the
 // stores stay), the device array of their powers is cleared before it is freed
 void wipe(void* p, size_t len) {
@@ -139,50 +78,29 @@ void wipe(void* p, size_t len) {
   for (size_t i = 0; i < len; i++) v[i] = 0;
 }
 
-bool same_file(const char* a, const char* b) {
-  struct stat sa, sb;
-  if (stat(a, &sa) != 0 || stat(b, &sb) != 0) return false;
-  return sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino;
-}
-
-// the byte layout of a ceremony file of sections 1-7 whose section 7 has len7 bytes
-struct PtauLayout {
-  uint64_t len[8], off[8], total;
-  PtauLayout(uint32_t power, uint64_t len7) {
-    const uint64_t N = 1ull << power;
-    const uint64_t l[8] = {0, 4 + 32 + 8, (2 * N - 1) * 64, N * 128, N * 64, N * 64, 128, len7};
-    total = 12;
-    for (uint32_t t = 1; t <= 7; t++) {
-      len[t] = l[t];
-      off[t] = total + 12;
-      total += 12 + l[t];
-    }
+// a ceremony file of sections 1-7 whose section 7 has len7 bytes, sized, its table and its header (section 1) written
+struct PtauFile : SectionFile {
+  static std::array<uint64_t, 7> lens(uint32_t power, uint64_t len7) {
+    std::array<uint64_t, 7> l{{4 + 32 + 8, 0, 0, 0, 0, 0, len7}};
+    for (const PowerSec& sc : ptau_power_secs(power)) l[sc.id - 1] = sc.bytes();
+    return l;
   }
-  void put_table(AtomicFile& fo, uint32_t power, uint32_t ceremony) const {
-    const uint32_t hdr[2] = {1, 7};   // version, sections
-    fo.put_at(0, "ptau", 4);
-    fo.put_at(4, hdr, 8);
-    for (uint32_t t = 1; t <= 7; t++) {
-      fo.put_at(off[t] - 12, &t, 4);
-      fo.put_at(off[t] - 8, &len[t], 8);
-    }
+  static constexpr uint32_t kIds[7] = {1, 2, 3, 4, 5, 6, 7};
+  PtauFile(const char* path, uint32_t power, uint32_t ceremony, uint64_t len7)
+      : SectionFile(path, "ptau", kIds, lens(power, len7).data(), 7) {
     uint8_t s1[44];
     const uint32_t n8 = 32;
     memcpy(s1, &n8, 4);
     memcpy(s1 + 4, HFqParams::P, 32);
     memcpy(s1 + 36, &power, 4);
     memcpy(s1 + 40, &ceremony, 4);
-    fo.put_at(off[1], s1, 44);
+    put(1, s1, 44);
   }
 };
 
 void ptau_new(uint32_t power, const char* out_path) {
   if (power < 1 || power > 28) throw SetupError("powersoftau new: power " + std::to_string(power) + " is outside [1, 28]");
-  const uint64_t N = 1ull << power;
-  const PtauLayout lay(power, 4);
-  AtomicFile fo(out_path);
-  fo.reserve(lay.total);
-  lay.put_table(fo, power, power);
+  PtauFile fo(out_path, power, power, 4);
   uint8_t g1[64], g2[128];
   h_affine_to_bytes<HFq>(host_generator<HFq>(), g1);
   h_affine_to_bytes<HFq2>(host_generator<HFq2>(), g2);
@@ -192,40 +110,23 @@ void ptau_new(uint32_t power, const char* out_path) {
     memcpy(&run1[64 * i], g1, 64);
     memcpy(&run2[128 * i], g2, 128);
   }
-  const uint64_t count[7] = {0, 0, 2 * N - 1, N, N, N, 1};
-  for (uint32_t t = 2; t <= 6; t++) {
-    const bool is2 = t == 3 || t == 6;
-    const uint64_t unit = is2 ? 128 : 64;
-    for (uint64_t done = 0; done < count[t]; done += kRunPoints)
-      fo.put_at(lay.off[t] + done * unit, is2 ? run2.data() : run1.data(), unit * std::min<uint64_t>(kRunPoints, count[t] - done));
-  }
+  for (const PowerSec& sc : ptau_power_secs(power))
+    for (uint64_t done = 0; done < sc.count; done += kRunPoints)
+      fo.put_at(sc.id, done * sc.unit(), sc.group == 2 ? run2.data() : run1.data(), sc.unit() * std::min<uint64_t>(kRunPoints, sc.count - done));
   const uint32_t zero = 0;
-  fo.put_at(lay.off[7], &zero, 4);
+  fo.put(7, &zero, 4);
   fo.commit();
 }
 
-struct Append {
-  uint32_t type = 0;   // 0 contribution, 1 beacon
-  std::string name;
-  std::vector<uint8_t> beacon;
-  uint32_t num_iterations_exp = 0;
-};
-
-void ptau_contribute(zkpoa_context* ctx, const char* in_path, const char* out_path, const uint8_t* secrets_le, const Append& ap) {
+void ptau_contribute(zkpoa_context* ctx, const char* in_path, const char* out_path, const uint8_t* secrets_le, const p2::RecordParams& ap) {
   PhaseTimer phase("powersoftau contribute", 34);
   if (same_file(in_path, out_path)) throw SetupError("powersoftau contribute: the output path names the input file");
-  if (ap.name.size() > 255 || ap.beacon.size() > 255) throw SetupError("powersoftau contribute: name or beacon longer than 255 bytes");
   MappedFile fi(in_path);   // mapped for the section table and section 7; the point sections stream with pread
   auto ps = bin_sections(fi, "ptau", 1, "ptau");
   const PtauShape shape = ptau_power_sections(fi, ps);
   const uint32_t power = shape.power;
   const uint64_t N = 1ull << power;
-  std::vector<p1::Record> records;
-  try {
-    records = p1::parse_section7(fi.p + ps[7].off, ps[7].len);
-  } catch (const std::runtime_error& e) {
-    throw SetupError(e.what());
-  }
+  std::vector<p1::Record> records = p1::parse_section7(fi.p + ps[7].off, ps[7].len);
   if (ps.count(12) || ps.count(13) || ps.count(14) || ps.count(15))
     fprintf(stderr, "zkpoa: powersoftau contribute: sections 12-15 (Lagrange form) of the input are dropped: they would be stale; "
                     "run `powersoftau prepare phase2` on the result\n");
@@ -247,36 +148,27 @@ void ptau_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
       else random_scalar(sec.x[k]);
     }
     uint8_t s[3][32];
-    if (!env_phase1_s(s))
+    // ZKPOA_PHASE1_S: "s_tau,s_alpha,s_beta", the s of the key's g1_s = s * G1
+    if (!env_scalars("ZKPOA_PHASE1_S", s, 3, "three numbers in [1, r) separated by commas", "the secrets of the contribution key's g1_s"))
       for (int k = 0; k < 3; k++) random_scalar(s[k]);
     uint8_t g1[64];
     h_affine_to_bytes<HFq>(host_generator<HFq>(), g1);
-    for (int k = 0; k < 3; k++) p1::mul_wire<HFq>(g1, s[k], sec.g1_s[k]);
+    for (int k = 0; k < 3; k++) p2::mul_wire<HFq>(g1, s[k], sec.g1_s[k]);
     wipe(s, sizeof s);
   }
   for (int k = 0; k < 3; k++)
     if (!scalar_in_range(sec.x[k], true)) throw SetupError("powersoftau contribute: tau, alpha and beta must be in [1, r)");
   p1::Record rec;
-  rec.type = ap.type;
-  rec.name = ap.name;
-  rec.beacon = ap.beacon;
-  rec.num_iterations_exp = ap.num_iterations_exp;
+  static_cast<p2::RecordParams&>(rec) = ap;
   p1::make_key(sec, challenge, rec.key);
   phase("sections, challenge, key");
 
   // ---- pass 1: the new sections, their compressed form into the response hash
   constexpr uint64_t kMaxPiece = 1ull << 20;   // 2 x 128 MiB of pinned read-back buffers; from power 20 up no section is whole on the host
   uint64_t piece = (uint64_t)ctx->opt_ptau_piece_points;
-  if (!piece) {   // from free HBM: a quarter of it for a piece's points, results, scalars and XYZZ scratch
-    size_t free_b = 0, total_b = 0;
-    ZK_HIP(hipMemGetInfo(&free_b, &total_b));
-    piece = std::max<uint64_t>(1ull << 12, std::min<uint64_t>(free_b / 4 / (128 + 128 + 32 + 256), kMaxPiece));
-  }
+  if (!piece) piece = piece_from_free_hbm(128 + 128 + 32 + 256, 1ull << 12, kMaxPiece);   // a piece's points, results, scalars and XYZZ scratch
   piece = std::min<uint64_t>(std::min<uint64_t>(piece, kMaxPiece), 2 * N);
-  const PtauLayout lay(power, ps[7].len + p1::kRecordFixed + p1::params_len(rec));
-  AtomicFile fo(out_path);
-  fo.reserve(lay.total);
-  lay.put_table(fo, power, shape.ceremony);
+  PtauFile fo(out_path, power, shape.ceremony, ps[7].len + p1::kRecordHead + rec.len());
   hipStream_t st = ctx->dev.lanes[0].stream;
   PointChecker points(ctx);
   const uint64_t slab = (uint64_t)ctx->opt_ptau_mul_slab;
@@ -291,14 +183,9 @@ void ptau_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
   p2::Blake2b resp;
   resp.update(challenge, 64);
   uint8_t one[32] = {1};
-  struct Job {
-    uint32_t sec;
-    int group;
-    uint64_t count;
-    const uint8_t *first, *ratio;
-  };
-  const Job jobs[5] = {{2, 1, 2 * N - 1, one, sec.x[0]}, {3, 2, N, one, sec.x[0]}, {4, 1, N, sec.x[1], sec.x[0]},
-                       {5, 1, N, sec.x[2], sec.x[0]}, {6, 2, 1, sec.x[2], one}};
+  // point i of section 2 + t takes first[t] * ratio[t]^i
+  const uint8_t* const first[5] = {one, one, sec.x[1], sec.x[2], sec.x[2]};
+  const uint8_t* const ratio[5] = {sec.x[0], sec.x[0], sec.x[0], sec.x[0], one};
   double read_ms = 0, compute_ms = 0, hash_ms = 0;
   // Read-back: piece p comes back into pinned buffer p & 1 behind the stream's kernels, and a writer thread puts it into
   // the file when its copy has landed -- while the device takes piece p + 1. A buffer is reused when its writer is done.
@@ -328,20 +215,14 @@ void ptau_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
   {
     HashStream hs(ctx, resp, 0);
     uint64_t p = 0;
-    for (const Job& j : jobs) {
-      const uint64_t unit = j.group == 2 ? 128 : 64;
-      const std::string what = "ptau section " + std::to_string(j.sec);
-      for (uint64_t i0 = 0; i0 < j.count; i0 += piece, p++) {
-        const uint64_t cnt = std::min(piece, j.count - i0);
-        const int b = (int)(p & 1);
+    for (const PowerSec& j : ptau_power_secs(power)) {
+      const uint64_t unit = j.unit();
+      const std::string what = "ptau section " + std::to_string(j.id);
+      for_each_piece(ctx, fi.fd, ps[j.id].off, j.count, unit, piece, d_in.p, [&](uint64_t i0, uint64_t cnt) {
+        const int b = (int)(p++ & 1);
         auto t0 = std::chrono::steady_clock::now();
-        ctx->uploader.upload(d_in.p, nullptr, cnt * unit, ctx->dev.device, st, fi.fd, ps[j.sec].off + i0 * unit);
-        read_ms += ms_since(t0);
-        t0 = std::chrono::steady_clock::now();
-        const uint32_t f = points.check(d_in.p, cnt, j.group, j.group == 2, what.c_str());
-        if (f & 2u) throw SetupError(what + ": a point is not on the curve");
-        if (f & 4u) throw SetupError(what + ": a point is outside G2");
-        power_scalars(ctx, j.first, j.ratio, i0, cnt, d_k.p);
+        points.require(d_in.p, cnt, j.group, j.group == 2, what.c_str());
+        power_scalars(ctx, first[j.id - 2], ratio[j.id - 2], i0, cnt, d_k.p);
         if (j.group == 2) scalar_mul_each_g2(ctx, d_in.p, d_k.p, cnt, d_out.p, (uint32_t*)d_flag.p, d_scratch.p, slab);
         else scalar_mul_each_g1(ctx, d_in.p, d_k.p, cnt, d_out.p, (uint32_t*)d_flag.p, d_scratch.p, slab);
         ZK_HIP(hipStreamSynchronize(st));
@@ -352,18 +233,19 @@ void ptau_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
         rb.wait(b);
         ZK_HIP(hipMemcpyAsync(rb.pinned[b], d_out.p, cnt * unit, hipMemcpyDeviceToHost, st));
         ZK_HIP(hipEventRecord(rb.ev[b], st));
-        const uint64_t at = lay.off[j.sec] + i0 * unit, len = cnt * unit;
+        const uint32_t id = j.id;
+        const uint64_t at = i0 * unit, len = cnt * unit;
         const int device = ctx->dev.device;
-        rb.writer[b] = std::thread([&rb, &fo, b, at, len, device] {
+        rb.writer[b] = std::thread([&rb, &fo, b, id, at, len, device] {
           const auto w0 = std::chrono::steady_clock::now();
           if (hipSetDevice(device) != hipSuccess || hipEventSynchronize(rb.ev[b]) != hipSuccess) {
             rb.failed = true;
             return;
           }
-          fo.put_at(at, rb.pinned[b], len);
+          fo.put_at(id, at, rb.pinned[b], len);
           rb.write_ms[b] += ms_since(w0);
         });
-      }
+      }, &read_ms);
     }
     rb.wait(0);
     rb.wait(1);
@@ -381,14 +263,12 @@ void ptau_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
   resp.final(response);
 
   // ---- pass 2: nextChallenge = Blake2b(response hash | hash form of the new sections 2-6), from the written file
-  std::map<uint32_t, Sec> outs;
-  for (uint32_t t = 1; t <= 7; t++) outs[t] = Sec{lay.off[t], lay.len[t]};
   struct ReadFd {   // the output is open for writing only: its bytes are read back through a descriptor of their own
     int fd;
     ~ReadFd() {
       if (fd >= 0) close(fd);
     }
-  } out_r{open(fo.tmp.c_str(), O_RDONLY | O_CLOEXEC)};
+  } out_r{open(fo.file.tmp.c_str(), O_RDONLY | O_CLOEXEC)};
   if (out_r.fd < 0) throw SetupError("powersoftau contribute: cannot read the output back");
   const int out_fd = out_r.fd;
   {
@@ -396,12 +276,12 @@ void ptau_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
     p2::Blake2b next;
     next.update(response, 64);
     HashStream hs(ctx, next, 0);
-    hash_form_ptau_sections(ctx, hs, out_fd, outs, power, d_in.p, piece);
+    hash_form_ptau_sections(ctx, hs, out_fd, fo.secs, power, d_in.p, piece);
     next.final(rec.next_challenge);
     hash_ms += ms_since(t0);
   }
   auto back = [&](uint32_t sec, uint64_t point, uint64_t unit, uint8_t* dst) {
-    if (pread(out_fd, dst, unit, (off_t)(lay.off[sec] + point * unit)) != (ssize_t)unit) throw SetupError("powersoftau contribute: cannot read the output back");
+    if (pread(out_fd, dst, unit, (off_t)(fo.off(sec) + point * unit)) != (ssize_t)unit) throw SetupError("powersoftau contribute: cannot read the output back");
   };
   back(2, 1, 64, rec.tau_g1);
   back(3, 1, 128, rec.tau_g2);
@@ -410,8 +290,7 @@ void ptau_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
   back(6, 0, 128, rec.beta_g2);
   records.push_back(rec);
   const std::vector<uint8_t> s7 = p1::write_section7(records);
-  if (s7.size() != lay.len[7]) throw SetupError("internal: section 7 has an unexpected size");
-  fo.put_at(lay.off[7], s7.data(), s7.size());
+  fo.put(7, s7.data(), s7.size());
   fo.commit();
   if (phase.verbose) {
     const char* what[4] = {"read (file -> HBM)", "compute (checks, scalars, products)", "hashes (response, nextChallenge)", "write (HBM -> file; overlaps the rest)"};
@@ -454,18 +333,7 @@ extern "C" int zkpoa_power_scalars_device(zkpoa_context* ctx, const uint8_t firs
 extern "C" int zkpoa_compressed_form(zkpoa_context* ctx, int group, const void* points, uint64_t n, uint64_t piece_points,
                                      void* out_bytes, uint8_t digest[64]) {
   ZK_API_BEGIN(ctx)
-  if ((group != 1 && group != 2) || (n && !points) || !digest) throw SetupError("compressed form: bad argument");
-  const uint64_t unit = group == 1 ? 64 : 128;
-  host_check_coords(static_cast<const uint8_t*>(points), n * unit / 32, "compressed form");
-  DevBuf d(n * unit);
-  d.up(points, n * unit);
-  p2::Blake2b h;
-  HashStream hs(ctx, h, piece_points);
-  std::vector<uint8_t> cap;
-  if (out_bytes) hs.capture = &cap;
-  hs.points(d.p, n, group, false, true);
-  h.final(digest);
-  if (out_bytes && n) memcpy(out_bytes, cap.data(), n * unit / 2);
+  points_form(ctx, group, points, n, piece_points, true, out_bytes, digest);
   ZK_API_END(ctx)
 }
 
@@ -480,8 +348,9 @@ extern "C" int zkpoa_ptau_contribute(zkpoa_context* ctx, const char* in_path, co
                                      const char* name) {
   ZK_API_BEGIN(ctx)
   if (!in_path || !out_path) throw SetupError("powersoftau contribute: null path");
-  Append ap;
+  p2::RecordParams ap;
   ap.name = name ? name : "";
+  ap.check("powersoftau contribute");
   ptau_contribute(ctx, in_path, out_path, secrets_le, ap);
   ZK_API_END(ctx)
 }
@@ -490,13 +359,12 @@ extern "C" int zkpoa_ptau_beacon(zkpoa_context* ctx, const char* in_path, const 
                                  unsigned long beacon_len, uint32_t num_iterations_exp, const char* name) {
   ZK_API_BEGIN(ctx)
   if (!in_path || !out_path || (!beacon && beacon_len)) throw SetupError("powersoftau beacon: null argument");
-  if (num_iterations_exp > p2::kMaxBeaconExp) throw SetupError("powersoftau beacon: numIterationsExp above 30 is refused (2^30 hashes take minutes; more would not finish)");
-  if (beacon_len > 255) throw SetupError("powersoftau beacon: a beacon longer than 255 bytes is refused");
-  Append ap;
+  p2::RecordParams ap;
   ap.type = 1;
   ap.name = name ? name : "";
   ap.beacon.assign(beacon, beacon + beacon_len);
   ap.num_iterations_exp = num_iterations_exp;
+  ap.check("powersoftau beacon");
   ptau_contribute(ctx, in_path, out_path, nullptr, ap);
   ZK_API_END(ctx)
 }

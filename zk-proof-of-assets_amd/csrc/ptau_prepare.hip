@@ -10,7 +10,8 @@
 // A source section is uploaded once, its levels run one after the other into one device copy of the output section,
 // which comes back in one piece. A level whose buffers do not fit in free HBM is an error before anything is written:
 // streaming a level through HBM in pieces is not done. Sections 1-7 are copied byte for byte, sections 12-15 of the
-// input, if any, are ignored; the output appears under its name only when it is complete (AtomicFile).
+// input, if any, are ignored; the output (csrc/setup_common.hip.h: SectionFile, 11 sections in the order 1-7, 12-15)
+// appears under its name only when it is complete.
 #include "setup_common.hip.h"
 #include "zkpoa_internal.hpp"
 
@@ -19,18 +20,6 @@
 using namespace zkpoa;
 
 namespace {
-
-struct PrepareJob {
-  uint32_t src, dst;
-  int group;
-  uint32_t top;   // levels 0..top
-};
-
-bool same_file(const char* a, const char* b) {
-  struct stat sa, sb;
-  if (stat(a, &sa) != 0 || stat(b, &sb) != 0) return false;
-  return sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino;
-}
 
 void ptau_prepare(zkpoa_context* ctx, const char* in_path, const char* out_path, uint32_t info[4]) {
   PhaseTimer phase("powersoftau prepare phase2", 34);
@@ -44,14 +33,12 @@ void ptau_prepare(zkpoa_context* ctx, const char* in_path, const char* out_path,
   info[1] = shape.ceremony;
   info[2] = ps.count(12) && ps.count(13) && ps.count(14) && ps.count(15) ? 1 : 0;
   info[3] = shape.contributions;
-  const PrepareJob jobs[4] = {{2, 12, 1, p + 1}, {3, 13, 2, p}, {4, 14, 1, p}, {5, 15, 1, p}};
-  auto unit = [](const PrepareJob& j) { return (uint64_t)(j.group == 2 ? 128 : 64); };
-  auto src_bytes = [&](const PrepareJob& j) { return unit(j) << j.top; };                 // section 2: with its infinity
-  auto out_bytes = [&](const PrepareJob& j) { return unit(j) * ((2ull << j.top) - 1); };
+  const auto jobs = ptau_lagrange_secs(p);
+  auto src_bytes = [](const LagrangeSec& j) { return j.unit() << j.top; };   // section 2: with its infinity
   {
     size_t free_b = 0, total_b = 0, need = 0;
     ZK_HIP(hipMemGetInfo(&free_b, &total_b));
-    for (const auto& j : jobs) need = std::max<size_t>(need, src_bytes(j) + out_bytes(j) + ec_intt_work_bytes(j.group, j.top));
+    for (const auto& j : jobs) need = std::max<size_t>(need, src_bytes(j) + j.bytes() + ec_intt_work_bytes(j.group, j.top));
     need += 64u << 20;   // flags, the allocator's granularity
     if (need > free_b)
       throw SetupError("powersoftau prepare phase2: power " + std::to_string(p) + " needs " + std::to_string(need >> 20) +
@@ -63,10 +50,7 @@ void ptau_prepare(zkpoa_context* ctx, const char* in_path, const char* out_path,
   hipStream_t st = ctx->dev.lanes[0].stream;
   PointChecker points(ctx);
   auto checked = [&](const void* d, uint64_t count, int group, bool subgroup, uint32_t sec) {
-    const std::string what = "ptau section " + std::to_string(sec);
-    const uint32_t f = points.check(d, count, group, subgroup, what.c_str());
-    if (f & 2u) throw SetupError(what + ": a point is not on the curve");
-    if (f & 4u) throw SetupError(what + ": a point is outside G2");
+    points.require(d, count, group, subgroup, ("ptau section " + std::to_string(sec)).c_str());
   };
   {
     DevBuf beta2(128);
@@ -75,42 +59,35 @@ void ptau_prepare(zkpoa_context* ctx, const char* in_path, const char* out_path,
   }
   UVec<uint8_t> out[4];
   for (int t = 0; t < 4; t++) {
-    const PrepareJob& j = jobs[t];
+    const LagrangeSec& j = jobs[t];
     const uint64_t have = ps[j.src].len;   // (2N - 1) * 64 for section 2: one point short of the top level
-    DevBuf src(src_bytes(j)), dst(out_bytes(j));
+    DevBuf src(src_bytes(j)), dst(j.bytes());
     ctx->uploader.upload(src.p, nullptr, have, ctx->dev.device, st, fp.fd, ps[j.src].off);
     if (have < src_bytes(j)) ZK_HIP(hipMemsetAsync(static_cast<char*>(src.p) + have, 0, src_bytes(j) - have, st));
-    checked(src.p, have / unit(j), j.group, j.group == 2, j.src);
+    checked(src.p, have / j.unit(), j.group, j.group == 2, j.src);
     std::unique_ptr<EcNttWork> wk(j.group == 2 ? ec_intt_work_g2(ctx, j.top) : ec_intt_work_g1(ctx, j.top));
     for (uint32_t l = 0; l <= j.top; l++) {
-      void* to = static_cast<char*>(dst.p) + unit(j) * ((1ull << l) - 1);
+      void* to = static_cast<char*>(dst.p) + j.unit() * ((1ull << l) - 1);
       if (j.group == 2) ec_intt_g2(ctx, *wk, src.p, l, to);
       else ec_intt_g1(ctx, *wk, src.p, l, to);
     }
     ZK_HIP(hipStreamSynchronize(st));
     ZK_HIP(hipGetLastError());
     if (phase.verbose) phase(("section " + std::to_string(j.dst) + " (upload, point checks, iNTT)").c_str());
-    out[t].alloc(out_bytes(j));
-    ZK_HIP(hipMemcpy(out[t].data(), dst.p, out_bytes(j), hipMemcpyDeviceToHost));
+    out[t].alloc(j.bytes());
+    ZK_HIP(hipMemcpy(out[t].data(), dst.p, j.bytes(), hipMemcpyDeviceToHost));
     if (phase.verbose) phase(("section " + std::to_string(j.dst) + " (download)").c_str());
   }
 
-  AtomicFile fo(out_path);
-  auto put32 = [&](uint32_t v) { fo.write(&v, 4); };
-  auto put64 = [&](uint64_t v) { fo.write(&v, 8); };
-  fo.write("ptau", 4);
-  put32(1);
-  put32(11);
-  for (uint32_t t = 1; t <= 7; t++) {
-    put32(t);
-    put64(ps[t].len);
-    fo.write_large(fp.p + ps[t].off, ps[t].len);
+  uint32_t ids[11];   // sections 1-7 as they are, then 12-15
+  uint64_t lens[11];
+  for (uint32_t t = 0; t < 11; t++) {
+    ids[t] = t < 7 ? t + 1 : jobs[t - 7].dst;
+    lens[t] = t < 7 ? ps[ids[t]].len : out[t - 7].size();
   }
-  for (int t = 0; t < 4; t++) {
-    put32(jobs[t].dst);
-    put64(out[t].size());
-    fo.write_large(out[t].data(), out[t].size());
-  }
+  SectionFile fo(out_path, "ptau", ids, lens, 11);
+  for (uint32_t t = 1; t <= 7; t++) fo.put(t, fp.p + ps[t].off, ps[t].len);
+  for (int t = 0; t < 4; t++) fo.put(jobs[t].dst, out[t].data(), out[t].size());
   fo.commit();
   phase("write");
 }

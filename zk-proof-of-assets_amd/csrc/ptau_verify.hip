@@ -15,8 +15,8 @@
 //     The top level p+1 of section 12 would need tau^(2N-1), which the file does not hold: that level is checked on
 //     the 2N - 1 powers that exist (u_{2N-1} = 0, P(x) = (1 - (rho x)^(2N-1)) / (1 - rho x)).
 // The weights are made on the device per piece (power tables by thread runs; the Lagrange side's 1 / (1 - rho w^j) by a
-// batched inversion, Montgomery's trick per thread run). Each section streams through HBM in pieces: upload from the
-// file, point checks (curve, range, G2 subgroup), MSMs with the piece's weights; the partial sums are added on the host.
+// batched inversion, Montgomery's trick per thread run). Each section streams through HBM in pieces
+// (csrc/setup_common.hip.h: for_each_piece; the sections' point counts: csrc/binfile.hpp): upload from the file, point checks (curve, range, G2 subgroup), MSMs with the piece's weights; the partial sums are added on the host.
 // Section 7 (DESIGN.md "Phase-1 transcript"): its records are checked on the host (csrc/phase1.hpp: keys, ratios, the
 // beacon, the last record against the file's points); the last nextChallenge needs the hash form of sections 2-6, which
 // streams from the file through the device conversion of csrc/phase2_dev.hip.h into Blake2b.
@@ -33,16 +33,6 @@ using namespace zkpoa;
 namespace {
 
 constexpr uint32_t kRun = 16;   // consecutive weights per thread: one exponentiation (and one inversion) per run
-
-ZK_DEV Fr fr_pow_u64(Fr b, uint64_t e) {
-  Fr r = Fr::one();
-  while (e) {
-    if (e & 1u) r = r * b;
-    b = b.sqr();
-    e >>= 1;
-  }
-  return r;
-}
 
 // level l of the Lagrange sections (n = 2^l points), Montgomery form; the same rho_l for every section
 struct PtauLevel {
@@ -141,11 +131,6 @@ static __global__ __launch_bounds__(256) void power_weights_kernel(const PtauLev
     if (k < m) store_field(olag + 32 * k, s[k].from_mont());
 }
 
-Fr fr_dev(const HFr& h) {
-  Fr f;
-  memcpy(&f, &h, 32);
-  return f;
-}
 HFr fr_pow_host(const HFr& b, uint64_t e) {
   const uint64_t ex[4] = {e, 0, 0, 0};
   return b.pow(ex);
@@ -184,11 +169,9 @@ struct Streamer {
            XYZZ<HF>* ratio, XYZZ<HF>* lag) {
     constexpr bool kG2 = std::is_same<HF, HFq2>::value;
     constexpr uint64_t unit = kG2 ? 128 : 64;
-    for (uint64_t i0 = 0; i0 < K; i0 += piece) {
-      const uint64_t cnt = K - i0 < piece ? K - i0 : piece;
-      ctx->uploader.upload(pts.p, nullptr, cnt * unit, ctx->dev.device, st, fd, sc.off + i0 * unit);
+    for_each_piece(ctx, fd, sc.off, K, unit, piece, pts.p, [&](uint64_t i0, uint64_t cnt) {
       if (points.check(pts.p, cnt, kG2 ? 2 : 1, subgroup, what) & 6u) bad_points = true;
-      if (mode == kCheck) continue;
+      if (mode == kCheck) return;
       const dim3 wgrid((uint32_t)((cnt + 256 * kRun - 1) / (256 * kRun)));
       if (mode == kPower)
         hipLaunchKernelGGL(power_weights_kernel, wgrid, dim3(256), 0, st, d_lv, n_levels, fr_dev(*rho), i0, cnt, K, w1.p,
@@ -207,7 +190,7 @@ struct Streamer {
       } else {
         msm(w1.p, lag);
       }
-    }
+    });
   }
 };
 
@@ -236,20 +219,14 @@ uint32_t ptau_verify(zkpoa_context* ctx, const char* path, uint64_t piece_points
   const bool prepared = n_lag == 4;
   if (prepared) {
     ptau_check_preparable(power);
-    const uint64_t wl[4] = {(4 * N - 1) * 64, (2 * N - 1) * 128, (2 * N - 1) * 64, (2 * N - 1) * 64};
-    for (uint32_t t = 12; t <= 15; t++)
-      if (ps[t].len != wl[t - 12]) throw SetupError("ptau: section " + std::to_string(t) + " has the wrong length for power " + std::to_string(power));
+    for (const LagrangeSec& sc : ptau_lagrange_secs(power))
+      if (ps[sc.dst].len != sc.bytes()) throw SetupError("ptau: section " + std::to_string(sc.dst) + " has the wrong length for power " + std::to_string(power));
   }
   info[0] = power;
   info[1] = shape.ceremony;
   info[2] = prepared ? 1 : 0;
   info[3] = shape.contributions;
-  std::vector<zkpoa::phase1::Record> records;
-  try {
-    records = zkpoa::phase1::parse_section7(fp.p + ps[7].off, ps[7].len);
-  } catch (const std::runtime_error& e) {
-    throw SetupError(e.what());
-  }
+  const std::vector<zkpoa::phase1::Record> records = zkpoa::phase1::parse_section7(fp.p + ps[7].off, ps[7].len);
   phase("sections");
 
   // ---- random weights: one rho per power section (ratio checks), one rho_l per level (Lagrange checks)
@@ -288,12 +265,7 @@ uint32_t ptau_verify(zkpoa_context* ctx, const char* path, uint64_t piece_points
   phase("random weights");
 
   // ---- the sections, streamed
-  if (!piece_points) {   // derived from free HBM: a quarter of it for the piece's points and weights
-    size_t free_b = 0, total_b = 0;
-    ZK_HIP(hipMemGetInfo(&free_b, &total_b));
-    piece_points = free_b / 4 / (128 + 64);
-    piece_points = std::max<uint64_t>(1ull << 16, std::min<uint64_t>(piece_points, 1ull << 26));
-  }
+  if (!piece_points) piece_points = piece_from_free_hbm(128 + 64, 1ull << 16, 1ull << 26);   // the piece's points and weights
   piece_points = std::min<uint64_t>(piece_points, 4 * N);   // no piece larger than the largest section
   Streamer sm(ctx, fp.fd, piece_points, (const PtauLevel*)d_lv.p);
   typedef XYZZ<HFq> P1;
@@ -301,17 +273,19 @@ uint32_t ptau_verify(zkpoa_context* ctx, const char* path, uint64_t piece_points
   P1 mT = P1::inf(), mA = P1::inf(), mB = P1::inf(), sT = P1::inf(), sA = P1::inf(), sB = P1::inf();
   P1 lT = P1::inf(), lA = P1::inf(), lB = P1::inf();
   P2 mU = P2::inf(), sU = P2::inf(), lU = P2::inf();
-  sm.run<HFq>(ps[2], 2 * N - 1, false, Streamer::kPower, &rho_T, n_levels, "ptau section 2", &mT, &sT);
-  sm.run<HFq2>(ps[3], N, true, Streamer::kPower, &rho_U, n_levels ? power + 1 : 0, "ptau section 3", &mU, &sU);
-  sm.run<HFq>(ps[4], N, false, Streamer::kPower, &rho_A, n_levels ? power + 1 : 0, "ptau section 4", &mA, &sA);
-  sm.run<HFq>(ps[5], N, false, Streamer::kPower, &rho_B, n_levels ? power + 1 : 0, "ptau section 5", &mB, &sB);
-  sm.run<HFq2>(ps[6], 1, true, Streamer::kCheck, nullptr, 0, "ptau section 6", (P2*)nullptr, (P2*)nullptr);
+  const auto pw = ptau_power_secs(power);   // sections 2-6: the typed sums above fix the order, the table the counts
+  sm.run<HFq>(ps[2], pw[0].count, false, Streamer::kPower, &rho_T, n_levels, "ptau section 2", &mT, &sT);
+  sm.run<HFq2>(ps[3], pw[1].count, true, Streamer::kPower, &rho_U, n_levels ? power + 1 : 0, "ptau section 3", &mU, &sU);
+  sm.run<HFq>(ps[4], pw[2].count, false, Streamer::kPower, &rho_A, n_levels ? power + 1 : 0, "ptau section 4", &mA, &sA);
+  sm.run<HFq>(ps[5], pw[3].count, false, Streamer::kPower, &rho_B, n_levels ? power + 1 : 0, "ptau section 5", &mB, &sB);
+  sm.run<HFq2>(ps[6], pw[4].count, true, Streamer::kCheck, nullptr, 0, "ptau section 6", (P2*)nullptr, (P2*)nullptr);
   phase("powers (upload, checks, MSMs)");
   if (prepared) {
-    sm.run<HFq>(ps[12], 4 * N - 1, false, Streamer::kLagrange, nullptr, 0, "ptau section 12", (P1*)nullptr, &lT);
-    sm.run<HFq2>(ps[13], 2 * N - 1, true, Streamer::kLagrange, nullptr, 0, "ptau section 13", (P2*)nullptr, &lU);
-    sm.run<HFq>(ps[14], 2 * N - 1, false, Streamer::kLagrange, nullptr, 0, "ptau section 14", (P1*)nullptr, &lA);
-    sm.run<HFq>(ps[15], 2 * N - 1, false, Streamer::kLagrange, nullptr, 0, "ptau section 15", (P1*)nullptr, &lB);
+    const auto lg = ptau_lagrange_secs(power);   // sections 12-15
+    sm.run<HFq>(ps[12], lg[0].count(), false, Streamer::kLagrange, nullptr, 0, "ptau section 12", (P1*)nullptr, &lT);
+    sm.run<HFq2>(ps[13], lg[1].count(), true, Streamer::kLagrange, nullptr, 0, "ptau section 13", (P2*)nullptr, &lU);
+    sm.run<HFq>(ps[14], lg[2].count(), false, Streamer::kLagrange, nullptr, 0, "ptau section 14", (P1*)nullptr, &lA);
+    sm.run<HFq>(ps[15], lg[3].count(), false, Streamer::kLagrange, nullptr, 0, "ptau section 15", (P1*)nullptr, &lB);
     phase("Lagrange form (upload, checks, MSMs)");
   }
 

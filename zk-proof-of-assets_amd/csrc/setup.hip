@@ -415,32 +415,7 @@ void circuit_hash(zkpoa_context* ctx, const char* ptau_path, const CsHashPoints&
   phase("circuit hash");
 }
 
-// A .zkey whose ten section lengths are known before their content: the file is sized, magic and section table are
-// written, and put() places a payload from any thread, in any order.
-struct ZkeyWriter {
-  AtomicFile fo;
-  uint64_t len[11], off[11];
-  ZkeyWriter(const char* path, const uint64_t sec_len[11]) : fo(path) {
-    uint64_t total = 12;
-    for (uint32_t t = 1; t <= 10; t++) {
-      len[t] = sec_len[t];
-      off[t] = total + 12;
-      total += 12 + len[t];
-    }
-    fo.reserve(total);
-    const uint32_t hdr[2] = {1, 10};   // version, sections
-    fo.put_at(0, "zkey", 4);
-    fo.put_at(4, hdr, 8);
-    for (uint32_t t = 1; t <= 10; t++) {
-      fo.put_at(off[t] - 12, &t, 4);
-      fo.put_at(off[t] - 8, &len[t], 8);
-    }
-  }
-  void put(uint32_t id, const void* p, uint64_t n) {
-    if (n != len[id]) throw SetupError("internal: section " + std::to_string(id) + " has an unexpected size");
-    fo.put_at(off[id], p, n);
-  }
-};
+constexpr uint32_t kZkeyIds[10] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10};   // a .zkey's sections, in the order snarkjs numbers them
 
 void put32(std::vector<uint8_t>& v, uint32_t x) { v.insert(v.end(), (uint8_t*)&x, (uint8_t*)&x + 4); }
 void put64(std::vector<uint8_t>& v, uint64_t x) { v.insert(v.end(), (uint8_t*)&x, (uint8_t*)&x + 8); }
@@ -469,8 +444,8 @@ void zkey_new(zkpoa_context* ctx, const char* r1cs_path, const char* ptau_path, 
   const uint64_t nCoefs = r.A.size() + r.B.size() + r.nPublic + 1;
   if (nCoefs > 0xffffffffull) throw SetupError("more than 2^32 coefficients");
   const uint64_t icb = ((uint64_t)r.nPublic + 1) * 64;
-  const uint64_t sec_len[11] = {0, 4, kHdrLen, icb, 4 + nCoefs * 44, m * 64, m * 64, m * 128, (m - r.nPublic - 1) * 64, n * 64, 64 + 4};
-  ZkeyWriter out(zkey_path, sec_len);
+  const uint64_t sec_len[10] = {4, kHdrLen, icb, 4 + nCoefs * 44, m * 64, m * 64, m * 128, (m - r.nPublic - 1) * 64, n * 64, 64 + 4};
+  SectionFile out(zkey_path, "zkey", kZkeyIds, sec_len, 10);
   auto put_section = [&](uint32_t id, const void* p, uint64_t len) { out.put(id, p, len); };
   std::exception_ptr host_err;
   double host_ms = 0;
@@ -600,7 +575,7 @@ void zkey_new(zkpoa_context* ctx, const char* r1cs_path, const char* ptau_path, 
   if (host_err) std::rethrow_exception(host_err);
   if (write_err) std::rethrow_exception(write_err);
   if (phase.verbose) fprintf(stderr, "zkpoa: zkey new: (header, coefficient and H sections built and written by a side thread meanwhile: %.1f ms)\n", host_ms);
-  out.fo.commit();
+  out.commit();
   phase("last sections written, key renamed into place");
 }
 
@@ -648,53 +623,10 @@ uint64_t wtns_check(zkpoa_context* ctx, const char* r1cs_path, const char* wtns_
 }
 
 // ---- the arithmetic of `snarkjs zkey contribute` (g16_setup.sh:262-266): delta <- d * delta, C and H <- C, H / d ---------
-// what `zkey contribute` / `zkey beacon` add to section 10 when the input carries a transcript
-struct Phase2Append {
-  uint32_t type = 0;   // 0 contribution, 1 beacon
-  std::string name;
-  std::vector<uint8_t> beacon;
-  uint32_t num_iterations_exp = 0;
-};
-void random_scalar(uint8_t d[32]) {   // uniform on [1, r): 254 random bits, rejected while >= r or zero
-  for (;;) {
-    urandom(d, 32);
-    d[31] &= 0x3f;
-    uint64_t v[4];
-    memcpy(v, d, 32);
-    if (!HFr::geq_p(v) && (v[0] | v[1] | v[2] | v[3])) break;
-  }
-}
-// ZKPOA_PHASE2_S (tests / reproducible records only): the s of g1_s = s * G1, decimal or 0x... hex, in [1, r)
-bool env_scalar(const char* name, uint8_t out[32]) {
-  const char* e = getenv(name);
-  if (!e) return false;
-  memset(out, 0, 32);
-  const bool hex = e[0] == '0' && (e[1] == 'x' || e[1] == 'X');
-  bool ok = *(hex ? e + 2 : e) != 0;
-  for (const char* p = hex ? e + 2 : e; *p && ok; p++) {
-    unsigned d = 99;
-    if (*p >= '0' && *p <= '9') d = (unsigned)(*p - '0');
-    else if (hex && (*p | 32) >= 'a' && (*p | 32) <= 'f') d = (unsigned)((*p | 32) - 'a' + 10);
-    if (d == 99) ok = false;
-    unsigned carry = d;
-    for (int i = 0; i < 32; i++) {
-      const unsigned v = out[i] * (hex ? 16u : 10u) + carry;
-      out[i] = (uint8_t)v;
-      carry = v >> 8;
-    }
-    if (carry) ok = false;
-  }
-  uint64_t v[4];
-  memcpy(v, out, 32);
-  if (!ok || HFr::geq_p(v) || !(v[0] | v[1] | v[2] | v[3])) throw SetupError(std::string(name) + " is not a number in [1, r)");
-  fprintf(stderr, "zkpoa: WARNING: a secret of the contribution record taken from %s -- for tests only\n", name);
-  return true;
-}
-
 // rec: null = the arithmetic alone, section 10 copied as it is (zkpoa_zkey_contribute); else the input must carry a
 // transcript, and a record is appended. A beacon's delta comes from its generator (delta_le is not read).
 void zkey_contribute(zkpoa_context* ctx, const char* in_path, const char* out_path, const uint8_t* delta_le,
-                     const Phase2Append* rec) {
+                     const zkpoa::phase2::RecordParams* rec) {
   namespace p2 = zkpoa::phase2;
   MappedFile fi(in_path);
   auto secs = bin_sections(fi, "zkey", 1, "zkey");
@@ -713,52 +645,41 @@ void zkey_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
   if (rec) {
     tr = p2::parse_section10(fi.p + secs[10].off, secs[10].len);
     if (!tr.present()) throw SetupError("zkey: the key carries no transcript (circuit hash is zero): make it with `zkey new --transcript`");
-    if (rec->name.size() > 255 || rec->beacon.size() > 255) throw SetupError("contribution name or beacon longer than 255 bytes");
   }
   if (rec && rec->type == 1) {   // d, then g1_s, from the beacon's generator: any verifier recomputes both
     uint32_t key[8];
     p2::beacon_key(rec->beacon.data(), rec->beacon.size(), rec->num_iterations_exp, key);
     p2::ChaCha rng(key);
-    p2::fr_from_rng(rng, d);
-    h_affine_to_bytes<HFq>(p2::g1_from_rng(rng), g1_s);
+    p2::beacon_draw(rng, d, g1_s);
   } else {
     if (delta_le) memcpy(d, delta_le, 32);
     else random_scalar(d);
     if (rec) {
-      uint8_t sb[32];
-      if (!env_scalar("ZKPOA_PHASE2_S", sb)) random_scalar(sb);
-      uint64_t sv[4];
-      memcpy(sv, sb, 32);
-      h_affine_to_bytes<HFq>(h_to_affine(h_mul(XYZZ<HFq>::from_affine(host_generator<HFq>()), sv)), g1_s);
+      uint8_t sb[1][32];   // ZKPOA_PHASE2_S: the s of g1_s = s * G1
+      if (!env_scalars("ZKPOA_PHASE2_S", sb, 1, "a number in [1, r)", "a secret of the contribution record")) random_scalar(sb[0]);
+      h_affine_to_bytes<HFq>(host_generator<HFq>(), g1_s);
+      p2::mul_wire<HFq>(g1_s, sb[0], g1_s);
     }
   }
-  uint64_t dv[4];
-  memcpy(dv, d, 32);
-  if (HFr::geq_p(dv) || !(dv[0] | dv[1] | dv[2] | dv[3])) throw SetupError("contribute: delta must be in [1, r)");
+  if (!scalar_in_range(d, true)) throw SetupError("contribute: delta must be in [1, r)");
   HFr dinv = HFr::from_bytes(d).to_mont().inv().from_mont();
   uint8_t dinv_le[32];
   memcpy(dinv_le, dinv.l, 32);
 
   std::vector<uint8_t> s2(fi.p + h.off, fi.p + h.off + h.len);
   host_check_coords(&s2[kDelta1], 2 + 4, "zkey delta1 / delta2");
-  {
-    Affine<HFq> d1 = h_affine_from_bytes<HFq>(&s2[kDelta1]);
-    Affine<HFq2> d2 = h_affine_from_bytes<HFq2>(&s2[kDelta2]);
-    h_affine_to_bytes<HFq>(h_to_affine(h_mul(XYZZ<HFq>::from_affine(d1), dv)), &s2[kDelta1]);
-    h_affine_to_bytes<HFq2>(h_to_affine(h_mul(XYZZ<HFq2>::from_affine(d2), dv)), &s2[kDelta2]);
-  }
+  p2::mul_wire<HFq>(&s2[kDelta1], d, &s2[kDelta1]);
+  p2::mul_wire<HFq2>(&s2[kDelta2], d, &s2[kDelta2]);
   std::vector<uint8_t> s10(fi.p + secs[10].off, fi.p + secs[10].off + secs[10].len);
   if (rec) {
     p2::Record nr;
-    nr.type = rec->type;
-    nr.name = rec->name;
-    nr.beacon = rec->beacon;
-    nr.num_iterations_exp = rec->num_iterations_exp;
+    static_cast<p2::RecordParams&>(nr) = *rec;
     memcpy(nr.delta_after, &s2[kDelta1], 64);
     memcpy(nr.g1_s, g1_s, 64);
-    h_affine_to_bytes<HFq>(h_to_affine(h_mul(XYZZ<HFq>::from_affine(h_affine_from_bytes<HFq>(g1_s)), dv)), nr.g1_sx);
+    p2::mul_wire<HFq>(g1_s, d, nr.g1_sx);
     p2::transcript_hash(tr, tr.records.size(), nr.g1_s, nr.g1_sx, nr.transcript);
-    h_affine_to_bytes<HFq2>(h_to_affine(h_mul(XYZZ<HFq2>::from_affine(p2::hash_to_g2(nr.transcript)), dv)), nr.g2_spx);
+    h_affine_to_bytes<HFq2>(p2::hash_to_g2(nr.transcript), nr.g2_spx);
+    p2::mul_wire<HFq2>(nr.g2_spx, d, nr.g2_spx);
     tr.records.push_back(nr);
     s10 = p2::write_section10(tr);
   }
@@ -775,11 +696,11 @@ void zkey_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
   };
   // the output is sized up front (the section lengths do not change): the sections that are copied as they are go into
   // it from a side thread while the device scales C and H
-  uint64_t sec_len[11] = {0};
-  for (uint32_t t = 1; t <= 10; t++) sec_len[t] = secs[t].len;
-  sec_len[10] = s10.size();
-  ZkeyWriter out(out_path, sec_len);   // temporary name + rename: in_path == out_path is fine (the mapping keeps the old inode)
-  auto put_section = [&](uint32_t t, const uint8_t* p) { out.put(t, p, sec_len[t]); };
+  uint64_t sec_len[10];
+  for (uint32_t t = 1; t <= 10; t++) sec_len[t - 1] = secs[t].len;
+  sec_len[9] = s10.size();
+  SectionFile out(out_path, "zkey", kZkeyIds, sec_len, 10);   // temporary name + rename: in_path == out_path is fine (the mapping keeps the old inode)
+  auto put_section = [&](uint32_t t, const uint8_t* p) { out.put(t, p, out.len(t)); };
   std::exception_ptr copy_err;
   std::thread copier([&] {
     try {
@@ -806,7 +727,7 @@ void zkey_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
   }
   copier.join();
   if (copy_err) std::rethrow_exception(copy_err);
-  out.fo.commit();
+  out.commit();
 }
 
 }  // namespace
@@ -821,12 +742,7 @@ uint32_t zkpoa::phase2_verify(zkpoa_context* ctx, const char* r1cs_path, const c
   PhaseTimer phase("zkey verify", 38);
   MappedFile fk(zkey_path);
   auto ks = bin_sections(fk, "zkey", 1, "zkey");
-  p2::Transcript tr;
-  try {
-    tr = p2::parse_section10(fk.p + ks[10].off, ks[10].len);
-  } catch (const std::runtime_error& e) {
-    throw SetupError(e.what());
-  }
+  p2::Transcript tr = p2::parse_section10(fk.p + ks[10].off, ks[10].len);
   uint32_t failed = 0;
   const uint8_t* hp = fk.p + ks[2].off;
   uint8_t cs[64];
@@ -879,13 +795,9 @@ uint32_t zkpoa::phase2_verify(zkpoa_context* ctx, const char* r1cs_path, const c
         uint8_t d[32], want[64];
         p2::beacon_key(rc.beacon.data(), rc.beacon.size(), rc.num_iterations_exp, key);
         p2::ChaCha rng(key);
-        p2::fr_from_rng(rng, d);
-        const pairing::G1 ws = p2::g1_from_rng(rng);
-        h_affine_to_bytes<HFq>(ws, want);
+        p2::beacon_draw(rng, d, want);
         if (memcmp(want, rc.g1_s, 64)) ok = false;
-        uint64_t dv[4];
-        memcpy(dv, d, 32);
-        h_affine_to_bytes<HFq>(h_to_affine(h_mul(XYZZ<HFq>::from_affine(ws), dv)), want);
+        p2::mul_wire<HFq>(want, d, want);
         if (memcmp(want, rc.g1_sx, 64)) ok = false;
       }
     }
@@ -938,8 +850,9 @@ extern "C" int zkpoa_zkey_contribute_ex(zkpoa_context* ctx, const char* zkey_in_
                                         const uint8_t* delta_le, const char* name) {
   ZK_API_BEGIN(ctx)
   if (!zkey_in_path || !zkey_out_path) throw SetupError("zkey contribute: null path");
-  Phase2Append rec;
+  zkpoa::phase2::RecordParams rec;
   rec.name = name ? name : "";
+  rec.check("zkey contribute");
   zkey_contribute(ctx, zkey_in_path, zkey_out_path, delta_le, &rec);
   ZK_API_END(ctx)
 }
@@ -949,33 +862,41 @@ extern "C" int zkpoa_zkey_beacon(zkpoa_context* ctx, const char* zkey_in_path, c
                                  const char* name) {
   ZK_API_BEGIN(ctx)
   if (!zkey_in_path || !zkey_out_path || (!beacon && beacon_len)) throw SetupError("zkey beacon: null argument");
-  if (num_iterations_exp > zkpoa::phase2::kMaxBeaconExp) throw SetupError("zkey beacon: numIterationsExp above 30 is refused (2^30 hashes take minutes; more would not finish)");
-  Phase2Append rec;
+  zkpoa::phase2::RecordParams rec;
   rec.type = 1;
   rec.name = name ? name : "";
   rec.beacon.assign(beacon, beacon + beacon_len);
   rec.num_iterations_exp = num_iterations_exp;
+  rec.check("zkey beacon");
   zkey_contribute(ctx, zkey_in_path, zkey_out_path, nullptr, &rec);
   ZK_API_END(ctx)
 }
 
-// test hooks of the transcript's device work: the hash form of n points of group 1 / 2 (host wire form) streamed in
-// pieces of piece_points, its Blake2b-512 digest, and optionally the bytes; T[i + n] - T[i] over 2n - 1 points
-extern "C" int zkpoa_hash_form(zkpoa_context* ctx, int group, const void* points, uint64_t n, uint64_t piece_points,
-                               void* out_bytes, uint8_t digest[64]) {
-  ZK_API_BEGIN(ctx)
-  if ((group != 1 && group != 2) || (n && !points) || !digest) throw SetupError("hash form: bad argument");
+// test hooks of the transcript's device work: the hash form (compressed: csrc/ptau_contribute.hip's hook, the compressed
+// form, half the bytes) of n points of group 1 / 2 (host wire form) streamed in pieces of piece_points, its Blake2b-512
+// digest, and optionally the bytes. The hash form's coordinates are range-checked on the device, the compressed form's
+// on the host. Then T[i + n] - T[i] over 2n - 1 points.
+void zkpoa::points_form(zkpoa_context* ctx, int group, const void* points, uint64_t n, uint64_t piece_points, bool compressed,
+                        void* out, uint8_t digest[64]) {
+  const char* const what = compressed ? "compressed form" : "hash form";
+  if ((group != 1 && group != 2) || (n && !points) || !digest) throw SetupError(std::string(what) + ": bad argument");
   const uint64_t unit = group == 1 ? 64 : 128;
+  if (compressed) host_check_coords(static_cast<const uint8_t*>(points), n * unit / 32, what);
   DevBuf d(n * unit);
   d.up(points, n * unit);
-  dev_check_coords(ctx, d.p, n * unit / 32, "hash form");
+  if (!compressed) dev_check_coords(ctx, d.p, n * unit / 32, what);
   zkpoa::phase2::Blake2b h;
   HashStream hs(ctx, h, piece_points);
   std::vector<uint8_t> cap;
-  if (out_bytes) hs.capture = &cap;
-  hs.points(d.p, n, group, false);
+  if (out) hs.capture = &cap;
+  hs.points(d.p, n, group, false, compressed);
   h.final(digest);
-  if (out_bytes && n) memcpy(out_bytes, cap.data(), n * unit);
+  if (out && n) memcpy(out, cap.data(), cap.size());
+}
+extern "C" int zkpoa_hash_form(zkpoa_context* ctx, int group, const void* points, uint64_t n, uint64_t piece_points,
+                               void* out_bytes, uint8_t digest[64]) {
+  ZK_API_BEGIN(ctx)
+  points_form(ctx, group, points, n, piece_points, false, out_bytes, digest);
   ZK_API_END(ctx)
 }
 

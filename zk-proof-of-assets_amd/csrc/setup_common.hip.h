@@ -1,16 +1,20 @@
 // What the file commands of csrc/setup.hip (`zkey new`, `zkey contribute`, `wtns check`), csrc/zkey_verify.hip
-// (`zkey verify`), csrc/ptau_verify.hip (`powersoftau verify`) and csrc/ptau_prepare.hip (`powersoftau prepare phase2`)
-// share: mapped files and their section tables (the scan itself: binfile.hpp), the ptau header and the shape of its power
-// sections, output files that appear only when complete (AtomicFile), the ZKPOA_VERBOSE phase timer, host threads and
-// arrays, the r1cs parser and its CSR, the ptau ranges a key is made from, the constraint-fold kernels, and the device
-// passes that check the points of a section (curve, range, G2 subgroup). Internal linkage: each translation unit has
-// its own copy.
+// (`zkey verify`), csrc/ptau_verify.hip (`powersoftau verify`), csrc/ptau_prepare.hip (`powersoftau prepare phase2`) and
+// csrc/ptau_contribute.hip (`powersoftau new / contribute / beacon`) share: mapped files and their section tables (the
+// scan itself and the point sections of a ceremony file: binfile.hpp), the ptau header and the shape of its power
+// sections, the scalars a command draws or takes from the environment (scalar_in_range, random_scalar, env_scalars over
+// parse_u256.hpp), output files that appear only when complete (AtomicFile) and whose sections are placed in any order
+// (SectionFile), the ZKPOA_VERBOSE phase timer, host threads and arrays, the r1cs parser and its CSR, the ptau ranges a
+// key is made from, the constraint-fold kernels, the piece loop that streams a section from its file through HBM
+// (for_each_piece, piece_from_free_hbm), and the device passes that check the points of a section (curve, range, G2
+// subgroup: PointChecker). Internal linkage: each translation unit has its own copy.
 #pragma once
 #include "binfile.hpp"
 #include "bn254_ec.hip.h"
 #include "device_ctx.hpp"
 #include "msm.hip.h"
 #include "pairing.hpp"
+#include "parse_u256.hpp"
 #include "zkpoa_internal.hpp"
 
 #include <fcntl.h>
@@ -43,6 +47,10 @@ template <> Affine<HFq2> host_generator<HFq2>();   // hooks_g2.hip
 // setup.hip: the transcript checks of `zkey verify` (ZKPOA_ZKEY_CSHASH | ZKPOA_ZKEY_CONTRIBUTIONS) on a key whose circuit
 // hash is not zero; a malformed section 10 throws
 uint32_t phase2_verify(zkpoa_context* ctx, const char* r1cs_path, const char* ptau_path, const char* zkey_path);
+// setup.hip: the test hooks zkpoa_hash_form / zkpoa_compressed_form. The hash form (compressed: the compressed form) of n
+// points of group 1 / 2 (host, wire form) streamed in pieces of piece_points, its Blake2b-512 digest and, with out, the bytes
+void points_form(zkpoa_context* ctx, int group, const void* points, uint64_t n, uint64_t piece_points, bool compressed,
+                 void* out, uint8_t digest[64]);
 inline std::atomic<bool>& defer_host_frees() {   // one flag for all the units
   static std::atomic<bool> on{false};
   return on;
@@ -129,10 +137,8 @@ PtauShape ptau_power_sections(const MappedFile& fp, std::map<uint32_t, Sec>& ps)
   PtauShape s{0, 0, 0};
   s.power = ptau_header(fp, ps[1], &s.ceremony);
   if (s.power < 1 || s.power > 28) throw SetupError("ptau: power " + std::to_string(s.power) + " is outside [1, 28]");
-  const uint64_t N = 1ull << s.power;
-  const uint64_t want[8] = {0, 0, (2 * N - 1) * 64, N * 128, N * 64, N * 64, 128, 0};
-  for (uint32_t t = 2; t <= 6; t++)
-    if (ps[t].len != want[t]) throw SetupError("ptau: section " + std::to_string(t) + " has the wrong length for power " + std::to_string(s.power));
+  for (const PowerSec& sc : ptau_power_secs(s.power))
+    if (ps[sc.id].len != sc.bytes()) throw SetupError("ptau: section " + std::to_string(sc.id) + " has the wrong length for power " + std::to_string(s.power));
   if (ps[7].len < 4) throw SetupError("ptau: section 7 has the wrong length");
   s.contributions = rd32(fp.p + ps[7].off);
   return s;
@@ -144,6 +150,54 @@ void ptau_check_preparable(uint32_t power) {
 
 void urandom(void* dst, size_t len) {
   if (const char* err = read_urandom(dst, len)) throw SetupError(err);
+}
+
+// ---- scalars: 32 B little-endian, standard form ---------------------------------------------------------------------
+bool scalar_in_range(const uint8_t le[32], bool nonzero) {   // below r, and not zero when nonzero
+  uint64_t v[4];
+  memcpy(v, le, 32);
+  return !HFr::geq_p(v) && (!nonzero || (v[0] | v[1] | v[2] | v[3]));
+}
+void random_scalar(uint8_t d[32]) {   // uniform on [1, r): 254 random bits, rejected while >= r or zero
+  do {
+    urandom(d, 32);
+    d[31] &= 0x3f;
+  } while (!scalar_in_range(d, true));
+}
+// Tests / reproducible records only: `count` numbers in [1, r), decimal or 0x... hex, separated by commas, from the
+// environment variable `name`. False when it is not set; anything else than `shape` throws; a warning names `secrets`.
+bool env_scalars(const char* name, uint8_t out[][32], int count, const char* shape, const char* secrets) {
+  const char* e = getenv(name);
+  if (!e) return false;
+  for (int k = 0; k < count; k++) {
+    const char* end = strchr(e, ',');
+    if ((k < count - 1) != (end != nullptr)) end = nullptr;   // too few numbers, or too many
+    else if (!end) end = e + strlen(e);
+    if (!end || !parse_u256(e, end, out[k]) || !scalar_in_range(out[k], true)) throw SetupError(std::string(name) + " is not " + shape);
+    e = end + 1;
+  }
+  fprintf(stderr, "zkpoa: WARNING: %s taken from %s -- for tests only\n", secrets, name);
+  return true;
+}
+Fr fr_dev(const HFr& h) {   // a kernel argument: the same limbs
+  Fr f;
+  memcpy(&f, &h, 32);
+  return f;
+}
+ZK_DEV Fr fr_pow_u64(Fr b, uint64_t e) {
+  Fr r = Fr::one();
+  while (e) {
+    if (e & 1u) r = r * b;
+    b = b.sqr();
+    e >>= 1;
+  }
+  return r;
+}
+
+bool same_file(const char* a, const char* b) {
+  struct stat sa, sb;
+  if (stat(a, &sa) != 0 || stat(b, &sb) != 0) return false;
+  return sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino;
 }
 
 // The curve's b in the wire encoding (G1: 3, first 32 B; G2: 3 / (9 + u), 64 B), made on the host.
@@ -257,7 +311,34 @@ struct PointChecker {
     if (f & 1u) throw SetupError(std::string(what) + ": a coordinate is not a field element (>= q)");
     return f;
   }
+  // the same for a command that refuses the file: either bit throws
+  void require(const void* d, uint64_t count, int group, bool subgroup, const char* what) {
+    const uint32_t f = check(d, count, group, subgroup, what);
+    if (f & 2u) throw SetupError(std::string(what) + ": a point is not on the curve");
+    if (f & 4u) throw SetupError(std::string(what) + ": a point is outside G2");
+  }
 };
+
+// ---- a section streamed from its file through HBM ------------------------------------------------------------------------
+// `count` elements of `unit` bytes at file_offset of fd, at most `piece` of them at a time: each piece is uploaded to d_buf
+// (the context's pinned uploader, lane 0's stream), then fn(i0, cnt) runs. upload_ms: the host's time in the uploads.
+template <class Fn>
+void for_each_piece(zkpoa_context* ctx, int fd, uint64_t file_offset, uint64_t count, uint64_t unit, uint64_t piece,
+                    void* d_buf, Fn fn, double* upload_ms = nullptr) {
+  for (uint64_t i0 = 0; i0 < count; i0 += piece) {
+    const uint64_t cnt = std::min(piece, count - i0);
+    const auto t0 = std::chrono::steady_clock::now();
+    ctx->uploader.upload(d_buf, nullptr, cnt * unit, ctx->dev.device, ctx->dev.lanes[0].stream, fd, file_offset + i0 * unit);
+    if (upload_ms) *upload_ms += ms_since(t0);
+    fn(i0, cnt);
+  }
+}
+// points per piece when a quarter of the free HBM goes to the pieces' buffers, within [lo, hi]
+uint64_t piece_from_free_hbm(uint64_t bytes_per_point, uint64_t lo, uint64_t hi) {
+  size_t free_b = 0, total_b = 0;
+  ZK_HIP(hipMemGetInfo(&free_b, &total_b));
+  return std::max<uint64_t>(lo, std::min<uint64_t>(free_b / 4 / bytes_per_point, hi));
+}
 
 // ---- `snarkjs wtns check`: constraint c holds iff <A_c, w> * <B_c, w> == <C_c, w> ------------------------------------
 // row_ptr[3 * c + m .. +1): the terms of matrix m of constraint c; coefficients and witness in Montgomery form.
@@ -365,99 +446,86 @@ struct UVec {   // a sized array of trivially copyable elements whose storage is
 // exists" step to pick up, and writing over the input of `zkey contribute` is safe (the mapping keeps the old inode).
 struct AtomicFile {
   std::string path, tmp;
-  FILE* f = nullptr;
-  bool ok = true;
+  int fd = -1;
+  std::atomic<bool> ok{true};
   explicit AtomicFile(const char* final_path) : path(final_path), tmp(path + ".tmp." + std::to_string((long)getpid())) {
-    f = fopen(tmp.c_str(), "wb");
-    if (!f) throw SetupError("cannot create " + tmp);
-  }
-  void write(const void* p, size_t len) {
-    if (ok && len) ok = fwrite(p, 1, len, f) == len;
-  }
-  // a payload of GBs: the stream is flushed, the file extended, and the bytes are copied by several threads through a
-  // shared mapping of their final place (buffered write() calls to one file queue up behind its inode lock -- measured on
-  // tmpfs: eight pwrite threads were no faster than one fwrite); the stream then continues behind them
-  void write_large(const void* p, size_t len) {
-    if (len < (64u << 20)) return write(p, len);
-    if (!ok) return;
-    if (fflush(f) != 0) {
-      ok = false;
-      return;
-    }
-    const off_t base = ftello(f);
-    const int fd = fileno(f);
-    if (base < 0 || ftruncate(fd, base + (off_t)len) != 0) {
-      ok = false;
-      return;
-    }
-    const off_t map_off = base & ~(off_t)4095;
-    const size_t lead = (size_t)(base - map_off);
-    void* m = mmap(nullptr, lead + len, PROT_READ | PROT_WRITE, MAP_SHARED, fd, map_off);
-    if (m == MAP_FAILED) {   // a file system without shared mappings: the plain way
-      ok = fseeko(f, base, SEEK_SET) == 0;
-      return write(p, len);
-    }
-    char* dst = static_cast<char*>(m) + lead;
-    parallel_ranges(len, 32ull << 20, [&](unsigned, uint64_t lo, uint64_t hi) { memcpy(dst + lo, static_cast<const char*>(p) + lo, hi - lo); });
-    ok = munmap(m, lead + len) == 0 && fseeko(f, base + (off_t)len, SEEK_SET) == 0;
+    fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (fd < 0) throw SetupError("cannot create " + tmp);
   }
   // Absolute placement, for a file whose section offsets are known before their content: reserve() sizes it, put_at()
-  // may then be called from several threads for disjoint ranges in any order (small ranges: pwrite; large ones: the
-  // shared-mapping copy of write_large). The FILE stream is not used in this mode.
-  std::atomic<bool> placed_ok{true};
+  // may then be called from several threads for disjoint ranges in any order.
   void reserve(uint64_t total) {
-    if (fflush(f) != 0 || ftruncate(fileno(f), (off_t)total) != 0) ok = false;
+    if (ftruncate(fd, (off_t)total) != 0) ok = false;
   }
-  void put_at(uint64_t off, const void* p, uint64_t len) {
-    if (!len) return;
-    const int fd = fileno(f);
-    if (len < (64u << 20)) {
-      uint64_t done = 0;
-      while (done < len) {
-        const ssize_t w = pwrite(fd, static_cast<const char*>(p) + done, len - done, (off_t)(off + done));
-        if (w <= 0) {
-          placed_ok = false;
-          return;
-        }
-        done += (uint64_t)w;
-      }
-      return;
-    }
+  // a payload of GBs is copied by several threads through a shared mapping of its final place (buffered write() calls to
+  // one file queue up behind its inode lock -- measured on tmpfs: eight pwrite threads were no faster than one fwrite);
+  // false without a shared mapping of this file: the caller writes the plain way
+  bool mapped_copy(uint64_t off, const void* p, uint64_t len) {
     const uint64_t map_off = off & ~4095ull, lead = off - map_off;
     void* m = mmap(nullptr, lead + len, PROT_READ | PROT_WRITE, MAP_SHARED, fd, (off_t)map_off);
-    if (m == MAP_FAILED) {
-      uint64_t done = 0;
-      while (done < len) {
-        const ssize_t w = pwrite(fd, static_cast<const char*>(p) + done, len - done, (off_t)(off + done));
-        if (w <= 0) {
-          placed_ok = false;
-          return;
-        }
-        done += (uint64_t)w;
-      }
-      return;
-    }
+    if (m == MAP_FAILED) return false;
     char* dst = static_cast<char*>(m) + lead;
     parallel_ranges(len, 32ull << 20, [&](unsigned, uint64_t lo, uint64_t hi) { memcpy(dst + lo, static_cast<const char*>(p) + lo, hi - lo); });
-    if (munmap(m, lead + len) != 0) placed_ok = false;
+    if (munmap(m, lead + len) != 0) ok = false;
+    return true;
+  }
+  void put_at(uint64_t off, const void* p, uint64_t len) {
+    if (len >= (64u << 20) && mapped_copy(off, p, len)) return;
+    for (uint64_t done = 0; done < len;) {
+      const ssize_t w = pwrite(fd, static_cast<const char*>(p) + done, len - done, (off_t)(off + done));
+      if (w <= 0) {
+        ok = false;
+        return;
+      }
+      done += (uint64_t)w;
+    }
   }
   void commit() {
-    ok = ok && placed_ok.load();
-    ok = (fclose(f) == 0) && ok;
-    f = nullptr;
-    if (!ok || rename(tmp.c_str(), path.c_str()) != 0) {
+    const bool good = (close(fd) == 0) && ok.load();
+    fd = -1;
+    if (!good || rename(tmp.c_str(), path.c_str()) != 0) {
       unlink(tmp.c_str());
       throw SetupError("write to " + path + " failed");
     }
   }
   ~AtomicFile() {
-    if (f) {
-      fclose(f);
+    if (fd >= 0) {
+      close(fd);
       unlink(tmp.c_str());
     }
   }
   AtomicFile(const AtomicFile&) = delete;
   AtomicFile& operator=(const AtomicFile&) = delete;
+};
+// An iden3 binary file whose section lengths are known before their content: the file is sized, the magic, version 1,
+// the section count and the table (sections in the order of ids) are written, and a payload is then placed from any
+// thread, in any order.
+struct SectionFile {
+  AtomicFile file;
+  std::map<uint32_t, Sec> secs;   // where each payload goes
+  SectionFile(const char* path, const char* magic, const uint32_t* ids, const uint64_t* lens, uint32_t count) : file(path) {
+    uint64_t total = 12;
+    for (uint32_t i = 0; i < count; i++) {
+      secs[ids[i]] = Sec{total + 12, lens[i]};
+      total += 12 + lens[i];
+    }
+    file.reserve(total);
+    const uint32_t hdr[2] = {1, count};   // version, sections
+    file.put_at(0, magic, 4);
+    file.put_at(4, hdr, 8);
+    for (uint32_t i = 0; i < count; i++) {
+      file.put_at(off(ids[i]) - 12, &ids[i], 4);
+      file.put_at(off(ids[i]) - 8, &lens[i], 8);
+    }
+  }
+  uint64_t off(uint32_t id) const { return secs.at(id).off; }
+  uint64_t len(uint32_t id) const { return secs.at(id).len; }
+  void put(uint32_t id, const void* p, uint64_t n) {   // the whole section
+    if (n != len(id)) throw SetupError("internal: section " + std::to_string(id) + " has an unexpected size");
+    file.put_at(off(id), p, n);
+  }
+  void put_at(uint32_t id, uint64_t byte_offset, const void* p, uint64_t n) { file.put_at(off(id) + byte_offset, p, n); }
+  void commit() { file.commit(); }
 };
 
 // Untrusted inputs: the device keeps Fq elements lazily in [0, 2q) and takes file bytes raw, so every

@@ -22,6 +22,7 @@
 // is not exercised.
 #include "../../include/zkpoa_prover.h"
 
+#include "parse_u256.hpp"
 #include "worker_exit.hpp"
 
 #include <stdio.h>
@@ -39,27 +40,6 @@ static std::string ptau_record_lines(const char* path, uint32_t* count) {
   if (zkpoa_ptau_contributions(path, count, &text[0], (unsigned long)text.size()) != PROVER_OK) return std::string();
   text.resize(strlen(text.c_str()));
   return text;
-}
-
-static bool parse_decimal_or_hex(const char* s, uint8_t out[32]) {   // ZKPOA_DELTA: decimal, or 0x... hex; < 2^256
-  memset(out, 0, 32);
-  if (!s || !*s) return false;
-  const bool hex = s[0] == '0' && (s[1] == 'x' || s[1] == 'X');
-  for (const char* p = hex ? s + 2 : s; *p; p++) {
-    unsigned d;
-    if (*p >= '0' && *p <= '9') d = (unsigned)(*p - '0');
-    else if (hex && *p >= 'a' && *p <= 'f') d = (unsigned)(*p - 'a' + 10);
-    else if (hex && *p >= 'A' && *p <= 'F') d = (unsigned)(*p - 'A' + 10);
-    else return false;
-    unsigned carry = d;
-    for (int i = 0; i < 32; i++) {
-      unsigned v = out[i] * (hex ? 16u : 10u) + carry;
-      out[i] = (uint8_t)v;
-      carry = v >> 8;
-    }
-    if (carry) return false;
-  }
-  return true;
 }
 
 // `zkey verify`: true when the key's delta2 equals its gamma2 (the generator, which the HEADER check holds it to): no
@@ -91,41 +71,42 @@ static bool delta2_is_gamma2(const char* zkey_path) {
   return same;
 }
 
+// The commands: the words that select one (a row with no words left over: the three file arguments alone are `zkey new`),
+// its positional arguments, which of them names the file it writes (-1: none), whether it runs in a worker process
+// (csrc/worker_exit.hpp) and whether its last two positionals are a beacon's hex bytes and exponent.
+enum Cmd { kZkeyNew, kZkeyContribute, kZkeyBeacon, kZkeyVerify, kWtnsCheck, kPtauVerify, kPtauPrepare, kPtauNew, kPtauContribute, kPtauBeacon };
+struct Command {
+  Cmd cmd;
+  const char* words[3];
+  int npos, out_pos;
+  bool worker, beacon;
+};
+static const Command kCommands[] = {
+    {kZkeyBeacon, {"zkey", "beacon"}, 4, 1, true, true},
+    {kZkeyContribute, {"zkey", "contribute"}, 2, 1, true, false},
+    {kZkeyVerify, {"zkey", "verify"}, 3, -1, false, false},
+    {kPtauVerify, {"powersoftau", "verify"}, 1, -1, false, false},
+    {kPtauPrepare, {"powersoftau", "prepare", "phase2"}, 2, 1, false, false},
+    {kPtauNew, {"powersoftau", "new"}, 3, 2, false, false},
+    {kPtauContribute, {"powersoftau", "contribute"}, 2, 1, false, false},
+    {kPtauBeacon, {"powersoftau", "beacon"}, 4, 1, false, true},   // the same beacon arguments as `zkey beacon`
+    {kWtnsCheck, {"wtns", "check"}, 2, -1, false, false},
+    {kZkeyNew, {"zkey", "new"}, 3, 2, true, false},
+    {kZkeyNew, {"groth16", "setup"}, 3, 2, true, false},
+    {kZkeyNew, {}, 3, 2, true, false}};
+
 int main(int argc, char** argv) {
   int a = 1;
-  bool contribute = false, check = false, verify = false, pverify = false, beacon = false, prepare = false;
-  bool pnew = false, pcontribute = false, pbeacon = false;
-  if (argc - a >= 2 && !strcmp(argv[a], "zkey") && !strcmp(argv[a + 1], "beacon")) {
-    beacon = true;
-    a += 2;
-  } else if (argc - a >= 2 && !strcmp(argv[a], "zkey") && !strcmp(argv[a + 1], "contribute")) {
-    contribute = true;
-    a += 2;
-  } else if (argc - a >= 2 && !strcmp(argv[a], "zkey") && !strcmp(argv[a + 1], "verify")) {
-    verify = true;
-    a += 2;
-  } else if (argc - a >= 2 && !strcmp(argv[a], "powersoftau") && !strcmp(argv[a + 1], "verify")) {
-    pverify = true;
-    a += 2;
-  } else if (argc - a >= 3 && !strcmp(argv[a], "powersoftau") && !strcmp(argv[a + 1], "prepare") && !strcmp(argv[a + 2], "phase2")) {
-    prepare = true;
-    a += 3;
-  } else if (argc - a >= 2 && !strcmp(argv[a], "powersoftau") && !strcmp(argv[a + 1], "new")) {
-    pnew = true;
-    a += 2;
-  } else if (argc - a >= 2 && !strcmp(argv[a], "powersoftau") && !strcmp(argv[a + 1], "contribute")) {
-    pcontribute = true;
-    a += 2;
-  } else if (argc - a >= 2 && !strcmp(argv[a], "powersoftau") && !strcmp(argv[a + 1], "beacon")) {
-    pbeacon = beacon = true;   // the same beacon arguments as `zkey beacon`
-    a += 2;
-  } else if (argc - a >= 2 && !strcmp(argv[a], "wtns") && !strcmp(argv[a + 1], "check")) {
-    check = true;
-    a += 2;
-  } else if (argc - a >= 2 && ((!strcmp(argv[a], "zkey") && !strcmp(argv[a + 1], "new")) ||
-                               (!strcmp(argv[a], "groth16") && !strcmp(argv[a + 1], "setup")))) {
-    a += 2;
+  const Command* c = kCommands;
+  for (;; c++) {
+    int w = 0;
+    while (w < 3 && c->words[w] && a + w < argc && !strcmp(argv[a + w], c->words[w])) w++;
+    if (w == 3 || !c->words[w]) {   // every word of the row matched
+      a += w;
+      break;
+    }
   }
+  const Cmd cmd = c->cmd;
   // snarkjs' options: --name=... / -n=... goes into the contribution record when the key carries a transcript; the
   // others (-e=..., -v) are accepted and ignored: the entropy text only feeds snarkjs' own random generator, the secret
   // here comes from /dev/urandom (or ZKPOA_DELTA). --transcript (`zkey new`) is this tool's own.
@@ -143,7 +124,7 @@ int main(int argc, char** argv) {
     if (npos < 4) pos[npos] = argv[i];
     npos++;
   }
-  if (npos != (pverify ? 1 : (beacon ? 4 : (contribute || check || prepare || pcontribute ? 2 : 3)))) {
+  if (npos != c->npos) {
     fprintf(stderr, "usage: zkpoa-setup [zkey new | groth16 setup] <circuit.r1cs> <pot.ptau> <circuit_0.zkey>\n"
                     "         [--transcript]   fill in section 10's circuit hash (needs the ptau's section 2)\n"
                     "       zkpoa-setup zkey contribute <in.zkey> <out.zkey> [--name=...] [-e=...]\n"
@@ -159,7 +140,7 @@ int main(int argc, char** argv) {
     return 2;
   }
   unsigned new_power = 0;
-  if (pnew) {
+  if (cmd == kPtauNew) {
     char* end = nullptr;
     const long v = strtol(pos[1], &end, 10);
     if ((strcmp(pos[0], "bn128") && strcmp(pos[0], "bn254")) || end == pos[1] || *end || v < 1 || v > 28) {
@@ -170,8 +151,8 @@ int main(int argc, char** argv) {
   }
   uint8_t delta[32];
   const uint8_t* delta_p = nullptr;
-  if (contribute && getenv("ZKPOA_DELTA")) {   // tests / reproducible keys only: the secret must not be kept
-    if (!parse_decimal_or_hex(getenv("ZKPOA_DELTA"), delta)) {
+  if (const char* e = cmd == kZkeyContribute ? getenv("ZKPOA_DELTA") : nullptr) {   // tests / reproducible keys only: the secret must not be kept
+    if (!zkpoa::parse_u256(e, e + strlen(e), delta)) {
       fprintf(stderr, "zkpoa-setup: ZKPOA_DELTA is not a number below 2^256\n");
       return 2;
     }
@@ -186,7 +167,7 @@ int main(int argc, char** argv) {
   uint8_t beacon_bytes[255];
   unsigned long beacon_len = 0;
   unsigned beacon_exp = 0;
-  if (beacon) {
+  if (c->beacon) {
     const char* h = pos[2];
     if (h[0] == '0' && (h[1] == 'x' || h[1] == 'X')) h += 2;
     const size_t hl = strlen(h);
@@ -200,7 +181,7 @@ int main(int argc, char** argv) {
     char* end = nullptr;
     const long e = strtol(pos[3], &end, 10);
     if (!ok || end == pos[3] || *end || e < 0 || e > 30) {
-      fprintf(stderr, "zkpoa-setup: %s beacon: the beacon must be 1-255 bytes of hex and numIterationsExp in [0, 30]\n", pbeacon ? "powersoftau" : "zkey");
+      fprintf(stderr, "zkpoa-setup: %s beacon: the beacon must be 1-255 bytes of hex and numIterationsExp in [0, 30]\n", cmd == kPtauBeacon ? "powersoftau" : "zkey");
       return 2;
     }
     beacon_len = hl / 2;
@@ -208,13 +189,12 @@ int main(int argc, char** argv) {
   }
   // does the input of `zkey contribute` carry a transcript? (host only; an unreadable file is reported by the command)
   bool in_transcript = false;
-  if (contribute) {
+  if (cmd == kZkeyContribute) {
     int has = 0;
     uint32_t cnt = 0;
     if (zkpoa_zkey_contributions(pos[0], &has, &cnt, nullptr, 0) == PROVER_OK) in_transcript = has != 0;
   }
-  const bool ptau_make = pnew || pcontribute || pbeacon;   // these run in this process, as `powersoftau prepare phase2`
-  zkpoa::WorkerExit we = zkpoa::WorkerExit::start(!check && !verify && !pverify && !prepare && !ptau_make, "zkpoa-setup");
+  zkpoa::WorkerExit we = zkpoa::WorkerExit::start(c->worker, "zkpoa-setup");
   if (we.is_worker()) zkpoa_setup_defer_host_frees(1);
   auto leave = [&](int code) -> int {
     if (we.is_worker()) we.leave(code);
@@ -229,7 +209,7 @@ int main(int argc, char** argv) {
     return leave(1);
   }
   int rc;
-  if (check) {   // snarkjs prints "WITNESS IS CORRECT" and exits 0, or names the failure and exits 1
+  if (cmd == kWtnsCheck) {   // snarkjs prints "WITNESS IS CORRECT" and exits 0, or names the failure and exits 1
     uint64_t bad = 0, first = 0;
     rc = zkpoa_wtns_check(ctx, pos[0], pos[1], &bad, &first);
     if (rc == PROVER_OK && bad == 0) printf("[INFO]  zkpoa: WITNESS IS CORRECT\n");
@@ -239,7 +219,7 @@ int main(int argc, char** argv) {
       zkpoa_context_destroy(ctx);
       return 1;
     }
-  } else if (verify) {   // snarkjs prints "ZKey Ok!" and exits 0, or names what does not match and exits 1
+  } else if (cmd == kZkeyVerify) {   // snarkjs prints "ZKey Ok!" and exits 0, or names what does not match and exits 1
     uint32_t failed = 0;
     rc = zkpoa_zkey_verify(ctx, pos[0], pos[1], pos[2], &failed);
     if (rc == PROVER_OK) {
@@ -277,7 +257,7 @@ int main(int argc, char** argv) {
       }
       printf("[INFO]  zkpoa: ZKey Ok!\n");
     }
-  } else if (pverify) {   // snarkjs prints "Powers of Tau Ok!" and exits 0, or names what does not hold and exits 1
+  } else if (cmd == kPtauVerify) {   // snarkjs prints "Powers of Tau Ok!" and exits 0, or names what does not hold and exits 1
     uint32_t failed = 0, info[4] = {0, 0, 0, 0};
     rc = zkpoa_ptau_verify(ctx, pos[0], 0, &failed, info);
     if (rc == PROVER_OK) {
@@ -311,15 +291,15 @@ int main(int argc, char** argv) {
         printf("[INFO]  zkpoa: contribution #%u: %s\n", k, line);
       printf("[INFO]  zkpoa: Powers of Tau Ok!\n");
     }
-  } else if (prepare) {   // snarkjs logs its progress and exits 0, or names what is wrong with the file and exits 1
+  } else if (cmd == kPtauPrepare) {   // snarkjs logs its progress and exits 0, or names what is wrong with the file and exits 1
     uint32_t info[4] = {0, 0, 0, 0};
     rc = zkpoa_ptau_prepare_phase2(ctx, pos[0], pos[1], info);
     if (rc == PROVER_OK) printf("[INFO]  zkpoa: Prepared phase 2\n");
-  } else if (pnew) {
+  } else if (cmd == kPtauNew) {
     rc = zkpoa_ptau_new(ctx, new_power, pos[2]);
     if (rc == PROVER_OK) printf("[INFO]  zkpoa: new ceremony file of power %u\n", new_power);
-  } else if (pcontribute || pbeacon) {
-    if (pbeacon) rc = zkpoa_ptau_beacon(ctx, pos[0], pos[1], beacon_bytes, beacon_len, beacon_exp, name);
+  } else if (cmd == kPtauContribute || cmd == kPtauBeacon) {
+    if (cmd == kPtauBeacon) rc = zkpoa_ptau_beacon(ctx, pos[0], pos[1], beacon_bytes, beacon_len, beacon_exp, name);
     else rc = zkpoa_ptau_contribute(ctx, pos[0], pos[1], nullptr, name);
     if (rc == PROVER_OK) {
       uint32_t n_records = 0;
@@ -329,16 +309,16 @@ int main(int argc, char** argv) {
       printf("[INFO]  zkpoa: contribution #%u: %s", n_records, records.empty() ? "\n" : records.c_str() + last);
     }
   } else {
-    if (beacon) rc = zkpoa_zkey_beacon(ctx, pos[0], pos[1], beacon_bytes, beacon_len, beacon_exp, name);
-    else if (contribute && in_transcript) rc = zkpoa_zkey_contribute_ex(ctx, pos[0], pos[1], delta_p, name);
-    else if (contribute) rc = zkpoa_zkey_contribute(ctx, pos[0], pos[1], delta_p);
+    if (cmd == kZkeyBeacon) rc = zkpoa_zkey_beacon(ctx, pos[0], pos[1], beacon_bytes, beacon_len, beacon_exp, name);
+    else if (cmd == kZkeyContribute && in_transcript) rc = zkpoa_zkey_contribute_ex(ctx, pos[0], pos[1], delta_p, name);
+    else if (cmd == kZkeyContribute) rc = zkpoa_zkey_contribute(ctx, pos[0], pos[1], delta_p);
     else rc = zkpoa_zkey_new_ex(ctx, pos[0], pos[1], pos[2], transcript ? ZKPOA_SETUP_TRANSCRIPT : 0u);
   }
   if (rc != PROVER_OK) fprintf(stderr, "zkpoa-setup: %s\n", zkpoa_last_error(ctx));
   if (!we.is_worker()) zkpoa_context_destroy(ctx);
   clock_gettime(CLOCK_MONOTONIC, &t1);
-  if (rc == PROVER_OK && getenv("ZKPOA_VERBOSE") && !check && !verify && !pverify)
-    fprintf(stderr, "zkpoa-setup: %s written in %.2f s\n", pos[contribute || beacon || prepare || pcontribute ? 1 : 2],
+  if (rc == PROVER_OK && getenv("ZKPOA_VERBOSE") && c->out_pos >= 0)
+    fprintf(stderr, "zkpoa-setup: %s written in %.2f s\n", pos[c->out_pos],
             (t1.tv_sec - t0.tv_sec) + (t1.tv_nsec - t0.tv_nsec) / 1e9);
   return leave(rc == PROVER_OK ? 0 : 1);
 }
