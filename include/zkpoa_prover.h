@@ -613,6 +613,11 @@ int zkpoa_curve_prim(zkpoa_context* ctx, int group, int op, const void* a, const
  * batch vectors of 2^log_n elements start stride elements apart (stride >= 2^log_n); elements between them are not
  * touched. data holds ((batch - 1) * stride + 2^log_n) * 32 bytes. */
 int zkpoa_ntt_form(zkpoa_context* ctx, void* data, unsigned log_n, int form, int inverse, unsigned batch, uint64_t stride);
+/* The NTT's pass plan for 2^log_n elements (test hook; needs no context, no GPU and reads no environment variable).
+ * tile_log: 0 = the tile size that log_n takes by default, 10 or 11 = that tile. Writes seven words per pass, in DIT
+ * order: s_lo, B, logT, grid.x, threads, dynamic LDS bytes, direct boundary table 0 / 1; passes that do not fit in cap
+ * words are left out. Returns the pass count, or -1 for log_n > 28 or any other tile_log. */
+int zkpoa_test_ntt_plan(unsigned log_n, unsigned tile_log, uint32_t* out, unsigned cap);
 
 #ifdef __cplusplus
 }

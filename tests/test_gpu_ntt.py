@@ -1,4 +1,4 @@
-"""The Fr NTT (csrc/ntt.hip.h) at every pass plan, form, radix and tile size, bit for bit against the C oracle.
+"""The Fr NTT (csrc/ntt.hip.h) at every pass plan, form and tile size, bit for bit against the C oracle.
 
 zkpoa_ntt reaches the natural-order form only (DIF passes, the last one storing at the bit-reversed position);
 zkpoa_ntt_form reaches the three the prover and the split chain run: plain DIF, plain DIT and the coset chain
@@ -183,7 +183,7 @@ def test_coset_form(ctx, k):
         _check_strided(got, wants, n, stride, "to_odd_coset k=%d stride=n+%d" % (k, stride - n))
 
 
-# ---- the forced tile size and radix (read once per process) --------------------------------------------------
+# ---- the forced tile size (read once per process) ------------------------------------------------------------
 _CHILD_NATURAL = (1, 2, 3, 10, 11, 12, 15, 19, 20)
 _CHILD_COSET = (11, 12, 20)
 _CHILD = """
@@ -208,12 +208,11 @@ c.close()
 """ % (_CHILD_NATURAL, _CHILD_COSET)
 
 
-def test_forced_tile_and_radix_in_children(ctx, tmp_path):
+def test_forced_tile_in_a_child(ctx, tmp_path):
     """ZKPOA_NTT_TILE=10 (the 1024-element tile plan that k >= 23 takes by default: here k = 11 is a B = 1 second pass,
-    k = 19 the 2-column pass, k = 20 the three-pass 10 + 5 + 5 plan of 2^26), ZKPOA_NTT_RADIX=2 (the one-stage-per-
-    barrier instantiations) and both together. Each is read once per process: a fresh child per setting, under a time
-    limit of its own, its exit status checked before the next starts. Its outputs equal the oracle's and, bit for
-    bit, the default path's in this process."""
+    k = 19 the 2-column pass, k = 20 the three-pass 10 + 5 + 5 plan of 2^26). It is read once per process: a fresh
+    child, under a time limit of its own, its exit status checked. Its outputs equal the oracle's and, bit for bit,
+    the default path's in this process."""
     want = {}
     for k in _CHILD_NATURAL:
         (tmp_path / ("x%d" % k)).write_bytes(_x(k))
@@ -225,8 +224,7 @@ def test_forced_tile_and_radix_in_children(ctx, tmp_path):
         (tmp_path / ("b%d" % k)).write_bytes(b"".join(vecs))
         want["c%d" % k] = b"".join(wants)
         _same(ctx.ntt_form(b"".join(vecs), k, 2, batch=3), want["c%d" % k], "default path k=%d to_odd_coset" % k)
-    for tag, env in (("tile10", {"ZKPOA_NTT_TILE": "10"}), ("radix2", {"ZKPOA_NTT_RADIX": "2"}),
-                     ("tile10_radix2", {"ZKPOA_NTT_TILE": "10", "ZKPOA_NTT_RADIX": "2"})):
+    for tag, env in (("tile10", {"ZKPOA_NTT_TILE": "10"}),):
         out = tmp_path / tag
         out.mkdir()
         rc = subprocess.run(["timeout", "-k", "10", "120", sys.executable, "-s", "-c", _CHILD, ROOT, str(tmp_path), str(out)],

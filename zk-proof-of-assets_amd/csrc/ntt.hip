@@ -9,37 +9,29 @@ static NttEngine* engine(zkpoa_context* ctx) {
   return ctx->ntt;
 }
 
+void ntt_prepare(zkpoa_context* ctx, hipStream_t st, uint32_t k) { (void)engine(ctx)->size(st, k); }
 void ntt_to_odd_coset(zkpoa_context* ctx, hipStream_t st, void* d_data, uint32_t k, uint32_t batch, size_t stride) {
   engine(ctx)->to_odd_coset(st, d_data, k, batch, stride);
 }
 void ntt_natural(zkpoa_context* ctx, hipStream_t st, void* d_data, uint32_t k, bool inverse) {
-  engine(ctx)->transform_natural(st, d_data, k, inverse);
-}
-void ntt_prepare(zkpoa_context* ctx, hipStream_t st, uint32_t k) {
-  if (k == 0) return;
   NttEngine* e = engine(ctx);
-  (void)e->tables(st, k, false);
-  (void)e->tables(st, k, true);
-  HFr inc = (k == 28) ? HFr::from_u64(25) : hfr_root_of_unity(k + 1);
-  HFr ninv = HFr::from_u64(1ull << k).inv();
-  (void)e->pow_tables(st, k, inc, ninv, k);
+  e->run(st, e->size(st, k), kNttNatural, inverse, d_data);
 }
 void ntt_dif(zkpoa_context* ctx, hipStream_t st, void* d_data, uint32_t k, bool inverse, uint32_t batch, size_t stride) {
-  engine(ctx)->dif(st, d_data, k, inverse, batch, stride);
+  NttEngine* e = engine(ctx);
+  e->run(st, e->size(st, k), kNttDif, inverse, d_data, batch, stride);
 }
 void ntt_dit(zkpoa_context* ctx, hipStream_t st, void* d_data, uint32_t k, bool inverse, uint32_t batch, size_t stride) {
-  engine(ctx)->dit(st, d_data, k, inverse, batch, stride);
+  NttEngine* e = engine(ctx);
+  e->run(st, e->size(st, k), kNttDit, inverse, d_data, batch, stride);
 }
 void ntt_split_mid(zkpoa_context* ctx, hipStream_t st, const void* in, void* out, uint32_t k, uint32_t G, uint32_t h,
                    uint32_t rank_stride) {
   engine(ctx)->split_mid(st, in, out, k, G, h, rank_stride);
 }
-void ntt_release(zkpoa_context* ctx) {
-  if (ctx->ntt) {
-    ctx->ntt->release();
-    delete ctx->ntt;
-    ctx->ntt = nullptr;
-  }
+void ntt_release(zkpoa_context* ctx) {   // the engine's members free their device memory
+  delete ctx->ntt;
+  ctx->ntt = nullptr;
 }
 
 }  // namespace zkpoa
@@ -71,7 +63,7 @@ extern "C" int zkpoa_ntt(zkpoa_context* ctx, void* data, unsigned log_n, int inv
   ZK_API_END(ctx)
 }
 
-// The forms the prover and the split chain run (zkpoa_ntt reaches transform_natural only), on a host buffer.
+// The forms the prover and the split chain run (zkpoa_ntt reaches the natural-order form only), on a host buffer.
 extern "C" int zkpoa_ntt_form(zkpoa_context* ctx, void* data, unsigned log_n, int form, int inverse, unsigned batch,
                               uint64_t stride) {
   ZK_API_BEGIN(ctx)
@@ -92,4 +84,18 @@ extern "C" int zkpoa_ntt_form(zkpoa_context* ctx, void* data, unsigned log_n, in
   ZK_HIP(hipGetLastError());
   ZK_HIP(hipMemcpy(data, d.p, bytes, hipMemcpyDeviceToHost));
   ZK_API_END(ctx)
+}
+
+// Test hook, no context and no GPU: the pass plan of a size-2^log_n transform, seven words per pass (s_lo, B, logT,
+// grid.x, threads, dynamic LDS bytes, direct table 0/1). tile_log 0 = the tile the size takes by default, 10 / 11 = that
+// tile. Returns the pass count (the first `cap` words' worth are written), -1 for arguments out of range.
+extern "C" int zkpoa_test_ntt_plan(unsigned log_n, unsigned tile_log, uint32_t* out, unsigned cap) {
+  if (log_n > 28 || (tile_log != 0 && tile_log != 10 && tile_log != 11)) return -1;
+  const auto plan = ntt_plan(log_n, tile_log ? tile_log : ntt_tile_log_by_size(log_n));
+  for (size_t i = 0; i < plan.size() && 7 * (i + 1) <= cap; i++) {
+    const NttPass& ps = plan[i];
+    const uint32_t w[7] = {ps.s_lo, ps.B, ps.logT, ps.grid, ps.threads, ps.lds_bytes, ps.direct ? 1u : 0u};
+    memcpy(out + 7 * i, w, sizeof w);
+  }
+  return (int)plan.size();
 }

@@ -5,8 +5,8 @@
 // transforms per proof, w = w[log2 n] (5^((r-1)/2^28) squared down), elements in Montgomery form.
 //
 // Structure: the log2(n) butterfly stages are cut into passes of B <= 11 consecutive stages.
-// One workgroup stages a tile of 2^B rows x T columns (2048 elements, 64 KiB) in LDS, runs the
-// B stages there with one barrier per stage, and writes the tile back: every pass reads and
+// One workgroup stages a tile of 2^B rows x T columns (2048 elements, 64 KiB; 1024 from 2^23 up) in LDS, runs
+// the B stages there, two per barrier, and writes the tile back: every pass reads and
 // writes each element once (HBM-bound part), all butterflies run out of LDS.
 //   * DIF (Gentleman-Sande) passes go from the top stage down: natural order in, bit-reversed out.
 //   * DIT (Cooley-Tukey) passes go from stage 0 up: bit-reversed in, natural order out.
@@ -19,17 +19,16 @@
 // Boundary twiddles of a pass whose table fits the cache (2^21 entries) are read as ONE value per element.
 #pragma once
 #include "bn254_field.hip.h"
-#include "device_ctx.hpp"
 #include "host_field.hpp"
+#include "zkpoa_internal.hpp"
 
-#include <map>
+#include <deque>
+#include <memory>
 #include <vector>
 
 namespace zkpoa {
 
-constexpr uint32_t kNttTileLog = 11;  // 2048 elements = 64 KiB of LDS per workgroup
-constexpr uint32_t kNttStridedB = 8;  // rows per tile in strided passes (x 8 columns)
-constexpr uint32_t kNttMaxStridedB = 10;  // a single strided pass may take up to 10 stages (x 2 columns)
+constexpr uint32_t kNttStridedB = 8;  // at most 2^8 rows per tile where the strided stages take several passes
 constexpr uint32_t kNttDirectMaxLog = 21;  // boundary twiddles as one table up to 2^21 entries (64 MiB, cache-resident)
 // threads per 2048-element tile: 8 waves share the 64 KiB tile, so with 2 tiles per CU every SIMD has 4 waves
 // to cover the multiply latency and the per-stage barriers (measured at 2^26: 256 threads +10 %, 1024 +10 %)
@@ -89,15 +88,26 @@ static __global__ __launch_bounds__(256) void ntt_direct_table_kernel(void* __re
   store_field(reinterpret_cast<char*>(out) + 32 * (size_t)i, tw_lookup(hi, lo, L, (col * r) << shift));
 }
 
+// v times the four-step twiddle W^((col * r) << shift) of tile row m (r = bitrev_B(m)) and column `col` of a pass over
+// stages [s_lo, s_lo + B): one value from the pass's direct table where it has one, else hi * lo. DIT passes apply it as
+// they load, DIF passes as they store.
+ZK_DEV Fr times_boundary_twiddle(const Fr& v, const void* __restrict__ direct, const void* __restrict__ hi,
+                                 const void* __restrict__ lo, uint32_t L, uint32_t s_lo, uint32_t B, uint32_t shift,
+                                 uint32_t m, uint32_t col) {
+  const uint32_t r = __brev(m) >> (32u - B);
+  if (direct) return v * load_field<Fr>(reinterpret_cast<const char*>(direct) + 32 * (((size_t)r << s_lo) + col));
+  return v * tw_lookup(hi, lo, L, (col * r) << shift);
+}
+
 // One pass over stages [s_lo, s_lo + B). Tile: 2^B rows (stride 2^s_lo elements) x 2^logT columns
 // (consecutive elements); requires logT <= s_lo. grid.x = n / 2^(B+logT). tw_direct (optional): the boundary
 // twiddles of this pass as one table (a single multiplication per element instead of hi * lo and then the product).
 // blockIdx.y = which of `batch` equally sized vectors, `batch_stride` bytes apart (the prover transforms A, B and C
 // of a proof together: a third of the launches, three times the workgroups per launch, one set of twiddle tables).
-// R4: two butterfly stages per barrier -- every thread takes the four rows of a radix-4 group through both stages in
+// Two butterfly stages per barrier: every thread takes the four rows of a radix-4 group through both stages in
 // registers (half the LDS round trips and barriers; the multiplication count is unchanged: in a prime field the
-// "free" rotation by i of a complex radix-4 butterfly is an ordinary product).
-template <bool DIF, int MODE, bool R4>
+// "free" rotation by i of a complex radix-4 butterfly is an ordinary product). An odd B ends with one radix-2 stage.
+template <bool DIF, int MODE>
 static __global__ __launch_bounds__(kNttThreads) void ntt_pass_kernel(const void* src, void* dst, size_t batch_stride,
                                                               uint32_t k, uint32_t s_lo,
                                                               uint32_t B, uint32_t logT,
@@ -121,11 +131,7 @@ static __global__ __launch_bounds__(kNttThreads) void ntt_pass_kernel(const void
     uint32_t c = e & (T - 1u), m = e >> logT;
     uint64_t p = base + ((uint64_t)m << s_lo) + c;
     Fr v = load_field<Fr>(sp + 32 * p);
-    if (!DIF && s_lo > 0) {
-      uint32_t r = __brev(m) >> (32u - B);
-      if (tw_direct) v = v * load_field<Fr>(reinterpret_cast<const char*>(tw_direct) + 32 * (((size_t)r << s_lo) + cg * T + c));
-      else v = v * tw_lookup(tw_hi, tw_lo, L, ((cg * T + c) * r) << shift);
-    }
+    if (!DIF && s_lo > 0) v = times_boundary_twiddle(v, tw_direct, tw_hi, tw_lo, L, s_lo, B, shift, m, cg * T + c);
     if (MODE == kPassPreScale) v = v * tw_lookup(sc_hi, sc_lo, Lc, __brev((uint32_t)p) >> (32u - k));
     lds_store(lds, tile, e, v);
   }
@@ -134,7 +140,7 @@ static __global__ __launch_bounds__(kNttThreads) void ntt_pass_kernel(const void
   const char* stw = reinterpret_cast<const char*>(small_tw);
   uint32_t it = 0;
   while (it < B) {
-    if (R4 && B - it >= 2u) {
+    if (B - it >= 2u) {
       // stages (sl, sl + 1), sl = the lower one: rows m0 + {0, h, 2h, 3h}, h = 2^sl, j = m0 mod h.
       // twiddles: t1 = W_{2h}^j (stage sl, both pairs), t2 = W_{4h}^j and t3 = W_{4h}^(j + h) (stage sl + 1)
       const uint32_t sl = DIF ? (B - 2u - it) : it;
@@ -211,11 +217,7 @@ static __global__ __launch_bounds__(kNttThreads) void ntt_pass_kernel(const void
     uint32_t c = e & (T - 1u), m = e >> logT;
     uint64_t p = base + ((uint64_t)m << s_lo) + c;
     Fr v = lds_load(lds, tile, e);
-    if (DIF && s_lo > 0) {
-      uint32_t r = __brev(m) >> (32u - B);
-      if (tw_direct) v = v * load_field<Fr>(reinterpret_cast<const char*>(tw_direct) + 32 * (((size_t)r << s_lo) + cg * T + c));
-      else v = v * tw_lookup(tw_hi, tw_lo, L, ((cg * T + c) * r) << shift);
-    }
+    if (DIF && s_lo > 0) v = times_boundary_twiddle(v, tw_direct, tw_hi, tw_lo, L, s_lo, B, shift, m, cg * T + c);
     if (MODE == kPassBitrevOut) {
       // the images of different tiles interleave: with more than one tile, dst must not be the buffer being read
       v = v * post;
@@ -291,46 +293,54 @@ static __global__ __launch_bounds__(256) void ntt_split_mid_kernel(const void* _
 }
 
 // ---- host side ---------------------------------------------------------------------------------
-struct NttPassDesc {
-  uint32_t s_lo, B, logT;
+// One pass, complete: its stages, its tile and its launch geometry.
+struct NttPass {
+  uint32_t s_lo, B, logT;   // stages [s_lo, s_lo + B); tile = 2^B rows x 2^logT columns
+  uint32_t grid;            // grid.x = n / tile
+  uint32_t threads;         // a quarter of the tile (one radix-4 group per thread and stage pair), 64 .. kNttThreads
+  uint32_t lds_bytes;       // 32 B per tile element
+  bool direct;              // its boundary twiddles fit one table: s_lo > 0 && s_lo + B <= kNttDirectMaxLog
 };
 
-// passes in DIT order (stage 0 upwards); DIF runs them in reverse
 // Tile size of a transform: 2048 elements (64 KiB: two workgroups of 512 threads per CU) up to 2^22, where it makes
 // the transform two passes; above that 1024 elements (32 KiB: FOUR workgroups of 256 threads per CU). The pass count
 // is the same there (2^26 = 10 + 8 + 8 stages instead of 11 + 8 + 7), and a workgroup's load -> butterflies -> store
 // phases do not overlap with each other, only with the other workgroups of the CU: four of them out of step keep the
-// multipliers busy while one loads or stores. ZKPOA_NTT_TILE=10|11 forces either (measurement).
+// multipliers busy while one loads or stores.
+constexpr uint32_t ntt_tile_log_by_size(uint32_t k) { return k >= 23 ? 10u : 11u; }
+// ZKPOA_NTT_TILE=10|11 forces either (measurement, and the tests' way to the large-size plan at a small k)
 inline uint32_t ntt_tile_log(uint32_t k) {
   static const int forced = [] {
     const char* e = getenv("ZKPOA_NTT_TILE");
     return e ? atoi(e) : 0;
   }();
-  if (forced == 10 || forced == 11) return (uint32_t)forced;
-  return k >= 23 ? 10u : 11u;
+  return forced == 10 || forced == 11 ? (uint32_t)forced : ntt_tile_log_by_size(k);
 }
 
-inline std::vector<NttPassDesc> ntt_plan(uint32_t k) {
-  std::vector<NttPassDesc> v;
+// The passes of a size-2^k transform on tiles of 2^tile_log elements, in DIT order (stage 0 upwards; DIF runs them in
+// reverse). A function of its two arguments alone.
+inline std::vector<NttPass> ntt_plan(uint32_t k, uint32_t tile_log) {
+  std::vector<NttPass> v;
+  auto add = [&](uint32_t s_lo, uint32_t B, uint32_t logT) {
+    const uint32_t t = B + logT;
+    v.push_back({s_lo, B, logT, 1u << (k - t), t >= 8 ? (t >= 11 ? kNttThreads : 1u << (t - 2)) : 64u, 32u << t,
+                 s_lo > 0 && s_lo + B <= kNttDirectMaxLog});
+  };
   if (k == 0) return v;
-  const uint32_t kNttTileLog = ntt_tile_log(k);   // shadows the constant: everything below is per transform size
-  const uint32_t kNttMaxStridedB = kNttTileLog - 1;
-  uint32_t b0 = k < kNttTileLog ? k : kNttTileLog;
-  v.push_back({0, b0, 0});
-  uint32_t rest = k - b0;
-  if (rest && rest <= kNttMaxStridedB) {
-    // one strided pass of `rest` stages: tile = 2^rest rows x 2^(11 - rest) columns (>= 64-B row segments).
+  const uint32_t b0 = k < tile_log ? k : tile_log, rest = k - b0;
+  add(0, b0, 0);
+  if (rest && rest < tile_log) {
+    // one strided pass of `rest` stages: tile = 2^rest rows x 2^(tile_log - rest) columns (>= 64-B row segments).
     // Fewer columns coalesce less well, but a whole pass (64 B/element of traffic + one boundary twiddle,
     // 2 modmuls/element) disappears; these sizes (n <= 2^21) also sit in the Infinity Cache.
-    v.push_back({b0, rest, kNttTileLog - rest});
+    add(b0, rest, tile_log - rest);
   } else if (rest) {
-    uint32_t npass = (rest + kNttStridedB - 1) / kNttStridedB;
-    uint32_t s = b0;
-    for (uint32_t i = 0; i < npass; i++) {
-      uint32_t b = rest / npass + (i < rest % npass ? 1 : 0);
-      // always a full 2048-element tile: fewer rows = more columns (r02 kept 8 columns, so a 5- or 6-stage pass ran
-      // on 256- or 512-element tiles with most of the workgroup idle: 2^22 and 2^24 were off the curve)
-      v.push_back({s, b, kNttTileLog - b});
+    const uint32_t npass = (rest + kNttStridedB - 1) / kNttStridedB;
+    for (uint32_t i = 0, s = b0; i < npass; i++) {
+      const uint32_t b = rest / npass + (i < rest % npass ? 1 : 0);
+      // always a full tile: fewer rows = more columns (r02 kept 8 columns, so a 5- or 6-stage pass ran on 256- or
+      // 512-element tiles with most of the workgroup idle: 2^22 and 2^24 were off the curve)
+      add(s, b, tile_log - b);
       s += b;
     }
   }
@@ -346,13 +356,19 @@ inline HFr hfr_root_of_unity(uint32_t k) {  // w[k], Montgomery
   return w;
 }
 
-struct NttTables {  // device tables for one (k, direction)
-  uint32_t k = 0, L = 0;
-  void* hi = nullptr;                 // W^(i * 2^L), i < 2^(k-L)
-  void* lo = nullptr;                 // W^i, i < 2^L
-  std::map<uint32_t, void*> small;    // B -> W_{2^B}^t, t < 2^(B-1)
-  std::map<uint32_t, void*> direct;   // s_lo -> boundary twiddles of the strided pass starting there (when small enough)
+inline HFr hfr_pow2(HFr x, uint32_t times) {  // x^(2^times)
+  for (uint32_t i = 0; i < times; i++) x = x.sqr();
+  return x;
+}
+
+// the shift between the inverse and the forward transform of the prover's chain: coefficient j times inc^j / n,
+// inc = w[k + 1] (the odd coset of the domain of twice the size; Fr has no w[29], so 2^28 shifts by the generator's 25)
+struct NttCosetShift {
+  HFr inc, ninv;
 };
+inline NttCosetShift ntt_coset_shift(uint32_t k) {
+  return {k == 28 ? HFr::from_u64(25) : hfr_root_of_unity(k + 1), HFr::from_u64(1ull << k).inv()};
+}
 
 inline Fr to_dev(const HFr& h) {
   Fr f;
@@ -365,154 +381,132 @@ inline void build_pow_table(hipStream_t st, const HFr& base, const HFr& scale, u
                      count, out);
 }
 
-struct NttEngine {
-  std::map<uint64_t, NttTables> cache;  // key = k*2 + inverse
-  std::map<uint64_t, std::pair<void*, void*>> coset_cache;  // k -> (hi, lo) of inc^j / n
+// Everything a transform of 2^k elements needs, built whole on the first use of that k: the plan and the device tables
+// its passes read. `mem` owns the tables, so a build that fails midway gives back what it had allocated.
+struct NttSize {
+  struct Twiddles {                       // of one direction: W = w[k] or its inverse
+    const void *hi, *lo;                  // W^(i * 2^L), i < 2^(k-L);  W^i, i < 2^L
+    std::vector<const void*> small;       // per pass: W_{2^B}^t, t < 2^(B-1) (passes of equal B share one)
+    std::vector<const void*> direct;      // per pass: its boundary twiddles as one table, nullptr where it has none
+  };
+  uint32_t k, L;                          // L = (k + 1) / 2: the split of every two-level table of this size
+  std::vector<NttPass> plan;
+  Twiddles tw[2];                         // [inverse]
+  const void *cos_hi, *cos_lo;            // inc^j / n, two-level like hi / lo
+  Fr ninv;                                // 1/n
+  std::deque<DevBuf> mem;
 
-  static HFr hpow2(HFr x, uint32_t times) {
-    for (uint32_t i = 0; i < times; i++) x = x.sqr();
-    return x;
-  }
+  void* table(size_t count) { return mem.emplace_back(count * 32).p; }
 
-  const NttTables& tables(hipStream_t st, uint32_t k, bool inverse) {
-    uint64_t key = (uint64_t)k * 2 + (inverse ? 1 : 0);
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
-    NttTables t;
-    t.k = k;
-    t.L = (k + 1) / 2;
-    HFr w = hfr_root_of_unity(k);
-    if (inverse) w = w.inv();
-    uint32_t nlo = 1u << t.L, nhi = 1u << (k - t.L);
-    ZK_HIP(hipMalloc(&t.hi, (size_t)nhi * 32));
-    ZK_HIP(hipMalloc(&t.lo, (size_t)nlo * 32));
-    build_pow_table(st, hpow2(w, t.L), HFr::one(), nhi, t.hi);
-    build_pow_table(st, w, HFr::one(), nlo, t.lo);
-    for (const auto& ps : ntt_plan(k)) {
-      if (t.small.count(ps.B)) continue;
-      void* p = nullptr;
-      uint32_t cnt = ps.B ? (1u << (ps.B - 1)) : 1u;
-      ZK_HIP(hipMalloc(&p, (size_t)cnt * 32));
-      build_pow_table(st, hpow2(w, k - ps.B), HFr::one(), cnt, p);  // W_{2^B} = W^(2^(k-B))
-      t.small[ps.B] = p;
-    }
-    for (const auto& ps : ntt_plan(k)) {
-      if (ps.s_lo == 0 || ps.s_lo + ps.B > kNttDirectMaxLog) continue;
-      void* p = nullptr;
-      const uint32_t cnt = 1u << (ps.s_lo + ps.B);
-      ZK_HIP(hipMalloc(&p, (size_t)cnt * 32));
-      hipLaunchKernelGGL(ntt_direct_table_kernel, dim3((cnt + 255) / 256), dim3(256), 0, st, p, ps.s_lo, ps.B,
-                         k - (ps.s_lo + ps.B), (const void*)t.hi, (const void*)t.lo, t.L);
-      t.direct[ps.s_lo] = p;
-    }
-    return cache.emplace(key, t).first->second;
-  }
-
-  // tables for p -> (inc^j) * scale with j < 2^k
-  std::pair<void*, void*> pow_tables(hipStream_t st, uint32_t k, const HFr& g, const HFr& scale, uint64_t cache_key) {
-    auto it = coset_cache.find(cache_key);
-    if (it != coset_cache.end()) return it->second;
-    uint32_t L = (k + 1) / 2;
-    void *hi = nullptr, *lo = nullptr;
-    ZK_HIP(hipMalloc(&hi, (size_t)(1u << (k - L)) * 32));
-    ZK_HIP(hipMalloc(&lo, (size_t)(1u << L) * 32));
-    build_pow_table(st, hpow2(g, L), HFr::one(), 1u << (k - L), hi);
-    build_pow_table(st, g, scale, 1u << L, lo);
-    return coset_cache.emplace(cache_key, std::make_pair(hi, lo)).first->second;
-  }
-
-  // mode applies to the pass over stages [0, B) (the last DIF pass / the first DIT pass). kPassPreScale: (sc_hi,
-  // sc_lo, Lc) two-level table of the per-element factor. kPassBitrevOut: the transform reads `d_data`, uses `tmp`
-  // (n elements) for the intermediate passes and leaves the NATURAL-order result, times `post`, in d_data.
-  // batch vectors of 2^k elements, batch_stride bytes apart, go through every pass together (grid.y = batch).
-  static bool radix4() {   // ZKPOA_NTT_RADIX=2: one stage per barrier, as before r03 (A/B measurement)
-    static const bool v = [] {
-      const char* e = getenv("ZKPOA_NTT_RADIX");
-      return !(e && !strcmp(e, "2"));
-    }();
-    return v;
-  }
-  template <bool DIF>
-  void run_passes(hipStream_t st, void* d_data, uint32_t k, bool inverse, int mode = kPassPlain,
-                  const void* sc_hi = nullptr, const void* sc_lo = nullptr, uint32_t Lc = 0, void* tmp = nullptr,
-                  const HFr* post = nullptr, uint32_t batch = 1, size_t batch_stride = 0) {
-    if (k == 0 || batch == 0) return;
-    if (mode == kPassBitrevOut && batch != 1) throw HipError("ntt: the natural-order form takes one vector at a time");
-    const NttTables& t = tables(st, k, inverse);
-    auto plan = ntt_plan(k);
-    const Fr post_d = to_dev(post ? *post : HFr::one());
-    for (size_t idx = 0; idx < plan.size(); idx++) {
-      const NttPassDesc& ps = DIF ? plan[plan.size() - 1 - idx] : plan[idx];
-      uint32_t tile_log = ps.B + ps.logT;
-      uint32_t grid = 1u << (k - tile_log);
-      // a quarter of the tile: one radix-4 group (or two radix-2 butterflies) per thread and stage pair
-      const uint32_t nthreads = tile_log >= 8 ? (tile_log >= 11 ? kNttThreads : (1u << (tile_log - 2))) : 64u;
-      size_t lds_bytes = (size_t)32 << tile_log;
-      auto dit = t.direct.find(ps.s_lo);
-      const void* direct = dit == t.direct.end() ? nullptr : dit->second;
-      const bool special = ps.s_lo == 0 && mode != kPassPlain;
-      const void* src = d_data;
-      void* dst = d_data;
-      if (mode == kPassBitrevOut && plan.size() > 1) {   // d -> tmp, tmp -> tmp ..., tmp -> d (bit-reversed positions)
-        src = idx == 0 ? d_data : tmp;
-        dst = idx + 1 == plan.size() ? d_data : tmp;
+  NttSize(hipStream_t st, uint32_t k_) : k(k_), L((k_ + 1) / 2), plan(ntt_plan(k_, ntt_tile_log(k_))) {
+    const uint32_t nlo = 1u << L, nhi = 1u << (k - L);
+    for (int inverse = 0; inverse < 2; inverse++) {
+      Twiddles& t = tw[inverse];
+      const HFr w = inverse ? hfr_root_of_unity(k).inv() : hfr_root_of_unity(k);
+      void *hi = table(nhi), *lo = table(nlo);
+      build_pow_table(st, hfr_pow2(w, L), HFr::one(), nhi, hi);
+      build_pow_table(st, w, HFr::one(), nlo, lo);
+      t.hi = hi;
+      t.lo = lo;
+      for (size_t i = 0; i < plan.size(); i++) {
+        const NttPass& ps = plan[i];
+        size_t same = 0;
+        while (plan[same].B != ps.B) same++;
+        if (same < i) {
+          t.small.push_back(t.small[same]);
+        } else {
+          void* p = table(1u << (ps.B - 1));
+          build_pow_table(st, hfr_pow2(w, k - ps.B), HFr::one(), 1u << (ps.B - 1), p);  // W_{2^B} = W^(2^(k-B))
+          t.small.push_back(p);
+        }
+        void* d = nullptr;
+        if (ps.direct) {
+          const uint32_t cnt = 1u << (ps.s_lo + ps.B);
+          d = table(cnt);
+          hipLaunchKernelGGL(ntt_direct_table_kernel, dim3((cnt + 255) / 256), dim3(256), 0, st, d, ps.s_lo, ps.B,
+                             k - (ps.s_lo + ps.B), t.hi, t.lo, L);
+        }
+        t.direct.push_back(d);
       }
-#define ZK_NTT_PASS_R(MODE_, R4_)                                                                                        \
-  hipLaunchKernelGGL((ntt_pass_kernel<DIF, MODE_, R4_>), dim3(grid, batch), dim3(nthreads), lds_bytes, st, src, dst,      \
-                     batch_stride, k, ps.s_lo, ps.B, ps.logT, (const void*)t.small.at(ps.B), (const void*)t.hi,          \
-                     (const void*)t.lo, t.L, direct, sc_hi, sc_lo, Lc, post_d)
-#define ZK_NTT_PASS(MODE_)              \
-  do {                                  \
-    if (radix4()) ZK_NTT_PASS_R(MODE_, true); \
-    else ZK_NTT_PASS_R(MODE_, false);   \
-  } while (0)
-      if (special && mode == kPassPreScale) ZK_NTT_PASS(kPassPreScale);
-      else if (special && mode == kPassBitrevOut) ZK_NTT_PASS(kPassBitrevOut);
-      else ZK_NTT_PASS(kPassPlain);
-#undef ZK_NTT_PASS
-#undef ZK_NTT_PASS_R
     }
+    const NttCosetShift sh = ntt_coset_shift(k);
+    void *hi = table(nhi), *lo = table(nlo);
+    build_pow_table(st, hfr_pow2(sh.inc, L), HFr::one(), nhi, hi);
+    build_pow_table(st, sh.inc, sh.ninv, nlo, lo);
+    cos_hi = hi;
+    cos_lo = lo;
+    ninv = to_dev(sh.ninv);
   }
+};
 
-  // natural -> bit-reversed, root w (or w^-1)
-  void dif(hipStream_t st, void* d, uint32_t k, bool inverse, uint32_t batch = 1, size_t stride = 0) {
-    run_passes<true>(st, d, k, inverse, kPassPlain, nullptr, nullptr, 0, nullptr, nullptr, batch, stride);
-  }
-  // bit-reversed -> natural
-  void dit(hipStream_t st, void* d, uint32_t k, bool inverse, uint32_t batch = 1, size_t stride = 0) {
-    run_passes<false>(st, d, k, inverse, kPassPlain, nullptr, nullptr, 0, nullptr, nullptr, batch, stride);
-  }
+// What a transform does besides the butterflies, each folded into the pass over stages [0, B):
+//   kNttDif      natural -> bit-reversed (Gentleman-Sande passes from the top stage down)
+//   kNttDit      bit-reversed -> natural (Cooley-Tukey passes from stage 0 up)
+//   kNttNatural  Fr.fft / Fr.ifft: natural order in and out. DIF passes, the last one kPassBitrevOut (times 1/n in the
+//                inverse); multi-pass sizes go d -> scratch ... -> d. One vector at a time.
+//   kNttCoset    DIT passes, the first one kPassPreScale with the size's coset table
+enum NttForm { kNttDif, kNttDit, kNttNatural, kNttCoset };
 
-  // Fr.fft / Fr.ifft semantics: natural order in and out. The bit-reversal and the 1/n of the inverse ride on the
-  // last DIF pass's store (no permutation kernel, no scaling kernel); multi-pass sizes go through a scratch buffer
-  // of n elements (grow-only, kept on the engine).
-  void* nat_tmp = nullptr;
+struct NttEngine {
+  std::unique_ptr<NttSize> sizes[29];
+  // scratch of the natural form, n elements (grow-only: smaller sizes reuse it)
+  std::unique_ptr<DevBuf> nat_tmp;
   size_t nat_tmp_bytes = 0;
-  void transform_natural(hipStream_t st, void* d, uint32_t k, bool inverse) {
-    if (k == 0) return;
-    const uint64_t n = 1ull << k;
-    if (ntt_plan(k).size() > 1 && nat_tmp_bytes < n * 32) {
+
+  const NttSize& size(hipStream_t st, uint32_t k) {
+    if (k > 28) throw HipError("ntt: log_n > 28 (two-adicity of Fr)");
+    if (!sizes[k]) sizes[k] = std::make_unique<NttSize>(st, k);
+    return *sizes[k];
+  }
+
+  template <bool DIF, int MODE>
+  static void launch(hipStream_t st, const NttSize& sz, bool inverse, size_t i, const void* src, void* dst, uint32_t batch,
+                     size_t batch_stride, const Fr& post) {
+    const NttPass& ps = sz.plan[i];
+    const NttSize::Twiddles& t = sz.tw[inverse];
+    hipLaunchKernelGGL((ntt_pass_kernel<DIF, MODE>), dim3(ps.grid, batch), dim3(ps.threads), ps.lds_bytes, st, src, dst,
+                       batch_stride, sz.k, ps.s_lo, ps.B, ps.logT, t.small[i], t.hi, t.lo, sz.L, t.direct[i], sz.cos_hi,
+                       sz.cos_lo, sz.L, post);
+  }
+
+  // `batch` vectors of 2^k elements, batch_stride bytes apart, go through every pass together (grid.y = batch)
+  void run(hipStream_t st, const NttSize& sz, NttForm form, bool inverse, void* d, uint32_t batch = 1,
+           size_t batch_stride = 0) {
+    const size_t np = sz.plan.size();
+    if (np == 0 || batch == 0) return;
+    const bool natural = form == kNttNatural, dif = natural || form == kNttDif;
+    if (natural && batch != 1) throw HipError("ntt: the natural-order form takes one vector at a time");
+    const size_t bytes = (size_t)32 << sz.k;
+    if (natural && np > 1 && nat_tmp_bytes < bytes) {
       ZK_HIP(hipStreamSynchronize(st));
-      if (nat_tmp) ZK_HIP(hipFree(nat_tmp));
-      nat_tmp = nullptr;
       nat_tmp_bytes = 0;
-      ZK_HIP(hipMalloc(&nat_tmp, n * 32));
-      nat_tmp_bytes = n * 32;
+      nat_tmp.reset();
+      nat_tmp = std::make_unique<DevBuf>(bytes);
+      nat_tmp_bytes = bytes;
     }
-    HFr ninv = HFr::from_u64(n).inv();
-    run_passes<true>(st, d, k, inverse, kPassBitrevOut, nullptr, nullptr, 0, nat_tmp, inverse ? &ninv : nullptr);
+    const Fr post = natural && inverse ? sz.ninv : to_dev(HFr::one());
+    for (size_t idx = 0; idx < np; idx++) {
+      const size_t i = dif ? np - 1 - idx : idx;
+      const void* src = d;
+      void* dst = d;
+      if (natural && np > 1) {   // d -> tmp, tmp -> tmp ..., tmp -> d (bit-reversed positions)
+        src = idx == 0 ? d : nat_tmp->p;
+        dst = idx + 1 == np ? d : nat_tmp->p;
+      }
+      const bool folded = i == 0 && (natural || form == kNttCoset);
+      if (folded && natural) launch<true, kPassBitrevOut>(st, sz, inverse, i, src, dst, batch, batch_stride, post);
+      else if (folded) launch<false, kPassPreScale>(st, sz, inverse, i, src, dst, batch, batch_stride, post);
+      else if (dif) launch<true, kPassPlain>(st, sz, inverse, i, src, dst, batch, batch_stride, post);
+      else launch<false, kPassPlain>(st, sz, inverse, i, src, dst, batch, batch_stride, post);
+    }
   }
 
   // evaluations on the domain -> evaluations on the odd coset (ifft, batchApplyKey(1, inc), fft): the coset shift
   // inc^j / n is applied by the forward transform's first pass as it loads (no separate scaling pass)
   void to_odd_coset(hipStream_t st, void* d, uint32_t k, uint32_t batch = 1, size_t stride = 0) {
-    if (k == 0) return;  // n = 1: constant polynomial
-    uint64_t n = 1ull << k;
-    HFr inc = (k == 28) ? HFr::from_u64(25) : hfr_root_of_unity(k + 1);
-    HFr ninv = HFr::from_u64(n).inv();
-    auto tb = pow_tables(st, k, inc, ninv, k);
-    dif(st, d, k, true, batch, stride);
-    run_passes<false>(st, d, k, false, kPassPreScale, tb.first, tb.second, (k + 1) / 2, nullptr, nullptr, batch, stride);
+    const NttSize& sz = size(st, k);
+    run(st, sz, kNttDif, true, d, batch, stride);
+    run(st, sz, kNttCoset, false, d, batch, stride);
   }
 
   // the part of to_odd_coset between the two exchanges when the transform is split over G ranks
@@ -522,12 +516,9 @@ struct NttEngine {
     uint32_t lg = 0;
     while ((1u << lg) < G) lg++;
     const uint32_t logM = k - lg, Q = (1u << logM) / G;
-    const NttTables& ti = tables(st, k, true);
-    const NttTables& tf = tables(st, k, false);
-    HFr inc = (k == 28) ? HFr::from_u64(25) : hfr_root_of_unity(k + 1);
-    auto tc = pow_tables(st, k, inc, HFr::from_u64(1ull << k).inv(), k);
+    const NttSize& sz = size(st, k);
     SplitRoots roots;
-    HFr wf = hpow2(hfr_root_of_unity(k), logM), wi = wf.inv(), af = HFr::one(), ai = HFr::one();
+    HFr wf = hfr_pow2(hfr_root_of_unity(k), logM), wi = wf.inv(), af = HFr::one(), ai = HFr::one();
     for (uint32_t e = 0; e < 8; e++) {
       roots.fwd[e] = to_dev(af);
       roots.inv[e] = to_dev(ai);
@@ -535,33 +526,13 @@ struct NttEngine {
       ai = ai * wi;
     }
     dim3 grid((Q + 255) / 256), block(256);
-    const uint32_t Lc = (k + 1) / 2;
-#define ZK_SPLIT_MID(GG)                                                                                            \
-  hipLaunchKernelGGL((ntt_split_mid_kernel<GG>), grid, block, 0, st, in, out, Q, rank_stride, h * Q, logM, roots,   \
-                     (const void*)ti.hi, (const void*)ti.lo, (const void*)tf.hi, (const void*)tf.lo, ti.L,          \
-                     (const void*)tc.first, (const void*)tc.second, Lc)
+#define ZK_SPLIT_MID(GG)                                                                                           \
+  hipLaunchKernelGGL((ntt_split_mid_kernel<GG>), grid, block, 0, st, in, out, Q, rank_stride, h * Q, logM, roots,  \
+                     sz.tw[1].hi, sz.tw[1].lo, sz.tw[0].hi, sz.tw[0].lo, sz.L, sz.cos_hi, sz.cos_lo, sz.L)
     if (G == 2) ZK_SPLIT_MID(2);
     else if (G == 4) ZK_SPLIT_MID(4);
     else ZK_SPLIT_MID(8);
 #undef ZK_SPLIT_MID
-  }
-
-  void release() {
-    for (auto& kv : cache) {
-      (void)hipFree(kv.second.hi);
-      (void)hipFree(kv.second.lo);
-      for (auto& s : kv.second.small) (void)hipFree(s.second);
-      for (auto& s : kv.second.direct) (void)hipFree(s.second);
-    }
-    if (nat_tmp) (void)hipFree(nat_tmp);
-    nat_tmp = nullptr;
-    nat_tmp_bytes = 0;
-    for (auto& kv : coset_cache) {
-      (void)hipFree(kv.second.first);
-      (void)hipFree(kv.second.second);
-    }
-    cache.clear();
-    coset_cache.clear();
   }
 };
 

@@ -180,7 +180,8 @@ void scalar_mul_each_g1(zkpoa_context* ctx, const void* d_points, const void* d_
 void scalar_mul_each_g2(zkpoa_context* ctx, const void* d_points, const void* d_scalars, uint64_t n, void* d_out, uint32_t* d_flags,
                         void* d_scratch, uint64_t slab);
 // ntt.hip
-void ntt_prepare(zkpoa_context* ctx, hipStream_t st, uint32_t k);  // builds twiddle tables (hipMalloc) once per k
+// the first use of a size builds its plan and every table (hipMalloc, kernels on st); later calls find it ready
+void ntt_prepare(zkpoa_context* ctx, hipStream_t st, uint32_t k);
 // batch > 1: that many vectors of 2^k elements, `stride` bytes apart, transformed together (one launch per pass)
 void ntt_to_odd_coset(zkpoa_context* ctx, hipStream_t st, void* d_data, uint32_t k, uint32_t batch = 1, size_t stride = 0);
 void ntt_natural(zkpoa_context* ctx, hipStream_t st, void* d_data, uint32_t k, bool inverse);
