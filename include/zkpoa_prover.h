@@ -608,6 +608,16 @@ int zkpoa_field_prim(zkpoa_context* ctx, int field, int op, const void* in, void
  * (xyzz_dbl_affine), 4 = k a (xyzz_mul_small). Arguments an op does not use may be NULL. */
 int zkpoa_curve_prim(zkpoa_context* ctx, int group, int op, const void* a, const void* b, const uint32_t* k,
                      void* out, uint64_t n);
+/* The G1 accumulation's field: Fq in 9 limbs of 29 bits, Montgomery radix 2^261 (csrc/fq29.hip.h). Elements of n
+ * records of 32-bit words, in and out. Ops 0-3 and 7 take each operand as 9 limbs exactly as given when raw != 0 (so
+ * operands at the edge of the header's bounds can be fed), as 8 words re-limbed on load otherwise, and return 9 limbs
+ * as computed: 0 = mul (a, b), 1 = sqr (a), 2 = dot2 (a0, b0, a1, b1), 3 = norm(a + (4q - b)),
+ * 7 = norm(a + (14q - b)). 4 = re-limb: 8 words -> 9 limbs, then the 8 words made from them (17 out).
+ * 5 = mixed addition as the accumulation kernel does it: XYZZ (32 words, wire form, infinity = zz 0), affine base
+ * (16 words), negate flag (1 word) -> canonical XYZZ (32 words). 6 = full addition: two XYZZ -> canonical XYZZ.
+ * 8 = a piece as msm_accum0_kernel sums it: 8 x (affine base, negate flag) = 136 words -> canonical XYZZ.
+ * raw is ignored by ops 4-6 and 8. */
+int zkpoa_fq29_prim(zkpoa_context* ctx, int op, const void* in, void* out, uint64_t n, int raw);
 /* The NTT's other forms on a host buffer, in place (parity tests). form: 0 = ntt_dif (natural in, bit-reversed out),
  * 1 = ntt_dit (bit-reversed in, natural out), 2 = ntt_to_odd_coset (inverse ignored). No 1/n in forms 0 and 1.
  * batch vectors of 2^log_n elements start stride elements apart (stride >= 2^log_n); elements between them are not

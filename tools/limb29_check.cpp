@@ -1,0 +1,99 @@
+// Host check of csrc/fq29.hip.h: the header's own text, compiled by g++ with the column-overflow counter on.
+// Build: g++ -O2 -std=c++17 -DZKPOA_LIMB29_CHECK -I zk-proof-of-assets_amd/csrc tools/limb29_check.cpp -o limb29_check
+// Use:   limb29_check OP < in > out      (tests/test_limb29_host.py drives it)
+// in:  u32 n, then n records of u32 words; out: n result records, then the overflow count as u64.
+//   op 0 mul       18 -> 9      op 1 sqr   9 -> 9      op 2 dot2 (a0 b0 a1 b1)  36 -> 9
+//   op 3 norm(a + (C4 - b))  18 -> 9
+//   op 4 re-limb   8 words -> 9 limbs, 8 words back
+//   op 6 full add  64 words (two wire XYZZ) -> 36 limbs (wire domain, class N)
+//   op 7 norm(a + (C14 - b)) 18 -> 9
+//   op 8 piece     u32 count, then count x (16 base words, u32 negate) -> 32 words (wire XYZZ, each < 3q)
+// (the numbers are zkpoa_fq29_prim's; its op 5, one mixed addition with every exceptional case, needs the device's
+// exact addition and has no host form)
+#include "fq29.hip.h"
+#include <stdio.h>
+#include <stdlib.h>
+#include <vector>
+using namespace zkpoa;
+
+static bool rd(void* p, size_t n) { return fread(p, 4, n, stdin) == n; }
+static void wr(const void* p, size_t n) { fwrite(p, 4, n, stdout); }
+static Fq29 limbs(const uint32_t* w) {
+  Fq29 r;
+  for (int i = 0; i < 9; i++) r.l[i] = w[i];
+  return r;
+}
+
+int main(int argc, char** argv) {
+  if (argc != 2) return 2;
+  const int op = atoi(argv[1]);
+  uint32_t n;
+  if (!rd(&n, 1)) return 3;
+  uint32_t w[64];
+  for (uint32_t e = 0; e < n; e++) {
+    Fq29 r;
+    switch (op) {
+      case 0:
+        if (!rd(w, 18)) return 3;
+        r = fq29_mul(limbs(w), limbs(w + 9));
+        wr(r.l, 9);
+        break;
+      case 1:
+        if (!rd(w, 9)) return 3;
+        r = fq29_sqr(limbs(w));
+        wr(r.l, 9);
+        break;
+      case 2:
+        if (!rd(w, 36)) return 3;
+        r = fq29_dot2(limbs(w), limbs(w + 9), limbs(w + 18), limbs(w + 27));
+        wr(r.l, 9);
+        break;
+      case 3:
+      case 7:
+        if (!rd(w, 18)) return 3;
+        r = op == 3 ? fq29_norm(fq29_sub<Fq29C4>(limbs(w), limbs(w + 9)))
+                    : fq29_norm(fq29_sub<Fq29C14>(limbs(w), limbs(w + 9)));
+        wr(r.l, 9);
+        break;
+      case 4: {
+        if (!rd(w, 8)) return 3;
+        r = fq29_from_words(w);
+        uint32_t back[8];
+        fq29_to_words(r, back);
+        wr(r.l, 9);
+        wr(back, 8);
+        break;
+      }
+      case 8: {
+        uint32_t count;
+        if (!rd(&count, 1)) return 3;
+        G1Piece29 s;
+        s.empty = true;
+        for (uint32_t k = 0; k < count; k++) {
+          if (!rd(w, 17)) return 3;
+          g1piece29_add(s, w, w + 8, w[16] != 0);
+        }
+        uint32_t out[32];
+        g1piece29_finish(s, out);
+        wr(out, 32);
+        break;
+      }
+      case 6: {
+        if (!rd(w, 64)) return 3;
+        Xyzz29S a, b;
+        xyzz29s_from_wire(a, fq29_from_words(w), fq29_from_words(w + 8), fq29_from_words(w + 16), fq29_from_words(w + 24));
+        xyzz29s_from_wire(b, fq29_from_words(w + 32), fq29_from_words(w + 40), fq29_from_words(w + 48),
+                          fq29_from_words(w + 56));
+        xyzz29s_add(a, b);
+        Fq29 o[4];
+        xyzz29s_to_wire(a, o[0], o[1], o[2], o[3]);
+        for (int i = 0; i < 4; i++) wr(o[i].l, 9);
+        break;
+      }
+      default: return 2;
+    }
+  }
+  const uint64_t ov = limb29_overflows;
+  wr(&ov, 2);
+  return 0;
+}

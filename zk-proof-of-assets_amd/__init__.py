@@ -52,7 +52,7 @@ EXPORTS = [
     "zkpoa_gen_bases_g1_device", "zkpoa_gen_bases_g2_device",
     "zkpoa_g1_sum", "zkpoa_g2_sum", "zkpoa_g1_mul", "zkpoa_g2_mul",
     "zkpoa_setup_defer_host_frees", "zkpoa_last_ms", "zkpoa_set_option", "zkpoa_msm_points_limit", "zkpoa_field_op", "zkpoa_group_add",
-    "zkpoa_field_prim", "zkpoa_curve_prim", "zkpoa_ntt_form", "zkpoa_test_ntt_plan",
+    "zkpoa_field_prim", "zkpoa_curve_prim", "zkpoa_fq29_prim", "zkpoa_ntt_form", "zkpoa_test_ntt_plan",
     "zkpoa_groth16_verify", "zkpoa_sanitize_proof", "zkpoa_groth16_verify_points", "zkpoa_zkey_vkey", "zkpoa_zkey_export_vkey",
     "zkpoa_zkey_read_h_scalars", "zkpoa_zkey_precompute",
     "zkpoa_context_stream", "zkpoa_context_synchronize",
@@ -149,6 +149,8 @@ def lib():
                                        ctypes.c_uint64, ctypes.c_int]
         L.zkpoa_curve_prim.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
+        L.zkpoa_fq29_prim.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                      ctypes.c_int]
         L.zkpoa_ntt_form.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_uint, ctypes.c_uint64]
         L.zkpoa_zkey_load.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong, c_void_pp]
@@ -467,6 +469,14 @@ class Context:
         out = ctypes.create_string_buffer(max(1, 4 * fb * n))
         self._check(lib().zkpoa_curve_prim(self._h, group, op, pa, pb, pk, out, n), "zkpoa_curve_prim")
         return out.raw[:4 * fb * n]
+
+    def fq29_prim(self, op, data, n, out_words, raw=True):
+        """zkpoa_fq29_prim: `data` holds the n records of the op (32-bit words, little-endian); returns the n result
+        records of `out_words` words each, as bytes."""
+        pin, kin = _buf(data)
+        out = ctypes.create_string_buffer(max(1, 4 * out_words * n))
+        self._check(lib().zkpoa_fq29_prim(self._h, op, pin, out, n, 1 if raw else 0), "zkpoa_fq29_prim")
+        return out.raw[:4 * out_words * n]
 
     def ntt_form(self, data, log_n, form, inverse=False, batch=1, stride=None):
         """zkpoa_ntt_form: form 0 = DIF (natural in, bit-reversed out), 1 = DIT (bit-reversed in, natural out), 2 = to the

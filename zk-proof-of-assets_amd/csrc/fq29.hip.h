@@ -1,0 +1,391 @@
+// BN254 base field in 9 limbs of 29 bits, Montgomery radix R' = 2^261: the G1 bucket accumulation's field.
+//
+// Fp<> (bn254_field.hip.h) multiplies 8 x 32-bit limbs: a column of partial products needs 67 bits, so every
+// v_mad_u64_u32 is followed by a v_addc into a third accumulator word -- half of the product's instructions carry
+// bits. With 29-bit limbs a whole column fits ONE 64-bit accumulator, the product is mads and one shift per column,
+// and the 7 spare bits of the radix (2^261 / q > 169.28) make every conditional subtraction unnecessary.
+//
+// Plain C++, no inline assembly: the same text compiles for the device (hipcc) and for the host (g++,
+// tools/limb29_check.cpp, where -DZKPOA_LIMB29_CHECK counts column overflows).
+//
+// OPERAND CLASSES (a value is sum l[i] 2^(29 i); it is a field element only modulo q, never reduced below q here)
+//   N  product output        limbs 0..7 < 2^29 ("normalised"), value < 3q
+//   X  accumulator X         normalised, value < 13q
+//   W  re-limbed wire word   normalised, value < 2^256 (< 5.3q), limb 8 < 2^24
+//   D  difference, sum       NOT normalised: every limb < 3 * 2^29, value < 17q
+//   a normalised value V has limb 8 = V >> 232, < 2^26 for V < 17q.
+// RULES
+//   * a product takes at most ONE class-D operand (dot2: one per product); a D that is squared or meets another D is
+//     normalised first (norm: one carry pass, value unchanged).
+//   * operand values satisfy va * vb <= 338 q^2 (dot2: the sum of its two products).
+// COLUMNS. Column k of a product adds at most 9 a_i b_(k-i) + 9 m_i q_(k-i) and the carry of column k-1 (< 2^35).
+// m_i, q_i < 2^29. Both operands normalised: < 18 * 2^58 < 2^63. One operand D: 9 * 3 * 2^58 + 9 * 2^58 = 36 * 2^58.
+// dot2 as the mixed addition uses it (r * d + ny * ppp: r, ppp normalised, d < 3 * 2^29, ny < 2 * 2^29 per limb):
+// 27 * 2^58 + 18 * 2^58 + 9 * 2^58 = 54 * 2^58; with two D operands of 3 * 2^29: 63 * 2^58 + 2^35 < 2^64. The square
+// doubles its cross terms by doubling one limb (< 2^30): the same sum as the product. No column reaches 2^64.
+// VALUES. The output is (a b + m q) / 2^261 with m < 2^261: < va vb / 2^261 + q <= 338 q^2 / (169.28 q) + q < 3q.
+// So N is closed under every product the rules allow; the largest in the mixed addition is 17q * 17q = 289 q^2.
+// SUBTRACTION is a + (C - b) per limb, C = k q in a "borrowed" representation whose limbs are all >= the largest
+// limb b can have (limbs 0..7: d_i + 2^29 - 1 with a borrow of one from the limb above; limb 8: d_8 - 1, which has to
+// be >= b >> 232, i.e. k q exceeds b's value bound by 2^232): nothing goes negative, per limb or in value.
+//   C4  = 4q   subtrahend N (< 3q);          limbs < 2^30
+//   C6  = 6q   subtrahend W (< 2^256);       limbs < 2^30
+//   C14 = 14q  subtrahend X (< 13q);         limbs < 2^30
+//   C10 = 10q  subtrahend ppp + 2 Q (limbs < 3 * 2^29, value < 9q): borrow of 4, limbs < 5 * 2^29
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define ZK29 __host__ __device__ __forceinline__
+#else
+#define ZK29 inline
+#endif
+
+namespace zkpoa {
+
+#if defined(ZKPOA_LIMB29_CHECK)
+static uint64_t limb29_overflows = 0;   // host builds only: columns that left 64 bits
+#endif
+
+struct Fq29 {
+  uint32_t l[9];
+};
+
+struct Fq29P {
+  static constexpr uint32_t M = 0x1fffffffu;
+  static constexpr uint32_t INV = 0x04866389u;   // -q^-1 mod 2^29
+  static constexpr uint32_t Q[9] = {0x187cfd47u, 0x010460b6u, 0x1c72a34fu, 0x02d522d0u, 0x1585d978u,
+                                    0x02db40c0u, 0x00a6e141u, 0x0e5c2634u, 0x0030644eu};
+};
+struct Fq29C4 {
+  static constexpr uint32_t v[9] = {0x21f3f51cu, 0x241182dau, 0x31ca8d3bu, 0x2b548b42u, 0x361765dfu,
+                                    0x2b6d0301u, 0x229b8503u, 0x397098cfu, 0x00c19138u};
+};
+struct Fq29C6 {
+  static constexpr uint32_t v[9] = {0x32edefaau, 0x261a4447u, 0x2aafd3d9u, 0x30fed0e4u, 0x212318cfu,
+                                    0x31238483u, 0x23e94785u, 0x3628e537u, 0x012259d5u};
+};
+struct Fq29C10 {
+  static constexpr uint32_t v[9] = {0x94e1e4c6u, 0x8a2bc71fu, 0x9c7a6112u, 0x9c535c24u, 0x973a7eacu,
+                                    0x9c908782u, 0x8684cc86u, 0x8f997e04u, 0x01e3eb0cu};
+};
+struct Fq29C14 {
+  static constexpr uint32_t v[9] = {0x36d5d9e2u, 0x2e3d49fdu, 0x2e44ee51u, 0x27a7e76bu, 0x2d51e490u,
+                                    0x27fd8a88u, 0x2920518eu, 0x290a16d7u, 0x02a57c49u};
+};
+// 2^e mod q, normalised: domain changes by one product (x 2^e / 2^261)
+struct Fq29K266 {
+  static constexpr uint32_t v[9] = {0x13349ca1u, 0x1a5d84a8u, 0x0a3e5cacu, 0x100249e0u, 0x12b951e8u,
+                                    0x0e92d304u, 0x14cb95b3u, 0x041b9d3du, 0x00058003u};
+};
+struct Fq29K271 {
+  static constexpr uint32_t v[9] = {0x1d1c9c4bu, 0x08a372eeu, 0x1273abadu, 0x17c9d397u, 0x1698b0a7u,
+                                    0x09c89e50u, 0x177e12abu, 0x185f3518u, 0x001ed378u};
+};
+struct Fq29K256 {
+  static constexpr uint32_t v[9] = {0x058f0d9du, 0x1aea1c6eu, 0x11c2cf74u, 0x11d651ebu, 0x1462c0a7u,
+                                    0x11b7bc3cu, 0x1cbd99bau, 0x183340fbu, 0x000e0a77u};
+};
+struct Fq29K251 {
+  static constexpr uint32_t v[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0x00080000u};
+};
+
+template <class C>
+ZK29 Fq29 fq29_const() {
+  Fq29 r;
+#pragma unroll
+  for (int i = 0; i < 9; i++) r.l[i] = C::v[i];
+  return r;
+}
+
+// acc += a * b: one v_mad_u64_u32, no carry-out (see COLUMNS)
+ZK29 void fq29_mac(uint64_t& acc, uint32_t a, uint32_t b) {
+#if defined(ZKPOA_LIMB29_CHECK)
+  if (__builtin_add_overflow(acc, (uint64_t)a * b, &acc)) limb29_overflows++;
+#else
+  acc += (uint64_t)a * b;
+#endif
+}
+
+// ---- 8 x 32 <-> 9 x 29: bit slicing only -------------------------------------------------------------------------
+ZK29 Fq29 fq29_from_words(const uint32_t* w) {   // any 256-bit value -> class W
+  Fq29 r;
+#pragma unroll
+  for (int i = 0; i < 9; i++) {
+    const int bo = 29 * i, wd = bo >> 5, sh = bo & 31;
+    uint64_t two = w[wd];
+    if (wd + 1 < 8) two |= (uint64_t)w[wd + 1] << 32;
+    r.l[i] = (uint32_t)(two >> sh) & Fq29P::M;
+  }
+  return r;
+}
+ZK29 void fq29_to_words(const Fq29& a, uint32_t* w) {   // normalised, value < 2^256
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    const int i0 = (32 * j) / 29, off = 32 * j - 29 * i0;
+    uint64_t t = a.l[i0] >> off;
+    t |= (uint64_t)a.l[i0 + 1] << (29 - off);
+    if (i0 + 2 < 9) t |= (uint64_t)a.l[i0 + 2] << (58 - off);
+    w[j] = (uint32_t)t;
+  }
+}
+
+// ---- sums and differences (class D results) ---------------------------------------------------------------------
+ZK29 Fq29 fq29_norm(const Fq29& a) {   // one carry pass: limbs 0..7 < 2^29, value unchanged
+  Fq29 r;
+  uint32_t c = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const uint32_t t = a.l[i] + c;
+    r.l[i] = t & Fq29P::M;
+    c = t >> 29;
+  }
+  r.l[8] = a.l[8] + c;
+  return r;
+}
+template <class C>
+ZK29 Fq29 fq29_sub(const Fq29& a, const Fq29& b) {   // a + (C - b): b of the class C is made for
+  Fq29 r;
+#pragma unroll
+  for (int i = 0; i < 9; i++) r.l[i] = a.l[i] + (C::v[i] - b.l[i]);
+  return r;
+}
+template <class C>
+ZK29 Fq29 fq29_neg(const Fq29& b) {   // C - b
+  Fq29 r;
+#pragma unroll
+  for (int i = 0; i < 9; i++) r.l[i] = C::v[i] - b.l[i];
+  return r;
+}
+
+// ---- Montgomery products, radix 2^261, product scanning ---------------------------------------------------------
+// column k < 9 fixes m_k so that the column's low 29 bits vanish; columns 9..16 leave limbs 0..7 and what remains of
+// the accumulator is limb 8. No final subtraction (see VALUES).
+ZK29 Fq29 fq29_mul(const Fq29& a, const Fq29& b) {
+  uint64_t acc = 0;
+  uint32_t m[9];
+  Fq29 r;
+#pragma unroll
+  for (int k = 0; k < 9; k++) {
+#pragma unroll
+    for (int i = 0; i <= k; i++) fq29_mac(acc, a.l[i], b.l[k - i]);
+#pragma unroll
+    for (int i = 0; i < k; i++) fq29_mac(acc, m[i], Fq29P::Q[k - i]);
+    m[k] = ((uint32_t)acc * Fq29P::INV) & Fq29P::M;
+    fq29_mac(acc, m[k], Fq29P::Q[0]);
+    acc >>= 29;
+  }
+#pragma unroll
+  for (int k = 9; k < 17; k++) {
+#pragma unroll
+    for (int i = k - 8; i < 9; i++) fq29_mac(acc, a.l[i], b.l[k - i]);
+#pragma unroll
+    for (int i = k - 8; i < 9; i++) fq29_mac(acc, m[i], Fq29P::Q[k - i]);
+    r.l[k - 9] = (uint32_t)acc & Fq29P::M;
+    acc >>= 29;
+  }
+  r.l[8] = (uint32_t)acc;
+  return r;
+}
+// a^2: the 36 cross products once, against a doubled limb (45 + 81 mads instead of 81 + 81). a normalised.
+ZK29 Fq29 fq29_sqr(const Fq29& a) {
+  uint32_t d[9];
+#pragma unroll
+  for (int i = 0; i < 9; i++) d[i] = a.l[i] << 1;
+  uint64_t acc = 0;
+  uint32_t m[9];
+  Fq29 r;
+#pragma unroll
+  for (int k = 0; k < 9; k++) {
+#pragma unroll
+    for (int i = 0; 2 * i < k; i++) fq29_mac(acc, a.l[i], d[k - i]);
+    if ((k & 1) == 0) fq29_mac(acc, a.l[k / 2], a.l[k / 2]);
+#pragma unroll
+    for (int i = 0; i < k; i++) fq29_mac(acc, m[i], Fq29P::Q[k - i]);
+    m[k] = ((uint32_t)acc * Fq29P::INV) & Fq29P::M;
+    fq29_mac(acc, m[k], Fq29P::Q[0]);
+    acc >>= 29;
+  }
+#pragma unroll
+  for (int k = 9; k < 17; k++) {
+#pragma unroll
+    for (int i = k - 8; 2 * i < k; i++) fq29_mac(acc, a.l[i], d[k - i]);
+    if ((k & 1) == 0) fq29_mac(acc, a.l[k / 2], a.l[k / 2]);
+#pragma unroll
+    for (int i = k - 8; i < 9; i++) fq29_mac(acc, m[i], Fq29P::Q[k - i]);
+    r.l[k - 9] = (uint32_t)acc & Fq29P::M;
+    acc >>= 29;
+  }
+  r.l[8] = (uint32_t)acc;
+  return r;
+}
+// (a0 b0 + a1 b1) / 2^261 under one reduction
+ZK29 Fq29 fq29_dot2(const Fq29& a0, const Fq29& b0, const Fq29& a1, const Fq29& b1) {
+  uint64_t acc = 0;
+  uint32_t m[9];
+  Fq29 r;
+#pragma unroll
+  for (int k = 0; k < 9; k++) {
+#pragma unroll
+    for (int i = 0; i <= k; i++) {
+      fq29_mac(acc, a0.l[i], b0.l[k - i]);
+      fq29_mac(acc, a1.l[i], b1.l[k - i]);
+    }
+#pragma unroll
+    for (int i = 0; i < k; i++) fq29_mac(acc, m[i], Fq29P::Q[k - i]);
+    m[k] = ((uint32_t)acc * Fq29P::INV) & Fq29P::M;
+    fq29_mac(acc, m[k], Fq29P::Q[0]);
+    acc >>= 29;
+  }
+#pragma unroll
+  for (int k = 9; k < 17; k++) {
+#pragma unroll
+    for (int i = k - 8; i < 9; i++) {
+      fq29_mac(acc, a0.l[i], b0.l[k - i]);
+      fq29_mac(acc, a1.l[i], b1.l[k - i]);
+    }
+#pragma unroll
+    for (int i = k - 8; i < 9; i++) fq29_mac(acc, m[i], Fq29P::Q[k - i]);
+    r.l[k - 9] = (uint32_t)acc & Fq29P::M;
+    acc >>= 29;
+  }
+  r.l[8] = (uint32_t)acc;
+  return r;
+}
+
+// ---- G1 accumulator ---------------------------------------------------------------------------------------------
+// Point (X / ZZ, Y / ZZZ) with X, Y held times 2^261 and ZZ, ZZZ times 2^266. A wire base (x 2^256, y 2^256) then
+// needs no conversion: (x 2^256)(ZZ 2^266) / 2^261 = x ZZ 2^261 lands in X's domain, and every later product of
+// madd-2008-s closes: pp, ppp, q in 2^261; ZZ pp, ZZZ ppp in 2^266. x, y: class X and N; zz, zzz: class N.
+struct Xyzz29 {
+  Fq29 x, y, zz, zzz;
+};
+
+// acc = (bx, by): bx class W, by class W or C6 - W
+ZK29 void xyzz29_open(Xyzz29& acc, const Fq29& bx, const Fq29& by) {
+  const Fq29 k = fq29_const<Fq29K266>();
+  acc.x = fq29_mul(bx, k);
+  acc.y = fq29_mul(by, k);
+  acc.zz = k;
+  acc.zzz = k;
+}
+// acc from wire XYZZ words (class W each), any representative of a non-infinity point
+ZK29 void xyzz29_from_wire(Xyzz29& acc, const Fq29& x, const Fq29& y, const Fq29& zz, const Fq29& zzz) {
+  const Fq29 k0 = fq29_const<Fq29K266>(), k1 = fq29_const<Fq29K271>();
+  acc.x = fq29_mul(x, k0);
+  acc.y = fq29_mul(y, k0);
+  acc.zz = fq29_mul(zz, k1);
+  acc.zzz = fq29_mul(zzz, k1);
+}
+// back to the wire domain (2^256), class N: the caller re-limbs and stores canonically
+ZK29 void xyzz29_to_wire(const Xyzz29& acc, Fq29& x, Fq29& y, Fq29& zz, Fq29& zzz) {
+  const Fq29 k0 = fq29_const<Fq29K256>(), k1 = fq29_const<Fq29K251>();
+  x = fq29_mul(acc.x, k0);
+  y = fq29_mul(acc.y, k0);
+  zz = fq29_mul(acc.zz, k1);
+  zzz = fq29_mul(acc.zzz, k1);
+}
+
+// acc += (bx, by), generic case only [madd-2008-s]: no test for acc = +-base. There pp_ = 0 (mod q), so ZZ becomes
+// 0 (mod q) and STAYS 0 through every later addition: the caller tests ZZ once at the end and redoes the piece with
+// the exact xyzz_add_affine. bx class W; by class W, or C6 - W for a negated base (limbs < 2^30, value < 6q).
+// Value products: u2 5.3 * 3, s2 6 * 3, pp 17^2 = 289, rr 7^2, ppp 17 * 3, q 13 * 3, y 7 * 17 + 4 * 3 = 131, zz 9.
+ZK29 void xyzz29_madd(Xyzz29& acc, const Fq29& bx, const Fq29& by) {
+  const Fq29 u2 = fq29_mul(bx, acc.zz);
+  const Fq29 s2 = fq29_mul(by, acc.zzz);
+  const Fq29 p = fq29_norm(fq29_sub<Fq29C14>(u2, acc.x));   // < 3q + 14q
+  const Fq29 r = fq29_norm(fq29_sub<Fq29C4>(s2, acc.y));    // < 3q + 4q
+  const Fq29 pp = fq29_sqr(p);
+  const Fq29 rr = fq29_sqr(r);
+  const Fq29 ppp = fq29_mul(p, pp);
+  const Fq29 q = fq29_mul(acc.x, pp);
+  Fq29 t;   // x3 = rr - ppp - 2q = rr + (C10 - (ppp + 2q)): limbs < 6 * 2^29, value < 3q + 10q
+#pragma unroll
+  for (int i = 0; i < 9; i++) t.l[i] = rr.l[i] + (Fq29C10::v[i] - (ppp.l[i] + 2u * q.l[i]));
+  const Fq29 x3 = fq29_norm(t);
+  // y3 = r (q - x3) - y1 ppp, one reduction: q - x3 class D (< 3q + 14q), -y1 = C4 - y1 (limbs < 2^30, < 4q)
+  acc.y = fq29_dot2(r, fq29_sub<Fq29C14>(q, x3), fq29_neg<Fq29C4>(acc.y), ppp);
+  acc.x = x3;
+  acc.zz = fq29_mul(acc.zz, pp);
+  acc.zzz = fq29_mul(acc.zzz, ppp);
+}
+
+// One piece of a bucket: a sum of wire-format affine bases (x then y, 8 words each, all-zero = infinity).
+struct G1Piece29 {
+  Xyzz29 a;
+  bool empty;
+};
+ZK29 void g1piece29_add(G1Piece29& s, const uint32_t* xw, const uint32_t* yw, bool negate) {
+  uint32_t any = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) any |= xw[i] | yw[i];
+  if (any == 0) return;   // infinity base
+  const Fq29 bx = fq29_from_words(xw);
+  Fq29 by = fq29_from_words(yw);
+#pragma unroll
+  for (int i = 0; i < 9; i++) by.l[i] = negate ? Fq29C6::v[i] - by.l[i] : by.l[i];
+  if (s.empty) {
+    xyzz29_open(s.a, bx, by);
+    s.empty = false;
+  } else {
+    xyzz29_madd(s.a, bx, by);
+  }
+}
+// wire XYZZ words of the sum, each < 3q and NOT canonical; all zero for an empty piece. A result whose ZZ is
+// 0 (mod q) is not a sum: the piece met acc = +-base and has to be redone with the exact addition.
+ZK29 void g1piece29_finish(const G1Piece29& s, uint32_t* out32) {
+  if (s.empty) {
+#pragma unroll
+    for (int i = 0; i < 32; i++) out32[i] = 0;
+    return;
+  }
+  Fq29 x, y, zz, zzz;
+  xyzz29_to_wire(s.a, x, y, zz, zzz);
+  fq29_to_words(x, out32);
+  fq29_to_words(y, out32 + 8);
+  fq29_to_words(zz, out32 + 16);
+  fq29_to_words(zzz, out32 + 24);
+}
+
+// acc += b, generic case only [add-2008-s], both in ONE domain (all four coordinates times 2^261: the reduction
+// kernels convert both operands on load). acc = +-b leaves ZZ = 0 (mod q), as above.
+struct Xyzz29S {
+  Fq29 x, y, zz, zzz;   // x class X, the others class N
+};
+ZK29 void xyzz29s_from_wire(Xyzz29S& a, const Fq29& x, const Fq29& y, const Fq29& zz, const Fq29& zzz) {
+  const Fq29 k = fq29_const<Fq29K266>();
+  a.x = fq29_mul(x, k);
+  a.y = fq29_mul(y, k);
+  a.zz = fq29_mul(zz, k);
+  a.zzz = fq29_mul(zzz, k);
+}
+ZK29 void xyzz29s_to_wire(const Xyzz29S& a, Fq29& x, Fq29& y, Fq29& zz, Fq29& zzz) {
+  const Fq29 k = fq29_const<Fq29K256>();
+  x = fq29_mul(a.x, k);
+  y = fq29_mul(a.y, k);
+  zz = fq29_mul(a.zz, k);
+  zzz = fq29_mul(a.zzz, k);
+}
+// Value products: u1 13 * 3, u2 13 * 3, s1, s2 9, pp 7^2, ppp 7 * 3, q 9, y 7 * 17 + 4 * 3, zz 9.
+ZK29 void xyzz29s_add(Xyzz29S& acc, const Xyzz29S& b) {
+  const Fq29 u1 = fq29_mul(acc.x, b.zz);
+  const Fq29 u2 = fq29_mul(b.x, acc.zz);
+  const Fq29 s1 = fq29_mul(acc.y, b.zzz);
+  const Fq29 s2 = fq29_mul(b.y, acc.zzz);
+  const Fq29 p = fq29_norm(fq29_sub<Fq29C4>(u2, u1));
+  const Fq29 r = fq29_norm(fq29_sub<Fq29C4>(s2, s1));
+  const Fq29 pp = fq29_sqr(p);
+  const Fq29 rr = fq29_sqr(r);
+  const Fq29 ppp = fq29_mul(p, pp);
+  const Fq29 q = fq29_mul(u1, pp);
+  Fq29 t;
+#pragma unroll
+  for (int i = 0; i < 9; i++) t.l[i] = rr.l[i] + (Fq29C10::v[i] - (ppp.l[i] + 2u * q.l[i]));
+  const Fq29 x3 = fq29_norm(t);
+  acc.y = fq29_dot2(r, fq29_sub<Fq29C14>(q, x3), fq29_neg<Fq29C4>(s1), ppp);
+  acc.x = x3;
+  acc.zz = fq29_mul(fq29_mul(acc.zz, b.zz), pp);
+  acc.zzz = fq29_mul(fq29_mul(acc.zzz, b.zzz), ppp);
+}
+
+}  // namespace zkpoa

@@ -26,6 +26,7 @@
 // bucket set and the same kernels run over n * W entries.
 #pragma once
 #include "bn254_ec.hip.h"
+#include "fq29.hip.h"
 #include "device_ctx.hpp"
 #include <string.h>
 #include <chrono>
@@ -639,8 +640,44 @@ static __global__ __launch_bounds__(256) void msm_piece_order_kernel(const uint3
   }
 }
 
+// ---- G1 sums in 9 x 29-bit limbs ------------------------------------------------------------------------------
+// The G1 accumulation adds in the field of fq29.hip.h (no carry instruction per partial product, no conditional
+// subtraction; tools/microbench_limb29.hip). Its additions are the generic formulas only: a sum that met acc = +-base
+// shows ZZ = 0 (mod q) at its end and is redone with the exact xyzz_add_affine / xyzz_add. Intermediate values are the
+// same field elements as in the 32-bit form and stores are canonical, so every stored byte is what it was.
+// -DZKPOA_G1_LIMB32 builds the 32-bit form (A/B switch).
+#if defined(ZKPOA_G1_LIMB32)
+constexpr bool kG1Limb29 = false;
+#else
+constexpr bool kG1Limb29 = true;
+#endif
+// wire words, each < 3q (fq29 class N re-limbed) -> XYZZ<Fq> in the lazy range [0, 2q)
+ZK_DEV XYZZ<Fq> xyzz_from_words_3q(const uint32_t* w) {
+  XYZZ<Fq> r;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    r.x.l[i] = w[i];
+    r.y.l[i] = w[8 + i];
+    r.zz.l[i] = w[16 + i];
+    r.zzz.l[i] = w[24 + i];
+  }
+  r.x = Fq::reduce_2p(r.x);
+  r.y = Fq::reduce_2p(r.y);
+  r.zz = Fq::reduce_2p(r.zz);
+  r.zzz = Fq::reduce_2p(r.zzz);
+  return r;
+}
+// the piece's sum; false if it is not one (see above)
+ZK_DEV bool g1piece29_result(const G1Piece29& s, XYZZ<Fq>& out) {
+  uint32_t w[32];
+  g1piece29_finish(s, w);
+  out = xyzz_from_words_3q(w);
+  return s.empty || !out.zz.is_zero();
+}
+
 // waves per SIMD the accumulation kernel is compiled for (register budget 512 / waves):
-// G1: 132 VGPRs -> 3 waves (4 waves = 128 VGPRs measured no faster: the kernel is at the ALU ceiling); G2: 256 -> 2
+// G1: 144 VGPRs in the 29-bit-limb form -> 3 waves (4 waves = 128 VGPRs spills 72 bytes per lane; the 32-bit form,
+// 132 VGPRs, measured no faster at 4: the kernel is at the ALU ceiling); G2: 256 -> 2
 template <class F> struct AccumWaves { static constexpr int N = 3; };
 template <> struct AccumWaves<Fq2> { static constexpr int N = 2; };
 
@@ -689,7 +726,30 @@ static __global__ __launch_bounds__(256, AccumWaves<F>::N) void msm_accum0_kerne
     const uint32_t i = k & 3u;
     return i == 0u ? cache.x : (i == 1u ? cache.y : (i == 2u ? cache.z : cache.w));
   };
-  if (kAccumPrefetch<F>) {
+  if constexpr (kG1Limb29 && std::is_same<F, Fq>::value) {
+    // G1: the piece is summed in 9 x 29-bit limbs (fq29.hip.h), generic additions only; same walk and prefetch
+    G1Piece29 s;
+    s.a = {};
+    s.empty = true;
+    uint32_t e = entry(start);
+    Affine<F> p = load_affine<F>(bases, e & 0x7fffffffu);
+    for (uint32_t k = start; k < end; k++) {
+      uint32_t e_cur = e;
+      Affine<F> p_cur = p;
+      if (k + 1 < end) {
+        e = entry(k + 1);
+        p = load_affine<F>(bases, e & 0x7fffffffu);
+      }
+      g1piece29_add(s, p_cur.x.l, p_cur.y.l, (e_cur >> 31) != 0);
+    }
+    if (!g1piece29_result(s, acc)) {   // the piece met acc = +-base: once more, with the exact addition
+      acc = XYZZ<F>::inf();
+      for (uint32_t k = start; k < end; k++) {
+        const uint32_t e2 = sorted[k];
+        xyzz_add_affine(acc, load_affine<F>(bases, e2 & 0x7fffffffu), (e2 >> 31) != 0);
+      }
+    }
+  } else if (kAccumPrefetch<F>) {
     uint32_t e = entry(start);
     Affine<F> p = load_affine<F>(bases, e & 0x7fffffffu);
     for (uint32_t k = start; k < end; k++) {

@@ -139,6 +139,7 @@ void field_prim_run_g1(zkpoa_context* ctx, int field, int op, const void* in, vo
 void field_prim_run_g2(zkpoa_context* ctx, int op, const void* in, void* out, uint64_t n, int raw);
 void curve_prim_run_g1(zkpoa_context* ctx, int op, const void* a, const void* b, const uint32_t* k, void* out,
                        uint64_t n);
+void fq29_prim_run(zkpoa_context* ctx, int op, const void* in, void* out, uint64_t n, int raw);
 void curve_prim_run_g2(zkpoa_context* ctx, int op, const void* a, const void* b, const uint32_t* k, void* out,
                        uint64_t n);
 void gen_bases_g1(zkpoa_context* ctx, const uint8_t a_le[32], const uint8_t b_le[32], uint64_t i0, uint64_t n, void* d_out);
