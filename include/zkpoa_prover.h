@@ -505,6 +505,51 @@ int zkpoa_ptau_contribute(zkpoa_context* ctx, const char* in_path, const char* o
  * above 30 and beacons above 255 bytes are refused. */
 int zkpoa_ptau_beacon(zkpoa_context* ctx, const char* in_path, const char* out_path, const uint8_t* beacon,
                       unsigned long beacon_len, uint32_t num_iterations_exp, const char* name);
+/* ---- challenge and response files: `snarkjs powersoftau export challenge / challenge contribute / import response`
+ * (DESIGN.md "Phase-1 transcript", "Challenge and response files"; N = 2^power).
+ *   challenge file: 64 B, the response hash of the ceremony file's last record (Blake2b-512 of the empty string for a
+ *     file without records) | the hash form of sections 2-6. Its Blake2b-512 is the ceremony file's challenge.
+ *   response file: 64 B, the challenge | the compressed form of the new sections 2-6 | the nine points of the key in
+ *     hash form (768 B). Its Blake2b-512 is the record's response hash.
+ * The formats follow snarkjs as far as they are known to this project; acceptance by snarkjs is not exercised.
+ * zkpoa_sqrt_device: n elements of Fq (field 0, 32 B) or Fq2 (field 2, 64 B, c0 then c1) in wire form (Montgomery,
+ *   little-endian, below q; host buffers) -> roots[i] = the root of a[i] that is not negative (not above (q - 1) / 2; for
+ *   Fq2 by c1, by c0 when c1 = 0), all-zero when a[i] is no square, and is_square[i] = 1 | 0. Every element takes the
+ *   same exponentiations: one in Fq, two in Fq2.
+ * zkpoa_decompressed_form: the inverse of zkpoa_compressed_form. n points of group 1 | 2 in compressed form (host) ->
+ *   out_points in wire form (host, 64 | 128 B each), converted on the device in pieces of piece_points (0 = 2^18).
+ *   PROVER_ERROR naming the first offending point's index for: both flag bits set, 0x40 followed by anything but zeros,
+ *   an x not below q, an x for which x^3 + b is no square. Subgroup membership is not checked here.
+ * zkpoa_from_hash_form: the inverse of zkpoa_hash_form, the same way. PROVER_ERROR naming the point's index for: bit 7
+ *   of its first byte set, 0x40 followed by anything but zeros, a coordinate not below q. Neither the curve equation nor
+ *   subgroup membership is checked here. */
+int zkpoa_sqrt_device(zkpoa_context* ctx, int field, const void* a, uint64_t n, void* roots, uint8_t* is_square);
+int zkpoa_decompressed_form(zkpoa_context* ctx, int group, const void* bytes, uint64_t n, uint64_t piece_points,
+                            void* out_points);
+int zkpoa_from_hash_form(zkpoa_context* ctx, int group, const void* bytes, uint64_t n, uint64_t piece_points,
+                         void* out_points);
+/* `powersoftau export challenge <in.ptau> <challenge>`: writes the challenge file of ptau_path; challenge_hash
+ * (optional) <- its Blake2b-512. Refused, with nothing left behind, when that hash is not the file's challenge (the
+ * nextChallenge of its last record; of a file without records, the challenge of the generators): the sections are then
+ * not the ones the last record describes. An output path that names the input is refused. */
+int zkpoa_ptau_export_challenge(zkpoa_context* ctx, const char* ptau_path, const char* challenge_path,
+                                uint8_t challenge_hash[64]);
+/* `powersoftau challenge contribute bn128 <challenge> <response>`: zkpoa_ptau_contribute's arithmetic on a challenge
+ * file. The power comes from the file's size (any other size is refused), the challenge is the Blake2b-512 of the
+ * whole file; the points are read back from hash form, checked (curve, G2 subgroup), multiplied and written in
+ * compressed form, in pieces (option "ptau_piece_points"). secrets_le and ZKPOA_PHASE1_S as zkpoa_ptau_contribute.
+ * response_hash (optional) <- the Blake2b-512 of the response file. */
+int zkpoa_ptau_challenge_contribute(zkpoa_context* ctx, const char* challenge_path, const char* response_path,
+                                    const uint8_t* secrets_le, uint8_t response_hash[64]);
+/* `powersoftau import response <old.ptau> <response> <new.ptau>`: new_path <- old_path's header, the response's
+ * sections decompressed on the device, and section 7 with one more record (type 0, `name`, the key from the response).
+ * Refused, with nothing left behind: a response whose size does not fit the old file's power or whose first 64 bytes
+ * are not the old file's challenge; a point that does not decompress (the message names section and index), is off
+ * its curve or outside G2; a record that does not verify against the old file's last record as zkpoa_ptau_verify checks
+ * it (the key's pairings, the ratios of tau, alpha and beta). That the sections are one chain of powers is NOT checked
+ * here: zkpoa_ptau_verify on the result does that. Sections 12-15 of the old file are dropped (a notice on stderr). */
+int zkpoa_ptau_import_response(zkpoa_context* ctx, const char* old_path, const char* response_path, const char* new_path,
+                               const char* name);
 /* Host only: *count <- the records of section 7, text (optional) <- one line "contribution <name> <response hash, hex>"
  * or "beacon <name> <response hash, hex>" per record. PROVER_ERROR for an unreadable file or a malformed section 7. */
 int zkpoa_ptau_contributions(const char* ptau_path, uint32_t* count, char* text, unsigned long cap);

@@ -68,6 +68,8 @@ EXPORTS = [
     "zkpoa_scalar_mul_each_device", "zkpoa_power_scalars_device", "zkpoa_compressed_form",
     "zkpoa_ptau_new", "zkpoa_ptau_contribute", "zkpoa_ptau_beacon", "zkpoa_ptau_contributions",
     "zkpoa_blake2b_state", "zkpoa_blake2b_restore",
+    "zkpoa_sqrt_device", "zkpoa_decompressed_form", "zkpoa_from_hash_form",
+    "zkpoa_ptau_export_challenge", "zkpoa_ptau_challenge_contribute", "zkpoa_ptau_import_response",
 ]
 
 
@@ -185,6 +187,15 @@ def lib():
         L.zkpoa_ptau_beacon.argtypes = L.zkpoa_zkey_beacon.argtypes
         L.zkpoa_ptau_contributions.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p,
                                                ctypes.c_ulong]
+        L.zkpoa_sqrt_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_void_p,
+                                        ctypes.c_void_p]
+        for f in (L.zkpoa_decompressed_form, L.zkpoa_from_hash_form):
+            f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
+        L.zkpoa_ptau_export_challenge.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
+        L.zkpoa_ptau_challenge_contribute.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
+                                                      ctypes.c_char_p]
+        L.zkpoa_ptau_import_response.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
+                                                 ctypes.c_char_p]
         L.zkpoa_blake2b_state.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
         L.zkpoa_blake2b_restore.argtypes = [ctypes.c_char_p]
         L.zkpoa_blake2b_restore.restype = ctypes.c_void_p
@@ -622,6 +633,56 @@ class Context:
         self._check(lib().zkpoa_ptau_beacon(self._h, os.fsencode(in_path), os.fsencode(out_path), bytes(beacon),
                                             len(beacon), num_iterations_exp, None if name is None else name.encode()),
                     "zkpoa_ptau_beacon")
+
+    def sqrt_device(self, field, a):
+        """Square roots on the device: a = n elements of Fq (field 0, 32 B each) or Fq2 (field 2, 64 B) in wire form ->
+        (roots, flags): the non-negative root of each element (all-zero when it is no square) and one 0/1 byte each."""
+        size = 64 if field == 2 else 32
+        n = len(a) // size
+        roots, ok = ctypes.create_string_buffer(max(1, n * size)), ctypes.create_string_buffer(max(1, n))
+        self._check(lib().zkpoa_sqrt_device(self._h, field, bytes(a), n, roots, ok), "zkpoa_sqrt_device")
+        return roots.raw[:n * size], ok.raw[:n]
+
+    def decompressed_form(self, group, data, piece_points=0):
+        """Compressed form (32 B per G1 point, 64 B per G2 point) -> wire-form points, on the device in pieces; a point
+        that does not decompress raises ZkpoaError naming its index."""
+        unit = 64 if group == 1 else 128
+        n = len(data) // (unit // 2)
+        out = ctypes.create_string_buffer(max(1, n * unit))
+        self._check(lib().zkpoa_decompressed_form(self._h, group, bytes(data), n, piece_points, out),
+                    "zkpoa_decompressed_form")
+        return out.raw[:n * unit]
+
+    def from_hash_form(self, group, data, piece_points=0):
+        """Hash form -> wire-form points, on the device in pieces; a point that is not in hash form raises ZkpoaError
+        naming its index."""
+        unit = 64 if group == 1 else 128
+        n = len(data) // unit
+        out = ctypes.create_string_buffer(max(1, n * unit))
+        self._check(lib().zkpoa_from_hash_form(self._h, group, bytes(data), n, piece_points, out), "zkpoa_from_hash_form")
+        return out.raw[:n * unit]
+
+    def ptau_export_challenge(self, ptau_path, challenge_path):
+        """`snarkjs powersoftau export challenge`: writes the challenge file -> its Blake2b-512, the file's challenge."""
+        h = ctypes.create_string_buffer(64)
+        self._check(lib().zkpoa_ptau_export_challenge(self._h, os.fsencode(ptau_path), os.fsencode(challenge_path), h),
+                    "zkpoa_ptau_export_challenge")
+        return h.raw
+
+    def ptau_challenge_contribute(self, challenge_path, response_path, secrets=None):
+        """`snarkjs powersoftau challenge contribute`: secrets as ptau_contribute -> the response file's Blake2b-512."""
+        sec = None if secrets is None else b"".join(int(x).to_bytes(32, "little") for x in secrets)
+        h = ctypes.create_string_buffer(64)
+        self._check(lib().zkpoa_ptau_challenge_contribute(self._h, os.fsencode(challenge_path),
+                                                          os.fsencode(response_path), sec, h),
+                    "zkpoa_ptau_challenge_contribute")
+        return h.raw
+
+    def ptau_import_response(self, old_path, response_path, new_path, name=None):
+        """`snarkjs powersoftau import response`: the response's sections and one more record into new_path."""
+        self._check(lib().zkpoa_ptau_import_response(self._h, os.fsencode(old_path), os.fsencode(response_path),
+                                                     os.fsencode(new_path), None if name is None else name.encode()),
+                    "zkpoa_ptau_import_response")
 
     def h_diff(self, points, n):
         """points[i + n] - points[i], i < n - 1, over 2n - 1 wire-form G1 points (device)."""

@@ -180,50 +180,67 @@ inline bool g2_ok(const uint8_t* w, pairing::G2* out) {
   *out = h_affine_from_bytes<HFq2>(w);
   return !out->is_inf() && pairing::g2_on_curve(*out) && h_mul(XYZZ<HFq2>::from_affine(*out), kR).is_inf();
 }
+// Where a trail stands before a record: the five points the record's are checked against (the generators before the
+// first) and the challenge its key was made for (the fresh challenge before the first).
+struct Trail {
+  pairing::G1 tau1, alpha1, beta1;
+  pairing::G2 tau2, beta2;
+  uint8_t challenge[64];
+};
+inline Trail fresh_trail(uint32_t power) {
+  Trail t{host_generator<HFq>(), host_generator<HFq>(), host_generator<HFq>(), host_generator<HFq2>(), host_generator<HFq2>(), {}};
+  fresh_challenge(power, t.challenge);
+  return t;
+}
+// the trail after r, taken from r alone: false when one of its five points is no point of its group
+inline bool trail_after(const Record& r, Trail* t) {
+  if (!g1_ok(r.tau_g1, &t->tau1) || !g2_ok(r.tau_g2, &t->tau2) || !g1_ok(r.alpha_g1, &t->alpha1) || !g1_ok(r.beta_g1, &t->beta1) ||
+      !g2_ok(r.beta_g2, &t->beta2))
+    return false;
+  memcpy(t->challenge, r.next_challenge, 64);
+  return true;
+}
+// One record against the trail before it: its points and its key's are points of their groups, a beacon's key is the
+// beacon's, each g2_spx carries the x of its g1_sx, and the record's points are the trail's times those x. On true the
+// trail has moved past the record.
+inline bool verify_record(const Record& r, Trail& t) {
+  pairing::G1 s[3], sx[3];
+  pairing::G2 spx[3], sp[3];
+  Trail next;
+  if (!trail_after(r, &next)) return false;
+  for (int k = 0; k < 3; k++)
+    if (!g1_ok(key_g1_s(r.key, k), &s[k]) || !g1_ok(key_g1_sx(r.key, k), &sx[k]) || !g2_ok(key_g2_spx(r.key, k), &spx[k]))
+      return false;
+  if (r.type == 1) {   // a beacon's secrets are public: g1_s and g1_sx recomputed
+    if (r.num_iterations_exp > p2::kMaxBeaconExp) return false;
+    Secrets bs;
+    beacon_secrets(r.beacon.data(), r.beacon.size(), r.num_iterations_exp, &bs);
+    for (int k = 0; k < 3; k++) {
+      uint8_t want[64];
+      p2::mul_wire<HFq>(bs.g1_s[k], bs.x[k], want);
+      if (memcmp(bs.g1_s[k], key_g1_s(r.key, k), 64) || memcmp(want, key_g1_sx(r.key, k), 64)) return false;
+    }
+  }
+  for (int k = 0; k < 3; k++) {
+    sp[k] = g2_sp(k, t.challenge, key_g1_s(r.key, k), key_g1_sx(r.key, k));
+    if (!pairing::pair_eq(s[k], spx[k], sx[k], sp[k])) return false;   // the same x in g1_sx and g2_spx
+  }
+  if (!pairing::pair_eq(next.tau1, sp[0], t.tau1, spx[0]) || !pairing::pair_eq(next.alpha1, sp[1], t.alpha1, spx[1]) ||
+      !pairing::pair_eq(next.beta1, sp[2], t.beta1, spx[2]))
+    return false;
+  if (!pairing::pair_eq(s[0], next.tau2, sx[0], t.tau2) || !pairing::pair_eq(s[2], next.beta2, sx[2], t.beta2)) return false;
+  t = next;
+  return true;
+}
 // Every record against the one before it (the generators and the fresh challenge before the first); the last record's
 // five points against the file's (T_1, U_1, A_0, B_0, beta2: wire form). On true, *last_response holds the last record's
 // response hash: the caller compares Blake2b(response | hash form of the file's sections 2-6) with its nextChallenge.
 inline bool verify_records(const std::vector<Record>& records, uint32_t power, const uint8_t* T1, const uint8_t* U1,
                            const uint8_t* A0, const uint8_t* B0, const uint8_t* beta2, uint8_t last_response[64]) {
   if (records.empty()) return true;
-  pairing::G1 p_tau1 = host_generator<HFq>(), p_alpha1 = p_tau1, p_beta1 = p_tau1;
-  pairing::G2 p_tau2 = host_generator<HFq2>(), p_beta2 = p_tau2;
-  uint8_t challenge[64];
-  fresh_challenge(power, challenge);
-  for (const Record& r : records) {
-    pairing::G1 tau1, alpha1, beta1, s[3], sx[3];
-    pairing::G2 tau2, beta2p, spx[3], sp[3];
-    if (!g1_ok(r.tau_g1, &tau1) || !g2_ok(r.tau_g2, &tau2) || !g1_ok(r.alpha_g1, &alpha1) || !g1_ok(r.beta_g1, &beta1) ||
-        !g2_ok(r.beta_g2, &beta2p))
-      return false;
-    for (int k = 0; k < 3; k++)
-      if (!g1_ok(key_g1_s(r.key, k), &s[k]) || !g1_ok(key_g1_sx(r.key, k), &sx[k]) || !g2_ok(key_g2_spx(r.key, k), &spx[k]))
-        return false;
-    if (r.type == 1) {   // a beacon's secrets are public: g1_s and g1_sx recomputed
-      if (r.num_iterations_exp > p2::kMaxBeaconExp) return false;
-      Secrets bs;
-      beacon_secrets(r.beacon.data(), r.beacon.size(), r.num_iterations_exp, &bs);
-      for (int k = 0; k < 3; k++) {
-        uint8_t want[64];
-        p2::mul_wire<HFq>(bs.g1_s[k], bs.x[k], want);
-        if (memcmp(bs.g1_s[k], key_g1_s(r.key, k), 64) || memcmp(want, key_g1_sx(r.key, k), 64)) return false;
-      }
-    }
-    for (int k = 0; k < 3; k++) {
-      sp[k] = g2_sp(k, challenge, key_g1_s(r.key, k), key_g1_sx(r.key, k));
-      if (!pairing::pair_eq(s[k], spx[k], sx[k], sp[k])) return false;   // the same x in g1_sx and g2_spx
-    }
-    if (!pairing::pair_eq(tau1, sp[0], p_tau1, spx[0]) || !pairing::pair_eq(alpha1, sp[1], p_alpha1, spx[1]) ||
-        !pairing::pair_eq(beta1, sp[2], p_beta1, spx[2]))
-      return false;
-    if (!pairing::pair_eq(s[0], tau2, sx[0], p_tau2) || !pairing::pair_eq(s[2], beta2p, sx[2], p_beta2)) return false;
-    p_tau1 = tau1;
-    p_alpha1 = alpha1;
-    p_beta1 = beta1;
-    p_tau2 = tau2;
-    p_beta2 = beta2p;
-    memcpy(challenge, r.next_challenge, 64);
-  }
+  Trail t = fresh_trail(power);
+  for (const Record& r : records)
+    if (!verify_record(r, t)) return false;
   const Record& last = records.back();
   if (memcmp(last.tau_g1, T1, 64) || memcmp(last.tau_g2, U1, 128) || memcmp(last.alpha_g1, A0, 64) ||
       memcmp(last.beta_g1, B0, 64) || memcmp(last.beta_g2, beta2, 128))

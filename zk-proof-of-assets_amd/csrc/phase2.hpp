@@ -330,6 +330,32 @@ inline void g2_hash_form(const pairing::G2& p, uint8_t out[128]) {
   fq_to_be(p.y.c1, out + 64);
   fq_to_be(p.y.c0, out + 96);
 }
+// The way back, for the handful of points of a key: hash form -> wire form. False for a coordinate not below q, a set bit
+// 7 in the first byte, or 0x40 followed by anything but zeros; 0x40 then zeros is infinity, the all-zero point.
+inline bool coords_from_hash_form(const uint8_t* in, int coords, const int* order, uint8_t* wire) {
+  if (in[0] & 0x80) return false;
+  if (in[0] == 0x40) {
+    for (int i = 1; i < 32 * coords; i++)
+      if (in[i]) return false;
+    memset(wire, 0, 32 * coords);
+    return true;
+  }
+  for (int c = 0; c < coords; c++) {
+    uint64_t v[4] = {0, 0, 0, 0};
+    for (int i = 0; i < 32; i++) v[3 - i / 8] |= (uint64_t)in[32 * c + i] << (56 - 8 * (i % 8));
+    if (HFq::geq_p(v)) return false;
+    HFq{{v[0], v[1], v[2], v[3]}}.to_mont().to_bytes(wire + 32 * order[c]);
+  }
+  return true;
+}
+inline bool g1_from_hash_form(const uint8_t in[64], uint8_t wire[64]) {
+  static const int order[2] = {0, 1};
+  return coords_from_hash_form(in, 2, order, wire);
+}
+inline bool g2_from_hash_form(const uint8_t in[128], uint8_t wire[128]) {
+  static const int order[4] = {1, 0, 3, 2};   // c1 then c0 -> c0 then c1
+  return coords_from_hash_form(in, 4, order, wire);
+}
 inline void hash_g1_wire(Blake2b& h, const uint8_t* wire) {
   uint8_t b[64];
   g1_hash_form(h_affine_from_bytes<HFq>(wire), b);

@@ -5,6 +5,8 @@
 #include "phase2.hpp"
 #include "setup_common.hip.h"
 
+#include <functional>
+
 namespace {
 
 // Wire form -> hash form. One lane per 32-byte coordinate (two 16 B loads, two 16 B stores): out of Montgomery form,
@@ -151,6 +153,7 @@ struct HashStream {
   double convert_ms = 0, hash_ms = 0;   // host clock: waiting for the device's pieces; hashing
   uint64_t bytes = 0;
   std::vector<uint8_t>* capture = nullptr;   // tests: the hash-form bytes as well
+  std::function<void(const uint8_t*, uint64_t)> sink;   // a command that also writes what it hashes: each piece, in order
   HashStream(zkpoa_context* c, zkpoa::phase2::Blake2b& h, uint64_t piece_points) : ctx(c), hasher(h) {
     if (!piece_points) piece_points = 1ull << 18;
     piece_bytes = piece_points * 128;   // a piece holds piece_points G2 points, or twice as many G1 points
@@ -196,6 +199,7 @@ struct HashStream {
       const auto t1 = std::chrono::steady_clock::now();
       hasher.update(pinned[b], cnt * unit);
       if (capture) capture->insert(capture->end(), pinned[b], pinned[b] + cnt * unit);
+      if (sink) sink(pinned[b], cnt * unit);
       convert_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
       hash_ms += zkpoa::ms_since(t1);
       bytes += cnt * unit;

@@ -118,6 +118,105 @@ void ptau_new(uint32_t power, const char* out_path) {
   fo.commit();
 }
 
+// ---- what `powersoftau contribute / beacon` and `powersoftau challenge contribute` share ---------------------------------
+struct WipeSecrets {
+  p1::Secrets& s;
+  ~WipeSecrets() { wipe(&s, sizeof s); }
+};
+struct WipeScalars {   // the powers of the secrets, on the device
+  DevBuf& k;
+  size_t len;
+  ~WipeScalars() { (void)hipMemset(k.p, 0, len); }
+};
+// tau, alpha, beta and the g1_s of their keys: a beacon's generator (type 1), else secrets_le (NULL: /dev/urandom) and
+// ZKPOA_PHASE1_S ("s_tau,s_alpha,s_beta", the s of g1_s = s * G1) or /dev/urandom
+void draw_secrets(const p2::RecordParams& ap, const uint8_t* secrets_le, const char* what, p1::Secrets* out) {
+  p1::Secrets& sec = *out;
+  if (ap.type == 1) {
+    p1::beacon_secrets(ap.beacon.data(), ap.beacon.size(), ap.num_iterations_exp, &sec);
+  } else {
+    for (int k = 0; k < 3; k++) {
+      if (secrets_le) memcpy(sec.x[k], secrets_le + 32 * k, 32);
+      else random_scalar(sec.x[k]);
+    }
+    uint8_t s[3][32];
+    if (!env_scalars("ZKPOA_PHASE1_S", s, 3, "three numbers in [1, r) separated by commas", "the secrets of the contribution key's g1_s"))
+      for (int k = 0; k < 3; k++) random_scalar(s[k]);
+    uint8_t g1[64];
+    h_affine_to_bytes<HFq>(host_generator<HFq>(), g1);
+    for (int k = 0; k < 3; k++) p2::mul_wire<HFq>(g1, s[k], sec.g1_s[k]);
+    wipe(s, sizeof s);
+  }
+  for (int k = 0; k < 3; k++)
+    if (!scalar_in_range(sec.x[k], true)) throw SetupError(std::string(what) + ": tau, alpha and beta must be in [1, r)");
+}
+// point i of section 2 + t takes first[t] * ratio[t]^i
+struct SectionScalars {
+  uint8_t one[32] = {1};
+  const uint8_t* first[5];
+  const uint8_t* ratio[5];
+  explicit SectionScalars(const p1::Secrets& sec)
+      : first{one, one, sec.x[1], sec.x[2], sec.x[2]}, ratio{sec.x[0], sec.x[0], sec.x[0], sec.x[0], one} {}
+  SectionScalars(const SectionScalars&) = delete;
+};
+// points per piece of a command that streams sections 2-6 through HBM: bytes_per_point of device buffers (what the
+// command allocates per point of a piece) in a quarter of the free HBM, 2 x 128 MiB of pinned read-back buffers at most;
+// from power 20 up no section is ever whole on the host
+constexpr uint64_t kMulBytesPerPoint = 128 + 128 + 32 + 256;   // a piece's points, results, scalars and XYZZ scratch
+uint64_t ptau_piece(zkpoa_context* ctx, uint64_t N, uint64_t bytes_per_point) {
+  constexpr uint64_t kMaxPiece = 1ull << 20;
+  uint64_t piece = (uint64_t)ctx->opt_ptau_piece_points;
+  if (!piece) piece = piece_from_free_hbm(bytes_per_point, 1ull << 12, kMaxPiece);
+  return std::min<uint64_t>(std::min<uint64_t>(piece, kMaxPiece), 2 * N);
+}
+// Read-back: piece p comes back into pinned buffer p & 1 behind the stream's kernels, and a writer thread puts it into
+// the file when its copy has landed -- while the device takes piece p + 1. A buffer is reused when its writer is done.
+struct ReadBack {
+  uint8_t* pinned[2] = {nullptr, nullptr};
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  std::thread writer[2];
+  std::atomic<bool> failed{false};
+  double write_ms[2] = {0, 0};   // each touched by its own writer only
+  explicit ReadBack(size_t bytes) {
+    for (int b = 0; b < 2; b++) {
+      ZK_HIP(hipHostMalloc((void**)&pinned[b], bytes, hipHostMallocDefault));
+      ZK_HIP(hipEventCreateWithFlags(&ev[b], hipEventDisableTiming));
+    }
+  }
+  void wait(int b) {
+    if (writer[b].joinable()) writer[b].join();
+  }
+  // len bytes at d_src, behind what st holds, to byte `at` of section id of fo
+  void send(int b, hipStream_t st, int device, const void* d_src, uint64_t len, SectionFile& fo, uint32_t id, uint64_t at) {
+    wait(b);
+    ZK_HIP(hipMemcpyAsync(pinned[b], d_src, len, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipEventRecord(ev[b], st));
+    writer[b] = std::thread([this, &fo, b, id, at, len, device] {
+      const auto w0 = std::chrono::steady_clock::now();
+      if (hipSetDevice(device) != hipSuccess || hipEventSynchronize(ev[b]) != hipSuccess) {
+        failed = true;
+        return;
+      }
+      fo.put_at(id, at, pinned[b], len);
+      write_ms[b] += ms_since(w0);
+    });
+  }
+  ~ReadBack() {
+    for (int b = 0; b < 2; b++) {
+      wait(b);
+      if (ev[b]) (void)hipEventDestroy(ev[b]);
+      if (pinned[b]) (void)hipHostFree(pinned[b]);
+    }
+  }
+};
+
+struct ReadFd {   // an output is open for writing only: its bytes are read back through a descriptor of their own
+  int fd;
+  ~ReadFd() {
+    if (fd >= 0) close(fd);
+  }
+};
+
 void ptau_contribute(zkpoa_context* ctx, const char* in_path, const char* out_path, const uint8_t* secrets_le, const p2::RecordParams& ap) {
   PhaseTimer phase("powersoftau contribute", 34);
   if (same_file(in_path, out_path)) throw SetupError("powersoftau contribute: the output path names the input file");
@@ -136,82 +235,28 @@ void ptau_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
 
   // ---- the secrets and the key
   p1::Secrets sec;
-  struct WipeSecrets {
-    p1::Secrets& s;
-    ~WipeSecrets() { wipe(&s, sizeof s); }
-  } wipe_sec{sec};
-  if (ap.type == 1) {
-    p1::beacon_secrets(ap.beacon.data(), ap.beacon.size(), ap.num_iterations_exp, &sec);
-  } else {
-    for (int k = 0; k < 3; k++) {
-      if (secrets_le) memcpy(sec.x[k], secrets_le + 32 * k, 32);
-      else random_scalar(sec.x[k]);
-    }
-    uint8_t s[3][32];
-    // ZKPOA_PHASE1_S: "s_tau,s_alpha,s_beta", the s of the key's g1_s = s * G1
-    if (!env_scalars("ZKPOA_PHASE1_S", s, 3, "three numbers in [1, r) separated by commas", "the secrets of the contribution key's g1_s"))
-      for (int k = 0; k < 3; k++) random_scalar(s[k]);
-    uint8_t g1[64];
-    h_affine_to_bytes<HFq>(host_generator<HFq>(), g1);
-    for (int k = 0; k < 3; k++) p2::mul_wire<HFq>(g1, s[k], sec.g1_s[k]);
-    wipe(s, sizeof s);
-  }
-  for (int k = 0; k < 3; k++)
-    if (!scalar_in_range(sec.x[k], true)) throw SetupError("powersoftau contribute: tau, alpha and beta must be in [1, r)");
+  WipeSecrets wipe_sec{sec};
+  draw_secrets(ap, secrets_le, "powersoftau contribute", &sec);
   p1::Record rec;
   static_cast<p2::RecordParams&>(rec) = ap;
   p1::make_key(sec, challenge, rec.key);
   phase("sections, challenge, key");
 
   // ---- pass 1: the new sections, their compressed form into the response hash
-  constexpr uint64_t kMaxPiece = 1ull << 20;   // 2 x 128 MiB of pinned read-back buffers; from power 20 up no section is whole on the host
-  uint64_t piece = (uint64_t)ctx->opt_ptau_piece_points;
-  if (!piece) piece = piece_from_free_hbm(128 + 128 + 32 + 256, 1ull << 12, kMaxPiece);   // a piece's points, results, scalars and XYZZ scratch
-  piece = std::min<uint64_t>(std::min<uint64_t>(piece, kMaxPiece), 2 * N);
+  const uint64_t piece = ptau_piece(ctx, N, kMulBytesPerPoint);
   PtauFile fo(out_path, power, shape.ceremony, ps[7].len + p1::kRecordHead + rec.len());
   hipStream_t st = ctx->dev.lanes[0].stream;
   PointChecker points(ctx);
   const uint64_t slab = (uint64_t)ctx->opt_ptau_mul_slab;
   DevBuf d_in(piece * 128), d_out(piece * 128), d_k(piece * 32), d_flag(64),
       d_scratch(std::max(scalar_mul_each_scratch_g1(piece, slab), scalar_mul_each_scratch_g2(piece, slab)));   // once per command
-  struct WipeScalars {   // the powers of the secrets
-    DevBuf& k;
-    size_t len;
-    ~WipeScalars() { (void)hipMemset(k.p, 0, len); }
-  } wipe_k{d_k, (size_t)piece * 32};
+  WipeScalars wipe_k{d_k, (size_t)piece * 32};
   ZK_HIP(hipMemsetAsync(d_flag.p, 0, 64, st));
   p2::Blake2b resp;
   resp.update(challenge, 64);
-  uint8_t one[32] = {1};
-  // point i of section 2 + t takes first[t] * ratio[t]^i
-  const uint8_t* const first[5] = {one, one, sec.x[1], sec.x[2], sec.x[2]};
-  const uint8_t* const ratio[5] = {sec.x[0], sec.x[0], sec.x[0], sec.x[0], one};
+  const SectionScalars sc(sec);
   double read_ms = 0, compute_ms = 0, hash_ms = 0;
-  // Read-back: piece p comes back into pinned buffer p & 1 behind the stream's kernels, and a writer thread puts it into
-  // the file when its copy has landed -- while the device takes piece p + 1. A buffer is reused when its writer is done.
-  struct ReadBack {
-    uint8_t* pinned[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    std::thread writer[2];
-    std::atomic<bool> failed{false};
-    double write_ms[2] = {0, 0};   // each touched by its own writer only
-    explicit ReadBack(size_t bytes) {
-      for (int b = 0; b < 2; b++) {
-        ZK_HIP(hipHostMalloc((void**)&pinned[b], bytes, hipHostMallocDefault));
-        ZK_HIP(hipEventCreateWithFlags(&ev[b], hipEventDisableTiming));
-      }
-    }
-    void wait(int b) {
-      if (writer[b].joinable()) writer[b].join();
-    }
-    ~ReadBack() {
-      for (int b = 0; b < 2; b++) {
-        wait(b);
-        if (ev[b]) (void)hipEventDestroy(ev[b]);
-        if (pinned[b]) (void)hipHostFree(pinned[b]);
-      }
-    }
-  } rb(piece * 128);
+  ReadBack rb(piece * 128);
   {
     HashStream hs(ctx, resp, 0);
     uint64_t p = 0;
@@ -222,7 +267,7 @@ void ptau_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
         const int b = (int)(p++ & 1);
         auto t0 = std::chrono::steady_clock::now();
         points.require(d_in.p, cnt, j.group, j.group == 2, what.c_str());
-        power_scalars(ctx, first[j.id - 2], ratio[j.id - 2], i0, cnt, d_k.p);
+        power_scalars(ctx, sc.first[j.id - 2], sc.ratio[j.id - 2], i0, cnt, d_k.p);
         if (j.group == 2) scalar_mul_each_g2(ctx, d_in.p, d_k.p, cnt, d_out.p, (uint32_t*)d_flag.p, d_scratch.p, slab);
         else scalar_mul_each_g1(ctx, d_in.p, d_k.p, cnt, d_out.p, (uint32_t*)d_flag.p, d_scratch.p, slab);
         ZK_HIP(hipStreamSynchronize(st));
@@ -230,21 +275,7 @@ void ptau_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
         t0 = std::chrono::steady_clock::now();
         hs.points(d_out.p, cnt, j.group, false, true);
         hash_ms += ms_since(t0);
-        rb.wait(b);
-        ZK_HIP(hipMemcpyAsync(rb.pinned[b], d_out.p, cnt * unit, hipMemcpyDeviceToHost, st));
-        ZK_HIP(hipEventRecord(rb.ev[b], st));
-        const uint32_t id = j.id;
-        const uint64_t at = i0 * unit, len = cnt * unit;
-        const int device = ctx->dev.device;
-        rb.writer[b] = std::thread([&rb, &fo, b, id, at, len, device] {
-          const auto w0 = std::chrono::steady_clock::now();
-          if (hipSetDevice(device) != hipSuccess || hipEventSynchronize(rb.ev[b]) != hipSuccess) {
-            rb.failed = true;
-            return;
-          }
-          fo.put_at(id, at, rb.pinned[b], len);
-          rb.write_ms[b] += ms_since(w0);
-        });
+        rb.send(b, st, ctx->dev.device, d_out.p, cnt * unit, fo, j.id, i0 * unit);
       }, &read_ms);
     }
     rb.wait(0);
@@ -263,12 +294,7 @@ void ptau_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
   resp.final(response);
 
   // ---- pass 2: nextChallenge = Blake2b(response hash | hash form of the new sections 2-6), from the written file
-  struct ReadFd {   // the output is open for writing only: its bytes are read back through a descriptor of their own
-    int fd;
-    ~ReadFd() {
-      if (fd >= 0) close(fd);
-    }
-  } out_r{open(fo.file.tmp.c_str(), O_RDONLY | O_CLOEXEC)};
+  ReadFd out_r{open(fo.file.tmp.c_str(), O_RDONLY | O_CLOEXEC)};
   if (out_r.fd < 0) throw SetupError("powersoftau contribute: cannot read the output back");
   const int out_fd = out_r.fd;
   {
@@ -297,6 +323,273 @@ void ptau_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
     const double ms[4] = {read_ms, compute_ms, hash_ms, write_ms};
     for (int i = 0; i < 4; i++) fprintf(stderr, "zkpoa: %s: %-*s %8.1f ms\n", phase.command, phase.width, what[i], ms[i]);
   }
+  phase("sections 2-7 written, file renamed into place");
+}
+
+// ---- challenge and response files (DESIGN.md "Phase-1 transcript", "Challenge and response files") ----------------------
+// challenge: 64 B (the last response hash) | hash form of sections 2-6;  response: 64 B (the challenge) | compressed form
+// of the new sections 2-6 | the key's nine points in hash form
+uint64_t challenge_file_bytes(uint32_t power) {
+  uint64_t n = 64;
+  for (const PowerSec& sc : ptau_power_secs(power)) n += sc.bytes();
+  return n;
+}
+uint64_t response_file_bytes(uint32_t power) { return 64 + (challenge_file_bytes(power) - 64) / 2 + p1::kKeyLen; }
+
+void verbose_split(const PhaseTimer& phase, std::initializer_list<std::pair<const char*, double>> parts) {
+  if (!phase.verbose) return;
+  for (const auto& p : parts) fprintf(stderr, "zkpoa: %s: %-*s %8.1f ms\n", phase.command, phase.width, p.first, p.second);
+}
+
+// `powersoftau export challenge`: the hash form that a challenge covers, written out as well as hashed
+void ptau_export_challenge(zkpoa_context* ctx, const char* in_path, const char* out_path, uint8_t challenge_hash[64]) {
+  PhaseTimer phase("powersoftau export challenge", 40);
+  if (same_file(in_path, out_path)) throw SetupError("powersoftau export challenge: the output path names the input file");
+  MappedFile fi(in_path);
+  auto ps = bin_sections(fi, "ptau", 1, "ptau");
+  const PtauShape shape = ptau_power_sections(fi, ps);
+  const std::vector<p1::Record> records = p1::parse_section7(fi.p + ps[7].off, ps[7].len);
+  uint8_t want[64], last_response[64];
+  if (records.empty()) {
+    p1::fresh_challenge(shape.power, want);
+    p2::blake2b512("", 0, last_response);
+  } else {
+    memcpy(want, records.back().next_challenge, 64);
+    if (!p1::response_hash(records.back().partial, records.back().key, last_response))
+      throw SetupError("powersoftau export challenge: the last record's partialHash is no Blake2b state");
+  }
+  AtomicFile fo(out_path);
+  fo.reserve(challenge_file_bytes(shape.power));
+  fo.put_at(0, last_response, 64);
+  const uint64_t piece = ptau_piece(ctx, 1ull << shape.power, 128);
+  DevBuf d_piece(piece * 128);
+  p2::Blake2b h;
+  h.update(last_response, 64);
+  double read_ms = 0, write_ms = 0;
+  uint64_t at = 64;
+  phase("sections, records");
+  {
+    HashStream hs(ctx, h, 0);
+    hs.sink = [&](const uint8_t* p, uint64_t len) {
+      const auto t0 = std::chrono::steady_clock::now();
+      fo.put_at(at, p, len);
+      at += len;
+      write_ms += ms_since(t0);
+    };
+    for (const PowerSec& sc : ptau_power_secs(shape.power))
+      for_each_piece(ctx, fi.fd, ps.at(sc.id).off, sc.count, sc.unit(), piece, d_piece.p,
+                     [&](uint64_t, uint64_t cnt) { hs.points(d_piece.p, cnt, sc.group, false); }, &read_ms);
+    verbose_split(phase, {{"read (file -> HBM)", read_ms}, {"convert (waiting for the device)", hs.convert_ms},
+                          {"hash (Blake2b)", hs.hash_ms - write_ms}, {"write (challenge file)", write_ms}});
+  }
+  uint8_t got[64];
+  h.final(got);
+  if (at != challenge_file_bytes(shape.power)) throw SetupError("powersoftau export challenge: internal: the challenge has an unexpected size");
+  if (memcmp(got, want, 64))
+    throw SetupError("powersoftau export challenge: the hash of sections 2-6 is not the file's challenge: they are not the sections "
+                     "its last record describes (a file without records must hold the generators)");
+  fo.commit();
+  if (challenge_hash) memcpy(challenge_hash, got, 64);
+  phase("challenge written, file renamed into place");
+}
+
+// `powersoftau challenge contribute`: `powersoftau contribute` without the ceremony file. The challenge is the hash of
+// the whole input and opens both the response and its hash, so the input is hashed in a pass of its own (host, from the
+// mapping) before the pass that converts, multiplies, compresses, hashes and writes.
+void ptau_challenge_contribute(zkpoa_context* ctx, const char* in_path, const char* out_path, const uint8_t* secrets_le,
+                               uint8_t response_hash[64]) {
+  PhaseTimer phase("powersoftau challenge contribute", 40);
+  if (same_file(in_path, out_path)) throw SetupError("powersoftau challenge contribute: the output path names the input file");
+  MappedFile fi(in_path);
+  uint32_t power = 1;
+  while (power <= 28 && challenge_file_bytes(power) != fi.size) power++;
+  if (power > 28) throw SetupError("powersoftau challenge contribute: a file of " + std::to_string(fi.size) + " bytes is no challenge of a power in [1, 28]");
+  const uint64_t N = 1ull << power;
+  uint8_t challenge[64];
+  {
+    p2::Blake2b h;
+    for (uint64_t done = 0; done < fi.size; done += 64ull << 20) h.update(fi.p + done, std::min<uint64_t>(64ull << 20, fi.size - done));
+    h.final(challenge);
+  }
+  phase("challenge (Blake2b of the input)");
+  p1::Secrets sec;
+  WipeSecrets wipe_sec{sec};
+  draw_secrets(p2::RecordParams{}, secrets_le, "powersoftau challenge contribute", &sec);
+  uint8_t key[p1::kKeyLen];
+  p1::make_key(sec, challenge, key);
+  phase("key");
+
+  const uint64_t piece = ptau_piece(ctx, N, 128 + kMulBytesPerPoint);   // and the piece in hash form
+  AtomicFile fo(out_path);
+  fo.reserve(response_file_bytes(power));
+  fo.put_at(0, challenge, 64);
+  hipStream_t st = ctx->dev.lanes[0].stream;
+  PointChecker points(ctx);
+  FormConverter conv(ctx);
+  const uint64_t slab = (uint64_t)ctx->opt_ptau_mul_slab;
+  DevBuf d_raw(piece * 128), d_in(piece * 128), d_out(piece * 128), d_k(piece * 32), d_flag(64),
+      d_scratch(std::max(scalar_mul_each_scratch_g1(piece, slab), scalar_mul_each_scratch_g2(piece, slab)));
+  WipeScalars wipe_k{d_k, (size_t)piece * 32};
+  ZK_HIP(hipMemsetAsync(d_flag.p, 0, 64, st));
+  p2::Blake2b resp;
+  resp.update(challenge, 64);
+  const SectionScalars sc(sec);
+  double read_ms = 0, convert_ms = 0, compute_ms = 0, hash_ms = 0, write_ms = 0;
+  uint64_t at = 64, in_off = 64;
+  {
+    HashStream hs(ctx, resp, 0);
+    hs.sink = [&](const uint8_t* p, uint64_t len) {
+      const auto t0 = std::chrono::steady_clock::now();
+      fo.put_at(at, p, len);
+      at += len;
+      write_ms += ms_since(t0);
+    };
+    for (const PowerSec& j : ptau_power_secs(power)) {
+      const std::string what = "powersoftau challenge contribute: section " + std::to_string(j.id);
+      for_each_piece(ctx, fi.fd, in_off, j.count, j.unit(), piece, d_raw.p, [&](uint64_t i0, uint64_t cnt) {
+        auto t0 = std::chrono::steady_clock::now();
+        conv.convert(false, j.group, d_raw.p, cnt, d_in.p);
+        conv.require(i0, what.c_str());
+        convert_ms += ms_since(t0);
+        t0 = std::chrono::steady_clock::now();
+        points.require(d_in.p, cnt, j.group, j.group == 2, what.c_str());
+        power_scalars(ctx, sc.first[j.id - 2], sc.ratio[j.id - 2], i0, cnt, d_k.p);
+        if (j.group == 2) scalar_mul_each_g2(ctx, d_in.p, d_k.p, cnt, d_out.p, (uint32_t*)d_flag.p, d_scratch.p, slab);
+        else scalar_mul_each_g1(ctx, d_in.p, d_k.p, cnt, d_out.p, (uint32_t*)d_flag.p, d_scratch.p, slab);
+        ZK_HIP(hipStreamSynchronize(st));
+        compute_ms += ms_since(t0);
+        t0 = std::chrono::steady_clock::now();
+        hs.points(d_out.p, cnt, j.group, false, true);
+        hash_ms += ms_since(t0);
+      }, &read_ms);
+      in_off += j.bytes();
+    }
+  }
+  {
+    uint32_t bad = 0;
+    ZK_HIP(hipMemcpy(&bad, d_flag.p, 4, hipMemcpyDeviceToHost));
+    if (bad) throw SetupError("powersoftau challenge contribute: internal: a scalar was not below r");
+  }
+  uint8_t key_form[p1::kKeyLen];
+  for (int i = 0; i < 6; i++) p2::g1_hash_form(h_affine_from_bytes<HFq>(key + 64 * i), key_form + 64 * i);
+  for (int i = 0; i < 3; i++) p2::g2_hash_form(h_affine_from_bytes<HFq2>(key + 384 + 128 * i), key_form + 384 + 128 * i);
+  resp.update(key_form, sizeof key_form);
+  fo.put_at(at, key_form, sizeof key_form);
+  if (at + sizeof key_form != response_file_bytes(power)) throw SetupError("powersoftau challenge contribute: internal: the response has an unexpected size");
+  uint8_t response[64];
+  resp.final(response);
+  fo.commit();
+  if (response_hash) memcpy(response_hash, response, 64);
+  verbose_split(phase, {{"read (file -> HBM)", read_ms}, {"convert (hash form -> wire form)", convert_ms},
+                        {"compute (checks, scalars, products)", compute_ms}, {"hash (compressed form, Blake2b)", hash_ms - write_ms},
+                        {"write (response file)", write_ms}});
+  phase("response written, file renamed into place");
+}
+
+// `powersoftau import response`: the response's sections decompressed and checked as `prepare phase2` checks points, written
+// as sections 2-6 of the new file; the record from the response's bytes and the new sections; the record checked against
+// the old file's trail as `powersoftau verify` checks a last record. That the sections are powers is left to `verify`.
+void ptau_import_response(zkpoa_context* ctx, const char* old_path, const char* resp_path, const char* new_path,
+                          const p2::RecordParams& ap) {
+  PhaseTimer phase("powersoftau import response", 40);
+  if (same_file(old_path, new_path) || same_file(resp_path, new_path))
+    throw SetupError("powersoftau import response: the output path names an input file");
+  MappedFile fi(old_path);
+  auto ps = bin_sections(fi, "ptau", 1, "ptau");
+  const PtauShape shape = ptau_power_sections(fi, ps);
+  const uint32_t power = shape.power;
+  std::vector<p1::Record> records = p1::parse_section7(fi.p + ps[7].off, ps[7].len);
+  if (ps.count(12) || ps.count(13) || ps.count(14) || ps.count(15))
+    fprintf(stderr, "zkpoa: powersoftau import response: sections 12-15 (Lagrange form) of the input are dropped: they would be stale; "
+                    "run `powersoftau prepare phase2` on the result\n");
+  p1::Trail trail;   // (the fresh challenge is a hash over 2^(power + 2) points: made only for a file without records)
+  if (records.empty()) trail = p1::fresh_trail(power);
+  else if (!p1::trail_after(records.back(), &trail))
+    throw SetupError("powersoftau import response: a point of the old file's last record is not a point of its group");
+  MappedFile fr(resp_path);
+  if (fr.size != response_file_bytes(power))
+    throw SetupError("powersoftau import response: a response to a challenge of power " + std::to_string(power) + " has " +
+                     std::to_string(response_file_bytes(power)) + " bytes, this file has " + std::to_string(fr.size));
+  if (memcmp(fr.p, trail.challenge, 64)) throw SetupError("powersoftau import response: the response answers another challenge than the old file's");
+  p1::Record rec;
+  static_cast<p2::RecordParams&>(rec) = ap;
+  const uint8_t* key_form = fr.p + fr.size - p1::kKeyLen;
+  for (int i = 0; i < 9; i++) {
+    const bool ok = i < 6 ? p2::g1_from_hash_form(key_form + 64 * i, rec.key + 64 * i)
+                          : p2::g2_from_hash_form(key_form + 384 + 128 * (i - 6), rec.key + 384 + 128 * (i - 6));
+    if (!ok) throw SetupError("powersoftau import response: point " + std::to_string(i) + " of the key is not in hash form (a coordinate not below q, or a flag bit)");
+  }
+  phase("old file, response, key");
+
+  // ---- pass 1: the response's sections into the new file; their bytes into the response hash
+  const uint64_t piece = ptau_piece(ctx, 1ull << power, 64 + 128);   // a piece compressed and in wire form
+  PtauFile fo(new_path, power, shape.ceremony, ps[7].len + p1::kRecordHead + rec.len());
+  hipStream_t st = ctx->dev.lanes[0].stream;
+  PointChecker points(ctx);
+  FormConverter conv(ctx);
+  DevBuf d_raw(piece * 64), d_pts(piece * 128);
+  ReadBack rb(piece * 128);
+  p2::Blake2b resp;
+  resp.update(fr.p, 64);
+  double read_ms = 0, decompress_ms = 0, check_ms = 0, hash_ms = 0;
+  uint64_t off = 64, p = 0;
+  for (const PowerSec& j : ptau_power_secs(power)) {
+    const uint64_t unit = j.unit(), in_unit = unit / 2;
+    const std::string what = "powersoftau import response: section " + std::to_string(j.id);
+    for_each_piece(ctx, fr.fd, off, j.count, in_unit, piece, d_raw.p, [&](uint64_t i0, uint64_t cnt) {
+      const int b = (int)(p++ & 1);
+      auto t0 = std::chrono::steady_clock::now();
+      conv.convert(true, j.group, d_raw.p, cnt, d_pts.p);
+      resp.update(fr.p + off + i0 * in_unit, cnt * in_unit);   // the host hashes while the device takes the roots
+      hash_ms += ms_since(t0);
+      t0 = std::chrono::steady_clock::now();
+      conv.require(i0, what.c_str());
+      decompress_ms += ms_since(t0);
+      t0 = std::chrono::steady_clock::now();
+      points.require(d_pts.p, cnt, j.group, j.group == 2, what.c_str());
+      check_ms += ms_since(t0);
+      rb.send(b, st, ctx->dev.device, d_pts.p, cnt * unit, fo, j.id, i0 * unit);
+    }, &read_ms);
+    off += j.count * in_unit;
+  }
+  rb.wait(0);
+  rb.wait(1);
+  if (rb.failed) throw SetupError("powersoftau import response: the read-back of a piece failed");
+  p1::blake2b_save(resp, rec.partial);
+  resp.update(key_form, p1::kKeyLen);
+  uint8_t response[64];
+  resp.final(response);
+
+  // ---- pass 2: nextChallenge from the written sections, as `powersoftau contribute` makes it
+  ReadFd out_r{open(fo.file.tmp.c_str(), O_RDONLY | O_CLOEXEC)};
+  if (out_r.fd < 0) throw SetupError("powersoftau import response: cannot read the output back");
+  {
+    const auto t0 = std::chrono::steady_clock::now();
+    p2::Blake2b next;
+    next.update(response, 64);
+    HashStream hs(ctx, next, 0);
+    hash_form_ptau_sections(ctx, hs, out_r.fd, fo.secs, power, d_pts.p, piece);
+    next.final(rec.next_challenge);
+    hash_ms += ms_since(t0);
+  }
+  auto back = [&](uint32_t sec, uint64_t point, uint64_t unit, uint8_t* dst) {
+    if (pread(out_r.fd, dst, unit, (off_t)(fo.off(sec) + point * unit)) != (ssize_t)unit) throw SetupError("powersoftau import response: cannot read the output back");
+  };
+  back(2, 1, 64, rec.tau_g1);
+  back(3, 1, 128, rec.tau_g2);
+  back(4, 0, 64, rec.alpha_g1);
+  back(5, 0, 64, rec.beta_g1);
+  back(6, 0, 128, rec.beta_g2);
+  if (!p1::verify_record(rec, trail))
+    throw SetupError("powersoftau import response: the record does not verify against the old file: the response's key does not "
+                     "tie its points to the old file's points and challenge");
+  records.push_back(rec);
+  const std::vector<uint8_t> s7 = p1::write_section7(records);
+  fo.put(7, s7.data(), s7.size());
+  fo.commit();
+  verbose_split(phase, {{"read (file -> HBM)", read_ms}, {"decompress (waiting for the device)", decompress_ms},
+                        {"checks (curve, G2 subgroup)", check_ms}, {"hashes (response, nextChallenge)", hash_ms},
+                        {"write (HBM -> file; overlaps the rest)", rb.write_ms[0] + rb.write_ms[1]}});
   phase("sections 2-7 written, file renamed into place");
 }
 
@@ -366,6 +659,33 @@ extern "C" int zkpoa_ptau_beacon(zkpoa_context* ctx, const char* in_path, const 
   ap.num_iterations_exp = num_iterations_exp;
   ap.check("powersoftau beacon");
   ptau_contribute(ctx, in_path, out_path, nullptr, ap);
+  ZK_API_END(ctx)
+}
+
+extern "C" int zkpoa_ptau_export_challenge(zkpoa_context* ctx, const char* ptau_path, const char* challenge_path,
+                                           uint8_t challenge_hash[64]) {
+  ZK_API_BEGIN(ctx)
+  if (!ptau_path || !challenge_path) throw SetupError("powersoftau export challenge: null path");
+  ptau_export_challenge(ctx, ptau_path, challenge_path, challenge_hash);
+  ZK_API_END(ctx)
+}
+
+extern "C" int zkpoa_ptau_challenge_contribute(zkpoa_context* ctx, const char* challenge_path, const char* response_path,
+                                               const uint8_t* secrets_le, uint8_t response_hash[64]) {
+  ZK_API_BEGIN(ctx)
+  if (!challenge_path || !response_path) throw SetupError("powersoftau challenge contribute: null path");
+  ptau_challenge_contribute(ctx, challenge_path, response_path, secrets_le, response_hash);
+  ZK_API_END(ctx)
+}
+
+extern "C" int zkpoa_ptau_import_response(zkpoa_context* ctx, const char* old_path, const char* response_path,
+                                          const char* new_path, const char* name) {
+  ZK_API_BEGIN(ctx)
+  if (!old_path || !response_path || !new_path) throw SetupError("powersoftau import response: null path");
+  p2::RecordParams ap;
+  ap.name = name ? name : "";
+  ap.check("powersoftau import response");
+  ptau_import_response(ctx, old_path, response_path, new_path, ap);
   ZK_API_END(ctx)
 }
 

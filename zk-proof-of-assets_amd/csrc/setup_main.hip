@@ -10,6 +10,9 @@
 //     snarkjs powersoftau new bn128 <power> <out.ptau>            (snarkjs README steps 1-4 and 6: the ceremony file itself,
 //     snarkjs powersoftau contribute <in.ptau> <out.ptau>          which the reference downloads,
 //     snarkjs powersoftau beacon <in> <out> <beaconHash(hex)> <numIterationsExp>   scripts/machine_initialization.sh:377-385)
+//     snarkjs powersoftau export challenge <in.ptau> [challenge]                 (snarkjs README step 5: a contribution by
+//     snarkjs powersoftau challenge contribute bn128 <challenge> [response]       somebody who never holds the ceremony
+//     snarkjs powersoftau import response <old.ptau> <response> <new.ptau>        file)
 // Same three file arguments (the words `zkey new` / `groth16 setup` are accepted and ignored, so the command line
 // can be kept as it is with the executable swapped). The .ptau must be prepared for phase 2, as snarkjs requires too:
 // `zkpoa-setup powersoftau prepare phase2` does that here. Exit status 0 / non-zero + message on stderr.
@@ -73,13 +76,16 @@ static bool delta2_is_gamma2(const char* zkey_path) {
 
 // The commands: the words that select one (a row with no words left over: the three file arguments alone are `zkey new`),
 // its positional arguments, which of them names the file it writes (-1: none), whether it runs in a worker process
-// (csrc/worker_exit.hpp) and whether its last two positionals are a beacon's hex bytes and exponent.
-enum Cmd { kZkeyNew, kZkeyContribute, kZkeyBeacon, kZkeyVerify, kWtnsCheck, kPtauVerify, kPtauPrepare, kPtauNew, kPtauContribute, kPtauBeacon };
+// (csrc/worker_exit.hpp), whether its last two positionals are a beacon's hex bytes and exponent, and the default of a
+// last positional that may be left out.
+enum Cmd { kZkeyNew, kZkeyContribute, kZkeyBeacon, kZkeyVerify, kWtnsCheck, kPtauVerify, kPtauPrepare, kPtauNew, kPtauContribute, kPtauBeacon,
+           kPtauExport, kPtauChallengeContribute, kPtauImport };
 struct Command {
   Cmd cmd;
   const char* words[3];
   int npos, out_pos;
   bool worker, beacon;
+  const char* last_default = nullptr;
 };
 static const Command kCommands[] = {
     {kZkeyBeacon, {"zkey", "beacon"}, 4, 1, true, true},
@@ -90,6 +96,9 @@ static const Command kCommands[] = {
     {kPtauNew, {"powersoftau", "new"}, 3, 2, false, false},
     {kPtauContribute, {"powersoftau", "contribute"}, 2, 1, false, false},
     {kPtauBeacon, {"powersoftau", "beacon"}, 4, 1, false, true},   // the same beacon arguments as `zkey beacon`
+    {kPtauExport, {"powersoftau", "export", "challenge"}, 2, 1, false, false, "challenge"},
+    {kPtauChallengeContribute, {"powersoftau", "challenge", "contribute"}, 3, 2, false, false, "response"},
+    {kPtauImport, {"powersoftau", "import", "response"}, 3, 2, false, false},
     {kWtnsCheck, {"wtns", "check"}, 2, -1, false, false},
     {kZkeyNew, {"zkey", "new"}, 3, 2, true, false},
     {kZkeyNew, {"groth16", "setup"}, 3, 2, true, false},
@@ -124,6 +133,7 @@ int main(int argc, char** argv) {
     if (npos < 4) pos[npos] = argv[i];
     npos++;
   }
+  if (c->last_default && npos == c->npos - 1) pos[npos++] = c->last_default;
   if (npos != c->npos) {
     fprintf(stderr, "usage: zkpoa-setup [zkey new | groth16 setup] <circuit.r1cs> <pot.ptau> <circuit_0.zkey>\n"
                     "         [--transcript]   fill in section 10's circuit hash (needs the ptau's section 2)\n"
@@ -136,7 +146,15 @@ int main(int argc, char** argv) {
                     "       zkpoa-setup powersoftau new bn128 <power> <out.ptau>\n"
                     "       zkpoa-setup powersoftau contribute <in.ptau> <out.ptau> [--name=...]\n"
                     "         (-e=<entropy> is accepted and ignored: the secrets come from /dev/urandom)\n"
-                    "       zkpoa-setup powersoftau beacon <in.ptau> <out.ptau> <beaconHash(hex)> <numIterationsExp> [--name=...]\n");
+                    "       zkpoa-setup powersoftau beacon <in.ptau> <out.ptau> <beaconHash(hex)> <numIterationsExp> [--name=...]\n"
+                    "       zkpoa-setup powersoftau export challenge <in.ptau> [challenge]\n"
+                    "       zkpoa-setup powersoftau challenge contribute bn128 <challenge> [response]\n"
+                    "         (--name=... and -e=... are accepted and ignored)\n"
+                    "       zkpoa-setup powersoftau import response <old.ptau> <response> <new.ptau> [--name=...]\n");
+    return 2;
+  }
+  if (cmd == kPtauChallengeContribute && strcmp(pos[0], "bn128") && strcmp(pos[0], "bn254")) {
+    fprintf(stderr, "zkpoa-setup: powersoftau challenge contribute: the curve must be bn128\n");
     return 2;
   }
   unsigned new_power = 0;
@@ -298,12 +316,22 @@ int main(int argc, char** argv) {
   } else if (cmd == kPtauNew) {
     rc = zkpoa_ptau_new(ctx, new_power, pos[2]);
     if (rc == PROVER_OK) printf("[INFO]  zkpoa: new ceremony file of power %u\n", new_power);
-  } else if (cmd == kPtauContribute || cmd == kPtauBeacon) {
+  } else if (cmd == kPtauExport || cmd == kPtauChallengeContribute) {   // snarkjs logs the hash of the file it wrote
+    uint8_t h[64];
+    if (cmd == kPtauExport) rc = zkpoa_ptau_export_challenge(ctx, pos[0], pos[1], h);
+    else rc = zkpoa_ptau_challenge_contribute(ctx, pos[1], pos[2], nullptr, h);
+    if (rc == PROVER_OK) {
+      char hex[129];
+      for (int i = 0; i < 64; i++) snprintf(hex + 2 * i, 3, "%02x", h[i]);
+      printf("[INFO]  zkpoa: %s hash: %s\n", cmd == kPtauExport ? "challenge" : "response", hex);
+    }
+  } else if (cmd == kPtauContribute || cmd == kPtauBeacon || cmd == kPtauImport) {
     if (cmd == kPtauBeacon) rc = zkpoa_ptau_beacon(ctx, pos[0], pos[1], beacon_bytes, beacon_len, beacon_exp, name);
+    else if (cmd == kPtauImport) rc = zkpoa_ptau_import_response(ctx, pos[0], pos[1], pos[2], name);
     else rc = zkpoa_ptau_contribute(ctx, pos[0], pos[1], nullptr, name);
     if (rc == PROVER_OK) {
       uint32_t n_records = 0;
-      const std::string records = ptau_record_lines(pos[1], &n_records);
+      const std::string records = ptau_record_lines(pos[c->out_pos], &n_records);
       size_t last = records.size() > 1 ? records.rfind('\n', records.size() - 2) : std::string::npos;   // the record just written
       last = last == std::string::npos ? 0 : last + 1;
       printf("[INFO]  zkpoa: contribution #%u: %s", n_records, records.empty() ? "\n" : records.c_str() + last);

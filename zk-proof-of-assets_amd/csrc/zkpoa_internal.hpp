@@ -180,6 +180,17 @@ void scalar_mul_each_g1(zkpoa_context* ctx, const void* d_points, const void* d_
                         void* d_scratch, uint64_t slab);
 void scalar_mul_each_g2(zkpoa_context* ctx, const void* d_points, const void* d_scalars, uint64_t n, void* d_out, uint32_t* d_flags,
                         void* d_scratch, uint64_t slab);
+// ptau_response.hip: hash form (compressed: compressed form) -> wire form on lane 0's stream. convert() enqueues n points
+// of group 1 / 2 from d_bytes into d_out (n x 64 / 128 B); a point that cannot be converted leaves its index and what is
+// wrong with it in `first` (the smallest index of all convert() calls since the last require()). require() synchronises
+// the stream and throws "<what>: point <i0 + index>: <why>" for it.
+struct FormConverter {
+  zkpoa_context* ctx;
+  DevBuf first;
+  explicit FormConverter(zkpoa_context* c);
+  void convert(bool compressed, int group, const void* d_bytes, uint64_t n, void* d_out);
+  void require(uint64_t i0, const char* what);
+};
 // ntt.hip
 // the first use of a size builds its plan and every table (hipMalloc, kernels on st); later calls find it ready
 void ntt_prepare(zkpoa_context* ctx, hipStream_t st, uint32_t k);
