@@ -439,3 +439,39 @@ def test_cli_export_contribute_import_verify(zk, tmp_path):
     assert _cli(zk, tmp_path, "import", "response", new, "response").returncode == 2
     assert _cli(zk, tmp_path, "challenge", "contribute", "bn128").returncode == 2
     assert not (tmp_path / "r2").exists() and _no_leftovers(tmp_path)
+
+
+# what ZKPOA_VERBOSE=1 prints on stderr, per command: (arguments, command name, width of the label column, labels in order)
+VERBOSE = [
+    (("new", "bn128", 2, "0.ptau"), "powersoftau new", 0, []),
+    (("contribute", "0.ptau", "1.ptau", "--name=alice"), "powersoftau contribute", 34,
+     ["sections, challenge, key", "read (file -> HBM)", "compute (checks, scalars, products)",
+      "hashes (response, nextChallenge)", "write (HBM -> file; overlaps the rest)",
+      "sections 2-7 written, file renamed into place"]),
+    (("export", "challenge", "1.ptau", "challenge"), "powersoftau export challenge", 40,
+     ["sections, records", "read (file -> HBM)", "convert (waiting for the device)", "hash (Blake2b)",
+      "write (challenge file)", "challenge written, file renamed into place"]),
+    (("challenge", "contribute", "bn128", "challenge", "response"), "powersoftau challenge contribute", 40,
+     ["challenge (Blake2b of the input)", "key", "read (file -> HBM)", "convert (hash form -> wire form)",
+      "compute (checks, scalars, products)", "hash (compressed form, Blake2b)", "write (response file)",
+      "response written, file renamed into place"]),
+    (("import", "response", "1.ptau", "response", "2.ptau", "--name=bob"), "powersoftau import response", 40,
+     ["old file, response, key", "read (file -> HBM)", "decompress (waiting for the device)", "checks (curve, G2 subgroup)",
+      "hashes (response, nextChallenge)", "write (HBM -> file; overlaps the rest)",
+      "sections 2-7 written, file renamed into place"]),
+]
+
+
+@gpu
+def test_cli_verbose_lines(zk, tmp_path):
+    """Power 2, one process per command: the `zkpoa: <command>: <label>` lines of ZKPOA_VERBOSE, in order, each label
+    padded to the command's column width and followed by " %8.1f ms" (the milliseconds themselves are not compared)."""
+    for args, command, width, labels in VERBOSE:
+        rc = subprocess.run([zk.SETUP_BIN, "powersoftau"] + [str(a) for a in args], cwd=tmp_path, capture_output=True,
+                            text=True, timeout=600, env=dict(os.environ, ZKPOA_VERBOSE="1"))
+        assert rc.returncode == 0, rc.stderr
+        lines = [ln for ln in rc.stderr.splitlines() if ln.startswith("zkpoa: powersoftau ")]
+        assert [ln[:-12] for ln in lines] == ["zkpoa: %s: %s" % (command, what.ljust(width)) for what in labels], rc.stderr
+        for ln in lines:
+            assert ln.endswith(" ms") and ln[-12] == " " and float(ln[-11:-3]) >= 0, ln
+    assert _no_leftovers(tmp_path)

@@ -200,6 +200,23 @@ inline bool trail_after(const Record& r, Trail* t) {
   memcpy(t->challenge, r.next_challenge, 64);
   return true;
 }
+// Where the trail of a file of 2^power with these records stands, the one statement of it: what the last record left,
+// or the fresh file's (whose challenge is a hash over 2^(power + 2) points: made only for a file without records).
+inline void trail_challenge(const std::vector<Record>& records, uint32_t power, uint8_t out[64]) {   // what the next key answers
+  if (records.empty()) fresh_challenge(power, out);
+  else memcpy(out, records.back().next_challenge, 64);
+}
+inline bool trail_end(const std::vector<Record>& records, uint32_t power, Trail* t) {   // false: as trail_after
+  if (!records.empty()) return trail_after(records.back(), t);
+  *t = fresh_trail(power);
+  return true;
+}
+// the response hash that opens a challenge file: Blake2b-512("") before the first record; false: as response_hash
+inline bool trail_response(const std::vector<Record>& records, uint8_t out[64]) {
+  if (!records.empty()) return response_hash(records.back().partial, records.back().key, out);
+  p2::blake2b512("", 0, out);
+  return true;
+}
 // One record against the trail before it: its points and its key's are points of their groups, a beacon's key is the
 // beacon's, each g2_spx carries the x of its g1_sx, and the record's points are the trail's times those x. On true the
 // trail has moved past the record.

@@ -208,15 +208,6 @@ struct HashStream {
   }
 };
 
-// The hash form of sections 2-6 of a ceremony file of 2^power (fd, its section table) into hs's hasher: what a
-// contribution's nextChallenge covers. The sections stream through d_piece (piece_points x 128 B of device memory).
-inline void hash_form_ptau_sections(zkpoa_context* ctx, HashStream& hs, int fd, const std::map<uint32_t, Sec>& ps, uint32_t power,
-                                    void* d_piece, uint64_t piece_points) {
-  for (const PowerSec& sc : ptau_power_secs(power))
-    for_each_piece(ctx, fd, ps.at(sc.id).off, sc.count, sc.unit(), piece_points, d_piece,
-                   [&](uint64_t, uint64_t cnt) { hs.points(d_piece, cnt, sc.group, false); });
-}
-
 // d_out[i] = T[i + n] - T[i] for i < n - 1 (T: the ptau's tau^i G1, at least 2n - 1 points on the device)
 inline void h_diff(zkpoa_context* ctx, const void* d_T, uint64_t n, void* d_out) {
   if (n < 2) return;

@@ -1,23 +1,20 @@
-// `snarkjs powersoftau new / contribute / beacon` on the device: making a ceremony file and extending it by one
-// contribution (DESIGN.md "Phase-1 transcript"; csrc/phase1.hpp holds the record, the key and the host checks).
+// `snarkjs powersoftau new / contribute / beacon / export challenge / challenge contribute / import response` on the
+// device: making a ceremony file, extending it by one contribution, and the same contribution by somebody who never holds
+// the file (DESIGN.md "Phase-1 transcript", "Challenge and response files"; csrc/phase1.hpp: the record, the key, the host
+// checks; csrc/ptau_file.hip.h: the file as it is opened and written; csrc/ptau_response.hip: back into wire form).
 //
 // snarkjs ptau layout, power p, N = 2^p (as csrc/ptau_verify.hip). A contribution with secrets tau, alpha, beta takes
 //   section 2, point i < 2N - 1:  * tau^i        section 3, i < N:  * tau^i
 //   section 4, i < N:  * alpha tau^i             section 5, i < N:  * beta tau^i          section 6:  * beta
-// Every point meets its own full-width scalar. The scalars are made on the device (power_scalars_kernel: first *
-// ratio^(i0 + i), one exponentiation per workgroup, a short one and a chain per thread), the products by
-// scalar_mul_each (csrc/ptau_contribute.hip.h: fixed signed 4-bit windows, every lane of a wave on the same path). The
-// sections stream through HBM in pieces (csrc/setup_common.hip.h: for_each_piece over the rows of ptau_power_secs, the
-// upload through the context's pinned uploader), point checks as `powersoftau prepare phase2` makes them
-// (PointChecker::require), scalars, products, the compressed form of the piece into the response hash
-// (HashStream, double-buffered pinned staging into the one serial Blake2b), read-back into one of two pinned buffers
-// behind the stream's kernels and a writer thread that puts it at its place in the output while the device takes the
-// next piece. A second pass over the written sections makes their hash form for nextChallenge, which starts with the
-// response hash and so cannot share the first pass. A piece is at most 2^20 points: from power 20 up no section is ever
-// whole on the host.
-#include "phase1.hpp"
+// Every point meets its own full-width scalar: made on the device (power_scalars_kernel), multiplied by scalar_mul_each
+// (csrc/ptau_contribute.hip.h). The sections stream through HBM in pieces of at most 2^20 points (for_each_piece of
+// csrc/setup_common.hip.h: from power 20 up no section is ever whole on the host). The four streaming commands are made of
+// the same parts: PtauInput; MulStep (point checks, scalars, products); HashStream (a piece's compressed or hash form into
+// the one serial Blake2b) with HashedWriter where the hashed bytes are the output; ReadBack (a writer thread per pinned
+// buffer puts a piece into the output while the device takes the next); close_record (a second pass over the written
+// sections: nextChallenge starts with the response hash and so cannot share the first) and append_record.
 #include "phase2_dev.hip.h"
-#include "setup_common.hip.h"
+#include "ptau_file.hip.h"
 #include "zkpoa_internal.hpp"
 
 using namespace zkpoa;
@@ -78,26 +75,6 @@ void wipe(void* p, size_t len) {
   for (size_t i = 0; i < len; i++) v[i] = 0;
 }
 
-// a ceremony file of sections 1-7 whose section 7 has len7 bytes, sized, its table and its header (section 1) written
-struct PtauFile : SectionFile {
-  static std::array<uint64_t, 7> lens(uint32_t power, uint64_t len7) {
-    std::array<uint64_t, 7> l{{4 + 32 + 8, 0, 0, 0, 0, 0, len7}};
-    for (const PowerSec& sc : ptau_power_secs(power)) l[sc.id - 1] = sc.bytes();
-    return l;
-  }
-  static constexpr uint32_t kIds[7] = {1, 2, 3, 4, 5, 6, 7};
-  PtauFile(const char* path, uint32_t power, uint32_t ceremony, uint64_t len7)
-      : SectionFile(path, "ptau", kIds, lens(power, len7).data(), 7) {
-    uint8_t s1[44];
-    const uint32_t n8 = 32;
-    memcpy(s1, &n8, 4);
-    memcpy(s1 + 4, HFqParams::P, 32);
-    memcpy(s1 + 36, &power, 4);
-    memcpy(s1 + 40, &ceremony, 4);
-    put(1, s1, 44);
-  }
-};
-
 void ptau_new(uint32_t power, const char* out_path) {
   if (power < 1 || power > 28) throw SetupError("powersoftau new: power " + std::to_string(power) + " is outside [1, 28]");
   PtauFile fo(out_path, power, power, 4);
@@ -118,20 +95,13 @@ void ptau_new(uint32_t power, const char* out_path) {
   fo.commit();
 }
 
-// ---- what `powersoftau contribute / beacon` and `powersoftau challenge contribute` share ---------------------------------
-struct WipeSecrets {
-  p1::Secrets& s;
-  ~WipeSecrets() { wipe(&s, sizeof s); }
-};
-struct WipeScalars {   // the powers of the secrets, on the device
-  DevBuf& k;
-  size_t len;
-  ~WipeScalars() { (void)hipMemset(k.p, 0, len); }
+// ---- the parts the streaming commands are made of ------------------------------------------------------------------------
+struct WipedSecrets : p1::Secrets {   // a command's secrets cannot be held without their wipe
+  ~WipedSecrets() { wipe(static_cast<p1::Secrets*>(this), sizeof(p1::Secrets)); }
 };
 // tau, alpha, beta and the g1_s of their keys: a beacon's generator (type 1), else secrets_le (NULL: /dev/urandom) and
 // ZKPOA_PHASE1_S ("s_tau,s_alpha,s_beta", the s of g1_s = s * G1) or /dev/urandom
-void draw_secrets(const p2::RecordParams& ap, const uint8_t* secrets_le, const char* what, p1::Secrets* out) {
-  p1::Secrets& sec = *out;
+void draw_secrets(const p2::RecordParams& ap, const uint8_t* secrets_le, const char* what, p1::Secrets& sec) {
   if (ap.type == 1) {
     p1::beacon_secrets(ap.beacon.data(), ap.beacon.size(), ap.num_iterations_exp, &sec);
   } else {
@@ -150,25 +120,40 @@ void draw_secrets(const p2::RecordParams& ap, const uint8_t* secrets_le, const c
   for (int k = 0; k < 3; k++)
     if (!scalar_in_range(sec.x[k], true)) throw SetupError(std::string(what) + ": tau, alpha and beta must be in [1, r)");
 }
-// point i of section 2 + t takes first[t] * ratio[t]^i
-struct SectionScalars {
-  uint8_t one[32] = {1};
-  const uint8_t* first[5];
-  const uint8_t* ratio[5];
-  explicit SectionScalars(const p1::Secrets& sec)
-      : first{one, one, sec.x[1], sec.x[2], sec.x[2]}, ratio{sec.x[0], sec.x[0], sec.x[0], sec.x[0], one} {}
-  SectionScalars(const SectionScalars&) = delete;
+constexpr uint64_t kMulBytesPerPoint = 128 + 128 + 32 + 256;   // a piece's points (the caller's), results, scalars and XYZZ scratch
+// The multiply step of a contribution, once per command: point i of section 2 + t times first[t] * ratio[t]^i. The
+// powers of the secrets (d_k) are cleared on the device by the destructor's body, which runs before any member is
+// destroyed: d_k still owns their memory then and is freed after it, on every exit path, exceptions included.
+struct MulStep {
+  zkpoa_context* ctx;
+  const std::string command;
+  const uint64_t slab;
+  PointChecker points;
+  const uint8_t one[32] = {1};
+  const uint8_t *const first[5], *const ratio[5];   // into `one` and the caller's secrets
+  DevBuf d_out, d_flag, d_scratch, d_k;   // a piece's products; the "scalar not below r" word; XYZZ scratch; the scalars
+  const size_t k_bytes;
+  MulStep(zkpoa_context* c, uint64_t piece, const char* cmd, const p1::Secrets& sec)
+      : ctx(c), command(cmd), slab((uint64_t)c->opt_ptau_mul_slab), points(c),
+        first{one, one, sec.x[1], sec.x[2], sec.x[2]}, ratio{sec.x[0], sec.x[0], sec.x[0], sec.x[0], one},
+        d_out(piece * 128), d_flag(64), d_scratch(std::max(scalar_mul_each_scratch(1, piece, slab), scalar_mul_each_scratch(2, piece, slab))),
+        d_k(piece * 32), k_bytes((size_t)piece * 32) {
+    ZK_HIP(hipMemsetAsync(d_flag.p, 0, 64, ctx->dev.lanes[0].stream));
+  }
+  ~MulStep() { (void)hipMemset(d_k.p, 0, k_bytes); }
+  // d_out = the products of the cnt points at d_in (wire form, checked here: `what` names them); the stream is idle on return
+  void run(const PowerSec& j, const void* d_in, uint64_t i0, uint64_t cnt, const char* what) {
+    points.require(d_in, cnt, j.group, j.group == 2, what);
+    power_scalars(ctx, first[j.id - 2], ratio[j.id - 2], i0, cnt, d_k.p);
+    scalar_mul_each(ctx, j.group, d_in, d_k.p, cnt, d_out.p, (uint32_t*)d_flag.p, d_scratch.p, slab);
+    ZK_HIP(hipStreamSynchronize(ctx->dev.lanes[0].stream));
+  }
+  void finish() {   // after the last piece
+    uint32_t bad = 0;
+    ZK_HIP(hipMemcpy(&bad, d_flag.p, 4, hipMemcpyDeviceToHost));
+    if (bad) throw SetupError(command + ": internal: a scalar was not below r");
+  }
 };
-// points per piece of a command that streams sections 2-6 through HBM: bytes_per_point of device buffers (what the
-// command allocates per point of a piece) in a quarter of the free HBM, 2 x 128 MiB of pinned read-back buffers at most;
-// from power 20 up no section is ever whole on the host
-constexpr uint64_t kMulBytesPerPoint = 128 + 128 + 32 + 256;   // a piece's points, results, scalars and XYZZ scratch
-uint64_t ptau_piece(zkpoa_context* ctx, uint64_t N, uint64_t bytes_per_point) {
-  constexpr uint64_t kMaxPiece = 1ull << 20;
-  uint64_t piece = (uint64_t)ctx->opt_ptau_piece_points;
-  if (!piece) piece = piece_from_free_hbm(bytes_per_point, 1ull << 12, kMaxPiece);
-  return std::min<uint64_t>(std::min<uint64_t>(piece, kMaxPiece), 2 * N);
-}
 // Read-back: piece p comes back into pinned buffer p & 1 behind the stream's kernels, and a writer thread puts it into
 // the file when its copy has landed -- while the device takes piece p + 1. A buffer is reused when its writer is done.
 struct ReadBack {
@@ -177,7 +162,9 @@ struct ReadBack {
   std::thread writer[2];
   std::atomic<bool> failed{false};
   double write_ms[2] = {0, 0};   // each touched by its own writer only
-  explicit ReadBack(size_t bytes) {
+  zkpoa_context* ctx;
+  uint64_t sent = 0;
+  ReadBack(zkpoa_context* c, size_t bytes) : ctx(c) {
     for (int b = 0; b < 2; b++) {
       ZK_HIP(hipHostMalloc((void**)&pinned[b], bytes, hipHostMallocDefault));
       ZK_HIP(hipEventCreateWithFlags(&ev[b], hipEventDisableTiming));
@@ -186,8 +173,10 @@ struct ReadBack {
   void wait(int b) {
     if (writer[b].joinable()) writer[b].join();
   }
-  // len bytes at d_src, behind what st holds, to byte `at` of section id of fo
-  void send(int b, hipStream_t st, int device, const void* d_src, uint64_t len, SectionFile& fo, uint32_t id, uint64_t at) {
+  // len bytes at d_src, behind what lane 0's stream holds, to byte `at` of section id of fo
+  void send(const void* d_src, uint64_t len, SectionFile& fo, uint32_t id, uint64_t at) {
+    const int b = (int)(sent++ & 1), device = ctx->dev.device;
+    hipStream_t st = ctx->dev.lanes[0].stream;
     wait(b);
     ZK_HIP(hipMemcpyAsync(pinned[b], d_src, len, hipMemcpyDeviceToHost, st));
     ZK_HIP(hipEventRecord(ev[b], st));
@@ -201,6 +190,11 @@ struct ReadBack {
       write_ms[b] += ms_since(w0);
     });
   }
+  void finish(const std::string& command) {   // after the last piece: every writer done, or the command fails
+    wait(0);
+    wait(1);
+    if (failed) throw SetupError(command + ": the read-back of a piece failed");
+  }
   ~ReadBack() {
     for (int b = 0; b < 2; b++) {
       wait(b);
@@ -210,119 +204,111 @@ struct ReadBack {
   }
 };
 
-struct ReadFd {   // an output is open for writing only: its bytes are read back through a descriptor of their own
-  int fd;
-  ~ReadFd() {
-    if (fd >= 0) close(fd);
+// The record of the sections just written, closed: rec->next_challenge = Blake2b(response hash | hash form of the new
+// sections 2-6) and the record's five points, from the file as written (a second pass through d_piece, piece x 128 B of
+// device memory). An output is open for writing only (AtomicFile): its bytes are read through a descriptor of their own.
+void close_record(zkpoa_context* ctx, const PtauFile& fo, const uint8_t response[64], void* d_piece, uint64_t piece,
+                  const std::string& command, p1::Record* rec) {
+  struct ReadFd {
+    int fd;
+    ~ReadFd() {
+      if (fd >= 0) close(fd);
+    }
+  } out{open(fo.file.tmp.c_str(), O_RDONLY | O_CLOEXEC)};
+  if (out.fd < 0) throw SetupError(command + ": cannot read the output back");
+  p2::Blake2b next;
+  next.update(response, 64);
+  HashStream hs(ctx, next, 0);
+  hash_form_ptau_sections(ctx, hs, out.fd, fo.secs, fo.power, d_piece, piece);
+  next.final(rec->next_challenge);
+  auto back = [&](uint32_t sec, uint64_t point, uint64_t unit, uint8_t* dst) {
+    if (pread(out.fd, dst, unit, (off_t)(fo.off(sec) + point * unit)) != (ssize_t)unit) throw SetupError(command + ": cannot read the output back");
+  };
+  back(2, 1, 64, rec->tau_g1);
+  back(3, 1, 128, rec->tau_g2);
+  back(4, 0, 64, rec->alpha_g1);
+  back(5, 0, 64, rec->beta_g1);
+  back(6, 0, 128, rec->beta_g2);
+}
+// the closed record after the input's, section 7 written, the file renamed into place
+void append_record(PtauFile& fo, std::vector<p1::Record>& records, const p1::Record& rec) {
+  records.push_back(rec);
+  const std::vector<uint8_t> s7 = p1::write_section7(records);
+  fo.put(7, s7.data(), s7.size());
+  fo.commit();
+}
+
+template <class Fn>
+void timed(double& ms, Fn fn) {   // ms += the host's time in fn
+  const auto t0 = std::chrono::steady_clock::now();
+  fn();
+  ms += ms_since(t0);
+}
+void verbose_split(const PhaseTimer& phase, std::initializer_list<std::pair<const char*, double>> parts) {
+  if (!phase.verbose) return;
+  for (const auto& p : parts) fprintf(stderr, "zkpoa: %s: %-*s %8.1f ms\n", phase.command, phase.width, p.first, p.second);
+}
+// A command that also writes what it hashes (HashStream::sink): each hashed piece, in order, at a running offset of fo
+struct HashedWriter {
+  AtomicFile& fo;
+  uint64_t at;
+  double write_ms = 0;   // inside the stream's hash_ms
+  void operator()(const uint8_t* p, uint64_t len) {
+    timed(write_ms, [&] { fo.put_at(at, p, len); });
+    at += len;
   }
 };
 
 void ptau_contribute(zkpoa_context* ctx, const char* in_path, const char* out_path, const uint8_t* secrets_le, const p2::RecordParams& ap) {
   PhaseTimer phase("powersoftau contribute", 34);
   if (same_file(in_path, out_path)) throw SetupError("powersoftau contribute: the output path names the input file");
-  MappedFile fi(in_path);   // mapped for the section table and section 7; the point sections stream with pread
-  auto ps = bin_sections(fi, "ptau", 1, "ptau");
-  const PtauShape shape = ptau_power_sections(fi, ps);
-  const uint32_t power = shape.power;
-  const uint64_t N = 1ull << power;
-  std::vector<p1::Record> records = p1::parse_section7(fi.p + ps[7].off, ps[7].len);
-  if (ps.count(12) || ps.count(13) || ps.count(14) || ps.count(15))
-    fprintf(stderr, "zkpoa: powersoftau contribute: sections 12-15 (Lagrange form) of the input are dropped: they would be stale; "
-                    "run `powersoftau prepare phase2` on the result\n");
+  PtauInput in(in_path);
+  const uint32_t power = in.shape.power;
+  in.warn_lagrange_dropped(phase.command);
   uint8_t challenge[64];
-  if (records.empty()) p1::fresh_challenge(power, challenge);
-  else memcpy(challenge, records.back().next_challenge, 64);
+  p1::trail_challenge(in.records, power, challenge);
 
   // ---- the secrets and the key
-  p1::Secrets sec;
-  WipeSecrets wipe_sec{sec};
-  draw_secrets(ap, secrets_le, "powersoftau contribute", &sec);
-  p1::Record rec;
-  static_cast<p2::RecordParams&>(rec) = ap;
+  WipedSecrets sec;
+  draw_secrets(ap, secrets_le, phase.command, sec);
+  p1::Record rec{ap};
   p1::make_key(sec, challenge, rec.key);
   phase("sections, challenge, key");
 
   // ---- pass 1: the new sections, their compressed form into the response hash
-  const uint64_t piece = ptau_piece(ctx, N, kMulBytesPerPoint);
-  PtauFile fo(out_path, power, shape.ceremony, ps[7].len + p1::kRecordHead + rec.len());
-  hipStream_t st = ctx->dev.lanes[0].stream;
-  PointChecker points(ctx);
-  const uint64_t slab = (uint64_t)ctx->opt_ptau_mul_slab;
-  DevBuf d_in(piece * 128), d_out(piece * 128), d_k(piece * 32), d_flag(64),
-      d_scratch(std::max(scalar_mul_each_scratch_g1(piece, slab), scalar_mul_each_scratch_g2(piece, slab)));   // once per command
-  WipeScalars wipe_k{d_k, (size_t)piece * 32};
-  ZK_HIP(hipMemsetAsync(d_flag.p, 0, 64, st));
+  const uint64_t piece = ptau_piece(ctx, 1ull << power, kMulBytesPerPoint);
+  // fo before rb: rb is destroyed first, and its destructor joins the writer threads, which write into fo -- also when
+  // an exception leaves the piece loop
+  PtauFile fo(out_path, power, in.shape.ceremony, in.ps[7].len + p1::kRecordHead + rec.len());
+  DevBuf d_in(piece * 128);
+  MulStep mul(ctx, piece, phase.command, sec);   // once per command
   p2::Blake2b resp;
   resp.update(challenge, 64);
-  const SectionScalars sc(sec);
   double read_ms = 0, compute_ms = 0, hash_ms = 0;
-  ReadBack rb(piece * 128);
+  ReadBack rb(ctx, piece * 128);
   {
     HashStream hs(ctx, resp, 0);
-    uint64_t p = 0;
     for (const PowerSec& j : ptau_power_secs(power)) {
-      const uint64_t unit = j.unit();
       const std::string what = "ptau section " + std::to_string(j.id);
-      for_each_piece(ctx, fi.fd, ps[j.id].off, j.count, unit, piece, d_in.p, [&](uint64_t i0, uint64_t cnt) {
-        const int b = (int)(p++ & 1);
-        auto t0 = std::chrono::steady_clock::now();
-        points.require(d_in.p, cnt, j.group, j.group == 2, what.c_str());
-        power_scalars(ctx, sc.first[j.id - 2], sc.ratio[j.id - 2], i0, cnt, d_k.p);
-        if (j.group == 2) scalar_mul_each_g2(ctx, d_in.p, d_k.p, cnt, d_out.p, (uint32_t*)d_flag.p, d_scratch.p, slab);
-        else scalar_mul_each_g1(ctx, d_in.p, d_k.p, cnt, d_out.p, (uint32_t*)d_flag.p, d_scratch.p, slab);
-        ZK_HIP(hipStreamSynchronize(st));
-        compute_ms += ms_since(t0);
-        t0 = std::chrono::steady_clock::now();
-        hs.points(d_out.p, cnt, j.group, false, true);
-        hash_ms += ms_since(t0);
-        rb.send(b, st, ctx->dev.device, d_out.p, cnt * unit, fo, j.id, i0 * unit);
+      for_each_piece(ctx, in.f.fd, in.ps[j.id].off, j.count, j.unit(), piece, d_in.p, [&](uint64_t i0, uint64_t cnt) {
+        timed(compute_ms, [&] { mul.run(j, d_in.p, i0, cnt, what.c_str()); });
+        timed(hash_ms, [&] { hs.points(mul.d_out.p, cnt, j.group, false, true); });
+        rb.send(mul.d_out.p, cnt * j.unit(), fo, j.id, i0 * j.unit());
       }, &read_ms);
     }
-    rb.wait(0);
-    rb.wait(1);
-    if (rb.failed) throw SetupError("powersoftau contribute: the read-back of a piece failed");
+    rb.finish(phase.command);
   }
-  const double write_ms = rb.write_ms[0] + rb.write_ms[1];
-  {
-    uint32_t bad = 0;
-    ZK_HIP(hipMemcpy(&bad, d_flag.p, 4, hipMemcpyDeviceToHost));
-    if (bad) throw SetupError("powersoftau contribute: internal: a scalar was not below r");
-  }
+  mul.finish();
   p1::blake2b_save(resp, rec.partial);
   p1::hash_key(resp, rec.key);
   uint8_t response[64];
   resp.final(response);
 
-  // ---- pass 2: nextChallenge = Blake2b(response hash | hash form of the new sections 2-6), from the written file
-  ReadFd out_r{open(fo.file.tmp.c_str(), O_RDONLY | O_CLOEXEC)};
-  if (out_r.fd < 0) throw SetupError("powersoftau contribute: cannot read the output back");
-  const int out_fd = out_r.fd;
-  {
-    auto t0 = std::chrono::steady_clock::now();
-    p2::Blake2b next;
-    next.update(response, 64);
-    HashStream hs(ctx, next, 0);
-    hash_form_ptau_sections(ctx, hs, out_fd, fo.secs, power, d_in.p, piece);
-    next.final(rec.next_challenge);
-    hash_ms += ms_since(t0);
-  }
-  auto back = [&](uint32_t sec, uint64_t point, uint64_t unit, uint8_t* dst) {
-    if (pread(out_fd, dst, unit, (off_t)(fo.off(sec) + point * unit)) != (ssize_t)unit) throw SetupError("powersoftau contribute: cannot read the output back");
-  };
-  back(2, 1, 64, rec.tau_g1);
-  back(3, 1, 128, rec.tau_g2);
-  back(4, 0, 64, rec.alpha_g1);
-  back(5, 0, 64, rec.beta_g1);
-  back(6, 0, 128, rec.beta_g2);
-  records.push_back(rec);
-  const std::vector<uint8_t> s7 = p1::write_section7(records);
-  fo.put(7, s7.data(), s7.size());
-  fo.commit();
-  if (phase.verbose) {
-    const char* what[4] = {"read (file -> HBM)", "compute (checks, scalars, products)", "hashes (response, nextChallenge)", "write (HBM -> file; overlaps the rest)"};
-    const double ms[4] = {read_ms, compute_ms, hash_ms, write_ms};
-    for (int i = 0; i < 4; i++) fprintf(stderr, "zkpoa: %s: %-*s %8.1f ms\n", phase.command, phase.width, what[i], ms[i]);
-  }
+  // ---- pass 2: nextChallenge from the written file, the record, section 7
+  timed(hash_ms, [&] { close_record(ctx, fo, response, d_in.p, piece, phase.command, &rec); });
+  append_record(fo, in.records, rec);
+  verbose_split(phase, {{"read (file -> HBM)", read_ms}, {"compute (checks, scalars, products)", compute_ms},
+                        {"hashes (response, nextChallenge)", hash_ms}, {"write (HBM -> file; overlaps the rest)", rb.write_ms[0] + rb.write_ms[1]}});
   phase("sections 2-7 written, file renamed into place");
 }
 
@@ -336,55 +322,36 @@ uint64_t challenge_file_bytes(uint32_t power) {
 }
 uint64_t response_file_bytes(uint32_t power) { return 64 + (challenge_file_bytes(power) - 64) / 2 + p1::kKeyLen; }
 
-void verbose_split(const PhaseTimer& phase, std::initializer_list<std::pair<const char*, double>> parts) {
-  if (!phase.verbose) return;
-  for (const auto& p : parts) fprintf(stderr, "zkpoa: %s: %-*s %8.1f ms\n", phase.command, phase.width, p.first, p.second);
-}
-
 // `powersoftau export challenge`: the hash form that a challenge covers, written out as well as hashed
 void ptau_export_challenge(zkpoa_context* ctx, const char* in_path, const char* out_path, uint8_t challenge_hash[64]) {
   PhaseTimer phase("powersoftau export challenge", 40);
   if (same_file(in_path, out_path)) throw SetupError("powersoftau export challenge: the output path names the input file");
-  MappedFile fi(in_path);
-  auto ps = bin_sections(fi, "ptau", 1, "ptau");
-  const PtauShape shape = ptau_power_sections(fi, ps);
-  const std::vector<p1::Record> records = p1::parse_section7(fi.p + ps[7].off, ps[7].len);
+  PtauInput in(in_path);
+  const uint32_t power = in.shape.power;
   uint8_t want[64], last_response[64];
-  if (records.empty()) {
-    p1::fresh_challenge(shape.power, want);
-    p2::blake2b512("", 0, last_response);
-  } else {
-    memcpy(want, records.back().next_challenge, 64);
-    if (!p1::response_hash(records.back().partial, records.back().key, last_response))
-      throw SetupError("powersoftau export challenge: the last record's partialHash is no Blake2b state");
-  }
+  p1::trail_challenge(in.records, power, want);
+  if (!p1::trail_response(in.records, last_response))
+    throw SetupError("powersoftau export challenge: the last record's partialHash is no Blake2b state");
   AtomicFile fo(out_path);
-  fo.reserve(challenge_file_bytes(shape.power));
+  fo.reserve(challenge_file_bytes(power));
   fo.put_at(0, last_response, 64);
-  const uint64_t piece = ptau_piece(ctx, 1ull << shape.power, 128);
+  const uint64_t piece = ptau_piece(ctx, 1ull << power, 128);
   DevBuf d_piece(piece * 128);
   p2::Blake2b h;
   h.update(last_response, 64);
-  double read_ms = 0, write_ms = 0;
-  uint64_t at = 64;
+  double read_ms = 0;
+  HashedWriter out{fo, 64};
   phase("sections, records");
   {
     HashStream hs(ctx, h, 0);
-    hs.sink = [&](const uint8_t* p, uint64_t len) {
-      const auto t0 = std::chrono::steady_clock::now();
-      fo.put_at(at, p, len);
-      at += len;
-      write_ms += ms_since(t0);
-    };
-    for (const PowerSec& sc : ptau_power_secs(shape.power))
-      for_each_piece(ctx, fi.fd, ps.at(sc.id).off, sc.count, sc.unit(), piece, d_piece.p,
-                     [&](uint64_t, uint64_t cnt) { hs.points(d_piece.p, cnt, sc.group, false); }, &read_ms);
+    hs.sink = std::ref(out);
+    hash_form_ptau_sections(ctx, hs, in.f.fd, in.ps, power, d_piece.p, piece, &read_ms);
     verbose_split(phase, {{"read (file -> HBM)", read_ms}, {"convert (waiting for the device)", hs.convert_ms},
-                          {"hash (Blake2b)", hs.hash_ms - write_ms}, {"write (challenge file)", write_ms}});
+                          {"hash (Blake2b)", hs.hash_ms - out.write_ms}, {"write (challenge file)", out.write_ms}});
   }
   uint8_t got[64];
   h.final(got);
-  if (at != challenge_file_bytes(shape.power)) throw SetupError("powersoftau export challenge: internal: the challenge has an unexpected size");
+  if (out.at != challenge_file_bytes(power)) throw SetupError("powersoftau export challenge: internal: the challenge has an unexpected size");
   if (memcmp(got, want, 64))
     throw SetupError("powersoftau export challenge: the hash of sections 2-6 is not the file's challenge: they are not the sections "
                      "its last record describes (a file without records must hold the generators)");
@@ -404,7 +371,6 @@ void ptau_challenge_contribute(zkpoa_context* ctx, const char* in_path, const ch
   uint32_t power = 1;
   while (power <= 28 && challenge_file_bytes(power) != fi.size) power++;
   if (power > 28) throw SetupError("powersoftau challenge contribute: a file of " + std::to_string(fi.size) + " bytes is no challenge of a power in [1, 28]");
-  const uint64_t N = 1ull << power;
   uint8_t challenge[64];
   {
     p2::Blake2b h;
@@ -412,77 +378,54 @@ void ptau_challenge_contribute(zkpoa_context* ctx, const char* in_path, const ch
     h.final(challenge);
   }
   phase("challenge (Blake2b of the input)");
-  p1::Secrets sec;
-  WipeSecrets wipe_sec{sec};
-  draw_secrets(p2::RecordParams{}, secrets_le, "powersoftau challenge contribute", &sec);
+  WipedSecrets sec;
+  draw_secrets(p2::RecordParams{}, secrets_le, phase.command, sec);
   uint8_t key[p1::kKeyLen];
   p1::make_key(sec, challenge, key);
   phase("key");
 
-  const uint64_t piece = ptau_piece(ctx, N, 128 + kMulBytesPerPoint);   // and the piece in hash form
+  const uint64_t piece = ptau_piece(ctx, 1ull << power, 128 + kMulBytesPerPoint);   // and the piece in hash form
   AtomicFile fo(out_path);
   fo.reserve(response_file_bytes(power));
   fo.put_at(0, challenge, 64);
-  hipStream_t st = ctx->dev.lanes[0].stream;
-  PointChecker points(ctx);
   FormConverter conv(ctx);
-  const uint64_t slab = (uint64_t)ctx->opt_ptau_mul_slab;
-  DevBuf d_raw(piece * 128), d_in(piece * 128), d_out(piece * 128), d_k(piece * 32), d_flag(64),
-      d_scratch(std::max(scalar_mul_each_scratch_g1(piece, slab), scalar_mul_each_scratch_g2(piece, slab)));
-  WipeScalars wipe_k{d_k, (size_t)piece * 32};
-  ZK_HIP(hipMemsetAsync(d_flag.p, 0, 64, st));
+  DevBuf d_raw(piece * 128), d_in(piece * 128);
+  MulStep mul(ctx, piece, phase.command, sec);
   p2::Blake2b resp;
   resp.update(challenge, 64);
-  const SectionScalars sc(sec);
-  double read_ms = 0, convert_ms = 0, compute_ms = 0, hash_ms = 0, write_ms = 0;
-  uint64_t at = 64, in_off = 64;
+  double read_ms = 0, convert_ms = 0, compute_ms = 0, hash_ms = 0;
+  HashedWriter out{fo, 64};
+  uint64_t in_off = 64;
   {
     HashStream hs(ctx, resp, 0);
-    hs.sink = [&](const uint8_t* p, uint64_t len) {
-      const auto t0 = std::chrono::steady_clock::now();
-      fo.put_at(at, p, len);
-      at += len;
-      write_ms += ms_since(t0);
-    };
+    hs.sink = std::ref(out);
     for (const PowerSec& j : ptau_power_secs(power)) {
       const std::string what = "powersoftau challenge contribute: section " + std::to_string(j.id);
       for_each_piece(ctx, fi.fd, in_off, j.count, j.unit(), piece, d_raw.p, [&](uint64_t i0, uint64_t cnt) {
-        auto t0 = std::chrono::steady_clock::now();
-        conv.convert(false, j.group, d_raw.p, cnt, d_in.p);
-        conv.require(i0, what.c_str());
-        convert_ms += ms_since(t0);
-        t0 = std::chrono::steady_clock::now();
-        points.require(d_in.p, cnt, j.group, j.group == 2, what.c_str());
-        power_scalars(ctx, sc.first[j.id - 2], sc.ratio[j.id - 2], i0, cnt, d_k.p);
-        if (j.group == 2) scalar_mul_each_g2(ctx, d_in.p, d_k.p, cnt, d_out.p, (uint32_t*)d_flag.p, d_scratch.p, slab);
-        else scalar_mul_each_g1(ctx, d_in.p, d_k.p, cnt, d_out.p, (uint32_t*)d_flag.p, d_scratch.p, slab);
-        ZK_HIP(hipStreamSynchronize(st));
-        compute_ms += ms_since(t0);
-        t0 = std::chrono::steady_clock::now();
-        hs.points(d_out.p, cnt, j.group, false, true);
-        hash_ms += ms_since(t0);
+        timed(convert_ms, [&] {
+          conv.convert(false, j.group, d_raw.p, cnt, d_in.p);
+          conv.require(i0, what.c_str());
+        });
+        timed(compute_ms, [&] { mul.run(j, d_in.p, i0, cnt, what.c_str()); });
+        timed(hash_ms, [&] { hs.points(mul.d_out.p, cnt, j.group, false, true); });
       }, &read_ms);
       in_off += j.bytes();
     }
   }
-  {
-    uint32_t bad = 0;
-    ZK_HIP(hipMemcpy(&bad, d_flag.p, 4, hipMemcpyDeviceToHost));
-    if (bad) throw SetupError("powersoftau challenge contribute: internal: a scalar was not below r");
-  }
+  mul.finish();
   uint8_t key_form[p1::kKeyLen];
   for (int i = 0; i < 6; i++) p2::g1_hash_form(h_affine_from_bytes<HFq>(key + 64 * i), key_form + 64 * i);
   for (int i = 0; i < 3; i++) p2::g2_hash_form(h_affine_from_bytes<HFq2>(key + 384 + 128 * i), key_form + 384 + 128 * i);
   resp.update(key_form, sizeof key_form);
-  fo.put_at(at, key_form, sizeof key_form);
-  if (at + sizeof key_form != response_file_bytes(power)) throw SetupError("powersoftau challenge contribute: internal: the response has an unexpected size");
+  fo.put_at(out.at, key_form, sizeof key_form);
+  if (out.at + sizeof key_form != response_file_bytes(power)) throw SetupError("powersoftau challenge contribute: internal: the response has an unexpected size");
   uint8_t response[64];
   resp.final(response);
   fo.commit();
   if (response_hash) memcpy(response_hash, response, 64);
   verbose_split(phase, {{"read (file -> HBM)", read_ms}, {"convert (hash form -> wire form)", convert_ms},
-                        {"compute (checks, scalars, products)", compute_ms}, {"hash (compressed form, Blake2b)", hash_ms - write_ms},
-                        {"write (response file)", write_ms}});
+                        {"compute (checks, scalars, products)", compute_ms}, {"hash (compressed form, Blake2b)", hash_ms - out.write_ms},
+                        {"write (response file)", out.write_ms}});
   phase("response written, file renamed into place");
 }
 
@@ -494,25 +437,18 @@ void ptau_import_response(zkpoa_context* ctx, const char* old_path, const char* 
   PhaseTimer phase("powersoftau import response", 40);
   if (same_file(old_path, new_path) || same_file(resp_path, new_path))
     throw SetupError("powersoftau import response: the output path names an input file");
-  MappedFile fi(old_path);
-  auto ps = bin_sections(fi, "ptau", 1, "ptau");
-  const PtauShape shape = ptau_power_sections(fi, ps);
-  const uint32_t power = shape.power;
-  std::vector<p1::Record> records = p1::parse_section7(fi.p + ps[7].off, ps[7].len);
-  if (ps.count(12) || ps.count(13) || ps.count(14) || ps.count(15))
-    fprintf(stderr, "zkpoa: powersoftau import response: sections 12-15 (Lagrange form) of the input are dropped: they would be stale; "
-                    "run `powersoftau prepare phase2` on the result\n");
-  p1::Trail trail;   // (the fresh challenge is a hash over 2^(power + 2) points: made only for a file without records)
-  if (records.empty()) trail = p1::fresh_trail(power);
-  else if (!p1::trail_after(records.back(), &trail))
+  PtauInput in(old_path);
+  const uint32_t power = in.shape.power;
+  in.warn_lagrange_dropped(phase.command);
+  p1::Trail trail;
+  if (!p1::trail_end(in.records, power, &trail))
     throw SetupError("powersoftau import response: a point of the old file's last record is not a point of its group");
   MappedFile fr(resp_path);
   if (fr.size != response_file_bytes(power))
     throw SetupError("powersoftau import response: a response to a challenge of power " + std::to_string(power) + " has " +
                      std::to_string(response_file_bytes(power)) + " bytes, this file has " + std::to_string(fr.size));
   if (memcmp(fr.p, trail.challenge, 64)) throw SetupError("powersoftau import response: the response answers another challenge than the old file's");
-  p1::Record rec;
-  static_cast<p2::RecordParams&>(rec) = ap;
+  p1::Record rec{ap};
   const uint8_t* key_form = fr.p + fr.size - p1::kKeyLen;
   for (int i = 0; i < 9; i++) {
     const bool ok = i < 6 ? p2::g1_from_hash_form(key_form + 64 * i, rec.key + 64 * i)
@@ -523,74 +459,54 @@ void ptau_import_response(zkpoa_context* ctx, const char* old_path, const char* 
 
   // ---- pass 1: the response's sections into the new file; their bytes into the response hash
   const uint64_t piece = ptau_piece(ctx, 1ull << power, 64 + 128);   // a piece compressed and in wire form
-  PtauFile fo(new_path, power, shape.ceremony, ps[7].len + p1::kRecordHead + rec.len());
-  hipStream_t st = ctx->dev.lanes[0].stream;
+  PtauFile fo(new_path, power, in.shape.ceremony, in.ps[7].len + p1::kRecordHead + rec.len());   // before rb, as in ptau_contribute
   PointChecker points(ctx);
   FormConverter conv(ctx);
   DevBuf d_raw(piece * 64), d_pts(piece * 128);
-  ReadBack rb(piece * 128);
+  ReadBack rb(ctx, piece * 128);
   p2::Blake2b resp;
   resp.update(fr.p, 64);
   double read_ms = 0, decompress_ms = 0, check_ms = 0, hash_ms = 0;
-  uint64_t off = 64, p = 0;
+  uint64_t off = 64;
   for (const PowerSec& j : ptau_power_secs(power)) {
     const uint64_t unit = j.unit(), in_unit = unit / 2;
     const std::string what = "powersoftau import response: section " + std::to_string(j.id);
     for_each_piece(ctx, fr.fd, off, j.count, in_unit, piece, d_raw.p, [&](uint64_t i0, uint64_t cnt) {
-      const int b = (int)(p++ & 1);
-      auto t0 = std::chrono::steady_clock::now();
-      conv.convert(true, j.group, d_raw.p, cnt, d_pts.p);
-      resp.update(fr.p + off + i0 * in_unit, cnt * in_unit);   // the host hashes while the device takes the roots
-      hash_ms += ms_since(t0);
-      t0 = std::chrono::steady_clock::now();
-      conv.require(i0, what.c_str());
-      decompress_ms += ms_since(t0);
-      t0 = std::chrono::steady_clock::now();
-      points.require(d_pts.p, cnt, j.group, j.group == 2, what.c_str());
-      check_ms += ms_since(t0);
-      rb.send(b, st, ctx->dev.device, d_pts.p, cnt * unit, fo, j.id, i0 * unit);
+      timed(hash_ms, [&] {
+        conv.convert(true, j.group, d_raw.p, cnt, d_pts.p);
+        resp.update(fr.p + off + i0 * in_unit, cnt * in_unit);   // the host hashes while the device takes the roots
+      });
+      timed(decompress_ms, [&] { conv.require(i0, what.c_str()); });
+      timed(check_ms, [&] { points.require(d_pts.p, cnt, j.group, j.group == 2, what.c_str()); });
+      rb.send(d_pts.p, cnt * unit, fo, j.id, i0 * unit);
     }, &read_ms);
     off += j.count * in_unit;
   }
-  rb.wait(0);
-  rb.wait(1);
-  if (rb.failed) throw SetupError("powersoftau import response: the read-back of a piece failed");
+  rb.finish(phase.command);
   p1::blake2b_save(resp, rec.partial);
   resp.update(key_form, p1::kKeyLen);
   uint8_t response[64];
   resp.final(response);
 
-  // ---- pass 2: nextChallenge from the written sections, as `powersoftau contribute` makes it
-  ReadFd out_r{open(fo.file.tmp.c_str(), O_RDONLY | O_CLOEXEC)};
-  if (out_r.fd < 0) throw SetupError("powersoftau import response: cannot read the output back");
-  {
-    const auto t0 = std::chrono::steady_clock::now();
-    p2::Blake2b next;
-    next.update(response, 64);
-    HashStream hs(ctx, next, 0);
-    hash_form_ptau_sections(ctx, hs, out_r.fd, fo.secs, power, d_pts.p, piece);
-    next.final(rec.next_challenge);
-    hash_ms += ms_since(t0);
-  }
-  auto back = [&](uint32_t sec, uint64_t point, uint64_t unit, uint8_t* dst) {
-    if (pread(out_r.fd, dst, unit, (off_t)(fo.off(sec) + point * unit)) != (ssize_t)unit) throw SetupError("powersoftau import response: cannot read the output back");
-  };
-  back(2, 1, 64, rec.tau_g1);
-  back(3, 1, 128, rec.tau_g2);
-  back(4, 0, 64, rec.alpha_g1);
-  back(5, 0, 64, rec.beta_g1);
-  back(6, 0, 128, rec.beta_g2);
+  // ---- pass 2: nextChallenge from the written sections, as `powersoftau contribute` makes it; the record against the trail
+  timed(hash_ms, [&] { close_record(ctx, fo, response, d_pts.p, piece, phase.command, &rec); });
   if (!p1::verify_record(rec, trail))
     throw SetupError("powersoftau import response: the record does not verify against the old file: the response's key does not "
                      "tie its points to the old file's points and challenge");
-  records.push_back(rec);
-  const std::vector<uint8_t> s7 = p1::write_section7(records);
-  fo.put(7, s7.data(), s7.size());
-  fo.commit();
+  append_record(fo, in.records, rec);
   verbose_split(phase, {{"read (file -> HBM)", read_ms}, {"decompress (waiting for the device)", decompress_ms},
                         {"checks (curve, G2 subgroup)", check_ms}, {"hashes (response, nextChallenge)", hash_ms},
                         {"write (HBM -> file; overlaps the rest)", rb.write_ms[0] + rb.write_ms[1]}});
   phase("sections 2-7 written, file renamed into place");
+}
+
+// a command's record parameters from its --name and, for a beacon (type 1), its bytes and exponent: checked once, whole
+// (RecordParams::check throws "<command>: ...")
+p2::RecordParams record_params(const char* command, const char* name, uint32_t type = 0, const uint8_t* beacon = nullptr,
+                               unsigned long beacon_len = 0, uint32_t num_iterations_exp = 0) {
+  p2::RecordParams ap{type, name ? name : "", {beacon, beacon + beacon_len}, num_iterations_exp};
+  ap.check(command);
+  return ap;
 }
 
 }  // namespace
@@ -601,10 +517,9 @@ extern "C" int zkpoa_scalar_mul_each_device(zkpoa_context* ctx, int group, const
   if (group != 1 && group != 2) throw SetupError("scalar_mul_each: group must be 1 (G1) or 2 (G2)");
   if (n && (!d_points || !d_scalars || !d_out)) throw SetupError("scalar_mul_each: null pointer");
   const uint64_t slab = (uint64_t)ctx->opt_ptau_mul_slab;
-  DevBuf flag(64), scratch(group == 2 ? scalar_mul_each_scratch_g2(n, slab) : scalar_mul_each_scratch_g1(n, slab));
+  DevBuf flag(64), scratch(scalar_mul_each_scratch(group, n, slab));
   ZK_HIP(hipMemsetAsync(flag.p, 0, 64, ctx->dev.lanes[0].stream));
-  if (group == 2) scalar_mul_each_g2(ctx, d_points, d_scalars, n, d_out, (uint32_t*)flag.p, scratch.p, slab);
-  else scalar_mul_each_g1(ctx, d_points, d_scalars, n, d_out, (uint32_t*)flag.p, scratch.p, slab);
+  scalar_mul_each(ctx, group, d_points, d_scalars, n, d_out, (uint32_t*)flag.p, scratch.p, slab);
   ZK_HIP(hipStreamSynchronize(ctx->dev.lanes[0].stream));
   ZK_HIP(hipGetLastError());
   uint32_t bad = 0;
@@ -641,10 +556,7 @@ extern "C" int zkpoa_ptau_contribute(zkpoa_context* ctx, const char* in_path, co
                                      const char* name) {
   ZK_API_BEGIN(ctx)
   if (!in_path || !out_path) throw SetupError("powersoftau contribute: null path");
-  p2::RecordParams ap;
-  ap.name = name ? name : "";
-  ap.check("powersoftau contribute");
-  ptau_contribute(ctx, in_path, out_path, secrets_le, ap);
+  ptau_contribute(ctx, in_path, out_path, secrets_le, record_params("powersoftau contribute", name));
   ZK_API_END(ctx)
 }
 
@@ -652,13 +564,7 @@ extern "C" int zkpoa_ptau_beacon(zkpoa_context* ctx, const char* in_path, const 
                                  unsigned long beacon_len, uint32_t num_iterations_exp, const char* name) {
   ZK_API_BEGIN(ctx)
   if (!in_path || !out_path || (!beacon && beacon_len)) throw SetupError("powersoftau beacon: null argument");
-  p2::RecordParams ap;
-  ap.type = 1;
-  ap.name = name ? name : "";
-  ap.beacon.assign(beacon, beacon + beacon_len);
-  ap.num_iterations_exp = num_iterations_exp;
-  ap.check("powersoftau beacon");
-  ptau_contribute(ctx, in_path, out_path, nullptr, ap);
+  ptau_contribute(ctx, in_path, out_path, nullptr, record_params("powersoftau beacon", name, 1, beacon, beacon_len, num_iterations_exp));
   ZK_API_END(ctx)
 }
 
@@ -682,10 +588,7 @@ extern "C" int zkpoa_ptau_import_response(zkpoa_context* ctx, const char* old_pa
                                           const char* new_path, const char* name) {
   ZK_API_BEGIN(ctx)
   if (!old_path || !response_path || !new_path) throw SetupError("powersoftau import response: null path");
-  p2::RecordParams ap;
-  ap.name = name ? name : "";
-  ap.check("powersoftau import response");
-  ptau_import_response(ctx, old_path, response_path, new_path, ap);
+  ptau_import_response(ctx, old_path, response_path, new_path, record_params("powersoftau import response", name));
   ZK_API_END(ctx)
 }
 

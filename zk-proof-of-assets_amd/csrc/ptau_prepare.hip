@@ -12,7 +12,7 @@
 // streaming a level through HBM in pieces is not done. Sections 1-7 are copied byte for byte, sections 12-15 of the
 // input, if any, are ignored; the output (csrc/setup_common.hip.h: SectionFile, 11 sections in the order 1-7, 12-15)
 // appears under its name only when it is complete.
-#include "setup_common.hip.h"
+#include "ptau_file.hip.h"
 #include "zkpoa_internal.hpp"
 
 #include <memory>
@@ -24,14 +24,12 @@ namespace {
 void ptau_prepare(zkpoa_context* ctx, const char* in_path, const char* out_path, uint32_t info[4]) {
   PhaseTimer phase("powersoftau prepare phase2", 34);
   if (same_file(in_path, out_path)) throw SetupError("powersoftau prepare phase2: the output path names the input file");
-  MappedFile fp(in_path);   // mapped for the section table and the copy of sections 1-7; the sources stream with pread
-  auto ps = bin_sections(fp, "ptau", 1, "ptau");
-  if (ps.count(1)) ptau_check_preparable(ptau_header(fp, ps[1]));   // before the lengths: no file of power 28 need exist
-  const PtauShape shape = ptau_power_sections(fp, ps);
+  PtauInput in(in_path, false, true);   // section 7 is copied unread; the power is checked before the lengths
+  auto& [fp, ps, shape, records] = in;
   const uint32_t p = shape.power;
   info[0] = p;
   info[1] = shape.ceremony;
-  info[2] = ps.count(12) && ps.count(13) && ps.count(14) && ps.count(15) ? 1 : 0;
+  info[2] = in.lagrange() == PtauInput::kAll ? 1 : 0;
   info[3] = shape.contributions;
   const auto jobs = ptau_lagrange_secs(p);
   auto src_bytes = [](const LagrangeSec& j) { return j.unit() << j.top; };   // section 2: with its infinity

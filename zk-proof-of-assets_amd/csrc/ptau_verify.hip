@@ -16,13 +16,12 @@
 //     the 2N - 1 powers that exist (u_{2N-1} = 0, P(x) = (1 - (rho x)^(2N-1)) / (1 - rho x)).
 // The weights are made on the device per piece (power tables by thread runs; the Lagrange side's 1 / (1 - rho w^j) by a
 // batched inversion, Montgomery's trick per thread run). Each section streams through HBM in pieces
-// (csrc/setup_common.hip.h: for_each_piece; the sections' point counts: csrc/binfile.hpp): upload from the file, point checks (curve, range, G2 subgroup), MSMs with the piece's weights; the partial sums are added on the host.
+// (csrc/setup_common.hip.h: for_each_piece; the file as it is opened: csrc/ptau_file.hip.h; the sections' point counts: csrc/binfile.hpp): upload from the file, point checks (curve, range, G2 subgroup), MSMs with the piece's weights; the partial sums are added on the host.
 // Section 7 (DESIGN.md "Phase-1 transcript"): its records are checked on the host (csrc/phase1.hpp: keys, ratios, the
 // beacon, the last record against the file's points); the last nextChallenge needs the hash form of sections 2-6, which
 // streams from the file through the device conversion of csrc/phase2_dev.hip.h into Blake2b.
-#include "phase1.hpp"
 #include "phase2_dev.hip.h"
-#include "setup_common.hip.h"
+#include "ptau_file.hip.h"
 #include "zkpoa_internal.hpp"
 
 #include <type_traits>
@@ -209,14 +208,12 @@ HFr draw_nonzero() {   // 253 random bits from /dev/urandom (below r), Montgomer
 uint32_t ptau_verify(zkpoa_context* ctx, const char* path, uint64_t piece_points, uint32_t info[4]) {
   PhaseTimer phase("powersoftau verify", 34);
   // ---- the file's shape: anything that contradicts the header is a malformed file
-  MappedFile fp(path);   // mapped for the section table and a few single points; the sections stream with pread
-  auto ps = bin_sections(fp, "ptau", 1, "ptau");
-  const PtauShape shape = ptau_power_sections(fp, ps);
+  PtauInput in(path, false);   // the records: after the checks of sections 12-15
+  auto& [fp, ps, shape, records] = in;
   const uint32_t power = shape.power;
   const uint64_t N = 1ull << power;
-  const int n_lag = (int)ps.count(12) + (int)ps.count(13) + (int)ps.count(14) + (int)ps.count(15);
-  if (n_lag != 0 && n_lag != 4) throw SetupError("ptau: only some of sections 12-15 (Lagrange form) are present");
-  const bool prepared = n_lag == 4;
+  if (in.lagrange() == PtauInput::kSome) throw SetupError("ptau: only some of sections 12-15 (Lagrange form) are present");
+  const bool prepared = in.lagrange() == PtauInput::kAll;
   if (prepared) {
     ptau_check_preparable(power);
     for (const LagrangeSec& sc : ptau_lagrange_secs(power))
@@ -226,7 +223,7 @@ uint32_t ptau_verify(zkpoa_context* ctx, const char* path, uint64_t piece_points
   info[1] = shape.ceremony;
   info[2] = prepared ? 1 : 0;
   info[3] = shape.contributions;
-  const std::vector<zkpoa::phase1::Record> records = zkpoa::phase1::parse_section7(fp.p + ps[7].off, ps[7].len);
+  in.parse_records();
   phase("sections");
 
   // ---- random weights: one rho per power section (ratio checks), one rho_l per level (Lagrange checks)

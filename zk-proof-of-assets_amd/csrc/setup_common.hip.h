@@ -1,13 +1,13 @@
-// What the file commands of csrc/setup.hip (`zkey new`, `zkey contribute`, `wtns check`), csrc/zkey_verify.hip
-// (`zkey verify`), csrc/ptau_verify.hip (`powersoftau verify`), csrc/ptau_prepare.hip (`powersoftau prepare phase2`) and
-// csrc/ptau_contribute.hip (`powersoftau new / contribute / beacon`) share: mapped files and their section tables (the
-// scan itself and the point sections of a ceremony file: binfile.hpp), the ptau header and the shape of its power
-// sections, the scalars a command draws or takes from the environment (scalar_in_range, random_scalar, env_scalars over
-// parse_u256.hpp), output files that appear only when complete (AtomicFile) and whose sections are placed in any order
-// (SectionFile), the ZKPOA_VERBOSE phase timer, host threads and arrays, the r1cs parser and its CSR, the ptau ranges a
-// key is made from, the constraint-fold kernels, the piece loop that streams a section from its file through HBM
-// (for_each_piece, piece_from_free_hbm), and the device passes that check the points of a section (curve, range, G2
-// subgroup: PointChecker). Internal linkage: each translation unit has its own copy.
+// What the file commands of csrc/setup.hip (`zkey new`, `zkey contribute`, `wtns check`), csrc/zkey_verify.hip (`zkey
+// verify`), csrc/ptau_verify.hip (`powersoftau verify`), csrc/ptau_prepare.hip (`powersoftau prepare phase2`) and
+// csrc/ptau_contribute.hip (the other `powersoftau` commands) share: mapped files and their section tables (the scan
+// and the point sections of a ceremony file: binfile.hpp), the ptau header and the shape of its power sections (the
+// file itself: ptau_file.hip.h), the scalars a command draws or takes from the environment (scalar_in_range,
+// random_scalar, env_scalars over parse_u256.hpp), output files that appear only when complete (AtomicFile) and whose
+// sections are placed in any order (SectionFile), the ZKPOA_VERBOSE phase timer, host threads and arrays, the r1cs
+// parser and its CSR, the ptau ranges a key is made from, the constraint-fold kernels, the piece loop that streams a
+// section from its file through HBM (for_each_piece, piece_from_free_hbm), and the device passes that check the points
+// of a section (curve, range, G2 subgroup: PointChecker). Internal linkage: each translation unit has its own copy.
 #pragma once
 #include "binfile.hpp"
 #include "bn254_ec.hip.h"

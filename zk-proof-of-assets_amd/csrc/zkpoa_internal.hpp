@@ -180,6 +180,15 @@ void scalar_mul_each_g1(zkpoa_context* ctx, const void* d_points, const void* d_
                         void* d_scratch, uint64_t slab);
 void scalar_mul_each_g2(zkpoa_context* ctx, const void* d_points, const void* d_scalars, uint64_t n, void* d_out, uint32_t* d_flags,
                         void* d_scratch, uint64_t slab);
+// the two by group (1: G1, 2: G2): the one place that branches
+inline size_t scalar_mul_each_scratch(int group, uint64_t n, uint64_t slab) {
+  return group == 2 ? scalar_mul_each_scratch_g2(n, slab) : scalar_mul_each_scratch_g1(n, slab);
+}
+inline void scalar_mul_each(zkpoa_context* ctx, int group, const void* d_points, const void* d_scalars, uint64_t n, void* d_out,
+                            uint32_t* d_flags, void* d_scratch, uint64_t slab) {
+  if (group == 2) scalar_mul_each_g2(ctx, d_points, d_scalars, n, d_out, d_flags, d_scratch, slab);
+  else scalar_mul_each_g1(ctx, d_points, d_scalars, n, d_out, d_flags, d_scratch, slab);
+}
 // ptau_response.hip: hash form (compressed: compressed form) -> wire form on lane 0's stream. convert() enqueues n points
 // of group 1 / 2 from d_bytes into d_out (n x 64 / 128 B); a point that cannot be converted leaves its index and what is
 // wrong with it in `first` (the smallest index of all convert() calls since the last require()). require() synchronises
