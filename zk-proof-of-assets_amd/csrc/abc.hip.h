@@ -316,18 +316,11 @@ static __global__ __launch_bounds__(256) void gather_bc32_kernel(const uint4* __
 }
 
 // ---- host: the row CSR of a key's coefficient records, built once per key ---------------------------------------------
-struct AbcCsr {   // device arrays, freed with the struct unless their owner-to-be has taken them (and nulled them here)
-  uint32_t *row_ptr = nullptr, *sig = nullptr, *long_list = nullptr;   // rows + 1 words; `total` signals; n_long constraints
-  void* vals = nullptr;                                                // `total` coefficients, 32 B each
+struct AbcCsr {   // device arrays, freed with the struct unless their owner-to-be has moved them out
+  DevMem row_ptr, sig, long_list;   // u32: rows + 1 words; `total` signals; n_long constraints
+  DevMem vals;                      // `total` coefficients, 32 B each
   uint32_t total = 0, n_long = 0;
   uint32_t err = 0;   // abc_count_kernel's bits (2: a value >= r, 1: matrix, row or signal out of range): the caller's call
-  AbcCsr() = default;
-  AbcCsr(const AbcCsr&) = delete;
-  AbcCsr& operator=(const AbcCsr&) = delete;
-  ~AbcCsr() {
-    for (void* p : {(void*)row_ptr, (void*)sig, (void*)long_list, vals})
-      if (p) (void)hipFree(p);
-  }
 };
 // d_recs: n_coefs 44-byte records on the device. With split_log > 0 only the records of the constraints
 // c = split_rank (mod 2^split_log) are kept, rows renumbered c >> split_log. Records with an error bit are left out.
@@ -337,7 +330,8 @@ inline void abc_build_csr(hipStream_t st, const void* d_recs, uint64_t n_coefs, 
   const uint32_t rows = 2 * (domain >> split_log);
   DevBuf d_cnt((size_t)rows * 4), d_rank((size_t)(n_coefs ? n_coefs : 1) * 4), d_bs(((size_t)rows / kScanTile + 2) * 4),
       d_misc(64);
-  ZK_HIP(hipMalloc(reinterpret_cast<void**>(&out.row_ptr), ((size_t)rows + 1) * 4));
+  out.row_ptr.alloc(((size_t)rows + 1) * 4);
+  uint32_t* const row_ptr = out.row_ptr.as<uint32_t>();
   ZK_HIP(hipMemsetAsync(d_cnt.p, 0, (size_t)rows * 4, st));
   ZK_HIP(hipMemsetAsync(d_misc.p, 0, 64, st));
   uint32_t* misc = (uint32_t*)d_misc.p;   // [0] the scan's total, then the long constraints' count; [4] error bits
@@ -345,34 +339,34 @@ inline void abc_build_csr(hipStream_t st, const void* d_recs, uint64_t n_coefs, 
   if (n_coefs) {
     hipLaunchKernelGGL(abc_count_kernel, dim3(grid), dim3(256), 0, st, (const CoefRec*)d_recs, n_coefs, domain, n_vars,
                        split_log, split_rank, (uint32_t*)d_cnt.p, (uint32_t*)d_rank.p, misc + 4);
-    scan_u32(st, (const uint32_t*)d_cnt.p, rows, 0, 0, out.row_ptr, (uint32_t*)d_bs.p, misc, nullptr);
-    ZK_HIP(hipMemcpyAsync(&out.total, out.row_ptr + rows, 4, hipMemcpyDeviceToHost, st));
+    scan_u32(st, (const uint32_t*)d_cnt.p, rows, 0, 0, row_ptr, (uint32_t*)d_bs.p, misc, nullptr);
+    ZK_HIP(hipMemcpyAsync(&out.total, row_ptr + rows, 4, hipMemcpyDeviceToHost, st));
   } else {
-    ZK_HIP(hipMemsetAsync(out.row_ptr, 0, ((size_t)rows + 1) * 4, st));
+    ZK_HIP(hipMemsetAsync(row_ptr, 0, ((size_t)rows + 1) * 4, st));
   }
   ZK_HIP(hipMemcpyAsync(&out.err, misc + 4, 4, hipMemcpyDeviceToHost, st));
   ZK_HIP(hipStreamSynchronize(st));
   ZK_HIP(hipGetLastError());
-  ZK_HIP(hipMalloc(reinterpret_cast<void**>(&out.sig), (size_t)(out.total ? out.total : 1) * 4));
-  ZK_HIP(hipMalloc(&out.vals, (size_t)(out.total ? out.total : 1) * 32));
+  out.sig.alloc((size_t)out.total * 4);
+  out.vals.alloc((size_t)out.total * 32);
   if (n_coefs) {
     hipLaunchKernelGGL(abc_scatter_kernel, dim3(grid), dim3(256), 0, st, (const CoefRec*)d_recs, n_coefs, split_log,
-                       (const uint32_t*)out.row_ptr, (const uint32_t*)d_rank.p, out.sig, out.vals);
+                       (const uint32_t*)row_ptr, (const uint32_t*)d_rank.p, out.sig.as<uint32_t>(), out.vals.get());
     ZK_HIP(hipStreamSynchronize(st));
     ZK_HIP(hipGetLastError());
   }
   // the constraints too long for one lane: counted, then listed
   const uint32_t lgrid = (rows / 2 + 255) / 256;
   ZK_HIP(hipMemsetAsync(misc, 0, 64, st));
-  hipLaunchKernelGGL(abc_long_list_kernel, dim3(lgrid), dim3(256), 0, st, (const uint32_t*)out.row_ptr, rows, misc,
+  hipLaunchKernelGGL(abc_long_list_kernel, dim3(lgrid), dim3(256), 0, st, (const uint32_t*)row_ptr, rows, misc,
                      (uint32_t*)nullptr);
   ZK_HIP(hipMemcpyAsync(&out.n_long, misc, 4, hipMemcpyDeviceToHost, st));
   ZK_HIP(hipStreamSynchronize(st));
-  ZK_HIP(hipMalloc(reinterpret_cast<void**>(&out.long_list), (size_t)(out.n_long ? out.n_long : 1) * 4));
+  out.long_list.alloc((size_t)out.n_long * 4);
   if (out.n_long) {
     ZK_HIP(hipMemsetAsync(misc, 0, 64, st));
-    hipLaunchKernelGGL(abc_long_list_kernel, dim3(lgrid), dim3(256), 0, st, (const uint32_t*)out.row_ptr, rows, misc,
-                       out.long_list);
+    hipLaunchKernelGGL(abc_long_list_kernel, dim3(lgrid), dim3(256), 0, st, (const uint32_t*)row_ptr, rows, misc,
+                       out.long_list.as<uint32_t>());
     ZK_HIP(hipStreamSynchronize(st));
   }
   ZK_HIP(hipGetLastError());

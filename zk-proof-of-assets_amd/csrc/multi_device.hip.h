@@ -261,35 +261,48 @@ DeviceSet* process_devices(uint32_t power, std::string& err, int* code) {
 }
 
 // ---- a key sharded over the ranks of the process ----------------------------------------------------------------------
+struct DevEvent {   // an owned hipEvent_t (timing disabled); empty = not created
+  hipEvent_t e = nullptr;
+  DevEvent() = default;
+  DevEvent(DevEvent&& o) noexcept : e(o.e) { o.e = nullptr; }
+  DevEvent& operator=(DevEvent&& o) noexcept {
+    std::swap(e, o.e);
+    return *this;
+  }
+  ~DevEvent() {
+    if (e) (void)hipEventDestroy(e);
+  }
+  void create() { ZK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); }   // on the current device
+  operator hipEvent_t() const { return e; }
+};
+
+struct RankState {   // what rank g holds, on device `device` (a failed load leaves the later members empty)
+  int device = 0;
+  KeyPtr shard;             // lives on context g
+  DevMem xa, xb1, xb2;      // split chain: send buffer, receive buffers of the two exchanges
+  DevEvent ev1, ev2;        // "my pushes of exchange 1 / 2 are enqueued up to here"
+  DevEvent evw;             // "my slice of the witness is on its way to every peer"
+};
+
 struct MultiKey {
-  std::vector<zkpoa_zkey*> shards;          // shard g lives on context g
+  std::vector<RankState> rank;
   bool split = false;                       // H-scalar chain split (G in {2, 4, 8}, G^2 <= domain) or replicated
-  std::vector<void*> xa, xb1, xb2;          // per rank: send buffer, receive buffers of the two exchanges
-  std::vector<hipEvent_t> ev1, ev2;         // per rank: "my pushes of exchange 1 / 2 are enqueued up to here"
-  std::vector<hipEvent_t> evw;              // per rank: "my slice of the witness is on its way to every peer"
   uint64_t xbytes = 0;                      // bytes of one exchange buffer: 3 * (domain / G) * 32
   uint64_t proofs_done = 0, table_bytes = 0;
   bool tables_tried = false;                // the shards' fixed-base tables have been built (or the attempt has been made)
   double load_ms = 0;
-};
-
-void multi_key_release(DeviceSet* ds, MultiKey* mk) {
-  if (!mk) return;
-  for (size_t g = 0; g < mk->shards.size(); g++) {
-    (void)hipSetDevice(ds->ids[g]);
-    (void)hipDeviceSynchronize();
-    for (std::vector<void*>* v : {&mk->xa, &mk->xb1, &mk->xb2})
-      if (g < v->size() && (*v)[g]) (void)hipFree((*v)[g]);
-    if (g < mk->ev1.size() && mk->ev1[g]) (void)hipEventDestroy(mk->ev1[g]);
-    if (g < mk->ev2.size() && mk->ev2[g]) (void)hipEventDestroy(mk->ev2[g]);
-    if (g < mk->evw.size() && mk->evw[g]) (void)hipEventDestroy(mk->evw[g]);
-    if (mk->shards[g]) {
-      mk->shards[g]->release();
-      delete mk->shards[g];
+  explicit MultiKey(const DeviceSet* ds) : rank(ds->ids.size()) {
+    for (size_t g = 0; g < rank.size(); g++) rank[g].device = ds->ids[g];
+  }
+  ~MultiKey() {   // rank by rank: peers may still push into this rank's buffers until its device has drained
+    for (RankState& r : rank) {
+      (void)hipSetDevice(r.device);
+      (void)hipDeviceSynchronize();
+      r = RankState();
     }
   }
-  delete mk;
-}
+};
+typedef std::unique_ptr<MultiKey> MultiKeyPtr;
 
 // run fn(g) on one thread per rank; the first exception (by rank) is rethrown after all have joined
 template <class Fn>
@@ -328,44 +341,28 @@ uint32_t multi_block_log(uint64_t n_vars, size_t G) {
   return multi_block_log_default(n_vars, G);
 }
 
-MultiKey* multi_key_load(DeviceSet* ds, const uint8_t* buf, uint64_t size) {
+MultiKeyPtr multi_key_load(DeviceSet* ds, const uint8_t* buf, uint64_t size) {
   const size_t G = ds->ids.size();
-  std::unique_ptr<MultiKey> mk(new MultiKey());
-  mk->shards.assign(G, nullptr);
+  MultiKeyPtr mk(new MultiKey(ds));
   auto t0 = std::chrono::steady_clock::now();
-  try {
-    ZkeySections zs;
-    std::unique_ptr<zkpoa_zkey> hdr = zkey_parse(buf, size, zs);   // validates the container once, before G uploads start
-    mk->split = (G == 2 || G == 4 || G == 8) && (uint64_t)hdr->domain >= (uint64_t)G * G;
-    const uint32_t bc = multi_block_log(hdr->nVars, G);
-    for_each_rank(ds, [&](size_t g) { mk->shards[g] = zkey_load_impl(ds->ctx[g], buf, size, g, G, mk->split, bc); });
-    mk->evw.assign(G, nullptr);
-    for (size_t g = 0; g < G; g++) {
-      ZK_HIP(hipSetDevice(ds->ids[g]));
-      ZK_HIP(hipEventCreateWithFlags(&mk->evw[g], hipEventDisableTiming));
-    }
-    if (mk->split) {
-      mk->xbytes = (uint64_t)3 * (hdr->domain / G) * 32;
-      mk->xa.assign(G, nullptr);
-      mk->xb1.assign(G, nullptr);
-      mk->xb2.assign(G, nullptr);
-      mk->ev1.assign(G, nullptr);
-      mk->ev2.assign(G, nullptr);
-      for (size_t g = 0; g < G; g++) {
-        ZK_HIP(hipSetDevice(ds->ids[g]));
-        ZK_HIP(hipMalloc(&mk->xa[g], mk->xbytes));
-        ZK_HIP(hipMalloc(&mk->xb1[g], mk->xbytes));
-        ZK_HIP(hipMalloc(&mk->xb2[g], mk->xbytes));
-        ZK_HIP(hipEventCreateWithFlags(&mk->ev1[g], hipEventDisableTiming));
-        ZK_HIP(hipEventCreateWithFlags(&mk->ev2[g], hipEventDisableTiming));
-      }
-    }
-  } catch (...) {
-    multi_key_release(ds, mk.release());
-    throw;
+  ZkeySections zs;
+  KeyPtr hdr = zkey_parse(buf, size, zs);   // validates the container once, before G uploads start
+  mk->split = (G == 2 || G == 4 || G == 8) && (uint64_t)hdr->domain >= (uint64_t)G * G;
+  const uint32_t bc = multi_block_log(hdr->nVars, G);
+  for_each_rank(ds, [&](size_t g) { mk->rank[g].shard = zkey_load_impl(ds->ctx[g], buf, size, g, G, mk->split, bc); });
+  if (mk->split) mk->xbytes = (uint64_t)3 * (hdr->domain / G) * 32;
+  for (RankState& r : mk->rank) {
+    ZK_HIP(hipSetDevice(r.device));
+    r.evw.create();
+    if (!mk->split) continue;
+    r.xa.alloc(mk->xbytes);
+    r.xb1.alloc(mk->xbytes);
+    r.xb2.alloc(mk->xbytes);
+    r.ev1.create();
+    r.ev2.create();
   }
   mk->load_ms = ms_since(t0);
-  return mk.release();
+  return mk;
 }
 
 // One exchange of the split chain, rank g's half: push chunk h of `src` (what rank h needs from g) into slot g of rank
@@ -394,18 +391,18 @@ inline std::atomic<long>& multi_proof_counter() {
   return v;
 }
 
-void multi_push(DeviceSet* ds, MultiKey* mk, size_t g, const void* src, std::vector<void*>& dst, hipEvent_t done) {
+void multi_push(DeviceSet* ds, MultiKey* mk, size_t g, const void* src, DevMem RankState::*dst, hipEvent_t done) {
   const size_t G = ds->ids.size();
   const uint64_t chunk = mk->xbytes / G;
   hipStream_t st = ds->ctx[g]->dev.lanes[0].stream;
   if (ds->peer_ok && !multi_force_copies() && chunk % 16 == 0) {
-    if (g == 0 && &dst == &mk->xb1 && multi_test_stale_at() && multi_proof_counter().load() == multi_test_stale_at()) {
+    if (g == 0 && dst == &RankState::xb1 && multi_test_stale_at() && multi_proof_counter().load() == multi_test_stale_at()) {
       ZK_HIP(hipEventRecord(done, st));   // (test hook: this push is withheld)
       return;
     }
     // one kernel writes all G chunks into the peers' receive buffers: all links busy at once (abc.hip.h)
     XchgDst d;
-    for (size_t h = 0; h < 8; h++) d.p[h] = h < G ? reinterpret_cast<char*>(dst[h]) + g * chunk : nullptr;
+    for (size_t h = 0; h < 8; h++) d.p[h] = h < G ? (mk->rank[h].*dst).as<char>() + g * chunk : nullptr;
     const uint64_t chunk16 = chunk / 16, total = chunk16 * G;
     hipLaunchKernelGGL(xchg_push_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, st,
                        reinterpret_cast<const uint4*>(src), d, chunk16, (uint32_t)G, (uint32_t)g);
@@ -414,7 +411,7 @@ void multi_push(DeviceSet* ds, MultiKey* mk, size_t g, const void* src, std::vec
     for (size_t k = 0; k < G; k++) {
       const size_t h = (g + k) % G;   // start with the own slot, then round the ring: no two ranks aim at one peer at once
       const char* s = reinterpret_cast<const char*>(src) + h * chunk;
-      char* d = reinterpret_cast<char*>(dst[h]) + g * chunk;
+      char* d = (mk->rank[h].*dst).as<char>() + g * chunk;
       if (ds->ids[g] == ds->ids[h]) ZK_HIP(hipMemcpyAsync(d, s, chunk, hipMemcpyDeviceToDevice, st));
       else ZK_HIP(hipMemcpyPeerAsync(d, ds->ids[h], s, ds->ids[g], chunk, st));
     }
@@ -443,7 +440,7 @@ void multi_prove_partials(DeviceSet* ds, MultiKey* mk, const WtnsView& w, uint8_
         }
       };
       zkpoa_context* ctx = ds->ctx[g];
-      zkpoa_zkey* zk = mk->shards[g];
+      zkpoa_zkey* zk = mk->rank[g].shard.get();
       hipStream_t st = nullptr;
       // tests: ZKPOA_TEST_FAIL_RANK=<g>[:<phase>] makes rank g fail at the start of that phase (1 = before the first
       // barrier, 2 = between the exchanges, 3 = before its MSMs): the other ranks must come back, not wait for ever
@@ -472,13 +469,13 @@ void multi_prove_partials(DeviceSet* ds, MultiKey* mk, const WtnsView& w, uint8_
           if (hi > lo) {
             w.upload(ctx, mine, lo, hi - lo, st);
             XchgDst d;
-            for (size_t h = 0; h < 8; h++) d.p[h] = h < G ? reinterpret_cast<char*>(mk->shards[h]->d_witness) + lo * 32 : nullptr;
+            for (size_t h = 0; h < 8; h++) d.p[h] = h < G ? reinterpret_cast<char*>(mk->rank[h].shard->d_witness) + lo * 32 : nullptr;
             const uint64_t n16 = (hi - lo) * 2, total = n16 * (G - 1);
             hipLaunchKernelGGL(xchg_bcast_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, st,
                                reinterpret_cast<const uint4*>(mine), d, n16, (uint32_t)G, (uint32_t)g);
             ZK_HIP(hipGetLastError());
           }
-          ZK_HIP(hipEventRecord(mk->evw[g], st));
+          ZK_HIP(hipEventRecord(mk->rank[g].evw, st));
         } else {
           w.upload(ctx, zk->d_witness, 0, w.n, st);   // replicated
         }
@@ -486,7 +483,7 @@ void multi_prove_partials(DeviceSet* ds, MultiKey* mk, const WtnsView& w, uint8_
       if (sliced) {
         bar.arrive_and_wait();   // every slice's event has been recorded
         phase([&] {
-          for (size_t h = 0; h < G; h++) ZK_HIP(hipStreamWaitEvent(st, mk->evw[h], 0));
+          for (size_t h = 0; h < G; h++) ZK_HIP(hipStreamWaitEvent(st, mk->rank[h].evw, 0));
           // the witness MSMs run on other lanes: they wait for this point of lane 0 (prove_partials, ev_witness)
           if (!ctx->ev_witness) ZK_HIP(hipEventCreateWithFlags(&ctx->ev_witness, hipEventDisableTiming));
           ZK_HIP(hipEventRecord(ctx->ev_witness, st));
@@ -496,22 +493,22 @@ void multi_prove_partials(DeviceSet* ds, MultiKey* mk, const WtnsView& w, uint8_
       phase([&] {
         zk->h_ready = false;
         if (mk->split) {
-          split_stage1(ctx, zk, mk->xa[g]);
-          multi_push(ds, mk, g, mk->xa[g], mk->xb1, mk->ev1[g]);
+          split_stage1(ctx, zk, mk->rank[g].xa.get());
+          multi_push(ds, mk, g, mk->rank[g].xa.get(), &RankState::xb1, mk->rank[g].ev1);
         }
       });
       if (mk->split) {
         bar.arrive_and_wait();   // every rank's event has been recorded: waiting on an unrecorded event is a no-op
         phase([&] {
           test_fail(2);
-          for (size_t h = 0; h < G; h++) ZK_HIP(hipStreamWaitEvent(st, mk->ev1[h], 0));
-          split_stage2(ctx, zk, mk->xb1[g], mk->xa[g]);   // xa[g] is free: this stream's own pushes precede this stage
-          multi_push(ds, mk, g, mk->xa[g], mk->xb2, mk->ev2[g]);
+          for (size_t h = 0; h < G; h++) ZK_HIP(hipStreamWaitEvent(st, mk->rank[h].ev1, 0));
+          split_stage2(ctx, zk, mk->rank[g].xb1.get(), mk->rank[g].xa.get());   // xa is free: this stream's own pushes precede this stage
+          multi_push(ds, mk, g, mk->rank[g].xa.get(), &RankState::xb2, mk->rank[g].ev2);
         });
         bar.arrive_and_wait();
         phase([&] {
-          for (size_t h = 0; h < G; h++) ZK_HIP(hipStreamWaitEvent(st, mk->ev2[h], 0));
-          split_stage3(ctx, zk, mk->xb2[g]);
+          for (size_t h = 0; h < G; h++) ZK_HIP(hipStreamWaitEvent(st, mk->rank[h].ev2, 0));
+          split_stage3(ctx, zk, mk->rank[g].xb2.get());
         });
       }
       // the witness MSMs start at once on their own lanes and overlap the chain still in flight on lane 0
@@ -542,7 +539,7 @@ void multi_prove_partials(DeviceSet* ds, MultiKey* mk, const WtnsView& w, uint8_
       (void)hipSetDevice(ds->ids[g]);
       (void)hipDeviceSynchronize();
       ds->ctx[g]->ev_witness_set = false;
-      mk->shards[g]->h_ready = false;
+      mk->rank[g].shard->h_ready = false;
     }
     (void)hipSetDevice(ds->ids[0]);
   }
@@ -564,9 +561,9 @@ void multi_precompute(DeviceSet* ds, MultiKey* mk) {
   std::vector<uint64_t> used(ds->ids.size(), 0);
   for_each_rank(ds, [&](size_t g) {
     try {
-      used[g] = zkey_precompute(ds->ctx[g], mk->shards[g], 0);
+      used[g] = zkey_precompute(ds->ctx[g], mk->rank[g].shard.get(), 0);
     } catch (const HipError&) {   // out of HBM: the classic form keeps working
-      mk->shards[g]->release_tables();
+      mk->rank[g].shard->release_tables();
       (void)hipGetLastError();
     }
   });

@@ -206,16 +206,6 @@ int prove_to_json(zkpoa_context* ctx, const zkpoa_zkey* zk, const WtnsSrc& wsrc,
   return check_and_emit(ctx, zk, pts, w, out, load_ms, zkey_size, cache_hit ? "cached," : "load");
 }
 
-// a key a request holds on one GPU: released (after the device has drained) when its owner lets go of it
-struct FreeKey {
-  void operator()(zkpoa_zkey* zk) const {
-    (void)hipDeviceSynchronize();
-    zk->release();
-    delete zk;
-  }
-};
-typedef std::unique_ptr<zkpoa_zkey, FreeKey> KeyPtr;
-
 // One-shot: load the key and prove, with the upload overlapped unless ZKPOA_OVERLAP=0. zk <- the loaded key, also when
 // the proof fails after the load (the caller caches it or lets it go). The load time reported is the time to the end
 // of the proof where load and prove are one phase.
@@ -228,20 +218,20 @@ int load_and_prove_to_json(zkpoa_context* ctx, const uint8_t* zkey, uint64_t zke
     const EnvBlinding bl;
     uint8_t parts[384], pts[256];
     const auto t0 = std::chrono::steady_clock::now();
-    zk.reset(load_prove_staged(ctx, zkey, zkey_size, w, parts, zkey_fd));
+    zk = load_prove_staged(ctx, zkey, zkey_size, w, parts, zkey_fd);
     if (zk) {
       assemble_proof(ctx, zk.get(), parts, bl.r, bl.s, t0, pts);
       return check_and_emit(ctx, zk.get(), pts, w, out, ctx->ms[5], zkey_size, "load overlapped with the prove:");
     }
   }
-  zk.reset(zkey_load_impl(ctx, zkey, zkey_size));
+  zk = zkey_load_impl(ctx, zkey, zkey_size);
   return prove_to_json(ctx, zk.get(), wsrc, out, ms_since(tl0), zkey_size, false);
 }
 
 // witness -> proof JSON on a loaded MultiKey (the multi-GPU twin of prove_to_json)
 int multi_prove_to_json(DeviceSet* ds, MultiKey* mk, const WtnsSrc& wsrc, const ProveOut& out, uint64_t zkey_size,
                         bool cache_hit) {
-  zkpoa_zkey* z0 = mk->shards[0];
+  zkpoa_zkey* z0 = mk->rank[0].shard.get();
   zkpoa_context* c0 = ds->ctx[0];
   WtnsView w = parse_wtns(wsrc);
   check_witness_len(w, z0);
@@ -357,13 +347,8 @@ struct KeyCache {
   }
 };
 
-struct FreeMultiKey {
-  void operator()(MultiKey* mk) const { multi_key_release(g_devset, mk); }   // (a sharded key exists only once the set does)
-};
-typedef std::unique_ptr<MultiKey, FreeMultiKey> MultiKeyPtr;
-
 KeyCache<zkpoa_zkey, FreeKey> g_key_cache;
-KeyCache<MultiKey, FreeMultiKey> g_multi_cache;
+KeyCache<MultiKey, std::default_delete<MultiKey>> g_multi_cache;
 
 // When a resident key gets its fixed-base tables (ZKPOA_PRECOMP). A whole set costs 0.25 s at the layer-one shape and
 // 3-7 s at layers two and three -- twenty to thirty proofs' worth -- and saves ~10 % per proof, so it pays after a few
@@ -441,7 +426,7 @@ int one_shot(const uint8_t* zkey, uint64_t zkey_size, const WtnsSrc& wsrc, const
   try {
     ZK_HIP(hipSetDevice(ctx->dev.device));
     if (ds->ids.size() > 1) {   // one proof over all ranks of the process
-      mk.reset(multi_key_load(ds, zkey, zkey_size));
+      mk = multi_key_load(ds, zkey, zkey_size);
       return multi_prove_to_json(ds, mk.get(), wsrc, out, zkey_size, false);
     }
     return load_and_prove_to_json(ctx, zkey, zkey_size, wsrc, out, zk);
@@ -465,7 +450,7 @@ int multi_file_prove(DeviceSet* ds, int fd, const struct stat& sb, const char* p
     if (!hit) {
       const MappedFile map(fd, sb, path);
       g_multi_cache.make_room(cap);
-      own.reset(g_multi_cache.load_retrying_alone(ds, [&] { return multi_key_load(ds, map.p, map.size); }));
+      own = g_multi_cache.load_retrying_alone(ds, [&] { return multi_key_load(ds, map.p, map.size); });
       mk = own.get();
       if (cap) g_multi_cache.insert(sb, std::move(own));
     }
@@ -499,19 +484,18 @@ int staged_prove(zkpoa_context* ctx, const zkpoa_zkey* zk, const WtnsSrc& wsrc, 
     ZK_HIP(hipSetDevice(ctx->dev.device));
     WtnsView w = parse_wtns(wsrc);
     check_witness_len(w, zk);
-    if (!zk->wbuf[0]) zk->wbuf[0] = zk->d_witness;   // adopt the buffer the key came with
     g_stage_cv.wait(stage_lk, [&] { return !zk->wbusy[0] || !zk->wbusy[1]; });
     slot = !zk->wbusy[0] ? 0 : 1;
-    if (!zk->wbuf[slot]) ZK_HIP(hipMalloc(&zk->wbuf[slot], (size_t)zk->nVars * 32));
+    if (!zk->wbuf[slot]) zk->wbuf[slot].alloc((size_t)zk->nVars * 32);   // (the second one: two requests overlap for the first time)
     zk->wbusy[slot] = true;
     g_staged_users++;
     const auto tu = std::chrono::steady_clock::now();
-    w.upload(ctx, zk->wbuf[slot], 0, w.n, cs);      // on the copy stream(s): lane 0 may be busy with another proof's chain
+    w.upload(ctx, zk->wbuf[slot].get(), 0, w.n, cs);      // on the copy stream(s): lane 0 may be busy with another proof's chain
     const float up_ms = (float)ms_since(tu);
     stage_lk.unlock();
     {
       std::lock_guard<std::mutex> lk(g_prove_mutex);
-      zk->d_witness = zk->wbuf[slot];
+      zk->d_witness = zk->wbuf[slot].get();
       const EnvBlinding bl;
       uint8_t pts[256];
       prove_core(ctx, zk, bl.r, bl.s, pts);
@@ -546,7 +530,7 @@ int single_file_prove(zkpoa_context* ctx, const DeviceSet* ds, int fd, const str
     const size_t cap = key_cache_capacity();
     zkpoa_zkey* zk = g_key_cache.find(sb);
     if (zk) {
-      if (zk->wbuf[0]) zk->d_witness = zk->wbuf[0];   // nothing is staged now: back to the first buffer
+      zk->d_witness = zk->wbuf[0].get();   // nothing is staged now: back to the first buffer
       // a key that comes out of the cache is being reused: build its fixed-base tables now, once (ZKPOA_PRECOMP=0 off)
       if (tables_due_now(zk->proofs_done, zk->tables_settled, zk->table_bytes)) {
         const auto tp0 = std::chrono::steady_clock::now();

@@ -93,185 +93,21 @@ const Section& need(const Sections& s, uint32_t id, const char* what) {
 const uint8_t kR[32] = {0x01, 0x00, 0x00, 0xf0, 0x93, 0xf5, 0xe1, 0x43, 0x91, 0x70, 0xb9, 0x79, 0x48, 0xe8, 0x33, 0x28,
                         0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
 
-void* dev_upload(zkpoa_context* ctx, const void* src, size_t bytes) {
-  void* d = nullptr;
+DevMem dev_upload(zkpoa_context* ctx, const void* src, size_t bytes) {
+  DevMem d;
   auto t0 = std::chrono::steady_clock::now();
-  ZK_HIP(hipMalloc(&d, bytes ? bytes : 1));
+  d.alloc(bytes);
   auto t1 = std::chrono::steady_clock::now();
-  try {
-    if (bytes) ctx->uploader.upload(d, src, bytes, ctx->dev.device, ctx->dev.lanes[0].stream);
-    if (req_getenv("ZKPOA_VERBOSE") && bytes > (16u << 20))
-      fprintf(stderr, "zkpoa:   upload %.0f MB: hipMalloc %.1f ms, copy %.1f ms\n", bytes / 1e6,
-              std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
-  } catch (...) {
-    (void)hipFree(d);
-    throw;
-  }
+  if (bytes) ctx->uploader.upload(d.get(), src, bytes, ctx->dev.device, ctx->dev.lanes[0].stream);
+  if (req_getenv("ZKPOA_VERBOSE") && bytes > (16u << 20))
+    fprintf(stderr, "zkpoa:   upload %.0f MB: hipMalloc %.1f ms, copy %.1f ms\n", bytes / 1e6,
+            std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
   return d;
 }
 
 }  // namespace
 
-// The five points of a zkey header the prover needs. Wire form (zkpoa_zkey_header, zkpoa_prove_assemble,
-// zkpoa_zkey_load_device): alpha1(64) beta1(64) beta2(128) delta1(64) delta2(128).
-struct HeaderPoints {   // (members in wire order)
-  Affine<HFq> alpha1, beta1;
-  Affine<HFq2> beta2;
-  Affine<HFq> delta1;
-  Affine<HFq2> delta2;
-};
-static HeaderPoints header_points(const uint8_t* alpha1, const uint8_t* beta1, const uint8_t* beta2, const uint8_t* delta1,
-                                  const uint8_t* delta2) {
-  return {h_affine_from_bytes<HFq>(alpha1), h_affine_from_bytes<HFq>(beta1), h_affine_from_bytes<HFq2>(beta2),
-          h_affine_from_bytes<HFq>(delta1), h_affine_from_bytes<HFq2>(delta2)};
-}
-static HeaderPoints header_points_from_bytes(const uint8_t in[448]) {   // the inverse of zkey_header_bytes
-  return header_points(in, in + 64, in + 128, in + 256, in + 320);
-}
-
-// ---- device-resident proving key -------------------------------------------------------------------
-struct zkpoa_zkey {
-  uint32_t nVars = 0, nPublic = 0, domain = 0, power = 0;
-  uint64_t nCoefs = 0;
-  HeaderPoints hdr;
-  // Verification key carried by the zkey itself (section 2: alpha1, beta2, gamma2, delta2; section 3: IC), wire
-  // format alpha1(64) beta2(128) gamma2(128) delta2(128) IC[(nPublic+1) x 64]. Empty for keys assembled from
-  // device buffers (zkpoa_zkey_load_device has no gamma2 / IC). Used by the self-check of the first proof(s).
-  std::vector<uint8_t> vkey_points;
-  mutable uint64_t selfchecks_done = 0;
-  void *dA = nullptr, *dB1 = nullptr, *dB2 = nullptr, *dC = nullptr, *dH = nullptr;
-  uint32_t* d_row_ptr = nullptr;
-  uint32_t* d_long = nullptr;   // constraints with more than kLongRow coefficients (abc.hip.h), n_long of them
-  uint32_t n_long = 0;
-  uint32_t* d_sig = nullptr;
-  void* d_vals = nullptr;
-  uint32_t* d_flag = nullptr; // [0]: a witness value >= r was seen by the last prove (range_check_kernel)
-  void* d_abc = nullptr;      // 3 * domain * 32 B work area (A_T, B_T, C_T)
-  mutable void* d_witness = nullptr;  // nVars * 32 B: the witness the next prove reads
-  // Witness staging of the resident prover (zkey_file_prove): two buffers, so that the witness of the NEXT request is
-  // uploaded while the current proof computes; d_witness points at the one being proved. wbuf[0] adopts the buffer the
-  // key was loaded with, wbuf[1] is allocated when a second request first overlaps.
-  mutable void* wbuf[2] = {nullptr, nullptr};
-  mutable bool wbusy[2] = {false, false};
-  bool owns_points = true;    // false when the point sections belong to the caller (zkpoa_zkey_load_device)
-  // Shard of the MSMs this handle covers: contiguous global index ranges. The device
-  // buffers dA/dB1/dB2 start at global wire index `wbase`, dC at C-section index `cbase`, dH at `hbase`.
-  uint64_t wlo = 0, wcnt = 0, wbase = 0;   // A, B1, B2: wire indices [wlo, wlo + wcnt)
-  uint64_t clo = 0, ccnt = 0, cbase = 0;   // C: section indices (wire nPublic+1+idx)
-  uint64_t hlo = 0, hcnt = 0, hbase = 0;   // H: domain indices
-  // Split H-scalar chain (SURVEY.md 8e rows NTT / buildABC / joinABC): split_world = G > 1 ranks each own the
-  // constraint rows c = split_rank (mod G) and end up with the H scalars of the odd-coset indices
-  // i = split_rank (mod G), so the H points are sharded cyclically: dHs[t] = H[t*G + split_rank].
-  uint32_t split_world = 0, split_rank = 0, split_log = 0;
-  bool csr_local = false;        // CSR holds only this rank's rows, renumbered c >> split_log
-  void* dHs = nullptr;           // cyclic H shard (owned), domain / split_world points
-  mutable bool h_ready = false;  // d_abc[0 .. domain/split_world) holds this proof's H scalars (stage 3 done)
-  uint64_t nCoefsLocal = 0;
-  // Block-cyclic shard of sections 5-8 (bc_log > 0; shard handles only): this rank holds the blocks b = bc_rank
-  // (mod bc_world) of 2^bc_log consecutive items -- wires for A / B1 / B2, section indices for C -- concatenated. A
-  // contiguous range inherits whatever clustering a real witness has (bit-decomposition wires come in runs of cheap
-  // 0 / 1 scalars, limbs in runs of full-width ones), so ranks would finish at different times; blocks of 2^16 wires
-  // dealt round-robin even that out while every block is still one contiguous byte range of the file. Local index j
-  // of a section <-> global index (((j >> L) * world + rank) << L) + (j & (2^L - 1)).
-  uint32_t bc_log = 0, bc_rank = 0, bc_world = 1;
-  void* d_cscal = nullptr;       // block-cyclic handles: the C query's witness values, gathered per proof
-  static uint64_t bc_count(uint64_t n, uint32_t L, uint64_t rank, uint64_t world) {
-    const uint64_t B = 1ull << L, nb = (n + B - 1) >> L;
-    if (nb <= rank) return 0;
-    uint64_t cnt = ((nb - rank + world - 1) / world) << L;
-    if ((nb - 1) % world == rank && (n & (B - 1))) cnt -= B - (n & (B - 1));
-    return cnt;
-  }
-  // A and B queries without their points at infinity (abc.hip.h): compacted copies of the resident range of
-  // section 5 resp. 6 / 7, the wire of every kept point, pos[i] = kept points before resident wire i (a shard's
-  // slice of the compacted arrays is [pos[wlo - wbase], pos[wlo + wcnt - wbase])), and the gathered scalars.
-  struct CompactQuery {
-    void *g1 = nullptr, *g2 = nullptr, *scalars = nullptr;
-    uint32_t *wire = nullptr, *pos = nullptr;
-    uint64_t res = 0;          // kept points in the resident range
-    uint64_t lo = 0, cnt = 0;  // this shard's slice of them
-    void release() {
-      void* ptrs[] = {g1, g2, scalars, wire, pos};
-      for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-      g1 = g2 = scalars = nullptr;
-      wire = pos = nullptr;
-    }
-  };
-  CompactQuery qA, qB;
-  // Fixed-base tables (msm.hip.h MsmTable; zkpoa_zkey_precompute): 2^(c*j) * P for every window j of a whole
-  // resident base array -- the compacted A / B queries, section 8, section 9. An MSM uses its table only when it
-  // covers exactly that array (a re-pointed shard of a resident key falls back to the classic form).
-  MsmTable *tA = nullptr, *tB1 = nullptr, *tB2 = nullptr, *tC = nullptr, *tH = nullptr;
-  bool tH_cyclic = false;     // tH was built from the cyclic shard dHs (split handles), not from dH
-  uint64_t table_bytes = 0;
-  // incremental build (zkey_precompute_step: one table per call, from the resident prover's idle time)
-  uint64_t table_budget = 0;  // fixed at the first step (half of the HBM free then)
-  bool tables_settled = false;   // every table that is wanted and fits has been built (or an attempt failed)
-  bool warmed = false;           // a throw-away proof has run since the tables settled (the lanes' workspaces regrown)
-  // digit density of the last witness measured on this handle (msm_density: non-zero digits per scalar for every
-  // window width). A circuit's witnesses all look alike (bits stay bits), so it is measured by the first proof only
-  // and sizes the windows of later proofs and of the witness tables (zkey_precompute after a proof).
-  mutable double witness_density[32];
-  mutable bool have_density = false;
-  std::atomic<uint64_t> proofs_done{0};   // groth16_prover_zkey_file's cache precomputes when a key is used a second time
-  void release_tables() {
-    for (MsmTable** t : {&tA, &tB1, &tB2, &tC, &tH}) {
-      msm_table_release(*t);
-      *t = nullptr;
-    }
-    table_bytes = 0;
-    tH_cyclic = false;
-    table_budget = 0;
-    tables_settled = false;
-    warmed = false;
-  }
-  void release_cyclic_h_table() {   // a new cyclic shard replaces dHs: the table built from the old one goes
-    if (!tH_cyclic) return;
-    uint64_t info[4];
-    msm_table_info(tH, info);
-    table_bytes -= std::min(info[3], table_bytes);
-    msm_table_release(tH);
-    tH = nullptr;
-    tH_cyclic = false;
-  }
-  // H scalars one proof leaves in d_abc: a rank of a split chain computes its domain / G, anyone else all of them
-  static uint64_t split_h_count(uint64_t domain, uint64_t world) { return domain / world; }
-  uint64_t h_scalar_count() const { return split_world > 1 ? split_h_count(domain, split_world) : domain; }
-  static void split(uint64_t n, uint64_t rank, uint64_t world, uint64_t& lo, uint64_t& cnt) {
-    uint64_t base = n / world, rem = n % world;
-    lo = rank * base + (rank < rem ? rank : rem);
-    cnt = base + (rank < rem ? 1 : 0);
-  }
-  void set_shard(uint64_t rank, uint64_t world) {
-    split(nVars, rank, world, wlo, wcnt);
-    split((uint64_t)nVars - nPublic - 1, rank, world, clo, ccnt);
-    split(domain, rank, world, hlo, hcnt);
-  }
-  void release() {
-    release_tables();
-    void* pts[] = {dA, dB1, dB2, dC, dH};
-    if (owns_points)
-      for (void* p : pts)
-        if (p) (void)hipFree(p);
-    if (wbuf[0] || wbuf[1]) {   // the staging pair owns the witness memory (d_witness points at one of them)
-      for (void*& w : wbuf) {
-        if (w) (void)hipFree(w);
-        w = nullptr;
-      }
-      d_witness = nullptr;
-    }
-    void* ptrs[] = {d_row_ptr, d_sig, d_vals, d_abc, d_witness, dHs, d_long, d_flag, d_cscal};
-    for (void* p : ptrs)
-      if (p) (void)hipFree(p);
-    qA.release();
-    qB.release();
-    dA = dB1 = dB2 = dC = dH = d_vals = d_abc = d_witness = dHs = d_cscal = nullptr;
-    d_long = nullptr;
-    d_flag = nullptr;
-    d_row_ptr = d_sig = nullptr;
-  }
-};
+#include "zkey_handle.hip.h"   // zkpoa_zkey: what a resident key holds and owns, its shard arithmetic, its header points
 
 namespace {
 
@@ -282,6 +118,22 @@ void range_check(hipStream_t st, const void* d, uint64_t count, uint32_t* d_flag
     hipLaunchKernelGGL((range_check_kernel<PRM>), dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, st, d, count, d_flag);
 }
 
+// Every coordinate of the part of a point section the handle holds must be a canonical Fq element (< q): one pass over
+// it on `st`, which ORs into the caller's zeroed flag word. The section must be resident.
+enum { kSecA, kSecB1, kSecB2, kSecC, kSecH };
+void section_range_check(const zkpoa_zkey* zk, int sec, hipStream_t st, uint32_t* d_flag) {
+  const bool cyclic = zk->split_world > 1;
+  switch (sec) {
+    case kSecA: return range_check<FqParams>(st, zk->dA.get(), zk->wcnt * 2, d_flag);
+    case kSecB1: return range_check<FqParams>(st, zk->dB1.get(), zk->wcnt * 2, d_flag);
+    case kSecB2: return range_check<FqParams>(st, zk->dB2.get(), zk->wcnt * 4, d_flag);
+    case kSecC: return range_check<FqParams>(st, zk->dC.get(), zk->ccnt * 2, d_flag);
+    default:
+      return range_check<FqParams>(st, cyclic ? zk->dHs.get() : zk->dH.get(),
+                                   (cyclic ? zk->h_scalar_count() : zk->hcnt) * 2, d_flag);
+  }
+}
+
 // CSR of the coefficient list by output row (2*c + m), into the handle; d_recs = device copy of the 44-byte records.
 // Also allocates the A/B/C work area and the witness buffer. With split_log > 0 (split chain loaded from a
 // file) only the records of this rank's constraints are kept, rows renumbered c >> split_log.
@@ -290,45 +142,31 @@ void build_csr(zkpoa_context* ctx, zkpoa_zkey* zk, const void* d_recs, bool loca
   const uint32_t lp = local_rows ? zk->split_log : 0u, part = local_rows ? zk->split_rank : 0u;
   const uint64_t n = zk->domain, m = zk->nVars;
   // work area: the chain transforms A_T, B_T, C_T in place (a split shard: its n / G rows of each)
-  if (!zk->d_abc) ZK_HIP(hipMalloc(&zk->d_abc, (size_t)3 * (n >> lp) * 32));
-  if (!zk->d_witness) ZK_HIP(hipMalloc(&zk->d_witness, (size_t)m * 32));
-  if (!zk->d_flag) ZK_HIP(hipMalloc(reinterpret_cast<void**>(&zk->d_flag), 1024));   // + scratch of msm_density at +256
+  if (!zk->d_abc) zk->d_abc.alloc((size_t)3 * (n >> lp) * 32);
+  if (!zk->wbuf[0]) {
+    zk->wbuf[0].alloc((size_t)m * 32);
+    zk->d_witness = zk->wbuf[0].get();
+  }
+  if (!zk->d_flag) zk->d_flag.alloc(1024);   // + scratch of msm_density at +256
   AbcCsr csr;
   abc_build_csr(st, d_recs, zk->nCoefs, zk->domain, zk->nVars, lp, part, csr);
   if (csr.err & 2u) throw ProverError(PROVER_ERROR, "zkey coefficient value is not a field element (>= r)");
   if (csr.err) throw ProverError(PROVER_ERROR, "zkey coefficient record out of range (matrix/constraint/signal)");
   zk->nCoefsLocal = csr.total;
   zk->csr_local = local_rows;
-  zk->d_row_ptr = csr.row_ptr;   // the handle owns the arrays from here (zkpoa_zkey::release)
-  zk->d_sig = csr.sig;
-  zk->d_vals = csr.vals;
-  zk->d_long = csr.long_list;
+  zk->d_row_ptr = std::move(csr.row_ptr);
+  zk->d_sig = std::move(csr.sig);
+  zk->d_vals = std::move(csr.vals);
+  zk->d_long = std::move(csr.long_list);
   zk->n_long = csr.n_long;
-  csr.row_ptr = csr.sig = csr.long_list = nullptr;
-  csr.vals = nullptr;
-}
-
-// split chain: world must be a power of two <= 8 with world^2 <= domain (every rank owns whole slots of
-// every other rank's transform)
-void check_split(const zkpoa_zkey* zk, uint64_t rank, uint64_t world) {
-  if (world < 2 || world > 8 || (world & (world - 1)) || rank >= world)
-    throw ProverError(PROVER_ERROR, "split chain: world must be 2, 4 or 8 and rank < world");
-  if ((uint64_t)zk->domain < world * world)
-    throw ProverError(PROVER_ERROR, "split chain: domain smaller than world^2");
-}
-
-void set_split(zkpoa_zkey* zk, uint64_t rank, uint64_t world) {
-  zk->split_world = (uint32_t)world;
-  zk->split_rank = (uint32_t)rank;
-  zk->split_log = world == 2 ? 1 : (world == 4 ? 2 : 3);
-  zk->h_ready = false;
 }
 
 // this shard's slice of a compacted query: two 4-byte reads of the position array
-void query_set_slice(const zkpoa_zkey* zk, zkpoa_zkey::CompactQuery& q) {
+void query_set_slice(const zkpoa_zkey* zk, CompactQuery& q) {
   uint32_t a = 0, b = 0;
-  ZK_HIP(hipMemcpy(&a, q.pos + (zk->wlo - zk->wbase), 4, hipMemcpyDeviceToHost));
-  ZK_HIP(hipMemcpy(&b, q.pos + (zk->wlo - zk->wbase + zk->wcnt), 4, hipMemcpyDeviceToHost));
+  const uint32_t* pos = q.pos.as<uint32_t>();
+  ZK_HIP(hipMemcpy(&a, pos + (zk->wlo - zk->wbase), 4, hipMemcpyDeviceToHost));
+  ZK_HIP(hipMemcpy(&b, pos + (zk->wlo - zk->wbase + zk->wcnt), 4, hipMemcpyDeviceToHost));
   q.lo = a;
   q.cnt = b - a;
 }
@@ -338,51 +176,49 @@ void queries_set_slice(zkpoa_zkey* zk) {
 }
 
 // Compact the resident range [wbase, wbase + wres) of a query (d1: G1 section, d2: its G2 twin or null) once per key.
-void query_compact(zkpoa_context* ctx, zkpoa_zkey* zk, zkpoa_zkey::CompactQuery& q, const void* d1, const void* d2,
+void query_compact(zkpoa_context* ctx, zkpoa_zkey* zk, CompactQuery& q, const void* d1, const void* d2,
                    uint64_t wres, hipStream_t st_in = nullptr) {
   hipStream_t st = st_in ? st_in : ctx->dev.lanes[0].stream;
   const uint32_t n = (uint32_t)wres;
   DevBuf keep(((size_t)n + 1) * 4), bs(((size_t)n / kScanTile + 2) * 4), misc(64);
-  ZK_HIP(hipMalloc(reinterpret_cast<void**>(&q.pos), ((size_t)n + 1) * 4));
+  q.pos.alloc(((size_t)n + 1) * 4);
+  uint32_t* pos = q.pos.as<uint32_t>();
   ZK_HIP(hipMemsetAsync(misc.p, 0, 64, st));
   uint32_t total = 0;
   if (n) {
     hipLaunchKernelGGL(query_keep_kernel, dim3((n + 255) / 256), dim3(256), 0, st, (const uint4*)d1, (const uint4*)d2, n,
                        (uint32_t*)keep.p);
-    scan_u32(st, (const uint32_t*)keep.p, n, 0, 0, q.pos, (uint32_t*)bs.p, (uint32_t*)misc.p, nullptr);
-    ZK_HIP(hipMemcpyAsync(&total, q.pos + n, 4, hipMemcpyDeviceToHost, st));
+    scan_u32(st, (const uint32_t*)keep.p, n, 0, 0, pos, (uint32_t*)bs.p, (uint32_t*)misc.p, nullptr);
+    ZK_HIP(hipMemcpyAsync(&total, pos + n, 4, hipMemcpyDeviceToHost, st));
   } else {
-    ZK_HIP(hipMemsetAsync(q.pos, 0, 4, st));
+    ZK_HIP(hipMemsetAsync(pos, 0, 4, st));
   }
   ZK_HIP(hipStreamSynchronize(st));
   ZK_HIP(hipGetLastError());
   q.res = total;
   const size_t cnt = total ? total : 1;
-  ZK_HIP(hipMalloc(&q.g1, cnt * 64));
-  if (d2) ZK_HIP(hipMalloc(&q.g2, cnt * 128));
-  ZK_HIP(hipMalloc(&q.scalars, cnt * 32));
-  ZK_HIP(hipMalloc(reinterpret_cast<void**>(&q.wire), cnt * 4));
+  q.g1.alloc(cnt * 64);
+  if (d2) q.g2.alloc(cnt * 128);
+  q.scalars.alloc(cnt * 32);
+  q.wire.alloc(cnt * 4);
   if (n) {
     hipLaunchKernelGGL(query_compact_kernel, dim3((n + 255) / 256), dim3(256), 0, st, (const uint4*)d1, (const uint4*)d2,
-                       (const uint32_t*)q.pos, n, (uint32_t)zk->wbase, zk->bc_log, zk->bc_rank, zk->bc_world, (uint4*)q.g1,
-                       (uint4*)q.g2, q.wire);
+                       (const uint32_t*)pos, n, (uint32_t)zk->wbase, zk->bc_log, zk->bc_rank, zk->bc_world,
+                       q.g1.as<uint4>(), q.g2.as<uint4>(), q.wire.as<uint32_t>());
     ZK_HIP(hipStreamSynchronize(st));
     ZK_HIP(hipGetLastError());
   }
   query_set_slice(zk, q);
 }
 
-// Both witness queries; when the handle owns the sections the originals are freed afterwards (nothing reads
-// them again: the MSMs use the compacted copies).
+// Both witness queries; the originals go afterwards (nothing reads them again: the MSMs use the compacted copies) --
+// freed when they are the handle's own, merely let go of when the caller lent them.
 void queries_compact(zkpoa_context* ctx, zkpoa_zkey* zk, uint64_t wres) {
-  query_compact(ctx, zk, zk->qA, zk->dA, nullptr, wres);
-  query_compact(ctx, zk, zk->qB, zk->dB1, zk->dB2, wres);
-  if (zk->owns_points) {
-    (void)hipFree(zk->dA);
-    (void)hipFree(zk->dB1);
-    (void)hipFree(zk->dB2);
-    zk->dA = zk->dB1 = zk->dB2 = nullptr;
-  }
+  query_compact(ctx, zk, zk->qA, zk->dA.get(), nullptr, wres);
+  query_compact(ctx, zk, zk->qB, zk->dB1.get(), zk->dB2.get(), wres);
+  zk->dA.reset();
+  zk->dB1.reset();
+  zk->dB2.reset();
 }
 
 // the five point sections and the coefficient section of a parsed zkey
@@ -390,8 +226,8 @@ struct ZkeySections {
   Section s4, s5, s6, s7, s8, s9;
 };
 
-// container + header validation; fills the handle's scalar fields, header points and verification key
-std::unique_ptr<zkpoa_zkey> zkey_parse(const uint8_t* buf, uint64_t size, ZkeySections& out) {
+// container + header validation; fills the handle's scalar fields, header points and verification key (host state only)
+KeyPtr zkey_parse(const uint8_t* buf, uint64_t size, ZkeySections& out) {
   Sections secs = parse_binfile(buf, size, "zkey", 2);
   const Section& s1 = need(secs, 1, "1 (protocol)");
   if (s1.len < 4 || rd32(s1.p) != 1) throw ProverError(PROVER_ERROR, "zkey file is not groth16");
@@ -400,7 +236,7 @@ std::unique_ptr<zkpoa_zkey> zkey_parse(const uint8_t* buf, uint64_t size, ZkeySe
   const ZkeyHeader h = read_zkey_header(s2.p);
   if (h.n8q != 32 || !h.q_ok) throw ProverError(PROVER_ERROR, "zkey curve not supported (q is not BN254)");
   if (h.n8r != 32 || !h.r_ok) throw ProverError(PROVER_ERROR, "zkey curve not supported (r is not BN254)");
-  std::unique_ptr<zkpoa_zkey> zk(new zkpoa_zkey());
+  KeyPtr zk(new zkpoa_zkey());
   zk->nVars = h.nVars;
   zk->nPublic = h.nPublic;
   zk->domain = h.domain;
@@ -439,34 +275,6 @@ std::unique_ptr<zkpoa_zkey> zkey_parse(const uint8_t* buf, uint64_t size, ZkeySe
   return zk;
 }
 
-// shard flags of the loaders (include/zkpoa_prover.h ZKPOA_SHARD_*): bit 0 = split chain, bits 8-15 = block-cyclic log
-void set_block_cyclic(zkpoa_zkey* zk, uint64_t rank, uint64_t world, uint32_t bc_log) {
-  if (bc_log == 0 || world <= 1) return;
-  if (bc_log < 4 || bc_log > 24) throw ProverError(PROVER_ERROR, "zkey shard: block-cyclic block size must be 2^4 .. 2^24 items");
-  zk->bc_log = bc_log;
-  zk->bc_rank = (uint32_t)rank;
-  zk->bc_world = (uint32_t)world;
-  zk->wlo = zk->wbase = 0;
-  zk->wcnt = zkpoa_zkey::bc_count(zk->nVars, bc_log, rank, world);
-  zk->clo = zk->cbase = 0;
-  zk->ccnt = zkpoa_zkey::bc_count((uint64_t)zk->nVars - zk->nPublic - 1, bc_log, rank, world);
-}
-
-// A new handle (its sizes set) becomes shard `rank` of `world`; world == 1: the whole key. Host state only: the
-// ranges, whose resident arrays start at the ranges themselves, then the split chain and the block-cyclic deal.
-void shard_init(zkpoa_zkey* zk, uint64_t rank, uint64_t world, bool split, uint32_t bc_log) {
-  if (world == 0 || rank >= world) throw ProverError(PROVER_ERROR, "zkey shard: rank/world out of range");
-  zk->set_shard(rank, world);
-  zk->wbase = zk->wlo; zk->cbase = zk->clo; zk->hbase = zk->hlo;
-  if (split) {
-    check_split(zk, rank, world);
-    set_split(zk, rank, world);
-    zk->hlo = zk->hbase = 0;
-    zk->hcnt = 0;   // no contiguous H range on this handle: its H points are the cyclic shard dHs
-  }
-  set_block_cyclic(zk, rank, world, bc_log);
-}
-
 struct LoadPhases {   // ZKPOA_VERBOSE: where a key load spends its time
   bool verbose = req_getenv("ZKPOA_VERBOSE") != nullptr;
   std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
@@ -481,12 +289,12 @@ struct LoadPhases {   // ZKPOA_VERBOSE: where a key load spends its time
 // the file: those go up only after the queries' originals are freed, and their device copy goes once the CSR exists.
 void finish_load(zkpoa_context* ctx, zkpoa_zkey* zk, const void* recs, bool recs_on_host, bool split, LoadPhases phase) {
   hipStream_t st = ctx->dev.lanes[0].stream;
-  if (zk->bc_log) ZK_HIP(hipMalloc(&zk->d_cscal, zk->ccnt ? zk->ccnt * 32 : 1));
+  if (zk->bc_log) zk->d_cscal.alloc(zk->ccnt * 32);
   queries_compact(ctx, zk, zk->wcnt);
   phase("A / B queries without infinity");
-  std::unique_ptr<void, hipError_t (*)(void*)> uploaded(nullptr, hipFree);
+  DevMem uploaded;
   if (recs_on_host) {
-    uploaded.reset(dev_upload(ctx, recs, zk->nCoefs * 44));
+    uploaded = dev_upload(ctx, recs, zk->nCoefs * 44);
     recs = uploaded.get();
     phase("coefficient section -> HBM");
   }
@@ -499,78 +307,65 @@ void finish_load(zkpoa_context* ctx, zkpoa_zkey* zk, const void* recs, bool recs
   phase("NTT tables");
 }
 
-zkpoa_zkey* zkey_load_impl(zkpoa_context* ctx, const uint8_t* buf, uint64_t size, uint64_t rank = 0,
-                           uint64_t world = 1, bool split = false, uint32_t bc_log = 0) {
+KeyPtr zkey_load_impl(zkpoa_context* ctx, const uint8_t* buf, uint64_t size, uint64_t rank = 0,
+                      uint64_t world = 1, bool split = false, uint32_t bc_log = 0) {
   ZkeySections zs;
-  std::unique_ptr<zkpoa_zkey> zk = zkey_parse(buf, size, zs);
+  KeyPtr zk = zkey_parse(buf, size, zs);
   const Section &s4 = zs.s4, &s5 = zs.s5, &s6 = zs.s6, &s7 = zs.s7, &s8 = zs.s8, &s9 = zs.s9;
   const uint64_t m = zk->nVars;
   shard_init(zk.get(), rank, world, split, bc_log);
+  zk->device = ctx->dev.device;   // from here on the handle holds device memory
   LoadPhases phase;
-  try {
-    // each rank uploads only its byte range(s) of every point section: one contiguous range, or with block-cyclic
-    // shards its blocks of 2^bc_log items one after the other (each still a contiguous byte range of the file)
-    auto upload_items = [&](const uint8_t* sec, uint64_t n_items, uint64_t lo, uint64_t cnt, size_t unit) -> void* {
-      if (!zk->bc_log) return dev_upload(ctx, sec + lo * unit, cnt * unit);
-      void* d = nullptr;
-      ZK_HIP(hipMalloc(&d, cnt ? cnt * unit : 1));
-      try {
-        const uint64_t B = 1ull << zk->bc_log;
-        for (uint64_t lb = 0;; lb++) {
-          const uint64_t start = (lb * world + rank) << zk->bc_log;
-          if (start >= n_items) break;
-          const uint64_t len = n_items - start < B ? n_items - start : B;
-          ctx->uploader.upload(reinterpret_cast<char*>(d) + (lb << zk->bc_log) * unit, sec + start * unit, len * unit,
-                               ctx->dev.device, ctx->dev.lanes[0].stream);
-        }
-      } catch (...) {
-        (void)hipFree(d);
-        throw;
-      }
-      return d;
-    };
-    zk->dA = upload_items(s5.p, m, zk->wlo, zk->wcnt, 64);
-    zk->dB1 = upload_items(s6.p, m, zk->wlo, zk->wcnt, 64);
-    zk->dB2 = upload_items(s7.p, m, zk->wlo, zk->wcnt, 128);
-    zk->dC = upload_items(s8.p, m - zk->nPublic - 1, zk->clo, zk->ccnt, 64);
-    if (split) {
-      // cyclic H shard: H[t * world + rank], gathered on the host (the section is walked once per rank)
-      const uint64_t cnt = zk->h_scalar_count();
-      std::vector<uint8_t> stage(cnt * 64);
-      const unsigned nthreads = 6;
-      std::vector<std::thread> th;
-      for (unsigned k = 0; k < nthreads; k++)
-        th.emplace_back([&, k] {
-          for (uint64_t t = cnt * k / nthreads; t < cnt * (k + 1) / nthreads; t++)
-            memcpy(stage.data() + t * 64, s9.p + (t * world + rank) * 64, 64);
-        });
-      for (auto& t : th) t.join();
-      zk->dHs = dev_upload(ctx, stage.data(), cnt * 64);
-    } else {
-      zk->dH = dev_upload(ctx, s9.p + zk->hlo * 64, zk->hcnt * 64);
+  // each rank uploads only its byte range(s) of every point section: one contiguous range, or with block-cyclic
+  // shards its blocks of 2^bc_log items one after the other (each still a contiguous byte range of the file)
+  auto upload_items = [&](const uint8_t* sec, uint64_t n_items, uint64_t lo, uint64_t cnt, size_t unit) -> DevMem {
+    if (!zk->bc_log) return dev_upload(ctx, sec + lo * unit, cnt * unit);
+    DevMem d;
+    d.alloc(cnt * unit);
+    const uint64_t B = 1ull << zk->bc_log;
+    for (uint64_t lb = 0;; lb++) {
+      const uint64_t start = (lb * world + rank) << zk->bc_log;
+      if (start >= n_items) break;
+      const uint64_t len = n_items - start < B ? n_items - start : B;
+      ctx->uploader.upload(d.as<char>() + (lb << zk->bc_log) * unit, sec + start * unit, len * unit, ctx->dev.device,
+                           ctx->dev.lanes[0].stream);
     }
-    phase("point sections 5-9 -> HBM");
-    {   // every coordinate must be a canonical Fq element (< q)
-      hipStream_t st0 = ctx->dev.lanes[0].stream;
-      DevBuf flag(64);
-      ZK_HIP(hipMemsetAsync(flag.p, 0, 64, st0));
-      range_check<FqParams>(st0, zk->dA, zk->wcnt * 2, (uint32_t*)flag.p);
-      range_check<FqParams>(st0, zk->dB1, zk->wcnt * 2, (uint32_t*)flag.p);
-      range_check<FqParams>(st0, zk->dB2, zk->wcnt * 4, (uint32_t*)flag.p);
-      range_check<FqParams>(st0, zk->dC, zk->ccnt * 2, (uint32_t*)flag.p);
-      range_check<FqParams>(st0, split ? zk->dHs : zk->dH, (split ? zk->h_scalar_count() : zk->hcnt) * 2, (uint32_t*)flag.p);
-      uint32_t bad = 0;
-      ZK_HIP(hipMemcpyAsync(&bad, flag.p, 4, hipMemcpyDeviceToHost, st0));
-      ZK_HIP(hipStreamSynchronize(st0));
-      if (bad) throw ProverError(PROVER_ERROR, "zkey point coordinate is not a field element (>= q)");
-      phase("coordinate range check");
-    }
-    finish_load(ctx, zk.get(), s4.p + 4, /*recs_on_host=*/true, split, phase);
-  } catch (...) {
-    zk->release();
-    throw;
+    return d;
+  };
+  zk->dA = upload_items(s5.p, m, zk->wlo, zk->wcnt, 64);
+  zk->dB1 = upload_items(s6.p, m, zk->wlo, zk->wcnt, 64);
+  zk->dB2 = upload_items(s7.p, m, zk->wlo, zk->wcnt, 128);
+  zk->dC = upload_items(s8.p, m - zk->nPublic - 1, zk->clo, zk->ccnt, 64);
+  if (split) {
+    // cyclic H shard: H[t * world + rank], gathered on the host (the section is walked once per rank)
+    const uint64_t cnt = zk->h_scalar_count();
+    std::vector<uint8_t> stage(cnt * 64);
+    const unsigned nthreads = 6;
+    std::vector<std::thread> th;
+    for (unsigned k = 0; k < nthreads; k++)
+      th.emplace_back([&, k] {
+        for (uint64_t t = cnt * k / nthreads; t < cnt * (k + 1) / nthreads; t++)
+          memcpy(stage.data() + t * 64, s9.p + (t * world + rank) * 64, 64);
+      });
+    for (auto& t : th) t.join();
+    zk->dHs = dev_upload(ctx, stage.data(), cnt * 64);
+  } else {
+    zk->dH = dev_upload(ctx, s9.p + zk->hlo * 64, zk->hcnt * 64);
   }
-  return zk.release();
+  phase("point sections 5-9 -> HBM");
+  {   // every coordinate must be a canonical Fq element (< q)
+    hipStream_t st0 = ctx->dev.lanes[0].stream;
+    DevBuf flag(64);
+    ZK_HIP(hipMemsetAsync(flag.p, 0, 64, st0));
+    for (int sec : {kSecA, kSecB1, kSecB2, kSecC, kSecH}) section_range_check(zk.get(), sec, st0, (uint32_t*)flag.p);
+    uint32_t bad = 0;
+    ZK_HIP(hipMemcpyAsync(&bad, flag.p, 4, hipMemcpyDeviceToHost, st0));
+    ZK_HIP(hipStreamSynchronize(st0));
+    if (bad) throw ProverError(PROVER_ERROR, "zkey point coordinate is not a field element (>= q)");
+    phase("coordinate range check");
+  }
+  finish_load(ctx, zk.get(), s4.p + 4, /*recs_on_host=*/true, split, phase);
+  return zk;
 }
 
 // H-scalar chain on lane.stream: A_T,B_T,C_T -> odd coset -> P (standard form) left in abc[0 .. n)
@@ -601,24 +396,24 @@ void h_chain(zkpoa_context* ctx, hipStream_t st, const uint32_t* row_ptr, const 
 void split_stage1(zkpoa_context* ctx, const zkpoa_zkey* zk, void* d_x) {
   hipStream_t st = ctx->dev.lanes[0].stream;
   const uint32_t M = zk->domain >> zk->split_log, kM = zk->power - zk->split_log, Q = M >> zk->split_log;
-  char* A = reinterpret_cast<char*>(zk->d_abc);
+  char* A = zk->d_abc.as<char>();
   char* B = A + (size_t)M * 32;
   char* C = B + (size_t)M * 32;
   zk->h_ready = false;
   // buildABC for the constraint rows c = rank (mod G): a rank-local CSR is already renumbered
-  hipLaunchKernelGGL(abc_rows_kernel, dim3((M + 255) / 256), dim3(256), 0, st, (const uint32_t*)zk->d_row_ptr,
-                     (const uint32_t*)zk->d_sig, (const void*)zk->d_vals, (const void*)zk->d_witness, M,
+  hipLaunchKernelGGL(abc_rows_kernel, dim3((M + 255) / 256), dim3(256), 0, st, zk->d_row_ptr.as<const uint32_t>(),
+                     zk->d_sig.as<const uint32_t>(), (const void*)zk->d_vals.get(), (const void*)zk->d_witness, M,
                      zk->csr_local ? 0u : zk->split_rank, zk->csr_local ? 1u : zk->split_world, (void*)A, (void*)B,
                      (void*)C);
   if (zk->n_long)   // a rank-local CSR lists its own rows; a full CSR lists all, the kernel keeps c = rank (mod G)
     hipLaunchKernelGGL(abc_long_rows_kernel, dim3((zk->n_long + 3) / 4), dim3(256), 0, st,
-                       (const uint32_t*)zk->d_row_ptr, (const uint32_t*)zk->d_sig, (const void*)zk->d_vals,
-                       (const void*)zk->d_witness, (const uint32_t*)zk->d_long, zk->n_long,
+                       zk->d_row_ptr.as<const uint32_t>(), zk->d_sig.as<const uint32_t>(), (const void*)zk->d_vals.get(),
+                       (const void*)zk->d_witness, zk->d_long.as<const uint32_t>(), zk->n_long,
                        zk->csr_local ? 0u : zk->split_log, zk->csr_local ? 0u : zk->split_rank, (void*)A, (void*)B,
                        (void*)C);
   ntt_dif(ctx, st, A, kM, true, 3, (size_t)M * 32);
   hipLaunchKernelGGL((split_pack_kernel<true>), dim3((uint32_t)(((uint64_t)6 * M + 255) / 256)), dim3(256), 0, st,
-                     (const uint4*)zk->d_abc, (uint4*)d_x, M, Q);
+                     zk->d_abc.as<const uint4>(), (uint4*)d_x, M, Q);
   ZK_HIP(hipGetLastError());
 }
 
@@ -634,14 +429,14 @@ void split_stage2(zkpoa_context* ctx, const zkpoa_zkey* zk, const void* d_in, vo
 void split_stage3(zkpoa_context* ctx, const zkpoa_zkey* zk, const void* d_x) {
   hipStream_t st = ctx->dev.lanes[0].stream;
   const uint32_t M = zk->domain >> zk->split_log, kM = zk->power - zk->split_log, Q = M >> zk->split_log;
-  char* A = reinterpret_cast<char*>(zk->d_abc);
+  char* A = zk->d_abc.as<char>();
   char* B = A + (size_t)M * 32;
   char* C = B + (size_t)M * 32;
   hipLaunchKernelGGL((split_pack_kernel<false>), dim3((uint32_t)(((uint64_t)6 * M + 255) / 256)), dim3(256), 0, st,
-                     (const uint4*)d_x, (uint4*)zk->d_abc, M, Q);
+                     (const uint4*)d_x, zk->d_abc.as<uint4>(), M, Q);
   ntt_dit(ctx, st, A, kM, false, 3, (size_t)M * 32);
   hipLaunchKernelGGL(abc_join_kernel, dim3((M + 255) / 256), dim3(256), 0, st, (const void*)A, (const void*)B,
-                     (const void*)C, M, zk->d_abc);
+                     (const void*)C, M, zk->d_abc.get());
   ZK_HIP(hipGetLastError());
   zk->h_ready = true;   // in stream order: the H MSM of zkpoa_prove_partials_device runs on the same stream
 }
@@ -790,30 +585,30 @@ StageView stage_view(const zkpoa_zkey* zk, int stage) {
   const MsmTable* t = nullptr;
   uint64_t first = 0;   // of these points, in bytes from the start of the array
   if (stage == kStageH && zk->split_world > 1) {   // the cyclic shard, all of it
-    v.array = zk->dHs;
+    v.array = zk->dHs.get();
     v.n = v.array_n = zk->h_scalar_count();
-    t = zk->tH_cyclic ? zk->tH : nullptr;
+    t = zk->tH_cyclic ? zk->tH.get() : nullptr;
   } else if (stage == kStageH) {
-    v.array = zk->dH;
+    v.array = zk->dH.get();
     v.n = zk->hcnt;
     first = (zk->hlo - zk->hbase) * 64;
     v.array_n = first ? 0 : v.n;
     v.scalar_off = zk->hlo;
-    t = zk->tH_cyclic ? nullptr : zk->tH;
+    t = zk->tH_cyclic ? nullptr : zk->tH.get();
   } else if (stage == kStageC) {
-    v.array = zk->dC;
+    v.array = zk->dC.get();
     v.n = zk->ccnt;
     first = (zk->clo - zk->cbase) * 64;
     v.array_n = first ? 0 : v.n;
     v.scalar_off = zk->clo;
-    t = zk->tC;
+    t = zk->tC.get();
   } else {
-    const zkpoa_zkey::CompactQuery& q = stage == kStageA ? zk->qA : zk->qB;
-    v.array = stage == kStageB2 ? q.g2 : q.g1;
+    const CompactQuery& q = stage == kStageA ? zk->qA : zk->qB;
+    v.array = stage == kStageB2 ? q.g2.get() : q.g1.get();
     v.n = q.cnt;
     v.array_n = q.res;
     first = q.lo * (stage == kStageB2 ? 128 : 64);
-    t = stage == kStageA ? zk->tA : !(zk->tB1 && zk->tB2) ? nullptr : stage == kStageB1 ? zk->tB1 : zk->tB2;
+    t = stage == kStageA ? zk->tA.get() : !(zk->tB1 && zk->tB2) ? nullptr : stage == kStageB1 ? zk->tB1.get() : zk->tB2.get();
   }
   if (v.array) v.bases = reinterpret_cast<const char*>(v.array) + first;
   else v.array_n = 0;
@@ -870,7 +665,7 @@ uint64_t zkey_precompute(zkpoa_context* ctx, zkpoa_zkey* zk, uint64_t budget, in
   // One list of the tables this handle could have, most valuable first (B1 and B2 are one step). n = 0: nothing to
   // build from -- an empty or absent array, or a range of section 8 / 9 that is not the whole resident array.
   struct Candidate {
-    MsmTable** slot;
+    MsmTablePtr* slot;
     bool g2;
     const void* bases;
     uint64_t n;
@@ -886,12 +681,11 @@ uint64_t zkey_precompute(zkpoa_context* ctx, zkpoa_zkey* zk, uint64_t budget, in
     }
     built++;
     try {
-      *t.slot = t.g2 ? msm_table_build_g2(ctx, t.bases, t.n, t.c) : msm_table_build_g1(ctx, t.bases, t.n, t.c);
+      t.slot->reset(t.g2 ? msm_table_build_g2(ctx, t.bases, t.n, t.c) : msm_table_build_g1(ctx, t.bases, t.n, t.c));
       zk->table_bytes += t.bytes();
       return true;
     } catch (const HipError&) {
       (void)hipGetLastError();
-      *t.slot = nullptr;
       return false;
     }
   };
@@ -906,7 +700,7 @@ uint64_t zkey_precompute(zkpoa_context* ctx, zkpoa_zkey* zk, uint64_t budget, in
   };
   msm_set_density_hint(nullptr);
   // (one window width for both B tables: the G2 model's -- shorter pieces -- as the shared sort is planned for G2)
-  auto candidate = [&](MsmTable** slot, int stage) {
+  auto candidate = [&](MsmTablePtr* slot, int stage) {
     const StageView v = stage_view(zk, stage);
     const int c = stage == kStageH ? force_c : v.array_n ? witness_c(v.array_n, stage == kStageB1 || stage == kStageB2) : 0;
     return Candidate{slot, stage == kStageB2, v.array, v.array_n, c};
@@ -942,8 +736,7 @@ uint64_t zkey_precompute(zkpoa_context* ctx, zkpoa_zkey* zk, uint64_t budget, in
       more = build(tB1) && build(tB2);
       if (!more && zk->tB1) {   // the pair is only usable together
         zk->table_bytes -= tB1.bytes();
-        msm_table_release(zk->tB1);
-        zk->tB1 = nullptr;
+        zk->tB1.reset();
       }
     }
   }
@@ -1058,7 +851,7 @@ static void budget_lane_workspaces(zkpoa_context* ctx, const zkpoa_zkey* zk) {
 // prove_partials first waits for the sections it needs and finishes their key-side preparation on its own lane.
 struct Staging {
   std::function<void()> prep_chain, prep_H, prep_A, prep_B, prep_C;
-  std::vector<void*> sinks[5];   // temporaries parked until the proof is done (hipFree waits for the whole device)
+  std::vector<void*> sinks[5];   // temporaries parked until the proof is done (freeing waits for the whole device)
 };
 
 void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], Staging* stg = nullptr) {
@@ -1107,7 +900,7 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
     std::call_once(density_once, [&] {
       if (zk->have_density) return;
       msm_density(ctx->dev.lanes[lane_id].stream, zk->d_witness, zk->nVars, zk->witness_density,
-                  reinterpret_cast<char*>(zk->d_flag) + 256);
+                  zk->d_flag.as<char>() + 256);
       zk->have_density = true;
     });
     return zk->have_density ? zk->witness_density : nullptr;
@@ -1118,11 +911,11 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
     if (!zk->have_density) (void)with_density(1);
     budget_lane_workspaces(ctx, zk);
   }
-  auto gather = [&](int lane_id, const zkpoa_zkey::CompactQuery& q) {
+  auto gather = [&](int lane_id, const CompactQuery& q) {
     if (q.cnt)
       hipLaunchKernelGGL(gather32_kernel, dim3((uint32_t)((q.cnt * 2 + 255) / 256)), dim3(256), 0,
-                         ctx->dev.lanes[lane_id].stream, (const uint4*)zk->d_witness, (const uint32_t*)q.wire + q.lo,
-                         q.cnt, (uint4*)q.scalars);
+                         ctx->dev.lanes[lane_id].stream, (const uint4*)zk->d_witness, q.wire.as<const uint32_t>() + q.lo,
+                         q.cnt, q.scalars.as<uint4>());
   };
   // opt_prove_serial (measurement only): every stage runs alone, one after the other, so the per-stage device times
   // are solo times and their sum / the overlapped wall time says how much the five lanes gain (bench.py).
@@ -1133,7 +926,7 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
     if (!zk->d_witness || !zk->qA.g1 || !zk->qA.scalars) throw ProverError(PROVER_ERROR, "internal: A stage started before its inputs");
     msm_set_density_hint(with_density(1));
     gather(1, zk->qA);
-    msm_run_g1(ctx, 1, vA.bases, zk->qA.scalars, vA.n, outA, msm_ms[1], vA.table);
+    msm_run_g1(ctx, 1, vA.bases, zk->qA.scalars.get(), vA.n, outA, msm_ms[1], vA.table);
   });
   if (serial) tA.join();
   // (a B query beyond the 32-bit entry index of one sort cannot share it: two chunked MSMs instead)
@@ -1157,7 +950,7 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
       auto ts0 = std::chrono::steady_clock::now();
       if (share_b) {
         try {
-          sr = msm_sort_run(ctx, 2, zk->qB.scalars, zk->qB.cnt, true, table_c_b);
+          sr = msm_sort_run(ctx, 2, zk->qB.scalars.get(), zk->qB.cnt, true, table_c_b);
         } catch (const OomError& e) {   // no room for the whole query's sort: B1 and B2 each go through it in pieces
           if (!ctx->shrink_after_oom(2, zk->qB.cnt)) throw;
           if (getenv("ZKPOA_VERBOSE")) fprintf(stderr, "zkpoa:   B query: %s; B1 and B2 sort their own pieces\n", e.what());
@@ -1173,7 +966,7 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
       throw;
     }
     if (share_b) msm_accum_g1(ctx, 2, sr, true, table_c_b ? msm_table_data(vB1.table) : vB1.bases, outB1, msm_ms[2]);
-    else msm_run_g1(ctx, 2, vB1.bases, zk->qB.scalars, vB1.n, outB1, msm_ms[2]);
+    else msm_run_g1(ctx, 2, vB1.bases, zk->qB.scalars.get(), vB1.n, outB1, msm_ms[2]);
     if (share_b) msm_ms[2][0] += sort_b_ms;
   });
   if (serial) tB1.join();
@@ -1190,7 +983,7 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
         shared = false;
       }
     }
-    if (!shared) msm_run_g2(ctx, 3, vB2.bases, zk->qB.scalars, vB2.n, outB2, msm_ms[3]);
+    if (!shared) msm_run_g2(ctx, 3, vB2.bases, zk->qB.scalars.get(), vB2.n, outB2, msm_ms[3]);
   });
   if (serial) tB2.join();
   std::thread tC = guarded(3, [&] {
@@ -1203,8 +996,8 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
         hipLaunchKernelGGL(gather_bc32_kernel, dim3((uint32_t)((zk->ccnt * 2 + 255) / 256)), dim3(256), 0,
                            ctx->dev.lanes[4].stream,
                            reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(zk->d_witness) + ((uint64_t)zk->nPublic + 1) * 32),
-                           zk->ccnt, zk->bc_log, zk->bc_rank, zk->bc_world, (uint4*)zk->d_cscal);
-      witC = reinterpret_cast<const char*>(zk->d_cscal);
+                           zk->ccnt, zk->bc_log, zk->bc_rank, zk->bc_world, zk->d_cscal.as<uint4>());
+      witC = zk->d_cscal.as<const char>();
     }
     msm_set_density_hint(with_density(4));
     msm_run_g1(ctx, 4, vC.bases, witC, vC.n, outC, msm_ms[4], vC.table);
@@ -1219,22 +1012,22 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
     if (!zk->d_witness || !zk->d_flag || (!split && (!zk->d_abc || !zk->d_row_ptr)))
       throw ProverError(PROVER_ERROR, "internal: chain stage started before its inputs");
     // witness values must be canonical (< r): one streaming pass on the chain's lane, flag read with the H MSM's results
-    ZK_HIP(hipMemsetAsync(zk->d_flag, 0, 4, l0.stream));
-    range_check<FrParams>(l0.stream, zk->d_witness, zk->nVars, zk->d_flag);
+    ZK_HIP(hipMemsetAsync(zk->d_flag.get(), 0, 4, l0.stream));
+    range_check<FrParams>(l0.stream, zk->d_witness, zk->nVars, zk->d_flag.as<uint32_t>());
     ZK_HIP(hipEventRecord(ctx->ev_a[5], l0.stream));
     if (!split)
-      h_chain(ctx, l0.stream, zk->d_row_ptr, zk->d_sig, zk->d_vals, zk->d_long, zk->n_long, zk->d_witness, zk->domain,
-              zk->power, zk->d_abc);
+      h_chain(ctx, l0.stream, zk->d_row_ptr.as<uint32_t>(), zk->d_sig.as<uint32_t>(), zk->d_vals.get(),
+              zk->d_long.as<uint32_t>(), zk->n_long, zk->d_witness, zk->domain, zk->power, zk->d_abc.get());
     ZK_HIP(hipEventRecord(ctx->ev_b[5], l0.stream));
     if (stg && stg->prep_H) stg->prep_H();
     const StageView vH = stage_view(zk, kStageH);
     if (vH.n && !vH.bases) throw ProverError(PROVER_ERROR, "internal: H stage started before its inputs");
     // (a split handle: the three stages left this rank's H scalars, odd-coset indices = rank mod G, in d_abc[0 .. n/G))
-    msm_run_g1(ctx, 0, vH.bases, reinterpret_cast<const char*>(zk->d_abc) + vH.scalar_off * 32, vH.n, outH, msm_ms[0],
+    msm_run_g1(ctx, 0, vH.bases, zk->d_abc.as<const char>() + vH.scalar_off * 32, vH.n, outH, msm_ms[0],
                vH.table);
     if (split) zk->h_ready = false;
     ZK_HIP(hipEventElapsedTime(&ctx->ms[3], ctx->ev_a[5], ctx->ev_b[5]));
-    msm_read_back(l0, zk->d_flag, 4);   // lane 0 is idle (its MSM has returned): the flag through its pinned buffer
+    msm_read_back(l0, zk->d_flag.get(), 4);   // lane 0 is idle (its MSM has returned): the flag through its pinned buffer
     witness_bad = *reinterpret_cast<const uint32_t*>(l0.pinned);
   } catch (...) {
     main_err = std::current_exception();
@@ -1297,19 +1090,6 @@ void prove_assemble(const HeaderPoints& h, const uint8_t sums[384], const uint8_
   h_affine_to_bytes<HFq>(h_to_affine(pi_a), proof_points);
   h_affine_to_bytes<HFq2>(h_to_affine(pi_b), proof_points + 64);
   h_affine_to_bytes<HFq>(h_to_affine(pi_c), proof_points + 192);
-}
-
-void zkey_header_bytes(const zkpoa_zkey* zk, uint8_t out[448]) {
-  h_affine_to_bytes<HFq>(zk->hdr.alpha1, out);
-  h_affine_to_bytes<HFq>(zk->hdr.beta1, out + 64);
-  h_affine_to_bytes<HFq2>(zk->hdr.beta2, out + 128);
-  h_affine_to_bytes<HFq>(zk->hdr.delta1, out + 256);
-  h_affine_to_bytes<HFq2>(zk->hdr.delta2, out + 320);
-}
-
-bool is_full_key(const zkpoa_zkey* zk) {
-  return zk->split_world <= 1 && zk->wlo == 0 && zk->wcnt == zk->nVars && zk->clo == 0 && zk->ccnt == (uint64_t)zk->nVars - zk->nPublic - 1 &&
-         zk->hlo == 0 && zk->hcnt == zk->domain;
 }
 
 // the partial sums of a whole key -> proof points; ctx->ms[5] <- the prove time, counted from t0
@@ -1407,17 +1187,23 @@ void prove_impl(zkpoa_context* ctx, const zkpoa_zkey* zk, const WtnsSrc& wsrc,
 // max(upload, compute) + the C MSM instead of upload + compute. Returns the loaded key (complete, reusable: the cache
 // keeps it) with `parts` = the five MSM results; nullptr when no copy stream could be created (caller: plain path).
 // zkey_fd >= 0: the file `buf` maps; the sections are then read with pread instead of through the mapping.
-zkpoa_zkey* load_prove_staged(zkpoa_context* ctx, const uint8_t* buf, uint64_t size, const WtnsView& w, uint8_t parts[384],
-                              int zkey_fd = -1) {
+//
+// What is destroyed when, on the way out -- the one place where the order matters, so it is the declaration order: the
+// handle `zk` is declared first and therefore goes LAST. Before it, in reverse order of declaration: `ending` cancels
+// and joins the uploader (nobody writes into the handle's arrays any more), drains the device and frees the parked
+// temporaries; then the staging hooks, the record and flag temporaries and the hold-back go; only then, on failure,
+// the handle frees its arrays (on success it has been moved out to the caller).
+KeyPtr load_prove_staged(zkpoa_context* ctx, const uint8_t* buf, uint64_t size, const WtnsView& w, uint8_t parts[384],
+                         int zkey_fd = -1) {
   hipStream_t cs = ctx->dev.copy_stream_wait();
   if (!cs) return nullptr;
   ZkeySections zs;
-  std::unique_ptr<zkpoa_zkey> zk = zkey_parse(buf, size, zs);
+  KeyPtr zk = zkey_parse(buf, size, zs);
   check_witness_len(w, zk.get());
   shard_init(zk.get(), 0, 1, false, 0);   // the whole key
   const uint64_t m = zk->nVars, n = zk->domain, nC = m - zk->nPublic - 1;
   {
-    // What the overlapped form holds at its peak: the sections AND the compacted copies of the A / B queries (a hipFree
+    // What the overlapped form holds at its peak: the sections AND the compacted copies of the A / B queries (freeing
     // would wait for the whole device, so the originals are only given back after the proof), the coefficient records
     // AND their CSR form, the chain's work area, the witness -- plus the lanes' workspaces. A key for which that leaves
     // the lanes less than a quarter of the card (2^28: 247 of 309 GB; 2^27: 125) is loaded first and proved afterwards (the caller's
@@ -1445,8 +1231,8 @@ zkpoa_zkey* load_prove_staged(zkpoa_context* ctx, const uint8_t* buf, uint64_t s
   } hold(ctx->key_hold_back, (double)n * 64 + (double)m * 256 + (double)nC * 64 + (double)zk->nCoefs * 36 +
                                (double)n * (8 + 96) + (double)m * (108 + 236));
   zkpoa_zkey* k = zk.get();
-  void* d_recs = nullptr;
-  uint32_t* d_cflag = nullptr;
+  k->device = ctx->dev.device;   // from here on the handle holds device memory
+  DevMem d_recs, d_cflag;   // the coefficient records until the CSR exists; the flag word of the coordinate checks
   enum { S_WIT, S_COEF, S_H, S_B1, S_B2, S_A, S_C, S_COUNT };
   std::promise<void> ready[S_COUNT];
   std::shared_future<void> have[S_COUNT];
@@ -1462,131 +1248,130 @@ zkpoa_zkey* load_prove_staged(zkpoa_context* ctx, const uint8_t* buf, uint64_t s
   };
   auto cleanup_temps = [&] {
     (void)hipDeviceSynchronize();
-    for (auto& v : stg.sinks) {
-      for (void* p : v) (void)hipFree(p);
-      v.clear();
-    }
-    if (d_recs) (void)hipFree(d_recs);
-    if (d_cflag) (void)hipFree(d_cflag);
-    d_recs = nullptr;
-    d_cflag = nullptr;
+    for (auto& v : stg.sinks) free_deferred(v);
   };
-  try {
-    auto alloc = [](void** p, uint64_t bytes) { ZK_HIP(hipMalloc(p, bytes ? bytes : 1)); };
-    alloc(reinterpret_cast<void**>(&d_cflag), 64);
-    ZK_HIP(hipMemsetAsync(d_cflag, 0, 64, ctx->dev.lanes[0].stream));   // stream-ordered, then waited for: the range checks
-    ZK_HIP(hipStreamSynchronize(ctx->dev.lanes[0].stream));              // that OR into it run on other (non-blocking) streams
-    alloc(&k->d_witness, m * 32);
-    alloc(&d_recs, zk->nCoefs * 44);
-    alloc(reinterpret_cast<void**>(&k->d_flag), 1024);
-    // each buffer is allocated by the uploader right before its section moves (hipMalloc of GBs is milliseconds each)
-    struct Item { int id; void** dst; const uint8_t* src; uint64_t bytes; };
-    const Item items[S_COUNT] = {
-        {S_WIT, &k->d_witness, w.values /* null: from w.fd */, m * 32}, {S_COEF, &d_recs, zs.s4.p + 4, zk->nCoefs * 44},
-        {S_H, &k->dH, zs.s9.p, n * 64},           {S_B1, &k->dB1, zs.s6.p, m * 64},
-        {S_B2, &k->dB2, zs.s7.p, m * 128},        {S_A, &k->dA, zs.s5.p, m * 64},
-        {S_C, &k->dC, zs.s8.p, nC * 64}};
-    uploader = std::thread([&] {
-      int i = 0;
-      try {
-        ZK_HIP(hipSetDevice(ctx->dev.device));
-        for (; i < S_COUNT; i++) {
-          if (cancel.load()) throw ProverError(PROVER_ERROR, "upload cancelled");
-          if (!*items[i].dst) {
-            ZK_HIP(hipMalloc(items[i].dst, items[i].bytes ? items[i].bytes : 1));
-            hold.done((double)items[i].bytes);
-          }
-          if (items[i].bytes) {
-            if (items[i].id == S_WIT && w.fd >= 0) {   // file-backed witness: pread into the pinned staging buffers
-              std::vector<uint8_t> small;
-              if (items[i].bytes < (4u << 20)) {
-                small.resize(items[i].bytes);
-                w.read(0, w.n, small.data());
-                ZK_HIP(hipMemcpyAsync(*items[i].dst, small.data(), items[i].bytes, hipMemcpyHostToDevice, cs));
-                ZK_HIP(hipStreamSynchronize(cs));
-              } else {
-                ctx->uploader.upload(*items[i].dst, nullptr, items[i].bytes, ctx->dev.device, cs, w.fd, w.off);
-              }
-            } else if (items[i].bytes < (4u << 20)) {   // small: one asynchronous copy on the copy stream (no null-stream copy here)
-              ZK_HIP(hipMemcpyAsync(*items[i].dst, items[i].src, items[i].bytes, hipMemcpyHostToDevice, cs));
+  struct Ending {   // however the function is left (the success path has done all of it already)
+    std::atomic<bool>& cancel;
+    std::thread& uploader;
+    std::function<void()> cleanup;
+    bool done = false;
+    ~Ending() {
+      if (done) return;
+      cancel.store(true);
+      if (uploader.joinable()) uploader.join();
+      cleanup();
+    }
+  } ending{cancel, uploader, cleanup_temps};
+  d_cflag.alloc(64);
+  uint32_t* const cflag = d_cflag.as<uint32_t>();
+  ZK_HIP(hipMemsetAsync(cflag, 0, 64, ctx->dev.lanes[0].stream));   // stream-ordered, then waited for: the range checks
+  ZK_HIP(hipStreamSynchronize(ctx->dev.lanes[0].stream));            // that OR into it run on other (non-blocking) streams
+  k->wbuf[0].alloc(m * 32);
+  k->d_witness = k->wbuf[0].get();
+  d_recs.alloc(zk->nCoefs * 44);
+  k->d_flag.alloc(1024);
+  // each buffer is allocated by the uploader right before its section moves (hipMalloc of GBs is milliseconds each)
+  struct Item { int id; DevMem* dst; const uint8_t* src; uint64_t bytes; };
+  const Item items[S_COUNT] = {
+      {S_WIT, &k->wbuf[0], w.values /* null: from w.fd */, m * 32}, {S_COEF, &d_recs, zs.s4.p + 4, zk->nCoefs * 44},
+      {S_H, &k->dH, zs.s9.p, n * 64},           {S_B1, &k->dB1, zs.s6.p, m * 64},
+      {S_B2, &k->dB2, zs.s7.p, m * 128},        {S_A, &k->dA, zs.s5.p, m * 64},
+      {S_C, &k->dC, zs.s8.p, nC * 64}};
+  uploader = std::thread([&] {
+    int i = 0;
+    try {
+      ZK_HIP(hipSetDevice(ctx->dev.device));
+      for (; i < S_COUNT; i++) {
+        if (cancel.load()) throw ProverError(PROVER_ERROR, "upload cancelled");
+        const Item& it = items[i];
+        if (!*it.dst) {
+          it.dst->alloc(it.bytes);
+          hold.done((double)it.bytes);
+        }
+        if (it.bytes) {
+          if (it.id == S_WIT && w.fd >= 0) {   // file-backed witness: pread into the pinned staging buffers
+            std::vector<uint8_t> small;
+            if (it.bytes < (4u << 20)) {
+              small.resize(it.bytes);
+              w.read(0, w.n, small.data());
+              ZK_HIP(hipMemcpyAsync(it.dst->get(), small.data(), it.bytes, hipMemcpyHostToDevice, cs));
               ZK_HIP(hipStreamSynchronize(cs));
             } else {
-              const bool from_file = zkey_fd >= 0 && items[i].src >= buf && items[i].src < buf + size;
-              ctx->uploader.upload(*items[i].dst, items[i].src, items[i].bytes, ctx->dev.device, cs,
-                                   from_file ? zkey_fd : -1, from_file ? (uint64_t)(items[i].src - buf) : 0);
+              ctx->uploader.upload(it.dst->get(), nullptr, it.bytes, ctx->dev.device, cs, w.fd, w.off);
             }
+          } else if (it.bytes < (4u << 20)) {   // small: one asynchronous copy on the copy stream (no null-stream copy here)
+            ZK_HIP(hipMemcpyAsync(it.dst->get(), it.src, it.bytes, hipMemcpyHostToDevice, cs));
+            ZK_HIP(hipStreamSynchronize(cs));
+          } else {
+            const bool from_file = zkey_fd >= 0 && it.src >= buf && it.src < buf + size;
+            ctx->uploader.upload(it.dst->get(), it.src, it.bytes, ctx->dev.device, cs, from_file ? zkey_fd : -1,
+                                 from_file ? (uint64_t)(it.src - buf) : 0);
           }
-          ready[items[i].id].set_value();
-          static const char* kNames[S_COUNT] = {"witness resident", "section 4 resident", "section 9 (H) resident",
-                                                "section 6 (B1) resident", "section 7 (B2) resident",
-                                                "section 5 (A) resident", "section 8 (C) resident"};
-          mark(kNames[items[i].id]);
         }
-      } catch (...) {
-        for (; i < S_COUNT; i++) ready[items[i].id].set_exception(std::current_exception());
+        ready[it.id].set_value();
+        static const char* kNames[S_COUNT] = {"witness resident", "section 4 resident", "section 9 (H) resident",
+                                              "section 6 (B1) resident", "section 7 (B2) resident",
+                                              "section 5 (A) resident", "section 8 (C) resident"};
+        mark(kNames[it.id]);
       }
-    });
-    ctx->dev.wait_lanes();   // the other lanes come up in the background while the first sections are already moving
-    Lane* L = ctx->dev.lanes;
-    stg.prep_chain = [&, k] {
-      have[S_WIT].get();
-      have[S_COEF].get();
-      build_csr(ctx, k, d_recs, false, L[0].stream);
-      ntt_prepare(ctx, L[0].stream, k->power);
-      hold.done((double)k->nCoefs * 36 + (double)n * (8 + 96));
-      mark("CSR + NTT tables built, H-scalar chain starts");
-    };
-    stg.prep_H = [&, k] {
-      mark("H-scalar chain enqueued");
-      have[S_H].get();
-      range_check<FqParams>(L[0].stream, k->dH, n * 2, d_cflag);
-    };
-    stg.prep_A = [&, k] {
-      have[S_WIT].get();
-      have[S_A].get();
-      range_check<FqParams>(L[1].stream, k->dA, m * 2, d_cflag);
-      query_compact(ctx, k, k->qA, k->dA, nullptr, m, L[1].stream);
-      hold.done((double)m * 108);
-      mark("A query compacted, A MSM starts");
-    };
-    stg.prep_B = [&, k] {
-      have[S_WIT].get();
-      have[S_B1].get();
-      have[S_B2].get();
-      range_check<FqParams>(L[2].stream, k->dB1, m * 2, d_cflag);
-      range_check<FqParams>(L[2].stream, k->dB2, m * 4, d_cflag);
-      query_compact(ctx, k, k->qB, k->dB1, k->dB2, m, L[2].stream);
-      hold.done((double)m * 236);
-      mark("B query compacted, B MSMs start");
-    };
-    stg.prep_C = [&, k] {
-      have[S_WIT].get();
-      have[S_C].get();
-      range_check<FqParams>(L[4].stream, k->dC, nC * 2, d_cflag);
-    };
-    mark("lanes up");
-    prove_partials(ctx, k, parts, &stg);
-    mark("all five MSMs done");
-    uploader.join();
-    uint32_t bad = 0;
-    ZK_HIP(hipDeviceSynchronize());
-    ZK_HIP(hipMemcpy(&bad, d_cflag, 4, hipMemcpyDeviceToHost));
-    if (bad) throw ProverError(PROVER_ERROR, "zkey point coordinate is not a field element (>= q)");
-    // the originals of the compacted queries are not read again
-    stg.sinks[4].push_back(k->dA);
-    stg.sinks[4].push_back(k->dB1);
-    stg.sinks[4].push_back(k->dB2);
-    k->dA = k->dB1 = k->dB2 = nullptr;
-    cleanup_temps();
-    mark("temporaries freed");
-  } catch (...) {
-    cancel.store(true);
-    if (uploader.joinable()) uploader.join();
-    cleanup_temps();
-    zk->release();
-    throw;
-  }
-  return zk.release();
+    } catch (...) {
+      for (; i < S_COUNT; i++) ready[items[i].id].set_exception(std::current_exception());
+    }
+  });
+  ctx->dev.wait_lanes();   // the other lanes come up in the background while the first sections are already moving
+  Lane* L = ctx->dev.lanes;
+  // (every coordinate check runs on the lane of the stage that reads the section)
+  stg.prep_chain = [&, k] {
+    have[S_WIT].get();
+    have[S_COEF].get();
+    build_csr(ctx, k, d_recs.get(), false, L[0].stream);
+    ntt_prepare(ctx, L[0].stream, k->power);
+    hold.done((double)k->nCoefs * 36 + (double)n * (8 + 96));
+    mark("CSR + NTT tables built, H-scalar chain starts");
+  };
+  stg.prep_H = [&, k] {
+    mark("H-scalar chain enqueued");
+    have[S_H].get();
+    section_range_check(k, kSecH, L[0].stream, cflag);
+  };
+  stg.prep_A = [&, k] {
+    have[S_WIT].get();
+    have[S_A].get();
+    section_range_check(k, kSecA, L[1].stream, cflag);
+    query_compact(ctx, k, k->qA, k->dA.get(), nullptr, m, L[1].stream);
+    hold.done((double)m * 108);
+    mark("A query compacted, A MSM starts");
+  };
+  stg.prep_B = [&, k] {
+    have[S_WIT].get();
+    have[S_B1].get();
+    have[S_B2].get();
+    section_range_check(k, kSecB1, L[2].stream, cflag);
+    section_range_check(k, kSecB2, L[2].stream, cflag);
+    query_compact(ctx, k, k->qB, k->dB1.get(), k->dB2.get(), m, L[2].stream);
+    hold.done((double)m * 236);
+    mark("B query compacted, B MSMs start");
+  };
+  stg.prep_C = [&, k] {
+    have[S_WIT].get();
+    have[S_C].get();
+    section_range_check(k, kSecC, L[4].stream, cflag);
+  };
+  mark("lanes up");
+  prove_partials(ctx, k, parts, &stg);
+  mark("all five MSMs done");
+  uploader.join();
+  uint32_t bad = 0;
+  ZK_HIP(hipDeviceSynchronize());
+  ZK_HIP(hipMemcpy(&bad, cflag, 4, hipMemcpyDeviceToHost));
+  if (bad) throw ProverError(PROVER_ERROR, "zkey point coordinate is not a field element (>= q)");
+  // the originals of the compacted queries are not read again: they go with the parked temporaries (take() + push_back,
+  // the one way a member of the handle ever gets into a sink)
+  for (DevMem* sec : {&k->dA, &k->dB1, &k->dB2}) stg.sinks[4].push_back(sec->take());
+  cleanup_temps();
+  ending.done = true;
+  mark("temporaries freed");
+  return zk;
 }
 
 #include "multi_device.hip.h"   // several GPUs: the device set of the process, sharded keys and their proof
@@ -1615,7 +1400,7 @@ template <class... Shard>
 static int zkey_load_abi(zkpoa_context* ctx, const void* zkey_buffer, unsigned long zkey_size, zkpoa_zkey** out, Shard... shard) {
   if (!ctx || !out || !zkey_buffer) return PROVER_ERROR;
   *out = nullptr;
-  return abi_call(ctx, [&] { *out = zkey_load_impl(ctx, static_cast<const uint8_t*>(zkey_buffer), zkey_size, shard...); });
+  return abi_call(ctx, [&] { *out = zkey_load_impl(ctx, static_cast<const uint8_t*>(zkey_buffer), zkey_size, shard...).release(); });
 }
 
 extern "C" int zkpoa_zkey_load(zkpoa_context* ctx, const void* zkey_buffer, unsigned long zkey_size, zkpoa_zkey** out) {
@@ -1636,12 +1421,6 @@ extern "C" int zkpoa_zkey_load_shard_ex(zkpoa_context* ctx, const void* zkey_buf
                                         uint64_t rank, uint64_t world, int flags, zkpoa_zkey** out) {
   return zkey_load_abi(ctx, zkey_buffer, zkey_size, out, rank, world, (flags & ZKPOA_SHARD_SPLIT_CHAIN) != 0,
                        ZKPOA_SHARD_BLOCK_LOG(flags));
-}
-
-// Can the handle be re-pointed at another shard? Only when every section is resident from its first item in file
-// order (loaded whole, not block-cyclic) and the CSR holds every row.
-static bool resident_unsharded(const zkpoa_zkey* zk) {
-  return !(zk->wbase || zk->cbase || zk->hbase || zk->csr_local || !zk->dH || zk->bc_log);
 }
 
 extern "C" int zkpoa_zkey_set_shard(zkpoa_zkey* zkey, uint64_t rank, uint64_t world) {
@@ -1666,13 +1445,9 @@ extern "C" int zkpoa_zkey_set_shard_split(zkpoa_context* ctx, zkpoa_zkey* zkey, 
     hipStream_t st = ctx->dev.lanes[0].stream;
     const uint64_t cnt = zkpoa_zkey::split_h_count(zkey->domain, world);
     zkey->release_cyclic_h_table();
-    if (zkey->dHs) {
-      ZK_HIP(hipFree(zkey->dHs));
-      zkey->dHs = nullptr;
-    }
-    ZK_HIP(hipMalloc(&zkey->dHs, cnt * 64));
+    zkey->dHs.alloc(cnt * 64);   // (the old shard is freed first)
     hipLaunchKernelGGL(strided_copy64_kernel, dim3((uint32_t)((cnt * 4 + 255) / 256)), dim3(256), 0, st,
-                       (const uint4*)zkey->dH, (uint4*)zkey->dHs, cnt, (uint32_t)rank, (uint32_t)world);
+                       zkey->dH.as<const uint4>(), zkey->dHs.as<uint4>(), cnt, (uint32_t)rank, (uint32_t)world);
     zkey->set_shard(rank, world);
     queries_set_slice(zkey);
     set_split(zkey, rank, world);
@@ -1799,15 +1574,7 @@ extern "C" int zkpoa_prove_assemble(const uint8_t header_points[448], const uint
   return PROVER_OK;
 }
 
-extern "C" void zkpoa_zkey_free(zkpoa_context* ctx, zkpoa_zkey* zkey) {
-  if (!zkey) return;
-  if (ctx) {
-    (void)hipSetDevice(ctx->dev.device);
-    (void)hipDeviceSynchronize();
-  }
-  zkey->release();
-  delete zkey;
-}
+extern "C" void zkpoa_zkey_free(zkpoa_context*, zkpoa_zkey* zkey) { KeyPtr dying(zkey); }
 
 extern "C" int zkpoa_zkey_info(const zkpoa_zkey* zkey, uint64_t out[4]) {
   if (!zkey || !out) return PROVER_ERROR;
@@ -1842,35 +1609,31 @@ extern "C" int zkpoa_zkey_load_device_shard(zkpoa_context* ctx, uint64_t n_vars,
   *out = nullptr;
   const bool split = (flags & ZKPOA_SHARD_SPLIT_CHAIN) != 0;
   return abi_call(ctx, [&] {
-    std::unique_ptr<zkpoa_zkey> zk(new zkpoa_zkey());
-    try {
-      if (log_domain > 28 || n_vars == 0 || n_vars > (1ull << 28) || n_public + 1 > n_vars || n_coefs > 0xffffffffull)
-        throw ProverError(PROVER_ERROR, "zkey_load_device: size out of range");
-      zk->nVars = (uint32_t)n_vars;
-      zk->nPublic = (uint32_t)n_public;
-      zk->power = log_domain;
-      zk->domain = 1u << log_domain;
-      zk->nCoefs = n_coefs;
-      zk->owns_points = false;
-      zk->dA = const_cast<void*>(d_A);
-      zk->dB1 = const_cast<void*>(d_B1);
-      zk->dB2 = const_cast<void*>(d_B2);
-      zk->dC = const_cast<void*>(d_C);
-      zk->hdr = header_points_from_bytes(header_points);
-      shard_init(zk.get(), rank, world, split, ZKPOA_SHARD_BLOCK_LOG(flags));
-      if (split) {
-        // the handle owns its cyclic H shard (release() frees it): a copy of the caller's, device to device
-        const size_t bytes = (size_t)zk->h_scalar_count() * 64;
-        ZK_HIP(hipMalloc(&zk->dHs, bytes));
-        ZK_HIP(hipMemcpy(zk->dHs, d_H, bytes, hipMemcpyDeviceToDevice));
-      } else {
-        zk->dH = const_cast<void*>(d_H);
-      }
-      finish_load(ctx, zk.get(), d_coef_records, /*recs_on_host=*/false, split, LoadPhases{/*verbose=*/false});
-    } catch (...) {
-      zk->release();
-      throw;
+    KeyPtr zk(new zkpoa_zkey());
+    if (log_domain > 28 || n_vars == 0 || n_vars > (1ull << 28) || n_public + 1 > n_vars || n_coefs > 0xffffffffull)
+      throw ProverError(PROVER_ERROR, "zkey_load_device: size out of range");
+    zk->nVars = (uint32_t)n_vars;
+    zk->nPublic = (uint32_t)n_public;
+    zk->power = log_domain;
+    zk->domain = 1u << log_domain;
+    zk->nCoefs = n_coefs;
+    zk->dA = DevMem::lent(d_A);   // the caller's sections: read, never freed
+    zk->dB1 = DevMem::lent(d_B1);
+    zk->dB2 = DevMem::lent(d_B2);
+    zk->dC = DevMem::lent(d_C);
+    zk->hdr = header_points_from_bytes(header_points);
+    shard_init(zk.get(), rank, world, split, ZKPOA_SHARD_BLOCK_LOG(flags));
+    zk->device = ctx->dev.device;
+    if (split) {
+      // the cyclic H shard is always the handle's own (zkpoa_zkey_set_shard_split replaces it): a copy of the
+      // caller's, device to device
+      const size_t bytes = (size_t)zk->h_scalar_count() * 64;
+      zk->dHs.alloc(bytes);
+      ZK_HIP(hipMemcpy(zk->dHs.get(), d_H, bytes, hipMemcpyDeviceToDevice));
+    } else {
+      zk->dH = DevMem::lent(d_H);
     }
+    finish_load(ctx, zk.get(), d_coef_records, /*recs_on_host=*/false, split, LoadPhases{/*verbose=*/false});
     *out = zk.release();
   });
 }
@@ -1923,7 +1686,7 @@ extern "C" int zkpoa_zkey_read_h_scalars(zkpoa_context* ctx, const zkpoa_zkey* z
     if (capacity < cnt * 32) throw ProverError(PROVER_ERROR_SHORT_BUFFER, "h-scalar buffer too small");
     if (!zkey->d_abc) throw ProverError(PROVER_ERROR, "no H scalars on this handle");
     ZK_HIP(hipDeviceSynchronize());
-    ZK_HIP(hipMemcpy(out, zkey->d_abc, cnt * 32, hipMemcpyDeviceToHost));
+    ZK_HIP(hipMemcpy(out, zkey->d_abc.get(), cnt * 32, hipMemcpyDeviceToHost));
   });
 }
 
@@ -1970,7 +1733,8 @@ extern "C" int zkpoa_h_scalars(zkpoa_context* ctx, const void* coeffs, unsigned 
     if (csr.err) throw ProverError(PROVER_ERROR, "h_scalars: coefficient record out of range or value >= r");
     ntt_prepare(ctx, st, log_domain);
     ZK_HIP(hipEventRecord(ctx->ev_a[5], st));
-    h_chain(ctx, st, csr.row_ptr, csr.sig, csr.vals, csr.long_list, csr.n_long, wit.p, domain, log_domain, abc.p);
+    h_chain(ctx, st, csr.row_ptr.as<uint32_t>(), csr.sig.as<uint32_t>(), csr.vals.get(), csr.long_list.as<uint32_t>(), csr.n_long,
+            wit.p, domain, log_domain, abc.p);
     ZK_HIP(hipEventRecord(ctx->ev_b[5], st));
     ZK_HIP(hipStreamSynchronize(st));
     ZK_HIP(hipGetLastError());

@@ -171,13 +171,13 @@ uint32_t zkey_verify(zkpoa_context* ctx, const char* r1cs_path, const char* ptau
     if (csr.err) failed |= ZKPOA_ZKEY_COEFFS;   // a record's matrix, row or signal out of range (the record is left out)
     const uint32_t lgrid = (uint32_t)((n + 255) / 256);
     char* K = reinterpret_cast<char*>(d_K.p);
-    hipLaunchKernelGGL(abc_rows_kernel, dim3(lgrid), dim3(256), 0, st, (const uint32_t*)csr.row_ptr, (const uint32_t*)csr.sig,
-                       (const void*)csr.vals, (const void*)d_rho.p, (uint32_t)n, 0u, 1u, (void*)K, (void*)(K + n * 32),
+    hipLaunchKernelGGL(abc_rows_kernel, dim3(lgrid), dim3(256), 0, st, csr.row_ptr.as<const uint32_t>(), csr.sig.as<const uint32_t>(),
+                       (const void*)csr.vals.get(), (const void*)d_rho.p, (uint32_t)n, 0u, 1u, (void*)K, (void*)(K + n * 32),
                        (void*)(K + 2 * n * 32));
     if (csr.n_long)   // the constraints too long for one lane: one wave each
-      hipLaunchKernelGGL(abc_long_rows_kernel, dim3((csr.n_long + 3) / 4), dim3(256), 0, st, (const uint32_t*)csr.row_ptr,
-                         (const uint32_t*)csr.sig, (const void*)csr.vals, (const void*)d_rho.p,
-                         (const uint32_t*)csr.long_list, csr.n_long, 0u, 0u, (void*)K, (void*)(K + n * 32),
+      hipLaunchKernelGGL(abc_long_rows_kernel, dim3((csr.n_long + 3) / 4), dim3(256), 0, st, csr.row_ptr.as<const uint32_t>(),
+                         csr.sig.as<const uint32_t>(), (const void*)csr.vals.get(), (const void*)d_rho.p,
+                         csr.long_list.as<const uint32_t>(), csr.n_long, 0u, 0u, (void*)K, (void*)(K + n * 32),
                          (void*)(K + 2 * n * 32));
     hipLaunchKernelGGL(fold_compare_kernel, dim3(lgrid), dim3(256), 0, st, d_S.p, (const void*)K, (uint32_t)n, fl);
     if (points.read()) failed |= ZKPOA_ZKEY_COEFFS;

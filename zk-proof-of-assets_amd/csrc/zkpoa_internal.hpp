@@ -89,8 +89,68 @@ inline std::vector<void*>*& deferred_free_sink() {
   static thread_local std::vector<void*>* sink = nullptr;
   return sink;
 }
+inline void free_deferred(std::vector<void*>& sink) {   // once the device has drained
+  for (void* p : sink) (void)hipFree(p);
+  sink.clear();
+}
 
-struct DevBuf {  // RAII device allocation for the host-buffer entry points
+// Device memory with one owner, for whatever outlives a call: the arrays of a key handle, exchange buffers, a CSR on
+// its way into a handle. Empty by default, move-only. An owner gives its memory back with hipFree and with nothing
+// else: a member of a long-lived object must never land in a deferred_free_sink() merely because it is destroyed while
+// one is set. Handing memory to a sink (or out through the C ABI) is always the explicit `sink.push_back(m.take())`.
+// lent(p) makes the one non-owning state -- memory that belongs to the caller: used like any other, never freed.
+// Temporaries of one call that should wait in the sink are DevBuf, below.
+class DevMem {
+  void* p_ = nullptr;
+  bool owned_ = true;
+
+ public:
+  DevMem() = default;
+  static DevMem lent(const void* callers) {
+    DevMem m;
+    m.p_ = const_cast<void*>(callers);
+    m.owned_ = false;
+    return m;
+  }
+  DevMem(DevMem&& o) noexcept : p_(o.p_), owned_(o.owned_) { o.forget(); }
+  DevMem& operator=(DevMem&& o) noexcept {
+    if (this != &o) {
+      reset();
+      p_ = o.p_;
+      owned_ = o.owned_;
+      o.forget();
+    }
+    return *this;
+  }
+  DevMem(const DevMem&) = delete;
+  DevMem& operator=(const DevMem&) = delete;
+  ~DevMem() { reset(); }
+  void alloc(size_t bytes) {   // replaces what was held; 0 bytes still gives a valid pointer
+    reset();
+    ZK_HIP(hipMalloc(&p_, bytes ? bytes : 1));
+  }
+  void reset() {
+    if (p_ && owned_) (void)hipFree(p_);
+    forget();
+  }
+  void* take() {   // the raw pointer, now the caller's to free; lent memory cannot be given away
+    void* p = owned_ ? p_ : nullptr;
+    forget();
+    return p;
+  }
+  void* get() const { return p_; }
+  template <class T>
+  T* as() const { return static_cast<T*>(p_); }
+  explicit operator bool() const { return p_ != nullptr; }
+
+ private:
+  void forget() {
+    p_ = nullptr;
+    owned_ = true;
+  }
+};
+
+struct DevBuf {  // a call's temporary device allocation: parked in the thread's deferred_free_sink() when one is set
   void* p = nullptr;
   explicit DevBuf(size_t bytes) { ZK_HIP(hipMalloc(&p, bytes ? bytes : 1)); }
   ~DevBuf() {
