@@ -673,6 +673,16 @@ int zkpoa_ntt_form(zkpoa_context* ctx, void* data, unsigned log_n, int form, int
  * order: s_lo, B, logT, grid.x, threads, dynamic LDS bytes, direct boundary table 0 / 1; passes that do not fit in cap
  * words are left out. Returns the pass count, or -1 for log_n > 28 or any other tile_log. */
 int zkpoa_test_ntt_plan(unsigned log_n, unsigned tile_log, uint32_t* out, unsigned cap);
+/* The plan of one MSM and the lane workspace it takes (test hook; needs no context, no GPU and reads no environment
+ * variable). The arguments are the whole request: n points (at most 2^28) sorted at once; c = the forced or the table's
+ * window width, 0 or a value outside 4..22 (merged: 4..25) = the cost model; merged = the fixed-base form; for_g2 = the
+ * sort feeds a G2 accumulation; density32_or_null = non-zero digits per scalar indexed by the window width (32 doubles,
+ * 4..25 are read), null = uniform scalars; k0 = the forced level-0 piece length, outside 8..512 = the rule. Writes
+ * thirteen words: c, W, Wb, ne, TB, K0, K, logS, logRows; sparse 0 / 1; bytes of the sort's, the G1 accumulation's and
+ * the G2 accumulation's workspace (0 for n == 0); words that do not fit in cap are left out. Returns 13, or -1 for
+ * n > 2^28, c outside 0..31, a flag that is not 0 / 1, k0 < 0 or a null out with cap > 0. */
+int zkpoa_test_msm_plan(uint64_t n, int c, int merged, int for_g2, const double* density32_or_null, int k0, uint64_t* out,
+                        unsigned cap);
 
 #ifdef __cplusplus
 }

@@ -52,7 +52,7 @@ EXPORTS = [
     "zkpoa_gen_bases_g1_device", "zkpoa_gen_bases_g2_device",
     "zkpoa_g1_sum", "zkpoa_g2_sum", "zkpoa_g1_mul", "zkpoa_g2_mul",
     "zkpoa_setup_defer_host_frees", "zkpoa_last_ms", "zkpoa_set_option", "zkpoa_msm_points_limit", "zkpoa_field_op", "zkpoa_group_add",
-    "zkpoa_field_prim", "zkpoa_curve_prim", "zkpoa_fq29_prim", "zkpoa_ntt_form", "zkpoa_test_ntt_plan",
+    "zkpoa_field_prim", "zkpoa_curve_prim", "zkpoa_fq29_prim", "zkpoa_ntt_form", "zkpoa_test_ntt_plan", "zkpoa_test_msm_plan",
     "zkpoa_groth16_verify", "zkpoa_sanitize_proof", "zkpoa_groth16_verify_points", "zkpoa_zkey_vkey", "zkpoa_zkey_export_vkey",
     "zkpoa_zkey_read_h_scalars", "zkpoa_zkey_precompute",
     "zkpoa_context_stream", "zkpoa_context_synchronize",

@@ -28,103 +28,12 @@
 #include "bn254_ec.hip.h"
 #include "fq29.hip.h"
 #include "device_ctx.hpp"
+#include "msm_plan.hpp"   // MsmRequest -> MsmPlan: every host-side decision, host-only
 #include <string.h>
 #include <chrono>
 #include <utility>
 
 namespace zkpoa {
-
-constexpr uint32_t kMaxPieceLenPlan = 512;   // = kMaxPieceLen of the piece-ordering kernels
-struct MsmPlan {
-  uint32_t n = 0;   // points
-  uint32_t c = 0;   // window bits
-  uint32_t W = 0;   // digit windows per scalar
-  uint32_t Nb = 0;  // buckets per bucket set = 2^(c-1)
-  // Fixed-base form (MsmTable below): the bases 2^(c*j) * P_i of every window j are precomputed, so the digits of
-  // ALL windows fall into ONE bucket set: Wb = 1 and the (point, window) entry w * n + i is itself the index into
-  // the table. Classic form: one bucket set per window, Wb = W.
-  bool merged = false;
-  uint32_t Wb = 0;  // bucket sets
-  uint32_t ne = 0;  // entries per bucket set: n (classic) or n * W (merged)
-  uint32_t TB = 0;  // total buckets = Wb * Nb
-  uint32_t K0 = 0;  // level-0 piece length
-  uint32_t K = 4;   // fan-in per thread for levels >= 1: hot buckets (witness bits) are latency-bound chains of full
-                    // additions, so a small fan-in with more levels beats 64 sequential additions per thread
-  // bucket reduction: the Nb buckets of a window form a rows x S matrix, b = hi * S + lo
-  uint32_t logS = 0, logRows = 0;
-};
-
-inline uint32_t msm_windows(uint32_t c) { return (254 + c - 1) / c; }
-// Density hint of the calling thread (the prover's witness stages set it): density[c] = expected non-zero digits per
-// scalar at window width c, 4 <= c <= 25, measured on this proof's witness (msm_density_kernel). Real witnesses are
-// mostly bits and short limbs, so a witness MSM has a fraction of the n * W entries of a uniform one -- and a window
-// sized for n * W entries then pays for millions of near-empty buckets (2^26 shape: the A query took 34 ms for 10 ms
-// of additions). nullptr = uniform scalars (every digit non-zero).
-constexpr int kDensityLo = 4, kDensityHi = 25;
-inline const double*& msm_density_hint() {
-  static thread_local const double* hint = nullptr;
-  return hint;
-}
-// experiments (zkpoa_set_option "msm_k0"): force the level-0 piece length; 0 = the rule below
-inline int& msm_forced_k0() {
-  static int k0 = 0;
-  return k0;
-}
-
-// Window width. Costs in units of one mixed addition: every (point, window) entry is one; a bucket costs ~3 in the
-// reduction (a row and a column full addition at 1.4 each + tree levels); one counting-sort pass moves ~20 B per
-// entry at ~3 TB/s, i.e. ~0.03 of an addition per entry and pass (measured per-kernel times at 2^20, r02).
-inline MsmPlan msm_make_plan(size_t n, int force_c = 0, bool for_g2 = false, bool merged = false) {
-  MsmPlan p;
-  p.n = (uint32_t)n;
-  p.merged = merged;
-  int best_c = 4;
-  double best = 1e300;
-  const double* density = msm_density_hint();   // merged form: the width is the table's (force_c) at run time, but a
-                                                // table for witness scalars is SIZED with the density of a witness
-  for (int c = 4; c <= (merged ? 25 : 22); c++) {
-    double W = (double)msm_windows((uint32_t)c);
-    double sets = merged ? 1.0 : W;
-    double passes = (double)((c - 1 + 7) / 8);
-    // entries that exist; the dense n x W digit matrix is still written once and read twice (0.04 of an addition
-    // per slot), and every bucket costs a slot in the piece list besides its two additions in the reduction
-    double entries = density ? density[c] * (double)n : W * (double)n;
-    double cost = entries * (1.0 + 0.03 * passes) + (density ? 0.04 * W * (double)n : 0.0) +
-                  (density ? 5.0 : 3.0) * sets * (double)(1u << (c - 1));
-    if (cost < best) {
-      best = cost;
-      best_c = c;
-    }
-  }
-  if (force_c >= 4 && force_c <= (merged ? 25 : 22)) best_c = force_c;
-  p.c = best_c;
-  p.W = msm_windows(p.c);
-  p.Nb = 1u << (p.c - 1);
-  p.Wb = merged ? 1u : p.W;
-  p.ne = merged ? p.n * p.W : p.n;
-  p.TB = p.Wb * p.Nb;
-  p.logS = (uint32_t)(p.c - 1 + 1) / 2;
-  p.logRows = (uint32_t)(p.c - 1) - p.logS;
-  // Level-0 piece length. One thread adds one piece sequentially: about twice the mean bucket occupancy, so
-  // most buckets are a single piece (uniform scalars: 128 at 2^20, 256 at 2^26). The kernel cannot end before
-  // K0 dependent mixed additions have run, and a G2 addition is ~15 us for a lone wave (256 of them: 4 ms), so
-  // a sort whose result also feeds a G2 accumulation (the prover's B query) uses a quarter of that; buckets
-  // longer than K0 continue in the partial-sum levels.
-  const double dens_entries = density ? density[p.c] * (double)p.n : (double)p.n * p.W;
-  double avg = (merged ? dens_entries : dens_entries / p.W) / (double)p.Nb;
-  uint32_t k0 = 32;
-  while (k0 < 2 * avg && k0 < 256) k0 <<= 1;
-  if (for_g2 && k0 > 32) k0 = k0 >= 128 ? k0 / 4 : 32;
-  // ... and short enough that the pieces fill the chip about 2.5 times over (256 CUs x 12 waves x 64 lanes at the
-  // accumulation kernel's 3 waves per SIMD; 2 for G2): with fewer, longer pieces the grid is one partial wave of
-  // work and the CUs idle behind its longest pieces (2^20 points: 128-long pieces ran at 0.84 of the ALU ceiling,
-  // 32-long ones at 0.95-1.0; the extra partial sums cost ~3 % more additions).
-  const double fill = dens_entries / (2.5 * 256.0 * (for_g2 ? 8.0 : 12.0) * 64.0);
-  while (k0 > 32 && (double)k0 > fill) k0 >>= 1;
-  if (msm_forced_k0() >= 8 && msm_forced_k0() <= (int)kMaxPieceLenPlan) k0 = (uint32_t)msm_forced_k0();
-  p.K0 = k0;
-  return p;
-}
 
 // ---- scalar recoding ------------------------------------------------------------------------
 // (r-1)/2 and r, 8 x u32 little-endian
@@ -1003,8 +912,8 @@ struct MsmSortLayout {
   uint32_t *pbkt = nullptr, *order = nullptr;   // piece -> bucket; piece ids, longest first
   uint32_t* digits() const { return reinterpret_cast<uint32_t*>(elist); }
   uint32_t* len_cursor() const { return len_hist + (kMaxPieceLen + 1); }
-  // Sparse or dense is decided per run from the density hint; the bytes must not depend on it, so the digit / entry
-  // region has the larger size and `pre` is always there.
+  // Sparse or dense (MsmPlan::sparse) can still be overridden per run (ZKPOA_NO_SPARSE); the bytes must not depend on it,
+  // so the digit / entry region has the larger size and `pre` is always there.
   template <class Taker>
   void carve(Taker& ws, const MsmPlan& p) {
     const SortPlan sp = make_sort_plan(p.ne, p.Wb, p.c);
@@ -1096,7 +1005,7 @@ inline void msm_reduce_levels(hipStream_t st, uint32_t TB, uint32_t K, const uin
 // use the witness -- so those three MSMs sort once.
 // Phase B (bases): bucket accumulation, further levels, bucket reduction, window sums to the host.
 struct MsmSorted {
-  MsmPlan p;
+  MsmPlan p;                    // with its request: all that phase B needs to know about phase A
   MsmSortLayout m;              // phase B reads counts, off0, po_a, sorted, order, pbkt
   uint32_t total1 = 0;          // level-0 pieces
   uint32_t total_entries = 0;   // (point, window) entries with a non-zero digit = mixed additions of the level-0 kernel
@@ -1114,33 +1023,30 @@ inline void lane_reserve(Lane& lane, size_t need) {
   }
 }
 
-// Phase A on lane.stream. `extra_bytes` is reserved on top (for a following phase B on the same lane).
-// The arena is reset here; the result stays valid until the lane's next msm_sort_phase. With
+// Phase A on lane.stream for the req.n scalars at d_scalars. `extra(plan)` bytes are reserved on top (for a following
+// phase B on the same lane). The arena is reset here; the result stays valid until the lane's next msm_sort_phase. With
 // sync_at_end the stream is synchronised on return, so other lanes may read the result.
-inline MsmSorted msm_sort_phase(Lane& lane, const void* d_scalars, size_t n, int force_c,
-                                size_t (*extra)(const MsmPlan&), bool sync_at_end = false, bool for_g2 = false,
-                                bool merged = false) {
+inline MsmSorted msm_sort_phase(Lane& lane, const void* d_scalars, const MsmRequest& req,
+                                size_t (*extra)(const MsmPlan&), bool sync_at_end = false) {
   MsmSorted sr;
-  sr.p = msm_make_plan(n, force_c, for_g2, merged);
+  sr.p = msm_make_plan(req);
   const MsmPlan& p = sr.p;
   // entry positions are 32-bit: n * W (+ a few per-bucket slots) must stay below 2^32; a merged entry index also
   // carries the sign in bit 31
   if ((uint64_t)p.n * p.W + p.TB >= 0xffff0000ull) throw HipError("msm: n * windows exceeds the 32-bit entry index");
-  if (merged && (uint64_t)p.n * p.W >= 0x80000000ull) throw HipError("msm: n * windows exceeds the fixed-base entry index");
+  if (p.merged && (uint64_t)p.n * p.W >= 0x80000000ull) throw HipError("msm: n * windows exceeds the fixed-base entry index");
   hipStream_t st = lane.stream;
   lane_reserve(lane, msm_sort_workspace_bytes(p) + (extra ? extra(p) : 0));
   lane.ws.reset();
   const SortPlan sp = make_sort_plan(p.ne, p.Wb, p.c);
   const MsmSortLayout& m = sr.m = msm_carve<MsmSortLayout>(lane.ws, p);
   ZK_HIP(hipMemsetAsync(m.counts, 0, m.zero_bytes, st));
-  // sparse scalars in the fixed-base form (a witness through its tables): a compact entry list instead of the dense
-  // digit array (msm_sort.hip.h msm_entries_kernel); ZKPOA_NO_SPARSE=1 keeps the dense form (measurement)
+  // the plan's entry form; ZKPOA_NO_SPARSE=1 keeps the dense form (measurement)
   static const bool no_sparse = [] {
     const char* e = getenv("ZKPOA_NO_SPARSE");
     return e && *e == '1';
   }();
-  const double* dens = msm_density_hint();
-  const bool sparse = merged && p.n && dens && dens[p.c] < 0.6 * (double)p.W && !no_sparse;
+  const bool sparse = p.sparse && !no_sparse;
   uint32_t* digits = sparse ? nullptr : m.digits();   // one region, one view per form
   uint2* elist = sparse ? m.elist : nullptr;
   uint32_t* pre = sparse ? m.pre : nullptr;
@@ -1332,9 +1238,9 @@ inline size_t msm_table_bytes(uint64_t n, uint32_t c) {
   return (size_t)n * msm_windows(c) * MsmSizes<F>::kAffine;
 }
 
-// Window width of a table over n bases (the merged-bucket cost model), or `force_c`.
-inline uint32_t msm_table_c(uint64_t n, int force_c = 0, bool for_g2 = false) {
-  return msm_make_plan((size_t)n, force_c, for_g2, true).c;
+// Window width of a table over n bases: `force_c`, else the merged-bucket cost model for scalars of that density.
+inline uint32_t msm_table_c(uint64_t n, int force_c, bool for_g2, const double* density = nullptr) {
+  return msm_make_plan(MsmRequest{n, force_c, true, for_g2, density, 0}).c;
 }
 
 // Builds the table on `st` (synchronised on return). Slabs of 2^20 points bound the scratch memory.
@@ -1378,15 +1284,16 @@ inline void msm_table_free(MsmTable& t) {
   t = MsmTable();
 }
 
-// One complete MSM on one lane (phase A + phase B). Returns the plan used. With a table (built from exactly these
-// n bases) the fixed-base form runs: d_bases is then not read.
+// One complete MSM on one lane (phase A + phase B) over req.n points. Returns the plan used. A merged request comes
+// with the table it was made from (built from exactly these n bases): the fixed-base form runs, d_bases is not read.
 template <class F>
-inline MsmPlan msm_device(Lane& lane, const void* d_bases, const void* d_scalars, size_t n, void* window_sums_host,
-                          int force_c = 0, float* accum_ms = nullptr, const MsmTable* table = nullptr,
+inline MsmPlan msm_device(Lane& lane, const void* d_bases, const void* d_scalars, const MsmRequest& req,
+                          void* window_sums_host, float* accum_ms = nullptr, const MsmTable* table = nullptr,
                           uint32_t* entries = nullptr) {
-  if (table && table->n != n) throw HipError("msm: the fixed-base table was built for another base array");
-  MsmSorted sr = msm_sort_phase(lane, d_scalars, n, table ? (int)table->c : force_c, &msm_accum_workspace_bytes<F>,
-                                false, FieldBytes<F>::N > 32, table != nullptr);
+  if (req.merged != (table != nullptr)) throw HipError("msm: internal: a merged request and its table go together");
+  if (table && (table->n != req.n || (int)table->c != req.c))
+    throw HipError("msm: the fixed-base table was built for another base array");
+  MsmSorted sr = msm_sort_phase(lane, d_scalars, req, &msm_accum_workspace_bytes<F>);
   msm_accum_phase<F>(lane, sr, table ? table->d : d_bases, window_sums_host, true, accum_ms);
   if (entries) *entries = sr.total_entries;
   return sr.p;

@@ -11,9 +11,10 @@ namespace zkpoa {
 // Entry positions are 32-bit (n x windows < 2^32), so an MSM over more than `opt_msm_max_points` points
 // (default 2^27; the largest domain a zkey may have is 2^28) runs in chunks whose results are added on the host.
 // `table` (optional): fixed-base table built from exactly these n bases -> merged-bucket form, d_bases unread.
+// `density` (optional): digit density of these scalars (msm_plan.hpp MsmRequest); every chunk is planned with it.
 template <class F, class HF>
 void msm_run(zkpoa_context* ctx, int lane_id, const void* d_bases, const void* d_scalars, uint64_t n, uint8_t* out,
-             float* ms2, const MsmTable* table = nullptr) {
+             float* ms2, const MsmTable* table = nullptr, const double* density = nullptr) {
   if (lane_id) ctx->dev.wait_lanes();
   ctx->dev.ensure_lane(lane_id);
   Lane& lane = ctx->dev.lanes[lane_id];
@@ -33,8 +34,9 @@ void msm_run(zkpoa_context* ctx, int lane_id, const void* d_bases, const void* d
     MsmPlan p;
     try {
       p = msm_device<F>(lane, reinterpret_cast<const char*>(d_bases) + done * MsmSizes<F>::kAffine,
-                        reinterpret_cast<const char*>(d_scalars) + done * 32, (size_t)cnt, wsums.data(),
-                        ctx->opt_msm_c, &acc_ms, table, &entries);
+                        reinterpret_cast<const char*>(d_scalars) + done * 32,
+                        msm_request(ctx, cnt, table ? (int)table->c : 0, FieldBytes<F>::N > 32, density), wsums.data(),
+                        &acc_ms, table, &entries);
     } catch (const OomError& e) {
       // HBM is full (a 2^27 key beside five whole-MSM workspaces; another process on the card): the workspace is
       // proportional to the points sorted at once, so go through them in halves -- the sum is the same

@@ -112,7 +112,7 @@ static __global__ __launch_bounds__(256) void msm_digits_kernel(const void* __re
 // ---- K0', sparse scalars, fixed-base form -----------------------------------------------------------------
 // A witness is mostly bits and short limbs: at the c = 17 of a witness table a scalar has ~3 non-zero digits of 15, and
 // the dense digit array above (n x W words written once, read by pass 0's count and again by its scatter) is four
-// fifths zeros. When the digit density says so (msm_sort_phase), the digits go straight into a COMPACT entry list
+// fifths zeros. When the plan says so (msm_plan.hpp MsmPlan::sparse: few non-zero digits), the digits go straight into a COMPACT entry list
 // instead -- (table index w * n + i | sign << 31, |digit| - 1), 8 bytes per non-zero digit, in no particular order (a
 // bucket sum does not care) -- and pass 0 runs over that list exactly as the later passes run over theirs. One
 // block-wide scan + one global atomic per block reserve the block's range of the list.

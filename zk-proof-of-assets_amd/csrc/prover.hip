@@ -623,6 +623,22 @@ StageView stage_view(const zkpoa_zkey* zk, int stage) {
   return v;
 }
 
+// The request (msm_plan.hpp) of a stage's MSM when it takes at most `limit` points at once. The budget (lane_needs) and
+// the shared sort of the B query build theirs here; a stage whose MSM may run in chunks hands msm_run the same pieces --
+// the view's table and `density` -- and msm_run makes each chunk's request from them with the same msm_request. A table
+// is only of use to a whole MSM, and only where the caller allows one. Who passes which density (DESIGN.md "MSM plans"):
+//   H (lane 0)                          none: uniform scalars
+//   A (1), C (4)                        this proof's witness density (with_density)
+//   B shared sort, B1's own MSM (2)     this proof's witness density
+//   B2 over the shared sort (3)         nothing to plan: the sort's plan
+//   B2's own MSM (3)                    none -- KNOWN MISMATCH: lane_needs sizes that lane with the density
+//   lane_needs                          H none; A, B, C the handle's recorded density, if it has one
+//   zkey_precompute (msm_table_c)       H table none; A / B / C widths the handle's recorded density, if it has one
+static MsmRequest stage_request(const zkpoa_context* ctx, const StageView& v, uint64_t limit, const double* density,
+                                bool for_g2, bool with_table = true) {
+  return msm_request(ctx, std::min(v.n, limit), with_table && v.n <= limit ? v.table_c : 0, for_g2, density);
+}
+
 // Fixed-base tables for a resident key, most valuable first, while they fit the budget (bytes; 0 = half of the HBM
 // that is free right now -- which leaves room for the per-lane sort / bucket workspaces). H and C first: the H MSM
 // closes the critical path and section 8 is the largest G1 array; then the A query; the B query needs both its
@@ -681,7 +697,7 @@ uint64_t zkey_precompute(zkpoa_context* ctx, zkpoa_zkey* zk, uint64_t budget, in
     }
     built++;
     try {
-      t.slot->reset(t.g2 ? msm_table_build_g2(ctx, t.bases, t.n, t.c) : msm_table_build_g1(ctx, t.bases, t.n, t.c));
+      *t.slot = t.g2 ? msm_table_build_g2(ctx, t.bases, t.n, t.c) : msm_table_build_g1(ctx, t.bases, t.n, t.c);
       zk->table_bytes += t.bytes();
       return true;
     } catch (const HipError&) {
@@ -689,16 +705,13 @@ uint64_t zkey_precompute(zkpoa_context* ctx, zkpoa_zkey* zk, uint64_t budget, in
       return false;
     }
   };
-  // H scalars are uniform; the A / B / C tables are sized for witness scalars when a proof has measured some
+  // H scalars are uniform (its table: msm_table_build's own width); the A / B / C tables are sized for witness scalars
+  // when a proof has measured some
   auto witness_c = [&](uint64_t n, bool g2) {
     if (const char* e = getenv("ZKPOA_WITNESS_TABLE_C"))   // experiments only
       if (atoi(e) >= 4 && atoi(e) <= 25) return atoi(e);
-    msm_set_density_hint(zk->have_density ? zk->witness_density : nullptr);
-    const int c = (int)msm_table_width(n, force_c, g2);
-    msm_set_density_hint(nullptr);
-    return c;
+    return (int)msm_table_c(n, force_c, g2, zk->have_density ? zk->witness_density : nullptr);
   };
-  msm_set_density_hint(nullptr);
   // (one window width for both B tables: the G2 model's -- shorter pieces -- as the shared sort is planned for G2)
   auto candidate = [&](MsmTablePtr* slot, int stage) {
     const StageView v = stage_view(zk, stage);
@@ -762,29 +775,25 @@ struct LaneNeeds {
 };
 static LaneNeeds lane_needs(const zkpoa_context* ctx, const zkpoa_zkey* zk, const uint64_t lim[5], bool with_tables) {
   LaneNeeds w;
-  const int fc = ctx->opt_msm_c;
   const StageView v[5] = {stage_view(zk, 0), stage_view(zk, 1), stage_view(zk, 2), stage_view(zk, 3), stage_view(zk, 4)};
-  // a table is only of use to a whole MSM (msm_run)
-  auto table_c = [&](int l, uint64_t limit) { return with_tables && v[l].n <= limit ? v[l].table_c : 0; };
   const double* dens = zk->have_density ? zk->witness_density : nullptr;
-  // H (lane 0): uniform scalars
-  msm_set_density_hint(nullptr);
-  w.bytes[0] = msm_workspace_g1(std::min(v[0].n, lim[0]), fc, false, table_c(0, lim[0]), true);
-  // A (lane 1), C (lane 4): witness scalars
-  msm_set_density_hint(dens);
-  w.bytes[1] = msm_workspace_g1(std::min(v[1].n, lim[1]), fc, false, table_c(1, lim[1]), true);
-  w.bytes[4] = msm_workspace_g1(std::min(v[4].n, lim[4]), fc, false, table_c(4, lim[4]), true);
+  auto whole_g1 = [&](int l, const double* density) {   // a lane's own G1 MSM: sort and accumulation in one arena
+    return msm_workspace(stage_request(ctx, v[l], lim[l], density, false, with_tables), kMsmSort | kMsmAccumG1);
+  };
+  w.bytes[kStageH] = whole_g1(kStageH, nullptr);   // uniform scalars
+  w.bytes[kStageA] = whole_g1(kStageA, dens);      // witness scalars
+  w.bytes[kStageC] = whole_g1(kStageC, dens);
   // B (lanes 2 and 3): one sort for both when the whole query fits one
-  const uint64_t nB = v[2].n, limB = std::min(lim[2], lim[3]);
+  const uint64_t nB = v[kStageB1].n, limB = std::min(lim[kStageB1], lim[kStageB2]);
   if (nB <= limB) {
-    const int tc = table_c(2, limB);
-    w.bytes[2] = msm_workspace_g1(nB, fc, true, tc, true);
-    w.bytes[3] = msm_workspace_g2(nB, fc, tc, false);
-  } else {
-    w.bytes[2] = msm_workspace_g1(std::min(nB, lim[2]), fc, false, 0, true);
-    w.bytes[3] = msm_workspace_g2(std::min(nB, lim[3]), fc, 0, true);
+    const MsmRequest shared = stage_request(ctx, v[kStageB1], limB, dens, true, with_tables);
+    w.bytes[kStageB1] = msm_workspace(shared, kMsmSort | kMsmAccumG1);
+    w.bytes[kStageB2] = msm_workspace(shared, kMsmAccumG2);
+  } else {   // two chunked MSMs, no table
+    w.bytes[kStageB1] = msm_workspace(stage_request(ctx, v[kStageB1], lim[kStageB1], dens, false, false), kMsmSort | kMsmAccumG1);
+    // KNOWN MISMATCH (DESIGN.md "MSM plans", follow-up): B2's own MSM runs with no density (prove_partials, tB2)
+    w.bytes[kStageB2] = msm_workspace(stage_request(ctx, v[kStageB2], lim[kStageB2], dens, true, false), kMsmSort | kMsmAccumG2);
   }
-  msm_set_density_hint(nullptr);
   return w;
 }
 
@@ -889,6 +898,7 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
   // Witness MSMs on their own lanes (host threads: each MSM has one mid-way read-back). B1 and B2 use the
   // same scalars (the witness values of the wires that occur in the B matrix), so their bucket sort runs once
   // (lane 2) and both accumulations read it; A and C sort on their own lanes.
+  std::unique_ptr<MsmSorted> sorted_b;   // owned here: freed after every stage has joined
   std::promise<const MsmSorted*> sorted_promise;
   std::shared_future<const MsmSorted*> sorted_ready = sorted_promise.get_future().share();
   // digit density of this proof's witness (non-zero digits per scalar for every window width), measured once by the
@@ -924,9 +934,9 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
     if (stg && stg->prep_A) stg->prep_A();
     const StageView vA = stage_view(zk, kStageA);
     if (!zk->d_witness || !zk->qA.g1 || !zk->qA.scalars) throw ProverError(PROVER_ERROR, "internal: A stage started before its inputs");
-    msm_set_density_hint(with_density(1));
+    const double* dens = with_density(1);
     gather(1, zk->qA);
-    msm_run_g1(ctx, 1, vA.bases, zk->qA.scalars.get(), vA.n, outA, msm_ms[1], vA.table);
+    msm_run_g1(ctx, 1, vA.bases, zk->qA.scalars.get(), vA.n, outA, msm_ms[1], vA.table, dens);
   });
   if (serial) tA.join();
   // (a B query beyond the 32-bit entry index of one sort cannot share it: two chunked MSMs instead)
@@ -936,8 +946,8 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
   int table_c_b = 0;
   float sort_b_ms = 0;   // the shared sort of the B query (host clock: the call returns with its stream synchronised)
   std::thread tB1 = guarded(1, [&] {
-    MsmSorted* sr = nullptr;
     StageView vB1;
+    const double* dens = nullptr;
     try {
       if (stg && stg->prep_B) stg->prep_B();
       vB1 = stage_view(zk, kStageB1);
@@ -945,12 +955,12 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
       table_c_b = share_b ? vB1.table_c : 0;
       if (!zk->d_witness || !zk->qB.g1 || !zk->qB.g2 || !zk->qB.scalars)
         throw ProverError(PROVER_ERROR, "internal: B stage started before its inputs");
-      msm_set_density_hint(with_density(2));
+      dens = with_density(2);
       gather(2, zk->qB);
       auto ts0 = std::chrono::steady_clock::now();
       if (share_b) {
         try {
-          sr = msm_sort_run(ctx, 2, zk->qB.scalars.get(), zk->qB.cnt, true, table_c_b);
+          sorted_b = msm_sort_run(ctx, 2, zk->qB.scalars.get(), stage_request(ctx, vB1, sort_limit, dens, true));
         } catch (const OomError& e) {   // no room for the whole query's sort: B1 and B2 each go through it in pieces
           if (!ctx->shrink_after_oom(2, zk->qB.cnt)) throw;
           if (getenv("ZKPOA_VERBOSE")) fprintf(stderr, "zkpoa:   B query: %s; B1 and B2 sort their own pieces\n", e.what());
@@ -960,13 +970,13 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
       }
       if (!share_b) ZK_HIP(hipStreamSynchronize(ctx->dev.lanes[2].stream));   // the gathered scalars are read on lane 3 too
       sort_b_ms = (float)ms_since(ts0);
-      sorted_promise.set_value(sr);
+      sorted_promise.set_value(sorted_b.get());
     } catch (...) {
       sorted_promise.set_exception(std::current_exception());
       throw;
     }
-    if (share_b) msm_accum_g1(ctx, 2, sr, true, table_c_b ? msm_table_data(vB1.table) : vB1.bases, outB1, msm_ms[2]);
-    else msm_run_g1(ctx, 2, vB1.bases, zk->qB.scalars.get(), vB1.n, outB1, msm_ms[2]);
+    if (share_b) msm_accum_g1(ctx, 2, sorted_b.get(), true, table_c_b ? msm_table_data(vB1.table) : vB1.bases, outB1, msm_ms[2]);
+    else msm_run_g1(ctx, 2, vB1.bases, zk->qB.scalars.get(), vB1.n, outB1, msm_ms[2], nullptr, dens);
     if (share_b) msm_ms[2][0] += sort_b_ms;
   });
   if (serial) tB1.join();
@@ -983,7 +993,8 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
         shared = false;
       }
     }
-    if (!shared) msm_run_g2(ctx, 3, vB2.bases, zk->qB.scalars.get(), vB2.n, outB2, msm_ms[3]);
+    // KNOWN MISMATCH (DESIGN.md "MSM plans", follow-up): no density here, while lane_needs sizes this lane with one
+    if (!shared) msm_run_g2(ctx, 3, vB2.bases, zk->qB.scalars.get(), vB2.n, outB2, msm_ms[3], nullptr, nullptr);
   });
   if (serial) tB2.join();
   std::thread tC = guarded(3, [&] {
@@ -999,8 +1010,7 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
                            zk->ccnt, zk->bc_log, zk->bc_rank, zk->bc_world, zk->d_cscal.as<uint4>());
       witC = zk->d_cscal.as<const char>();
     }
-    msm_set_density_hint(with_density(4));
-    msm_run_g1(ctx, 4, vC.bases, witC, vC.n, outC, msm_ms[4], vC.table);
+    msm_run_g1(ctx, 4, vC.bases, witC, vC.n, outC, msm_ms[4], vC.table, with_density(4));
   });
   if (serial) tC.join();
 
@@ -1039,10 +1049,7 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
     tB2.join();
     tC.join();
   }
-  try {
-    msm_sorted_free(const_cast<MsmSorted*>(sorted_ready.get()));
-  } catch (...) {
-  }
+  sorted_b.reset();
   if (main_err) std::rethrow_exception(main_err);
   for (auto& e : errs)
     if (e) std::rethrow_exception(e);

@@ -31,11 +31,6 @@ struct CompactQuery {
   uint64_t lo = 0, cnt = 0;  // this shard's slice of them
 };
 
-struct MsmTableFree {
-  void operator()(MsmTable* t) const { msm_table_release(t); }
-};
-typedef std::unique_ptr<MsmTable, MsmTableFree> MsmTablePtr;
-
 // ---- device-resident proving key -------------------------------------------------------------------
 // Every device array is a DevMem member, so the compiler's destructor gives back exactly what the handle owns. A
 // handle that has touched a device is destroyed through FreeKey (below), which drains that device first.

@@ -103,8 +103,8 @@ extern "C" int zkpoa_set_option(zkpoa_context* ctx, const char* key, long value)
     ctx->opt_ptau_mul_slab = value;
     return PROVER_OK;
   }
-  if (!strcmp(key, "msm_k0")) {           // experiments: level-0 piece length of the bucket accumulation (process-wide)
-    msm_set_forced_k0((int)value);
+  if (!strcmp(key, "msm_k0")) {           // experiments: level-0 piece length of the bucket accumulation
+    ctx->opt_msm_k0 = (int)value;
     return PROVER_OK;
   }
   if (!strcmp(key, "prove_serial")) {     // measurement: no overlap between the stages of a prove
@@ -220,15 +220,10 @@ extern "C" int zkpoa_msm_table_build(zkpoa_context* ctx, int group, const void* 
   ZK_API_BEGIN(ctx)
   check_n(n);
   if (group != 1 && group != 2) throw HipError("msm_table_build: group must be 1 or 2");
-  zkpoa_msm_table* h = new zkpoa_msm_table();
+  std::unique_ptr<zkpoa_msm_table> h(new zkpoa_msm_table());
   h->group = group;
-  try {
-    h->t = group == 1 ? msm_table_build_g1(ctx, d_bases, n, window_bits) : msm_table_build_g2(ctx, d_bases, n, window_bits);
-  } catch (...) {
-    delete h;
-    throw;
-  }
-  *out = h;
+  h->t = group == 1 ? msm_table_build_g1(ctx, d_bases, n, window_bits) : msm_table_build_g2(ctx, d_bases, n, window_bits);
+  *out = h.release();
   ZK_API_END(ctx)
 }
 extern "C" void zkpoa_msm_table_free(zkpoa_context* ctx, zkpoa_msm_table* table) {
@@ -237,12 +232,11 @@ extern "C" void zkpoa_msm_table_free(zkpoa_context* ctx, zkpoa_msm_table* table)
     (void)hipSetDevice(ctx->dev.device);
     (void)hipDeviceSynchronize();
   }
-  msm_table_release(table->t);
   delete table;
 }
 extern "C" int zkpoa_msm_table_info(const zkpoa_msm_table* table, uint64_t out[4]) {
   if (!table || !table->t || !out) return PROVER_ERROR;
-  msm_table_info(table->t, out);
+  msm_table_info(table->t.get(), out);
   return PROVER_OK;
 }
 extern "C" int zkpoa_msm_table_run_lane(zkpoa_context* ctx, int lane, const zkpoa_msm_table* table,
@@ -251,9 +245,9 @@ extern "C" int zkpoa_msm_table_run_lane(zkpoa_context* ctx, int lane, const zkpo
   try {
     ZK_HIP(hipSetDevice(ctx->dev.device));
     uint64_t info[4];
-    msm_table_info(table->t, info);
-    if (table->group == 1) msm_run_g1(ctx, lane, nullptr, d_scalars, info[0], out, ctx->lane_ms[lane], table->t);
-    else msm_run_g2(ctx, lane, nullptr, d_scalars, info[0], out, ctx->lane_ms[lane], table->t);
+    msm_table_info(table->t.get(), info);
+    if (table->group == 1) msm_run_g1(ctx, lane, nullptr, d_scalars, info[0], out, ctx->lane_ms[lane], table->t.get());
+    else msm_run_g2(ctx, lane, nullptr, d_scalars, info[0], out, ctx->lane_ms[lane], table->t.get());
   } catch (const std::exception& e) {
     return PROVER_ERROR;   // last_error is shared between lanes: not touched
   }

@@ -4,16 +4,24 @@
 #include "device_ctx.hpp"
 #include "fast_upload.hpp"
 #include "host_curve.hpp"
+#include "msm_plan.hpp"
 
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <memory>
 #include <string>
 #include <vector>
 
 namespace zkpoa {
 struct NttEngine;
-struct MsmTable;
+struct MsmTable;    // msm.hip.h: fixed-base table 2^(c*j) * P_i of one base array
+struct MsmSorted;   // msm.hip.h: the result of an MSM's sort phase
+void msm_table_release(MsmTable* t);   // its device memory and the object
+struct MsmTableFree {
+  void operator()(MsmTable* t) const { msm_table_release(t); }
+};
+typedef std::unique_ptr<MsmTable, MsmTableFree> MsmTablePtr;
 }
 
 struct zkpoa_poseidon_state;   // poseidon.hip: device copy of the Poseidon parameters
@@ -28,7 +36,8 @@ struct zkpoa_context {
   float io_ms[2] = {0, 0};   // last prove from a host buffer: [0] witness -> HBM (host clock), [1] its bytes / 1e6
   float lane_ms[zkpoa::DeviceCtx::kLanes][2] = {};   // per-lane {whole MSM, accumulation kernel} of the last MSM
   double lane_adds[zkpoa::DeviceCtx::kLanes] = {};   // per-lane mixed additions of that kernel (non-zero digits)
-  int opt_msm_c = 0;
+  int opt_msm_c = 0;    // forced window width; 0 (or out of range) = the cost model
+  int opt_msm_k0 = 0;   // experiments: forced level-0 piece length; 0 (or out of range) = the rule (msm_plan.hpp)
   long opt_msm_max_points = 0;   // 0 = default (2^27): larger MSMs run in chunks
   long opt_ptau_piece_points = 0;   // powersoftau contribute / beacon: points per piece; 0 = derived from free HBM
   long opt_ptau_mul_slab = 0;       // scalar_mul_each: points per launch; 0 = 2^20 (tests: cross a slab border at a small size)
@@ -71,7 +80,7 @@ struct zkpoa_context {
 };
 
 struct zkpoa_msm_table {   // C-ABI handle of a fixed-base table (zkpoa_msm_table_build)
-  zkpoa::MsmTable* t = nullptr;
+  zkpoa::MsmTablePtr t;
   int group = 1;
 };
 
@@ -167,31 +176,31 @@ struct DevBuf {  // a call's temporary device allocation: parked in the thread's
 
 
 // per-group entry points, each compiled in its own translation unit (msm_g1.hip, msm_g2.hip, ...)
-struct MsmTable;   // msm.hip.h: fixed-base table 2^(c*j) * P_i of one base array
+// The request (msm_plan.hpp) of an MSM of this context over n points at once: the context's options, and the window
+// width of the fixed-base table the MSM runs through (table_c > 0: merged form) -- else the forced width, else the model's.
+// density: that of the scalars (msm_density), nullptr = uniform. for_g2: the sort feeds a G2 accumulation.
+inline MsmRequest msm_request(const zkpoa_context* ctx, uint64_t n, int table_c, bool for_g2, const double* density) {
+  return MsmRequest{n, table_c > 0 ? table_c : ctx->opt_msm_c, table_c > 0, for_g2, density, ctx->opt_msm_k0};
+}
+// One MSM, in chunks of at most the lane's point limit; a chunked MSM gives up `table`. density: of these scalars.
 void msm_run_g1(zkpoa_context* ctx, int lane_id, const void* d_bases, const void* d_scalars, uint64_t n, uint8_t* out,
-                float* ms2, const MsmTable* table = nullptr);
+                float* ms2, const MsmTable* table = nullptr, const double* density = nullptr);
 void msm_run_g2(zkpoa_context* ctx, int lane_id, const void* d_bases, const void* d_scalars, uint64_t n, uint8_t* out,
-                float* ms2, const MsmTable* table = nullptr);
-// tables: built on lane 0's stream (synchronised on return); c = 0 picks the width from the cost model
-MsmTable* msm_table_build_g1(zkpoa_context* ctx, const void* d_bases, uint64_t n, int c);
-MsmTable* msm_table_build_g2(zkpoa_context* ctx, const void* d_bases, uint64_t n, int c);
+                float* ms2, const MsmTable* table = nullptr, const double* density = nullptr);
+// tables: built on lane 0's stream (synchronised on return); c = 0 picks the width from the cost model (uniform scalars)
+MsmTablePtr msm_table_build_g1(zkpoa_context* ctx, const void* d_bases, uint64_t n, int c);
+MsmTablePtr msm_table_build_g2(zkpoa_context* ctx, const void* d_bases, uint64_t n, int c);
 size_t msm_table_bytes_g1(uint64_t n, int c);
 size_t msm_table_bytes_g2(uint64_t n, int c);
-uint32_t msm_table_width(uint64_t n, int c, bool g2);
-void msm_table_release(MsmTable* t);
 const void* msm_table_data(const MsmTable* t);
 void msm_table_info(const MsmTable* t, uint64_t out[4]);   // n, c, W, bytes
-// bytes of lane workspace an MSM over n points reserves (msm.hip.h msm_sort/accum_workspace_bytes of its plan, which
-// follows the calling thread's density hint). g1: bucket sort (for_g2: one that also feeds a G2 accumulation) and, with
-// `accum`, the G1 accumulation in the same arena; g2: the G2 accumulation and, with `sort`, its own sort.
-// table_c > 0: the fixed-base form with that window width.
-size_t msm_workspace_g1(uint64_t n, int force_c, bool for_g2, int table_c, bool accum);
-size_t msm_workspace_g2(uint64_t n, int force_c, int table_c, bool sort);
-void msm_set_forced_k0(int k0);
+// bytes of lane workspace the named parts of the request's plan reserve (msm.hip.h msm_sort/accum_workspace_bytes):
+// a whole MSM is its sort and one accumulation in the same arena; an accumulation over another lane's sort is that alone.
+enum MsmPart : unsigned { kMsmSort = 1, kMsmAccumG1 = 2, kMsmAccumG2 = 4 };
+size_t msm_workspace(const MsmRequest& req, unsigned parts);   // 0 for req.n == 0
 // non-zero digits per scalar for every window width (index c, 4..25) of n scalars on the device; synchronises st
 // (d_scratch: 256 B of device memory of the caller's -- no allocation here: a hipFree would wait for every lane)
 void msm_density(hipStream_t st, const void* d_scalars, uint64_t n, double out[32], void* d_scratch);
-void msm_set_density_hint(const double* density);   // for the calling thread; nullptr = uniform scalars
 void group_add_run_g1(zkpoa_context* ctx, const void* a, const void* b, void* out, uint64_t n);
 void group_add_run_g2(zkpoa_context* ctx, const void* a, const void* b, void* out, uint64_t n);
 // zkpoa_field_prim / zkpoa_curve_prim (hooks.hip.h): an unknown op throws, also for n == 0
@@ -206,12 +215,10 @@ void gen_bases_g1(zkpoa_context* ctx, const uint8_t a_le[32], const uint8_t b_le
 void gen_bases_g2(zkpoa_context* ctx, const uint8_t a_le[32], const uint8_t b_le[32], uint64_t i0, uint64_t n, void* d_out);
 // shared-sort form (prover: the A, B1 and B2 queries use the same witness scalars): sort once on `lane`
 // (stream synchronised on return), then accumulate each base array on its own lane.
-struct MsmSorted;
-// for_g2: the result also feeds a G2 accumulation (shorter pieces: a G2 addition has 3x the latency)
-// table_c > 0: sort for the fixed-base (merged-bucket) form with that window width
-MsmSorted* msm_sort_run(zkpoa_context* ctx, int lane_id, const void* d_scalars, uint64_t n,
-                        bool for_g2 = false, int table_c = 0);  // delete with msm_sorted_free
-void msm_sorted_free(MsmSorted* sr);
+// The sorting lane also accumulates a G1 array afterwards (room for that is reserved in the same arena). The owner
+// keeps the result alive until every accumulation over it has returned. (std::default_delete needs the complete type:
+// only a translation unit that includes msm.hip.h can own one.)
+std::unique_ptr<MsmSorted> msm_sort_run(zkpoa_context* ctx, int lane_id, const void* d_scalars, const MsmRequest& req);
 void msm_accum_g1(zkpoa_context* ctx, int lane_id, const MsmSorted* sr, bool own_arena, const void* d_bases,
                   uint8_t* out, float* ms2);
 void msm_accum_g2(zkpoa_context* ctx, int lane_id, const MsmSorted* sr, bool own_arena, const void* d_bases,
