@@ -612,11 +612,32 @@ int zkpoa_merkle_leaves(zkpoa_context* ctx, const zkpoa_merkle* tree, uint64_t f
 int zkpoa_merkle_path(zkpoa_context* ctx, const zkpoa_merkle* tree, uint64_t leaf_index, uint8_t* path_le,
                       uint8_t* path_indices);
 
+/* ---- ECDSA -> ECDSA*: secp256k1 recovery, Keccak-256, Ethereum addresses; GPU ----------------------------------
+ * Stands in for the arithmetic of the reference's scripts/ecdsa_sigs_parser.ts + scripts/lib/ecdsa_star.ts (run at
+ * scripts/full_workflow.sh:354-357 with ethers and noble-secp256k1). Host buffers, nothing kept between calls.
+ * Byte order: every 32-byte integer of these three entry points (r, s, msghash, r', x, y) is BIG-endian, as the hex
+ * strings of a signatures file spell it and as Keccak takes a public key; digests and addresses are in their own order.
+ * zkpoa_ecdsa_star: n signatures. r, s, msghash: n x 32 B; v: n bytes (27 / 28); address20: n x 20 B, the address each
+ * signer claims. Out: r' (n x 32 B; the y coordinate of the nonce point R = (r, r'), parity by v), the recovered key
+ * Q = r^-1 (s R - z G) as x || y (n x 64 B), the address derived from it (n x 20 B) and a status byte per signature,
+ * the first that applies: 0 ok; 1 v is not 27 or 28; 2 r or s is zero or not below the group order; 3 s >= 2^255;
+ * 4 r^3 + 7 is not a square; 5 the key is the point at infinity; 6 the derived address differs from the one given.
+ * Statuses 1-5 come with zeros in every output, status 6 with what was derived. Only recovery ids 0 and 1 exist (an r
+ * that would need r + n is not tried). Returns PROVER_OK when it ran, whatever the statuses; n = 0 is a no-op.
+ * zkpoa_keccak256: n messages of one common length message_len (0..4096 bytes) packed back to back -> n x 32 B.
+ * zkpoa_eth_address: ethers.computeAddress for n uncompressed keys (x || y, n x 64 B): the 20 address bytes and the
+ * EIP-55 text, "0x" + 40 characters per key (n x 42 B, no terminator). */
+int zkpoa_ecdsa_star(zkpoa_context* ctx, uint64_t n, const void* r, const void* s, const void* msghash, const uint8_t* v,
+                     const void* address20, void* out_rprime, void* out_pubkey_xy, void* out_address20, uint8_t* out_status);
+int zkpoa_keccak256(zkpoa_context* ctx, const void* messages, uint64_t message_len, uint64_t n, void* out32);
+int zkpoa_eth_address(zkpoa_context* ctx, const void* pubkey_xy, uint64_t n, void* out_address20, void* out_checksum42);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* Timings (ms, HIP events on the stream that ran the kernels) of the last call on this context.
  * id: 0 = whole device part of last MSM, 1 = its bucket-accumulation kernel (dominant kernel),
  *     2 = last NTT, 3 = last prove: ABC+NTT chain, 4 = last prove: all MSMs, 5 = last prove: total,
- *     6 = last prove: self-check (host pairing check; 0 when it did not run), 7 = last Merkle tree build.
+ *     6 = last prove: self-check (host pairing check; 0 when it did not run), 7 = last Merkle tree build,
+ *     8 = last zkpoa_ecdsa_star: its kernels.
  * Also: tuning knobs. key "msm_c" forces the Pippenger window (0 = auto); key "msm_max_points" sets the
  * number of points one bucket sort may take (0 = 2^27; larger MSMs run in chunks -- tests force small values);
  * key "prove_serial" = 1 runs the stages of a prove one after the other (solo device times for the roofline);

@@ -17,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libzkpoa_prover.so")
 PROVER_BIN = os.path.join(_HERE, "prover")
 MERKLE_BIN = os.path.join(_HERE, "merkle-tree")
+SIGS_BIN = os.path.join(_HERE, "ecdsa-sigs-parser")
 SETUP_BIN = os.path.join(_HERE, "zkpoa-setup")
 
 PROVER_OK = 0
@@ -70,6 +71,7 @@ EXPORTS = [
     "zkpoa_blake2b_state", "zkpoa_blake2b_restore",
     "zkpoa_sqrt_device", "zkpoa_decompressed_form", "zkpoa_from_hash_form",
     "zkpoa_ptau_export_challenge", "zkpoa_ptau_challenge_contribute", "zkpoa_ptau_import_response",
+    "zkpoa_ecdsa_star", "zkpoa_keccak256", "zkpoa_eth_address",
 ]
 
 
@@ -118,6 +120,9 @@ def lib():
         L.zkpoa_merkle_root.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.zkpoa_merkle_leaves.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
         L.zkpoa_merkle_path.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+        L.zkpoa_ecdsa_star.argtypes = [ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * 9
+        L.zkpoa_keccak256.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
+        L.zkpoa_eth_address.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
         L.zkpoa_last_error.argtypes = [ctypes.c_void_p]
         L.zkpoa_last_error.restype = ctypes.c_char_p
         L.zkpoa_last_ms.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -406,6 +411,39 @@ class Context:
 
     def poseidon2_device(self, d_left, d_right, n, d_out):
         self._check(lib().zkpoa_poseidon2_device(self._h, d_left, d_right, n, d_out), "zkpoa_poseidon2_device")
+
+    # ---- ECDSA -> ECDSA* (scripts/ecdsa_sigs_parser.ts): 32-byte integers big-endian ------------------------------
+    def ecdsa_star(self, r, s, msghash, v, addresses):
+        """n signatures: r, s, msghash n x 32 B big-endian, v n bytes, addresses n x 20 B ->
+        (r' n x 32 B, keys n x 64 B (x || y), derived addresses n x 20 B, status bytes); include/zkpoa_prover.h."""
+        n = len(v)
+        if len(r) != 32 * n or len(s) != 32 * n or len(msghash) != 32 * n or len(addresses) != 20 * n:
+            raise ZkpoaError("ecdsa_star: the arrays do not describe %d signatures" % n)
+        bufs = [_buf(bytes(x)) for x in (r, s, msghash, v, addresses)]
+        outs = [ctypes.create_string_buffer(max(1, k * n)) for k in (32, 64, 20, 1)]
+        self._check(lib().zkpoa_ecdsa_star(self._h, n, *([b[0] for b in bufs] + outs)), "zkpoa_ecdsa_star")
+        return tuple(o.raw[:k * n] for o, k in zip(outs, (32, 64, 20, 1)))
+
+    def keccak256(self, messages, length):
+        """Keccak-256 of len(messages) / length messages of `length` bytes packed back to back (length 0: pass n)."""
+        if length:
+            n, data = len(messages) // length, bytes(messages)
+        else:
+            n, data = int(messages), b""
+        pm, km = _buf(data)
+        out = ctypes.create_string_buffer(max(1, 32 * n))
+        self._check(lib().zkpoa_keccak256(self._h, pm, length, n, out), "zkpoa_keccak256")
+        return out.raw[:32 * n]
+
+    def eth_address(self, pubkeys):
+        """ethers.computeAddress for n x 64 B keys (x || y big-endian) -> (n x 20 B, list of n EIP-55 strings)."""
+        n = len(pubkeys) // 64
+        pk, kk = _buf(bytes(pubkeys))
+        addr = ctypes.create_string_buffer(max(1, 20 * n))
+        text = ctypes.create_string_buffer(max(1, 42 * n))
+        self._check(lib().zkpoa_eth_address(self._h, pk, n, addr, text), "zkpoa_eth_address")
+        chars = text.raw[:42 * n].decode()   # .raw copies the whole buffer: once, not per key
+        return addr.raw[:20 * n], [chars[42 * i:42 * i + 42] for i in range(n)]
 
     def merkle_build(self, addresses, balances, device=False, n=None):
         """Tree over (address, balance) pairs: host buffers (n x 32 B LE each) or, with device=True, device pointers."""

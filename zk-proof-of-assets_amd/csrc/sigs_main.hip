@@ -1,0 +1,615 @@
+// `ecdsa-sigs-parser` -- stands in for two TypeScript steps of the reference's workflow:
+//   ecdsa-sigs-parser --signatures <in.json> --output-path <out.json>             scripts/ecdsa_sigs_parser.ts
+//       (full_workflow.sh:354-357): ECDSA signatures -> ECDSA* attestations. Recovery, r', Keccak and the address
+//       comparison run on the GPU (zkpoa_ecdsa_star, zkpoa_eth_address); the output is the text that
+//       JSON.stringify(outputData, jsonReplacer, 2) writes, byte for byte, and appears only when complete.
+//   ecdsa-sigs-parser layer-one-input -i <parsed.json> -o <out.json> [-s start] [-e end]
+//       scripts/input_prep_for_layer_one.ts (full_workflow.sh:497-501): host only, the signatures of one batch as
+//       4 x 64-bit limbs.
+// Both files are read through a pull parser over the mapped text: a million signatures are 350 MB of JSON in and over
+// a gigabyte out, and neither is ever held as a tree. The output is formatted by the host threads 2^16 entries at a
+// time. Exit status 0, or 1 with one line on stderr and no output file.
+#include "../../include/zkpoa_prover.h"
+#include "setup_common.hip.h"
+
+#include <stdio.h>
+#include <stdlib.h>
+
+namespace {
+
+typedef unsigned __int128 u128;
+
+struct InputError : std::runtime_error {
+  explicit InputError(const std::string& m) : std::runtime_error(m) {}
+};
+
+// ---- a read-only mapping of a whole file ---------------------------------------------------------------------------
+struct MappedText {
+  const char* base = nullptr;
+  size_t size = 0;
+  explicit MappedText(const std::string& path) {
+    const int fd = open(path.c_str(), O_RDONLY);
+    struct stat sb;
+    if (fd < 0 || fstat(fd, &sb) != 0) {
+      if (fd >= 0) close(fd);
+      throw InputError("cannot open " + path);
+    }
+    size = (size_t)sb.st_size;
+    if (size) {
+      void* m = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
+      if (m == MAP_FAILED) {
+        close(fd);
+        throw InputError("cannot map " + path);
+      }
+      base = static_cast<const char*>(m);
+    }
+    close(fd);
+  }
+  ~MappedText() {
+    if (base) munmap(const_cast<char*>(base), size);
+  }
+  MappedText(const MappedText&) = delete;
+  MappedText& operator=(const MappedText&) = delete;
+};
+
+// ---- JSON, pulled: the caller says what it expects next; whatever it does not know it skips -------------------------
+struct Span {
+  const char *b, *e;
+  size_t size() const { return (size_t)(e - b); }
+  bool is(const char* s) const { return size() == strlen(s) && memcmp(b, s, size()) == 0; }
+  std::string str() const { return std::string(b, e); }
+};
+
+struct Json {
+  const char *p, *e;
+  [[noreturn]] void fail(const char* what) const { throw InputError(std::string("malformed JSON: ") + what); }
+  void ws() {
+    while (p < e && (*p == ' ' || *p == '\n' || *p == '\t' || *p == '\r')) p++;
+  }
+  bool take(char c) {
+    ws();
+    if (p < e && *p == c) {
+      p++;
+      return true;
+    }
+    return false;
+  }
+  void expect(char c, const char* what) {
+    if (!take(c)) fail(what);
+  }
+  // a string without escapes (no key or value of these files has any): the characters between the quotes
+  Span string() {
+    expect('"', "a string was expected");
+    const char* b = p;
+    while (p < e && *p != '"') {
+      if (*p == '\\') fail("an escape in a key or a number string");
+      p++;
+    }
+    if (p >= e) fail("unterminated string");
+    return Span{b, p++};
+  }
+  Span number() {
+    ws();
+    const char* b = p;
+    while (p < e && (*p == '-' || *p == '+' || *p == '.' || (*p >= '0' && *p <= '9') || (*p | 32) == 'e')) p++;
+    if (b == p) fail("a number was expected");
+    return Span{b, p};
+  }
+  void skip() {   // any value
+    ws();
+    if (p >= e) fail("a value was expected");
+    if (*p == '"') {
+      p++;
+      while (p < e && *p != '"') p += (*p == '\\') ? 2 : 1;
+      if (p >= e) fail("unterminated string");
+      p++;
+    } else if (*p == '{') {
+      object([&](const Span&) { skip(); });
+    } else if (*p == '[') {
+      array([&](uint64_t) { skip(); });
+    } else {
+      const char* b = p;
+      while (p < e && *p != ',' && *p != '}' && *p != ']' && *p != ' ' && *p != '\n' && *p != '\t' && *p != '\r') p++;
+      if (b == p) fail("a value was expected");
+    }
+  }
+  template <class Fn>
+  void object(Fn member) {   // member(key) consumes the value
+    expect('{', "an object was expected");
+    if (take('}')) return;
+    do {
+      const Span key = string();
+      expect(':', "':' was expected");
+      member(key);
+    } while (take(','));
+    expect('}', "'}' was expected");
+  }
+  template <class Fn>
+  uint64_t array(Fn element) {   // element(index) consumes the value; returns the length
+    expect('[', "an array was expected");
+    uint64_t i = 0;
+    if (take(']')) return 0;
+    do element(i++);
+    while (take(','));
+    expect(']', "']' was expected");
+    return i;
+  }
+  void end() {
+    ws();
+    if (p != e) fail("text after the value");
+  }
+};
+
+// ---- 256-bit integers: big-endian bytes <-> decimal -------------------------------------------------------------------
+struct U256 {
+  uint64_t v[4] = {0, 0, 0, 0};   // least significant first
+  static U256 from_be(const uint8_t* b) {
+    U256 x;
+    for (int i = 0; i < 32; i++) x.v[3 - i / 8] |= (uint64_t)b[i] << (8 * (7 - i % 8));
+    return x;
+  }
+  bool mul_add(uint64_t mul, uint64_t add) {   // *this = *this * mul + add; false on overflow
+    u128 carry = add;
+    for (int i = 0; i < 4; i++) {
+      const u128 cur = (u128)v[i] * mul + carry;
+      v[i] = (uint64_t)cur;
+      carry = cur >> 64;
+    }
+    return carry == 0;
+  }
+  void append_dec(std::string& out) const {   // 19 digits per pass
+    uint64_t t[4] = {v[0], v[1], v[2], v[3]};
+    uint64_t part[5];
+    int parts = 0;
+    while (t[0] | t[1] | t[2] | t[3]) {
+      u128 rem = 0;
+      for (int k = 3; k >= 0; k--) {
+        const u128 cur = (rem << 64) | t[k];
+        t[k] = (uint64_t)(cur / 10000000000000000000ull);
+        rem = cur % 10000000000000000000ull;
+      }
+      part[parts++] = (uint64_t)rem;
+    }
+    if (!parts) {
+      out.push_back('0');
+      return;
+    }
+    char buf[24];
+    out.append(buf, (size_t)snprintf(buf, sizeof(buf), "%llu", (unsigned long long)part[parts - 1]));
+    for (int k = parts - 2; k >= 0; k--) out.append(buf, (size_t)snprintf(buf, sizeof(buf), "%019llu", (unsigned long long)part[k]));
+  }
+};
+
+U256 parse_number(const Span& s, const char* what) {   // decimal or 0x hex, below 2^256
+  // the decimal strings these files are full of: up to 19 digits per step
+  bool plain = s.size() > 0 && s.size() <= 78;
+  for (const char* q = s.b; plain && q < s.e; q++) plain = *q >= '0' && *q <= '9';
+  if (plain) {
+    U256 x;
+    bool fits = true;
+    for (const char* q = s.b; q < s.e;) {
+      uint64_t chunk = 0, scale = 1;
+      for (int k = 0; k < 19 && q < s.e; k++, q++) {
+        chunk = chunk * 10 + (uint64_t)(*q - '0');
+        scale *= 10;
+      }
+      fits = x.mul_add(scale, chunk) && fits;
+    }
+    if (!fits) throw InputError(std::string(what) + " is not a number below 2^256: " + s.str());
+    return x;
+  }
+  uint8_t le[32];
+  if (!zkpoa::parse_u256(s.b, s.e, le)) throw InputError(std::string(what) + " is not a number below 2^256: " + s.str());
+  U256 x;
+  memcpy(x.v, le, 32);
+  return x;
+}
+
+int hex_digit(char c) {
+  if (c >= '0' && c <= '9') return c - '0';
+  if ((c | 32) >= 'a' && (c | 32) <= 'f') return (c | 32) - 'a' + 10;
+  return -1;
+}
+// "0x" + exactly 2 * bytes hex digits -> bytes
+bool parse_hex_bytes(const Span& s, uint8_t* out, size_t bytes) {
+  if (s.size() != 2 + 2 * bytes || s.b[0] != '0' || s.b[1] != 'x') return false;
+  for (size_t i = 0; i < bytes; i++) {
+    const int hi = hex_digit(s.b[2 + 2 * i]), lo = hex_digit(s.b[3 + 2 * i]);
+    if (hi < 0 || lo < 0) return false;
+    out[i] = (uint8_t)(16 * hi + lo);
+  }
+  return true;
+}
+
+// "0x" + 1..64 hex digits -> 32 bytes, big-endian, padded on the left
+bool parse_hex_u256(const Span& s, uint8_t* out) {
+  if (s.size() < 3 || s.size() > 66 || s.b[0] != '0' || s.b[1] != 'x') return false;
+  memset(out, 0, 32);
+  int pos = 63;   // nibble index from the left of the 64
+  for (const char* q = s.e - 1; q >= s.b + 2; q--, pos--) {
+    const int d = hex_digit(*q);
+    if (d < 0) return false;
+    out[pos / 2] |= (uint8_t)((pos & 1) ? d : d << 4);
+  }
+  return true;
+}
+
+std::string entry(uint64_t i) { return "entry " + std::to_string(i) + ": "; }
+
+void write_ranges(AtomicFile& fo, uint64_t& off, const std::vector<std::string>& parts) {
+  for (const std::string& s : parts) {
+    fo.put_at(off, s.data(), s.size());
+    off += s.size();
+  }
+}
+
+// ---- parsing mode --------------------------------------------------------------------------------------------------
+struct Signatures {
+  std::vector<uint8_t> r, s, z, v, addr;   // 32, 32, 32, 1, 20 bytes per entry
+  std::vector<char> addr_text;             // 42 characters per entry, as given
+  std::vector<std::string> balance;        // decimal, no leading zeros
+  uint64_t n = 0;
+};
+
+void read_signatures(const std::string& path, Signatures& g) {
+  MappedText text(path);
+  Json js{text.base, text.base + text.size};
+  js.array([&](uint64_t i) {
+    bool have_sig = false, have_addr = false, have_bal = false;
+    g.r.resize(32 * (i + 1));
+    g.s.resize(32 * (i + 1));
+    g.z.resize(32 * (i + 1));
+    g.v.resize(i + 1);
+    g.addr.resize(20 * (i + 1));
+    g.addr_text.resize(42 * (i + 1));
+    js.object([&](const Span& key) {
+      if (key.is("signature")) {
+        unsigned seen = 0;
+        js.object([&](const Span& k2) {
+          if (k2.is("r") || k2.is("s")) {
+            const Span h = js.string();
+            // a 32-byte quantity: ethers takes "0x" + 64 digits; shorter spellings are padded here
+            if (!parse_hex_u256(h, (k2.b[0] == 'r' ? g.r.data() : g.s.data()) + 32 * i))
+              throw InputError(entry(i) + "signature." + k2.str() + " is not 0x-prefixed hex of at most 32 bytes");
+            seen |= k2.b[0] == 'r' ? 1u : 2u;
+          } else if (k2.is("msghash")) {
+            if (!parse_hex_bytes(js.string(), g.z.data() + 32 * i, 32)) throw InputError(entry(i) + "signature.msghash is not 0x + 64 hex digits");
+            seen |= 4u;
+          } else if (k2.is("v")) {
+            const Span num = js.number();
+            char* rest = nullptr;
+            const std::string t = num.str();
+            const long val = strtol(t.c_str(), &rest, 10);
+            if (!rest || *rest) throw InputError(entry(i) + "signature.v is not an integer: " + t);
+            g.v[i] = (uint8_t)(val < 0 || val > 255 ? 255 : val);   // anything but 27 / 28 is status 1
+            seen |= 8u;
+          } else {
+            js.skip();
+          }
+        });
+        if (seen != 15u) throw InputError(entry(i) + "signature needs r, s, v and msghash");
+        have_sig = true;
+      } else if (key.is("address")) {
+        const Span a = js.string();
+        if (!parse_hex_bytes(a, g.addr.data() + 20 * i, 20)) throw InputError(entry(i) + "address is not 0x + 40 hex digits: " + a.str());
+        memcpy(g.addr_text.data() + 42 * i, a.b, 42);
+        have_addr = true;
+      } else if (key.is("balance")) {
+        Span b = js.string();
+        if (b.size() && b.e[-1] == 'n') b.e--;   // a BigInt literal's suffix, as the reference accepts it
+        if (!b.size()) throw InputError(entry(i) + "balance is empty");
+        for (const char* q = b.b; q < b.e; q++)
+          if (*q < '0' || *q > '9') throw InputError(entry(i) + "balance is not a decimal number: " + b.str());
+        while (b.size() > 1 && *b.b == '0') b.b++;
+        g.balance.push_back(b.str());
+        have_bal = true;
+      } else {
+        js.skip();
+      }
+    });
+    if (!have_sig || !have_addr || !have_bal) throw InputError(entry(i) + "needs signature, address and balance");
+    g.n = i + 1;
+  });
+  js.end();
+}
+
+const char* status_text(unsigned st) {
+  switch (st) {
+    case 2: return "r or s is zero or not below the group order";
+    case 3: return "non-canonical s (s >= 2^255)";
+    case 4: return "r is not the x coordinate of a curve point";
+    case 5: return "the recovered public key is the point at infinity";
+    default: return "unknown status";
+  }
+}
+
+void put_big(std::string& o, const char* indent, const char* key, const U256& x, bool last) {
+  o += indent;
+  o += "\"";
+  o += key;
+  o += "\": {\n";
+  o += indent;
+  o += "  \"__bigint__\": \"";
+  x.append_dec(o);
+  o += "\"\n";
+  o += indent;
+  o += last ? "}\n" : "},\n";
+}
+
+int parse_mode(const std::string& in_path, const std::string& out_path, bool verbose) {
+  zkpoa_context* ctx = nullptr;
+  char err[512] = {0};
+  long dev = 0;
+  if (const char* e = getenv("ZKPOA_DEVICE")) {
+    char* rest = nullptr;
+    dev = strtol(e, &rest, 10);
+    if (rest == e || *rest || dev < 0 || dev > 1023) throw InputError(std::string("ZKPOA_DEVICE: not a device index: ") + e);
+  }
+  // the device context (HIP start-up) is created on a second thread while this one reads the file
+  int ctx_rc = PROVER_OK;
+  std::thread ctx_thread([&] { ctx_rc = zkpoa_context_create((int)dev, &ctx, err, sizeof(err)); });
+  Signatures g;
+  PhaseTimer lap("ecdsa-sigs-parser", 8);
+  try {
+    read_signatures(in_path, g);
+  } catch (...) {
+    ctx_thread.join();
+    throw;
+  }
+  lap("read");
+  ctx_thread.join();   // what is left of the start-up counts as device time
+  const uint64_t n = g.n;
+  printf("Parsing %llu ECDSA signatures..\n", (unsigned long long)n);
+  if (ctx_rc != PROVER_OK) throw InputError(err);
+  std::vector<uint8_t> rprime(32 * n + 1), pub(64 * n + 1), derived(20 * n + 1), status(n + 1);
+  std::vector<char> text(42 * n + 1);
+  if (zkpoa_ecdsa_star(ctx, n, g.r.data(), g.s.data(), g.z.data(), g.v.data(), g.addr.data(), rprime.data(), pub.data(),
+                       derived.data(), status.data()) != PROVER_OK)
+    throw InputError(std::string("zkpoa_ecdsa_star: ") + zkpoa_last_error(ctx));
+  if (zkpoa_eth_address(ctx, pub.data(), n, derived.data(), text.data()) != PROVER_OK)
+    throw InputError(std::string("zkpoa_eth_address: ") + zkpoa_last_error(ctx));
+  lap("device");
+  // the reference compares strings: the address given must be the EIP-55 spelling of the one derived
+  for (uint64_t i = 0; i < n; i++) {
+    const unsigned st = status[i];
+    if (st == 1) throw InputError(entry(i) + "Invalid ECDSA 'v' value " + std::to_string((int)g.v[i]) + " (must be 27 or 28)");
+    if (st != 0 && st != 6) throw InputError(entry(i) + status_text(st));
+    if (st == 6 || memcmp(&text[42 * i], &g.addr_text[42 * i], 42) != 0)
+      throw InputError(entry(i) + "the address given is " + std::string(&g.addr_text[42 * i], 42) + " but the signature's key has address " +
+                       std::string(&text[42 * i], 42));
+  }
+  printf("Successfully parsed ECDSA signatures and converted them to ECDSA* signatures\n");
+  AtomicFile fo(out_path.c_str());
+  uint64_t off = 0;
+  const std::string head = n ? "{\n  \"accountAttestations\": [\n" : "{\n  \"accountAttestations\": []\n}";
+  fo.put_at(off, head.data(), head.size());
+  off += head.size();
+  constexpr uint64_t kRound = 1u << 16;
+  for (uint64_t i0 = 0; i0 < n; i0 += kRound) {
+    const uint64_t m = std::min(kRound, n - i0);
+    std::vector<std::string> parts(host_threads() + 1);
+    parallel_ranges(m, 256, [&](unsigned t, uint64_t lo, uint64_t hi) {
+      std::string& o = parts[t];
+      o.reserve((hi - lo) * 1400);
+      for (uint64_t i = i0 + lo; i < i0 + hi; i++) {
+        o += "    {\n      \"signature\": {\n";
+        put_big(o, "        ", "r", U256::from_be(&g.r[32 * i]), false);
+        put_big(o, "        ", "s", U256::from_be(&g.s[32 * i]), false);
+        put_big(o, "        ", "r_prime", U256::from_be(&rprime[32 * i]), false);
+        o += "        \"pubkey\": {\n";
+        put_big(o, "          ", "x", U256::from_be(&pub[64 * i]), false);
+        put_big(o, "          ", "y", U256::from_be(&pub[64 * i + 32]), true);
+        o += "        },\n        \"msghash\": {\n          \"__uint8array__\": [\n";
+        for (int k = 0; k < 32; k++) {
+          o += "            ";
+          o += std::to_string((unsigned)g.z[32 * i + k]);
+          o += k < 31 ? ",\n" : "\n";
+        }
+        o += "          ]\n        }\n      },\n      \"accountData\": {\n";
+        uint8_t a32[32] = {0};
+        memcpy(a32 + 12, &derived[20 * i], 20);
+        put_big(o, "        ", "address", U256::from_be(a32), false);
+        o += "        \"balance\": {\n          \"__bigint__\": \"" + g.balance[i] + "\"\n        }\n      }\n    }";
+        o += i + 1 < n ? ",\n" : "\n  ]\n}";
+      }
+    });
+    write_ranges(fo, off, parts);
+  }
+  fo.commit();
+  lap("write");
+  return 0;
+}
+
+// ---- layer-one-input mode ------------------------------------------------------------------------------------------
+struct StarSig {
+  U256 r, s, rprime, x, y, msghash;
+};
+
+U256 read_bigint(Json& js, const char* what) {
+  U256 out;
+  bool seen = false;
+  js.object([&](const Span& k) {
+    if (k.is("__bigint__")) {
+      out = parse_number(js.string(), what);
+      seen = true;
+    } else {
+      js.skip();
+    }
+  });
+  if (!seen) throw InputError(std::string(what) + " is not a {\"__bigint__\": ...} object");
+  return out;
+}
+
+void put_limbs(std::string& o, const char* indent, const U256& x, bool last) {
+  o += indent;
+  o += "[\n";
+  for (int k = 0; k < 4; k++) {
+    o += indent;
+    o += "  \"" + std::to_string((unsigned long long)x.v[k]) + (k < 3 ? "\",\n" : "\"\n");
+  }
+  o += indent;
+  o += last ? "]\n" : "],\n";
+}
+
+int layer_one_mode(const std::string& in_path, const std::string& out_path, long long start, long long end) {
+  printf("Preparing input for layer 1 using the following data:\n- System input: %s\n- Start index for batch: %lld\n"
+         "- End index for batch: %lld\nPath to write processed data to: %s\n\n",
+         in_path.c_str(), start, end, out_path.c_str());
+  std::vector<StarSig> sigs;   // entries first_kept, first_kept + 1, ...
+  const long long first_kept = start > 0 ? start : 0;
+  long long total = 0;
+  {
+    MappedText text(in_path);
+    Json js{text.base, text.base + text.size};
+    bool seen = false;
+    js.object([&](const Span& key) {
+      if (!key.is("accountAttestations")) return js.skip();
+      seen = true;
+      js.array([&](uint64_t i) {
+        // only the entries the range can reach are converted; the others are counted and skipped
+        total = (long long)i + 1;
+        if ((start >= 0 && (long long)i < start) || (end >= 0 && (long long)i >= end)) return js.skip();
+        StarSig g;
+        unsigned have = 0;
+        js.object([&](const Span& k1) {
+          if (!k1.is("signature")) return js.skip();
+          js.object([&](const Span& k2) {
+            if (k2.is("r")) g.r = read_bigint(js, "r"), have |= 1u;
+            else if (k2.is("s")) g.s = read_bigint(js, "s"), have |= 2u;
+            else if (k2.is("r_prime")) g.rprime = read_bigint(js, "r_prime"), have |= 4u;
+            else if (k2.is("pubkey")) {
+              js.object([&](const Span& k3) {
+                if (k3.is("x")) g.x = read_bigint(js, "pubkey.x"), have |= 8u;
+                else if (k3.is("y")) g.y = read_bigint(js, "pubkey.y"), have |= 16u;
+                else js.skip();
+              });
+            } else if (k2.is("msghash")) {
+              js.object([&](const Span& k3) {
+                if (!k3.is("__uint8array__")) return js.skip();
+                uint8_t bytes[32] = {0};
+                const uint64_t len = js.array([&](uint64_t k) {
+                  const std::string t = js.number().str();
+                  char* rest = nullptr;
+                  const long val = strtol(t.c_str(), &rest, 10);
+                  if (!rest || *rest || val < 0 || val > 255 || k >= 32) throw InputError(entry(i) + "msghash is not 32 bytes");
+                  bytes[k] = (uint8_t)val;
+                });
+                if (len != 32) throw InputError(entry(i) + "msghash is not 32 bytes");
+                g.msghash = U256::from_be(bytes);
+                have |= 32u;
+              });
+            } else {
+              js.skip();
+            }
+          });
+        });
+        if (have != 63u) throw InputError(entry(i) + "signature needs r, s, r_prime, pubkey.x, pubkey.y and msghash");
+        sigs.push_back(g);
+      });
+    });
+    js.end();
+    if (!seen) throw InputError("no accountAttestations in " + in_path);
+  }
+  const long long len = total;
+  if (end == -1) {
+    printf("Batch contains all input data i.e. there is only 1 batch\n");
+    end = len;
+  }
+  if (start >= end) throw InputError("startIndex " + std::to_string(start) + " must be less than endIndex " + std::to_string(end));
+  // Array.prototype.slice: a negative index counts from the end, both are clamped to [0, length]
+  const long long lo = std::min(len, start < 0 ? std::max(0ll, len + start) : start);
+  const long long hi = std::max(lo, std::min(len, end < 0 ? std::max(0ll, len + end) : end));
+  const uint64_t m = (uint64_t)(hi - lo);
+  AtomicFile fo(out_path.c_str());
+  uint64_t off = 0;
+  const char* names[5] = {"r", "s", "rprime", "pubkey", "msghash"};
+  for (int f = 0; f < 5; f++) {
+    std::string headtxt = std::string(f ? "" : "{\n") + "  \"" + names[f] + (m ? "\": [\n" : "\": []");
+    fo.put_at(off, headtxt.data(), headtxt.size());
+    off += headtxt.size();
+    std::vector<std::string> parts(host_threads() + 1);
+    parallel_ranges(m, 1024, [&](unsigned t, uint64_t a, uint64_t b) {
+      std::string& o = parts[t];
+      for (uint64_t i = a; i < b; i++) {
+        const StarSig& g = sigs[(uint64_t)(lo - first_kept) + i];
+        const bool last = i + 1 == m;
+        if (f == 3) {
+          o += "    [\n";
+          put_limbs(o, "      ", g.x, false);
+          put_limbs(o, "      ", g.y, true);
+          o += last ? "    ]\n" : "    ],\n";
+        } else {
+          put_limbs(o, "    ", f == 0 ? g.r : f == 1 ? g.s : f == 2 ? g.rprime : g.msghash, last);
+        }
+      }
+    });
+    write_ranges(fo, off, parts);
+    const std::string tail = std::string(m ? "  ]" : "") + (f < 4 ? ",\n" : "\n}");
+    fo.put_at(off, tail.data(), tail.size());
+    off += tail.size();
+  }
+  fo.commit();
+  return 0;
+}
+
+bool parse_index(const char* s, long long& out) {
+  char* rest = nullptr;
+  out = strtoll(s, &rest, 10);
+  return rest != s && !*rest;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  const bool verbose = getenv("ZKPOA_VERBOSE") != nullptr;
+  int rc = 0;
+  try {
+    const bool layer_one = argc > 1 && strcmp(argv[1], "layer-one-input") == 0;
+    std::string in, out;
+    long long start = 0, end = -1;
+    for (int i = layer_one ? 2 : 1; i < argc; i++) {
+      std::string a = argv[i];
+      std::string val;
+      bool has = false;
+      const size_t eq = a.find('=');
+      if (a.rfind("--", 0) == 0 && eq != std::string::npos) {
+        val = a.substr(eq + 1);
+        a = a.substr(0, eq);
+        has = true;
+      }
+      auto value = [&]() -> std::string {
+        if (has) return val;
+        if (i + 1 >= argc) throw InputError("option " + a + " needs a value");
+        return argv[++i];
+      };
+      if (a == "-h" || a == "--help") {
+        printf("Usage: ecdsa-sigs-parser --signatures <in.json> --output-path <out.json>\n"
+               "       ecdsa-sigs-parser layer-one-input --poa-input-data <parsed.json> --write-layer-one-data-to <out.json>\n"
+               "                         [--account-start-index <i>] [--account-end-index <j>]\n");
+        return 0;
+      } else if (!layer_one && (a == "-s" || a == "--signatures")) in = value();
+      else if (!layer_one && (a == "-o" || a == "--output-path")) out = value();
+      else if (layer_one && (a == "-i" || a == "--poa-input-data")) in = value();
+      else if (layer_one && (a == "-o" || a == "--write-layer-one-data-to")) out = value();
+      else if (layer_one && (a == "-s" || a == "--account-start-index")) {
+        if (!parse_index(value().c_str(), start)) throw InputError("--account-start-index is not an integer");
+      } else if (layer_one && (a == "-e" || a == "--account-end-index")) {
+        if (!parse_index(value().c_str(), end)) throw InputError("--account-end-index is not an integer");
+      } else throw InputError("unknown argument " + a);
+    }
+    if (in.empty() || out.empty()) {
+      fprintf(stderr, layer_one ? "error: layer-one-input needs --poa-input-data <FILE> and --write-layer-one-data-to <FILE>\n"
+                                : "error: --signatures <FILE> and --output-path <FILE> are required\n");
+      return 2;
+    }
+    rc = layer_one ? layer_one_mode(in, out, start, end) : parse_mode(in, out, verbose);
+  } catch (const std::exception& e) {
+    fprintf(stderr, "Error: %s\n", e.what());
+    rc = 1;
+  }
+  // the output is complete and renamed into place (or the error is on stderr): leave without the HIP runtime's
+  // teardown, as merkle-tree does
+  fflush(stdout);
+  fflush(stderr);
+  _exit(rc);
+}
