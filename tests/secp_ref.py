@@ -1,6 +1,7 @@
 """Big-integer restatement of the ecdsa-sigs-parser step: secp256k1 public-key recovery in the ECDSA* form, Keccak-256,
 Ethereum addresses with the EIP-55 checksum, the two JSON texts of the command, and a generator of signatures whose
 answers are known by construction. Independent of the device code (plain Python integers) and of ethers / noble."""
+import copy
 import json
 import random
 
@@ -290,3 +291,23 @@ def layer_one_text(parser_text, start=0, end=-1):
         out["pubkey"].append([limbs64(int(sig["pubkey"]["x"]["__bigint__"])), limbs64(int(sig["pubkey"]["y"]["__bigint__"]))])
         out["msghash"].append(limbs64(int.from_bytes(bytes(sig["msghash"]["__uint8array__"]), "big")))
     return json.dumps(out, indent=2)
+
+
+def with_unknown_members(doc, bare=0):
+    """A parsed-signatures document with members no reader of it knows: nested arrays and objects, strings with escapes,
+    true / false / null, negative and exponent numbers, and under keys that begin with "extra" (which
+    tools/host_text_check.cpp skips whole) keys with escapes and a __bigint__ that is not one of the file's. accountData
+    comes before signature, and entry `bare` has its address as a bare number."""
+    nest = {"flags": [True, False, None], "numbers": [-12, 2.5e-3, -1E+20, 0], "deep": [[1, [2, {"k": "v \" \\ \u00e9"}]], [], {}]}
+    out = {"extra_head": {"accountAttestations": [{"__bigint__": "7"}], "k\"e\\y\u00e9": [[], {}, [[["x"]]]]}, "version": 3}
+    atts = []
+    for i, a in enumerate(doc["accountAttestations"]):
+        data = copy.deepcopy(a["accountData"])
+        if i == bare:
+            data["address"] = {"__bigint__": int(data["address"]["__bigint__"])}
+        data = dict({"extra_note": "quote \" backslash \\ e-acute \u00e9 brackets ]}["}, **data, label="it's \"mine\"", tags=nest)
+        atts.append({"extra": [{"__bigint__": "8", "s\\": None}], "accountData": data, "meta": nest,
+                     "signature": a["signature"]})
+    out["accountAttestations"] = atts
+    out["trailer"] = {"count": len(atts), "ok": True, "extra_tail": "\\"}
+    return out

@@ -175,6 +175,36 @@ def test_merkle_tree_cli_drop_in(zk, tmp_path):
     assert rc.returncode != 0 and "not below the BN254 scalar modulus" in rc.stderr
 
 
+def test_merkle_tree_cli_skips_what_it_does_not_know(zk, tmp_path):
+    """The parsed-signatures file is pulled, not held as a tree: with unknown members everywhere (nested values, escapes in
+    strings, accountData before signature, one __bigint__ a bare number), written compact, both output files are the bytes
+    the plain file gives. A skipped member nested 100 000 deep is refused in one line, and nothing is written."""
+    import secp_ref as sr
+    addr, bal = anon_set()
+    poa = {"accountAttestations": [
+        {"signature": {"r": {"__bigint__": "1"}, "s": {"__bigint__": "2"}},
+         "accountData": {"address": {"__bigint__": str(addr[i])}, "balance": {"__bigint__": str(bal[i])}}} for i in [1, 3, 9]]}
+    texts = {"plain": json.dumps(poa, indent=2), "unknown": json.dumps(sr.with_unknown_members(poa), separators=(",", ":")),
+             "deep": '{"accountAttestations": [], "history": ' + "[" * 100000 + "]" * 100000 + "}"}
+    assert '"__bigint__":%d}' % addr[1] in texts["unknown"]
+    assert texts["unknown"].index('"accountData"') < texts["unknown"].index('"signature"')
+    rcs = {}
+    for name, text in texts.items():
+        (tmp_path / (name + ".json")).write_text(text)
+        (tmp_path / name).mkdir()
+        rcs[name] = subprocess.run([zk.MERKLE_BIN, "--anon-set", os.path.join(GOLDEN, "ref", "merkle", "anonymity_set_10.csv"),
+                                    "--poa-input-data", str(tmp_path / (name + ".json")), "--output-dir", str(tmp_path / name)],
+                                   capture_output=True, text=True, timeout=120)
+    assert rcs["plain"].returncode == 0 and rcs["unknown"].returncode == 0, (rcs["plain"].stderr, rcs["unknown"].stderr)
+    assert (tmp_path / "plain" / "merkle_root.json").read_text() == '{\n  "__bigint__": "%d"\n}' % REF_ROOT
+    assert len(json.loads((tmp_path / "plain" / "merkle_proofs.json").read_text())["leaves"]) == 3
+    for out in ("merkle_root.json", "merkle_proofs.json"):
+        assert (tmp_path / "unknown" / out).read_bytes() == (tmp_path / "plain" / out).read_bytes()
+    assert rcs["deep"].returncode == 1
+    assert rcs["deep"].stderr.count("\n") == 1 and "nesting too deep" in rcs["deep"].stderr
+    assert os.listdir(tmp_path / "deep") == []
+
+
 @pytest.mark.parametrize("threads", ["1", "7"])
 def test_merkle_tree_cli_reads_a_messy_csv_in_parallel(zk, tmp_path, threads):
     """The CLI maps the anonymity set and parses it in pieces cut at line starts, one per thread (a 10 M-line set is ~650 MB

@@ -2,12 +2,12 @@
 //   hipcc -std=c++17 -O1 -g --offload-host-only -Xarch_host -fsanitize=address,undefined \
 //         -I zk-proof-of-assets_amd/csrc tools/record_codec_check.hip -o tools/record_codec_check
 //   tools/record_codec_check [file.ptau | file.zkey]...
-// parse_u256 (csrc/parse_u256.hpp) on accepted and refused texts; RecordParams (csrc/phase2.hpp) written and parsed back
+// U256::parse_number (csrc/host_text.hpp) on accepted and refused texts; RecordParams (csrc/phase2.hpp) written and parsed back
 // for an empty record, a name alone and a beacon with a 255-byte name and a 255-byte beacon, and every truncation of the
 // written bytes refused; for each file named, write_section7(parse_section7(x)) == x (.ptau) or the same for section 10
 // (.zkey) over the section's bytes. Exit status 0 and "ok", or the first failure.
 #include "binfile.hpp"
-#include "parse_u256.hpp"
+#include "host_text.hpp"
 #include "phase1.hpp"
 
 #include <stdio.h>
@@ -35,7 +35,10 @@ namespace p2 = zkpoa::phase2;
 static bool parses(const std::string& s, uint8_t out[32]) {
   // an exact-size copy with no terminator: a read past `end` is the sanitizer's to find
   std::vector<char> v(s.begin(), s.end());
-  return zkpoa::parse_u256(v.data(), v.data() + v.size(), out);
+  zkpoa::U256 x;
+  const bool ok = x.parse_number(v.data(), v.data() + v.size());
+  x.to_le(out);
+  return ok;
 }
 
 static void check_parser() {

@@ -4,6 +4,8 @@
 // Same class interface as the device Fp so the curve templates in bn254_ec.hip.h serve both.
 // This is product code (it never runs an MSM/NTT on the CPU: the hot path is HIP-only).
 #pragma once
+#include "host_text.hpp"
+
 #include <stdint.h>
 #include <string.h>
 #include <string>
@@ -155,25 +157,8 @@ struct HFp {
   }
   // decimal string of the standard-form value
   std::string to_dec() const {
-    HFp s = from_mont();
-    uint64_t v[4] = {s.l[0], s.l[1], s.l[2], s.l[3]};
-    std::string out;
-    while (v[0] | v[1] | v[2] | v[3]) {
-      u128 rem = 0;
-      for (int i = 3; i >= 0; i--) {
-        u128 cur = (rem << 64) | v[i];
-        v[i] = (uint64_t)(cur / 10000000000000000000ull);
-        rem = cur % 10000000000000000000ull;
-      }
-      uint64_t chunk = (uint64_t)rem;
-      bool more = (v[0] | v[1] | v[2] | v[3]) != 0;
-      for (int d = 0; d < 19 && (more || chunk); d++) {
-        out.push_back('0' + (chunk % 10));
-        chunk /= 10;
-      }
-    }
-    if (out.empty()) out = "0";
-    return std::string(out.rbegin(), out.rend());
+    const HFp s = from_mont();
+    return U256{{s.l[0], s.l[1], s.l[2], s.l[3]}}.dec();
   }
 };
 

@@ -7,101 +7,29 @@
 // path and index bits. The hashing runs on the GPU (libzkpoa_prover.so: csrc/poseidon.hip); the reference's own note
 // says 2.5 hours for a 10 M set on the CPU (merkle_tree.rs:3-5). Exit status 0 / non-zero + message, like the prover.
 #include "../../include/zkpoa_prover.h"
-#include "mini_json.hpp"
+#include "host_files.hpp"
+#include "host_text.hpp"
 
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <unistd.h>
-#include <string.h>
-
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-
-#include <exception>
-#include <fstream>
-#include <memory>
-#include <sstream>
-#include <stdexcept>
-#include <string>
 #include <chrono>
-#include <thread>
-#include <vector>
+#include <memory>
 
-using zkpoa::json::JVal;
-typedef unsigned __int128 u128;
+using namespace zkpoa;
 
 static const uint64_t kR[4] = {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull};
 
-struct U256 {
-  uint64_t v[4] = {0, 0, 0, 0};
-  bool mul_add(unsigned mul, unsigned add) {   // v = v * mul + add; false on overflow
-    u128 carry = add;
-    for (int i = 0; i < 4; i++) {
-      u128 cur = (u128)v[i] * mul + carry;
-      v[i] = (uint64_t)cur;
-      carry = cur >> 64;
-    }
-    return carry == 0;
-  }
-  bool below_r() const {
-    for (int i = 3; i >= 0; i--) {
-      if (v[i] < kR[i]) return true;
-      if (v[i] > kR[i]) return false;
-    }
-    return false;
-  }
-  std::string dec() const {
-    uint64_t t[4] = {v[0], v[1], v[2], v[3]};
-    std::string rev;
-    while (t[0] | t[1] | t[2] | t[3]) {
-      u128 rem = 0;
-      for (int k = 3; k >= 0; k--) {
-        u128 cur = (rem << 64) | t[k];
-        t[k] = (uint64_t)(cur / 10);
-        rem = cur % 10;
-      }
-      rev.push_back((char)('0' + (int)rem));
-    }
-    return rev.empty() ? "0" : std::string(rev.rbegin(), rev.rend());
-  }
-};
-
-static U256 parse_num(const char* b, const char* e, unsigned base, const char* what) {
+// a field element from its digits: decimal, or the hex digits of a csv address after its prefix
+static U256 parse_num(const char* b, const char* e, bool hex, const char* what) {
   U256 x;
   if (b == e) throw std::runtime_error(std::string("empty ") + what);
-  for (const char* q = b; q < e; q++) {
-    const char ch = *q;
-    unsigned d;
-    if (ch >= '0' && ch <= '9') d = (unsigned)(ch - '0');
-    else if (base == 16 && ch >= 'a' && ch <= 'f') d = (unsigned)(ch - 'a' + 10);
-    else if (base == 16 && ch >= 'A' && ch <= 'F') d = (unsigned)(ch - 'A' + 10);
-    else throw std::runtime_error(std::string("malformed ") + what + ": " + std::string(b, e));
-    if (!x.mul_add(base, d)) throw std::runtime_error(std::string(what) + " does not fit 256 bits: " + std::string(b, e));
+  if (!(hex ? x.parse_hex(b, e) : x.parse_dec(b, e))) {   // a character that is no digit, or digits of 2^256 and above
+    bool digits = true;
+    for (const char* q = b; q < e; q++) digits = digits && (hex ? hex_digit(*q) >= 0 : *q >= '0' && *q <= '9');
+    throw std::runtime_error(digits ? std::string(what) + " does not fit 256 bits: " + std::string(b, e)
+                                    : std::string("malformed ") + what + ": " + std::string(b, e));
   }
   // light-poseidon's hash_bytes_be refuses inputs that are not field elements (the Rust binary would panic)
-  if (!x.below_r()) throw std::runtime_error(std::string(what) + " is not below the BN254 scalar modulus: " + std::string(b, e));
+  if (!x.below(kR)) throw std::runtime_error(std::string(what) + " is not below the BN254 scalar modulus: " + std::string(b, e));
   return x;
-}
-
-static U256 parse_num(const std::string& s, unsigned base, const char* what) {
-  return parse_num(s.data(), s.data() + s.size(), base, what);
-}
-
-static std::string read_file(const std::string& path) {
-  std::ifstream f(path, std::ios::binary);
-  if (!f) throw std::runtime_error("cannot open " + path);
-  std::stringstream ss;
-  ss << f.rdbuf();
-  return ss.str();
-}
-
-static void write_file(const std::string& path, const std::string& text) {
-  std::string tmp = path + ".tmp." + std::to_string((long)getpid());
-  FILE* f = fopen(tmp.c_str(), "wb");
-  if (!f || fwrite(text.data(), 1, text.size(), f) != text.size() || fclose(f) != 0 || rename(tmp.c_str(), path.c_str()) != 0)
-    throw std::runtime_error("cannot write " + path);
 }
 
 // ---- the anonymity set: a 10 M-line csv is ~650 MB of text, and a line-at-a-time reader would take longer over it than
@@ -134,7 +62,7 @@ static void parse_row(const char* b, const char* e, uint64_t* addr, uint64_t* ba
   trim_span(bb, be);
   if (ae - ab < 3 || ab[0] != '0' || (ab[1] != 'x' && ab[1] != 'X'))
     throw std::runtime_error("address is not 0x-prefixed hex: " + std::string(ab, ae));
-  const U256 av = parse_num(ab + 2, ae, 16, "address"), bv = parse_num(bb, be, 10, "balance");
+  const U256 av = parse_num(ab + 2, ae, true, "address"), bv = parse_num(bb, be, false, "balance");
   memcpy(addr, av.v, 32);
   memcpy(bal, bv.v, 32);
 }
@@ -150,93 +78,98 @@ struct Limbs {
   uint64_t* data() { return p.get(); }
 };
 static void read_anonymity_set(const std::string& path, Limbs& addr, Limbs& bal) {
-  int fd = open(path.c_str(), O_RDONLY);
-  struct stat sb;
-  if (fd < 0 || fstat(fd, &sb) != 0) {
-    if (fd >= 0) close(fd);
-    throw std::runtime_error("cannot open " + path);
-  }
-  const size_t size = (size_t)sb.st_size;
-  if (size == 0) {
-    close(fd);
-    return;
-  }
-  void* map = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
-  close(fd);
-  if (map == MAP_FAILED) throw std::runtime_error("cannot map " + path);
-  const char* base = static_cast<const char*>(map);
-  const char* end = base + size;
-  try {
-    // the heading: the first non-blank line
-    const char* body = end;
-    {
-      const char* b = base;
-      while (b < end) {
-        const char* nl = static_cast<const char*>(memchr(b, '\n', (size_t)(end - b)));
-        const char* le = nl ? nl : end;
-        const char *tb = b, *te = le;
-        trim_span(tb, te);
-        b = nl ? nl + 1 : end;
-        if (tb < te) {
-          body = b;
-          break;
-        }
+  const MappedFile map(path.c_str());
+  if (!map.size) return;
+  const char *base = map.begin(), *end = map.end();
+  // the heading: the first non-blank line
+  const char* body = end;
+  {
+    const char* b = base;
+    while (b < end) {
+      const char* nl = static_cast<const char*>(memchr(b, '\n', (size_t)(end - b)));
+      const char* le = nl ? nl : end;
+      const char *tb = b, *te = le;
+      trim_span(tb, te);
+      b = nl ? nl + 1 : end;
+      if (tb < te) {
+        body = b;
+        break;
       }
     }
-    unsigned T = std::thread::hardware_concurrency();
-    if (T > 16) T = 16;
-    bool forced = false;
-    if (const char* e = getenv("ZKPOA_MERKLE_THREADS")) {
-      char* rest = nullptr;
-      const long v = strtol(e, &rest, 10);
-      if (rest == e || *rest || v < 1 || v > 256)
-        throw std::runtime_error(std::string("ZKPOA_MERKLE_THREADS must be 1..256, not '") + e + "'");
-      T = (unsigned)v;
-      forced = true;
-    }
-    if (T < 1) T = 1;
-    if ((size_t)(end - body) < (1u << 16) && !forced) T = 1;
-    std::vector<const char*> cut(T + 1, end);
-    cut[0] = body;
-    for (unsigned t = 1; t < T; t++) {   // piece boundaries moved forward to the next line start
-      const char* p = body + (size_t)(end - body) / T * t;
-      if (p < cut[t - 1]) p = cut[t - 1];
-      const char* nl = p < end ? static_cast<const char*>(memchr(p, '\n', (size_t)(end - p))) : nullptr;
-      cut[t] = nl ? nl + 1 : end;
-    }
-    std::vector<uint64_t> rows(T, 0);
-    std::vector<std::exception_ptr> errs(T);
-    auto run = [&](auto fn) {
-      std::vector<std::thread> th;
-      for (unsigned t = 0; t < T; t++)
-        th.emplace_back([&, t] {
-          try {
-            fn(t);
-          } catch (...) {
-            errs[t] = std::current_exception();
-          }
-        });
-      for (auto& x : th) x.join();
-      for (auto& e : errs)
-        if (e) std::rethrow_exception(e);   // the first failing piece in file order
-    };
-    run([&](unsigned t) { for_lines(cut[t], cut[t + 1], [&](const char*, const char*) { rows[t]++; }); });
-    std::vector<uint64_t> first(T + 1, 0);
-    for (unsigned t = 0; t < T; t++) first[t + 1] = first[t] + rows[t];
-    addr.alloc(first[T]);
-    bal.alloc(first[T]);
-    run([&](unsigned t) {
-      uint64_t r = first[t];
-      for_lines(cut[t], cut[t + 1], [&](const char* b, const char* e) {
-        parse_row(b, e, addr.data() + 4 * r, bal.data() + 4 * r);
-        r++;
-      });
-    });
-  } catch (...) {
-    munmap(map, size);
-    throw;
   }
-  munmap(map, size);
+  unsigned T = std::thread::hardware_concurrency();
+  if (T > 16) T = 16;
+  bool forced = false;
+  if (const char* e = getenv("ZKPOA_MERKLE_THREADS")) {
+    char* rest = nullptr;
+    const long v = strtol(e, &rest, 10);
+    if (rest == e || *rest || v < 1 || v > 256)
+      throw std::runtime_error(std::string("ZKPOA_MERKLE_THREADS must be 1..256, not '") + e + "'");
+    T = (unsigned)v;
+    forced = true;
+  }
+  if (T < 1) T = 1;
+  if ((size_t)(end - body) < (1u << 16) && !forced) T = 1;
+  std::vector<const char*> cut(T + 1, end);
+  cut[0] = body;
+  for (unsigned t = 1; t < T; t++) {   // piece boundaries moved forward to the next line start
+    const char* p = body + (size_t)(end - body) / T * t;
+    if (p < cut[t - 1]) p = cut[t - 1];
+    const char* nl = p < end ? static_cast<const char*>(memchr(p, '\n', (size_t)(end - p))) : nullptr;
+    cut[t] = nl ? nl + 1 : end;
+  }
+  std::vector<uint64_t> rows(T, 0);
+  run_threads(T, [&](unsigned t) { for_lines(cut[t], cut[t + 1], [&](const char*, const char*) { rows[t]++; }); });
+  std::vector<uint64_t> first(T + 1, 0);
+  for (unsigned t = 0; t < T; t++) first[t + 1] = first[t] + rows[t];
+  addr.alloc(first[T]);
+  bal.alloc(first[T]);
+  run_threads(T, [&](unsigned t) {
+    uint64_t r = first[t];
+    for_lines(cut[t], cut[t + 1], [&](const char* b, const char* e) {
+      parse_row(b, e, addr.data() + 4 * r, bal.data() + 4 * r);
+      r++;
+    });
+  });
+}
+
+// ---- the owned addresses: accountAttestations[].accountData.{address, balance}.__bigint__ (decimal), merkle_tree.rs:
+// 296-327. The file is 1.6 GB at 2^20 entries: it is pulled through its mapping, and whatever else it holds is skipped.
+struct Owned {
+  std::vector<uint64_t> addr, bal;       // 4 limbs per entry
+  std::vector<std::string> addr_s, bal_s;   // as given: the proofs file repeats them
+};
+static void read_owned(const std::string& path, Owned& o) {
+  const MappedFile text(path.c_str());
+  Json js{text.begin(), text.end()};
+  bool seen = false;
+  js.object([&](const Span& key) {
+    if (!key.is("accountAttestations")) return js.skip();
+    seen = true;
+    js.array([&](uint64_t i) {
+      Span field[2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // address, balance
+      js.object([&](const Span& k1) {
+        if (!k1.is("accountData")) return js.skip();
+        js.object([&](const Span& k2) {
+          const int f = k2.is("address") ? 0 : k2.is("balance") ? 1 : -1;
+          if (f < 0) return js.skip();
+          js.object([&](const Span& k3) {
+            if (!k3.is("__bigint__")) return js.skip();
+            field[f] = js.scalar();
+          });
+        });
+      });
+      if (!field[0].b || !field[1].b)
+        throw std::runtime_error("entry " + std::to_string(i) + " has no accountData.{address, balance}.__bigint__");
+      const U256 av = parse_num(field[0].b, field[0].e, false, "address"), bv = parse_num(field[1].b, field[1].e, false, "balance");
+      o.addr.insert(o.addr.end(), av.v, av.v + 4);
+      o.bal.insert(o.bal.end(), bv.v, bv.v + 4);
+      o.addr_s.push_back(field[0].str());
+      o.bal_s.push_back(field[1].str());
+    });
+  });
+  js.end();
+  if (!seen) throw std::runtime_error("no accountAttestations in " + path);
 }
 
 #define ZK_CALL(expr, what)                                                                       \
@@ -270,37 +203,21 @@ int main(int argc, char** argv) {
                     "--poa-input-data <FILE_PATH> --output-dir <DIR_PATH>\n");
     return 2;
   }
-  zkpoa_context* ctx = nullptr;
   zkpoa_merkle* tree = nullptr;
   int rc = 0;
   try {
     printf("Initiating Merkle Tree build..\n");
     printf("Trying to read given file '\"%s\"'\n", anon.c_str());
     // csv: heading line "address,eth_balance", then 0x-prefixed hex address, decimal balance (merkle_tree.rs:212-246)
-    // the device context (HIP start-up, ~0.4 s) is created on a second thread while this one reads the set
-    char err[512] = {0};
-    long dev = 0;
-    if (const char* e = getenv("ZKPOA_DEVICE")) {
-      char* rest = nullptr;
-      dev = strtol(e, &rest, 10);
-      if (rest == e || *rest || dev < 0 || dev > 1023) throw std::runtime_error(std::string("ZKPOA_DEVICE: not a device index: ") + e);
-    }
-    int ctx_rc = PROVER_OK;
-    std::thread ctx_thread([&] { ctx_rc = zkpoa_context_create((int)dev, &ctx, err, sizeof(err)); });
+    ContextStart start(device_from_env());   // the device starts up while this thread reads the set
     Limbs addr, bal;
     const double t0 = now_s();
-    try {
-      read_anonymity_set(anon, addr, bal);
-    } catch (...) {
-      ctx_thread.join();
-      throw;
-    }
+    read_anonymity_set(anon, addr, bal);
     const double t_read = now_s();
-    ctx_thread.join();
     const uint64_t n = addr.rows;
     if (n == 0) throw std::runtime_error("the anonymity set is empty");
     printf("Converting lines in '\"%s\"' into leaf nodes.. (leaf node = hash(address, balance))\n", anon.c_str());
-    if (ctx_rc != PROVER_OK) throw std::runtime_error(err);
+    zkpoa_context* ctx = start.get();
     const double t_ctx = now_s();
     ZK_CALL(zkpoa_merkle_build(ctx, addr.data(), bal.data(), n, &tree), "merkle tree build");
     if (verbose)
@@ -312,30 +229,18 @@ int main(int argc, char** argv) {
     printf("Number of leaves (after adding padding nodes): %llu\n", 1ull << info[1]);
     printf("Creating Merkle tree..\n");
     printf("Done creating Merkle tree of height %llu\n", (unsigned long long)info[1] + 1);   // rs_merkle depth()
+    const double t_paths = now_s();
+    Owned own;   // read before anything is written: a file that cannot be read leaves no output behind
+    read_owned(poa, own);
     U256 root;
     ZK_CALL(zkpoa_merkle_root(ctx, tree, reinterpret_cast<uint8_t*>(root.v)), "merkle root");
     const std::string root_path = outdir + "/merkle_root.json", proofs_path = outdir + "/merkle_proofs.json";
-    write_file(root_path, "{\n  \"__bigint__\": \"" + root.dec() + "\"\n}");
+    write_text_atomic(root_path, "{\n  \"__bigint__\": \"" + root.dec() + "\"\n}");
     printf("Root hash %s written to file \"%s\"\n", root.dec().c_str(), root_path.c_str());
 
-    const double t_paths = now_s();
-    // owned addresses: accountAttestations[].accountData.{address, balance}.__bigint__ (decimal), merkle_tree.rs:296-327
-    JVal doc = zkpoa::json::parse_json(read_file(poa).c_str());
-    const JVal& atts = doc.at("accountAttestations");
-    if (atts.kind != JVal::ARR) throw std::runtime_error("accountAttestations is not an array");
-    std::vector<uint64_t> oaddr, obal;
-    std::vector<std::string> oaddr_s, obal_s;
-    for (const JVal& a : atts.items) {
-      const JVal& d = a.at("accountData");
-      oaddr_s.push_back(d.at("address").at("__bigint__").scalar());
-      obal_s.push_back(d.at("balance").at("__bigint__").scalar());
-      U256 av = parse_num(oaddr_s.back(), 10, "address"), bv = parse_num(obal_s.back(), 10, "balance");
-      oaddr.insert(oaddr.end(), av.v, av.v + 4);
-      obal.insert(obal.end(), bv.v, bv.v + 4);
-    }
-    const uint64_t m = oaddr_s.size();
+    const uint64_t m = own.addr_s.size();
     std::vector<uint64_t> ohash(4 * (m ? m : 1));
-    if (m) ZK_CALL(zkpoa_poseidon2(ctx, oaddr.data(), obal.data(), m, ohash.data()), "owned leaf hashes");
+    if (m) ZK_CALL(zkpoa_poseidon2(ctx, own.addr.data(), own.bal.data(), m, ohash.data()), "owned leaf hashes");
     // forward scan of the anonymity set for each owned leaf, in order (merkle_tree.rs:329-346: the owned addresses
     // must appear in the set in the same order, or the Rust binary panics)
     std::vector<uint64_t> leaves(4 * n);
@@ -345,7 +250,7 @@ int main(int argc, char** argv) {
     for (uint64_t i = 0; i < m; i++) {
       while (pos < n && memcmp(&leaves[4 * pos], &ohash[4 * i], 32) != 0) pos++;
       if (pos >= n)
-        throw std::runtime_error("Owned leaf " + oaddr_s[i] + " at index " + std::to_string(i) +
+        throw std::runtime_error("Owned leaf " + own.addr_s[i] + " at index " + std::to_string(i) +
                                  " does not exist in the anonymity set");
       index[i] = pos;
     }
@@ -354,8 +259,8 @@ int main(int argc, char** argv) {
     for (uint64_t i = 0; i < m; i++) {
       U256 h;
       memcpy(h.v, &ohash[4 * i], 32);
-      js += std::string(i ? "," : "") + "\n    {\n      \"address\": {\n        \"__bigint__\": \"" + oaddr_s[i] +
-            "\"\n      },\n      \"balance\": {\n        \"__bigint__\": \"" + obal_s[i] +
+      js += std::string(i ? "," : "") + "\n    {\n      \"address\": {\n        \"__bigint__\": \"" + own.addr_s[i] +
+            "\"\n      },\n      \"balance\": {\n        \"__bigint__\": \"" + own.bal_s[i] +
             "\"\n      },\n      \"hash\": {\n        \"__bigint__\": \"" + h.dec() + "\"\n      }\n    }";
     }
     js += m ? "\n  ],\n  \"path_elements\": [" : "],\n  \"path_elements\": [";
@@ -378,7 +283,7 @@ int main(int argc, char** argv) {
       js += k ? "\n    ]" : "]";
     }
     js += m ? "\n  ]\n}" : "]\n}";
-    write_file(proofs_path, js);
+    write_text_atomic(proofs_path, js);
     if (verbose) fprintf(stderr, "merkle-tree: %llu paths and both files %.3f s\n", (unsigned long long)m, now_s() - t_paths);
   } catch (const std::exception& e) {
     fprintf(stderr, "Error: %s\n", e.what());

@@ -1,6 +1,9 @@
-// A minimal JSON reader (objects, arrays, strings, bare numbers) shared by the host-only tools: the verifier /
-// sanitizer (vkey, proof, public files) and the Merkle-tree CLI (the parsed-signatures file). Nesting is capped.
+// A minimal JSON reader (objects, arrays, strings, bare numbers) that builds a tree: for the three small files of the
+// verifier / sanitizer (vkey, proof, public), which are looked up by key and index. Anything large is read with the pull
+// parser of host_text.hpp instead; the nesting cap, kJsonMaxDepth, is that header's, one for both readers.
 #pragma once
+#include "host_text.hpp"
+
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -28,8 +31,6 @@ struct JVal {
     return text;
   }
 };
-
-constexpr int kJsonMaxDepth = 32;   // proof / vkey / public files nest 5 deep; deeper input is rejected, not recursed into
 
 struct JParser {
   const char* p;

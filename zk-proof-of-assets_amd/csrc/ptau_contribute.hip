@@ -368,6 +368,7 @@ void ptau_challenge_contribute(zkpoa_context* ctx, const char* in_path, const ch
   PhaseTimer phase("powersoftau challenge contribute", 40);
   if (same_file(in_path, out_path)) throw SetupError("powersoftau challenge contribute: the output path names the input file");
   MappedFile fi(in_path);
+  nonempty(fi);
   uint32_t power = 1;
   while (power <= 28 && challenge_file_bytes(power) != fi.size) power++;
   if (power > 28) throw SetupError("powersoftau challenge contribute: a file of " + std::to_string(fi.size) + " bytes is no challenge of a power in [1, 28]");
@@ -444,6 +445,7 @@ void ptau_import_response(zkpoa_context* ctx, const char* old_path, const char* 
   if (!p1::trail_end(in.records, power, &trail))
     throw SetupError("powersoftau import response: a point of the old file's last record is not a point of its group");
   MappedFile fr(resp_path);
+  nonempty(fr);
   if (fr.size != response_file_bytes(power))
     throw SetupError("powersoftau import response: a response to a challenge of power " + std::to_string(power) + " has " +
                      std::to_string(response_file_bytes(power)) + " bytes, this file has " + std::to_string(fr.size));

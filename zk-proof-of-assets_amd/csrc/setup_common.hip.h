@@ -1,39 +1,27 @@
 // What the file commands of csrc/setup.hip (`zkey new`, `zkey contribute`, `wtns check`), csrc/zkey_verify.hip (`zkey
 // verify`), csrc/ptau_verify.hip (`powersoftau verify`), csrc/ptau_prepare.hip (`powersoftau prepare phase2`) and
-// csrc/ptau_contribute.hip (the other `powersoftau` commands) share: mapped files and their section tables (the scan
+// csrc/ptau_contribute.hip (the other `powersoftau` commands) share: the section tables of mapped files (the scan
 // and the point sections of a ceremony file: binfile.hpp), the ptau header and the shape of its power sections (the
 // file itself: ptau_file.hip.h), the scalars a command draws or takes from the environment (scalar_in_range,
-// random_scalar, env_scalars over parse_u256.hpp), output files that appear only when complete (AtomicFile) and whose
-// sections are placed in any order (SectionFile), the ZKPOA_VERBOSE phase timer, host threads and arrays, the r1cs
+// random_scalar, env_scalars), output files whose sections are placed in any order (SectionFile), host arrays, the r1cs
 // parser and its CSR, the ptau ranges a key is made from, the constraint-fold kernels, the piece loop that streams a
 // section from its file through HBM (for_each_piece, piece_from_free_hbm), and the device passes that check the points
 // of a section (curve, range, G2 subgroup: PointChecker). Internal linkage: each translation unit has its own copy.
+// What is neither device nor setup -- mapped files, AtomicFile, the phase timer, host threads, numbers as text -- is
+// host_files.hpp and host_text.hpp.
 #pragma once
 #include "binfile.hpp"
 #include "bn254_ec.hip.h"
 #include "device_ctx.hpp"
+#include "host_files.hpp"
+#include "host_text.hpp"
 #include "msm.hip.h"
 #include "pairing.hpp"
-#include "parse_u256.hpp"
 #include "zkpoa_internal.hpp"
 
-#include <fcntl.h>
-#include <string.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
-#include <time.h>
-
 #include <algorithm>
-#include <atomic>
-#include <exception>
 #include <map>
 #include <memory>
-#include <stdexcept>
-#include <string>
-#include <thread>
-#include <vector>
 
 using namespace zkpoa;
 
@@ -63,54 +51,17 @@ struct SetupError : std::runtime_error {
   explicit SetupError(const std::string& m) : std::runtime_error(m) {}
 };
 
-// ZKPOA_VERBOSE: where a command spends its time. One line per phase: "zkpoa: <command>: <what>  <ms since the last>"
-struct PhaseTimer {
-  const char* command;
-  int width;   // of the <what> column (each command keeps its own: logs of different dates compare)
-  const bool verbose = getenv("ZKPOA_VERBOSE") != nullptr;
-  struct timespec t0;
-  PhaseTimer(const char* cmd, int w) : command(cmd), width(w) { clock_gettime(CLOCK_MONOTONIC, &t0); }
-  void operator()(const char* what) {
-    if (!verbose) return;
-    struct timespec t;
-    clock_gettime(CLOCK_MONOTONIC, &t);
-    fprintf(stderr, "zkpoa: %s: %-*s %8.1f ms\n", command, width, what, (t.tv_sec - t0.tv_sec) * 1e3 + (t.tv_nsec - t0.tv_nsec) / 1e6);
-    t0 = t;
-  }
-};
-
-struct MappedFile {
-  const uint8_t* p = nullptr;
-  uint64_t size = 0;
-  int fd = -1;
-  explicit MappedFile(const char* path) {
-    fd = open(path, O_RDONLY);
-    if (fd < 0) throw SetupError(std::string("cannot open ") + path);
-    struct stat sb;
-    if (fstat(fd, &sb) != 0 || sb.st_size <= 0) {
-      close(fd);
-      throw SetupError(std::string("cannot stat ") + path);
-    }
-    size = (uint64_t)sb.st_size;
-    void* m = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
-    if (m == MAP_FAILED) {
-      close(fd);
-      throw SetupError(std::string("cannot map ") + path);
-    }
-    p = static_cast<const uint8_t*>(m);
-  }
-  ~MappedFile() {
-    if (p) munmap(const_cast<uint8_t*>(p), size);
-    if (fd >= 0) close(fd);
-  }
-  MappedFile(const MappedFile&) = delete;
-  MappedFile& operator=(const MappedFile&) = delete;
-};
+// Every input of these commands begins with a header: an empty file is refused in the words the commands always had for
+// it. bin_sections does this for the files that have a section table; a command that maps another kind calls it itself.
+void nonempty(const MappedFile& f) {
+  if (!f.size) throw SetupError("cannot stat " + f.path);
+}
 
 // the section table of an iden3 binary file (binfile.hpp), with the setup commands' error texts
 std::map<uint32_t, Sec> bin_sections(const MappedFile& f, const char* magic, uint32_t max_version, const char* what) {
   static const char* const why[] = {"", "bad magic", "unsupported version", "truncated section table",
                                     "section runs past the end of the file"};
+  nonempty(f);
   std::map<uint32_t, Sec> out;
   const BinScan r = bin_scan(f.p, f.size, magic, max_version, out);
   if (r != kBinOk) throw SetupError(std::string(what) + ": " + why[r]);
@@ -173,7 +124,10 @@ bool env_scalars(const char* name, uint8_t out[][32], int count, const char* sha
     const char* end = strchr(e, ',');
     if ((k < count - 1) != (end != nullptr)) end = nullptr;   // too few numbers, or too many
     else if (!end) end = e + strlen(e);
-    if (!end || !parse_u256(e, end, out[k]) || !scalar_in_range(out[k], true)) throw SetupError(std::string(name) + " is not " + shape);
+    U256 x;
+    const bool parsed = end && x.parse_number(e, end);
+    x.to_le(out[k]);
+    if (!parsed || !scalar_in_range(out[k], true)) throw SetupError(std::string(name) + " is not " + shape);
     e = end + 1;
   }
   fprintf(stderr, "zkpoa: WARNING: %s taken from %s -- for tests only\n", secrets, name);
@@ -380,42 +334,7 @@ static __global__ __launch_bounds__(256) void fr_to_mont_kernel(void* __restrict
   store_field(p, v.to_mont());
 }
 
-// ---- host-side parallelism (r04) ---------------------------------------------------------------------------------------
-// At the layer-three shape `zkey new` reads 62 GB and writes 35 GB, and the device's share of the command is 3.5 s: what
-// was left was one host thread parsing, copying and converting (54 s in all). Every host stage below is split over
-// the host's threads; the arrays they fill are not zero-filled first (UVec), the threads are the first to touch them.
-unsigned host_threads() {
-  unsigned t = std::thread::hardware_concurrency();
-  if (const char* e = getenv("ZKPOA_SETUP_THREADS")) {
-    char* end = nullptr;
-    const long v = strtol(e, &end, 10);
-    if (end != e && !*end && v >= 1 && v <= 256) t = (unsigned)v;
-  }
-  return t < 1 ? 1 : (t > 32 ? 32 : t);
-}
-// fn(t, lo, hi) over [0, count) cut into host_threads() ranges; the first exception (in range order) is rethrown
-template <class Fn>
-void parallel_ranges(uint64_t count, uint64_t min_per_thread, Fn fn) {
-  unsigned T = host_threads();
-  if (count / (min_per_thread ? min_per_thread : 1) < T) T = (unsigned)(count / (min_per_thread ? min_per_thread : 1));
-  if (T <= 1) {
-    fn(0u, (uint64_t)0, count);
-    return;
-  }
-  std::vector<std::exception_ptr> errs(T);
-  std::vector<std::thread> th;
-  for (unsigned t = 0; t < T; t++)
-    th.emplace_back([&, t] {
-      try {
-        fn(t, count * t / T, count * (t + 1) / T);
-      } catch (...) {
-        errs[t] = std::current_exception();
-      }
-    });
-  for (auto& x : th) x.join();
-  for (auto& e : errs)
-    if (e) std::rethrow_exception(e);
-}
+// the threads that fill a host array are the first to touch it (host_files.hpp: parallel_ranges)
 template <class T>
 struct UVec {   // a sized array of trivially copyable elements whose storage is NOT value-initialised
   std::unique_ptr<T[]> p;
@@ -441,62 +360,6 @@ struct UVec {   // a sized array of trivially copyable elements whose storage is
   const T* end() const { return p.get() + n; }
 };
 
-// Output files are written under a temporary name and renamed into place (as prover_main's write_atomic): a failure
-// part-way (ENOSPC, HIP error, kill) never leaves a truncated .zkey under the final name for a later "skip if the zkey
-// exists" step to pick up, and writing over the input of `zkey contribute` is safe (the mapping keeps the old inode).
-struct AtomicFile {
-  std::string path, tmp;
-  int fd = -1;
-  std::atomic<bool> ok{true};
-  explicit AtomicFile(const char* final_path) : path(final_path), tmp(path + ".tmp." + std::to_string((long)getpid())) {
-    fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
-    if (fd < 0) throw SetupError("cannot create " + tmp);
-  }
-  // Absolute placement, for a file whose section offsets are known before their content: reserve() sizes it, put_at()
-  // may then be called from several threads for disjoint ranges in any order.
-  void reserve(uint64_t total) {
-    if (ftruncate(fd, (off_t)total) != 0) ok = false;
-  }
-  // a payload of GBs is copied by several threads through a shared mapping of its final place (buffered write() calls to
-  // one file queue up behind its inode lock -- measured on tmpfs: eight pwrite threads were no faster than one fwrite);
-  // false without a shared mapping of this file: the caller writes the plain way
-  bool mapped_copy(uint64_t off, const void* p, uint64_t len) {
-    const uint64_t map_off = off & ~4095ull, lead = off - map_off;
-    void* m = mmap(nullptr, lead + len, PROT_READ | PROT_WRITE, MAP_SHARED, fd, (off_t)map_off);
-    if (m == MAP_FAILED) return false;
-    char* dst = static_cast<char*>(m) + lead;
-    parallel_ranges(len, 32ull << 20, [&](unsigned, uint64_t lo, uint64_t hi) { memcpy(dst + lo, static_cast<const char*>(p) + lo, hi - lo); });
-    if (munmap(m, lead + len) != 0) ok = false;
-    return true;
-  }
-  void put_at(uint64_t off, const void* p, uint64_t len) {
-    if (len >= (64u << 20) && mapped_copy(off, p, len)) return;
-    for (uint64_t done = 0; done < len;) {
-      const ssize_t w = pwrite(fd, static_cast<const char*>(p) + done, len - done, (off_t)(off + done));
-      if (w <= 0) {
-        ok = false;
-        return;
-      }
-      done += (uint64_t)w;
-    }
-  }
-  void commit() {
-    const bool good = (close(fd) == 0) && ok.load();
-    fd = -1;
-    if (!good || rename(tmp.c_str(), path.c_str()) != 0) {
-      unlink(tmp.c_str());
-      throw SetupError("write to " + path + " failed");
-    }
-  }
-  ~AtomicFile() {
-    if (fd >= 0) {
-      close(fd);
-      unlink(tmp.c_str());
-    }
-  }
-  AtomicFile(const AtomicFile&) = delete;
-  AtomicFile& operator=(const AtomicFile&) = delete;
-};
 // An iden3 binary file whose section lengths are known before their content: the file is sized, the magic, version 1,
 // the section count and the table (sections in the order of ids) are written, and a payload is then placed from any
 // thread, in any order.

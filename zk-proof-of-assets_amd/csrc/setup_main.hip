@@ -25,7 +25,7 @@
 // is not exercised.
 #include "../../include/zkpoa_prover.h"
 
-#include "parse_u256.hpp"
+#include "host_text.hpp"
 #include "worker_exit.hpp"
 
 #include <stdio.h>
@@ -170,11 +170,13 @@ int main(int argc, char** argv) {
   uint8_t delta[32];
   const uint8_t* delta_p = nullptr;
   if (const char* e = cmd == kZkeyContribute ? getenv("ZKPOA_DELTA") : nullptr) {   // tests / reproducible keys only: the secret must not be kept
-    if (!zkpoa::parse_u256(e, e + strlen(e), delta)) {
+    zkpoa::U256 d;
+    if (!d.parse_number(e, e + strlen(e))) {
       fprintf(stderr, "zkpoa-setup: ZKPOA_DELTA is not a number below 2^256\n");
       return 2;
     }
     fprintf(stderr, "zkpoa-setup: WARNING: delta taken from ZKPOA_DELTA -- whoever knows it can forge proofs for this key\n");
+    d.to_le(delta);
     delta_p = delta;
   }
   // `zkey new` / `zkey contribute` run in a worker process and this one leaves as soon as the key is renamed into place

@@ -10,227 +10,30 @@
 // a gigabyte out, and neither is ever held as a tree. The output is formatted by the host threads 2^16 entries at a
 // time. Exit status 0, or 1 with one line on stderr and no output file.
 #include "../../include/zkpoa_prover.h"
-#include "setup_common.hip.h"
+#include "host_files.hpp"
+#include "host_text.hpp"
 
-#include <stdio.h>
-#include <stdlib.h>
+#include <algorithm>
+
+using namespace zkpoa;
 
 namespace {
-
-typedef unsigned __int128 u128;
 
 struct InputError : std::runtime_error {
   explicit InputError(const std::string& m) : std::runtime_error(m) {}
 };
 
-// ---- a read-only mapping of a whole file ---------------------------------------------------------------------------
-struct MappedText {
-  const char* base = nullptr;
-  size_t size = 0;
-  explicit MappedText(const std::string& path) {
-    const int fd = open(path.c_str(), O_RDONLY);
-    struct stat sb;
-    if (fd < 0 || fstat(fd, &sb) != 0) {
-      if (fd >= 0) close(fd);
-      throw InputError("cannot open " + path);
-    }
-    size = (size_t)sb.st_size;
-    if (size) {
-      void* m = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
-      if (m == MAP_FAILED) {
-        close(fd);
-        throw InputError("cannot map " + path);
-      }
-      base = static_cast<const char*>(m);
-    }
-    close(fd);
-  }
-  ~MappedText() {
-    if (base) munmap(const_cast<char*>(base), size);
-  }
-  MappedText(const MappedText&) = delete;
-  MappedText& operator=(const MappedText&) = delete;
-};
-
-// ---- JSON, pulled: the caller says what it expects next; whatever it does not know it skips -------------------------
-struct Span {
-  const char *b, *e;
-  size_t size() const { return (size_t)(e - b); }
-  bool is(const char* s) const { return size() == strlen(s) && memcmp(b, s, size()) == 0; }
-  std::string str() const { return std::string(b, e); }
-};
-
-struct Json {
-  const char *p, *e;
-  [[noreturn]] void fail(const char* what) const { throw InputError(std::string("malformed JSON: ") + what); }
-  void ws() {
-    while (p < e && (*p == ' ' || *p == '\n' || *p == '\t' || *p == '\r')) p++;
-  }
-  bool take(char c) {
-    ws();
-    if (p < e && *p == c) {
-      p++;
-      return true;
-    }
-    return false;
-  }
-  void expect(char c, const char* what) {
-    if (!take(c)) fail(what);
-  }
-  // a string without escapes (no key or value of these files has any): the characters between the quotes
-  Span string() {
-    expect('"', "a string was expected");
-    const char* b = p;
-    while (p < e && *p != '"') {
-      if (*p == '\\') fail("an escape in a key or a number string");
-      p++;
-    }
-    if (p >= e) fail("unterminated string");
-    return Span{b, p++};
-  }
-  Span number() {
-    ws();
-    const char* b = p;
-    while (p < e && (*p == '-' || *p == '+' || *p == '.' || (*p >= '0' && *p <= '9') || (*p | 32) == 'e')) p++;
-    if (b == p) fail("a number was expected");
-    return Span{b, p};
-  }
-  void skip() {   // any value
-    ws();
-    if (p >= e) fail("a value was expected");
-    if (*p == '"') {
-      p++;
-      while (p < e && *p != '"') p += (*p == '\\') ? 2 : 1;
-      if (p >= e) fail("unterminated string");
-      p++;
-    } else if (*p == '{') {
-      object([&](const Span&) { skip(); });
-    } else if (*p == '[') {
-      array([&](uint64_t) { skip(); });
-    } else {
-      const char* b = p;
-      while (p < e && *p != ',' && *p != '}' && *p != ']' && *p != ' ' && *p != '\n' && *p != '\t' && *p != '\r') p++;
-      if (b == p) fail("a value was expected");
-    }
-  }
-  template <class Fn>
-  void object(Fn member) {   // member(key) consumes the value
-    expect('{', "an object was expected");
-    if (take('}')) return;
-    do {
-      const Span key = string();
-      expect(':', "':' was expected");
-      member(key);
-    } while (take(','));
-    expect('}', "'}' was expected");
-  }
-  template <class Fn>
-  uint64_t array(Fn element) {   // element(index) consumes the value; returns the length
-    expect('[', "an array was expected");
-    uint64_t i = 0;
-    if (take(']')) return 0;
-    do element(i++);
-    while (take(','));
-    expect(']', "']' was expected");
-    return i;
-  }
-  void end() {
-    ws();
-    if (p != e) fail("text after the value");
-  }
-};
-
-// ---- 256-bit integers: big-endian bytes <-> decimal -------------------------------------------------------------------
-struct U256 {
-  uint64_t v[4] = {0, 0, 0, 0};   // least significant first
-  static U256 from_be(const uint8_t* b) {
-    U256 x;
-    for (int i = 0; i < 32; i++) x.v[3 - i / 8] |= (uint64_t)b[i] << (8 * (7 - i % 8));
-    return x;
-  }
-  bool mul_add(uint64_t mul, uint64_t add) {   // *this = *this * mul + add; false on overflow
-    u128 carry = add;
-    for (int i = 0; i < 4; i++) {
-      const u128 cur = (u128)v[i] * mul + carry;
-      v[i] = (uint64_t)cur;
-      carry = cur >> 64;
-    }
-    return carry == 0;
-  }
-  void append_dec(std::string& out) const {   // 19 digits per pass
-    uint64_t t[4] = {v[0], v[1], v[2], v[3]};
-    uint64_t part[5];
-    int parts = 0;
-    while (t[0] | t[1] | t[2] | t[3]) {
-      u128 rem = 0;
-      for (int k = 3; k >= 0; k--) {
-        const u128 cur = (rem << 64) | t[k];
-        t[k] = (uint64_t)(cur / 10000000000000000000ull);
-        rem = cur % 10000000000000000000ull;
-      }
-      part[parts++] = (uint64_t)rem;
-    }
-    if (!parts) {
-      out.push_back('0');
-      return;
-    }
-    char buf[24];
-    out.append(buf, (size_t)snprintf(buf, sizeof(buf), "%llu", (unsigned long long)part[parts - 1]));
-    for (int k = parts - 2; k >= 0; k--) out.append(buf, (size_t)snprintf(buf, sizeof(buf), "%019llu", (unsigned long long)part[k]));
-  }
-};
-
 U256 parse_number(const Span& s, const char* what) {   // decimal or 0x hex, below 2^256
-  // the decimal strings these files are full of: up to 19 digits per step
-  bool plain = s.size() > 0 && s.size() <= 78;
-  for (const char* q = s.b; plain && q < s.e; q++) plain = *q >= '0' && *q <= '9';
-  if (plain) {
-    U256 x;
-    bool fits = true;
-    for (const char* q = s.b; q < s.e;) {
-      uint64_t chunk = 0, scale = 1;
-      for (int k = 0; k < 19 && q < s.e; k++, q++) {
-        chunk = chunk * 10 + (uint64_t)(*q - '0');
-        scale *= 10;
-      }
-      fits = x.mul_add(scale, chunk) && fits;
-    }
-    if (!fits) throw InputError(std::string(what) + " is not a number below 2^256: " + s.str());
-    return x;
-  }
-  uint8_t le[32];
-  if (!zkpoa::parse_u256(s.b, s.e, le)) throw InputError(std::string(what) + " is not a number below 2^256: " + s.str());
   U256 x;
-  memcpy(x.v, le, 32);
+  if (!x.parse_number(s.b, s.e)) throw InputError(std::string(what) + " is not a number below 2^256: " + s.str());
   return x;
-}
-
-int hex_digit(char c) {
-  if (c >= '0' && c <= '9') return c - '0';
-  if ((c | 32) >= 'a' && (c | 32) <= 'f') return (c | 32) - 'a' + 10;
-  return -1;
-}
-// "0x" + exactly 2 * bytes hex digits -> bytes
-bool parse_hex_bytes(const Span& s, uint8_t* out, size_t bytes) {
-  if (s.size() != 2 + 2 * bytes || s.b[0] != '0' || s.b[1] != 'x') return false;
-  for (size_t i = 0; i < bytes; i++) {
-    const int hi = hex_digit(s.b[2 + 2 * i]), lo = hex_digit(s.b[3 + 2 * i]);
-    if (hi < 0 || lo < 0) return false;
-    out[i] = (uint8_t)(16 * hi + lo);
-  }
-  return true;
 }
 
 // "0x" + 1..64 hex digits -> 32 bytes, big-endian, padded on the left
 bool parse_hex_u256(const Span& s, uint8_t* out) {
-  if (s.size() < 3 || s.size() > 66 || s.b[0] != '0' || s.b[1] != 'x') return false;
-  memset(out, 0, 32);
-  int pos = 63;   // nibble index from the left of the 64
-  for (const char* q = s.e - 1; q >= s.b + 2; q--, pos--) {
-    const int d = hex_digit(*q);
-    if (d < 0) return false;
-    out[pos / 2] |= (uint8_t)((pos & 1) ? d : d << 4);
-  }
+  U256 x;
+  if (s.size() < 3 || s.size() > 66 || s.b[0] != '0' || s.b[1] != 'x' || !x.parse_hex(s.b + 2, s.e)) return false;
+  x.to_be(out);
   return true;
 }
 
@@ -252,8 +55,8 @@ struct Signatures {
 };
 
 void read_signatures(const std::string& path, Signatures& g) {
-  MappedText text(path);
-  Json js{text.base, text.base + text.size};
+  MappedFile text(path.c_str());
+  Json js{text.begin(), text.end()};
   js.array([&](uint64_t i) {
     bool have_sig = false, have_addr = false, have_bal = false;
     g.r.resize(32 * (i + 1));
@@ -336,31 +139,15 @@ void put_big(std::string& o, const char* indent, const char* key, const U256& x,
   o += last ? "}\n" : "},\n";
 }
 
-int parse_mode(const std::string& in_path, const std::string& out_path, bool verbose) {
-  zkpoa_context* ctx = nullptr;
-  char err[512] = {0};
-  long dev = 0;
-  if (const char* e = getenv("ZKPOA_DEVICE")) {
-    char* rest = nullptr;
-    dev = strtol(e, &rest, 10);
-    if (rest == e || *rest || dev < 0 || dev > 1023) throw InputError(std::string("ZKPOA_DEVICE: not a device index: ") + e);
-  }
-  // the device context (HIP start-up) is created on a second thread while this one reads the file
-  int ctx_rc = PROVER_OK;
-  std::thread ctx_thread([&] { ctx_rc = zkpoa_context_create((int)dev, &ctx, err, sizeof(err)); });
+int parse_mode(const std::string& in_path, const std::string& out_path) {
+  ContextStart start(device_from_env());   // the device starts up while this thread reads the file
   Signatures g;
   PhaseTimer lap("ecdsa-sigs-parser", 8);
-  try {
-    read_signatures(in_path, g);
-  } catch (...) {
-    ctx_thread.join();
-    throw;
-  }
+  read_signatures(in_path, g);
   lap("read");
-  ctx_thread.join();   // what is left of the start-up counts as device time
   const uint64_t n = g.n;
   printf("Parsing %llu ECDSA signatures..\n", (unsigned long long)n);
-  if (ctx_rc != PROVER_OK) throw InputError(err);
+  zkpoa_context* ctx = start.get();   // what is left of the start-up counts as device time
   std::vector<uint8_t> rprime(32 * n + 1), pub(64 * n + 1), derived(20 * n + 1), status(n + 1);
   std::vector<char> text(42 * n + 1);
   if (zkpoa_ecdsa_star(ctx, n, g.r.data(), g.s.data(), g.z.data(), g.v.data(), g.addr.data(), rprime.data(), pub.data(),
@@ -459,8 +246,8 @@ int layer_one_mode(const std::string& in_path, const std::string& out_path, long
   const long long first_kept = start > 0 ? start : 0;
   long long total = 0;
   {
-    MappedText text(in_path);
-    Json js{text.base, text.base + text.size};
+    MappedFile text(in_path.c_str());
+    Json js{text.begin(), text.end()};
     bool seen = false;
     js.object([&](const Span& key) {
       if (!key.is("accountAttestations")) return js.skip();
@@ -561,7 +348,6 @@ bool parse_index(const char* s, long long& out) {
 }  // namespace
 
 int main(int argc, char** argv) {
-  const bool verbose = getenv("ZKPOA_VERBOSE") != nullptr;
   int rc = 0;
   try {
     const bool layer_one = argc > 1 && strcmp(argv[1], "layer-one-input") == 0;
@@ -602,7 +388,7 @@ int main(int argc, char** argv) {
                                 : "error: --signatures <FILE> and --output-path <FILE> are required\n");
       return 2;
     }
-    rc = layer_one ? layer_one_mode(in, out, start, end) : parse_mode(in, out, verbose);
+    rc = layer_one ? layer_one_mode(in, out, start, end) : parse_mode(in, out);
   } catch (const std::exception& e) {
     fprintf(stderr, "Error: %s\n", e.what());
     rc = 1;

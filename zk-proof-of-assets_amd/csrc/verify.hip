@@ -8,6 +8,7 @@
 #include "pairing.hpp"
 #include "../../include/zkpoa_prover.h"
 #include "host_curve.hpp"
+#include "host_text.hpp"
 #include "mini_json.hpp"
 
 #include <stdexcept>
@@ -33,33 +34,10 @@ using zkpoa::json::JVal;
 using zkpoa::json::parse_json;
 
 // ---- decimal <-> field ----------------------------------------------------------------------------------
-// decimal string -> 256-bit integer (false if not decimal or >= 2^256)
-bool parse_u256(const std::string& s, uint64_t out[4]) {
-  out[0] = out[1] = out[2] = out[3] = 0;
-  if (s.empty()) return false;
-  for (char ch : s) {
-    if (ch < '0' || ch > '9') return false;
-    u128 carry = (unsigned)(ch - '0');
-    for (int i = 0; i < 4; i++) {
-      u128 cur = (u128)out[i] * 10 + carry;
-      out[i] = (uint64_t)cur;
-      carry = cur >> 64;
-    }
-    if (carry) return false;
-  }
-  return true;
-}
-bool lt_modulus(const uint64_t v[4], const uint64_t p[4]) {
-  for (int i = 3; i >= 0; i--) {
-    if (v[i] < p[i]) return true;
-    if (v[i] > p[i]) return false;
-  }
-  return false;
-}
 HFq fq_from_dec(const std::string& s) {
-  uint64_t v[4];
-  if (!parse_u256(s, v) || !lt_modulus(v, HFqParams::P)) throw std::runtime_error("coordinate is not a field element: " + s);
-  HFq r{{v[0], v[1], v[2], v[3]}};
+  U256 v;
+  if (!v.parse_dec(s.data(), s.data() + s.size()) || !v.below(HFqParams::P)) throw std::runtime_error("coordinate is not a field element: " + s);
+  HFq r{{v.v[0], v.v[1], v.v[2], v.v[3]}};
   return r.to_mont();
 }
 HFq2 fq2_from_json(const JVal& v) { return HFq2{fq_from_dec(v[0].scalar()), fq_from_dec(v[1].scalar())}; }
@@ -145,8 +123,12 @@ bool verify_impl(const JVal& vkj, const JVal& pubj, const JVal& prj) {
   Proof pr = proof_from_json(prj, ZRule::Jacobian);
   if (pubj.kind != JVal::ARR || pubj.items.size() != vk.nPublic) return false;
   std::vector<uint64_t> pub(4 * vk.nPublic + 4);
-  for (size_t i = 0; i < vk.nPublic; i++)
-    if (!parse_u256(pubj[i].scalar(), &pub[4 * i]) || !lt_modulus(&pub[4 * i], HFrParams::P)) return false;
+  for (size_t i = 0; i < vk.nPublic; i++) {
+    const std::string& t = pubj[i].scalar();
+    U256 v;
+    if (!v.parse_dec(t.data(), t.data() + t.size()) || !v.below(HFrParams::P)) return false;
+    memcpy(&pub[4 * i], v.v, 32);
+  }
   return verify_core(vk, pr, pub.data());
 }
 
@@ -183,25 +165,12 @@ std::string sanitize_impl(const JVal& vkj, const JVal& pubj, const JVal& prj) {
   o += ", \"pubInput\": [";
   if (pubj.kind != JVal::ARR) throw std::runtime_error("public.json is not an array");
   for (size_t i = 0; i < pubj.items.size(); i++) {
-    uint64_t s[4];
-    if (!parse_u256(pubj[i].scalar(), s)) throw std::runtime_error("public input is not a decimal integer");
+    const std::string& t = pubj[i].scalar();
+    U256 v;
+    if (!v.parse_dec(t.data(), t.data() + t.size())) throw std::runtime_error("public input is not a decimal integer");
     // int(pubInput): re-emit the canonical decimal (strips leading zeros like Python's int())
-    std::string dec;
-    {  // decimal of a raw 256-bit integer
-      uint64_t v[4] = {s[0], s[1], s[2], s[3]};
-      std::string rev;
-      while (v[0] | v[1] | v[2] | v[3]) {
-        u128 rem = 0;
-        for (int k = 3; k >= 0; k--) {
-          u128 cur = (rem << 64) | v[k];
-          v[k] = (uint64_t)(cur / 10);
-          rem = cur % 10;
-        }
-        rev.push_back((char)('0' + (int)rem));
-      }
-      dec = rev.empty() ? "0" : std::string(rev.rbegin(), rev.rend());
-    }
-    o += dec + (i + 1 < pubj.items.size() ? ", " : "");
+    v.append_dec(o);
+    o += i + 1 < pubj.items.size() ? ", " : "";
   }
   o += "]}";
   return o;
@@ -375,7 +344,7 @@ extern "C" int zkpoa_groth16_verify_points(const uint8_t* vkey_points, unsigned 
     std::vector<uint64_t> pub(4 * (size_t)n_public + 4);
     for (unsigned long i = 0; i < n_public; i++) {
       memcpy(&pub[4 * i], public_le + 32 * i, 32);
-      if (!lt_modulus(&pub[4 * i], HFrParams::P)) return ZKPOA_VERIFY_INVALID_PROOF;
+      if (!U256::from_le(public_le + 32 * i).below(HFrParams::P)) return ZKPOA_VERIFY_INVALID_PROOF;
     }
     return verify_core(vk, pr, pub.data()) ? PROVER_OK : ZKPOA_VERIFY_INVALID_PROOF;
   } catch (const std::exception& e) {
