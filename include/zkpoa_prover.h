@@ -682,7 +682,10 @@ int zkpoa_curve_prim(zkpoa_context* ctx, int group, int op, const void* a, const
  * 5 = mixed addition as the accumulation kernel does it: XYZZ (32 words, wire form, infinity = zz 0), affine base
  * (16 words), negate flag (1 word) -> canonical XYZZ (32 words). 6 = full addition: two XYZZ -> canonical XYZZ.
  * 8 = a piece as msm_accum0_kernel sums it: 8 x (affine base, negate flag) = 136 words -> canonical XYZZ.
- * raw is ignored by ops 4-6 and 8. */
+ * The packed partial sums of the G1 MSM (128 bytes: the four coordinates times 2^261, each below 2^256; infinity =
+ * all zero): 10 = packed + packed -> packed (32 words), then one word that is 1 when the generic sum was poisoned
+ * and the exact addition redid it, then 3 zero words; 11 = a piece as op 8 -> packed, same 36 words out;
+ * 12 = packed -> canonical wire XYZZ. There is no op 9. raw is ignored by ops 4-6 and 8-12. */
 int zkpoa_fq29_prim(zkpoa_context* ctx, int op, const void* in, void* out, uint64_t n, int raw);
 /* The NTT's other forms on a host buffer, in place (parity tests). form: 0 = ntt_dif (natural in, bit-reversed out),
  * 1 = ntt_dit (bit-reversed in, natural out), 2 = ntt_to_odd_coset (inverse ignored). No 1/n in forms 0 and 1.

@@ -8,7 +8,11 @@
 //   op 6 full add  64 words (two wire XYZZ) -> 36 limbs (wire domain, class N)
 //   op 7 norm(a + (C14 - b)) 18 -> 9
 //   op 8 piece     u32 count, then count x (16 base words, u32 negate) -> 32 words (wire XYZZ, each < 3q)
-// (the numbers are zkpoa_fq29_prim's; its op 5, one mixed addition with every exceptional case, needs the device's
+//   op 10 packed add     64 words (two packed sums) -> 32 words (packed; generic addition only, no redo)
+//   op 11 piece closed   as op 8 -> 32 packed words, then 1 word: 1 = a sum, 0 = poisoned (ZZ = 0 mod q)
+//   op 13 X below 2^256  9 limbs (class X, as given) -> 9 limbs, the 8 words made from them, 9 limbs sliced back
+//   op 14 pack, unpack   36 limbs (Xyzz29S as given) -> 32 words, 36 limbs
+// (the numbers are zkpoa_fq29_prim's where it has the op; its op 5, one mixed addition with every exceptional case, needs the device's
 // exact addition and has no host form)
 #include "fq29.hip.h"
 #include <stdio.h>
@@ -88,6 +92,60 @@ int main(int argc, char** argv) {
         Fq29 o[4];
         xyzz29s_to_wire(a, o[0], o[1], o[2], o[3]);
         for (int i = 0; i < 4; i++) wr(o[i].l, 9);
+        break;
+      }
+      case 10: {
+        if (!rd(w, 64)) return 3;
+        Xyzz29S a, b;
+        xyzz29s_unpack(a, w);
+        xyzz29s_unpack(b, w + 32);
+        xyzz29s_add(a, b);
+        uint32_t out[32];
+        xyzz29s_pack(a, out);
+        wr(out, 32);
+        break;
+      }
+      case 11: {
+        uint32_t count;
+        if (!rd(&count, 1)) return 3;
+        G1Piece29 s;
+        s.a = {};
+        s.empty = true;
+        for (uint32_t k = 0; k < count; k++) {
+          if (!rd(w, 17)) return 3;
+          g1piece29_add(s, w, w + 8, w[16] != 0);
+        }
+        uint32_t out[33] = {};
+        out[32] = 1;
+        if (!s.empty) {
+          Xyzz29S c;
+          out[32] = g1piece29_close(s, c) ? 1 : 0;
+          xyzz29s_pack(c, out);
+        }
+        wr(out, 33);
+        break;
+      }
+      case 13: {
+        if (!rd(w, 9)) return 3;
+        r = fq29_below_2p256(limbs(w));
+        uint32_t back[8];
+        fq29_to_words(r, back);
+        wr(r.l, 9);
+        wr(back, 8);
+        wr(fq29_from_words(back).l, 9);
+        break;
+      }
+      case 14: {
+        if (!rd(w, 36)) return 3;
+        Xyzz29S a = {limbs(w), limbs(w + 9), limbs(w + 18), limbs(w + 27)}, b;
+        uint32_t out[32];
+        xyzz29s_pack(a, out);
+        xyzz29s_unpack(b, out);
+        wr(out, 32);
+        wr(b.x.l, 9);
+        wr(b.y.l, 9);
+        wr(b.zz.l, 9);
+        wr(b.zzz.l, 9);
         break;
       }
       default: return 2;

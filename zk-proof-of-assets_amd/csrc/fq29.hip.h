@@ -11,7 +11,8 @@
 // OPERAND CLASSES (a value is sum l[i] 2^(29 i); it is a field element only modulo q, never reduced below q here)
 //   N  product output        limbs 0..7 < 2^29 ("normalised"), value < 3q
 //   X  accumulator X         normalised, value < 13q
-//   W  re-limbed wire word   normalised, value < 2^256 (< 5.3q), limb 8 < 2^24
+//   W  re-limbed 8-word value normalised, value < 2^256 (< 5.3q), limb 8 < 2^24: a wire word, or a word of a PACKED
+//                            partial sum (below) -- any of its four coordinates
 //   D  difference, sum       NOT normalised: every limb < 3 * 2^29, value < 17q
 //   a normalised value V has limb 8 = V >> 232, < 2^26 for V < 17q.
 // RULES
@@ -56,6 +57,10 @@ struct Fq29P {
   static constexpr uint32_t INV = 0x04866389u;   // -q^-1 mod 2^29
   static constexpr uint32_t Q[9] = {0x187cfd47u, 0x010460b6u, 0x1c72a34fu, 0x02d522d0u, 0x1585d978u,
                                     0x02db40c0u, 0x00a6e141u, 0x0e5c2634u, 0x0030644eu};
+};
+struct Fq29Q2 {   // 2q, normalised
+  static constexpr uint32_t v[9] = {0x10f9fa8eu, 0x0208c16du, 0x18e5469eu, 0x05aa45a1u, 0x0b0bb2f0u,
+                                    0x05b68181u, 0x014dc282u, 0x1cb84c68u, 0x0060c89cu};
 };
 struct Fq29C4 {
   static constexpr uint32_t v[9] = {0x21f3f51cu, 0x241182dau, 0x31ca8d3bu, 0x2b548b42u, 0x361765dfu,
@@ -128,6 +133,35 @@ ZK29 void fq29_to_words(const Fq29& a, uint32_t* w) {   // normalised, value < 2
     if (i0 + 2 < 9) t |= (uint64_t)a.l[i0 + 2] << (58 - off);
     w[j] = (uint32_t)t;
   }
+}
+
+// value = 0 (mod q) for a class-N value: 0, q or 2q
+ZK29 bool fq29_is_zero_mod_q(const Fq29& a) {
+  uint32_t d0 = 0, d1 = 0, d2 = 0;
+#pragma unroll
+  for (int i = 0; i < 9; i++) {
+    d0 |= a.l[i];
+    d1 |= a.l[i] ^ Fq29P::Q[i];
+    d2 |= a.l[i] ^ Fq29Q2::v[i];
+  }
+  return d0 == 0 || d1 == 0 || d2 == 0;
+}
+// class X (any normalised value with limb 8 < 2^26) -> the same field element below 2^256, normalised, by a quotient
+// estimate: k = limb 8 / ((q >> 232) + 1) never exceeds value / q, so value - k q >= 0, and limb 8 < (k + 1)(q8 + 1)
+// leaves value - k q < (q8 + k + 1) 2^232 < q + 14 * 2^232. Nine multiply-adds and one division by a constant; the
+// alternative, a product by 2^261 mod q, is a whole Montgomery product (162).
+ZK29 Fq29 fq29_below_2p256(const Fq29& a) {
+  const uint32_t k = a.l[8] / ((Fq29P::Q[8]) + 1u);
+  Fq29 r;
+  int64_t c = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    c += (int64_t)a.l[i] - (int64_t)((uint64_t)k * Fq29P::Q[i]);
+    r.l[i] = (uint32_t)c & Fq29P::M;
+    c >>= 29;
+  }
+  r.l[8] = (uint32_t)((int64_t)a.l[8] - (int64_t)((uint64_t)k * Fq29P::Q[8]) + c);
+  return r;
 }
 
 // ---- sums and differences (class D results) ---------------------------------------------------------------------
@@ -347,8 +381,8 @@ ZK29 void g1piece29_finish(const G1Piece29& s, uint32_t* out32) {
   fq29_to_words(zzz, out32 + 24);
 }
 
-// acc += b, generic case only [add-2008-s], both in ONE domain (all four coordinates times 2^261: the reduction
-// kernels convert both operands on load). acc = +-b leaves ZZ = 0 (mod q), as above.
+// acc += b, generic case only [add-2008-s], both in ONE domain (all four coordinates times 2^261: the domain the
+// partial sums keep between the kernels, packed form below). acc = +-b leaves ZZ = 0 (mod q), as above.
 struct Xyzz29S {
   Fq29 x, y, zz, zzz;   // x class X, the others class N
 };
@@ -367,12 +401,20 @@ ZK29 void xyzz29s_to_wire(const Xyzz29S& a, Fq29& x, Fq29& y, Fq29& zz, Fq29& zz
   zzz = fq29_mul(a.zzz, k);
 }
 // Value products: u1 13 * 3, u2 13 * 3, s1, s2 9, pp 7^2, ppp 7 * 3, q 9, y 7 * 17 + 4 * 3, zz 9.
+// With operands loaded from the packed form (below) any coordinate may be class W (< 5.3q) instead of N, and x is X or
+// W: u1, u2 13 * 5.3 = 69, s1, s2 5.3^2 = 28.1, zz1 zz2 and zzz1 zzz2 28.1; everything after the first four products
+// sees product outputs only (u1, s1, p, r: as above), so the largest stays y at 131 <= 338. COLUMNS: every loaded
+// limb is normalised (limbs 0..7 < 2^29 by the slicing, limb 8 < 2^24), so the products that take loaded operands
+// are "both operands normalised" (< 18 * 2^58); the D operands are the same three as above.
 ZK29 void xyzz29s_add(Xyzz29S& acc, const Xyzz29S& b) {
+  // (order: each input coordinate dies as early as it can -- at most 7 field elements live besides the product at work)
   const Fq29 u1 = fq29_mul(acc.x, b.zz);
   const Fq29 u2 = fq29_mul(b.x, acc.zz);
+  const Fq29 zz12 = fq29_mul(acc.zz, b.zz);
+  const Fq29 p = fq29_norm(fq29_sub<Fq29C4>(u2, u1));
   const Fq29 s1 = fq29_mul(acc.y, b.zzz);
   const Fq29 s2 = fq29_mul(b.y, acc.zzz);
-  const Fq29 p = fq29_norm(fq29_sub<Fq29C4>(u2, u1));
+  const Fq29 zzz12 = fq29_mul(acc.zzz, b.zzz);
   const Fq29 r = fq29_norm(fq29_sub<Fq29C4>(s2, s1));
   const Fq29 pp = fq29_sqr(p);
   const Fq29 rr = fq29_sqr(r);
@@ -384,8 +426,39 @@ ZK29 void xyzz29s_add(Xyzz29S& acc, const Xyzz29S& b) {
   const Fq29 x3 = fq29_norm(t);
   acc.y = fq29_dot2(r, fq29_sub<Fq29C14>(q, x3), fq29_neg<Fq29C4>(s1), ppp);
   acc.x = x3;
-  acc.zz = fq29_mul(fq29_mul(acc.zz, b.zz), pp);
-  acc.zzz = fq29_mul(fq29_mul(acc.zzz, b.zzz), ppp);
+  acc.zz = fq29_mul(zz12, pp);
+  acc.zzz = fq29_mul(zzz12, ppp);
+}
+
+
+// ---- packed partial sums: 128 bytes, the form between the kernels ------------------------------------------------
+// A G1 partial sum in HBM is its Xyzz29S (all four coordinates times 2^261) with every coordinate brought below 2^256
+// and re-limbed into 8 words: x then y, zz, zzz. Infinity is 32 zero words (a sum's ZZ is never 0 as a value: poison
+// is not stored, and a non-infinity ZZ is a non-zero field element). y, zz, zzz are class N or W and fit as they
+// are; x is class X and is reduced by fq29_below_2p256. Loading is bit slicing only: every coordinate comes back class W.
+// A stored ZZ is always a product output (class N, < 3q) -- a piece's closing product, an addition's, a conversion's, or
+// such a word loaded and stored again unchanged -- which is what lets fq29_is_zero_mod_q test a sum's ZZ against 0, q, 2q.
+ZK29 void xyzz29s_pack(const Xyzz29S& a, uint32_t* w32) {
+  fq29_to_words(fq29_below_2p256(a.x), w32);
+  fq29_to_words(a.y, w32 + 8);
+  fq29_to_words(a.zz, w32 + 16);
+  fq29_to_words(a.zzz, w32 + 24);
+}
+ZK29 void xyzz29s_unpack(Xyzz29S& a, const uint32_t* w32) {
+  a.x = fq29_from_words(w32);
+  a.y = fq29_from_words(w32 + 8);
+  a.zz = fq29_from_words(w32 + 16);
+  a.zzz = fq29_from_words(w32 + 24);
+}
+// the piece's sum in the single domain: ZZ, ZZZ from 2^266 to 2^261 (one product each), X and Y as they are. False
+// if it is not a sum (ZZ = 0 mod q: the piece met acc = +-base); the piece must not be empty.
+ZK29 bool g1piece29_close(const G1Piece29& s, Xyzz29S& out) {
+  const Fq29 k = fq29_const<Fq29K256>();
+  out.x = s.a.x;
+  out.y = s.a.y;
+  out.zz = fq29_mul(s.a.zz, k);
+  out.zzz = fq29_mul(s.a.zzz, k);
+  return !fq29_is_zero_mod_q(out.zz);
 }
 
 }  // namespace zkpoa

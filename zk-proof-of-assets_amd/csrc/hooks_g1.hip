@@ -25,7 +25,8 @@ struct Fq29Arity {
   int in_raw, in_words, out;
 };
 static Fq29Arity fq29_prim_arity(int op) {
-  static constexpr Fq29Arity k[] = {{18, 16, 9}, {9, 8, 9}, {36, 32, 9}, {18, 16, 9}, {8, 8, 17}, {49, 49, 32}, {64, 64, 32}, {18, 16, 9}, {136, 136, 32}};
+  static constexpr Fq29Arity k[] = {{18, 16, 9}, {9, 8, 9}, {36, 32, 9}, {18, 16, 9}, {8, 8, 17}, {49, 49, 32}, {64, 64, 32}, {18, 16, 9}, {136, 136, 32},
+                                    {0, 0, 0}, {64, 64, 36}, {136, 136, 36}, {32, 32, 32}};
   if (op < 0 || op >= (int)(sizeof(k) / sizeof(k[0]))) return {0, 0, 0};
   return k[op];
 }
@@ -128,6 +129,46 @@ static __global__ __launch_bounds__(256) void fq29_prim_kernel(int op, const uin
       store_xyzz(dst, 0, acc);
       break;
     }
+    case 10: {   // packed + packed -> packed as the partial-sum kernels add; word 32 = 1 when the exact addition redid it
+      const G1Sum29 a = g1sum29_load(src, 0), b = g1sum29_load(src, 1);
+      G1Sum29 acc = a;
+      RedPacked29::add(acc, b);
+      const bool redo = RedPacked29::poisoned(acc);
+      if (redo) {
+        XYZZ<Fq> e = g1sum29_to_wire(a);
+        xyzz_add(e, g1sum29_to_wire(b));
+        RedExact29::store<false>(dst, 0, e);
+      } else {
+        RedPacked29::store<false>(dst, 0, acc);
+      }
+      dst[32] = redo ? 1u : 0u;
+      dst[33] = dst[34] = dst[35] = 0;
+      break;
+    }
+    case 11: {   // a piece of 8 bases as msm_accum0_kernel closes it -> packed; word 32 as above
+      G1Piece29 s;
+      s.a = {};
+      s.empty = true;
+      for (int k = 0; k < 8; k++) {
+        const Affine<Fq> p = {fq(17 * k), fq(17 * k + 8)};
+        g1piece29_add(s, p.x.l, p.y.l, src[17 * k + 16] != 0);
+      }
+      G1Sum29 sum = RedPacked29::inf();
+      sum.inf = s.empty;
+      const bool redo = !s.empty && !g1piece29_close(s, sum.p);
+      if (redo) {
+        XYZZ<Fq> acc = XYZZ<Fq>::inf();
+        for (int k = 0; k < 8; k++) xyzz_add_affine(acc, Affine<Fq>{fq(17 * k), fq(17 * k + 8)}, src[17 * k + 16] != 0);
+        sum = g1sum29_from_wire(acc);
+      }
+      g1sum29_store(dst, 0, sum);
+      dst[32] = redo ? 1u : 0u;
+      dst[33] = dst[34] = dst[35] = 0;
+      break;
+    }
+    case 12:   // packed -> canonical wire XYZZ, as the last kernel of the reduction stores it
+      RedPacked29::store<true>(dst, 0, g1sum29_load(src, 0));
+      break;
     default: {   // 6: wire XYZZ + wire XYZZ -> canonical XYZZ
       XYZZ<Fq> acc = {fq(0), fq(8), fq(16), fq(24)};
       xyzz_add29(acc, XYZZ<Fq>{fq(32), fq(40), fq(48), fq(56)});

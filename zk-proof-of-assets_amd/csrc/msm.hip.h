@@ -584,6 +584,174 @@ ZK_DEV bool g1piece29_result(const G1Piece29& s, XYZZ<Fq>& out) {
   return s.empty || !out.zz.is_zero();
 }
 
+// ---- G1 partial sums between the kernels: the packed 29-bit form ------------------------------------------------
+// Level 0 closes a piece into the packed form of fq29.hip.h (128 bytes, all four coordinates times 2^261, below
+// 2^256) and the partial-sum levels and the bucket reduction keep it: a load is bit slicing, an addition is
+// xyzz29s_add with no conversion around it, a store normalises X once. In registers a sum is its Xyzz29S and an
+// explicit infinity flag: ZZ = 0 (mod q) marks a POISONED sum (the generic addition met acc = +-b) and cannot double
+// as infinity. Poison is never stored: whoever is about to store tests ZZ and redoes its sum with the exact 32-bit
+// xyzz_add, converting the operands to the wire domain and the result back (ZZ^3 = ZZZ^2 holds for the wire values,
+// not for packed words read as wire words). The last kernel of the chain writes canonical wire XYZZ for the host.
+struct G1Sum29 {
+  Xyzz29S p;
+  bool inf;
+};
+ZK_DEV G1Sum29 g1sum29_load(const void* base, size_t idx) {
+  const uint4* q = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(base) + idx * 128);
+  uint32_t w[32], any = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const uint4 v = q[i];
+    w[4 * i] = v.x;
+    w[4 * i + 1] = v.y;
+    w[4 * i + 2] = v.z;
+    w[4 * i + 3] = v.w;
+    any |= v.x | v.y | v.z | v.w;
+  }
+  G1Sum29 r;
+  xyzz29s_unpack(r.p, w);
+  r.inf = any == 0;
+  return r;
+}
+ZK_DEV void g1sum29_store(void* base, size_t idx, const G1Sum29& v) {
+  uint4* q = reinterpret_cast<uint4*>(reinterpret_cast<char*>(base) + idx * 128);
+  uint32_t w[32];
+  xyzz29s_pack(v.p, w);
+#pragma unroll
+  for (int i = 0; i < 8; i++)
+    q[i] = v.inf ? make_uint4(0, 0, 0, 0) : make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+}
+// packed domain -> wire XYZZ in the lazy range, and back (any representative; class N on the way back)
+ZK_DEV XYZZ<Fq> g1sum29_to_wire(const G1Sum29& v) {
+  if (v.inf) return XYZZ<Fq>::inf();
+  Fq29 o[4];
+  xyzz29s_to_wire(v.p, o[0], o[1], o[2], o[3]);
+  uint32_t w[32];
+#pragma unroll
+  for (int c = 0; c < 4; c++) fq29_to_words(o[c], w + 8 * c);
+  return xyzz_from_words_3q(w);
+}
+ZK_DEV G1Sum29 g1sum29_from_wire(const XYZZ<Fq>& a) {
+  G1Sum29 r;
+  r.inf = a.is_inf();
+  xyzz29s_from_wire(r.p, fq29_from_words(a.x.l), fq29_from_words(a.y.l), fq29_from_words(a.zz.l), fq29_from_words(a.zzz.l));
+  return r;
+}
+
+// How a partial-sum kernel holds, moves and adds its sums: three forms with one interface, so every kernel body below
+// is written once. store<Wire>: the kernel's output form (Wire: canonical wire XYZZ). kLds: LDS bytes per thread.
+//   RedWire<F>    wire XYZZ throughout, exact addition: G2, the 32-bit build, the key set-up
+//   RedPacked29   packed in HBM, 9-limb words through LDS (37 words per thread, word-major: no conversion, no bank
+//                 conflict), generic addition: poisoned() has to be asked before a store
+//   RedExact29    the same memory form with the exact 32-bit addition (operands converted on load): the redo
+template <class F>
+struct RedWire {
+  using Pt = XYZZ<F>;
+  static constexpr size_t kLds = 4 * FieldBytes<F>::N;
+  static ZK_DEV Pt inf() { return XYZZ<F>::inf(); }
+  static ZK_DEV Pt load(const void* base, size_t idx) { return load_xyzz<F>(base, idx); }
+  template <bool Wire>
+  static ZK_DEV void store(void* base, size_t idx, const Pt& v) { store_xyzz(base, idx, v); }
+  static ZK_DEV void lds_put(char* lds, uint32_t tid, uint32_t, const Pt& v) { store_xyzz(lds, tid, v); }
+  static ZK_DEV Pt lds_get(const char* lds, uint32_t tid, uint32_t) { return load_xyzz<F>(lds, tid); }
+  static ZK_DEV void add(Pt& acc, const Pt& o) { xyzz_add(acc, o); }
+  static ZK_DEV bool poisoned(const Pt&) { return false; }
+};
+struct RedPacked29 {
+  using Pt = G1Sum29;
+  static constexpr size_t kLds = 37 * 4;
+  static ZK_DEV Pt inf() {
+    Pt r;
+    r.p = {};
+    r.inf = true;
+    return r;
+  }
+  static ZK_DEV Pt load(const void* base, size_t idx) { return g1sum29_load(base, idx); }
+  template <bool Wire>
+  static ZK_DEV void store(void* base, size_t idx, const Pt& v) {
+    if constexpr (Wire) store_xyzz(base, idx, g1sum29_to_wire(v));
+    else g1sum29_store(base, idx, v);
+  }
+  static ZK_DEV void lds_put(char* lds, uint32_t tid, uint32_t nthreads, const Pt& v) {
+    uint32_t* w = reinterpret_cast<uint32_t*>(lds) + tid;
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+      w[(size_t)i * nthreads] = v.p.x.l[i];
+      w[(size_t)(9 + i) * nthreads] = v.p.y.l[i];
+      w[(size_t)(18 + i) * nthreads] = v.p.zz.l[i];
+      w[(size_t)(27 + i) * nthreads] = v.p.zzz.l[i];
+    }
+    w[(size_t)36 * nthreads] = v.inf ? 1u : 0u;
+  }
+  static ZK_DEV Pt lds_get(const char* lds, uint32_t tid, uint32_t nthreads) {
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(lds) + tid;
+    Pt v;
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+      v.p.x.l[i] = w[(size_t)i * nthreads];
+      v.p.y.l[i] = w[(size_t)(9 + i) * nthreads];
+      v.p.zz.l[i] = w[(size_t)(18 + i) * nthreads];
+      v.p.zzz.l[i] = w[(size_t)(27 + i) * nthreads];
+    }
+    v.inf = w[(size_t)36 * nthreads] != 0;
+    return v;
+  }
+  // x of either operand is class X or W, the rest N or W (fq29.hip.h, xyzz29s_add); skipped by the whole wave when
+  // every lane's operand is infinity
+  static ZK_DEV void add(Pt& acc, const Pt& o) {
+    if (o.inf) return;
+    if (acc.inf) {
+      acc = o;
+      return;
+    }
+    xyzz29s_add(acc.p, o.p);
+  }
+  static ZK_DEV bool poisoned(const Pt& v) { return !v.inf && fq29_is_zero_mod_q(v.p.zz); }
+};
+struct RedExact29 {
+  using Pt = XYZZ<Fq>;
+  static constexpr size_t kLds = 4 * FieldBytes<Fq>::N;
+  static ZK_DEV Pt inf() { return XYZZ<Fq>::inf(); }
+  static ZK_DEV Pt load(const void* base, size_t idx) { return g1sum29_to_wire(g1sum29_load(base, idx)); }
+  template <bool Wire>
+  static ZK_DEV void store(void* base, size_t idx, const Pt& v) {
+    if constexpr (Wire) store_xyzz(base, idx, v);
+    else g1sum29_store(base, idx, g1sum29_from_wire(v));
+  }
+  static ZK_DEV void lds_put(char* lds, uint32_t tid, uint32_t, const Pt& v) { store_xyzz(lds, tid, v); }
+  static ZK_DEV Pt lds_get(const char* lds, uint32_t tid, uint32_t) { return load_xyzz<Fq>(lds, tid); }
+  static ZK_DEV void add(Pt& acc, const Pt& o) { xyzz_add(acc, o); }
+  static ZK_DEV bool poisoned(const Pt&) { return false; }
+};
+// The redo reads what the first attempt read, at the same addresses. Handed the same pointer and indices, the compiler
+// keeps the first attempt's loaded words and the redo's precomputed addresses alive through the whole generic sum (20 to
+// 30 VGPRs, which then spill); the redo takes its pointer and its per-lane indices through these.
+ZK_DEV const void* red_reread(const void* p) {
+  asm volatile("" : "+s"(p) : : "memory");
+  return p;
+}
+// The workgroup's vote on "some storing lane holds poison", as a value the compiler knows to be uniform: the redo is
+// then a branch of the whole workgroup and the generic sum is not kept alive across it.
+template <bool Packed>
+ZK_DEV bool red_vote(bool mine) {
+  if constexpr (!Packed) return false;
+  else return __builtin_amdgcn_readfirstlane(__syncthreads_or(mine ? 1 : 0)) != 0;
+}
+template <class T>
+ZK_DEV T red_again(T v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+static_assert(RedExact29::kLds <= RedPacked29::kLds, "the redo shares the LDS of the first attempt");
+// The G1 MSM's form, unless the 32-bit build is asked for
+template <class F>
+constexpr bool kPackedSums = kG1Limb29 && std::is_same<F, Fq>::value;
+// waves per SIMD the packed kernels are compiled for: 3 (<= 168 VGPRs), so that they co-reside with accumulation waves
+template <bool Packed>
+constexpr int kRedWaves = Packed ? 3 : 1;
+template <class F, bool Packed>
+using RedOps = typename std::conditional<Packed, RedPacked29, RedWire<F>>::type;
+
 // waves per SIMD the accumulation kernel is compiled for (register budget 512 / waves):
 // G1: 144 VGPRs in the 29-bit-limb form -> 3 waves (4 waves = 128 VGPRs spills 72 bytes per lane; the 32-bit form,
 // 132 VGPRs, measured no faster at 4: the kernel is at the ALU ceiling); G2: 256 -> 2
@@ -651,13 +819,19 @@ static __global__ __launch_bounds__(256, AccumWaves<F>::N) void msm_accum0_kerne
       }
       g1piece29_add(s, p_cur.x.l, p_cur.y.l, (e_cur >> 31) != 0);
     }
-    if (!g1piece29_result(s, acc)) {   // the piece met acc = +-base: once more, with the exact addition
-      acc = XYZZ<F>::inf();
+    // the piece closes straight into the packed form (two products; X is normalised by the store): ZZ is tested once
+    G1Sum29 sum = RedPacked29::inf();
+    sum.inf = s.empty;
+    if (!s.empty && !g1piece29_close(s, sum.p)) {   // the piece met acc = +-base: once more, with the exact addition
       for (uint32_t k = start; k < end; k++) {
         const uint32_t e2 = sorted[k];
         xyzz_add_affine(acc, load_affine<F>(bases, e2 & 0x7fffffffu), (e2 >> 31) != 0);
       }
+      sum = g1sum29_from_wire(acc);
     }
+    if ((cnt + K0 - 1) / K0 == 1) g1sum29_store(buckets, b, sum);
+    else g1sum29_store(P1, t, sum);
+    return;
   } else if (kAccumPrefetch<F>) {
     uint32_t e = entry(start);
     Affine<F> p = load_affine<F>(bases, e & 0x7fffffffu);
@@ -685,12 +859,20 @@ static __global__ __launch_bounds__(256, AccumWaves<F>::N) void msm_accum0_kerne
 }
 
 // level l >= 1: items are XYZZ partial sums. Input items of bucket b: pin = pc_in[b] > 1 ? pc_in[b] : 0,
-// stored at Pin[po_in[b] ...]; output pieces enumerated by po_out.
-template <class F>
-static __global__ __launch_bounds__(256) void msm_accumN_kernel(const void* __restrict__ Pin,
+// stored at Pin[po_in[b] ...]; output pieces enumerated by po_out. Packed: items and outputs in the packed 29-bit form;
+// a lane whose chain came out poisoned redoes it, its wave with it, with the exact addition.
+template <class Ops>
+ZK_DEV typename Ops::Pt msm_sum_chain(const void* __restrict__ Pin, uint32_t start, uint32_t end) {
+  typename Ops::Pt acc = Ops::load(Pin, start);
+  for (uint32_t k = start + 1; k < end; k++) Ops::add(acc, Ops::load(Pin, k));
+  return acc;
+}
+template <class F, bool Packed = false>
+static __global__ __launch_bounds__(256, kRedWaves<Packed>) void msm_accumN_kernel(const void* __restrict__ Pin,
                                                          const uint32_t* __restrict__ po_in,
                                                          const uint32_t* __restrict__ po_out, uint32_t TB, uint32_t K,
                                                          void* __restrict__ buckets, void* __restrict__ Pout) {
+  using Ops = RedOps<F, Packed>;
   uint32_t t = blockIdx.x * 256u + threadIdx.x;
   uint32_t total = po_out[TB];
   if (t >= total) return;
@@ -700,14 +882,18 @@ static __global__ __launch_bounds__(256) void msm_accumN_kernel(const void* __re
   uint32_t start = po_in[b] + j * K;
   uint32_t end = po_in[b] + cnt;
   if (end - start > K) end = start + K;
-  XYZZ<F> acc = load_xyzz<F>(Pin, start);
-  for (uint32_t k = start + 1; k < end; k++) {
-    XYZZ<F> q = load_xyzz<F>(Pin, k);
-    xyzz_add(acc, q);
+  const bool last = po_out[b + 1] - po_out[b] == 1;
+  void* dst = last ? buckets : Pout;
+  const size_t di = last ? b : t;
+  const typename Ops::Pt acc = msm_sum_chain<Ops>(Pin, start, end);
+  // A poisoned lane takes its whole wave into the redo (the other lanes' exact sums are the same points): the branch is
+  // then one of the wave, known to the compiler as such, and the generic sum is not kept alive across the redo.
+  const bool redo = Packed && __builtin_amdgcn_readfirstlane(__any(Ops::poisoned(acc)) ? 1 : 0) != 0;
+  if (!redo) Ops::template store<false>(dst, di, acc);
+  if constexpr (Packed) {
+    if (redo)
+      RedExact29::store<false>(dst, di, msm_sum_chain<RedExact29>(red_reread(Pin), red_again(start), red_again(end)));
   }
-  uint32_t pieces = po_out[b + 1] - po_out[b];
-  if (pieces == 1) store_xyzz(buckets, b, acc);
-  else store_xyzz(Pout, t, acc);
 }
 
 // ---- 5: bucket reduction ----------------------------------------------------------------------
@@ -739,12 +925,45 @@ inline uint32_t msm_reduce_log_parts(uint32_t logRows, uint32_t logS = 0, uint32
 }
 inline uint32_t msm_reduce_bits(uint32_t logS) { return logS + 1; }   // column weights go up to S = 2^logS
 
-template <class F>
-static __global__ __launch_bounds__(256) void msm_bucket_sums_kernel(const void* __restrict__ buckets,
+// The body of each kernel is written once over the form of its sums (RedOps). Packed: the 29-bit form; every lane about
+// to store asks poisoned(), the workgroup votes, and on a hit the whole workgroup runs its body again in the exact form
+// (a poisoned operand anywhere in a tree reaches the storing lane: zz3 = zz1 zz2 pp stays 0). WireOut: the output is
+// canonical wire XYZZ (the last kernel before the host).
+template <class Ops>
+ZK_DEV typename Ops::Pt msm_bucket_sums_body(const void* __restrict__ buckets, const uint32_t* __restrict__ counts,
+                                             bool valid, size_t base, uint32_t stride, uint32_t part, uint32_t per,
+                                             uint32_t per_max, uint32_t logParts, char* lds_raw) {
+  const uint32_t parts = 1u << logParts;
+  typename Ops::Pt acc = Ops::inf();
+  // iterations [0, per_max): this thread's buckets from HBM; then logParts tree levels through LDS.
+  // (Tried and dropped, r02: handing each tree level's additions to the first threads of the workgroup so that idle
+  // lanes form whole waves that skip the addition -- fewer wave-additions, same depth: no gain alone or six in flight.)
+  for (uint32_t it = 0; it < per_max + logParts; it++) {
+    typename Ops::Pt other = Ops::inf();
+    if (it < per_max) {
+      // an empty bucket was never written (the array is not cleared: 3.2 GB per 2^26 MSM): its count says so
+      if (valid && it < per) {
+        const size_t bi = base + (size_t)(part * per + it) * stride;
+        if (counts[bi]) other = Ops::load(buckets, bi);
+      }
+    } else {
+      const uint32_t st = parts >> (it - per_max + 1u);
+      Ops::lds_put(lds_raw, threadIdx.x, 256u, acc);
+      __syncthreads();
+      if (part < st) other = Ops::lds_get(lds_raw, threadIdx.x + st, 256u);
+      __syncthreads();
+    }
+    Ops::add(acc, other);
+  }
+  return acc;
+}
+template <class F, bool Packed = false>
+static __global__ __launch_bounds__(256, kRedWaves<Packed>) void msm_bucket_sums_kernel(const void* __restrict__ buckets,
                                                                      const uint32_t* __restrict__ counts, uint32_t W,
                                                                      uint32_t Nb, uint32_t logS, uint32_t logRows,
                                                                      uint32_t logParts, uint32_t E,
                                                                      void* __restrict__ out) {
+  using Ops = RedOps<F, Packed>;
   extern __shared__ __attribute__((aligned(16))) char lds_raw[];
   const uint32_t gid = blockIdx.x * 256u + threadIdx.x;
   const uint32_t parts = 1u << logParts, part = gid & (parts - 1u), o = gid >> logParts;
@@ -757,83 +976,80 @@ static __global__ __launch_bounds__(256) void msm_bucket_sums_kernel(const void*
   const size_t base = (size_t)w * Nb + (is_row ? (size_t)idx * S : (size_t)idx);
   const uint32_t per = len >> logParts;   // logParts <= min(logS, logRows)
   const uint32_t per_max = S >> logParts; // uniform trip count (S >= rows)
-  XYZZ<F> acc = XYZZ<F>::inf();
-  // iterations [0, per_max): this thread's buckets from HBM; then logParts tree levels through LDS.
-  // (Tried and dropped, r02: handing each tree level's additions to the first threads of the workgroup so that idle
-  // lanes form whole waves that skip the addition -- fewer wave-additions, same depth: no gain alone or six in flight.)
-  for (uint32_t it = 0; it < per_max + logParts; it++) {
-    XYZZ<F> other = XYZZ<F>::inf();
-    if (it < per_max) {
-      // an empty bucket was never written (the array is not cleared: 3.2 GB per 2^26 MSM): its count says so
-      if (valid && it < per) {
-        const size_t bi = base + (size_t)(part * per + it) * stride;
-        if (counts[bi]) other = load_xyzz<F>(buckets, bi);
-      }
-    } else {
-      const uint32_t st = parts >> (it - per_max + 1u);
-      store_xyzz(lds_raw, threadIdx.x, acc);
-      __syncthreads();
-      if (part < st) other = load_xyzz<F>(lds_raw, threadIdx.x + st);
-      __syncthreads();
+  const bool mine = valid && part == 0;
+  const size_t oi = ((size_t)w * 2u + (is_row ? 0u : 1u)) * E + idx;
+  const typename Ops::Pt acc =
+      msm_bucket_sums_body<Ops>(buckets, counts, valid, base, stride, part, per, per_max, logParts, lds_raw);
+  const bool redo = red_vote<Packed>(mine && Ops::poisoned(acc));
+  if (!redo && mine) Ops::template store<false>(out, oi, acc);
+  if constexpr (Packed) {
+    if (redo) {
+      const XYZZ<Fq> e =
+          msm_bucket_sums_body<RedExact29>(red_reread(buckets), counts, valid, red_again(base), red_again(stride),
+                                           red_again(part), red_again(per), per_max, logParts, lds_raw);
+      if (mine) RedExact29::store<false>(out, oi, e);
     }
-    xyzz_add(acc, other);
   }
-  if (valid && part == 0) store_xyzz(out, ((size_t)w * 2u + (is_row ? 0u : 1u)) * E + idx, acc);
 }
 
 // Y[(g * nbits + b) * S_out + blockIdx.x] = sum of the X[g * E + idx], idx in this block's 256, whose weight has bit b
 // (g = w * 2 + grp; weight = idx for row sums, idx + 1 for column sums, 0 for padding entries).
 // ONE wave per workgroup: each lane adds its 4 entries, then 6 LDS tree levels (a 256-thread workgroup would keep
 // three of its four waves parked at the barriers of the tree, each holding ~140 VGPRs).
-template <class F>
-static __global__ __launch_bounds__(64) void msm_bit_tree_sum_kernel(const void* __restrict__ X, uint32_t E,
+// msm_tree_sum_kernel is the same tree with every entry taken (bit < 0): Y[w][blockIdx.x] = sum of
+// X[w][blockIdx.x*256 .. +256) (cnt entries per group, E apart).
+template <class Ops>
+ZK_DEV typename Ops::Pt msm_tree_body(const void* __restrict__ X, size_t row, uint32_t cnt, uint32_t grp, int bit,
+                                      char* lds_raw) {
+  typename Ops::Pt v = Ops::inf();
+  // iterations 0..3: this lane's entries from HBM; 4..9: tree levels through LDS (one inlined addition site)
+  for (uint32_t it = 0; it < 10; it++) {
+    typename Ops::Pt o = Ops::inf();
+    if (it < 4) {
+      const uint32_t idx = blockIdx.x * 256u + it * 64u + threadIdx.x;
+      const uint32_t k = idx < cnt ? (grp ? idx + 1u : idx) : 0u;
+      if (bit < 0 ? idx < cnt : ((k >> bit) & 1u) != 0) o = Ops::load(X, row + idx);
+    } else {
+      const uint32_t stride = 32u >> (it - 4);
+      Ops::lds_put(lds_raw, threadIdx.x, 64u, v);
+      __syncthreads();
+      if (threadIdx.x < stride) o = Ops::lds_get(lds_raw, threadIdx.x + stride, 64u);
+      __syncthreads();
+    }
+    Ops::add(v, o);
+  }
+  return v;
+}
+// the tree of one workgroup in the kernel's form, once more in the exact form if lane 0 holds poison, stored by lane 0
+template <class F, bool Packed, bool WireOut>
+ZK_DEV void msm_tree_run(const void* __restrict__ X, size_t row, uint32_t cnt, uint32_t grp, int bit, void* __restrict__ Y,
+                         size_t oi, char* lds_raw) {
+  using Ops = RedOps<F, Packed>;
+  const typename Ops::Pt v = msm_tree_body<Ops>(X, row, cnt, grp, bit, lds_raw);
+  const bool redo = red_vote<Packed>(threadIdx.x == 0 && Ops::poisoned(v));
+  if (!redo && threadIdx.x == 0) Ops::template store<WireOut>(Y, oi, v);
+  if constexpr (Packed) {
+    if (redo) {
+      const XYZZ<Fq> e = msm_tree_body<RedExact29>(red_reread(X), row, cnt, grp, bit, lds_raw);
+      if (threadIdx.x == 0) RedExact29::store<WireOut>(Y, oi, e);
+    }
+  }
+}
+template <class F, bool Packed = false, bool WireOut = false>
+static __global__ __launch_bounds__(64, kRedWaves<Packed>) void msm_bit_tree_sum_kernel(const void* __restrict__ X, uint32_t E,
                                                                      uint32_t logS, uint32_t logRows, uint32_t nbits,
                                                                      uint32_t S_out, void* __restrict__ Y) {
   extern __shared__ __attribute__((aligned(16))) char lds_raw[];
   const uint32_t g = blockIdx.y / nbits, b = blockIdx.y % nbits, grp = g & 1u;
   const uint32_t cnt = grp ? (1u << logS) : (1u << logRows);
-  XYZZ<F> v = XYZZ<F>::inf();
-  // iterations 0..3: this lane's entries from HBM; 4..9: tree levels through LDS (one inlined addition site)
-  for (uint32_t it = 0; it < 10; it++) {
-    XYZZ<F> o = XYZZ<F>::inf();
-    if (it < 4) {
-      const uint32_t idx = blockIdx.x * 256u + it * 64u + threadIdx.x;
-      const uint32_t k = idx < cnt ? (grp ? idx + 1u : idx) : 0u;
-      if ((k >> b) & 1u) o = load_xyzz<F>(X, (size_t)g * E + idx);
-    } else {
-      const uint32_t stride = 32u >> (it - 4);
-      store_xyzz(lds_raw, threadIdx.x, v);
-      __syncthreads();
-      if (threadIdx.x < stride) o = load_xyzz<F>(lds_raw, threadIdx.x + stride);
-      __syncthreads();
-    }
-    xyzz_add(v, o);
-  }
-  if (threadIdx.x == 0) store_xyzz(Y, (size_t)blockIdx.y * S_out + blockIdx.x, v);
+  msm_tree_run<F, Packed, WireOut>(X, (size_t)g * E, cnt, grp, (int)b, Y, (size_t)blockIdx.y * S_out + blockIdx.x, lds_raw);
 }
-
-// Y[w][blockIdx.x] = sum of X[w][blockIdx.x*256 .. +256) (S entries per window); same one-wave shape.
-template <class F>
-static __global__ __launch_bounds__(64) void msm_tree_sum_kernel(const void* __restrict__ X, uint32_t S, uint32_t S_out,
+template <class F, bool Packed = false, bool WireOut = false>
+static __global__ __launch_bounds__(64, kRedWaves<Packed>) void msm_tree_sum_kernel(const void* __restrict__ X, uint32_t S, uint32_t S_out,
                                                            void* __restrict__ Y) {
   extern __shared__ __attribute__((aligned(16))) char lds_raw[];
   const uint32_t w = blockIdx.y;
-  XYZZ<F> v = XYZZ<F>::inf();
-  for (uint32_t it = 0; it < 10; it++) {
-    XYZZ<F> o = XYZZ<F>::inf();
-    if (it < 4) {
-      const uint32_t idx = blockIdx.x * 256u + it * 64u + threadIdx.x;
-      if (idx < S) o = load_xyzz<F>(X, (size_t)w * S + idx);
-    } else {
-      const uint32_t stride = 32u >> (it - 4);
-      store_xyzz(lds_raw, threadIdx.x, v);
-      __syncthreads();
-      if (threadIdx.x < stride) o = load_xyzz<F>(lds_raw, threadIdx.x + stride);
-      __syncthreads();
-    }
-    xyzz_add(v, o);
-  }
-  if (threadIdx.x == 0) store_xyzz(Y, (size_t)w * S_out + blockIdx.x, v);
+  msm_tree_run<F, Packed, WireOut>(X, (size_t)w * S, S, 0u, -1, Y, (size_t)w * S_out + blockIdx.x, lds_raw);
 }
 
 // ---- host driver ------------------------------------------------------------------------------
@@ -979,7 +1195,8 @@ inline size_t msm_accum_workspace_bytes(const MsmPlan& p) { return msm_layout_by
 // more than one partial sum, one thread adds up to K of them. po_in: the TB + 1 offsets of the items entering the first
 // level (read-only); the levels' own offsets ping-pong between po_b / po_c, their sums between Pin / Pout (capacities in
 // XYZZ). max_items: most items in one bucket; total_in: at most this many enter the level. scan(in, out): its mode-3 scan.
-template <class F, class Scan>
+// Packed: the items are packed 29-bit sums (the G1 MSM's level 0 wrote them); otherwise wire XYZZ.
+template <class F, bool Packed = false, class Scan>
 inline void msm_reduce_levels(hipStream_t st, uint32_t TB, uint32_t K, const uint32_t* po_in, uint32_t* po_b,
                               uint32_t* po_c, char* Pin, size_t cap_in, char* Pout, size_t cap_out, uint64_t max_items,
                               uint64_t total_in, void* buckets, Scan scan) {
@@ -988,7 +1205,7 @@ inline void msm_reduce_levels(hipStream_t st, uint32_t TB, uint32_t K, const uin
     uint64_t bound = total_in / 2 + 1;  // every unfinished bucket holds >= 2 items and emits <= items/2 + 1 pieces
     if (bound > cap_out) throw HipError("msm: level buffer too small");
     scan(po_in, po_out);
-    hipLaunchKernelGGL((msm_accumN_kernel<F>), dim3((uint32_t)((bound + 255) / 256)), dim3(256), 0, st, (const void*)Pin,
+    hipLaunchKernelGGL((msm_accumN_kernel<F, Packed>), dim3((uint32_t)((bound + 255) / 256)), dim3(256), 0, st, (const void*)Pin,
                        po_in, (const uint32_t*)po_out, TB, K, buckets, (void*)Pout);
     max_items = (max_items + K - 1) / K;
     total_in = bound;
@@ -1137,22 +1354,34 @@ inline void msm_accum_phase(Lane& lane, const MsmSorted& sr, const void* d_bases
   // further levels while some bucket still has more than one partial sum; the shared po_a is read-only,
   // the level offsets ping-pong between this phase's own po_b / po_c
   auto scan = [&](auto* in, auto* out) { lane_scan(lane, ScanPair{in, p.TB, 3, p.K, out, m.misc + 3, -1}, m.block_sums); };
-  msm_reduce_levels<F>(st, p.TB, p.K, sr.m.po_a, m.po_b, m.po_c, m.P1, m.p1_cap, m.P2, m.p2_cap,
+  constexpr bool kPacked = kPackedSums<F>;   // level 0 wrote packed sums; the last kernel below writes the wire form
+  constexpr size_t kLds = RedOps<F, kPacked>::kLds;
+  msm_reduce_levels<F, kPacked>(st, p.TB, p.K, sr.m.po_a, m.po_b, m.po_c, m.P1, m.p1_cap, m.P2, m.p2_cap,
                        ((uint64_t)sr.max_count + p.K0 - 1) / p.K0, sr.total1, m.buckets, scan);
   // bucket reduction: row / column sums, then per (window, group, weight bit) the total of the sums with that bit
   {
     uint32_t log_parts = msm_reduce_log_parts(p.logRows, p.logS, p.Wb);
     uint64_t threads = ((uint64_t)p.Wb << log_parts) * ((1u << p.logRows) + E);
-    hipLaunchKernelGGL((msm_bucket_sums_kernel<F>), dim3((uint32_t)((threads + 255) / 256)), dim3(256),
-                       256 * MsmSizes<F>::kXyzz, st, (const void*)m.buckets, (const uint32_t*)sr.m.counts, p.Wb, p.Nb, p.logS,
+    hipLaunchKernelGGL((msm_bucket_sums_kernel<F, kPacked>), dim3((uint32_t)((threads + 255) / 256)), dim3(256),
+                       256 * kLds, st, (const void*)m.buckets, (const uint32_t*)sr.m.counts, p.Wb, p.Nb, p.logS,
                        p.logRows, log_parts, E, (void*)m.X);
   }
   char *cur = m.Y1, *next = m.Y2;
-  hipLaunchKernelGGL((msm_bit_tree_sum_kernel<F>), dim3(S1, sums), dim3(64), 64 * MsmSizes<F>::kXyzz, st,
-                     (const void*)m.X, E, p.logS, p.logRows, nbits, S1, (void*)cur);
-  for (uint32_t S = S1; S > 1; S = (S + 255) / 256, std::swap(cur, next))
-    hipLaunchKernelGGL((msm_tree_sum_kernel<F>), dim3((S + 255) / 256, sums), dim3(64), 64 * MsmSizes<F>::kXyzz, st,
-                       (const void*)cur, S, (S + 255) / 256, (void*)next);
+  if (S1 == 1)
+    hipLaunchKernelGGL((msm_bit_tree_sum_kernel<F, kPacked, true>), dim3(S1, sums), dim3(64), 64 * kLds, st,
+                       (const void*)m.X, E, p.logS, p.logRows, nbits, S1, (void*)cur);
+  else
+    hipLaunchKernelGGL((msm_bit_tree_sum_kernel<F, kPacked, false>), dim3(S1, sums), dim3(64), 64 * kLds, st,
+                       (const void*)m.X, E, p.logS, p.logRows, nbits, S1, (void*)cur);
+  for (uint32_t S = S1; S > 1; S = (S + 255) / 256, std::swap(cur, next)) {
+    const uint32_t S_out = (S + 255) / 256;
+    if (S_out == 1)
+      hipLaunchKernelGGL((msm_tree_sum_kernel<F, kPacked, true>), dim3(S_out, sums), dim3(64), 64 * kLds, st,
+                         (const void*)cur, S, S_out, (void*)next);
+    else
+      hipLaunchKernelGGL((msm_tree_sum_kernel<F, kPacked, false>), dim3(S_out, sums), dim3(64), 64 * kLds, st,
+                         (const void*)cur, S, S_out, (void*)next);
+  }
   msm_read_back(lane, cur, (size_t)sums * MsmSizes<F>::kXyzz);
   ZK_HIP(hipGetLastError());
   memcpy(window_sums_host, lane.pinned, (size_t)sums * MsmSizes<F>::kXyzz);
