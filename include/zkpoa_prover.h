@@ -707,6 +707,23 @@ int zkpoa_test_ntt_plan(unsigned log_n, unsigned tile_log, uint32_t* out, unsign
  * n > 2^28, c outside 0..31, a flag that is not 0 / 1, k0 < 0 or a null out with cap > 0. */
 int zkpoa_test_msm_plan(uint64_t n, int c, int merged, int for_g2, const double* density32_or_null, int k0, uint64_t* out,
                         unsigned cap);
+/* Phase A of one MSM -- digits or the compact entry list, the counting-sort passes, the scans, the piece ordering --
+ * on n host scalars (32 B little-endian), run on lane `lane` through the prover's own entry, and what it hands the
+ * accumulation (test hook). n .. k0 are the request, as in zkpoa_test_msm_plan. Writes plan: the thirteen words of
+ * zkpoa_test_msm_plan; totals: non-zero digits (entries), the largest bucket, level-0 pieces; and seven arrays of 32-bit
+ * words, out[i] with room for cap[i] words: 0 = counts[TB] (entries per bucket), 1 = off0[TB + 1] (their exclusive sum),
+ * 2 = po_a[TB + 1] (exclusive sum of the buckets' piece counts), 3 = sorted[entries] (point index, merged form: table
+ * index w * n + i, | sign << 31, grouped by bucket in off0's order), 4 = pbkt[pieces] (bucket of each piece),
+ * 5 = order[pieces] (piece ids, longest first), 6 = len_hist[K0 + 1] (pieces of each length, as the scan left them).
+ * Returns PROVER_ERROR_SHORT_BUFFER when a capacity is too small: plan and totals are written, none of the arrays is.
+ * PROVER_ERROR for arguments out of range (as zkpoa_test_msm_plan; lane outside 0..11) or a device failure. */
+int zkpoa_test_msm_sort(zkpoa_context* ctx, int lane, const void* scalars, uint64_t n, int c, int merged, int for_g2,
+                        const double* density32_or_null, int k0, uint64_t plan[13], uint32_t totals[3],
+                        uint32_t* const out[7], const uint64_t cap[7]);
+/* The digit density the prover measures on a witness (test hook), on n host scalars: for c = 4..25 out[c] = the sum of
+ * ceil(bit length of min(s, r - s) / c) over the scalars, divided by n; elsewhere, and everywhere for n = 0, the
+ * uniform default ceil(254 / max(c, 4)). */
+int zkpoa_test_msm_density(zkpoa_context* ctx, const void* scalars, uint64_t n, double out[32]);
 
 #ifdef __cplusplus
 }

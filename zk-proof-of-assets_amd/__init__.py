@@ -54,6 +54,7 @@ EXPORTS = [
     "zkpoa_g1_sum", "zkpoa_g2_sum", "zkpoa_g1_mul", "zkpoa_g2_mul",
     "zkpoa_setup_defer_host_frees", "zkpoa_last_ms", "zkpoa_set_option", "zkpoa_msm_points_limit", "zkpoa_field_op", "zkpoa_group_add",
     "zkpoa_field_prim", "zkpoa_curve_prim", "zkpoa_fq29_prim", "zkpoa_ntt_form", "zkpoa_test_ntt_plan", "zkpoa_test_msm_plan",
+    "zkpoa_test_msm_sort", "zkpoa_test_msm_density",
     "zkpoa_groth16_verify", "zkpoa_sanitize_proof", "zkpoa_groth16_verify_points", "zkpoa_zkey_vkey", "zkpoa_zkey_export_vkey",
     "zkpoa_zkey_read_h_scalars", "zkpoa_zkey_precompute",
     "zkpoa_context_stream", "zkpoa_context_synchronize",
@@ -160,6 +161,15 @@ def lib():
                                       ctypes.c_int]
         L.zkpoa_ntt_form.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_uint, ctypes.c_uint64]
+        L.zkpoa_test_msm_plan.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.POINTER(ctypes.c_uint64),
+                                          ctypes.c_uint]
+        L.zkpoa_test_msm_sort.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
+                                          ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32),
+                                          ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)]
+        L.zkpoa_test_msm_density.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                             ctypes.POINTER(ctypes.c_double)]
         L.zkpoa_zkey_load.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong, c_void_pp]
         L.zkpoa_zkey_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.zkpoa_zkey_free.restype = None
@@ -526,6 +536,38 @@ class Context:
         out = ctypes.create_string_buffer(max(1, 4 * out_words * n))
         self._check(lib().zkpoa_fq29_prim(self._h, op, pin, out, n, 1 if raw else 0), "zkpoa_fq29_prim")
         return out.raw[:4 * out_words * n]
+
+    def test_msm_sort(self, scalars, n, c=0, merged=False, for_g2=False, density=None, k0=0, lane=0, caps=None):
+        """zkpoa_test_msm_sort: phase A of one MSM request on host scalars -> a dict with "plan" (the thirteen words of
+        zkpoa_test_msm_plan), "total_entries", "max_count", "total1", and counts, off0, po_a, sorted, pbkt, order,
+        len_hist as bytes of 32-bit words. caps: the seven capacities in words (default: each array's upper bound)."""
+        dens = (ctypes.c_double * 32)(*density) if density is not None else None
+        plan = (ctypes.c_uint64 * 13)()
+        if lib().zkpoa_test_msm_plan(n, c, int(merged), int(for_g2), dens, k0, plan, 13) != 13:
+            raise ZkpoaError("zkpoa_test_msm_plan: arguments out of range")
+        W, TB, K0 = plan[1], plan[4], plan[5]
+        if caps is None:        # every piece holds an entry, every entry is one of the n * W digits
+            caps = [TB, TB + 1, TB + 1, n * W, n * W, n * W, K0 + 1]
+        bufs = [(ctypes.c_uint32 * max(1, k))() for k in caps]
+        out = (ctypes.c_void_p * 7)(*[ctypes.addressof(b) for b in bufs])
+        totals = (ctypes.c_uint32 * 3)()
+        ps, ks = _buf(scalars)
+        rc = lib().zkpoa_test_msm_sort(self._h, lane, ps, n, c, int(merged), int(for_g2), dens, k0, plan, totals, out,
+                                       (ctypes.c_uint64 * 7)(*caps))
+        if rc != PROVER_OK:
+            raise ZkpoaError("zkpoa_test_msm_sort failed (%d)" % rc)
+        sizes = [TB, TB + 1, TB + 1, totals[0], totals[2], totals[2], K0 + 1]
+        res = {"plan": list(plan), "total_entries": totals[0], "max_count": totals[1], "total1": totals[2]}
+        for name, b, k in zip(("counts", "off0", "po_a", "sorted", "pbkt", "order", "len_hist"), bufs, sizes):
+            res[name] = bytes(memoryview(b).cast("B")[:4 * k])
+        return res
+
+    def test_msm_density(self, scalars, n):
+        """zkpoa_test_msm_density: the 32 doubles the prover's density measurement gives for n host scalars."""
+        out = (ctypes.c_double * 32)()
+        ps, ks = _buf(scalars)
+        self._check(lib().zkpoa_test_msm_density(self._h, ps, n, out), "zkpoa_test_msm_density")
+        return list(out)
 
     def ntt_form(self, data, log_n, form, inverse=False, batch=1, stride=None):
         """zkpoa_ntt_form: form 0 = DIF (natural in, bit-reversed out), 1 = DIT (bit-reversed in, natural out), 2 = to the

@@ -52,6 +52,14 @@ void msm_accum_g1(zkpoa_context* ctx, int lane_id, const MsmSorted* sr, bool own
 }
 }  // namespace zkpoa
 
+// the thirteen words the test hooks below report of a plan (and of the request it was made from)
+static void plan_words(const zkpoa::MsmPlan& p, uint64_t w[13]) {
+  using namespace zkpoa;
+  const uint64_t v[13] = {p.c, p.W, p.Wb, p.ne, p.TB, p.K0, p.K, p.logS, p.logRows, p.sparse ? 1u : 0u,
+                          msm_workspace(p.req, kMsmSort), msm_workspace(p.req, kMsmAccumG1), msm_workspace(p.req, kMsmAccumG2)};
+  for (int i = 0; i < 13; i++) w[i] = v[i];
+}
+
 // Test hook, no context, no GPU, no environment variable: the plan of one request and the workspace its parts take.
 // Thirteen words: c, W, Wb, ne, TB, K0, K, logS, logRows; sparse; bytes of the sort, of the G1 and of the G2 accumulation
 // (0 for n == 0). density: null or 32 doubles indexed by the window width. Returns 13 (the first `cap` words are written),
@@ -60,10 +68,60 @@ extern "C" int zkpoa_test_msm_plan(uint64_t n, int c, int merged, int for_g2, co
                                    uint64_t* out, unsigned cap) {
   using namespace zkpoa;
   if (n > (1ull << 28) || c < 0 || c > 31 || (merged | for_g2) >> 1 || k0 < 0 || (!out && cap)) return -1;
-  const MsmRequest req{n, c, merged != 0, for_g2 != 0, density32_or_null, k0};
-  const MsmPlan p = msm_make_plan(req);
-  const uint64_t w[13] = {p.c, p.W, p.Wb, p.ne, p.TB, p.K0, p.K, p.logS, p.logRows, p.sparse ? 1u : 0u,
-                          msm_workspace(req, kMsmSort), msm_workspace(req, kMsmAccumG1), msm_workspace(req, kMsmAccumG2)};
+  const MsmPlan p = msm_make_plan(MsmRequest{n, c, merged != 0, for_g2 != 0, density32_or_null, k0});
+  uint64_t w[13];
+  plan_words(p, w);
   for (unsigned i = 0; i < 13 && i < cap; i++) out[i] = w[i];
   return 13;
+}
+
+// Test hook: phase A of one request on host scalars, through msm_sort_run (the prover's own entry: no second copy of the
+// launch sequence), and what it hands phase B copied back. The arrays are checked against their capacities before any
+// of them is written. len_hist is read AFTER the piece ordering: msm_piece_order_kernel only reads the histogram (its
+// cursors are an array of their own, MsmSortLayout::len_cursor), so these are the words the scan left.
+extern "C" int zkpoa_test_msm_sort(zkpoa_context* ctx, int lane, const void* scalars, uint64_t n, int c, int merged, int for_g2,
+                                   const double* density32_or_null, int k0, uint64_t plan[13], uint32_t totals[3],
+                                   uint32_t* const out[7], const uint64_t cap[7]) {
+  using namespace zkpoa;
+  if (!ctx || lane < 0 || lane >= DeviceCtx::kLanes || n > (1ull << 28) || c < 0 || c > 31 || (merged | for_g2) >> 1 || k0 < 0 ||
+      (n && !scalars) || !plan || !totals || !out || !cap)
+    return PROVER_ERROR;
+  try {
+    ZK_HIP(hipSetDevice(ctx->dev.device));
+    if (lane) ctx->dev.wait_lanes();
+    ctx->dev.ensure_lane(lane);
+    const MsmRequest req{n, c, merged != 0, for_g2 != 0, density32_or_null, k0};
+    DevBuf ds(n * 32);
+    ds.up(scalars, n * 32);
+    const std::unique_ptr<MsmSorted> sr = msm_sort_run(ctx, lane, ds.p, req);   // (synchronised on return)
+    const MsmPlan& p = sr->p;
+    const MsmSortLayout& m = sr->m;
+    plan_words(p, plan);   // of the plan that ran
+    totals[0] = sr->total_entries;
+    totals[1] = sr->max_count;
+    totals[2] = sr->total1;
+    const struct {
+      const uint32_t* d;
+      uint64_t count;
+    } parts[7] = {{m.counts, p.TB},           {m.off0, (uint64_t)p.TB + 1}, {m.po_a, (uint64_t)p.TB + 1}, {m.sorted, sr->total_entries},
+                  {m.pbkt, sr->total1},       {m.order, sr->total1},        {m.len_hist, (uint64_t)p.K0 + 1}};
+    for (int i = 0; i < 7; i++)
+      if (cap[i] < parts[i].count || (parts[i].count && !out[i])) return PROVER_ERROR_SHORT_BUFFER;
+    for (int i = 0; i < 7; i++)
+      if (parts[i].count) ZK_HIP(hipMemcpy(out[i], parts[i].d, parts[i].count * 4, hipMemcpyDeviceToHost));
+  } catch (const std::exception& e) {
+    return PROVER_ERROR;   // last_error is shared between lanes: not touched
+  }
+  return PROVER_OK;
+}
+
+// Test hook: msm_density (the prover's measurement of a witness) on host scalars, on lane 0's stream.
+extern "C" int zkpoa_test_msm_density(zkpoa_context* ctx, const void* scalars, uint64_t n, double out[32]) {
+  using namespace zkpoa;
+  ZK_API_BEGIN(ctx)
+  if (n > (1ull << 28) || (n && !scalars) || !out) throw std::runtime_error("zkpoa_test_msm_density: arguments out of range");
+  DevBuf ds(n * 32), scratch(32 * 8);
+  ds.up(scalars, n * 32);
+  msm_density(ctx->dev.lanes[0].stream, ds.p, n, out, scratch.p);
+  ZK_API_END(ctx)
 }
