@@ -29,6 +29,109 @@ def test_header_symbols_all_exported(zk):
     assert sorted(zk.EXPORTS) == declared
 
 
+def _c_class(decl):
+    """The class of a C parameter or return type as the header spells it: "ptr", "void", "f4", or i / u + size in bytes
+    on LP64. `decl` may carry the parameter's name and `const`."""
+    if "*" in decl or "[" in decl:
+        return "ptr"
+    words = [w for w in re.findall(r"\w+", decl) if w != "const"]
+    for n in (2, 1):                                   # "unsigned long name" before "unsigned name"
+        kind = {"void": "void", "float": "f4", "int": "i4", "long": "i8", "unsigned": "u4", "uint32_t": "u4",
+                "unsigned long": "u8", "uint64_t": "u8"}.get(" ".join(words[:n]))
+        if kind and len(words) - n <= 1:                # what is left is at most the name
+            return kind
+    raise AssertionError("a type the header's vocabulary does not have: %r" % decl)
+
+
+def _ctypes_class(t):
+    if t is None:
+        return "void"
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return "ptr"
+    if t is ctypes.c_float:
+        return "f4"
+    assert t in (ctypes.c_int, ctypes.c_long, ctypes.c_uint, ctypes.c_ulong, ctypes.c_uint32, ctypes.c_uint64), t
+    return ("i" if t in (ctypes.c_int, ctypes.c_long) else "u") + str(ctypes.sizeof(t))
+
+
+def _header_prototypes():
+    """name -> (return class, [parameter classes]) of every prototype of include/zkpoa_prover.h."""
+    text = open(os.path.join(ROOT, "include", "zkpoa_prover.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    protos = {}
+    for ret, name, args in re.findall(r"([\w \t*]+?[\s*])((?:zkpoa|groth16)_\w+)\s*\(([^()]*)\)\s*;", text):
+        assert name not in protos
+        args = [] if args.strip() == "void" else [a.strip() for a in args.split(",")]
+        protos[name] = (_c_class(ret + " ret"), [_c_class(a) for a in args])
+    return protos
+
+
+def test_signatures_match_header(zk):
+    """zk-proof-of-assets_amd/_abi.py's table against the header, parameter by parameter: count and class (pointer,
+    signed / unsigned integer of 4 or 8 bytes, float) of every parameter and of the return value; then that lib() has
+    applied a signature to every symbol of both tables."""
+    from zkpoa_amd import _abi
+    protos = _header_prototypes()
+    assert sorted(protos) == _declared_symbols() and len(protos) == 132
+    wrong = []
+    for name, (ret, params) in protos.items():
+        if name not in _abi.SIGNATURES:
+            wrong.append("%s: no entry in the table" % name)
+            continue
+        restype, argtypes = _abi.signature(_abi.SIGNATURES[name])
+        if _ctypes_class(restype) != ret:
+            wrong.append("%s: returns %s, the table says %s" % (name, ret, _ctypes_class(restype)))
+        if len(argtypes) != len(params):
+            wrong.append("%s: %d parameters, the table has %d" % (name, len(params), len(argtypes)))
+            continue
+        wrong += ["%s: parameter %d is %s, the table says %s" % (name, i, c, _ctypes_class(t))
+                  for i, (c, t) in enumerate(zip(params, argtypes)) if _ctypes_class(t) != c]
+    assert wrong == []
+    assert sorted(_abi.SIGNATURES) == sorted(protos) and not set(_abi.HOOK_SIGNATURES) & set(protos)
+    L = zk.lib()
+    for table in (_abi.SIGNATURES, _abi.HOOK_SIGNATURES):
+        for name, spec in table.items():
+            restype, argtypes = _abi.signature(spec)
+            fn = getattr(L, name)
+            assert fn.argtypes is not None and list(fn.argtypes) == argtypes and fn.restype == restype, name
+
+
+def test_handles_close_once(zk):
+    """The base of MerkleTree, MsmTable and ZKey frees its native handle once however often it is closed, and not at
+    all once its context is gone. A Python stand-in: no library call is involved."""
+    freed = []
+
+    class Ctx:
+        _h = 11
+
+    class Stub(zk._Handle):
+        def __init__(self, ctx):
+            self._ctx, self._h = ctx, 22
+
+        def _free(self, ctx_h, h):
+            freed.append((ctx_h, h))
+
+    ctx = Ctx()
+    h = Stub(ctx)
+    h.close()
+    h.close()
+    del h
+    assert freed == [(11, 22)]
+    h = Stub(ctx)
+    del h                                   # never closed: __del__ frees it
+    assert freed == [(11, 22)] * 2
+    h = Stub(ctx)
+    ctx._h = None                           # Context.close() leaves this behind
+    h.close()
+    assert h._h is None
+    h.close()
+    del h
+    assert freed == [(11, 22)] * 2
+    for cls in (zk.MerkleTree, zk.MsmTable, zk.ZKey):
+        assert issubclass(cls, zk._Handle) and "close" not in vars(cls) and "__del__" not in vars(cls)
+
+
 def test_host_only_group_helpers(zk):
     G = g16.g1_to_bytes(bn.G1_GEN)
     assert g16.g1_from_bytes(zk.g1_mul(G, 123456789)) == bn.g1_mul(bn.G1_GEN, 123456789)
@@ -209,7 +312,6 @@ def test_automatic_gpu_choice_of_the_multi_gpu_drop_in(zk):
     import ctypes
     L = zk.lib()
     f = L.zkpoa_test_auto_pick_devices
-    f.argtypes = [ctypes.c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_ulong, ctypes.c_uint, ctypes.POINTER(ctypes.c_int)]
 
     def pick(count, power, pid, busy=0, min_power=24):
         out = (ctypes.c_int * 8)()
@@ -237,8 +339,6 @@ def test_block_size_of_the_block_cyclic_shards(zk):
     items, fewer for small keys so that every rank still holds at least eight blocks, never fewer than 2^4."""
     import ctypes
     f = zk.lib().zkpoa_test_multi_block_log
-    f.argtypes = [ctypes.c_uint64, ctypes.c_uint]
-    f.restype = ctypes.c_uint
     # the reference's shapes: layer one (2.08 M wires: 31 blocks of 2^16), two (21.4 M), three (52.4 M)
     assert [f(2083343, g) for g in (1, 2, 4, 8)] == [16, 16, 15, 14]
     assert [f(21356921, g) for g in (1, 2, 4, 8)] == [16] * 4 and [f(52367163, g) for g in (2, 4, 8)] == [16] * 3

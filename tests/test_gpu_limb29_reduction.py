@@ -152,9 +152,6 @@ K0 = 8          # the smallest piece length the option accepts
 
 def msm_plan(zk, n, c, k0, merged=0):
     f = zk.lib().zkpoa_test_msm_plan
-    f.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
-                  ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint]
-    f.restype = ctypes.c_int
     out = (ctypes.c_uint64 * 13)()
     assert f(n, c, merged, 0, None, k0, out, 13) == 13
     return dict(zip(("c", "W", "Wb", "ne", "TB", "K0", "K", "logS", "logRows"), out))

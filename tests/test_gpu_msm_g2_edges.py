@@ -25,9 +25,6 @@ SIZE = 128
 
 def msm_plan(zk, n, c, k0, merged=0):
     f = zk.lib().zkpoa_test_msm_plan
-    f.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
-                  ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint]
-    f.restype = ctypes.c_int
     out = (ctypes.c_uint64 * 13)()
     assert f(n, c, merged, 1, None, k0, out, 13) == 13                 # for_g2 = 1: the request a G2 MSM makes
     return dict(zip(("c", "W", "Wb", "ne", "TB", "K0", "K", "logS", "logRows"), out))

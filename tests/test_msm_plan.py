@@ -32,9 +32,6 @@ def golden():
 @pytest.fixture(scope="module")
 def plan(zk):
     f = zk.lib().zkpoa_test_msm_plan
-    f.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
-                  ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint]
-    f.restype = ctypes.c_int
     dens = {kind: density(kind) for kind in ("none", "bits", "limbs64", "uniform")}
 
     def call(n, c, for_g2, merged, kind, k0=0, cap=13):

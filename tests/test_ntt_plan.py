@@ -22,8 +22,6 @@ def golden():
 @pytest.fixture(scope="module")
 def plan(zk):
     f = zk.lib().zkpoa_test_ntt_plan
-    f.argtypes = [ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint]
-    f.restype = ctypes.c_int
 
     def call(k, tile_log, cap=7 * 8):
         out = (ctypes.c_uint32 * max(cap, 1))()

@@ -24,8 +24,6 @@ def child(path, nbytes):
     z = load_package()
     ctx = z.Context(0)
     L = z.lib()
-    L.zkpoa_test_upload.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
-                                    ctypes.POINTER(ctypes.c_float)]
     dst = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
     ms = ctypes.c_float(0)
 

@@ -13,18 +13,17 @@ is usable, calls raise. (The directory name has a hyphen, so the package is load
 import ctypes
 import os
 
+from ._abi import (EXPORTS, LIB_PATH, PROVER_ERROR, PROVER_ERROR_RUNTIME, PROVER_ERROR_SHORT_BUFFER,  # noqa: F401
+                   PROVER_INVALID_WITNESS_LENGTH, PROVER_OK, ZkpoaError, _buf, _name, _Out, _replace_file, _scalar,
+                   _sized, lib)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libzkpoa_prover.so")
 PROVER_BIN = os.path.join(_HERE, "prover")
 MERKLE_BIN = os.path.join(_HERE, "merkle-tree")
 SIGS_BIN = os.path.join(_HERE, "ecdsa-sigs-parser")
 SETUP_BIN = os.path.join(_HERE, "zkpoa-setup")
-
-PROVER_OK = 0
-PROVER_ERROR = 1
-PROVER_ERROR_SHORT_BUFFER = 2
-PROVER_INVALID_WITNESS_LENGTH = 3
-PROVER_ERROR_RUNTIME = 4
+VERIFY_BIN = os.path.join(_HERE, "zkpoa-verify")
+SANITIZE_BIN = os.path.join(_HERE, "zkpoa-sanitize")
 
 # the bits of zkpoa_zkey_verify's result (include/zkpoa_prover.h ZKPOA_ZKEY_*)
 ZKEY_CHECKS = {"HEADER": 0x01, "POINTS": 0x02, "DELTA": 0x04, "COEFFS": 0x08, "A": 0x10, "B1": 0x20, "B2": 0x40,
@@ -35,282 +34,10 @@ PTAU_CHECKS = {"POINTS": 0x001, "TAU_G1": 0x002, "TAU_G2": 0x004, "ALPHA": 0x008
                "LAGRANGE_TAU_G1": 0x020, "LAGRANGE_TAU_G2": 0x040, "LAGRANGE_ALPHA": 0x080, "LAGRANGE_BETA": 0x100,
                "CONTRIBUTIONS": 0x200}
 
-# every symbol include/zkpoa_prover.h declares
-EXPORTS = [
-    "groth16_prover", "groth16_prover_zkey_file",
-    "zkpoa_context_create", "zkpoa_context_destroy", "zkpoa_last_error",
-    "zkpoa_zkey_load", "zkpoa_zkey_free", "zkpoa_zkey_info", "zkpoa_prove",
-    "zkpoa_zkey_load_device", "zkpoa_zkey_load_device_shard", "zkpoa_prove_device", "zkpoa_setup_accumulate", "zkpoa_zkey_new", "zkpoa_zkey_contribute", "zkpoa_wtns_check", "zkpoa_zkey_verify", "zkpoa_ptau_verify",
-    "zkpoa_ec_intt_device", "zkpoa_ptau_prepare_phase2",
-    "zkpoa_groth16_prover_files", "zkpoa_set_thread_options", "zkpoa_clear_thread_options", "zkpoa_idle_work", "zkpoa_zkey_load_shard", "zkpoa_zkey_load_shard_ex", "zkpoa_zkey_set_shard", "zkpoa_zkey_header",
-    "zkpoa_prove_partials", "zkpoa_prove_partials_device", "zkpoa_prove_assemble",
-    "zkpoa_zkey_load_shard_split", "zkpoa_zkey_set_shard_split", "zkpoa_witness_load",
-    "zkpoa_split_stage1", "zkpoa_split_stage2", "zkpoa_split_stage3",
-    "zkpoa_proof_to_json", "zkpoa_public_to_json",
-    "zkpoa_msm_g1", "zkpoa_msm_g2", "zkpoa_ntt", "zkpoa_h_scalars",
-    "zkpoa_msm_g1_device", "zkpoa_msm_g2_device", "zkpoa_ntt_device",
-    "zkpoa_msm_g1_device_lane", "zkpoa_last_ms_lane",
-    "zkpoa_gen_bases_g1_device", "zkpoa_gen_bases_g2_device",
-    "zkpoa_g1_sum", "zkpoa_g2_sum", "zkpoa_g1_mul", "zkpoa_g2_mul",
-    "zkpoa_setup_defer_host_frees", "zkpoa_last_ms", "zkpoa_set_option", "zkpoa_msm_points_limit", "zkpoa_field_op", "zkpoa_group_add",
-    "zkpoa_field_prim", "zkpoa_curve_prim", "zkpoa_fq29_prim", "zkpoa_ntt_form", "zkpoa_test_ntt_plan", "zkpoa_test_msm_plan",
-    "zkpoa_test_msm_sort", "zkpoa_test_msm_density",
-    "zkpoa_groth16_verify", "zkpoa_sanitize_proof", "zkpoa_groth16_verify_points", "zkpoa_zkey_vkey", "zkpoa_zkey_export_vkey",
-    "zkpoa_zkey_read_h_scalars", "zkpoa_zkey_precompute",
-    "zkpoa_context_stream", "zkpoa_context_synchronize",
-    "zkpoa_poseidon_params", "zkpoa_poseidon2", "zkpoa_poseidon2_device", "zkpoa_merkle_build", "zkpoa_merkle_build_device", "zkpoa_merkle_free",
-    "zkpoa_merkle_info", "zkpoa_merkle_root", "zkpoa_merkle_leaves", "zkpoa_merkle_path",
-    "zkpoa_msm_table_build", "zkpoa_msm_table_free", "zkpoa_msm_table_info", "zkpoa_msm_table_run_lane",
-    "zkpoa_zkey_new_ex", "zkpoa_zkey_contribute_ex", "zkpoa_zkey_beacon", "zkpoa_zkey_contributions",
-    "zkpoa_hash_form", "zkpoa_h_diff",
-    "zkpoa_blake2b512", "zkpoa_blake2b_new", "zkpoa_blake2b_update", "zkpoa_blake2b_final", "zkpoa_sha256",
-    "zkpoa_chacha_new", "zkpoa_chacha_next_u32", "zkpoa_chacha_next_u64", "zkpoa_chacha_next_bool", "zkpoa_chacha_free",
-    "zkpoa_fq_sqrt", "zkpoa_fq2_sqrt", "zkpoa_fr_from_rng", "zkpoa_g1_from_rng", "zkpoa_g2_from_rng", "zkpoa_hash_to_g2",
-    "zkpoa_beacon_key",
-    "zkpoa_scalar_mul_each_device", "zkpoa_power_scalars_device", "zkpoa_compressed_form",
-    "zkpoa_ptau_new", "zkpoa_ptau_contribute", "zkpoa_ptau_beacon", "zkpoa_ptau_contributions",
-    "zkpoa_blake2b_state", "zkpoa_blake2b_restore",
-    "zkpoa_sqrt_device", "zkpoa_decompressed_form", "zkpoa_from_hash_form",
-    "zkpoa_ptau_export_challenge", "zkpoa_ptau_challenge_contribute", "zkpoa_ptau_import_response",
-    "zkpoa_ecdsa_star", "zkpoa_keccak256", "zkpoa_eth_address",
-]
-
-
-class ZkpoaError(RuntimeError):
-    pass
-
 
 def shard_flags(split=False, block_log=0):
     """include/zkpoa_prover.h: ZKPOA_SHARD_SPLIT_CHAIN | ZKPOA_SHARD_BLOCK_CYCLIC(block_log)."""
     return (1 if split else 0) | ((int(block_log) & 0xff) << 8)
-
-
-_lib = None
-
-
-def lib():
-    """The loaded shared library; raises loudly when it has not been built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ZkpoaError("libzkpoa_prover.so not built (%s): run `python -c 'import __graft_entry__ as g; "
-                             "g.build()'` -- there is no CPU fallback" % LIB_PATH)
-        # PyTorch-ROCm wheels bundle their own libamdhip64 / libhsa-runtime64. If our library (linked
-        # against /opt/rocm) is loaded first, torch's HSA copy later fails to open the device ("No HIP GPUs
-        # are available"); loaded in this order both HIP runtimes share torch's HSA runtime (same SONAME).
-        try:
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        L = ctypes.CDLL(LIB_PATH)
-        c_void_pp = ctypes.POINTER(ctypes.c_void_p)
-        ul_p = ctypes.POINTER(ctypes.c_ulong)
-        L.zkpoa_context_create.argtypes = [ctypes.c_int, c_void_pp, ctypes.c_char_p, ctypes.c_ulong]
-        L.zkpoa_context_destroy.argtypes = [ctypes.c_void_p]
-        L.zkpoa_context_destroy.restype = None
-        L.zkpoa_context_stream.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        L.zkpoa_context_stream.restype = ctypes.c_void_p
-        L.zkpoa_context_synchronize.argtypes = [ctypes.c_void_p]
-        for name in ("zkpoa_poseidon2", "zkpoa_poseidon2_device"):
-            getattr(L, name).argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
-        for name in ("zkpoa_merkle_build", "zkpoa_merkle_build_device"):
-            getattr(L, name).argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, c_void_pp]
-        L.zkpoa_merkle_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        L.zkpoa_merkle_free.restype = None
-        L.zkpoa_merkle_info.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
-        L.zkpoa_merkle_root.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        L.zkpoa_merkle_leaves.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
-        L.zkpoa_merkle_path.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
-        L.zkpoa_ecdsa_star.argtypes = [ctypes.c_void_p, ctypes.c_uint64] + [ctypes.c_void_p] * 9
-        L.zkpoa_keccak256.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
-        L.zkpoa_eth_address.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
-        L.zkpoa_last_error.argtypes = [ctypes.c_void_p]
-        L.zkpoa_last_error.restype = ctypes.c_char_p
-        L.zkpoa_last_ms.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        L.zkpoa_last_ms.restype = ctypes.c_float
-        L.zkpoa_set_option.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_long]
-        L.zkpoa_msm_points_limit.argtypes = [ctypes.c_void_p]
-        L.zkpoa_msm_points_limit.restype = ctypes.c_uint64
-        for name in ("zkpoa_msm_g1", "zkpoa_msm_g2", "zkpoa_msm_g1_device", "zkpoa_msm_g2_device"):
-            getattr(L, name).argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
-                                         ctypes.c_void_p]
-        L.zkpoa_msm_g1_device_lane.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                               ctypes.c_uint64, ctypes.c_void_p]
-        L.zkpoa_last_ms_lane.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
-        L.zkpoa_last_ms_lane.restype = ctypes.c_float
-        L.zkpoa_ntt.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_int]
-        L.zkpoa_ntt_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_int]
-        L.zkpoa_h_scalars.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p,
-                                      ctypes.c_uint64, ctypes.c_uint, ctypes.c_void_p]
-        for name in ("zkpoa_gen_bases_g1_device", "zkpoa_gen_bases_g2_device"):
-            getattr(L, name).argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint64,
-                                         ctypes.c_uint64, ctypes.c_void_p]
-        for name in ("zkpoa_g1_sum", "zkpoa_g2_sum"):
-            getattr(L, name).argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
-        for name in ("zkpoa_g1_mul", "zkpoa_g2_mul"):
-            getattr(L, name).argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p]
-        L.zkpoa_field_op.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                     ctypes.c_void_p, ctypes.c_uint64]
-        L.zkpoa_group_add.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                      ctypes.c_void_p, ctypes.c_uint64]
-        L.zkpoa_field_prim.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                       ctypes.c_uint64, ctypes.c_int]
-        L.zkpoa_curve_prim.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
-        L.zkpoa_fq29_prim.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
-                                      ctypes.c_int]
-        L.zkpoa_ntt_form.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_int, ctypes.c_int,
-                                     ctypes.c_uint, ctypes.c_uint64]
-        L.zkpoa_test_msm_plan.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                          ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.POINTER(ctypes.c_uint64),
-                                          ctypes.c_uint]
-        L.zkpoa_test_msm_sort.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
-                                          ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
-                                          ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32),
-                                          ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)]
-        L.zkpoa_test_msm_density.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
-                                             ctypes.POINTER(ctypes.c_double)]
-        L.zkpoa_zkey_load.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong, c_void_pp]
-        L.zkpoa_zkey_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        L.zkpoa_zkey_free.restype = None
-        L.zkpoa_zkey_info.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
-        L.zkpoa_prove.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong,
-                                  ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong]
-        L.zkpoa_zkey_load_device.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint] + \
-            [ctypes.c_void_p] * 6 + [ctypes.c_uint64, ctypes.c_char_p, c_void_pp]
-        L.zkpoa_setup_accumulate.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
-                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
-                                             ctypes.c_uint64, ctypes.c_void_p]
-        L.zkpoa_zkey_new.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
-        L.zkpoa_zkey_new_ex.argtypes = L.zkpoa_zkey_new.argtypes + [ctypes.c_uint32]
-        L.zkpoa_zkey_contribute_ex.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
-                                               ctypes.c_char_p]
-        L.zkpoa_zkey_beacon.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_ulong,
-                                        ctypes.c_uint32, ctypes.c_char_p]
-        L.zkpoa_zkey_contributions.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int),
-                                               ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p, ctypes.c_ulong]
-        L.zkpoa_hash_form.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64,
-                                      ctypes.c_void_p, ctypes.c_char_p]
-        L.zkpoa_compressed_form.argtypes = L.zkpoa_hash_form.argtypes
-        L.zkpoa_scalar_mul_each_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_uint64, ctypes.c_void_p]
-        L.zkpoa_power_scalars_device.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint64,
-                                                 ctypes.c_uint64, ctypes.c_void_p]
-        L.zkpoa_ptau_new.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_char_p]
-        L.zkpoa_ptau_contribute.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
-                                            ctypes.c_char_p]
-        L.zkpoa_ptau_beacon.argtypes = L.zkpoa_zkey_beacon.argtypes
-        L.zkpoa_ptau_contributions.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p,
-                                               ctypes.c_ulong]
-        L.zkpoa_sqrt_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_void_p,
-                                        ctypes.c_void_p]
-        for f in (L.zkpoa_decompressed_form, L.zkpoa_from_hash_form):
-            f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
-        L.zkpoa_ptau_export_challenge.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
-        L.zkpoa_ptau_challenge_contribute.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
-                                                      ctypes.c_char_p]
-        L.zkpoa_ptau_import_response.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
-                                                 ctypes.c_char_p]
-        L.zkpoa_blake2b_state.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
-        L.zkpoa_blake2b_restore.argtypes = [ctypes.c_char_p]
-        L.zkpoa_blake2b_restore.restype = ctypes.c_void_p
-        L.zkpoa_h_diff.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
-        L.zkpoa_blake2b512.argtypes = [ctypes.c_char_p, ctypes.c_ulong, ctypes.c_char_p]
-        L.zkpoa_blake2b_new.restype = ctypes.c_void_p
-        L.zkpoa_blake2b_update.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_ulong]
-        L.zkpoa_blake2b_final.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
-        L.zkpoa_sha256.argtypes = [ctypes.c_char_p, ctypes.c_ulong, ctypes.c_char_p]
-        key_t = ctypes.POINTER(ctypes.c_uint32)
-        L.zkpoa_chacha_new.argtypes = [key_t]
-        L.zkpoa_chacha_new.restype = ctypes.c_void_p
-        L.zkpoa_chacha_next_u32.argtypes = [ctypes.c_void_p]
-        L.zkpoa_chacha_next_u32.restype = ctypes.c_uint32
-        L.zkpoa_chacha_next_u64.argtypes = [ctypes.c_void_p]
-        L.zkpoa_chacha_next_u64.restype = ctypes.c_uint64
-        L.zkpoa_chacha_next_bool.argtypes = [ctypes.c_void_p]
-        L.zkpoa_chacha_free.argtypes = [ctypes.c_void_p]
-        L.zkpoa_chacha_free.restype = None
-        L.zkpoa_fq_sqrt.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
-        L.zkpoa_fq2_sqrt.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
-        for f in (L.zkpoa_fr_from_rng, L.zkpoa_g1_from_rng, L.zkpoa_g2_from_rng):
-            f.argtypes = [key_t, ctypes.c_char_p]
-        L.zkpoa_hash_to_g2.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
-        L.zkpoa_beacon_key.argtypes = [ctypes.c_char_p, ctypes.c_ulong, ctypes.c_uint32, key_t]
-        L.zkpoa_wtns_check.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p,
-                                       ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
-        L.zkpoa_zkey_contribute.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
-        L.zkpoa_zkey_verify.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
-                                        ctypes.POINTER(ctypes.c_uint32)]
-        L.zkpoa_ptau_verify.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32),
-                                        ctypes.POINTER(ctypes.c_uint32)]
-        L.zkpoa_ec_intt_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
-        L.zkpoa_ptau_prepare_phase2.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p,
-                                                ctypes.POINTER(ctypes.c_uint32)]
-        L.zkpoa_zkey_load_device_shard.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint,
-                                                   ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int] + \
-            [ctypes.c_void_p] * 6 + [ctypes.c_uint64, ctypes.c_char_p, c_void_pp]
-        L.zkpoa_prove_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p,
-                                         ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong]
-        L.zkpoa_zkey_load_shard_ex.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong, ctypes.c_uint64,
-                                               ctypes.c_uint64, ctypes.c_int, c_void_pp]
-        L.zkpoa_zkey_load_shard.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong, ctypes.c_uint64,
-                                            ctypes.c_uint64, c_void_pp]
-        L.zkpoa_zkey_set_shard.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]
-        L.zkpoa_zkey_load_shard_split.argtypes = L.zkpoa_zkey_load_shard.argtypes
-        L.zkpoa_zkey_set_shard_split.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]
-        L.zkpoa_witness_load.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong,
-                                         ctypes.c_void_p, ctypes.c_ulong]
-        L.zkpoa_split_stage1.argtypes = [ctypes.c_void_p] * 4
-        L.zkpoa_split_stage2.argtypes = [ctypes.c_void_p] * 4
-        L.zkpoa_split_stage3.argtypes = [ctypes.c_void_p] * 3
-        L.zkpoa_zkey_header.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        L.zkpoa_prove_partials.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong,
-                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong]
-        L.zkpoa_prove_partials_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        L.zkpoa_prove_assemble.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
-                                           ctypes.c_void_p]
-        L.zkpoa_groth16_verify.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p,
-                                           ctypes.c_ulong]
-        L.zkpoa_sanitize_proof.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p, ul_p,
-                                           ctypes.c_void_p, ctypes.c_ulong]
-        L.zkpoa_groth16_verify_points.argtypes = [ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.c_ulong, ctypes.c_void_p, ctypes.c_ulong]
-        L.zkpoa_zkey_vkey.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ul_p]
-        L.zkpoa_zkey_precompute.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
-                                            ctypes.POINTER(ctypes.c_uint64)]
-        L.zkpoa_msm_table_build.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
-                                            c_void_pp]
-        L.zkpoa_msm_table_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        L.zkpoa_msm_table_free.restype = None
-        L.zkpoa_msm_table_info.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
-        L.zkpoa_msm_table_run_lane.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                               ctypes.c_void_p]
-        L.zkpoa_zkey_read_h_scalars.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong]
-        L.zkpoa_proof_to_json.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ul_p]
-        L.zkpoa_public_to_json.argtypes = [ctypes.c_void_p, ctypes.c_ulong, ctypes.c_int, ctypes.c_void_p, ul_p]
-        L.groth16_prover.argtypes = [ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p, ctypes.c_ulong,
-                                     ctypes.c_void_p, ul_p, ctypes.c_void_p, ul_p, ctypes.c_void_p, ctypes.c_ulong]
-        L.groth16_prover_zkey_file.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_ulong,
-                                               ctypes.c_void_p, ul_p, ctypes.c_void_p, ul_p, ctypes.c_void_p,
-                                               ctypes.c_ulong]
-        _lib = L
-    return _lib
-
-
-def _buf(b):
-    """read-only bytes-like -> (ctypes pointer, keepalive); no copy (a 2^20 MSM hands over 96 MiB per call)."""
-    if isinstance(b, bytes):
-        return ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p), b
-    if isinstance(b, bytearray):
-        arr = (ctypes.c_char * len(b)).from_buffer(b)
-        return ctypes.cast(arr, ctypes.c_void_p), arr
-    # numpy array or anything exposing the buffer protocol
-    mv = memoryview(b)
-    if mv.readonly:
-        raw = mv.tobytes()
-        return ctypes.cast(ctypes.c_char_p(raw), ctypes.c_void_p), raw
-    arr = (ctypes.c_char * mv.nbytes).from_buffer(b)
-    return ctypes.cast(arr, ctypes.c_void_p), arr
 
 
 class Context:
@@ -415,9 +142,9 @@ class Context:
         n = len(left) // 32
         pl, kl = _buf(left)
         pr, kr = _buf(right)
-        out = ctypes.create_string_buffer(max(1, 32 * n))
+        out = _Out(32 * n)
         self._check(lib().zkpoa_poseidon2(self._h, pl, pr, n, out), "zkpoa_poseidon2")
-        return out.raw[:32 * n]
+        return out.bytes()
 
     def poseidon2_device(self, d_left, d_right, n, d_out):
         self._check(lib().zkpoa_poseidon2_device(self._h, d_left, d_right, n, d_out), "zkpoa_poseidon2_device")
@@ -430,9 +157,9 @@ class Context:
         if len(r) != 32 * n or len(s) != 32 * n or len(msghash) != 32 * n or len(addresses) != 20 * n:
             raise ZkpoaError("ecdsa_star: the arrays do not describe %d signatures" % n)
         bufs = [_buf(bytes(x)) for x in (r, s, msghash, v, addresses)]
-        outs = [ctypes.create_string_buffer(max(1, k * n)) for k in (32, 64, 20, 1)]
+        outs = [_Out(k * n) for k in (32, 64, 20, 1)]
         self._check(lib().zkpoa_ecdsa_star(self._h, n, *([b[0] for b in bufs] + outs)), "zkpoa_ecdsa_star")
-        return tuple(o.raw[:k * n] for o, k in zip(outs, (32, 64, 20, 1)))
+        return tuple(o.bytes() for o in outs)
 
     def keccak256(self, messages, length):
         """Keccak-256 of len(messages) / length messages of `length` bytes packed back to back (length 0: pass n)."""
@@ -441,19 +168,18 @@ class Context:
         else:
             n, data = int(messages), b""
         pm, km = _buf(data)
-        out = ctypes.create_string_buffer(max(1, 32 * n))
+        out = _Out(32 * n)
         self._check(lib().zkpoa_keccak256(self._h, pm, length, n, out), "zkpoa_keccak256")
-        return out.raw[:32 * n]
+        return out.bytes()
 
     def eth_address(self, pubkeys):
         """ethers.computeAddress for n x 64 B keys (x || y big-endian) -> (n x 20 B, list of n EIP-55 strings)."""
         n = len(pubkeys) // 64
         pk, kk = _buf(bytes(pubkeys))
-        addr = ctypes.create_string_buffer(max(1, 20 * n))
-        text = ctypes.create_string_buffer(max(1, 42 * n))
+        addr, text = _Out(20 * n), _Out(42 * n)
         self._check(lib().zkpoa_eth_address(self._h, pk, n, addr, text), "zkpoa_eth_address")
-        chars = text.raw[:42 * n].decode()   # .raw copies the whole buffer: once, not per key
-        return addr.raw[:20 * n], [chars[42 * i:42 * i + 42] for i in range(n)]
+        chars = text.bytes().decode()        # bytes() copies the whole buffer: once, not per key
+        return addr.bytes(), [chars[42 * i:42 * i + 42] for i in range(n)]
 
     def merkle_build(self, addresses, balances, device=False, n=None):
         """Tree over (address, balance) pairs: host buffers (n x 32 B LE each) or, with device=True, device pointers."""
@@ -479,13 +205,11 @@ class Context:
         self._check(lib().zkpoa_ntt_device(self._h, d_data, log_n, 1 if inverse else 0), "zkpoa_ntt_device")
 
     def gen_bases_g1_device(self, a, b, i0, n, d_out):
-        self._check(lib().zkpoa_gen_bases_g1_device(self._h, int(a).to_bytes(32, "little"),
-                                                    int(b).to_bytes(32, "little"), i0, n, d_out),
+        self._check(lib().zkpoa_gen_bases_g1_device(self._h, _scalar(a), _scalar(b), i0, n, d_out),
                     "zkpoa_gen_bases_g1_device")
 
     def gen_bases_g2_device(self, a, b, i0, n, d_out):
-        self._check(lib().zkpoa_gen_bases_g2_device(self._h, int(a).to_bytes(32, "little"),
-                                                    int(b).to_bytes(32, "little"), i0, n, d_out),
+        self._check(lib().zkpoa_gen_bases_g2_device(self._h, _scalar(a), _scalar(b), i0, n, d_out),
                     "zkpoa_gen_bases_g2_device")
 
     # ---- element-wise hooks ------------------------------------------------------------------
@@ -493,18 +217,18 @@ class Context:
         n = len(a) // 32
         pa, ka = _buf(a)
         pb, kb = _buf(b) if b is not None else (None, None)
-        out = ctypes.create_string_buffer(max(1, 32 * n))
+        out = _Out(32 * n)
         self._check(lib().zkpoa_field_op(self._h, field, op, pa, pb, out, n), "zkpoa_field_op")
-        return out.raw[:32 * n]
+        return out.bytes()
 
     def group_add(self, group, a, b):
         size = 64 if group == 1 else 128
         n = len(a) // size
         pa, ka = _buf(a)
         pb, kb = _buf(b)
-        out = ctypes.create_string_buffer(max(1, size * n))
+        out = _Out(size * n)
         self._check(lib().zkpoa_group_add(self._h, group, pa, pb, out, n), "zkpoa_group_add")
-        return out.raw[:size * n]
+        return out.bytes()
 
     def field_prim(self, field, op, operands, n_out=1, raw=True):
         """zkpoa_field_prim: `operands` is the list of the op's operand arrays (n elements each, 32 B or 64 B for
@@ -513,9 +237,10 @@ class Context:
         n = len(operands[0]) // size if operands else 0
         assert all(len(x) == n * size for x in operands)
         pin, kin = _buf(b"".join(operands))
-        out = ctypes.create_string_buffer(max(1, size * n * n_out))
+        out = _Out(size * n * n_out)
         self._check(lib().zkpoa_field_prim(self._h, field, op, pin, out, n, 1 if raw else 0), "zkpoa_field_prim")
-        return [out.raw[size * n * j:size * n * (j + 1)] for j in range(n_out)]
+        res = out.bytes()
+        return [res[size * n * j:size * n * (j + 1)] for j in range(n_out)]
 
     def curve_prim(self, group, op, a=None, b=None, k=None, n=None):
         """zkpoa_curve_prim: a, b as the op takes them (XYZZ / affine bytes), k a sequence of u32; returns n XYZZ."""
@@ -525,17 +250,17 @@ class Context:
         pa, ka = _buf(a) if a is not None else (None, None)
         pb, kb = _buf(b) if b is not None else (None, None)
         pk, kk = _buf(b"".join(int(v).to_bytes(4, "little") for v in k)) if k is not None else (None, None)
-        out = ctypes.create_string_buffer(max(1, 4 * fb * n))
+        out = _Out(4 * fb * n)
         self._check(lib().zkpoa_curve_prim(self._h, group, op, pa, pb, pk, out, n), "zkpoa_curve_prim")
-        return out.raw[:4 * fb * n]
+        return out.bytes()
 
     def fq29_prim(self, op, data, n, out_words, raw=True):
         """zkpoa_fq29_prim: `data` holds the n records of the op (32-bit words, little-endian); returns the n result
         records of `out_words` words each, as bytes."""
         pin, kin = _buf(data)
-        out = ctypes.create_string_buffer(max(1, 4 * out_words * n))
+        out = _Out(4 * out_words * n)
         self._check(lib().zkpoa_fq29_prim(self._h, op, pin, out, n, 1 if raw else 0), "zkpoa_fq29_prim")
-        return out.raw[:4 * out_words * n]
+        return out.bytes()
 
     def test_msm_sort(self, scalars, n, c=0, merged=False, for_g2=False, density=None, k0=0, lane=0, caps=None):
         """zkpoa_test_msm_sort: phase A of one MSM request on host scalars -> a dict with "plan" (the thirteen words of
@@ -588,13 +313,8 @@ class Context:
     def load_zkey_device(self, n_vars, n_public, log_domain, d_A, d_B1, d_B2, d_C, d_H, d_coefs, n_coefs,
                          header_points):
         """Proving key from device-resident sections (device pointers as ints); the caller keeps them alive."""
-        key = ZKey.__new__(ZKey)
-        key._ctx = self
-        key._h = ctypes.c_void_p()
-        self._check(lib().zkpoa_zkey_load_device(self._h, n_vars, n_public, log_domain, d_A, d_B1, d_B2, d_C, d_H,
-                                                 d_coefs, n_coefs, bytes(header_points), ctypes.byref(key._h)),
-                    "zkpoa_zkey_load_device")
-        return key
+        return ZKey._adopt(self, lib().zkpoa_zkey_load_device, n_vars, n_public, log_domain, d_A, d_B1, d_B2, d_C, d_H,
+                           d_coefs, n_coefs, bytes(header_points))
 
     def setup_accumulate(self, group, d_points, n_points, d_coefs, d_point_index, d_signal, nnz, n_signals, d_out):
         """out[s] = sum of coefs[e] * points[point_index[e]] over the entries of signal s (device pointers as ints):
@@ -647,9 +367,8 @@ class Context:
 
     def zkey_contribute(self, zkey_in_path, zkey_out_path, delta=None):
         """The arithmetic of `snarkjs zkey contribute` (delta: int in [1, r), None = random)."""
-        d = None if delta is None else int(delta).to_bytes(32, "little")
-        self._check(lib().zkpoa_zkey_contribute(self._h, os.fsencode(zkey_in_path), os.fsencode(zkey_out_path), d),
-                    "zkpoa_zkey_contribute")
+        self._check(lib().zkpoa_zkey_contribute(self._h, os.fsencode(zkey_in_path), os.fsencode(zkey_out_path),
+                                                _scalar(delta)), "zkpoa_zkey_contribute")
 
     def zkey_new_ex(self, r1cs_path, ptau_path, zkey_path, flags=SETUP_TRANSCRIPT):
         """`zkey new` with section 10's circuit hash filled in (include/zkpoa_prover.h: zkpoa_zkey_new_ex)."""
@@ -658,32 +377,30 @@ class Context:
 
     def zkey_contribute_ex(self, zkey_in_path, zkey_out_path, delta=None, name=None):
         """`zkey contribute` on a key with a transcript: the arithmetic and a contribution record."""
-        d = None if delta is None else int(delta).to_bytes(32, "little")
-        self._check(lib().zkpoa_zkey_contribute_ex(self._h, os.fsencode(zkey_in_path), os.fsencode(zkey_out_path), d,
-                                                   None if name is None else name.encode()), "zkpoa_zkey_contribute_ex")
+        self._check(lib().zkpoa_zkey_contribute_ex(self._h, os.fsencode(zkey_in_path), os.fsencode(zkey_out_path),
+                                                   _scalar(delta), _name(name)), "zkpoa_zkey_contribute_ex")
 
     def zkey_beacon(self, zkey_in_path, zkey_out_path, beacon, num_iterations_exp, name=None):
         """`snarkjs zkey beacon`: beacon bytes, 2^num_iterations_exp SHA-256 iterations (at most 2^30)."""
         self._check(lib().zkpoa_zkey_beacon(self._h, os.fsencode(zkey_in_path), os.fsencode(zkey_out_path), bytes(beacon),
-                                            len(beacon), num_iterations_exp, None if name is None else name.encode()),
-                    "zkpoa_zkey_beacon")
+                                            len(beacon), num_iterations_exp, _name(name)), "zkpoa_zkey_beacon")
 
     def hash_form(self, group, points, piece_points=0):
         """Hash form of wire-form points, converted on the device in pieces: -> (bytes, Blake2b-512 digest)."""
         unit = 64 if group == 1 else 128
         n = len(points) // unit
-        out, dg = ctypes.create_string_buffer(max(1, n * unit)), ctypes.create_string_buffer(64)
+        out, dg = _Out(n * unit), ctypes.create_string_buffer(64)
         self._check(lib().zkpoa_hash_form(self._h, group, bytes(points), n, piece_points, out, dg), "zkpoa_hash_form")
-        return out.raw[:n * unit], dg.raw
+        return out.bytes(), dg.raw
 
     def compressed_form(self, group, points, piece_points=0):
         """Compressed form of wire-form points, converted on the device in pieces: -> (bytes, Blake2b-512 digest)."""
         unit = 64 if group == 1 else 128
         n = len(points) // unit
-        out, dg = ctypes.create_string_buffer(max(1, n * unit // 2)), ctypes.create_string_buffer(64)
+        out, dg = _Out(n * unit // 2), ctypes.create_string_buffer(64)
         self._check(lib().zkpoa_compressed_form(self._h, group, bytes(points), n, piece_points, out, dg),
                     "zkpoa_compressed_form")
-        return out.raw[:n * unit // 2], dg.raw
+        return out.bytes(), dg.raw
 
     def scalar_mul_each(self, group, d_points, d_scalars, n, d_out):
         """d_out[i] = k_i * P_i over n points of G1 (group 1) or G2 (2): device pointers as ints, points in wire format,
@@ -693,8 +410,7 @@ class Context:
 
     def power_scalars(self, first, ratio, i0, n, d_out):
         """d_out[i] = first * ratio^(i0 + i), i < n, 32 B little-endian (device pointer as int)."""
-        self._check(lib().zkpoa_power_scalars_device(self._h, int(first).to_bytes(32, "little"),
-                                                     int(ratio).to_bytes(32, "little"), i0, n, d_out),
+        self._check(lib().zkpoa_power_scalars_device(self._h, _scalar(first), _scalar(ratio), i0, n, d_out),
                     "zkpoa_power_scalars_device")
 
     def ptau_new(self, power, out_path):
@@ -704,43 +420,42 @@ class Context:
     def ptau_contribute(self, in_path, out_path, secrets=None, name=None):
         """`snarkjs powersoftau contribute`: secrets = (tau, alpha, beta), ints in [1, r), None = random; appends a
         record to section 7 (include/zkpoa_prover.h: zkpoa_ptau_contribute)."""
-        sec = None if secrets is None else b"".join(int(x).to_bytes(32, "little") for x in secrets)
-        self._check(lib().zkpoa_ptau_contribute(self._h, os.fsencode(in_path), os.fsencode(out_path), sec,
-                                                None if name is None else name.encode()), "zkpoa_ptau_contribute")
+        sec = None if secrets is None else b"".join(_scalar(x) for x in secrets)
+        self._check(lib().zkpoa_ptau_contribute(self._h, os.fsencode(in_path), os.fsencode(out_path), sec, _name(name)),
+                    "zkpoa_ptau_contribute")
 
     def ptau_beacon(self, in_path, out_path, beacon, num_iterations_exp, name=None):
         """`snarkjs powersoftau beacon`: beacon bytes, 2^num_iterations_exp SHA-256 iterations (at most 2^30)."""
         self._check(lib().zkpoa_ptau_beacon(self._h, os.fsencode(in_path), os.fsencode(out_path), bytes(beacon),
-                                            len(beacon), num_iterations_exp, None if name is None else name.encode()),
-                    "zkpoa_ptau_beacon")
+                                            len(beacon), num_iterations_exp, _name(name)), "zkpoa_ptau_beacon")
 
     def sqrt_device(self, field, a):
         """Square roots on the device: a = n elements of Fq (field 0, 32 B each) or Fq2 (field 2, 64 B) in wire form ->
         (roots, flags): the non-negative root of each element (all-zero when it is no square) and one 0/1 byte each."""
         size = 64 if field == 2 else 32
         n = len(a) // size
-        roots, ok = ctypes.create_string_buffer(max(1, n * size)), ctypes.create_string_buffer(max(1, n))
+        roots, ok = _Out(n * size), _Out(n)
         self._check(lib().zkpoa_sqrt_device(self._h, field, bytes(a), n, roots, ok), "zkpoa_sqrt_device")
-        return roots.raw[:n * size], ok.raw[:n]
+        return roots.bytes(), ok.bytes()
 
     def decompressed_form(self, group, data, piece_points=0):
         """Compressed form (32 B per G1 point, 64 B per G2 point) -> wire-form points, on the device in pieces; a point
         that does not decompress raises ZkpoaError naming its index."""
         unit = 64 if group == 1 else 128
         n = len(data) // (unit // 2)
-        out = ctypes.create_string_buffer(max(1, n * unit))
+        out = _Out(n * unit)
         self._check(lib().zkpoa_decompressed_form(self._h, group, bytes(data), n, piece_points, out),
                     "zkpoa_decompressed_form")
-        return out.raw[:n * unit]
+        return out.bytes()
 
     def from_hash_form(self, group, data, piece_points=0):
         """Hash form -> wire-form points, on the device in pieces; a point that is not in hash form raises ZkpoaError
         naming its index."""
         unit = 64 if group == 1 else 128
         n = len(data) // unit
-        out = ctypes.create_string_buffer(max(1, n * unit))
+        out = _Out(n * unit)
         self._check(lib().zkpoa_from_hash_form(self._h, group, bytes(data), n, piece_points, out), "zkpoa_from_hash_form")
-        return out.raw[:n * unit]
+        return out.bytes()
 
     def ptau_export_challenge(self, ptau_path, challenge_path):
         """`snarkjs powersoftau export challenge`: writes the challenge file -> its Blake2b-512, the file's challenge."""
@@ -751,7 +466,7 @@ class Context:
 
     def ptau_challenge_contribute(self, challenge_path, response_path, secrets=None):
         """`snarkjs powersoftau challenge contribute`: secrets as ptau_contribute -> the response file's Blake2b-512."""
-        sec = None if secrets is None else b"".join(int(x).to_bytes(32, "little") for x in secrets)
+        sec = None if secrets is None else b"".join(_scalar(x) for x in secrets)
         h = ctypes.create_string_buffer(64)
         self._check(lib().zkpoa_ptau_challenge_contribute(self._h, os.fsencode(challenge_path),
                                                           os.fsencode(response_path), sec, h),
@@ -761,8 +476,7 @@ class Context:
     def ptau_import_response(self, old_path, response_path, new_path, name=None):
         """`snarkjs powersoftau import response`: the response's sections and one more record into new_path."""
         self._check(lib().zkpoa_ptau_import_response(self._h, os.fsencode(old_path), os.fsencode(response_path),
-                                                     os.fsencode(new_path), None if name is None else name.encode()),
-                    "zkpoa_ptau_import_response")
+                                                     os.fsencode(new_path), _name(name)), "zkpoa_ptau_import_response")
 
     def h_diff(self, points, n):
         """points[i + n] - points[i], i < n - 1, over 2n - 1 wire-form G1 points (device)."""
@@ -775,55 +489,34 @@ class Context:
         """Shard `rank` of `world` from device-resident sections that hold only this rank's ranges -- or, with
         block_log = L > 0, its blocks of 2^L items (block b to rank b mod world) concatenated
         (include/zkpoa_prover.h: zkpoa_zkey_load_device_shard, ZKPOA_SHARD_*); the caller keeps the buffers alive."""
-        key = ZKey.__new__(ZKey)
-        key._ctx = self
-        key._h = ctypes.c_void_p()
-        self._check(lib().zkpoa_zkey_load_device_shard(self._h, n_vars, n_public, log_domain, rank, world,
-                                                       shard_flags(split, block_log), d_A, d_B1, d_B2, d_C, d_H, d_coefs, n_coefs,
-                                                       bytes(header_points), ctypes.byref(key._h)),
-                    "zkpoa_zkey_load_device_shard")
-        return key
+        return ZKey._adopt(self, lib().zkpoa_zkey_load_device_shard, n_vars, n_public, log_domain, rank, world,
+                           shard_flags(split, block_log), d_A, d_B1, d_B2, d_C, d_H, d_coefs, n_coefs, bytes(header_points))
 
     def load_zkey_shard(self, zkey_bytes, rank, world):
         """Shard `rank` of `world` of a proving key: only that byte range of sections 5-9 is uploaded."""
-        key = ZKey.__new__(ZKey)
-        key._ctx = self
-        key._h = ctypes.c_void_p()
         p, k = _buf(zkey_bytes)
-        self._check(lib().zkpoa_zkey_load_shard(self._h, p, len(zkey_bytes), rank, world, ctypes.byref(key._h)),
-                    "zkpoa_zkey_load_shard")
-        return key
+        return ZKey._adopt(self, lib().zkpoa_zkey_load_shard, p, len(zkey_bytes), rank, world)
 
     def load_zkey_shard_ex(self, zkey_bytes, rank, world, split=False, block_log=0):
         """Shard `rank` of `world` with shard flags (include/zkpoa_prover.h ZKPOA_SHARD_*): `split` = the H-scalar chain
         is split too; block_log = L > 0 = sections 5-8 dealt out in blocks of 2^L items instead of one range per rank
         (what the prover's own multi-GPU path, env ZKPOA_DEVICES, loads)."""
-        key = ZKey.__new__(ZKey)
-        key._ctx = self
-        key._h = ctypes.c_void_p()
         p, k = _buf(zkey_bytes)
-        self._check(lib().zkpoa_zkey_load_shard_ex(self._h, p, len(zkey_bytes), rank, world, shard_flags(split, block_log),
-                                                   ctypes.byref(key._h)), "zkpoa_zkey_load_shard_ex")
-        return key
+        return ZKey._adopt(self, lib().zkpoa_zkey_load_shard_ex, p, len(zkey_bytes), rank, world,
+                           shard_flags(split, block_log))
 
     def load_zkey_shard_split(self, zkey_bytes, rank, world):
         """Like load_zkey_shard, with the H-scalar chain split too: this rank's constraint rows (c = rank mod
         world) of the coefficient list and the cyclic H-point shard H[t*world + rank]."""
-        key = ZKey.__new__(ZKey)
-        key._ctx = self
-        key._h = ctypes.c_void_p()
         p, k = _buf(zkey_bytes)
-        self._check(lib().zkpoa_zkey_load_shard_split(self._h, p, len(zkey_bytes), rank, world, ctypes.byref(key._h)),
-                    "zkpoa_zkey_load_shard_split")
-        return key
+        return ZKey._adopt(self, lib().zkpoa_zkey_load_shard_split, p, len(zkey_bytes), rank, world)
 
     def witness_load(self, zkey, wtns_bytes):
         """Parse a .wtns and upload it into the key's witness buffer -> public bytes."""
         pw, kw = _buf(wtns_bytes)
-        npub = zkey.info()[1]
-        pub = ctypes.create_string_buffer(max(1, 32 * npub))
-        self._check(lib().zkpoa_witness_load(self._h, zkey._h, pw, len(wtns_bytes), pub, 32 * npub), "zkpoa_witness_load")
-        return pub.raw[:32 * npub]
+        pub = _Out(32 * zkey.info()[1])
+        self._check(lib().zkpoa_witness_load(self._h, zkey._h, pw, len(wtns_bytes), pub, pub.n), "zkpoa_witness_load")
+        return pub.bytes()
 
     def split_stage1(self, zkey, d_witness, d_exchange):
         self._check(lib().zkpoa_split_stage1(self._h, zkey._h, d_witness, d_exchange), "zkpoa_split_stage1")
@@ -838,11 +531,10 @@ class Context:
         """-> (partials[384] = A|B1|B2|C|H MSM results of the key's shard, public bytes)"""
         pw, kw = _buf(wtns_bytes)
         parts = ctypes.create_string_buffer(384)
-        npub = zkey.info()[1]
-        pub = ctypes.create_string_buffer(max(1, 32 * npub))
-        self._check(lib().zkpoa_prove_partials(self._h, zkey._h, pw, len(wtns_bytes), parts, pub, 32 * npub),
+        pub = _Out(32 * zkey.info()[1])
+        self._check(lib().zkpoa_prove_partials(self._h, zkey._h, pw, len(wtns_bytes), parts, pub, pub.n),
                     "zkpoa_prove_partials")
-        return parts.raw, pub.raw[:32 * npub]
+        return parts.raw, pub.bytes()
 
     def prove_partials_device(self, zkey, d_witness):
         parts = ctypes.create_string_buffer(384)
@@ -859,42 +551,58 @@ class Context:
 
     def prove_device(self, zkey, d_witness, r=None, s=None):
         """Prove with the witness already in HBM -> (proof_points[256], public bytes)."""
-        rb = None if r is None else int(r).to_bytes(32, "little")
-        sb = None if s is None else int(s).to_bytes(32, "little")
         proof = ctypes.create_string_buffer(256)
-        npub = zkey.info()[1]
-        pub = ctypes.create_string_buffer(max(1, 32 * npub))
-        self._check(lib().zkpoa_prove_device(self._h, zkey._h, d_witness, rb, sb, proof, pub, 32 * npub),
+        pub = _Out(32 * zkey.info()[1])
+        self._check(lib().zkpoa_prove_device(self._h, zkey._h, d_witness, _scalar(r), _scalar(s), proof, pub, pub.n),
                     "zkpoa_prove_device")
-        return proof.raw, pub.raw[:32 * npub]
+        return proof.raw, pub.bytes()
 
     def prove(self, zkey, wtns_bytes, r=None, s=None):
         """-> (proof_points[256 bytes], public[nPublic*32 bytes])"""
         pw, kw = _buf(wtns_bytes)
-        rb = None if r is None else int(r).to_bytes(32, "little")
-        sb = None if s is None else int(s).to_bytes(32, "little")
         proof = ctypes.create_string_buffer(256)
-        npub = zkey.info()[1]
-        pub = ctypes.create_string_buffer(max(1, 32 * npub))
-        rc = lib().zkpoa_prove(self._h, zkey._h, pw, len(wtns_bytes), rb, sb, proof, pub, 32 * npub)
-        self._check(rc, "zkpoa_prove")
-        return proof.raw, pub.raw[:32 * npub]
+        pub = _Out(32 * zkey.info()[1])
+        self._check(lib().zkpoa_prove(self._h, zkey._h, pw, len(wtns_bytes), _scalar(r), _scalar(s), proof, pub, pub.n),
+                    "zkpoa_prove")
+        return proof.raw, pub.bytes()
 
 
-class MerkleTree:
+class _Handle:
+    """A native object that lives inside a Context: `_ctx`, the handle `_h`, and one way to let go of it. A subclass
+    states `_free(ctx_handle, handle)`; it runs once, and only while the context is still open (destroying the context
+    has freed what hung off it)."""
+
+    def _open(self, ctx, load, *args):
+        """load(ctx, *args, &handle), a loader of the C ABI, makes the native object; a failure names the loader."""
+        self._ctx, self._h = ctx, ctypes.c_void_p()
+        ctx._check(load(ctx._h, *args, ctypes.byref(self._h)), load.__name__)
+
+    def close(self):
+        if self._h and self._ctx._h:
+            self._free(self._ctx._h, self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MerkleTree(_Handle):
     """The anonymity-set Poseidon Merkle tree resident in HBM (zkpoa_merkle_build)."""
 
     def __init__(self, ctx, addresses, balances, device=False, n=None):
-        self._ctx = ctx
-        self._h = ctypes.c_void_p()
         if device:
-            ctx._check(lib().zkpoa_merkle_build_device(ctx._h, addresses, balances, n, ctypes.byref(self._h)),
-                       "zkpoa_merkle_build_device")
+            self._open(ctx, lib().zkpoa_merkle_build_device, addresses, balances, n)
         else:
             n = len(addresses) // 32 if n is None else n
             pa, ka = _buf(addresses)
             pb, kb = _buf(balances)
-            ctx._check(lib().zkpoa_merkle_build(ctx._h, pa, pb, n, ctypes.byref(self._h)), "zkpoa_merkle_build")
+            self._open(ctx, lib().zkpoa_merkle_build, pa, pb, n)
+
+    def _free(self, ctx_h, h):
+        lib().zkpoa_merkle_free(ctx_h, h)
 
     def info(self):
         """(n, path length, nodes)"""
@@ -909,38 +617,28 @@ class MerkleTree:
 
     def leaves(self, first=0, count=None):
         count = (1 << self.info()[1]) - first if count is None else count
-        out = ctypes.create_string_buffer(max(1, 32 * count))
+        out = _Out(32 * count)
         self._ctx._check(lib().zkpoa_merkle_leaves(self._ctx._h, self._h, first, count, out), "zkpoa_merkle_leaves")
-        return out.raw[:32 * count]
+        return out.bytes()
 
     def path(self, index):
         """(sibling hashes from the leaves up as ints, index bits)"""
         k = self.info()[1]
-        elems = ctypes.create_string_buffer(max(1, 32 * k))
-        bits = ctypes.create_string_buffer(max(1, k))
+        elems, bits = _Out(32 * k), _Out(k)
         self._ctx._check(lib().zkpoa_merkle_path(self._ctx._h, self._h, index, elems, bits), "zkpoa_merkle_path")
-        return ([int.from_bytes(elems.raw[32 * i:32 * i + 32], "little") for i in range(k)], list(bits.raw[:k]))
-
-    def close(self):
-        if self._h and self._ctx._h:
-            lib().zkpoa_merkle_free(self._ctx._h, self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        raw = elems.bytes()
+        return ([int.from_bytes(raw[32 * i:32 * i + 32], "little") for i in range(k)], list(bits.bytes()))
 
 
-class MsmTable:
+class MsmTable(_Handle):
     """Fixed-base table 2^(c*j) * P_i of a resident base array (zkpoa_msm_table_build)."""
 
     def __init__(self, ctx, group, d_bases, n, window_bits=0):
-        self._ctx, self.group = ctx, group
-        self._h = ctypes.c_void_p()
-        ctx._check(lib().zkpoa_msm_table_build(ctx._h, group, d_bases, n, window_bits, ctypes.byref(self._h)),
-                   "zkpoa_msm_table_build")
+        self.group = group
+        self._open(ctx, lib().zkpoa_msm_table_build, group, d_bases, n, window_bits)
+
+    def _free(self, ctx_h, h):
+        lib().zkpoa_msm_table_free(ctx_h, h)
 
     def info(self):
         """(n, window_bits, windows, bytes)"""
@@ -948,26 +646,23 @@ class MsmTable:
         lib().zkpoa_msm_table_info(self._h, out)
         return tuple(int(v) for v in out)
 
-    def close(self):
-        if self._h and self._ctx._h:
-            lib().zkpoa_msm_table_free(self._ctx._h, self._h)
-        self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class ZKey:
+class ZKey(_Handle):
     """A proving key resident in HBM (zkey sections 4-9 uploaded once)."""
 
     def __init__(self, ctx, zkey_bytes):
-        self._ctx = ctx
-        self._h = ctypes.c_void_p()
         p, k = _buf(zkey_bytes)
-        ctx._check(lib().zkpoa_zkey_load(ctx._h, p, len(zkey_bytes), ctypes.byref(self._h)), "zkpoa_zkey_load")
+        self._open(ctx, lib().zkpoa_zkey_load, p, len(zkey_bytes))
+
+    @classmethod
+    def _adopt(cls, ctx, load, *args):
+        """The key that one of the other loaders makes: load(ctx, *args, &key), see _Handle._open."""
+        key = cls.__new__(cls)
+        key._open(ctx, load, *args)
+        return key
+
+    def _free(self, ctx_h, h):
+        lib().zkpoa_zkey_free(ctx_h, h)
 
     def info(self):
         out = (ctypes.c_uint64 * 4)()
@@ -994,11 +689,10 @@ class ZKey:
     def vkey_points(self):
         """The verification key the zkey carries (sections 2-3): alpha1(64) beta2(128) gamma2(128) delta2(128) +
         IC[(nPublic+1) x 64], wire format; None for keys assembled from device buffers."""
-        size = ctypes.c_ulong(0)
-        if lib().zkpoa_zkey_vkey(self._h, None, ctypes.byref(size)) != PROVER_ERROR_SHORT_BUFFER:
+        rc, (buf,) = _sized(lambda *out: lib().zkpoa_zkey_vkey(self._h, *out), 0)
+        if buf is None:         # the question for the size was not answered with one: the handle has no key
             return None
-        buf = ctypes.create_string_buffer(size.value)
-        if lib().zkpoa_zkey_vkey(self._h, buf, ctypes.byref(size)) != PROVER_OK:
+        if rc != PROVER_OK:
             raise ZkpoaError("zkpoa_zkey_vkey failed")
         return buf.raw
 
@@ -1008,25 +702,9 @@ class ZKey:
         lib().zkpoa_zkey_header(self._h, out)
         return out.raw
 
-    def close(self):
-        if self._h and self._ctx._h:
-            lib().zkpoa_zkey_free(self._ctx._h, self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _json_call(fn, *args):
-    size = ctypes.c_ulong(0)
-    rc = fn(*args, None, ctypes.byref(size))
-    if rc not in (PROVER_OK, PROVER_ERROR_SHORT_BUFFER):
-        raise ZkpoaError("json conversion failed")
-    buf = ctypes.create_string_buffer(size.value)
-    rc = fn(*args, buf, ctypes.byref(size))
+    rc, (buf,) = _sized(lambda *out: fn(*args, *out), 0)
     if rc != PROVER_OK:
         raise ZkpoaError("json conversion failed")
     return buf.value.decode()
@@ -1042,10 +720,6 @@ def public_to_json(public_le, style="rapidsnark"):
     return _json_call(lib().zkpoa_public_to_json, p, len(public_le) // 32, 0 if style == "rapidsnark" else 1)
 
 
-VERIFY_BIN = os.path.join(_HERE, "zkpoa-verify")
-SANITIZE_BIN = os.path.join(_HERE, "zkpoa-sanitize")
-
-
 def groth16_verify(vkey_json, public_json, proof_json):
     """`snarkjs groth16 verify` on the three JSON texts (host only) -> True / False; raises on malformed input."""
     err = ctypes.create_string_buffer(512)
@@ -1059,17 +733,10 @@ def groth16_verify(vkey_json, public_json, proof_json):
 
 def export_vkey(zkey_bytes):
     """`snarkjs zkey export verificationkey`: the text of <circuit>_vkey.json from a zkey image (host only)."""
-    L = lib()
-    L.zkpoa_zkey_export_vkey.argtypes = [ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p,
-                                         ctypes.POINTER(ctypes.c_ulong), ctypes.c_void_p, ctypes.c_ulong]
     p, k = _buf(zkey_bytes)
-    size = ctypes.c_ulong(0)
     err = ctypes.create_string_buffer(512)
-    rc = L.zkpoa_zkey_export_vkey(p, len(zkey_bytes), None, ctypes.byref(size), err, 512)
-    if rc != PROVER_ERROR_SHORT_BUFFER:
-        raise ZkpoaError("zkpoa_zkey_export_vkey: " + err.value.decode())
-    buf = ctypes.create_string_buffer(size.value)
-    if L.zkpoa_zkey_export_vkey(p, len(zkey_bytes), buf, ctypes.byref(size), err, 512) != PROVER_OK:
+    rc, (buf,) = _sized(lambda *out: lib().zkpoa_zkey_export_vkey(p, len(zkey_bytes), *out, err, 512), 0)
+    if rc != PROVER_OK:
         raise ZkpoaError("zkpoa_zkey_export_vkey: " + err.value.decode())
     return buf.value.decode()
 
@@ -1077,7 +744,6 @@ def export_vkey(zkey_bytes):
 def poseidon_params():
     """(round constants, MDS rows) the library generates (host only), as Python ints."""
     buf = ctypes.create_string_buffer(204 * 32)
-    lib().zkpoa_poseidon_params.argtypes = [ctypes.c_void_p]
     if lib().zkpoa_poseidon_params(buf) != PROVER_OK:
         raise ZkpoaError("zkpoa_poseidon_params failed")
     vals = [int.from_bytes(buf.raw[32 * i:32 * i + 32], "little") for i in range(204)]
@@ -1100,14 +766,8 @@ def groth16_verify_points(vkey_points, proof_points, public_le):
 def sanitize_proof(vkey_json, public_json, proof_json):
     """The text sanitize_groth16_proof.py writes to sanitized_proof.json (host only)."""
     err = ctypes.create_string_buffer(512)
-    size = ctypes.c_ulong(1 << 16)
-    buf = ctypes.create_string_buffer(size.value)
-    rc = lib().zkpoa_sanitize_proof(vkey_json.encode(), public_json.encode(), proof_json.encode(), buf,
-                                    ctypes.byref(size), err, 512)
-    if rc == PROVER_ERROR_SHORT_BUFFER:
-        buf = ctypes.create_string_buffer(size.value)
-        rc = lib().zkpoa_sanitize_proof(vkey_json.encode(), public_json.encode(), proof_json.encode(), buf,
-                                        ctypes.byref(size), err, 512)
+    rc, (buf,) = _sized(lambda *out: lib().zkpoa_sanitize_proof(vkey_json.encode(), public_json.encode(),
+                                                                proof_json.encode(), *out, err, 512), 1 << 16)
     if rc != PROVER_OK:
         raise ZkpoaError("zkpoa_sanitize_proof: " + err.value.decode())
     return buf.value.decode()
@@ -1115,10 +775,8 @@ def sanitize_proof(vkey_json, public_json, proof_json):
 
 def prove_assemble(header_points, partial_sums, r=None, s=None):
     """Host-only randomised assembly: header (448 B) + summed partials (384 B) + r, s -> proof_points[256]."""
-    rb = None if r is None else int(r).to_bytes(32, "little")
-    sb = None if s is None else int(s).to_bytes(32, "little")
     out = ctypes.create_string_buffer(256)
-    if lib().zkpoa_prove_assemble(bytes(header_points), bytes(partial_sums), rb, sb, out) != PROVER_OK:
+    if lib().zkpoa_prove_assemble(bytes(header_points), bytes(partial_sums), _scalar(r), _scalar(s), out) != PROVER_OK:
         raise ZkpoaError("zkpoa_prove_assemble failed")
     return out.raw
 
@@ -1146,13 +804,13 @@ def g2_sum(points):
 
 def g1_mul(point, k):
     out = ctypes.create_string_buffer(64)
-    lib().zkpoa_g1_mul(point, int(k).to_bytes(32, "little"), out)
+    lib().zkpoa_g1_mul(point, _scalar(k), out)
     return out.raw
 
 
 def g2_mul(point, k):
     out = ctypes.create_string_buffer(128)
-    lib().zkpoa_g2_mul(point, int(k).to_bytes(32, "little"), out)
+    lib().zkpoa_g2_mul(point, _scalar(k), out)
     return out.raw
 
 
@@ -1246,12 +904,12 @@ class ChaCha:
 
 def fq_sqrt(a):
     out = ctypes.create_string_buffer(32)
-    return int.from_bytes(out.raw, "little") if lib().zkpoa_fq_sqrt(int(a).to_bytes(32, "little"), out) else None
+    return int.from_bytes(out.raw, "little") if lib().zkpoa_fq_sqrt(_scalar(a), out) else None
 
 
 def fq2_sqrt(a):
     out = ctypes.create_string_buffer(64)
-    if not lib().zkpoa_fq2_sqrt(int(a[0]).to_bytes(32, "little") + int(a[1]).to_bytes(32, "little"), out):
+    if not lib().zkpoa_fq2_sqrt(_scalar(a[0]) + _scalar(a[1]), out):
         return None
     return (int.from_bytes(out.raw[:32], "little"), int.from_bytes(out.raw[32:], "little"))
 
@@ -1287,51 +945,31 @@ def beacon_key(beacon, num_iterations_exp):
     return list(key)
 
 
+def _prove_to_files(what, prover, proof_path, public_path):
+    """prover(proof buffer, &size, public buffer, &size, error buffer, its size) is one of the one-shot entry points with
+    its inputs bound: the two JSON texts go to their files. The first buffers (4 KiB, 1 MiB) hold any proof the
+    reference's circuits make, so the prover runs once; only a short buffer makes it run again."""
+    err = ctypes.create_string_buffer(1024)
+    rc, (proof, public) = _sized(lambda *out: prover(*out, err, 1024), 1 << 12, 1 << 20)
+    if rc != PROVER_OK:
+        raise ZkpoaError("%s failed (%d): %s" % (what, rc, err.value.decode()))
+    _replace_file(proof_path, proof.value)
+    _replace_file(public_path, public.value)
+
+
 def groth16_prove(zkey_path, wtns_path, proof_path, public_path):
     """The reference's prove step (scripts/g16_prove.sh:248-252) through the C ABI:
     same four arguments as the `prover` executable."""
     with open(wtns_path, "rb") as f:
         wtns = f.read()
     pw, kw = _buf(wtns)
-    psz = ctypes.c_ulong(1 << 12)
-    usz = ctypes.c_ulong(1 << 20)
-    proof = ctypes.create_string_buffer(psz.value)
-    public = ctypes.create_string_buffer(usz.value)
-    err = ctypes.create_string_buffer(1024)
-    rc = lib().groth16_prover_zkey_file(os.fsencode(zkey_path), pw, len(wtns), proof, ctypes.byref(psz), public,
-                                        ctypes.byref(usz), err, 1024)
-    if rc == PROVER_ERROR_SHORT_BUFFER:
-        proof = ctypes.create_string_buffer(psz.value)
-        public = ctypes.create_string_buffer(usz.value)
-        rc = lib().groth16_prover_zkey_file(os.fsencode(zkey_path), pw, len(wtns), proof, ctypes.byref(psz), public,
-                                            ctypes.byref(usz), err, 1024)
-    if rc != PROVER_OK:
-        raise ZkpoaError("groth16_prover failed (%d): %s" % (rc, err.value.decode()))
-    for path, text in ((proof_path, proof.value), (public_path, public.value)):
-        tmp = "%s.tmp.%d" % (path, os.getpid())
-        with open(tmp, "wb") as f:
-            f.write(text)
-        os.replace(tmp, path)
+    _prove_to_files("groth16_prover", lambda *out: lib().groth16_prover_zkey_file(os.fsencode(zkey_path), pw, len(wtns), *out),
+                    proof_path, public_path)
 
 
 def groth16_prove_files(zkey_path, wtns_path, proof_path, public_path):
     """The same step with both inputs as paths (zkpoa_groth16_prover_files: what the `prover` executable calls; the
     witness goes from the page cache straight into the upload's pinned buffers, never mapped or copied on the host)."""
-    psz = ctypes.c_ulong(1 << 12)
-    usz = ctypes.c_ulong(1 << 20)
-    proof = ctypes.create_string_buffer(psz.value)
-    public = ctypes.create_string_buffer(usz.value)
-    err = ctypes.create_string_buffer(1024)
-    fn = lib().zkpoa_groth16_prover_files
-    rc = fn(os.fsencode(zkey_path), os.fsencode(wtns_path), proof, ctypes.byref(psz), public, ctypes.byref(usz), err, 1024)
-    if rc == PROVER_ERROR_SHORT_BUFFER:
-        proof = ctypes.create_string_buffer(psz.value)
-        public = ctypes.create_string_buffer(usz.value)
-        rc = fn(os.fsencode(zkey_path), os.fsencode(wtns_path), proof, ctypes.byref(psz), public, ctypes.byref(usz), err, 1024)
-    if rc != PROVER_OK:
-        raise ZkpoaError("zkpoa_groth16_prover_files failed (%d): %s" % (rc, err.value.decode()))
-    for path, text in ((proof_path, proof.value), (public_path, public.value)):
-        tmp = "%s.tmp.%d" % (path, os.getpid())
-        with open(tmp, "wb") as f:
-            f.write(text)
-        os.replace(tmp, path)
+    _prove_to_files("zkpoa_groth16_prover_files",
+                    lambda *out: lib().zkpoa_groth16_prover_files(os.fsencode(zkey_path), os.fsencode(wtns_path), *out),
+                    proof_path, public_path)
