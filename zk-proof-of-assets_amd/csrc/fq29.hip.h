@@ -5,8 +5,8 @@
 // bits. With 29-bit limbs a whole column fits ONE 64-bit accumulator, the product is mads and one shift per column,
 // and the 7 spare bits of the radix (2^261 / q > 169.28) make every conditional subtraction unnecessary.
 //
-// Plain C++, no inline assembly: the same text compiles for the device (hipcc) and for the host (g++,
-// tools/limb29_check.cpp, where -DZKPOA_LIMB29_CHECK counts column overflows).
+// Plain C++ and one empty asm statement (device builds only, see COLUMN CHAINS): the same text compiles for the device
+// (hipcc) and for the host (g++, tools/limb29_check.cpp, where -DZKPOA_LIMB29_CHECK counts column overflows).
 //
 // OPERAND CLASSES (a value is sum l[i] 2^(29 i); it is a field element only modulo q, never reduced below q here)
 //   N  product output        limbs 0..7 < 2^29 ("normalised"), value < 3q
@@ -24,6 +24,21 @@
 // dot2 as the mixed addition uses it (r * d + ny * ppp: r, ppp normalised, d < 3 * 2^29, ny < 2 * 2^29 per limb):
 // 27 * 2^58 + 18 * 2^58 + 9 * 2^58 = 54 * 2^58; with two D operands of 3 * 2^29: 63 * 2^58 + 2^35 < 2^64. The square
 // doubles its cross terms by doubling one limb (< 2^30): the same sum as the product. No column reaches 2^64.
+// COLUMN CHAINS. A column is written as one chain: acc >>= 29, then acc += a_i b_j ... . v_mad_u64_u32 takes its 64-bit
+// addend for free, so the shifted carry can be the addend of the column's first product. Left alone, the compiler's
+// reassociation ranks the carry last: it starts every column at 0 beside the tail of the column before and joins the
+// two with "v_lshl_add_u64 x, y, 0, x" -- 16 plain 64-bit adds per product, 144 of the 2152 instructions of one mixed
+// addition (1467 of them mads), and the accumulation kernel runs at the issue rate of that stream. So on the device
+// fq29_mac ends with an empty asm that READS acc: every partial sum then has a second use, sums with two uses are not
+// reassociated, and each column stays the one chain it is written as. The mixed addition is 2015 instructions with
+// the same 1467 mads and no 64-bit add (profiles/loop_mix_{parent,change}.txt; 16.4 -> 17.8 G additions/s at 3 waves
+// per SIMD, profiles/microbench_limb29_column_chain.txt). Two lighter forms were measured and dropped: the marker on a
+// column's first product only leaves the rest of the column to be summed from 0 and joined (144 -> 54); an asm that
+// also WRITES acc ("+v") removes every join but the hazard pass then puts an s_nop after every mad (1284 in the
+// addition: 15.8 G/s, slower than the parent). Reading costs no instruction and no register. The one product that
+// opens a chain from acc = 0 with another product behind it (dot2, column 0) carries no marker: it has no carry to
+// keep in front, and marked, it is computed twice (the compiler commutes the pair). COLUMNS, VALUES and the operand
+// classes are untouched: the same products are added, in the order written, to the same accumulator.
 // VALUES. The output is (a b + m q) / 2^261 with m < 2^261: < va vb / 2^261 + q <= 338 q^2 / (169.28 q) + q < 3q.
 // So N is closed under every product the rules allow; the largest in the mixed addition is 17q * 17q = 289 q^2.
 // SUBTRACTION is a + (C - b) per limb, C = k q in a "borrowed" representation whose limbs are all >= the largest
@@ -103,12 +118,21 @@ ZK29 Fq29 fq29_const() {
   return r;
 }
 
-// acc += a * b: one v_mad_u64_u32, no carry-out (see COLUMNS)
-ZK29 void fq29_mac(uint64_t& acc, uint32_t a, uint32_t b) {
+// acc += a * b: one v_mad_u64_u32, no carry-out (see COLUMNS). The product that opens a column chain with nothing in
+// front of it (acc = 0) where another product follows at once: no use to mark, see COLUMN CHAINS.
+ZK29 void fq29_mac_open(uint64_t& acc, uint32_t a, uint32_t b) {
 #if defined(ZKPOA_LIMB29_CHECK)
   if (__builtin_add_overflow(acc, (uint64_t)a * b, &acc)) limb29_overflows++;
 #else
   acc += (uint64_t)a * b;
+#endif
+}
+// The same, and the sum is USED a second time on the device (an empty asm that reads it: no instruction): see COLUMN
+// CHAINS. On the host this is fq29_mac_open.
+ZK29 void fq29_mac(uint64_t& acc, uint32_t a, uint32_t b) {
+  fq29_mac_open(acc, a, b);
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : : "v"(acc));
 #endif
 }
 
@@ -262,7 +286,8 @@ ZK29 Fq29 fq29_dot2(const Fq29& a0, const Fq29& b0, const Fq29& a1, const Fq29& 
   for (int k = 0; k < 9; k++) {
 #pragma unroll
     for (int i = 0; i <= k; i++) {
-      fq29_mac(acc, a0.l[i], b0.l[k - i]);
+      if (k == 0) fq29_mac_open(acc, a0.l[0], b0.l[0]);
+      else fq29_mac(acc, a0.l[i], b0.l[k - i]);
       fq29_mac(acc, a1.l[i], b1.l[k - i]);
     }
 #pragma unroll

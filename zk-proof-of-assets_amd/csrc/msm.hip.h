@@ -808,16 +808,23 @@ static __global__ __launch_bounds__(256, AccumWaves<F>::N) void msm_accum0_kerne
     G1Piece29 s;
     s.a = {};
     s.empty = true;
-    uint32_t e = entry(start);
-    Affine<F> p = load_affine<F>(bases, e & 0x7fffffffu);
-    for (uint32_t k = start; k < end; k++) {
-      uint32_t e_cur = e;
-      Affine<F> p_cur = p;
+    // One base in flight under the current addition, the two in two fixed register sets: the loop is unrolled by two
+    // and the sets swap roles, so no iteration copies the sixteen words of the prefetched base.
+    uint32_t e0 = entry(start), e1 = 0;
+    Affine<F> p0 = load_affine<F>(bases, e0 & 0x7fffffffu), p1 = p0;
+    for (uint32_t k = start; k < end;) {
       if (k + 1 < end) {
-        e = entry(k + 1);
-        p = load_affine<F>(bases, e & 0x7fffffffu);
+        e1 = entry(k + 1);
+        p1 = load_affine<F>(bases, e1 & 0x7fffffffu);
       }
-      g1piece29_add(s, p_cur.x.l, p_cur.y.l, (e_cur >> 31) != 0);
+      g1piece29_add(s, p0.x.l, p0.y.l, (e0 >> 31) != 0);
+      if (++k >= end) break;
+      if (k + 1 < end) {
+        e0 = entry(k + 1);
+        p0 = load_affine<F>(bases, e0 & 0x7fffffffu);
+      }
+      g1piece29_add(s, p1.x.l, p1.y.l, (e1 >> 31) != 0);
+      k++;
     }
     // the piece closes straight into the packed form (two products; X is normalised by the store): ZZ is tested once
     G1Sum29 sum = RedPacked29::inf();
