@@ -632,6 +632,11 @@ int zkpoa_ecdsa_star(zkpoa_context* ctx, uint64_t n, const void* r, const void* 
 int zkpoa_keccak256(zkpoa_context* ctx, const void* messages, uint64_t message_len, uint64_t n, void* out32);
 int zkpoa_eth_address(zkpoa_context* ctx, const void* pubkey_xy, uint64_t n, void* out_address20, void* out_checksum42);
 
+/* ---- the input steps after the proofs; host only, no context, no GPU -------------------------------------------
+ * The Poseidon of any circomlib width, the sponge of input_prep_for_layer_two.ts and the ed25519 Pedersen commitment
+ * of pedersen_commitment_checker.ts: four entry points, declared in a header of their own next to this one. */
+#include "zkpoa_layer_inputs.h"
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* Timings (ms, HIP events on the stream that ran the kernels) of the last call on this context.
  * id: 0 = whole device part of last MSM, 1 = its bucket-accumulation kernel (dominant kernel),

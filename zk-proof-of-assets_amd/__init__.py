@@ -750,6 +750,44 @@ def poseidon_params():
     return vals[:195], [vals[195 + 3 * i:198 + 3 * i] for i in range(3)]
 
 
+def _le32(values):
+    return b"".join(int(v).to_bytes(32, "little") for v in values)
+
+
+def poseidon_hash(inputs, init_state=0, n_out=1):
+    """circomlibjs poseidon(inputs, initState, nOut) for 1..16 inputs (host only) -> the first n_out state elements."""
+    out = ctypes.create_string_buffer(32 * max(1, n_out))
+    if lib().zkpoa_poseidon_hash(_le32(inputs), len(inputs), _le32([init_state]), n_out, out) != PROVER_OK:
+        raise ZkpoaError("zkpoa_poseidon_hash: 1..16 inputs below the field's order and 1..len + 1 outputs are needed")
+    return [int.from_bytes(out.raw[32 * i:32 * i + 32], "little") for i in range(n_out)]
+
+
+def poseidon_sponge(inputs):
+    """The reference's poseidonSponge (input_prep_for_layer_two.ts) over one or more field elements; host only."""
+    out = ctypes.create_string_buffer(32)
+    if lib().zkpoa_poseidon_sponge(_le32(inputs), len(inputs), out) != PROVER_OK:
+        raise ZkpoaError("zkpoa_poseidon_sponge: at least one input, all below the field's order, is needed")
+    return int.from_bytes(out.raw, "little")
+
+
+def pedersen_commit(secret, blinding):
+    """secret * G + blinding * H on ed25519 as the reference computes it (host only) -> (x, y, z, t)."""
+    out = ctypes.create_string_buffer(128)
+    if lib().zkpoa_pedersen_commit(_le32([secret]), _le32([blinding]), out) != PROVER_OK:
+        raise ZkpoaError("zkpoa_pedersen_commit failed")
+    return tuple(int.from_bytes(out.raw[32 * i:32 * i + 32], "little") for i in range(4))
+
+
+def pedersen_check(secret, blinding, signals):
+    """Is that commitment the point in the first 12 public signals of the layer-three circuit? Host only."""
+    if len(signals) < 12:
+        raise ZkpoaError("pedersen_check: the commitment is the first 12 public signals, %d given" % len(signals))
+    equal = ctypes.c_int(0)
+    if lib().zkpoa_pedersen_check(_le32([secret]), _le32([blinding]), _le32(signals[:12]), ctypes.byref(equal)) != PROVER_OK:
+        raise ZkpoaError("zkpoa_pedersen_check failed")
+    return bool(equal.value)
+
+
 def groth16_verify_points(vkey_points, proof_points, public_le):
     """The same check on wire-format points (ZKey.vkey_points(), Context.prove() outputs); host only."""
     err = ctypes.create_string_buffer(512)

@@ -163,6 +163,14 @@ SIGNATURES = {
 }
 EXPORTS = list(SIGNATURES)
 
+# every symbol include/zkpoa_layer_inputs.h declares (the header zkpoa_prover.h includes): host only, no context
+LAYER_INPUT_SIGNATURES = {
+    "zkpoa_poseidon_hash":             "i: s u s u p",
+    "zkpoa_poseidon_sponge":           "i: s u64 p",
+    "zkpoa_pedersen_commit":           "i: s s p",
+    "zkpoa_pedersen_check":            "i: s s s i*",
+}
+
 # test and measurement hooks the library exports but the public header deliberately leaves out
 HOOK_SIGNATURES = {
     "zkpoa_test_upload":               "i: p s u64 u64 p f*",       # csrc/zkpoa_api.hip
@@ -195,7 +203,7 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        for table in (SIGNATURES, HOOK_SIGNATURES):
+        for table in (SIGNATURES, LAYER_INPUT_SIGNATURES, HOOK_SIGNATURES):
             for name, spec in table.items():
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = signature(spec)

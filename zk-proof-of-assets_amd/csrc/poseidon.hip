@@ -5,8 +5,8 @@
 // merkle_tree.rs:3-5): leaf = Poseidon(address, balance) (:206-269), zero-valued padding leaves up to a power of two
 // (:261-266), node = Poseidon(left, right) (:138-178), rs_merkle tree (:411), sibling paths for the owned addresses
 // (:290-396). The hash is light-poseidon 0.2.0 `new_circom(2)` = circomlib's Poseidon, width 3, x^5, 8 full + 57
-// partial rounds; its parameters come from the Poseidon reference generator (Grain LFSR), regenerated here on the
-// host (the crates are not vendored) and pinned by the reference's committed anonymity set / Merkle root.
+// partial rounds; its parameters come from the Poseidon reference generator (Grain LFSR), regenerated on the
+// host by poseidon_host.hpp (the crates are not vendored) and pinned by the reference's committed anonymity set / Merkle root.
 //
 // Device mapping: one hash per lane, the 3-element state in registers (24 VGPRs), round constants and matrices read
 // through wave-uniform (scalar) loads from a 14 KB table. Integer-VALU-bound like everything else on this path; 64 B
@@ -20,6 +20,7 @@
 // derived on the host from the plain parameters (host_params); zkpoa_poseidon_params still exports the plain ones,
 // and the parity tests compare the device hashes with the oracle's textbook permutation.
 #include "bn254_field.hip.h"
+#include "poseidon_host.hpp"
 #include "zkpoa_internal.hpp"
 
 #include <string.h>
@@ -51,90 +52,12 @@ struct PoseidonTables {   // Montgomery form, device layout: the sparse-partial-
   Fr M[kT][kT];           // MDS matrix (full rounds; M[0][0] also in the partial rounds)
 };
 
-// ---- parameter generation (host): generate_parameters_grain.sage 1 0 254 3 8 57 ------------------------------
-struct Grain {
-  uint8_t st[80];
-  int step() {
-    int nb = st[62] ^ st[51] ^ st[38] ^ st[23] ^ st[13] ^ st[0];
-    memmove(st, st + 1, 79);
-    st[79] = (uint8_t)nb;
-    return nb;
-  }
-  int bit() {   // self-shrinking generator: a 0 discards the bit that follows it
-    int nb = step();
-    while (nb == 0) {
-      step();
-      nb = step();
-    }
-    return step();
-  }
-  Grain(unsigned t, unsigned rf, unsigned rp) {
-    const unsigned vals[6] = {1, 0, 254, t, rf, rp}, widths[6] = {2, 4, 12, 12, 10, 10};   // field, sbox, n, t, R_F, R_P
-    unsigned pos = 0;
-    for (int f = 0; f < 6; f++)
-      for (int b = (int)widths[f] - 1; b >= 0; b--) st[pos++] = (vals[f] >> b) & 1u;
-    while (pos < 80) st[pos++] = 1;
-    for (int i = 0; i < 160; i++) step();
-  }
-  void bits254(uint64_t out[4]) {   // most significant bit first
-    out[0] = out[1] = out[2] = out[3] = 0;
-    for (int i = 253; i >= 0; i--)
-      if (bit()) out[i >> 6] |= 1ull << (i & 63);
-  }
-};
-
-bool below_r(const uint64_t v[4]) {
-  for (int i = 3; i >= 0; i--) {
-    if (v[i] < HFrParams::P[i]) return true;
-    if (v[i] > HFrParams::P[i]) return false;
-  }
-  return false;
-}
-
+// ---- parameters (host): the library's one generator, poseidon_host.hpp, at t = 3 and R_P = 57 -------------------
 void host_params(PoseidonParams& out) {
-  Grain g(kT, kRF, kRP);
-  for (int i = 0; i < kRounds * kT;) {   // round constants: rejection sampling
-    uint64_t v[4];
-    g.bits254(v);
-    if (!below_r(v)) continue;
-    HFr c = HFr{{v[0], v[1], v[2], v[3]}}.to_mont();
-    memcpy(&out.C[i++], &c, 32);
-  }
-  for (;;) {   // MDS: Cauchy matrix 1 / (x_i + y_j) over 2t distinct elements (reduced, not rejected)
-    HFr xy[2 * kT];
-    bool ok = true;
-    for (int i = 0; i < 2 * kT; i++) {
-      uint64_t v[4];
-      g.bits254(v);
-      if (!below_r(v)) {   // F(bits): reduced, not rejected (2^254 < 2r: one subtraction)
-        unsigned __int128 bw = 0;
-        for (int q = 0; q < 4; q++) {
-          unsigned __int128 d = (unsigned __int128)v[q] - HFrParams::P[q] - bw;
-          v[q] = (uint64_t)d;
-          bw = (d >> 64) & 1;
-        }
-      }
-      HFr e{{v[0], v[1], v[2], v[3]}};
-      xy[i] = e.to_mont();
-    }
-    for (int i = 0; i < 2 * kT && ok; i++)
-      for (int j = 0; j < i; j++)
-        if (xy[i] == xy[j]) ok = false;
-    HFr m[kT][kT];
-    for (int i = 0; i < kT && ok; i++)
-      for (int j = 0; j < kT; j++) {
-        HFr s = xy[i] + xy[kT + j];
-        if (s.is_zero()) {
-          ok = false;
-          break;
-        }
-        m[i][j] = s.inv();
-      }
-    if (!ok) continue;
-    for (int i = 0; i < kT; i++)
-      for (int j = 0; j < kT; j++) memcpy(&out.M[i][j], &m[i][j], 32);
-    return;
-  }
+  PoseidonHostParams p;
+  poseidon_generate(kT, kRP, p);
+  memcpy(out.C, p.C.data(), sizeof(out.C));
+  memcpy(out.M, p.M.data(), sizeof(out.M));
 }
 
 // ---- the sparse form of the partial rounds (Poseidon paper, appendix B), derived on the host ---------------------

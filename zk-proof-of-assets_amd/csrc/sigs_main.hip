@@ -1,4 +1,4 @@
-// `ecdsa-sigs-parser` -- stands in for two TypeScript steps of the reference's workflow:
+// `ecdsa-sigs-parser` -- stands in for five TypeScript steps of the reference's workflow:
 //   ecdsa-sigs-parser --signatures <in.json> --output-path <out.json>             scripts/ecdsa_sigs_parser.ts
 //       (full_workflow.sh:354-357): ECDSA signatures -> ECDSA* attestations. Recovery, r', Keccak and the address
 //       comparison run on the GPU (zkpoa_ecdsa_star, zkpoa_eth_address); the output is the text that
@@ -6,28 +6,23 @@
 //   ecdsa-sigs-parser layer-one-input -i <parsed.json> -o <out.json> [-s start] [-e end]
 //       scripts/input_prep_for_layer_one.ts (full_workflow.sh:497-501): host only, the signatures of one batch as
 //       4 x 64-bit limbs.
+//   ecdsa-sigs-parser layer-two-input | layer-three-input | pedersen-check ...
+//       the workflow's last three node steps (full_workflow.sh:521-529, :575-579, :588-591), host only: this file only
+//       reads their options and hands over to layer_inputs.hpp, which also holds what layer-one-input shares with them.
 // Both files are read through a pull parser over the mapped text: a million signatures are 350 MB of JSON in and over
 // a gigabyte out, and neither is ever held as a tree. The output is formatted by the host threads 2^16 entries at a
 // time. Exit status 0, or 1 with one line on stderr and no output file.
 #include "../../include/zkpoa_prover.h"
 #include "host_files.hpp"
 #include "host_text.hpp"
+#include "layer_inputs.hpp"
 
 #include <algorithm>
 
 using namespace zkpoa;
+using namespace zkpoa::layer_inputs;
 
 namespace {
-
-struct InputError : std::runtime_error {
-  explicit InputError(const std::string& m) : std::runtime_error(m) {}
-};
-
-U256 parse_number(const Span& s, const char* what) {   // decimal or 0x hex, below 2^256
-  U256 x;
-  if (!x.parse_number(s.b, s.e)) throw InputError(std::string(what) + " is not a number below 2^256: " + s.str());
-  return x;
-}
 
 // "0x" + 1..64 hex digits -> 32 bytes, big-endian, padded on the left
 bool parse_hex_u256(const Span& s, uint8_t* out) {
@@ -36,8 +31,6 @@ bool parse_hex_u256(const Span& s, uint8_t* out) {
   x.to_be(out);
   return true;
 }
-
-std::string entry(uint64_t i) { return "entry " + std::to_string(i) + ": "; }
 
 void write_ranges(AtomicFile& fo, uint64_t& off, const std::vector<std::string>& parts) {
   for (const std::string& s : parts) {
@@ -212,38 +205,13 @@ struct StarSig {
   U256 r, s, rprime, x, y, msghash;
 };
 
-U256 read_bigint(Json& js, const char* what) {
-  U256 out;
-  bool seen = false;
-  js.object([&](const Span& k) {
-    if (k.is("__bigint__")) {
-      out = parse_number(js.string(), what);
-      seen = true;
-    } else {
-      js.skip();
-    }
-  });
-  if (!seen) throw InputError(std::string(what) + " is not a {\"__bigint__\": ...} object");
-  return out;
-}
-
-void put_limbs(std::string& o, const char* indent, const U256& x, bool last) {
-  o += indent;
-  o += "[\n";
-  for (int k = 0; k < 4; k++) {
-    o += indent;
-    o += "  \"" + std::to_string((unsigned long long)x.v[k]) + (k < 3 ? "\",\n" : "\"\n");
-  }
-  o += indent;
-  o += last ? "]\n" : "],\n";
-}
-
-int layer_one_mode(const std::string& in_path, const std::string& out_path, long long start, long long end) {
+int layer_one_mode(const std::string& in_path, const std::string& out_path, BatchRange range) {
+  const long long start = range.start, end = range.end;
   printf("Preparing input for layer 1 using the following data:\n- System input: %s\n- Start index for batch: %lld\n"
          "- End index for batch: %lld\nPath to write processed data to: %s\n\n",
          in_path.c_str(), start, end, out_path.c_str());
   std::vector<StarSig> sigs;   // entries first_kept, first_kept + 1, ...
-  const long long first_kept = start > 0 ? start : 0;
+  const long long first_kept = range.first_kept();
   long long total = 0;
   {
     MappedFile text(in_path.c_str());
@@ -255,7 +223,7 @@ int layer_one_mode(const std::string& in_path, const std::string& out_path, long
       js.array([&](uint64_t i) {
         // only the entries the range can reach are converted; the others are counted and skipped
         total = (long long)i + 1;
-        if ((start >= 0 && (long long)i < start) || (end >= 0 && (long long)i >= end)) return js.skip();
+        if (!range.reaches(i)) return js.skip();
         StarSig g;
         unsigned have = 0;
         js.object([&](const Span& k1) {
@@ -297,15 +265,9 @@ int layer_one_mode(const std::string& in_path, const std::string& out_path, long
     js.end();
     if (!seen) throw InputError("no accountAttestations in " + in_path);
   }
-  const long long len = total;
-  if (end == -1) {
-    printf("Batch contains all input data i.e. there is only 1 batch\n");
-    end = len;
-  }
-  if (start >= end) throw InputError("startIndex " + std::to_string(start) + " must be less than endIndex " + std::to_string(end));
-  // Array.prototype.slice: a negative index counts from the end, both are clamped to [0, length]
-  const long long lo = std::min(len, start < 0 ? std::max(0ll, len + start) : start);
-  const long long hi = std::max(lo, std::min(len, end < 0 ? std::max(0ll, len + end) : end));
+  range.close(total);
+  long long lo, hi;
+  range.slice(total, lo, hi);
   const uint64_t m = (uint64_t)(hi - lo);
   AtomicFile fo(out_path.c_str());
   uint64_t off = 0;
@@ -339,10 +301,103 @@ int layer_one_mode(const std::string& in_path, const std::string& out_path, long
   return 0;
 }
 
+const char kUsage[] =
+    "Usage: ecdsa-sigs-parser --signatures <in.json> --output-path <out.json>\n"
+    "       ecdsa-sigs-parser layer-one-input --poa-input-data <parsed.json> --write-layer-one-data-to <out.json>\n"
+    "                         [--account-start-index <i>] [--account-end-index <j>]\n"
+    "       ecdsa-sigs-parser layer-two-input --poa-input-data <parsed.json> --merkle-root <merkle_root.json>\n"
+    "                         --merkle-proofs <merkle_proofs.json> --layer-one-sanitized-proof <sanitized_proof.json>\n"
+    "                         --write-x-coords-hash-to <hash.txt> --write-layer-two-data-to <out.json>\n"
+    "                         [--account-start-index <i>] [--account-end-index <j>]\n"
+    "       ecdsa-sigs-parser layer-three-input --merkle-root-path <merkle_root.json>\n"
+    "                         --layer-two-sanitized-proof-paths <a.json,b.json,...> --write-layer-three-data-to <out.json>\n"
+    "                         --blindingFactor <decimal or 0x-hex>\n"
+    "       ecdsa-sigs-parser pedersen-check --poa-input-data <parsed.json> --layer-three-public-inputs <public.json>\n"
+    "                         --blindingFactor <decimal or 0x-hex>\n";
+
+// the three modes of layer_inputs.hpp: the reference's option names (-h is layer two's hash path, as there)
+int layer_inputs_main(const std::string& mode, int argc, char** argv) {
+  if (mode == "layer-two-input") {
+    static const Option known[] = {{"--poa-input-data", "-i"},           {"--merkle-root", "-t"},
+                                   {"--merkle-proofs", "-p"},            {"--write-x-coords-hash-to", "-h"},
+                                   {"--layer-one-sanitized-proof", "-d"}, {"--write-layer-two-data-to", "-o"},
+                                   {"--account-start-index", "-s"},      {"--account-end-index", "-e"}};
+    const auto got = parse_options(argc, argv, 2, known, 8);
+    BatchRange range;
+    range.start = index_option(got, "--account-start-index", 0);
+    range.end = index_option(got, "--account-end-index", -1);
+    LayerTwoPaths p;
+    const char* m = mode.c_str();
+    p.input = required(got, m, "--poa-input-data");
+    p.merkle_root = required(got, m, "--merkle-root");
+    p.merkle_proofs = required(got, m, "--merkle-proofs");
+    p.hash_out = required(got, m, "--write-x-coords-hash-to");
+    p.layer_one_proof = required(got, m, "--layer-one-sanitized-proof");
+    p.out = required(got, m, "--write-layer-two-data-to");
+    return layer_two_mode(p, range);
+  }
+  if (mode == "layer-three-input") {
+    static const Option known[] = {{"--merkle-root-path", "-m"}, {"--layer-two-sanitized-proof-paths", "-p"},
+                                   {"--write-layer-three-data-to", "-o"}, {"--blindingFactor", nullptr}};
+    const auto got = parse_options(argc, argv, 2, known, 4);
+    const char* m = mode.c_str();
+    return layer_three_mode(required(got, m, "--merkle-root-path"), required(got, m, "--layer-two-sanitized-proof-paths"),
+                            required(got, m, "--write-layer-three-data-to"), required(got, m, "--blindingFactor"));
+  }
+  static const Option known[] = {{"--poa-input-data", "-i"}, {"--layer-three-public-inputs", "-p"}, {"--blindingFactor", nullptr}};
+  const auto got = parse_options(argc, argv, 2, known, 3);
+  const char* m = mode.c_str();
+  return pedersen_check_mode(required(got, m, "--poa-input-data"), required(got, m, "--layer-three-public-inputs"),
+                             required(got, m, "--blindingFactor"));
+}
+
 bool parse_index(const char* s, long long& out) {
   char* rest = nullptr;
   out = strtoll(s, &rest, 10);
   return rest != s && !*rest;
+}
+
+// the parser and layer-one-input
+int first_modes_main(bool layer_one, int argc, char** argv) {
+  std::string in, out;
+  long long start = 0, end = -1;
+  for (int i = layer_one ? 2 : 1; i < argc; i++) {
+    std::string a = argv[i];
+    std::string val;
+    bool has = false;
+    const size_t eq = a.find('=');
+    if (a.rfind("--", 0) == 0 && eq != std::string::npos) {
+      val = a.substr(eq + 1);
+      a = a.substr(0, eq);
+      has = true;
+    }
+    auto value = [&]() -> std::string {
+      if (has) return val;
+      if (i + 1 >= argc) throw InputError("option " + a + " needs a value");
+      return argv[++i];
+    };
+    if (a == "-h" || a == "--help") {
+      printf("%s", kUsage);
+      return 0;
+    } else if (!layer_one && (a == "-s" || a == "--signatures")) in = value();
+    else if (!layer_one && (a == "-o" || a == "--output-path")) out = value();
+    else if (layer_one && (a == "-i" || a == "--poa-input-data")) in = value();
+    else if (layer_one && (a == "-o" || a == "--write-layer-one-data-to")) out = value();
+    else if (layer_one && (a == "-s" || a == "--account-start-index")) {
+      if (!parse_index(value().c_str(), start)) throw InputError("--account-start-index is not an integer");
+    } else if (layer_one && (a == "-e" || a == "--account-end-index")) {
+      if (!parse_index(value().c_str(), end)) throw InputError("--account-end-index is not an integer");
+    } else throw InputError("unknown argument " + a);
+  }
+  if (in.empty() || out.empty()) {
+    fprintf(stderr, layer_one ? "error: layer-one-input needs --poa-input-data <FILE> and --write-layer-one-data-to <FILE>\n"
+                              : "error: --signatures <FILE> and --output-path <FILE> are required\n");
+    return 2;
+  }
+  BatchRange range;
+  range.start = start;
+  range.end = end;
+  return layer_one ? layer_one_mode(in, out, range) : parse_mode(in, out);
 }
 
 }  // namespace
@@ -350,45 +405,12 @@ bool parse_index(const char* s, long long& out) {
 int main(int argc, char** argv) {
   int rc = 0;
   try {
-    const bool layer_one = argc > 1 && strcmp(argv[1], "layer-one-input") == 0;
-    std::string in, out;
-    long long start = 0, end = -1;
-    for (int i = layer_one ? 2 : 1; i < argc; i++) {
-      std::string a = argv[i];
-      std::string val;
-      bool has = false;
-      const size_t eq = a.find('=');
-      if (a.rfind("--", 0) == 0 && eq != std::string::npos) {
-        val = a.substr(eq + 1);
-        a = a.substr(0, eq);
-        has = true;
-      }
-      auto value = [&]() -> std::string {
-        if (has) return val;
-        if (i + 1 >= argc) throw InputError("option " + a + " needs a value");
-        return argv[++i];
-      };
-      if (a == "-h" || a == "--help") {
-        printf("Usage: ecdsa-sigs-parser --signatures <in.json> --output-path <out.json>\n"
-               "       ecdsa-sigs-parser layer-one-input --poa-input-data <parsed.json> --write-layer-one-data-to <out.json>\n"
-               "                         [--account-start-index <i>] [--account-end-index <j>]\n");
-        return 0;
-      } else if (!layer_one && (a == "-s" || a == "--signatures")) in = value();
-      else if (!layer_one && (a == "-o" || a == "--output-path")) out = value();
-      else if (layer_one && (a == "-i" || a == "--poa-input-data")) in = value();
-      else if (layer_one && (a == "-o" || a == "--write-layer-one-data-to")) out = value();
-      else if (layer_one && (a == "-s" || a == "--account-start-index")) {
-        if (!parse_index(value().c_str(), start)) throw InputError("--account-start-index is not an integer");
-      } else if (layer_one && (a == "-e" || a == "--account-end-index")) {
-        if (!parse_index(value().c_str(), end)) throw InputError("--account-end-index is not an integer");
-      } else throw InputError("unknown argument " + a);
-    }
-    if (in.empty() || out.empty()) {
-      fprintf(stderr, layer_one ? "error: layer-one-input needs --poa-input-data <FILE> and --write-layer-one-data-to <FILE>\n"
-                                : "error: --signatures <FILE> and --output-path <FILE> are required\n");
-      return 2;
-    }
-    rc = layer_one ? layer_one_mode(in, out, start, end) : parse_mode(in, out);
+    const std::string mode = argc > 1 ? argv[1] : "";
+    if (mode == "layer-two-input" || mode == "layer-three-input" || mode == "pedersen-check") rc = layer_inputs_main(mode, argc, argv);
+    else rc = first_modes_main(mode == "layer-one-input", argc, argv);
+  } catch (const UsageError& e) {
+    fprintf(stderr, "error: %s\n%s", e.what(), kUsage);
+    rc = 2;
   } catch (const std::exception& e) {
     fprintf(stderr, "Error: %s\n", e.what());
     rc = 1;
