@@ -1,6 +1,6 @@
 // The parts the instruction bound of the ECDSA* kernel is built from: register-only loops of the
 // secp256k1 field product and square, the product modulo the group order, the three group operations of the ladder and
-// the Keccak permutation, at the recovery kernel's own shape (workgroups of 64, as many as fill the card twice at the
+// the Keccak permutation, and for the signing kernel the SHA-256 compression, at the recovery kernel's own shape (workgroups of 64, as many as fill the card twice at the
 // occupancy the compiler gives them). Prints operations per second of the whole card.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I zk-proof-of-assets_amd/csrc tools/microbench_secp.hip -o tools/microbench_secp
 #include "secp256k1.hip.h"
@@ -27,7 +27,8 @@ __device__ uint32_t fold(const secp::Fp& a) {
   return s;
 }
 
-// 0 Fp product, 1 Fp square, 2 product modulo n, 3 xyzz_dbl, 4 xyzz_add, 5 xyzz_add_affine, 6 Keccak-f[1600]
+// 0 Fp product, 1 Fp square, 2 product modulo n, 3 xyzz_dbl, 4 xyzz_add, 5 xyzz_add_affine, 6 Keccak-f[1600],
+// 7 SHA-256 compression
 template <int OP>
 __global__ __launch_bounds__(64) void k_op(const uint32_t* in, uint32_t* out, int iters) {
   const int t = blockIdx.x * 64 + threadIdx.x;
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(64) void k_op(const uint32_t* in, uint32_t* out, in
       else xyzz_add_affine(acc, p, (i & 1) != 0);
     }
     res = fold(acc.x + acc.y + acc.zz + acc.zzz);
-  } else {
+  } else if (OP == 6) {
     uint64_t a[25];
 #pragma unroll
     for (int i = 0; i < 25; i++) a[i] = in[(t + i) & 8191];
@@ -74,6 +75,18 @@ __global__ __launch_bounds__(64) void k_op(const uint32_t* in, uint32_t* out, in
     for (int i = 0; i < iters; i++) keccak::f1600(a);
 #pragma unroll
     for (int i = 0; i < 25; i++) res ^= (uint32_t)a[i] ^ (uint32_t)(a[i] >> 32);
+  } else {
+    uint32_t h[8], blk[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) blk[i] = in[(t + i) & 8191];
+    sha256::initial_state(h);
+#pragma unroll 1
+    for (int i = 0; i < iters; i++) {
+      sha256::compress(h, blk);
+      blk[3] ^= h[0];   // the next block depends on this state
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) res ^= h[i];
   }
   out[t] = res;
 }
@@ -114,5 +127,6 @@ int main() {
   run<4>("xyzz_add", in, out, 2000);
   run<5>("xyzz_add_affine", in, out, 2000);
   run<6>("Keccak-f[1600]", in, out, 2000);
+  run<7>("SHA-256 compress", in, out, 4000);
   return 0;
 }

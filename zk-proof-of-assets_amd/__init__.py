@@ -181,6 +181,58 @@ class Context:
         chars = text.bytes().decode()        # bytes() copies the whole buffer: once, not per key
         return addr.bytes(), [chars[42 * i:42 * i + 42] for i in range(n)]
 
+    # ---- signing (tests/generate_ecdsa_signatures.ts): include/zkpoa_ecdsa_sign.h; 32-byte integers big-endian -----
+    def sha256(self, messages, length):
+        """SHA-256 of len(messages) / length messages of `length` bytes packed back to back (length 0: pass n)."""
+        if length:
+            n, data = len(messages) // length, bytes(messages)
+        else:
+            n, data = int(messages), b""
+        pm, km = _buf(data)
+        out = _Out(32 * n)
+        self._check(lib().zkpoa_sha256_batch(self._h, pm, length, n, out), "zkpoa_sha256_batch")
+        return out.bytes()
+
+    def secp256k1_pubkey(self, seckeys):
+        """n x 32 B keys -> (keys n x 64 B (x || y), addresses n x 20 B, status bytes: 1 = key zero or not below n)."""
+        n = len(seckeys) // 32
+        pk, kk = _buf(bytes(seckeys))
+        outs = [_Out(k * n) for k in (64, 20, 1)]
+        self._check(lib().zkpoa_secp256k1_pubkey(self._h, n, pk, *outs), "zkpoa_secp256k1_pubkey")
+        return tuple(o.bytes() for o in outs)
+
+    def secp256k1_derive_keys(self, seed, first, n):
+        """The n keys (SHA-256(seed || be64(i)) mod (n - 1)) + 1 for i = first ..: n x 32 B."""
+        ps, ks = _buf(bytes(seed))
+        out = _Out(32 * n)
+        self._check(lib().zkpoa_secp256k1_derive_keys(self._h, ps, len(seed), first, n, out), "zkpoa_secp256k1_derive_keys")
+        return out.bytes()
+
+    def rfc6979_nonce(self, seckeys, msghash, skip=0):
+        """The RFC 6979 candidate after `skip` refusals for n keys and n hashes (n x 32 B each) -> n x 32 B."""
+        n = len(seckeys) // 32
+        if len(msghash) != 32 * n:
+            raise ZkpoaError("rfc6979_nonce: %d keys need as many hashes" % n)
+        pk, kk = _buf(bytes(seckeys))
+        pz, kz = _buf(bytes(msghash))
+        out = _Out(32 * n)
+        self._check(lib().zkpoa_rfc6979_nonce(self._h, n, pk, pz, skip, out), "zkpoa_rfc6979_nonce")
+        return out.bytes()
+
+    def ecdsa_sign(self, seckeys, msghash, stride=None):
+        """n signatures with RFC 6979 nonces and low s. msghash: 32 B for all keys or n x 32 B (stride: 0 / 32, by default
+        told from its length) -> (r, s n x 32 B, v n bytes, keys n x 64 B, addresses n x 20 B, status bytes)."""
+        n = len(seckeys) // 32
+        if stride is None:
+            stride = 0 if len(msghash) == 32 and n != 1 else 32
+        if stride in (0, 32) and len(msghash) != (32 * n if stride else 32):
+            raise ZkpoaError("ecdsa_sign: the hashes do not fit %d keys with stride %d" % (n, stride))
+        pk, kk = _buf(bytes(seckeys))
+        pz, kz = _buf(bytes(msghash))
+        outs = [_Out(k * n) for k in (32, 32, 1, 64, 20, 1)]
+        self._check(lib().zkpoa_ecdsa_sign(self._h, n, pk, pz, stride, *outs), "zkpoa_ecdsa_sign")
+        return tuple(o.bytes() for o in outs)
+
     def merkle_build(self, addresses, balances, device=False, n=None):
         """Tree over (address, balance) pairs: host buffers (n x 32 B LE each) or, with device=True, device pointers."""
         return MerkleTree(self, addresses, balances, device, n)

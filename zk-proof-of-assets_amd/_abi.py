@@ -171,6 +171,15 @@ LAYER_INPUT_SIGNATURES = {
     "zkpoa_pedersen_check":            "i: s s s i*",
 }
 
+# every symbol include/zkpoa_ecdsa_sign.h declares (zkpoa_prover.h includes that header too): signing, on the GPU
+SIGN_SIGNATURES = {
+    "zkpoa_sha256_batch":              "i: p p u64 u64 p",
+    "zkpoa_secp256k1_pubkey":          "i: p u64 p p p p",
+    "zkpoa_secp256k1_derive_keys":     "i: p p u64 u64 u64 p",
+    "zkpoa_rfc6979_nonce":             "i: p u64 p p u32 p",
+    "zkpoa_ecdsa_sign":                "i: p u64 p p u64 p p p p p p",
+}
+
 # test and measurement hooks the library exports but the public header deliberately leaves out
 HOOK_SIGNATURES = {
     "zkpoa_test_upload":               "i: p s u64 u64 p f*",       # csrc/zkpoa_api.hip
@@ -203,7 +212,7 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        for table in (SIGNATURES, LAYER_INPUT_SIGNATURES, HOOK_SIGNATURES):
+        for table in (SIGNATURES, LAYER_INPUT_SIGNATURES, SIGN_SIGNATURES, HOOK_SIGNATURES):
             for name, spec in table.items():
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = signature(spec)

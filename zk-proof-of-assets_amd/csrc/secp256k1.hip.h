@@ -13,11 +13,15 @@
 // Sc, integers modulo the group order n. n has no form that helps beyond being close to 2^256: a product is folded
 // three times with 2^256 = c (mod n), c = 2^256 - n (129 bits), and corrected once. Canonical [0, n) as well.
 //
+// The last part is the other direction, signing (`ecdsa-sigs-parser sign`): RFC 6979 nonces over csrc/sha256.hip.h, a
+// fixed-base multiplication by G from a shared table, and the ECDSA equation.
+//
 // Everything is __host__ __device__ plain C++ (the compiler turns a u32 x u32 + u64 into v_mad_u64_u32), so the same
 // text runs in a CPU program against a big-integer model.
 #pragma once
 #include "bn254_ec.hip.h"
 #include "keccak.hip.h"
+#include "sha256.hip.h"
 
 namespace zkpoa {
 namespace secp {
@@ -615,6 +619,260 @@ ZK_HD Recovered recover_one(const uint32_t (&r_in)[8], const uint32_t (&s_in)[8]
   }
   if (status != kOk && status != kAddress) {
     out.r_prime = Fp::zero();
+    out.q = {Fp::zero(), Fp::zero()};
+#pragma unroll
+    for (int i = 0; i < 5; i++) out.addr[i] = 0;
+  }
+  out.status = status;
+  return out;
+}
+
+// ---- signing: RFC 6979 nonces, a fixed-base multiplication by G, the ECDSA equation -------------------------------
+// What `ecdsa-sigs-parser sign` computes per key, and what noble-secp256k1's sign(msghash, key, {canonical: true})
+// gives: HMAC-SHA256 DRBG, no extra entropy, low s with the recovery bit flipped. NOT hardened against side channels:
+// the table index, the skipped zero digits and the branch on a high scalar all depend on the key and the nonce.
+enum SignStatus : uint8_t {
+  kSignOk = 0,
+  kSignBadKey = 1,   // the key is zero or not below n
+  kSignHighX = 2,    // the nonce point's x is n or more: r = x - n would need recovery id 2 / 3, which v = 27 / 28 cannot say
+};
+
+ZK_HD Sc sc_add(const Sc& a, const Sc& b) {   // (a + b) mod n of canonical values
+  Sc r;
+  uint64_t c = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    c += (uint64_t)a.l[i] + b.l[i];
+    r.l[i] = (uint32_t)c;
+    c >>= 32;
+  }
+  r.add_c((c != 0 || r.ge_n()) ? 1u : 0u);   // the sum is below 2n: one correction
+  return r;
+}
+
+// The key of `--generate-keys`: (h mod (n - 1)) + 1 for a 256-bit h, in [1, n). n - 1 > 2^255: one subtraction at most,
+// and h - (n - 1) = h + (2^256 - n) + 1 modulo 2^256.
+ZK_HD Sc key_from_hash(const uint32_t (&h)[8]) {
+  Sc r;
+#pragma unroll
+  for (int i = 0; i < 8; i++) r.l[i] = h[i];
+  const bool ge = r.borrow_of([](int i) { return i ? Sc::N(i) : Sc::N(0) - 1u; }) == 0;
+  if (ge) r.add_c(1u);
+  uint64_t c = ge ? 2u : 1u;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    c += r.l[i];
+    r.l[i] = (uint32_t)c;
+    c >>= 32;
+  }
+  return r;
+}
+
+// key `index` of a seed: key_from_hash(SHA-256(seed || the index as 8 big-endian bytes))
+ZK_HD Sc derive_key(const uint8_t* seed, uint32_t seed_len, uint64_t index) {
+  uint32_t h[8], l[8];
+  sha256::digest_of([=](uint32_t j) -> uint32_t { return j < seed_len ? seed[j] : (uint32_t)(index >> (8 * (7 - (j - seed_len)))) & 0xffu; },
+                    seed_len + 8, h);
+#pragma unroll
+  for (int i = 0; i < 8; i++) l[i] = h[7 - i];
+  return key_from_hash(l);
+}
+
+// The table of the fixed-base multiplication: m 16^i G for i = 0 .. 63 and m = 1 .. 8, affine, entry (i, m) at
+// tab[8 i + m - 1]: the eight entries a window can ask for are 512 consecutive bytes. 512 points, 32 KiB, the same for
+// every lane. Built on the host, once: 8 additions per window and 4 doublings to the next.
+constexpr int kFixedWindows = 64;
+constexpr int kFixedEntries = 8 * kFixedWindows;
+inline void fixed_base_table(AffineK* tab) {
+  AffineK base = generator();
+  for (int i = 0; i < kFixedWindows; i++) {
+    XyzzK e = XyzzK::from_affine(base);
+    tab[8 * i] = base;
+    for (int m = 1; m < 8; m++) {
+      xyzz_add_affine(e, base, false);
+      tab[8 * i + m] = to_affine(e);
+    }
+    xyzz_add_affine(e, base, false);              // 9 * 16^i G
+    xyzz_add_affine(e, tab[8 * i + 6], false);    // + 7 * 16^i G
+    base = to_affine(e);
+  }
+}
+
+// k G for k in [1, n): signed digits in [-7, 8] as double_mul takes them (a scalar above (n - 1) / 2 is replaced by n - k
+// with every sign flipped, so the top digit never carries), one mixed addition per non-zero digit, no doubling. The
+// digit selects an entry of the shared table in global memory: all lanes are at the same window, so a wave reads from
+// one 512-byte row. Never infinity: the digits describe k or n - k, neither a multiple of n.
+ZK_HD XyzzK fixed_mul(Sc k, const AffineK* ftab) {
+  const bool neg = k.is_high();
+  if (neg) k = k.neg();
+  uint32_t mag[8];
+  uint64_t sgn;
+  recode_signed4(k.l, mag, sgn);
+  if (neg) sgn = ~sgn;
+  XyzzK acc = XyzzK::inf();
+#pragma unroll 1
+  for (int i = 0; i < kFixedWindows; i++) {   // least significant digit first: the order is free without doublings
+    const uint32_t m = mag[0] & 15u;
+    const bool minus = (sgn & 1u) != 0;
+#pragma unroll
+    for (int w = 0; w < 7; w++) mag[w] = (mag[w] >> 4) | (mag[w + 1] << 28);
+    mag[7] >>= 4;
+    sgn >>= 1;
+    if (m) xyzz_add_affine(acc, ftab[8 * i + (int)m - 1], minus);
+  }
+  return acc;
+}
+
+// HMAC-DRBG of RFC 6979 section 3.2 with SHA-256. K and V as big-endian words (word 0 = the first four bytes).
+struct Drbg {
+  uint32_t K[8], V[8];
+};
+// One HMAC of the generator. kind 0: K = HMAC(K, V || tag || x || h) (steps d and f); kind 1: K = HMAC(K, V || 0x00) (the
+// retry of step h.3); kind 2: V = HMAC(K, V). kind and tag must be the same in every lane.
+ZK_HD void drbg_hmac(Drbg& g, int kind, uint32_t tag, const uint32_t (&x)[8], const uint32_t (&h)[8]) {
+  uint32_t m0[16], m1[16], out[8];
+#pragma unroll
+  for (int i = 0; i < 16; i++) m1[i] = 0;
+  if (kind == 0) sha256::pad_97(g.V, tag, x, h, m0, m1);
+  else if (kind == 1) sha256::pad_33(g.V, 0u, m0);
+  else sha256::pad_32(g.V, m0);
+  sha256::hmac32(g.K, m0, m1, kind == 0, out);
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    if (kind == 2) g.V[i] = out[i];
+    else g.K[i] = out[i];
+  }
+}
+// HMACs first .. first + count - 1 of the sequence d, e, f, g, h.2 (0 .. 4: after them V is the first candidate) and then
+// the retry's three per rejected candidate (K = HMAC(K, V || 0x00), V = HMAC(K, V), and h.2 again). One loop and one call:
+// a kernel holds the HMAC once however many of them it runs.
+ZK_HD void rfc6979_run(Drbg& g, const uint32_t (&x)[8], const uint32_t (&h)[8], int first, int count) {
+#pragma unroll 1
+  for (int s = first; s < first + count; s++) {
+    int kind;
+    if (s < 5) kind = (s == 0 || s == 2) ? 0 : 2;
+    else kind = (s - 5) % 3 == 0 ? 1 : 2;
+    drbg_hmac(g, kind, s == 2 ? 1u : 0u, x, h);
+  }
+}
+// steps b - h.2: x = int2octets(key), h = bits2octets(message hash) = the hash, minus n when it is n or more
+ZK_HD void rfc6979_begin(Drbg& g, const uint32_t (&x)[8], const uint32_t (&h)[8]) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    g.K[i] = 0;
+    g.V[i] = 0x01010101u;
+  }
+  rfc6979_run(g, x, h, 0, 5);
+}
+// step h.3 for a candidate that was refused: afterwards V is the next one. `refused`: how many were refused before it.
+ZK_HD void rfc6979_retry(Drbg& g, const uint32_t (&x)[8], const uint32_t (&h)[8], int refused) {
+  rfc6979_run(g, x, h, 5 + 3 * refused, 3);
+}
+// a 256-bit integer (least significant limb first) as the words of its 32 big-endian bytes, and back
+ZK_HD void be_words(const uint32_t (&l)[8], uint32_t (&w)[8]) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) w[i] = l[7 - i];
+}
+// The candidate after `skip` refusals for this key and hash, valid or not (bits2int of V: qlen = 256, nothing to shift).
+// The key is taken as it is, also when it is zero or not below n.
+ZK_HD void rfc6979_candidate(const uint32_t (&key)[8], const uint32_t (&hash)[8], int skip, uint32_t (&k)[8]) {
+  Sc z;
+#pragma unroll
+  for (int i = 0; i < 8; i++) z.l[i] = hash[i];
+  z = z.reduce_once();
+  uint32_t x[8], h[8];
+  be_words(key, x);
+  be_words(z.l, h);
+  Drbg g;
+  rfc6979_begin(g, x, h);
+#pragma unroll 1
+  for (int j = 0; j < skip; j++) rfc6979_retry(g, x, h, j);
+  be_words(g.V, k);
+}
+
+struct PublicKey {
+  AffineK q;
+  uint32_t addr[5];
+  uint32_t status;
+};
+// Q = d G and its address. Status 1 for a key that is zero or not below n: zeros, after the same walk with key 1.
+ZK_HD PublicKey public_key(const uint32_t (&d_in)[8], const AffineK* ftab) {
+  Sc d;
+#pragma unroll
+  for (int i = 0; i < 8; i++) d.l[i] = d_in[i];
+  const uint32_t status = (d.is_zero() || d.ge_n()) ? kSignBadKey : kSignOk;
+  if (status != kSignOk) d = Sc::one();
+  PublicKey out;
+  out.q = to_affine(fixed_mul(d, ftab));
+  eth_address_words(out.q, out.addr);
+  if (status != kSignOk) {
+    out.q = {Fp::zero(), Fp::zero()};
+#pragma unroll
+    for (int i = 0; i < 5; i++) out.addr[i] = 0;
+  }
+  out.status = status;
+  return out;
+}
+
+struct Signed {
+  Sc r, s;
+  uint32_t v;
+  AffineK q;
+  uint32_t addr[5];
+  uint32_t status;
+};
+// One signature: Q = d G and its address, R = k G, r = R.x mod n, s = (z + r d) / k with z = hash mod n, the recovery bit
+// = the parity of R.y, flipped when s is replaced by n - s because it is above (n - 1) / 2; v = 27 + bit. The two
+// conversions to affine share one inversion. A candidate that is 0 or not below n, or that gives r = 0 or s = 0, is
+// refused and the generator's retry step gives the next: the loop runs once but for an event of probability 2^-128. A
+// lane with a bad key walks the same path with key 1 and gets zeros.
+ZK_HD Signed sign_one(const uint32_t (&d_in)[8], const uint32_t (&z_in)[8], const AffineK* ftab) {
+  Sc d, z;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    d.l[i] = d_in[i];
+    z.l[i] = z_in[i];
+  }
+  uint32_t status = (d.is_zero() || d.ge_n()) ? kSignBadKey : kSignOk;
+  if (status != kSignOk) d = Sc::one();
+  // (Nothing but the key and the hash is kept across the generator, and the generator's state is not kept across the
+  // multiplications: a retry, which never happens, starts all of it again. That is what keeps the registers down.)
+  Signed out;
+  int refused = 0;
+#pragma unroll 1
+  for (;;) {
+    Sc k;
+    rfc6979_candidate(d.l, z.l, refused, k.l);
+    const bool bad_k = k.is_zero() || k.ge_n();
+    if (bad_k) k = Sc::one();
+    const XyzzK Q = fixed_mul(d, ftab);
+    const XyzzK R = fixed_mul(k, ftab);
+    // 1 / Q.zzz and 1 / R.zzz from one inversion; x = X / ZZ = X (ZZ / ZZZ)^2, y = Y / ZZZ as to_affine
+    const Fp t = (Q.zzz * R.zzz).inv();
+    const Fp iq = t * R.zzz, ir = t * Q.zzz;
+    const Fp zq = Q.zz * iq, zr = R.zz * ir;
+    out.q = {Q.x * zq.sqr(), Q.y * iq};
+    const AffineK ra = {R.x * zr.sqr(), R.y * ir};
+#pragma unroll
+    for (int i = 0; i < 8; i++) out.r.l[i] = ra.x.l[i];
+    const bool high_x = out.r.ge_n();
+    if (high_x) out.r = Sc::one();
+    out.s = k.inv() * sc_add(z.reduce_once(), out.r * d);
+    uint32_t bit = ra.y.is_odd() ? 1u : 0u;
+    if (out.s.is_high()) {
+      out.s = out.s.neg();
+      bit ^= 1u;
+    }
+    out.v = 27u + bit;
+    const bool refuse = bad_k || (!high_x && (out.r.is_zero() || out.s.is_zero()));
+    if (status == kSignOk && !refuse && high_x) status = kSignHighX;
+    if (status != kSignOk || !refuse) break;
+    refused++;
+  }
+  eth_address_words(out.q, out.addr);
+  if (status != kSignOk) {
+    out.r = out.s = {{0, 0, 0, 0, 0, 0, 0, 0}};
+    out.v = 0;
     out.q = {Fp::zero(), Fp::zero()};
 #pragma unroll
     for (int i = 0; i < 5; i++) out.addr[i] = 0;

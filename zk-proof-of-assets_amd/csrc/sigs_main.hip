@@ -1,4 +1,5 @@
-// `ecdsa-sigs-parser` -- stands in for five TypeScript steps of the reference's workflow:
+// `ecdsa-sigs-parser` -- stands in for five TypeScript steps of the reference's workflow, and (sign, anon-set: further
+// down) for the two test scripts that make the workflow's first two files:
 //   ecdsa-sigs-parser --signatures <in.json> --output-path <out.json>             scripts/ecdsa_sigs_parser.ts
 //       (full_workflow.sh:354-357): ECDSA signatures -> ECDSA* attestations. Recovery, r', Keccak and the address
 //       comparison run on the GPU (zkpoa_ecdsa_star, zkpoa_eth_address); the output is the text that
@@ -301,8 +302,326 @@ int layer_one_mode(const std::string& in_path, const std::string& out_path, Batc
   return 0;
 }
 
+// ---- sign and anon-set modes -----------------------------------------------------------------------------------------
+// The two files the workflow starts from, which the reference makes with tests/generate_ecdsa_signatures.ts (noble's
+// sign, at most 128 keys of a list in the script) and tests/generate_anon_set.ts (at most about 10,600 addresses). Keys
+// come from a file or are derived from a seed on the GPU; signing, public keys, addresses and the filler accounts'
+// hashes run there (include/zkpoa_ecdsa_sign.h), sorting and formatting on the host threads. Not hardened against side
+// channels, and the keys pass through host memory and a text file: made for rehearsals and test data.
+constexpr uint64_t kGroupOrder[4] = {0xbfd25e8cd0364141ull, 0xbaaedce6af48a03bull, 0xfffffffffffffffeull, 0xffffffffffffffffull};
+
+struct Keys {
+  std::vector<uint8_t> key;       // 32 bytes per key, big-endian
+  std::vector<U256> balance;
+  std::vector<uint64_t> line;     // of the key file, 1-based; empty for derived keys
+  uint64_t n = 0;
+};
+
+U256 default_balance(const U256& key) {   // the reference's generateDeterministicBalance: key mod 1000
+  unsigned __int128 rem = 0;
+  for (int k = 3; k >= 0; k--) rem = ((rem << 64) | key.v[k]) % 1000u;
+  U256 b;
+  b.v[0] = (uint64_t)rem;
+  return b;
+}
+
+// <decimal or 0x-hex key>[,<decimal balance>] per line; blank lines and lines that begin with # are skipped. The first
+// bad line ends the command: "key <line number>: ...".
+void read_keys(const std::string& path, Keys& g) {
+  MappedFile text(path.c_str());
+  const char *p = text.begin(), *end = text.end();
+  for (uint64_t line = 1; p < end; line++) {
+    const char* eol = static_cast<const char*>(memchr(p, '\n', (size_t)(end - p)));
+    const char *b = p, *e = eol ? eol : end;
+    p = eol ? eol + 1 : end;
+    auto blank = [](char c) { return c == ' ' || c == '\t' || c == '\r'; };
+    while (b < e && blank(*b)) b++;
+    while (e > b && blank(e[-1])) e--;
+    if (b == e || *b == '#') continue;
+    const std::string where = "key " + std::to_string(line) + ": ";
+    const char* comma = static_cast<const char*>(memchr(b, ',', (size_t)(e - b)));
+    const char* ke = comma ? comma : e;
+    while (ke > b && blank(ke[-1])) ke--;
+    U256 key, bal;
+    if (!key.parse_number(b, ke)) throw InputError(where + "not a decimal or 0x-hex number below 2^256: " + std::string(b, ke));
+    if (!(key.v[0] | key.v[1] | key.v[2] | key.v[3])) throw InputError(where + "the key is zero");
+    if (!key.below(kGroupOrder)) throw InputError(where + "the key is not below the group order");
+    if (comma) {
+      const char* bb = comma + 1;
+      while (bb < e && blank(*bb)) bb++;
+      if (!bal.parse_dec(bb, e)) throw InputError(where + "the balance is not a decimal number below 2^256: " + std::string(bb, e));
+    } else {
+      bal = default_balance(key);
+    }
+    g.key.resize(32 * (g.n + 1));
+    key.to_be(&g.key[32 * g.n]);
+    g.balance.push_back(bal);
+    g.line.push_back(line);
+    g.n++;
+  }
+}
+
+void derive_keys(zkpoa_context* ctx, const std::string& seed, uint64_t count, Keys& g) {
+  g.key.resize(32 * count + 1);
+  if (zkpoa_secp256k1_derive_keys(ctx, seed.data(), seed.size(), 0, count, g.key.data()) != PROVER_OK)
+    throw InputError(std::string("zkpoa_secp256k1_derive_keys: ") + zkpoa_last_error(ctx));
+  g.balance.resize(count);
+  parallel_ranges(count, 4096, [&](unsigned, uint64_t lo, uint64_t hi) {
+    for (uint64_t i = lo; i < hi; i++) g.balance[i] = default_balance(U256::from_be(&g.key[32 * i]));
+  });
+  g.n = count;
+}
+
+void put_hex(std::string& o, const uint8_t* b, size_t bytes) {
+  static const char digits[] = "0123456789abcdef";
+  for (size_t i = 0; i < bytes; i++) {
+    o.push_back(digits[b[i] >> 4]);
+    o.push_back(digits[b[i] & 15]);
+  }
+}
+
+// indices 0 .. n-1 by the 20 address bytes, ascending; equal addresses keep their order (Array.prototype.sort is stable)
+// The first eight bytes travel with the index, so that nearly every comparison stays inside the array being sorted; the
+// host threads sort a piece each, then merge the pieces pairwise.
+std::vector<uint32_t> order_by_address(const uint8_t* addr20, uint64_t n) {
+  struct Item {
+    uint64_t head;
+    uint32_t idx;
+  };
+  std::vector<Item> items(n);
+  parallel_ranges(n, 4096, [&](unsigned, uint64_t lo, uint64_t hi) {
+    for (uint64_t i = lo; i < hi; i++) {
+      uint64_t head = 0;
+      for (int k = 0; k < 8; k++) head = (head << 8) | addr20[20 * i + k];
+      items[i] = {head, (uint32_t)i};
+    }
+  });
+  auto less = [&](const Item& a, const Item& b) {
+    if (a.head != b.head) return a.head < b.head;
+    const int c = memcmp(addr20 + 20ull * a.idx + 8, addr20 + 20ull * b.idx + 8, 12);
+    return c ? c < 0 : a.idx < b.idx;
+  };
+  unsigned pieces = 1;
+  while (pieces * 2 <= host_threads() && n / (pieces * 2) >= 1024) pieces *= 2;
+  auto cut = [&](unsigned p) { return items.begin() + (ptrdiff_t)(n * p / pieces); };
+  run_threads(pieces, [&](unsigned t) { std::sort(cut(t), cut(t + 1), less); });
+  for (unsigned width = 1; width < pieces; width *= 2)
+    run_threads(pieces / (2 * width), [&](unsigned t) { std::inplace_merge(cut(2 * width * t), cut(2 * width * t + width), cut(2 * width * (t + 1)), less); });
+  std::vector<uint32_t> idx(n);
+  parallel_ranges(n, 4096, [&](unsigned, uint64_t lo, uint64_t hi) {
+    for (uint64_t i = lo; i < hi; i++) idx[i] = items[i].idx;
+  });
+  return idx;
+}
+
+// entry(o, i) appends entry i of n; the file is head + the entries in blocks of 2^16 over the host threads + tail
+template <class Fn>
+void write_entries(const std::string& path, const std::string& head, const std::string& tail, uint64_t n, uint64_t bytes_each, Fn entry) {
+  AtomicFile fo(path.c_str());
+  uint64_t off = 0;
+  fo.put_at(off, head.data(), head.size());
+  off += head.size();
+  constexpr uint64_t kRound = 1u << 16;
+  for (uint64_t i0 = 0; i0 < n; i0 += kRound) {
+    const uint64_t m = std::min(kRound, n - i0);
+    std::vector<std::string> parts(host_threads() + 1);
+    parallel_ranges(m, 256, [&](unsigned t, uint64_t lo, uint64_t hi) {
+      std::string& o = parts[t];
+      o.reserve((hi - lo) * bytes_each);
+      for (uint64_t i = i0 + lo; i < i0 + hi; i++) entry(o, i);
+    });
+    write_ranges(fo, off, parts);
+  }
+  fo.put_at(off, tail.data(), tail.size());
+  fo.commit();
+}
+
+// the key source of both modes: exactly one of --keys <file> and --generate-keys <N> --seed <text>
+struct KeySource {
+  std::string file, seed;
+  uint64_t count = 0;
+  bool generate = false;
+};
+
+bool parse_count(const std::string& s, uint64_t& out) {
+  if (s.empty() || s.size() > 10) return false;
+  out = 0;
+  for (char c : s) {
+    if (c < '0' || c > '9') return false;
+    out = out * 10 + (uint64_t)(c - '0');
+  }
+  return out <= (1ull << 32);
+}
+
+KeySource key_source(const std::map<std::string, std::string>& got, const char* mode) {
+  KeySource src;
+  const bool file = got.count("--keys"), gen = got.count("--generate-keys");
+  if (file == gen) throw UsageError(std::string(mode) + " needs either --keys <file> or --generate-keys <N> --seed <text>");
+  if (file) {
+    if (got.count("--seed")) throw UsageError("--seed goes with --generate-keys");
+    src.file = got.at("--keys");
+    return src;
+  }
+  if (!got.count("--seed")) throw UsageError("--generate-keys needs --seed <text>");
+  if (!parse_count(got.at("--generate-keys"), src.count)) throw UsageError("--generate-keys is not a number of keys up to 2^32");
+  src.seed = got.at("--seed");
+  if (src.seed.size() > 4084) throw UsageError("--seed is at most 4084 bytes");
+  src.generate = true;
+  return src;
+}
+
+const std::string& needed(const std::map<std::string, std::string>& got, const char* mode, const char* name) {
+  const auto it = got.find(name);
+  if (it == got.end() || it->second.empty()) throw UsageError(std::string(mode) + " needs " + name + " <value>");
+  return it->second;
+}
+
+void write_key_file(const std::string& path, const Keys& g) {
+  write_entries(path, "", "", g.n, 68, [&](std::string& o, uint64_t i) {
+    o += "0x";
+    put_hex(o, &g.key[32 * i], 32);
+    o += "\n";
+  });
+}
+
+int sign_mode(int argc, char** argv) {
+  static const Option known[] = {{"--keys", nullptr}, {"--generate-keys", nullptr}, {"--seed", nullptr},       {"--message", nullptr},
+                                 {"--msghash", nullptr}, {"--output-path", "-o"},   {"--write-keys", nullptr}};
+  const auto got = parse_options(argc, argv, 2, known, 7);
+  const KeySource src = key_source(got, "sign");
+  if (got.count("--message") == got.count("--msghash")) throw UsageError("sign needs either --message <text> or --msghash 0x<64 hex digits>");
+  const std::string out_path = needed(got, "sign", "--output-path");
+  uint8_t z[32];
+  if (got.count("--message")) {
+    const std::string& msg = got.at("--message");
+    zkpoa_sha256(msg.data(), msg.size(), z);
+  } else {
+    const std::string& h = got.at("--msghash");
+    if (!parse_hex_bytes(Span{h.data(), h.data() + h.size()}, z, 32)) throw UsageError("--msghash is not 0x + 64 hex digits");
+  }
+  ContextStart start(device_from_env());
+  PhaseTimer lap("ecdsa-sigs-parser sign", 8);
+  Keys g;
+  if (!src.generate) read_keys(src.file, g);
+  zkpoa_context* ctx = start.get();
+  if (src.generate) derive_keys(ctx, src.seed, src.count, g);
+  lap("keys");
+  const uint64_t n = g.n;
+  printf("Signing with %llu keys..\n", (unsigned long long)n);
+  std::vector<uint8_t> r(32 * n + 1), s(32 * n + 1), v(n + 1), pub(64 * n + 1), addr(20 * n + 1), status(n + 1);
+  std::vector<char> text(42 * n + 1);
+  if (zkpoa_ecdsa_sign(ctx, n, g.key.data(), z, 0, r.data(), s.data(), v.data(), pub.data(), addr.data(), status.data()) != PROVER_OK)
+    throw InputError(std::string("zkpoa_ecdsa_sign: ") + zkpoa_last_error(ctx));
+  for (uint64_t i = 0; i < n; i++)
+    if (status[i])
+      throw InputError("key " + std::to_string(g.line.empty() ? i + 1 : g.line[i]) +
+                       (status[i] == 2 ? ": the nonce point's x coordinate is not below the group order (v cannot express it)"
+                                       : ": the key is zero or not below the group order"));
+  if (zkpoa_eth_address(ctx, pub.data(), n, addr.data(), text.data()) != PROVER_OK)
+    throw InputError(std::string("zkpoa_eth_address: ") + zkpoa_last_error(ctx));
+  lap("device");
+  const std::vector<uint32_t> order = order_by_address(addr.data(), n);
+  lap("sort");
+  std::string zhex;
+  put_hex(zhex, z, 32);
+  write_entries(out_path, "[", "]", n, 420, [&](std::string& o, uint64_t k) {
+    const uint64_t i = order[k];
+    if (k) o += ",";
+    o += "{\"signature\":{\"r\":\"0x";
+    put_hex(o, &r[32 * i], 32);
+    o += "\",\"s\":\"0x";
+    put_hex(o, &s[32 * i], 32);
+    o += "\",\"v\":" + std::to_string((unsigned)v[i]) + ",\"msghash\":\"0x" + zhex + "\"},\"address\":\"";
+    o.append(&text[42 * i], 42);
+    o += "\",\"balance\":\"";
+    g.balance[i].append_dec(o);
+    o += "n\"}";
+  });
+  if (got.count("--write-keys")) write_key_file(got.at("--write-keys"), g);
+  lap("write");
+  printf("Wrote %llu signatures to %s\n", (unsigned long long)n, out_path.c_str());
+  return 0;
+}
+
+int anon_set_mode(int argc, char** argv) {
+  static const Option known[] = {{"--keys", nullptr}, {"--generate-keys", nullptr}, {"--seed", nullptr}, {"--num-addresses", "-n"},
+                                 {"--output-path", "-o"}};
+  const auto got = parse_options(argc, argv, 2, known, 5);
+  const KeySource src = key_source(got, "anon-set");
+  uint64_t total = 0;
+  if (!parse_count(needed(got, "anon-set", "--num-addresses"), total) || total == 0)
+    throw UsageError("--num-addresses is not a number of addresses from 1 to 2^32");
+  const std::string out_path = needed(got, "anon-set", "--output-path");
+  ContextStart start(device_from_env());
+  PhaseTimer lap("ecdsa-sigs-parser anon-set", 8);
+  Keys g;
+  if (!src.generate) read_keys(src.file, g);
+  zkpoa_context* ctx = start.get();
+  if (src.generate) derive_keys(ctx, src.seed, std::min(src.count, total), g);
+  const uint64_t owned = std::min(g.n, total);
+  std::vector<uint8_t> addr(20 * total + 1);
+  std::vector<U256> balance(total);
+  {
+    std::vector<uint8_t> pub(64 * owned + 1), status(owned + 1);
+    if (zkpoa_secp256k1_pubkey(ctx, owned, g.key.data(), pub.data(), addr.data(), status.data()) != PROVER_OK)
+      throw InputError(std::string("zkpoa_secp256k1_pubkey: ") + zkpoa_last_error(ctx));
+    for (uint64_t i = 0; i < owned; i++) {
+      if (status[i]) throw InputError("key " + std::to_string(g.line.empty() ? i + 1 : g.line[i]) + ": the key is zero or not below the group order");
+      balance[i] = g.balance[i];
+    }
+  }
+  // the filler accounts: D_j = Keccak-256(seed || "anon" || be64(j)), address = its last 20 bytes, balance = its first 8
+  // bytes (big-endian) mod 10^6; a million at a time
+  const size_t len = src.seed.size() + 12;
+  constexpr uint64_t kSlab = 1u << 20;
+  std::vector<uint8_t> msgs, digests;
+  for (uint64_t j0 = 0; owned + j0 < total; j0 += kSlab) {
+    const uint64_t m = std::min(kSlab, total - owned - j0);
+    msgs.resize(len * m);
+    digests.resize(32 * m);
+    parallel_ranges(m, 4096, [&](unsigned, uint64_t lo, uint64_t hi) {
+      for (uint64_t j = lo; j < hi; j++) {
+        uint8_t* q = &msgs[len * j];
+        memcpy(q, src.seed.data(), src.seed.size());
+        memcpy(q + src.seed.size(), "anon", 4);
+        for (int k = 0; k < 8; k++) q[src.seed.size() + 4 + k] = (uint8_t)((j0 + j) >> (8 * (7 - k)));
+      }
+    });
+    if (zkpoa_keccak256(ctx, msgs.data(), len, m, digests.data()) != PROVER_OK)
+      throw InputError(std::string("zkpoa_keccak256: ") + zkpoa_last_error(ctx));
+    parallel_ranges(m, 4096, [&](unsigned, uint64_t lo, uint64_t hi) {
+      for (uint64_t j = lo; j < hi; j++) {
+        const uint8_t* d = &digests[32 * j];
+        memcpy(&addr[20 * (owned + j0 + j)], d + 12, 20);
+        uint64_t head = 0;
+        for (int k = 0; k < 8; k++) head = (head << 8) | d[k];
+        balance[owned + j0 + j].v[0] = head % 1000000u;
+      }
+    });
+  }
+  lap("device");
+  const std::vector<uint32_t> order = order_by_address(addr.data(), total);
+  lap("sort");
+  write_entries(out_path, "address,eth_balance\n", "", total, 100, [&](std::string& o, uint64_t k) {
+    const uint64_t i = order[k];
+    o += "0x000000000000000000000000";
+    put_hex(o, &addr[20 * i], 20);
+    o += ",";
+    balance[i].append_dec(o);
+    o += "\n";
+  });
+  lap("write");
+  printf("Wrote an anonymity set of %llu addresses (%llu of them from keys) to %s\n", (unsigned long long)total, (unsigned long long)owned,
+         out_path.c_str());
+  return 0;
+}
+
 const char kUsage[] =
     "Usage: ecdsa-sigs-parser --signatures <in.json> --output-path <out.json>\n"
+    "       ecdsa-sigs-parser sign (--keys <file> | --generate-keys <N> --seed <text>)\n"
+    "                         (--message <text> | --msghash 0x<64 hex>) --output-path <signatures.json> [--write-keys <file>]\n"
+    "       ecdsa-sigs-parser anon-set (--keys <file> | --generate-keys <N> --seed <text>) --num-addresses <M>\n"
+    "                         --output-path <anonymity_set.csv>\n"
     "       ecdsa-sigs-parser layer-one-input --poa-input-data <parsed.json> --write-layer-one-data-to <out.json>\n"
     "                         [--account-start-index <i>] [--account-end-index <j>]\n"
     "       ecdsa-sigs-parser layer-two-input --poa-input-data <parsed.json> --merkle-root <merkle_root.json>\n"
@@ -407,6 +726,8 @@ int main(int argc, char** argv) {
   try {
     const std::string mode = argc > 1 ? argv[1] : "";
     if (mode == "layer-two-input" || mode == "layer-three-input" || mode == "pedersen-check") rc = layer_inputs_main(mode, argc, argv);
+    else if (mode == "sign") rc = sign_mode(argc, argv);
+    else if (mode == "anon-set") rc = anon_set_mode(argc, argv);
     else rc = first_modes_main(mode == "layer-one-input", argc, argv);
   } catch (const UsageError& e) {
     fprintf(stderr, "error: %s\n%s", e.what(), kUsage);
