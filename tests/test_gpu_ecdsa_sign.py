@@ -162,6 +162,24 @@ def test_round_trip_through_recovery(ctx, pool):
     assert st2 == bytes(257) and pk2 == pk and ad2 == ad
 
 
+def test_second_launch_of_one_lane(ctx):
+    """2^20 + 1 keys: the second launch of zkpoa_ecdsa_sign and of zkpoa_secp256k1_pubkey holds the last one alone."""
+    n = (1 << 20) + 1
+    seed, h = b"slab", hashlib.sha256(b"slab").digest()
+    keys = ctx.secp256k1_derive_keys(seed, 0, n)
+    r, s, v, pk, ad, st = ctx.ecdsa_sign(keys, h, 0)
+    assert st == bytes(n)
+    assert ctx.secp256k1_pubkey(keys) == (pk, ad, bytes(n))
+    rp, pk2, ad2, st2 = ctx.ecdsa_star(r, s, h * n, v, ad)
+    assert st2 == bytes(n)
+    assert pk2 == pk and ad2 == ad
+    i = n - 1
+    d = sg.derive_key(seed, i)
+    assert keys[32 * i:] == be(d)
+    assert dict(status=st[i], r=ints(r, i), s=ints(s, i), v=v[i], pub=(ints(pk, 2 * i), ints(pk, 2 * i + 1)), address=ad[20 * i:]) == \
+        want_sign(d, int.from_bytes(h, "big"))
+
+
 # ---- the commands ------------------------------------------------------------------------------------------------------
 def run(argv):
     return subprocess.run([str(a) for a in argv], capture_output=True, text=True, timeout=120)

@@ -1,6 +1,7 @@
 """secp256k1 recovery, Keccak-256 and Ethereum addresses on the device (zkpoa_ecdsa_star, zkpoa_keccak256,
 zkpoa_eth_address) and the ecdsa-sigs-parser command, against tests/secp_ref.py. Every entry's every output and status
 is compared; nothing is left out of a comparison."""
+import hashlib
 import json
 import random
 import subprocess
@@ -8,6 +9,7 @@ import subprocess
 import pytest
 
 import secp_ref as sr
+import sign_ref as sg
 from test_secp_ref import fixture_text, sigs_bin  # noqa: F401  (sigs_bin is a fixture)
 
 pytestmark = pytest.mark.gpu
@@ -280,3 +282,45 @@ def test_command_stops_at_a_bad_entry(sigs_bin, tmp_path, pool, what):
         assert doc[17]["address"] in lines[0] and given in lines[0]
     assert not out.exists()
     assert list(tmp_path.iterdir()) == [tmp_path / "signatures.json"]
+
+
+def test_command_on_no_signatures(sigs_bin, tmp_path):
+    rc, out = parse(sigs_bin, tmp_path, "[]")
+    assert rc.returncode == 0, rc.stderr
+    assert out.read_text() == '{\n  "accountAttestations": []\n}'
+
+
+def test_commands_across_a_round_of_the_writer(sigs_bin, tmp_path):
+    """65537 entries: the writers of both commands begin a second round of 2^16 for the last one. The parser derives
+    every address again from its signature and refuses a mismatch, so its exit status checks all of the sign file."""
+    n = (1 << 16) + 1
+    sigs, parsed = tmp_path / "signatures.json", tmp_path / "parsed.json"
+    for argv in ([sigs_bin, "sign", "--generate-keys", str(n), "--seed", "round", "--message", "m", "--output-path", str(sigs)],
+                 [sigs_bin, "--signatures", str(sigs), "--output-path", str(parsed)]):
+        rc = subprocess.run(argv, capture_output=True, text=True, timeout=120)
+        assert rc.returncode == 0, rc.stderr
+    given, got = json.loads(sigs.read_text()), json.loads(parsed.read_text())["accountAttestations"]
+    assert len(given) == n and len(got) == n
+    for i in (n - 2, n - 1):
+        assert [int(got[i]["signature"][k]["__bigint__"]) for k in "rs"] == [int(given[i]["signature"][k], 16) for k in "rs"], i
+
+
+def test_second_launch_of_one_lane(ctx):
+    """2^18 + 1 signatures made by zkpoa_ecdsa_sign: the recovery's second launch holds the last one alone."""
+    n = (1 << 18) + 1
+    seed, h = b"slab", hashlib.sha256(b"slab").digest()
+    keys = ctx.secp256k1_derive_keys(seed, 0, n)
+    r, s, v, pk, ad, st = ctx.ecdsa_sign(keys, h, 0)
+    assert st == bytes(n)
+    rp, pk2, ad2, st2 = ctx.ecdsa_star(r, s, h * n, v, ad)
+    assert st2 == bytes(n)
+    assert pk2 == pk and ad2 == ad
+    i, z = n - 1, int.from_bytes(h, "big")
+    d = sg.derive_key(seed, i)
+    assert keys[32 * i:] == be(d)
+    want = sg.sign(d, z)
+    assert (want["status"], be(want["r"]), be(want["s"]), want["v"]) == (0, r[32 * i:], s[32 * i:], v[i])
+    assert sr.recover(want["r"], want["s"], want["v"], z, want["address"]) == \
+        (sr.OK, int.from_bytes(rp[32 * i:], "big"), (int.from_bytes(pk2[64 * i:64 * i + 32], "big"), int.from_bytes(pk2[64 * i + 32:], "big")),
+         ad2[20 * i:])
+    assert want["pub"] == (int.from_bytes(pk[64 * i:64 * i + 32], "big"), int.from_bytes(pk[64 * i + 32:], "big")) and want["address"] == ad[20 * i:]

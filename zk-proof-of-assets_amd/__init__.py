@@ -149,6 +149,19 @@ class Context:
     def poseidon2_device(self, d_left, d_right, n, d_out):
         self._check(lib().zkpoa_poseidon2_device(self._h, d_left, d_right, n, d_out), "zkpoa_poseidon2_device")
 
+    # ---- one item per lane: the calls of include/zkpoa_prover.h and include/zkpoa_ecdsa_sign.h below --------------------
+    def _lanes(self, name, args, out_sizes):
+        """The C function `name`(handle, *args, *outputs): the bytes-like ones among args go over as buffers, the integers
+        as they are, and there is one output buffer per size -> the outputs' bytes, in order."""
+        ins = [a if isinstance(a, int) else _buf(bytes(a)) for a in args]
+        outs = [_Out(k) for k in out_sizes]
+        self._check(getattr(lib(), name)(self._h, *([a if isinstance(a, int) else a[0] for a in ins] + outs)), name)
+        return tuple(o.bytes() for o in outs)
+
+    def _hashes(self, name, messages, length):
+        n, data = (len(messages) // length, messages) if length else (int(messages), b"")
+        return self._lanes(name, (data, length, n), [32 * n])[0]
+
     # ---- ECDSA -> ECDSA* (scripts/ecdsa_sigs_parser.ts): 32-byte integers big-endian ------------------------------
     def ecdsa_star(self, r, s, msghash, v, addresses):
         """n signatures: r, s, msghash n x 32 B big-endian, v n bytes, addresses n x 20 B ->
@@ -156,68 +169,39 @@ class Context:
         n = len(v)
         if len(r) != 32 * n or len(s) != 32 * n or len(msghash) != 32 * n or len(addresses) != 20 * n:
             raise ZkpoaError("ecdsa_star: the arrays do not describe %d signatures" % n)
-        bufs = [_buf(bytes(x)) for x in (r, s, msghash, v, addresses)]
-        outs = [_Out(k * n) for k in (32, 64, 20, 1)]
-        self._check(lib().zkpoa_ecdsa_star(self._h, n, *([b[0] for b in bufs] + outs)), "zkpoa_ecdsa_star")
-        return tuple(o.bytes() for o in outs)
+        return self._lanes("zkpoa_ecdsa_star", (n, r, s, msghash, v, addresses), [32 * n, 64 * n, 20 * n, n])
 
     def keccak256(self, messages, length):
         """Keccak-256 of len(messages) / length messages of `length` bytes packed back to back (length 0: pass n)."""
-        if length:
-            n, data = len(messages) // length, bytes(messages)
-        else:
-            n, data = int(messages), b""
-        pm, km = _buf(data)
-        out = _Out(32 * n)
-        self._check(lib().zkpoa_keccak256(self._h, pm, length, n, out), "zkpoa_keccak256")
-        return out.bytes()
+        return self._hashes("zkpoa_keccak256", messages, length)
 
     def eth_address(self, pubkeys):
         """ethers.computeAddress for n x 64 B keys (x || y big-endian) -> (n x 20 B, list of n EIP-55 strings)."""
         n = len(pubkeys) // 64
-        pk, kk = _buf(bytes(pubkeys))
-        addr, text = _Out(20 * n), _Out(42 * n)
-        self._check(lib().zkpoa_eth_address(self._h, pk, n, addr, text), "zkpoa_eth_address")
-        chars = text.bytes().decode()        # bytes() copies the whole buffer: once, not per key
-        return addr.bytes(), [chars[42 * i:42 * i + 42] for i in range(n)]
+        addr, text = self._lanes("zkpoa_eth_address", (pubkeys, n), [20 * n, 42 * n])
+        chars = text.decode()
+        return addr, [chars[42 * i:42 * i + 42] for i in range(n)]
 
     # ---- signing (tests/generate_ecdsa_signatures.ts): include/zkpoa_ecdsa_sign.h; 32-byte integers big-endian -----
     def sha256(self, messages, length):
         """SHA-256 of len(messages) / length messages of `length` bytes packed back to back (length 0: pass n)."""
-        if length:
-            n, data = len(messages) // length, bytes(messages)
-        else:
-            n, data = int(messages), b""
-        pm, km = _buf(data)
-        out = _Out(32 * n)
-        self._check(lib().zkpoa_sha256_batch(self._h, pm, length, n, out), "zkpoa_sha256_batch")
-        return out.bytes()
+        return self._hashes("zkpoa_sha256_batch", messages, length)
 
     def secp256k1_pubkey(self, seckeys):
         """n x 32 B keys -> (keys n x 64 B (x || y), addresses n x 20 B, status bytes: 1 = key zero or not below n)."""
         n = len(seckeys) // 32
-        pk, kk = _buf(bytes(seckeys))
-        outs = [_Out(k * n) for k in (64, 20, 1)]
-        self._check(lib().zkpoa_secp256k1_pubkey(self._h, n, pk, *outs), "zkpoa_secp256k1_pubkey")
-        return tuple(o.bytes() for o in outs)
+        return self._lanes("zkpoa_secp256k1_pubkey", (n, seckeys), [64 * n, 20 * n, n])
 
     def secp256k1_derive_keys(self, seed, first, n):
         """The n keys (SHA-256(seed || be64(i)) mod (n - 1)) + 1 for i = first ..: n x 32 B."""
-        ps, ks = _buf(bytes(seed))
-        out = _Out(32 * n)
-        self._check(lib().zkpoa_secp256k1_derive_keys(self._h, ps, len(seed), first, n, out), "zkpoa_secp256k1_derive_keys")
-        return out.bytes()
+        return self._lanes("zkpoa_secp256k1_derive_keys", (seed, len(seed), first, n), [32 * n])[0]
 
     def rfc6979_nonce(self, seckeys, msghash, skip=0):
         """The RFC 6979 candidate after `skip` refusals for n keys and n hashes (n x 32 B each) -> n x 32 B."""
         n = len(seckeys) // 32
         if len(msghash) != 32 * n:
             raise ZkpoaError("rfc6979_nonce: %d keys need as many hashes" % n)
-        pk, kk = _buf(bytes(seckeys))
-        pz, kz = _buf(bytes(msghash))
-        out = _Out(32 * n)
-        self._check(lib().zkpoa_rfc6979_nonce(self._h, n, pk, pz, skip, out), "zkpoa_rfc6979_nonce")
-        return out.bytes()
+        return self._lanes("zkpoa_rfc6979_nonce", (n, seckeys, msghash, skip), [32 * n])[0]
 
     def ecdsa_sign(self, seckeys, msghash, stride=None):
         """n signatures with RFC 6979 nonces and low s. msghash: 32 B for all keys or n x 32 B (stride: 0 / 32, by default
@@ -227,11 +211,7 @@ class Context:
             stride = 0 if len(msghash) == 32 and n != 1 else 32
         if stride in (0, 32) and len(msghash) != (32 * n if stride else 32):
             raise ZkpoaError("ecdsa_sign: the hashes do not fit %d keys with stride %d" % (n, stride))
-        pk, kk = _buf(bytes(seckeys))
-        pz, kz = _buf(bytes(msghash))
-        outs = [_Out(k * n) for k in (32, 32, 1, 64, 20, 1)]
-        self._check(lib().zkpoa_ecdsa_sign(self._h, n, pk, pz, stride, *outs), "zkpoa_ecdsa_sign")
-        return tuple(o.bytes() for o in outs)
+        return self._lanes("zkpoa_ecdsa_sign", (n, seckeys, msghash, stride), [32 * n, 32 * n, n, 64 * n, 20 * n, n])
 
     def merkle_build(self, addresses, balances, device=False, n=None):
         """Tree over (address, balance) pairs: host buffers (n x 32 B LE each) or, with device=True, device pointers."""

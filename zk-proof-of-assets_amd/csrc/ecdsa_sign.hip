@@ -3,8 +3,8 @@
 // batched SHA-256, public keys, the nonce candidates, and the derived keys of `ecdsa-sigs-parser sign --generate-keys`.
 // The arithmetic is csrc/secp256k1.hip.h and csrc/sha256.hip.h; this file is the kernels and the C ABI
 // (include/zkpoa_ecdsa_sign.h). Not hardened against side channels: see the header.
+#include "lane_batch.hip.h"
 #include "secp256k1.hip.h"
-#include "zkpoa_internal.hpp"
 
 #include <mutex>
 
@@ -31,11 +31,7 @@ __global__ __launch_bounds__(kSignThreads) void ecdsa_sign_kernel(const void* __
   store_be32(out_r, t, res.r.l);
   store_be32(out_s, t, res.s.l);
   out_v[t] = (uint8_t)res.v;
-  store_be32(out_pubkey, 2 * t, res.q.x.l);
-  store_be32(out_pubkey, 2 * t + 1, res.q.y.l);
-#pragma unroll
-  for (int i = 0; i < 5; i++) out_address[5 * t + i] = res.addr[i];
-  out_status[t] = (uint8_t)res.status;
+  store_key_outputs(t, res.q, res.addr, res.status, out_pubkey, out_address, out_status);
 }
 
 __global__ __launch_bounds__(kSignThreads) void pubkey_kernel(const void* __restrict__ seckeys, const AffineK* __restrict__ ftab, uint64_t n,
@@ -46,11 +42,7 @@ __global__ __launch_bounds__(kSignThreads) void pubkey_kernel(const void* __rest
   uint32_t d[8];
   load_be32(seckeys, t, d);
   const PublicKey res = public_key(d, ftab);
-  store_be32(out_pubkey, 2 * t, res.q.x.l);
-  store_be32(out_pubkey, 2 * t + 1, res.q.y.l);
-#pragma unroll
-  for (int i = 0; i < 5; i++) out_address[5 * t + i] = res.addr[i];
-  out_status[t] = (uint8_t)res.status;
+  store_key_outputs(t, res.q, res.addr, res.status, out_pubkey, out_address, out_status);
 }
 
 __global__ __launch_bounds__(kSignThreads) void rfc6979_nonce_kernel(const void* __restrict__ seckeys, const void* __restrict__ msghash,
@@ -91,40 +83,19 @@ const AffineK* fixed_table_host() {
   return tab;
 }
 
-// A call's device memory that held keys or nonces: overwritten on the stream before it is given back.
-struct SecretBuf {
-  DevBuf buf;
-  size_t bytes;
-  hipStream_t st;
-  SecretBuf(size_t n, hipStream_t s) : buf(n), bytes(n), st(s) {}
-  ~SecretBuf() {
-    if (bytes) (void)hipMemsetAsync(buf.p, 0, bytes, st);
-    (void)hipStreamSynchronize(st);
-  }
-};
-
-uint32_t blocks_of(uint64_t lanes, uint32_t threads) { return (uint32_t)((lanes + threads - 1) / threads); }
-
-void finish(hipStream_t st) {
-  ZK_HIP(hipStreamSynchronize(st));
-  ZK_HIP(hipGetLastError());
-}
-
 }  // namespace
 
 extern "C" int zkpoa_sha256_batch(zkpoa_context* ctx, const void* messages, uint64_t message_len, uint64_t n, void* out32) {
   ZK_API_BEGIN(ctx)
   if (message_len > 4096) throw HipError("sha256: messages of at most 4096 bytes");
-  if (n == 0) return PROVER_OK;
-  if (n > (1ull << 32)) throw HipError("sha256: at most 2^32 messages per call");
-  if ((!messages && message_len) || !out32) throw HipError("sha256: null argument");
-  DevBuf dm(message_len * n), dout(32 * n);
-  dm.up(messages, message_len * n);
+  if (!batch_wanted("sha256", "messages", n, (messages || !message_len) && out32)) return PROVER_OK;
+  LaneIn dm(messages, message_len, n);
+  LaneOut dout(out32, 32, n);
   hipStream_t st = ctx->dev.lanes[0].stream;
-  hipLaunchKernelGGL(sha256_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, st, static_cast<const uint8_t*>(dm.p), (uint32_t)message_len, n,
-                     static_cast<uint32_t*>(dout.p));
+  hipLaunchKernelGGL(sha256_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, st, dm.at<const uint8_t>(0), (uint32_t)message_len, n,
+                     dout.at<uint32_t>(0));
   finish(st);
-  ZK_HIP(hipMemcpy(out32, dout.p, 32 * n, hipMemcpyDeviceToHost));
+  dout.down();
   ZK_API_END(ctx)
 }
 
@@ -132,59 +103,46 @@ extern "C" int zkpoa_secp256k1_derive_keys(zkpoa_context* ctx, const void* seed,
                                            void* out_seckeys) {
   ZK_API_BEGIN(ctx)
   if (seed_len > 4096) throw HipError("derive_keys: a seed of at most 4096 bytes");
-  if (n == 0) return PROVER_OK;
-  if (n > (1ull << 32)) throw HipError("derive_keys: at most 2^32 keys per call");
-  if ((!seed && seed_len) || !out_seckeys) throw HipError("derive_keys: null argument");
+  if (!batch_wanted("derive_keys", "keys", n, (seed || !seed_len) && out_seckeys)) return PROVER_OK;
   hipStream_t st = ctx->dev.lanes[0].stream;
-  DevBuf ds(seed_len);
-  ds.up(seed, seed_len);
-  SecretBuf dk(32 * n, st);
-  hipLaunchKernelGGL(derive_keys_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, st, static_cast<const uint8_t*>(ds.p), (uint32_t)seed_len,
-                     first, n, dk.buf.p);
+  LaneIn ds(seed, seed_len, 1);
+  LaneOut<SecretBuf> dk(out_seckeys, 32, n, st);
+  hipLaunchKernelGGL(derive_keys_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, st, ds.at<const uint8_t>(0), (uint32_t)seed_len, first, n,
+                     dk.at<void>(0));
   finish(st);
-  ZK_HIP(hipMemcpy(out_seckeys, dk.buf.p, 32 * n, hipMemcpyDeviceToHost));
+  dk.down();
   ZK_API_END(ctx)
 }
 
 extern "C" int zkpoa_secp256k1_pubkey(zkpoa_context* ctx, uint64_t n, const void* seckeys, void* out_pubkey_xy, void* out_address20,
                                       uint8_t* out_status) {
   ZK_API_BEGIN(ctx)
-  if (n == 0) return PROVER_OK;
-  if (n > (1ull << 32)) throw HipError("secp256k1_pubkey: at most 2^32 keys per call");
-  if (!seckeys || !out_pubkey_xy || !out_address20 || !out_status) throw HipError("secp256k1_pubkey: null argument");
+  if (!batch_wanted("secp256k1_pubkey", "keys", n, seckeys && out_pubkey_xy && out_address20 && out_status)) return PROVER_OK;
   hipStream_t st = ctx->dev.lanes[0].stream;
-  DevBuf dtab(kFixedEntries * sizeof(AffineK)), opk(64 * n), oad(20 * n), ost(n);
-  dtab.up(fixed_table_host(), kFixedEntries * sizeof(AffineK));
-  SecretBuf dk(32 * n, st);
-  dk.buf.up(seckeys, 32 * n);
-  for (uint64_t i0 = 0; i0 < n; i0 += kSignLanesMax) {
-    const uint64_t m = std::min(kSignLanesMax, n - i0);
-    hipLaunchKernelGGL(pubkey_kernel, dim3(blocks_of(m, kSignThreads)), dim3(kSignThreads), 0, st,
-                       static_cast<const char*>(dk.buf.p) + 32 * i0, static_cast<const AffineK*>(dtab.p), m,
-                       static_cast<char*>(opk.p) + 64 * i0, static_cast<uint32_t*>(oad.p) + 5 * i0, static_cast<uint8_t*>(ost.p) + i0);
-  }
+  LaneIn dtab(fixed_table_host(), sizeof(AffineK), kFixedEntries);
+  LaneOut opk(out_pubkey_xy, 64, n), oad(out_address20, 20, n), ost(out_status, 1, n);
+  LaneIn<SecretBuf> dk(seckeys, 32, n, st);
+  for_slabs(n, kSignLanesMax, [&](uint64_t i0, uint64_t m) {
+    hipLaunchKernelGGL(pubkey_kernel, dim3(blocks_of(m, kSignThreads)), dim3(kSignThreads), 0, st, dk.at<const void>(i0),
+                       dtab.at<const AffineK>(0), m, opk.at<void>(i0), oad.at<uint32_t>(i0), ost.at<uint8_t>(i0));
+  });
   finish(st);
-  ZK_HIP(hipMemcpy(out_pubkey_xy, opk.p, 64 * n, hipMemcpyDeviceToHost));
-  ZK_HIP(hipMemcpy(out_address20, oad.p, 20 * n, hipMemcpyDeviceToHost));
-  ZK_HIP(hipMemcpy(out_status, ost.p, n, hipMemcpyDeviceToHost));
+  for (const auto* o : {&opk, &oad, &ost}) o->down();
   ZK_API_END(ctx)
 }
 
 extern "C" int zkpoa_rfc6979_nonce(zkpoa_context* ctx, uint64_t n, const void* seckeys, const void* msghash, uint32_t skip, void* out_k) {
   ZK_API_BEGIN(ctx)
   if (skip > 64) throw HipError("rfc6979_nonce: skip is at most 64");
-  if (n == 0) return PROVER_OK;
-  if (n > (1ull << 32)) throw HipError("rfc6979_nonce: at most 2^32 keys per call");
-  if (!seckeys || !msghash || !out_k) throw HipError("rfc6979_nonce: null argument");
+  if (!batch_wanted("rfc6979_nonce", "keys", n, seckeys && msghash && out_k)) return PROVER_OK;
   hipStream_t st = ctx->dev.lanes[0].stream;
-  DevBuf dz(32 * n);
-  dz.up(msghash, 32 * n);
-  SecretBuf dk(32 * n, st), ok(32 * n, st);
-  dk.buf.up(seckeys, 32 * n);
-  hipLaunchKernelGGL(rfc6979_nonce_kernel, dim3(blocks_of(n, kSignThreads)), dim3(kSignThreads), 0, st, dk.buf.p, dz.p, (int)skip, n,
-                     ok.buf.p);
+  LaneIn dz(msghash, 32, n);
+  LaneIn<SecretBuf> dk(seckeys, 32, n, st);
+  LaneOut<SecretBuf> ok(out_k, 32, n, st);
+  hipLaunchKernelGGL(rfc6979_nonce_kernel, dim3(blocks_of(n, kSignThreads)), dim3(kSignThreads), 0, st, dk.at<const void>(0),
+                     dz.at<const void>(0), (int)skip, n, ok.at<void>(0));
   finish(st);
-  ZK_HIP(hipMemcpy(out_k, ok.buf.p, 32 * n, hipMemcpyDeviceToHost));
+  ok.down();
   ZK_API_END(ctx)
 }
 
@@ -193,36 +151,19 @@ extern "C" int zkpoa_ecdsa_sign(zkpoa_context* ctx, uint64_t n, const void* seck
   ZK_API_BEGIN(ctx)
   ctx->ms[8] = 0;
   if (msghash_stride != 0 && msghash_stride != 32) throw HipError("ecdsa_sign: msghash_stride is 0 (one hash) or 32 (one per key)");
-  if (n == 0) return PROVER_OK;
-  if (n > (1ull << 32)) throw HipError("ecdsa_sign: at most 2^32 keys per call");
-  if (!seckeys || !msghash || !out_r || !out_s || !out_v || !out_pubkey_xy || !out_address20 || !out_status)
-    throw HipError("ecdsa_sign: null argument");
+  if (!batch_wanted("ecdsa_sign", "keys", n, seckeys && msghash && out_r && out_s && out_v && out_pubkey_xy && out_address20 && out_status))
+    return PROVER_OK;
   hipStream_t st = ctx->dev.lanes[0].stream;
-  const uint64_t hashes = msghash_stride ? n : 1;
-  const uint32_t hash_words = msghash_stride ? 8u : 0u;
-  DevBuf dtab(kFixedEntries * sizeof(AffineK)), dz(32 * hashes);
-  DevBuf orr(32 * n), os(32 * n), ov(n), opk(64 * n), oad(20 * n), ost(n);
-  dtab.up(fixed_table_host(), kFixedEntries * sizeof(AffineK));
-  dz.up(msghash, 32 * hashes);
-  SecretBuf dk(32 * n, st);
-  dk.buf.up(seckeys, 32 * n);
-  ZK_HIP(hipEventRecord(ctx->ev_a[0], st));
-  for (uint64_t i0 = 0; i0 < n; i0 += kSignLanesMax) {
-    const uint64_t m = std::min(kSignLanesMax, n - i0);
-    hipLaunchKernelGGL(ecdsa_sign_kernel, dim3(blocks_of(m, kSignThreads)), dim3(kSignThreads), 0, st,
-                       static_cast<const char*>(dk.buf.p) + 32 * i0, static_cast<const uint32_t*>(dz.p) + hash_words * i0, hash_words,
-                       static_cast<const AffineK*>(dtab.p), m, static_cast<char*>(orr.p) + 32 * i0, static_cast<char*>(os.p) + 32 * i0,
-                       static_cast<uint8_t*>(ov.p) + i0, static_cast<char*>(opk.p) + 64 * i0, static_cast<uint32_t*>(oad.p) + 5 * i0,
-                       static_cast<uint8_t*>(ost.p) + i0);
-  }
-  ZK_HIP(hipEventRecord(ctx->ev_b[0], st));
-  finish(st);
-  ZK_HIP(hipEventElapsedTime(&ctx->ms[8], ctx->ev_a[0], ctx->ev_b[0]));
-  ZK_HIP(hipMemcpy(out_r, orr.p, 32 * n, hipMemcpyDeviceToHost));
-  ZK_HIP(hipMemcpy(out_s, os.p, 32 * n, hipMemcpyDeviceToHost));
-  ZK_HIP(hipMemcpy(out_v, ov.p, n, hipMemcpyDeviceToHost));
-  ZK_HIP(hipMemcpy(out_pubkey_xy, opk.p, 64 * n, hipMemcpyDeviceToHost));
-  ZK_HIP(hipMemcpy(out_address20, oad.p, 20 * n, hipMemcpyDeviceToHost));
-  ZK_HIP(hipMemcpy(out_status, ost.p, n, hipMemcpyDeviceToHost));
+  LaneIn dtab(fixed_table_host(), sizeof(AffineK), kFixedEntries), dz(msghash, 32, msghash_stride ? n : 1);
+  LaneOut orr(out_r, 32, n), os(out_s, 32, n), ov(out_v, 1, n), opk(out_pubkey_xy, 64, n), oad(out_address20, 20, n), ost(out_status, 1, n);
+  LaneIn<SecretBuf> dk(seckeys, 32, n, st);
+  timed_launches(ctx, st, [&] {
+    for_slabs(n, kSignLanesMax, [&](uint64_t i0, uint64_t m) {
+      hipLaunchKernelGGL(ecdsa_sign_kernel, dim3(blocks_of(m, kSignThreads)), dim3(kSignThreads), 0, st, dk.at<const void>(i0),
+                         dz.at<const uint32_t>(msghash_stride ? i0 : 0), msghash_stride ? 8u : 0u, dtab.at<const AffineK>(0), m,
+                         orr.at<void>(i0), os.at<void>(i0), ov.at<uint8_t>(i0), opk.at<void>(i0), oad.at<uint32_t>(i0), ost.at<uint8_t>(i0));
+    });
+  });
+  for (const auto* o : {&orr, &os, &ov, &opk, &oad, &ost}) o->down();
   ZK_API_END(ctx)
 }

@@ -2,8 +2,8 @@
 // (recover the public key, build r', derive the Ethereum address and compare it), one signature per lane, plus the two
 // pieces of it that stand on their own: batched Keccak-256 and ethers.computeAddress. The arithmetic is
 // csrc/secp256k1.hip.h and csrc/keccak.hip.h; this file is the kernels and the C ABI (include/zkpoa_prover.h).
+#include "lane_batch.hip.h"
 #include "secp256k1.hip.h"
-#include "zkpoa_internal.hpp"
 
 using namespace zkpoa;
 using namespace zkpoa::secp;
@@ -32,11 +32,7 @@ __global__ __launch_bounds__(kSigThreads) void ecdsa_star_kernel(const void* __r
   const LaneTable lt{tables + t, stride};
   const Recovered res = recover_one(rl, sl, zl, v[t], given, gtab, lt);
   store_be32(out_rprime, t, res.r_prime.l);
-  store_be32(out_pubkey, 2 * t, res.q.x.l);
-  store_be32(out_pubkey, 2 * t + 1, res.q.y.l);
-#pragma unroll
-  for (int i = 0; i < 5; i++) out_address[5 * t + i] = res.addr[i];
-  out_status[t] = (uint8_t)res.status;
+  store_key_outputs(t, res.q, res.addr, res.status, out_pubkey, out_address, out_status);
 }
 
 __global__ __launch_bounds__(256) void keccak256_kernel(const uint8_t* __restrict__ messages, uint32_t len, uint64_t n,
@@ -86,74 +82,52 @@ extern "C" int zkpoa_ecdsa_star(zkpoa_context* ctx, uint64_t n, const void* r, c
                                 uint8_t* out_status) {
   ZK_API_BEGIN(ctx)
   ctx->ms[8] = 0;
-  if (n == 0) return PROVER_OK;
-  if (n > (1ull << 32)) throw HipError("ecdsa_star: at most 2^32 signatures per call");
-  if (!r || !s || !msghash || !v || !address20 || !out_rprime || !out_pubkey_xy || !out_address20 || !out_status)
-    throw HipError("ecdsa_star: null argument");
+  if (!batch_wanted("ecdsa_star", "signatures", n,
+                    r && s && msghash && v && address20 && out_rprime && out_pubkey_xy && out_address20 && out_status))
+    return PROVER_OK;
   const uint64_t lanes = std::min<uint64_t>((n + kSigThreads - 1) / kSigThreads * kSigThreads, kSigLanesMax);
   AffineK gt[8];
   generator_table(gt);
-  DevBuf dr(32 * n), ds(32 * n), dz(32 * n), dv(n), da(20 * n), dg(sizeof(gt)), dtab(lanes * kTableBytesPerLane);
-  DevBuf orp(32 * n), opk(64 * n), oad(20 * n), ost(n);
-  dr.up(r, 32 * n);
-  ds.up(s, 32 * n);
-  dz.up(msghash, 32 * n);
-  dv.up(v, n);
-  da.up(address20, 20 * n);
-  dg.up(gt, sizeof(gt));
+  LaneIn dr(r, 32, n), ds(s, 32, n), dz(msghash, 32, n), dv(v, 1, n), da(address20, 20, n), dg(gt, sizeof(gt), 1);
+  DevBuf dtab(lanes * kTableBytesPerLane);
+  LaneOut orp(out_rprime, 32, n), opk(out_pubkey_xy, 64, n), oad(out_address20, 20, n), ost(out_status, 1, n);
   hipStream_t st = ctx->dev.lanes[0].stream;
-  ZK_HIP(hipEventRecord(ctx->ev_a[0], st));
-  for (uint64_t i0 = 0; i0 < n; i0 += lanes) {
-    const uint64_t m = std::min(lanes, n - i0);
-    hipLaunchKernelGGL(ecdsa_star_kernel, dim3((uint32_t)((m + kSigThreads - 1) / kSigThreads)), dim3(kSigThreads), 0, st,
-                       static_cast<const char*>(dr.p) + 32 * i0, static_cast<const char*>(ds.p) + 32 * i0,
-                       static_cast<const char*>(dz.p) + 32 * i0, static_cast<const uint8_t*>(dv.p) + i0,
-                       static_cast<const uint32_t*>(da.p) + 5 * i0, static_cast<const AffineK*>(dg.p),
-                       static_cast<uint32_t*>(dtab.p), lanes, m, static_cast<char*>(orp.p) + 32 * i0,
-                       static_cast<char*>(opk.p) + 64 * i0, static_cast<uint32_t*>(oad.p) + 5 * i0,
-                       static_cast<uint8_t*>(ost.p) + i0);
-  }
-  ZK_HIP(hipEventRecord(ctx->ev_b[0], st));
-  ZK_HIP(hipStreamSynchronize(st));
-  ZK_HIP(hipGetLastError());
-  ZK_HIP(hipEventElapsedTime(&ctx->ms[8], ctx->ev_a[0], ctx->ev_b[0]));
-  ZK_HIP(hipMemcpy(out_rprime, orp.p, 32 * n, hipMemcpyDeviceToHost));
-  ZK_HIP(hipMemcpy(out_pubkey_xy, opk.p, 64 * n, hipMemcpyDeviceToHost));
-  ZK_HIP(hipMemcpy(out_address20, oad.p, 20 * n, hipMemcpyDeviceToHost));
-  ZK_HIP(hipMemcpy(out_status, ost.p, n, hipMemcpyDeviceToHost));
+  timed_launches(ctx, st, [&] {
+    for_slabs(n, lanes, [&](uint64_t i0, uint64_t m) {
+      hipLaunchKernelGGL(ecdsa_star_kernel, dim3(blocks_of(m, kSigThreads)), dim3(kSigThreads), 0, st, dr.at<const void>(i0),
+                         ds.at<const void>(i0), dz.at<const void>(i0), dv.at<const uint8_t>(i0), da.at<const uint32_t>(i0),
+                         dg.at<const AffineK>(0), static_cast<uint32_t*>(dtab.p), lanes, m, orp.at<void>(i0), opk.at<void>(i0),
+                         oad.at<uint32_t>(i0), ost.at<uint8_t>(i0));
+    });
+  });
+  for (const auto* o : {&orp, &opk, &oad, &ost}) o->down();
   ZK_API_END(ctx)
 }
 
 extern "C" int zkpoa_keccak256(zkpoa_context* ctx, const void* messages, uint64_t message_len, uint64_t n, void* out32) {
   ZK_API_BEGIN(ctx)
   if (message_len > 4096) throw HipError("keccak256: messages of at most 4096 bytes");
-  if (n == 0) return PROVER_OK;
-  if (n > (1ull << 32)) throw HipError("keccak256: at most 2^32 messages per call");
-  if ((!messages && message_len) || !out32) throw HipError("keccak256: null argument");
-  DevBuf dm(message_len * n), dout(32 * n);
-  dm.up(messages, message_len * n);
+  if (!batch_wanted("keccak256", "messages", n, (messages || !message_len) && out32)) return PROVER_OK;
+  LaneIn dm(messages, message_len, n);
+  LaneOut dout(out32, 32, n);
   hipStream_t st = ctx->dev.lanes[0].stream;
-  hipLaunchKernelGGL(keccak256_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, static_cast<const uint8_t*>(dm.p),
-                     (uint32_t)message_len, n, static_cast<uint64_t*>(dout.p));
-  ZK_HIP(hipStreamSynchronize(st));
-  ZK_HIP(hipGetLastError());
-  ZK_HIP(hipMemcpy(out32, dout.p, 32 * n, hipMemcpyDeviceToHost));
+  hipLaunchKernelGGL(keccak256_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, st, dm.at<const uint8_t>(0), (uint32_t)message_len, n,
+                     dout.at<uint64_t>(0));
+  finish(st);
+  dout.down();
   ZK_API_END(ctx)
 }
 
 extern "C" int zkpoa_eth_address(zkpoa_context* ctx, const void* pubkey_xy, uint64_t n, void* out_address20, void* out_checksum42) {
   ZK_API_BEGIN(ctx)
-  if (n == 0) return PROVER_OK;
-  if (n > (1ull << 32)) throw HipError("eth_address: at most 2^32 keys per call");
-  if (!pubkey_xy || !out_address20 || !out_checksum42) throw HipError("eth_address: null argument");
-  DevBuf dk(64 * n), da(20 * n), dt(42 * n);
-  dk.up(pubkey_xy, 64 * n);
+  if (!batch_wanted("eth_address", "keys", n, pubkey_xy && out_address20 && out_checksum42)) return PROVER_OK;
+  LaneIn dk(pubkey_xy, 64, n);
+  LaneOut da(out_address20, 20, n), dt(out_checksum42, 42, n);
   hipStream_t st = ctx->dev.lanes[0].stream;
-  hipLaunchKernelGGL(eth_address_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, dk.p, n, static_cast<uint32_t*>(da.p),
-                     static_cast<uint8_t*>(dt.p));
-  ZK_HIP(hipStreamSynchronize(st));
-  ZK_HIP(hipGetLastError());
-  ZK_HIP(hipMemcpy(out_address20, da.p, 20 * n, hipMemcpyDeviceToHost));
-  ZK_HIP(hipMemcpy(out_checksum42, dt.p, 42 * n, hipMemcpyDeviceToHost));
+  hipLaunchKernelGGL(eth_address_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, st, dk.at<const void>(0), n, da.at<uint32_t>(0),
+                     dt.at<uint8_t>(0));
+  finish(st);
+  da.down();
+  dt.down();
   ZK_API_END(ctx)
 }

@@ -16,16 +16,12 @@
 #include "poseidon_host.hpp"
 
 #include <algorithm>
-#include <map>
 
 namespace zkpoa {
 namespace layer_inputs {
 
 struct InputError : std::runtime_error {
   explicit InputError(const std::string& m) : std::runtime_error(m) {}
-};
-struct UsageError : std::runtime_error {   // exit status 2 and the usage text
-  explicit UsageError(const std::string& m) : std::runtime_error(m) {}
 };
 
 inline U256 parse_number(const Span& s, const char* what) {   // decimal or 0x hex, below 2^256
@@ -83,45 +79,26 @@ struct BatchRange {
   }
 };
 
-// ---- the command line: the reference's option names, long (--name value, --name=value) and short -------------------
-struct Option {
-  const char *name, *alt;   // "--poa-input-data", "-i"
-};
-inline std::map<std::string, std::string> parse_options(int argc, char** argv, int first, const Option* known, size_t n_known) {
-  std::map<std::string, std::string> got;
-  for (int i = first; i < argc; i++) {
-    std::string a = argv[i], val;
-    bool has = false;
-    const size_t eq = a.find('=');
-    if (a.rfind("--", 0) == 0 && eq != std::string::npos) {
-      val = a.substr(eq + 1);
-      a = a.substr(0, eq);
-      has = true;
-    }
-    const Option* opt = nullptr;
-    for (size_t k = 0; k < n_known; k++)
-      if (a == known[k].name || (known[k].alt && a == known[k].alt)) opt = &known[k];
-    if (!opt) throw UsageError("unknown argument " + a);
-    if (!has) {
-      if (i + 1 >= argc) throw UsageError("option " + a + " needs a value");
-      val = argv[++i];
-    }
-    got[opt->name] = val;
-  }
-  return got;
-}
-inline const std::string& required(const std::map<std::string, std::string>& got, const char* mode, const char* name) {
-  const auto it = got.find(name);
-  if (it == got.end() || it->second.empty()) throw InputError(std::string(mode) + " needs " + name + " <value>");
-  return it->second;
-}
-inline long long index_option(const std::map<std::string, std::string>& got, const char* name, long long otherwise) {
-  const auto it = got.find(name);
-  if (it == got.end()) return otherwise;
-  char* rest = nullptr;
-  const long long v = strtoll(it->second.c_str(), &rest, 10);
-  if (rest == it->second.c_str() || *rest) throw UsageError(std::string(name) + " is not an integer");
-  return v;
+// The accountAttestations of a parsed-signatures file: entry(js, i) reads element i; the elements the range cannot reach
+// are skipped unread (BatchRange(): none is). -> the array's length
+template <class Fn>
+long long for_each_attestation(const std::string& path, const BatchRange& range, Fn entry) {
+  MappedFile text(path.c_str());
+  Json js{text.begin(), text.end()};
+  long long total = 0;
+  bool seen = false;
+  js.object([&](const Span& key) {
+    if (!key.is("accountAttestations")) return js.skip();
+    seen = true;
+    js.array([&](uint64_t i) {
+      total = (long long)i + 1;
+      if (!range.reaches(i)) return js.skip();
+      entry(js, i);
+    });
+  });
+  js.end();
+  if (!seen) throw InputError("no accountAttestations in " + path);
+  return total;
 }
 
 // ---- JSON.stringify(value, null, 2) of a value as it stands in a file: the layout changes, scalars are copied -------
@@ -158,45 +135,32 @@ struct Account {
 // accountAttestations[i].signature.pubkey.{x, y} and .accountData.{address, balance} of the entries the range reaches;
 // -> the array's length
 inline long long read_accounts(const std::string& path, const BatchRange& range, std::vector<Account>& kept) {
-  MappedFile text(path.c_str());
-  Json js{text.begin(), text.end()};
-  long long total = 0;
-  bool seen = false;
-  js.object([&](const Span& key) {
-    if (!key.is("accountAttestations")) return js.skip();
-    seen = true;
-    js.array([&](uint64_t i) {
-      total = (long long)i + 1;
-      if (!range.reaches(i)) return js.skip();
-      Account a;
-      unsigned have = 0;
-      js.object([&](const Span& k1) {
-        if (k1.is("signature")) {
-          js.object([&](const Span& k2) {
-            if (!k2.is("pubkey")) return js.skip();
-            js.object([&](const Span& k3) {
-              if (k3.is("x")) a.x = read_bigint(js, "pubkey.x"), have |= 1u;
-              else if (k3.is("y")) a.y = read_bigint(js, "pubkey.y"), have |= 2u;
-              else js.skip();
-            });
-          });
-        } else if (k1.is("accountData")) {
-          js.object([&](const Span& k2) {
-            if (k2.is("address")) a.address = read_bigint(js, "accountData.address"), have |= 4u;
-            else if (k2.is("balance")) a.balance = read_bigint(js, "accountData.balance"), have |= 8u;
+  return for_each_attestation(path, range, [&](Json& js, uint64_t i) {
+    Account a;
+    unsigned have = 0;
+    js.object([&](const Span& k1) {
+      if (k1.is("signature")) {
+        js.object([&](const Span& k2) {
+          if (!k2.is("pubkey")) return js.skip();
+          js.object([&](const Span& k3) {
+            if (k3.is("x")) a.x = read_bigint(js, "pubkey.x"), have |= 1u;
+            else if (k3.is("y")) a.y = read_bigint(js, "pubkey.y"), have |= 2u;
             else js.skip();
           });
-        } else {
-          js.skip();
-        }
-      });
-      if (have != 15u) throw InputError(entry(i) + "needs signature.pubkey.{x, y} and accountData.{address, balance}");
-      kept.push_back(a);
+        });
+      } else if (k1.is("accountData")) {
+        js.object([&](const Span& k2) {
+          if (k2.is("address")) a.address = read_bigint(js, "accountData.address"), have |= 4u;
+          else if (k2.is("balance")) a.balance = read_bigint(js, "accountData.balance"), have |= 8u;
+          else js.skip();
+        });
+      } else {
+        js.skip();
+      }
     });
+    if (have != 15u) throw InputError(entry(i) + "needs signature.pubkey.{x, y} and accountData.{address, balance}");
+    kept.push_back(a);
   });
-  js.end();
-  if (!seen) throw InputError("no accountAttestations in " + path);
-  return total;
 }
 
 struct ProofsSlice {
@@ -481,36 +445,25 @@ inline int layer_three_mode(const std::string& root_path, const std::string& pro
 inline int pedersen_check_mode(const std::string& input_path, const std::string& public_path, const std::string& blinding_text) {
   const U256 blinding = parse_blinding_factor(blinding_text);
   U256 sum;
-  {
-    MappedFile text(input_path.c_str());
-    Json js{text.begin(), text.end()};
-    bool seen = false;
-    js.object([&](const Span& key) {
-      if (!key.is("accountAttestations")) return js.skip();
-      seen = true;
-      js.array([&](uint64_t i) {
-        bool have = false;
-        js.object([&](const Span& k1) {
-          if (!k1.is("accountData")) return js.skip();
-          js.object([&](const Span& k2) {
-            if (!k2.is("balance")) return js.skip();
-            const U256 b = read_bigint(js, "accountData.balance");
-            unsigned __int128 c = 0;
-            for (int k = 0; k < 4; k++) {
-              c += (unsigned __int128)sum.v[k] + b.v[k];
-              sum.v[k] = (uint64_t)c;
-              c >>= 64;
-            }
-            if (c) throw InputError("the balance sum is not below 2^256");
-            have = true;
-          });
-        });
-        if (!have) throw InputError(entry(i) + "needs accountData.balance");
+  for_each_attestation(input_path, BatchRange(), [&](Json& js, uint64_t i) {
+    bool have = false;
+    js.object([&](const Span& k1) {
+      if (!k1.is("accountData")) return js.skip();
+      js.object([&](const Span& k2) {
+        if (!k2.is("balance")) return js.skip();
+        const U256 b = read_bigint(js, "accountData.balance");
+        unsigned __int128 c = 0;
+        for (int k = 0; k < 4; k++) {
+          c += (unsigned __int128)sum.v[k] + b.v[k];
+          sum.v[k] = (uint64_t)c;
+          c >>= 64;
+        }
+        if (c) throw InputError("the balance sum is not below 2^256");
+        have = true;
       });
     });
-    js.end();
-    if (!seen) throw InputError("no accountAttestations in " + input_path);
-  }
+    if (!have) throw InputError(entry(i) + "needs accountData.balance");
+  });
   U256 signals[12];
   {
     MappedFile text(public_path.c_str());

@@ -390,6 +390,15 @@ ZK_HD void store_be32(void* base, uint64_t idx, const uint32_t (&l)[8]) {
 #pragma unroll
   for (int i = 0; i < 8; i++) w[i] = bswap32(l[7 - i]);
 }
+// what lane t of the recovery, signing and public-key kernels ends with: its key, address words and status
+ZK_HD void store_key_outputs(uint64_t t, const AffineK& q, const uint32_t (&addr)[5], uint32_t status, void* out_pubkey,
+                             uint32_t* out_address, uint8_t* out_status) {
+  store_be32(out_pubkey, 2 * t, q.x.l);
+  store_be32(out_pubkey, 2 * t + 1, q.y.l);
+#pragma unroll
+  for (int i = 0; i < 5; i++) out_address[5 * t + i] = addr[i];
+  out_status[t] = (uint8_t)status;
+}
 
 // ---- the Ethereum address of a public key --------------------------------------------------------------------------
 // Keccak-256 of the 64 bytes x || y (big-endian), last 20 bytes: as five words in memory order (word k = bytes 4k..)

@@ -19,6 +19,7 @@
 #include "layer_inputs.hpp"
 
 #include <algorithm>
+#include <map>
 
 using namespace zkpoa;
 using namespace zkpoa::layer_inputs;
@@ -33,11 +34,116 @@ bool parse_hex_u256(const Span& s, uint8_t* out) {
   return true;
 }
 
-void write_ranges(AtomicFile& fo, uint64_t& off, const std::vector<std::string>& parts) {
-  for (const std::string& s : parts) {
-    fo.put_at(off, s.data(), s.size());
-    off += s.size();
+// all of the text is a decimal integer (strtoll's: out of range gives the nearest end of the range)
+bool parse_integer(const std::string& t, long long& out) {
+  char* rest = nullptr;
+  out = strtoll(t.c_str(), &rest, 10);
+  return rest != t.c_str() && !*rest;
+}
+
+// ---- the command line: the reference's option names, long (--name value, --name=value) and short -------------------
+// What is wrong with a command line: its spelling (an unknown option, a value that is missing or no number, options that
+// do not go together), or a required option that is absent. How a mode answers either is in the table of modes.
+struct CliError : std::runtime_error {
+  bool absent;
+  explicit CliError(const std::string& m, bool absent_ = false) : std::runtime_error(m), absent(absent_) {}
+};
+struct Option {
+  const char *name, *alt;   // "--poa-input-data", "-i"
+};
+struct Cli {
+  const char* mode;
+  std::map<std::string, std::string> got;   // by the long name
+  bool has(const char* name) const { return got.count(name) != 0; }
+  const std::string& value(const char* name) const {   // "" when not given
+    static const std::string none;
+    const auto it = got.find(name);
+    return it == got.end() ? none : it->second;
   }
+  const std::string& required(const char* name) const {
+    if (value(name).empty()) throw CliError(std::string(mode) + " needs " + name + " <value>", true);
+    return value(name);
+  }
+  long long integer(const char* name, long long otherwise) const {
+    long long v = otherwise;
+    if (has(name) && !parse_integer(value(name), v)) throw CliError(std::string(name) + " is not an integer");
+    return v;
+  }
+  // a number of things, least .. 2^32, written as at most ten digits and nothing else
+  uint64_t count(const char* name, long long least, const char* complaint) const {
+    const std::string& s = value(name);
+    long long v;
+    if (s.size() > 10 || s.find_first_not_of("0123456789") != std::string::npos || !parse_integer(s, v) || v < least || v > (1ll << 32))
+      throw CliError(std::string(name) + " is not a number of " + complaint);
+    return (uint64_t)v;
+  }
+  BatchRange batch_range() const {
+    BatchRange range;
+    range.start = integer("--account-start-index", 0);
+    range.end = integer("--account-end-index", -1);
+    return range;
+  }
+};
+// help: -h / --help end the reading and are reported as "--help"
+Cli parse_options(int argc, char** argv, int first, const char* mode, const std::vector<Option>& known, bool help) {
+  Cli cli{mode, {}};
+  for (int i = first; i < argc; i++) {
+    std::string a = argv[i], val;
+    bool has = false;
+    const size_t eq = a.find('=');
+    if (a.rfind("--", 0) == 0 && eq != std::string::npos) {
+      val = a.substr(eq + 1);
+      a = a.substr(0, eq);
+      has = true;
+    }
+    if (help && (a == "-h" || a == "--help")) {
+      cli.got["--help"];
+      return cli;
+    }
+    const Option* opt = nullptr;
+    for (const Option& k : known)
+      if (a == k.name || (k.alt && a == k.alt)) opt = &k;
+    if (!opt) throw CliError("unknown argument " + a);
+    if (!has) {
+      if (i + 1 >= argc) throw CliError("option " + a + " needs a value");
+      val = argv[++i];
+    }
+    cli.got[opt->name] = val;
+  }
+  return cli;
+}
+
+// ---- the entry writer ----------------------------------------------------------------------------------------------
+void put_text(AtomicFile& fo, uint64_t& off, const std::string& s) {
+  fo.put_at(off, s.data(), s.size());
+  off += s.size();
+}
+
+// entry(o, i) appends entry i of n. The entries go to `off` in rounds of 2^16, each formatted by the host threads, a
+// thread taking at least `least` entries and expecting `bytes_each` bytes per entry.
+template <class Fn>
+void put_entries(AtomicFile& fo, uint64_t& off, uint64_t n, uint64_t least, uint64_t bytes_each, Fn entry) {
+  constexpr uint64_t kRound = 1u << 16;
+  for (uint64_t i0 = 0; i0 < n; i0 += kRound) {
+    std::vector<std::string> parts(host_threads() + 1);
+    parallel_ranges(std::min(kRound, n - i0), least, [&](unsigned t, uint64_t lo, uint64_t hi) {
+      std::string& o = parts[t];
+      o.reserve((hi - lo) * bytes_each);
+      for (uint64_t i = i0 + lo; i < i0 + hi; i++) entry(o, i);
+    });
+    for (const std::string& s : parts) put_text(fo, off, s);
+  }
+}
+
+// a whole file: head + the entries + tail, in place only when complete
+template <class Fn>
+void write_entries(const std::string& path, const std::string& head, const std::string& tail, uint64_t n, uint64_t bytes_each, Fn entry) {
+  AtomicFile fo(path.c_str());
+  uint64_t off = 0;
+  put_text(fo, off, head);
+  put_entries(fo, off, n, 256, bytes_each, entry);
+  put_text(fo, off, tail);
+  fo.commit();
 }
 
 // ---- parsing mode --------------------------------------------------------------------------------------------------
@@ -73,11 +179,9 @@ void read_signatures(const std::string& path, Signatures& g) {
             if (!parse_hex_bytes(js.string(), g.z.data() + 32 * i, 32)) throw InputError(entry(i) + "signature.msghash is not 0x + 64 hex digits");
             seen |= 4u;
           } else if (k2.is("v")) {
-            const Span num = js.number();
-            char* rest = nullptr;
-            const std::string t = num.str();
-            const long val = strtol(t.c_str(), &rest, 10);
-            if (!rest || *rest) throw InputError(entry(i) + "signature.v is not an integer: " + t);
+            const std::string t = js.number().str();
+            long long val;
+            if (!parse_integer(t, val)) throw InputError(entry(i) + "signature.v is not an integer: " + t);
             g.v[i] = (uint8_t)(val < 0 || val > 255 ? 255 : val);   // anything but 27 / 28 is status 1
             seen |= 8u;
           } else {
@@ -133,7 +237,9 @@ void put_big(std::string& o, const char* indent, const char* key, const U256& x,
   o += last ? "}\n" : "},\n";
 }
 
-int parse_mode(const std::string& in_path, const std::string& out_path) {
+int parse_mode(const Cli& cli) {
+  const std::string &in_path = cli.value("--signatures"), &out_path = cli.value("--output-path");
+  if (in_path.empty() || out_path.empty()) throw CliError("--signatures <FILE> and --output-path <FILE> are required", true);
   ContextStart start(device_from_env());   // the device starts up while this thread reads the file
   Signatures g;
   PhaseTimer lap("ecdsa-sigs-parser", 8);
@@ -160,43 +266,28 @@ int parse_mode(const std::string& in_path, const std::string& out_path) {
                        std::string(&text[42 * i], 42));
   }
   printf("Successfully parsed ECDSA signatures and converted them to ECDSA* signatures\n");
-  AtomicFile fo(out_path.c_str());
-  uint64_t off = 0;
-  const std::string head = n ? "{\n  \"accountAttestations\": [\n" : "{\n  \"accountAttestations\": []\n}";
-  fo.put_at(off, head.data(), head.size());
-  off += head.size();
-  constexpr uint64_t kRound = 1u << 16;
-  for (uint64_t i0 = 0; i0 < n; i0 += kRound) {
-    const uint64_t m = std::min(kRound, n - i0);
-    std::vector<std::string> parts(host_threads() + 1);
-    parallel_ranges(m, 256, [&](unsigned t, uint64_t lo, uint64_t hi) {
-      std::string& o = parts[t];
-      o.reserve((hi - lo) * 1400);
-      for (uint64_t i = i0 + lo; i < i0 + hi; i++) {
-        o += "    {\n      \"signature\": {\n";
-        put_big(o, "        ", "r", U256::from_be(&g.r[32 * i]), false);
-        put_big(o, "        ", "s", U256::from_be(&g.s[32 * i]), false);
-        put_big(o, "        ", "r_prime", U256::from_be(&rprime[32 * i]), false);
-        o += "        \"pubkey\": {\n";
-        put_big(o, "          ", "x", U256::from_be(&pub[64 * i]), false);
-        put_big(o, "          ", "y", U256::from_be(&pub[64 * i + 32]), true);
-        o += "        },\n        \"msghash\": {\n          \"__uint8array__\": [\n";
-        for (int k = 0; k < 32; k++) {
-          o += "            ";
-          o += std::to_string((unsigned)g.z[32 * i + k]);
-          o += k < 31 ? ",\n" : "\n";
-        }
-        o += "          ]\n        }\n      },\n      \"accountData\": {\n";
-        uint8_t a32[32] = {0};
-        memcpy(a32 + 12, &derived[20 * i], 20);
-        put_big(o, "        ", "address", U256::from_be(a32), false);
-        o += "        \"balance\": {\n          \"__bigint__\": \"" + g.balance[i] + "\"\n        }\n      }\n    }";
-        o += i + 1 < n ? ",\n" : "\n  ]\n}";
-      }
-    });
-    write_ranges(fo, off, parts);
-  }
-  fo.commit();
+  write_entries(out_path, n ? "{\n  \"accountAttestations\": [\n" : "{\n  \"accountAttestations\": []\n}", n ? "  ]\n}" : "", n, 1400,
+                [&](std::string& o, uint64_t i) {
+                  o += "    {\n      \"signature\": {\n";
+                  put_big(o, "        ", "r", U256::from_be(&g.r[32 * i]), false);
+                  put_big(o, "        ", "s", U256::from_be(&g.s[32 * i]), false);
+                  put_big(o, "        ", "r_prime", U256::from_be(&rprime[32 * i]), false);
+                  o += "        \"pubkey\": {\n";
+                  put_big(o, "          ", "x", U256::from_be(&pub[64 * i]), false);
+                  put_big(o, "          ", "y", U256::from_be(&pub[64 * i + 32]), true);
+                  o += "        },\n        \"msghash\": {\n          \"__uint8array__\": [\n";
+                  for (int k = 0; k < 32; k++) {
+                    o += "            ";
+                    o += std::to_string((unsigned)g.z[32 * i + k]);
+                    o += k < 31 ? ",\n" : "\n";
+                  }
+                  o += "          ]\n        }\n      },\n      \"accountData\": {\n";
+                  uint8_t a32[32] = {0};
+                  memcpy(a32 + 12, &derived[20 * i], 20);
+                  put_big(o, "        ", "address", U256::from_be(a32), false);
+                  o += "        \"balance\": {\n          \"__bigint__\": \"" + g.balance[i] + "\"\n        }\n      }\n    }";
+                  o += i + 1 < n ? ",\n" : "\n";
+                });
   lap("write");
   return 0;
 }
@@ -206,66 +297,52 @@ struct StarSig {
   U256 r, s, rprime, x, y, msghash;
 };
 
-int layer_one_mode(const std::string& in_path, const std::string& out_path, BatchRange range) {
-  const long long start = range.start, end = range.end;
+int layer_one_mode(const Cli& cli) {
+  BatchRange range = cli.batch_range();
+  const std::string &in_path = cli.value("--poa-input-data"), &out_path = cli.value("--write-layer-one-data-to");
+  if (in_path.empty() || out_path.empty())
+    throw CliError("layer-one-input needs --poa-input-data <FILE> and --write-layer-one-data-to <FILE>", true);
   printf("Preparing input for layer 1 using the following data:\n- System input: %s\n- Start index for batch: %lld\n"
          "- End index for batch: %lld\nPath to write processed data to: %s\n\n",
-         in_path.c_str(), start, end, out_path.c_str());
-  std::vector<StarSig> sigs;   // entries first_kept, first_kept + 1, ...
+         in_path.c_str(), range.start, range.end, out_path.c_str());
+  std::vector<StarSig> sigs;   // entries first_kept, first_kept + 1, ...: only those the range can reach are converted
   const long long first_kept = range.first_kept();
-  long long total = 0;
-  {
-    MappedFile text(in_path.c_str());
-    Json js{text.begin(), text.end()};
-    bool seen = false;
-    js.object([&](const Span& key) {
-      if (!key.is("accountAttestations")) return js.skip();
-      seen = true;
-      js.array([&](uint64_t i) {
-        // only the entries the range can reach are converted; the others are counted and skipped
-        total = (long long)i + 1;
-        if (!range.reaches(i)) return js.skip();
-        StarSig g;
-        unsigned have = 0;
-        js.object([&](const Span& k1) {
-          if (!k1.is("signature")) return js.skip();
-          js.object([&](const Span& k2) {
-            if (k2.is("r")) g.r = read_bigint(js, "r"), have |= 1u;
-            else if (k2.is("s")) g.s = read_bigint(js, "s"), have |= 2u;
-            else if (k2.is("r_prime")) g.rprime = read_bigint(js, "r_prime"), have |= 4u;
-            else if (k2.is("pubkey")) {
-              js.object([&](const Span& k3) {
-                if (k3.is("x")) g.x = read_bigint(js, "pubkey.x"), have |= 8u;
-                else if (k3.is("y")) g.y = read_bigint(js, "pubkey.y"), have |= 16u;
-                else js.skip();
-              });
-            } else if (k2.is("msghash")) {
-              js.object([&](const Span& k3) {
-                if (!k3.is("__uint8array__")) return js.skip();
-                uint8_t bytes[32] = {0};
-                const uint64_t len = js.array([&](uint64_t k) {
-                  const std::string t = js.number().str();
-                  char* rest = nullptr;
-                  const long val = strtol(t.c_str(), &rest, 10);
-                  if (!rest || *rest || val < 0 || val > 255 || k >= 32) throw InputError(entry(i) + "msghash is not 32 bytes");
-                  bytes[k] = (uint8_t)val;
-                });
-                if (len != 32) throw InputError(entry(i) + "msghash is not 32 bytes");
-                g.msghash = U256::from_be(bytes);
-                have |= 32u;
-              });
-            } else {
-              js.skip();
-            }
+  const long long total = for_each_attestation(in_path, range, [&](Json& js, uint64_t i) {
+    StarSig g;
+    unsigned have = 0;
+    js.object([&](const Span& k1) {
+      if (!k1.is("signature")) return js.skip();
+      js.object([&](const Span& k2) {
+        if (k2.is("r")) g.r = read_bigint(js, "r"), have |= 1u;
+        else if (k2.is("s")) g.s = read_bigint(js, "s"), have |= 2u;
+        else if (k2.is("r_prime")) g.rprime = read_bigint(js, "r_prime"), have |= 4u;
+        else if (k2.is("pubkey")) {
+          js.object([&](const Span& k3) {
+            if (k3.is("x")) g.x = read_bigint(js, "pubkey.x"), have |= 8u;
+            else if (k3.is("y")) g.y = read_bigint(js, "pubkey.y"), have |= 16u;
+            else js.skip();
           });
-        });
-        if (have != 63u) throw InputError(entry(i) + "signature needs r, s, r_prime, pubkey.x, pubkey.y and msghash");
-        sigs.push_back(g);
+        } else if (k2.is("msghash")) {
+          js.object([&](const Span& k3) {
+            if (!k3.is("__uint8array__")) return js.skip();
+            uint8_t bytes[32] = {0};
+            const uint64_t len = js.array([&](uint64_t k) {
+              long long val;
+              if (!parse_integer(js.number().str(), val) || val < 0 || val > 255 || k >= 32) throw InputError(entry(i) + "msghash is not 32 bytes");
+              bytes[k] = (uint8_t)val;
+            });
+            if (len != 32) throw InputError(entry(i) + "msghash is not 32 bytes");
+            g.msghash = U256::from_be(bytes);
+            have |= 32u;
+          });
+        } else {
+          js.skip();
+        }
       });
     });
-    js.end();
-    if (!seen) throw InputError("no accountAttestations in " + in_path);
-  }
+    if (have != 63u) throw InputError(entry(i) + "signature needs r, s, r_prime, pubkey.x, pubkey.y and msghash");
+    sigs.push_back(g);
+  });
   range.close(total);
   long long lo, hi;
   range.slice(total, lo, hi);
@@ -274,33 +351,25 @@ int layer_one_mode(const std::string& in_path, const std::string& out_path, Batc
   uint64_t off = 0;
   const char* names[5] = {"r", "s", "rprime", "pubkey", "msghash"};
   for (int f = 0; f < 5; f++) {
-    std::string headtxt = std::string(f ? "" : "{\n") + "  \"" + names[f] + (m ? "\": [\n" : "\": []");
-    fo.put_at(off, headtxt.data(), headtxt.size());
-    off += headtxt.size();
-    std::vector<std::string> parts(host_threads() + 1);
-    parallel_ranges(m, 1024, [&](unsigned t, uint64_t a, uint64_t b) {
-      std::string& o = parts[t];
-      for (uint64_t i = a; i < b; i++) {
-        const StarSig& g = sigs[(uint64_t)(lo - first_kept) + i];
-        const bool last = i + 1 == m;
-        if (f == 3) {
-          o += "    [\n";
-          put_limbs(o, "      ", g.x, false);
-          put_limbs(o, "      ", g.y, true);
-          o += last ? "    ]\n" : "    ],\n";
-        } else {
-          put_limbs(o, "    ", f == 0 ? g.r : f == 1 ? g.s : f == 2 ? g.rprime : g.msghash, last);
-        }
+    put_text(fo, off, std::string(f ? "" : "{\n") + "  \"" + names[f] + (m ? "\": [\n" : "\": []"));
+    put_entries(fo, off, m, 1024, 0, [&](std::string& o, uint64_t i) {
+      const StarSig& g = sigs[(uint64_t)(lo - first_kept) + i];
+      const bool last = i + 1 == m;
+      if (f == 3) {
+        o += "    [\n";
+        put_limbs(o, "      ", g.x, false);
+        put_limbs(o, "      ", g.y, true);
+        o += last ? "    ]\n" : "    ],\n";
+      } else {
+        put_limbs(o, "    ", f == 0 ? g.r : f == 1 ? g.s : f == 2 ? g.rprime : g.msghash, last);
       }
     });
-    write_ranges(fo, off, parts);
-    const std::string tail = std::string(m ? "  ]" : "") + (f < 4 ? ",\n" : "\n}");
-    fo.put_at(off, tail.data(), tail.size());
-    off += tail.size();
+    put_text(fo, off, std::string(m ? "  ]" : "") + (f < 4 ? ",\n" : "\n}"));
   }
   fo.commit();
   return 0;
 }
+
 
 // ---- sign and anon-set modes -----------------------------------------------------------------------------------------
 // The two files the workflow starts from, which the reference makes with tests/generate_ecdsa_signatures.ts (noble's
@@ -414,28 +483,6 @@ std::vector<uint32_t> order_by_address(const uint8_t* addr20, uint64_t n) {
   return idx;
 }
 
-// entry(o, i) appends entry i of n; the file is head + the entries in blocks of 2^16 over the host threads + tail
-template <class Fn>
-void write_entries(const std::string& path, const std::string& head, const std::string& tail, uint64_t n, uint64_t bytes_each, Fn entry) {
-  AtomicFile fo(path.c_str());
-  uint64_t off = 0;
-  fo.put_at(off, head.data(), head.size());
-  off += head.size();
-  constexpr uint64_t kRound = 1u << 16;
-  for (uint64_t i0 = 0; i0 < n; i0 += kRound) {
-    const uint64_t m = std::min(kRound, n - i0);
-    std::vector<std::string> parts(host_threads() + 1);
-    parallel_ranges(m, 256, [&](unsigned t, uint64_t lo, uint64_t hi) {
-      std::string& o = parts[t];
-      o.reserve((hi - lo) * bytes_each);
-      for (uint64_t i = i0 + lo; i < i0 + hi; i++) entry(o, i);
-    });
-    write_ranges(fo, off, parts);
-  }
-  fo.put_at(off, tail.data(), tail.size());
-  fo.commit();
-}
-
 // the key source of both modes: exactly one of --keys <file> and --generate-keys <N> --seed <text>
 struct KeySource {
   std::string file, seed;
@@ -443,37 +490,21 @@ struct KeySource {
   bool generate = false;
 };
 
-bool parse_count(const std::string& s, uint64_t& out) {
-  if (s.empty() || s.size() > 10) return false;
-  out = 0;
-  for (char c : s) {
-    if (c < '0' || c > '9') return false;
-    out = out * 10 + (uint64_t)(c - '0');
-  }
-  return out <= (1ull << 32);
-}
-
-KeySource key_source(const std::map<std::string, std::string>& got, const char* mode) {
+KeySource key_source(const Cli& cli) {
   KeySource src;
-  const bool file = got.count("--keys"), gen = got.count("--generate-keys");
-  if (file == gen) throw UsageError(std::string(mode) + " needs either --keys <file> or --generate-keys <N> --seed <text>");
+  const bool file = cli.has("--keys");
+  if (file == cli.has("--generate-keys")) throw CliError(std::string(cli.mode) + " needs either --keys <file> or --generate-keys <N> --seed <text>");
   if (file) {
-    if (got.count("--seed")) throw UsageError("--seed goes with --generate-keys");
-    src.file = got.at("--keys");
+    if (cli.has("--seed")) throw CliError("--seed goes with --generate-keys");
+    src.file = cli.value("--keys");
     return src;
   }
-  if (!got.count("--seed")) throw UsageError("--generate-keys needs --seed <text>");
-  if (!parse_count(got.at("--generate-keys"), src.count)) throw UsageError("--generate-keys is not a number of keys up to 2^32");
-  src.seed = got.at("--seed");
-  if (src.seed.size() > 4084) throw UsageError("--seed is at most 4084 bytes");
+  if (!cli.has("--seed")) throw CliError("--generate-keys needs --seed <text>");
+  src.count = cli.count("--generate-keys", 0, "keys up to 2^32");
+  src.seed = cli.value("--seed");
+  if (src.seed.size() > 4084) throw CliError("--seed is at most 4084 bytes");
   src.generate = true;
   return src;
-}
-
-const std::string& needed(const std::map<std::string, std::string>& got, const char* mode, const char* name) {
-  const auto it = got.find(name);
-  if (it == got.end() || it->second.empty()) throw UsageError(std::string(mode) + " needs " + name + " <value>");
-  return it->second;
 }
 
 void write_key_file(const std::string& path, const Keys& g) {
@@ -484,20 +515,17 @@ void write_key_file(const std::string& path, const Keys& g) {
   });
 }
 
-int sign_mode(int argc, char** argv) {
-  static const Option known[] = {{"--keys", nullptr}, {"--generate-keys", nullptr}, {"--seed", nullptr},       {"--message", nullptr},
-                                 {"--msghash", nullptr}, {"--output-path", "-o"},   {"--write-keys", nullptr}};
-  const auto got = parse_options(argc, argv, 2, known, 7);
-  const KeySource src = key_source(got, "sign");
-  if (got.count("--message") == got.count("--msghash")) throw UsageError("sign needs either --message <text> or --msghash 0x<64 hex digits>");
-  const std::string out_path = needed(got, "sign", "--output-path");
+int sign_mode(const Cli& cli) {
+  const KeySource src = key_source(cli);
+  if (cli.has("--message") == cli.has("--msghash")) throw CliError("sign needs either --message <text> or --msghash 0x<64 hex digits>");
+  const std::string& out_path = cli.required("--output-path");
   uint8_t z[32];
-  if (got.count("--message")) {
-    const std::string& msg = got.at("--message");
+  if (cli.has("--message")) {
+    const std::string& msg = cli.value("--message");
     zkpoa_sha256(msg.data(), msg.size(), z);
   } else {
-    const std::string& h = got.at("--msghash");
-    if (!parse_hex_bytes(Span{h.data(), h.data() + h.size()}, z, 32)) throw UsageError("--msghash is not 0x + 64 hex digits");
+    const std::string& h = cli.value("--msghash");
+    if (!parse_hex_bytes(Span{h.data(), h.data() + h.size()}, z, 32)) throw CliError("--msghash is not 0x + 64 hex digits");
   }
   ContextStart start(device_from_env());
   PhaseTimer lap("ecdsa-sigs-parser sign", 8);
@@ -537,21 +565,17 @@ int sign_mode(int argc, char** argv) {
     g.balance[i].append_dec(o);
     o += "n\"}";
   });
-  if (got.count("--write-keys")) write_key_file(got.at("--write-keys"), g);
+  if (cli.has("--write-keys")) write_key_file(cli.value("--write-keys"), g);
   lap("write");
   printf("Wrote %llu signatures to %s\n", (unsigned long long)n, out_path.c_str());
   return 0;
 }
 
-int anon_set_mode(int argc, char** argv) {
-  static const Option known[] = {{"--keys", nullptr}, {"--generate-keys", nullptr}, {"--seed", nullptr}, {"--num-addresses", "-n"},
-                                 {"--output-path", "-o"}};
-  const auto got = parse_options(argc, argv, 2, known, 5);
-  const KeySource src = key_source(got, "anon-set");
-  uint64_t total = 0;
-  if (!parse_count(needed(got, "anon-set", "--num-addresses"), total) || total == 0)
-    throw UsageError("--num-addresses is not a number of addresses from 1 to 2^32");
-  const std::string out_path = needed(got, "anon-set", "--output-path");
+int anon_set_mode(const Cli& cli) {
+  const KeySource src = key_source(cli);
+  cli.required("--num-addresses");
+  const uint64_t total = cli.count("--num-addresses", 1, "addresses from 1 to 2^32");
+  const std::string& out_path = cli.required("--output-path");
   ContextStart start(device_from_env());
   PhaseTimer lap("ecdsa-sigs-parser anon-set", 8);
   Keys g;
@@ -634,104 +658,72 @@ const char kUsage[] =
     "       ecdsa-sigs-parser pedersen-check --poa-input-data <parsed.json> --layer-three-public-inputs <public.json>\n"
     "                         --blindingFactor <decimal or 0x-hex>\n";
 
-// the three modes of layer_inputs.hpp: the reference's option names (-h is layer two's hash path, as there)
-int layer_inputs_main(const std::string& mode, int argc, char** argv) {
-  if (mode == "layer-two-input") {
-    static const Option known[] = {{"--poa-input-data", "-i"},           {"--merkle-root", "-t"},
-                                   {"--merkle-proofs", "-p"},            {"--write-x-coords-hash-to", "-h"},
-                                   {"--layer-one-sanitized-proof", "-d"}, {"--write-layer-two-data-to", "-o"},
-                                   {"--account-start-index", "-s"},      {"--account-end-index", "-e"}};
-    const auto got = parse_options(argc, argv, 2, known, 8);
-    BatchRange range;
-    range.start = index_option(got, "--account-start-index", 0);
-    range.end = index_option(got, "--account-end-index", -1);
-    LayerTwoPaths p;
-    const char* m = mode.c_str();
-    p.input = required(got, m, "--poa-input-data");
-    p.merkle_root = required(got, m, "--merkle-root");
-    p.merkle_proofs = required(got, m, "--merkle-proofs");
-    p.hash_out = required(got, m, "--write-x-coords-hash-to");
-    p.layer_one_proof = required(got, m, "--layer-one-sanitized-proof");
-    p.out = required(got, m, "--write-layer-two-data-to");
-    return layer_two_mode(p, range);
-  }
-  if (mode == "layer-three-input") {
-    static const Option known[] = {{"--merkle-root-path", "-m"}, {"--layer-two-sanitized-proof-paths", "-p"},
-                                   {"--write-layer-three-data-to", "-o"}, {"--blindingFactor", nullptr}};
-    const auto got = parse_options(argc, argv, 2, known, 4);
-    const char* m = mode.c_str();
-    return layer_three_mode(required(got, m, "--merkle-root-path"), required(got, m, "--layer-two-sanitized-proof-paths"),
-                            required(got, m, "--write-layer-three-data-to"), required(got, m, "--blindingFactor"));
-  }
-  static const Option known[] = {{"--poa-input-data", "-i"}, {"--layer-three-public-inputs", "-p"}, {"--blindingFactor", nullptr}};
-  const auto got = parse_options(argc, argv, 2, known, 3);
-  const char* m = mode.c_str();
-  return pedersen_check_mode(required(got, m, "--poa-input-data"), required(got, m, "--layer-three-public-inputs"),
-                             required(got, m, "--blindingFactor"));
+// the three modes of layer_inputs.hpp
+int layer_two_cli(const Cli& cli) {
+  const BatchRange range = cli.batch_range();
+  LayerTwoPaths p;
+  p.input = cli.required("--poa-input-data");
+  p.merkle_root = cli.required("--merkle-root");
+  p.merkle_proofs = cli.required("--merkle-proofs");
+  p.hash_out = cli.required("--write-x-coords-hash-to");
+  p.layer_one_proof = cli.required("--layer-one-sanitized-proof");
+  p.out = cli.required("--write-layer-two-data-to");
+  return layer_two_mode(p, range);
+}
+int layer_three_cli(const Cli& cli) {
+  return layer_three_mode(cli.required("--merkle-root-path"), cli.required("--layer-two-sanitized-proof-paths"),
+                          cli.required("--write-layer-three-data-to"), cli.required("--blindingFactor"));
+}
+int pedersen_check_cli(const Cli& cli) {
+  return pedersen_check_mode(cli.required("--poa-input-data"), cli.required("--layer-three-public-inputs"), cli.required("--blindingFactor"));
 }
 
-bool parse_index(const char* s, long long& out) {
-  char* rest = nullptr;
-  out = strtoll(s, &rest, 10);
-  return rest != s && !*rest;
-}
-
-// the parser and layer-one-input
-int first_modes_main(bool layer_one, int argc, char** argv) {
-  std::string in, out;
-  long long start = 0, end = -1;
-  for (int i = layer_one ? 2 : 1; i < argc; i++) {
-    std::string a = argv[i];
-    std::string val;
-    bool has = false;
-    const size_t eq = a.find('=');
-    if (a.rfind("--", 0) == 0 && eq != std::string::npos) {
-      val = a.substr(eq + 1);
-      a = a.substr(0, eq);
-      has = true;
-    }
-    auto value = [&]() -> std::string {
-      if (has) return val;
-      if (i + 1 >= argc) throw InputError("option " + a + " needs a value");
-      return argv[++i];
-    };
-    if (a == "-h" || a == "--help") {
-      printf("%s", kUsage);
-      return 0;
-    } else if (!layer_one && (a == "-s" || a == "--signatures")) in = value();
-    else if (!layer_one && (a == "-o" || a == "--output-path")) out = value();
-    else if (layer_one && (a == "-i" || a == "--poa-input-data")) in = value();
-    else if (layer_one && (a == "-o" || a == "--write-layer-one-data-to")) out = value();
-    else if (layer_one && (a == "-s" || a == "--account-start-index")) {
-      if (!parse_index(value().c_str(), start)) throw InputError("--account-start-index is not an integer");
-    } else if (layer_one && (a == "-e" || a == "--account-end-index")) {
-      if (!parse_index(value().c_str(), end)) throw InputError("--account-end-index is not an integer");
-    } else throw InputError("unknown argument " + a);
-  }
-  if (in.empty() || out.empty()) {
-    fprintf(stderr, layer_one ? "error: layer-one-input needs --poa-input-data <FILE> and --write-layer-one-data-to <FILE>\n"
-                              : "error: --signatures <FILE> and --output-path <FILE> are required\n");
-    return 2;
-  }
-  BatchRange range;
-  range.start = start;
-  range.end = end;
-  return layer_one ? layer_one_mode(in, out, range) : parse_mode(in, out);
-}
+// How a mode answers a CliError: with "error: ..." and the usage text (exit status 2), with "Error: ..." as for any
+// other failure (1), or with "error: ..." alone (2).
+enum Answer { kWithUsage, kAsFailure, kBrief };
+struct Mode {
+  const char* name;               // argv[1]; the parser itself has none, and its options begin there
+  std::vector<Option> options;    // the reference's names
+  Answer misspelt, absent;        // the answer to a command line that cannot be read, and to one that lacks a required option
+  bool help;                      // -h / --help print the usage (in layer-two-input -h is the hash path, as in the reference)
+  int (*run)(const Cli&);
+};
+const Mode kModes[] = {
+    {"sign", {{"--keys", nullptr}, {"--generate-keys", nullptr}, {"--seed", nullptr}, {"--message", nullptr}, {"--msghash", nullptr},
+              {"--output-path", "-o"}, {"--write-keys", nullptr}},
+     kWithUsage, kWithUsage, false, sign_mode},
+    {"anon-set", {{"--keys", nullptr}, {"--generate-keys", nullptr}, {"--seed", nullptr}, {"--num-addresses", "-n"}, {"--output-path", "-o"}},
+     kWithUsage, kWithUsage, false, anon_set_mode},
+    {"layer-one-input", {{"--poa-input-data", "-i"}, {"--write-layer-one-data-to", "-o"}, {"--account-start-index", "-s"},
+                         {"--account-end-index", "-e"}},
+     kAsFailure, kBrief, true, layer_one_mode},
+    {"layer-two-input", {{"--poa-input-data", "-i"}, {"--merkle-root", "-t"}, {"--merkle-proofs", "-p"}, {"--write-x-coords-hash-to", "-h"},
+                         {"--layer-one-sanitized-proof", "-d"}, {"--write-layer-two-data-to", "-o"}, {"--account-start-index", "-s"},
+                         {"--account-end-index", "-e"}},
+     kWithUsage, kAsFailure, false, layer_two_cli},
+    {"layer-three-input", {{"--merkle-root-path", "-m"}, {"--layer-two-sanitized-proof-paths", "-p"}, {"--write-layer-three-data-to", "-o"},
+                           {"--blindingFactor", nullptr}},
+     kWithUsage, kAsFailure, false, layer_three_cli},
+    {"pedersen-check", {{"--poa-input-data", "-i"}, {"--layer-three-public-inputs", "-p"}, {"--blindingFactor", nullptr}},
+     kWithUsage, kAsFailure, false, pedersen_check_cli},
+    {"", {{"--signatures", "-s"}, {"--output-path", "-o"}}, kAsFailure, kBrief, true, parse_mode},   // the last: any other first word
+};
 
 }  // namespace
 
 int main(int argc, char** argv) {
+  const Mode* mode = kModes;
+  while (*mode->name && !(argc > 1 && !strcmp(argv[1], mode->name))) mode++;
   int rc = 0;
   try {
-    const std::string mode = argc > 1 ? argv[1] : "";
-    if (mode == "layer-two-input" || mode == "layer-three-input" || mode == "pedersen-check") rc = layer_inputs_main(mode, argc, argv);
-    else if (mode == "sign") rc = sign_mode(argc, argv);
-    else if (mode == "anon-set") rc = anon_set_mode(argc, argv);
-    else rc = first_modes_main(mode == "layer-one-input", argc, argv);
-  } catch (const UsageError& e) {
-    fprintf(stderr, "error: %s\n%s", e.what(), kUsage);
-    rc = 2;
+    const Cli cli = parse_options(argc, argv, *mode->name ? 2 : 1, mode->name, mode->options, mode->help);
+    if (cli.has("--help")) printf("%s", kUsage);
+    else rc = mode->run(cli);
+  } catch (const CliError& e) {
+    const Answer how = e.absent ? mode->absent : mode->misspelt;
+    if (how == kAsFailure) fprintf(stderr, "Error: %s\n", e.what());
+    else fprintf(stderr, "error: %s\n%s", e.what(), how == kWithUsage ? kUsage : "");
+    rc = how == kAsFailure ? 1 : 2;
   } catch (const std::exception& e) {
     fprintf(stderr, "Error: %s\n", e.what());
     rc = 1;
