@@ -637,6 +637,11 @@ int zkpoa_eth_address(zkpoa_context* ctx, const void* pubkey_xy, uint64_t n, voi
  * tests/generate_anon_set.ts): five entry points, declared in a header of their own next to this one. */
 #include "zkpoa_ecdsa_sign.h"
 
+/* ---- HD-wallet key sources: BIP-32 children of one parent, batched SHA-512 / HMAC-SHA512; GPU, and host helpers ------
+ * Where `ecdsa-sigs-parser sign`, `anon-set` and `hd-list` take the keys of a mnemonic, an xprv or an xpub from: nine
+ * entry points, declared in a header of their own next to this one. */
+#include "zkpoa_hd_wallet.h"
+
 /* ---- the input steps after the proofs; host only, no context, no GPU -------------------------------------------
  * The Poseidon of any circomlib width, the sponge of input_prep_for_layer_two.ts and the ed25519 Pedersen commitment
  * of pedersen_commitment_checker.ts: four entry points, declared in a header of their own next to this one. */
@@ -647,7 +652,7 @@ int zkpoa_eth_address(zkpoa_context* ctx, const void* pubkey_xy, uint64_t n, voi
  * id: 0 = whole device part of last MSM, 1 = its bucket-accumulation kernel (dominant kernel),
  *     2 = last NTT, 3 = last prove: ABC+NTT chain, 4 = last prove: all MSMs, 5 = last prove: total,
  *     6 = last prove: self-check (host pairing check; 0 when it did not run), 7 = last Merkle tree build,
- *     8 = last zkpoa_ecdsa_star or zkpoa_ecdsa_sign: its kernels.
+ *     8 = last zkpoa_ecdsa_star, zkpoa_ecdsa_sign, zkpoa_bip32_children or zkpoa_bip32_tweak: its kernels.
  * Also: tuning knobs. key "msm_c" forces the Pippenger window (0 = auto); key "msm_max_points" sets the
  * number of points one bucket sort may take (0 = 2^27; larger MSMs run in chunks -- tests force small values);
  * key "prove_serial" = 1 runs the stages of a prove one after the other (solo device times for the roofline);

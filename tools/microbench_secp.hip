@@ -1,9 +1,10 @@
 // The parts the instruction bound of the ECDSA* kernel is built from: register-only loops of the
 // secp256k1 field product and square, the product modulo the group order, the three group operations of the ladder and
-// the Keccak permutation, and for the signing kernel the SHA-256 compression, at the recovery kernel's own shape (workgroups of 64, as many as fill the card twice at the
+// the Keccak permutation, for the signing kernel the SHA-256 compression and for BIP-32 the SHA-512 compression, at the recovery kernel's own shape (workgroups of 64, as many as fill the card twice at the
 // occupancy the compiler gives them). Prints operations per second of the whole card.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I zk-proof-of-assets_amd/csrc tools/microbench_secp.hip -o tools/microbench_secp
 #include "secp256k1.hip.h"
+#include "sha512.hip.h"
 #include <stdio.h>
 #include <algorithm>
 #include <vector>
@@ -28,7 +29,7 @@ __device__ uint32_t fold(const secp::Fp& a) {
 }
 
 // 0 Fp product, 1 Fp square, 2 product modulo n, 3 xyzz_dbl, 4 xyzz_add, 5 xyzz_add_affine, 6 Keccak-f[1600],
-// 7 SHA-256 compression
+// 7 SHA-256 compression, 8 SHA-512 compression
 template <int OP>
 __global__ __launch_bounds__(64) void k_op(const uint32_t* in, uint32_t* out, int iters) {
   const int t = blockIdx.x * 64 + threadIdx.x;
@@ -75,6 +76,18 @@ __global__ __launch_bounds__(64) void k_op(const uint32_t* in, uint32_t* out, in
     for (int i = 0; i < iters; i++) keccak::f1600(a);
 #pragma unroll
     for (int i = 0; i < 25; i++) res ^= (uint32_t)a[i] ^ (uint32_t)(a[i] >> 32);
+  } else if (OP == 8) {
+    uint64_t h[8], blk[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) blk[i] = ((uint64_t)in[(t + 2 * i) & 8191] << 32) | in[(t + 2 * i + 1) & 8191];
+    sha512::initial_state(h);
+#pragma unroll 1
+    for (int i = 0; i < iters; i++) {
+      sha512::compress(h, blk);
+      blk[3] ^= h[0];   // the next block depends on this state
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) res ^= (uint32_t)h[i] ^ (uint32_t)(h[i] >> 32);
   } else {
     uint32_t h[8], blk[16];
 #pragma unroll
@@ -128,5 +141,6 @@ int main() {
   run<5>("xyzz_add_affine", in, out, 2000);
   run<6>("Keccak-f[1600]", in, out, 2000);
   run<7>("SHA-256 compress", in, out, 4000);
+  run<8>("SHA-512 compress", in, out, 2000);
   return 0;
 }

@@ -213,6 +213,41 @@ class Context:
             raise ZkpoaError("ecdsa_sign: the hashes do not fit %d keys with stride %d" % (n, stride))
         return self._lanes("zkpoa_ecdsa_sign", (n, seckeys, msghash, stride), [32 * n, 32 * n, n, 64 * n, 20 * n, n])
 
+    # ---- HD-wallet key sources (BIP-32): include/zkpoa_hd_wallet.h; 32-byte integers big-endian, keys as 33 B key data --
+    def sha512(self, messages, length):
+        """SHA-512 of len(messages) / length messages of `length` bytes packed back to back (length 0: pass n) -> n x 64 B."""
+        n, data = (len(messages) // length, messages) if length else (int(messages), b"")
+        return self._lanes("zkpoa_sha512_batch", (data, length, n), [64 * n])[0]
+
+    def hmac_sha512(self, key, messages, length):
+        """HMAC-SHA512 of such a batch under one key of any length -> n x 64 B."""
+        n, data = (len(messages) // length, messages) if length else (int(messages), b"")
+        return self._lanes("zkpoa_hmac_sha512_batch", (key, len(key), data, length, n), [64 * n])[0]
+
+    def bip32_children(self, parent_key, chain, first, n):
+        """Children first .. first + n - 1 of one parent (33 B key data: 00 || k or 02 / 03 || x; 32 B chain code) ->
+        (key data n x 33 B, chain codes n x 32 B, keys n x 64 B (x || y), addresses n x 20 B, status bytes: 1 = BIP-32's
+        invalid child). A public parent with a hardened index in the range raises."""
+        if len(parent_key) != 33 or len(chain) != 32:
+            raise ZkpoaError("bip32_children: the parent is 33 B of key data and a 32 B chain code")
+        return self._lanes("zkpoa_bip32_children", (parent_key, chain, first, n), [33 * n, 32 * n, 64 * n, 20 * n, n])
+
+    def bip32_tweak(self, parent_key, tweaks):
+        """The child-key step after its HMAC, for n tweaks IL (n x 32 B) -> (key data, keys, addresses, status bytes)."""
+        n = len(tweaks) // 32
+        if len(parent_key) != 33:
+            raise ZkpoaError("bip32_tweak: the parent is 33 B of key data")
+        return self._lanes("zkpoa_bip32_tweak", (parent_key, n, tweaks), [33 * n, 64 * n, 20 * n, n])
+
+    def bip32_derive_path(self, key, chain, path):
+        """The key at `path` ("m/44'/60'/0'/0") below (key data, chain code) -> (key data, chain code)."""
+        if len(key) != 33 or len(chain) != 32:
+            raise ZkpoaError("bip32_derive_path: the key is 33 B of key data and a 32 B chain code")
+        ins = [_buf(bytes(key)), _buf(bytes(chain))]
+        outs = [_Out(33), _Out(32)]
+        self._check(lib().zkpoa_bip32_derive_path(self._h, ins[0][0], ins[1][0], path.encode(), *outs), "zkpoa_bip32_derive_path")
+        return outs[0].bytes(), outs[1].bytes()
+
     def merkle_build(self, addresses, balances, device=False, n=None):
         """Tree over (address, balance) pairs: host buffers (n x 32 B LE each) or, with device=True, device pointers."""
         return MerkleTree(self, addresses, balances, device, n)
@@ -870,6 +905,44 @@ def g2_sum(points):
     out = ctypes.create_string_buffer(128)
     lib().zkpoa_g2_sum(p, len(points) // 128, out)
     return out.raw
+
+
+# ---- HD wallets, host only (include/zkpoa_hd_wallet.h) ----------------------------------------------------------------
+def bip32_master(seed):
+    """The master key of a 16..64 B seed -> (key data 00 || k, chain code)."""
+    key, chain = _Out(33), _Out(32)
+    if lib().zkpoa_bip32_master(_buf(bytes(seed))[0], len(seed), key, chain) != PROVER_OK:
+        raise ZkpoaError("zkpoa_bip32_master: a seed of 16..64 bytes whose key is in [1, group order) is needed")
+    return key.bytes(), chain.bytes()
+
+
+def bip39_seed(mnemonic, passphrase=""):
+    """The 64 B seed of a mnemonic (PBKDF2-HMAC-SHA512, 2048 rounds). ASCII only; neither the word list nor the checksum
+    is checked."""
+    out = _Out(64)
+    try:
+        args = mnemonic.encode("ascii"), passphrase.encode("ascii")
+    except UnicodeEncodeError:
+        raise ZkpoaError("bip39_seed: ASCII only (NFKD normalisation is not implemented)")
+    if b"\0" in args[0] + args[1] or lib().zkpoa_bip39_seed(args[0], args[1], out) != PROVER_OK:
+        raise ZkpoaError("zkpoa_bip39_seed: an ASCII mnemonic and passphrase of at most 4096 bytes each are needed")
+    return out.bytes()
+
+
+def bip32_parse_key(text):
+    """An xprv / xpub string -> (key data, chain code, depth, child index); ZkpoaError for anything else."""
+    key, chain, where = _Out(33), _Out(32), (ctypes.c_uint32 * 2)()
+    if "\0" in text or lib().zkpoa_bip32_parse_key(text.encode("utf-8", "replace"), key, chain, where) != PROVER_OK:
+        raise ZkpoaError("zkpoa_bip32_parse_key: not an xprv / xpub (alphabet, length, checksum, version or key)")
+    return key.bytes(), chain.bytes(), int(where[0]), int(where[1])
+
+
+def bip32_parse_path(path):
+    """"m/44'/60'/0'/0" -> [indices], a hardened level with bit 31 set; ZkpoaError for anything that is no path."""
+    index, levels = (ctypes.c_uint32 * 255)(), ctypes.c_uint32(0)
+    if "\0" in path or lib().zkpoa_bip32_parse_path(path.encode("utf-8", "replace"), index, ctypes.byref(levels)) != PROVER_OK:
+        raise ZkpoaError("zkpoa_bip32_parse_path: not a path of at most 255 levels: %r" % path)
+    return list(index[:levels.value])
 
 
 def g1_mul(point, k):

@@ -180,6 +180,20 @@ SIGN_SIGNATURES = {
     "zkpoa_ecdsa_sign":                "i: p u64 p p u64 p p p p p p",
 }
 
+# every symbol include/zkpoa_hd_wallet.h declares (zkpoa_prover.h includes that header too): BIP-32 key sources; the
+# first four and the last on the GPU, the others host only and without a context
+HD_SIGNATURES = {
+    "zkpoa_sha512_batch":              "i: p p u64 u64 p",
+    "zkpoa_hmac_sha512_batch":         "i: p p u64 p u64 u64 p",
+    "zkpoa_bip32_children":            "i: p p p u64 u64 p p p p p",
+    "zkpoa_bip32_tweak":               "i: p p u64 p p p p p",
+    "zkpoa_bip32_master":              "i: p u64 p p",
+    "zkpoa_bip39_seed":                "i: s s p",
+    "zkpoa_bip32_parse_key":           "i: s p p u32*",
+    "zkpoa_bip32_parse_path":          "i: s u32* u32*",
+    "zkpoa_bip32_derive_path":         "i: p p p s p p",
+}
+
 # test and measurement hooks the library exports but the public header deliberately leaves out
 HOOK_SIGNATURES = {
     "zkpoa_test_upload":               "i: p s u64 u64 p f*",       # csrc/zkpoa_api.hip
@@ -212,7 +226,7 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        for table in (SIGNATURES, LAYER_INPUT_SIGNATURES, SIGN_SIGNATURES, HOOK_SIGNATURES):
+        for table in (SIGNATURES, LAYER_INPUT_SIGNATURES, SIGN_SIGNATURES, HD_SIGNATURES, HOOK_SIGNATURES):
             for name, spec in table.items():
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = signature(spec)

@@ -75,15 +75,15 @@ __global__ __launch_bounds__(256) void derive_keys_kernel(const uint8_t* __restr
   store_be32(out_keys, t, derive_key(seed, seed_len, first + t).l);
 }
 
+}  // namespace
+
 // the table of fixed_mul: computed once per process on the host (512 additions), copied to the device by each call
-const AffineK* fixed_table_host() {
+const AffineK* zkpoa::secp::fixed_table_host() {
   static AffineK tab[kFixedEntries];
   static std::once_flag once;
   std::call_once(once, [] { fixed_base_table(tab); });
   return tab;
 }
-
-}  // namespace
 
 extern "C" int zkpoa_sha256_batch(zkpoa_context* ctx, const void* messages, uint64_t message_len, uint64_t n, void* out32) {
   ZK_API_BEGIN(ctx)

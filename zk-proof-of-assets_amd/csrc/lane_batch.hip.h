@@ -1,5 +1,5 @@
-// What the one-item-per-lane entry points of ecdsa_star.hip and ecdsa_sign.hip share: the check of their arguments, the
-// arrays of a call on the device, the loop over launches, and the wait after them. Internal to those two files.
+// What the one-item-per-lane entry points of ecdsa_star.hip, ecdsa_sign.hip and bip32.hip share: the check of their
+// arguments, the arrays of a call on the device, the loop over launches, and the wait after them. Internal to those files.
 #pragma once
 #include "zkpoa_internal.hpp"
 

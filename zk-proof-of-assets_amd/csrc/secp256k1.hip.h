@@ -706,6 +706,7 @@ inline void fixed_base_table(AffineK* tab) {
     base = to_affine(e);
   }
 }
+const AffineK* fixed_table_host();   // that table, built on first use and kept (csrc/ecdsa_sign.hip): the library's one copy
 
 // k G for k in [1, n): signed digits in [-7, 8] as double_mul takes them (a scalar above (n - 1) / 2 is replaced by n - k
 // with every sign flipped, so the top digit never carries), one mixed addition per non-zero digit, no doubling. The

@@ -10,6 +10,9 @@
 //   ecdsa-sigs-parser layer-two-input | layer-three-input | pedersen-check ...
 //       the workflow's last three node steps (full_workflow.sh:521-529, :575-579, :588-591), host only: this file only
 //       reads their options and hands over to layer_inputs.hpp, which also holds what layer-one-input shares with them.
+//   ecdsa-sigs-parser hd-list <HD source> -o <addresses.csv>
+//       no counterpart in the reference: the addresses of a BIP-32 wallet's children (include/zkpoa_hd_wallet.h), the
+//       watch-only listing; the same HD source is a key source of sign and anon-set.
 // Both files are read through a pull parser over the mapped text: a million signatures are 350 MB of JSON in and over
 // a gigabyte out, and neither is ever held as a tree. The output is formatted by the host threads 2^16 entries at a
 // time. Exit status 0, or 1 with one line on stderr and no output file.
@@ -374,15 +377,17 @@ int layer_one_mode(const Cli& cli) {
 // ---- sign and anon-set modes -----------------------------------------------------------------------------------------
 // The two files the workflow starts from, which the reference makes with tests/generate_ecdsa_signatures.ts (noble's
 // sign, at most 128 keys of a list in the script) and tests/generate_anon_set.ts (at most about 10,600 addresses). Keys
-// come from a file or are derived from a seed on the GPU; signing, public keys, addresses and the filler accounts'
+// come from a file, are derived from a seed on the GPU, or are the children of a BIP-32 key (further down); signing, public keys, addresses and the filler accounts'
 // hashes run there (include/zkpoa_ecdsa_sign.h), sorting and formatting on the host threads. Not hardened against side
 // channels, and the keys pass through host memory and a text file: made for rehearsals and test data.
 constexpr uint64_t kGroupOrder[4] = {0xbfd25e8cd0364141ull, 0xbaaedce6af48a03bull, 0xfffffffffffffffeull, 0xffffffffffffffffull};
 
 struct Keys {
-  std::vector<uint8_t> key;       // 32 bytes per key, big-endian
+  std::vector<uint8_t> key;       // 32 bytes per key, big-endian; none under a public HD source
   std::vector<U256> balance;
   std::vector<uint64_t> line;     // of the key file, 1-based; empty for derived keys
+  std::vector<uint8_t> addr, pub; // an HD source only: 20 and 64 bytes per account, which its derivation gives already
+  std::vector<uint64_t> index;    // an HD source only: the child index of each account
   uint64_t n = 0;
 };
 
@@ -483,17 +488,124 @@ std::vector<uint32_t> order_by_address(const uint8_t* addr20, uint64_t n) {
   return idx;
 }
 
-// the key source of both modes: exactly one of --keys <file> and --generate-keys <N> --seed <text>
+// ---- HD key sources: a BIP-32 wallet (include/zkpoa_hd_wallet.h) -------------------------------------------------------
+// --hd-key <xprv | xpub>, --mnemonic <words> [--passphrase <text>] or --hd-seed 0x<hex> name a key; --hd-path leads from it
+// to the account key, whose children --hd-first .. --hd-first + --hd-count - 1 are the accounts. Everything up to the
+// account key's path is read and checked on the host, before the device is touched.
+constexpr const char* kHdOptions[] = {"--hd-key", "--mnemonic", "--passphrase", "--hd-seed", "--hd-path", "--hd-first", "--hd-count"};
+
+struct HdSource {
+  bool given = false;
+  uint8_t key[33] = {0}, chain[32] = {0};   // the key the path starts from
+  std::string path;
+  uint64_t first = 0, count = 0;
+  bool is_public() const { return key[0] != 0; }
+};
+
+// an option's text, or with a leading @ the contents of that file without the blanks and line ends around it: a secret
+// need not stand in the process list
+std::string text_or_file(const std::string& v) {
+  if (v.empty() || v[0] != '@') return v;
+  MappedFile f(v.c_str() + 1);
+  const char *b = f.begin(), *e = f.end();
+  auto blank = [](char c) { return c == ' ' || c == '\t' || c == '\r' || c == '\n'; };
+  while (b < e && blank(*b)) b++;
+  while (e > b && blank(e[-1])) e--;
+  return std::string(b, e);
+}
+
+HdSource hd_source(const Cli& cli) {
+  HdSource hd;
+  const int named = (int)cli.has("--hd-key") + (int)cli.has("--mnemonic") + (int)cli.has("--hd-seed");
+  if (named == 0) {
+    for (const char* o : kHdOptions)
+      if (cli.has(o)) throw CliError(std::string(o) + " goes with --hd-key, --mnemonic or --hd-seed");
+    return hd;
+  }
+  if (named > 1) throw CliError("--hd-key, --mnemonic and --hd-seed exclude each other");
+  if (cli.has("--passphrase") && !cli.has("--mnemonic")) throw CliError("--passphrase goes with --mnemonic");
+  hd.given = true;
+  if (cli.has("--hd-key")) {
+    uint32_t where[2];
+    if (zkpoa_bip32_parse_key(text_or_file(cli.value("--hd-key")).c_str(), hd.key, hd.chain, where) != PROVER_OK)
+      throw CliError("--hd-key is not an xprv / xpub (base58 alphabet, length, checksum, version or key)");
+  } else {
+    uint8_t seed[64];
+    size_t seed_len = 64;
+    if (cli.has("--mnemonic")) {
+      if (zkpoa_bip39_seed(text_or_file(cli.value("--mnemonic")).c_str(), text_or_file(cli.value("--passphrase")).c_str(), seed) != PROVER_OK)
+        throw CliError("--mnemonic and --passphrase are ASCII text of at most 4096 bytes (NFKD normalisation is not implemented)");
+    } else {
+      const std::string hex = text_or_file(cli.value("--hd-seed"));
+      seed_len = hex.size() >= 2 ? (hex.size() - 2) / 2 : 0;
+      if (seed_len < 16 || seed_len > 64 || !parse_hex_bytes(Span{hex.data(), hex.data() + hex.size()}, seed, seed_len))
+        throw CliError("--hd-seed is 0x and 16 to 64 bytes of hex digits");
+    }
+    if (zkpoa_bip32_master(seed, seed_len, hd.key, hd.chain) != PROVER_OK) throw CliError("the seed has no master key (IL is zero or not below the group order)");
+  }
+  hd.path = cli.has("--hd-path") ? cli.value("--hd-path") : (cli.has("--hd-key") ? "m" : "m/44'/60'/0'/0");
+  uint32_t levels[255], n_levels = 0;
+  if (zkpoa_bip32_parse_path(hd.path.c_str(), levels, &n_levels) != PROVER_OK)
+    throw CliError("--hd-path is not a path (m, m/0, m/44'/60'/0'/0; at most 255 levels): " + hd.path);
+  for (uint32_t i = 0; i < n_levels; i++)
+    if (hd.is_public() && (levels[i] >> 31)) throw CliError("--hd-path has a hardened level, which an xpub cannot derive: " + hd.path);
+  cli.required("--hd-count");
+  hd.count = cli.count("--hd-count", 0, "children up to 2^32");
+  if (cli.has("--hd-first")) hd.first = cli.count("--hd-first", 0, "children to skip, up to 2^32");
+  if (hd.first + hd.count > (1ull << 32)) throw CliError("--hd-first + --hd-count is at most 2^32");
+  if (hd.is_public() && hd.first + hd.count > (1ull << 31)) throw CliError("an xpub has no hardened children: --hd-first + --hd-count is at most 2^31");
+  return hd;
+}
+
+// The accounts of an HD source: the children first .. first + count - 1 of the key at the path, on the GPU. The balance
+// of an account is its address mod 1000, so that the xprv and its xpub tell the same. A child that BIP-32 calls invalid
+// is skipped, with a line on stderr.
+void derive_hd(zkpoa_context* ctx, const HdSource& hd, uint64_t count, Keys& g) {
+  uint8_t key[33], chain[32];
+  if (zkpoa_bip32_derive_path(ctx, hd.key, hd.chain, hd.path.c_str(), key, chain) != PROVER_OK)
+    throw InputError(std::string("zkpoa_bip32_derive_path: ") + zkpoa_last_error(ctx));
+  std::vector<uint8_t> key33(33 * count + 1), chains(32 * count + 1), status(count + 1);
+  g.addr.resize(20 * count + 1);
+  g.pub.resize(64 * count + 1);
+  if (zkpoa_bip32_children(ctx, key, chain, hd.first, count, key33.data(), chains.data(), g.pub.data(), g.addr.data(), status.data()) != PROVER_OK)
+    throw InputError(std::string("zkpoa_bip32_children: ") + zkpoa_last_error(ctx));
+  if (!hd.is_public()) g.key.resize(32 * count + 1);
+  g.balance.resize(count);
+  g.index.resize(count);
+  for (uint64_t i = 0; i < count; i++) {
+    if (status[i]) {
+      fprintf(stderr, "ecdsa-sigs-parser: child %llu is invalid (BIP-32) and is skipped\n", (unsigned long long)(hd.first + i));
+      continue;
+    }
+    if (!hd.is_public()) memcpy(&g.key[32 * g.n], &key33[33 * i + 1], 32);
+    memmove(&g.addr[20 * g.n], &g.addr[20 * i], 20);
+    memmove(&g.pub[64 * g.n], &g.pub[64 * i], 64);
+    uint8_t a32[32] = {0};
+    memcpy(a32 + 12, &g.addr[20 * g.n], 20);
+    g.balance[g.n] = default_balance(U256::from_be(a32));
+    g.index[g.n] = hd.first + i;
+    g.n++;
+  }
+}
+
+// the key source of the modes: exactly one of --keys <file>, --generate-keys <N> --seed <text> and an HD source
 struct KeySource {
   std::string file, seed;
   uint64_t count = 0;
   bool generate = false;
+  HdSource hd;
 };
 
 KeySource key_source(const Cli& cli) {
   KeySource src;
+  src.hd = hd_source(cli);
   const bool file = cli.has("--keys");
-  if (file == cli.has("--generate-keys")) throw CliError(std::string(cli.mode) + " needs either --keys <file> or --generate-keys <N> --seed <text>");
+  if ((int)file + (int)cli.has("--generate-keys") + (int)src.hd.given != 1)
+    throw CliError(std::string(cli.mode) + " needs exactly one of --keys <file>, --generate-keys <N> --seed <text> and an HD source (--hd-key, --mnemonic, --hd-seed)");
+  if (src.hd.given) {
+    if (cli.has("--seed")) throw CliError("--seed goes with --generate-keys");
+    return src;
+  }
   if (file) {
     if (cli.has("--seed")) throw CliError("--seed goes with --generate-keys");
     src.file = cli.value("--keys");
@@ -507,16 +619,22 @@ KeySource key_source(const Cli& cli) {
   return src;
 }
 
-void write_key_file(const std::string& path, const Keys& g) {
-  write_entries(path, "", "", g.n, 68, [&](std::string& o, uint64_t i) {
+// with_balance: "0x<key>,<balance>" lines, for keys whose balance is not the default of a key file (an HD source's)
+void write_key_file(const std::string& path, const Keys& g, bool with_balance) {
+  write_entries(path, "", "", g.n, 72, [&](std::string& o, uint64_t i) {
     o += "0x";
     put_hex(o, &g.key[32 * i], 32);
+    if (with_balance) {
+      o += ",";
+      g.balance[i].append_dec(o);
+    }
     o += "\n";
   });
 }
 
 int sign_mode(const Cli& cli) {
   const KeySource src = key_source(cli);
+  if (src.hd.given && src.hd.is_public()) throw CliError("sign needs private keys, and --hd-key is an xpub");
   if (cli.has("--message") == cli.has("--msghash")) throw CliError("sign needs either --message <text> or --msghash 0x<64 hex digits>");
   const std::string& out_path = cli.required("--output-path");
   uint8_t z[32];
@@ -530,9 +648,10 @@ int sign_mode(const Cli& cli) {
   ContextStart start(device_from_env());
   PhaseTimer lap("ecdsa-sigs-parser sign", 8);
   Keys g;
-  if (!src.generate) read_keys(src.file, g);
+  if (!src.generate && !src.hd.given) read_keys(src.file, g);
   zkpoa_context* ctx = start.get();
   if (src.generate) derive_keys(ctx, src.seed, src.count, g);
+  if (src.hd.given) derive_hd(ctx, src.hd, src.hd.count, g);
   lap("keys");
   const uint64_t n = g.n;
   printf("Signing with %llu keys..\n", (unsigned long long)n);
@@ -565,7 +684,7 @@ int sign_mode(const Cli& cli) {
     g.balance[i].append_dec(o);
     o += "n\"}";
   });
-  if (cli.has("--write-keys")) write_key_file(cli.value("--write-keys"), g);
+  if (cli.has("--write-keys")) write_key_file(cli.value("--write-keys"), g, src.hd.given);
   lap("write");
   printf("Wrote %llu signatures to %s\n", (unsigned long long)n, out_path.c_str());
   return 0;
@@ -579,13 +698,17 @@ int anon_set_mode(const Cli& cli) {
   ContextStart start(device_from_env());
   PhaseTimer lap("ecdsa-sigs-parser anon-set", 8);
   Keys g;
-  if (!src.generate) read_keys(src.file, g);
+  if (!src.generate && !src.hd.given) read_keys(src.file, g);
   zkpoa_context* ctx = start.get();
   if (src.generate) derive_keys(ctx, src.seed, std::min(src.count, total), g);
+  if (src.hd.given) derive_hd(ctx, src.hd, std::min(src.hd.count, total), g);
   const uint64_t owned = std::min(g.n, total);
   std::vector<uint8_t> addr(20 * total + 1);
   std::vector<U256> balance(total);
-  {
+  if (src.hd.given) {   // the derivation gave the addresses already, and an xpub has no keys to give
+    memcpy(addr.data(), g.addr.data(), 20 * owned);
+    std::copy(g.balance.begin(), g.balance.begin() + (ptrdiff_t)owned, balance.begin());
+  } else {
     std::vector<uint8_t> pub(64 * owned + 1), status(owned + 1);
     if (zkpoa_secp256k1_pubkey(ctx, owned, g.key.data(), pub.data(), addr.data(), status.data()) != PROVER_OK)
       throw InputError(std::string("zkpoa_secp256k1_pubkey: ") + zkpoa_last_error(ctx));
@@ -640,12 +763,35 @@ int anon_set_mode(const Cli& cli) {
   return 0;
 }
 
+// the watch-only listing: the addresses of an HD source's children, in the order of their indices
+int hd_list_mode(const Cli& cli) {
+  const HdSource hd = hd_source(cli);
+  if (!hd.given) throw CliError("hd-list needs an HD source: --hd-key <xprv | xpub>, --mnemonic <words> or --hd-seed 0x<hex>");
+  const std::string& out_path = cli.required("--output-path");
+  ContextStart start(device_from_env());
+  PhaseTimer lap("ecdsa-sigs-parser hd-list", 8);
+  Keys g;
+  derive_hd(start.get(), hd, hd.count, g);
+  std::vector<char> text(42 * g.n + 1);
+  if (zkpoa_eth_address(start.get(), g.pub.data(), g.n, g.addr.data(), text.data()) != PROVER_OK)
+    throw InputError(std::string("zkpoa_eth_address: ") + zkpoa_last_error(start.get()));
+  lap("device");
+  write_entries(out_path, "index,address\n", "", g.n, 56, [&](std::string& o, uint64_t i) {
+    o += std::to_string(g.index[i]) + ",";
+    o.append(&text[42 * i], 42);
+    o += "\n";
+  });
+  lap("write");
+  printf("Wrote %llu addresses to %s\n", (unsigned long long)g.n, out_path.c_str());
+  return 0;
+}
+
 const char kUsage[] =
     "Usage: ecdsa-sigs-parser --signatures <in.json> --output-path <out.json>\n"
-    "       ecdsa-sigs-parser sign (--keys <file> | --generate-keys <N> --seed <text>)\n"
+    "       ecdsa-sigs-parser sign (--keys <file> | --generate-keys <N> --seed <text> | <HD source: hd-list --help>)\n"
     "                         (--message <text> | --msghash 0x<64 hex>) --output-path <signatures.json> [--write-keys <file>]\n"
-    "       ecdsa-sigs-parser anon-set (--keys <file> | --generate-keys <N> --seed <text>) --num-addresses <M>\n"
-    "                         --output-path <anonymity_set.csv>\n"
+    "       ecdsa-sigs-parser anon-set (--keys <file> | --generate-keys <N> --seed <text> | <HD source: hd-list --help>)\n"
+    "                         --num-addresses <M> --output-path <anonymity_set.csv>\n"
     "       ecdsa-sigs-parser layer-one-input --poa-input-data <parsed.json> --write-layer-one-data-to <out.json>\n"
     "                         [--account-start-index <i>] [--account-end-index <j>]\n"
     "       ecdsa-sigs-parser layer-two-input --poa-input-data <parsed.json> --merkle-root <merkle_root.json>\n"
@@ -657,6 +803,16 @@ const char kUsage[] =
     "                         --blindingFactor <decimal or 0x-hex>\n"
     "       ecdsa-sigs-parser pedersen-check --poa-input-data <parsed.json> --layer-three-public-inputs <public.json>\n"
     "                         --blindingFactor <decimal or 0x-hex>\n";
+
+// hd-list's own usage, which also spells the HD source that sign and anon-set take (kUsage keeps its sixteen lines)
+const char kHdUsage[] =
+    "Usage: ecdsa-sigs-parser hd-list <HD source> --output-path <addresses.csv>      (index,address per child)\n"
+    "       <HD source>, also a key source of sign (private only) and anon-set: the children i = first .. first + N - 1 of a\n"
+    "       BIP-32 key, as accounts with balance = address mod 1000\n"
+    "         --hd-key <xprv...|xpub...|@file> | --mnemonic <words|@file> [--passphrase <text|@file>] | --hd-seed 0x<hex>\n"
+    "         [--hd-path <path>]   from that key to the children's parent; default m/44'/60'/0'/0 (m for --hd-key)\n"
+    "         [--hd-first <i>] --hd-count <N>\n"
+    "       @file: the value is the file's text. The mnemonic's words and checksum are not checked; ASCII only.\n";
 
 // the three modes of layer_inputs.hpp
 int layer_two_cli(const Cli& cli) {
@@ -687,13 +843,20 @@ struct Mode {
   Answer misspelt, absent;        // the answer to a command line that cannot be read, and to one that lacks a required option
   bool help;                      // -h / --help print the usage (in layer-two-input -h is the hash path, as in the reference)
   int (*run)(const Cli&);
+  const char* usage = kUsage;     // what its help and its kWithUsage answers print
 };
+std::vector<Option> with_hd(std::vector<Option> own) {   // a mode's own options and those of an HD source
+  for (const char* o : kHdOptions) own.push_back({o, nullptr});
+  return own;
+}
 const Mode kModes[] = {
-    {"sign", {{"--keys", nullptr}, {"--generate-keys", nullptr}, {"--seed", nullptr}, {"--message", nullptr}, {"--msghash", nullptr},
-              {"--output-path", "-o"}, {"--write-keys", nullptr}},
+    {"sign", with_hd({{"--keys", nullptr}, {"--generate-keys", nullptr}, {"--seed", nullptr}, {"--message", nullptr}, {"--msghash", nullptr},
+                      {"--output-path", "-o"}, {"--write-keys", nullptr}}),
      kWithUsage, kWithUsage, false, sign_mode},
-    {"anon-set", {{"--keys", nullptr}, {"--generate-keys", nullptr}, {"--seed", nullptr}, {"--num-addresses", "-n"}, {"--output-path", "-o"}},
+    {"anon-set", with_hd({{"--keys", nullptr}, {"--generate-keys", nullptr}, {"--seed", nullptr}, {"--num-addresses", "-n"},
+                          {"--output-path", "-o"}}),
      kWithUsage, kWithUsage, false, anon_set_mode},
+    {"hd-list", with_hd({{"--output-path", "-o"}}), kWithUsage, kWithUsage, true, hd_list_mode, kHdUsage},
     {"layer-one-input", {{"--poa-input-data", "-i"}, {"--write-layer-one-data-to", "-o"}, {"--account-start-index", "-s"},
                          {"--account-end-index", "-e"}},
      kAsFailure, kBrief, true, layer_one_mode},
@@ -717,12 +880,12 @@ int main(int argc, char** argv) {
   int rc = 0;
   try {
     const Cli cli = parse_options(argc, argv, *mode->name ? 2 : 1, mode->name, mode->options, mode->help);
-    if (cli.has("--help")) printf("%s", kUsage);
+    if (cli.has("--help")) printf("%s", mode->usage);
     else rc = mode->run(cli);
   } catch (const CliError& e) {
     const Answer how = e.absent ? mode->absent : mode->misspelt;
     if (how == kAsFailure) fprintf(stderr, "Error: %s\n", e.what());
-    else fprintf(stderr, "error: %s\n%s", e.what(), how == kWithUsage ? kUsage : "");
+    else fprintf(stderr, "error: %s\n%s", e.what(), how == kWithUsage ? mode->usage : "");
     rc = how == kAsFailure ? 1 : 2;
   } catch (const std::exception& e) {
     fprintf(stderr, "Error: %s\n", e.what());
