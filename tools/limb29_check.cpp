@@ -12,6 +12,8 @@
 //   op 11 piece closed   as op 8 -> 32 packed words, then 1 word: 1 = a sum, 0 = poisoned (ZZ = 0 mod q)
 //   op 13 X below 2^256  9 limbs (class X, as given) -> 9 limbs, the 8 words made from them, 9 limbs sliced back
 //   op 14 pack, unpack   36 limbs (Xyzz29S as given) -> 32 words, 36 limbs
+//   op 15 times 32       9 limbs (class W or C6 - W, as given) -> 9 limbs: how a piece opens (host form only)
+//   op 16 divide by 32   9 limbs (class N, as given) -> 9 limbs: how a piece closes (host form only)
 // (the numbers are zkpoa_fq29_prim's where it has the op; its op 5, one mixed addition with every exceptional case, needs the device's
 // exact addition and has no host form)
 #include "fq29.hip.h"
@@ -148,6 +150,12 @@ int main(int argc, char** argv) {
         wr(b.zzz.l, 9);
         break;
       }
+      case 15:
+      case 16:
+        if (!rd(w, 9)) return 3;
+        r = op == 15 ? fq29_times32(limbs(w)) : fq29_div32(limbs(w));
+        wr(r.l, 9);
+        break;
       default: return 2;
     }
   }

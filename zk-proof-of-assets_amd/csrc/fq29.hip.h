@@ -19,11 +19,24 @@
 //   * a product takes at most ONE class-D operand (dot2: one per product); a D that is squared or meets another D is
 //     normalised first (norm: one carry pass, value unchanged).
 //   * operand values satisfy va * vb <= 338 q^2 (dot2: the sum of its two products).
-// COLUMNS. Column k of a product adds at most 9 a_i b_(k-i) + 9 m_i q_(k-i) and the carry of column k-1 (< 2^35).
-// m_i, q_i < 2^29. Both operands normalised: < 18 * 2^58 < 2^63. One operand D: 9 * 3 * 2^58 + 9 * 2^58 = 36 * 2^58.
-// dot2 as the mixed addition uses it (r * d + ny * ppp: r, ppp normalised, d < 3 * 2^29, ny < 2 * 2^29 per limb):
-// 27 * 2^58 + 18 * 2^58 + 9 * 2^58 = 54 * 2^58; with two D operands of 3 * 2^29: 63 * 2^58 + 2^35 < 2^64. The square
-// doubles its cross terms by doubling one limb (< 2^30): the same sum as the product. No column reaches 2^64.
+// COLUMNS. Column k of a product adds at most 9 a_i b_(k-i), 9 m_i q_(k-i) and the carry of column k-1 (< 2^35).
+// mul and sqr keep their quotient limbs m_0..m_7 UNMASKED (32 bits, see QUOTIENT LIMBS), so their m part is bounded
+// through q: sum m_i q_(k-i) < 2^32 * (q_0 + ... + q_8) = 2^32 * 1616751127 < 0.377 * 2^64 in any column. Both
+// operands normalised: a b part 9 * 2^58 = 0.141 * 2^64, total < 0.52 * 2^64. One operand D, or the negated base
+// C6 - W (limbs < 2^30): a b part at most 27 * 2^58 = 0.422 * 2^64, total < 0.80 * 2^64. The square doubles its cross
+// terms by doubling one limb (< 2^30): the same sum as the product of two normalised operands.
+// dot2 MASKS every m_i (< 2^29); as the mixed addition uses it (r * d + ny * ppp: r, ppp normalised, d < 3 * 2^29,
+// ny < 2 * 2^29 per limb): 27 * 2^58 + 18 * 2^58 + 9 * 2^58 = 54 * 2^58; with two D operands of 3 * 2^29:
+// 63 * 2^58 + 2^35 < 2^64. (Unmasked, its m part alone would add 0.377 * 2^64 to 54 * 2^58 = 0.844 * 2^64: it keeps
+// its masks.) No column reaches 2^64.
+// QUOTIENT LIMBS. Column k < 9 needs an m_k with acc + m_k q_0 = 0 (mod 2^29). mt_k = lo32(acc) * INV mod 2^32 is
+// such a value: mt_k = m_k (mod 2^29), m_k = mt_k & M the masked one. What mt_k has above bit 29 is a multiple of
+// 2^29 q added to the column, i.e. a multiple of q one column up, and column k + 1 computes its own m from the
+// accumulator that holds it: every column's low 29 bits still vanish and the sum is still a b + Mt q with
+// Mt = sum mt_k 2^(29 k). So the mask (one v_and per column) is spent only where the SIZE of Mt matters: on m_8.
+// With m_8 < 2^29 and the others < 2^32, Mt < 2^261 + 2^32 (2^232 - 1) / (2^29 - 1) < 2^261 + 2^235.1.
+// Eight masks less in each of the mixed addition's six products and two squares: 64 of its 177 v_and_b32, 2015 -> 1951
+// instructions with the same 1467 mads (profiles/loop_mix_quotient_mask_{parent,change}.txt).
 // COLUMN CHAINS. A column is written as one chain: acc >>= 29, then acc += a_i b_j ... . v_mad_u64_u32 takes its 64-bit
 // addend for free, so the shifted carry can be the addend of the column's first product. Left alone, the compiler's
 // reassociation ranks the carry last: it starts every column at 0 beside the tail of the column before and joins the
@@ -39,7 +52,8 @@
 // opens a chain from acc = 0 with another product behind it (dot2, column 0) carries no marker: it has no carry to
 // keep in front, and marked, it is computed twice (the compiler commutes the pair). COLUMNS, VALUES and the operand
 // classes are untouched: the same products are added, in the order written, to the same accumulator.
-// VALUES. The output is (a b + m q) / 2^261 with m < 2^261: < va vb / 2^261 + q <= 338 q^2 / (169.28 q) + q < 3q.
+// VALUES. The output is (a b + Mt q) / 2^261 with Mt < 2^261 (1 + 2^-25.9) (dot2: < 2^261):
+// < va vb / 2^261 + q (1 + 2^-25.9) <= 338 q^2 / (169.28 q) + 1.00000002 q < 2.9967 q + 0.00000002 q < 3q.
 // So N is closed under every product the rules allow; the largest in the mixed addition is 17q * 17q = 289 q^2.
 // SUBTRACTION is a + (C - b) per limb, C = k q in a "borrowed" representation whose limbs are all >= the largest
 // limb b can have (limbs 0..7: d_i + 2^29 - 1 with a borrow of one from the limb above; limb 8: d_8 - 1, which has to
@@ -188,6 +202,51 @@ ZK29 Fq29 fq29_below_2p256(const Fq29& a) {
   return r;
 }
 
+// 32 a for a of class W or the negated base C6 - W (limbs < 2^30, value < 6q: 32 a < 192q does not fit 2^261, its limb
+// 8 needs 31 bits), brought below q (1 + 2^-13): normalised, class N and class X at once. This is the product by
+// 2^266 mod q (a wire word into the accumulator's X, Y domain) without a product. The limbs are shifted in place,
+// t_i = (a_i mod 2^24) 2^5 + (a_(i-1) >> 24) < 2^29 + 64 and t_8 = 32 a_8 + (a_7 >> 24) < 2^30 + 64 (a_8 < 6 (q_8 + 1)
+// < 2^25), nothing carried; then the quotient estimate of fq29_below_2p256, k = t_8 / (q_8 + 1) <= 192: k q <
+// k (q_8 + 1) 2^232 <= t_8 2^232 <= 32 a, so nothing goes negative, and with t_8 + 1 <= (k + 1)(q_8 + 1) and the limbs
+// below t_8 summing to less than 2^232 (1 + 2^-22), 32 a - k q < (q_8 + k + 1 + 2^-22) 2^232 < q + 194 * 2^232.
+// The subtraction's carry pass normalises. 9 multiply-adds, against the product's 162.
+ZK29 Fq29 fq29_times32(const Fq29& a) {
+  uint32_t t[9];
+  t[0] = (a.l[0] & 0xffffffu) << 5;
+#pragma unroll
+  for (int i = 1; i < 8; i++) t[i] = ((a.l[i] & 0xffffffu) << 5) + (a.l[i - 1] >> 24);
+  t[8] = (a.l[8] << 5) + (a.l[7] >> 24);
+  const uint32_t k = t[8] / ((Fq29P::Q[8]) + 1u);
+  Fq29 r;
+  int64_t c = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    c += (int64_t)t[i] - (int64_t)((uint64_t)k * Fq29P::Q[i]);
+    r.l[i] = (uint32_t)c & Fq29P::M;
+    c >>= 29;
+  }
+  r.l[8] = (uint32_t)((int64_t)t[8] - (int64_t)((uint64_t)k * Fq29P::Q[8]) + c);
+  return r;
+}
+// a / 32 for a normalised a: one 5-bit Montgomery step, (a + m q) >> 5 with m = a_0 * INV mod 32 (INV = -1/q mod 2^29
+// is -1/q mod 32 as well), value (a + m q) / 32 < (va + 31 q) / 32: class N (< 3q) gives < 1.0625 q, normalised. This
+// is the product by 2^256 mod q (2^266 to 2^261) without a product. a = 0 (mod q), i.e. j q with j <= 2, gives
+// (j + m) q / 32 with j + m <= 33 a multiple of 32: 0 or q, never another representative. The shift is folded into the
+// carry pass: limb i enters at bit 29 i - 5 = 29 (i - 1) + 24, so the accumulator stays below 2^60.
+ZK29 Fq29 fq29_div32(const Fq29& a) {
+  const uint32_t m = (a.l[0] * Fq29P::INV) & 31u;
+  Fq29 r;
+  uint64_t acc = ((uint64_t)a.l[0] + (uint64_t)m * Fq29P::Q[0]) >> 5;
+#pragma unroll
+  for (int i = 1; i < 9; i++) {
+    acc += ((uint64_t)a.l[i] + (uint64_t)m * Fq29P::Q[i]) << 24;
+    r.l[i - 1] = (uint32_t)acc & Fq29P::M;
+    acc >>= 29;
+  }
+  r.l[8] = (uint32_t)acc;
+  return r;
+}
+
 // ---- sums and differences (class D results) ---------------------------------------------------------------------
 ZK29 Fq29 fq29_norm(const Fq29& a) {   // one carry pass: limbs 0..7 < 2^29, value unchanged
   Fq29 r;
@@ -217,8 +276,8 @@ ZK29 Fq29 fq29_neg(const Fq29& b) {   // C - b
 }
 
 // ---- Montgomery products, radix 2^261, product scanning ---------------------------------------------------------
-// column k < 9 fixes m_k so that the column's low 29 bits vanish; columns 9..16 leave limbs 0..7 and what remains of
-// the accumulator is limb 8. No final subtraction (see VALUES).
+// column k < 9 fixes m_k so that the column's low 29 bits vanish (mul, sqr: m_0..m_7 unmasked, see QUOTIENT LIMBS);
+// columns 9..16 leave limbs 0..7 and what remains of the accumulator is limb 8. No final subtraction (see VALUES).
 ZK29 Fq29 fq29_mul(const Fq29& a, const Fq29& b) {
   uint64_t acc = 0;
   uint32_t m[9];
@@ -229,7 +288,8 @@ ZK29 Fq29 fq29_mul(const Fq29& a, const Fq29& b) {
     for (int i = 0; i <= k; i++) fq29_mac(acc, a.l[i], b.l[k - i]);
 #pragma unroll
     for (int i = 0; i < k; i++) fq29_mac(acc, m[i], Fq29P::Q[k - i]);
-    m[k] = ((uint32_t)acc * Fq29P::INV) & Fq29P::M;
+    m[k] = (uint32_t)acc * Fq29P::INV;
+    if (k == 8) m[k] &= Fq29P::M;
     fq29_mac(acc, m[k], Fq29P::Q[0]);
     acc >>= 29;
   }
@@ -260,7 +320,8 @@ ZK29 Fq29 fq29_sqr(const Fq29& a) {
     if ((k & 1) == 0) fq29_mac(acc, a.l[k / 2], a.l[k / 2]);
 #pragma unroll
     for (int i = 0; i < k; i++) fq29_mac(acc, m[i], Fq29P::Q[k - i]);
-    m[k] = ((uint32_t)acc * Fq29P::INV) & Fq29P::M;
+    m[k] = (uint32_t)acc * Fq29P::INV;
+    if (k == 8) m[k] &= Fq29P::M;
     fq29_mac(acc, m[k], Fq29P::Q[0]);
     acc >>= 29;
   }
@@ -320,11 +381,12 @@ struct Xyzz29 {
   Fq29 x, y, zz, zzz;
 };
 
-// acc = (bx, by): bx class W, by class W or C6 - W
+// acc = (bx, by): bx class W, by class W or C6 - W. 2^256 to 2^261 is a factor of 32: no product (fq29_times32);
+// X and Y come out normalised and below q (1 + 2^-13), inside class X and class N.
 ZK29 void xyzz29_open(Xyzz29& acc, const Fq29& bx, const Fq29& by) {
   const Fq29 k = fq29_const<Fq29K266>();
-  acc.x = fq29_mul(bx, k);
-  acc.y = fq29_mul(by, k);
+  acc.x = fq29_times32(bx);
+  acc.y = fq29_times32(by);
   acc.zz = k;
   acc.zzz = k;
 }
@@ -461,8 +523,9 @@ ZK29 void xyzz29s_add(Xyzz29S& acc, const Xyzz29S& b) {
 // and re-limbed into 8 words: x then y, zz, zzz. Infinity is 32 zero words (a sum's ZZ is never 0 as a value: poison
 // is not stored, and a non-infinity ZZ is a non-zero field element). y, zz, zzz are class N or W and fit as they
 // are; x is class X and is reduced by fq29_below_2p256. Loading is bit slicing only: every coordinate comes back class W.
-// A stored ZZ is always a product output (class N, < 3q) -- a piece's closing product, an addition's, a conversion's, or
-// such a word loaded and stored again unchanged -- which is what lets fq29_is_zero_mod_q test a sum's ZZ against 0, q, 2q.
+// A stored ZZ is always class N (< 3q) -- a piece's closing division by 32 (< 1.0625 q), an addition's or a conversion's
+// product output, or such a word loaded and stored again unchanged -- which is what lets fq29_is_zero_mod_q test a
+// sum's ZZ against 0, q, 2q.
 ZK29 void xyzz29s_pack(const Xyzz29S& a, uint32_t* w32) {
   fq29_to_words(fq29_below_2p256(a.x), w32);
   fq29_to_words(a.y, w32 + 8);
@@ -475,14 +538,14 @@ ZK29 void xyzz29s_unpack(Xyzz29S& a, const uint32_t* w32) {
   a.zz = fq29_from_words(w32 + 16);
   a.zzz = fq29_from_words(w32 + 24);
 }
-// the piece's sum in the single domain: ZZ, ZZZ from 2^266 to 2^261 (one product each), X and Y as they are. False
-// if it is not a sum (ZZ = 0 mod q: the piece met acc = +-base); the piece must not be empty.
+// the piece's sum in the single domain: ZZ, ZZZ from 2^266 to 2^261 (a division by 32 each: fq29_div32, no product;
+// class N in, normalised and below 1.0625 q out), X and Y as they are. False if it is not a sum (ZZ = 0 mod q: the
+// piece met acc = +-base, and a ZZ of 0, q or 2q divides to 0 or q); the piece must not be empty.
 ZK29 bool g1piece29_close(const G1Piece29& s, Xyzz29S& out) {
-  const Fq29 k = fq29_const<Fq29K256>();
   out.x = s.a.x;
   out.y = s.a.y;
-  out.zz = fq29_mul(s.a.zz, k);
-  out.zzz = fq29_mul(s.a.zzz, k);
+  out.zz = fq29_div32(s.a.zz);
+  out.zzz = fq29_div32(s.a.zzz);
   return !fq29_is_zero_mod_q(out.zz);
 }
 
