@@ -702,6 +702,10 @@ int zkpoa_curve_prim(zkpoa_context* ctx, int group, int op, const void* a, const
  * and the exact addition redid it, then 3 zero words; 11 = a piece as op 8 -> packed, same 36 words out;
  * 12 = packed -> canonical wire XYZZ. There is no op 9. raw is ignored by ops 4-6 and 8-12. */
 int zkpoa_fq29_prim(zkpoa_context* ctx, int op, const void* in, void* out, uint64_t n, int raw);
+/* The secp256k1 layer's own functions (csrc/secp256k1.hip.h: Fp, Sc, recode_signed4, to_affine, fixed_mul, double_mul) on
+ * raw 8-word values, one record per lane: one entry point, declared with its op numbers in a header of its own next to
+ * this one. */
+#include "zkpoa_secp_prim.h"
 /* The NTT's other forms on a host buffer, in place (parity tests). form: 0 = ntt_dif (natural in, bit-reversed out),
  * 1 = ntt_dit (bit-reversed in, natural out), 2 = ntt_to_odd_coset (inverse ignored). No 1/n in forms 0 and 1.
  * batch vectors of 2^log_n elements start stride elements apart (stride >= 2^log_n); elements between them are not

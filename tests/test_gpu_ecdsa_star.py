@@ -8,6 +8,7 @@ import subprocess
 
 import pytest
 
+import secp_limb_ref as lr
 import secp_ref as sr
 import sign_ref as sg
 from test_secp_ref import fixture_text, sigs_bin  # noqa: F401  (sigs_bin is a fixture)
@@ -140,6 +141,25 @@ def test_edges(ctx):
     for name in ("k=1", "k=n-1", "infinity", "z>=n"):
         i = names.index(name)
         assert run(ctx, [cases[i]]) == [want[i]], name
+
+
+def test_steered_inner_scalars(ctx):
+    """The scalars inside a recovery, u2 = s / r and u1 = -z / r, are random whatever r, s and z are; here they are
+    chosen (tests/secp_limb_ref.py: s = u2 r, z = -u1 r, R = k G for small and large k): both at the borders of the
+    signed recoding and of the halving, with R among the entries of the ladder's shared table of G, so that its additions
+    double, cancel and pass through infinity. Combinations whose s is 0 or not below 2^255 must be refused as such."""
+    steered = lr.steered_recoveries()
+    want = [exp for _, _, exp in steered]
+    statuses = [w[0] for w in want]
+    assert statuses.count(sr.OK) >= 60 and {sr.BAD_SCALAR, sr.HIGH_S, sr.INFINITY} <= set(statuses)
+    assert set(statuses) <= {sr.OK, sr.BAD_SCALAR, sr.HIGH_S, sr.INFINITY}
+    for (_, (r, s, v, z, _), _), w in zip(steered, want):
+        assert w[0] == (sr.BAD_SCALAR if s == 0 else sr.HIGH_S if s >= 1 << 255 else w[0])
+        if w[0] != sr.OK:
+            assert w[1:] == ZEROS
+    got = run(ctx, [c for _, c, _ in steered])
+    bad = [name for (name, _, _), g, w in zip(steered, got, want) if g != w]
+    assert bad[:10] == []
 
 
 @pytest.fixture(scope="module")

@@ -329,6 +329,14 @@ class Context:
         self._check(lib().zkpoa_fq29_prim(self._h, op, pin, out, n, 1 if raw else 0), "zkpoa_fq29_prim")
         return out.bytes()
 
+    def secp_prim(self, op, data, n, out_words):
+        """zkpoa_secp_prim: `data` holds the op's operand arrays back to back (n values of eight little-endian 32-bit
+        words each); returns its result arrays likewise, `out_words` words per record in all, as bytes."""
+        pin, kin = _buf(data)
+        out = _Out(4 * out_words * n)
+        self._check(lib().zkpoa_secp_prim(self._h, op, pin, out, n), "zkpoa_secp_prim")
+        return out.bytes()
+
     def test_msm_sort(self, scalars, n, c=0, merged=False, for_g2=False, density=None, k0=0, lane=0, caps=None):
         """zkpoa_test_msm_sort: phase A of one MSM request on host scalars -> a dict with "plan" (the thirteen words of
         zkpoa_test_msm_plan), "total_entries", "max_count", "total1", and counts, off0, po_a, sorted, pbkt, order,

@@ -194,6 +194,11 @@ HD_SIGNATURES = {
     "zkpoa_bip32_derive_path":         "i: p p p s p p",
 }
 
+# the one symbol include/zkpoa_secp_prim.h declares (zkpoa_prover.h includes that header beside its other test hooks)
+SECP_PRIM_SIGNATURES = {
+    "zkpoa_secp_prim":                 "i: p i p p u64",
+}
+
 # test and measurement hooks the library exports but the public header deliberately leaves out
 HOOK_SIGNATURES = {
     "zkpoa_test_upload":               "i: p s u64 u64 p f*",       # csrc/zkpoa_api.hip
@@ -226,7 +231,7 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        for table in (SIGNATURES, LAYER_INPUT_SIGNATURES, SIGN_SIGNATURES, HD_SIGNATURES, HOOK_SIGNATURES):
+        for table in (SIGNATURES, LAYER_INPUT_SIGNATURES, SIGN_SIGNATURES, HD_SIGNATURES, SECP_PRIM_SIGNATURES, HOOK_SIGNATURES):
             for name, spec in table.items():
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = signature(spec)

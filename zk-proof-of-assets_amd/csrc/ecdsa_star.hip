@@ -64,17 +64,6 @@ __global__ __launch_bounds__(256) void eth_address_kernel(const void* __restrict
   for (int i = 0; i < 21; i++) dst[i] = (uint16_t)(text[2 * i] | (text[2 * i + 1] << 8));
 }
 
-// 1G .. 8G in affine form, the same for every lane: computed here (seven additions) rather than spelt out
-void generator_table(AffineK (&tab)[8]) {
-  const AffineK g = generator();
-  XyzzK e = XyzzK::from_affine(g);
-  tab[0] = g;
-  for (int m = 1; m < 8; m++) {
-    xyzz_add_affine(e, g, false);
-    tab[m] = to_affine(e);
-  }
-}
-
 }  // namespace
 
 extern "C" int zkpoa_ecdsa_star(zkpoa_context* ctx, uint64_t n, const void* r, const void* s, const void* msghash, const uint8_t* v,

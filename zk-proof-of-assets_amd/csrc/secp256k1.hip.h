@@ -520,6 +520,18 @@ struct LaneTable {
   }
 };
 
+// 1G .. 8G in affine form, the shared table of double_mul, the same for every lane: computed on the host (seven
+// additions) rather than spelt out
+inline void generator_table(AffineK (&tab)[8]) {
+  const AffineK g = generator();
+  XyzzK e = XyzzK::from_affine(g);
+  tab[0] = g;
+  for (int m = 1; m < 8; m++) {
+    xyzz_add_affine(e, g, false);
+    tab[m] = to_affine(e);
+  }
+}
+
 // u2 R + u1 G. One ladder for both bases (Straus, interleaved): 64 windows of 4 doublings, one addition from the
 // lane's table of R and one mixed addition from the shared affine table 1G .. 8G (gtab, 8 x 64 B). A scalar above
 // (n - 1) / 2 is replaced by n - k with the sign of every digit flipped.
