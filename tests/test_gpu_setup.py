@@ -310,6 +310,10 @@ def test_setup_outputs_are_atomic_and_inputs_range_checked(ctx, zk, tmp_path):
         with pytest.raises(zk.ZkpoaError, match="field element"):
             ctx.zkey_new(tmp_path / "c.r1cs", tmp_path / "bad.ptau", tmp_path / "bad.zkey")
         assert not (tmp_path / "bad.zkey").exists()
+        assert not [x.name for x in tmp_path.iterdir() if ".tmp." in x.name]
+    # sections 13-15 fail in the device stage with writers in flight: none is left behind, and the context is whole
+    ctx.zkey_new(tmp_path / "c.r1cs", tmp_path / "pot.ptau", tmp_path / "again.zkey")
+    assert (tmp_path / "again.zkey").read_bytes() == want0
     # ... and the same for a point of section 9 of a key handed to contribute
     zsecs = {t: lst[0] for t, lst in g16.read_binfile(want0, "zkey", 1).items()}
     badk = bytearray(want0)

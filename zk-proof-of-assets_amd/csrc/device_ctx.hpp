@@ -150,7 +150,7 @@ struct DeviceCtx {
   bool ok = false;
   // last-run kernel timing (HIP events on the lane's stream), for bench.py's roofline object
   float last_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  std::thread bg_;
+  std::thread bg_;   // not a SideTask: it signals readiness twice mid-way (condition variables) and outlives every call
   std::mutex bg_mutex_;
   std::condition_variable bg_cv_;
   bool lanes_ready_ = false;     // lanes 1 .. kEagerLanes-1 exist (or bg_err_ says why not); extras may still be coming up

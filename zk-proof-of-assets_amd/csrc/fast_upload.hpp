@@ -5,6 +5,7 @@
 // staging copies and PCIe DMA all overlap.
 #pragma once
 #include "device_ctx.hpp"
+#include "host_threads.hpp"
 
 #include <ctype.h>
 #include <pthread.h>
@@ -46,42 +47,30 @@ class FastUploader {
       return;
     }
     ensure(device, stream);
-    const int T = threads_;
-    std::vector<std::thread> th;
-    std::vector<std::exception_ptr> errs(T);
-    size_t per = ((bytes / T) + 4095) & ~size_t(4095);
-    for (int t = 0; t < T; t++) {
-      size_t lo = (size_t)t * per;
-      if (lo >= bytes) break;
-      size_t hi = lo + per < bytes ? lo + per : bytes;
-      th.emplace_back([this, t, lo, hi, dst, src, device, stream, fd, file_off, &errs] {
-        try {
-          ZK_HIP(hipSetDevice(device));
-          if (have_cpus_) (void)pthread_setaffinity_np(pthread_self(), sizeof(cpus_), &cpus_);
-          Slot& s = slots_[t];
-          // streams: the caller's plus the uploader's own, as many as exist by now (they come up in the background);
-          // one stream -- one SDMA queue -- moves ~36 GB/s whatever the thread count, four reach the link's ~53 GB/s
-          const int ns = n_own_.load(std::memory_order_acquire);
-          const int pick = t % (ns + 1);
-          hipStream_t st = pick == ns ? stream : own_[pick];
-          int b = 0;
-          for (size_t off = lo; off < hi; off += kChunk, b ^= 1) {
-            size_t len = hi - off < kChunk ? hi - off : kChunk;
-            ZK_HIP(hipEventSynchronize(s.done[b]));  // the DMA that last used this buffer has finished
-            if (fd >= 0) read_all(fd, static_cast<char*>(s.pinned[b]), len, file_off + off);
-            else memcpy(s.pinned[b], reinterpret_cast<const char*>(src) + off, len);
-            ZK_HIP(hipMemcpyAsync(reinterpret_cast<char*>(dst) + off, s.pinned[b], len, hipMemcpyHostToDevice, st));
-            ZK_HIP(hipEventRecord(s.done[b], st));
-          }
-          for (int k = 0; k < 2; k++) ZK_HIP(hipEventSynchronize(s.done[k]));
-        } catch (...) {
-          errs[t] = std::current_exception();
-        }
-      });
-    }
-    for (auto& t : th) t.join();
-    for (auto& e : errs)
-      if (e) std::rethrow_exception(e);
+    const size_t per = ((bytes / threads_) + 4095) & ~size_t(4095);
+    unsigned used = 0;   // the non-empty slices
+    while ((int)used < threads_ && used * per < bytes) used++;
+    run_threads(used, [&, this](unsigned t) {
+      const size_t lo = t * per, hi = lo + per < bytes ? lo + per : bytes;
+      ZK_HIP(hipSetDevice(device));
+      if (have_cpus_) (void)pthread_setaffinity_np(pthread_self(), sizeof(cpus_), &cpus_);
+      Slot& s = slots_[t];
+      // streams: the caller's plus the uploader's own, as many as exist by now (they come up in the background);
+      // one stream -- one SDMA queue -- moves ~36 GB/s whatever the thread count, four reach the link's ~53 GB/s
+      const int ns = n_own_.load(std::memory_order_acquire);
+      const int pick = (int)t % (ns + 1);
+      hipStream_t st = pick == ns ? stream : own_[pick];
+      int b = 0;
+      for (size_t off = lo; off < hi; off += kChunk, b ^= 1) {
+        size_t len = hi - off < kChunk ? hi - off : kChunk;
+        ZK_HIP(hipEventSynchronize(s.done[b]));  // the DMA that last used this buffer has finished
+        if (fd >= 0) read_all(fd, static_cast<char*>(s.pinned[b]), len, file_off + off);
+        else memcpy(s.pinned[b], reinterpret_cast<const char*>(src) + off, len);
+        ZK_HIP(hipMemcpyAsync(reinterpret_cast<char*>(dst) + off, s.pinned[b], len, hipMemcpyHostToDevice, st));
+        ZK_HIP(hipEventRecord(s.done[b], st));
+      }
+      for (int k = 0; k < 2; k++) ZK_HIP(hipEventSynchronize(s.done[k]));
+    });
   }
 
   // Streams of the uploader's own (ZKPOA_UPLOAD_STREAMS, default 3: four with the caller's). Called from the context's

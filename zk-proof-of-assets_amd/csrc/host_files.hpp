@@ -1,10 +1,11 @@
 // The file and thread side of the host programs, in one place: a whole file mapped read-only (MappedFile), output that
-// appears under its name only when complete (AtomicFile, write_text_atomic), the host's threads (host_threads,
-// run_threads, parallel_ranges), the ZKPOA_VERBOSE phase timer, ZKPOA_DEVICE, and the device context started on a second
+// appears under its name only when complete (AtomicFile, write_text_atomic), the host's threads (host_threads.hpp:
+// SideTask, run_threads, parallel_ranges), the ZKPOA_VERBOSE phase timer, ZKPOA_DEVICE, and the device context started on a second
 // thread while the first reads its input (ContextStart). Host only, no HIP: next to the public C header this is all a
 // command-line front end needs. Failures are std::runtime_error.
 #pragma once
 #include "../../include/zkpoa_prover.h"
+#include "host_threads.hpp"
 
 #include <fcntl.h>
 #include <stdio.h>
@@ -16,11 +17,8 @@
 #include <unistd.h>
 
 #include <atomic>
-#include <exception>
 #include <stdexcept>
 #include <string>
-#include <thread>
-#include <vector>
 
 namespace zkpoa {
 
@@ -72,45 +70,6 @@ struct MappedFile {
   const char* begin() const { return reinterpret_cast<const char*>(p); }   // as text
   const char* end() const { return begin() + size; }
 };
-
-// ---- host-side parallelism ---------------------------------------------------------------------------------------------
-// At the layer-three shape `zkey new` reads 62 GB and writes 35 GB, and the device's share of the command is 3.5 s: what
-// was left was one host thread parsing, copying and converting (54 s in all). Every host stage is split over the host's
-// threads; the arrays they fill are not zero-filled first, the threads are the first to touch them.
-inline unsigned host_threads() {
-  unsigned t = std::thread::hardware_concurrency();
-  if (const char* e = getenv("ZKPOA_SETUP_THREADS")) {
-    char* end = nullptr;
-    const long v = strtol(e, &end, 10);
-    if (end != e && !*end && v >= 1 && v <= 256) t = (unsigned)v;
-  }
-  return t < 1 ? 1 : (t > 32 ? 32 : t);
-}
-// fn(t) on T threads; all are joined, then the first exception in the order of t is rethrown
-template <class Fn>
-void run_threads(unsigned T, Fn fn) {
-  std::vector<std::exception_ptr> errs(T);
-  std::vector<std::thread> th;
-  for (unsigned t = 0; t < T; t++)
-    th.emplace_back([&, t] {
-      try {
-        fn(t);
-      } catch (...) {
-        errs[t] = std::current_exception();
-      }
-    });
-  for (auto& x : th) x.join();
-  for (auto& e : errs)
-    if (e) std::rethrow_exception(e);
-}
-// fn(t, lo, hi) over [0, count) cut into host_threads() ranges
-template <class Fn>
-void parallel_ranges(uint64_t count, uint64_t min_per_thread, Fn fn) {
-  unsigned T = host_threads();
-  if (count / (min_per_thread ? min_per_thread : 1) < T) T = (unsigned)(count / (min_per_thread ? min_per_thread : 1));
-  if (T <= 1) return fn(0u, (uint64_t)0, count);
-  run_threads(T, [&](unsigned t) { fn(t, count * t / T, count * (t + 1) / T); });
-}
 
 // Output files are written under a temporary name and renamed into place (as prover_main's write_atomic): a failure
 // part-way (ENOSPC, HIP error, kill) never leaves a truncated .zkey under the final name for a later "skip if the zkey
@@ -189,17 +148,14 @@ struct ContextStart {
   zkpoa_context* ctx = nullptr;
   char err[512] = {0};
   int rc = PROVER_OK;
-  std::thread thread;
-  explicit ContextStart(int device) : thread([this, device] { rc = zkpoa_context_create(device, &ctx, err, sizeof(err)); }) {}
-  void wait() {
-    if (thread.joinable()) thread.join();
-  }
+  SideTask task;   // the last member: joined before the others go
+  explicit ContextStart(int device) : task([this, device] { rc = zkpoa_context_create(device, &ctx, err, sizeof(err)); }) {}
+  void wait() { task.wait(); }
   zkpoa_context* get() {
-    wait();
+    task.get();
     if (rc != PROVER_OK) throw std::runtime_error(err);
     return ctx;
   }
-  ~ContextStart() { wait(); }
   ContextStart(const ContextStart&) = delete;
   ContextStart& operator=(const ContextStart&) = delete;
 };

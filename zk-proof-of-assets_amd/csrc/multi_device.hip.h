@@ -216,16 +216,10 @@ DeviceSet* process_devices(uint32_t power, std::string& err, int* code) {
     select_devices(*ds, power);
     const size_t G = ds->ids.size();
     ds->ctx.assign(G, nullptr);
-    std::vector<std::string> errs(G);
-    std::vector<std::thread> th;
-    for (size_t g = 0; g < G; g++)
-      th.emplace_back([&, g] {
-        char msg[512] = {0};
-        if (zkpoa_context_create(ds->ids[g], &ds->ctx[g], msg, sizeof(msg)) != PROVER_OK) errs[g] = msg[0] ? msg : "context creation failed";
-      });
-    for (auto& t : th) t.join();
-    for (size_t g = 0; g < G; g++)
-      if (!errs[g].empty()) throw HipError(errs[g]);
+    run_threads((unsigned)G, [&](unsigned g) {
+      char msg[512] = {0};
+      if (zkpoa_context_create(ds->ids[g], &ds->ctx[g], msg, sizeof(msg)) != PROVER_OK) throw HipError(msg[0] ? msg : "context creation failed");
+    });
     // peer access between distinct devices: the exchanges then go GPU to GPU over xGMI instead of through the host
     for (size_t g = 0; g < G; g++)
       for (size_t h = 0; h < G; h++) {
@@ -307,21 +301,10 @@ typedef std::unique_ptr<MultiKey> MultiKeyPtr;
 // run fn(g) on one thread per rank; the first exception (by rank) is rethrown after all have joined
 template <class Fn>
 void for_each_rank(DeviceSet* ds, Fn fn) {
-  const size_t G = ds->ids.size();
-  std::vector<std::exception_ptr> errs(G);
-  std::vector<std::thread> th;
-  for (size_t g = 0; g < G; g++)
-    th.emplace_back([&, g] {
-      try {
-        ZK_HIP(hipSetDevice(ds->ids[g]));
-        fn(g);
-      } catch (...) {
-        errs[g] = std::current_exception();
-      }
-    });
-  for (auto& t : th) t.join();
-  for (auto& e : errs)
-    if (e) std::rethrow_exception(e);
+  run_threads((unsigned)ds->ids.size(), [&](unsigned g) {
+    ZK_HIP(hipSetDevice(ds->ids[g]));
+    fn(g);
+  });
 }
 
 // Block size of the block-cyclic sections: 2^16 items, less for small keys so that every rank still gets at least
@@ -426,7 +409,7 @@ void multi_prove_partials(DeviceSet* ds, MultiKey* mk, const WtnsView& w, uint8_
   RankBarrier bar((unsigned)G);
   std::atomic<bool> failed{false};
   std::vector<std::exception_ptr> errs(G);
-  std::vector<std::thread> th;
+  std::vector<std::thread> th;   // not a SideTasks: the barrier must learn how many ranks did NOT start (bar.abandon below)
   th.reserve(G);
   auto rank_main = [&](size_t g) {
       // Phases separated by barriers; a rank that fails keeps arriving at the barriers so that nobody waits for ever.

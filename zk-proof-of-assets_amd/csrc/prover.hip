@@ -341,13 +341,10 @@ KeyPtr zkey_load_impl(zkpoa_context* ctx, const uint8_t* buf, uint64_t size, uin
     const uint64_t cnt = zk->h_scalar_count();
     std::vector<uint8_t> stage(cnt * 64);
     const unsigned nthreads = 6;
-    std::vector<std::thread> th;
-    for (unsigned k = 0; k < nthreads; k++)
-      th.emplace_back([&, k] {
-        for (uint64_t t = cnt * k / nthreads; t < cnt * (k + 1) / nthreads; t++)
-          memcpy(stage.data() + t * 64, s9.p + (t * world + rank) * 64, 64);
-      });
-    for (auto& t : th) t.join();
+    run_threads(nthreads, [&](unsigned k) {
+      for (uint64_t t = cnt * k / nthreads; t < cnt * (k + 1) / nthreads; t++)
+        memcpy(stage.data() + t * 64, s9.p + (t * world + rank) * 64, 64);
+    });
     zk->dHs = dev_upload(ctx, stage.data(), cnt * 64);
   } else {
     zk->dH = dev_upload(ctx, s9.p + zk->hlo * 64, zk->hcnt * 64);
@@ -872,7 +869,6 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
   uint8_t* outB2 = out + 128;
   uint8_t* outC = out + 256;
   uint8_t* outH = out + 320;
-  std::exception_ptr errs[4];
   float msm_ms[5][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}};
   // A, B1 and B2 run over the compacted queries (points at infinity dropped at key load) and gathered scalars. Every
   // device pointer is read INSIDE its stage, after the stage's staging hook: a staged prove allocates and fills the
@@ -885,14 +881,10 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
     ctx->ev_witness_set = false;
   }
   auto guarded = [&](int slot, std::function<void()> fn) {
-    return std::thread([&, slot, fn] {
-      try {
-        ZK_HIP(hipSetDevice(ctx->dev.device));
-        if (stg) deferred_free_sink() = &stg->sinks[slot];
-        fn();
-      } catch (...) {
-        errs[slot] = std::current_exception();
-      }
+    return SideTask([&, slot, fn] {
+      ZK_HIP(hipSetDevice(ctx->dev.device));
+      if (stg) deferred_free_sink() = &stg->sinks[slot];
+      fn();
     });
   };
   // Witness MSMs on their own lanes (host threads: each MSM has one mid-way read-back). B1 and B2 use the
@@ -930,7 +922,7 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
   // opt_prove_serial (measurement only): every stage runs alone, one after the other, so the per-stage device times
   // are solo times and their sum / the overlapped wall time says how much the five lanes gain (bench.py).
   const bool serial = ctx->opt_prove_serial != 0;
-  std::thread tA = guarded(0, [&] {
+  SideTask tA = guarded(0, [&] {
     if (stg && stg->prep_A) stg->prep_A();
     const StageView vA = stage_view(zk, kStageA);
     if (!zk->d_witness || !zk->qA.g1 || !zk->qA.scalars) throw ProverError(PROVER_ERROR, "internal: A stage started before its inputs");
@@ -938,14 +930,14 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
     gather(1, zk->qA);
     msm_run_g1(ctx, 1, vA.bases, zk->qA.scalars.get(), vA.n, outA, msm_ms[1], vA.table, dens);
   });
-  if (serial) tA.join();
+  if (serial) tA.wait();
   // (a B query beyond the 32-bit entry index of one sort cannot share it: two chunked MSMs instead)
   // (nor can one whose whole-query workspace did not fit in HBM on an earlier MSM of this context: msm_points_limit)
   const uint64_t sort_limit = std::min(ctx->msm_points_limit(2), ctx->msm_points_limit(3));
   bool share_b = false;      // set by the B1 stage, read by the B2 stage after the sort has been published
   int table_c_b = 0;
   float sort_b_ms = 0;   // the shared sort of the B query (host clock: the call returns with its stream synchronised)
-  std::thread tB1 = guarded(1, [&] {
+  SideTask tB1 = guarded(1, [&] {
     StageView vB1;
     const double* dens = nullptr;
     try {
@@ -979,8 +971,8 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
     else msm_run_g1(ctx, 2, vB1.bases, zk->qB.scalars.get(), vB1.n, outB1, msm_ms[2], nullptr, dens);
     if (share_b) msm_ms[2][0] += sort_b_ms;
   });
-  if (serial) tB1.join();
-  std::thread tB2 = guarded(2, [&] {
+  if (serial) tB1.wait();
+  SideTask tB2 = guarded(2, [&] {
     const MsmSorted* sr = sorted_ready.get();
     const StageView vB2 = stage_view(zk, kStageB2);
     bool shared = share_b;
@@ -996,8 +988,8 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
     // KNOWN MISMATCH (DESIGN.md "MSM plans", follow-up): no density here, while lane_needs sizes this lane with one
     if (!shared) msm_run_g2(ctx, 3, vB2.bases, zk->qB.scalars.get(), vB2.n, outB2, msm_ms[3], nullptr, nullptr);
   });
-  if (serial) tB2.join();
-  std::thread tC = guarded(3, [&] {
+  if (serial) tB2.wait();
+  SideTask tC = guarded(3, [&] {
     if (stg && stg->prep_C) stg->prep_C();
     const StageView vC = stage_view(zk, kStageC);
     const char* witC = reinterpret_cast<const char*>(zk->d_witness) + ((uint64_t)zk->nPublic + 1 + vC.scalar_off) * 32;
@@ -1012,7 +1004,7 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
     }
     msm_run_g1(ctx, 4, vC.bases, witC, vC.n, outC, msm_ms[4], vC.table, with_density(4));
   });
-  if (serial) tC.join();
+  if (serial) tC.wait();
 
   std::exception_ptr main_err;
   uint32_t witness_bad = 0;
@@ -1043,16 +1035,10 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
     main_err = std::current_exception();
   }
   deferred_free_sink() = nullptr;
-  if (!serial) {
-    tA.join();
-    tB1.join();
-    tB2.join();
-    tC.join();
-  }
+  for (SideTask* t : {&tA, &tB1, &tB2, &tC}) t->wait();
   sorted_b.reset();
   if (main_err) std::rethrow_exception(main_err);
-  for (auto& e : errs)
-    if (e) std::rethrow_exception(e);
+  for (SideTask* t : {&tA, &tB1, &tB2, &tC}) t->get();
   if (witness_bad) throw ProverError(PROVER_ERROR, "witness value is not a field element (>= r)");
   auto t1 = std::chrono::steady_clock::now();
   ctx->ms[4] = std::chrono::duration<float, std::milli>(t1 - t0).count();
@@ -1245,7 +1231,7 @@ KeyPtr load_prove_staged(zkpoa_context* ctx, const uint8_t* buf, uint64_t size, 
   std::shared_future<void> have[S_COUNT];
   for (int i = 0; i < S_COUNT; i++) have[i] = ready[i].get_future().share();
   std::atomic<bool> cancel{false};
-  std::thread uploader;
+  std::thread uploader;   // not a SideTask: cancel, join and drain the device are one unit (Ending), in that order
   Staging stg;
   const bool verbose = req_getenv("ZKPOA_VERBOSE") != nullptr;
   const auto t_start = std::chrono::steady_clock::now();

@@ -401,7 +401,7 @@ static int server_main(const std::string& sock) {
       if (wake[1] >= 0) (void)!write(wake[1], "x", 1);
     }
   };
-  std::vector<std::thread> pool;
+  std::vector<std::thread> pool;   // not a SideTasks: the _exit path below deliberately joins nobody
   for (int w = 0; w < workers; w++)
     pool.emplace_back([&] {
       for (;;) {

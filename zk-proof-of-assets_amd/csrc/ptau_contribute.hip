@@ -159,8 +159,8 @@ struct MulStep {
 struct ReadBack {
   uint8_t* pinned[2] = {nullptr, nullptr};
   hipEvent_t ev[2] = {nullptr, nullptr};
-  std::thread writer[2];
-  std::atomic<bool> failed{false};
+  SideTask writer[2];
+  bool failed = false;   // a writer threw: kept here, its slot takes the next piece
   double write_ms[2] = {0, 0};   // each touched by its own writer only
   zkpoa_context* ctx;
   uint64_t sent = 0;
@@ -170,8 +170,12 @@ struct ReadBack {
       ZK_HIP(hipEventCreateWithFlags(&ev[b], hipEventDisableTiming));
     }
   }
-  void wait(int b) {
-    if (writer[b].joinable()) writer[b].join();
+  void wait(int b) noexcept {
+    try {
+      writer[b].get();
+    } catch (...) {
+      failed = true;
+    }
   }
   // len bytes at d_src, behind what lane 0's stream holds, to byte `at` of section id of fo
   void send(const void* d_src, uint64_t len, SectionFile& fo, uint32_t id, uint64_t at) {
@@ -180,12 +184,10 @@ struct ReadBack {
     wait(b);
     ZK_HIP(hipMemcpyAsync(pinned[b], d_src, len, hipMemcpyDeviceToHost, st));
     ZK_HIP(hipEventRecord(ev[b], st));
-    writer[b] = std::thread([this, &fo, b, id, at, len, device] {
+    writer[b] = SideTask([this, &fo, b, id, at, len, device] {
       const auto w0 = std::chrono::steady_clock::now();
-      if (hipSetDevice(device) != hipSuccess || hipEventSynchronize(ev[b]) != hipSuccess) {
-        failed = true;
-        return;
-      }
+      ZK_HIP(hipSetDevice(device));
+      ZK_HIP(hipEventSynchronize(ev[b]));
       fo.put_at(id, at, pinned[b], len);
       write_ms[b] += ms_since(w0);
     });
@@ -197,7 +199,7 @@ struct ReadBack {
   }
   ~ReadBack() {
     for (int b = 0; b < 2; b++) {
-      wait(b);
+      wait(b);   // before its buffer and its event go
       if (ev[b]) (void)hipEventDestroy(ev[b]);
       if (pinned[b]) (void)hipHostFree(pinned[b]);
     }

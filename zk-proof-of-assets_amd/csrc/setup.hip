@@ -26,8 +26,6 @@
 #include "setup_common.hip.h"
 #include "zkpoa_internal.hpp"
 
-#include <mutex>
-
 using namespace zkpoa;
 
 namespace {
@@ -447,120 +445,94 @@ void zkey_new(zkpoa_context* ctx, const char* r1cs_path, const char* ptau_path, 
   const uint64_t sec_len[10] = {4, kHdrLen, icb, 4 + nCoefs * 44, m * 64, m * 64, m * 128, (m - r.nPublic - 1) * 64, n * 64, 64 + 4};
   SectionFile out(zkey_path, "zkey", kZkeyIds, sec_len, 10);
   auto put_section = [&](uint32_t id, const void* p, uint64_t len) { out.put(id, p, len); };
-  std::exception_ptr host_err;
   double host_ms = 0;
-  std::thread host_sections([&] {
-    try {
-      struct timespec h0, h1;
-      clock_gettime(CLOCK_MONOTONIC, &h0);
-      const uint32_t one_u32 = 1;   // section 1: protocol id 1 = groth16
-      put_section(1, &one_u32, 4);
-      std::vector<uint8_t> s2, s10(64 + 4, 0);
-      put32(s2, 32);
-      s2.insert(s2.end(), (const uint8_t*)HFqParams::P, (const uint8_t*)HFqParams::P + 32);
-      put32(s2, 32);
-      s2.insert(s2.end(), (const uint8_t*)HFrParams::P, (const uint8_t*)HFrParams::P + 32);
-      put32(s2, r.nWires);
-      put32(s2, r.nPublic);
-      put32(s2, (uint32_t)n);
-      uint8_t g1[64], g2[128];
-      h_affine_to_bytes<HFq>(host_generator<HFq>(), g1);
-      h_affine_to_bytes<HFq2>(host_generator<HFq2>(), g2);
-      s2.insert(s2.end(), alpha1, alpha1 + 64);
-      s2.insert(s2.end(), beta1, beta1 + 64);
-      s2.insert(s2.end(), beta2, beta2 + 128);
-      s2.insert(s2.end(), g2, g2 + 128);   // gamma2 = the generator until a contribution changes delta
-      s2.insert(s2.end(), g1, g1 + 64);    // delta1
-      s2.insert(s2.end(), g2, g2 + 128);   // delta2
-      put_section(2, s2.data(), s2.size());
-      if (!transcript) put_section(10, s10.data(), s10.size());
-      // coefficients: A and B terms per constraint, then the public rows; values scaled by R^2
-      UVec<uint8_t> s4(4 + nCoefs * 44);
-      {
-        const uint32_t nc32 = (uint32_t)nCoefs;
-        memcpy(s4.data(), &nc32, 4);
-      }
-      auto rec = [&](uint64_t at, uint32_t mtx, uint32_t c, uint32_t sgn, const uint8_t* coef) {
-        uint8_t* o = s4.data() + 4 + at * 44;
-        memcpy(o, &mtx, 4);
-        memcpy(o + 4, &c, 4);
-        memcpy(o + 8, &sgn, 4);
-        HFr v = HFr::from_bytes(coef).to_mont();   // limbs = coef * R
-        HFr w = v.to_mont();                       // limbs = coef * R^2
-        memcpy(o + 12, w.l, 32);
-      };
-      // constraint ranges in parallel: a range starts at the first A / B term of its first constraint, and its records
-      // start at the count of A and B terms before that
-      parallel_ranges(r.nConstraints, 1u << 14, [&](unsigned, uint64_t c0, uint64_t c1) {
-        auto first = [&](const UVec<Term>& v, uint32_t c) {
-          return (size_t)(std::lower_bound(v.begin(), v.end(), c, [](const Term& t, uint32_t key) { return t.c < key; }) - v.begin());
-        };
-        size_t ia = first(r.A, (uint32_t)c0), ib = first(r.B, (uint32_t)c0);
-        uint64_t at = ia + ib;
-        for (uint32_t c = (uint32_t)c0; c < (uint32_t)c1; c++) {
-          for (; ia < r.A.size() && r.A[ia].c == c; ia++) rec(at++, 0, c, r.A[ia].s, r.A[ia].coef);
-          for (; ib < r.B.size() && r.B[ib].c == c; ib++) rec(at++, 1, c, r.B[ib].s, r.B[ib].coef);
-        }
-      });
-      {
-        const uint8_t one[32] = {1};
-        for (uint32_t i = 0; i <= r.nPublic; i++) rec(r.A.size() + r.B.size() + i, 0, r.nConstraints + i, i, one);
-      }
-      put_section(4, s4.data(), s4.size());
-      UVec<uint8_t> s9(n * 64);
-      parallel_ranges(n, 1u << 18, [&](unsigned, uint64_t lo, uint64_t hi) {
-        for (uint64_t i = lo; i < hi; i++) memcpy(&s9[i * 64], &Hs[(2 * i + 1) * 64], 64);   // odd points of the 2n basis
-      });
-      put_section(9, s9.data(), s9.size());
-      clock_gettime(CLOCK_MONOTONIC, &h1);
-      host_ms = (h1.tv_sec - h0.tv_sec) * 1e3 + (h1.tv_nsec - h0.tv_nsec) / 1e6;
-    } catch (...) {
-      host_err = std::current_exception();
+  SideTask host_sections([&] {
+    struct timespec h0, h1;
+    clock_gettime(CLOCK_MONOTONIC, &h0);
+    const uint32_t one_u32 = 1;   // section 1: protocol id 1 = groth16
+    put_section(1, &one_u32, 4);
+    std::vector<uint8_t> s2, s10(64 + 4, 0);
+    put32(s2, 32);
+    s2.insert(s2.end(), (const uint8_t*)HFqParams::P, (const uint8_t*)HFqParams::P + 32);
+    put32(s2, 32);
+    s2.insert(s2.end(), (const uint8_t*)HFrParams::P, (const uint8_t*)HFrParams::P + 32);
+    put32(s2, r.nWires);
+    put32(s2, r.nPublic);
+    put32(s2, (uint32_t)n);
+    uint8_t g1[64], g2[128];
+    h_affine_to_bytes<HFq>(host_generator<HFq>(), g1);
+    h_affine_to_bytes<HFq2>(host_generator<HFq2>(), g2);
+    s2.insert(s2.end(), alpha1, alpha1 + 64);
+    s2.insert(s2.end(), beta1, beta1 + 64);
+    s2.insert(s2.end(), beta2, beta2 + 128);
+    s2.insert(s2.end(), g2, g2 + 128);   // gamma2 = the generator until a contribution changes delta
+    s2.insert(s2.end(), g1, g1 + 64);    // delta1
+    s2.insert(s2.end(), g2, g2 + 128);   // delta2
+    put_section(2, s2.data(), s2.size());
+    if (!transcript) put_section(10, s10.data(), s10.size());
+    // coefficients: A and B terms per constraint, then the public rows; values scaled by R^2
+    UVec<uint8_t> s4(4 + nCoefs * 44);
+    {
+      const uint32_t nc32 = (uint32_t)nCoefs;
+      memcpy(s4.data(), &nc32, 4);
     }
-  });
-  // a point section is handed to a writer thread as soon as it is back from the device: it goes into the file while the
-  // device works on the next one
-  std::vector<std::thread> writers;
-  std::mutex werr_mutex;
-  std::exception_ptr write_err;
-  auto write_async = [&](uint32_t id, const uint8_t* p, uint64_t len) {
-    writers.emplace_back([&, id, p, len] {
-      try {
-        put_section(id, p, len);
-      } catch (...) {
-        std::lock_guard<std::mutex> lk(werr_mutex);
-        if (!write_err) write_err = std::current_exception();
+    auto rec = [&](uint64_t at, uint32_t mtx, uint32_t c, uint32_t sgn, const uint8_t* coef) {
+      uint8_t* o = s4.data() + 4 + at * 44;
+      memcpy(o, &mtx, 4);
+      memcpy(o + 4, &c, 4);
+      memcpy(o + 8, &sgn, 4);
+      HFr v = HFr::from_bytes(coef).to_mont();   // limbs = coef * R
+      HFr w = v.to_mont();                       // limbs = coef * R^2
+      memcpy(o + 12, w.l, 32);
+    };
+    // constraint ranges in parallel: a range starts at the first A / B term of its first constraint, and its records
+    // start at the count of A and B terms before that
+    parallel_ranges(r.nConstraints, 1u << 14, [&](unsigned, uint64_t c0, uint64_t c1) {
+      auto first = [&](const UVec<Term>& v, uint32_t c) {
+        return (size_t)(std::lower_bound(v.begin(), v.end(), c, [](const Term& t, uint32_t key) { return t.c < key; }) - v.begin());
+      };
+      size_t ia = first(r.A, (uint32_t)c0), ib = first(r.B, (uint32_t)c0);
+      uint64_t at = ia + ib;
+      for (uint32_t c = (uint32_t)c0; c < (uint32_t)c1; c++) {
+        for (; ia < r.A.size() && r.A[ia].c == c; ia++) rec(at++, 0, c, r.A[ia].s, r.A[ia].coef);
+        for (; ib < r.B.size() && r.B[ib].c == c; ib++) rec(at++, 1, c, r.B[ib].s, r.B[ib].coef);
       }
     });
-  };
-  struct Joiner {   // (the device stage below may throw: the side threads are joined whatever happens)
-    std::thread& t;
-    std::vector<std::thread>& w;
-    ~Joiner() {
-      if (t.joinable()) t.join();
-      for (auto& x : w)
-        if (x.joinable()) x.join();
+    {
+      const uint8_t one[32] = {1};
+      for (uint32_t i = 0; i <= r.nPublic; i++) rec(r.A.size() + r.B.size() + i, 0, r.nConstraints + i, i, one);
     }
-  } joiner{host_sections, writers};
-  UVec<uint8_t> secA, secB1, secB2, secK;   // (alive until every writer has been joined)
+    put_section(4, s4.data(), s4.size());
+    UVec<uint8_t> s9(n * 64);
+    parallel_ranges(n, 1u << 18, [&](unsigned, uint64_t lo, uint64_t hi) {
+      for (uint64_t i = lo; i < hi; i++) memcpy(&s9[i * 64], &Hs[(2 * i + 1) * 64], 64);   // odd points of the 2n basis
+    });
+    put_section(9, s9.data(), s9.size());
+    clock_gettime(CLOCK_MONOTONIC, &h1);
+    host_ms = (h1.tv_sec - h0.tv_sec) * 1e3 + (h1.tv_nsec - h0.tv_nsec) / 1e6;
+  });
+  // a point section is handed to a writer thread as soon as it is back from the device: it goes into the file while the
+  // device works on the next one. The section moves into its writer and lives as long as that thread. The device stage
+  // below may throw: the tasks are then joined by their destructors, before the file and the inputs declared above go.
+  SideTasks writers;
+  auto write_async = [&](uint32_t id, UVec<uint8_t>&& sec) {
+    writers.start([&, id, sec = std::move(sec)] { put_section(id, sec.data(), sec.size()); });
+  };
   std::unique_ptr<DevBuf> dA, dB1, dB2, dKout;   // transcript: the results stay on the device for the circuit hash
   {
     DevBuf dL1(n * 64);
     dL1.up(L1.data(), L1.size());
     dev_check_coords(ctx, dL1.p, 2 * n, "ptau tau*G1 (Lagrange)");
-    secA = run_accumulate<Fq>(ctx, dL1, n, eA, m, transcript ? &dA : nullptr);
-    write_async(5, secA.data(), secA.size());
-    secB1 = run_accumulate<Fq>(ctx, dL1, n, eB, m, transcript ? &dB1 : nullptr);
-    write_async(6, secB1.data(), secB1.size());
+    write_async(5, run_accumulate<Fq>(ctx, dL1, n, eA, m, transcript ? &dA : nullptr));
+    write_async(6, run_accumulate<Fq>(ctx, dL1, n, eB, m, transcript ? &dB1 : nullptr));
   }
   {
     DevBuf dL2(n * 128);
     dL2.up(L2.data(), L2.size());
     dev_check_coords(ctx, dL2.p, 4 * n, "ptau tau*G2 (Lagrange)");
-    secB2 = run_accumulate<Fq2>(ctx, dL2, n, eB, m, transcript ? &dB2 : nullptr);
-    write_async(7, secB2.data(), secB2.size());
+    write_async(7, run_accumulate<Fq2>(ctx, dL2, n, eB, m, transcript ? &dB2 : nullptr));
   }
-  secK = accumulate_k(ctx, pt, n, eK, m, transcript ? &dKout : nullptr);
+  const UVec<uint8_t> secK = accumulate_k(ctx, pt, n, eK, m, transcript ? &dKout : nullptr);
   phase("point sections (upload, device, download)");
   put_section(3, secK.data(), icb);
   put_section(8, secK.data() + icb, secK.size() - icb);
@@ -570,10 +542,8 @@ void zkey_new(zkpoa_context* ctx, const char* r1cs_path, const char* ptau_path, 
     circuit_hash(ctx, ptau_path, k, phase, s10);
     put_section(10, s10, sizeof s10);
   }
-  host_sections.join();
-  for (auto& x : writers) x.join();
-  if (host_err) std::rethrow_exception(host_err);
-  if (write_err) std::rethrow_exception(write_err);
+  host_sections.get();   // the host sections' error first, then the writers'
+  writers.get();
   if (phase.verbose) fprintf(stderr, "zkpoa: zkey new: (header, coefficient and H sections built and written by a side thread meanwhile: %.1f ms)\n", host_ms);
   out.commit();
   phase("last sections written, key renamed into place");
@@ -701,22 +671,11 @@ void zkey_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
   sec_len[9] = s10.size();
   SectionFile out(out_path, "zkey", kZkeyIds, sec_len, 10);   // temporary name + rename: in_path == out_path is fine (the mapping keeps the old inode)
   auto put_section = [&](uint32_t t, const uint8_t* p) { out.put(t, p, out.len(t)); };
-  std::exception_ptr copy_err;
-  std::thread copier([&] {
-    try {
-      put_section(2, s2.data());
-      put_section(10, s10.data());
-      for (uint32_t t : {1u, 3u, 4u, 5u, 6u, 7u}) put_section(t, fi.p + secs[t].off);
-    } catch (...) {
-      copy_err = std::current_exception();
-    }
+  SideTask copier([&] {
+    put_section(2, s2.data());
+    put_section(10, s10.data());
+    for (uint32_t t : {1u, 3u, 4u, 5u, 6u, 7u}) put_section(t, fi.p + secs[t].off);
   });
-  struct Joiner {
-    std::thread& t;
-    ~Joiner() {
-      if (t.joinable()) t.join();
-    }
-  } joiner{copier};
   {
     const UVec<uint8_t> s8 = scaled(secs[8]);
     put_section(8, s8.data());
@@ -725,8 +684,7 @@ void zkey_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
     const UVec<uint8_t> s9 = scaled(secs[9]);
     put_section(9, s9.data());
   }
-  copier.join();
-  if (copy_err) std::rethrow_exception(copy_err);
+  copier.get();
   out.commit();
 }
 
