@@ -1,6 +1,8 @@
 // Device context shared by the MSM / NTT / ABC stages: one HIP device, a set of streams, and a
 // grow-only workspace arena per stream so that no hipMalloc happens inside a timed step.
 #pragma once
+#include "options.hpp"
+
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -165,7 +167,6 @@ struct DeviceCtx {
   bool copy_done_ = false;
 
   void init(int dev) {
-    const bool verbose = getenv("ZKPOA_VERBOSE") != nullptr;
     auto now_ms = [] {
       struct timespec ts;
       clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -186,11 +187,10 @@ struct DeviceCtx {
     // lane 0 carries the prover's critical path (H-scalar chain -> H MSM): highest stream priority
     // A stream with its pinned buffer and events costs ~12 ms to create: lane 0 now, the others on a background
     // thread (they are first needed by the MSMs of a prove, after the key has been uploaded) -> wait_lanes().
-    {
-      const char* pe0 = getenv("ZKPOA_LANE_PRIO");
-      lanes[0].init(pe0 && !strcmp(pe0, "none") ? 0 : 2);
-    }
-    bg_ = std::thread([this] {
+    enum { kPrioLadder, kPrioFlat, kPrioNone, kPrioLadder2, kPrioTop1 };   // the words of ZKPOA_LANE_PRIO
+    const int pattern = opt_choice(O_LANE_PRIO);
+    lanes[0].init(pattern == kPrioNone ? 0 : 2);
+    bg_ = std::thread([this, pattern] {
       try {
         ZK_HIP(hipSetDevice(device));
         // highest priority: a copy queued at normal priority waits behind the lanes' kernels (fast_upload.hpp)
@@ -213,14 +213,11 @@ struct DeviceCtx {
         // (tools/ab_streams.sh): every lane at the same priority costs 8-10 % of the six-in-flight MSM rate and of a
         // 2^21 proof (the lanes then move in lock step and their accumulation kernels collide); which lanes get which
         // level matters little (within 3 %); ZKPOA_LANE_PRIO = flat | none | ladder2 selects the other patterns tried.
-        const char* pe = getenv("ZKPOA_LANE_PRIO");
-        const bool flat = pe && !strcmp(pe, "flat"), none = pe && !strcmp(pe, "none"), ladder2 = pe && !strcmp(pe, "ladder2");
-        const bool top1 = pe && !strcmp(pe, "top1");   // the chain's lane alone at the top level
-        static const int kLadder[6] = {2, 2, 1, 1, 0, 0}, kLadder2[6] = {2, 0, 1, 2, 0, 1}, kTop1[6] = {2, 1, 1, 0, 0, 0};
+        // (top1: the chain's lane alone at the top level)
+        static const int kLevel[5][6] = {{2, 2, 1, 1, 0, 0}, {0, 0, 0, 1, 0, 0}, {0, 0, 0, 0, 0, 0}, {2, 0, 1, 2, 0, 1}, {2, 1, 1, 0, 0, 0}};
         // (created one after the other: side by side they take just as long -- the runtime serialises stream creation;
         // measured r04, "lanes up" 47-58 ms either way)
-        for (int i = 1; i < kEagerLanes; i++)
-          lanes[i].init(none ? 0 : ladder2 ? kLadder2[i] : top1 ? kTop1[i] : flat ? (i == 3 ? 1 : 0) : kLadder[i]);
+        for (int i = 1; i < kEagerLanes; i++) lanes[i].init(kLevel[pattern][i]);
       } catch (...) {
         bg_err_ = std::current_exception();
         {
@@ -242,9 +239,8 @@ struct DeviceCtx {
         }
       }
     });
-    if (verbose)
-      fprintf(stderr, "zkpoa: HIP runtime up in %.1f ms, first lane in %.1f ms (the other %d in the background)\n",
-              t1 - t0, now_ms() - t1, kEagerLanes - 1);
+    vlog("zkpoa: HIP runtime up in %.1f ms, first lane in %.1f ms (the other %d in the background)\n", t1 - t0, now_ms() - t1,
+         kEagerLanes - 1);
     ok = true;
   }
   // the copy stream (nullptr when it could not be created: callers then copy on lane 0's stream)

@@ -83,18 +83,19 @@ class FastUploader {
   // for its own process: with the default of 4 hardware queues the eleven streams of a context share queues, and a
   // copy then sits behind a kernel of the lane it shares with). Default: 1 own stream, 3 when GPU_MAX_HW_QUEUES >= 8.
   void add_streams(int device) {
-    int want = 1;
-    if (const char* q = getenv("GPU_MAX_HW_QUEUES"))
-      if (atoi(q) >= 8) want = 3;
-    if (const char* e = getenv("ZKPOA_UPLOAD_STREAMS")) want = atoi(e);
-    if (want > kMaxOwnStreams) want = kMaxOwnStreams;
+    int want = (int)opt_long(O_UPLOAD_STREAMS);
+    static_assert(kMaxOwnStreams == 8, "the range of ZKPOA_UPLOAD_STREAMS");
+    if (want < 0) {
+      const char* q = getenv("GPU_MAX_HW_QUEUES");
+      want = q && atoi(q) >= 8 ? 3 : 1;
+    }
     for (int i = n_own_.load(); i < want; i++) {
       if (hipSetDevice(device) != hipSuccess) return;
       hipStream_t st = nullptr;
       int lo = 0, hi = 0;   // numerically lower = higher priority
       (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-      const char* pe = getenv("ZKPOA_UPLOAD_STREAM_PRIO");
-      const int prio = pe && !strcmp(pe, "normal") ? (lo + hi) / 2 : pe && !strcmp(pe, "low") ? lo : hi;
+      const int word = opt_choice(O_UPLOAD_STREAM_PRIO);   // high | normal | low
+      const int prio = word == 1 ? (lo + hi) / 2 : word == 2 ? lo : hi;
       if (hipStreamCreateWithPriority(&st, hipStreamNonBlocking, prio) != hipSuccess) {
         (void)hipGetLastError();
         return;
@@ -200,19 +201,14 @@ class FastUploader {
     if (ready_) return;
     // Threads: each copies its slice through its own pair of pinned buffers. Measured on an MI355X box (r04,
     // tools/file_inclusive.py): see DESIGN.md section 7 for the rates; ZKPOA_UPLOAD_THREADS overrides (1..16).
-    if (const char* e = getenv("ZKPOA_UPLOAD_THREADS")) {
-      const int v = atoi(e);
-      if (v >= 1 && v <= kMaxThreads) threads_ = v;
-    }
+    static_assert(kMaxThreads == 16, "the range of ZKPOA_UPLOAD_THREADS");
+    threads_ = (int)opt_long(O_UPLOAD_THREADS);
     unsigned hw = std::thread::hardware_concurrency();
     if (hw && (int)hw < threads_) threads_ = (int)hw;
     ZK_HIP(hipSetDevice(device));
     // the staging threads (and the first touch of their pinned buffers) stay on the CPUs of the GPU's NUMA node: 51 vs
     // 47 GB/s on a two-socket box (ZKPOA_UPLOAD_AFFINITY=off: wherever the scheduler puts them)
-    {
-      const char* e = getenv("ZKPOA_UPLOAD_AFFINITY");
-      if (!e || strcmp(e, "off") != 0) have_cpus_ = gpu_node_cpus(device, &cpus_);
-    }
+    if (opt_choice(O_UPLOAD_AFFINITY) == 0) have_cpus_ = gpu_node_cpus(device, &cpus_);   // gpu | off
     cpu_set_t before;
     const bool moved = have_cpus_ && pthread_getaffinity_np(pthread_self(), sizeof(before), &before) == 0 &&
                        pthread_setaffinity_np(pthread_self(), sizeof(cpus_), &cpus_) == 0;

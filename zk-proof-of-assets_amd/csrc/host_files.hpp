@@ -26,7 +26,7 @@ namespace zkpoa {
 struct PhaseTimer {
   const char* command;
   int width;   // of the <what> column (each command keeps its own: logs of different dates compare)
-  const bool verbose = getenv("ZKPOA_VERBOSE") != nullptr;
+  const bool verbose = opt_verbose();
   struct timespec t0;
   PhaseTimer(const char* cmd, int w) : command(cmd), width(w) { clock_gettime(CLOCK_MONOTONIC, &t0); }
   void operator()(const char* what) {
@@ -133,14 +133,7 @@ inline void write_text_atomic(const std::string& path, const std::string& text) 
   f.commit();
 }
 
-inline int device_from_env() {   // ZKPOA_DEVICE, or 0
-  const char* e = getenv("ZKPOA_DEVICE");
-  if (!e) return 0;
-  char* rest = nullptr;
-  const long dev = strtol(e, &rest, 10);
-  if (rest == e || *rest || dev < 0 || dev > 1023) throw std::runtime_error(std::string("ZKPOA_DEVICE: not a device index: ") + e);
-  return (int)dev;
-}
+inline int device_from_env() { return (int)opt_long(O_DEVICE); }   // ZKPOA_DEVICE, or 0
 
 // The device context (HIP start-up, ~0.4 s) is created on a second thread while the first reads the command's input.
 // get() waits for it and throws the text of a creation that failed; leaving the scope any other way joins the thread.

@@ -3,6 +3,8 @@
 // thread and its callable: what the thread reads is moved into the callable, or declared before the task. Standard
 // library only, no HIP.
 #pragma once
+#include "options.hpp"
+
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -25,7 +27,8 @@ class SideTask {
   SideTask() = default;
   template <class Fn>
   explicit SideTask(Fn fn) : err_(new std::exception_ptr) {
-    thread_ = spawn([fn = std::move(fn), err = err_.get()]() mutable {
+    thread_ = spawn([fn = std::move(fn), err = err_.get(), options = opt_overlay()]() mutable {
+      opt_overlay() = std::move(options);   // the task works for the request of the thread that started it
       try {
         fn();
       } catch (...) {
@@ -89,11 +92,7 @@ class SideTasks {
 // threads; the arrays they fill are not zero-filled first, the threads are the first to touch them.
 inline unsigned host_threads() {
   unsigned t = std::thread::hardware_concurrency();
-  if (const char* e = getenv("ZKPOA_SETUP_THREADS")) {
-    char* end = nullptr;
-    const long v = strtol(e, &end, 10);
-    if (end != e && !*end && v >= 1 && v <= 256) t = (unsigned)v;
-  }
+  if (const long v = opt_long(O_SETUP_THREADS)) t = (unsigned)v;
   return t < 1 ? 1 : (t > 32 ? 32 : t);
 }
 // fn(t) on T threads; all are joined, then the first exception in the order of t is rethrown (a thread that cannot be

@@ -99,15 +99,8 @@ static void read_anonymity_set(const std::string& path, Limbs& addr, Limbs& bal)
   }
   unsigned T = std::thread::hardware_concurrency();
   if (T > 16) T = 16;
-  bool forced = false;
-  if (const char* e = getenv("ZKPOA_MERKLE_THREADS")) {
-    char* rest = nullptr;
-    const long v = strtol(e, &rest, 10);
-    if (rest == e || *rest || v < 1 || v > 256)
-      throw std::runtime_error(std::string("ZKPOA_MERKLE_THREADS must be 1..256, not '") + e + "'");
-    T = (unsigned)v;
-    forced = true;
-  }
+  const long forced = opt_long(O_MERKLE_THREADS);
+  if (forced) T = (unsigned)forced;
   if (T < 1) T = 1;
   if ((size_t)(end - body) < (1u << 16) && !forced) T = 1;
   std::vector<const char*> cut(T + 1, end);
@@ -180,7 +173,7 @@ static void read_owned(const std::string& path, Owned& o) {
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 int main(int argc, char** argv) {
-  const bool verbose = getenv("ZKPOA_VERBOSE") && *getenv("ZKPOA_VERBOSE") && strcmp(getenv("ZKPOA_VERBOSE"), "0") != 0;
+  const bool verbose = opt_verbose();
   std::string anon, poa, outdir;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];

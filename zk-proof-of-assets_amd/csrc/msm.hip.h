@@ -395,13 +395,7 @@ static __global__ __launch_bounds__(kScanBlock) void scan_pair_kernel(ScanPair a
   }
 }
 
-inline bool scan_three_kernel() {
-  static const bool v = [] {
-    const char* e = getenv("ZKPOA_SCAN");
-    return e && !strcmp(e, "3");
-  }();
-  return v;
-}
+inline bool scan_three_kernel() { return opt_choice(O_SCAN) == 1; }   // 1 | 3
 
 // Per-lane scratch of scan_pair (device_ctx.hpp Lane::scan_*): two status arrays + the ticket counters, zeroed when
 // (re)allocated only; gen counts the calls on the lane.
@@ -1242,8 +1236,8 @@ inline void lane_reserve(Lane& lane, size_t need) {
     const auto t0 = std::chrono::steady_clock::now();
     lane.ws.reserve(need);
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (ms > 20.0 && getenv("ZKPOA_VERBOSE"))   // (only when a workspace grows: first proof on a key, or after precompute)
-      fprintf(stderr, "zkpoa:   lane workspace grows to %.2f GB: hipFree + hipMalloc %.1f ms\n", need / 1e9, ms);
+    // (only when a workspace grows: first proof on a key, or after precompute)
+    if (ms > 20.0) vlog("zkpoa:   lane workspace grows to %.2f GB: hipFree + hipMalloc %.1f ms\n", need / 1e9, ms);
   }
 }
 
@@ -1266,11 +1260,7 @@ inline MsmSorted msm_sort_phase(Lane& lane, const void* d_scalars, const MsmRequ
   const MsmSortLayout& m = sr.m = msm_carve<MsmSortLayout>(lane.ws, p);
   ZK_HIP(hipMemsetAsync(m.counts, 0, m.zero_bytes, st));
   // the plan's entry form; ZKPOA_NO_SPARSE=1 keeps the dense form (measurement)
-  static const bool no_sparse = [] {
-    const char* e = getenv("ZKPOA_NO_SPARSE");
-    return e && *e == '1';
-  }();
-  const bool sparse = p.sparse && !no_sparse;
+  const bool sparse = p.sparse && !opt_flag(O_NO_SPARSE);
   uint32_t* digits = sparse ? nullptr : m.digits();   // one region, one view per form
   uint2* elist = sparse ? m.elist : nullptr;
   uint32_t* pre = sparse ? m.pre : nullptr;

@@ -50,9 +50,8 @@ void msm_run(zkpoa_context* ctx, int lane_id, const void* d_bases, const void* d
         }
         throw;
       }
-      if (getenv("ZKPOA_VERBOSE"))
-        fprintf(stderr, "zkpoa:   lane %d: %s for %llu points at once; continuing with at most %llu\n", lane_id, e.what(),
-                (unsigned long long)cnt, (unsigned long long)ctx->msm_points_limit(lane_id));
+      vlog("zkpoa:   lane %d: %s for %llu points at once; continuing with at most %llu\n", lane_id, e.what(),
+           (unsigned long long)cnt, (unsigned long long)ctx->msm_points_limit(lane_id));
       continue;
     }
     adds += entries;

@@ -70,19 +70,6 @@ struct DeviceSet {
   }
 };
 
-// env integer with a range, or `dflt` when unset / empty; a malformed or out-of-range value is an input error
-long env_long(const char* name, long lo, long hi, long dflt) {
-  const char* e = getenv(name);
-  if (!e || !*e) return dflt;
-  char* end = nullptr;
-  errno = 0;
-  const long v = strtol(e, &end, 10);
-  if (errno || end == e || *end || v < lo || v > hi)
-    throw ProverError(PROVER_ERROR, std::string(name) + "='" + e + "' is not an integer in [" + std::to_string(lo) + ", " +
-                                    std::to_string(hi) + "]");
-  return v;
-}
-
 std::mutex g_devset_mutex;
 DeviceSet* g_devset = nullptr;
 
@@ -113,7 +100,7 @@ int try_lock_gpu(int dev, bool block) {
     // Wait for the holder, but not for ever: a wedged holder must not hang every later prover. After
     // ZKPOA_GPU_LOCK_WAIT_S seconds (default 1800: a queue of layer-three proofs is minutes, not hours) the wait is
     // reported and this process shares the GPU without the lock.
-    const long wait_s = env_long("ZKPOA_GPU_LOCK_WAIT_S", 0, 86400, 1800);
+    const long wait_s = opt_long(O_GPU_LOCK_WAIT_S);
     const auto t0 = std::chrono::steady_clock::now();
     for (;;) {
       if (flock(fd, LOCK_EX | LOCK_NB) == 0) return fd;
@@ -158,7 +145,7 @@ void select_devices(DeviceSet& ds, uint32_t power) {
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
     throw HipError("zkpoa: no HIP device visible (the MSM/NTT path is HIP-only; there is no CPU fallback)");
-  if (const char* e = getenv("ZKPOA_DEVICES")) {
+  if (const char* e = opt_text(O_DEVICES)) {
     if (*e && strcmp(e, "auto") != 0) {
       for (const char* p = e; *p;) {
         char* end = nullptr;
@@ -175,9 +162,9 @@ void select_devices(DeviceSet& ds, uint32_t power) {
       return;
     }
   }
-  if (const char* e = getenv("ZKPOA_DEVICE")) {
+  if (const char* e = opt_text(O_DEVICE)) {
     if (*e) {
-      ds.ids.push_back((int)env_long("ZKPOA_DEVICE", 0, count - 1, 0));
+      ds.ids.push_back((int)opt_long(O_DEVICE, 0, count - 1));
       return;
     }
   }
@@ -186,7 +173,7 @@ void select_devices(DeviceSet& ds, uint32_t power) {
     return;
   }
   ds.automatic = true;
-  const uint32_t min_power = (uint32_t)env_long("ZKPOA_MULTI_MIN_POWER", 0, 64, 24);
+  const uint32_t min_power = (uint32_t)opt_long(O_MULTI_MIN_POWER);
   std::vector<int> fds;
   ds.ids = auto_pick_devices(count, power, min_power, (unsigned long)getpid(), [&](int d, bool block) {
     int fd = try_lock_gpu(d, block);
@@ -234,7 +221,7 @@ DeviceSet* process_devices(uint32_t power, std::string& err, int* code) {
           ds->peer_ok = false;   // no direct path between this pair: the exchanges go through hipMemcpyPeerAsync
         }
       }
-    if (req_getenv("ZKPOA_VERBOSE")) {
+    if (opt_verbose()) {
       std::string list;
       for (size_t g = 0; g < G; g++) list += (g ? "," : "") + std::to_string(ds->ids[g]);
       fprintf(stderr, "zkpoa: %zu rank(s) on HIP device(s) %s%s, contexts ready in %.1f ms\n", G, list.c_str(),
@@ -244,6 +231,9 @@ DeviceSet* process_devices(uint32_t power, std::string& err, int* code) {
   } catch (const ProverError& e) {
     err = e.what();
     if (code) *code = e.code;
+    return nullptr;
+  } catch (const OptionError& e) {   // a malformed ZKPOA_* variable: *code says input error already
+    err = e.what();
     return nullptr;
   } catch (const std::exception& e) {   // HipError, bad_alloc, a thread that could not be started
     err = e.what();
@@ -315,13 +305,10 @@ uint32_t multi_block_log_default(uint64_t n_vars, size_t G) {
   return L;
 }
 uint32_t multi_block_log(uint64_t n_vars, size_t G) {
-  if (const char* e = getenv("ZKPOA_SHARD_BLOCK_LOG"))
-    if (*e) {
-      const long v = env_long("ZKPOA_SHARD_BLOCK_LOG", 0, 24, 0);
-      if (v != 0 && v < 4) throw ProverError(PROVER_ERROR, "ZKPOA_SHARD_BLOCK_LOG: 0 (contiguous ranges) or 4 .. 24");
-      return (uint32_t)v;
-    }
-  return multi_block_log_default(n_vars, G);
+  const long v = opt_long(O_SHARD_BLOCK_LOG);
+  if (v < 0) return multi_block_log_default(n_vars, G);
+  if (v != 0 && v < 4) throw ProverError(PROVER_ERROR, "ZKPOA_SHARD_BLOCK_LOG: 0 (contiguous ranges) or 4 .. 24");
+  return (uint32_t)v;
 }
 
 MultiKeyPtr multi_key_load(DeviceSet* ds, const uint8_t* buf, uint64_t size) {
@@ -353,22 +340,13 @@ MultiKeyPtr multi_key_load(DeviceSet* ds, const uint8_t* buf, uint64_t size) {
 // ZKPOA_EXCHANGE=copy: hipMemcpyPeerAsync exchanges, whole witness per rank -- also switched on for the rest of the
 // process when a proof made with the peer-store exchanges fails its self-check (multi_prove_to_json)
 inline std::atomic<int>& multi_copies_state() {
-  static std::atomic<int> v{[] {
-    const char* e = getenv("ZKPOA_EXCHANGE");
-    return e && !strcmp(e, "copy") ? 1 : 0;
-  }()};
+  static std::atomic<int> v{opt_choice(O_EXCHANGE)};   // peer | copy
   return v;
 }
 inline bool multi_force_copies() { return multi_copies_state().load() != 0; }
 // tests: ZKPOA_TEST_STALE_EXCHANGE=<n> -- in the n-th multi-rank proof of the process rank 0 does not push its first
 // exchange (its peers keep what the previous proof left there): what a missing release / acquire would look like
-inline long multi_test_stale_at() {
-  static const long v = [] {
-    const char* e = getenv("ZKPOA_TEST_STALE_EXCHANGE");
-    return e && *e ? strtol(e, nullptr, 10) : 0L;
-  }();
-  return v;
-}
+inline long multi_test_stale_at() { return opt_long(O_TEST_STALE_EXCHANGE); }
 inline std::atomic<long>& multi_proof_counter() {
   static std::atomic<long> v{0};
   return v;
@@ -411,7 +389,9 @@ void multi_prove_partials(DeviceSet* ds, MultiKey* mk, const WtnsView& w, uint8_
   std::vector<std::exception_ptr> errs(G);
   std::vector<std::thread> th;   // not a SideTasks: the barrier must learn how many ranks did NOT start (bar.abandon below)
   th.reserve(G);
+  const OptOverlay request_options = opt_overlay();   // the rank threads work for this thread's request (as a SideTask does)
   auto rank_main = [&](size_t g) {
+      opt_overlay() = request_options;
       // Phases separated by barriers; a rank that fails keeps arriving at the barriers so that nobody waits for ever.
       auto phase = [&](const std::function<void()>& fn) {
         if (failed.load()) return;
@@ -430,7 +410,7 @@ void multi_prove_partials(DeviceSet* ds, MultiKey* mk, const WtnsView& w, uint8_
       // (read once per process: no getenv on the proving path)
       auto test_fail = [&](int at) {
         static const std::pair<long, long> hook = [] {
-          const char* e = getenv("ZKPOA_TEST_FAIL_RANK");
+          const char* e = opt_text(O_TEST_FAIL_RANK);
           if (!e || !*e) return std::pair<long, long>(-1, 0);
           const char* colon = strchr(e, ':');
           return std::pair<long, long>(strtol(e, nullptr, 10), colon ? strtol(colon + 1, nullptr, 10) : 1);

@@ -310,11 +310,8 @@ struct NttPass {
 constexpr uint32_t ntt_tile_log_by_size(uint32_t k) { return k >= 23 ? 10u : 11u; }
 // ZKPOA_NTT_TILE=10|11 forces either (measurement, and the tests' way to the large-size plan at a small k)
 inline uint32_t ntt_tile_log(uint32_t k) {
-  static const int forced = [] {
-    const char* e = getenv("ZKPOA_NTT_TILE");
-    return e ? atoi(e) : 0;
-  }();
-  return forced == 10 || forced == 11 ? (uint32_t)forced : ntt_tile_log_by_size(k);
+  const long forced = opt_long(O_NTT_TILE);
+  return forced ? (uint32_t)forced : ntt_tile_log_by_size(k);
 }
 
 // The passes of a size-2^k transform on tiles of 2^tile_log elements, in DIT order (stage 0 upwards; DIF runs them in

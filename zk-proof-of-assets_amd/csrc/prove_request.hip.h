@@ -146,7 +146,8 @@ struct EnvBlinding {
   uint8_t rb[32], sb[32];
   const uint8_t *r = nullptr, *s = nullptr;
   EnvBlinding() {
-    if (req_getenv("ZKPOA_R") || req_getenv("ZKPOA_S")) {
+    const char *er = opt_text(O_R), *es = opt_text(O_S);
+    if (er || es) {
       static bool warned = false;
       if (!warned) {
         warned = true;
@@ -154,12 +155,12 @@ struct EnvBlinding {
                         "not zero-knowledge; unset them in production\n");
       }
     }
-    if (const char* e = req_getenv("ZKPOA_R")) {
-      if (!parse_decimal_mod_r(e, rb)) throw ProverError(PROVER_ERROR, "ZKPOA_R is not a decimal number");
+    if (er) {
+      if (!parse_decimal_mod_r(er, rb)) throw ProverError(PROVER_ERROR, "ZKPOA_R is not a decimal number");
       r = rb;
     }
-    if (const char* e = req_getenv("ZKPOA_S")) {
-      if (!parse_decimal_mod_r(e, sb)) throw ProverError(PROVER_ERROR, "ZKPOA_S is not a decimal number");
+    if (es) {
+      if (!parse_decimal_mod_r(es, sb)) throw ProverError(PROVER_ERROR, "ZKPOA_S is not a decimal number");
       s = sb;
     }
   }
@@ -170,17 +171,13 @@ struct EnvBlinding {
 // proof points + public values -> the two JSON texts (ZKPOA_JSON style) + the ZKPOA_VERBOSE phase line
 int emit_outputs(zkpoa_context* ctx, const zkpoa_zkey* zk, const uint8_t pts[256], const uint8_t* pub, const ProveOut& out,
                  double load_ms, uint64_t zkey_size, const char* how) {
-  int style = 0;
-  if (const char* e = req_getenv("ZKPOA_JSON")) style = (strcmp(e, "snarkjs") == 0) ? 1 : 0;
+  const int style = opt_choice(O_JSON);   // rapidsnark | snarkjs
   const int rc = out.write(proof_json(pts, style), public_json(pub, zk->nPublic, style));
-  if (req_getenv("ZKPOA_VERBOSE")) {
-    fprintf(stderr,
-            "zkpoa: nVars=%u nPublic=%u domain=2^%u nCoefs=%llu | zkey %s %.1f ms (%.2f GB/s) | witness -> HBM %.2f ms "
-            "(%.0f MB, %.1f GB/s) | h-chain %.2f ms, msm phase %.2f ms, prove %.2f ms, self-check %.2f ms\n",
-            zk->nVars, zk->nPublic, zk->power, (unsigned long long)zk->nCoefs, how, load_ms,
-            load_ms > 0 ? (double)zkey_size / load_ms / 1e6 : 0.0, ctx->io_ms[0], ctx->io_ms[1],
-            ctx->io_ms[0] > 0 ? ctx->io_ms[1] / ctx->io_ms[0] : 0.0, ctx->ms[3], ctx->ms[4], ctx->ms[5], ctx->ms[6]);
-  }
+  vlog("zkpoa: nVars=%u nPublic=%u domain=2^%u nCoefs=%llu | zkey %s %.1f ms (%.2f GB/s) | witness -> HBM %.2f ms "
+       "(%.0f MB, %.1f GB/s) | h-chain %.2f ms, msm phase %.2f ms, prove %.2f ms, self-check %.2f ms\n",
+       zk->nVars, zk->nPublic, zk->power, (unsigned long long)zk->nCoefs, how, load_ms,
+       load_ms > 0 ? (double)zkey_size / load_ms / 1e6 : 0.0, ctx->io_ms[0], ctx->io_ms[1],
+       ctx->io_ms[0] > 0 ? ctx->io_ms[1] / ctx->io_ms[0] : 0.0, ctx->ms[3], ctx->ms[4], ctx->ms[5], ctx->ms[6]);
   return rc;
 }
 
@@ -211,9 +208,8 @@ int prove_to_json(zkpoa_context* ctx, const zkpoa_zkey* zk, const WtnsSrc& wsrc,
 // of the proof where load and prove are one phase.
 int load_and_prove_to_json(zkpoa_context* ctx, const uint8_t* zkey, uint64_t zkey_size, const WtnsSrc& wsrc,
                            const ProveOut& out, KeyPtr& zk, int zkey_fd = -1) {
-  const char* ov = getenv("ZKPOA_OVERLAP");
   const auto tl0 = std::chrono::steady_clock::now();
-  if (!ov || strcmp(ov, "0") != 0) {
+  if (opt_flag(O_OVERLAP)) {
     WtnsView w = parse_wtns(wsrc);
     const EnvBlinding bl;
     uint8_t parts[384], pts[256];
@@ -260,10 +256,9 @@ int multi_prove_to_json(DeviceSet* ds, MultiKey* mk, const WtnsSrc& wsrc, const 
     assemble_proof(c0, z0, parts, bl.r, bl.s, t0, pts);
     selfcheck(c0, z0, pts, pubs, ~0ull);   // this one must verify
   }
-  if (req_getenv("ZKPOA_VERBOSE"))
-    fprintf(stderr, "zkpoa: one proof over %zu ranks: H-scalar chain %s, sections 5-8 %s, %.2f GB of fixed-base tables; "
-                    "prove %.2f ms\n", ds->ids.size(), mk->split ? "split (2 peer-to-peer exchanges)" : "replicated",
-            z0->bc_log ? "block-cyclic" : "contiguous ranges", mk->table_bytes / 1e9, c0->ms[5]);
+  vlog("zkpoa: one proof over %zu ranks: H-scalar chain %s, sections 5-8 %s, %.2f GB of fixed-base tables; prove %.2f ms\n",
+       ds->ids.size(), mk->split ? "split (2 peer-to-peer exchanges)" : "replicated",
+       z0->bc_log ? "block-cyclic" : "contiguous ranges", mk->table_bytes / 1e9, c0->ms[5]);
   return emit_outputs(c0, z0, pts, pubs, out, mk->load_ms, zkey_size, cache_hit ? "cached," : "sharded load");
 }
 
@@ -279,12 +274,7 @@ int multi_prove_to_json(DeviceSet* ds, MultiKey* mk, const WtnsSrc& wsrc, const 
 // cache is released. Touched only under g_stage_mutex; changed only with both locks held and g_staged_users == 0.
 uint64_t g_key_clock = 0;
 
-size_t key_cache_capacity() {
-  const char* e = getenv("ZKPOA_KEY_CACHE");
-  if (!e || !*e) return 2;
-  long v = atol(e);
-  return v < 0 ? 0 : (size_t)v;
-}
+size_t key_cache_capacity() { return (size_t)opt_long(O_KEY_CACHE); }
 
 template <class Key, class Free>
 struct KeyCache {
@@ -357,24 +347,12 @@ KeyCache<MultiKey, std::default_delete<MultiKey>> g_multi_cache;
 // -- zkpoa_idle_work builds one table per call when the library has nothing else to do (the `prover` server calls it
 // after 300 ms without a request) -- except for a key that has served ZKPOA_PRECOMP_AFTER proofs (default 64) in a host
 // that never calls it. "eager" = the r03 behaviour, "0" = never.
-enum PrecompPolicy { kPrecompOff, kPrecompEager, kPrecompIdle };
-PrecompPolicy precomp_policy() {
-  const char* e = getenv("ZKPOA_PRECOMP");
-  if (!e || !*e) return kPrecompIdle;
-  if (!strcmp(e, "0") || !strcmp(e, "off")) return kPrecompOff;
-  if (!strcmp(e, "eager")) return kPrecompEager;
-  return kPrecompIdle;
-}
-uint64_t precomp_after() {
-  const char* e = getenv("ZKPOA_PRECOMP_AFTER");
-  const long v = e && *e ? atol(e) : 64;
-  return v < 1 ? 1 : (uint64_t)v;
-}
+enum PrecompPolicy { kPrecompIdle, kPrecompOff, kPrecompOffWord, kPrecompEager };   // the row's words: idle | 0 | off | eager
 // must this request build the key's tables before it proves? (done = proofs the key has served, settled / bytes = its tables)
 bool tables_due_now(uint64_t done, bool settled, uint64_t bytes) {
-  switch (precomp_policy()) {
+  switch (opt_choice(O_PRECOMP)) {
     case kPrecompEager: return done == 1 && bytes == 0;
-    case kPrecompIdle: return done >= precomp_after() && !settled && bytes == 0;
+    case kPrecompIdle: return done >= (uint64_t)opt_long(O_PRECOMP_AFTER) && !settled && bytes == 0;
     default: return false;
   }
 }
@@ -458,9 +436,8 @@ int multi_file_prove(DeviceSet* ds, int fd, const struct stat& sb, const char* p
       const auto tp0 = std::chrono::steady_clock::now();
       multi_precompute(ds, mk);
       mk->tables_tried = true;
-      if (req_getenv("ZKPOA_VERBOSE"))
-        fprintf(stderr, "zkpoa: fixed-base tables for the cached key on %zu ranks: %.2f GB in %.0f ms\n", ds->ids.size(),
-                mk->table_bytes / 1e9, ms_since(tp0));
+      vlog("zkpoa: fixed-base tables for the cached key on %zu ranks: %.2f GB in %.0f ms\n", ds->ids.size(),
+           mk->table_bytes / 1e9, ms_since(tp0));
     }
     rc = multi_prove_to_json(ds, mk, wsrc, out, (uint64_t)sb.st_size, hit);
     mk->proofs_done++;
@@ -536,8 +513,7 @@ int single_file_prove(zkpoa_context* ctx, const DeviceSet* ds, int fd, const str
         const auto tp0 = std::chrono::steady_clock::now();
         try {
           uint64_t used = zkey_precompute(ctx, zk, 0);
-          if (req_getenv("ZKPOA_VERBOSE"))
-            fprintf(stderr, "zkpoa: fixed-base tables for the cached key: %.2f GB in %.0f ms\n", used / 1e9, ms_since(tp0));
+          vlog("zkpoa: fixed-base tables for the cached key: %.2f GB in %.0f ms\n", used / 1e9, ms_since(tp0));
         } catch (const HipError&) {   // out of HBM: the classic form keeps working
           zk->release_tables();
           (void)hipGetLastError();
@@ -598,7 +574,7 @@ int zkey_file_prove(const char* path, const WtnsSrc& wsrc, const ProveOut& out) 
 
 // zkpoa_idle_work (prover.hip): one step of background work, or 0 when there is none or a request is in flight
 int idle_work() {
-  if (precomp_policy() != kPrecompIdle) return 0;
+  if (opt_choice(O_PRECOMP) != kPrecompIdle) return 0;
   std::unique_lock<std::mutex> stage_lk(g_stage_mutex, std::try_to_lock);
   if (!stage_lk.owns_lock() || g_staged_users) return 0;
   std::unique_lock<std::mutex> lk(g_prove_mutex, std::try_to_lock);
@@ -609,7 +585,6 @@ int idle_work() {
     ds = g_devset;
   }
   if (!ds) return 0;
-  const bool verbose = getenv("ZKPOA_VERBOSE") != nullptr;
   try {
     if (ds->ids.size() > 1) {   // a sharded key: the whole set of tables in one step, no warm-up proof
       for (auto& c : g_multi_cache.entries)
@@ -617,9 +592,8 @@ int idle_work() {
           const auto t0 = std::chrono::steady_clock::now();
           c.key->tables_tried = true;
           multi_precompute(ds, c.key.get());
-          if (verbose)
-            fprintf(stderr, "zkpoa: idle: fixed-base tables for the cached key on %zu ranks: %.2f GB in %.0f ms\n", ds->ids.size(),
-                    c.key->table_bytes / 1e9, ms_since(t0));
+          vlog("zkpoa: idle: fixed-base tables for the cached key on %zu ranks: %.2f GB in %.0f ms\n", ds->ids.size(),
+               c.key->table_bytes / 1e9, ms_since(t0));
           return 1;
         }
       return 0;
@@ -643,7 +617,7 @@ int idle_work() {
           c.key->warmed = true;
           uint8_t parts[384];
           prove_partials(ctx, c.key.get(), parts);
-          if (verbose) fprintf(stderr, "zkpoa: idle: warm-up proof through the new tables: %.0f ms\n", ms_since(t0));
+          vlog("zkpoa: idle: warm-up proof through the new tables: %.0f ms\n", ms_since(t0));
           return 1;
         }
       return 0;
@@ -656,10 +630,8 @@ int idle_work() {
       (void)hipGetLastError();
       pick->tables_settled = true;
     }
-    if (verbose)
-      fprintf(stderr, "zkpoa: idle: fixed-base table step for the cached key: +%.2f GB in %.0f ms (%.2f GB so far%s)\n",
-              (pick->table_bytes - before) / 1e9, ms_since(t0), pick->table_bytes / 1e9,
-              pick->tables_settled ? ", complete" : "");
+    vlog("zkpoa: idle: fixed-base table step for the cached key: +%.2f GB in %.0f ms (%.2f GB so far%s)\n",
+         (pick->table_bytes - before) / 1e9, ms_since(t0), pick->table_bytes / 1e9, pick->tables_settled ? ", complete" : "");
     return 1;
   } catch (const std::exception&) {
     return 0;

@@ -40,29 +40,6 @@ struct ProverError : std::runtime_error {
   ProverError(int c, const std::string& s) : std::runtime_error(s), code(c) {}
 };
 
-// ---- per-request options ---------------------------------------------------------------------------------
-// The one-shot entry points take r, s, the JSON style and verbosity from the environment (ZKPOA_R / _S / _JSON /
-// _VERBOSE). A resident server answers several clients from several threads and must not mutate its process
-// environment per request: zkpoa_set_thread_options gives the calling thread values that take precedence over the
-// environment for its following calls (empty string = "unset for this thread even if the environment has it").
-struct ReqOptions {
-  bool active = false;
-  std::string r, s, json, verbose;
-};
-ReqOptions& req_options() {
-  static thread_local ReqOptions o;
-  return o;
-}
-const char* req_getenv(const char* name) {
-  const ReqOptions& o = req_options();
-  if (o.active) {
-    const std::string* v = !strcmp(name, "ZKPOA_R") ? &o.r : !strcmp(name, "ZKPOA_S") ? &o.s :
-                           !strcmp(name, "ZKPOA_JSON") ? &o.json : !strcmp(name, "ZKPOA_VERBOSE") ? &o.verbose : nullptr;
-    if (v) return v->empty() ? nullptr : v->c_str();
-  }
-  return getenv(name);
-}
-
 // ---- binfile container (the scan itself: binfile.hpp) with the prover's error texts
 struct Section {
   const uint8_t* p = nullptr;
@@ -99,9 +76,9 @@ DevMem dev_upload(zkpoa_context* ctx, const void* src, size_t bytes) {
   d.alloc(bytes);
   auto t1 = std::chrono::steady_clock::now();
   if (bytes) ctx->uploader.upload(d.get(), src, bytes, ctx->dev.device, ctx->dev.lanes[0].stream);
-  if (req_getenv("ZKPOA_VERBOSE") && bytes > (16u << 20))
-    fprintf(stderr, "zkpoa:   upload %.0f MB: hipMalloc %.1f ms, copy %.1f ms\n", bytes / 1e6,
-            std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
+  if (bytes > (16u << 20))
+    vlog("zkpoa:   upload %.0f MB: hipMalloc %.1f ms, copy %.1f ms\n", bytes / 1e6,
+         std::chrono::duration<double, std::milli>(t1 - t0).count(), ms_since(t1));
   return d;
 }
 
@@ -276,7 +253,7 @@ KeyPtr zkey_parse(const uint8_t* buf, uint64_t size, ZkeySections& out) {
 }
 
 struct LoadPhases {   // ZKPOA_VERBOSE: where a key load spends its time
-  bool verbose = req_getenv("ZKPOA_VERBOSE") != nullptr;
+  bool verbose = opt_verbose();
   std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
   void operator()(const char* what) {
     if (verbose) fprintf(stderr, "zkpoa: zkey load: %-34s %7.1f ms\n", what, ms_since(t));
@@ -705,8 +682,7 @@ uint64_t zkey_precompute(zkpoa_context* ctx, zkpoa_zkey* zk, uint64_t budget, in
   // H scalars are uniform (its table: msm_table_build's own width); the A / B / C tables are sized for witness scalars
   // when a proof has measured some
   auto witness_c = [&](uint64_t n, bool g2) {
-    if (const char* e = getenv("ZKPOA_WITNESS_TABLE_C"))   // experiments only
-      if (atoi(e) >= 4 && atoi(e) <= 25) return atoi(e);
+    if (const long c = opt_long(O_WITNESS_TABLE_C)) return (int)c;   // experiments only
     return (int)msm_table_c(n, force_c, g2, zk->have_density ? zk->witness_density : nullptr);
   };
   // (one window width for both B tables: the G2 model's -- shorter pieces -- as the shared sort is planned for G2)
@@ -843,12 +819,10 @@ static void budget_lane_workspaces(zkpoa_context* ctx, const zkpoa_zkey* zk) {
     ZK_HIP(hipStreamSynchronize(ctx->dev.lanes[l].stream));
     ctx->dev.lanes[l].ws.release();
   }
-  if (getenv("ZKPOA_VERBOSE"))
-    fprintf(stderr,
-            "zkpoa:   HBM budget: %.1f GB free + %.1f GB held by the lanes; MSMs take at most H %llu, A %llu, B1 %llu, B2 %llu, "
-            "C %llu points at once (workspaces %.1f GB)\n",
-            free_b / 1e9, held / 1e9, (unsigned long long)lim[0], (unsigned long long)lim[1], (unsigned long long)lim[2],
-            (unsigned long long)lim[3], (unsigned long long)lim[4], w.total() / 1e9);
+  vlog("zkpoa:   HBM budget: %.1f GB free + %.1f GB held by the lanes; MSMs take at most H %llu, A %llu, B1 %llu, B2 %llu, "
+       "C %llu points at once (workspaces %.1f GB)\n",
+       free_b / 1e9, held / 1e9, (unsigned long long)lim[0], (unsigned long long)lim[1], (unsigned long long)lim[2],
+       (unsigned long long)lim[3], (unsigned long long)lim[4], w.total() / 1e9);
 }
 
 // Partial MSM results of this handle's shard: A(64) B1(64) B2(128) C(64) H(64). The witness is already
@@ -897,8 +871,7 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
   // first witness stage that gets there, on its own lane; the classic-form witness MSMs size their windows with it
   std::once_flag density_once;
   auto with_density = [&](int lane_id) -> const double* {
-    const char* nd = getenv("ZKPOA_NO_DENSITY");
-    if ((nd && *nd && strcmp(nd, "0") != 0) || !zk->d_flag || !zk->d_witness) return nullptr;
+    if (opt_flag(O_NO_DENSITY) || !zk->d_flag || !zk->d_witness) return nullptr;
     std::call_once(density_once, [&] {
       if (zk->have_density) return;
       msm_density(ctx->dev.lanes[lane_id].stream, zk->d_witness, zk->nVars, zk->witness_density,
@@ -955,7 +928,7 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
           sorted_b = msm_sort_run(ctx, 2, zk->qB.scalars.get(), stage_request(ctx, vB1, sort_limit, dens, true));
         } catch (const OomError& e) {   // no room for the whole query's sort: B1 and B2 each go through it in pieces
           if (!ctx->shrink_after_oom(2, zk->qB.cnt)) throw;
-          if (getenv("ZKPOA_VERBOSE")) fprintf(stderr, "zkpoa:   B query: %s; B1 and B2 sort their own pieces\n", e.what());
+          vlog("zkpoa:   B query: %s; B1 and B2 sort their own pieces\n", e.what());
           share_b = false;
           table_c_b = 0;
         }
@@ -981,7 +954,7 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
         msm_accum_g2(ctx, 3, sr, false, table_c_b ? msm_table_data(vB2.table) : vB2.bases, outB2, msm_ms[3]);
       } catch (const OomError& e) {   // the G2 buckets of the whole query did not fit beside the rest: own sort, in pieces
         if (!ctx->shrink_after_oom(3, zk->qB.cnt)) throw;
-        if (getenv("ZKPOA_VERBOSE")) fprintf(stderr, "zkpoa:   B2: %s; sorting its own pieces\n", e.what());
+        vlog("zkpoa:   B2: %s; sorting its own pieces\n", e.what());
         shared = false;
       }
     }
@@ -1109,11 +1082,8 @@ void prove_core(zkpoa_context* ctx, const zkpoa_zkey* zk, const uint8_t* r_le, c
 // handle (a key whose conventions differ from SURVEY.md 8c fails on first contact, not downstream), "all" = every
 // proof. Host only (csrc/verify.hip, ~7 ms). Keys without section 3 / assembled from device buffers are skipped.
 int selfcheck_mode() {
-  const char* e = getenv("ZKPOA_SELFCHECK");
-  if (!e || !*e) return 1;
-  if (!strcmp(e, "0") || !strcmp(e, "off")) return 0;
-  if (!strcmp(e, "all") || !strcmp(e, "2")) return 2;
-  return 1;
+  static const int kMode[] = {1, 0, 0, 2, 2};   // of the row's words: 1 | 0 | off | all | 2
+  return kMode[opt_choice(O_SELFCHECK)];
 }
 
 struct SelfCheckFailed : ProverError {   // the proof was computed and does not verify (as opposed to "could not be checked")
@@ -1134,7 +1104,7 @@ void selfcheck(zkpoa_context* ctx, const zkpoa_zkey* zk, const uint8_t proof_poi
   ctx->ms[6] = (float)ms_since(t0);
   if (rc == PROVER_OK) {
     zk->selfchecks_done++;
-    if (req_getenv("ZKPOA_VERBOSE")) fprintf(stderr, "zkpoa: self-check: proof verifies against the zkey's own verification key (%.1f ms)\n", ctx->ms[6]);
+    vlog("zkpoa: self-check: proof verifies against the zkey's own verification key (%.1f ms)\n", ctx->ms[6]);
     return;
   }
   if (rc == ZKPOA_VERIFY_INVALID_PROOF)
@@ -1206,9 +1176,8 @@ KeyPtr load_prove_staged(zkpoa_context* ctx, const uint8_t* buf, uint64_t size, 
     const double peak = (double)n * 64 + (double)m * (64 + 128 + 64) + (double)nC * 64 + (double)m * 32 +
                         (double)zk->nCoefs * (44 + 36) + (double)n * (8 + 96) + (double)m * (108 + 236);
     if (peak > 0.72 * (double)total_b || peak > 0.8 * (double)free_b) {
-      if (req_getenv("ZKPOA_VERBOSE"))
-        fprintf(stderr, "zkpoa: the overlapped load would hold %.0f GB at its peak (%.0f GB free of %.0f): loading the key first\n",
-                peak / 1e9, free_b / 1e9, total_b / 1e9);
+      vlog("zkpoa: the overlapped load would hold %.0f GB at its peak (%.0f GB free of %.0f): loading the key first\n",
+           peak / 1e9, free_b / 1e9, total_b / 1e9);
       return nullptr;
     }
   }
@@ -1233,7 +1202,7 @@ KeyPtr load_prove_staged(zkpoa_context* ctx, const uint8_t* buf, uint64_t size, 
   std::atomic<bool> cancel{false};
   std::thread uploader;   // not a SideTask: cancel, join and drain the device are one unit (Ending), in that order
   Staging stg;
-  const bool verbose = req_getenv("ZKPOA_VERBOSE") != nullptr;
+  const bool verbose = opt_verbose();
   const auto t_start = std::chrono::steady_clock::now();
   auto mark = [&, verbose](const char* what) {   // ZKPOA_VERBOSE: the timeline of an overlapped load + prove
     if (verbose)
@@ -1794,7 +1763,7 @@ extern "C" int zkpoa_groth16_prover_files(const char* zkey_file_path, const char
 }
 
 extern "C" int zkpoa_set_thread_options(const char* r_dec, const char* s_dec, const char* json_style, int verbose) {
-  ReqOptions& o = req_options();
+  OptOverlay& o = opt_overlay();
   o.active = true;
   o.r = r_dec ? r_dec : "";
   o.s = s_dec ? s_dec : "";
@@ -1804,7 +1773,7 @@ extern "C" int zkpoa_set_thread_options(const char* r_dec, const char* s_dec, co
 }
 
 extern "C" int zkpoa_clear_thread_options(void) {
-  req_options() = ReqOptions();
+  opt_overlay() = OptOverlay();
   return PROVER_OK;
 }
 

@@ -41,12 +41,15 @@
 #include <thread>
 #include <vector>
 
+using namespace zkpoa;
+
 // The library is loaded on demand (dlopen): a client of the resident server never proves itself, and resolving
 // libzkpoa_prover.so with the HIP runtime behind it costs ~11 ms of every call (measured r04: 28 ms per layer-one
 // proof through the server, of which 15 in the server). Looked for next to this executable, then on the usual path.
 typedef int (*prover_files_fn)(const char*, const char*, char*, unsigned long*, char*, unsigned long*, char*, unsigned long);
 typedef int (*thread_options_fn)(const char*, const char*, const char*, int);
 static thread_options_fn g_set_thread_options = nullptr;   // per-request r, s, JSON style, verbosity of a server thread
+static int (*g_clear_thread_options)(void) = nullptr;      // ... which end with the request (the thread's idle work is nobody's)
 typedef int (*idle_work_fn)(void);
 static std::atomic<idle_work_fn> g_idle_work{nullptr};     // one step of the library's background work (fixed-base tables)
 static std::mutex g_load_mutex;
@@ -74,6 +77,7 @@ static prover_files_fn load_prover(std::string& message) {
   fn = reinterpret_cast<prover_files_fn>(dlsym(h, "zkpoa_groth16_prover_files"));
   if (!fn) message = "Error: libzkpoa_prover.so does not export zkpoa_groth16_prover_files";
   g_set_thread_options = reinterpret_cast<thread_options_fn>(dlsym(h, "zkpoa_set_thread_options"));
+  g_clear_thread_options = reinterpret_cast<int (*)(void)>(dlsym(h, "zkpoa_clear_thread_options"));
   g_idle_work.store(reinterpret_cast<idle_work_fn>(dlsym(h, "zkpoa_idle_work")));
   return fn;
 }
@@ -175,10 +179,6 @@ static void log_fault(const char* what, const std::string& detail, const char* z
   }
   fprintf(stderr, "zkpoa: GPU-side failure recorded in %s\n", path.c_str());
 }
-static bool strict_mode() {
-  const char* e = getenv("ZKPOA_STRICT");
-  return e && *e && strcmp(e, "0") != 0;
-}
 enum { kExitStrict = 5 };   // ZKPOA_STRICT=1: the server failed and the fallback was refused
 
 // ---- server mode ---------------------------------------------------------------------------------------
@@ -225,9 +225,9 @@ static bool recv_msg(int fd, std::string& m) {
 }
 
 static std::string server_socket_path() {
-  const char* e = getenv("ZKPOA_SERVER");
+  const char* e = opt_text(O_SERVER);
   if (e && e[0] == '/') return e;
-  const char* dev = getenv("ZKPOA_DEVICE");
+  const char* dev = opt_text(O_DEVICE);
   return "/tmp/zkpoa-" + std::to_string((long)getuid()) + "/prover-dev" + (dev && *dev ? dev : "0") + ".sock";
 }
 
@@ -238,7 +238,7 @@ static bool secure_dir(const std::string& sock) {
   if (mkdir(dir.c_str(), 0700) != 0 && errno != EEXIST) return false;
   struct stat sb;
   if (lstat(dir.c_str(), &sb) != 0 || !S_ISDIR(sb.st_mode) || sb.st_uid != getuid()) return false;
-  return (sb.st_mode & 0077) == 0 || getenv("ZKPOA_SERVER")[0] == '/';   // an explicit path is the caller's choice
+  return (sb.st_mode & 0077) == 0 || opt_text(O_SERVER)[0] == '/';   // an explicit path is the caller's choice
 }
 
 // pid of the server behind a connected socket, taken from the kernel (SO_PEERCRED: the credentials of the process that
@@ -298,16 +298,12 @@ static int server_main(const std::string& sock) {
   bool ok = ls >= 0 && bind(ls, reinterpret_cast<struct sockaddr*>(&sa), sizeof(sa)) == 0 && listen(ls, 64) == 0;
   umask(old);
   if (!ok) return 1;
-  int idle_s = 600;
-  if (const char* e = getenv("ZKPOA_SERVER_IDLE_S")) idle_s = atoi(e) > 0 ? atoi(e) : idle_s;
+  const long idle_s = opt_long(O_SERVER_IDLE_S);
   // Requests are served by a small pool of threads (ZKPOA_SERVER_WORKERS, default 2): the library stages the witness
   // of one request while it proves another (two locks inside zkpoa_groth16_prover_files), so the batch jobs the
   // reference runs in parallel (scripts/full_workflow.sh:552) do not pay the witness upload one after the other.
-  double idle_work_ms = 300;
-  if (const char* e = getenv("ZKPOA_SERVER_IDLE_WORK_MS")) idle_work_ms = atof(e) >= 0 ? atof(e) : idle_work_ms;
-  int workers = 2;
-  if (const char* e = getenv("ZKPOA_SERVER_WORKERS")) workers = atoi(e) >= 1 && atoi(e) <= 8 ? atoi(e) : workers;
-  static const bool test_crash = getenv("ZKPOA_SERVER_TEST_CRASH") != nullptr;   // tests: die with a request in hand
+  const double idle_work_ms = (double)opt_long(O_SERVER_IDLE_WORK_MS);
+  const long workers = opt_long(O_SERVER_WORKERS);
   std::mutex qm;
   std::condition_variable qcv;
   std::vector<int> queue;          // accepted connections waiting for a worker
@@ -337,8 +333,7 @@ static int server_main(const std::string& sock) {
       return;
     }
     {   // a client that connects and then says nothing must not hold a worker
-      struct timeval tv = {10, 0};
-      if (const char* e = getenv("ZKPOA_SERVER_RCV_TIMEOUT_S")) tv.tv_sec = atoi(e) > 0 ? atoi(e) : 10;
+      struct timeval tv = {opt_long(O_SERVER_RCV_TIMEOUT_S), 0};
       (void)setsockopt(c, SOL_SOCKET, SO_RCVTIMEO, &tv, sizeof(tv));
       (void)setsockopt(c, SOL_SOCKET, SO_SNDTIMEO, &tv, sizeof(tv));
     }
@@ -367,7 +362,7 @@ static int server_main(const std::string& sock) {
       } else if (f.size() >= 9 && f[0] == "prove") {
         const double t0 = now_ms();
         std::string message;
-        if (test_crash) _exit(3);
+        if (opt_flag(O_SERVER_TEST_CRASH)) _exit(3);   // tests: die with a request in hand
         bool runtime_failure = false;
         // r, s, JSON style and verbosity of THIS request, for this thread only (the library's phase line of a verbose
         // request goes to <socket>.log); never through the process environment: other workers are proving
@@ -376,6 +371,7 @@ static int server_main(const std::string& sock) {
           g_set_thread_options(f[5].empty() ? nullptr : f[5].c_str(), f[6].empty() ? nullptr : f[6].c_str(),
                                f[7].empty() ? nullptr : f[7].c_str(), f[8].empty() ? 0 : 1);
         int rc = prove_files(f[1].c_str(), f[2].c_str(), f[3].c_str(), f[4].c_str(), message, &runtime_failure);
+        if (g_clear_thread_options) g_clear_thread_options();
         if (rc == EXIT_SUCCESS) idle_pending.store(true);
         if (rc == EXIT_SUCCESS && !f[8].empty())
           message = "zkpoa: prover server pid " + std::to_string((long)getpid()) + " served the proof in " +
@@ -522,9 +518,9 @@ static int client_main(char** argv, const std::string& sock, bool stop) {
   if (stop) {
     req = "stop";
   } else {
-    auto env = [](const char* n) { const char* e = getenv(n); return std::string(e ? e : ""); };
+    auto text = [](Opt id) { const char* e = opt_text(id); return std::string(e ? e : ""); };
     const std::string fields[] = {"prove", abs_path(argv[1]), abs_path(argv[2]), abs_path(argv[3]), abs_path(argv[4]),
-                                  env("ZKPOA_R"), env("ZKPOA_S"), env("ZKPOA_JSON"), env("ZKPOA_VERBOSE")};
+                                  text(O_R), text(O_S), opt_choice(O_JSON) ? "snarkjs" : "", opt_verbose() ? "1" : ""};
     for (size_t i = 0; i < 9; i++) {
       if (i) req.push_back('\0');
       req += fields[i];
@@ -533,9 +529,7 @@ static int client_main(char** argv, const std::string& sock, bool stop) {
   std::string reply;
   {   // a server stuck on the GPU must not hang the workflow for ever: generous, since a layer-three proof with a cold
       // 21 GB key takes tens of seconds (ZKPOA_SERVER_TIMEOUT_S)
-    int to = 1800;
-    if (const char* e = getenv("ZKPOA_SERVER_TIMEOUT_S")) to = atoi(e) > 0 ? atoi(e) : to;
-    struct timeval tv = {to, 0};
+    struct timeval tv = {opt_long(O_SERVER_TIMEOUT_S), 0};
     (void)setsockopt(fd, SOL_SOCKET, SO_RCVTIMEO, &tv, sizeof(tv));
   }
   errno = 0;
@@ -553,8 +547,7 @@ static int client_main(char** argv, const std::string& sock, bool stop) {
     // process that took it is still the one that listens) is the server ended -- it may hold tens of GB of cached keys
     // in HBM. Never a re-exec: this process proves itself, a later call starts a fresh server.
     bool killed = false, alive = kill((pid_t)spid, 0) == 0;
-    const char* kw = getenv("ZKPOA_SERVER_KILL_WEDGED");
-    if (timed_out && alive && kw && !strcmp(kw, "1") && spid > 1 && spid != (long)getpid()) {
+    if (timed_out && alive && opt_flag(O_SERVER_KILL_WEDGED) && spid > 1 && spid != (long)getpid()) {
       int lf = open((sock + ".lock").c_str(), O_RDWR | O_CLOEXEC | O_NOFOLLOW);
       bool held = false;
       if (lf >= 0) {
@@ -570,7 +563,7 @@ static int client_main(char** argv, const std::string& sock, bool stop) {
     log_fault(timed_out ? "prover server did not answer in time" : "prover server went away without answering",
               std::string("server pid ") + std::to_string(spid) + (killed ? " (killed)" : alive ? " (left running)" : " (gone)"),
               argv[1]);
-    if (strict_mode()) {
+    if (opt_flag(O_STRICT)) {
       fprintf(stderr, "zkpoa: the prover server went away without answering; ZKPOA_STRICT is set: not proving in-process\n");
       return kExitStrict;
     }
@@ -580,7 +573,7 @@ static int client_main(char** argv, const std::string& sock, bool stop) {
   close(fd);
   if (reply[0] == 'R') {
     log_fault("prover server reported a GPU runtime failure", reply.substr(1), argv[1]);
-    if (strict_mode()) {
+    if (opt_flag(O_STRICT)) {
       fprintf(stderr, "zkpoa: the prover server reported a GPU runtime failure (%s); ZKPOA_STRICT is set: not proving "
                       "in-process\n", reply.c_str() + 1);
       return kExitStrict;
@@ -600,8 +593,7 @@ int main(int argc, char** argv) {
   // default of four hardware queues they share queues, so an upload that should overlap the compute sits behind a
   // lane's kernels. Never overrides the caller's own setting.
   setenv("GPU_MAX_HW_QUEUES", "16", 0);
-  const char* srv = getenv("ZKPOA_SERVER");
-  const bool use_server = srv && *srv && strcmp(srv, "0") != 0;
+  const bool use_server = opt_flag(O_SERVER);
   if (argc == 2 && strcmp(argv[1], "--stop-server") == 0) {
     if (!use_server) setenv("ZKPOA_SERVER", "1", 1);
     return client_main(argv, server_socket_path(), true);
@@ -613,7 +605,7 @@ int main(int argc, char** argv) {
   if (use_server) {
     int rc = client_main(argv, server_socket_path(), false);
     if (rc >= 0) {
-      if (getenv("ZKPOA_VERBOSE")) fprintf(stderr, "zkpoa: prover process total %.1f ms\n", now_ms() - t_start);
+      vlog("zkpoa: prover process total %.1f ms\n", now_ms() - t_start);
       return rc;
     }
     // no server reachable: prove in this process (still on the GPU)
@@ -631,9 +623,9 @@ int main(int argc, char** argv) {
     if (we.is_worker()) we.leave(rc);
     return rc;
   }
-  if (getenv("ZKPOA_VERBOSE"))   // (CLOCK_MONOTONIC stamps: a caller can see what it waited for before main and after it)
-    fprintf(stderr, "zkpoa: prover process total %.1f ms (main entered at %.1f, leaving at %.1f)%s\n", now_ms() - t_start, t_start,
-            now_ms(), we.is_worker() ? "; worker process, the caller is released now" : "");
+  // (CLOCK_MONOTONIC stamps: a caller can see what it waited for before main and after it)
+  vlog("zkpoa: prover process total %.1f ms (main entered at %.1f, leaving at %.1f)%s\n", now_ms() - t_start, t_start, now_ms(),
+       we.is_worker() ? "; worker process, the caller is released now" : "");
   // Both outputs are complete and renamed into place: leave without running the HIP runtime's teardown
   // (freeing tens of GB of device memory and its queues costs ~0.25 s that a one-shot prover never gets back).
   we.leave(EXIT_SUCCESS);

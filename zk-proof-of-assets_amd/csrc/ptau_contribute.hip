@@ -110,7 +110,7 @@ void draw_secrets(const p2::RecordParams& ap, const uint8_t* secrets_le, const c
       else random_scalar(sec.x[k]);
     }
     uint8_t s[3][32];
-    if (!env_scalars("ZKPOA_PHASE1_S", s, 3, "three numbers in [1, r) separated by commas", "the secrets of the contribution key's g1_s"))
+    if (!env_scalars(O_PHASE1_S, s, 3, "three numbers in [1, r) separated by commas", "the secrets of the contribution key's g1_s"))
       for (int k = 0; k < 3; k++) random_scalar(s[k]);
     uint8_t g1[64];
     h_affine_to_bytes<HFq>(host_generator<HFq>(), g1);

@@ -626,7 +626,7 @@ void zkey_contribute(zkpoa_context* ctx, const char* in_path, const char* out_pa
     else random_scalar(d);
     if (rec) {
       uint8_t sb[1][32];   // ZKPOA_PHASE2_S: the s of g1_s = s * G1
-      if (!env_scalars("ZKPOA_PHASE2_S", sb, 1, "a number in [1, r)", "a secret of the contribution record")) random_scalar(sb[0]);
+      if (!env_scalars(O_PHASE2_S, sb, 1, "a number in [1, r)", "a secret of the contribution record")) random_scalar(sb[0]);
       h_affine_to_bytes<HFq>(host_generator<HFq>(), g1_s);
       p2::mul_wire<HFq>(g1_s, sb[0], g1_s);
     }

@@ -116,9 +116,9 @@ void random_scalar(uint8_t d[32]) {   // uniform on [1, r): 254 random bits, rej
   } while (!scalar_in_range(d, true));
 }
 // Tests / reproducible records only: `count` numbers in [1, r), decimal or 0x... hex, separated by commas, from the
-// environment variable `name`. False when it is not set; anything else than `shape` throws; a warning names `secrets`.
-bool env_scalars(const char* name, uint8_t out[][32], int count, const char* shape, const char* secrets) {
-  const char* e = getenv(name);
+// text row `id`. False when it is not set; anything else than `shape` throws; a warning names `secrets`.
+bool env_scalars(Opt id, uint8_t out[][32], int count, const char* shape, const char* secrets) {
+  const char *e = opt_text(id), *name = opt_row(id).name;
   if (!e) return false;
   for (int k = 0; k < count; k++) {
     const char* end = strchr(e, ',');

@@ -25,6 +25,7 @@
 // is not exercised.
 #include "../../include/zkpoa_prover.h"
 
+#include "host_files.hpp"
 #include "host_text.hpp"
 #include "worker_exit.hpp"
 
@@ -169,7 +170,7 @@ int main(int argc, char** argv) {
   }
   uint8_t delta[32];
   const uint8_t* delta_p = nullptr;
-  if (const char* e = cmd == kZkeyContribute ? getenv("ZKPOA_DELTA") : nullptr) {   // tests / reproducible keys only: the secret must not be kept
+  if (const char* e = cmd == kZkeyContribute ? zkpoa::opt_text(zkpoa::O_DELTA) : nullptr) {   // tests / reproducible keys only: the secret must not be kept
     zkpoa::U256 d;
     if (!d.parse_number(e, e + strlen(e))) {
       fprintf(stderr, "zkpoa-setup: ZKPOA_DELTA is not a number below 2^256\n");
@@ -224,11 +225,16 @@ int main(int argc, char** argv) {
   clock_gettime(CLOCK_MONOTONIC, &t0);
   zkpoa_context* ctx = nullptr;
   char err[512] = {0};
-  if (zkpoa_context_create(getenv("ZKPOA_DEVICE") ? atoi(getenv("ZKPOA_DEVICE")) : 0, &ctx, err, sizeof err) != PROVER_OK) {
+  int rc = PROVER_ERROR;
+  try {
+    rc = zkpoa_context_create(zkpoa::device_from_env(), &ctx, err, sizeof err);
+  } catch (const zkpoa::OptionError& e) {
+    snprintf(err, sizeof err, "%s", e.what());
+  }
+  if (rc != PROVER_OK) {
     fprintf(stderr, "zkpoa-setup: %s\n", err);
     return leave(1);
   }
-  int rc;
   if (cmd == kWtnsCheck) {   // snarkjs prints "WITNESS IS CORRECT" and exits 0, or names the failure and exits 1
     uint64_t bad = 0, first = 0;
     rc = zkpoa_wtns_check(ctx, pos[0], pos[1], &bad, &first);
@@ -347,8 +353,7 @@ int main(int argc, char** argv) {
   if (rc != PROVER_OK) fprintf(stderr, "zkpoa-setup: %s\n", zkpoa_last_error(ctx));
   if (!we.is_worker()) zkpoa_context_destroy(ctx);
   clock_gettime(CLOCK_MONOTONIC, &t1);
-  if (rc == PROVER_OK && getenv("ZKPOA_VERBOSE") && c->out_pos >= 0)
-    fprintf(stderr, "zkpoa-setup: %s written in %.2f s\n", pos[c->out_pos],
-            (t1.tv_sec - t0.tv_sec) + (t1.tv_nsec - t0.tv_nsec) / 1e9);
+  if (rc == PROVER_OK && c->out_pos >= 0)
+    zkpoa::vlog("zkpoa-setup: %s written in %.2f s\n", pos[c->out_pos], (t1.tv_sec - t0.tv_sec) + (t1.tv_nsec - t0.tv_nsec) / 1e9);
   return leave(rc == PROVER_OK ? 0 : 1);
 }

@@ -11,6 +11,8 @@
 //   * the worker keeps its GPU lock file until it is gone, so the next command on that GPU starts after it.
 // ZKPOA_DETACH_EXIT=0: one process. =always: a worker whatever `wanted` says (tests).
 #pragma once
+#include "options.hpp"
+
 #include <dlfcn.h>
 #include <errno.h>
 #include <fcntl.h>
@@ -32,9 +34,8 @@ struct WorkerExit {
   // process of a pair it does not return: it exits with the worker's status.
   static WorkerExit start(bool wanted, const char* who) {
     WorkerExit w;
-    const char* det = getenv("ZKPOA_DETACH_EXIT");
-    if (det && strcmp(det, "0") == 0) return w;
-    if (!wanted && !(det && strcmp(det, "always") == 0)) return w;
+    const int det = opt_choice(O_DETACH_EXIT);   // auto | 0 | always
+    if (det == 1 || (!wanted && det != 2)) return w;
     for (const char* lib : {"libhsa-runtime64.so.1", "libhsa-runtime64.so", "libamdhip64.so.7", "libamdhip64.so.6", "libamdhip64.so"})
       if (void* h = dlopen(lib, RTLD_NOLOAD | RTLD_LAZY)) {
         dlclose(h);

@@ -32,15 +32,7 @@ extern "C" int zkpoa_context_create(int device, zkpoa_context** out, char* error
     c->dev.init(device);
     for (auto& l : c->dev.lanes) l.ws.hold_back = &c->key_hold_back;
     // cap of every MSM lane's workspace (as option lane_workspace_max_mb): a card shared with other work
-    if (const char* e = getenv("ZKPOA_LANE_WORKSPACE_MAX_MB")) {
-      if (*e) {
-        char* end = nullptr;
-        const long v = strtol(e, &end, 10);
-        if (end == e || *end || v < 0 || v > (1l << 20))
-          throw std::runtime_error(std::string("ZKPOA_LANE_WORKSPACE_MAX_MB='") + e + "' is not a number of MiB");
-        for (auto& l : c->dev.lanes) l.ws.limit = (size_t)v << 20;
-      }
-    }
+    for (auto& l : c->dev.lanes) l.ws.limit = (size_t)opt_long(O_LANE_WORKSPACE_MAX_MB) << 20;
     for (int i = 0; i < DeviceCtx::kLanes; i++) {
       ZK_HIP(hipEventCreate(&c->ev_a[i]));
       ZK_HIP(hipEventCreate(&c->ev_b[i]));
