@@ -722,7 +722,9 @@ int zkpoa_test_ntt_plan(unsigned log_n, unsigned tile_log, uint32_t* out, unsign
  * sort feeds a G2 accumulation; density32_or_null = non-zero digits per scalar indexed by the window width (32 doubles,
  * 4..25 are read), null = uniform scalars; k0 = the forced level-0 piece length, outside 8..512 = the rule. Writes
  * thirteen words: c, W, Wb, ne, TB, K0, K, logS, logRows; sparse 0 / 1; bytes of the sort's, the G1 accumulation's and
- * the G2 accumulation's workspace (0 for n == 0); words that do not fit in cap are left out. Returns 13, or -1 for
+ * the G2 accumulation's workspace (0 for n == 0; the sizes without the guards that ZKPOA_WS_GUARD=1, a test hook of the
+ * environment, puts behind every region of a lane's workspace to catch a kernel writing past its region: an MSM then
+ * fails with an error naming the region); words that do not fit in cap are left out. Returns 13, or -1 for
  * n > 2^28, c outside 0..31, a flag that is not 0 / 1, k0 < 0 or a null out with cap > 0. */
 int zkpoa_test_msm_plan(uint64_t n, int c, int merged, int for_g2, const double* density32_or_null, int k0, uint64_t* out,
                         unsigned cap);

@@ -113,6 +113,11 @@ def test_the_table_is_well_formed(rows):
         assert not by_name[name].latched                                   # tests change these between calls
     for name in ("ZKPOA_SCAN", "ZKPOA_NO_SPARSE", "ZKPOA_NTT_TILE", "ZKPOA_EXCHANGE"):
         assert by_name[name].latched
+    # the workspace guard and its self-test: off unless asked for, hooks, and read at every use (tests set them per case)
+    guard, clobber = by_name["ZKPOA_WS_GUARD"], by_name["ZKPOA_TEST_WS_CLOBBER"]
+    assert (guard.kind, guard.dflt, guard.hook, guard.latched, guard.strict) == ("flag", 0, True, False, False)
+    assert (clobber.kind, clobber.dflt, clobber.lo, clobber.hook, clobber.latched, clobber.strict) == ("int", 0, 0, True, False, False)
+    assert clobber.hi >= 64 and want(clobber, "1") == "1" and want(clobber, "-1") == "0" and want(guard, "1") == "1"
     assert by_name["ZKPOA_OVERLAP"].dflt == 1 and by_name["ZKPOA_UPLOAD_AFFINITY"].words == ["gpu", "off"]
     assert by_name["ZKPOA_DETACH_EXIT"].words == ["auto", "0", "always"]
     # the values that documents, tests, tools and bench.py use keep their meaning

@@ -63,6 +63,7 @@ struct Arena {
     if (base) ZK_HIP(hipFree(base));
     base = nullptr;
     cap = off = 0;   // (a failed allocation below must not leave a capacity without memory behind it)
+    guards.clear();
     const hipError_t e = hipMalloc(&base, bytes);
     if (e == hipErrorOutOfMemory) {
       base = nullptr;
@@ -72,12 +73,34 @@ struct Arena {
     ZK_HIP(e);
     cap = bytes;
   }
-  void reset() { off = 0; }
+  // Guard mode (ZKPOA_WS_GUARD, a test hook): every region is followed by a guard that starts at the first byte after the
+  // region's exact size and runs to its 256-byte rounded end plus 256 bytes (the arena's alignment, so every later
+  // offset stays aligned). The owner stamps the guards after carving and looks at them when its kernels have finished
+  // (msm.hip.h lane_guard_stamp / lane_guard_check): a write past a region's end shows even when it is one word long and
+  // would otherwise land in padding. Off (the default), take() hands out the offsets it always has.
+  struct Guard {
+    size_t off, len;     // [off, off + len) of the arena
+    const char* name;    // the region it follows: a string literal, and its index (-1: none) for an array of regions
+    int idx;
+    std::string region() const { return idx < 0 ? std::string(name) : std::string(name) + "[" + std::to_string(idx) + "]"; }
+  };
+  static constexpr size_t kAlign = 256;
+  static constexpr unsigned char kGuardByte = 0xA5;
+  bool guard = false;
+  std::vector<Guard> guards;
+  // bytes a region of `exact` bytes takes from the arena (ArenaCount, msm.hip.h, sizes with the same function)
+  static size_t span(size_t exact, bool guarded) { return ((exact + kAlign - 1) & ~(kAlign - 1)) + (guarded ? kAlign : 0); }
+  void reset(bool guarded = false) {
+    off = 0;
+    guard = guarded;
+    guards.clear();
+  }
   template <class T>
-  T* take(size_t count) {
-    size_t bytes = (count * sizeof(T) + 255) & ~size_t(255);
+  T* take(size_t count, const char* name = "", int idx = -1) {
+    const size_t exact = count * sizeof(T), bytes = span(exact, guard);
     if (off + bytes > cap) throw HipError("arena overflow (reserve() too small)");
     T* p = reinterpret_cast<T*>(base + off);
+    if (guard) guards.push_back(Guard{off + exact, bytes - exact, name, idx});
     off += bytes;
     return p;
   }
@@ -85,6 +108,7 @@ struct Arena {
     if (base) (void)hipFree(base);
     base = nullptr;
     cap = off = 0;
+    guards.clear();
   }
 };
 

@@ -1090,13 +1090,18 @@ inline void lane_scan(Lane& lane, const ScanPair& a, uint32_t* block_sums) {
 // ---- workspace layouts: a phase's share of the lane arena is described ONCE -------------------------------------
 // carve() names every region in arena order with its element count, against a taker: Arena (device_ctx.hpp) hands the
 // memory out, ArenaCount only adds up what it would hand out -- what reserve() and the prover's HBM budget are sized with.
+// Every region has a name (the layout's field, and the index within an array of regions): the arena's guard mode
+// (device_ctx.hpp, ZKPOA_WS_GUARD) reports a write past a region's end by it. `guard` is an argument of everything that
+// sizes, never read from the environment here: the caller that sizes and the caller that carves pass the same value.
 struct ArenaCount {
   size_t off = 0;
-  template <class T> T* take(size_t count) { return off += (count * sizeof(T) + 255) & ~size_t(255), nullptr; }   // (Arena::take)
+  bool guard = false;
+  template <class T> T* take(size_t count, const char* = "", int = -1) { return off += Arena::span(count * sizeof(T), guard), nullptr; }   // (Arena::take)
 };
 template <class Layout>
-inline size_t msm_layout_bytes(const MsmPlan& p) {
+inline size_t msm_layout_bytes(const MsmPlan& p, bool guard) {
   ArenaCount count;
+  count.guard = guard;
   Layout().carve(count, p);
   return count.off;
 }
@@ -1105,8 +1110,48 @@ inline Layout msm_carve(Arena& ws, const MsmPlan& p) {
   Layout m;
   const size_t start = ws.off;
   m.carve(ws, p);   // (one comparison per MSM keeps the two takers honest)
-  if (ws.off - start != msm_layout_bytes<Layout>(p)) throw HipError("msm: internal: workspace layout and its size disagree");
+  if (ws.off - start != msm_layout_bytes<Layout>(p, ws.guard)) throw HipError("msm: internal: workspace layout and its size disagree");
   return m;
+}
+
+// Guard mode of the lane arena. A phase stamps the guards it carved (those from index `first` on) with the guard byte,
+// on the lane's stream; when its kernels have finished it looks at EVERY guard of the arena, from offset 0 to ws.off.
+// A changed byte is a HipError that names the phase, the region the guard follows and the first changed byte's offset
+// within the guard. Guards are never read by a kernel: this shows writes past a region's end, not reads.
+// ZKPOA_TEST_WS_CLOBBER = k (tests): the host first overwrites one byte of the arena's k-th guard, so that the check is
+// itself checked without a kernel that misbehaves.
+inline void lane_guard_stamp(Lane& lane, size_t first) {
+  for (size_t i = first; i < lane.ws.guards.size(); i++) {
+    const Arena::Guard& g = lane.ws.guards[i];
+    ZK_HIP(hipMemsetAsync(lane.ws.base + g.off, Arena::kGuardByte, g.len, lane.stream));
+  }
+}
+inline void lane_guard_check(Lane& lane, const char* phase) {
+  const Arena& ws = lane.ws;
+  if (!ws.guard) return;
+  const long k = opt_long(O_TEST_WS_CLOBBER);
+  if (k >= 1 && (size_t)k <= ws.guards.size())
+    ZK_HIP(hipMemsetAsync(ws.base + ws.guards[k - 1].off, (unsigned char)~Arena::kGuardByte, 1, lane.stream));
+  size_t total = 0;
+  for (const Arena::Guard& g : ws.guards) total += g.len;
+  std::vector<unsigned char> h(total);
+  size_t at = 0;
+  for (const Arena::Guard& g : ws.guards) {
+    if (g.off + g.len > ws.off) throw HipError("msm: internal: a workspace guard lies outside the carved arena");
+    ZK_HIP(hipMemcpyAsync(h.data() + at, ws.base + g.off, g.len, hipMemcpyDeviceToHost, lane.stream));
+    at += g.len;
+  }
+  ZK_HIP(hipStreamSynchronize(lane.stream));
+  at = 0;
+  for (size_t i = 0; i < ws.guards.size(); at += ws.guards[i].len, i++) {
+    const Arena::Guard& g = ws.guards[i];
+    for (size_t b = 0; b < g.len; b++)
+      if (h[at + b] != Arena::kGuardByte)
+        throw HipError(std::string("msm: workspace guard: the ") + phase + " phase left a write past the end of region '" +
+                       g.region() + "' (guard " + std::to_string(i + 1) + " of " + std::to_string(ws.guards.size()) +
+                       "): first changed byte at offset " + std::to_string(b) + " of the guard's " + std::to_string(g.len) +
+                       " bytes");
+  }
 }
 inline size_t msm_piece_cap(const MsmPlan& p) { return (size_t)p.n * p.W / p.K0 + p.TB + 1; }   // level-0 pieces at most
 
@@ -1135,27 +1180,27 @@ struct MsmSortLayout {
   void carve(Taker& ws, const MsmPlan& p) {
     const SortPlan sp = make_sort_plan(p.ne, p.Wb, p.c);
     const size_t T = (size_t)p.n * p.W, head = ws.off;
-    counts = ws.template take<uint32_t>(p.TB);
-    for (uint32_t l = 0; l + 1 < sp.npass; l++) seg_cnt[l] = ws.template take<uint32_t>(sp.segs[l + 1] + 1);
-    misc = ws.template take<uint32_t>(16);
-    len_hist = ws.template take<uint32_t>(2 * (kMaxPieceLen + 1));
+    counts = ws.template take<uint32_t>(p.TB, "counts");
+    for (uint32_t l = 0; l + 1 < sp.npass; l++) seg_cnt[l] = ws.template take<uint32_t>(sp.segs[l + 1] + 1, "seg_cnt", (int)l);
+    misc = ws.template take<uint32_t>(16, "misc");
+    len_hist = ws.template take<uint32_t>(2 * (kMaxPieceLen + 1), "len_hist");
     zero_bytes = ws.off - head;
-    off0 = ws.template take<uint32_t>(p.TB + 1);
-    po_a = ws.template take<uint32_t>(p.TB + 1);
-    elist = ws.template take<uint2>(T);
-    pre = ws.template take<uint32_t>(8);
-    for (uint32_t k = 0; k < 2; k++) ebuf[k] = sp.npass > k + 1 ? ws.template take<uint2>(T) : nullptr;
+    off0 = ws.template take<uint32_t>(p.TB + 1, "off0");
+    po_a = ws.template take<uint32_t>(p.TB + 1, "po_a");
+    elist = ws.template take<uint2>(T, "elist");
+    pre = ws.template take<uint32_t>(8, "pre");
+    for (uint32_t k = 0; k < 2; k++) ebuf[k] = sp.npass > k + 1 ? ws.template take<uint2>(T, "ebuf", (int)k) : nullptr;
     for (uint32_t l = 0; l < sp.npass; l++) {
       if (l + 1 < sp.npass) {
-        seg_off[l] = ws.template take<uint32_t>(sp.segs[l + 1] + 1);
-        seg_tpo[l] = ws.template take<uint32_t>(sp.segs[l + 1] + 1);
+        seg_off[l] = ws.template take<uint32_t>(sp.segs[l + 1] + 1, "seg_off", (int)l);
+        seg_tpo[l] = ws.template take<uint32_t>(sp.segs[l + 1] + 1, "seg_tpo", (int)l);
       }
-      base[l] = ws.template take<uint32_t>((size_t)sp.tasks_max[l] << sp.bits[l]);
+      base[l] = ws.template take<uint32_t>((size_t)sp.tasks_max[l] << sp.bits[l], "base", (int)l);
     }
-    sorted = ws.template take<uint32_t>(T);
-    block_sums = ws.template take<uint32_t>(p.TB / kScanTile + 2);
-    pbkt = ws.template take<uint32_t>(msm_piece_cap(p));
-    order = ws.template take<uint32_t>(msm_piece_cap(p));
+    sorted = ws.template take<uint32_t>(T, "sorted");
+    block_sums = ws.template take<uint32_t>(p.TB / kScanTile + 2, "block_sums");
+    pbkt = ws.template take<uint32_t>(msm_piece_cap(p), "pbkt");
+    order = ws.template take<uint32_t>(msm_piece_cap(p), "order");
   }
 };
 
@@ -1172,25 +1217,26 @@ struct MsmAccumLayout {
   void carve(Taker& ws, const MsmPlan& p) {
     constexpr size_t kXyzz = MsmSizes<F>::kXyzz;
     const size_t E = (size_t)1 << p.logS, sums = (size_t)2 * p.Wb * msm_reduce_bits(p.logS);
-    po_b = ws.template take<uint32_t>(p.TB + 1);
-    po_c = ws.template take<uint32_t>(p.TB + 1);
-    block_sums = ws.template take<uint32_t>(p.TB / kScanTile + 2);
-    misc = ws.template take<uint32_t>(16);
-    buckets = ws.template take<char>((size_t)p.TB * kXyzz);
+    po_b = ws.template take<uint32_t>(p.TB + 1, "po_b");
+    po_c = ws.template take<uint32_t>(p.TB + 1, "po_c");
+    block_sums = ws.template take<uint32_t>(p.TB / kScanTile + 2, "accum block_sums");
+    misc = ws.template take<uint32_t>(16, "accum misc");
+    buckets = ws.template take<char>((size_t)p.TB * kXyzz, "buckets");
     p1_cap = msm_piece_cap(p);
     p2_cap = p1_cap / 2 + 1;
-    P1 = ws.template take<char>(p1_cap * kXyzz);
-    P2 = ws.template take<char>(p2_cap * kXyzz);
-    X = ws.template take<char>(2 * p.Wb * E * kXyzz);
-    Y1 = ws.template take<char>((E + 255) / 256 * sums * kXyzz);
-    Y2 = ws.template take<char>((E + 255) / 256 * sums * kXyzz);
+    P1 = ws.template take<char>(p1_cap * kXyzz, "P1");
+    P2 = ws.template take<char>(p2_cap * kXyzz, "P2");
+    X = ws.template take<char>(2 * p.Wb * E * kXyzz, "X");
+    Y1 = ws.template take<char>((E + 255) / 256 * sums * kXyzz, "Y1");
+    Y2 = ws.template take<char>((E + 255) / 256 * sums * kXyzz, "Y2");
   }
 };
 
 // Bytes of lane arena a phase takes for plan p: the counting run of its layout, plus slack.
-inline size_t msm_sort_workspace_bytes(const MsmPlan& p) { return msm_layout_bytes<MsmSortLayout>(p) + (1 << 12) - 256; }
+// (guard: the arena's guard mode, which every region's guard makes larger)
+inline size_t msm_sort_workspace_bytes(const MsmPlan& p, bool guard) { return msm_layout_bytes<MsmSortLayout>(p, guard) + (1 << 12) - 256; }
 template <class F>
-inline size_t msm_accum_workspace_bytes(const MsmPlan& p) { return msm_layout_bytes<MsmAccumLayout<F>>(p) + (1 << 12); }
+inline size_t msm_accum_workspace_bytes(const MsmPlan& p, bool guard) { return msm_layout_bytes<MsmAccumLayout<F>>(p, guard) + (1 << 12); }
 
 // Partial-sum levels (after the MSM's level 0, and after the key set-up's multiplications): while some bucket still holds
 // more than one partial sum, one thread adds up to K of them. po_in: the TB + 1 offsets of the items entering the first
@@ -1241,11 +1287,12 @@ inline void lane_reserve(Lane& lane, size_t need) {
   }
 }
 
-// Phase A on lane.stream for the req.n scalars at d_scalars. `extra(plan)` bytes are reserved on top (for a following
-// phase B on the same lane). The arena is reset here; the result stays valid until the lane's next msm_sort_phase. With
-// sync_at_end the stream is synchronised on return, so other lanes may read the result.
+// Phase A on lane.stream for the req.n scalars at d_scalars. `extra(plan, guard)` bytes are reserved on top (for a
+// following phase B on the same lane, sized in the same guard mode). The arena is reset here; the result stays valid
+// until the lane's next msm_sort_phase. With sync_at_end the stream is synchronised on return, so other lanes may read
+// the result.
 inline MsmSorted msm_sort_phase(Lane& lane, const void* d_scalars, const MsmRequest& req,
-                                size_t (*extra)(const MsmPlan&), bool sync_at_end = false) {
+                                size_t (*extra)(const MsmPlan&, bool), bool sync_at_end = false) {
   MsmSorted sr;
   sr.p = msm_make_plan(req);
   const MsmPlan& p = sr.p;
@@ -1254,11 +1301,13 @@ inline MsmSorted msm_sort_phase(Lane& lane, const void* d_scalars, const MsmRequ
   if ((uint64_t)p.n * p.W + p.TB >= 0xffff0000ull) throw HipError("msm: n * windows exceeds the 32-bit entry index");
   if (p.merged && (uint64_t)p.n * p.W >= 0x80000000ull) throw HipError("msm: n * windows exceeds the fixed-base entry index");
   hipStream_t st = lane.stream;
-  lane_reserve(lane, msm_sort_workspace_bytes(p) + (extra ? extra(p) : 0));
-  lane.ws.reset();
+  const bool guard = opt_flag(O_WS_GUARD);   // (tests) holds for the whole MSM: phase B in this arena follows ws.guard
+  lane_reserve(lane, msm_sort_workspace_bytes(p, guard) + (extra ? extra(p, guard) : 0));
+  lane.ws.reset(guard);
   const SortPlan sp = make_sort_plan(p.ne, p.Wb, p.c);
   const MsmSortLayout& m = sr.m = msm_carve<MsmSortLayout>(lane.ws, p);
   ZK_HIP(hipMemsetAsync(m.counts, 0, m.zero_bytes, st));
+  lane_guard_stamp(lane, 0);   // after the memset: it runs over the guards inside the head block
   // the plan's entry form; ZKPOA_NO_SPARSE=1 keeps the dense form (measurement)
   const bool sparse = p.sparse && !opt_flag(O_NO_SPARSE);
   uint32_t* digits = sparse ? nullptr : m.digits();   // one region, one view per form
@@ -1317,6 +1366,7 @@ inline MsmSorted msm_sort_phase(Lane& lane, const void* d_scalars, const MsmRequ
                        (const uint32_t*)m.counts, (const uint32_t*)m.po_a, p.TB, p.K0, (const uint32_t*)m.len_hist,
                        m.len_cursor(), m.pbkt, m.order);
   }
+  lane_guard_check(lane, "sort");   // (guard mode: synchronises)
   if (sync_at_end) ZK_HIP(hipStreamSynchronize(st));  // other lanes are about to read the result
   return sr;
 }
@@ -1333,10 +1383,13 @@ inline void msm_accum_phase(Lane& lane, const MsmSorted& sr, const void* d_bases
   const MsmPlan& p = sr.p;
   hipStream_t st = lane.stream;
   if (!own_arena) {
-    lane_reserve(lane, msm_accum_workspace_bytes<F>(p));
-    lane.ws.reset();
+    const bool guard = opt_flag(O_WS_GUARD);
+    lane_reserve(lane, msm_accum_workspace_bytes<F>(p, guard));
+    lane.ws.reset(guard);
   }
+  const size_t first_guard = lane.ws.guards.size();
   const MsmAccumLayout<F> m = msm_carve<MsmAccumLayout<F>>(lane.ws, p);
+  lane_guard_stamp(lane, first_guard);
   const uint32_t E = 1u << p.logS, S1 = (E + 255) / 256;   // entries per (window, row|column) group; logS >= logRows
   const uint32_t nbits = msm_reduce_bits(p.logS), sums = 2u * p.Wb * nbits;   // per-bit totals of every group
 
@@ -1381,6 +1434,8 @@ inline void msm_accum_phase(Lane& lane, const MsmSorted& sr, const void* d_bases
   }
   msm_read_back(lane, cur, (size_t)sums * MsmSizes<F>::kXyzz);
   ZK_HIP(hipGetLastError());
+  // every guard of this arena: the sort's too when it was carved here (with another lane's sort, that lane checked them)
+  lane_guard_check(lane, "accumulation");
   memcpy(window_sums_host, lane.pinned, (size_t)sums * MsmSizes<F>::kXyzz);
   if (accum_ms) ZK_HIP(hipEventElapsedTime(accum_ms, lane.ev0, lane.ev1));
 }

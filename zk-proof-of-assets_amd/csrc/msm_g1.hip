@@ -29,11 +29,11 @@ void msm_density(hipStream_t st, const void* d_scalars, uint64_t n, double out[3
   ZK_HIP(hipStreamSynchronize(st));
   for (int c = kDensityLo; c <= kDensityHi; c++) out[c] = (double)h[c - kDensityLo] / (double)n;
 }
-size_t msm_workspace(const MsmRequest& req, unsigned parts) {   // (layouts only: no G2 kernel is instantiated here)
+size_t msm_workspace(const MsmRequest& req, unsigned parts, bool guard) {   // (layouts only: no G2 kernel is instantiated here)
   if (req.n == 0) return 0;
   const MsmPlan p = msm_make_plan(req);
-  return (parts & kMsmSort ? msm_sort_workspace_bytes(p) : 0) + (parts & kMsmAccumG1 ? msm_accum_workspace_bytes<Fq>(p) : 0) +
-         (parts & kMsmAccumG2 ? msm_accum_workspace_bytes<Fq2>(p) : 0);
+  return (parts & kMsmSort ? msm_sort_workspace_bytes(p, guard) : 0) + (parts & kMsmAccumG1 ? msm_accum_workspace_bytes<Fq>(p, guard) : 0) +
+         (parts & kMsmAccumG2 ? msm_accum_workspace_bytes<Fq2>(p, guard) : 0);
 }
 void msm_table_info(const MsmTable* t, uint64_t out[4]) {
   out[0] = t->n;
@@ -52,11 +52,12 @@ void msm_accum_g1(zkpoa_context* ctx, int lane_id, const MsmSorted* sr, bool own
 }
 }  // namespace zkpoa
 
-// the thirteen words the test hooks below report of a plan (and of the request it was made from)
+// the thirteen words the test hooks below report of a plan (and of the request it was made from); the sizes are those
+// of the unguarded arena, whatever ZKPOA_WS_GUARD says
 static void plan_words(const zkpoa::MsmPlan& p, uint64_t w[13]) {
   using namespace zkpoa;
   const uint64_t v[13] = {p.c, p.W, p.Wb, p.ne, p.TB, p.K0, p.K, p.logS, p.logRows, p.sparse ? 1u : 0u,
-                          msm_workspace(p.req, kMsmSort), msm_workspace(p.req, kMsmAccumG1), msm_workspace(p.req, kMsmAccumG2)};
+                          msm_workspace(p.req, kMsmSort, false), msm_workspace(p.req, kMsmAccumG1, false), msm_workspace(p.req, kMsmAccumG2, false)};
   for (int i = 0; i < 13; i++) w[i] = v[i];
 }
 

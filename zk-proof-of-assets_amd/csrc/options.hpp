@@ -75,6 +75,8 @@ enum OptUse { kKnob, kHook };          // a hook serves tests, experiments and m
   X(SERVER_TEST_CRASH, kOptFlag, 0, 1, nullptr, 0, kLenient, kLatched, kHook, nullptr, "tests: the server dies with a request in hand")  \
   X(TEST_STALE_EXCHANGE, kOptInt, 0, 1000000000, nullptr, 0, kLenient, kLatched, kHook, nullptr, "tests: rank 0 withholds its first exchange in the n-th multi-rank proof") \
   X(TEST_FAIL_RANK, kOptText, 0, 0, nullptr, 0, kLenient, kLatched, kHook, nullptr, "tests: g[:phase], rank g fails at the start of that phase") \
+  X(WS_GUARD, kOptFlag, 0, 1, nullptr, 0, kLenient, kEveryUse, kHook, nullptr, "tests: guard bytes behind every region of an MSM lane's workspace, checked when each phase ends") \
+  X(TEST_WS_CLOBBER, kOptInt, 0, 1000000000, nullptr, 0, kLenient, kEveryUse, kHook, nullptr, "tests: under WS_GUARD the host overwrites one byte of the arena's k-th guard before a check; 0 = off") \
   X(DELTA, kOptText, 0, 0, nullptr, 0, kStrict, kEveryUse, kHook, nullptr, "zkpoa-setup zkey contribute: the secret delta, for reproducible keys") \
   X(PHASE1_S, kOptText, 0, 0, nullptr, 0, kStrict, kEveryUse, kHook, nullptr, "powersoftau contribute: s_tau,s_alpha,s_beta of the contribution record") \
   X(PHASE2_S, kOptText, 0, 0, nullptr, 0, kStrict, kEveryUse, kHook, nullptr, "zkey contribute: the s of the contribution record's g1_s")

@@ -750,8 +750,9 @@ static LaneNeeds lane_needs(const zkpoa_context* ctx, const zkpoa_zkey* zk, cons
   LaneNeeds w;
   const StageView v[5] = {stage_view(zk, 0), stage_view(zk, 1), stage_view(zk, 2), stage_view(zk, 3), stage_view(zk, 4)};
   const double* dens = zk->have_density ? zk->witness_density : nullptr;
+  const bool guard = opt_flag(O_WS_GUARD);   // (tests) the lanes will carve guarded arenas: budget for them
   auto whole_g1 = [&](int l, const double* density) {   // a lane's own G1 MSM: sort and accumulation in one arena
-    return msm_workspace(stage_request(ctx, v[l], lim[l], density, false, with_tables), kMsmSort | kMsmAccumG1);
+    return msm_workspace(stage_request(ctx, v[l], lim[l], density, false, with_tables), kMsmSort | kMsmAccumG1, guard);
   };
   w.bytes[kStageH] = whole_g1(kStageH, nullptr);   // uniform scalars
   w.bytes[kStageA] = whole_g1(kStageA, dens);      // witness scalars
@@ -760,12 +761,12 @@ static LaneNeeds lane_needs(const zkpoa_context* ctx, const zkpoa_zkey* zk, cons
   const uint64_t nB = v[kStageB1].n, limB = std::min(lim[kStageB1], lim[kStageB2]);
   if (nB <= limB) {
     const MsmRequest shared = stage_request(ctx, v[kStageB1], limB, dens, true, with_tables);
-    w.bytes[kStageB1] = msm_workspace(shared, kMsmSort | kMsmAccumG1);
-    w.bytes[kStageB2] = msm_workspace(shared, kMsmAccumG2);
+    w.bytes[kStageB1] = msm_workspace(shared, kMsmSort | kMsmAccumG1, guard);
+    w.bytes[kStageB2] = msm_workspace(shared, kMsmAccumG2, guard);
   } else {   // two chunked MSMs, no table
-    w.bytes[kStageB1] = msm_workspace(stage_request(ctx, v[kStageB1], lim[kStageB1], dens, false, false), kMsmSort | kMsmAccumG1);
+    w.bytes[kStageB1] = msm_workspace(stage_request(ctx, v[kStageB1], lim[kStageB1], dens, false, false), kMsmSort | kMsmAccumG1, guard);
     // KNOWN MISMATCH (DESIGN.md "MSM plans", follow-up): B2's own MSM runs with no density (prove_partials, tB2)
-    w.bytes[kStageB2] = msm_workspace(stage_request(ctx, v[kStageB2], lim[kStageB2], dens, true, false), kMsmSort | kMsmAccumG2);
+    w.bytes[kStageB2] = msm_workspace(stage_request(ctx, v[kStageB2], lim[kStageB2], dens, true, false), kMsmSort | kMsmAccumG2, guard);
   }
   return w;
 }

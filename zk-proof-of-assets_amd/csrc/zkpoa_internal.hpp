@@ -197,7 +197,8 @@ void msm_table_info(const MsmTable* t, uint64_t out[4]);   // n, c, W, bytes
 // bytes of lane workspace the named parts of the request's plan reserve (msm.hip.h msm_sort/accum_workspace_bytes):
 // a whole MSM is its sort and one accumulation in the same arena; an accumulation over another lane's sort is that alone.
 enum MsmPart : unsigned { kMsmSort = 1, kMsmAccumG1 = 2, kMsmAccumG2 = 4 };
-size_t msm_workspace(const MsmRequest& req, unsigned parts);   // 0 for req.n == 0
+// guard: sized for the arena's guard mode (ZKPOA_WS_GUARD; the caller reads the option, this function does not).
+size_t msm_workspace(const MsmRequest& req, unsigned parts, bool guard);   // 0 for req.n == 0
 // non-zero digits per scalar for every window width (index c, 4..25) of n scalars on the device; synchronises st
 // (d_scratch: 256 B of device memory of the caller's -- no allocation here: a hipFree would wait for every lane)
 void msm_density(hipStream_t st, const void* d_scalars, uint64_t n, double out[32], void* d_scratch);
