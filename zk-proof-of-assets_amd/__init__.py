@@ -20,6 +20,7 @@ from ._abi import (EXPORTS, LIB_PATH, PROVER_ERROR, PROVER_ERROR_RUNTIME, PROVER
 _HERE = os.path.dirname(os.path.abspath(__file__))
 PROVER_BIN = os.path.join(_HERE, "prover")
 MERKLE_BIN = os.path.join(_HERE, "merkle-tree")
+AUDIT_BIN = os.path.join(_HERE, "zkpoa-audit")
 SIGS_BIN = os.path.join(_HERE, "ecdsa-sigs-parser")
 SETUP_BIN = os.path.join(_HERE, "zkpoa-setup")
 VERIFY_BIN = os.path.join(_HERE, "zkpoa-verify")
@@ -38,6 +39,15 @@ PTAU_CHECKS = {"POINTS": 0x001, "TAU_G1": 0x002, "TAU_G2": 0x004, "ALPHA": 0x008
 def shard_flags(split=False, block_log=0):
     """include/zkpoa_prover.h: ZKPOA_SHARD_SPLIT_CHAIN | ZKPOA_SHARD_BLOCK_CYCLIC(block_log)."""
     return (1 if split else 0) | ((int(block_log) & 0xff) << 8)
+
+
+ASSETS_SET, ASSETS_ROOT, ASSETS_COMMITMENT, ASSETS_PROOF = 1, 2, 4, 8   # Context.assets_verify's failed checks
+
+
+class AssetsReport(ctypes.Structure):
+    """zkpoa_assets_report of include/zkpoa_audit.h"""
+    _fields_ = [("root_le", ctypes.c_uint8 * 32), ("commitment", ctypes.c_uint8 * 32), ("rows", ctypes.c_uint64),
+                ("duplicate_rows", ctypes.c_uint64), ("first_dup", ctypes.c_uint64 * 2), ("ascending", ctypes.c_int)]
 
 
 class Context:
@@ -251,6 +261,37 @@ class Context:
     def merkle_build(self, addresses, balances, device=False, n=None):
         """Tree over (address, balance) pairs: host buffers (n x 32 B LE each) or, with device=True, device pointers."""
         return MerkleTree(self, addresses, balances, device, n)
+
+    def anon_set_index(self, d_addresses, n, d_perm):
+        """d_perm[0..n) (u32, device) <- the row numbers of the n device-resident 32-byte keys ordered by (key, row): a
+        stable sort, exact for every input."""
+        self._check(lib().zkpoa_anon_set_index_device(self._h, d_addresses, n, d_perm), "zkpoa_anon_set_index_device")
+
+    def anon_set_audit(self, addresses, n=None):
+        """The duplicate check of a published set's addresses (host buffer, n x 32 B LE) -> (rows that repeat an earlier
+        row's address, the pair (i, j) with the smallest such j or None, is the file strictly ascending)."""
+        n = len(addresses) // 32 if n is None else n
+        p, keep = _buf(addresses)
+        out = (ctypes.c_uint64 * 4)()
+        self._check(lib().zkpoa_anon_set_audit(self._h, p, n, out), "zkpoa_anon_set_audit")
+        return int(out[0]), ((int(out[1]), int(out[2])) if out[0] else None), bool(out[3])
+
+    def assets_verify(self, addresses, balances, vkey_json, public_json, proof_json, expected_commitment=None, n=None):
+        """The verifier's whole check -> (failed checks: a mask of ASSETS_SET / ROOT / COMMITMENT / PROOF, report dict);
+        every check runs whatever the others found. Raises on malformed JSON or a set value that is no field element."""
+        n = len(addresses) // 32 if n is None else n
+        pa, ka = _buf(addresses)
+        pb, kb = _buf(balances)
+        failed = ctypes.c_uint32(0)
+        rep = AssetsReport()
+        self._check(lib().zkpoa_assets_verify(self._h, pa, pb, n, vkey_json.encode(), public_json.encode(), proof_json.encode(),
+                                              None if expected_commitment is None else _buf(bytes(expected_commitment))[0],
+                                              ctypes.byref(failed), ctypes.addressof(rep)), "zkpoa_assets_verify")
+        return int(failed.value), {
+            "root": int.from_bytes(bytes(rep.root_le), "little"), "commitment": bytes(rep.commitment), "rows": int(rep.rows),
+            "duplicate_rows": int(rep.duplicate_rows),
+            "first_dup": (int(rep.first_dup[0]), int(rep.first_dup[1])) if rep.duplicate_rows else None,
+            "ascending": bool(rep.ascending)}
 
     def msm_table(self, group, d_bases, n, window_bits=0):
         """Fixed-base table over n device-resident bases (group 1 = G1, 2 = G2) -> MsmTable."""
@@ -861,6 +902,18 @@ def pedersen_check(secret, blinding, signals):
     if lib().zkpoa_pedersen_check(_le32([secret]), _le32([blinding]), _le32(signals[:12]), ctypes.byref(equal)) != PROVER_OK:
         raise ZkpoaError("zkpoa_pedersen_check failed")
     return bool(equal.value)
+
+
+def pedersen_decode(signals):
+    """The point the layer-three circuit's first 12 public signals spell -> its 32-byte RFC 8032 encoding, or None when
+    a signal is 2^85 or more, Z = 0 or the coordinates are not on ed25519. Torsion is not checked. Host only."""
+    if len(signals) < 12:
+        raise ZkpoaError("pedersen_decode: the commitment is the first 12 public signals, %d given" % len(signals))
+    out = ctypes.create_string_buffer(32)
+    valid = ctypes.c_int(0)
+    if lib().zkpoa_pedersen_decode(_le32(signals[:12]), out, ctypes.byref(valid)) != PROVER_OK:
+        raise ZkpoaError("zkpoa_pedersen_decode failed")
+    return out.raw if valid.value else None
 
 
 def groth16_verify_points(vkey_points, proof_points, public_le):

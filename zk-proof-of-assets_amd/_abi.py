@@ -194,6 +194,15 @@ HD_SIGNATURES = {
     "zkpoa_bip32_derive_path":         "i: p p p s p p",
 }
 
+# every symbol include/zkpoa_audit.h declares (zkpoa_prover.h includes that header too): the verifier's side; the
+# third is host only and without a context, the others run on the GPU
+AUDIT_SIGNATURES = {
+    "zkpoa_anon_set_index_device":     "i: p p u64 p",
+    "zkpoa_anon_set_audit":            "i: p p u64 u64*",
+    "zkpoa_pedersen_decode":           "i: s p i*",
+    "zkpoa_assets_verify":             "i: p p p u64 s s s p u32* p",
+}
+
 # the one symbol include/zkpoa_secp_prim.h declares (zkpoa_prover.h includes that header beside its other test hooks)
 SECP_PRIM_SIGNATURES = {
     "zkpoa_secp_prim":                 "i: p i p p u64",
@@ -231,7 +240,8 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        for table in (SIGNATURES, LAYER_INPUT_SIGNATURES, SIGN_SIGNATURES, HD_SIGNATURES, SECP_PRIM_SIGNATURES, HOOK_SIGNATURES):
+        for table in (SIGNATURES, LAYER_INPUT_SIGNATURES, SIGN_SIGNATURES, HD_SIGNATURES, AUDIT_SIGNATURES, SECP_PRIM_SIGNATURES,
+                      HOOK_SIGNATURES):
             for name, spec in table.items():
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = signature(spec)

@@ -1,5 +1,6 @@
 // Host-only C entry points of the layer-two / layer-three input arithmetic (include/zkpoa_layer_inputs.h): the Poseidon
-// of poseidon_host.hpp and the ed25519 commitment of pedersen_host.hpp. No context, no GPU.
+// of poseidon_host.hpp and the ed25519 commitment of pedersen_host.hpp; and the verifier's reading of that commitment
+// (zkpoa_pedersen_decode, include/zkpoa_audit.h). No context, no GPU.
 #include "../../include/zkpoa_prover.h"
 #include "pedersen_host.hpp"
 #include "poseidon_host.hpp"
@@ -68,5 +69,14 @@ extern "C" int zkpoa_pedersen_check(const uint8_t secret[32], const uint8_t blin
   U256 sig[12];
   for (int i = 0; i < 12; i++) sig[i] = U256::from_le(signals + 32 * i);
   *equal = ed_equal(pedersen_commit(U256::from_le(secret), U256::from_le(blinding)), pedersen_dechunk(sig)) ? 1 : 0;
+  LI_END
+}
+
+extern "C" int zkpoa_pedersen_decode(const uint8_t signals[12 * 32], uint8_t compressed32[32], int* valid) {
+  if (!signals || !compressed32 || !valid) return PROVER_ERROR;
+  LI_TRY
+  U256 sig[12];
+  for (int i = 0; i < 12; i++) sig[i] = U256::from_le(signals + 32 * i);
+  *valid = pedersen_decode(sig, compressed32) ? 1 : 0;
   LI_END
 }

@@ -89,6 +89,16 @@ struct Fe25519 {
     const U256 x = canon(a);
     return (x.v[0] | x.v[1] | x.v[2] | x.v[3]) == 0;
   }
+  static U256 inv(const U256& a) {   // a^(p - 2), bit by bit from the top; 0 for a = 0
+    static const uint64_t E[4] = {0xffffffffffffffebull, 0xffffffffffffffffull, 0xffffffffffffffffull, 0x7fffffffffffffffull};
+    U256 r;
+    r.v[0] = 1;
+    for (int b = 254; b >= 0; b--) {
+      r = mul(r, r);
+      if ((E[b >> 6] >> (b & 63)) & 1) r = mul(r, a);
+    }
+    return r;
+  }
 };
 
 struct EdPoint {
@@ -116,9 +126,14 @@ inline const EdPoint& pedersen_generator_h() {
   return h;
 }
 
+inline const U256& ed_d() {   // the curve's d = -121665 / 121666
+  static const U256 d = u256_dec("37095705934669439343138083508754565189542113879843219016388785533085940283555");
+  return d;
+}
+
 inline EdPoint ed_add(const EdPoint& p, const EdPoint& q) {   // pointAdd
   typedef Fe25519 F;
-  static const U256 d = u256_dec("37095705934669439343138083508754565189542113879843219016388785533085940283555");
+  const U256& d = ed_d();
   const U256 A = F::mul(F::sub(p.y, p.x), F::sub(q.y, q.x));
   const U256 B = F::mul(F::add(p.y, p.x), F::add(q.y, q.x));
   const U256 tt = F::mul(p.t, q.t), zz = F::mul(p.z, q.z);
@@ -162,6 +177,28 @@ inline EdPoint pedersen_dechunk(const U256 signals[12]) {
 inline bool ed_equal(const EdPoint& p, const EdPoint& q) {   // pointEqual: x1 z2 = x2 z1 and y1 z2 = y2 z1
   typedef Fe25519 F;
   return F::is_zero(F::sub(F::mul(p.x, q.z), F::mul(q.x, p.z))) && F::is_zero(F::sub(F::mul(p.y, q.z), F::mul(q.y, p.z)));
+}
+
+// The point the layer-three circuit's first 12 public signals spell, as a verifier reads it: false when a signal does not
+// fit 85 bits, Z = 0, or (X, Y, Z, T) does not satisfy the extended-coordinate equations of ed25519,
+// -X^2 + Y^2 = Z^2 + d T^2 and X Y = Z T. compressed <- the RFC 8032 encoding of (X / Z, Y / Z): y little-endian, bit
+// 255 = the low bit of x. Whether the point lies in the prime-order subgroup is NOT checked.
+inline bool pedersen_decode(const U256 signals[12], uint8_t compressed[32]) {
+  typedef Fe25519 F;
+  memset(compressed, 0, 32);
+  for (int i = 0; i < 12; i++)
+    if (signals[i].v[3] | signals[i].v[2] | (signals[i].v[1] >> 21)) return false;
+  const EdPoint p = pedersen_dechunk(signals);
+  if (F::is_zero(p.z)) return false;
+  const U256 xx = F::mul(p.x, p.x), yy = F::mul(p.y, p.y), zz = F::mul(p.z, p.z), tt = F::mul(p.t, p.t);
+  if (!F::is_zero(F::sub(F::sub(yy, xx), F::add(zz, F::mul(ed_d(), tt))))) return false;
+  if (!F::is_zero(F::sub(F::mul(p.x, p.y), F::mul(p.z, p.t)))) return false;
+  const U256 zi = F::inv(p.z);
+  const U256 x = F::canon(F::mul(p.x, zi));
+  U256 y = F::canon(F::mul(p.y, zi));
+  y.v[3] |= (x.v[0] & 1) << 63;
+  y.to_le(compressed);
+  return true;
 }
 
 // x as three 85-bit chunks, least significant first (chunkBigInt(x, 2^85), padded to 3)

@@ -32,7 +32,7 @@ struct zkpoa_context {
   zkpoa::NttEngine* ntt = nullptr;
   zkpoa::FastUploader uploader;   // pinned, multi-threaded host -> HBM path for zkey sections / witnesses
   std::string last_error;
-  float ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  float ms[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   float io_ms[2] = {0, 0};   // last prove from a host buffer: [0] witness -> HBM (host clock), [1] its bytes / 1e6
   float lane_ms[zkpoa::DeviceCtx::kLanes][2] = {};   // per-lane {whole MSM, accumulation kernel} of the last MSM
   double lane_adds[zkpoa::DeviceCtx::kLanes] = {};   // per-lane mixed additions of that kernel (non-zero digits)
