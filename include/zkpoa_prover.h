@@ -652,13 +652,19 @@ int zkpoa_eth_address(zkpoa_context* ctx, const void* pubkey_xy, uint64_t n, voi
  * four entry points, declared in a header of their own next to this one. */
 #include "zkpoa_audit.h"
 
+/* ---- the owned leaves at the prover's scale: a lookup through that stable index (any order, exact), the same over a
+ * resident tree, and the sibling paths of any number of leaves gathered by one kernel, where the single-leaf path entry
+ * point above copies 32 bytes per level: four entry points, declared in a header of their own next to this one. */
+#include "zkpoa_merkle_paths.h"
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* Timings (ms, HIP events on the stream that ran the kernels) of the last call on this context.
  * id: 0 = whole device part of last MSM, 1 = its bucket-accumulation kernel (dominant kernel),
  *     2 = last NTT, 3 = last prove: ABC+NTT chain, 4 = last prove: all MSMs, 5 = last prove: total,
  *     6 = last prove: self-check (host pairing check; 0 when it did not run), 7 = last Merkle tree build,
  *     8 = last zkpoa_ecdsa_star, zkpoa_ecdsa_sign, zkpoa_bip32_children or zkpoa_bip32_tweak: its kernels,
- *     9 = last zkpoa_anon_set_index_device or zkpoa_anon_set_audit: its kernels.
+ *     9 = last zkpoa_anon_set_index_device or zkpoa_anon_set_audit: its kernels,
+ *     10 = last zkpoa_anon_set_find_device, zkpoa_merkle_find, zkpoa_merkle_paths or zkpoa_merkle_paths_device: its kernels.
  * Also: tuning knobs. key "msm_c" forces the Pippenger window (0 = auto); key "msm_max_points" sets the
  * number of points one bucket sort may take (0 = 2^27; larger MSMs run in chunks -- tests force small values);
  * key "prove_serial" = 1 runs the stages of a prove one after the other (solo device times for the roofline);

@@ -267,6 +267,12 @@ class Context:
         stable sort, exact for every input."""
         self._check(lib().zkpoa_anon_set_index_device(self._h, d_addresses, n, d_perm), "zkpoa_anon_set_index_device")
 
+    def anon_set_find(self, d_keys, n, d_perm, d_queries, m, d_first, d_count):
+        """Lookup through the stable index (all device pointers): d_count[i] <- the rows whose key equals query i,
+        d_first[i] <- the lowest of them, 0xFFFFFFFF when there is none. d_keys, d_perm: as anon_set_index took and left them."""
+        self._check(lib().zkpoa_anon_set_find_device(self._h, d_keys, n, d_perm, d_queries, m, d_first, d_count),
+                    "zkpoa_anon_set_find_device")
+
     def anon_set_audit(self, addresses, n=None):
         """The duplicate check of a published set's addresses (host buffer, n x 32 B LE) -> (rows that repeat an earlier
         row's address, the pair (i, j) with the smallest such j or None, is the file strictly ascending)."""
@@ -744,6 +750,32 @@ class MerkleTree(_Handle):
         self._ctx._check(lib().zkpoa_merkle_path(self._ctx._h, self._h, index, elems, bits), "zkpoa_merkle_path")
         raw = elems.bytes()
         return ([int.from_bytes(raw[32 * i:32 * i + 32], "little") for i in range(k)], list(bits.bytes()))
+
+    def find(self, hashes):
+        """Leaf hashes (m x 32 B LE) looked up among the set's own leaves (padding is never searched) -> (first, count),
+        numpy uint32 arrays: the lowest row that holds the hash (0xFFFFFFFF: none) and how many rows do."""
+        import numpy as np
+        m = len(hashes) // 32
+        p, keep = _buf(hashes)
+        first, count = np.zeros(m, dtype=np.uint32), np.zeros(m, dtype=np.uint32)
+        self._ctx._check(lib().zkpoa_merkle_find(self._ctx._h, self._h, p, m, first.ctypes.data, count.ctypes.data),
+                         "zkpoa_merkle_find")
+        return first, count
+
+    def paths(self, indices):
+        """The sibling paths of any number of leaves in one go -> (m x k x 32 B, m x k index bits as bytes): what m calls
+        of path() give, back to back."""
+        import numpy as np
+        idx = np.ascontiguousarray(indices, dtype=np.uint64)
+        m, k = len(idx), self.info()[1]
+        elems, bits = _Out(32 * k * m), _Out(k * m)
+        self._ctx._check(lib().zkpoa_merkle_paths(self._ctx._h, self._h, idx.ctypes.data, m, elems, bits), "zkpoa_merkle_paths")
+        return elems.bytes(), bits.bytes()
+
+    def paths_device(self, d_indices, m, d_out):
+        """The gather kernel alone: d_indices (m x u64) and d_out (m x k x 32 B) are device pointers; an index that is
+        not below 2^k gives a path of zeros."""
+        self._ctx._check(lib().zkpoa_merkle_paths_device(self._ctx._h, self._h, d_indices, m, d_out), "zkpoa_merkle_paths_device")
 
 
 class MsmTable(_Handle):

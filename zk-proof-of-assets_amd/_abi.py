@@ -203,6 +203,15 @@ AUDIT_SIGNATURES = {
     "zkpoa_assets_verify":             "i: p p p u64 s s s p u32* p",
 }
 
+# every symbol include/zkpoa_merkle_paths.h declares (zkpoa_prover.h includes that header too): the owned leaves at the
+# prover's scale, all on the GPU
+MERKLE_PATHS_SIGNATURES = {
+    "zkpoa_anon_set_find_device":      "i: p p u64 p p u64 p p",
+    "zkpoa_merkle_find":               "i: p p p u64 p p",
+    "zkpoa_merkle_paths":              "i: p p p u64 p p",
+    "zkpoa_merkle_paths_device":       "i: p p p u64 p",
+}
+
 # the one symbol include/zkpoa_secp_prim.h declares (zkpoa_prover.h includes that header beside its other test hooks)
 SECP_PRIM_SIGNATURES = {
     "zkpoa_secp_prim":                 "i: p i p p u64",
@@ -240,8 +249,8 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        for table in (SIGNATURES, LAYER_INPUT_SIGNATURES, SIGN_SIGNATURES, HD_SIGNATURES, AUDIT_SIGNATURES, SECP_PRIM_SIGNATURES,
-                      HOOK_SIGNATURES):
+        for table in (SIGNATURES, LAYER_INPUT_SIGNATURES, SIGN_SIGNATURES, HD_SIGNATURES, AUDIT_SIGNATURES,
+                      MERKLE_PATHS_SIGNATURES, SECP_PRIM_SIGNATURES, HOOK_SIGNATURES):
             for name, spec in table.items():
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = signature(spec)

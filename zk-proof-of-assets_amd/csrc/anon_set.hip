@@ -1,5 +1,7 @@
 // The verifier's side (include/zkpoa_audit.h): the stable index of the published set's addresses and the exact duplicate
 // check over it (anon_set_sort.hip.h), and zkpoa_assets_verify, which binds set, root, commitment and proof together.
+// Also what queries that index (include/zkpoa_merkle_paths.h): zkpoa_anon_set_find_device, and the find over a tree's
+// stored leaves that poseidon.hip's zkpoa_merkle_find hands over to.
 //
 // Why a sort. The layer-two circuit proves inclusion of H(address, balance), and the reference's ascending-order check
 // keeps the prover from using one owned address twice; nothing keeps the prover from publishing a set that holds its
@@ -48,6 +50,23 @@ AuditCounts audit_device(zkpoa_context* ctx, const void* d_keys, uint64_t n, uin
   return out;
 }
 
+// the find kernel over device buffers between the context's event pair, waited for; its time into ms[10] (added to what
+// is there when `add`: a first find's index build comes before it)
+void find_device(zkpoa_context* ctx, const void* d_keys, uint64_t n, const uint32_t* d_perm, const void* d_queries, uint64_t m,
+                 uint32_t* d_first, uint32_t* d_count, bool add) {
+  if (!add) ctx->ms[10] = 0;
+  if (m == 0) return;
+  hipStream_t st = ctx->dev.lanes[0].stream;
+  ZK_HIP(hipEventRecord(ctx->ev_a[0], st));
+  anon_set_find(st, d_keys, n, d_perm, d_queries, m, d_first, d_count);
+  ZK_HIP(hipEventRecord(ctx->ev_b[0], st));
+  ZK_HIP(hipStreamSynchronize(st));
+  ZK_HIP(hipGetLastError());
+  float ms = 0;
+  ZK_HIP(hipEventElapsedTime(&ms, ctx->ev_a[0], ctx->ev_b[0]));
+  ctx->ms[10] += ms;
+}
+
 const uint64_t kFrOrder[4] = {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull};
 
 // the row of the first of n x 32 B values that is not below r, or n
@@ -80,6 +99,40 @@ extern "C" int zkpoa_anon_set_index_device(zkpoa_context* ctx, const void* d_add
   if (n && (!d_addresses || !d_perm)) throw HipError("anon set: null pointer");
   (void)audit_device(ctx, d_addresses, n, d_perm, false);
   ZK_API_END(ctx)
+}
+
+extern "C" int zkpoa_anon_set_find_device(zkpoa_context* ctx, const void* d_keys, uint64_t n, const uint32_t* d_perm,
+                                          const void* d_queries, uint64_t m, uint32_t* d_first, uint32_t* d_count) {
+  ZK_API_BEGIN(ctx)
+  if (n >> 32 || m >> 32) throw HipError("anon set: at most 2^32 - 1 rows and queries");
+  if (m && (!d_queries || !d_first || !d_count || (n && (!d_keys || !d_perm)))) throw HipError("anon set: null pointer");
+  find_device(ctx, d_keys, n, d_perm, d_queries, m, d_first, d_count, false);
+  ZK_API_END(ctx)
+}
+
+void zkpoa::anon_set_find_indexed(zkpoa_context* ctx, const void* d_keys, uint64_t n, DevMem& perm, const void* queries,
+                                  uint64_t m, uint32_t* first, uint32_t* count) {
+  ctx->ms[10] = 0;
+  if (n >> 32 || m >> 32) throw HipError("anon set: at most 2^32 - 1 rows and queries");
+  if (!perm && n) {   // the first find over these keys: their index, kept by the caller
+    hipStream_t st = ctx->dev.lanes[0].stream;
+    DevMem fresh;
+    fresh.alloc(n * 4);
+    AnonSetWork wk(n);
+    ZK_HIP(hipEventRecord(ctx->ev_a[0], st));
+    anon_set_index(st, wk, d_keys, n, fresh.as<uint32_t>());
+    ZK_HIP(hipEventRecord(ctx->ev_b[0], st));
+    ZK_HIP(hipStreamSynchronize(st));
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipEventElapsedTime(&ctx->ms[10], ctx->ev_a[0], ctx->ev_b[0]));
+    perm = std::move(fresh);
+  }
+  if (m == 0) return;
+  DevBuf q(m * 32), f(m * 4), c(m * 4);
+  q.up(queries, m * 32);
+  find_device(ctx, d_keys, n, perm.as<uint32_t>(), q.p, m, static_cast<uint32_t*>(f.p), static_cast<uint32_t*>(c.p), true);
+  ZK_HIP(hipMemcpy(first, f.p, m * 4, hipMemcpyDeviceToHost));
+  ZK_HIP(hipMemcpy(count, c.p, m * 4, hipMemcpyDeviceToHost));
 }
 
 extern "C" int zkpoa_anon_set_audit(zkpoa_context* ctx, const void* addresses, uint64_t n, uint64_t out[4]) {

@@ -19,6 +19,8 @@
 // its own running count per digit in LDS, read by the whole wave in one instruction before the group's first lane
 // stores the sum back; the waves of a tile are ordered by the prefix of their counts, the tiles by the scan.
 // All equal keys, two values, keys sharing 31 bytes: the same instructions run as for random keys, fewer passes.
+//   find     : what queries the index. One lane per query, a lower-bound and an upper-bound binary search over
+//              keys[perm[.]]: the number of rows with the query's key and, the order being stable, the lowest of them.
 #pragma once
 #include "msm.hip.h"   // the u32 scan
 #include "zkpoa_internal.hpp"
@@ -197,6 +199,62 @@ static __global__ __launch_bounds__(kAnonWg) void anon_adjacent_kernel(const uin
   }
 }
 
+// The index's order: keys as 256-bit little-endian integers, most significant limb first (the last pass of the sort is
+// byte 31). -1, 0, 1 for a below, equal to, above b; a key is two 16-byte vectors.
+ZK_DEV int anon_key_compare(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
+  const uint32_t a[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+  const uint32_t b[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+  int c = 0;
+#pragma unroll
+  for (int j = 0; j < 8; j++) c = a[j] != b[j] ? (a[j] < b[j] ? -1 : 1) : c;   // the highest limb that differs decides
+  return c;
+}
+
+// One lane per query: the equal run of the query in keys[perm[.]], by a lower-bound and an upper-bound binary search.
+// count <- its length, first <- the row at its start (stable index: the lowest such row), kAnonNoRow for an empty run.
+// Every probe is one dependent 4 B read of perm and two 16 B reads of the key. An entry of perm that is no row number is
+// not followed: the query reports no match.
+static __global__ __launch_bounds__(kAnonWg) void anon_find_kernel(const uint4* __restrict__ keys, uint64_t n,
+                                                                   const uint32_t* __restrict__ perm,
+                                                                   const uint4* __restrict__ queries, uint64_t m,
+                                                                   uint32_t* __restrict__ first, uint32_t* __restrict__ count) {
+  const uint64_t i = (uint64_t)blockIdx.x * kAnonWg + threadIdx.x;
+  if (i >= m) return;
+  const uint4 q0 = queries[2 * i], q1 = queries[2 * i + 1];
+  bool sound = true;
+  // lower bound: the first position whose key is not below the query; above: the lowest position seen to hold a larger key
+  uint64_t lo = 0, hi = n, above = n;
+  while (lo < hi && sound) {
+    const uint64_t mid = lo + ((hi - lo) >> 1);
+    const uint32_t row = perm[mid];
+    if (row >= n) {
+      sound = false;
+      break;
+    }
+    const int c = anon_key_compare(keys[2 * (uint64_t)row], keys[2 * (uint64_t)row + 1], q0, q1);
+    if (c < 0) lo = mid + 1;
+    else hi = mid;
+    if (c > 0) above = mid;
+  }
+  const uint64_t begin = lo;
+  // upper bound: the first position in [begin, above) whose key is above the query
+  hi = above;
+  while (lo < hi && sound) {
+    const uint64_t mid = lo + ((hi - lo) >> 1);
+    const uint32_t row = perm[mid];
+    if (row >= n) {
+      sound = false;
+      break;
+    }
+    const int c = anon_key_compare(keys[2 * (uint64_t)row], keys[2 * (uint64_t)row + 1], q0, q1);
+    if (c <= 0) lo = mid + 1;
+    else hi = mid;
+  }
+  const bool found = sound && lo > begin;
+  count[i] = found ? (uint32_t)(lo - begin) : 0;
+  first[i] = found ? perm[begin] : kAnonNoRow;
+}
+
 // Device memory of one index: the other permutation buffer, the (digit, tile) table and its scan
 struct AnonSetWork {
   uint32_t tiles;
@@ -251,6 +309,16 @@ inline void anon_set_adjacent(hipStream_t st, const void* d_keys, const uint32_t
   const uint32_t blocks = (uint32_t)std::min<uint64_t>(2048, (n + kAnonWg - 1) / kAnonWg);
   hipLaunchKernelGGL(anon_adjacent_kernel, dim3(blocks), dim3(kAnonWg), 0, st, static_cast<const uint4*>(d_keys), d_perm, n,
                      static_cast<unsigned long long*>(d_res));
+}
+
+// d_first, d_count (m words each) <- the equal run of each of the m queries in the index d_perm of the n keys, enqueued
+// on st. n = 0: every count is 0 and neither keys nor perm is read.
+inline void anon_set_find(hipStream_t st, const void* d_keys, uint64_t n, const uint32_t* d_perm, const void* d_queries,
+                          uint64_t m, uint32_t* d_first, uint32_t* d_count) {
+  if (m == 0) return;
+  if (n >> 32 || m >> 32) throw HipError("anon set: at most 2^32 - 1 rows and queries");
+  hipLaunchKernelGGL(anon_find_kernel, dim3((uint32_t)((m + kAnonWg - 1) / kAnonWg)), dim3(kAnonWg), 0, st,
+                     static_cast<const uint4*>(d_keys), n, d_perm, static_cast<const uint4*>(d_queries), m, d_first, d_count);
 }
 
 }  // namespace zkpoa

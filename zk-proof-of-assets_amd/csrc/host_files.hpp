@@ -1,5 +1,6 @@
 // The file and thread side of the host programs, in one place: a whole file mapped read-only (MappedFile), output that
-// appears under its name only when complete (AtomicFile, write_text_atomic), the host's threads (host_threads.hpp:
+// appears under its name only when complete (AtomicFile, write_text_atomic), the entry writer over it (put_text,
+// put_entries, write_entries), the host's threads (host_threads.hpp:
 // SideTask, run_threads, parallel_ranges), the ZKPOA_VERBOSE phase timer, ZKPOA_DEVICE, and the device context started on a second
 // thread while the first reads its input (ContextStart). Host only, no HIP: next to the public C header this is all a
 // command-line front end needs. Failures are std::runtime_error.
@@ -16,9 +17,11 @@
 #include <time.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 namespace zkpoa {
 
@@ -131,6 +134,46 @@ inline void write_text_atomic(const std::string& path, const std::string& text) 
   AtomicFile f(path.c_str());
   f.put_at(0, text.data(), text.size());
   f.commit();
+}
+
+// ---- the entry writer: a text file of many entries, formatted by the host threads and never held whole ----------------
+inline void put_text(AtomicFile& fo, uint64_t& off, const std::string& s) {
+  fo.put_at(off, s.data(), s.size());
+  off += s.size();
+}
+
+// entry(o, i) appends entry i of n. The entries go to `off` in rounds of 2^16, each formatted by the host threads, a
+// thread taking at least `least` entries and expecting `bytes_each` bytes per entry. round(i0, count) runs on the
+// calling thread before the entries [i0, i0 + count) are formatted: what a round's entries read is fetched there.
+constexpr uint64_t kEntryRound = 1u << 16;
+template <class Round, class Fn>
+void put_entries(AtomicFile& fo, uint64_t& off, uint64_t n, uint64_t least, uint64_t bytes_each, Round round, Fn entry) {
+  for (uint64_t i0 = 0; i0 < n; i0 += kEntryRound) {
+    const uint64_t count = std::min(kEntryRound, n - i0);
+    round(i0, count);
+    std::vector<std::string> parts(host_threads() + 1);
+    parallel_ranges(count, least, [&](unsigned t, uint64_t lo, uint64_t hi) {
+      std::string& o = parts[t];
+      o.reserve((hi - lo) * bytes_each);
+      for (uint64_t i = i0 + lo; i < i0 + hi; i++) entry(o, i);
+    });
+    for (const std::string& s : parts) put_text(fo, off, s);
+  }
+}
+template <class Fn>
+void put_entries(AtomicFile& fo, uint64_t& off, uint64_t n, uint64_t least, uint64_t bytes_each, Fn entry) {
+  put_entries(fo, off, n, least, bytes_each, [](uint64_t, uint64_t) {}, entry);
+}
+
+// a whole file: head + the entries + tail, in place only when complete
+template <class Fn>
+void write_entries(const std::string& path, const std::string& head, const std::string& tail, uint64_t n, uint64_t bytes_each, Fn entry) {
+  AtomicFile fo(path.c_str());
+  uint64_t off = 0;
+  put_text(fo, off, head);
+  put_entries(fo, off, n, 256, bytes_each, entry);
+  put_text(fo, off, tail);
+  fo.commit();
 }
 
 inline int device_from_env() { return (int)opt_long(O_DEVICE); }   // ZKPOA_DEVICE, or 0

@@ -25,6 +25,7 @@
 
 #include <string.h>
 
+#include <algorithm>
 #include <array>
 #include <memory>
 #include <stdexcept>
@@ -296,10 +297,35 @@ struct zkpoa_merkle {
   unsigned log_leaves = 0;
   uint64_t n_set = 0;         // leaves that came from the anonymity set (the rest are zero padding)
   float build_ms = 0;
+  zkpoa::DevMem leaf_index;   // the stable index of the first n_set leaves (4 B per row), built by the first find
 };
 
 // level l (0 = leaves) starts at node offset 2^(k+1) - 2^(k+1-l)
-static uint64_t level_offset(unsigned k, unsigned l) { return (2ull << k) - (2ull << (k - l)); }
+static __host__ __device__ uint64_t level_offset(unsigned k, unsigned l) { return (2ull << k) - (2ull << (k - l)); }
+
+// The sibling paths of m leaves: out element (i, l) <- node (leaf_index[i] >> l) ^ 1 of level l. One work item per
+// 16-byte half of an output element, so consecutive lanes store consecutive vectors (the output goes out as full lines)
+// and the two lanes of an element share one 32-byte sector on the read side. A leaf index that is not below 2^k gives
+// zeros and reads nothing. Everything is 64-bit: 2 m k passes 2^32 at a few million paths, a node's byte offset at 2^27 leaves.
+static __global__ __launch_bounds__(256) void merkle_paths_kernel(const uint4* __restrict__ levels, unsigned k,
+                                                                  const uint64_t* __restrict__ leaf_index, uint64_t m,
+                                                                  uint4* __restrict__ out) {
+  const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= 2 * m * k) return;
+  const uint64_t e = t >> 1, i = e / k;
+  const unsigned l = (unsigned)(e - i * k);
+  const uint64_t leaf = leaf_index[i];
+  uint4 v = make_uint4(0, 0, 0, 0);
+  if ((leaf >> k) == 0) v = levels[2 * (level_offset(k, l) + ((leaf >> l) ^ 1)) + (t & 1)];
+  out[t] = v;
+}
+
+// enqueued on st; k >= 1, m k < 2^37 (the grid)
+static void launch_paths(hipStream_t st, const zkpoa_merkle* tree, const uint64_t* d_leaf_index, uint64_t m, void* d_out) {
+  const uint64_t items = 2 * m * tree->log_leaves;
+  hipLaunchKernelGGL(merkle_paths_kernel, dim3((uint32_t)((items + 255) / 256)), dim3(256), 0, st,
+                     static_cast<const uint4*>(tree->d_levels), tree->log_leaves, d_leaf_index, m, static_cast<uint4*>(d_out));
+}
 
 extern "C" int zkpoa_merkle_build_device(zkpoa_context* ctx, const void* d_addresses, const void* d_balances, uint64_t n,
                                          zkpoa_merkle** out) {
@@ -400,5 +426,68 @@ extern "C" int zkpoa_merkle_path(zkpoa_context* ctx, const zkpoa_merkle* tree, u
     i >>= 1;
   }
   ZK_HIP(hipStreamSynchronize(ctx->dev.lanes[0].stream));
+  ZK_API_END(ctx)
+}
+
+// ---- the owned leaves at the prover's scale (include/zkpoa_merkle_paths.h) --------------------------------------------
+extern "C" int zkpoa_merkle_find(zkpoa_context* ctx, zkpoa_merkle* tree, const void* leaf_hashes, uint64_t m, uint32_t* first,
+                                 uint32_t* count) {
+  if (!tree || (m && (!leaf_hashes || !first || !count))) return PROVER_ERROR;
+  ZK_API_BEGIN(ctx)
+  // the padding leaves are not part of the keys: a zero hash is looked for among the set's own rows only
+  anon_set_find_indexed(ctx, tree->d_levels, tree->n_set, tree->leaf_index, leaf_hashes, m, first, count);
+  ZK_API_END(ctx)
+}
+
+extern "C" int zkpoa_merkle_paths_device(zkpoa_context* ctx, const zkpoa_merkle* tree, const uint64_t* d_leaf_index, uint64_t m,
+                                         void* d_paths) {
+  if (!tree || (m && (!d_leaf_index || !d_paths))) return PROVER_ERROR;
+  ZK_API_BEGIN(ctx)
+  ctx->ms[10] = 0;
+  const unsigned k = tree->log_leaves;
+  if (m >> 37 || m * k >> 37) throw HipError("merkle: at most 2^37 path elements in one call");
+  if (m && k) {
+    hipStream_t st = ctx->dev.lanes[0].stream;
+    ZK_HIP(hipEventRecord(ctx->ev_a[0], st));
+    launch_paths(st, tree, d_leaf_index, m, d_paths);
+    ZK_HIP(hipEventRecord(ctx->ev_b[0], st));
+    ZK_HIP(hipStreamSynchronize(st));
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipEventElapsedTime(&ctx->ms[10], ctx->ev_a[0], ctx->ev_b[0]));
+  }
+  ZK_API_END(ctx)
+}
+
+extern "C" int zkpoa_merkle_paths(zkpoa_context* ctx, const zkpoa_merkle* tree, const uint64_t* leaf_index, uint64_t m,
+                                  uint8_t* paths_le, uint8_t* path_indices) {
+  if (!tree || (m && !leaf_index)) return PROVER_ERROR;
+  ZK_API_BEGIN(ctx)
+  ctx->ms[10] = 0;
+  const unsigned k = tree->log_leaves;
+  for (uint64_t i = 0; i < m; i++)   // before anything is launched
+    if (leaf_index[i] >> k) throw HipError("merkle: leaf index out of range (entry " + std::to_string(i) + ")");
+  if (m && k) {
+    if (!paths_le) throw HipError("merkle: null pointer");
+    constexpr uint64_t kRound = 1u << 16;   // indices per launch: the device's share does not grow with m
+    const uint64_t round = std::min(m, kRound);
+    DevBuf d_index(round * 8), d_out(round * k * 32);
+    hipStream_t st = ctx->dev.lanes[0].stream;
+    for (uint64_t i0 = 0; i0 < m; i0 += kRound) {
+      const uint64_t cnt = std::min(kRound, m - i0);
+      ZK_HIP(hipMemcpyAsync(d_index.p, leaf_index + i0, cnt * 8, hipMemcpyHostToDevice, st));
+      ZK_HIP(hipEventRecord(ctx->ev_a[0], st));
+      launch_paths(st, tree, static_cast<const uint64_t*>(d_index.p), cnt, d_out.p);
+      ZK_HIP(hipEventRecord(ctx->ev_b[0], st));
+      ZK_HIP(hipMemcpyAsync(paths_le + i0 * k * 32, d_out.p, cnt * k * 32, hipMemcpyDeviceToHost, st));
+      ZK_HIP(hipStreamSynchronize(st));
+      ZK_HIP(hipGetLastError());
+      float ms = 0;
+      ZK_HIP(hipEventElapsedTime(&ms, ctx->ev_a[0], ctx->ev_b[0]));
+      ctx->ms[10] += ms;
+    }
+    if (path_indices)
+      for (uint64_t i = 0; i < m; i++)
+        for (unsigned l = 0; l < k; l++) path_indices[i * k + l] = (uint8_t)((leaf_index[i] >> l) & 1);
+  }
   ZK_API_END(ctx)
 }

@@ -116,38 +116,7 @@ Cli parse_options(int argc, char** argv, int first, const char* mode, const std:
   return cli;
 }
 
-// ---- the entry writer ----------------------------------------------------------------------------------------------
-void put_text(AtomicFile& fo, uint64_t& off, const std::string& s) {
-  fo.put_at(off, s.data(), s.size());
-  off += s.size();
-}
-
-// entry(o, i) appends entry i of n. The entries go to `off` in rounds of 2^16, each formatted by the host threads, a
-// thread taking at least `least` entries and expecting `bytes_each` bytes per entry.
-template <class Fn>
-void put_entries(AtomicFile& fo, uint64_t& off, uint64_t n, uint64_t least, uint64_t bytes_each, Fn entry) {
-  constexpr uint64_t kRound = 1u << 16;
-  for (uint64_t i0 = 0; i0 < n; i0 += kRound) {
-    std::vector<std::string> parts(host_threads() + 1);
-    parallel_ranges(std::min(kRound, n - i0), least, [&](unsigned t, uint64_t lo, uint64_t hi) {
-      std::string& o = parts[t];
-      o.reserve((hi - lo) * bytes_each);
-      for (uint64_t i = i0 + lo; i < i0 + hi; i++) entry(o, i);
-    });
-    for (const std::string& s : parts) put_text(fo, off, s);
-  }
-}
-
-// a whole file: head + the entries + tail, in place only when complete
-template <class Fn>
-void write_entries(const std::string& path, const std::string& head, const std::string& tail, uint64_t n, uint64_t bytes_each, Fn entry) {
-  AtomicFile fo(path.c_str());
-  uint64_t off = 0;
-  put_text(fo, off, head);
-  put_entries(fo, off, n, 256, bytes_each, entry);
-  put_text(fo, off, tail);
-  fo.commit();
-}
+// (the entry writer -- put_text, put_entries, write_entries -- is host_files.hpp's: `merkle-tree` writes through it too)
 
 // ---- parsing mode --------------------------------------------------------------------------------------------------
 struct Signatures {

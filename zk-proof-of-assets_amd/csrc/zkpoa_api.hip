@@ -68,7 +68,7 @@ extern "C" const char* zkpoa_last_error(const zkpoa_context* ctx) {
 }
 
 extern "C" float zkpoa_last_ms(const zkpoa_context* ctx, int id) {
-  if (!ctx || id < 0 || id >= 10) return -1.f;
+  if (!ctx || id < 0 || id >= 11) return -1.f;
   return ctx->ms[id];
 }
 

@@ -32,7 +32,7 @@ struct zkpoa_context {
   zkpoa::NttEngine* ntt = nullptr;
   zkpoa::FastUploader uploader;   // pinned, multi-threaded host -> HBM path for zkey sections / witnesses
   std::string last_error;
-  float ms[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  float ms[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   float io_ms[2] = {0, 0};   // last prove from a host buffer: [0] witness -> HBM (host clock), [1] its bytes / 1e6
   float lane_ms[zkpoa::DeviceCtx::kLanes][2] = {};   // per-lane {whole MSM, accumulation kernel} of the last MSM
   double lane_adds[zkpoa::DeviceCtx::kLanes] = {};   // per-lane mixed additions of that kernel (non-zero digits)
@@ -282,6 +282,10 @@ void ntt_split_mid(zkpoa_context* ctx, hipStream_t st, const void* in, void* out
                    uint32_t rank_stride);
 void ntt_release(zkpoa_context* ctx);
 void poseidon_release(zkpoa_context* ctx);
+// anon_set.hip: host queries (m x 32 B) looked up among n keys on the device through their stable index, which is built
+// into `perm` first when that is still empty; first, count: host, m words. ms[10] <- the kernels' time.
+void anon_set_find_indexed(zkpoa_context* ctx, const void* d_keys, uint64_t n, DevMem& perm, const void* queries, uint64_t m,
+                           uint32_t* first, uint32_t* count);
 }  // namespace zkpoa
 
 #define ZK_API_BEGIN(ctx)  \
