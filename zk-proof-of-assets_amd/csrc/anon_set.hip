@@ -22,21 +22,18 @@ struct AuditCounts {
   int ascending;
 };
 
-// keys on the device -> d_perm and the counts; the kernels' time between the context's event pair into ms[9]
+// keys on the device -> d_perm and the counts; the kernels' time into ms[kMsAnonIndex]
 AuditCounts audit_device(zkpoa_context* ctx, const void* d_keys, uint64_t n, uint32_t* d_perm, bool compare) {
   AuditCounts out{0, {~0ull, ~0ull}, 1};
-  ctx->ms[9] = 0;
+  ctx->ms[kMsAnonIndex] = 0;
   if (n == 0) return out;
   hipStream_t st = ctx->dev.lanes[0].stream;
   AnonSetWork wk(n);
   DevBuf res(24);
-  ZK_HIP(hipEventRecord(ctx->ev_a[0], st));
-  anon_set_index(st, wk, d_keys, n, d_perm);
-  if (compare) anon_set_adjacent(st, d_keys, d_perm, n, res.p);
-  ZK_HIP(hipEventRecord(ctx->ev_b[0], st));
-  ZK_HIP(hipStreamSynchronize(st));
-  ZK_HIP(hipGetLastError());
-  ZK_HIP(hipEventElapsedTime(&ctx->ms[9], ctx->ev_a[0], ctx->ev_b[0]));
+  timed(ctx, st, kMsAnonIndex, [&] {
+    anon_set_index(st, wk, d_keys, n, d_perm);
+    if (compare) anon_set_adjacent(st, d_keys, d_perm, n, res.p);
+  });
   if (compare) {
     uint64_t r[3];
     ZK_HIP(hipMemcpy(r, res.p, 24, hipMemcpyDeviceToHost));
@@ -50,21 +47,14 @@ AuditCounts audit_device(zkpoa_context* ctx, const void* d_keys, uint64_t n, uin
   return out;
 }
 
-// the find kernel over device buffers between the context's event pair, waited for; its time into ms[10] (added to what
-// is there when `add`: a first find's index build comes before it)
+// the find kernel over device buffers, waited for; its time into ms[kMsAnonFind] (added to what is there when `add`: a
+// first find's index build comes before it)
 void find_device(zkpoa_context* ctx, const void* d_keys, uint64_t n, const uint32_t* d_perm, const void* d_queries, uint64_t m,
                  uint32_t* d_first, uint32_t* d_count, bool add) {
-  if (!add) ctx->ms[10] = 0;
+  if (!add) ctx->ms[kMsAnonFind] = 0;
   if (m == 0) return;
   hipStream_t st = ctx->dev.lanes[0].stream;
-  ZK_HIP(hipEventRecord(ctx->ev_a[0], st));
-  anon_set_find(st, d_keys, n, d_perm, d_queries, m, d_first, d_count);
-  ZK_HIP(hipEventRecord(ctx->ev_b[0], st));
-  ZK_HIP(hipStreamSynchronize(st));
-  ZK_HIP(hipGetLastError());
-  float ms = 0;
-  ZK_HIP(hipEventElapsedTime(&ms, ctx->ev_a[0], ctx->ev_b[0]));
-  ctx->ms[10] += ms;
+  timed(ctx, st, kMsAnonFind, [&] { anon_set_find(st, d_keys, n, d_perm, d_queries, m, d_first, d_count); }, add);
 }
 
 const uint64_t kFrOrder[4] = {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull};
@@ -112,27 +102,22 @@ extern "C" int zkpoa_anon_set_find_device(zkpoa_context* ctx, const void* d_keys
 
 void zkpoa::anon_set_find_indexed(zkpoa_context* ctx, const void* d_keys, uint64_t n, DevMem& perm, const void* queries,
                                   uint64_t m, uint32_t* first, uint32_t* count) {
-  ctx->ms[10] = 0;
+  ctx->ms[kMsAnonFind] = 0;
   if (n >> 32 || m >> 32) throw HipError("anon set: at most 2^32 - 1 rows and queries");
   if (!perm && n) {   // the first find over these keys: their index, kept by the caller
     hipStream_t st = ctx->dev.lanes[0].stream;
     DevMem fresh;
     fresh.alloc(n * 4);
     AnonSetWork wk(n);
-    ZK_HIP(hipEventRecord(ctx->ev_a[0], st));
-    anon_set_index(st, wk, d_keys, n, fresh.as<uint32_t>());
-    ZK_HIP(hipEventRecord(ctx->ev_b[0], st));
-    ZK_HIP(hipStreamSynchronize(st));
-    ZK_HIP(hipGetLastError());
-    ZK_HIP(hipEventElapsedTime(&ctx->ms[10], ctx->ev_a[0], ctx->ev_b[0]));
+    timed(ctx, st, kMsAnonFind, [&] { anon_set_index(st, wk, d_keys, n, fresh.as<uint32_t>()); });
     perm = std::move(fresh);
   }
   if (m == 0) return;
-  DevBuf q(m * 32), f(m * 4), c(m * 4);
-  q.up(queries, m * 32);
-  find_device(ctx, d_keys, n, perm.as<uint32_t>(), q.p, m, static_cast<uint32_t*>(f.p), static_cast<uint32_t*>(c.p), true);
-  ZK_HIP(hipMemcpy(first, f.p, m * 4, hipMemcpyDeviceToHost));
-  ZK_HIP(hipMemcpy(count, c.p, m * 4, hipMemcpyDeviceToHost));
+  LaneIn q(queries, 32, m);
+  LaneOut f(first, 4, m), c(count, 4, m);
+  find_device(ctx, d_keys, n, perm.as<uint32_t>(), q.at<const void>(0), m, f.at<uint32_t>(0), c.at<uint32_t>(0), true);
+  f.down();
+  c.down();
 }
 
 extern "C" int zkpoa_anon_set_audit(zkpoa_context* ctx, const void* addresses, uint64_t n, uint64_t out[4]) {
@@ -212,7 +197,8 @@ extern "C" int zkpoa_assets_verify(zkpoa_context* ctx, const void* addresses, co
   }
   if (opt_verbose())
     fprintf(stderr, "zkpoa: assets verify: %llu rows: range check %.1f ms, proof %.1f ms, upload %.1f ms, index %.1f ms (kernels %.2f), "
-                    "tree %.1f ms (kernels %.2f)\n", (unsigned long long)n, t_check, t_proof, t_upload, t_index, ctx->ms[9], t_tree, ctx->ms[7]);
+                    "tree %.1f ms (kernels %.2f)\n", (unsigned long long)n, t_check, t_proof, t_upload, t_index,
+            ctx->ms[kMsAnonIndex], t_tree, ctx->ms[kMsMerkleBuild]);
 
   // the commitment the proof binds
   bool point = false;

@@ -212,7 +212,7 @@ void join_key_data(const std::vector<uint8_t>& prefix, const std::vector<uint8_t
 }
 
 // The tweak kernel over n lanes and its outputs; tweaks: on the device. chain: the device array of the chain codes, or
-// nullptr. Called inside timed_launches.
+// nullptr. Called inside timed().
 struct TweakOut {
   LaneOut<SecretBuf> key32;
   LaneOut<> prefix, pub, addr, status;
@@ -245,7 +245,7 @@ bool public_key_data(const uint8_t* key33) { return key33[0] != 0; }
 // zkpoa_bip32_children, and each level of zkpoa_bip32_derive_path
 void children(zkpoa_context* ctx, const uint8_t* parent_key33, const uint8_t* chain32, uint64_t first, uint64_t n, void* out_key33,
               void* out_chain32, void* out_pubkey_xy, void* out_address20, uint8_t* out_status) {
-  ctx->ms[8] = 0;
+  ctx->ms[kMsLaneBatch] = 0;
   if (first > (1ull << 32) || n > (1ull << 32) - first) throw HipError("bip32_children: first_index + n is at most 2^32");
   if (!batch_wanted("bip32_children", "children", n,
                     parent_key33 && chain32 && out_key33 && out_chain32 && out_pubkey_xy && out_address20 && out_status))
@@ -259,7 +259,7 @@ void children(zkpoa_context* ctx, const uint8_t* parent_key33, const uint8_t* ch
   LaneArray<SecretBuf> il(32, n, st);
   LaneOut ochain(out_chain32, 32, n);
   TweakOut out(n, st, out_key33, out_pubkey_xy, out_address20, out_status);
-  timed_launches(ctx, st, [&] {
+  timed(ctx, st, kMsLaneBatch, [&] {
     for_slabs(n, kTweakLanesMax, [&](uint64_t i0, uint64_t m) {
       hipLaunchKernelGGL(bip32_hmac_kernel, dim3(blocks_of(m, 256)), dim3(256), 0, st, dpar.at<const Parent>(0), first + i0, m,
                          il.at<uint32_t>(i0), ochain.at<uint32_t>(i0));
@@ -387,7 +387,7 @@ extern "C" int zkpoa_bip32_children(zkpoa_context* ctx, const uint8_t* parent_ke
 extern "C" int zkpoa_bip32_tweak(zkpoa_context* ctx, const uint8_t* parent_key33, uint64_t n, const void* tweaks32, void* out_key33,
                                  void* out_pubkey_xy, void* out_address20, uint8_t* out_status) {
   ZK_API_BEGIN(ctx)
-  ctx->ms[8] = 0;
+  ctx->ms[kMsLaneBatch] = 0;
   if (!batch_wanted("bip32_tweak", "tweaks", n, parent_key33 && tweaks32 && out_key33 && out_pubkey_xy && out_address20 && out_status))
     return PROVER_OK;
   Parent par;
@@ -397,7 +397,7 @@ extern "C" int zkpoa_bip32_tweak(zkpoa_context* ctx, const uint8_t* parent_key33
   LaneIn<SecretBuf> dpar(&par, sizeof(par), 1, st), dil(tweaks32, 32, n, st);
   memset(&par, 0, sizeof(par));
   TweakOut out(n, st, out_key33, out_pubkey_xy, out_address20, out_status);
-  timed_launches(ctx, st, [&] { out.launch(st, dpar.at<const Parent>(0), dil.at<const void>(0), nullptr, dtab.at<const AffineK>(0), n); });
+  timed(ctx, st, kMsLaneBatch, [&] { out.launch(st, dpar.at<const Parent>(0), dil.at<const void>(0), nullptr, dtab.at<const AffineK>(0), n); });
   out.down();
   ZK_API_END(ctx)
 }

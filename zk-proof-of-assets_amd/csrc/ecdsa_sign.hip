@@ -149,7 +149,7 @@ extern "C" int zkpoa_rfc6979_nonce(zkpoa_context* ctx, uint64_t n, const void* s
 extern "C" int zkpoa_ecdsa_sign(zkpoa_context* ctx, uint64_t n, const void* seckeys, const void* msghash, uint64_t msghash_stride,
                                 void* out_r, void* out_s, uint8_t* out_v, void* out_pubkey_xy, void* out_address20, uint8_t* out_status) {
   ZK_API_BEGIN(ctx)
-  ctx->ms[8] = 0;
+  ctx->ms[kMsLaneBatch] = 0;
   if (msghash_stride != 0 && msghash_stride != 32) throw HipError("ecdsa_sign: msghash_stride is 0 (one hash) or 32 (one per key)");
   if (!batch_wanted("ecdsa_sign", "keys", n, seckeys && msghash && out_r && out_s && out_v && out_pubkey_xy && out_address20 && out_status))
     return PROVER_OK;
@@ -157,7 +157,7 @@ extern "C" int zkpoa_ecdsa_sign(zkpoa_context* ctx, uint64_t n, const void* seck
   LaneIn dtab(fixed_table_host(), sizeof(AffineK), kFixedEntries), dz(msghash, 32, msghash_stride ? n : 1);
   LaneOut orr(out_r, 32, n), os(out_s, 32, n), ov(out_v, 1, n), opk(out_pubkey_xy, 64, n), oad(out_address20, 20, n), ost(out_status, 1, n);
   LaneIn<SecretBuf> dk(seckeys, 32, n, st);
-  timed_launches(ctx, st, [&] {
+  timed(ctx, st, kMsLaneBatch, [&] {
     for_slabs(n, kSignLanesMax, [&](uint64_t i0, uint64_t m) {
       hipLaunchKernelGGL(ecdsa_sign_kernel, dim3(blocks_of(m, kSignThreads)), dim3(kSignThreads), 0, st, dk.at<const void>(i0),
                          dz.at<const uint32_t>(msghash_stride ? i0 : 0), msghash_stride ? 8u : 0u, dtab.at<const AffineK>(0), m,

@@ -70,7 +70,7 @@ extern "C" int zkpoa_ecdsa_star(zkpoa_context* ctx, uint64_t n, const void* r, c
                                 const void* address20, void* out_rprime, void* out_pubkey_xy, void* out_address20,
                                 uint8_t* out_status) {
   ZK_API_BEGIN(ctx)
-  ctx->ms[8] = 0;
+  ctx->ms[kMsLaneBatch] = 0;
   if (!batch_wanted("ecdsa_star", "signatures", n,
                     r && s && msghash && v && address20 && out_rprime && out_pubkey_xy && out_address20 && out_status))
     return PROVER_OK;
@@ -81,7 +81,7 @@ extern "C" int zkpoa_ecdsa_star(zkpoa_context* ctx, uint64_t n, const void* r, c
   DevBuf dtab(lanes * kTableBytesPerLane);
   LaneOut orp(out_rprime, 32, n), opk(out_pubkey_xy, 64, n), oad(out_address20, 20, n), ost(out_status, 1, n);
   hipStream_t st = ctx->dev.lanes[0].stream;
-  timed_launches(ctx, st, [&] {
+  timed(ctx, st, kMsLaneBatch, [&] {
     for_slabs(n, lanes, [&](uint64_t i0, uint64_t m) {
       hipLaunchKernelGGL(ecdsa_star_kernel, dim3(blocks_of(m, kSigThreads)), dim3(kSigThreads), 0, st, dr.at<const void>(i0),
                          ds.at<const void>(i0), dz.at<const void>(i0), dv.at<const uint8_t>(i0), da.at<const uint32_t>(i0),

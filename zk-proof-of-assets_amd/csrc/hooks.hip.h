@@ -115,30 +115,29 @@ void gen_bases(zkpoa_context* ctx, const uint8_t a_le[32], const uint8_t b_le[32
   for (uint64_t off = 0; off < n; off += slab) {
     uint64_t cnt = n - off < slab ? n - off : slab;
     uint64_t threads = (cnt + CH - 1) / CH;
-    hipLaunchKernelGGL((gen_bases_kernel<F>), dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, lane.stream, dG,
+    hipLaunchKernelGGL((gen_bases_kernel<F>), dim3(blocks_of(threads, 256)), dim3(256), 0, lane.stream, dG,
                        dB, am, bm, i0 + off, cnt, CH, scratch.p);
-    hipLaunchKernelGGL((xyzz_to_affine_kernel<F>), dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, lane.stream,
+    hipLaunchKernelGGL((xyzz_to_affine_kernel<F>), dim3(blocks_of(cnt, 256)), dim3(256), 0, lane.stream,
                        (const void*)scratch.p, (void*)(reinterpret_cast<char*>(d_out) + off * MsmSizes<F>::kAffine),
                        cnt);
   }
-  ZK_HIP(hipStreamSynchronize(lane.stream));
-  ZK_HIP(hipGetLastError());
+  finish(lane.stream);
 }
 
 
 template <class F>
 inline void group_add_run(zkpoa_context* ctx, const void* a, const void* b, void* out, uint64_t n) {
   constexpr size_t A = MsmSizes<F>::kAffine;
-  DevBuf da(n * A), db(n * A), dx(n * MsmSizes<F>::kXyzz), dout(n * A);
-  ZK_HIP(hipMemcpy(da.p, a, n * A, hipMemcpyHostToDevice));
-  ZK_HIP(hipMemcpy(db.p, b, n * A, hipMemcpyHostToDevice));
+  LaneIn da(a, A, n), db(b, A, n);
+  DevBuf dx(n * MsmSizes<F>::kXyzz);
+  LaneOut dout(out, A, n);
   hipStream_t st = ctx->dev.lanes[0].stream;
-  dim3 grid((uint32_t)((n + 255) / 256));
-  hipLaunchKernelGGL((group_add_kernel<F>), grid, dim3(256), 0, st, (const void*)da.p, (const void*)db.p, dx.p, n);
-  hipLaunchKernelGGL((xyzz_to_affine_kernel<F>), grid, dim3(256), 0, st, (const void*)dx.p, dout.p, n);
-  ZK_HIP(hipStreamSynchronize(st));
-  ZK_HIP(hipGetLastError());
-  ZK_HIP(hipMemcpy(out, dout.p, n * A, hipMemcpyDeviceToHost));
+  dim3 grid(blocks_of(n, 256));
+  hipLaunchKernelGGL((group_add_kernel<F>), grid, dim3(256), 0, st, da.template at<const void>(0),
+                     db.template at<const void>(0), dx.p, n);
+  hipLaunchKernelGGL((xyzz_to_affine_kernel<F>), grid, dim3(256), 0, st, (const void*)dx.p, dout.template at<void>(0), n);
+  finish(st);
+  dout.down();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -243,14 +242,13 @@ inline void field_prim_run(zkpoa_context* ctx, int field, int op, const void* in
   if (ar.in == 0) throw HipError("field_prim: bad field/op");
   if (n == 0) return;
   constexpr size_t B = FieldBytes<F>::N;
-  DevBuf din(n * ar.in * B), dout(n * ar.out * B);
-  ZK_HIP(hipMemcpy(din.p, in, n * ar.in * B, hipMemcpyHostToDevice));
+  LaneIn din(in, ar.in * B, n);
+  LaneOut dout(out, ar.out * B, n);
   hipStream_t st = ctx->dev.lanes[0].stream;
-  dim3 grid((uint32_t)((n + 255) / 256));
-  hipLaunchKernelGGL((field_prim_kernel<F>), grid, dim3(256), 0, st, op, (const void*)din.p, dout.p, n, raw);
-  ZK_HIP(hipStreamSynchronize(st));
-  ZK_HIP(hipGetLastError());
-  ZK_HIP(hipMemcpy(out, dout.p, n * ar.out * B, hipMemcpyDeviceToHost));
+  hipLaunchKernelGGL((field_prim_kernel<F>), dim3(blocks_of(n, 256)), dim3(256), 0, st, op, din.template at<const void>(0),
+                     dout.template at<void>(0), n, raw);
+  finish(st);
+  dout.down();
 }
 
 // curve op: 0 = xyzz_add(a, b XYZZ), 1 = xyzz_add_affine(a, b affine, negate k != 0), 2 = xyzz_dbl(a),
@@ -292,17 +290,14 @@ inline void curve_prim_run(zkpoa_context* ctx, int op, const void* a, const void
   constexpr size_t X = MsmSizes<F>::kXyzz;
   const bool use_a = op != 3, use_b = op <= 1 || op == 3, use_k = op == 1 || op == 4;
   const size_t bsz = op == 0 ? X : MsmSizes<F>::kAffine;
-  DevBuf da(use_a ? n * X : 0), db(use_b ? n * bsz : 0), dk(use_k ? n * 4 : 0), dout(n * X);
-  if (use_a) ZK_HIP(hipMemcpy(da.p, a, n * X, hipMemcpyHostToDevice));
-  if (use_b) ZK_HIP(hipMemcpy(db.p, b, n * bsz, hipMemcpyHostToDevice));
-  if (use_k) ZK_HIP(hipMemcpy(dk.p, k, n * 4, hipMemcpyHostToDevice));
+  // an operand the op does not use: no items, so nothing is read from the caller's pointer
+  LaneIn da(a, X, use_a ? n : 0), db(b, bsz, use_b ? n : 0), dk(k, 4, use_k ? n : 0);
+  LaneOut dout(out, X, n);
   hipStream_t st = ctx->dev.lanes[0].stream;
-  dim3 grid((uint32_t)((n + 255) / 256));
-  hipLaunchKernelGGL((curve_prim_kernel<F>), grid, dim3(256), 0, st, op, (const void*)da.p, (const void*)db.p,
-                     (const uint32_t*)dk.p, dout.p, n);
-  ZK_HIP(hipStreamSynchronize(st));
-  ZK_HIP(hipGetLastError());
-  ZK_HIP(hipMemcpy(out, dout.p, n * X, hipMemcpyDeviceToHost));
+  hipLaunchKernelGGL((curve_prim_kernel<F>), dim3(blocks_of(n, 256)), dim3(256), 0, st, op, da.template at<const void>(0),
+                     db.template at<const void>(0), dk.template at<const uint32_t>(0), dout.template at<void>(0), n);
+  finish(st);
+  dout.down();
 }
 
 }  // namespace zkpoa

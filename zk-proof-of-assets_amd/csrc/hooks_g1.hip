@@ -182,15 +182,13 @@ void fq29_prim_run(zkpoa_context* ctx, int op, const void* in, void* out, uint64
   if (ar.out == 0) throw HipError("fq29_prim: bad op");
   if (n == 0) return;
   const uint32_t in_words = raw ? ar.in_raw : ar.in_words;
-  const size_t bin = n * in_words * 4, bout = n * ar.out * 4;
-  DevBuf din(bin), dout(bout);
-  ZK_HIP(hipMemcpy(din.p, in, bin, hipMemcpyHostToDevice));
+  LaneIn din(in, (size_t)in_words * 4, n);
+  LaneOut dout(out, (size_t)ar.out * 4, n);
   hipStream_t st = ctx->dev.lanes[0].stream;
-  hipLaunchKernelGGL(fq29_prim_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, op, (const uint32_t*)din.p,
-                     (uint32_t*)dout.p, n, raw ? 1 : 0, in_words, (uint32_t)ar.out);
-  ZK_HIP(hipStreamSynchronize(st));
-  ZK_HIP(hipGetLastError());
-  ZK_HIP(hipMemcpy(out, dout.p, bout, hipMemcpyDeviceToHost));
+  hipLaunchKernelGGL(fq29_prim_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, st, op, din.at<const uint32_t>(0),
+                     dout.at<uint32_t>(0), n, raw ? 1 : 0, in_words, (uint32_t)ar.out);
+  finish(st);
+  dout.down();
 }
 void gen_bases_g1(zkpoa_context* ctx, const uint8_t a_le[32], const uint8_t b_le[32], uint64_t i0, uint64_t n, void* d_out) {
   gen_bases<Fq, HFq>(ctx, a_le, b_le, i0, n, d_out);
@@ -203,17 +201,15 @@ extern "C" int zkpoa_field_op(zkpoa_context* ctx, int field, int op, const void*
   ZK_API_BEGIN(ctx)
   if (field < 0 || field > 1 || op < 0 || op > 5) throw HipError("field_op: bad field/op");
   if (n == 0) return PROVER_OK;
-  DevBuf da(n * 32), db(n * 32), dout(n * 32);
-  ZK_HIP(hipMemcpy(da.p, a, n * 32, hipMemcpyHostToDevice));
-  if (b) ZK_HIP(hipMemcpy(db.p, b, n * 32, hipMemcpyHostToDevice));
+  LaneIn da(a, 32, n), db(b, 32, b ? n : 0);
+  LaneOut dout(out, 32, n);
   hipStream_t st = ctx->dev.lanes[0].stream;
-  dim3 grid((uint32_t)((n + 255) / 256));
-  const void* bp = b ? db.p : nullptr;
-  if (field == 0) hipLaunchKernelGGL((zkpoa::field_op_kernel<Fq>), grid, dim3(256), 0, st, op, (const void*)da.p, bp, dout.p, n);
-  else hipLaunchKernelGGL((zkpoa::field_op_kernel<Fr>), grid, dim3(256), 0, st, op, (const void*)da.p, bp, dout.p, n);
-  ZK_HIP(hipStreamSynchronize(st));
-  ZK_HIP(hipGetLastError());
-  ZK_HIP(hipMemcpy(out, dout.p, n * 32, hipMemcpyDeviceToHost));
+  dim3 grid(blocks_of(n, 256));
+  const void *ap = da.at<const void>(0), *bp = b ? db.at<const void>(0) : nullptr;   // no b: the kernel takes zero for it
+  if (field == 0) hipLaunchKernelGGL((zkpoa::field_op_kernel<Fq>), grid, dim3(256), 0, st, op, ap, bp, dout.at<void>(0), n);
+  else hipLaunchKernelGGL((zkpoa::field_op_kernel<Fr>), grid, dim3(256), 0, st, op, ap, bp, dout.at<void>(0), n);
+  finish(st);
+  dout.down();
   ZK_API_END(ctx)
 }
 

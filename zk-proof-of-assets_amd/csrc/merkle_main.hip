@@ -19,6 +19,9 @@
 
 using namespace zkpoa;
 
+// This main is a client of the C ABI and sees the public header only, so the time slot it reads is the public id.
+constexpr int kFindKernelsMsId = 10;   // zkpoa_last_ms: the kernels of the last find or path gather
+
 // ---- the owned addresses: accountAttestations[].accountData.{address, balance}.__bigint__ (decimal), merkle_tree.rs:
 // 296-327. The file is 1.6 GB at 2^20 entries: it is pulled through its mapping, and whatever else it holds is skipped.
 struct Owned {
@@ -139,7 +142,7 @@ int main(int argc, char** argv) {
     const double t_find = now_s();
     std::vector<uint32_t> first(m ? m : 1), count(m ? m : 1);
     if (m) ZK_CALL(zkpoa_merkle_find(ctx, tree, ohash.data(), m, first.data(), count.data()), "find owned leaves");
-    const float find_kernel_ms = zkpoa_last_ms(ctx, 10);
+    const float find_kernel_ms = zkpoa_last_ms(ctx, kFindKernelsMsId);
     std::vector<uint64_t> index(m);
     bool indexed = true;
     for (uint64_t i = 0; i < m; i++) {
@@ -196,7 +199,7 @@ int main(int argc, char** argv) {
                   ZK_CALL(zkpoa_merkle_paths(ctx, tree, index.data() + i0, cnt, reinterpret_cast<uint8_t*>(path.data()), nullptr),
                           "merkle paths");
                   paths_s += now_s() - t0;
-                  gather_kernel_ms += zkpoa_last_ms(ctx, 10);
+                  gather_kernel_ms += zkpoa_last_ms(ctx, kFindKernelsMsId);
                   path_i0 = i0;
                 },
                 [&](std::string& o, uint64_t i) {

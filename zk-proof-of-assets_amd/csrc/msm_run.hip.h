@@ -12,6 +12,8 @@ namespace zkpoa {
 // (default 2^27; the largest domain a zkey may have is 2^28) runs in chunks whose results are added on the host.
 // `table` (optional): fixed-base table built from exactly these n bases -> merged-bucket form, d_bases unread.
 // `density` (optional): digit density of these scalars (msm_plan.hpp MsmRequest); every chunk is planned with it.
+// The two timed sections here are not a KernelTimer: other lanes run beside this one, so they wait for the lane's own
+// stop event and leave the thread's last error alone, and their times go to ms2 and not to a slot.
 template <class F, class HF>
 void msm_run(zkpoa_context* ctx, int lane_id, const void* d_bases, const void* d_scalars, uint64_t n, uint8_t* out,
              float* ms2, const MsmTable* table = nullptr, const double* density = nullptr) {

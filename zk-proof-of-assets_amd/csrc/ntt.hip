@@ -40,26 +40,19 @@ using namespace zkpoa;
 extern "C" int zkpoa_ntt_device(zkpoa_context* ctx, void* d_data, unsigned log_n, int inverse) {
   ZK_API_BEGIN(ctx)
   if (log_n > 28) throw HipError("ntt: log_n > 28 (two-adicity of Fr)");
-  Lane& lane = ctx->dev.lanes[0];
-  ntt_prepare(ctx, lane.stream, log_n);
-  ZK_HIP(hipEventRecord(ctx->ev_a[0], lane.stream));
-  ntt_natural(ctx, lane.stream, d_data, log_n, inverse != 0);
-  ZK_HIP(hipEventRecord(ctx->ev_b[0], lane.stream));
-  ZK_HIP(hipStreamSynchronize(lane.stream));
-  ZK_HIP(hipGetLastError());
-  ZK_HIP(hipEventElapsedTime(&ctx->ms[2], ctx->ev_a[0], ctx->ev_b[0]));
+  hipStream_t st = ctx->dev.lanes[0].stream;
+  ntt_prepare(ctx, st, log_n);
+  timed(ctx, st, kMsNtt, [&] { ntt_natural(ctx, st, d_data, log_n, inverse != 0); });
   ZK_API_END(ctx)
 }
 
 extern "C" int zkpoa_ntt(zkpoa_context* ctx, void* data, unsigned log_n, int inverse) {
   ZK_API_BEGIN(ctx)
   if (log_n > 28) throw HipError("ntt: log_n > 28 (two-adicity of Fr)");
-  size_t bytes = (size_t)32 << log_n;
-  DevBuf d(bytes);
-  ZK_HIP(hipMemcpy(d.p, data, bytes, hipMemcpyHostToDevice));
-  int rc = zkpoa_ntt_device(ctx, d.p, log_n, inverse);
+  LaneInOut d(data, 32, 1ull << log_n);
+  int rc = zkpoa_ntt_device(ctx, d.at<void>(0), log_n, inverse);
   if (rc != PROVER_OK) return rc;
-  ZK_HIP(hipMemcpy(data, d.p, bytes, hipMemcpyDeviceToHost));
+  d.down();
   ZK_API_END(ctx)
 }
 
@@ -72,17 +65,15 @@ extern "C" int zkpoa_ntt_form(zkpoa_context* ctx, void* data, unsigned log_n, in
   if (batch == 0 || batch > 65535) throw HipError("ntt_form: batch is 1..65535 (grid.y)");
   const uint64_t n = 1ull << log_n;
   if (stride < n) throw HipError("ntt_form: stride < 2^log_n");
-  const size_t bytes = (size_t)((batch - 1) * stride + n) * 32;
-  DevBuf d(bytes);
-  d.up(data, bytes);
+  LaneInOut d(data, 32, (batch - 1) * stride + n);
+  void* dp = d.at<void>(0);
   hipStream_t st = ctx->dev.lanes[0].stream;
   ntt_prepare(ctx, st, log_n);
-  if (form == 0) ntt_dif(ctx, st, d.p, log_n, inverse != 0, batch, (size_t)stride * 32);
-  else if (form == 1) ntt_dit(ctx, st, d.p, log_n, inverse != 0, batch, (size_t)stride * 32);
-  else ntt_to_odd_coset(ctx, st, d.p, log_n, batch, (size_t)stride * 32);
-  ZK_HIP(hipStreamSynchronize(st));
-  ZK_HIP(hipGetLastError());
-  ZK_HIP(hipMemcpy(data, d.p, bytes, hipMemcpyDeviceToHost));
+  if (form == 0) ntt_dif(ctx, st, dp, log_n, inverse != 0, batch, (size_t)stride * 32);
+  else if (form == 1) ntt_dit(ctx, st, dp, log_n, inverse != 0, batch, (size_t)stride * 32);
+  else ntt_to_odd_coset(ctx, st, dp, log_n, batch, (size_t)stride * 32);
+  finish(st);
+  d.down();
   ZK_API_END(ctx)
 }
 

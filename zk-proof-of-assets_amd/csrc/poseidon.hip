@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void poseidon2_kernel(const PoseidonTables* __
 void launch_hash(hipStream_t st, const PoseidonTables* prm, const void* l, const void* r, uint64_t stride, uint64_t n,
                  void* out) {
   if (n)
-    hipLaunchKernelGGL(poseidon2_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, prm, l, r, stride, n, out);
+    hipLaunchKernelGGL(poseidon2_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, st, prm, l, r, stride, n, out);
 }
 
 }  // namespace
@@ -274,29 +274,25 @@ extern "C" int zkpoa_poseidon2_device(zkpoa_context* ctx, const void* d_left, co
   ZK_API_BEGIN(ctx)
   hipStream_t st = ctx->dev.lanes[0].stream;
   launch_hash(st, device_params(ctx), d_left, d_right, 1, n, d_out);
-  ZK_HIP(hipStreamSynchronize(st));
-  ZK_HIP(hipGetLastError());
+  finish(st);
   ZK_API_END(ctx)
 }
 
 extern "C" int zkpoa_poseidon2(zkpoa_context* ctx, const void* left, const void* right, uint64_t n, void* out) {
   ZK_API_BEGIN(ctx)
-  DevBuf dl(n * 32), dr(n * 32), dout(n * 32);
-  ZK_HIP(hipMemcpy(dl.p, left, n * 32, hipMemcpyHostToDevice));
-  ZK_HIP(hipMemcpy(dr.p, right, n * 32, hipMemcpyHostToDevice));
+  LaneIn dl(left, 32, n), dr(right, 32, n);
+  LaneOut dout(out, 32, n);
   hipStream_t st = ctx->dev.lanes[0].stream;
-  launch_hash(st, device_params(ctx), dl.p, dr.p, 1, n, dout.p);
-  ZK_HIP(hipStreamSynchronize(st));
-  ZK_HIP(hipGetLastError());
-  ZK_HIP(hipMemcpy(out, dout.p, n * 32, hipMemcpyDeviceToHost));
+  launch_hash(st, device_params(ctx), dl.at<const void>(0), dr.at<const void>(0), 1, n, dout.at<void>(0));
+  finish(st);
+  dout.down();
   ZK_API_END(ctx)
 }
 
 struct zkpoa_merkle {
-  void* d_levels = nullptr;   // (2^(k+1) - 1) nodes, leaves first, root last; 32 B LE standard form
+  zkpoa::DevMem d_levels;     // (2^(k+1) - 1) nodes, leaves first, root last; 32 B LE standard form
   unsigned log_leaves = 0;
   uint64_t n_set = 0;         // leaves that came from the anonymity set (the rest are zero padding)
-  float build_ms = 0;
   zkpoa::DevMem leaf_index;   // the stable index of the first n_set leaves (4 B per row), built by the first find
 };
 
@@ -323,8 +319,8 @@ static __global__ __launch_bounds__(256) void merkle_paths_kernel(const uint4* _
 // enqueued on st; k >= 1, m k < 2^37 (the grid)
 static void launch_paths(hipStream_t st, const zkpoa_merkle* tree, const uint64_t* d_leaf_index, uint64_t m, void* d_out) {
   const uint64_t items = 2 * m * tree->log_leaves;
-  hipLaunchKernelGGL(merkle_paths_kernel, dim3((uint32_t)((items + 255) / 256)), dim3(256), 0, st,
-                     static_cast<const uint4*>(tree->d_levels), tree->log_leaves, d_leaf_index, m, static_cast<uint4*>(d_out));
+  hipLaunchKernelGGL(merkle_paths_kernel, dim3(blocks_of(items, 256)), dim3(256), 0, st, tree->d_levels.as<const uint4>(),
+                     tree->log_leaves, d_leaf_index, m, static_cast<uint4*>(d_out));
 }
 
 extern "C" int zkpoa_merkle_build_device(zkpoa_context* ctx, const void* d_addresses, const void* d_balances, uint64_t n,
@@ -339,27 +335,18 @@ extern "C" int zkpoa_merkle_build_device(zkpoa_context* ctx, const void* d_addre
   t->log_leaves = k;
   t->n_set = n;
   const uint64_t N = 1ull << k, nodes = 2 * N - 1;
-  ZK_HIP(hipMalloc(&t->d_levels, nodes * 32));
+  t->d_levels.alloc(nodes * 32);
   hipStream_t st = ctx->dev.lanes[0].stream;
   const PoseidonTables* prm = device_params(ctx);
-  char* lv = reinterpret_cast<char*>(t->d_levels);
-  try {
-    ZK_HIP(hipEventRecord(ctx->ev_a[0], st));
+  char* lv = t->d_levels.as<char>();
+  timed(ctx, st, kMsMerkleBuild, [&] {
     if (N > n) ZK_HIP(hipMemsetAsync(lv + n * 32, 0, (N - n) * 32, st));
     launch_hash(st, prm, d_addresses, d_balances, 1, n, lv);
     for (unsigned l = 0; l < k; l++) {
       const char* in = lv + level_offset(k, l) * 32;
       launch_hash(st, prm, in, in + 32, 2, N >> (l + 1), lv + level_offset(k, l + 1) * 32);
     }
-    ZK_HIP(hipEventRecord(ctx->ev_b[0], st));
-    ZK_HIP(hipStreamSynchronize(st));
-    ZK_HIP(hipGetLastError());
-    ZK_HIP(hipEventElapsedTime(&t->build_ms, ctx->ev_a[0], ctx->ev_b[0]));
-    ctx->ms[7] = t->build_ms;
-  } catch (...) {
-    (void)hipFree(t->d_levels);
-    throw;
-  }
+  });
   *out = t.release();
   ZK_API_END(ctx)
 }
@@ -380,7 +367,6 @@ extern "C" int zkpoa_merkle_build(zkpoa_context* ctx, const void* addresses, con
 extern "C" void zkpoa_merkle_free(zkpoa_context* ctx, zkpoa_merkle* tree) {
   if (!tree) return;
   if (ctx) (void)hipSetDevice(ctx->dev.device);
-  if (tree->d_levels) (void)hipFree(tree->d_levels);
   delete tree;
 }
 
@@ -396,7 +382,7 @@ extern "C" int zkpoa_merkle_root(zkpoa_context* ctx, const zkpoa_merkle* tree, u
   if (!tree || !root_le) return PROVER_ERROR;
   ZK_API_BEGIN(ctx)
   const uint64_t nodes = (2ull << tree->log_leaves) - 1;
-  ZK_HIP(hipMemcpy(root_le, reinterpret_cast<const char*>(tree->d_levels) + (nodes - 1) * 32, 32, hipMemcpyDeviceToHost));
+  ZK_HIP(hipMemcpy(root_le, tree->d_levels.as<const char>() + (nodes - 1) * 32, 32, hipMemcpyDeviceToHost));
   ZK_API_END(ctx)
 }
 
@@ -406,7 +392,7 @@ extern "C" int zkpoa_merkle_leaves(zkpoa_context* ctx, const zkpoa_merkle* tree,
   ZK_API_BEGIN(ctx)
   const uint64_t n_leaves = 1ull << tree->log_leaves;
   if (first > n_leaves || count > n_leaves - first) throw HipError("merkle: leaf range out of bounds");
-  ZK_HIP(hipMemcpy(out, reinterpret_cast<const char*>(tree->d_levels) + first * 32, count * 32, hipMemcpyDeviceToHost));
+  ZK_HIP(hipMemcpy(out, tree->d_levels.as<const char>() + first * 32, count * 32, hipMemcpyDeviceToHost));
   ZK_API_END(ctx)
 }
 
@@ -420,7 +406,7 @@ extern "C" int zkpoa_merkle_path(zkpoa_context* ctx, const zkpoa_merkle* tree, u
   if (leaf_index >> k) throw HipError("merkle: leaf index out of range");
   uint64_t i = leaf_index;
   for (unsigned l = 0; l < k; l++) {
-    const char* src = reinterpret_cast<const char*>(tree->d_levels) + (level_offset(k, l) + (i ^ 1)) * 32;
+    const char* src = tree->d_levels.as<const char>() + (level_offset(k, l) + (i ^ 1)) * 32;
     ZK_HIP(hipMemcpyAsync(path_le + 32 * l, src, 32, hipMemcpyDeviceToHost, ctx->dev.lanes[0].stream));
     if (path_indices) path_indices[l] = (uint8_t)(i & 1);
     i >>= 1;
@@ -435,7 +421,7 @@ extern "C" int zkpoa_merkle_find(zkpoa_context* ctx, zkpoa_merkle* tree, const v
   if (!tree || (m && (!leaf_hashes || !first || !count))) return PROVER_ERROR;
   ZK_API_BEGIN(ctx)
   // the padding leaves are not part of the keys: a zero hash is looked for among the set's own rows only
-  anon_set_find_indexed(ctx, tree->d_levels, tree->n_set, tree->leaf_index, leaf_hashes, m, first, count);
+  anon_set_find_indexed(ctx, tree->d_levels.get(), tree->n_set, tree->leaf_index, leaf_hashes, m, first, count);
   ZK_API_END(ctx)
 }
 
@@ -443,17 +429,12 @@ extern "C" int zkpoa_merkle_paths_device(zkpoa_context* ctx, const zkpoa_merkle*
                                          void* d_paths) {
   if (!tree || (m && (!d_leaf_index || !d_paths))) return PROVER_ERROR;
   ZK_API_BEGIN(ctx)
-  ctx->ms[10] = 0;
+  ctx->ms[kMsAnonFind] = 0;
   const unsigned k = tree->log_leaves;
   if (m >> 37 || m * k >> 37) throw HipError("merkle: at most 2^37 path elements in one call");
   if (m && k) {
     hipStream_t st = ctx->dev.lanes[0].stream;
-    ZK_HIP(hipEventRecord(ctx->ev_a[0], st));
-    launch_paths(st, tree, d_leaf_index, m, d_paths);
-    ZK_HIP(hipEventRecord(ctx->ev_b[0], st));
-    ZK_HIP(hipStreamSynchronize(st));
-    ZK_HIP(hipGetLastError());
-    ZK_HIP(hipEventElapsedTime(&ctx->ms[10], ctx->ev_a[0], ctx->ev_b[0]));
+    timed(ctx, st, kMsAnonFind, [&] { launch_paths(st, tree, d_leaf_index, m, d_paths); });
   }
   ZK_API_END(ctx)
 }
@@ -462,7 +443,7 @@ extern "C" int zkpoa_merkle_paths(zkpoa_context* ctx, const zkpoa_merkle* tree, 
                                   uint8_t* paths_le, uint8_t* path_indices) {
   if (!tree || (m && !leaf_index)) return PROVER_ERROR;
   ZK_API_BEGIN(ctx)
-  ctx->ms[10] = 0;
+  ctx->ms[kMsAnonFind] = 0;
   const unsigned k = tree->log_leaves;
   for (uint64_t i = 0; i < m; i++)   // before anything is launched
     if (leaf_index[i] >> k) throw HipError("merkle: leaf index out of range (entry " + std::to_string(i) + ")");
@@ -472,18 +453,15 @@ extern "C" int zkpoa_merkle_paths(zkpoa_context* ctx, const zkpoa_merkle* tree, 
     const uint64_t round = std::min(m, kRound);
     DevBuf d_index(round * 8), d_out(round * k * 32);
     hipStream_t st = ctx->dev.lanes[0].stream;
+    KernelTimer gather = KernelTimer::lane0(ctx, st);
     for (uint64_t i0 = 0; i0 < m; i0 += kRound) {
       const uint64_t cnt = std::min(kRound, m - i0);
       ZK_HIP(hipMemcpyAsync(d_index.p, leaf_index + i0, cnt * 8, hipMemcpyHostToDevice, st));
-      ZK_HIP(hipEventRecord(ctx->ev_a[0], st));
+      gather.start();
       launch_paths(st, tree, static_cast<const uint64_t*>(d_index.p), cnt, d_out.p);
-      ZK_HIP(hipEventRecord(ctx->ev_b[0], st));
+      gather.stop();
       ZK_HIP(hipMemcpyAsync(paths_le + i0 * k * 32, d_out.p, cnt * k * 32, hipMemcpyDeviceToHost, st));
-      ZK_HIP(hipStreamSynchronize(st));
-      ZK_HIP(hipGetLastError());
-      float ms = 0;
-      ZK_HIP(hipEventElapsedTime(&ms, ctx->ev_a[0], ctx->ev_b[0]));
-      ctx->ms[10] += ms;
+      gather.read(kMsAnonFind, true);   // the copy back is behind the stop: waited for, not timed
     }
     if (path_indices)
       for (uint64_t i = 0; i < m; i++)

@@ -177,7 +177,7 @@ int emit_outputs(zkpoa_context* ctx, const zkpoa_zkey* zk, const uint8_t pts[256
        "(%.0f MB, %.1f GB/s) | h-chain %.2f ms, msm phase %.2f ms, prove %.2f ms, self-check %.2f ms\n",
        zk->nVars, zk->nPublic, zk->power, (unsigned long long)zk->nCoefs, how, load_ms,
        load_ms > 0 ? (double)zkey_size / load_ms / 1e6 : 0.0, ctx->io_ms[0], ctx->io_ms[1],
-       ctx->io_ms[0] > 0 ? ctx->io_ms[1] / ctx->io_ms[0] : 0.0, ctx->ms[3], ctx->ms[4], ctx->ms[5], ctx->ms[6]);
+       ctx->io_ms[0] > 0 ? ctx->io_ms[1] / ctx->io_ms[0] : 0.0, ctx->ms[kMsChain], ctx->ms[kMsMsmPhase], ctx->ms[kMsProve], ctx->ms[kMsSelfCheck]);
   return rc;
 }
 
@@ -217,7 +217,7 @@ int load_and_prove_to_json(zkpoa_context* ctx, const uint8_t* zkey, uint64_t zke
     zk = load_prove_staged(ctx, zkey, zkey_size, w, parts, zkey_fd);
     if (zk) {
       assemble_proof(ctx, zk.get(), parts, bl.r, bl.s, t0, pts);
-      return check_and_emit(ctx, zk.get(), pts, w, out, ctx->ms[5], zkey_size, "load overlapped with the prove:");
+      return check_and_emit(ctx, zk.get(), pts, w, out, ctx->ms[kMsProve], zkey_size, "load overlapped with the prove:");
     }
   }
   zk = zkey_load_impl(ctx, zkey, zkey_size);
@@ -258,7 +258,7 @@ int multi_prove_to_json(DeviceSet* ds, MultiKey* mk, const WtnsSrc& wsrc, const 
   }
   vlog("zkpoa: one proof over %zu ranks: H-scalar chain %s, sections 5-8 %s, %.2f GB of fixed-base tables; prove %.2f ms\n",
        ds->ids.size(), mk->split ? "split (2 peer-to-peer exchanges)" : "replicated",
-       z0->bc_log ? "block-cyclic" : "contiguous ranges", mk->table_bytes / 1e9, c0->ms[5]);
+       z0->bc_log ? "block-cyclic" : "contiguous ranges", mk->table_bytes / 1e9, c0->ms[kMsProve]);
   return emit_outputs(c0, z0, pts, pubs, out, mk->load_ms, zkey_size, cache_hit ? "cached," : "sharded load");
 }
 

@@ -170,8 +170,7 @@ void query_compact(zkpoa_context* ctx, zkpoa_zkey* zk, CompactQuery& q, const vo
   } else {
     ZK_HIP(hipMemsetAsync(pos, 0, 4, st));
   }
-  ZK_HIP(hipStreamSynchronize(st));
-  ZK_HIP(hipGetLastError());
+  finish(st);
   q.res = total;
   const size_t cnt = total ? total : 1;
   q.g1.alloc(cnt * 64);
@@ -182,8 +181,7 @@ void query_compact(zkpoa_context* ctx, zkpoa_zkey* zk, CompactQuery& q, const vo
     hipLaunchKernelGGL(query_compact_kernel, dim3((n + 255) / 256), dim3(256), 0, st, (const uint4*)d1, (const uint4*)d2,
                        (const uint32_t*)pos, n, (uint32_t)zk->wbase, zk->bc_log, zk->bc_rank, zk->bc_world,
                        q.g1.as<uint4>(), q.g2.as<uint4>(), q.wire.as<uint32_t>());
-    ZK_HIP(hipStreamSynchronize(st));
-    ZK_HIP(hipGetLastError());
+    finish(st);
   }
   query_set_slice(zk, q);
 }
@@ -990,11 +988,12 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
     // witness values must be canonical (< r): one streaming pass on the chain's lane, flag read with the H MSM's results
     ZK_HIP(hipMemsetAsync(zk->d_flag.get(), 0, 4, l0.stream));
     range_check<FrParams>(l0.stream, zk->d_witness, zk->nVars, zk->d_flag.as<uint32_t>());
-    ZK_HIP(hipEventRecord(ctx->ev_a[5], l0.stream));
+    KernelTimer chain = KernelTimer::chain(ctx, l0.stream);
+    chain.start();
     if (!split)
       h_chain(ctx, l0.stream, zk->d_row_ptr.as<uint32_t>(), zk->d_sig.as<uint32_t>(), zk->d_vals.get(),
               zk->d_long.as<uint32_t>(), zk->n_long, zk->d_witness, zk->domain, zk->power, zk->d_abc.get());
-    ZK_HIP(hipEventRecord(ctx->ev_b[5], l0.stream));
+    chain.stop();
     if (stg && stg->prep_H) stg->prep_H();
     const StageView vH = stage_view(zk, kStageH);
     if (vH.n && !vH.bases) throw ProverError(PROVER_ERROR, "internal: H stage started before its inputs");
@@ -1002,7 +1001,7 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
     msm_run_g1(ctx, 0, vH.bases, zk->d_abc.as<const char>() + vH.scalar_off * 32, vH.n, outH, msm_ms[0],
                vH.table);
     if (split) zk->h_ready = false;
-    ZK_HIP(hipEventElapsedTime(&ctx->ms[3], ctx->ev_a[5], ctx->ev_b[5]));
+    chain.store(kMsChain);   // no wait of its own: the H MSM, later on the same stream, has returned
     msm_read_back(l0, zk->d_flag.get(), 4);   // lane 0 is idle (its MSM has returned): the flag through its pinned buffer
     witness_bad = *reinterpret_cast<const uint32_t*>(l0.pinned);
   } catch (...) {
@@ -1015,9 +1014,9 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
   for (SideTask* t : {&tA, &tB1, &tB2, &tC}) t->get();
   if (witness_bad) throw ProverError(PROVER_ERROR, "witness value is not a field element (>= r)");
   auto t1 = std::chrono::steady_clock::now();
-  ctx->ms[4] = std::chrono::duration<float, std::milli>(t1 - t0).count();
-  ctx->ms[0] = msm_ms[0][0];
-  ctx->ms[1] = msm_ms[0][1];
+  ctx->ms[kMsMsmPhase] = std::chrono::duration<float, std::milli>(t1 - t0).count();
+  ctx->ms[kMsMsm] = msm_ms[0][0];
+  ctx->ms[kMsMsmAccum] = msm_ms[0][1];
   for (int l = 0; l < 5; l++) {   // per-lane MSM timings (H, A, B1, B2, C): zkpoa_last_ms_lane
     ctx->lane_ms[l][0] = msm_ms[l][0];
     ctx->lane_ms[l][1] = msm_ms[l][1];
@@ -1059,11 +1058,11 @@ void prove_assemble(const HeaderPoints& h, const uint8_t sums[384], const uint8_
   h_affine_to_bytes<HFq>(h_to_affine(pi_c), proof_points + 192);
 }
 
-// the partial sums of a whole key -> proof points; ctx->ms[5] <- the prove time, counted from t0
+// the partial sums of a whole key -> proof points; ctx->ms[kMsProve] <- the prove time, counted from t0
 void assemble_proof(zkpoa_context* ctx, const zkpoa_zkey* zk, const uint8_t parts[384], const uint8_t* r_le,
                     const uint8_t* s_le, std::chrono::steady_clock::time_point t0, uint8_t proof_points[256]) {
   prove_assemble(zk->hdr, parts, r_le, s_le, proof_points);
-  ctx->ms[5] = (float)ms_since(t0);
+  ctx->ms[kMsProve] = (float)ms_since(t0);
 }
 
 // unsharded prove = partials of the whole key + assembly
@@ -1095,17 +1094,17 @@ struct SelfCheckFailed : ProverError {   // the proof was computed and does not 
 // exchange buffer can only show from the second proof on)
 void selfcheck(zkpoa_context* ctx, const zkpoa_zkey* zk, const uint8_t proof_points[256], const uint8_t* public_le,
                uint64_t first_n = 1) {
-  ctx->ms[6] = 0;
+  ctx->ms[kMsSelfCheck] = 0;
   const int mode = selfcheck_mode();
   if (mode == 0 || zk->vkey_points.empty() || (mode == 1 && zk->selfchecks_done >= first_n)) return;
   auto t0 = std::chrono::steady_clock::now();
   char msg[256] = {0};
   int rc = zkpoa_groth16_verify_points(zk->vkey_points.data(), (unsigned long)zk->vkey_points.size(), proof_points,
                                        public_le, zk->nPublic, msg, sizeof(msg));
-  ctx->ms[6] = (float)ms_since(t0);
+  ctx->ms[kMsSelfCheck] = (float)ms_since(t0);
   if (rc == PROVER_OK) {
     zk->selfchecks_done++;
-    vlog("zkpoa: self-check: proof verifies against the zkey's own verification key (%.1f ms)\n", ctx->ms[6]);
+    vlog("zkpoa: self-check: proof verifies against the zkey's own verification key (%.1f ms)\n", ctx->ms[kMsSelfCheck]);
     return;
   }
   if (rc == ZKPOA_VERIFY_INVALID_PROOF)
@@ -1415,8 +1414,7 @@ extern "C" int zkpoa_zkey_set_shard_split(zkpoa_context* ctx, zkpoa_zkey* zkey, 
     queries_set_slice(zkey);
     set_split(zkey, rank, world);
     ntt_prepare(ctx, st, zkey->power - zkey->split_log);
-    ZK_HIP(hipStreamSynchronize(st));
-    ZK_HIP(hipGetLastError());
+    finish(st);
   });
 }
 
@@ -1487,8 +1485,7 @@ extern "C" void* zkpoa_context_stream(zkpoa_context* ctx, int lane) {
 extern "C" int zkpoa_context_synchronize(zkpoa_context* ctx) {
   if (!ctx) return PROVER_ERROR;
   return abi_call(ctx, [&] {
-    ZK_HIP(hipStreamSynchronize(ctx->dev.lanes[0].stream));
-    ZK_HIP(hipGetLastError());
+    finish(ctx->dev.lanes[0].stream);
   });
 }
 
@@ -1688,20 +1685,16 @@ extern "C" int zkpoa_h_scalars(zkpoa_context* ctx, const void* coeffs, unsigned 
     if (coeffs_size != 4 + ncoef * 44) throw ProverError(PROVER_ERROR, "h_scalars: coefficient payload has the wrong size");
     const uint32_t domain = 1u << log_domain;
     hipStream_t st = ctx->dev.lanes[0].stream;
-    DevBuf recs(ncoef * 44), abc((size_t)3 * domain * 32), wit(n_vars * 32);
-    ZK_HIP(hipMemcpy(recs.p, cb + 4, ncoef * 44, hipMemcpyHostToDevice));
-    ZK_HIP(hipMemcpy(wit.p, witness, n_vars * 32, hipMemcpyHostToDevice));
+    LaneIn recs(cb + 4, 44, ncoef), wit(witness, 32, n_vars);
+    DevBuf abc((size_t)3 * domain * 32);
     AbcCsr csr;
-    abc_build_csr(st, recs.p, ncoef, domain, (uint32_t)n_vars, 0u, 0u, csr);
+    abc_build_csr(st, recs.at<void>(0), ncoef, domain, (uint32_t)n_vars, 0u, 0u, csr);
     if (csr.err) throw ProverError(PROVER_ERROR, "h_scalars: coefficient record out of range or value >= r");
     ntt_prepare(ctx, st, log_domain);
-    ZK_HIP(hipEventRecord(ctx->ev_a[5], st));
-    h_chain(ctx, st, csr.row_ptr.as<uint32_t>(), csr.sig.as<uint32_t>(), csr.vals.get(), csr.long_list.as<uint32_t>(), csr.n_long,
-            wit.p, domain, log_domain, abc.p);
-    ZK_HIP(hipEventRecord(ctx->ev_b[5], st));
-    ZK_HIP(hipStreamSynchronize(st));
-    ZK_HIP(hipGetLastError());
-    ZK_HIP(hipEventElapsedTime(&ctx->ms[3], ctx->ev_a[5], ctx->ev_b[5]));
+    timed(ctx, st, kMsChain, [&] {
+      h_chain(ctx, st, csr.row_ptr.as<uint32_t>(), csr.sig.as<uint32_t>(), csr.vals.get(), csr.long_list.as<uint32_t>(), csr.n_long,
+              wit.at<void>(0), domain, log_domain, abc.p);
+    });
     ZK_HIP(hipMemcpy(out, abc.p, (size_t)domain * 32, hipMemcpyDeviceToHost));
   });
 }

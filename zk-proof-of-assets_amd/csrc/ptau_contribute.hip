@@ -524,8 +524,7 @@ extern "C" int zkpoa_scalar_mul_each_device(zkpoa_context* ctx, int group, const
   DevBuf flag(64), scratch(scalar_mul_each_scratch(group, n, slab));
   ZK_HIP(hipMemsetAsync(flag.p, 0, 64, ctx->dev.lanes[0].stream));
   scalar_mul_each(ctx, group, d_points, d_scalars, n, d_out, (uint32_t*)flag.p, scratch.p, slab);
-  ZK_HIP(hipStreamSynchronize(ctx->dev.lanes[0].stream));
-  ZK_HIP(hipGetLastError());
+  finish(ctx->dev.lanes[0].stream);
   uint32_t bad = 0;
   ZK_HIP(hipMemcpy(&bad, flag.p, 4, hipMemcpyDeviceToHost));
   if (bad) throw SetupError("scalar_mul_each: a scalar is not below r");
@@ -537,8 +536,7 @@ extern "C" int zkpoa_power_scalars_device(zkpoa_context* ctx, const uint8_t firs
   ZK_API_BEGIN(ctx)
   if (!first_le || !ratio_le || (n && !d_out)) throw SetupError("power scalars: null argument");
   power_scalars(ctx, first_le, ratio_le, i0, n, d_out);
-  ZK_HIP(hipStreamSynchronize(ctx->dev.lanes[0].stream));
-  ZK_HIP(hipGetLastError());
+  finish(ctx->dev.lanes[0].stream);
   ZK_API_END(ctx)
 }
 

@@ -100,8 +100,7 @@ extern "C" int zkpoa_ec_intt_device(zkpoa_context* ctx, int group, const void* d
   std::unique_ptr<EcNttWork> wk(group == 2 ? ec_intt_work_g2(ctx, log_n) : ec_intt_work_g1(ctx, log_n));
   if (group == 2) ec_intt_g2(ctx, *wk, d_in, log_n, d_out);
   else ec_intt_g1(ctx, *wk, d_in, log_n, d_out);
-  ZK_HIP(hipStreamSynchronize(ctx->dev.lanes[0].stream));
-  ZK_HIP(hipGetLastError());
+  finish(ctx->dev.lanes[0].stream);
   ZK_API_END(ctx)
 }
 

@@ -37,6 +37,8 @@ extern "C" int zkpoa_context_create(int device, zkpoa_context** out, char* error
       ZK_HIP(hipEventCreate(&c->ev_a[i]));
       ZK_HIP(hipEventCreate(&c->ev_b[i]));
     }
+    ZK_HIP(hipEventCreate(&c->ev_chain_a));
+    ZK_HIP(hipEventCreate(&c->ev_chain_b));
   } catch (const std::exception& e) {
     set_err(error_msg, error_msg_maxsize, e.what());
     delete c;
@@ -55,6 +57,8 @@ extern "C" void zkpoa_context_destroy(zkpoa_context* ctx) {
     if (ctx->ev_a[i]) (void)hipEventDestroy(ctx->ev_a[i]);
     if (ctx->ev_b[i]) (void)hipEventDestroy(ctx->ev_b[i]);
   }
+  for (hipEvent_t e : {ctx->ev_chain_a, ctx->ev_chain_b})
+    if (e) (void)hipEventDestroy(e);
   ntt_release(ctx);
   poseidon_release(ctx);
   ctx->dev.join_background();   // it may still be adding the uploader's streams
@@ -68,7 +72,7 @@ extern "C" const char* zkpoa_last_error(const zkpoa_context* ctx) {
 }
 
 extern "C" float zkpoa_last_ms(const zkpoa_context* ctx, int id) {
-  if (!ctx || id < 0 || id >= 11) return -1.f;
+  if (!ctx || id < 0 || id >= kMsCount) return -1.f;
   return ctx->ms[id];
 }
 

@@ -26,13 +26,24 @@ typedef std::unique_ptr<MsmTable, MsmTableFree> MsmTablePtr;
 
 struct zkpoa_poseidon_state;   // poseidon.hip: device copy of the Poseidon parameters
 
+namespace zkpoa {
+// The slots of zkpoa_context::ms: the ids of zkpoa_last_ms, 0 to 10 in this order. The ids are ABI and do not move, and
+// include/zkpoa_prover.h says what each holds: a new slot goes before kMsCount, and into that comment.
+enum MsSlot : int {
+  kMsMsm, kMsMsmAccum, kMsNtt, kMsChain, kMsMsmPhase, kMsProve, kMsSelfCheck, kMsMerkleBuild, kMsLaneBatch, kMsAnonIndex,
+  kMsAnonFind, kMsCount
+};
+// an MSM fills {whole, accumulation} through one `float* ms2` (msm_run.hip.h), which for the context is `ms` itself
+static_assert(kMsMsm == 0 && kMsMsmAccum == 1, "msm_run's ms2 = ctx->ms needs the two MSM slots first and adjacent");
+}  // namespace zkpoa
+
 struct zkpoa_context {
   zkpoa::DeviceCtx dev;
   zkpoa_poseidon_state* poseidon = nullptr;
   zkpoa::NttEngine* ntt = nullptr;
   zkpoa::FastUploader uploader;   // pinned, multi-threaded host -> HBM path for zkey sections / witnesses
   std::string last_error;
-  float ms[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  float ms[zkpoa::kMsCount] = {};   // zkpoa_last_ms, by MsSlot
   float io_ms[2] = {0, 0};   // last prove from a host buffer: [0] witness -> HBM (host clock), [1] its bytes / 1e6
   float lane_ms[zkpoa::DeviceCtx::kLanes][2] = {};   // per-lane {whole MSM, accumulation kernel} of the last MSM
   double lane_adds[zkpoa::DeviceCtx::kLanes] = {};   // per-lane mixed additions of that kernel (non-zero digits)
@@ -75,8 +86,11 @@ struct zkpoa_context {
   // split chain: the witness copy of zkpoa_split_stage1 is enqueued on lane 0; the other lanes' MSMs wait for it
   hipEvent_t ev_witness = nullptr;
   bool ev_witness_set = false;
+  // start / stop event of every lane: an MSM on lane l records pair l, a one-shot entry point pair 0 (KernelTimer)
   hipEvent_t ev_a[zkpoa::DeviceCtx::kLanes] = {};
   hipEvent_t ev_b[zkpoa::DeviceCtx::kLanes] = {};
+  // the H chain's own pair: a prove reads it after the H MSM, which has recorded lane 0's pair again by then
+  hipEvent_t ev_chain_a = nullptr, ev_chain_b = nullptr;
 };
 
 struct zkpoa_msm_table {   // C-ABI handle of a fixed-base table (zkpoa_msm_table_build)
@@ -173,6 +187,94 @@ struct DevBuf {  // a call's temporary device allocation: parked in the thread's
     if (bytes) ZK_HIP(hipMemcpy(static_cast<char*>(p) + at, src, bytes, hipMemcpyHostToDevice));
   }
 };
+
+// ---- the shape of a one-shot entry point ------------------------------------------------------------------------------
+// The caller's arrays onto the device (LaneIn; LaneOut for results), the launches on lane 0's stream over
+// blocks_of(n, threads) workgroups -- inside timed() when the call reports its kernel time --, finish(), down().
+// Large pageable inputs go through ctx->uploader into a DevBuf instead: LaneIn is the plain blocking copy.
+inline uint32_t blocks_of(uint64_t lanes, uint32_t threads) { return (uint32_t)((lanes + threads - 1) / threads); }
+
+inline void finish(hipStream_t st) {
+  ZK_HIP(hipStreamSynchronize(st));
+  ZK_HIP(hipGetLastError());
+}
+
+// One array of a call on the device: n items of `each` bytes, which is said here and nowhere else. Buf is DevBuf, or
+// lane_batch.hip.h's SecretBuf (with its stream as the last argument) for keys and nonces.
+template <class Buf>
+struct LaneArray {
+  Buf buf;
+  size_t each;
+  uint64_t n;
+  template <class... A>
+  LaneArray(size_t each_, uint64_t n_, A... a) : buf(each_ * n_, a...), each(each_), n(n_) {}
+  template <class T>
+  T* at(uint64_t i0) const {   // item i0, where a launch over the items from i0 on begins
+    return reinterpret_cast<T*>(static_cast<char*>(buf.p) + each * i0);
+  }
+};
+// uploaded from the caller's array. An operand the call does not use is given n = 0: nothing is read from `host`,
+// which may then be null, and at(0) is still a pointer into device memory.
+template <class Buf = DevBuf>
+struct LaneIn : LaneArray<Buf> {
+  template <class... A>
+  LaneIn(const void* host, size_t each_, uint64_t n_, A... a) : LaneArray<Buf>(each_, n_, a...) {
+    this->buf.up(host, each_ * n_);
+  }
+};
+template <class Buf = DevBuf>
+struct LaneOut : LaneArray<Buf> {   // down() copies it into the caller's array
+  void* host;
+  template <class... A>
+  LaneOut(void* host_, size_t each_, uint64_t n_, A... a) : LaneArray<Buf>(each_, n_, a...), host(host_) {}
+  void down() const { ZK_HIP(hipMemcpy(host, this->buf.p, this->each * this->n, hipMemcpyDeviceToHost)); }
+};
+template <class Buf = DevBuf>
+struct LaneInOut : LaneOut<Buf> {   // transformed in place: uploaded from the caller's array, and down() copies it back
+  template <class... A>
+  LaneInOut(void* host_, size_t each_, uint64_t n_, A... a) : LaneOut<Buf>(host_, each_, n_, a...) {
+    this->buf.up(host_, each_ * n_);
+  }
+};
+
+// launch(i0, m) for the items i0 .. i0 + m - 1, at most `slab` of them at a time
+template <class Fn>
+void for_slabs(uint64_t n, uint64_t slab, Fn launch) {
+  for (uint64_t i0 = 0; i0 < n; i0 += slab) launch(i0, std::min(slab, n - i0));
+}
+
+// The kernel time of a call, into a slot of zkpoa_context::ms: start(), the launches, stop(), then read(), which waits
+// for the stream, checks the last error and sets the slot (add: adds to what it holds). Only what lies between start()
+// and stop() is timed; more may be enqueued between stop() and read(). A call that can return before its launches sets
+// its slot to 0 first. One timer per event pair at a time.
+struct KernelTimer {
+  zkpoa_context* ctx;
+  hipStream_t st;
+  hipEvent_t a, b;
+  static KernelTimer lane0(zkpoa_context* ctx, hipStream_t st) { return {ctx, st, ctx->ev_a[0], ctx->ev_b[0]}; }
+  static KernelTimer chain(zkpoa_context* ctx, hipStream_t st) { return {ctx, st, ctx->ev_chain_a, ctx->ev_chain_b}; }
+  void start() { ZK_HIP(hipEventRecord(a, st)); }
+  void stop() { ZK_HIP(hipEventRecord(b, st)); }
+  // read() without the wait and the check, for a caller that has waited for later work of the stream by other means
+  void store(MsSlot slot, bool add = false) {
+    float ms = 0;
+    ZK_HIP(hipEventElapsedTime(&ms, a, b));
+    ctx->ms[slot] = add ? ctx->ms[slot] + ms : ms;
+  }
+  void read(MsSlot slot, bool add = false) {
+    finish(st);
+    store(slot, add);
+  }
+};
+// the common case: nothing between the launches and the wait
+template <class Fn>
+void timed(zkpoa_context* ctx, hipStream_t st, MsSlot slot, Fn launches, bool add = false) {
+  KernelTimer t = KernelTimer::lane0(ctx, st);
+  t.start();
+  launches();
+  t.stop();
+  t.read(slot, add);
+}
 
 
 // per-group entry points, each compiled in its own translation unit (msm_g1.hip, msm_g2.hip, ...)
@@ -283,7 +385,7 @@ void ntt_split_mid(zkpoa_context* ctx, hipStream_t st, const void* in, void* out
 void ntt_release(zkpoa_context* ctx);
 void poseidon_release(zkpoa_context* ctx);
 // anon_set.hip: host queries (m x 32 B) looked up among n keys on the device through their stable index, which is built
-// into `perm` first when that is still empty; first, count: host, m words. ms[10] <- the kernels' time.
+// into `perm` first when that is still empty; first, count: host, m words. ms[kMsAnonFind] <- the kernels' time.
 void anon_set_find_indexed(zkpoa_context* ctx, const void* d_keys, uint64_t n, DevMem& perm, const void* queries, uint64_t m,
                            uint32_t* first, uint32_t* count);
 }  // namespace zkpoa
