@@ -657,12 +657,18 @@ int zkpoa_eth_address(zkpoa_context* ctx, const void* pubkey_xy, uint64_t n, voi
  * point above copies 32 bytes per level: four entry points, declared in a header of their own next to this one. */
 #include "zkpoa_merkle_paths.h"
 
+/* ---- the anonymity set against an Ethereum state root: Merkle-Patricia account proofs (what `eth_getProof` returns)
+ * hashed and walked on the device, a block header's hash and state root, and the whole check of a set's balances
+ * against a file of such proofs: four entry points, declared in a header of their own next to this one. */
+#include "zkpoa_state_proof.h"
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* Timings (ms, HIP events on the stream that ran the kernels) of the last call on this context.
  * id: 0 = whole device part of last MSM, 1 = its bucket-accumulation kernel (dominant kernel),
  *     2 = last NTT, 3 = last prove: ABC+NTT chain, 4 = last prove: all MSMs, 5 = last prove: total,
  *     6 = last prove: self-check (host pairing check; 0 when it did not run), 7 = last Merkle tree build,
- *     8 = last zkpoa_ecdsa_star, zkpoa_ecdsa_sign, zkpoa_bip32_children or zkpoa_bip32_tweak: its kernels,
+ *     8 = last zkpoa_ecdsa_star, zkpoa_ecdsa_sign, zkpoa_bip32_children, zkpoa_bip32_tweak, zkpoa_mpt_verify or
+ *         zkpoa_eth_account_proofs: its kernels (after zkpoa_anon_set_state_check_file: those of all its slabs),
  *     9 = last zkpoa_anon_set_index_device or zkpoa_anon_set_audit: its kernels,
  *     10 = last zkpoa_anon_set_find_device, zkpoa_merkle_find, zkpoa_merkle_paths or zkpoa_merkle_paths_device: its kernels.
  * Also: tuning knobs. key "msm_c" forces the Pippenger window (0 = auto); key "msm_max_points" sets the

@@ -50,6 +50,34 @@ class AssetsReport(ctypes.Structure):
                 ("duplicate_rows", ctypes.c_uint64), ("first_dup", ctypes.c_uint64 * 2), ("ascending", ctypes.c_int)]
 
 
+ASSETS_STATE = 0x10                     # include/zkpoa_state_proof.h: the set against an Ethereum state root
+MPT_KEY32, MPT_ADDRESS20 = 0, 1         # Context.mpt_verify's key kinds
+MPT_STATUS = ("present", "absent", "no nodes", "hash", "rlp", "child", "short", "long", "hex-prefix", "account")
+
+
+class StateReport(ctypes.Structure):
+    """zkpoa_state_report of include/zkpoa_state_proof.h"""
+    _fields_ = [("rows", ctypes.c_uint64), ("proven_present", ctypes.c_uint64), ("proven_absent", ctypes.c_uint64),
+                ("rows_without_proof", ctypes.c_uint64), ("rows_failed", ctypes.c_uint64), ("rows_differ", ctypes.c_uint64),
+                ("proofs_read", ctypes.c_uint64), ("proofs_not_in_set", ctypes.c_uint64), ("first_bad_row", ctypes.c_uint64),
+                ("first_bad_kind", ctypes.c_uint32), ("first_bad_status", ctypes.c_uint32), ("first_bad_where", ctypes.c_uint32),
+                ("first_diff_absent", ctypes.c_uint32), ("first_diff_row", ctypes.c_uint64),
+                ("first_diff_chain_balance32", ctypes.c_uint8 * 32), ("kernel_ms", ctypes.c_float)]
+
+
+def _node_args(nodes, node_offset, node_length, first_node):
+    """The node arguments of include/zkpoa_state_proof.h from bytes and three integer sequences -> (ctypes arguments,
+    keepalives)"""
+    import numpy as np
+    off = np.ascontiguousarray(node_offset, dtype=np.uint64)
+    length = np.ascontiguousarray(node_length, dtype=np.uint32)
+    first = np.ascontiguousarray(first_node, dtype=np.uint64)
+    pn, kn = _buf(bytes(nodes) if len(nodes) else b"\0")
+    as_ptr = lambda a, t: a.ctypes.data_as(ctypes.POINTER(t))
+    return ((pn, len(nodes), as_ptr(off, ctypes.c_uint64), as_ptr(length, ctypes.c_uint32), as_ptr(first, ctypes.c_uint64)),
+            (kn, off, length, first))
+
+
 class Context:
     """A device context (one GPU). Raises if no HIP device is usable."""
 
@@ -298,6 +326,60 @@ class Context:
             "duplicate_rows": int(rep.duplicate_rows),
             "first_dup": (int(rep.first_dup[0]), int(rep.first_dup[1])) if rep.duplicate_rows else None,
             "ascending": bool(rep.ascending)}
+
+    # ---- the set against an Ethereum state root (include/zkpoa_state_proof.h) ------------------------------------------
+    def mpt_verify(self, keys, root, nodes, node_offset, node_length, first_node, key_kind=MPT_KEY32):
+        """Merkle-Patricia proofs of n keys (n x 32 B, or n x 20 B addresses with key_kind=MPT_ADDRESS20) under `root`:
+        the nodes in one 8-aligned blob with their offsets and lengths, first_node[i] .. first_node[i + 1] those of item
+        i, root first -> (status bytes, where: numpy uint32, value spans: numpy uint64 [n, 2] = offset into nodes, length)."""
+        import numpy as np
+        n = len(first_node) - 1
+        if len(keys) != n * (20 if key_kind == MPT_ADDRESS20 else 32) or len(root) != 32:
+            raise ZkpoaError("mpt_verify: the keys and first_node do not describe the same number of items")
+        args, keep = _node_args(nodes, node_offset, node_length, first_node)
+        status, where, span = _Out(n), np.zeros(max(n, 1), dtype=np.uint32), np.zeros((max(n, 1), 2), dtype=np.uint64)
+        self._check(lib().zkpoa_mpt_verify(self._h, n, _buf(bytes(keys) or b"\0")[0], key_kind, bytes(root), *args, status,
+                                           where.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                           span.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))), "zkpoa_mpt_verify")
+        return status.bytes(), where[:n], span[:n]
+
+    def eth_account_proofs(self, addresses, root, nodes, node_offset, node_length, first_node, with_hashes=True):
+        """Account proofs (what eth_getProof returns) of n x 20 B addresses under a state root -> (status bytes, where,
+        nonces: numpy uint64, balances n x 32 B big-endian, storage roots, code hashes (n x 32 B each, None without
+        with_hashes)); all zero unless the status is 0."""
+        import numpy as np
+        n = len(first_node) - 1
+        if len(addresses) != 20 * n or len(root) != 32:
+            raise ZkpoaError("eth_account_proofs: the addresses and first_node do not describe the same number of items")
+        args, keep = _node_args(nodes, node_offset, node_length, first_node)
+        status, where, nonce = _Out(n), np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint64)
+        balance, sroot, code = _Out(32 * n), _Out(32 * n) if with_hashes else None, _Out(32 * n) if with_hashes else None
+        self._check(lib().zkpoa_eth_account_proofs(self._h, n, _buf(bytes(addresses) or b"\0")[0], bytes(root), *args, status,
+                                                   where.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                                   nonce.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), balance, sroot, code),
+                    "zkpoa_eth_account_proofs")
+        return (status.bytes(), where[:n], nonce[:n], balance.bytes(), sroot.bytes() if with_hashes else None,
+                code.bytes() if with_hashes else None)
+
+    def anon_set_state_check(self, addresses, balances, proofs_path, root, unit_divisor=1, n=None):
+        """The whole check of a set (host buffers, n x 32 B LE each) against a JSON Lines file of eth_getProof results
+        under a state root -> a dict of zkpoa_state_report's fields, with "ok": every row has a valid proof that gives
+        its balance. Raises only for an unreadable or malformed file."""
+        n = len(addresses) // 32 if n is None else n
+        pa, ka = _buf(addresses if len(addresses) else b"\0")
+        pb, kb = _buf(balances if len(balances) else b"\0")
+        rep = StateReport()
+        self._check(lib().zkpoa_anon_set_state_check_file(self._h, pa, pb, n, os.fsencode(proofs_path), bytes(root), unit_divisor,
+                                                          ctypes.addressof(rep)), "zkpoa_anon_set_state_check_file")
+        none = (1 << 64) - 1
+        out = {name: int(getattr(rep, name)) for name, _ in StateReport._fields_[:8]}
+        out.update(ok=rep.first_bad_row == none, first_bad_row=None if rep.first_bad_row == none else int(rep.first_bad_row),
+                   first_bad_kind=int(rep.first_bad_kind), first_bad_status=int(rep.first_bad_status),
+                   first_bad_where=int(rep.first_bad_where), first_diff_absent=bool(rep.first_diff_absent),
+                   first_diff_row=None if rep.first_diff_row == none else int(rep.first_diff_row),
+                   first_diff_chain_balance=int.from_bytes(bytes(rep.first_diff_chain_balance32), "big"),
+                   kernel_ms=float(rep.kernel_ms))
+        return out
 
     def msm_table(self, group, d_bases, n, window_bits=0):
         """Fixed-base table over n device-resident bases (group 1 = G1, 2 = G2) -> MsmTable."""
@@ -877,6 +959,14 @@ def groth16_verify(vkey_json, public_json, proof_json):
     if rc == 0x10:
         return False
     raise ZkpoaError("zkpoa_groth16_verify: " + err.value.decode())
+
+
+def eth_block_header(rlp):
+    """A block header's RLP -> (its hash, the state root, the number); host only. ZkpoaError for what is no header."""
+    h, root, number = _Out(32), _Out(32), ctypes.c_uint64(0)
+    if lib().zkpoa_eth_block_header(bytes(rlp) or None, len(rlp), h, root, ctypes.byref(number)) != PROVER_OK:
+        raise ZkpoaError("zkpoa_eth_block_header: not the RLP of a block header")
+    return h.bytes(), root.bytes(), int(number.value)
 
 
 def export_vkey(zkey_bytes):

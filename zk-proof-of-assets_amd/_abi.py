@@ -212,6 +212,15 @@ MERKLE_PATHS_SIGNATURES = {
     "zkpoa_merkle_paths_device":       "i: p p p u64 p",
 }
 
+# every symbol include/zkpoa_state_proof.h declares (zkpoa_prover.h includes that header too): the set against an
+# Ethereum state root; the third is host only and without a context, the others run on the GPU
+STATE_PROOF_SIGNATURES = {
+    "zkpoa_mpt_verify":                "i: p u64 p i p p u64 u64* u32* u64* p u32* u64*",
+    "zkpoa_eth_account_proofs":        "i: p u64 p p p u64 u64* u32* u64* p u32* u64* p p p",
+    "zkpoa_eth_block_header":          "i: p u64 p p u64*",
+    "zkpoa_anon_set_state_check_file": "i: p p p u64 s p u64 p",
+}
+
 # the one symbol include/zkpoa_secp_prim.h declares (zkpoa_prover.h includes that header beside its other test hooks)
 SECP_PRIM_SIGNATURES = {
     "zkpoa_secp_prim":                 "i: p i p p u64",
@@ -250,7 +259,7 @@ def lib():
             pass
         L = ctypes.CDLL(LIB_PATH)
         for table in (SIGNATURES, LAYER_INPUT_SIGNATURES, SIGN_SIGNATURES, HD_SIGNATURES, AUDIT_SIGNATURES,
-                      MERKLE_PATHS_SIGNATURES, SECP_PRIM_SIGNATURES, HOOK_SIGNATURES):
+                      MERKLE_PATHS_SIGNATURES, STATE_PROOF_SIGNATURES, SECP_PRIM_SIGNATURES, HOOK_SIGNATURES):
             for name, spec in table.items():
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = signature(spec)

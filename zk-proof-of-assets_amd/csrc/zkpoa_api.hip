@@ -99,6 +99,11 @@ extern "C" int zkpoa_set_option(zkpoa_context* ctx, const char* key, long value)
     ctx->opt_ptau_mul_slab = value;
     return PROVER_OK;
   }
+  if (!strcmp(key, "state_proof_slab")) {    // tests: several slabs of zkpoa_mpt_verify at a small size
+    if (value < 0) return PROVER_ERROR;
+    ctx->opt_state_proof_slab = value;
+    return PROVER_OK;
+  }
   if (!strcmp(key, "msm_k0")) {           // experiments: level-0 piece length of the bucket accumulation
     ctx->opt_msm_k0 = (int)value;
     return PROVER_OK;

@@ -52,6 +52,7 @@ struct zkpoa_context {
   long opt_msm_max_points = 0;   // 0 = default (2^27): larger MSMs run in chunks
   long opt_ptau_piece_points = 0;   // powersoftau contribute / beacon: points per piece; 0 = derived from free HBM
   long opt_ptau_mul_slab = 0;       // scalar_mul_each: points per launch; 0 = 2^20 (tests: cross a slab border at a small size)
+  long opt_state_proof_slab = 0;    // zkpoa_mpt_verify and its kin: items per slab; 0 = 2^20 (tests: the same)
   // Set when a lane's workspace for a whole MSM did not fit in HBM (found out by a failed reservation: msm_run, or
   // ahead of a proof: prover.hip budget_lane_workspaces): from then on the MSMs of that lane take at most this many
   // points at a time (never below 2^16); 0 = no limit of this kind.
