@@ -1,6 +1,7 @@
 // Device context shared by the MSM / NTT / ABC stages: one HIP device, a set of streams, and a
 // grow-only workspace arena per stream so that no hipMalloc happens inside a timed step.
 #pragma once
+#include "device_handles.hpp"
 #include "options.hpp"
 
 #include <hip/hip_runtime.h>
@@ -21,27 +22,15 @@
 
 namespace zkpoa {
 
-struct HipError : std::runtime_error {
-  explicit HipError(const std::string& s) : std::runtime_error(s) {}
-};
-
 // a lane's workspace did not fit: the MSM drivers answer by working through the points in smaller pieces (msm_run)
 struct OomError : HipError {
   explicit OomError(const std::string& s) : HipError(s) {}
 };
 
-#define ZK_HIP(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t _e = (expr);                                                                       \
-    if (_e != hipSuccess)                                                                         \
-      throw ::zkpoa::HipError(std::string(#expr) + " failed: " + hipGetErrorString(_e) + " at " + \
-                              __FILE__ + ":" + std::to_string(__LINE__));                         \
-  } while (0)
-
 // Grow-only bump arena. reset() rewinds; take() never frees, it reallocates when too small
 // (only legal while nothing is in flight on the owning stream -> callers reserve() up front).
 struct Arena {
-  char* base = nullptr;
+  DevMem base;
   size_t cap = 0;
   size_t off = 0;
   size_t limit = 0;   // 0 = whatever HBM holds; else reserve() refuses more than this (option lane_workspace_max_mb)
@@ -60,13 +49,11 @@ struct Arena {
         throw OomError("workspace of " + std::to_string(bytes >> 20) + " MiB would take HBM the key still being loaded needs (" +
                        std::to_string(keep >> 20) + " MiB to come, " + std::to_string(free_b >> 20) + " MiB free)");
     }
-    if (base) ZK_HIP(hipFree(base));
-    base = nullptr;
+    base.reset();
     cap = off = 0;   // (a failed allocation below must not leave a capacity without memory behind it)
     guards.clear();
-    const hipError_t e = hipMalloc(&base, bytes);
+    const hipError_t e = base.try_alloc(bytes);
     if (e == hipErrorOutOfMemory) {
-      base = nullptr;
       (void)hipGetLastError();   // the error is reported by the exception, not left behind for the next launch check
       throw OomError("workspace of " + std::to_string(bytes >> 20) + " MiB: out of device memory");
     }
@@ -99,33 +86,33 @@ struct Arena {
   T* take(size_t count, const char* name = "", int idx = -1) {
     const size_t exact = count * sizeof(T), bytes = span(exact, guard);
     if (off + bytes > cap) throw HipError("arena overflow (reserve() too small)");
-    T* p = reinterpret_cast<T*>(base + off);
+    T* p = reinterpret_cast<T*>(base.as<char>() + off);
     if (guard) guards.push_back(Guard{off + exact, bytes - exact, name, idx});
     off += bytes;
     return p;
   }
-  void release() {
-    if (base) (void)hipFree(base);
-    base = nullptr;
+  // the prover hands a lane's workspace back ahead of a key's tables, or to size it anew: limit and hold_back stay
+  void give_back() {
+    base.reset();
     cap = off = 0;
     guards.clear();
   }
 };
 
 struct Lane {  // one stream + its workspace + a pinned host staging area for small read-backs
-  hipStream_t stream = nullptr;
+  DevStream stream;
   Arena ws;
-  void* pinned = nullptr;
-  void* pinned_dev = nullptr;   // the same memory as kernels address it (read-backs are written by a kernel, not copied)
-  size_t pinned_cap = 0;
+  PinnedMem pinned;        // mapped to the device: read-backs are written by a kernel, not copied
+  size_t pinned_cap = 0;   // read-backs use [0, pinned_cap) of it; the fault word sits behind them
   // host copy of an MSM's read-back (the per-bit totals of its bucket reduction), owned by the lane: a fresh
   // 256 KB buffer per call would be an mmap + munmap each time, and unmapping is slow in a process whose address
   // space the GPU driver watches (measured: 11 % of the six-in-flight 2^20 MSM rate)
   std::vector<char> host_sums;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  DevEvent ev0, ev1;     // the accumulation kernel of an MSM on this lane
+  DevEvent ev_a, ev_b;   // a whole MSM on this lane; lane 0's pair also times the one-shot entry points (KernelTimer)
   // scratch of the single-launch scans (msm.hip.h scan_pair): status words + ticket counters, cleared only when
   // (re)allocated -- every call stamps its words with the next generation number
-  void* scan_scratch = nullptr;
+  DevMem scan_scratch;
   uint32_t scan_tiles = 0, scan_gen = 0;
   // The look-back of scan_pair waits for words other workgroups publish: a wait that can never end (an ordering mistake
   // on the host side, a wiped scratch) must surface as an error, not as a hung GPU. After scan_poll_limit polls of one
@@ -134,35 +121,33 @@ struct Lane {  // one stream + its workspace + a pinned host staging area for sm
   // scan_test_withhold (tests only, zkpoa_set_option): tile 0 never publishes its prefix.
   uint32_t scan_poll_limit = 1u << 24, scan_test_withhold = 0;
   static constexpr size_t kFaultBytes = 64;
-  volatile uint32_t* fault_word() const { return reinterpret_cast<volatile uint32_t*>(static_cast<char*>(pinned) + pinned_cap); }
-  uint32_t* fault_word_dev() const { return reinterpret_cast<uint32_t*>(static_cast<char*>(pinned_dev) + pinned_cap); }
-  // level 2 = highest, 1 = middle, 0 = lowest stream priority
+  volatile uint32_t* fault_word() const { return reinterpret_cast<volatile uint32_t*>(pinned.as<char>() + pinned_cap); }
+  uint32_t* fault_word_dev() const { return reinterpret_cast<uint32_t*>(static_cast<char*>(pinned.dev()) + pinned_cap); }
+  // level 2 = highest, 1 = middle, 0 = lowest stream priority. Built aside and moved in whole: a failure half-way
+  // leaves the lane empty, and ensure_lane tries again on the next call.
   void init(int level = 0) {
     int lo = 0, hi = 0;  // numerically lower = higher priority
     ZK_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
     int prio = level >= 2 ? hi : (level == 1 ? (lo + hi) / 2 : lo);
     // creating the stream is the expensive part (10-50 ms: a hardware queue comes up with it)
-    ZK_HIP(hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, prio));
-    pinned_cap = (1 << 20) - kFaultBytes;   // read-backs use [0, pinned_cap); the fault word sits behind them
-    ZK_HIP(hipHostMalloc(&pinned, pinned_cap + kFaultBytes, hipHostMallocDefault));
-    ZK_HIP(hipHostGetDevicePointer(&pinned_dev, pinned, 0));
-    memset(static_cast<char*>(pinned) + pinned_cap, 0, kFaultBytes);
-    host_sums.assign(pinned_cap + kFaultBytes, 0);
-    ZK_HIP(hipEventCreate(&ev0));
-    ZK_HIP(hipEventCreate(&ev1));
-  }
-  void destroy() {
-    ws.release();
-    if (scan_scratch) (void)hipFree(scan_scratch);
-    scan_scratch = nullptr;
-    scan_tiles = scan_gen = 0;
-    if (pinned) (void)hipHostFree(pinned);
-    if (stream) (void)hipStreamDestroy(stream);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    pinned = nullptr;
-    stream = nullptr;
-    ev0 = ev1 = nullptr;
+    DevStream st;
+    st.create(prio);
+    const size_t cap = (1 << 20) - kFaultBytes;
+    PinnedMem pin;
+    pin.alloc(cap + kFaultBytes);
+    pin.map_to_device();
+    memset(pin.as<char>() + cap, 0, kFaultBytes);
+    std::vector<char> sums(cap + kFaultBytes, 0);
+    DevEvent e[4];
+    for (DevEvent& ev : e) ev.create(hipEventDefault);
+    stream = std::move(st);
+    pinned = std::move(pin);
+    pinned_cap = cap;
+    host_sums = std::move(sums);
+    ev0 = std::move(e[0]);
+    ev1 = std::move(e[1]);
+    ev_a = std::move(e[2]);
+    ev_b = std::move(e[3]);
   }
 };
 
@@ -174,8 +159,6 @@ struct DeviceCtx {
   Lane lanes[kLanes];
   std::mutex lazy_mutex_;
   bool ok = false;
-  // last-run kernel timing (HIP events on the lane's stream), for bench.py's roofline object
-  float last_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   std::thread bg_;   // not a SideTask: it signals readiness twice mid-way (condition variables) and outlives every call
   std::mutex bg_mutex_;
   std::condition_variable bg_cv_;
@@ -183,7 +166,7 @@ struct DeviceCtx {
   std::exception_ptr bg_err_;
   // A stream of its own for host -> HBM copies that run WHILE lanes compute (one-shot proves overlap the zkey upload
   // with the MSMs). First thing the background thread creates; copy_stream_wait() blocks until it exists.
-  hipStream_t copy_stream = nullptr;
+  DevStream copy_stream;
   std::function<void(hipStream_t)> after_copy_stream;   // runs on the background thread once the copy stream exists
   std::function<void()> after_lanes;                    // runs on the background thread once every eager lane is up
   std::mutex copy_mutex_;
@@ -220,8 +203,7 @@ struct DeviceCtx {
         // highest priority: a copy queued at normal priority waits behind the lanes' kernels (fast_upload.hpp)
         int plo = 0, phi = 0;
         (void)hipDeviceGetStreamPriorityRange(&plo, &phi);
-        hipError_t ce = hipStreamCreateWithPriority(&copy_stream, hipStreamNonBlocking, phi);
-        if (ce != hipSuccess) copy_stream = nullptr;
+        (void)copy_stream.try_create(phi);
         if (copy_stream && after_copy_stream) {
           try {
             after_copy_stream(copy_stream);
@@ -296,14 +278,11 @@ struct DeviceCtx {
   void join_background() {
     if (bg_.joinable()) bg_.join();
   }
-  void destroy() {
-    if (!ok) return;
+  // the members give their streams, memory and events back on this device; nothing here waits for the device (an
+  // owner with work in flight drains it first: ~zkpoa_context)
+  ~DeviceCtx() {
     join_background();
-    (void)hipSetDevice(device);
-    for (auto& l : lanes) l.destroy();
-    if (copy_stream) (void)hipStreamDestroy(copy_stream);
-    copy_stream = nullptr;
-    ok = false;
+    if (ok) (void)hipSetDevice(device);
   }
 };
 

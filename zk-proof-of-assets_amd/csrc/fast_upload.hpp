@@ -27,8 +27,6 @@ class FastUploader {
   // start-up cost that a one-shot prover pays every time (12 x 8 MiB cost ~60 ms, 12 x 2 MiB ~15 ms)
   static constexpr size_t kChunk = 2u << 20;
 
-  ~FastUploader() { release(); }
-
   // `stream`: an existing stream of the caller that is idle during the upload (the context's lane 0). Creating
   // a HIP stream costs 10-50 ms (it brings up a hardware queue), which a one-shot prover pays on every run, so
   // the uploader owns none by default: the copies of all threads interleave on the one stream at full PCIe rate.
@@ -59,7 +57,7 @@ class FastUploader {
       // one stream -- one SDMA queue -- moves ~36 GB/s whatever the thread count, four reach the link's ~53 GB/s
       const int ns = n_own_.load(std::memory_order_acquire);
       const int pick = (int)t % (ns + 1);
-      hipStream_t st = pick == ns ? stream : own_[pick];
+      hipStream_t st = pick == ns ? stream : own_[pick].s;
       int b = 0;
       for (size_t off = lo; off < hi; off += kChunk, b ^= 1) {
         size_t len = hi - off < kChunk ? hi - off : kChunk;
@@ -91,17 +89,15 @@ class FastUploader {
     }
     for (int i = n_own_.load(); i < want; i++) {
       if (hipSetDevice(device) != hipSuccess) return;
-      hipStream_t st = nullptr;
       int lo = 0, hi = 0;   // numerically lower = higher priority
       (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
       const int word = opt_choice(O_UPLOAD_STREAM_PRIO);   // high | normal | low
       const int prio = word == 1 ? (lo + hi) / 2 : word == 2 ? lo : hi;
-      if (hipStreamCreateWithPriority(&st, hipStreamNonBlocking, prio) != hipSuccess) {
+      if (own_[i].try_create(prio) != hipSuccess) {
         (void)hipGetLastError();
         return;
       }
-      own_[i] = st;
-      n_own_.store(i + 1, std::memory_order_release);
+      n_own_.store(i + 1, std::memory_order_release);   // published once it exists
     }
   }
 
@@ -111,34 +107,19 @@ class FastUploader {
     ensure_locked(device, stream);
   }
 
-  void release() {
-    for (auto& s : slots_) {
-      for (int b = 0; b < 2; b++) {
-        if (s.done[b]) (void)hipEventDestroy(s.done[b]);
-        s.pinned[b] = nullptr;
-        s.done[b] = nullptr;
-      }
-    }
-    const int ns = n_own_.exchange(0);
-    for (int i = 0; i < ns; i++) (void)hipStreamDestroy(own_[i]);
-    if (block_) (void)hipHostFree(block_);
-    block_ = nullptr;
-    ready_ = false;
-  }
-
  private:
   struct Slot {
-    void* pinned[2] = {nullptr, nullptr};
-    hipEvent_t done[2] = {nullptr, nullptr};
+    void* pinned[2] = {nullptr, nullptr};   // into block_
+    DevEvent done[2];
   };
   Slot slots_[kMaxThreads];
-  void* block_ = nullptr;
-  bool ready_ = false;
+  PinnedMem block_;
+  bool ready_ = false;   // block_ and every slot of threads_ are in place
   int threads_ = 8;
   cpu_set_t cpus_;            // the CPUs of the GPU's NUMA node (staging copies stay on its socket)
   bool have_cpus_ = false;
   static constexpr int kMaxOwnStreams = 8;
-  hipStream_t own_[kMaxOwnStreams] = {};
+  DevStream own_[kMaxOwnStreams];
   std::atomic<int> n_own_{0};
 
   static void read_all(int fd, char* out, size_t len, uint64_t pos) {
@@ -212,19 +193,32 @@ class FastUploader {
     cpu_set_t before;
     const bool moved = have_cpus_ && pthread_getaffinity_np(pthread_self(), sizeof(before), &before) == 0 &&
                        pthread_setaffinity_np(pthread_self(), sizeof(cpus_), &cpus_) == 0;
-    ZK_HIP(hipHostMalloc(&block_, (size_t)threads_ * 2 * kChunk, hipHostMallocDefault));   // one pinning call
-    if (moved) {
-      memset(block_, 0, (size_t)threads_ * 2 * kChunk);   // first touch on the GPU's node
-      (void)pthread_setaffinity_np(pthread_self(), sizeof(before), &before);
+    // built aside and moved in whole: a failure half-way leaves nothing behind, and the next call starts afresh
+    PinnedMem block;
+    {
+      struct Restore {   // the calling thread goes back to its own CPUs, also when the pinning fails
+        const cpu_set_t* to;
+        ~Restore() {
+          if (to) (void)pthread_setaffinity_np(pthread_self(), sizeof(*to), to);
+        }
+      } restore{moved ? &before : nullptr};
+      block.alloc((size_t)threads_ * 2 * kChunk);         // one pinning call
+      if (moved) memset(block.get(), 0, block.bytes());   // first touch on the GPU's node
     }
+    DevEvent done[kMaxThreads][2];
     for (int t = 0; t < threads_; t++) {
-      Slot& s = slots_[t];
       for (int b = 0; b < 2; b++) {
-        s.pinned[b] = static_cast<char*>(block_) + ((size_t)t * 2 + b) * kChunk;
-        ZK_HIP(hipEventCreate(&s.done[b]));
-        ZK_HIP(hipEventRecord(s.done[b], stream));
+        done[t][b].create(hipEventDefault);
+        ZK_HIP(hipEventRecord(done[t][b], stream));
       }
     }
+    for (int t = 0; t < threads_; t++) {
+      for (int b = 0; b < 2; b++) {
+        slots_[t].pinned[b] = block.as<char>() + ((size_t)t * 2 + b) * kChunk;
+        slots_[t].done[b] = std::move(done[t][b]);
+      }
+    }
+    block_ = std::move(block);
     ready_ = true;
   }
 };

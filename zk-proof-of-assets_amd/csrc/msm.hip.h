@@ -412,20 +412,18 @@ inline void scan_pair(Lane& lane, const ScanPair& a) {
   }
   if (lane.scan_tiles < ntiles || lane.scan_gen >= 0x3ffffff0u) {
     ZK_HIP(hipStreamSynchronize(lane.stream));
-    if (lane.scan_scratch) ZK_HIP(hipFree(lane.scan_scratch));
-    lane.scan_scratch = nullptr;
     const uint32_t cap = ntiles < 1024 ? 1024 : ntiles * 2;
     const size_t bytes = (size_t)cap * 16 + 256;
-    ZK_HIP(hipMalloc(&lane.scan_scratch, bytes));
+    lane.scan_scratch.alloc(bytes);   // (gives the old block back first)
     // on the lane's own stream: a null-stream hipMemset is not ordered against a non-blocking stream, and a clear that
     // lands after the first scan has started would wipe live tickets and status words
-    ZK_HIP(hipMemsetAsync(lane.scan_scratch, 0, bytes, lane.stream));
+    ZK_HIP(hipMemsetAsync(lane.scan_scratch.get(), 0, bytes, lane.stream));
     lane.scan_tiles = cap;
     lane.scan_gen = 0;
   }
   const uint32_t gen = ++lane.scan_gen;   // generation 0 never appears in a live status word
-  uint32_t* tickets = reinterpret_cast<uint32_t*>(lane.scan_scratch);
-  uint64_t* st_a = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(lane.scan_scratch) + 256);
+  uint32_t* tickets = lane.scan_scratch.as<uint32_t>();
+  uint64_t* st_a = reinterpret_cast<uint64_t*>(lane.scan_scratch.as<char>() + 256);
   uint64_t* st_b = st_a + lane.scan_tiles;
   const ScanGuard guard{lane.scan_poll_limit, lane.scan_test_withhold, lane.fault_word_dev()};
   hipLaunchKernelGGL(scan_pair_kernel, dim3(ntiles), dim3(kScanBlock), 0, lane.stream, a, st_a, st_b, tickets, gen, ntiles,
@@ -1072,7 +1070,7 @@ inline void msm_read_back(Lane& lane, const void* d_src, size_t bytes) {
   const uint32_t n16 = (uint32_t)((bytes + 15) / 16);
   const uint32_t grid = n16 > 4096 ? 16u : (n16 + 255) / 256;
   hipLaunchKernelGGL(msm_to_host_kernel, dim3(grid ? grid : 1), dim3(256), 0, lane.stream, (const uint4*)d_src,
-                     (uint4*)lane.pinned_dev, n16);
+                     (uint4*)lane.pinned.dev(), n16);
   ZK_HIP(hipStreamSynchronize(lane.stream));
   lane_check_fault(lane);
 }
@@ -1123,7 +1121,7 @@ inline Layout msm_carve(Arena& ws, const MsmPlan& p) {
 inline void lane_guard_stamp(Lane& lane, size_t first) {
   for (size_t i = first; i < lane.ws.guards.size(); i++) {
     const Arena::Guard& g = lane.ws.guards[i];
-    ZK_HIP(hipMemsetAsync(lane.ws.base + g.off, Arena::kGuardByte, g.len, lane.stream));
+    ZK_HIP(hipMemsetAsync(lane.ws.base.as<char>() + g.off, Arena::kGuardByte, g.len, lane.stream));
   }
 }
 inline void lane_guard_check(Lane& lane, const char* phase) {
@@ -1131,14 +1129,14 @@ inline void lane_guard_check(Lane& lane, const char* phase) {
   if (!ws.guard) return;
   const long k = opt_long(O_TEST_WS_CLOBBER);
   if (k >= 1 && (size_t)k <= ws.guards.size())
-    ZK_HIP(hipMemsetAsync(ws.base + ws.guards[k - 1].off, (unsigned char)~Arena::kGuardByte, 1, lane.stream));
+    ZK_HIP(hipMemsetAsync(ws.base.as<char>() + ws.guards[k - 1].off, (unsigned char)~Arena::kGuardByte, 1, lane.stream));
   size_t total = 0;
   for (const Arena::Guard& g : ws.guards) total += g.len;
   std::vector<unsigned char> h(total);
   size_t at = 0;
   for (const Arena::Guard& g : ws.guards) {
     if (g.off + g.len > ws.off) throw HipError("msm: internal: a workspace guard lies outside the carved arena");
-    ZK_HIP(hipMemcpyAsync(h.data() + at, ws.base + g.off, g.len, hipMemcpyDeviceToHost, lane.stream));
+    ZK_HIP(hipMemcpyAsync(h.data() + at, ws.base.as<char>() + g.off, g.len, hipMemcpyDeviceToHost, lane.stream));
     at += g.len;
   }
   ZK_HIP(hipStreamSynchronize(lane.stream));
@@ -1355,7 +1353,7 @@ inline MsmSorted msm_sort_phase(Lane& lane, const void* d_scalars, const MsmRequ
 #undef ZK_SORT_SCATTER
     }
   }
-  uint32_t* hb = reinterpret_cast<uint32_t*>(lane.pinned);
+  uint32_t* hb = lane.pinned.as<uint32_t>();
   msm_read_back(lane, m.misc, 16);
   sr.total_entries = hb[0];
   sr.max_count = hb[1];
@@ -1436,7 +1434,7 @@ inline void msm_accum_phase(Lane& lane, const MsmSorted& sr, const void* d_bases
   ZK_HIP(hipGetLastError());
   // every guard of this arena: the sort's too when it was carved here (with another lane's sort, that lane checked them)
   lane_guard_check(lane, "accumulation");
-  memcpy(window_sums_host, lane.pinned, (size_t)sums * MsmSizes<F>::kXyzz);
+  memcpy(window_sums_host, lane.pinned.get(), (size_t)sums * MsmSizes<F>::kXyzz);
   if (accum_ms) ZK_HIP(hipEventElapsedTime(accum_ms, lane.ev0, lane.ev1));
 }
 
@@ -1447,7 +1445,7 @@ inline void msm_accum_phase(Lane& lane, const MsmSorted& sr, const void* d_bases
 // 14..15 windows; 2^26: c 20 -> 24, 13 -> 11 windows: that many fewer mixed additions in the kernel that is >90 %
 // of an MSM), (b) divides the bucket-reduction work by W, (c) leaves the host a single window to combine.
 struct MsmTable {
-  void* d = nullptr;     // W * n points
+  DevMem d;              // W * n points
   uint64_t n = 0;        // points per window (= the base array it was built from)
   uint32_t c = 0, W = 0;
   size_t bytes = 0;
@@ -1533,36 +1531,21 @@ inline MsmTable msm_table_build(hipStream_t st, const void* d_bases, uint64_t n,
   t.W = msm_windows(c);
   t.bytes = msm_table_bytes<F>(n, c);
   if ((uint64_t)n * t.W >= 0x80000000ull) throw HipError("msm table: n * windows exceeds the fixed-base entry index");
-  ZK_HIP(hipMalloc(&t.d, t.bytes ? t.bytes : 1));
+  t.d.alloc(t.bytes);
   const uint64_t slab = 1ull << 20;
-  void* scratch = nullptr;
-  void* prefix = nullptr;
-  try {
-    ZK_HIP(hipMalloc(&scratch, (size_t)(n < slab ? (n ? n : 1) : slab) * t.W * MsmSizes<F>::kXyzz));
-    ZK_HIP(hipMalloc(&prefix, (size_t)(n < slab ? (n ? n : 1) : slab) * t.W * FieldBytes<F>::N));
-    for (uint64_t off = 0; off < n; off += slab) {
-      const uint64_t cnt = n - off < slab ? n - off : slab;
-      hipLaunchKernelGGL((msm_table_chain_kernel<F>), dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, st, d_bases, off,
-                         cnt, t.c, t.W, scratch);
-      hipLaunchKernelGGL((msm_table_affine_kernel<F>), dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, st,
-                         (const void*)scratch, prefix, off, cnt, n, t.W, t.d);
-    }
-    ZK_HIP(hipStreamSynchronize(st));
-    ZK_HIP(hipGetLastError());
-  } catch (...) {
-    if (scratch) (void)hipFree(scratch);
-    if (prefix) (void)hipFree(prefix);
-    (void)hipFree(t.d);
-    throw;
+  DevMem scratch, prefix;
+  scratch.alloc((size_t)(n < slab ? (n ? n : 1) : slab) * t.W * MsmSizes<F>::kXyzz);
+  prefix.alloc((size_t)(n < slab ? (n ? n : 1) : slab) * t.W * FieldBytes<F>::N);
+  for (uint64_t off = 0; off < n; off += slab) {
+    const uint64_t cnt = n - off < slab ? n - off : slab;
+    hipLaunchKernelGGL((msm_table_chain_kernel<F>), dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, st, d_bases, off,
+                       cnt, t.c, t.W, scratch.get());
+    hipLaunchKernelGGL((msm_table_affine_kernel<F>), dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, st,
+                       (const void*)scratch.get(), prefix.get(), off, cnt, n, t.W, t.d.get());
   }
-  (void)hipFree(scratch);
-  (void)hipFree(prefix);
+  ZK_HIP(hipStreamSynchronize(st));
+  ZK_HIP(hipGetLastError());
   return t;
-}
-
-inline void msm_table_free(MsmTable& t) {
-  if (t.d) (void)hipFree(t.d);
-  t = MsmTable();
 }
 
 // One complete MSM on one lane (phase A + phase B) over req.n points. Returns the plan used. A merged request comes
@@ -1575,7 +1558,7 @@ inline MsmPlan msm_device(Lane& lane, const void* d_bases, const void* d_scalars
   if (table && (table->n != req.n || (int)table->c != req.c))
     throw HipError("msm: the fixed-base table was built for another base array");
   MsmSorted sr = msm_sort_phase(lane, d_scalars, req, &msm_accum_workspace_bytes<F>);
-  msm_accum_phase<F>(lane, sr, table ? table->d : d_bases, window_sums_host, true, accum_ms);
+  msm_accum_phase<F>(lane, sr, table ? table->d.get() : d_bases, window_sums_host, true, accum_ms);
   if (entries) *entries = sr.total_entries;
   return sr.p;
 }

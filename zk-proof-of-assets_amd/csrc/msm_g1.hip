@@ -12,12 +12,8 @@ MsmTablePtr msm_table_build_g1(zkpoa_context* ctx, const void* d_bases, uint64_t
   return t;
 }
 size_t msm_table_bytes_g1(uint64_t n, int c) { return msm_table_bytes<Fq>(n, msm_table_c(n, c, false)); }
-void msm_table_release(MsmTable* t) {
-  if (!t) return;
-  msm_table_free(*t);
-  delete t;
-}
-const void* msm_table_data(const MsmTable* t) { return t ? t->d : nullptr; }
+void msm_table_release(MsmTable* t) { delete t; }
+const void* msm_table_data(const MsmTable* t) { return t ? t->d.get() : nullptr; }
 void msm_density(hipStream_t st, const void* d_scalars, uint64_t n, double out[32], void* d_scratch) {
   for (int c = 0; c < 32; c++) out[c] = (double)msm_windows(c < 4 ? 4u : (uint32_t)c);   // uniform default
   if (n == 0) return;

@@ -32,7 +32,7 @@ void msm_run(zkpoa_context* ctx, int lane_id, const void* d_bases, const void* d
     const uint64_t cnt = n - done < max_pts ? n - done : max_pts;
     float acc_ms = 0;
     uint32_t entries = 0;
-    ZK_HIP(hipEventRecord(ctx->ev_a[lane_id], lane.stream));
+    ZK_HIP(hipEventRecord(lane.ev_a, lane.stream));
     MsmPlan p;
     try {
       p = msm_device<F>(lane, reinterpret_cast<const char*>(d_bases) + done * MsmSizes<F>::kAffine,
@@ -57,10 +57,10 @@ void msm_run(zkpoa_context* ctx, int lane_id, const void* d_bases, const void* d
       continue;
     }
     adds += entries;
-    ZK_HIP(hipEventRecord(ctx->ev_b[lane_id], lane.stream));
-    ZK_HIP(hipEventSynchronize(ctx->ev_b[lane_id]));
+    ZK_HIP(hipEventRecord(lane.ev_b, lane.stream));
+    ZK_HIP(hipEventSynchronize(lane.ev_b));
     float tot = 0;
-    ZK_HIP(hipEventElapsedTime(&tot, ctx->ev_a[lane_id], ctx->ev_b[lane_id]));
+    ZK_HIP(hipEventElapsedTime(&tot, lane.ev_a, lane.ev_b));
     tot_ms += tot;
     acc_sum += acc_ms;
     XYZZ<HF> r = h_combine_windows<HF>(wsums.data(), p.Wb, p.c, p.logS);
@@ -82,15 +82,16 @@ template <class F, class HF>
 void msm_accum_run(zkpoa_context* ctx, int lane_id, const MsmSorted& sr, bool own_arena, const void* d_bases,
                    uint8_t* out, float* ms2) {
   if (lane_id) ctx->dev.wait_lanes();
+  ctx->dev.ensure_lane(lane_id);
   Lane& lane = ctx->dev.lanes[lane_id];
   std::vector<char>& wsums = lane.host_sums;
   float acc_ms = 0;
-  ZK_HIP(hipEventRecord(ctx->ev_a[lane_id], lane.stream));
+  ZK_HIP(hipEventRecord(lane.ev_a, lane.stream));
   msm_accum_phase<F>(lane, sr, d_bases, wsums.data(), own_arena, &acc_ms);
-  ZK_HIP(hipEventRecord(ctx->ev_b[lane_id], lane.stream));
-  ZK_HIP(hipEventSynchronize(ctx->ev_b[lane_id]));
+  ZK_HIP(hipEventRecord(lane.ev_b, lane.stream));
+  ZK_HIP(hipEventSynchronize(lane.ev_b));
   float tot = 0;
-  ZK_HIP(hipEventElapsedTime(&tot, ctx->ev_a[lane_id], ctx->ev_b[lane_id]));
+  ZK_HIP(hipEventElapsedTime(&tot, lane.ev_a, lane.ev_b));
   if (ms2) {
     ms2[0] = tot;
     ms2[1] = acc_ms;

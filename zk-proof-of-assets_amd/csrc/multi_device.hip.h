@@ -245,21 +245,6 @@ DeviceSet* process_devices(uint32_t power, std::string& err, int* code) {
 }
 
 // ---- a key sharded over the ranks of the process ----------------------------------------------------------------------
-struct DevEvent {   // an owned hipEvent_t (timing disabled); empty = not created
-  hipEvent_t e = nullptr;
-  DevEvent() = default;
-  DevEvent(DevEvent&& o) noexcept : e(o.e) { o.e = nullptr; }
-  DevEvent& operator=(DevEvent&& o) noexcept {
-    std::swap(e, o.e);
-    return *this;
-  }
-  ~DevEvent() {
-    if (e) (void)hipEventDestroy(e);
-  }
-  void create() { ZK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); }   // on the current device
-  operator hipEvent_t() const { return e; }
-};
-
 struct RankState {   // what rank g holds, on device `device` (a failed load leaves the later members empty)
   int device = 0;
   KeyPtr shard;             // lives on context g
@@ -323,13 +308,13 @@ MultiKeyPtr multi_key_load(DeviceSet* ds, const uint8_t* buf, uint64_t size) {
   if (mk->split) mk->xbytes = (uint64_t)3 * (hdr->domain / G) * 32;
   for (RankState& r : mk->rank) {
     ZK_HIP(hipSetDevice(r.device));
-    r.evw.create();
+    r.evw.create(hipEventDisableTiming);
     if (!mk->split) continue;
     r.xa.alloc(mk->xbytes);
     r.xb1.alloc(mk->xbytes);
     r.xb2.alloc(mk->xbytes);
-    r.ev1.create();
-    r.ev2.create();
+    r.ev1.create(hipEventDisableTiming);
+    r.ev2.create(hipEventDisableTiming);
   }
   mk->load_ms = ms_since(t0);
   return mk;
@@ -448,9 +433,7 @@ void multi_prove_partials(DeviceSet* ds, MultiKey* mk, const WtnsView& w, uint8_
         phase([&] {
           for (size_t h = 0; h < G; h++) ZK_HIP(hipStreamWaitEvent(st, mk->rank[h].evw, 0));
           // the witness MSMs run on other lanes: they wait for this point of lane 0 (prove_partials, ev_witness)
-          if (!ctx->ev_witness) ZK_HIP(hipEventCreateWithFlags(&ctx->ev_witness, hipEventDisableTiming));
-          ZK_HIP(hipEventRecord(ctx->ev_witness, st));
-          ctx->ev_witness_set = true;
+          ctx->record_witness_event(st);
         });
       }
       phase([&] {

@@ -147,9 +147,9 @@ struct HashStream {
   zkpoa_context* ctx;
   zkpoa::phase2::Blake2b& hasher;
   uint64_t piece_bytes;
-  uint8_t* pinned[2] = {nullptr, nullptr};
-  void* d_stage[2] = {nullptr, nullptr};
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  PinnedMem pinned[2];
+  DevMem d_stage[2];
+  DevEvent ev[2];
   double convert_ms = 0, hash_ms = 0;   // host clock: waiting for the device's pieces; hashing
   uint64_t bytes = 0;
   std::vector<uint8_t>* capture = nullptr;   // tests: the hash-form bytes as well
@@ -158,16 +158,9 @@ struct HashStream {
     if (!piece_points) piece_points = 1ull << 18;
     piece_bytes = piece_points * 128;   // a piece holds piece_points G2 points, or twice as many G1 points
     for (int b = 0; b < 2; b++) {
-      ZK_HIP(hipHostMalloc((void**)&pinned[b], piece_bytes, hipHostMallocDefault));
-      ZK_HIP(hipMalloc(&d_stage[b], piece_bytes));
-      ZK_HIP(hipEventCreateWithFlags(&ev[b], hipEventDisableTiming));
-    }
-  }
-  ~HashStream() {
-    for (int b = 0; b < 2; b++) {
-      if (ev[b]) (void)hipEventDestroy(ev[b]);
-      if (d_stage[b]) (void)hipFree(d_stage[b]);
-      if (pinned[b]) (void)hipHostFree(pinned[b]);
+      pinned[b].alloc(piece_bytes);
+      d_stage[b].alloc(piece_bytes);
+      ev[b].create(hipEventDisableTiming);
     }
   }
   HashStream(const HashStream&) = delete;
@@ -182,11 +175,11 @@ struct HashStream {
       const uint64_t cnt = std::min(per_piece, count - first), coords = cnt * (in_unit / 32);
       const uint4* src = reinterpret_cast<const uint4*>(static_cast<const char*>(d) + first * in_unit);
       const dim3 grid((uint32_t)((coords + 255) / 256)), pgrid((uint32_t)((cnt + 255) / 256));
-      if (compressed && group == 1) hipLaunchKernelGGL((compressed_form_kernel<Fq>), pgrid, dim3(256), 0, st, (const void*)src, (uint4*)d_stage[b], cnt);
-      else if (compressed) hipLaunchKernelGGL((compressed_form_kernel<Fq2>), pgrid, dim3(256), 0, st, (const void*)src, (uint4*)d_stage[b], cnt);
-      else if (group == 1) hipLaunchKernelGGL((hash_form_kernel<2>), grid, dim3(256), 0, st, src, (uint4*)d_stage[b], coords);
-      else hipLaunchKernelGGL((hash_form_kernel<4>), grid, dim3(256), 0, st, src, (uint4*)d_stage[b], coords);
-      ZK_HIP(hipMemcpyAsync(pinned[b], d_stage[b], cnt * unit, hipMemcpyDeviceToHost, st));
+      if (compressed && group == 1) hipLaunchKernelGGL((compressed_form_kernel<Fq>), pgrid, dim3(256), 0, st, (const void*)src, d_stage[b].as<uint4>(), cnt);
+      else if (compressed) hipLaunchKernelGGL((compressed_form_kernel<Fq2>), pgrid, dim3(256), 0, st, (const void*)src, d_stage[b].as<uint4>(), cnt);
+      else if (group == 1) hipLaunchKernelGGL((hash_form_kernel<2>), grid, dim3(256), 0, st, src, d_stage[b].as<uint4>(), coords);
+      else hipLaunchKernelGGL((hash_form_kernel<4>), grid, dim3(256), 0, st, src, d_stage[b].as<uint4>(), coords);
+      ZK_HIP(hipMemcpyAsync(pinned[b].get(), d_stage[b].get(), cnt * unit, hipMemcpyDeviceToHost, st));
       ZK_HIP(hipEventRecord(ev[b], st));
     };
     if (count) issue(0, 0);
@@ -197,9 +190,10 @@ struct HashStream {
       const auto t0 = std::chrono::steady_clock::now();
       ZK_HIP(hipEventSynchronize(ev[b]));
       const auto t1 = std::chrono::steady_clock::now();
-      hasher.update(pinned[b], cnt * unit);
-      if (capture) capture->insert(capture->end(), pinned[b], pinned[b] + cnt * unit);
-      if (sink) sink(pinned[b], cnt * unit);
+      const uint8_t* piece = pinned[b].as<const uint8_t>();
+      hasher.update(piece, cnt * unit);
+      if (capture) capture->insert(capture->end(), piece, piece + cnt * unit);
+      if (sink) sink(piece, cnt * unit);
       convert_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
       hash_ms += zkpoa::ms_since(t1);
       bytes += cnt * unit;

@@ -225,7 +225,7 @@ void launch_hash(hipStream_t st, const PoseidonTables* prm, const void* l, const
 
 // parameters live with the context (uploaded on first use)
 struct zkpoa_poseidon_state {
-  PoseidonTables* d = nullptr;
+  DevMem d;   // a PoseidonTables
 };
 
 static const PoseidonTables* device_params(zkpoa_context* ctx) {
@@ -235,20 +235,17 @@ static const PoseidonTables* device_params(zkpoa_context* ctx) {
     std::unique_ptr<PoseidonTables> tb(new PoseidonTables());
     host_params(*h);
     host_tables(*h, *tb);
-    ZK_HIP(hipMalloc(reinterpret_cast<void**>(&s->d), sizeof(PoseidonTables)));
-    ZK_HIP(hipMemcpy(s->d, tb.get(), sizeof(PoseidonTables), hipMemcpyHostToDevice));
+    s->d.alloc(sizeof(PoseidonTables));
+    ZK_HIP(hipMemcpy(s->d.get(), tb.get(), sizeof(PoseidonTables), hipMemcpyHostToDevice));
     ctx->poseidon = s.release();
   }
-  return ctx->poseidon->d;
+  return ctx->poseidon->d.as<const PoseidonTables>();
 }
 
 namespace zkpoa {
 void poseidon_release(zkpoa_context* ctx) {
-  if (ctx->poseidon) {
-    if (ctx->poseidon->d) (void)hipFree(ctx->poseidon->d);
-    delete ctx->poseidon;
-    ctx->poseidon = nullptr;
-  }
+  delete ctx->poseidon;
+  ctx->poseidon = nullptr;
 }
 }  // namespace zkpoa
 

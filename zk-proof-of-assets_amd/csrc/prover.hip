@@ -702,7 +702,7 @@ uint64_t zkey_precompute(zkpoa_context* ctx, zkpoa_zkey* zk, uint64_t budget, in
       zk->tables_settled = true;
       return zk->table_bytes;
     }
-    for (auto& l : ctx->dev.lanes) l.ws.release();
+    for (auto& l : ctx->dev.lanes) l.ws.give_back();
   }
   bool more = true;
   // (a table that exists already counts as fitting: its bytes are in table_bytes)
@@ -816,7 +816,7 @@ static void budget_lane_workspaces(zkpoa_context* ctx, const zkpoa_zkey* zk) {
     if (lim[l] < ctx->msm_points_limit(l)) ctx->oom_max_points[l] = lim[l];
   for (int l = 0; l < 5; l++) {   // every lane starts again from what it needs now (nothing is in flight: prove start)
     ZK_HIP(hipStreamSynchronize(ctx->dev.lanes[l].stream));
-    ctx->dev.lanes[l].ws.release();
+    ctx->dev.lanes[l].ws.give_back();
   }
   vlog("zkpoa:   HBM budget: %.1f GB free + %.1f GB held by the lanes; MSMs take at most H %llu, A %llu, B1 %llu, B2 %llu, "
        "C %llu points at once (workspaces %.1f GB)\n",
@@ -1003,7 +1003,7 @@ void prove_partials(zkpoa_context* ctx, const zkpoa_zkey* zk, uint8_t out[384], 
     if (split) zk->h_ready = false;
     chain.store(kMsChain);   // no wait of its own: the H MSM, later on the same stream, has returned
     msm_read_back(l0, zk->d_flag.get(), 4);   // lane 0 is idle (its MSM has returned): the flag through its pinned buffer
-    witness_bad = *reinterpret_cast<const uint32_t*>(l0.pinned);
+    witness_bad = *l0.pinned.as<const uint32_t>();
   } catch (...) {
     main_err = std::current_exception();
   }
@@ -1447,9 +1447,7 @@ extern "C" int zkpoa_split_stage1(zkpoa_context* ctx, const zkpoa_zkey* zkey, co
     hipStream_t st = ctx->dev.lanes[0].stream;
     if (d_witness && d_witness != zkey->d_witness) {
       ZK_HIP(hipMemcpyAsync(zkey->d_witness, d_witness, (size_t)zkey->nVars * 32, hipMemcpyDeviceToDevice, st));
-      if (!ctx->ev_witness) ZK_HIP(hipEventCreateWithFlags(&ctx->ev_witness, hipEventDisableTiming));
-      ZK_HIP(hipEventRecord(ctx->ev_witness, st));   // the witness MSMs run on other lanes: they wait for this copy
-      ctx->ev_witness_set = true;
+      ctx->record_witness_event(st);   // the witness MSMs run on other lanes: they wait for this copy
     }
     split_stage1(ctx, zkey, d_exchange);
   });
@@ -1479,7 +1477,7 @@ extern "C" void* zkpoa_context_stream(zkpoa_context* ctx, int lane) {
   } catch (const std::exception&) {
     return nullptr;
   }
-  return reinterpret_cast<void*>(ctx->dev.lanes[lane].stream);
+  return reinterpret_cast<void*>(ctx->dev.lanes[lane].stream.s);
 }
 
 extern "C" int zkpoa_context_synchronize(zkpoa_context* ctx) {

@@ -157,8 +157,8 @@ struct MulStep {
 // Read-back: piece p comes back into pinned buffer p & 1 behind the stream's kernels, and a writer thread puts it into
 // the file when its copy has landed -- while the device takes piece p + 1. A buffer is reused when its writer is done.
 struct ReadBack {
-  uint8_t* pinned[2] = {nullptr, nullptr};
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  PinnedMem pinned[2];
+  DevEvent ev[2];
   SideTask writer[2];
   bool failed = false;   // a writer threw: kept here, its slot takes the next piece
   double write_ms[2] = {0, 0};   // each touched by its own writer only
@@ -166,8 +166,8 @@ struct ReadBack {
   uint64_t sent = 0;
   ReadBack(zkpoa_context* c, size_t bytes) : ctx(c) {
     for (int b = 0; b < 2; b++) {
-      ZK_HIP(hipHostMalloc((void**)&pinned[b], bytes, hipHostMallocDefault));
-      ZK_HIP(hipEventCreateWithFlags(&ev[b], hipEventDisableTiming));
+      pinned[b].alloc(bytes);
+      ev[b].create(hipEventDisableTiming);
     }
   }
   void wait(int b) noexcept {
@@ -182,13 +182,13 @@ struct ReadBack {
     const int b = (int)(sent++ & 1), device = ctx->dev.device;
     hipStream_t st = ctx->dev.lanes[0].stream;
     wait(b);
-    ZK_HIP(hipMemcpyAsync(pinned[b], d_src, len, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipMemcpyAsync(pinned[b].get(), d_src, len, hipMemcpyDeviceToHost, st));
     ZK_HIP(hipEventRecord(ev[b], st));
     writer[b] = SideTask([this, &fo, b, id, at, len, device] {
       const auto w0 = std::chrono::steady_clock::now();
       ZK_HIP(hipSetDevice(device));
       ZK_HIP(hipEventSynchronize(ev[b]));
-      fo.put_at(id, at, pinned[b], len);
+      fo.put_at(id, at, pinned[b].get(), len);
       write_ms[b] += ms_since(w0);
     });
   }
@@ -197,12 +197,9 @@ struct ReadBack {
     wait(1);
     if (failed) throw SetupError(command + ": the read-back of a piece failed");
   }
-  ~ReadBack() {
-    for (int b = 0; b < 2; b++) {
-      wait(b);   // before its buffer and its event go
-      if (ev[b]) (void)hipEventDestroy(ev[b]);
-      if (pinned[b]) (void)hipHostFree(pinned[b]);
-    }
+  ~ReadBack() {   // the writers are done before the buffers and events they read go
+    wait(0);
+    wait(1);
   }
 };
 

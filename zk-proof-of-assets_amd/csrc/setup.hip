@@ -227,7 +227,7 @@ void setup_accumulate(zkpoa_context* ctx, const void* d_points, uint64_t n_point
                        (uint32_t*)counts.p, m);
   scan_u32(st, (const uint32_t*)counts.p, S, 0, 0, (uint32_t*)off.p, (uint32_t*)block_sums.p, m + 1, m + 2);
   msm_read_back(lane, m, 16);
-  const uint32_t* hb = reinterpret_cast<const uint32_t*>(lane.pinned);
+  const uint32_t* hb = lane.pinned.as<const uint32_t>();
   const uint32_t flags = hb[0], total = hb[1], max_seg = hb[2];
   if (flags & 1u) throw HipError("setup_accumulate: signal or point index out of range");
   if (flags & 2u) throw HipError("setup_accumulate: coefficient is not a field element (>= r)");
@@ -585,7 +585,7 @@ uint64_t wtns_check(zkpoa_context* ctx, const char* r1cs_path, const char* wtns_
                        (void*)nullptr, 0u);
   msm_read_back(ctx->dev.lanes[0], fl, 16);
   ZK_HIP(hipGetLastError());
-  const uint32_t* hb = reinterpret_cast<const uint32_t*>(ctx->dev.lanes[0].pinned);
+  const uint32_t* hb = ctx->dev.lanes[0].pinned.as<const uint32_t>();
   if (hb[3]) throw SetupError("wtns: a value is not a field element (>= r)");
   if (hb[2]) throw SetupError("r1cs: a coefficient is not a field element (>= r)");
   if (first_bad) *first_bad = hb[1];

@@ -249,7 +249,7 @@ struct PointChecker {
   uint32_t read() {   // word 0 (the stream is synchronised), then every flag word zeroed
     msm_read_back(lane, flags.p, 4);
     uint32_t f;
-    memcpy(&f, lane.pinned, 4);
+    memcpy(&f, lane.pinned.get(), 4);
     ZK_HIP(hipMemsetAsync(flags.p, 0, 64, lane.stream));
     return f;
   }

@@ -24,8 +24,9 @@ void set_err(char* buf, unsigned long cap, const std::string& msg) {
 extern "C" int zkpoa_context_create(int device, zkpoa_context** out, char* error_msg, unsigned long error_msg_maxsize) {
   if (!out) return PROVER_ERROR;
   *out = nullptr;
-  zkpoa_context* c = new zkpoa_context();
   try {
+    std::unique_ptr<zkpoa_context> ctx(new zkpoa_context());   // a failure below takes down what has come up by then
+    zkpoa_context* c = ctx.get();
     // the uploader's pinned staging buffers (24 MiB, ~15 ms to pin) come up with the copy stream, off the main thread
     c->dev.after_copy_stream = [c, device](hipStream_t st) { c->uploader.prepare(device, st); };
     c->dev.after_lanes = [c, device] { c->uploader.add_streams(device); };
@@ -33,39 +34,27 @@ extern "C" int zkpoa_context_create(int device, zkpoa_context** out, char* error
     for (auto& l : c->dev.lanes) l.ws.hold_back = &c->key_hold_back;
     // cap of every MSM lane's workspace (as option lane_workspace_max_mb): a card shared with other work
     for (auto& l : c->dev.lanes) l.ws.limit = (size_t)opt_long(O_LANE_WORKSPACE_MAX_MB) << 20;
-    for (int i = 0; i < DeviceCtx::kLanes; i++) {
-      ZK_HIP(hipEventCreate(&c->ev_a[i]));
-      ZK_HIP(hipEventCreate(&c->ev_b[i]));
-    }
-    ZK_HIP(hipEventCreate(&c->ev_chain_a));
-    ZK_HIP(hipEventCreate(&c->ev_chain_b));
+    c->ev_chain_a.create(hipEventDefault);
+    c->ev_chain_b.create(hipEventDefault);
+    *out = ctx.release();
   } catch (const std::exception& e) {
     set_err(error_msg, error_msg_maxsize, e.what());
-    delete c;
     return PROVER_ERROR;
   }
-  *out = c;
   return PROVER_OK;
 }
 
-extern "C" void zkpoa_context_destroy(zkpoa_context* ctx) {
-  if (!ctx) return;
-  (void)hipSetDevice(ctx->dev.device);
-  (void)hipDeviceSynchronize();
-  if (ctx->ev_witness) (void)hipEventDestroy(ctx->ev_witness);
-  for (int i = 0; i < DeviceCtx::kLanes; i++) {
-    if (ctx->ev_a[i]) (void)hipEventDestroy(ctx->ev_a[i]);
-    if (ctx->ev_b[i]) (void)hipEventDestroy(ctx->ev_b[i]);
+zkpoa_context::~zkpoa_context() {
+  if (dev.ok) {   // (else the device context never came up: nothing is in flight, and no device is touched for it)
+    (void)hipSetDevice(dev.device);
+    (void)hipDeviceSynchronize();
   }
-  for (hipEvent_t e : {ctx->ev_chain_a, ctx->ev_chain_b})
-    if (e) (void)hipEventDestroy(e);
-  ntt_release(ctx);
-  poseidon_release(ctx);
-  ctx->dev.join_background();   // it may still be adding the uploader's streams
-  ctx->uploader.release();
-  ctx->dev.destroy();
-  delete ctx;
+  dev.join_background();   // before anything else: it may still be adding the uploader's streams
+  ntt_release(this);
+  poseidon_release(this);
 }
+
+extern "C" void zkpoa_context_destroy(zkpoa_context* ctx) { delete ctx; }
 
 extern "C" const char* zkpoa_last_error(const zkpoa_context* ctx) {
   return ctx ? ctx->last_error.c_str() : "null context";

@@ -17,7 +17,7 @@ namespace zkpoa {
 struct NttEngine;
 struct MsmTable;    // msm.hip.h: fixed-base table 2^(c*j) * P_i of one base array
 struct MsmSorted;   // msm.hip.h: the result of an MSM's sort phase
-void msm_table_release(MsmTable* t);   // its device memory and the object
+void msm_table_release(MsmTable* t);   // delete, where the type is complete (msm_g1.hip)
 struct MsmTableFree {
   void operator()(MsmTable* t) const { msm_table_release(t); }
 };
@@ -37,7 +37,14 @@ enum MsSlot : int {
 static_assert(kMsMsm == 0 && kMsMsmAccum == 1, "msm_run's ms2 = ctx->ms needs the two MSM slots first and adjacent");
 }  // namespace zkpoa
 
+// Teardown (~zkpoa_context, zkpoa_api.hip): the device is drained and the background thread joined -- it may still be
+// inside uploader.add_streams --, the NTT and Poseidon state go, then the members in reverse order of declaration: the
+// events, the uploader (its own streams, events and pinned block), and last `dev` (the lanes and the copy stream).
 struct zkpoa_context {
+  zkpoa_context() = default;
+  ~zkpoa_context();
+  zkpoa_context(const zkpoa_context&) = delete;
+  zkpoa_context& operator=(const zkpoa_context&) = delete;
   zkpoa::DeviceCtx dev;
   zkpoa_poseidon_state* poseidon = nullptr;
   zkpoa::NttEngine* ntt = nullptr;
@@ -85,13 +92,17 @@ struct zkpoa_context {
   std::atomic<int64_t> key_hold_back{0};
   int opt_prove_serial = 0;      // measurement: run the stages of a prove one at a time (solo device times)
   // split chain: the witness copy of zkpoa_split_stage1 is enqueued on lane 0; the other lanes' MSMs wait for it
-  hipEvent_t ev_witness = nullptr;
+  zkpoa::DevEvent ev_witness;   // created by the first caller of record_witness_event
   bool ev_witness_set = false;
-  // start / stop event of every lane: an MSM on lane l records pair l, a one-shot entry point pair 0 (KernelTimer)
-  hipEvent_t ev_a[zkpoa::DeviceCtx::kLanes] = {};
-  hipEvent_t ev_b[zkpoa::DeviceCtx::kLanes] = {};
+  // (the start / stop pair of every lane is the lane's: Lane::ev_a, ev_b)
   // the H chain's own pair: a prove reads it after the H MSM, which has recorded lane 0's pair again by then
-  hipEvent_t ev_chain_a = nullptr, ev_chain_b = nullptr;
+  zkpoa::DevEvent ev_chain_a, ev_chain_b;
+  // "the witness is in place up to here on st": the MSMs of the other lanes wait for it (prove_partials)
+  void record_witness_event(hipStream_t st) {
+    if (!ev_witness) ev_witness.create(hipEventDisableTiming);
+    ZK_HIP(hipEventRecord(ev_witness, st));
+    ev_witness_set = true;
+  }
 };
 
 struct zkpoa_msm_table {   // C-ABI handle of a fixed-base table (zkpoa_msm_table_build)
@@ -118,62 +129,8 @@ inline void free_deferred(std::vector<void*>& sink) {   // once the device has d
   sink.clear();
 }
 
-// Device memory with one owner, for whatever outlives a call: the arrays of a key handle, exchange buffers, a CSR on
-// its way into a handle. Empty by default, move-only. An owner gives its memory back with hipFree and with nothing
-// else: a member of a long-lived object must never land in a deferred_free_sink() merely because it is destroyed while
-// one is set. Handing memory to a sink (or out through the C ABI) is always the explicit `sink.push_back(m.take())`.
-// lent(p) makes the one non-owning state -- memory that belongs to the caller: used like any other, never freed.
-// Temporaries of one call that should wait in the sink are DevBuf, below.
-class DevMem {
-  void* p_ = nullptr;
-  bool owned_ = true;
-
- public:
-  DevMem() = default;
-  static DevMem lent(const void* callers) {
-    DevMem m;
-    m.p_ = const_cast<void*>(callers);
-    m.owned_ = false;
-    return m;
-  }
-  DevMem(DevMem&& o) noexcept : p_(o.p_), owned_(o.owned_) { o.forget(); }
-  DevMem& operator=(DevMem&& o) noexcept {
-    if (this != &o) {
-      reset();
-      p_ = o.p_;
-      owned_ = o.owned_;
-      o.forget();
-    }
-    return *this;
-  }
-  DevMem(const DevMem&) = delete;
-  DevMem& operator=(const DevMem&) = delete;
-  ~DevMem() { reset(); }
-  void alloc(size_t bytes) {   // replaces what was held; 0 bytes still gives a valid pointer
-    reset();
-    ZK_HIP(hipMalloc(&p_, bytes ? bytes : 1));
-  }
-  void reset() {
-    if (p_ && owned_) (void)hipFree(p_);
-    forget();
-  }
-  void* take() {   // the raw pointer, now the caller's to free; lent memory cannot be given away
-    void* p = owned_ ? p_ : nullptr;
-    forget();
-    return p;
-  }
-  void* get() const { return p_; }
-  template <class T>
-  T* as() const { return static_cast<T*>(p_); }
-  explicit operator bool() const { return p_ != nullptr; }
-
- private:
-  void forget() {
-    p_ = nullptr;
-    owned_ = true;
-  }
-};
-
+// (DevMem, the owning handle of whatever outlives a call, is in device_handles.hpp: it never lands in a sink by being
+// destroyed.)
 struct DevBuf {  // a call's temporary device allocation: parked in the thread's deferred_free_sink() when one is set
   void* p = nullptr;
   explicit DevBuf(size_t bytes) { ZK_HIP(hipMalloc(&p, bytes ? bytes : 1)); }
@@ -252,7 +209,7 @@ struct KernelTimer {
   zkpoa_context* ctx;
   hipStream_t st;
   hipEvent_t a, b;
-  static KernelTimer lane0(zkpoa_context* ctx, hipStream_t st) { return {ctx, st, ctx->ev_a[0], ctx->ev_b[0]}; }
+  static KernelTimer lane0(zkpoa_context* ctx, hipStream_t st) { return {ctx, st, ctx->dev.lanes[0].ev_a, ctx->dev.lanes[0].ev_b}; }
   static KernelTimer chain(zkpoa_context* ctx, hipStream_t st) { return {ctx, st, ctx->ev_chain_a, ctx->ev_chain_b}; }
   void start() { ZK_HIP(hipEventRecord(a, st)); }
   void stop() { ZK_HIP(hipEventRecord(b, st)); }
